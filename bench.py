@@ -17,14 +17,24 @@ moves the RGBA8 rows to rank 0, which de-interleaves and reads the frame back --
 the timed region ("scaling": "strong" -- the total work is the same frame for every N).
 torch.distributed only distributes the communicator id and reduces the timings.
 
+A plain run sets up, warms up, times the K steps and prints the line: the headline figure, the
+configuration and the trace kernel's time per step (`roofline.kernel_ms`, from HIP events of the
+timed steps).  Everything else runs only with --full:
+
 `roofline` reports the ceiling that binds the dominant (trace) kernel -- VALU issue for the
 Cornell / own-tree / sphere kernels, L2 bandwidth for the reference walk -- from per-segment
 constants of a rocprofv3 PMC profile of THIS build (profiles/*_pmc.json, stamped with the
 source fingerprint; a profile of another build is refused), times the segment rate measured
-here.  SURVEY.md section 8(d)'s algorithmic-bytes figure and the measured HBM traffic are
-reported beside it (`roofline.algorithmic`, `roofline.hbm`).
+here.  SURVEY.md section 8(d)'s algorithmic-bytes figure (an instrumented pass before the timed
+steps) and the measured HBM traffic are reported beside it (`roofline.algorithmic`,
+`roofline.hbm`), with the L1 / L2 gather ceilings and the copy bandwidth measured on the device.
+`verify` checks the frame's CRC against the single-GPU table, `end_to_end` times one more render
+on a fresh engine piece by piece, `cpu_baseline` runs the CPU oracle on a sample of the workload.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c1|c2|c3|c4|c5|lamp]
+--dump-outputs DIR writes what the timed path returned in its last step (the RGBA8 frame, as
+float32) to DIR/*.npy; the inputs are seeded, so the files of two builds compare one to one.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c1|c2|c3|c4|c5|lamp] [--full] [--dump-outputs DIR]
 """
 import argparse
 import glob
@@ -70,7 +80,13 @@ def parse():
     ap.add_argument("--color-budget-mib", type=int, default=0, help="colour-buffer budget of the stream kernels (0 = library default)")
     ap.add_argument("--dump-frame", default="", help="rank 0 writes the last assembled RGBA8 frame to this .npy")
     ap.add_argument("--no-end-to-end", action="store_true", help="skip the end_to_end leg (one more full render on a fresh engine)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the instrumented pass, roofline, verify, end_to_end and cpu_baseline legs (a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes what the last timed step returned (the frame, float32) to DIR/<name>.npy")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.fast_bvh:
         a.walk = "own-host"
     if a.device_bvh:
@@ -247,6 +263,26 @@ def end_to_end(scene, wkw, kernel, device):
     return out, frame
 
 
+DUMP_FULL_PIXELS = 3 << 20      # up to 48 MiB of float32 RGBA: the whole frame (C1, C2, C3)
+DUMP_SAMPLE_PIXELS = 2 << 20    # larger frames (C4, C5, lamp): this many pixels, 32 MiB + 16 MiB of indices
+
+
+def dump_outputs(out_dir, frame):
+    """--dump-outputs: the frame the last timed step returned (RGBA8 [H, W, 4], as the caller receives it) as float32,
+    DIR/frame.npy.  A frame of more than DUMP_FULL_PIXELS pixels is written as a fixed, seeded sample of its pixels instead:
+    DIR/frame_sample.npy [k, 4] float32 and their row-major pixel indices DIR/frame_sample_index.npy [k] float64."""
+    import numpy as np
+    fr = np.ascontiguousarray(frame if isinstance(frame, np.ndarray) else frame.cpu().numpy())
+    os.makedirs(out_dir, exist_ok=True)
+    h, w = fr.shape[0], fr.shape[1]
+    if h * w <= DUMP_FULL_PIXELS:
+        np.save(os.path.join(out_dir, "frame.npy"), fr.astype(np.float32))
+        return
+    idx = np.sort(np.random.default_rng(0).choice(h * w, DUMP_SAMPLE_PIXELS, replace=False))
+    np.save(os.path.join(out_dir, "frame_sample.npy"), fr.reshape(h * w, -1)[idx].astype(np.float32))
+    np.save(os.path.join(out_dir, "frame_sample_index.npy"), idx.astype(np.float64))
+
+
 def load_pmc(key, kernel_name, fingerprint):
     """Per-segment constants of the dominant kernel from the rocprofv3 PMC profile of this build
     (tools/profile_bench.sh -> profiles/<tag>_<key>_pmc.json).  -> (dict | None, note)."""
@@ -307,9 +343,9 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # ---- instrumented pass (untimed): work counters for the algorithmic-bytes figure
+    # ---- instrumented pass (untimed, --full): work counters for the algorithmic-bytes figure
     stats = None
-    if not a.no_stats:
+    if a.full and not a.no_stats:
         r = ShardedRenderer(scene, rank, world, local_rank, a.stripe_rows, kernel=a.kernel, stats=True,
                             color_budget_mib=a.color_budget_mib, **wkw)
         r.engine.reset_stats()
@@ -338,17 +374,19 @@ def main():
     seg_per_step = st["segments"] // max(a.steps, 1)
     paths_per_step = st["paths"] // max(a.steps, 1)
 
-    # ---- what the exchange looked like from inside (rb_comm_info): the communicator as RCCL itself reports it, this
-    # rank's share of the last gather, this rank's trace-kernel time per step
-    ci = r.engine.comm_info() if r.library_gather else {"rccl_ranks": 0, "rccl_rank": 0, "gather_ms": 0.0}
-    mine = torch.tensor([float(ci["rccl_ranks"]), float(ci["rccl_rank"]), float(ci["gather_ms"]),
-                         st["trace_ms"] / max(a.steps, 1)], dtype=torch.float64, device=red_dev)
-    per_rank = [torch.zeros_like(mine) for _ in range(world)]
-    if world > 1:
-        dist.all_gather(per_rank, mine)
-    else:
-        per_rank = [mine]
-    per_rank = [[float(x) for x in t.tolist()] for t in per_rank]
+    # ---- what the exchange looked like from inside (rb_comm_info, --full): the communicator as RCCL itself reports it,
+    # this rank's share of the last gather, this rank's trace-kernel time per step
+    per_rank = None
+    if a.full:
+        ci = r.engine.comm_info() if r.library_gather else {"rccl_ranks": 0, "rccl_rank": 0, "gather_ms": 0.0}
+        mine = torch.tensor([float(ci["rccl_ranks"]), float(ci["rccl_rank"]), float(ci["gather_ms"]),
+                             st["trace_ms"] / max(a.steps, 1)], dtype=torch.float64, device=red_dev)
+        per_rank = [torch.zeros_like(mine) for _ in range(world)]
+        if world > 1:
+            dist.all_gather(per_rank, mine)
+        else:
+            per_rank = [mine]
+        per_rank = [[float(x) for x in t.tolist()] for t in per_rank]
 
     tt = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
     cnt = torch.tensor([float(seg_per_step), float(paths_per_step)], dtype=torch.float64, device=red_dev)
@@ -361,6 +399,8 @@ def main():
     if rank == 0 and a.dump_frame and frame is not None:
         import numpy as np
         np.save(a.dump_frame, frame if isinstance(frame, np.ndarray) else frame.cpu().numpy())
+    if rank == 0 and a.dump_outputs and frame is not None:
+        dump_outputs(a.dump_outputs, frame)
     if rank == 0:
         value = seg_total * a.steps / elapsed / 1e6
         # dominant kernel: the trace kernel.  A step is `launches` launches of it; duration per launch
@@ -368,94 +408,96 @@ def main():
         launches = max(int(st["launches"]) // max(a.steps, 1), 1)
         trace_ms_step = st["trace_ms"] / max(a.steps, 1)
         k_ms = trace_ms_step / launches
-        seg_rate = seg_per_step / (trace_ms_step * 1e-3) if trace_ms_step > 0 else 0.0   # this rank's segments/s inside the trace kernel
-        fingerprint = _lib.source_fingerprint()
-        key = a.workload + ("" if not a.walk else "_" + a.walk.replace("-", "")) + ("_skip" if a.skip_near_degenerate else "")
-        pmc, pmc_note = load_pmc(key, kernel_name, fingerprint)
-        roof = {"bound": None, "achieved": None, "peak": None, "unit": None, "frac": None, "traffic": None,
-                "kernel": kernel_name + "<false>", "kernel_ms": k_ms, "launches_per_step": launches,
-                "accumulate_ms_per_step": st["accumulate_ms"] / max(a.steps, 1), "source_fingerprint": fingerprint}
-        if pmc is not None:
-            c = pmc["per_segment"]
-            valu = {"achieved": c["valu_instr"] * seg_rate / 1e9, "peak": VALU_PEAK_GINSTR, "unit": "G wave-instr/s",
-                    "instr_per_segment": c["valu_instr"], "lane_utilisation": pmc["derived"].get("valu_lane_utilisation"),
-                    "wait_any_frac": pmc["derived"].get("wait_any_frac"), "clock_GHz": pmc["derived"].get("clock_GHz")}
-            valu["frac"] = valu["achieved"] / valu["peak"]
-            hbm = {"achieved": c["hbm_bytes"] * seg_rate / 1e9, "peak": HBM_PEAK_GBPS, "unit": "GB/s"}
-            hbm["frac"] = hbm["achieved"] / hbm["peak"]
-            l2 = None
-            if c.get("l2_bytes") is not None:
-                l2 = {"achieved": c["l2_bytes"] * seg_rate / 1e9, "peak": L2_PEAK_GBPS, "unit": "GB/s",
-                      "l1_accesses_per_segment": c.get("tcp_accesses")}
-                l2["frac"] = l2["achieved"] / l2["peak"]
-            # the L1 / texture-address path: the kernel's L1 access rate against the rate this box sustains on divergent
-            # 16-byte gathers that hit L1; and its L1 -> L2 request rate against the box's rate on gathers that miss L1
-            l1 = None
-            l1_peak = measured_l1_ceiling(local_rank)
-            l2_gather = measured_l1_ceiling(local_rank, 2 << 20)
-            if c.get("tcp_accesses") and l1_peak:
-                l1 = {"achieved": c["tcp_accesses"] * seg_rate / 1e9, "peak": l1_peak / 1e9, "unit": "G accesses/s",
-                      "accesses_per_segment": c["tcp_accesses"],
-                      "accesses_per_triangle_test": (c["tcp_accesses"] / (stats["tris_tested"] / max(stats["segments"], 1)))
-                      if (stats and stats.get("tris_tested")) else None}
-                l1["frac"] = l1["achieved"] / l1["peak"]
-            if l2 and l2_gather:   # 64-byte requests: against the measured gather rate, not the streaming figure
-                l2["streaming_peak"] = l2["peak"]
-                l2["peak"] = l2_gather * 64.0 / 1e9
-                l2["frac"] = l2["achieved"] / l2["peak"]
-            # the binding ceiling = the largest of the fractions
-            cands = [("valu", valu)] + ([("l1", l1)] if l1 else []) + ([("l2", l2)] if l2 else []) + [("hbm", hbm)]
-            bound, top = max(cands, key=lambda kv: kv[1]["frac"])
-            roof.update({"bound": bound, "achieved": top["achieved"], "peak": top["peak"], "unit": top["unit"],
-                         "frac": top["frac"], "traffic": c["hbm_bytes"] * seg_per_step / launches,
-                         "valu": valu, "l1": l1, "hbm": hbm, "l2": l2, "pmc_profile": pmc["_path"]})
-        else:
-            roof["note"] = pmc_note
-        if stats is not None and k_ms > 0:
-            owned = r.owned
-            algo_step = abi.algorithmic_bytes(stats, owned * scene.width * launches, resumed=False)
-            algo = algo_step / launches
-            roof["algorithmic"] = {"bytes_per_launch": algo, "bytes_per_segment": algo_step / max(stats["segments"], 1),
-                                   "GBps": algo / (k_ms * 1e-3) / 1e9,
-                                   "note": "SURVEY.md 8(d) logical bytes / launch time; served from the scalar cache / L1 / L2, "
-                                           "so it is not a fraction of any one ceiling"}
-            roof["work_per_segment"] = {k: stats[k] / max(stats["segments"], 1)
-                                        for k in ("nodes_popped", "tris_tested", "spheres_tested", "lights_tested", "mesh_hits")}
-        try:
-            roof["measured_copy_peak"] = measured_copy_bandwidth(f"cuda:{local_rank}")  # GB/s, read + write
-        except Exception:
-            pass
-        # ---- the frame itself: a checksum every N must reproduce (the sharded frame is the single-GPU frame by construction)
-        import zlib
-        import numpy as np
-        fr = None if frame is None else (frame if isinstance(frame, np.ndarray) else frame.cpu().numpy())
-        crc = None if fr is None else (zlib.crc32(np.ascontiguousarray(fr).tobytes()) & 0xFFFFFFFF)
-        expect = None
-        try:
-            table = json.load(open(os.path.join(ROOT, "profiles", "frame_crc32.json")))
-            expect = table.get(f"{a.workload}:{scene.width}x{scene.height}:{spp}spp:depth{int(scene.uniforms['max_depth'][0])}")
-        except Exception:
-            pass
-        verify = {"frame_crc32": crc, "frame_crc32_single_gpu": expect,
-                  "frame_matches_single_gpu": (None if (crc is None or expect is None) else bool(crc == expect))}
-        if world > 1:
-            verify.update({"rccl_ranks_reported": [int(x[0]) for x in per_rank], "rccl_rank_reported": [int(x[1]) for x in per_rank],
-                           "gather_ms_by_rank": [x[2] for x in per_rank], "trace_ms_per_step_by_rank": [x[3] for x in per_rank],
-                           "trace_ms_per_step_min": min(x[3] for x in per_rank), "trace_ms_per_step_max": max(x[3] for x in per_rank),
-                           "exchange": r.gather_note})
-        e2e = None
-        if world == 1 and not a.no_end_to_end:
-            e2e, e2e_frame = end_to_end(scene, wkw, a.kernel, local_rank)
-            e2e["frame_equals_timed_frame"] = bool(fr is not None and np.array_equal(e2e_frame, fr))
-        # (the CPU leg last: the end_to_end leg above should find the device as the timed steps left it, not after 15 s of idling)
-        cpu = None
-        if a.cpu_seconds > 0 and world == 1:
-            cpu = cpu_baseline(scene, a.cpu_seconds)
+        roof = {"kernel": kernel_name + "<false>", "kernel_ms": k_ms, "launches_per_step": launches,
+                "accumulate_ms_per_step": st["accumulate_ms"] / max(a.steps, 1)}
+        cpu = e2e = verify = None
+        if a.full:
+            seg_rate = seg_per_step / (trace_ms_step * 1e-3) if trace_ms_step > 0 else 0.0   # this rank's segments/s inside the trace kernel
+            fingerprint = _lib.source_fingerprint()
+            key = a.workload + ("" if not a.walk else "_" + a.walk.replace("-", "")) + ("_skip" if a.skip_near_degenerate else "")
+            pmc, pmc_note = load_pmc(key, kernel_name, fingerprint)
+            roof = {"bound": None, "achieved": None, "peak": None, "unit": None, "frac": None, "traffic": None,
+                    "kernel": kernel_name + "<false>", "kernel_ms": k_ms, "launches_per_step": launches,
+                    "accumulate_ms_per_step": st["accumulate_ms"] / max(a.steps, 1), "source_fingerprint": fingerprint}
+            if pmc is not None:
+                c = pmc["per_segment"]
+                valu = {"achieved": c["valu_instr"] * seg_rate / 1e9, "peak": VALU_PEAK_GINSTR, "unit": "G wave-instr/s",
+                        "instr_per_segment": c["valu_instr"], "lane_utilisation": pmc["derived"].get("valu_lane_utilisation"),
+                        "wait_any_frac": pmc["derived"].get("wait_any_frac"), "clock_GHz": pmc["derived"].get("clock_GHz")}
+                valu["frac"] = valu["achieved"] / valu["peak"]
+                hbm = {"achieved": c["hbm_bytes"] * seg_rate / 1e9, "peak": HBM_PEAK_GBPS, "unit": "GB/s"}
+                hbm["frac"] = hbm["achieved"] / hbm["peak"]
+                l2 = None
+                if c.get("l2_bytes") is not None:
+                    l2 = {"achieved": c["l2_bytes"] * seg_rate / 1e9, "peak": L2_PEAK_GBPS, "unit": "GB/s",
+                          "l1_accesses_per_segment": c.get("tcp_accesses")}
+                    l2["frac"] = l2["achieved"] / l2["peak"]
+                # the L1 / texture-address path: the kernel's L1 access rate against the rate this device sustains on divergent
+                # 16-byte gathers that hit L1; and its L1 -> L2 request rate against the device's rate on gathers that miss L1
+                l1 = None
+                l1_peak = measured_l1_ceiling(local_rank)
+                l2_gather = measured_l1_ceiling(local_rank, 2 << 20)
+                if c.get("tcp_accesses") and l1_peak:
+                    l1 = {"achieved": c["tcp_accesses"] * seg_rate / 1e9, "peak": l1_peak / 1e9, "unit": "G accesses/s",
+                          "accesses_per_segment": c["tcp_accesses"],
+                          "accesses_per_triangle_test": (c["tcp_accesses"] / (stats["tris_tested"] / max(stats["segments"], 1)))
+                          if (stats and stats.get("tris_tested")) else None}
+                    l1["frac"] = l1["achieved"] / l1["peak"]
+                if l2 and l2_gather:   # 64-byte requests: against the measured gather rate, not the streaming figure
+                    l2["streaming_peak"] = l2["peak"]
+                    l2["peak"] = l2_gather * 64.0 / 1e9
+                    l2["frac"] = l2["achieved"] / l2["peak"]
+                # the binding ceiling = the largest of the fractions
+                cands = [("valu", valu)] + ([("l1", l1)] if l1 else []) + ([("l2", l2)] if l2 else []) + [("hbm", hbm)]
+                bound, top = max(cands, key=lambda kv: kv[1]["frac"])
+                roof.update({"bound": bound, "achieved": top["achieved"], "peak": top["peak"], "unit": top["unit"],
+                             "frac": top["frac"], "traffic": c["hbm_bytes"] * seg_per_step / launches,
+                             "valu": valu, "l1": l1, "hbm": hbm, "l2": l2, "pmc_profile": pmc["_path"]})
+            else:
+                roof["note"] = pmc_note
+            if stats is not None and k_ms > 0:
+                owned = r.owned
+                algo_step = abi.algorithmic_bytes(stats, owned * scene.width * launches, resumed=False)
+                algo = algo_step / launches
+                roof["algorithmic"] = {"bytes_per_launch": algo, "bytes_per_segment": algo_step / max(stats["segments"], 1),
+                                       "GBps": algo / (k_ms * 1e-3) / 1e9,
+                                       "note": "SURVEY.md 8(d) logical bytes / launch time; served from the scalar cache / L1 / L2, "
+                                               "so it is not a fraction of any one ceiling"}
+                roof["work_per_segment"] = {k: stats[k] / max(stats["segments"], 1)
+                                            for k in ("nodes_popped", "tris_tested", "spheres_tested", "lights_tested", "mesh_hits")}
+            try:
+                roof["measured_copy_peak"] = measured_copy_bandwidth(f"cuda:{local_rank}")  # GB/s, read + write
+            except Exception:
+                pass
+            # ---- the frame itself: a checksum every N must reproduce (the sharded frame is the single-GPU frame by construction)
+            import zlib
+            import numpy as np
+            fr = None if frame is None else (frame if isinstance(frame, np.ndarray) else frame.cpu().numpy())
+            crc = None if fr is None else (zlib.crc32(np.ascontiguousarray(fr).tobytes()) & 0xFFFFFFFF)
+            expect = None
+            try:
+                table = json.load(open(os.path.join(ROOT, "profiles", "frame_crc32.json")))
+                expect = table.get(f"{a.workload}:{scene.width}x{scene.height}:{spp}spp:depth{int(scene.uniforms['max_depth'][0])}")
+            except Exception:
+                pass
+            verify = {"frame_crc32": crc, "frame_crc32_single_gpu": expect,
+                      "frame_matches_single_gpu": (None if (crc is None or expect is None) else bool(crc == expect))}
+            if world > 1:
+                verify.update({"rccl_ranks_reported": [int(x[0]) for x in per_rank], "rccl_rank_reported": [int(x[1]) for x in per_rank],
+                               "gather_ms_by_rank": [x[2] for x in per_rank], "trace_ms_per_step_by_rank": [x[3] for x in per_rank],
+                               "trace_ms_per_step_min": min(x[3] for x in per_rank), "trace_ms_per_step_max": max(x[3] for x in per_rank),
+                               "exchange": r.gather_note})
+            if world == 1 and not a.no_end_to_end:
+                e2e, e2e_frame = end_to_end(scene, wkw, a.kernel, local_rank)
+                e2e["frame_equals_timed_frame"] = bool(fr is not None and np.array_equal(e2e_frame, fr))
+            # (the CPU leg last: the end_to_end leg above should find the device as the timed steps left it, not after 15 s of idling)
+            if a.cpu_seconds > 0 and world == 1:
+                cpu = cpu_baseline(scene, a.cpu_seconds)
         out = {
             "metric": "Msamples/s (ray-segments/s)", "value": value, "unit": "Msamples/s",
             "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": elapsed / a.steps * 1e3,
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
-            "data": "synthetic",
+            "data": "synthetic", "full": a.full,
             "config": {"workload": desc, "width": scene.width, "height": scene.height, "spp": spp,
                        "max_depth": int(scene.uniforms["max_depth"][0]), "segments_per_step": int(seg_total),
                        "paths_per_step": int(paths_total), "Mpaths_per_s": paths_total * a.steps / elapsed / 1e6,

@@ -28,7 +28,7 @@ def _run(args, nproc, tmp_path):
 
 
 def test_two_ranks_reproduce_the_single_rank_frame(tmp_path):
-    common = ["--workload", "c1", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0"]
+    common = ["--workload", "c1", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--full"]
     one = _run(common + ["--gpus", "1", "--dump-frame", str(tmp_path / "one.npy")], 1, tmp_path)
     two = _run(common + ["--gpus", "2", "--backend", "gloo", "--same-device", "--dump-frame", str(tmp_path / "two.npy")],
                2, tmp_path)
@@ -59,7 +59,8 @@ def test_two_ranks_reproduce_the_single_rank_frame(tmp_path):
 def test_the_eight_gpu_configurations_shard_too(workload, tmp_path):
     # BASELINE configs 4 and 5 are the ones quoted on 8 GPUs: one sample per pixel of their real frames, two ranks on one
     # device, against the single-rank frame
-    common = ["--workload", workload, "--spp", "1", "--steps", "1", "--warmup", "0", "--cpu-seconds", "0", "--no-stats", "--no-end-to-end"]
+    common = ["--workload", workload, "--spp", "1", "--steps", "1", "--warmup", "0", "--cpu-seconds", "0", "--no-stats", "--no-end-to-end",
+              "--full"]
     one = _run(common + ["--gpus", "1"], 1, tmp_path)
     two = _run(common + ["--gpus", "2", "--backend", "gloo", "--same-device"], 2, tmp_path)
     assert one["verify"]["frame_crc32"] == two["verify"]["frame_crc32"] is not None

@@ -318,16 +318,18 @@ def test_loaded_scene_file_renders_bit_exact_on_gpu(tmp_path):
     assert np.array_equal(np.asarray(Image.open(p)).reshape(-1), np.asarray(f.pixels).reshape(-1))
 
 
-def test_reference_lamp_scene_fixture_matches_the_rscn_file():
-    # the committed DATA fixture is what the loader makes of the reference's .rscn (dev container only)
-    src = "/root/reference/included/fixtures/scenes/final_cornell_with_lamp_and_spheres.rscn"
+REF_FIXTURES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_fixtures")
+
+
+def test_reference_lamp_scene_fixture_matches_the_rscn_file(tmp_path):
+    # the committed DATA fixture is what the loader makes of the reference's .rscn (a copy of the archive with the same
+    # entries, deflated instead of stored: tests/golden/ref_fixtures/)
+    src = os.path.join(REF_FIXTURES, "final_cornell_with_lamp_and_spheres.rscn")
     a = _refscenes.ref_lamp()
     u = a.uniforms[0]
     assert (len(a.bvh_triangles), len(a.spheres), u["width"], u["height"], u["total_samples"]) == (68768, 4, 2056, 2056, 512)
     assert u["color_hash_enabled"] == 0 and len(a.bvh_nodes) == 2047
-    if not os.path.isfile(src):
-        pytest.skip("reference checkout not present")
-    b = scene_io.load_scene(src)
+    b = scene_io.load_scene(src, extract_dir=str(tmp_path / "rscn"))
     for k in ("uniforms", "spheres", "lights", "meshes", "bvh_triangles", "bvh_nodes", "bvh_indices", "uvs"):
         assert np.array_equal(getattr(a, k), getattr(b, k)), k
 
@@ -447,13 +449,20 @@ def test_deep_device_tree_with_the_other_dispatch_shapes(kernel, builder):
     assert np.array_equal(acc.view(np.uint32), o_acc.view(np.uint32)) and np.array_equal(f.pixels, o_rgba)
 
 
-def test_reference_benchmark_scene_file_loads():
+def test_reference_benchmark_scene_file_loads(tmp_path):
     # the scene file the reference's own benchmark mode renders (control_plane/modes/benchmark.rs):
-    # 16 624 textured triangles and a point light, 512 x 512.  Dev container only -- the file is not copied.
-    root = "/root/reference/included"
+    # 16 624 textured triangles and a point light, 512 x 512.  Its files are in tests/golden/ref_fixtures/benchmark/
+    # (the OBJ gzipped, the albedo texture re-encoded with the same pixels); laid out here as the reference ships them.
+    import gzip
+    import shutil
+    src = os.path.join(REF_FIXTURES, "benchmark")
+    root = str(tmp_path / "included")
+    shutil.copytree(src, os.path.join(root, "fixtures"))
+    mesh = os.path.join(root, "fixtures", "ferris_high_poly", "ferris3d_v1.0.obj")
+    with gzip.open(mesh + ".gz", "rb") as f, open(mesh, "wb") as g:
+        shutil.copyfileobj(f, g)
+    os.remove(mesh + ".gz")
     path = os.path.join(root, "fixtures", "benchmark.json")
-    if not os.path.isfile(path):
-        pytest.skip("reference checkout not present")
     s = scene_io.load_scene(path, included_root=root)
     u = s.uniforms[0]
     assert (len(s.bvh_triangles), len(s.meshes), len(s.lights), len(s.spheres)) == (16624, 1, 1, 0)

@@ -82,8 +82,8 @@ derived = {
     "kernel_ms_bench_hip_events": e["roofline"]["kernel_ms"],
     "Msamples_per_s_unprofiled": e["value"],
 }
-d = {"command": f"tools/profile_bench.sh {tag} {key} {args}: rocprofv3 --pmc <group> -- python3 bench.py {args} --steps 1 --warmup 1 "
-                "--cpu-seconds 0 --no-stats (four counter passes), rocprofv3 --kernel-trace --stats -- python3 bench.py ... --steps 3",
+d = {"command": f"tools/profile_bench.sh {tag} {key} {args}: rocprofv3 --pmc <group> -- python3 bench.py {args} --full --steps 1 --warmup 1 "
+                "--cpu-seconds 0 --no-stats (four counter passes), rocprofv3 --kernel-trace --stats -- python3 bench.py ... --full --steps 3",
      "workload": b["config"]["workload"], "kernel": kernel, "source_fingerprint": _lib.source_fingerprint(),
      "git_head": os.popen("git -C %s rev-parse --short HEAD 2>/dev/null" % os.path.dirname(os.path.abspath(__file__))).read().strip() or None,
      "segments_in_a_pmc_pass": seg_run, "counters_dominant_kernel": {k: v for k, v in cnt.items()},
