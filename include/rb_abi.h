@@ -263,6 +263,14 @@ enum {
     RB_FLAG_CHUNK_TREE_DEVICE = 16384u, /* ... or on the device (one thread block per reference leaf) whatever the mesh's size; by default the
                                            device builds it from 16 384 triangle slots up.  A caller's tree with leaves of more than 256
                                            triangles is built on the host either way.  The frame does not depend on the builder. */
+    RB_FLAG_BUILD_TREE = 32768u,      /* the engine builds the reference-layout tree itself from bvh_triangles -- the canonical tree of
+                                         rb_bvh_build_canonical, on the device (rb_bvh_build_device) -- so that the caller sends
+                                         triangles only.  bvh_nodes and bvh_indices must then be RB_KEEP in every config (else
+                                         RB_ERR_INVALID_BVH); the tree follows the triangles field: Create / Update rebuild it, Delete
+                                         empties it, Keep keeps it.  Non-finite vertices are RB_ERR_INVALID_BVH.  Every walk works
+                                         unchanged; rb_engine_tree reads the tree back, rb_tree_builder names its builder */
+    RB_FLAG_BUILD_TREE_HOST = 65536u, /* the same, built on the host (rb_bvh_build_canonical: the same bytes).  Both flags together
+                                         are RB_ERR_INVALID_OPTIONS */
     RB_FLAG_SKIP_NEAR_DEGENERATE = 512u /* with the library's tree: skip its second pass.  The walk then answers only for
                                            hits whose ray is more than ~1.7 degrees off the plane of a LARGE triangle
                                            (L^2 > 1.6e-2); a hit the reference reports from a near-zero determinant there can be
@@ -438,6 +446,30 @@ int rb_last_dispatch_ms(rb_engine* e, float* ms);
 int rb_bvh_build(const rb_gpu_triangle* tris, size_t n_tris,
                  rb_bvh_node* nodes_out, size_t nodes_capacity, size_t* n_nodes,
                  uint32_t* indices_out);
+
+/* The canonical reference-layout tree: rb_bvh_build's topology, numbering and node count (they follow from n_tris alone) with
+ * every choice BVH::new leaves open fixed -- centroids ((v0 + v1) + v2) / 3 in f32, ordered by (centroid along the axis, triangle
+ * index) with -0 == +0, the left child the first count / 2 of its node in that order, leaves listed in ascending index, boxes
+ * the min / max of the vertices under the total order in which -0 < +0.  Where no centroid tie
+ * straddles a median it is rb_bvh_build's tree with every leaf sorted.  A non-finite vertex coordinate is RB_ERR_INVALID_BVH
+ * (rb_last_error(NULL) names the triangle).  Same two-call protocol as rb_bvh_build, but the size query (nodes_out == NULL)
+ * answers from n_tris alone, without building (tris may be NULL there); built on the host's threads. */
+int rb_bvh_build_canonical(const rb_gpu_triangle* tris, size_t n_tris,
+                           rb_bvh_node* nodes_out, size_t nodes_capacity, size_t* n_nodes,
+                           uint32_t* indices_out);
+/* The same bytes built on `device` (-1 = current): host arrays in and out, the build itself on the GPU (presorted id lists per
+ * axis, one stable partition per depth).  The size query (nodes_out == NULL) touches no device and may pass tris == NULL. */
+int rb_bvh_build_device(int32_t device, const rb_gpu_triangle* tris, size_t n_tris,
+                        rb_bvh_node* nodes_out, size_t nodes_capacity, size_t* n_nodes,
+                        uint32_t* indices_out);
+/* Two-call read-back of the reference-layout tree the engine walks -- the caller's, or its own under RB_FLAG_BUILD_TREE:
+ * pass nodes_out == NULL and indices_out == NULL to query n_nodes / n_indices.  Either array may be NULL to skip it. */
+int rb_engine_tree(rb_engine* e, rb_bvh_node* nodes_out, size_t nodes_capacity, size_t* n_nodes,
+                   uint32_t* indices_out, size_t indices_capacity, size_t* n_indices);
+/* Which builder produced the tree the engine walks: "device", "host" (RB_FLAG_BUILD_TREE / _HOST), "caller" (sent in the
+ * config), or "" when there is none.  `build_ms`, if not NULL, receives the wall time of the engine's own build with its
+ * read-back of the nodes (0 for the caller's tree). */
+const char* rb_tree_builder(const rb_engine* e, float* build_ms);
 
 /* Test aid (host only, no device): builds the chunked walk's tree for this mesh and this caller tree and checks the
  * structural invariants the kernel relies on (every valid slot in exactly one chunk, ranks consistent, references in range,

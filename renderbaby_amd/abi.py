@@ -75,6 +75,8 @@ FLAG_SPHERE_TREE_HOST = 2048
 FLAG_SPHERE_TREE_DEVICE = 4096
 FLAG_CHUNK_TREE_HOST = 8192
 FLAG_CHUNK_TREE_DEVICE = 16384
+FLAG_BUILD_TREE = 32768        # the engine builds the reference-layout tree from the triangles (on the device)
+FLAG_BUILD_TREE_HOST = 65536   # ... on the host
 COMM_ID_BYTES = 128
 
 

@@ -20,7 +20,9 @@
 // milliseconds.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstring>
+#include <vector>
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -1180,6 +1182,293 @@ int device_fast_bvh_build(const rb_gpu_triangle* tris, const uint32_t* indices, 
     if (e != hipSuccess) return done(e);
     e = hipStreamSynchronize(stream);
     if (e == hipSuccess) e = hipMemcpy(info_out, d_info, sizeof(DeviceTreeInfo), hipMemcpyDeviceToHost);
+    return done(e);
+}
+
+
+// ---- The canonical reference-layout tree (rb_bvh.cpp bvh_build_canonical is the checker).  Its topology
+// follows from n alone (bvh_skeleton, on the host: the nodes of each depth with their ranges), so what is left is which
+// triangles land in each range.  Three lists of the triangle ids sorted once by (centroid along the axis, id) -- stable radix
+// sorts of order-preserving u32 keys over iota -- and a fourth in id order; per depth:
+//   k_rt_segmap   position -> segment of this depth (binary search over the depth's first triangles), or none
+//   k_rt_bounds   node boxes: min / max of the per-triangle bounds as order-preserving u32 atomics (exact, order-free,
+//                 -0 < +0), a wavefront inside one segment reducing first
+//   k_rt_flags    per splitting segment: its axis from the box; the first count / 2 positions of that axis's list go left
+//   k_rt_pack     the left flag of the element at every position of the four lists, two lists per u64 (no carry: n < 2^32)
+//   two exclusive scans, then k_rt_scatter: a stable partition of every list inside every splitting segment
+// Every list keeps its order inside each half, so the lists stay sorted by (centroid, id) per segment and the id list in id
+// order: the leaves' contents are its ranges.  No host synchronisation between the first launch and the last.
+namespace {
+constexpr uint32_t kRtNone = 0xFFFFFFFFu;
+constexpr uint32_t kRtBlock = 256u;
+constexpr uint32_t kRtMaxBlocks = 2048u;
+
+__device__ __forceinline__ uint32_t f2ord_canon(float f) { return f2ord(f == 0.0f ? 0.0f : f); }   // -0 == +0 as a key
+
+__global__ void __launch_bounds__(kRtBlock) k_rt_prep(const rb_gpu_triangle* __restrict__ tris, uint32_t n,
+                                                       uint32_t* __restrict__ kx, uint32_t* __restrict__ ky, uint32_t* __restrict__ kz,
+                                                       uint32_t* __restrict__ ids, uint4* __restrict__ tbmin, uint4* __restrict__ tbmax) {
+    for (uint32_t i = blockIdx.x * kRtBlock + threadIdx.x; i < n; i += gridDim.x * kRtBlock) {
+        const rb_gpu_triangle t = tris[i];
+        uint32_t mn[3], mx[3], key[3];
+        for (int a = 0; a < 3; ++a) {
+            key[a] = f2ord_canon(((t.v0[a] + t.v1[a]) + t.v2[a]) / 3.0f);   // Builder::centroid, bvh.rs:152-154
+            const uint32_t o0 = f2ord(t.v0[a]), o1 = f2ord(t.v1[a]), o2 = f2ord(t.v2[a]);
+            mn[a] = min(o0, min(o1, o2));
+            mx[a] = max(o0, max(o1, o2));
+        }
+        kx[i] = key[0];
+        ky[i] = key[1];
+        kz[i] = key[2];
+        ids[i] = i;
+        tbmin[i] = make_uint4(mn[0], mn[1], mn[2], 0u);
+        tbmax[i] = make_uint4(mx[0], mx[1], mx[2], 0u);
+    }
+}
+
+// segs: {first, count, node, leaf} of one depth, in order of `first`
+__global__ void __launch_bounds__(kRtBlock) k_rt_segmap(const uint4* __restrict__ segs, uint32_t n_segs, uint32_t n,
+                                                         uint32_t* __restrict__ segmap) {
+    for (uint32_t p = blockIdx.x * kRtBlock + threadIdx.x; p < n; p += gridDim.x * kRtBlock) {
+        uint32_t lo = 0, hi = n_segs;   // the last segment with first <= p, if any
+        while (hi - lo > 1u) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (segs[mid].x <= p) lo = mid;
+            else hi = mid;
+        }
+        const uint4 s = segs[lo];
+        segmap[p] = (s.x <= p && p - s.x < s.y) ? lo : kRtNone;
+    }
+}
+
+// box[node] = {min xyz, -, max xyz, -} as order-preserving u32 (min starts at all ones, max at zero).  Every block takes one
+// contiguous range of positions; a wavefront reduces each step and carries the result while its segment stays the same, so
+// a segment costs one set of atomics per wavefront that meets it -- and the top depths' few large segments one per block
+// (the waves' last carries are combined in LDS): the first version's atomics per wavefront and step made the top depths
+// contend on one address (C5: 3.3 of 5.1 ms).
+__device__ __forceinline__ void rt_box_atomics(uint32_t* __restrict__ box, uint32_t node, const uint32_t mn[3], const uint32_t mx[3]) {
+    uint32_t* b = box + 8u * node;
+    for (int a = 0; a < 3; ++a) {
+        atomicMin(&b[a], mn[a]);
+        atomicMax(&b[4 + a], mx[a]);
+    }
+}
+
+__global__ void __launch_bounds__(kRtBlock) k_rt_bounds(const uint4* __restrict__ segs, const uint32_t* __restrict__ segmap, uint32_t n,
+                                                         const uint32_t* __restrict__ ids, const uint4* __restrict__ tbmin,
+                                                         const uint4* __restrict__ tbmax, uint32_t* __restrict__ box) {
+    __shared__ uint32_t carry[kRtBlock / 64u][7];
+    const uint32_t per = (((n + gridDim.x - 1u) / gridDim.x) + kRtBlock - 1u) & ~(kRtBlock - 1u);
+    const uint32_t begin = min(n, blockIdx.x * per), end = min(n, begin + per);
+    uint32_t cs = kRtNone, cmn[3] = {kRtNone, kRtNone, kRtNone}, cmx[3] = {0u, 0u, 0u};   // the wavefront's carry (uniform)
+    for (uint32_t base = begin; base < end; base += kRtBlock) {   // wave-uniform loop
+        const uint32_t p = base + threadIdx.x;
+        uint32_t s = kRtNone, mn[3] = {kRtNone, kRtNone, kRtNone}, mx[3] = {0u, 0u, 0u};
+        if (p < end) {
+            s = segmap[p];
+            if (s != kRtNone) {
+                const uint32_t id = ids[p];
+                const uint4 a = tbmin[id], b = tbmax[id];
+                mn[0] = a.x; mn[1] = a.y; mn[2] = a.z;
+                mx[0] = b.x; mx[1] = b.y; mx[2] = b.z;
+            }
+        }
+        const uint32_t s0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)s);
+        if (__ballot(s != s0) == 0ull) {   // the whole wavefront in one segment (or in none)
+            if (s0 == kRtNone) continue;
+            for (int a = 0; a < 3; ++a)
+                for (int off = 32; off > 0; off >>= 1) {
+                    mn[a] = min(mn[a], (uint32_t)__shfl_xor((int)mn[a], off, 64));
+                    mx[a] = max(mx[a], (uint32_t)__shfl_xor((int)mx[a], off, 64));
+                }
+            if (s0 != cs) {
+                if (cs != kRtNone && (threadIdx.x & 63u) == 0u) rt_box_atomics(box, segs[cs].z, cmn, cmx);
+                cs = s0;
+                for (int a = 0; a < 3; ++a) { cmn[a] = mn[a]; cmx[a] = mx[a]; }
+            } else {
+                for (int a = 0; a < 3; ++a) { cmn[a] = min(cmn[a], mn[a]); cmx[a] = max(cmx[a], mx[a]); }
+            }
+        } else if (s != kRtNone) {
+            rt_box_atomics(box, segs[s].z, mn, mx);
+        }
+    }
+    const uint32_t w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63u) == 0u) {
+        carry[w][0] = cs;
+        for (int a = 0; a < 3; ++a) { carry[w][1 + a] = cmn[a]; carry[w][4 + a] = cmx[a]; }
+    }
+    __syncthreads();
+    if (threadIdx.x != 0u) return;
+    for (uint32_t i = 0; i < kRtBlock / 64u; ++i) {   // one set of atomics per distinct carried segment
+        const uint32_t si = carry[i][0];
+        if (si == kRtNone) continue;
+        uint32_t mn[3] = {carry[i][1], carry[i][2], carry[i][3]}, mx[3] = {carry[i][4], carry[i][5], carry[i][6]};
+        for (uint32_t j = i + 1u; j < kRtBlock / 64u; ++j)
+            if (carry[j][0] == si) {
+                for (int a = 0; a < 3; ++a) { mn[a] = min(mn[a], carry[j][1 + a]); mx[a] = max(mx[a], carry[j][4 + a]); }
+                carry[j][0] = kRtNone;
+            }
+        rt_box_atomics(box, segs[si].z, mn, mx);
+    }
+}
+
+__device__ __forceinline__ uint32_t rt_axis(const uint32_t* b) {   // bvh.rs:125-135 on the node box's f32 extents
+    const float ex = ord2f(b[4]) - ord2f(b[0]), ey = ord2f(b[5]) - ord2f(b[1]), ez = ord2f(b[6]) - ord2f(b[2]);
+    return (ex > ey && ex > ez) ? 0u : ((ey > ez) ? 1u : 2u);
+}
+
+// the left flag per triangle id, from the position in the splitting axis's list
+__global__ void __launch_bounds__(kRtBlock) k_rt_flags(const uint4* __restrict__ segs, const uint32_t* __restrict__ segmap, uint32_t n,
+                                                        const uint32_t* __restrict__ lx, const uint32_t* __restrict__ ly,
+                                                        const uint32_t* __restrict__ lz, const uint32_t* __restrict__ box,
+                                                        uint8_t* __restrict__ left) {
+    for (uint32_t p = blockIdx.x * kRtBlock + threadIdx.x; p < n; p += gridDim.x * kRtBlock) {
+        const uint32_t si = segmap[p];
+        if (si == kRtNone) continue;
+        const uint4 s = segs[si];
+        if (s.w) continue;   // a leaf: not split
+        const uint32_t axis = rt_axis(box + 8u * s.z);
+        const uint32_t id = axis == 0u ? lx[p] : (axis == 1u ? ly[p] : lz[p]);
+        left[id] = (p - s.x < s.y / 2u) ? 1u : 0u;
+    }
+}
+
+__global__ void __launch_bounds__(kRtBlock) k_rt_pack(const uint4* __restrict__ segs, const uint32_t* __restrict__ segmap, uint32_t n,
+                                                       const uint32_t* __restrict__ lists, const uint8_t* __restrict__ left,
+                                                       unsigned long long* __restrict__ f01, unsigned long long* __restrict__ f23) {
+    for (uint32_t p = blockIdx.x * kRtBlock + threadIdx.x; p < n; p += gridDim.x * kRtBlock) {
+        const uint32_t si = segmap[p];
+        unsigned long long a = 0ull, b = 0ull;
+        if (si != kRtNone && !segs[si].w) {
+            a = (unsigned long long)left[lists[p]] | ((unsigned long long)left[lists[(size_t)n + p]] << 32);
+            b = (unsigned long long)left[lists[2u * (size_t)n + p]] | ((unsigned long long)left[lists[3u * (size_t)n + p]] << 32);
+        }
+        f01[p] = a;
+        f23[p] = b;
+    }
+}
+
+// stable partition inside every splitting segment: the k-th left element of a segment goes to first + k, the k-th right one
+// to first + count / 2 + k; every other position keeps its element
+__global__ void __launch_bounds__(kRtBlock) k_rt_scatter(const uint4* __restrict__ segs, const uint32_t* __restrict__ segmap, uint32_t n,
+                                                          const uint32_t* __restrict__ lists, uint32_t* __restrict__ out,
+                                                          const unsigned long long* __restrict__ f01, const unsigned long long* __restrict__ f23,
+                                                          const unsigned long long* __restrict__ s01, const unsigned long long* __restrict__ s23) {
+    for (uint32_t p = blockIdx.x * kRtBlock + threadIdx.x; p < n; p += gridDim.x * kRtBlock) {
+        const uint32_t si = segmap[p];
+        const uint4 s = si != kRtNone ? segs[si] : make_uint4(0u, 0u, 0u, 1u);
+        if (s.w) {
+            for (uint32_t k = 0; k < 4u; ++k) out[k * (size_t)n + p] = lists[k * (size_t)n + p];
+            continue;
+        }
+        const unsigned long long b01 = s01[p] - s01[s.x], b23 = s23[p] - s23[s.x];   // left elements before p in the segment
+        const unsigned long long own01 = f01[p], own23 = f23[p];
+        const uint32_t before[4] = {(uint32_t)b01, (uint32_t)(b01 >> 32), (uint32_t)b23, (uint32_t)(b23 >> 32)};
+        const uint32_t own[4] = {(uint32_t)own01, (uint32_t)(own01 >> 32), (uint32_t)own23, (uint32_t)(own23 >> 32)};
+        const uint32_t rel = p - s.x, half = s.y / 2u;
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; ++k) {
+            const uint32_t dst = own[k] ? s.x + before[k] : s.x + half + (rel - before[k]);
+            if (dst - s.x < s.y) out[k * (size_t)n + dst] = lists[k * (size_t)n + p];   // always (the flags agree on every list)
+        }
+    }
+}
+
+// the skeleton's nodes (already in d_nodes) get their boxes
+__global__ void __launch_bounds__(kRtBlock) k_rt_emit(uint32_t n_nodes, const uint32_t* __restrict__ box, rb_bvh_node* __restrict__ nodes) {
+    const uint32_t i = blockIdx.x * kRtBlock + threadIdx.x;
+    if (i >= n_nodes) return;
+    const uint32_t* b = box + 8u * i;
+    rb_bvh_node& o = nodes[i];
+    for (int a = 0; a < 3; ++a) {
+        o.aabb_min[a] = ord2f(b[a]);
+        o.aabb_max[a] = ord2f(b[4 + a]);
+    }
+}
+
+__global__ void __launch_bounds__(kRtBlock) k_rt_box_init(uint32_t n_nodes, uint32_t* __restrict__ box) {
+    const uint32_t i = blockIdx.x * kRtBlock + threadIdx.x;
+    if (i >= 8u * n_nodes) return;
+    box[i] = (i & 4u) ? 0u : kRtNone;
+}
+
+inline dim3 rt_grid(size_t work) { return dim3((uint32_t)std::min<size_t>((work + kRtBlock - 1u) / kRtBlock, kRtMaxBlocks)); }
+}  // namespace
+
+int device_reference_bvh_build(const rb_gpu_triangle* d_tris, uint32_t n, rb_bvh_node* d_nodes, uint32_t* d_indices, void* stream_) {
+    if (n == 0u || n >= (1u << 31)) return static_cast<int>(hipErrorInvalidValue);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    TreeSkeleton sk;
+    bvh_skeleton(n, sk);
+    const uint32_t n_nodes = static_cast<uint32_t>(sk.nodes.size()), depths = static_cast<uint32_t>(sk.level_begin.size() - 1u);
+    std::vector<uint4> segs(n_nodes);   // {first, count, node, leaf}, depth by depth
+    for (uint32_t j = 0; j < n_nodes; ++j)
+        segs[j] = make_uint4(sk.level_first[j], sk.level_count[j], sk.level_nodes[j], sk.nodes[sk.level_nodes[j]].primitive_count ? 1u : 0u);
+    size_t sort_bytes = 0, scan_bytes = 0;
+    hipError_t e = rocprim::radix_sort_pairs(nullptr, sort_bytes, static_cast<uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr),
+                                             static_cast<uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr), n, 0, 32, stream);
+    if (e != hipSuccess) return static_cast<int>(e);
+    e = rocprim::exclusive_scan(nullptr, scan_bytes, static_cast<unsigned long long*>(nullptr), static_cast<unsigned long long*>(nullptr),
+                                0ull, n, rocprim::plus<unsigned long long>(), stream);
+    if (e != hipSuccess) return static_cast<int>(e);
+    size_t off = 0;
+    auto carve = [&](size_t bytes) { const size_t o = off; off += align256(bytes); return o; };
+    const size_t o_keys = carve(12u * size_t(n)), o_keys_out = carve(4u * size_t(n));
+    const size_t o_la = carve(16u * size_t(n)), o_lb = carve(16u * size_t(n));
+    const size_t o_tbmin = carve(16u * size_t(n)), o_tbmax = carve(16u * size_t(n));
+    const size_t o_segmap = carve(4u * size_t(n)), o_left = carve(size_t(n));
+    const size_t o_f01 = carve(8u * size_t(n)), o_f23 = carve(8u * size_t(n)), o_s01 = carve(8u * size_t(n)), o_s23 = carve(8u * size_t(n));
+    const size_t o_box = carve(32u * size_t(n_nodes)), o_segs = carve(16u * size_t(n_nodes));
+    const size_t o_sort = carve(sort_bytes), o_scan = carve(scan_bytes);
+    char* base = nullptr;
+    e = hipMalloc(reinterpret_cast<void**>(&base), off);
+    if (e != hipSuccess) return static_cast<int>(e);
+    auto at = [&](size_t o) { return base + o; };
+    auto done = [&](hipError_t err) {
+        const hipError_t st = hipStreamSynchronize(stream);   // also keeps `segs` and `sk` alive under their copies
+        (void)hipFree(base);
+        return static_cast<int>(err != hipSuccess ? err : st);
+    };
+    uint32_t* keys = reinterpret_cast<uint32_t*>(at(o_keys));
+    uint32_t* keys_out = reinterpret_cast<uint32_t*>(at(o_keys_out));
+    uint32_t *la = reinterpret_cast<uint32_t*>(at(o_la)), *lb = reinterpret_cast<uint32_t*>(at(o_lb));   // lists x, y, z, id
+    uint4 *tbmin = reinterpret_cast<uint4*>(at(o_tbmin)), *tbmax = reinterpret_cast<uint4*>(at(o_tbmax));
+    uint32_t* segmap = reinterpret_cast<uint32_t*>(at(o_segmap));
+    uint8_t* left = reinterpret_cast<uint8_t*>(at(o_left));
+    unsigned long long *f01 = reinterpret_cast<unsigned long long*>(at(o_f01)), *f23 = reinterpret_cast<unsigned long long*>(at(o_f23));
+    unsigned long long *s01 = reinterpret_cast<unsigned long long*>(at(o_s01)), *s23 = reinterpret_cast<unsigned long long*>(at(o_s23));
+    uint32_t* box = reinterpret_cast<uint32_t*>(at(o_box));
+    uint4* d_segs = reinterpret_cast<uint4*>(at(o_segs));
+    const size_t nn = n;
+    e = hipMemcpyAsync(d_segs, segs.data(), 16u * size_t(n_nodes), hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_nodes, sk.nodes.data(), sizeof(rb_bvh_node) * n_nodes, hipMemcpyHostToDevice, stream);
+    if (e != hipSuccess) return done(e);
+    const dim3 grid = rt_grid(n), block(kRtBlock);
+    const dim3 bgrid((uint32_t)std::min<size_t>((nn + 4u * kRtBlock - 1u) / (4u * kRtBlock), 1024u));   // k_rt_bounds: >= 4 steps per block
+    hipLaunchKernelGGL(k_rt_box_init, dim3((8u * n_nodes + kRtBlock - 1u) / kRtBlock), block, 0, stream, n_nodes, box);
+    hipLaunchKernelGGL(k_rt_prep, grid, block, 0, stream, d_tris, n, keys, keys + nn, keys + 2u * nn, la + 3u * nn, tbmin, tbmax);
+    for (uint32_t a = 0; a < 3u && e == hipSuccess; ++a)   // stable: equal keys keep ascending ids
+        e = rocprim::radix_sort_pairs(at(o_sort), sort_bytes, keys + a * nn, keys_out, la + 3u * nn, la + a * nn, n, 0, 32, stream);
+    if (e != hipSuccess) return done(e);
+    for (uint32_t d = 0; d < depths; ++d) {
+        const uint32_t s_first = sk.level_begin[d], s_n = sk.level_begin[d + 1u] - s_first;
+        bool splits = false;
+        for (uint32_t j = s_first; j < s_first + s_n; ++j) splits |= segs[j].w == 0u;
+        const uint4* ls = d_segs + s_first;
+        hipLaunchKernelGGL(k_rt_segmap, grid, block, 0, stream, ls, s_n, n, segmap);
+        hipLaunchKernelGGL(k_rt_bounds, bgrid, block, 0, stream, ls, segmap, n, la + 3u * nn, tbmin, tbmax, box);
+        if (!splits) continue;
+        hipLaunchKernelGGL(k_rt_flags, grid, block, 0, stream, ls, segmap, n, la, la + nn, la + 2u * nn, box, left);
+        hipLaunchKernelGGL(k_rt_pack, grid, block, 0, stream, ls, segmap, n, la, left, f01, f23);
+        e = rocprim::exclusive_scan(at(o_scan), scan_bytes, f01, s01, 0ull, n, rocprim::plus<unsigned long long>(), stream);
+        if (e == hipSuccess) e = rocprim::exclusive_scan(at(o_scan), scan_bytes, f23, s23, 0ull, n, rocprim::plus<unsigned long long>(), stream);
+        if (e != hipSuccess) return done(e);
+        hipLaunchKernelGGL(k_rt_scatter, grid, block, 0, stream, ls, segmap, n, la, lb, f01, f23, s01, s23);
+        std::swap(la, lb);
+    }
+    hipLaunchKernelGGL(k_rt_emit, dim3((n_nodes + kRtBlock - 1u) / kRtBlock), block, 0, stream, n_nodes, box, d_nodes);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(d_indices, la + 3u * nn, 4u * nn, hipMemcpyDeviceToDevice, stream);
     return done(e);
 }
 

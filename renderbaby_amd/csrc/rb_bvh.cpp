@@ -45,6 +45,11 @@ struct Builder {
     std::vector<float> cen[3];       // centroid per triangle and axis
     std::vector<float> tmn, tmx;     // bounds per triangle (3 floats each)
     uint32_t fork_levels = 0;
+    bool canonical = false;          // bvh_build_canonical: (centroid, index) order, sorted leaves, -0 < +0 in min / max
+
+    // min / max under the total order in which -0 < +0 (the canonical boxes' bits do not depend on the order of reduction)
+    static float tot_min(float a, float b) { return (a < b || (a == b && std::signbit(a))) ? a : b; }
+    static float tot_max(float a, float b) { return (a > b || (a == b && !std::signbit(a))) ? a : b; }
 
     static float centroid(const rb_gpu_triangle& t, int axis) {
         return ((t.v0[axis] + t.v1[axis]) + t.v2[axis]) / 3.0f;  // bvh.rs:152-154
@@ -61,6 +66,11 @@ struct Builder {
                 const rb_gpu_triangle& t = tris[i];
                 for (int a = 0; a < 3; ++a) {
                     cen[a][i] = centroid(t, a);
+                    if (canonical) {
+                        tmn[3 * i + a] = tot_min(t.v0[a], tot_min(t.v1[a], t.v2[a]));
+                        tmx[3 * i + a] = tot_max(t.v0[a], tot_max(t.v1[a], t.v2[a]));
+                        continue;
+                    }
                     tmn[3 * i + a] = std::min(t.v0[a], std::min(t.v1[a], t.v2[a]));
                     tmx[3 * i + a] = std::max(t.v0[a], std::max(t.v1[a], t.v2[a]));
                 }
@@ -85,8 +95,8 @@ struct Builder {
         for (size_t i = first; i < first + count; ++i) {
             const size_t t = idx[i];
             for (int a = 0; a < 3; ++a) {
-                mn[a] = std::min(mn[a], tmn[3 * t + a]);
-                mx[a] = std::max(mx[a], tmx[3 * t + a]);
+                mn[a] = canonical ? tot_min(mn[a], tmn[3 * t + a]) : std::min(mn[a], tmn[3 * t + a]);
+                mx[a] = canonical ? tot_max(mx[a], tmx[3 * t + a]) : std::max(mx[a], tmx[3 * t + a]);
             }
         }
         rb_bvh_node n;
@@ -97,14 +107,19 @@ struct Builder {
             n.first_primitive = static_cast<uint32_t>(first);
             n.primitive_count = static_cast<uint32_t>(count);
             nodes[me] = n;
+            if (canonical) std::sort(idx.begin() + first, idx.begin() + first + count);
             return;
         }
         const float ex = mx[0] - mn[0], ey = mx[1] - mn[1], ez = mx[2] - mn[2];
         const int axis = (ex > ey && ex > ez) ? 0 : ((ey > ez) ? 1 : 2);  // bvh.rs:125-135
         const size_t mid = first + count / 2;
         const float* c = cen[axis].data();
-        std::nth_element(idx.begin() + first, idx.begin() + mid, idx.begin() + first + count,
-                         [c](uint32_t a, uint32_t b) { return c[a] < c[b]; });
+        if (canonical)   // a total order: the left half is the first count / 2 in (centroid, index) order, whatever the algorithm
+            std::nth_element(idx.begin() + first, idx.begin() + mid, idx.begin() + first + count,
+                             [c](uint32_t a, uint32_t b) { return (c[a] < c[b]) || (c[a] == c[b] && a < b); });
+        else
+            std::nth_element(idx.begin() + first, idx.begin() + mid, idx.begin() + first + count,
+                             [c](uint32_t a, uint32_t b) { return c[a] < c[b]; });
         const uint32_t l = me + 1u, r = me + 1u + static_cast<uint32_t>(nodes_of(mid - first));
         n.left = l;
         n.right = r;
@@ -122,19 +137,72 @@ struct Builder {
 
 }  // namespace
 
-void bvh_build(const rb_gpu_triangle* tris, size_t n_tris, std::vector<rb_bvh_node>& nodes,
-               std::vector<uint32_t>& indices) {
+namespace {
+void build_tree(const rb_gpu_triangle* tris, size_t n_tris, std::vector<rb_bvh_node>& nodes, std::vector<uint32_t>& indices,
+                bool canonical) {
     nodes.clear();
     indices.resize(n_tris);
     for (size_t i = 0; i < n_tris; ++i) indices[i] = static_cast<uint32_t>(i);
     if (n_tris == 0) return;  // the adapter never builds an empty tree (scene_engine_adapter.rs:435-440)
     const char* seq = std::getenv("RB_HOST_BUILD_SEQUENTIAL");
     const size_t threads = (seq && seq[0] == '1') ? 1u : std::min<size_t>(std::max(1u, std::thread::hardware_concurrency()), 32u);
-    Builder b{tris, indices, nodes, {}, {}, {}, 0};
+    Builder b{tris, indices, nodes, {}, {}, {}, 0, canonical};
     for (size_t t = 1; t < threads; t *= 2) b.fork_levels++;   // 2^levels subtrees in flight
     b.prepare(n_tris, threads);
     nodes.resize(Builder::nodes_of(n_tris));
     b.node(0, n_tris, 0u, 0u);
+}
+}  // namespace
+
+void bvh_build(const rb_gpu_triangle* tris, size_t n_tris, std::vector<rb_bvh_node>& nodes,
+               std::vector<uint32_t>& indices) {
+    build_tree(tris, n_tris, nodes, indices, false);
+}
+
+void bvh_build_canonical(const rb_gpu_triangle* tris, size_t n_tris, std::vector<rb_bvh_node>& nodes,
+                         std::vector<uint32_t>& indices) {
+    build_tree(tris, n_tris, nodes, indices, true);
+}
+
+size_t first_non_finite(const rb_gpu_triangle* tris, size_t n_tris) {
+    for (size_t i = 0; i < n_tris; ++i)
+        for (int a = 0; a < 3; ++a)
+            if (!std::isfinite(tris[i].v0[a]) || !std::isfinite(tris[i].v1[a]) || !std::isfinite(tris[i].v2[a])) return i;
+    return n_tris;
+}
+
+size_t bvh_node_count(size_t n_tris) { return n_tris ? Builder::nodes_of(n_tris) : 0; }
+
+void bvh_skeleton(size_t n_tris, TreeSkeleton& sk) {
+    sk.nodes.assign(bvh_node_count(n_tris), rb_bvh_node{});
+    sk.level_nodes.clear();
+    sk.level_first.clear();
+    sk.level_count.clear();
+    sk.level_begin.assign(1, 0u);
+    if (n_tris == 0) return;
+    struct Seg { size_t first, count; uint32_t me; };
+    std::vector<Seg> cur{{0, n_tris, 0u}}, next;
+    while (!cur.empty()) {   // breadth first: a depth's nodes come out in order of their first triangle
+        next.clear();
+        for (const Seg& s : cur) {
+            rb_bvh_node& n = sk.nodes[s.me];
+            sk.level_nodes.push_back(s.me);
+            sk.level_first.push_back(static_cast<uint32_t>(s.first));
+            sk.level_count.push_back(static_cast<uint32_t>(s.count));
+            if (s.count <= kMaxLeaf) {
+                n.first_primitive = static_cast<uint32_t>(s.first);
+                n.primitive_count = static_cast<uint32_t>(s.count);
+                continue;
+            }
+            const size_t half = s.count / 2;
+            n.left = s.me + 1u;
+            n.right = s.me + 1u + static_cast<uint32_t>(Builder::nodes_of(half));
+            next.push_back({s.first, half, n.left});
+            next.push_back({s.first + half, s.count - half, n.right});
+        }
+        sk.level_begin.push_back(static_cast<uint32_t>(sk.level_nodes.size()));
+        cur.swap(next);
+    }
 }
 
 // Iterative DFS from node 0 following exactly the children the shader would push

@@ -33,6 +33,25 @@ void bvh_build(const rb_gpu_triangle* tris, size_t n_tris, std::vector<rb_bvh_no
                std::vector<uint32_t>& indices);
 bool bvh_validate(const rb_bvh_node* nodes, uint32_t node_count, uint32_t max_stack, std::string& why,
                   uint32_t* depth_out);
+// The canonical reference-layout tree: bvh_build's topology with every choice it leaves open fixed --
+// (centroid, index) order, leaves in ascending index, boxes under the total order -0 < +0.  The caller has refused non-finite
+// vertices (first_non_finite).
+void bvh_build_canonical(const rb_gpu_triangle* tris, size_t n_tris, std::vector<rb_bvh_node>& nodes,
+                         std::vector<uint32_t>& indices);
+// index of the first triangle with a non-finite vertex coordinate, or n_tris
+size_t first_non_finite(const rb_gpu_triangle* tris, size_t n_tris);
+// What follows from the triangle count alone (identical for bvh_build and the canonical builders): the nodes with their
+// children and leaf ranges and zero boxes, and the nodes of each depth in order of their first triangle (= pre-order within a
+// depth) with the triangle range of each.
+struct TreeSkeleton {
+    std::vector<rb_bvh_node> nodes;
+    std::vector<uint32_t> level_nodes;   // node indices, depth by depth
+    std::vector<uint32_t> level_first;   // per entry of level_nodes: the node's first triangle ...
+    std::vector<uint32_t> level_count;   // ... and its triangle count
+    std::vector<uint32_t> level_begin;   // depth d = level_nodes[level_begin[d] .. level_begin[d + 1])
+};
+void bvh_skeleton(size_t n_tris, TreeSkeleton& sk);
+size_t bvh_node_count(size_t n_tris);   // = bvh_skeleton(n_tris).nodes.size(), without building it
 
 // The two-box node of the library's own TRIANGLE tree (leaves of <= 2: 0x80000000 | (count-1) << 28 | first).
 struct alignas(16) SphereNode {
@@ -228,6 +247,10 @@ struct DeviceTreeInfo {
 int device_fast_bvh_build(const rb_gpu_triangle* tris, const uint32_t* indices, const uint32_t* slots, uint32_t n,
                           const uint32_t* slot_meta, SphereNode* nodes_out, uint32_t* fast_slots_out, DeviceTreeInfo* info_out,
                           void* stream, bool plain_lbvh);
+// ---- rb_build.hip: the canonical reference-layout tree (bvh_build_canonical's bytes) built on the device from d_tris (n
+// finite triangles, 1 <= n < 2^31).  d_nodes holds bvh_skeleton(n).nodes.size() nodes, d_indices n.  Synchronises `stream`;
+// returns a hipError_t (hipErrorOutOfMemory when its scratch does not fit).
+int device_reference_bvh_build(const rb_gpu_triangle* d_tris, uint32_t n, rb_bvh_node* d_nodes, uint32_t* d_indices, void* stream);
 
 // ---- device-side counters (one block of u64 in device memory)
 enum Counter : uint32_t {

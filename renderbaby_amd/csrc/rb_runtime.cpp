@@ -165,6 +165,8 @@ struct rb_engine {
     uint32_t bvh_stack = 0;          // traversal-stack entries the current tree needs
 
     std::vector<rb_bvh_node> host_nodes;  // kept for validation when nodes/indices change separately
+    const char* tree_builder = "";         // who made the reference-layout tree: "device" | "host" (RB_FLAG_BUILD_TREE*) | "caller"
+    float tree_build_ms = 0.0f;
     uint32_t width = 0, height = 0, local_rows = 0, padded_rows = 0;
 
     rb_stats stats{};
@@ -426,6 +428,8 @@ Act field_action(int idx, const rb_field& f, bool first) {
     return Act::None;
 }
 
+// RB_FLAG_BUILD_TREE / _HOST: the engine makes the reference-layout tree from the triangles itself
+bool builds_tree(const rb_engine* e) { return (e->opt.flags & (RB_FLAG_BUILD_TREE | RB_FLAG_BUILD_TREE_HOST)) != 0u; }
 // may the library's own tree be wanted for this engine's meshes?  (host copies of triangles / indices are kept then)
 bool may_want_own_tree(const rb_engine* e) { return !(e->opt.flags & RB_FLAG_REFERENCE_WALK); }
 // a mesh of `n` elements whose host copy can wait (ensure_host_mesh): large enough for the device builder, and no flag that
@@ -480,6 +484,8 @@ int apply_field(rb_engine* e, int idx, const rb_field& f, bool first) {
             e->n_nodes = static_cast<uint32_t>(n);
             e->host_nodes.assign(static_cast<const rb_bvh_node*>(src), static_cast<const rb_bvh_node*>(src) + n);
             e->prep_dirty = true;
+            e->tree_builder = n ? "caller" : "";
+            e->tree_build_ms = 0.0f;
             break;
         case 6:
             rc = upload(e, e->indices, src, n, &e->n_indices, true);
@@ -525,7 +531,22 @@ int validate_scene(rb_engine* e, const rb_config* cfg, bool first, ScenePlan& pl
     // ---- the tree the kernels would walk
     const rb_bvh_node* nodes = e->host_nodes.data();
     uint32_t n_nodes = static_cast<uint32_t>(e->host_nodes.size());
-    if (a_nodes == Act::Take) {
+    rb::TreeSkeleton own;   // RB_FLAG_BUILD_TREE: the tree the engine will build -- its shape follows from the triangle count
+    const bool own_tree = builds_tree(e);
+    if (own_tree && (cfg->bvh_nodes.change != RB_KEEP || cfg->bvh_indices.change != RB_KEEP))
+        return fail(e, RB_ERR_INVALID_BVH, "the engine builds the tree itself (RB_FLAG_BUILD_TREE): bvh_nodes and bvh_indices must be Keep");
+    if (own_tree && a_tris == Act::Take) {
+        const rb_gpu_triangle* t = static_cast<const rb_gpu_triangle*>(cfg->bvh_triangles.ptr);
+        if (cfg->bvh_triangles.count >= (1ull << 31)) return fail(e, RB_ERR_INVALID_BVH, "too many triangles");
+        const size_t bad = rb::first_non_finite(t, cfg->bvh_triangles.count);
+        if (bad < cfg->bvh_triangles.count)
+            return fail(e, RB_ERR_INVALID_BVH, "triangle %zu has a non-finite vertex coordinate", bad);
+        rb::bvh_skeleton(cfg->bvh_triangles.count, own);
+        nodes = own.nodes.data();
+        n_nodes = static_cast<uint32_t>(own.nodes.size());
+    } else if (own_tree && a_tris == Act::Delete) {
+        n_nodes = 0;
+    } else if (a_nodes == Act::Take) {
         nodes = static_cast<const rb_bvh_node*>(cfg->bvh_nodes.ptr);
         if (cfg->bvh_nodes.count >= (1ull << 31)) return fail(e, RB_ERR_INVALID_BVH, "too many BVH nodes");
         n_nodes = static_cast<uint32_t>(cfg->bvh_nodes.count);
@@ -535,6 +556,8 @@ int validate_scene(rb_engine* e, const rb_config* cfg, bool first, ScenePlan& pl
     uint64_t index_len = e->n_indices;  // arrayLength(&bvh_indices): an empty vector still has one element
     if (a_idx == Act::Take) index_len = std::max<uint64_t>(cfg->bvh_indices.count, 1);
     else if (a_idx == Act::Delete) index_len = 1;
+    if (own_tree && a_tris == Act::Take) index_len = std::max<uint64_t>(cfg->bvh_triangles.count, 1);
+    else if (own_tree && a_tris == Act::Delete) index_len = 1;
     if (index_len >= (1ull << 31)) return fail(e, RB_ERR_INVALID_BVH, "too many BVH indices");
     plan.bvh_stack = e->bvh_stack;
     if (n_nodes > 0) {
@@ -1028,6 +1051,72 @@ int read_rgba(rb_engine* e, uint8_t* out) {
     return read_slot_rgba(e, e->cur, out);
 }
 
+// RB_FLAG_BUILD_TREE: the canonical reference-layout tree of the n triangles just uploaded (host copy `src`, borrowed for the
+// update), in place of the caller's bvh_nodes / bvh_indices.  On the device by default: the nodes are read back (48 B per 128
+// triangles) for validation and the host walks' builders, the indices stay on the device (fetched back by ensure_host_mesh if a
+// host builder needs them).  A device short of memory for the builder's scratch falls back to the host builder: the same tree.
+int build_engine_tree(rb_engine* e, const rb_gpu_triangle* src, size_t n) {
+    const auto t_begin = std::chrono::steady_clock::now();
+    e->prep_dirty = true;
+    e->tree_builder = "";
+    e->tree_build_ms = 0.0f;
+    int rc = RB_OK;
+    if (n == 0) {   // Delete, or an empty vector: an empty tree
+        rc = upload(e, e->nodes, nullptr, 0, nullptr, true);
+        if (!rc) rc = upload(e, e->indices, nullptr, 0, &e->n_indices, true);
+        if (rc) return rc;
+        e->n_nodes = 0;
+        e->host_nodes.clear();
+        e->host_index_len = 0;
+        e->host_indices_stale = false;
+        std::vector<uint32_t>().swap(e->host_indices);
+        return RB_OK;
+    }
+    const char* builder = "host";
+    if (!(e->opt.flags & RB_FLAG_BUILD_TREE_HOST)) {
+        const size_t nn = rb::bvh_node_count(n);
+        HIP_TRY(e, e->nodes.resize(nn));
+        HIP_TRY(e, e->indices.resize(n));
+        const int brc = rb::device_reference_bvh_build(e->tris.ptr, static_cast<uint32_t>(n), e->nodes.ptr, e->indices.ptr, e->stream);
+        if (brc == hipSuccess) {
+            e->host_nodes.resize(nn);
+            HIP_TRY(e, hipMemcpyAsync(e->host_nodes.data(), e->nodes.ptr, sizeof(rb_bvh_node) * nn, hipMemcpyDeviceToHost, e->stream));
+            HIP_TRY(e, hipStreamSynchronize(e->stream));
+            e->n_nodes = static_cast<uint32_t>(nn);
+            e->n_indices = static_cast<uint32_t>(n);
+            if (may_want_own_tree(e)) {
+                e->host_index_len = n;
+                e->host_indices_stale = true;
+                std::vector<uint32_t>().swap(e->host_indices);
+            }
+            builder = "device";
+        } else if (brc != hipErrorOutOfMemory) {
+            return fail(e, RB_ERR_DEVICE, "device tree build failed: %s", hipGetErrorString(static_cast<hipError_t>(brc)));
+        } else {
+            (void)hipGetLastError();
+        }
+    }
+    if (builder[0] == 'h') {
+        std::vector<rb_bvh_node> nodes;
+        std::vector<uint32_t> idx;
+        rb::bvh_build_canonical(src, n, nodes, idx);
+        rc = upload(e, e->nodes, nodes.data(), nodes.size(), nullptr, true);
+        if (!rc) rc = upload(e, e->indices, idx.data(), idx.size(), &e->n_indices, true);
+        if (rc) return rc;
+        HIP_TRY(e, hipStreamSynchronize(e->stream));   // `nodes` / `idx` are moved below, but the copies read them now
+        e->n_nodes = static_cast<uint32_t>(nodes.size());
+        e->host_nodes = std::move(nodes);
+        if (may_want_own_tree(e)) {
+            e->host_index_len = n;
+            e->host_indices_stale = false;
+            e->host_indices = std::move(idx);
+        }
+    }
+    e->tree_builder = builder;
+    e->tree_build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    return RB_OK;
+}
+
 int update_fields(rb_engine* e, const rb_config* cfg) {
     int rc = check_fields(e, cfg);
     if (rc) return rc;
@@ -1062,8 +1151,16 @@ int update_fields(rb_engine* e, const rb_config* cfg) {
         rc = apply_field(e, i, *field_at(cfg, i), first);
         if (rc) return rc;
     }
+    if (builds_tree(e)) {   // the tree follows the triangles field (RB_FLAG_BUILD_TREE)
+        const Act a_tris = field_action(7, cfg->bvh_triangles, first);
+        if (a_tris != Act::None) {
+            rc = build_engine_tree(e, static_cast<const rb_gpu_triangle*>(a_tris == Act::Take ? cfg->bvh_triangles.ptr : nullptr),
+                                   a_tris == Act::Take ? cfg->bvh_triangles.count : 0);
+            if (rc) return rc;
+        }
+    }
     e->last_change_spheres = cfg->spheres.change;
-    e->last_change_nodes = cfg->bvh_nodes.change;
+    e->last_change_nodes = builds_tree(e) ? cfg->bvh_triangles.change : cfg->bvh_nodes.change;
     e->last_change_tris = cfg->bvh_triangles.change;
     e->bvh_stack = plan.bvh_stack;
     e->max_mesh_index = plan.max_mesh_index;
@@ -1188,6 +1285,10 @@ rb_engine* create_single(const rb_config* cfg, const rb_options& opt) {
         return nullptr;
     }
     if (opt.kernel > RB_KERNEL_STREAM) { fail(nullptr, RB_ERR_INVALID_OPTIONS, "unknown kernel %u", opt.kernel); return nullptr; }
+    if ((opt.flags & RB_FLAG_BUILD_TREE) && (opt.flags & RB_FLAG_BUILD_TREE_HOST)) {
+        fail(nullptr, RB_ERR_INVALID_OPTIONS, "RB_FLAG_BUILD_TREE and RB_FLAG_BUILD_TREE_HOST exclude each other");
+        return nullptr;
+    }
     int dev = opt.device;
     if (dev < 0) {
         if (hipGetDevice(&dev) != hipSuccess) { fail(nullptr, RB_ERR_DEVICE, "no HIP device available"); return nullptr; }
@@ -1821,6 +1922,91 @@ int rb_bvh_build(const rb_gpu_triangle* tris, size_t n_tris, rb_bvh_node* nodes_
     std::memcpy(nodes_out, nodes.data(), nodes.size() * sizeof(rb_bvh_node));
     if (indices_out) std::memcpy(indices_out, indices.data(), indices.size() * sizeof(uint32_t));
     return RB_OK;
+}
+
+int rb_bvh_build_canonical(const rb_gpu_triangle* tris, size_t n_tris, rb_bvh_node* nodes_out, size_t nodes_capacity,
+                           size_t* n_nodes, uint32_t* indices_out) {
+    if (!n_nodes) return RB_ERR_NULL_ARGUMENT;
+    if (n_tris >= (1ull << 31)) return fail(nullptr, RB_ERR_INVALID_BVH, "too many triangles");
+    *n_nodes = rb::bvh_node_count(n_tris);
+    if (!nodes_out) return RB_OK;   // the size query follows from n_tris alone: no build
+    if (n_tris > 0 && !tris) return RB_ERR_NULL_ARGUMENT;
+    if (nodes_capacity < *n_nodes) return RB_ERR_INVALID_BVH;
+    const size_t bad = rb::first_non_finite(tris, n_tris);
+    if (bad < n_tris) return fail(nullptr, RB_ERR_INVALID_BVH, "triangle %zu has a non-finite vertex coordinate", bad);
+    std::vector<rb_bvh_node> nodes;
+    std::vector<uint32_t> indices;
+    rb::bvh_build_canonical(tris, n_tris, nodes, indices);
+    std::memcpy(nodes_out, nodes.data(), nodes.size() * sizeof(rb_bvh_node));
+    if (indices_out) std::memcpy(indices_out, indices.data(), indices.size() * sizeof(uint32_t));
+    return RB_OK;
+}
+
+int rb_bvh_build_device(int32_t device, const rb_gpu_triangle* tris, size_t n_tris, rb_bvh_node* nodes_out, size_t nodes_capacity,
+                        size_t* n_nodes, uint32_t* indices_out) {
+    if (!n_nodes) return RB_ERR_NULL_ARGUMENT;
+    if (n_tris >= (1ull << 31)) return fail(nullptr, RB_ERR_INVALID_BVH, "too many triangles");
+    const size_t nn = rb::bvh_node_count(n_tris);
+    *n_nodes = nn;
+    if (!nodes_out) return RB_OK;   // the size query touches no device (nor the triangles)
+    if (n_tris > 0 && !tris) return RB_ERR_NULL_ARGUMENT;
+    if (nodes_capacity < nn) return RB_ERR_INVALID_BVH;
+    const size_t bad = rb::first_non_finite(tris, n_tris);
+    if (bad < n_tris) return fail(nullptr, RB_ERR_INVALID_BVH, "triangle %zu has a non-finite vertex coordinate", bad);
+    if (n_tris == 0) return RB_OK;
+    if (device >= 0 && hipSetDevice(device) != hipSuccess) return fail(nullptr, RB_ERR_DEVICE, "hipSetDevice(%d) failed", device);
+    rb_gpu_triangle* d_tris = nullptr;
+    rb_bvh_node* d_nodes = nullptr;
+    uint32_t* d_idx = nullptr;
+    hipStream_t stream = nullptr;
+    hipError_t st = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
+    if (st == hipSuccess) st = hipMalloc(reinterpret_cast<void**>(&d_tris), sizeof(rb_gpu_triangle) * n_tris);
+    if (st == hipSuccess) st = hipMalloc(reinterpret_cast<void**>(&d_nodes), sizeof(rb_bvh_node) * nn);
+    if (st == hipSuccess) st = hipMalloc(reinterpret_cast<void**>(&d_idx), 4u * n_tris);
+    if (st == hipSuccess) st = hipMemcpyAsync(d_tris, tris, sizeof(rb_gpu_triangle) * n_tris, hipMemcpyHostToDevice, stream);
+    if (st == hipSuccess) st = static_cast<hipError_t>(rb::device_reference_bvh_build(d_tris, static_cast<uint32_t>(n_tris), d_nodes, d_idx, stream));
+    if (st == hipSuccess) st = hipMemcpyAsync(nodes_out, d_nodes, sizeof(rb_bvh_node) * nn, hipMemcpyDeviceToHost, stream);
+    if (st == hipSuccess && indices_out) st = hipMemcpyAsync(indices_out, d_idx, 4u * n_tris, hipMemcpyDeviceToHost, stream);
+    if (st == hipSuccess) st = hipStreamSynchronize(stream);
+    if (stream) (void)hipStreamSynchronize(stream);
+    (void)hipFree(d_tris);
+    (void)hipFree(d_nodes);
+    (void)hipFree(d_idx);
+    if (stream) (void)hipStreamDestroy(stream);
+    if (st != hipSuccess) return fail(nullptr, RB_ERR_DEVICE, "device tree build failed: %s", hipGetErrorString(st));
+    return RB_OK;
+}
+
+int rb_engine_tree(rb_engine* e, rb_bvh_node* nodes_out, size_t nodes_capacity, size_t* n_nodes, uint32_t* indices_out,
+                   size_t indices_capacity, size_t* n_indices) {
+    if (!e || !n_nodes || !n_indices) return RB_ERR_NULL_ARGUMENT;
+    rb_engine* g = e;
+    std::unique_lock<std::mutex> group_lock;
+    if (is_group(e)) {   // the handle's own lock first, then the part's (every part holds the same tree)
+        group_lock = std::unique_lock<std::mutex>(g->mu);
+        e = e->parts[0].get();
+    }
+    std::lock_guard<std::mutex> lock(e->mu);
+    const size_t nn = e->host_nodes.size(), ni = nn ? e->n_indices : 0;
+    *n_nodes = nn;
+    *n_indices = ni;
+    if (nodes_out) {
+        if (nodes_capacity < nn) return fail(g, RB_ERR_INVALID_BVH, "nodes_out holds %zu of %zu nodes", nodes_capacity, nn);
+        if (nn) std::memcpy(nodes_out, e->host_nodes.data(), sizeof(rb_bvh_node) * nn);
+    }
+    if (indices_out && ni) {
+        if (indices_capacity < ni) return fail(g, RB_ERR_INVALID_BVH, "indices_out holds %zu of %zu indices", indices_capacity, ni);
+        set_device(e);
+        HIP_TRY(e, hipStreamSynchronize(e->stream));
+        HIP_TRY(e, hipMemcpy(indices_out, e->indices.ptr, 4u * ni, hipMemcpyDeviceToHost));
+    }
+    return RB_OK;
+}
+
+const char* rb_tree_builder(const rb_engine* e, float* build_ms) {
+    if (e && is_group(e)) e = e->parts[0].get();
+    if (build_ms) *build_ms = e ? e->tree_build_ms : 0.0f;
+    return (e && !e->host_nodes.empty()) ? e->tree_builder : "";
 }
 
 const char* rb_version(void) { return "renderbaby-hip 0.3 (gfx950)"; }

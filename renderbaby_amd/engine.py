@@ -72,16 +72,18 @@ class RenderConfig:
         return RenderConfigBuilder()
 
     @staticmethod
-    def from_scene(scene, create=True):
+    def from_scene(scene, create=True, with_tree=True):
         """What generate_full_render_command_builder emits
         (scene_engine_adapter.rs:463-490): all ``*_create`` on the first render;
-        afterwards Update for everything except the three BVH fields, which stay Create."""
+        afterwards Update for everything except the three BVH fields, which stay Create.
+        ``with_tree=False``: bvh_nodes and bvh_indices are Keep -- for an engine that builds the tree itself
+        (``Engine(..., build_tree=...)``)."""
         mk = Change.create if create else Change.update
         return RenderConfig(
             uniforms=mk(scene.uniforms), spheres=mk(scene.spheres), uvs=mk(scene.uvs), meshes=mk(scene.meshes),
-            lights=mk(scene.lights), bvh_nodes=Change.create(scene.bvh_nodes),
-            bvh_indices=Change.create(scene.bvh_indices), bvh_triangles=Change.create(scene.bvh_triangles),
-            textures=mk(scene.textures))
+            lights=mk(scene.lights), bvh_nodes=Change.create(scene.bvh_nodes) if with_tree else Change.keep(),
+            bvh_indices=Change.create(scene.bvh_indices) if with_tree else Change.keep(),
+            bvh_triangles=Change.create(scene.bvh_triangles), textures=mk(scene.textures))
 
     # ---- marshalling
     def to_c(self):
@@ -173,9 +175,11 @@ class Engine:
                  no_sphere_bvh=False, fast_bvh=False, lds_mode=0, device_bvh=False, no_leaf_stepping=False,
                  device_lbvh=False, reference_walk=False, host_bvh=False, devices=None, gather_peer_copy=False,
                  no_run_ahead=False, own_tree=False, skip_near_degenerate=False, queue_batch=0, chunk_walk=False,
-                 sphere_tree=None, chunk_tree=None):
+                 sphere_tree=None, chunk_tree=None, build_tree=None):
         """``devices`` (list of HIP ordinals): one handle over several devices of this process
-        (rb_create_multi): rows sharded in stripes, one RCCL gather per delivered frame."""
+        (rb_create_multi): rows sharded in stripes, one RCCL gather per delivered frame.
+        ``build_tree`` ("device" | "host"): the engine builds the reference-layout tree from the triangles itself
+        (RB_FLAG_BUILD_TREE): send configs with ``RenderConfig.from_scene(scene, with_tree=False)``."""
         self._lib = load()
         cfg, keep = rc.to_c()
         opt = abi.Options()
@@ -194,7 +198,8 @@ class Engine:
             | (abi.FLAG_NO_RUN_AHEAD if no_run_ahead else 0) | (abi.FLAG_SKIP_NEAR_DEGENERATE if skip_near_degenerate else 0) \
             | (abi.FLAG_CHUNK_WALK if chunk_walk else 0) \
             | {None: 0, "host": abi.FLAG_SPHERE_TREE_HOST, "device": abi.FLAG_SPHERE_TREE_DEVICE}[sphere_tree] \
-            | {None: 0, "host": abi.FLAG_CHUNK_TREE_HOST, "device": abi.FLAG_CHUNK_TREE_DEVICE}[chunk_tree]   # who builds the chunked walk's tree
+            | {None: 0, "host": abi.FLAG_CHUNK_TREE_HOST, "device": abi.FLAG_CHUNK_TREE_DEVICE}[chunk_tree] \
+            | {None: 0, "host": abi.FLAG_BUILD_TREE_HOST, "device": abi.FLAG_BUILD_TREE}[build_tree]   # who builds the chunked walk's tree / the reference-layout tree
         opt._reserved[0] = blocks_per_cu
         opt._reserved[1] = color_budget_mib
         opt._reserved[2] = queue_batch   # items a wave reserves per queue atomic (0 = the launcher's choice)
@@ -374,6 +379,23 @@ class Engine:
         """("device" | "host" | "", build milliseconds) of the chunked walk's tree (multi-node meshes, the default walk)."""
         ms = C.c_float()
         name = (self._lib.rb_chunk_tree_builder(self._h, C.byref(ms)) or b"").decode()
+        return name, ms.value
+
+    def tree(self):
+        """(abi.BVH_NODE[], uint32[] indices) of the reference-layout tree the engine walks (rb_engine_tree): the caller's,
+        or the engine's own under ``build_tree``."""
+        nn, ni = C.c_size_t(0), C.c_size_t(0)
+        self._check(self._lib.rb_engine_tree(self._h, None, 0, C.byref(nn), None, 0, C.byref(ni)))
+        nodes = np.zeros(nn.value, dtype=abi.BVH_NODE)
+        indices = np.zeros(ni.value, dtype=np.uint32)
+        self._check(self._lib.rb_engine_tree(self._h, nodes.ctypes.data if nn.value else None, len(nodes), C.byref(nn),
+                                             indices.ctypes.data if ni.value else None, len(indices), C.byref(ni)))
+        return nodes, indices
+
+    def tree_builder(self):
+        """("device" | "host" | "caller" | "", build milliseconds) of the reference-layout tree the engine walks."""
+        ms = C.c_float()
+        name = (self._lib.rb_tree_builder(self._h, C.byref(ms)) or b"").decode()
         return name, ms.value
 
     def debug_chunk_tree(self):

@@ -10,11 +10,12 @@ dumps every thread's stack to the same file together with the (seed, variant, ke
 writes seed, variant, the differing pixel coordinates and the raw frame / accumulation / oracle arrays to
 gpurun_out/fuzz_mismatch_<seed>_<variant>.npz.
 """
+import dataclasses
 import faulthandler
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
-from renderbaby_amd import Engine, RenderConfig, abi, scenes
+from renderbaby_amd import Engine, RenderConfig, abi, bvh, scenes
 from tests import _oracle
 
 
@@ -142,6 +143,20 @@ def variants(scene):
     return v
 
 
+def build_tree_variants(scene):
+    """The engine builds the canonical tree itself (RB_FLAG_BUILD_TREE) from the triangles alone; main() checks these against
+    the oracle walking that tree (kept apart from variants(), whose callers send the scene's own tree)."""
+    if len(scene.bvh_triangles) == 0:
+        return []
+    v = [("build-tree", dict(build_tree="device")), ("build-tree-host", dict(build_tree="host")),
+         ("build-tree-reference", dict(build_tree="device", reference_walk=True)),
+         ("build-tree-queue", dict(build_tree="device", kernel=abi.KERNEL_QUEUE))]
+    only = os.environ.get("FUZZ_VARIANTS")
+    if only:
+        v = [x for x in v if x[0] in only.split(",")]
+    return v
+
+
 def main():
     first = int(sys.argv[1]) if len(sys.argv) > 1 else 0
     count = int(sys.argv[2]) if len(sys.argv) > 2 else 100
@@ -156,12 +171,21 @@ def main():
         s = random_scene(seed)
         fault.write(f"# seed {seed}\n"); fault.flush()
         faulthandler.dump_traceback_later(scene_timeout, repeat=False, file=fault, exit=False)
-        o_acc, _, o_rgba, o_st = _oracle.render(s)
-        rc = RenderConfig.from_scene(s)
-        for name, kw in variants(s):
+        plain = _oracle.render(s)
+        canonical = None
+        for name, kw in variants(s) + build_tree_variants(s):
             if trace is not None:
                 trace.seek(0); trace.truncate(); trace.write(f"{seed} {name}\n"); trace.flush()
             try:
+                if "build_tree" in kw:   # the oracle walks the canonical tree, the engine gets the triangles only
+                    if canonical is None:   # (a scene the canonical builder refuses is a refusal of this variant, not the campaign's end)
+                        nodes, idx = bvh.build_canonical(s.bvh_triangles)
+                        canonical = _oracle.render(dataclasses.replace(s, bvh_nodes=nodes, bvh_indices=idx))
+                    o_acc, _, o_rgba, o_st = canonical
+                    rc = RenderConfig.from_scene(s, with_tree=False)
+                else:
+                    o_acc, _, o_rgba, o_st = plain
+                    rc = RenderConfig.from_scene(s)
                 fault.write(f"#   variant {name}\n"); fault.flush()
                 e = Engine.new(rc, stats=True, **kw)
                 frame = e.render(rc); acc = e.read_accumulation(); st = e.stats(); kname = e.last_kernel_name(); e.close()

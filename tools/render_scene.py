@@ -16,6 +16,7 @@ ap.add_argument("scene"); ap.add_argument("png")
 ap.add_argument("--spp", type=int, default=None); ap.add_argument("--max-depth", type=int, default=5)
 ap.add_argument("--width", type=int, default=0); ap.add_argument("--height", type=int, default=0)
 ap.add_argument("--fast-bvh", action="store_true"); ap.add_argument("--device-bvh", action="store_true")
+ap.add_argument("--build-tree", action="store_true", help="send triangles only: the engine builds the mesh's tree on the device")
 ap.add_argument("--included-root", default=None); ap.add_argument("--every", type=int, default=0)
 a = ap.parse_args()
 
@@ -25,8 +26,8 @@ if a.width and a.height:
     s = s.with_params(width=a.width, height=a.height)
 print(f"loaded {a.scene}: {len(s.bvh_triangles)} triangles, {len(s.spheres)} spheres, {len(s.lights)} lights, "
       f"{len(s.textures)} textures, {s.width}x{s.height}, {s.total_samples} spp ({time.time() - t0:.2f} s)")
-rc = RenderConfig.from_scene(s)
-eng = Engine.new(rc, fast_bvh=a.fast_bvh, device_bvh=a.device_bvh)
+rc = RenderConfig.from_scene(s, with_tree=not a.build_tree)
+eng = Engine.new(rc, fast_bvh=a.fast_bvh, device_bvh=a.device_bvh, build_tree="device" if a.build_tree else None)
 t0 = time.time()
 if a.every > 0:
     base, ext = os.path.splitext(a.png)
