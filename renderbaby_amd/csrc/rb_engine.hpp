@@ -1,0 +1,226 @@
+// rb_engine.hpp -- the engine's state, shared by the runtime (rb_runtime.cpp) and the acceleration structures it builds
+// (rb_accel.cpp).  Host code only: not part of the ABI, and no .hip file includes it.
+#pragma once
+#include <hip/hip_runtime_api.h>
+
+#include <algorithm>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "rb_internal.hpp"
+#include "rb_rccl.hpp"
+
+namespace rb {
+
+template <typename T>
+struct DevBuf {
+    T* ptr = nullptr;
+    size_t count = 0;     // elements allocated
+    ~DevBuf() { release(); }
+    void release() {
+        if (ptr) (void)hipFree(ptr);
+        ptr = nullptr;
+        count = 0;
+    }
+    hipError_t resize(size_t n) {
+        if (n == count && ptr) return hipSuccess;
+        release();
+        if (n == 0) return hipSuccess;
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(&ptr), n * sizeof(T));
+        if (e == hipSuccess) count = n;
+        return e;
+    }
+    void adopt(T* p, size_t n) {   // take over an allocation made elsewhere (rb_build.hip)
+        release();
+        ptr = p;
+        count = n;
+    }
+    // scratch that is sized per launch: keep an allocation that is large enough and not wastefully so
+    hipError_t reserve(size_t n) {
+        if (ptr && n <= count && count <= 4 * std::max<size_t>(n, 1)) return hipSuccess;
+        return resize(n);
+    }
+};
+
+// One frame: the accumulation (vec4<f32> per pixel: sum of radiance, sample count) and the packed RGBA8
+// image the kernels derive from it.  `done` is recorded after the launches that produced this slot.
+struct FrameSlot {
+    DevBuf<float> accum;
+    DevBuf<uint32_t> rgba;
+    hipEvent_t done = nullptr;
+};
+
+// ---- the acceleration structures (rb_accel.cpp): each keeps its device buffers, its header and one build record: which
+// builder made it and how long that took (rb_*_builder).  An empty name means "not built".
+struct BuildRecord {
+    const char* builder = "";
+    float ms = 0.0f;
+    bool built() const { return builder[0] != '\0'; }
+};
+
+struct SphereAccel {   // the spheres' tree: "device-median" | "host-median"
+    DevBuf<SphereNode4> nodes;
+    DevBuf<float> leaf;
+    DevBuf<uint32_t> id;
+    uint32_t root = 0, depth = 0;   // depth: the stack entries of its walk
+    BuildRecord rec;
+};
+
+struct ChunkAccel {    // the chunked walk's tree (ChunkTree): "device" | "host"
+    DevBuf<ChunkNode> nodes;
+    DevBuf<float> a, b, c;
+    DevBuf<uint32_t> rank_slot;
+    DevBuf<uint32_t> pos_slot, pos_rank;   // chunk order -> slot / rank: read by the gather at build time, kept for rb_debug_engine_chunk_tree
+    size_t n_nodes = 0;
+    uint32_t root = 0, depth = 0;
+    BuildRecord rec;
+};
+
+struct OwnAccel {      // the library's own triangle tree (walk mode "fast"): "device-ploc" | "device-lbvh" | "host-sah"
+    DevBuf<SphereNode> nodes;
+    DevBuf<PrepTri> tris;
+    DevBuf<uint32_t> slots, slot_meta, ref_parent, stack_overflow;
+    DevBuf<GrazeNode> gnodes;
+    DevBuf<uint32_t> gslots;
+    DeviceTreeInfo info{};   // root, depth, margin, root_amax and the mesh bounds, whichever builder ran
+    BuildRecord rec;
+};
+
+// The mesh walks an engine may build, from its options alone (mesh_walks); the mesh decides the rest.
+struct MeshWalks {
+    bool host_mesh = false;   // not RB_FLAG_REFERENCE_WALK: a host builder may need the host's copy of the mesh
+    bool chunk = false;       // the chunked walk's tree, tried first
+    bool own_named = false;   // a flag names the library's own tree: wanted at any size (unless the reference walk is named) ...
+    bool own(uint32_t n_tris) const { return host_mesh && (own_named || n_tris >= kOwnTreeDefaultMinTriangles); }  // ... else from this size up
+};
+
+}  // namespace rb
+
+struct rb_engine {
+    std::mutex mu;
+    mutable std::mutex err_mu;       // guards `error` for the const getters (rb_get_size, rb_last_error)
+    mutable std::string error;
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipStream_t copy_stream = nullptr;   // read-backs into page-locked caller memory
+    hipEvent_t ev_begin = nullptr, ev_end = nullptr;
+    std::vector<hipEvent_t> ev_pool;   // per launch chunk: begin, after-trace, end
+    uint32_t ev_used = 0;
+    const char* last_kernel_name = "";
+    rb_options opt{};
+
+    bool initialized = false;        // GpuWrapper::initialized (gpu_wrapper.rs:69,117)
+    bool have_uniforms = false;      // last update carried Create/Update uniforms (:303-329)
+    bool scene_valid = false;        // the buffers hold a scene that passed validate_scene (set by the last update)
+    rb_uniforms uniforms{};          // as handed over (before count patch-up)
+    rb_progressive prh{};            // gpu_wrapper.rs:19-53
+    bool iter_initialized = false;   // RaytracerFrameIterator::initialized (lib.rs:131)
+    uint32_t iter_passes_per_frame = 1;  // rb_iter_set_passes_per_frame (1 = the reference's one frame per pass)
+
+    // element counts = what arrayLength() / the patched uniforms see
+    uint32_t n_spheres = 0, n_lights = 0, n_meshes = 0, n_nodes = 0, n_indices = 0, n_tris = 0, n_uvs = 0,
+             n_tex = 0;
+    // Change of the last update for the three patched counts (gpu_wrapper.rs:475-495)
+    uint32_t last_change_spheres = RB_KEEP, last_change_nodes = RB_KEEP, last_change_tris = RB_KEEP;
+    bool prep_dirty = true;
+    uint32_t prep_tri_count = 0xFFFFFFFFu;  // uniforms.bvh_triangle_count (patched) the prepared triangles were made for
+
+    rb::DevBuf<rb_sphere> spheres;
+    rb::DevBuf<rb_point_light> lights;
+    rb::DevBuf<rb_mesh> meshes;
+    rb::DevBuf<rb_bvh_node> nodes;
+    rb::DevBuf<uint32_t> indices;
+    rb::DevBuf<rb_gpu_triangle> tris;
+    rb::DevBuf<rb::PrepTri> ptris;
+    rb::DevBuf<rb::PrepTriShade> pshade;
+    rb::DevBuf<float> uvs;
+    rb::DevBuf<uint32_t> tex_data;
+    rb::DevBuf<rb_texture_info> tex_info;
+    rb::DevBuf<float> srgb_lut;
+    rb::FrameSlot slot[2];           // slot[cur] holds the committed frame
+    int cur = 0;
+    bool spec_valid = false;         // slot[1 - cur] holds passes [spec_first, +spec_n) run ahead on top of slot[cur]
+    uint32_t spec_first = 0, spec_n = 0;
+    rb::DevBuf<unsigned long long> counters;
+    rb::DevBuf<uint32_t> queue;
+    rb::SphereAccel sph;
+    rb::ChunkAccel chunk;
+    rb::OwnAccel own;
+    rb::BuildRecord tree;            // who made the reference-layout tree (`nodes`, `indices`): "device" | "host" (RB_FLAG_BUILD_TREE*) | "caller"
+    // The host's copy of the mesh, for the host builders and the checkers.  A large mesh (>= kChunkDeviceBuildMin elements: the
+    // device builder's territory) is NOT copied at rb_update -- a second 88 MB in host memory cost C5's update 10 of its 14 ms --
+    // but fetched back from the device buffer if a host builder turns out to be needed after all (ensure_host_mesh).
+    std::vector<rb_gpu_triangle> host_tris;
+    std::vector<uint32_t> host_indices;
+    size_t host_tri_len = 0, host_index_len = 0;   // what the vectors hold, or would hold (0: the engine keeps no copy)
+    bool host_tris_stale = false, host_indices_stale = false;
+    bool stack_depth_covers = true;    // set with KParams::stack_depth: every walk in use fits its LDS column
+    rb::DevBuf<float> colors;        // RB_KERNEL_STREAM: float4 per (pixel, sample) of one launch chunk
+    uint64_t color_budget = 0;       // bytes `colors` may take (0 = ask the device at the next dispatch)
+    uint32_t bvh_stack = 0;          // traversal-stack entries the current tree needs
+
+    std::vector<rb_bvh_node> host_nodes;  // kept for validation when nodes/indices change separately
+    uint32_t width = 0, height = 0, local_rows = 0, padded_rows = 0;
+
+    rb_stats stats{};
+    float last_dispatch_ms = 0.0f;
+    uint32_t last_launches = 0;
+    bool timing_pending = false;
+    uint32_t max_mesh_index = 0;  // over the uploaded triangles
+
+    // ---- several devices behind one handle (rb_create_multi): this engine only coordinates; every part is a
+    // complete engine for one shard on one device.  Or one process per device (rb_comm_init_rank): this engine
+    // is shard `opt.shard_rank` and `net` holds its communicator.
+    std::vector<std::unique_ptr<rb_engine>> parts;
+    rb::Gather net;
+};
+
+namespace rb {
+
+// sets the error text of `e` (of the failing create when e is NULL) and returns `code`
+int fail(const rb_engine* e, int code, const char* fmt, ...);
+
+#define HIP_TRY(e, call)                                                                          \
+    do {                                                                                          \
+        hipError_t _st = (call);                                                                  \
+        if (_st != hipSuccess)                                                                    \
+            return rb::fail((e), RB_ERR_DEVICE, "%s failed: %s", #call, hipGetErrorString(_st));  \
+    } while (0)
+
+// create_storage_buffer -- buffers.rs:232-249: an empty slice still allocates one
+// zero-filled element (wgpu zero-initialises), so arrayLength() is 1.
+// The copy is queued on the engine's stream from caller memory: every path that calls this ends in
+// update_locked's hipStreamSynchronize (or an earlier one) before the caller gets its buffers back.
+template <typename T>
+int upload(rb_engine* e, DevBuf<T>& buf, const void* src, size_t count, uint32_t* visible_len, bool pad_empty) {
+    const size_t alloc = (count == 0 && pad_empty) ? 1 : count;
+    HIP_TRY(e, buf.resize(alloc));
+    if (count > 0) {
+        HIP_TRY(e, hipMemcpyAsync(buf.ptr, src, count * sizeof(T), hipMemcpyHostToDevice, e->stream));
+    } else if (alloc > 0) {
+        HIP_TRY(e, hipMemsetAsync(buf.ptr, 0, alloc * sizeof(T), e->stream));
+    }
+    if (visible_len) *visible_len = static_cast<uint32_t>(alloc);
+    return RB_OK;
+}
+
+inline bool is_group(const rb_engine* e) { return !e->parts.empty(); }
+inline void set_device(const rb_engine* e) { (void)hipSetDevice(e->device); }
+inline uint32_t kernel_of(const rb_options& opt) { return opt.kernel ? opt.kernel : RB_KERNEL_STREAM; }
+
+// ---- rb_accel.cpp
+constexpr uint32_t kBuildTreeFlags = RB_FLAG_BUILD_TREE | RB_FLAG_BUILD_TREE_HOST;          // the engine builds the reference-layout tree
+constexpr uint32_t kOwnTreeFlags = RB_FLAG_FAST_BVH | RB_FLAG_DEVICE_BVH | RB_FLAG_HOST_BVH;  // they name the own tree as the walk
+inline bool builds_tree(const rb_engine* e) { return (e->opt.flags & kBuildTreeFlags) != 0u; }
+MeshWalks mesh_walks(const rb_options& opt);
+bool host_copy_can_wait(const rb_engine* e, size_t n);   // may a mesh field of n elements leave its host copy to ensure_host_mesh?
+int ensure_host_mesh(rb_engine* e);
+int build_sphere_bvh(rb_engine* e, const rb_sphere* s, size_t n);              // Take / Delete of spheres
+int build_engine_tree(rb_engine* e, const rb_gpu_triangle* src, size_t n);     // RB_FLAG_BUILD_TREE: Take / Delete of triangles
+int build_chunk_tree(rb_engine* e, uint32_t tri_count);   // ensure_prepared, when wanted (tri_count: the patched count)
+int build_own_tree(rb_engine* e, uint32_t tri_count);
+uint32_t accel_params(const rb_engine* e, KParams& p);     // every structure's KParams fields; returns the stack entries needed
+
+}  // namespace rb

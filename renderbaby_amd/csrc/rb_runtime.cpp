@@ -17,174 +17,17 @@
 //  * row-stripe sharding over several devices behind this same boundary -- one engine per device inside
 //    one process (rb_create_multi) or one process per device (rb_comm_init_rank) -- with ONE RCCL gather
 //    of the RGBA8 stripes to the root per delivered frame; rccl_gather.cpp.
-#include <hip/hip_runtime_api.h>
-
-#include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <memory>
-#include <mutex>
-#include <string>
-#include <vector>
 
-#include "rb_internal.hpp"
-#include "rb_rccl.hpp"
+#include "rb_engine.hpp"
 
-namespace {
+static thread_local std::string g_create_error;
 
-thread_local std::string g_create_error;
-
-template <typename T>
-struct DevBuf {
-    T* ptr = nullptr;
-    size_t count = 0;     // elements allocated
-    ~DevBuf() { release(); }
-    void release() {
-        if (ptr) (void)hipFree(ptr);
-        ptr = nullptr;
-        count = 0;
-    }
-    hipError_t resize(size_t n) {
-        if (n == count && ptr) return hipSuccess;
-        release();
-        if (n == 0) return hipSuccess;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&ptr), n * sizeof(T));
-        if (e == hipSuccess) count = n;
-        return e;
-    }
-    void adopt(T* p, size_t n) {   // take over an allocation made elsewhere (rb_build.hip)
-        release();
-        ptr = p;
-        count = n;
-    }
-    // scratch that is sized per launch: keep an allocation that is large enough and not wastefully so
-    hipError_t reserve(size_t n) {
-        if (ptr && n <= count && count <= 4 * std::max<size_t>(n, 1)) return hipSuccess;
-        return resize(n);
-    }
-};
-
-// One frame: the accumulation (vec4<f32> per pixel: sum of radiance, sample count) and the packed RGBA8
-// image the kernels derive from it.  `done` is recorded after the launches that produced this slot.
-struct FrameSlot {
-    DevBuf<float> accum;
-    DevBuf<uint32_t> rgba;
-    hipEvent_t done = nullptr;
-};
-
-}  // namespace
-
-struct rb_engine {
-    std::mutex mu;
-    mutable std::mutex err_mu;       // guards `error` for the const getters (rb_get_size, rb_last_error)
-    mutable std::string error;
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipStream_t copy_stream = nullptr;   // read-backs into page-locked caller memory
-    hipEvent_t ev_begin = nullptr, ev_end = nullptr;
-    std::vector<hipEvent_t> ev_pool;   // per launch chunk: begin, after-trace, end
-    uint32_t ev_used = 0;
-    const char* last_kernel_name = "";
-    rb_options opt{};
-
-    bool initialized = false;        // GpuWrapper::initialized (gpu_wrapper.rs:69,117)
-    bool have_uniforms = false;      // last update carried Create/Update uniforms (:303-329)
-    bool scene_valid = false;        // the buffers hold a scene that passed validate_scene (set by the last update)
-    rb_uniforms uniforms{};          // as handed over (before count patch-up)
-    rb_progressive prh{};            // gpu_wrapper.rs:19-53
-    bool iter_initialized = false;   // RaytracerFrameIterator::initialized (lib.rs:131)
-    uint32_t iter_passes_per_frame = 1;  // rb_iter_set_passes_per_frame (1 = the reference's one frame per pass)
-
-    // element counts = what arrayLength() / the patched uniforms see
-    uint32_t n_spheres = 0, n_lights = 0, n_meshes = 0, n_nodes = 0, n_indices = 0, n_tris = 0, n_uvs = 0,
-             n_tex = 0;
-    // Change of the last update for the three patched counts (gpu_wrapper.rs:475-495)
-    uint32_t last_change_spheres = RB_KEEP, last_change_nodes = RB_KEEP, last_change_tris = RB_KEEP;
-    bool prep_dirty = true;
-    uint32_t prep_tri_count = 0xFFFFFFFFu;  // uniforms.bvh_triangle_count (patched) the prepared triangles were made for
-
-    DevBuf<rb_sphere> spheres;
-    DevBuf<rb_point_light> lights;
-    DevBuf<rb_mesh> meshes;
-    DevBuf<rb_bvh_node> nodes;
-    DevBuf<uint32_t> indices;
-    DevBuf<rb_gpu_triangle> tris;
-    DevBuf<rb::PrepTri> ptris;
-    DevBuf<rb::PrepTriShade> pshade;
-    DevBuf<float> uvs;
-    DevBuf<uint32_t> tex_data;
-    DevBuf<rb_texture_info> tex_info;
-    DevBuf<float> srgb_lut;
-    FrameSlot slot[2];               // slot[cur] holds the committed frame
-    int cur = 0;
-    bool spec_valid = false;         // slot[1 - cur] holds passes [spec_first, +spec_n) run ahead on top of slot[cur]
-    uint32_t spec_first = 0, spec_n = 0;
-    DevBuf<unsigned long long> counters;
-    DevBuf<uint32_t> queue;
-    DevBuf<rb::SphereNode> fast_nodes; // the library's own triangle tree (walk mode "fast")
-    DevBuf<rb::PrepTri> fast_tris;
-    DevBuf<uint32_t> fast_slots, slot_meta, ref_parent, stack_overflow;
-    DevBuf<rb::GrazeNode> gnodes;
-    DevBuf<uint32_t> gslots;
-    uint32_t fast_root = 0, fast_depth = 0;
-    float fast_margin = 0.0f, fast_root_amax = 0.0f;
-    float fast_bmin[3] = {0, 0, 0}, fast_bmax[3] = {0, 0, 0};
-    bool fast_ready = false;
-    float fast_build_ms = 0.0f;
-    const char* fast_builder = "";  // which builder produced the fast tree ("host-sah" / "device-ploc" / "device-lbvh")
-    DevBuf<rb::ChunkNode> chunk_nodes; // the chunked walk (rb_internal.hpp, ChunkTree)
-    DevBuf<float> chunk_a, chunk_b, chunk_c;
-    DevBuf<uint32_t> chunk_rank_slot;
-    DevBuf<uint32_t> chunk_pos_slot, chunk_pos_rank;   // chunk order -> slot / rank: read by the gather at build time, kept for rb_debug_engine_chunk_tree
-    size_t chunk_n_nodes = 0;
-    const char* chunk_builder = "";   // "device" | "host"
-    uint32_t chunk_root = 0, chunk_depth = 0;
-    bool chunk_ready = false;
-    float chunk_build_ms = 0.0f;
-    // The host's copy of the mesh, for the host builders and the checkers.  A large mesh (>= kChunkDeviceBuildMin elements: the
-    // device builder's territory) is NOT copied at rb_update -- a second 88 MB in host memory cost C5's update 10 of its 14 ms --
-    // but fetched back from the device buffer if a host builder turns out to be needed after all (ensure_host_mesh).
-    std::vector<rb_gpu_triangle> host_tris;
-    std::vector<uint32_t> host_indices;
-    size_t host_tri_len = 0, host_index_len = 0;   // what the vectors hold, or would hold (0: the engine keeps no copy)
-    bool host_tris_stale = false, host_indices_stale = false;
-    DevBuf<rb::SphereNode4> sph_nodes;  // own sphere acceleration structure (n_spheres > threshold)
-    DevBuf<float> sph_leaf;
-    DevBuf<uint32_t> sph_id;
-    uint32_t sph_root = 0, sph_depth = 0;
-    bool sph_bvh = false;
-    bool stack_depth_covers = true;    // set with KParams::stack_depth: every walk in use fits its LDS column
-    const char* sph_builder = "";      // "device-median" | "host-median" | "" (linear scan)
-    float sph_build_ms = 0.0f;
-    DevBuf<float> colors;            // RB_KERNEL_STREAM: float4 per (pixel, sample) of one launch chunk
-    uint64_t color_budget = 0;       // bytes `colors` may take (0 = ask the device at the next dispatch)
-    uint32_t bvh_stack = 0;          // traversal-stack entries the current tree needs
-
-    std::vector<rb_bvh_node> host_nodes;  // kept for validation when nodes/indices change separately
-    const char* tree_builder = "";         // who made the reference-layout tree: "device" | "host" (RB_FLAG_BUILD_TREE*) | "caller"
-    float tree_build_ms = 0.0f;
-    uint32_t width = 0, height = 0, local_rows = 0, padded_rows = 0;
-
-    rb_stats stats{};
-    float last_dispatch_ms = 0.0f;
-    uint32_t last_launches = 0;
-    bool timing_pending = false;
-    uint32_t max_mesh_index = 0;  // over the uploaded triangles
-
-    // ---- several devices behind one handle (rb_create_multi): this engine only coordinates; every part is a
-    // complete engine for one shard on one device.  Or one process per device (rb_comm_init_rank): this engine
-    // is shard `opt.shard_rank` and `net` holds its communicator.
-    std::vector<std::unique_ptr<rb_engine>> parts;
-    rb::Gather net;
-};
-
-namespace {
-
-int fail(const rb_engine* e, int code, const char* fmt, ...) {
+int rb::fail(const rb_engine* e, int code, const char* fmt, ...) {
     char buf[512];
     va_list ap;
     va_start(ap, fmt);
@@ -199,12 +42,7 @@ int fail(const rb_engine* e, int code, const char* fmt, ...) {
     return code;
 }
 
-#define HIP_TRY(e, call)                                                                          \
-    do {                                                                                          \
-        hipError_t _st = (call);                                                                  \
-        if (_st != hipSuccess)                                                                    \
-            return fail((e), RB_ERR_DEVICE, "%s failed: %s", #call, hipGetErrorString(_st));      \
-    } while (0)
+namespace {
 
 const char* kFieldNames[9] = {"uniforms", "spheres", "uvs", "meshes", "lights",
                               "bvh_nodes", "bvh_indices", "bvh_triangles", "textures"};
@@ -216,26 +54,26 @@ const rb_field* field_at(const rb_config* c, int i) {
 }
 
 int check_fields(rb_engine* e, const rb_config* cfg) {
-    if (!cfg) return fail(e, RB_ERR_NULL_ARGUMENT, "config is NULL");
+    if (!cfg) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "config is NULL");
     for (int i = 0; i < 9; ++i) {
         const rb_field* f = field_at(cfg, i);
-        if (f->change > RB_DELETE) return fail(e, RB_ERR_NULL_ARGUMENT, "%s: bad change tag %u", kFieldNames[i], f->change);
+        if (f->change > RB_DELETE) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "%s: bad change tag %u", kFieldNames[i], f->change);
         if ((f->change == RB_CREATE || f->change == RB_UPDATE) && f->count > 0 && !f->ptr)
-            return fail(e, RB_ERR_NULL_ARGUMENT, "%s: count %zu with NULL pointer", kFieldNames[i], f->count);
+            return rb::fail(e, RB_ERR_NULL_ARGUMENT, "%s: count %zu with NULL pointer", kFieldNames[i], f->count);
     }
     if ((cfg->uniforms.change == RB_CREATE || cfg->uniforms.change == RB_UPDATE) && cfg->uniforms.count != 1)
-        return fail(e, RB_ERR_INVALID_UNIFORMS, "uniforms: expected exactly one rb_uniforms, got %zu", cfg->uniforms.count);
+        return rb::fail(e, RB_ERR_INVALID_UNIFORMS, "uniforms: expected exactly one rb_uniforms, got %zu", cfg->uniforms.count);
     return RB_OK;
 }
 
 // RenderConfig::validate_init -- render_config.rs:163-185
 int validate_init(rb_engine* e, const rb_config* c) {
-    if (c->uniforms.change != RB_CREATE) return fail(e, RB_ERR_INVALID_UNIFORMS, "Invalid Uniforms");
-    if (c->spheres.change != RB_CREATE) return fail(e, RB_ERR_INVALID_SPHERES, "Invalid Spheres");
-    if (c->uvs.change != RB_CREATE) return fail(e, RB_ERR_INVALID_UVS, "Invalid UVs");
-    if (c->meshes.change != RB_CREATE) return fail(e, RB_ERR_INVALID_MESHES, "Invalid Meshes");
-    if (c->lights.change != RB_CREATE) return fail(e, RB_ERR_INVALID_LIGHTS, "Invalid Lights");
-    if (c->textures.change != RB_CREATE) return fail(e, RB_ERR_INVALID_TEXTURES, "Invalid Textures");
+    if (c->uniforms.change != RB_CREATE) return rb::fail(e, RB_ERR_INVALID_UNIFORMS, "Invalid Uniforms");
+    if (c->spheres.change != RB_CREATE) return rb::fail(e, RB_ERR_INVALID_SPHERES, "Invalid Spheres");
+    if (c->uvs.change != RB_CREATE) return rb::fail(e, RB_ERR_INVALID_UVS, "Invalid UVs");
+    if (c->meshes.change != RB_CREATE) return rb::fail(e, RB_ERR_INVALID_MESHES, "Invalid Meshes");
+    if (c->lights.change != RB_CREATE) return rb::fail(e, RB_ERR_INVALID_LIGHTS, "Invalid Lights");
+    if (c->textures.change != RB_CREATE) return rb::fail(e, RB_ERR_INVALID_TEXTURES, "Invalid Textures");
     return RB_OK;
 }
 
@@ -246,53 +84,36 @@ int validate(rb_engine* e, const rb_config* c) {
     if (has_data(c->uniforms)) {
         const rb_uniforms* u = static_cast<const rb_uniforms*>(c->uniforms.ptr);
         if (!(u->camera.pane_distance >= 0.0f && u->camera.pane_distance <= 100.0f))
-            return fail(e, RB_ERR_PANE_DISTANCE_OUT_OF_BOUNDS, "Pane-Distance is out of bounds");
+            return rb::fail(e, RB_ERR_PANE_DISTANCE_OUT_OF_BOUNDS, "Pane-Distance is out of bounds");
         if (!(u->camera.pane_width >= 0.0f && u->camera.pane_width <= 1000.0f))
-            return fail(e, RB_ERR_PANE_WIDTH_OUT_OF_BOUNDS, "Pane-Distance is out of bounds");  // sic, :631-633
+            return rb::fail(e, RB_ERR_PANE_WIDTH_OUT_OF_BOUNDS, "Pane-Distance is out of bounds");  // sic, :631-633
         const float* d = u->camera.dir;
         const float len_sq = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
-        if (len_sq < 1.1920929e-07f) return fail(e, RB_ERR_INVALID_CAMERA_DIRECTION, "Invalid camera direction");
+        if (len_sq < 1.1920929e-07f) return rb::fail(e, RB_ERR_INVALID_CAMERA_DIRECTION, "Invalid camera direction");
     } else if (c->uniforms.change == RB_DELETE) {
-        return fail(e, RB_ERR_CANNOT_DELETE_NONEXISTENT, "Cannot delete none existent");
+        return rb::fail(e, RB_ERR_CANNOT_DELETE_NONEXISTENT, "Cannot delete none existent");
     }
     if (has_data(c->spheres)) {
         const rb_sphere* s = static_cast<const rb_sphere*>(c->spheres.ptr);
         for (size_t i = 0; i < c->spheres.count; ++i)
-            if (s[i].radius <= 0.0f) return fail(e, RB_ERR_INVALID_SPHERES, "Invalid Spheres");
+            if (s[i].radius <= 0.0f) return rb::fail(e, RB_ERR_INVALID_SPHERES, "Invalid Spheres");
     }
     if (has_data(c->uvs)) {
-        if (c->uvs.count % 2 != 0) return fail(e, RB_ERR_INVALID_UVS, "Invalid UVs");
+        if (c->uvs.count % 2 != 0) return rb::fail(e, RB_ERR_INVALID_UVS, "Invalid UVs");
     } else if (c->uvs.change == RB_DELETE) {
-        return fail(e, RB_ERR_UNSUPPORTED_DELETE, "not yet implemented: Implement UVs Deletion");
+        return rb::fail(e, RB_ERR_UNSUPPORTED_DELETE, "not yet implemented: Implement UVs Deletion");
     }
     if (c->meshes.change == RB_DELETE)
-        return fail(e, RB_ERR_UNSUPPORTED_DELETE, "not yet implemented: Implement meshes Deletion");
+        return rb::fail(e, RB_ERR_UNSUPPORTED_DELETE, "not yet implemented: Implement meshes Deletion");
     if (has_data(c->lights)) {
         const rb_point_light* l = static_cast<const rb_point_light*>(c->lights.ptr);
         for (size_t i = 0; i < c->lights.count; ++i)
-            if (l[i].radius <= 0.0f) return fail(e, RB_ERR_INVALID_LIGHTS, "Invalid Lights");
+            if (l[i].radius <= 0.0f) return rb::fail(e, RB_ERR_INVALID_LIGHTS, "Invalid Lights");
     } else if (c->lights.change == RB_DELETE) {
-        return fail(e, RB_ERR_UNSUPPORTED_DELETE, "not yet implemented: Implement lights Deletion");
+        return rb::fail(e, RB_ERR_UNSUPPORTED_DELETE, "not yet implemented: Implement lights Deletion");
     }
     if (c->textures.change == RB_DELETE)
-        return fail(e, RB_ERR_UNSUPPORTED_DELETE, "not yet implemented: Implement textures Deletion");
-    return RB_OK;
-}
-
-// create_storage_buffer -- buffers.rs:232-249: an empty slice still allocates one
-// zero-filled element (wgpu zero-initialises), so arrayLength() is 1.
-// The copy is queued on the engine's stream from caller memory: every path that calls this ends in
-// update_locked's hipStreamSynchronize (or an earlier one) before the caller gets its buffers back.
-template <typename T>
-int upload(rb_engine* e, DevBuf<T>& buf, const void* src, size_t count, uint32_t* visible_len, bool pad_empty) {
-    const size_t alloc = (count == 0 && pad_empty) ? 1 : count;
-    HIP_TRY(e, buf.resize(alloc));
-    if (count > 0) {
-        HIP_TRY(e, hipMemcpyAsync(buf.ptr, src, count * sizeof(T), hipMemcpyHostToDevice, e->stream));
-    } else if (alloc > 0) {
-        HIP_TRY(e, hipMemsetAsync(buf.ptr, 0, alloc * sizeof(T), e->stream));
-    }
-    if (visible_len) *visible_len = static_cast<uint32_t>(alloc);
+        return rb::fail(e, RB_ERR_UNSUPPORTED_DELETE, "not yet implemented: Implement textures Deletion");
     return RB_OK;
 }
 
@@ -318,12 +139,12 @@ StripeGeometry stripe_geometry(const rb_options& opt, uint32_t h) {
 int resize_frame(rb_engine* e, uint32_t w, uint32_t h) {
     const StripeGeometry g = stripe_geometry(e->opt, h);
     const uint64_t px = static_cast<uint64_t>(w) * g.padded;
-    if (px >= (1ull << 31)) return fail(e, RB_ERR_INVALID_UNIFORMS, "frame of %u x %u pixels is too large", w, h);
+    if (px >= (1ull << 31)) return rb::fail(e, RB_ERR_INVALID_UNIFORMS, "frame of %u x %u pixels is too large", w, h);
     e->spec_valid = false;
     e->cur = 0;
     e->slot[1].accum.release();   // the run-ahead slot is (re)allocated when the iterator first needs it
     e->slot[1].rgba.release();
-    FrameSlot& s = e->slot[0];
+    rb::FrameSlot& s = e->slot[0];
     HIP_TRY(e, s.accum.resize(px * 4));
     HIP_TRY(e, s.rgba.resize(px));
     if (px) {
@@ -348,9 +169,9 @@ int upload_textures(rb_engine* e, const rb_field& f) {
         data.insert(data.end(), t[i].rgba_data, t[i].rgba_data + n);
         offset += t[i].width * t[i].height;
     }
-    int rc = upload(e, e->tex_data, data.data(), data.size(), nullptr, true);
+    int rc = rb::upload(e, e->tex_data, data.data(), data.size(), nullptr, true);
     if (rc) return rc;
-    rc = upload(e, e->tex_info, info.data(), info.size(), nullptr, true);
+    rc = rb::upload(e, e->tex_info, info.data(), info.size(), nullptr, true);
     if (rc) return rc;
     HIP_TRY(e, hipStreamSynchronize(e->stream));  // `data`/`info` are locals
     e->n_tex = static_cast<uint32_t>(f.count);
@@ -360,59 +181,7 @@ int upload_textures(rb_engine* e, const rb_field& f) {
 int prep_materials(rb_engine* e, rb_material* first, size_t stride, size_t n) {
     if (!first || n == 0) return RB_OK;
     int rc = rb::launch_prep_materials(first, static_cast<uint32_t>(stride), static_cast<uint32_t>(n), e->stream);
-    if (rc) return fail(e, RB_ERR_DEVICE, "material prep launch failed: %s", hipGetErrorString(static_cast<hipError_t>(rc)));
-    return RB_OK;
-}
-
-// Spheres beyond kSphereBvhThreshold get the library's own acceleration structure; the
-// reference's linear scan (shader.wgsl:574-586) stays the rule for small counts.  From kSphereDeviceBuildMin spheres
-// up the tree is made on the device from the copy that is already there (rb_build.hip: the same median splits, one
-// segmented sort per level; 10^6 spheres in milliseconds where the host takes 0.1 s);
-// RB_FLAG_SPHERE_TREE_HOST / RB_FLAG_SPHERE_TREE_DEVICE force either builder.  The frame does not depend on which one ran.
-int build_sphere_bvh(rb_engine* e, const rb_sphere* s, size_t n) {
-    e->sph_bvh = false;
-    e->sph_builder = "";
-    if (n <= rb::kSphereBvhThreshold || n >= (1u << 27) || (e->opt.flags & RB_FLAG_NO_SPHERE_BVH)) return RB_OK;
-    const auto t_begin = std::chrono::steady_clock::now();
-    const bool force_host = (e->opt.flags & RB_FLAG_SPHERE_TREE_HOST) != 0u, force_dev = (e->opt.flags & RB_FLAG_SPHERE_TREE_DEVICE) != 0u;
-    if (!force_host && (force_dev || n >= rb::kSphereDeviceBuildMin)) {
-        HIP_TRY(e, e->sph_nodes.resize(rb::sphere_tree_node_capacity(n)));
-        HIP_TRY(e, e->sph_leaf.resize(n * 4));
-        HIP_TRY(e, e->sph_id.resize(n));
-        rb::DeviceSphereTreeInfo info{};
-        const int rc = rb::device_sphere_bvh_build(e->spheres.ptr, static_cast<uint32_t>(n), e->sph_nodes.ptr, e->sph_leaf.ptr, e->sph_id.ptr,
-                                                   &info, e->stream);
-        if (rc) return fail(e, RB_ERR_DEVICE, "device sphere tree build failed: %s", hipGetErrorString(static_cast<hipError_t>(rc)));
-        if (rb::sphere_stack_entries(info.depth) > rb::kStackDepth) return RB_OK;   // beyond 16 M spheres: the scan (the host's tree is as deep)
-        e->sph_root = info.root;
-        e->sph_depth = rb::sphere_stack_entries(info.depth);
-        e->sph_bvh = true;
-        e->sph_builder = "device-median";
-        e->sph_build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-        return RB_OK;
-    }
-    std::vector<rb::SphereNode4> nodes;
-    std::vector<uint32_t> order;
-    uint32_t levels4 = 0;
-    rb::sphere_bvh_build(s, n, nodes, order, &e->sph_root, &levels4);
-    if (rb::sphere_stack_entries(levels4) > rb::kStackDepth) return RB_OK;
-    e->sph_depth = rb::sphere_stack_entries(levels4);
-    std::vector<float> leaf(n * 4);
-    for (size_t j = 0; j < n; ++j) {
-        const rb_sphere& sp = s[order[j]];
-        leaf[j * 4 + 0] = sp.center[0];
-        leaf[j * 4 + 1] = sp.center[1];
-        leaf[j * 4 + 2] = sp.center[2];
-        leaf[j * 4 + 3] = sp.radius;
-    }
-    int rc = upload(e, e->sph_nodes, nodes.data(), nodes.size(), nullptr, true);
-    if (!rc) rc = upload(e, e->sph_leaf, leaf.data(), leaf.size(), nullptr, true);
-    if (!rc) rc = upload(e, e->sph_id, order.data(), order.size(), nullptr, true);
-    if (rc) return rc;
-    HIP_TRY(e, hipStreamSynchronize(e->stream));  // the vectors above are locals
-    e->sph_bvh = true;
-    e->sph_builder = "host-median";
-    e->sph_build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    if (rc) return rb::fail(e, RB_ERR_DEVICE, "material prep launch failed: %s", hipGetErrorString(static_cast<hipError_t>(rc)));
     return RB_OK;
 }
 
@@ -428,31 +197,6 @@ Act field_action(int idx, const rb_field& f, bool first) {
     return Act::None;
 }
 
-// RB_FLAG_BUILD_TREE / _HOST: the engine makes the reference-layout tree from the triangles itself
-bool builds_tree(const rb_engine* e) { return (e->opt.flags & (RB_FLAG_BUILD_TREE | RB_FLAG_BUILD_TREE_HOST)) != 0u; }
-// may the library's own tree be wanted for this engine's meshes?  (host copies of triangles / indices are kept then)
-bool may_want_own_tree(const rb_engine* e) { return !(e->opt.flags & RB_FLAG_REFERENCE_WALK); }
-// a mesh of `n` elements whose host copy can wait (ensure_host_mesh): large enough for the device builder, and no flag that
-// sends the build to a host builder anyway
-bool host_copy_can_wait(const rb_engine* e, size_t n) {
-    return n >= rb::kChunkDeviceBuildMin && !(e->opt.flags & (RB_FLAG_CHUNK_TREE_HOST | RB_FLAG_FAST_BVH | RB_FLAG_HOST_BVH | RB_FLAG_DEVICE_BVH));
-}
-// is it wanted for a mesh of n_tris triangles?
-bool wants_own_tree(const rb_engine* e, uint32_t n_tris) {   // (asked only when the chunked walk is not in use)
-    if (e->opt.flags & RB_FLAG_REFERENCE_WALK) return false;
-    if (e->opt.flags & (RB_FLAG_FAST_BVH | RB_FLAG_DEVICE_BVH | RB_FLAG_HOST_BVH)) return true;
-    return n_tris >= rb::kOwnTreeDefaultMinTriangles;
-}
-
-// The chunked walk (k_trace_chunk) is the walk of every multi-node mesh unless the caller names another one: it is
-// the fastest exact walk at every size measured (profiles/r03_walks.txt: 576 to 1 048 578 triangles).
-bool wants_chunk_walk(const rb_engine* e) {
-    const uint32_t kern = e->opt.kernel ? e->opt.kernel : RB_KERNEL_STREAM;
-    if (kern != RB_KERNEL_STREAM) return false;   // the one-pixel-per-lane dispatch shapes walk per segment
-    if (e->opt.flags & RB_FLAG_CHUNK_WALK) return true;
-    return !(e->opt.flags & (RB_FLAG_REFERENCE_WALK | RB_FLAG_FAST_BVH | RB_FLAG_DEVICE_BVH | RB_FLAG_HOST_BVH));
-}
-
 int apply_field(rb_engine* e, int idx, const rb_field& f, bool first) {
     const Act act = field_action(idx, f, first);
     if (act == Act::None) return RB_OK;
@@ -462,48 +206,47 @@ int apply_field(rb_engine* e, int idx, const rb_field& f, bool first) {
     int rc = RB_OK;
     switch (idx) {
         case 1:
-            rc = upload(e, e->spheres, src, n, nullptr, true);
+            rc = rb::upload(e, e->spheres, src, n, nullptr, true);
             e->n_spheres = static_cast<uint32_t>(n);
             if (!rc) rc = prep_materials(e, e->spheres.ptr ? &e->spheres.ptr->material : nullptr, sizeof(rb_sphere), n);
-            if (!rc) rc = build_sphere_bvh(e, static_cast<const rb_sphere*>(src), n);
+            if (!rc) rc = rb::build_sphere_bvh(e, static_cast<const rb_sphere*>(src), n);
             break;
-        case 2: rc = upload(e, e->uvs, src, n, nullptr, true); e->n_uvs = static_cast<uint32_t>(n); break;
+        case 2: rc = rb::upload(e, e->uvs, src, n, nullptr, true); e->n_uvs = static_cast<uint32_t>(n); break;
         case 3:
-            rc = upload(e, e->meshes, src, n, nullptr, true);
+            rc = rb::upload(e, e->meshes, src, n, nullptr, true);
             e->n_meshes = static_cast<uint32_t>(n);
             if (!rc) rc = prep_materials(e, e->meshes.ptr ? &e->meshes.ptr->material : nullptr, sizeof(rb_mesh), n);
             break;
         case 4:
             // delete_lights creates a 4-byte buffer (buffers.rs:389-391): arrayLength() == 0
-            rc = upload(e, e->lights, src, n, &e->n_lights, !del);
+            rc = rb::upload(e, e->lights, src, n, &e->n_lights, !del);
             if (del) e->n_lights = 0;
             if (!rc) rc = prep_materials(e, e->lights.ptr ? &e->lights.ptr->material : nullptr, sizeof(rb_point_light), e->n_lights);
             break;
         case 5:
-            rc = upload(e, e->nodes, src, n, nullptr, true);
+            rc = rb::upload(e, e->nodes, src, n, nullptr, true);
             e->n_nodes = static_cast<uint32_t>(n);
             e->host_nodes.assign(static_cast<const rb_bvh_node*>(src), static_cast<const rb_bvh_node*>(src) + n);
             e->prep_dirty = true;
-            e->tree_builder = n ? "caller" : "";
-            e->tree_build_ms = 0.0f;
+            e->tree = {n ? "caller" : "", 0.0f};
             break;
         case 6:
-            rc = upload(e, e->indices, src, n, &e->n_indices, true);
+            rc = rb::upload(e, e->indices, src, n, &e->n_indices, true);
             e->prep_dirty = true;
-            if (may_want_own_tree(e)) {
+            if (rb::mesh_walks(e->opt).host_mesh) {
                 e->host_index_len = n;
-                e->host_indices_stale = host_copy_can_wait(e, n);
+                e->host_indices_stale = rb::host_copy_can_wait(e, n);
                 if (e->host_indices_stale) std::vector<uint32_t>().swap(e->host_indices);
                 else e->host_indices.assign(static_cast<const uint32_t*>(src), static_cast<const uint32_t*>(src) + n);
             }
             break;
         case 7:
-            rc = upload(e, e->tris, src, n, nullptr, true);
+            rc = rb::upload(e, e->tris, src, n, nullptr, true);
             e->n_tris = static_cast<uint32_t>(n);
             e->prep_dirty = true;
-            if (may_want_own_tree(e)) {
+            if (rb::mesh_walks(e->opt).host_mesh) {
                 e->host_tri_len = n;
-                e->host_tris_stale = host_copy_can_wait(e, n);
+                e->host_tris_stale = rb::host_copy_can_wait(e, n);
                 if (e->host_tris_stale) std::vector<rb_gpu_triangle>().swap(e->host_tris);
                 else e->host_tris.assign(static_cast<const rb_gpu_triangle*>(src), static_cast<const rb_gpu_triangle*>(src) + n);
             }
@@ -532,15 +275,15 @@ int validate_scene(rb_engine* e, const rb_config* cfg, bool first, ScenePlan& pl
     const rb_bvh_node* nodes = e->host_nodes.data();
     uint32_t n_nodes = static_cast<uint32_t>(e->host_nodes.size());
     rb::TreeSkeleton own;   // RB_FLAG_BUILD_TREE: the tree the engine will build -- its shape follows from the triangle count
-    const bool own_tree = builds_tree(e);
+    const bool own_tree = rb::builds_tree(e);
     if (own_tree && (cfg->bvh_nodes.change != RB_KEEP || cfg->bvh_indices.change != RB_KEEP))
-        return fail(e, RB_ERR_INVALID_BVH, "the engine builds the tree itself (RB_FLAG_BUILD_TREE): bvh_nodes and bvh_indices must be Keep");
+        return rb::fail(e, RB_ERR_INVALID_BVH, "the engine builds the tree itself (RB_FLAG_BUILD_TREE): bvh_nodes and bvh_indices must be Keep");
     if (own_tree && a_tris == Act::Take) {
         const rb_gpu_triangle* t = static_cast<const rb_gpu_triangle*>(cfg->bvh_triangles.ptr);
-        if (cfg->bvh_triangles.count >= (1ull << 31)) return fail(e, RB_ERR_INVALID_BVH, "too many triangles");
+        if (cfg->bvh_triangles.count >= (1ull << 31)) return rb::fail(e, RB_ERR_INVALID_BVH, "too many triangles");
         const size_t bad = rb::first_non_finite(t, cfg->bvh_triangles.count);
         if (bad < cfg->bvh_triangles.count)
-            return fail(e, RB_ERR_INVALID_BVH, "triangle %zu has a non-finite vertex coordinate", bad);
+            return rb::fail(e, RB_ERR_INVALID_BVH, "triangle %zu has a non-finite vertex coordinate", bad);
         rb::bvh_skeleton(cfg->bvh_triangles.count, own);
         nodes = own.nodes.data();
         n_nodes = static_cast<uint32_t>(own.nodes.size());
@@ -548,7 +291,7 @@ int validate_scene(rb_engine* e, const rb_config* cfg, bool first, ScenePlan& pl
         n_nodes = 0;
     } else if (a_nodes == Act::Take) {
         nodes = static_cast<const rb_bvh_node*>(cfg->bvh_nodes.ptr);
-        if (cfg->bvh_nodes.count >= (1ull << 31)) return fail(e, RB_ERR_INVALID_BVH, "too many BVH nodes");
+        if (cfg->bvh_nodes.count >= (1ull << 31)) return rb::fail(e, RB_ERR_INVALID_BVH, "too many BVH nodes");
         n_nodes = static_cast<uint32_t>(cfg->bvh_nodes.count);
     } else if (a_nodes == Act::Delete) {
         n_nodes = 0;
@@ -558,17 +301,17 @@ int validate_scene(rb_engine* e, const rb_config* cfg, bool first, ScenePlan& pl
     else if (a_idx == Act::Delete) index_len = 1;
     if (own_tree && a_tris == Act::Take) index_len = std::max<uint64_t>(cfg->bvh_triangles.count, 1);
     else if (own_tree && a_tris == Act::Delete) index_len = 1;
-    if (index_len >= (1ull << 31)) return fail(e, RB_ERR_INVALID_BVH, "too many BVH indices");
+    if (index_len >= (1ull << 31)) return rb::fail(e, RB_ERR_INVALID_BVH, "too many BVH indices");
     plan.bvh_stack = e->bvh_stack;
     if (n_nodes > 0) {
         std::string why;
         uint32_t depth = 0;
-        if (!rb::bvh_validate(nodes, n_nodes, rb::kStackDepth, why, &depth)) return fail(e, RB_ERR_INVALID_BVH, "%s", why.c_str());
+        if (!rb::bvh_validate(nodes, n_nodes, rb::kStackDepth, why, &depth)) return rb::fail(e, RB_ERR_INVALID_BVH, "%s", why.c_str());
         plan.bvh_stack = depth;
         for (uint32_t i = 0; i < n_nodes; ++i) {
             const rb_bvh_node& n = nodes[i];
             if (n.primitive_count > 0 && static_cast<uint64_t>(n.first_primitive) + n.primitive_count > index_len)
-                return fail(e, RB_ERR_INVALID_BVH, "leaf %u covers [%u, +%u) of %llu bvh_indices", i, n.first_primitive,
+                return rb::fail(e, RB_ERR_INVALID_BVH, "leaf %u covers [%u, +%u) of %llu bvh_indices", i, n.first_primitive,
                             n.primitive_count, static_cast<unsigned long long>(index_len));
         }
     }
@@ -581,7 +324,7 @@ int validate_scene(rb_engine* e, const rb_config* cfg, bool first, ScenePlan& pl
         for (size_t i = 0; i < cfg->bvh_triangles.count; ++i) mx = std::max(mx, t[i].mesh_index);
         plan.max_mesh_index = mx;
         n_tris = cfg->bvh_triangles.count;
-        if (n_tris >= (1ull << 31)) return fail(e, RB_ERR_INVALID_BVH, "too many triangles");
+        if (n_tris >= (1ull << 31)) return rb::fail(e, RB_ERR_INVALID_BVH, "too many triangles");
     } else if (a_tris == Act::Delete) {
         n_tris = 0;
         plan.max_mesh_index = 0;
@@ -591,25 +334,23 @@ int validate_scene(rb_engine* e, const rb_config* cfg, bool first, ScenePlan& pl
     const uint32_t color_hash = take_uniforms ? static_cast<const rb_uniforms*>(cfg->uniforms.ptr)->color_hash_enabled
                                               : e->uniforms.color_hash_enabled;
     if (n_tris > 0 && color_hash == 0 && plan.max_mesh_index >= n_meshes)
-        return fail(e, RB_ERR_INVALID_MESHES, "a triangle references mesh %u of %llu", plan.max_mesh_index,
+        return rb::fail(e, RB_ERR_INVALID_MESHES, "a triangle references mesh %u of %llu", plan.max_mesh_index,
                     static_cast<unsigned long long>(n_meshes));
     // ---- textures and the frame
     if (field_action(8, cfg->textures, first) == Act::Take) {
         const rb_texture* t = static_cast<const rb_texture*>(cfg->textures.ptr);
         for (size_t i = 0; i < cfg->textures.count; ++i) {
-            if (t[i].width == 0 || t[i].height == 0) return fail(e, RB_ERR_INVALID_TEXTURES, "texture %zu is empty", i);
-            if (!t[i].rgba_data) return fail(e, RB_ERR_INVALID_TEXTURES, "texture %zu has no data", i);
+            if (t[i].width == 0 || t[i].height == 0) return rb::fail(e, RB_ERR_INVALID_TEXTURES, "texture %zu is empty", i);
+            if (!t[i].rgba_data) return rb::fail(e, RB_ERR_INVALID_TEXTURES, "texture %zu has no data", i);
         }
     }
     if (take_uniforms) {
         const rb_uniforms* u = static_cast<const rb_uniforms*>(cfg->uniforms.ptr);
         const uint64_t px = static_cast<uint64_t>(u->width) * stripe_geometry(e->opt, u->height).padded;
-        if (px >= (1ull << 31)) return fail(e, RB_ERR_INVALID_UNIFORMS, "frame of %u x %u pixels is too large", u->width, u->height);
+        if (px >= (1ull << 31)) return rb::fail(e, RB_ERR_INVALID_UNIFORMS, "frame of %u x %u pixels is too large", u->width, u->height);
     }
     return RB_OK;
 }
-
-void set_device(const rb_engine* e) { (void)hipSetDevice(e->device); }
 
 // update_uniforms count patch-up -- gpu_wrapper.rs:475-495: Create/Update overwrite the count with the
 // vector length, Delete zeroes it, Keep leaves the caller's value (clamped to the buffer here so that a
@@ -618,25 +359,6 @@ uint32_t patch_count(uint32_t change, uint32_t given, uint32_t len) {
     if (change == RB_CREATE || change == RB_UPDATE) return len;
     if (change == RB_DELETE) return 0u;
     return std::min(given, len);
-}
-
-// The host builders and checkers read host_tris / host_indices: bring back what rb_update left on the device only.
-int ensure_host_mesh(rb_engine* e) {
-    if (!e->host_tris_stale && !e->host_indices_stale) return RB_OK;
-    HIP_TRY(e, hipStreamSynchronize(e->stream));
-    if (e->host_tris_stale) {
-        if (e->host_tri_len > e->tris.count) return fail(e, RB_ERR_DEVICE, "the triangle buffer is shorter than the mesh it was made from");
-        e->host_tris.resize(e->host_tri_len);
-        HIP_TRY(e, hipMemcpy(e->host_tris.data(), e->tris.ptr, sizeof(rb_gpu_triangle) * e->host_tri_len, hipMemcpyDeviceToHost));
-        e->host_tris_stale = false;
-    }
-    if (e->host_indices_stale) {
-        if (e->host_index_len > e->indices.count) return fail(e, RB_ERR_DEVICE, "the index buffer is shorter than the mesh it was made from");
-        e->host_indices.resize(e->host_index_len);
-        HIP_TRY(e, hipMemcpy(e->host_indices.data(), e->indices.ptr, 4u * e->host_index_len, hipMemcpyDeviceToHost));
-        e->host_indices_stale = false;
-    }
-    return RB_OK;
 }
 
 int ensure_prepared(rb_engine* e) {
@@ -648,157 +370,13 @@ int ensure_prepared(rb_engine* e) {
     HIP_TRY(e, e->ptris.resize(len));
     HIP_TRY(e, e->pshade.resize(len));
     int rc = rb::launch_prep_tris(e->tris.ptr, tri_count, e->indices.ptr, len, e->ptris.ptr, e->pshade.ptr, e->stream);
-    if (rc) return fail(e, RB_ERR_DEVICE, "prep kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(rc)));
+    if (rc) return rb::fail(e, RB_ERR_DEVICE, "prep kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(rc)));
     e->prep_dirty = false;
     e->prep_tri_count = tri_count;
-    // ---- the chunked walk's tree: the caller's tree with the library's own levels below its leaves
-    e->chunk_ready = false;
-    e->fast_ready = false;
-    if (wants_chunk_walk(e) && e->host_nodes.size() > 1 && e->host_tri_len > 0 && e->host_index_len > 0 && tri_count > 0) {
-        const auto t_begin = std::chrono::steady_clock::now();
-        const uint32_t n_tris = std::min<uint32_t>(tri_count, static_cast<uint32_t>(e->host_tri_len));
-        const uint32_t n_idx = static_cast<uint32_t>(e->host_index_len), n_nodes = static_cast<uint32_t>(e->host_nodes.size());
-        // which builder: the device one from kChunkDeviceBuildMin slots up (one block per reference leaf; C5's 10^6 triangles
-        // in a few ms where the host's threads take 11-15), the host's below; either can be forced.  Same walk, same frames.
-        const bool force_host = (e->opt.flags & RB_FLAG_CHUNK_TREE_HOST) != 0u, force_dev = (e->opt.flags & RB_FLAG_CHUNK_TREE_DEVICE) != 0u;
-        bool built = false;
-        size_t n = 0;
-        e->chunk_builder = "";
-        if (!force_host && (force_dev || n_idx >= rb::kChunkDeviceBuildMin) && n_idx <= e->indices.count && n_tris <= e->tris.count) {
-            rb::DeviceChunkTree dt;
-            const int brc = rb::device_chunk_tree_build(e->tris.ptr, n_tris, e->indices.ptr, n_idx, e->host_nodes.data(), n_nodes, rb::kStackDepth, &dt, e->stream);
-            if (brc > 0) return fail(e, RB_ERR_DEVICE, "chunk tree build failed: %s", hipGetErrorString(static_cast<hipError_t>(brc)));
-            if (brc == 0) {
-                e->chunk_nodes.adopt(dt.nodes, dt.nodes_capacity);
-                e->chunk_rank_slot.adopt(dt.rank_slot, dt.n_pos);
-                e->chunk_pos_slot.adopt(dt.pos_slot, dt.n_pos);
-                e->chunk_pos_rank.adopt(dt.pos_rank, dt.n_pos);
-                e->chunk_n_nodes = dt.n_nodes;
-                e->chunk_root = dt.root;
-                e->chunk_depth = dt.depth;
-                n = dt.n_pos;
-                built = true;
-                e->chunk_builder = "device";
-            }
-        }
-        if (!built) {
-            rb::ChunkTree ct;
-            rc = ensure_host_mesh(e);
-            if (rc) return rc;
-            if (rb::chunk_tree_build(e->host_tris.data(), n_tris, e->host_indices.data(), n_idx, e->host_nodes.data(), n_nodes, rb::kStackDepth, ct)) {
-                n = ct.pos_slot.size();
-                rc = upload(e, e->chunk_nodes, ct.nodes.data(), ct.nodes.size(), nullptr, true);
-                if (!rc) rc = upload(e, e->chunk_rank_slot, ct.rank_slot.data(), ct.rank_slot.size(), nullptr, true);
-                if (!rc) rc = upload(e, e->chunk_pos_slot, ct.pos_slot.data(), n, nullptr, true);
-                if (!rc) rc = upload(e, e->chunk_pos_rank, ct.pos_rank.data(), n, nullptr, true);
-                if (rc) return rc;
-                HIP_TRY(e, hipStreamSynchronize(e->stream));  // `ct` is a local
-                e->chunk_n_nodes = ct.nodes.size();
-                e->chunk_root = ct.root;
-                e->chunk_depth = ct.depth;
-                built = true;
-                e->chunk_builder = "host";
-            }
-        }
-        if (built) {
-            HIP_TRY(e, e->chunk_a.resize(n * 4));
-            HIP_TRY(e, e->chunk_b.resize(n * 4));
-            HIP_TRY(e, e->chunk_c.resize(n * 4));
-            rc = rb::launch_chunk_gather(e->ptris.ptr, e->chunk_pos_slot.ptr, e->chunk_pos_rank.ptr, static_cast<uint32_t>(n), e->chunk_a.ptr, e->chunk_b.ptr,
-                                         e->chunk_c.ptr, e->stream);
-            if (rc) return fail(e, RB_ERR_DEVICE, "chunk gather launch failed");
-            HIP_TRY(e, hipStreamSynchronize(e->stream));
-            e->chunk_ready = true;
-            e->chunk_build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-        }
-    }
-    // ---- the library's own tree over the same triangles
-    if (!e->chunk_ready && wants_own_tree(e, tri_count) && e->host_nodes.size() > 1 && e->host_tri_len > 0 && e->host_index_len > 0 && tri_count > 0) {
-        rc = ensure_host_mesh(e);
-        if (rc) return rc;
-        rb::FastTree ft;
-        const auto t_begin = std::chrono::steady_clock::now();
-        const uint32_t n_idx = static_cast<uint32_t>(e->host_indices.size());
-        const uint32_t n_nodes = static_cast<uint32_t>(e->host_nodes.size());
-        const uint32_t n_tris = std::min<uint32_t>(tri_count, static_cast<uint32_t>(e->host_tris.size()));
-        bool built = false;
-        e->fast_builder = "";
-        // which builder: the device one from kDeviceBuildMinTriangles up (milliseconds instead of ~0.15 s per
-        // million triangles), the host's binned SAH below; either can be forced
-        const float small_cap = (e->opt.flags & RB_FLAG_SKIP_NEAR_DEGENERATE) ? 0.0f : rb::kFastSmallCap;
-        const bool force_host = (e->opt.flags & RB_FLAG_HOST_BVH) != 0u, force_dev = (e->opt.flags & RB_FLAG_DEVICE_BVH) != 0u;
-        const bool try_device = !force_host && (force_dev || n_tris >= rb::kDeviceBuildMinTriangles);
-        if (try_device) {
-            // reference-order metadata on the host (one pass over the caller's tree), the tree on the device
-            if (rb::fast_bvh_prepare(e->host_tris.data(), n_tris, e->host_indices.data(), n_idx, e->host_nodes.data(), n_nodes, ft, small_cap) &&
-                ft.slots.size() >= 1024) {
-                const uint32_t n = static_cast<uint32_t>(ft.slots.size());
-                DevBuf<uint32_t> visit_slots;
-                rc = upload(e, visit_slots, ft.slots.data(), ft.slots.size(), nullptr, true);
-                if (!rc) rc = upload(e, e->slot_meta, ft.slot_meta.data(), ft.slot_meta.size(), nullptr, true);
-                if (rc) return rc;
-                HIP_TRY(e, e->fast_nodes.resize(n - 1));
-                HIP_TRY(e, e->fast_slots.resize(n));
-                rb::DeviceTreeInfo info{};
-                rc = rb::device_fast_bvh_build(e->tris.ptr, e->indices.ptr, visit_slots.ptr, n, e->slot_meta.ptr, e->fast_nodes.ptr,
-                                               e->fast_slots.ptr, &info, e->stream, (e->opt.flags & RB_FLAG_DEVICE_LBVH) != 0u);
-                if (rc && rc != static_cast<int>(hipErrorNotReady))
-                    return fail(e, RB_ERR_DEVICE, "device BVH build failed: %s", hipGetErrorString(static_cast<hipError_t>(rc)));
-                if (rc) info.depth = 0xFFFFFFFFu;  // clustering did not converge within its round limit: host builder
-                // a tree deeper than the LDS stack spills to a global scratch column per lane, which only the
-                // persistent kernels (bounded grid) get; otherwise use the depth-limited host builder
-                const uint32_t kern = e->opt.kernel ? e->opt.kernel : RB_KERNEL_STREAM;
-                bool usable = info.depth <= rb::kStackDepth;
-                if (!usable && kern != RB_KERNEL_PIXEL && info.depth <= 128u) {
-                    const size_t lanes = rb::stream_kernel_max_threads(e->opt._reserved[0]);
-                    HIP_TRY(e, e->stack_overflow.resize(lanes * (info.depth - rb::kStackDepth)));
-                    usable = true;
-                }
-                if (usable) {
-                    ft.root = info.root;
-                    ft.depth = info.depth;
-                    ft.margin = info.margin;
-                    ft.root_amax = info.root_amax;
-                    for (int i = 0; i < 3; ++i) {
-                        ft.bmin[i] = info.bmin[i];
-                        ft.bmax[i] = info.bmax[i];
-                    }
-                    built = true;
-                    e->fast_builder = (e->opt.flags & RB_FLAG_DEVICE_LBVH) ? "device-lbvh" : "device-ploc";
-                }
-            }
-        }
-        if (!built) {
-            if (!rb::fast_bvh_build(e->host_tris.data(), n_tris, e->host_indices.data(), n_idx, e->host_nodes.data(), n_nodes,
-                                    rb::kStackDepth, ft, small_cap))
-                return RB_OK;  // keep the reference walk
-            rc = upload(e, e->fast_nodes, ft.nodes.data(), ft.nodes.size(), nullptr, true);
-            if (!rc) rc = upload(e, e->fast_slots, ft.slots.data(), ft.slots.size(), nullptr, true);
-            if (rc) return rc;
-            e->fast_builder = "host-sah";
-        }
-        rc = upload(e, e->slot_meta, ft.slot_meta.data(), ft.slot_meta.size(), nullptr, true);
-        if (!rc) rc = upload(e, e->ref_parent, ft.ref_parent.data(), ft.ref_parent.size(), nullptr, true);
-        if (!rc) rc = upload(e, e->gnodes, ft.gnodes.data(), ft.gnodes.size(), nullptr, true);
-        if (!rc) rc = upload(e, e->gslots, ft.gslots.data(), ft.gslots.size(), nullptr, true);
-        if (rc) return rc;
-        const size_t n_items = e->fast_slots.count;
-        HIP_TRY(e, e->fast_tris.resize(n_items));
-        rc = rb::launch_gather_tris(e->ptris.ptr, e->fast_slots.ptr, static_cast<uint32_t>(n_items), e->fast_tris.ptr, e->stream);
-        if (rc) return fail(e, RB_ERR_DEVICE, "gather kernel launch failed");
-        HIP_TRY(e, hipStreamSynchronize(e->stream));  // `ft` is a local
-        e->fast_build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-        e->fast_root = ft.root;
-        e->fast_depth = ft.depth;
-        e->fast_margin = ft.margin;
-        e->fast_root_amax = ft.root_amax;
-        for (int i = 0; i < 3; ++i) {
-            e->fast_bmin[i] = ft.bmin[i];
-            e->fast_bmax[i] = ft.bmax[i];
-        }
-        e->fast_ready = true;
-    }
-    return RB_OK;
+    // ---- the mesh walk's tree (rb_accel.cpp): the chunked walk's if wanted, else the library's own if wanted
+    e->chunk.rec = e->own.rec = {};
+    rc = rb::build_chunk_tree(e, tri_count);
+    return (rc || e->chunk.rec.built()) ? rc : rb::build_own_tree(e, tri_count);
 }
 
 rb::KParams make_params(rb_engine* e, uint32_t first_pass, uint32_t n_passes, int src, int dst) {
@@ -837,47 +415,9 @@ rb::KParams make_params(rb_engine* e, uint32_t first_pass, uint32_t n_passes, in
     p.stripe_rows = e->opt.stripe_rows ? e->opt.stripe_rows : rb::kDefaultStripeRows;
     p.local_rows = e->local_rows;
     p.colors = e->colors.ptr;
-    const bool use_chunk = e->chunk_ready && p.u.bvh_node_count == e->n_nodes && p.u.bvh_node_count > 1u;
-    p.chunk_nodes = use_chunk ? e->chunk_nodes.ptr : nullptr;
-    p.chunk_a = e->chunk_a.ptr;
-    p.chunk_b = e->chunk_b.ptr;
-    p.chunk_c = e->chunk_c.ptr;
-    p.chunk_rank_slot = e->chunk_rank_slot.ptr;
-    p.chunk_root = e->chunk_root;
-    p.chunk_n = static_cast<uint32_t>(e->chunk_rank_slot.count);
-    const bool use_fast = !use_chunk && e->fast_ready && p.u.bvh_node_count == e->n_nodes && p.u.bvh_node_count > 1u;
-    p.fast_nodes = use_fast ? e->fast_nodes.ptr : nullptr;
-    p.gnodes = e->gnodes.ptr;
-    p.gslots = e->gslots.ptr;
-    p.fast_skip_second_pass = (e->opt.flags & RB_FLAG_SKIP_NEAR_DEGENERATE) ? 1u : 0u;
-    p.fast_tris = reinterpret_cast<const float*>(e->fast_tris.ptr);
-    p.fast_slots = e->fast_slots.ptr;
-    p.slot_meta = e->slot_meta.ptr;
-    p.ref_parent = e->ref_parent.ptr;
-    p.fast_root = e->fast_root;
-    p.fast_margin = e->fast_margin;
-    p.fast_root_amax = e->fast_root_amax;
-    for (int i = 0; i < 3; ++i) {
-        p.fast_bmin[i] = e->fast_bmin[i];
-        p.fast_bmax[i] = e->fast_bmax[i];
-    }
-    const bool use_sph_bvh = e->sph_bvh && p.u.spheres_count == e->n_spheres;
-    p.sph_nodes = use_sph_bvh ? e->sph_nodes.ptr : nullptr;
-    p.sph_leaf = e->sph_leaf.ptr;
-    p.sph_id = e->sph_id.ptr;
-    p.sph_root = e->sph_root;
-    // a single-node tree is walked without a stack (rb_kernels.hip, intersect_bvh)
-    p.stack_depth = (p.u.bvh_node_count <= 1u) ? 0u : std::max(e->bvh_stack, 1u);
-    if (use_sph_bvh) p.stack_depth = std::max(p.stack_depth, e->sph_depth);
-    if (use_fast) p.stack_depth = std::max(p.stack_depth, std::min(e->fast_depth, rb::kStackDepth));
-    // (max with what is there already: with no_leaf_stepping the launch falls to the per-segment kernel, which walks the
-    // CALLER's tree and needs bvh_stack entries -- the chunk tree can be shallower where it prunes empty subtrees)
-    if (use_chunk) p.stack_depth = std::max(p.stack_depth, e->chunk_depth + 1u);
-    // every walk a launch can run must fit the column it shares with the others (rb_internal.hpp, kStackEntryBytes)
-    e->stack_depth_covers = p.stack_depth <= rb::kStackDepth && (p.u.bvh_node_count <= 1u || p.stack_depth >= e->bvh_stack) &&
-                            (!use_sph_bvh || p.stack_depth >= e->sph_depth) && (!use_chunk || p.stack_depth >= e->chunk_depth + 1u) &&
-                            (!use_fast || p.stack_depth >= std::min(e->fast_depth, rb::kStackDepth));
-    p.stack_overflow = e->stack_overflow.ptr;
+    // stack_depth: the largest need of the walks a launch can run, each of which must fit the column (rb_internal.hpp)
+    p.stack_depth = rb::accel_params(e, p);
+    e->stack_depth_covers = p.stack_depth <= rb::kStackDepth;
     p.blocks_per_cu = e->opt._reserved[0];
     // the caller's reservation size: a multiple of 64 items, at most 4096 (the launcher's own range; beyond it the
     // 32-bit queue arithmetic of the stream kernels could wrap and hand items out twice)
@@ -888,9 +428,9 @@ rb::KParams make_params(rb_engine* e, uint32_t first_pass, uint32_t n_passes, in
 }
 
 int require_ready(rb_engine* e) {
-    if (!e->initialized) return fail(e, RB_ERR_NOT_INITIALIZED, "engine has not received its first update");
-    if (!e->scene_valid) return fail(e, RB_ERR_DEVICE, "the last update failed half-way on the device; send the scene again");
-    if (!e->have_uniforms) return fail(e, RB_ERR_UNIFORMS_NOT_INITIALIZED, "Uniforms must be initialized");
+    if (!e->initialized) return rb::fail(e, RB_ERR_NOT_INITIALIZED, "engine has not received its first update");
+    if (!e->scene_valid) return rb::fail(e, RB_ERR_DEVICE, "the last update failed half-way on the device; send the scene again");
+    if (!e->have_uniforms) return rb::fail(e, RB_ERR_UNIFORMS_NOT_INITIALIZED, "Uniforms must be initialized");
     return RB_OK;
 }
 
@@ -940,7 +480,7 @@ uint64_t color_budget_bytes(rb_engine* e) {
 // (pixel, sample) of a launch chunk.  Keeps the item count below 2^31 and, unless the caller fixed the chunk, the buffer
 // within the budget; if the device cannot give even that, halves.  Allocates (lazily: the first dispatch, or rb_reserve).
 int reserve_colors(rb_engine* e, uint32_t n_passes, uint32_t* chunk_out) {
-    const uint32_t kernel = e->opt.kernel ? e->opt.kernel : RB_KERNEL_STREAM;
+    const uint32_t kernel = rb::kernel_of(e->opt);
     uint32_t chunk = e->opt.passes_per_launch ? e->opt.passes_per_launch : n_passes;
     if (kernel == RB_KERNEL_STREAM && n_passes != 0 && e->width != 0 && e->local_rows != 0) {
         const uint64_t tiles = static_cast<uint64_t>((e->width + 7) / 8) * ((e->local_rows + 7) / 8);
@@ -948,14 +488,14 @@ int reserve_colors(rb_engine* e, uint32_t n_passes, uint32_t* chunk_out) {
         const uint64_t budget_items = color_budget_bytes(e) / 16ull;
         uint64_t max_chunk = std::min<uint64_t>((1ull << 31) / std::max<uint64_t>(per_pass, 1) , 0xFFFFFFFFull);
         if (!e->opt.passes_per_launch) max_chunk = std::min(max_chunk, std::max<uint64_t>(budget_items / std::max<uint64_t>(per_pass, 1), 1));
-        if (max_chunk == 0) return fail(e, RB_ERR_INVALID_UNIFORMS, "frame too large for one launch");
+        if (max_chunk == 0) return rb::fail(e, RB_ERR_INVALID_UNIFORMS, "frame too large for one launch");
         chunk = static_cast<uint32_t>(std::min<uint64_t>(chunk, max_chunk));
         for (;;) {
             const hipError_t st = e->colors.reserve(per_pass * chunk * 4);
             if (st == hipSuccess) break;
             (void)hipGetLastError();  // clear the sticky out-of-memory status
             if (st != hipErrorOutOfMemory || chunk == 1)
-                return fail(e, RB_ERR_DEVICE, "colour buffer of %llu bytes: %s", static_cast<unsigned long long>(per_pass * chunk * 16ull),
+                return rb::fail(e, RB_ERR_DEVICE, "colour buffer of %llu bytes: %s", static_cast<unsigned long long>(per_pass * chunk * 16ull),
                             hipGetErrorString(st));
             chunk = (chunk + 1) / 2;
         }
@@ -978,7 +518,7 @@ int dispatch(rb_engine* e, uint32_t first_pass, uint32_t n_passes, int src, int 
         rc = accumulate_timing(e);
         if (rc) return rc;
     }
-    const uint32_t kernel = e->opt.kernel ? e->opt.kernel : RB_KERNEL_STREAM;
+    const uint32_t kernel = rb::kernel_of(e->opt);
     const bool stats = (e->opt.flags & RB_FLAG_STATS) != 0;
     uint32_t chunk = 0;
     rc = reserve_colors(e, n_passes, &chunk);
@@ -990,7 +530,7 @@ int dispatch(rb_engine* e, uint32_t first_pass, uint32_t n_passes, int src, int 
         const uint32_t n = std::min(chunk, n_passes - done);
         // the first chunk resumes `src`; later chunks of the same group continue in `dst`
         rb::KParams p = make_params(e, first_pass + done, n, done == 0 ? src : dst, dst);
-        if (!e->stack_depth_covers) return fail(e, RB_ERR_DEVICE, "internal: a traversal is deeper than its LDS stack column (%u entries)", p.stack_depth);
+        if (!e->stack_depth_covers) return rb::fail(e, RB_ERR_DEVICE, "internal: a traversal is deeper than its LDS stack column (%u entries)", p.stack_depth);
         rb::LaunchInfo li{};
         // per-chunk timing events (first 256 chunks of a group; later ones only count in the total)
         hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
@@ -1005,7 +545,7 @@ int dispatch(rb_engine* e, uint32_t first_pass, uint32_t n_passes, int src, int 
             HIP_TRY(e, hipEventRecord(ev[0], e->stream));
         }
         rc = rb::launch_render(p, kernel, stats, e->stream, &li, ev[1]);
-        if (rc) return fail(e, RB_ERR_DEVICE, "render kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(rc)));
+        if (rc) return rb::fail(e, RB_ERR_DEVICE, "render kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(rc)));
         if (ev[2]) {
             if (kernel != RB_KERNEL_STREAM) HIP_TRY(e, hipEventRecord(ev[1], e->stream));
             HIP_TRY(e, hipEventRecord(ev[2], e->stream));
@@ -1026,7 +566,7 @@ int dispatch(rb_engine* e, uint32_t first_pass, uint32_t n_passes, int src, int 
 // for the launches that produced the slot, then a blocking copy.  The engine's stream is non-blocking, so a
 // pass the iterator has already started on the OTHER slot keeps running underneath this copy.
 int read_slot_rgba(rb_engine* e, int slot, uint8_t* out) {
-    if (!out) return fail(e, RB_ERR_NULL_ARGUMENT, "rgba_out is NULL");
+    if (!out) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "rgba_out is NULL");
     const uint32_t sc = e->opt.shard_count > 1 ? e->opt.shard_count : 1;
     const size_t bytes = static_cast<size_t>(e->width) * 4 * (sc == 1 ? e->height : e->padded_rows);
     if (bytes == 0) return RB_OK;
@@ -1049,72 +589,6 @@ int read_rgba(rb_engine* e, uint8_t* out) {
     // uploads and clears queued after the slot's last launch group must be over as well
     HIP_TRY(e, hipEventRecord(e->slot[e->cur].done, e->stream));
     return read_slot_rgba(e, e->cur, out);
-}
-
-// RB_FLAG_BUILD_TREE: the canonical reference-layout tree of the n triangles just uploaded (host copy `src`, borrowed for the
-// update), in place of the caller's bvh_nodes / bvh_indices.  On the device by default: the nodes are read back (48 B per 128
-// triangles) for validation and the host walks' builders, the indices stay on the device (fetched back by ensure_host_mesh if a
-// host builder needs them).  A device short of memory for the builder's scratch falls back to the host builder: the same tree.
-int build_engine_tree(rb_engine* e, const rb_gpu_triangle* src, size_t n) {
-    const auto t_begin = std::chrono::steady_clock::now();
-    e->prep_dirty = true;
-    e->tree_builder = "";
-    e->tree_build_ms = 0.0f;
-    int rc = RB_OK;
-    if (n == 0) {   // Delete, or an empty vector: an empty tree
-        rc = upload(e, e->nodes, nullptr, 0, nullptr, true);
-        if (!rc) rc = upload(e, e->indices, nullptr, 0, &e->n_indices, true);
-        if (rc) return rc;
-        e->n_nodes = 0;
-        e->host_nodes.clear();
-        e->host_index_len = 0;
-        e->host_indices_stale = false;
-        std::vector<uint32_t>().swap(e->host_indices);
-        return RB_OK;
-    }
-    const char* builder = "host";
-    if (!(e->opt.flags & RB_FLAG_BUILD_TREE_HOST)) {
-        const size_t nn = rb::bvh_node_count(n);
-        HIP_TRY(e, e->nodes.resize(nn));
-        HIP_TRY(e, e->indices.resize(n));
-        const int brc = rb::device_reference_bvh_build(e->tris.ptr, static_cast<uint32_t>(n), e->nodes.ptr, e->indices.ptr, e->stream);
-        if (brc == hipSuccess) {
-            e->host_nodes.resize(nn);
-            HIP_TRY(e, hipMemcpyAsync(e->host_nodes.data(), e->nodes.ptr, sizeof(rb_bvh_node) * nn, hipMemcpyDeviceToHost, e->stream));
-            HIP_TRY(e, hipStreamSynchronize(e->stream));
-            e->n_nodes = static_cast<uint32_t>(nn);
-            e->n_indices = static_cast<uint32_t>(n);
-            if (may_want_own_tree(e)) {
-                e->host_index_len = n;
-                e->host_indices_stale = true;
-                std::vector<uint32_t>().swap(e->host_indices);
-            }
-            builder = "device";
-        } else if (brc != hipErrorOutOfMemory) {
-            return fail(e, RB_ERR_DEVICE, "device tree build failed: %s", hipGetErrorString(static_cast<hipError_t>(brc)));
-        } else {
-            (void)hipGetLastError();
-        }
-    }
-    if (builder[0] == 'h') {
-        std::vector<rb_bvh_node> nodes;
-        std::vector<uint32_t> idx;
-        rb::bvh_build_canonical(src, n, nodes, idx);
-        rc = upload(e, e->nodes, nodes.data(), nodes.size(), nullptr, true);
-        if (!rc) rc = upload(e, e->indices, idx.data(), idx.size(), &e->n_indices, true);
-        if (rc) return rc;
-        HIP_TRY(e, hipStreamSynchronize(e->stream));   // `nodes` / `idx` are moved below, but the copies read them now
-        e->n_nodes = static_cast<uint32_t>(nodes.size());
-        e->host_nodes = std::move(nodes);
-        if (may_want_own_tree(e)) {
-            e->host_index_len = n;
-            e->host_indices_stale = false;
-            e->host_indices = std::move(idx);
-        }
-    }
-    e->tree_builder = builder;
-    e->tree_build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-    return RB_OK;
 }
 
 int update_fields(rb_engine* e, const rb_config* cfg) {
@@ -1151,16 +625,16 @@ int update_fields(rb_engine* e, const rb_config* cfg) {
         rc = apply_field(e, i, *field_at(cfg, i), first);
         if (rc) return rc;
     }
-    if (builds_tree(e)) {   // the tree follows the triangles field (RB_FLAG_BUILD_TREE)
+    if (rb::builds_tree(e)) {   // the tree follows the triangles field (RB_FLAG_BUILD_TREE)
         const Act a_tris = field_action(7, cfg->bvh_triangles, first);
         if (a_tris != Act::None) {
-            rc = build_engine_tree(e, static_cast<const rb_gpu_triangle*>(a_tris == Act::Take ? cfg->bvh_triangles.ptr : nullptr),
+            rc = rb::build_engine_tree(e, static_cast<const rb_gpu_triangle*>(a_tris == Act::Take ? cfg->bvh_triangles.ptr : nullptr),
                                    a_tris == Act::Take ? cfg->bvh_triangles.count : 0);
             if (rc) return rc;
         }
     }
     e->last_change_spheres = cfg->spheres.change;
-    e->last_change_nodes = builds_tree(e) ? cfg->bvh_triangles.change : cfg->bvh_nodes.change;
+    e->last_change_nodes = rb::builds_tree(e) ? cfg->bvh_triangles.change : cfg->bvh_nodes.change;
     e->last_change_tris = cfg->bvh_triangles.change;
     e->bvh_stack = plan.bvh_stack;
     e->max_mesh_index = plan.max_mesh_index;
@@ -1177,7 +651,7 @@ int update_locked(rb_engine* e, const rb_config* cfg) {
     const int rc = update_fields(e, cfg);
     const hipError_t st = hipStreamSynchronize(e->stream);
     if (rc) return rc;
-    if (st != hipSuccess) return fail(e, RB_ERR_DEVICE, "hipStreamSynchronize: %s", hipGetErrorString(st));
+    if (st != hipSuccess) return rb::fail(e, RB_ERR_DEVICE, "hipStreamSynchronize: %s", hipGetErrorString(st));
     return RB_OK;
 }
 
@@ -1195,7 +669,7 @@ int render_async(rb_engine* e) {
 }
 
 int render_locked(rb_engine* e, uint8_t* rgba_out) {
-    if (!rgba_out && !(e->net.nranks > 1 && e->net.rank != 0)) return fail(e, RB_ERR_NULL_ARGUMENT, "rgba_out is NULL");
+    if (!rgba_out && !(e->net.nranks > 1 && e->net.rank != 0)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "rgba_out is NULL");
     int rc = render_async(e);
     if (rc) return rc;
     if (e->net.nranks > 1) {  // one process per device: the frame is assembled on rank 0
@@ -1203,7 +677,7 @@ int render_locked(rb_engine* e, uint8_t* rgba_out) {
         if (rb::gather_process(e->net, e->slot[e->cur].rgba.ptr, e->width, e->height, e->padded_rows,
                                e->opt.stripe_rows ? e->opt.stripe_rows : rb::kDefaultStripeRows, e->copy_stream, e->slot[e->cur].done,
                                rgba_out, why))
-            return fail(e, RB_ERR_DEVICE, "%s", why.c_str());
+            return rb::fail(e, RB_ERR_DEVICE, "%s", why.c_str());
     } else {
         rc = read_rgba(e, rgba_out);
         if (rc) return rc;
@@ -1241,7 +715,7 @@ int iter_advance(rb_engine* e, uint32_t per_frame) {
     if (rc) return rc;
     // ---- run ahead: the next group on the other slot
     if (!(e->opt.flags & RB_FLAG_NO_RUN_AHEAD) && e->prh.current_pass < e->prh.total_passes) {
-        FrameSlot& o = e->slot[1 - e->cur];
+        rb::FrameSlot& o = e->slot[1 - e->cur];
         const size_t px = static_cast<size_t>(e->width) * e->padded_rows;
         if (o.accum.count != px * 4 || o.rgba.count != px) {
             HIP_TRY(e, o.accum.resize(px * 4));
@@ -1263,9 +737,9 @@ int iter_advance(rb_engine* e, uint32_t per_frame) {
 
 int iter_next_locked(rb_engine* e, uint8_t* rgba_out) {
     if (!(e->prh.current_pass < e->prh.total_passes))
-        return fail(e, RB_ERR_NO_MORE_FRAMES, "No more frames available");  // lib.rs:170-177
+        return rb::fail(e, RB_ERR_NO_MORE_FRAMES, "No more frames available");  // lib.rs:170-177
     const bool multiproc = e->net.nranks > 1;
-    if (!rgba_out && !(multiproc && e->net.rank != 0)) return fail(e, RB_ERR_NULL_ARGUMENT, "rgba_out is NULL");
+    if (!rgba_out && !(multiproc && e->net.rank != 0)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "rgba_out is NULL");
     int rc = iter_advance(e, e->iter_passes_per_frame);
     if (rc) return rc;
     if (multiproc) {
@@ -1273,7 +747,7 @@ int iter_next_locked(rb_engine* e, uint8_t* rgba_out) {
         if (rb::gather_process(e->net, e->slot[e->cur].rgba.ptr, e->width, e->height, e->padded_rows,
                                e->opt.stripe_rows ? e->opt.stripe_rows : rb::kDefaultStripeRows, e->copy_stream, e->slot[e->cur].done,
                                rgba_out, why))
-            return fail(e, RB_ERR_DEVICE, "%s", why.c_str());
+            return rb::fail(e, RB_ERR_DEVICE, "%s", why.c_str());
         return RB_OK;
     }
     return read_slot_rgba(e, e->cur, rgba_out);  // lib.rs:205
@@ -1281,19 +755,19 @@ int iter_next_locked(rb_engine* e, uint8_t* rgba_out) {
 
 rb_engine* create_single(const rb_config* cfg, const rb_options& opt) {
     if (opt.shard_count > 1 && opt.shard_rank >= opt.shard_count) {
-        fail(nullptr, RB_ERR_INVALID_OPTIONS, "shard_rank %u >= shard_count %u", opt.shard_rank, opt.shard_count);
+        rb::fail(nullptr, RB_ERR_INVALID_OPTIONS, "shard_rank %u >= shard_count %u", opt.shard_rank, opt.shard_count);
         return nullptr;
     }
-    if (opt.kernel > RB_KERNEL_STREAM) { fail(nullptr, RB_ERR_INVALID_OPTIONS, "unknown kernel %u", opt.kernel); return nullptr; }
-    if ((opt.flags & RB_FLAG_BUILD_TREE) && (opt.flags & RB_FLAG_BUILD_TREE_HOST)) {
-        fail(nullptr, RB_ERR_INVALID_OPTIONS, "RB_FLAG_BUILD_TREE and RB_FLAG_BUILD_TREE_HOST exclude each other");
+    if (opt.kernel > RB_KERNEL_STREAM) { rb::fail(nullptr, RB_ERR_INVALID_OPTIONS, "unknown kernel %u", opt.kernel); return nullptr; }
+    if ((opt.flags & rb::kBuildTreeFlags) == rb::kBuildTreeFlags) {
+        rb::fail(nullptr, RB_ERR_INVALID_OPTIONS, "RB_FLAG_BUILD_TREE and RB_FLAG_BUILD_TREE_HOST exclude each other");
         return nullptr;
     }
     int dev = opt.device;
     if (dev < 0) {
-        if (hipGetDevice(&dev) != hipSuccess) { fail(nullptr, RB_ERR_DEVICE, "no HIP device available"); return nullptr; }
+        if (hipGetDevice(&dev) != hipSuccess) { rb::fail(nullptr, RB_ERR_DEVICE, "no HIP device available"); return nullptr; }
     }
-    if (hipSetDevice(dev) != hipSuccess) { fail(nullptr, RB_ERR_DEVICE, "hipSetDevice(%d) failed", dev); return nullptr; }
+    if (hipSetDevice(dev) != hipSuccess) { rb::fail(nullptr, RB_ERR_DEVICE, "hipSetDevice(%d) failed", dev); return nullptr; }
     rb_engine* e = new rb_engine();
     e->device = dev;
     e->opt = opt;
@@ -1301,10 +775,10 @@ rb_engine* create_single(const rb_config* cfg, const rb_options& opt) {
     // whatever the host program's flags say -- the escape hatch from the culled walks (whose exactness is derived and fuzzed,
     // DESIGN.md section 4.2) that needs no rebuild of the host
     if (const char* rw = std::getenv("RB_REFERENCE_WALK"); rw && rw[0] == '1')
-        e->opt.flags = (e->opt.flags & ~(RB_FLAG_FAST_BVH | RB_FLAG_DEVICE_BVH | RB_FLAG_DEVICE_LBVH | RB_FLAG_HOST_BVH | RB_FLAG_CHUNK_WALK |
-                                         RB_FLAG_SKIP_NEAR_DEGENERATE)) | RB_FLAG_REFERENCE_WALK;
+        e->opt.flags = (e->opt.flags & ~(rb::kOwnTreeFlags | RB_FLAG_DEVICE_LBVH | RB_FLAG_CHUNK_WALK | RB_FLAG_SKIP_NEAR_DEGENERATE)) |
+                       RB_FLAG_REFERENCE_WALK;
     auto bail = [&](const char* what, hipError_t st) -> rb_engine* {
-        fail(nullptr, RB_ERR_DEVICE, "%s failed: %s", what, hipGetErrorString(st));
+        rb::fail(nullptr, RB_ERR_DEVICE, "%s failed: %s", what, hipGetErrorString(st));
         rb_destroy(e);
         return nullptr;
     };
@@ -1313,7 +787,7 @@ rb_engine* create_single(const rb_config* cfg, const rb_options& opt) {
     if ((st = hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", st);
     if ((st = hipEventCreate(&e->ev_begin)) != hipSuccess) return bail("hipEventCreate", st);
     if ((st = hipEventCreate(&e->ev_end)) != hipSuccess) return bail("hipEventCreate", st);
-    for (FrameSlot& s : e->slot)
+    for (rb::FrameSlot& s : e->slot)
         if ((st = hipEventCreateWithFlags(&s.done, hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", st);
     if ((st = e->counters.resize(rb::C_COUNT)) != hipSuccess) return bail("hipMalloc(counters)", st);
     if ((st = e->queue.resize(rb::kQueueWords)) != hipSuccess) return bail("hipMalloc(queue)", st);
@@ -1335,7 +809,7 @@ rb_engine* create_single(const rb_config* cfg, const rb_options& opt) {
 
 bool check_create(const rb_config* cfg) {
     g_create_error.clear();
-    if (!cfg) { fail(nullptr, RB_ERR_NULL_ARGUMENT, "config is NULL"); return false; }
+    if (!cfg) { rb::fail(nullptr, RB_ERR_NULL_ARGUMENT, "config is NULL"); return false; }
     if (check_fields(nullptr, cfg)) return false;
     // GpuBuffers::new panics unless these are Create (buffers.rs:74-97)
     if (validate_init(nullptr, cfg)) return false;
@@ -1351,8 +825,6 @@ rb_engine* create_impl(const rb_config* cfg, const rb_options* opt_in) {
 }
 
 // ------------------------------------------------------------------ several devices, one handle ----
-bool is_group(const rb_engine* e) { return !e->parts.empty(); }
-
 void copy_error(rb_engine* g, const rb_engine* part) {
     std::string msg;
     {
@@ -1365,7 +837,7 @@ void copy_error(rb_engine* g, const rb_engine* part) {
 
 #define PART_TRY(g, part, call)            \
     do {                                   \
-        set_device(part);                  \
+        rb::set_device(part);              \
         const int _rc = (call);            \
         if (_rc) {                         \
             copy_error((g), (part));       \
@@ -1392,7 +864,7 @@ int group_deliver(rb_engine* g, uint8_t* rgba_out, bool fold_timing) {
     const uint32_t sr = p0->opt.stripe_rows ? p0->opt.stripe_rows : rb::kDefaultStripeRows;
     std::string why;
     if (rb::gather_group(g->net, src, p0->width, p0->height, p0->padded_rows, sr, rgba_out, why))
-        return fail(g, RB_ERR_DEVICE, "%s", why.c_str());
+        return rb::fail(g, RB_ERR_DEVICE, "%s", why.c_str());
     // (the iterator folds a group's timing when it commits it: waiting for the events here would wait for the pass
     // that has just been started ahead)
     if (fold_timing)
@@ -1401,7 +873,7 @@ int group_deliver(rb_engine* g, uint8_t* rgba_out, bool fold_timing) {
 }
 
 int group_render(rb_engine* g, uint8_t* rgba_out) {
-    if (!rgba_out) return fail(g, RB_ERR_NULL_ARGUMENT, "rgba_out is NULL");
+    if (!rgba_out) return rb::fail(g, RB_ERR_NULL_ARGUMENT, "rgba_out is NULL");
     for (auto& p : g->parts) PART_TRY(g, p.get(), render_async(p.get()));  // all devices render concurrently
     g->prh = g->parts[0]->prh;
     return group_deliver(g, rgba_out, true);
@@ -1409,8 +881,8 @@ int group_render(rb_engine* g, uint8_t* rgba_out) {
 
 int group_iter_next(rb_engine* g, uint8_t* rgba_out) {
     rb_engine* p0 = g->parts[0].get();
-    if (!(p0->prh.current_pass < p0->prh.total_passes)) return fail(g, RB_ERR_NO_MORE_FRAMES, "No more frames available");
-    if (!rgba_out) return fail(g, RB_ERR_NULL_ARGUMENT, "rgba_out is NULL");
+    if (!(p0->prh.current_pass < p0->prh.total_passes)) return rb::fail(g, RB_ERR_NO_MORE_FRAMES, "No more frames available");
+    if (!rgba_out) return rb::fail(g, RB_ERR_NULL_ARGUMENT, "rgba_out is NULL");
     for (auto& pp : g->parts) PART_TRY(g, pp.get(), iter_advance(pp.get(), g->iter_passes_per_frame));   // every part runs ahead
     g->prh = p0->prh;
     return group_deliver(g, rgba_out, false);
@@ -1427,13 +899,13 @@ rb_engine* rb_create_ex(const rb_config* cfg, const rb_options* opt) { return cr
 rb_engine* rb_create_multi(const rb_config* cfg, const rb_options* opt_in, const int32_t* devices, uint32_t n_devices) {
     if (!check_create(cfg)) return nullptr;
     if (!devices || n_devices == 0 || n_devices > 64) {
-        fail(nullptr, RB_ERR_INVALID_OPTIONS, "rb_create_multi needs 1..64 devices");
+        rb::fail(nullptr, RB_ERR_INVALID_OPTIONS, "rb_create_multi needs 1..64 devices");
         return nullptr;
     }
     rb_options opt{};
     if (opt_in) opt = *opt_in;
     if (opt.shard_count > 1) {
-        fail(nullptr, RB_ERR_INVALID_OPTIONS, "rb_create_multi shards by itself: leave shard_rank / shard_count zero");
+        rb::fail(nullptr, RB_ERR_INVALID_OPTIONS, "rb_create_multi shards by itself: leave shard_rank / shard_count zero");
         return nullptr;
     }
     std::unique_ptr<rb_engine> g(new rb_engine());
@@ -1455,7 +927,7 @@ rb_engine* rb_create_multi(const rb_config* cfg, const rb_options* opt_in, const
     std::string why;
     if (rb::gather_init_group(g->net, devs, (opt.flags & RB_FLAG_GATHER_PEER_COPY) != 0u, why)) {
         rb_destroy(g.release());
-        fail(nullptr, RB_ERR_DEVICE, "%s", why.c_str());
+        rb::fail(nullptr, RB_ERR_DEVICE, "%s", why.c_str());
         return nullptr;
     }
     rb_engine* out = g.release();
@@ -1484,14 +956,14 @@ int rb_comm_unique_id(uint8_t id_out[RB_COMM_ID_BYTES]) {
 int rb_comm_init_rank(rb_engine* e, const uint8_t id[RB_COMM_ID_BYTES], uint32_t rank, uint32_t nranks) {
     if (!e || !id) return RB_ERR_NULL_ARGUMENT;
     std::lock_guard<std::mutex> lock(e->mu);
-    if (is_group(e)) return fail(e, RB_ERR_INVALID_OPTIONS, "rb_comm_init_rank is for single-device engines");
+    if (rb::is_group(e)) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "rb_comm_init_rank is for single-device engines");
     const uint32_t sc = e->opt.shard_count > 1 ? e->opt.shard_count : 1;
     if (nranks != sc || rank != (sc > 1 ? e->opt.shard_rank : 0u))
-        return fail(e, RB_ERR_INVALID_OPTIONS, "communicator rank %u of %u does not match shard %u of %u", rank, nranks,
+        return rb::fail(e, RB_ERR_INVALID_OPTIONS, "communicator rank %u of %u does not match shard %u of %u", rank, nranks,
                     e->opt.shard_rank, sc);
-    set_device(e);
+    rb::set_device(e);
     std::string why;
-    if (rb::gather_init_rank(e->net, e->device, id, rank, nranks, why)) return fail(e, RB_ERR_DEVICE, "%s", why.c_str());
+    if (rb::gather_init_rank(e->net, e->device, id, rank, nranks, why)) return rb::fail(e, RB_ERR_DEVICE, "%s", why.c_str());
     return RB_OK;
 }
 
@@ -1499,16 +971,16 @@ int rb_comm_info(rb_engine* e, uint32_t* rccl_ranks, uint32_t* rccl_rank, float*
     if (!e) return RB_ERR_NULL_ARGUMENT;
     std::lock_guard<std::mutex> lock(e->mu);
     std::string why;
-    if (rb::gather_comm_info(e->net, rccl_ranks, rccl_rank, why)) return fail(e, RB_ERR_DEVICE, "%s", why.c_str());
+    if (rb::gather_comm_info(e->net, rccl_ranks, rccl_rank, why)) return rb::fail(e, RB_ERR_DEVICE, "%s", why.c_str());
     if (last_gather_ms) *last_gather_ms = e->net.last_ms;
     return RB_OK;
 }
 
 void rb_destroy(rb_engine* e) {
     if (!e) return;
-    if (is_group(e)) {
+    if (rb::is_group(e)) {
         for (auto& p : e->parts) {
-            set_device(p.get());
+            rb::set_device(p.get());
             if (p->stream) (void)hipStreamSynchronize(p->stream);
         }
         rb::gather_destroy(e->net);
@@ -1516,7 +988,7 @@ void rb_destroy(rb_engine* e) {
         delete e;
         return;
     }
-    set_device(e);
+    rb::set_device(e);
     // every launch, copy and event record of this engine was queued on its one stream: when that has
     // drained nothing on the device refers to the buffers, events or communicator any more
     if (e->stream) (void)hipStreamSynchronize(e->stream);
@@ -1527,7 +999,7 @@ void rb_destroy(rb_engine* e) {
     rb::gather_destroy(e->net);
     if (e->ev_begin) (void)hipEventDestroy(e->ev_begin);
     if (e->ev_end) (void)hipEventDestroy(e->ev_end);
-    for (FrameSlot& s : e->slot)
+    for (rb::FrameSlot& s : e->slot)
         if (s.done) (void)hipEventDestroy(s.done);
     for (hipEvent_t x : e->ev_pool) (void)hipEventDestroy(x);
     if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -1549,27 +1021,27 @@ const char* rb_last_error(const rb_engine* e) {
 int rb_update(rb_engine* e, const rb_config* cfg) {
     if (!e) return RB_ERR_NULL_ARGUMENT;
     std::lock_guard<std::mutex> lock(e->mu);
-    if (is_group(e)) return group_update(e, cfg);
-    set_device(e);
+    if (rb::is_group(e)) return group_update(e, cfg);
+    rb::set_device(e);
     return update_locked(e, cfg);
 }
 
 int rb_render(rb_engine* e, uint8_t* rgba_out) {
     if (!e) return RB_ERR_NULL_ARGUMENT;
     std::lock_guard<std::mutex> lock(e->mu);
-    if (is_group(e)) return group_render(e, rgba_out);
-    set_device(e);
+    if (rb::is_group(e)) return group_render(e, rgba_out);
+    rb::set_device(e);
     return render_locked(e, rgba_out);
 }
 
 int rb_render_config(rb_engine* e, const rb_config* cfg, uint8_t* rgba_out) {
     if (!e) return RB_ERR_NULL_ARGUMENT;
     std::lock_guard<std::mutex> lock(e->mu);
-    if (is_group(e)) {
+    if (rb::is_group(e)) {
         const int rc = group_update(e, cfg);
         return rc ? rc : group_render(e, rgba_out);
     }
-    set_device(e);
+    rb::set_device(e);
     int rc = update_locked(e, cfg);
     if (rc) return rc;
     return render_locked(e, rgba_out);
@@ -1578,7 +1050,7 @@ int rb_render_config(rb_engine* e, const rb_config* cfg, uint8_t* rgba_out) {
 int rb_iter_begin(rb_engine* e, const rb_config* cfg) {
     if (!e) return RB_ERR_NULL_ARGUMENT;
     std::lock_guard<std::mutex> lock(e->mu);
-    if (is_group(e)) {
+    if (rb::is_group(e)) {
         int rc = group_update(e, cfg);
         if (rc) return rc;
         for (auto& p : e->parts) {
@@ -1589,7 +1061,7 @@ int rb_iter_begin(rb_engine* e, const rb_config* cfg) {
         e->prh = e->parts[0]->prh;
         return RB_OK;
     }
-    set_device(e);
+    rb::set_device(e);
     int rc = update_locked(e, cfg);
     if (rc) return rc;
     rc = require_ready(e);
@@ -1603,15 +1075,15 @@ int rb_iter_begin(rb_engine* e, const rb_config* cfg) {
 int rb_iter_has_next(rb_engine* e) {
     if (!e) return 0;
     std::lock_guard<std::mutex> lock(e->mu);
-    const rb_engine* s = is_group(e) ? e->parts[0].get() : e;
+    const rb_engine* s = rb::is_group(e) ? e->parts[0].get() : e;
     return s->prh.current_pass < s->prh.total_passes ? 1 : 0;  // lib.rs:153-156
 }
 
 int rb_iter_next(rb_engine* e, uint8_t* rgba_out) {
     if (!e) return RB_ERR_NULL_ARGUMENT;
     std::lock_guard<std::mutex> lock(e->mu);
-    if (is_group(e)) return group_iter_next(e, rgba_out);
-    set_device(e);
+    if (rb::is_group(e)) return group_iter_next(e, rgba_out);
+    rb::set_device(e);
     return iter_next_locked(e, rgba_out);
 }
 
@@ -1627,7 +1099,7 @@ int rb_iter_set_passes_per_frame(rb_engine* e, uint32_t n) {
 int rb_get_size(const rb_engine* e, uint32_t* width, uint32_t* height) {
     if (!e) return RB_ERR_NULL_ARGUMENT;
     std::lock_guard<std::mutex> lock(const_cast<rb_engine*>(e)->mu);
-    if (!e->have_uniforms) return fail(e, RB_ERR_UNIFORMS_NOT_INITIALIZED, "Uniforms must be initialized");  // gpu_wrapper.rs:313,321
+    if (!e->have_uniforms) return rb::fail(e, RB_ERR_UNIFORMS_NOT_INITIALIZED, "Uniforms must be initialized");  // gpu_wrapper.rs:313,321
     if (width) *width = e->width;
     if (height) *height = e->height;
     return RB_OK;
@@ -1636,14 +1108,14 @@ int rb_get_size(const rb_engine* e, uint32_t* width, uint32_t* height) {
 int rb_clear(rb_engine* e) {
     if (!e) return RB_ERR_NULL_ARGUMENT;
     std::lock_guard<std::mutex> lock(e->mu);
-    if (is_group(e)) {
+    if (rb::is_group(e)) {
         for (auto& p : e->parts) {
             PART_TRY(e, p.get(), require_ready(p.get()));
             PART_TRY(e, p.get(), clear_accum(p.get()));
         }
         return RB_OK;
     }
-    set_device(e);
+    rb::set_device(e);
     int rc = require_ready(e);
     if (rc) return rc;
     return clear_accum(e);
@@ -1652,7 +1124,7 @@ int rb_clear(rb_engine* e) {
 int rb_dispatch(rb_engine* e, uint32_t first_pass, uint32_t n_passes) {
     if (!e) return RB_ERR_NULL_ARGUMENT;
     std::lock_guard<std::mutex> lock(e->mu);
-    if (is_group(e)) {
+    if (rb::is_group(e)) {
         for (auto& p : e->parts) {
             PART_TRY(e, p.get(), require_ready(p.get()));
             p->spec_valid = false;
@@ -1660,7 +1132,7 @@ int rb_dispatch(rb_engine* e, uint32_t first_pass, uint32_t n_passes) {
         }
         return RB_OK;
     }
-    set_device(e);
+    rb::set_device(e);
     int rc = require_ready(e);
     if (rc) return rc;
     e->spec_valid = false;
@@ -1671,15 +1143,15 @@ int rb_reserve(rb_engine* e, uint32_t n_passes) {
     if (!e) return RB_ERR_NULL_ARGUMENT;
     std::lock_guard<std::mutex> lock(e->mu);
     auto one = [&](rb_engine* p) {
-        set_device(p);
+        rb::set_device(p);
         int rc = require_ready(p);
         if (!rc) rc = ensure_prepared(p);
         uint32_t chunk = 0;
         if (!rc) rc = reserve_colors(p, n_passes, &chunk);
-        if (!rc && hipStreamSynchronize(p->stream) != hipSuccess) rc = fail(p, RB_ERR_DEVICE, "synchronise failed");
+        if (!rc && hipStreamSynchronize(p->stream) != hipSuccess) rc = rb::fail(p, RB_ERR_DEVICE, "synchronise failed");
         return rc;
     };
-    if (is_group(e)) {
+    if (rb::is_group(e)) {
         for (auto& p : e->parts) PART_TRY(e, p.get(), one(p.get()));
         return RB_OK;
     }
@@ -1689,14 +1161,14 @@ int rb_reserve(rb_engine* e, uint32_t n_passes) {
 int rb_sync(rb_engine* e) {
     if (!e) return RB_ERR_NULL_ARGUMENT;
     std::lock_guard<std::mutex> lock(e->mu);
-    if (is_group(e)) {
+    if (rb::is_group(e)) {
         for (auto& p : e->parts) {
-            set_device(p.get());
+            rb::set_device(p.get());
             HIP_TRY(e, hipStreamSynchronize(p->stream));
         }
         return RB_OK;
     }
-    set_device(e);
+    rb::set_device(e);
     HIP_TRY(e, hipStreamSynchronize(e->stream));
     return RB_OK;
 }
@@ -1704,11 +1176,11 @@ int rb_sync(rb_engine* e) {
 int rb_read_rgba(rb_engine* e, uint8_t* rgba_out) {
     if (!e) return RB_ERR_NULL_ARGUMENT;
     std::lock_guard<std::mutex> lock(e->mu);
-    if (is_group(e)) {
-        if (!rgba_out) return fail(e, RB_ERR_NULL_ARGUMENT, "rgba_out is NULL");
+    if (rb::is_group(e)) {
+        if (!rgba_out) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "rgba_out is NULL");
         return group_deliver(e, rgba_out, false);
     }
-    set_device(e);
+    rb::set_device(e);
     int rc = require_ready(e);
     if (rc) return rc;
     return read_rgba(e, rgba_out);
@@ -1717,8 +1189,8 @@ int rb_read_rgba(rb_engine* e, uint8_t* rgba_out) {
 int rb_read_accumulation(rb_engine* e, float* accum_out) {
     if (!e) return RB_ERR_NULL_ARGUMENT;
     std::lock_guard<std::mutex> lock(e->mu);
-    if (!accum_out) return fail(e, RB_ERR_NULL_ARGUMENT, "accum_out is NULL");
-    if (is_group(e)) {
+    if (!accum_out) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "accum_out is NULL");
+    if (rb::is_group(e)) {
         // debugging / checkpoint path: every part's rows through the host, in image order
         rb_engine* p0 = e->parts[0].get();
         const uint32_t w = p0->width, h = p0->height, sr = p0->opt.stripe_rows ? p0->opt.stripe_rows : rb::kDefaultStripeRows;
@@ -1736,7 +1208,7 @@ int rb_read_accumulation(rb_engine* e, float* accum_out) {
         }
         return RB_OK;
     }
-    set_device(e);
+    rb::set_device(e);
     int rc = require_ready(e);
     if (rc) return rc;
     const uint32_t rows = (e->opt.shard_count > 1) ? e->padded_rows : e->height;
@@ -1761,7 +1233,7 @@ void rb_host_free(void* p) {
 int rb_device_rgba(rb_engine* e, void** d_ptr, size_t* bytes) {
     if (!e) return RB_ERR_NULL_ARGUMENT;
     std::lock_guard<std::mutex> lock(e->mu);
-    if (is_group(e)) {  // the assembled frame on the root device (valid after a render / iterator step)
+    if (rb::is_group(e)) {  // the assembled frame on the root device (valid after a render / iterator step)
         if (d_ptr) *d_ptr = rb::gather_frame_ptr(e->net);
         if (bytes) *bytes = static_cast<size_t>(e->width) * e->height * 4;
         return RB_OK;
@@ -1773,7 +1245,7 @@ int rb_device_rgba(rb_engine* e, void** d_ptr, size_t* bytes) {
 
 int rb_local_rows(const rb_engine* e, uint32_t* rows, uint32_t* padded_rows) {
     if (!e) return RB_ERR_NULL_ARGUMENT;
-    if (is_group(e)) {  // the handle delivers whole frames
+    if (rb::is_group(e)) {  // the handle delivers whole frames
         if (rows) *rows = e->height;
         if (padded_rows) *padded_rows = e->height;
         return RB_OK;
@@ -1793,7 +1265,7 @@ int rb_local_rows(const rb_engine* e, uint32_t* rows, uint32_t* padded_rows) {
 
 int rb_global_row(const rb_engine* e, uint32_t local_row, uint32_t* global_row) {
     if (!e || !global_row) return RB_ERR_NULL_ARGUMENT;
-    if (is_group(e)) { *global_row = local_row; return RB_OK; }
+    if (rb::is_group(e)) { *global_row = local_row; return RB_OK; }
     const uint32_t sc = e->opt.shard_count > 1 ? e->opt.shard_count : 1;
     const uint32_t sr = e->opt.stripe_rows ? e->opt.stripe_rows : rb::kDefaultStripeRows;
     if (sc == 1) { *global_row = local_row; return RB_OK; }
@@ -1830,7 +1302,7 @@ static int part_stats(rb_engine* e, rb_stats* out);
 int rb_get_stats(rb_engine* e, rb_stats* out) {
     if (!e || !out) return RB_ERR_NULL_ARGUMENT;
     std::lock_guard<std::mutex> lock(e->mu);
-    if (is_group(e)) {  // work counters add up; the devices run side by side, so times are the slowest part's
+    if (rb::is_group(e)) {  // work counters add up; the devices run side by side, so times are the slowest part's
         rb_stats sum{};
         for (auto& p : e->parts) {
             rb_stats s{};
@@ -1846,7 +1318,7 @@ int rb_get_stats(rb_engine* e, rb_stats* out) {
         *out = sum;
         return RB_OK;
     }
-    set_device(e);
+    rb::set_device(e);
     return part_stats(e, out);
 }
 
@@ -1874,11 +1346,11 @@ static int part_reset_stats(rb_engine* e);
 int rb_reset_stats(rb_engine* e) {
     if (!e) return RB_ERR_NULL_ARGUMENT;
     std::lock_guard<std::mutex> lock(e->mu);
-    if (is_group(e)) {
+    if (rb::is_group(e)) {
         for (auto& p : e->parts) PART_TRY(e, p.get(), part_reset_stats(p.get()));
         return RB_OK;
     }
-    set_device(e);
+    rb::set_device(e);
     return part_reset_stats(e);
 }
 
@@ -1895,7 +1367,7 @@ static int part_reset_stats(rb_engine* e) {
 int rb_last_dispatch_ms(rb_engine* e, float* ms) {
     if (!e || !ms) return RB_ERR_NULL_ARGUMENT;
     std::lock_guard<std::mutex> lock(e->mu);
-    if (is_group(e)) {
+    if (rb::is_group(e)) {
         *ms = 0.0f;
         for (auto& p : e->parts) {
             PART_TRY(e, p.get(), accumulate_timing(p.get()));
@@ -1903,129 +1375,18 @@ int rb_last_dispatch_ms(rb_engine* e, float* ms) {
         }
         return RB_OK;
     }
-    set_device(e);
+    rb::set_device(e);
     int rc = accumulate_timing(e);
     if (rc) return rc;
     *ms = e->last_dispatch_ms;
     return RB_OK;
 }
 
-int rb_bvh_build(const rb_gpu_triangle* tris, size_t n_tris, rb_bvh_node* nodes_out, size_t nodes_capacity,
-                 size_t* n_nodes, uint32_t* indices_out) {
-    if (!n_nodes || (n_tris > 0 && !tris)) return RB_ERR_NULL_ARGUMENT;
-    std::vector<rb_bvh_node> nodes;
-    std::vector<uint32_t> indices;
-    rb::bvh_build(tris, n_tris, nodes, indices);
-    *n_nodes = nodes.size();
-    if (!nodes_out) return RB_OK;
-    if (nodes_capacity < nodes.size()) return RB_ERR_INVALID_BVH;
-    std::memcpy(nodes_out, nodes.data(), nodes.size() * sizeof(rb_bvh_node));
-    if (indices_out) std::memcpy(indices_out, indices.data(), indices.size() * sizeof(uint32_t));
-    return RB_OK;
-}
-
-int rb_bvh_build_canonical(const rb_gpu_triangle* tris, size_t n_tris, rb_bvh_node* nodes_out, size_t nodes_capacity,
-                           size_t* n_nodes, uint32_t* indices_out) {
-    if (!n_nodes) return RB_ERR_NULL_ARGUMENT;
-    if (n_tris >= (1ull << 31)) return fail(nullptr, RB_ERR_INVALID_BVH, "too many triangles");
-    *n_nodes = rb::bvh_node_count(n_tris);
-    if (!nodes_out) return RB_OK;   // the size query follows from n_tris alone: no build
-    if (n_tris > 0 && !tris) return RB_ERR_NULL_ARGUMENT;
-    if (nodes_capacity < *n_nodes) return RB_ERR_INVALID_BVH;
-    const size_t bad = rb::first_non_finite(tris, n_tris);
-    if (bad < n_tris) return fail(nullptr, RB_ERR_INVALID_BVH, "triangle %zu has a non-finite vertex coordinate", bad);
-    std::vector<rb_bvh_node> nodes;
-    std::vector<uint32_t> indices;
-    rb::bvh_build_canonical(tris, n_tris, nodes, indices);
-    std::memcpy(nodes_out, nodes.data(), nodes.size() * sizeof(rb_bvh_node));
-    if (indices_out) std::memcpy(indices_out, indices.data(), indices.size() * sizeof(uint32_t));
-    return RB_OK;
-}
-
-int rb_bvh_build_device(int32_t device, const rb_gpu_triangle* tris, size_t n_tris, rb_bvh_node* nodes_out, size_t nodes_capacity,
-                        size_t* n_nodes, uint32_t* indices_out) {
-    if (!n_nodes) return RB_ERR_NULL_ARGUMENT;
-    if (n_tris >= (1ull << 31)) return fail(nullptr, RB_ERR_INVALID_BVH, "too many triangles");
-    const size_t nn = rb::bvh_node_count(n_tris);
-    *n_nodes = nn;
-    if (!nodes_out) return RB_OK;   // the size query touches no device (nor the triangles)
-    if (n_tris > 0 && !tris) return RB_ERR_NULL_ARGUMENT;
-    if (nodes_capacity < nn) return RB_ERR_INVALID_BVH;
-    const size_t bad = rb::first_non_finite(tris, n_tris);
-    if (bad < n_tris) return fail(nullptr, RB_ERR_INVALID_BVH, "triangle %zu has a non-finite vertex coordinate", bad);
-    if (n_tris == 0) return RB_OK;
-    if (device >= 0 && hipSetDevice(device) != hipSuccess) return fail(nullptr, RB_ERR_DEVICE, "hipSetDevice(%d) failed", device);
-    rb_gpu_triangle* d_tris = nullptr;
-    rb_bvh_node* d_nodes = nullptr;
-    uint32_t* d_idx = nullptr;
-    hipStream_t stream = nullptr;
-    hipError_t st = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
-    if (st == hipSuccess) st = hipMalloc(reinterpret_cast<void**>(&d_tris), sizeof(rb_gpu_triangle) * n_tris);
-    if (st == hipSuccess) st = hipMalloc(reinterpret_cast<void**>(&d_nodes), sizeof(rb_bvh_node) * nn);
-    if (st == hipSuccess) st = hipMalloc(reinterpret_cast<void**>(&d_idx), 4u * n_tris);
-    if (st == hipSuccess) st = hipMemcpyAsync(d_tris, tris, sizeof(rb_gpu_triangle) * n_tris, hipMemcpyHostToDevice, stream);
-    if (st == hipSuccess) st = static_cast<hipError_t>(rb::device_reference_bvh_build(d_tris, static_cast<uint32_t>(n_tris), d_nodes, d_idx, stream));
-    if (st == hipSuccess) st = hipMemcpyAsync(nodes_out, d_nodes, sizeof(rb_bvh_node) * nn, hipMemcpyDeviceToHost, stream);
-    if (st == hipSuccess && indices_out) st = hipMemcpyAsync(indices_out, d_idx, 4u * n_tris, hipMemcpyDeviceToHost, stream);
-    if (st == hipSuccess) st = hipStreamSynchronize(stream);
-    if (stream) (void)hipStreamSynchronize(stream);
-    (void)hipFree(d_tris);
-    (void)hipFree(d_nodes);
-    (void)hipFree(d_idx);
-    if (stream) (void)hipStreamDestroy(stream);
-    if (st != hipSuccess) return fail(nullptr, RB_ERR_DEVICE, "device tree build failed: %s", hipGetErrorString(st));
-    return RB_OK;
-}
-
-int rb_engine_tree(rb_engine* e, rb_bvh_node* nodes_out, size_t nodes_capacity, size_t* n_nodes, uint32_t* indices_out,
-                   size_t indices_capacity, size_t* n_indices) {
-    if (!e || !n_nodes || !n_indices) return RB_ERR_NULL_ARGUMENT;
-    rb_engine* g = e;
-    std::unique_lock<std::mutex> group_lock;
-    if (is_group(e)) {   // the handle's own lock first, then the part's (every part holds the same tree)
-        group_lock = std::unique_lock<std::mutex>(g->mu);
-        e = e->parts[0].get();
-    }
-    std::lock_guard<std::mutex> lock(e->mu);
-    const size_t nn = e->host_nodes.size(), ni = nn ? e->n_indices : 0;
-    *n_nodes = nn;
-    *n_indices = ni;
-    if (nodes_out) {
-        if (nodes_capacity < nn) return fail(g, RB_ERR_INVALID_BVH, "nodes_out holds %zu of %zu nodes", nodes_capacity, nn);
-        if (nn) std::memcpy(nodes_out, e->host_nodes.data(), sizeof(rb_bvh_node) * nn);
-    }
-    if (indices_out && ni) {
-        if (indices_capacity < ni) return fail(g, RB_ERR_INVALID_BVH, "indices_out holds %zu of %zu indices", indices_capacity, ni);
-        set_device(e);
-        HIP_TRY(e, hipStreamSynchronize(e->stream));
-        HIP_TRY(e, hipMemcpy(indices_out, e->indices.ptr, 4u * ni, hipMemcpyDeviceToHost));
-    }
-    return RB_OK;
-}
-
-const char* rb_tree_builder(const rb_engine* e, float* build_ms) {
-    if (e && is_group(e)) e = e->parts[0].get();
-    if (build_ms) *build_ms = e ? e->tree_build_ms : 0.0f;
-    return (e && !e->host_nodes.empty()) ? e->tree_builder : "";
-}
-
 const char* rb_version(void) { return "renderbaby-hip 0.3 (gfx950)"; }
 
 const char* rb_last_kernel_name(const rb_engine* e) {
     if (!e) return "";
-    return is_group(e) ? e->parts[0]->last_kernel_name : e->last_kernel_name;
-}
-
-const char* rb_fast_bvh_builder(const rb_engine* e, float* build_ms) {
-    if (e && is_group(e)) e = e->parts[0].get();
-    if (build_ms) *build_ms = e ? e->fast_build_ms : 0.0f;
-    return (e && e->fast_ready) ? e->fast_builder : "";
-}
-
-const char* rb_sphere_tree_builder(const rb_engine* e, float* build_ms) {
-    if (e && is_group(e)) e = e->parts[0].get();
-    if (build_ms) *build_ms = (e && e->sph_bvh) ? e->sph_build_ms : 0.0f;
-    return (e && e->sph_bvh) ? e->sph_builder : "";
+    return rb::is_group(e) ? e->parts[0]->last_kernel_name : e->last_kernel_name;
 }
 
 int rb_device_name(int device, char* buf, size_t buf_len) {
@@ -2065,78 +1426,6 @@ int rb_debug_div_exhaustive(uint32_t b_begin, uint32_t b_count, uint32_t ea, uin
     (void)hipMemcpy(out16, d, 128, hipMemcpyDeviceToHost);
     (void)hipFree(d);
     return (rc || st != hipSuccess) ? RB_ERR_DEVICE : RB_OK;
-}
-
-namespace {
-void chunk_tree_census(const rb::ChunkTree& t, uint64_t out6[6]) {
-    uint64_t chunks = 0, unbounded = 0;
-    for (const rb::ChunkNode& c : t.nodes) {
-        chunks += ((c.lref != rb::kChunkNone && (c.lref & rb::kChunkLeaf)) ? 1 : 0) + ((c.rref != rb::kChunkNone && (c.rref & rb::kChunkLeaf)) ? 1 : 0);
-        unbounded += ((c.lref != rb::kChunkNone && (c.lfac >> 16) == 0x7F80u) ? 1 : 0) + ((c.rref != rb::kChunkNone && (c.rfac >> 16) == 0x7F80u) ? 1 : 0);
-    }
-    out6[0] = 1;
-    out6[1] = t.nodes.size();
-    out6[2] = t.pos_slot.size();
-    out6[3] = t.depth;
-    out6[4] = chunks;
-    out6[5] = unbounded;
-}
-}  // namespace
-
-// Test aid (host only): the chunked walk's tree for a mesh and a caller tree, with its invariants checked.
-int rb_debug_chunk_tree(const rb_gpu_triangle* tris, size_t n_tris, const rb_bvh_node* nodes, size_t n_nodes, const uint32_t* indices,
-                        size_t n_indices, uint64_t out6[6]) {
-    if (!tris || !nodes || !indices || !out6) return RB_ERR_NULL_ARGUMENT;
-    if (n_tris >= (1ull << 31) || n_nodes >= (1ull << 31) || n_indices >= (1ull << 31)) return RB_ERR_INVALID_BVH;
-    std::string why;
-    if (!rb::bvh_validate(nodes, static_cast<uint32_t>(n_nodes), rb::kStackDepth, why, nullptr)) return fail(nullptr, RB_ERR_INVALID_BVH, "%s", why.c_str());
-    rb::ChunkTree t;
-    for (int i = 0; i < 6; ++i) out6[i] = 0;
-    if (!rb::chunk_tree_build(tris, static_cast<uint32_t>(n_tris), indices, static_cast<uint32_t>(n_indices), nodes,
-                              static_cast<uint32_t>(n_nodes), rb::kStackDepth, t))
-        return RB_OK;   // out6[0] == 0: this tree is left to another walk
-    if (!rb::chunk_tree_check(t, tris, static_cast<uint32_t>(n_tris), indices, static_cast<uint32_t>(n_indices), rb::kStackDepth, why))
-        return fail(nullptr, RB_ERR_INVALID_BVH, "chunk tree: %s", why.c_str());
-    chunk_tree_census(t, out6);
-    return RB_OK;
-}
-
-int rb_debug_engine_chunk_tree(rb_engine* e, uint64_t out6[6]) {
-    if (!e || !out6) return RB_ERR_NULL_ARGUMENT;
-    if (is_group(e)) e = e->parts[0].get();
-    std::lock_guard<std::mutex> lock(e->mu);
-    set_device(e);
-    for (int i = 0; i < 6; ++i) out6[i] = 0;
-    if (!e->chunk_ready) return RB_OK;
-    rb::ChunkTree t;
-    const size_t n = e->chunk_rank_slot.count;
-    t.nodes.resize(e->chunk_n_nodes);
-    t.pos_slot.resize(n);
-    t.pos_rank.resize(n);
-    t.rank_slot.resize(n);
-    t.root = e->chunk_root;
-    t.depth = e->chunk_depth;
-    HIP_TRY(e, hipStreamSynchronize(e->stream));
-    HIP_TRY(e, hipMemcpy(t.nodes.data(), e->chunk_nodes.ptr, sizeof(rb::ChunkNode) * t.nodes.size(), hipMemcpyDeviceToHost));
-    HIP_TRY(e, hipMemcpy(t.pos_slot.data(), e->chunk_pos_slot.ptr, 4u * n, hipMemcpyDeviceToHost));
-    HIP_TRY(e, hipMemcpy(t.pos_rank.data(), e->chunk_pos_rank.ptr, 4u * n, hipMemcpyDeviceToHost));
-    HIP_TRY(e, hipMemcpy(t.rank_slot.data(), e->chunk_rank_slot.ptr, 4u * n, hipMemcpyDeviceToHost));
-    std::string why;
-    {
-        const int hrc = ensure_host_mesh(e);
-        if (hrc) return hrc;
-    }
-    const uint32_t n_tris = std::min<uint32_t>(e->prep_tri_count, static_cast<uint32_t>(e->host_tris.size()));
-    if (!rb::chunk_tree_check(t, e->host_tris.data(), n_tris, e->host_indices.data(), static_cast<uint32_t>(e->host_indices.size()), rb::kStackDepth, why))
-        return fail(e, RB_ERR_INVALID_BVH, "chunk tree (%s builder): %s", e->chunk_builder, why.c_str());
-    chunk_tree_census(t, out6);
-    return RB_OK;
-}
-
-const char* rb_chunk_tree_builder(const rb_engine* e, float* build_ms) {
-    if (e && is_group(e)) e = e->parts[0].get();
-    if (build_ms) *build_ms = (e && e->chunk_ready) ? e->chunk_build_ms : 0.0f;
-    return (e && e->chunk_ready) ? e->chunk_builder : "";
 }
 
 int rb_measure_l1_gather(int32_t device, uint64_t table_bytes, double* accesses_per_s) {
