@@ -512,6 +512,56 @@ int rb_debug_div_exhaustive(uint32_t b_begin, uint32_t b_count, uint32_t ea, uin
  * "k_queue", "k_pixel"). */
 const char* rb_last_kernel_name(const rb_engine* e);
 
+/* ---- Closest-hit queries (no reference counterpart).  A query answers, for one ray: what does
+ * `closest_hit` hold at shader.wgsl:603, after the ground, BVH, sphere and point-light stages of one bounce-loop iteration?
+ * Same category order, strict `<`, `t > 0.001`, 1e20 start, phantom light, kept counts and numerics contract as a render of
+ * the uploaded scene.  A query draws no random number and touches neither the accumulation, the RGBA8 frame, the colour
+ * buffer nor the work counters (rb_get_stats does not move); a pass the progressive iterator has started ahead stays valid. */
+typedef struct rb_ray { float origin[3]; float _pad0; float dir[3]; float _pad1; } rb_ray;          /* 32 B */
+enum { RB_HIT_NONE = 0, RB_HIT_GROUND = 1, RB_HIT_TRIANGLE = 2, RB_HIT_SPHERE = 3, RB_HIT_LIGHT = 4,
+       RB_HIT_INVALID = 0xFFFFFFFFu };
+typedef struct rb_hit {                                                                             /* 48 B */
+    float t;            /* closest_hit.t; 1e20f for NONE / INVALID */
+    uint32_t kind;      /* RB_HIT_* */
+    uint32_t prim;      /* triangle: index into bvh_triangles; sphere / light: its index; else 0xFFFFFFFF */
+    uint32_t mesh;      /* triangle: its mesh_index; else 0xFFFFFFFF */
+    float u, v;         /* triangle: the barycentrics intersect_triangle returned for the winner; else 0 */
+    uint32_t _pad[2];
+    float normal[3];    /* closest_hit.normal as the shader sets it (no flip); 0 for NONE / INVALID */
+    float _pad1;
+} rb_hit;
+typedef struct rb_surface {                                                                         /* 48 B */
+    float albedo[3];    /* what :644-651 would multiply into the attenuation (specular if is_metal, else diffuse x texture); 0 for NONE / INVALID */
+    uint32_t flags;     /* bit 0 is_metal, bit 1 use_texture */
+    float emissive[3];  /* closest_hit.material.emissive; NONE: uniforms.sky_color; INVALID: 0 */
+    int32_t texture_index;
+    float uv[2];        /* closest_hit.uv as the shader leaves it */
+    float _pad[2];
+} rb_surface;
+/* n rays from host memory (pageable, or page-locked as rb_render recognises it) against the uploaded scene; hits_out[n], and
+ * surf_out[n] unless NULL.  The device normalises `dir` (v / sqrt((x x + y y) + z z)) and measures t along the normalised
+ * direction: the walks' culling margins are derived for |d| = 1 +- 4 ulp.  A ray whose origin or normalised direction has a
+ * non-finite or all-zero component set (a zero direction, or one so long that its squared length overflows) is RB_HIT_INVALID and is not walked.  Rays go through the device in
+ * pieces of at most 2^22 rays (128 MiB of rays, 2 x 192 MiB of records: the scratch does not grow with n).  n > 2^31 - 64 is
+ * RB_ERR_INVALID_OPTIONS; n == 0 is RB_OK.
+ * The walk is the one a render of this scene with this engine's flags takes: the chunked walk for multi-node meshes by
+ * default, the per-lane reference walk under RB_FLAG_REFERENCE_WALK and for trees of at most one node, the sphere tree for
+ * more than 64 spheres.  RB_FLAG_FAST_BVH engines are answered by the per-lane reference walk over the caller's tree: the
+ * library's own tree has no query form (it returns the same winner by construction). */
+int rb_cast_rays(rb_engine* e, const rb_ray* rays, size_t n, rb_hit* hits_out, rb_surface* surf_out);
+/* One ray per pixel through the pixel CENTRE (the primary ray of the render with both jitter offsets 0), in the
+ * orientation of the delivered RGBA8 frame: row-major, top row first, x mirrored -- a pixel of the displayed image indexes its
+ * record.  A sharded engine delivers its padded_rows local rows in local stripe order like rb_read_accumulation (rows of the
+ * padding: RB_HIT_INVALID); a multi-device handle the whole frame, computed on devices[0]. */
+int rb_render_hits(rb_engine* e, rb_hit* hits_out, rb_surface* surf_out);
+/* rb_render_hits for one displayed pixel (px from the left, py from the top of the whole image, also on a sharded engine). */
+int rb_pick(rb_engine* e, uint32_t px, uint32_t py, rb_hit* hit_out, rb_surface* surf_out);
+/* Name of the kernel the most recent query used ("k_query", "k_query_bvh", "k_query_chunk"; "" before the first). */
+const char* rb_last_query_kernel_name(const rb_engine* e);
+/* Measurement aid for tools/query_rate.py, not part of the query interface (it may change or go): kernel time of the most
+ * recent query, HIP events around its launches, summed over the pieces, ms. */
+int rb_last_query_ms(rb_engine* e, float* ms);
+
 /* Which builder produced the library's own tree: "host-sah", "device-ploc", "device-lbvh", or "" when
  * there is none (flag not set, single-node tree, or the scene keeps the exact walk).  Valid after the
  * first rb_dispatch / rb_render that follows an update.  `build_ms`, if not NULL, receives the wall
@@ -556,6 +606,16 @@ static_assert(offsetof(rb_material, emissive) == 48, "emissive @48");
 static_assert(offsetof(rb_material, texture_index) == 72, "texture_index @72");
 static_assert(offsetof(rb_bvh_node, left) == 32, "left @32");
 static_assert(offsetof(rb_gpu_triangle, mesh_index) == 48, "mesh_index @48");
+static_assert(sizeof(rb_ray) == 32, "rb_ray is 32 B");
+static_assert(sizeof(rb_hit) == 48, "rb_hit is 48 B");
+static_assert(sizeof(rb_surface) == 48, "rb_surface is 48 B");
+static_assert(offsetof(rb_ray, dir) == 16, "dir @16");
+static_assert(offsetof(rb_hit, u) == 16, "u @16");
+static_assert(offsetof(rb_hit, normal) == 32, "normal @32");
+static_assert(offsetof(rb_surface, flags) == 12, "flags @12");
+static_assert(offsetof(rb_surface, emissive) == 16, "emissive @16");
+static_assert(offsetof(rb_surface, texture_index) == 28, "texture_index @28");
+static_assert(offsetof(rb_surface, uv) == 32, "uv @32");
 #else
 _Static_assert(sizeof(rb_camera) == 48, "Camera is 48 B");
 _Static_assert(sizeof(rb_uniforms) == 144, "Uniforms is 144 B");
@@ -567,6 +627,9 @@ _Static_assert(sizeof(rb_bvh_node) == 48, "BVHNode is 48 B");
 _Static_assert(sizeof(rb_gpu_triangle) == 64, "GPUTriangle is 64 B");
 _Static_assert(sizeof(rb_texture_info) == 16, "TextureInfo is 16 B");
 _Static_assert(sizeof(rb_progressive) == 16, "ProgressiveRenderHelper is 16 B");
+_Static_assert(sizeof(rb_ray) == 32, "rb_ray is 32 B");
+_Static_assert(sizeof(rb_hit) == 48, "rb_hit is 48 B");
+_Static_assert(sizeof(rb_surface) == 48, "rb_surface is 48 B");
 #endif
 
 #endif /* RB_ABI_H */

@@ -168,6 +168,38 @@ class Engine final : public Renderer {
         check(h_->e, rb_iter_begin(h_->e, &m.c));
         return std::make_unique<Iter>(h_);
     }
+    // ---- closest-hit queries (extension; rb_abi.h): what closest_hit holds for a ray, without shading
+    struct Hits {
+        uint32_t width = 0, rows = 0;       // rows: the image height (a sharded engine: its padded local rows)
+        std::vector<rb_hit> hits;           // [row * width + x], orientation of the delivered frame
+        std::vector<rb_surface> surfaces;   // empty unless asked for
+    };
+    Hits cast_rays(const std::vector<rb_ray>& rays, bool surfaces = false) {
+        Hits r;
+        r.width = static_cast<uint32_t>(rays.size());
+        r.rows = 1;
+        r.hits.resize(rays.size());
+        if (surfaces) r.surfaces.resize(rays.size());
+        check(h_->e, rb_cast_rays(h_->e, rays.data(), rays.size(), r.hits.data(), surfaces ? r.surfaces.data() : nullptr));
+        return r;
+    }
+    Hits render_hits(bool surfaces = false) {
+        Hits r;
+        uint32_t h = 0, owned = 0, padded = 0;
+        check(h_->e, rb_get_size(h_->e, &r.width, &h));
+        check(h_->e, rb_local_rows(h_->e, &owned, &padded));
+        r.rows = padded;   // == height unless sharded
+        r.hits.resize(static_cast<size_t>(r.width) * r.rows);
+        if (surfaces) r.surfaces.resize(r.hits.size());
+        check(h_->e, rb_render_hits(h_->e, r.hits.data(), surfaces ? r.surfaces.data() : nullptr));
+        return r;
+    }
+    // the displayed pixel (px from the left, py from the top): "sphere 3" / "mesh 2, triangle 517" for a click
+    rb_hit pick(uint32_t px, uint32_t py, rb_surface* surface = nullptr) {
+        rb_hit hit{};
+        check(h_->e, rb_pick(h_->e, px, py, &hit, surface));
+        return hit;
+    }
     rb_engine* raw() const { return h_->e; }
 };
 

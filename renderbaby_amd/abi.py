@@ -40,9 +40,20 @@ GPU_TRIANGLE = np.dtype([("v0", f4, (3,)), ("v0_index", u4), ("v1", f4, (3,)), (
                          ("v2", f4, (3,)), ("v2_index", u4), ("mesh_index", u4),
                          ("_pad0", u4), ("_pad1", u4), ("_pad2", u4)])
 
+# closest-hit queries (rb_cast_rays / rb_render_hits / rb_pick)
+RAY = np.dtype([("origin", f4, (3,)), ("_pad0", f4), ("dir", f4, (3,)), ("_pad1", f4)])
+HIT = np.dtype([("t", f4), ("kind", u4), ("prim", u4), ("mesh", u4), ("u", f4), ("v", f4), ("_pad", u4, (2,)),
+                ("normal", f4, (3,)), ("_pad1", f4)])
+SURFACE = np.dtype([("albedo", f4, (3,)), ("flags", u4), ("emissive", f4, (3,)), ("texture_index", i4),
+                    ("uv", f4, (2,)), ("_pad", f4, (2,))])
+HIT_NONE, HIT_GROUND, HIT_TRIANGLE, HIT_SPHERE, HIT_LIGHT, HIT_INVALID = 0, 1, 2, 3, 4, 0xFFFFFFFF
+SURFACE_IS_METAL, SURFACE_USE_TEXTURE = 1, 2
+NO_INDEX = 0xFFFFFFFF
+
 SIZES = {"camera": (CAMERA, 48), "uniforms": (UNIFORMS, 144), "material": (MATERIAL, 80),
          "sphere": (SPHERE, 96), "point_light": (POINT_LIGHT, 96), "mesh": (MESH, 96),
-         "bvh_node": (BVH_NODE, 48), "gpu_triangle": (GPU_TRIANGLE, 64)}
+         "bvh_node": (BVH_NODE, 48), "gpu_triangle": (GPU_TRIANGLE, 64),
+         "ray": (RAY, 32), "hit": (HIT, 48), "surface": (SURFACE, 48)}
 for _n, (_dt, _sz) in SIZES.items():
     assert _dt.itemsize == _sz, (_n, _dt.itemsize, _sz)
 
@@ -97,6 +108,20 @@ class Options(C.Structure):
     _fields_ = [("device", C.c_int32), ("shard_rank", C.c_uint32), ("shard_count", C.c_uint32),
                 ("stripe_rows", C.c_uint32), ("passes_per_launch", C.c_uint32), ("kernel", C.c_uint32),
                 ("flags", C.c_uint32), ("_reserved", C.c_uint32 * 5)]
+
+
+class Ray(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("_pad0", C.c_float), ("dir", C.c_float * 3), ("_pad1", C.c_float)]
+
+
+class Hit(C.Structure):
+    _fields_ = [("t", C.c_float), ("kind", C.c_uint32), ("prim", C.c_uint32), ("mesh", C.c_uint32), ("u", C.c_float),
+                ("v", C.c_float), ("_pad", C.c_uint32 * 2), ("normal", C.c_float * 3), ("_pad1", C.c_float)]
+
+
+class Surface(C.Structure):
+    _fields_ = [("albedo", C.c_float * 3), ("flags", C.c_uint32), ("emissive", C.c_float * 3),
+                ("texture_index", C.c_int32), ("uv", C.c_float * 2), ("_pad", C.c_float * 2)]
 
 
 class Stats(C.Structure):

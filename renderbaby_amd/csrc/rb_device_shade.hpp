@@ -420,6 +420,127 @@ DEV bool segment_post(const KParams& p, Path& pt, const TriHit th, const SegStat
     return pt.depth < p.u.max_depth;
 }
 
+// The closest-hit QUERY's end of a segment (rb_query.hip): what segment_post does between the spheres and
+// "is_metal" -- point lights, sky, the winner's HitRecord fields -- written out as the three 16-byte quads of an rb_hit and of
+// an rb_surface instead of being shaded.  No random number is drawn and nothing but `out` is written.
+struct HitQuads {
+    v4f h0, h1, h2, s0, s1, s2;   // (named members: an array here ends up in scratch memory)
+};
+DEV void hit_quads_empty(HitQuads& out, uint32_t kind, f3 emissive) {
+    const uint32_t none = 0xFFFFFFFFu;
+    out.h0 = v4f{1e20f, __uint_as_float(kind), __uint_as_float(none), __uint_as_float(none)};
+    out.h1 = out.h2 = out.s0 = out.s2 = v4f{0.0f, 0.0f, 0.0f, 0.0f};
+    out.s1 = v4f{emissive.x, emissive.y, emissive.z, __uint_as_float(none)};   // texture_index -1
+}
+DEV void segment_resolve(const KParams& p, f3 o, f3 d, const TriHit th, const SegState st, float closest_t, uint32_t sphere_idx,
+                         HitQuads& out) {
+    const float a = dot(d, d);
+    uint32_t kind = st.kind;
+    float uvx = st.uvx, uvy = st.uvy;
+    bool use_tex = st.use_tex;
+    const bool tri_won_a = st.tri_won_a;
+    if (sphere_idx != 0xFFFFFFFFu) kind = K_SPHERE;
+
+    // Point lights :590-601 (arrayLength: the phantom light of an empty buffer is scanned like any other)
+    uint32_t light_idx = 0xFFFFFFFFu;
+    const cf4p lgt4 = (cf4p)p.lights;
+    for (uint32_t base = 0; base < p.n_lights; base += 32u) {
+        const uint32_t n = (p.n_lights - base < 32u) ? p.n_lights - base : 32u;
+        uint32_t cand = 0u;
+        for (uint32_t k = 0; k < n; k++) {
+            const v4f cr = lgt4[(base + k) * 6u];
+            const f3 oc = o - mk(cr.x, cr.y, cr.z);
+            const float half_b = dot(oc, d);
+            const float c = dot(oc, oc) - cr.w * cr.w;
+            const float disc = half_b * half_b - a * c;
+            cand |= (disc < 0.0f) ? 0u : (1u << k);
+        }
+        while (cand != 0u) {
+            const uint32_t k = (uint32_t)__ffs((int)cand) - 1u;
+            cand &= cand - 1u;
+            const v4f cr = lgt4[(base + k) * 6u];
+            const float t = isect_sphere(o, d, a, mk(cr.x, cr.y, cr.z), cr.w);
+            if (t > 0.001f && t < closest_t) {
+                closest_t = t;
+                light_idx = base + k;
+            }
+        }
+    }
+    if (light_idx != 0xFFFFFFFFu) kind = K_LIGHT;
+
+    if (kind == K_NONE) {   // :604-608
+        hit_quads_empty(out, K_NONE, ld3(p.u.sky_color));
+        return;
+    }
+
+    const f3 pos = o + closest_t * d;
+    f3 normal = mk(0.0f, 1.0f, 0.0f);
+    uint32_t prim = 0xFFFFFFFFu, mesh = 0xFFFFFFFFu;
+    float bu = 0.0f, bv = 0.0f;
+    Mat m;
+    m.diffuse = mk(0, 0, 0);
+    m.specular = mk(0, 0, 0);
+    m.emissive = mk(0, 0, 0);
+    m.fuzz = 1.0f;
+    m.metal = false;
+    m.tex = -1;
+    if (tri_won_a) {
+        // :361-372: the BVH hit replaced closest_hit with its uv and use_texture, whoever wins afterwards
+        const cu4p pr = (cu4p)p.ptris + th.slot * 4u;
+        const v4u p0 = pr[0], p1 = pr[1];
+        tri_uv(p, th, uvx, uvy);
+        if (p.u.color_hash_enabled != 0u) {
+            use_tex = false;
+            if (kind == K_TRI) m.diffuse = hash_to_color(p0.w + 1u);
+        } else {
+            const rb_material* mm = &p.meshes[p1.w].material;
+            if (kind == K_TRI) {
+                m = load_mat(mm);
+                use_tex = m.tex >= 0;
+            } else {
+                use_tex = load_tex_index(mm) >= 0;
+            }
+        }
+        if (kind == K_TRI) {
+            prim = p0.w;
+            mesh = p1.w;
+            bu = th.u;
+            bv = th.v;
+            const v4f s = ((cf4p)p.ptris)[th.slot * 4u + 3u];
+            normal = mk(s.x, s.y, s.z);
+        }
+    }
+    if (kind == K_GROUND) m.diffuse = mk(0.5f, 0.5f, 0.5f);
+    if (sphere_idx != 0xFFFFFFFFu) {
+        const rb_sphere* s = p.spheres + sphere_idx;
+        if (kind == K_SPHERE) {
+            m = load_mat(&s->material);
+            use_tex = m.tex >= 0;
+            const v4f cr = ((cf4p)s)[0];
+            normal = normalize(pos - mk(cr.x, cr.y, cr.z));
+            prim = sphere_idx;
+        } else {
+            use_tex = load_tex_index(&s->material) >= 0;   // the sphere won before a light did: lights do not reset use_texture
+        }
+    }
+    if (kind == K_LIGHT) {
+        const rb_point_light* l = p.lights + light_idx;
+        m = load_mat(&l->material);
+        const v4f cr = ((cf4p)l)[0];
+        normal = normalize(pos - mk(cr.x, cr.y, cr.z));
+        prim = light_idx;
+    }
+    // :644-651
+    f3 albedo = m.metal ? m.specular : m.diffuse;
+    if (!m.metal && use_tex) albedo = albedo * sample_texture(p, m.tex, uvx, uvy);
+    out.h0 = v4f{closest_t, __uint_as_float(kind), __uint_as_float(prim), __uint_as_float(mesh)};
+    out.h1 = v4f{bu, bv, 0.0f, 0.0f};
+    out.h2 = v4f{normal.x, normal.y, normal.z, 0.0f};
+    out.s0 = v4f{albedo.x, albedo.y, albedo.z, __uint_as_float((m.metal ? 1u : 0u) | (use_tex ? 2u : 0u))};
+    out.s1 = v4f{m.emissive.x, m.emissive.y, m.emissive.z, __uint_as_float((uint32_t)m.tex)};
+    out.s2 = v4f{uvx, uvy, 0.0f, 0.0f};
+}
+
 // One iteration of the bounce loop after the triangle traversal (`th`: its winner).
 template <bool STATS, bool SPHTREE = true>
 DEV bool segment_finish(const KParams& p, Path& pt, const TriHit th, uint32_t* stack, uint32_t stride,

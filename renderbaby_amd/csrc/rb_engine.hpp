@@ -164,6 +164,15 @@ struct rb_engine {
     std::vector<rb_bvh_node> host_nodes;  // kept for validation when nodes/indices change separately
     uint32_t width = 0, height = 0, local_rows = 0, padded_rows = 0;
 
+    // closest-hit queries (rb_cast_rays / rb_render_hits / rb_pick): scratch for one piece of at most rb::kQueryPiece rays (a
+    // frame piece: whole 8-row bands, so at least 8 x width records), the kernel and the kernel time of the last one; nothing of a render is touched
+    rb::DevBuf<rb_ray> q_rays;
+    rb::DevBuf<rb_hit> q_hits;
+    rb::DevBuf<rb_surface> q_surf;
+    hipEvent_t ev_q[2] = {nullptr, nullptr};
+    const char* last_query_kernel_name = "";
+    float last_query_ms = 0.0f;
+
     rb_stats stats{};
     float last_dispatch_ms = 0.0f;
     uint32_t last_launches = 0;

@@ -363,6 +363,30 @@ struct LaunchInfo {
     const char* kernel_name;
 };
 
+// ---- rb_query.hip: closest-hit queries.  One launch answers one piece: `n` rays of a device buffer, or
+// the pixel centres of a window of the frame in DISPLAYED coordinates (x mirrored like the RGBA8 frame).  `hits` / `surf` are
+// device buffers in the ABI's layout (record i = ray i, or window pixel (row, column) = row * win_w + column).
+struct QueryArgs {
+    const rb_ray* rays;       // nullptr: the pixel source
+    rb_hit* hits;
+    rb_surface* surf;         // may be nullptr
+    uint32_t n;               // ray source: rays in this piece
+    uint32_t win_x, win_y, win_w, win_h;   // pixel source: window origin (displayed x, row) and size
+    uint32_t win_global;      // pixel source: rows are image rows (else this shard's local rows)
+};
+#ifndef RB_QUERY_PIECE_LOG2
+#define RB_QUERY_PIECE_LOG2 22
+#endif
+// rays per launch: the query scratch is 128 + 192 + 192 MiB whatever n is (a frame piece: whole 8-row bands, so max(2^22, 8 x width)
+// records).  2^20 cost the lamp fixture 1.76 instead of 1.22 ms of kernel time: every piece ends in a tail, and the copy-out of
+// the piece before has pushed the tree out of L2 (five times the render's L2 misses per frame; profiles/r06_query_rate.txt)
+// rays per launch: the query scratch is 128 + 192 + 192 MiB whatever n is (a frame piece: whole 8-row bands, so max(2^22, 8 x width)
+// records).  2^20 cost the lamp fixture 1.76 instead of 1.22 ms of kernel time: every piece ends in a tail, and the copy-out of
+// the piece before has pushed the tree out of L2 (five times the render's L2 misses per frame; profiles/r06_query_rate.txt)
+constexpr uint32_t kQueryPiece = 1u << RB_QUERY_PIECE_LOG2;
+int launch_query(const KParams& p, const QueryArgs& q, void* stream, LaunchInfo* info);
+Cam host_cam(const rb_uniforms& u);   // rb_kernels.hip: the camera of a launch, shader.wgsl:690,702-708
+
 // ---- rb_kernels.hip
 // All return hipError_t as int (0 = success); launches are asynchronous on `stream`.
 int launch_render(const KParams& p, uint32_t kernel, bool stats, void* stream, LaunchInfo* info,

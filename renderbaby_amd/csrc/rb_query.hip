@@ -1,0 +1,330 @@
+// rb_query.hip -- closest-hit queries (rb_cast_rays / rb_render_hits / rb_pick): the closest-hit search
+// of one bounce-loop iteration (shader.wgsl:534-601) for a GIVEN ray, with the winner written out as an rb_hit and an
+// rb_surface instead of being shaded.  Same numerics contract as rb_kernels.hip (no FMA contraction, correctly rounded / and
+// sqrt), the same device functions for every test, and the walk a render of the scene would take:
+//   k_query        trees of at most one node and at most 64 spheres: the scans
+//   k_query_bvh    the per-lane reference walk (intersect_bvh) and, inside it, the per-lane sphere tree walk
+//   k_query_chunk  the chunked walk: k_trace_chunk's node and pooled leaf phases, then the same finish per lane
+// One ray per lane on a plain grid sized to the piece.  Measured against a depth-1 render of the same frame -- the persistent
+// grid with its item queue -- this form issues 15 % fewer vector instructions at a higher lane utilisation and, with pieces of
+// 2^22 rays, takes 14-17 % less time on the mesh scenes (profiles/r06_query_rate.txt); what did cost time was many small launches.
+//
+// Records leave through the wave's LDS corner: a lane's record is three 16-byte quads 48 bytes apart from its neighbour's, so
+// direct stores would touch every 64-byte sector of the wave's 3 KiB three times with a quarter of it each.  Staged, a wave
+// writes its 64 records as three stores of 64 consecutive quads (ray source) or as eight runs of 384 bytes (pixel source: one
+// run per row of its 8x8 tile) -- whole sectors -- and the device buffer is already in the ABI's layout: the read-back is one
+// copy, into page-locked caller memory a DMA with no host pass.  (Three planes of quads would coalesce as well but leave the
+// interleaving to the host.)
+#include "rb_device_chunk.hpp"
+
+#pragma clang fp contract(off)
+
+namespace rb {
+namespace {
+
+#ifndef RB_QUERY_BLOCK
+#define RB_QUERY_BLOCK 64
+#endif
+// threads per block (64, 128 or 256).  One wave per block: a block gives its LDS and its slot back when its wave's slowest ray is
+// done, not when the slowest of four waves is (lamp fixture 1.22 -> 1.17 ms, C5 1.68 -> 1.62 ms; profiles/r06_query_rate.txt)
+constexpr uint32_t kQueryBlock = RB_QUERY_BLOCK;
+static_assert(kQueryBlock == 64 || kQueryBlock == 128 || kQueryBlock == 256, "whole waves, at most the stacks' 256 columns");
+constexpr uint32_t kQueryWaveLds = 64u * 48u;   // one wave's 64 records of 48 B
+static_assert(kQueryWaveLds == kChunkWaveLds, "k_query_chunk stages its records in the corner its walk has finished with");
+
+// This lane's ray and where its record goes.
+struct QueryLane {
+    f3 o, d;
+    bool live;    // there is a ray (ray source: index < n; pixel source: inside the window)
+    bool valid;   // ... and it is finite after normalisation, and for a pixel inside the image
+};
+
+// shader.wgsl:693-709 for the pixel CENTRE: start_path_hashed's arithmetic with both offsets 0.0f
+DEV f3 centre_ray_dir(const KParams& p, uint32_t x, uint32_t y) {
+    const Cam& c = p.cam;
+    const float ax = (float)x + 0.0f, ay = (float)y + 0.0f;
+    float qx, qy;
+    if (c.fast_wh) {
+        qx = __builtin_copysignf(div_newton(ax, c.wm1, c.inv_wm1), ax);
+        qy = __builtin_copysignf(div_newton(ay, c.hm1, c.inv_hm1), ay);
+    } else {
+        qx = ax / c.wm1;
+        qy = ay / c.hm1;
+    }
+    const float u = ((qx * 2.0f) - 1.0f) * c.aspect;
+    const float v = 1.0f - qy * 2.0f;
+    return normalize(((c.fov * u) * ld3(c.right) + (c.fov * v) * ld3(c.up)) + ld3(c.fwd));
+}
+
+DEV bool finite3(f3 a) {
+    const uint32_t m = 0x7F800000u;
+    return (__float_as_uint(a.x) & m) != m && (__float_as_uint(a.y) & m) != m && (__float_as_uint(a.z) & m) != m;
+}
+// a direction the walks can take: finite and not zero (a vector whose squared length overflows normalises to (0, 0, 0): every
+// slab test would say "enter", and |d| = 1 +- 4 ulp, what the culling margins are derived for, would not hold)
+DEV bool usable_dir(f3 d) { return finite3(d) && !(d.x == 0.0f && d.y == 0.0f && d.z == 0.0f); }
+
+// `wave`: the wave's index in the launch.  Ray source: rays wave * 64 + lane.  Pixel source: tile `wave` of the window,
+// 8 x 8 pixels in DISPLAYED coordinates (x mirrored: shader x = width - 1 - displayed x).
+DEV QueryLane query_lane(const KParams& p, const QueryArgs q, uint32_t wave, uint32_t lane) {
+    QueryLane r;
+    r.o = r.d = mk(0, 0, 0);
+    if (q.rays != nullptr) {
+        const uint32_t i = wave * 64u + lane;
+        r.live = i < q.n;
+        if (r.live) {
+            const v4f a = ((const v4f*)q.rays)[(size_t)i * 2u], b = ((const v4f*)q.rays)[(size_t)i * 2u + 1u];
+            r.o = mk(a.x, a.y, a.z);
+            r.d = normalize(mk(b.x, b.y, b.z));
+        }
+        r.valid = r.live && finite3(r.o) && usable_dir(r.d);
+        return r;
+    }
+    const uint32_t tiles_x = (q.win_w + 7u) / 8u;
+    const uint32_t tx = wave % tiles_x, ty = wave / tiles_x;
+    const uint32_t cx = tx * 8u + (lane & 7u), cy = ty * 8u + (lane >> 3);
+    r.live = cx < q.win_w && cy < q.win_h;
+    const uint32_t xd = q.win_x + cx, row = q.win_y + cy;
+    const uint32_t y = q.win_global ? row : global_row(p, row);
+    r.valid = r.live && xd < p.u.width && y < p.u.height;
+    if (r.valid) {
+        r.o = ld3(p.cam.pos);
+        r.d = centre_ray_dir(p, p.u.width - 1u - xd, y);
+        r.valid = finite3(r.o) && usable_dir(r.d);
+    }
+    return r;
+}
+
+// The wave's 64 records (three quads per lane) through `stage` (64 * 48 B of LDS) to `dst` in the ABI's layout.
+DEV void store_records(const QueryArgs q, uint32_t wave, uint32_t lane, lds_v4f* stage, v4f rec0, v4f rec1, v4f rec2, void* dst_) {
+    v4f* const dst = (v4f*)dst_;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();   // whoever read this corner before is done with it
+    stage[lane * 3u] = rec0;
+    stage[lane * 3u + 1u] = rec1;
+    stage[lane * 3u + 2u] = rec2;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (uint32_t k = 0; k < 3u; k++) {
+        const uint32_t j = k * 64u + lane;   // quad j of the wave = quad j % 3 of its record j / 3
+        const v4f val = stage[j];
+        if (q.rays != nullptr) {
+            const uint32_t first = wave * 64u;   // (the last block's spare waves start beyond n: they store nothing)
+            const uint32_t n = first >= q.n ? 0u : q.n - first < 64u ? q.n - first : 64u;
+            if (j < n * 3u) dst[(size_t)first * 3u + j] = val;
+        } else {
+            const uint32_t tiles_x = (q.win_w + 7u) / 8u;   // (>= 1: the pixel source has no empty window)
+            const uint32_t tx = wave % tiles_x, ty = wave / tiles_x;
+            const uint32_t r = j / 24u, w = j % 24u;   // row of the tile, quad within the row's 8 records
+            const uint32_t cy = ty * 8u + r, cx = tx * 8u + w / 3u;
+            if (cy < q.win_h && cx < q.win_w) dst[((size_t)cy * q.win_w + tx * 8u) * 3u + w] = val;
+        }
+    }
+}
+
+// everything after the triangle walk: ground, spheres, lights, the winner's record, the stores
+DEV void query_finish(const KParams& p, const QueryArgs q, const QueryLane& ql, const TriHit th, uint32_t* stack, uint32_t stride,
+                      uint32_t wave, uint32_t lane, lds_v4f* stage) {
+    HitQuads out;
+    hit_quads_empty(out, 0xFFFFFFFFu /* RB_HIT_INVALID */, mk(0, 0, 0));
+    if (ql.valid) {
+        Tally<false> tl;
+        Path pt;
+        pt.o = ql.o;
+        pt.d = ql.d;
+        const SegState st = segment_pre<false>(fresh_params(p), pt, th, tl);
+        float closest_t = st.closest_t;
+        uint32_t sphere_idx = 0xFFFFFFFFu;
+        segment_spheres<false, true>(fresh_params(p), ql.o, ql.d, dot(ql.d, ql.d), closest_t, sphere_idx, stack, stride, tl);
+        segment_resolve(fresh_params(p), ql.o, ql.d, th, st, closest_t, sphere_idx, out);
+    }
+    store_records(q, wave, lane, stage, out.h0, out.h1, out.h2, q.hits);
+    if (q.surf != nullptr) store_records(q, wave, lane, stage, out.s0, out.s1, out.s2, q.surf);
+}
+
+// ---- the per-lane walks.  MULTI = false: trees of at most one node (the multi-node walk stays out of the kernel).
+template <bool MULTI>
+__global__ void __launch_bounds__(kQueryBlock) k_query(const KParams p, const QueryArgs q) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_stack[];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t wave = blockIdx.x * (kQueryBlock / 64u) + (tid >> 6);
+    uint32_t* const stack = stack_column(s_stack, tid);
+    lds_v4f* const stage = (lds_v4f*)(reinterpret_cast<unsigned char*>(s_stack + p.stack_depth * kQueryBlock) + (tid >> 6) * kQueryWaveLds);
+    const QueryLane ql = query_lane(fresh_params(p), q, wave, lane);
+    TriHit th;
+    th.hit = false;
+    th.t = 1e20f;
+    th.u = th.v = 0.0f;
+    th.slot = 0u;
+    if (ql.valid) {
+        Tally<false> tl;
+        th = intersect_bvh<false, MULTI>(fresh_params(p), ql.o, ql.d, stack, kQueryBlock, tl);
+    }
+    query_finish(p, q, ql, th, stack, kQueryBlock, wave, lane, stage);
+}
+
+// ---- the chunked walk: lane = ray at the nodes, lane = triangle for the pooled chunks (k_trace_chunk's phases 3 and 4
+// with nothing to refill: a lane leaves the loop's work when its walk is complete, the wave when all have).
+__global__ void __launch_bounds__(kQueryBlock) k_query_chunk(const KParams p, const QueryArgs q) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_stack[];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t wave = blockIdx.x * (kQueryBlock / 64u) + (tid >> 6);
+    uint32_t* const stack = stack_column(s_stack, tid);
+    unsigned char* const wl = reinterpret_cast<unsigned char*>(s_stack + p.stack_depth * kQueryBlock) + (tid >> 6) * kChunkWaveLds;
+    lds_v4f* const rayrec = (lds_v4f*)wl;                    // [64][2]: {o, chunk put aside}, {d, chunk stood at}
+    lds_u64* const best = (lds_u64*)(wl + 64u * 32u);        // [64]: (t bits) << 32 | rank
+    lds_u32* const units = (lds_u32*)(wl + 64u * 40u);       // [128]: ray lane (| 64: its second chunk) of every pooled (ray, chunk) pair
+    Tally<false> tl;
+
+    const QueryLane ql = query_lane(fresh_params(p), q, wave, lane);
+    const f3 o = ql.o, d = ql.d;
+    bool trav = false;
+    uint32_t cur = kChunkNone, pend = kChunkNone;
+    unsigned long long key = kChunkNoHit;
+    int sp = 0;
+    const f3 inv = mk(rcp_exact(d.x), rcp_exact(d.y), rcp_exact(d.z));
+    if (ql.valid) {   // the root's own box (shader.wgsl:283-315), then its two children
+        const KParams& fp = fresh_params(p);
+        const cf4p rn = (cf4p)fp.nodes;
+        const v4f n0 = rn[0], n1 = rn[1];
+        if (isect_aabb(o, inv, mk(n0.x, n0.y, n0.z), mk(n1.x, n1.y, n1.z))) {
+            cur = fp.chunk_root;
+            trav = true;
+        }
+    }
+    auto set_aside = [&]() {
+        if (trav && cur != kChunkNone && (cur & kChunkLeaf) != 0u && pend == kChunkNone) {
+            pend = cur;
+            if (sp == 0) {
+                cur = kChunkNone;
+            } else {
+                sp--;
+                cur = stack[sp * kQueryBlock];
+            }
+        }
+    };
+    set_aside();   // (a root that is one chunk)
+
+    while (__ballot(trav) != 0ull) {
+        // ---- tree: a few node steps while enough lanes are at a node
+#pragma unroll 1
+        for (int it = 0; it < RB_CHUNK_NODE_STEPS; ++it) {
+            const bool at_node = trav && cur != kChunkNone && (cur & kChunkLeaf) == 0u;
+            const uint32_t n = (uint32_t)__popcll(__ballot(at_node));
+            if (n == 0u || (it > 0 && n < (uint32_t)RB_CHUNK_NODE_LANES)) break;
+            if (at_node) {
+                if (!chunk_node_step<false>(p, stack, kQueryBlock, o, d, inv, __uint_as_float((uint32_t)(key >> 32)), cur, sp, tl)) {
+                    if (pend != kChunkNone) cur = kChunkNone;   // nothing left to walk, one chunk still to be tested
+                    else trav = false;
+                }
+                set_aside();
+            }
+        }
+        // ---- leaves: pool the (ray, chunk) pairs of the lanes that hold a chunk, kChunkTris lanes per pair
+        const bool lf = trav && cur != kChunkNone && (cur & kChunkLeaf) != 0u;   // waits at a chunk
+        const bool lp = trav && pend != kChunkNone;                              // holds one aside
+        const unsigned long long m = __ballot(lf), mp = __ballot(lp);
+        const uint32_t n_pend = (uint32_t)__popcll(mp), n_units = n_pend + (uint32_t)__popcll(m);
+        const uint32_t n_node = (uint32_t)__popcll(__ballot(trav && cur != kChunkNone && !lf));
+        if (n_units != 0u && (n_units >= (uint32_t)RB_CHUNK_LEAF_LANES || n_node == 0u)) {
+            const unsigned long long below = (1ull << lane) - 1ull;
+            if (lp) units[(uint32_t)__popcll(mp & below)] = lane;
+            if (lf) units[n_pend + (uint32_t)__popcll(m & below)] = lane | 64u;
+            if (lf || lp) {
+                const v4f r0 = {o.x, o.y, o.z, __uint_as_float(pend)}, r1 = {d.x, d.y, d.z, __uint_as_float(cur)};
+                rayrec[lane * 2u] = r0;
+                rayrec[lane * 2u + 1u] = r1;
+                best[lane] = key;
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            const cf4p ca = (cf4p)p.chunk_a, cb = (cf4p)p.chunk_b, cc = (cf4p)p.chunk_c;
+            constexpr uint32_t kPairsPerRound = 64u / kChunkTris;
+#pragma unroll 1
+            for (uint32_t g0 = 0; g0 < n_units; g0 += kPairsPerRound) {
+                const uint32_t g = g0 + lane / kChunkTris;
+                const bool ok = g < n_units;
+                const uint32_t e = units[ok ? g : 0u];   // (entry 0 exists: n_units != 0)
+                const uint32_t rl = e & 63u;
+                const v4f r0 = rayrec[rl * 2u], r1 = rayrec[rl * 2u + 1u];
+                const uint32_t ref = __float_as_uint((e & 64u) ? r1.w : r0.w), first = ref & 0x03FFFFFFu, cnt = ((ref >> 26) & 31u) + 1u;
+                const uint32_t j = lane & (kChunkTris - 1u);
+                const bool valid = ok && j < cnt;
+                const uint32_t pos = first + (j < cnt ? j : 0u);   // (position `first` exists: a chunk holds at least one triangle)
+                const v4f ta = ca[pos], tb = cb[pos], tc = cc[pos];
+                float u, v;
+                const float t = isect_triangle(mk(r0.x, r0.y, r0.z), mk(r1.x, r1.y, r1.z), mk(ta.x, ta.y, ta.z), mk(tb.x, tb.y, tb.z),
+                                               mk(tc.x, tc.y, tc.z), u, v);
+                if (valid && t > 0.001f) {
+                    const unsigned long long k = ((unsigned long long)__float_as_uint(t) << 32) | __float_as_uint(ta.w);
+                    __hip_atomic_fetch_min(&best[rl], k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            if (lf || lp) {
+                key = best[lane];
+                pend = kChunkNone;
+                if (lf || cur == kChunkNone) {   // the chunk the lane stood at is done, or there was nothing left to walk
+                    if (sp == 0) {
+                        trav = false;
+                    } else {
+                        sp--;
+                        cur = stack[sp * kQueryBlock];
+                    }
+                }
+                set_aside();
+            }
+        }
+    }
+
+    // ---- the winner's (t, u, v) again from its prepared record: the same operations on the same values
+    TriHit th;
+    th.hit = key != kChunkNoHit;
+    th.t = 1e20f;
+    th.u = th.v = 0.0f;
+    th.slot = 0u;
+    if (th.hit) {
+        const KParams& fp = fresh_params(p);
+        th.slot = cptr(fp.chunk_rank_slot)[(uint32_t)key];
+        const cf4p tp = (cf4p)fp.ptris + (size_t)th.slot * 4u;
+        const v4f a = tp[0], b = tp[1], c = tp[2];
+        th.t = isect_triangle(o, d, mk(a.x, a.y, a.z), mk(b.x, b.y, b.z), mk(c.x, c.y, c.z), th.u, th.v);
+    }
+    query_finish(p, q, ql, th, stack, kQueryBlock, wave, lane, (lds_v4f*)wl);
+}
+
+}  // namespace
+
+int launch_query(const KParams& p_, const QueryArgs& q, void* stream_, LaunchInfo* info) {
+    KParams p = p_;
+    p.cam = host_cam(p.u);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    LaunchInfo li{};
+    li.block = kQueryBlock;
+    const uint64_t waves = q.rays != nullptr ? ((uint64_t)q.n + 63u) / 64u : (uint64_t)((q.win_w + 7u) / 8u) * ((q.win_h + 7u) / 8u);
+    if (waves == 0u || waves > 0x7FFFFFFFull) return waves == 0u ? 0 : (int)hipErrorInvalidValue;
+    li.grid = (uint32_t)((waves + kQueryBlock / 64u - 1u) / (kQueryBlock / 64u));
+    li.lds_bytes = (size_t)kStackEntryBytes * p.stack_depth * kQueryBlock + (kQueryBlock / 64u) * kQueryWaveLds;
+    // the walk, by launch_render's rule for a render of this scene with these flags
+    const bool multi = p.u.bvh_node_count > 1u && !p.no_leaf_stepping;
+    const dim3 grid(li.grid), block(li.block);
+    if (multi && p.chunk_nodes != nullptr) {
+        li.kernel_name = "k_query_chunk";
+        hipLaunchKernelGGL(k_query_chunk, grid, block, li.lds_bytes, stream, p, q);
+    } else {
+        p.fast_nodes = nullptr;   // the library's own tree has no query form: the reference walk over the caller's tree
+        if (p.u.bvh_node_count > 1u || p.sph_nodes != nullptr) {
+            li.kernel_name = "k_query_bvh";
+            hipLaunchKernelGGL(k_query<true>, grid, block, li.lds_bytes, stream, p, q);
+        } else {
+            li.kernel_name = "k_query";
+            hipLaunchKernelGGL(k_query<false>, grid, block, li.lds_bytes, stream, p, q);
+        }
+    }
+    if (info) *info = li;
+    return (int)hipGetLastError();
+}
+
+}  // namespace rb

@@ -888,6 +888,105 @@ int group_iter_next(rb_engine* g, uint8_t* rgba_out) {
     return group_deliver(g, rgba_out, false);
 }
 
+// ------------------------------------------------------------------ closest-hit queries ----
+// (rb_abi.h)  A query reads the scene and writes its own scratch: it is queued on the engine's stream
+// behind whatever runs there -- a pass the iterator has started ahead included, which stays valid -- and uses events of its
+// own, so neither the work counters nor the timing of a launch group move.
+bool page_locked(const void* p) {
+    hipPointerAttribute_t attr{};
+    if (p && hipPointerGetAttributes(&attr, p) == hipSuccess && attr.type == hipMemoryTypeHost) return true;
+    (void)hipGetLastError();   // an unregistered pointer makes the query fail: that is the ordinary case
+    return false;
+}
+
+// device -> caller memory behind the stream's work: a DMA into page-locked memory, a blocking copy otherwise
+int query_copy_out(rb_engine* e, void* dst, const void* src, size_t bytes, bool pinned) {
+    if (pinned) {
+        HIP_TRY(e, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, e->stream));
+        return RB_OK;
+    }
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    HIP_TRY(e, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+    return RB_OK;
+}
+
+int query_begin(rb_engine* e, rb::KParams* p, size_t records, bool rays, bool surf) {
+    int rc = require_ready(e);
+    if (!rc) rc = ensure_prepared(e);
+    if (rc) return rc;
+    *p = make_params(e, 0, 0, e->cur, e->cur);
+    if (!e->stack_depth_covers) return rb::fail(e, RB_ERR_DEVICE, "internal: a traversal is deeper than its LDS stack column (%u entries)", p->stack_depth);
+    for (hipEvent_t& x : e->ev_q)
+        if (!x) HIP_TRY(e, hipEventCreate(&x));
+    if (rays) HIP_TRY(e, e->q_rays.reserve(records));
+    HIP_TRY(e, e->q_hits.reserve(records));
+    if (surf) HIP_TRY(e, e->q_surf.reserve(records));
+    e->last_query_ms = 0.0f;
+    return RB_OK;
+}
+
+// one piece: launch between the query's two events, copy the records out, fold the kernel time
+int query_piece(rb_engine* e, const rb::KParams& p, rb::QueryArgs q, size_t records, rb_hit* hits_out, rb_surface* surf_out,
+                bool hits_pinned, bool surf_pinned) {
+    q.hits = e->q_hits.ptr;
+    q.surf = surf_out ? e->q_surf.ptr : nullptr;
+    rb::LaunchInfo li{};
+    HIP_TRY(e, hipEventRecord(e->ev_q[0], e->stream));
+    const int st = rb::launch_query(p, q, e->stream, &li);
+    if (st) return rb::fail(e, RB_ERR_DEVICE, "query kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
+    HIP_TRY(e, hipEventRecord(e->ev_q[1], e->stream));
+    if (li.kernel_name) e->last_query_kernel_name = li.kernel_name;
+    int rc = query_copy_out(e, hits_out, e->q_hits.ptr, records * sizeof(rb_hit), hits_pinned);
+    if (!rc && surf_out) rc = query_copy_out(e, surf_out, e->q_surf.ptr, records * sizeof(rb_surface), surf_pinned);
+    if (rc) return rc;
+    HIP_TRY(e, hipStreamSynchronize(e->stream));   // the scratch is the next piece's
+    float ms = 0.0f;
+    HIP_TRY(e, hipEventElapsedTime(&ms, e->ev_q[0], e->ev_q[1]));
+    e->last_query_ms += ms;
+    return RB_OK;
+}
+
+int cast_rays_locked(rb_engine* e, const rb_ray* rays, size_t n, rb_hit* hits_out, rb_surface* surf_out) {
+    rb::KParams p{};
+    const size_t piece = std::min<size_t>(n, rb::kQueryPiece);
+    int rc = query_begin(e, &p, piece, true, surf_out != nullptr);
+    if (rc || n == 0) return rc;
+    const bool hits_pinned = page_locked(hits_out), surf_pinned = page_locked(surf_out);
+    for (size_t done = 0; done < n; done += piece) {
+        const size_t m = std::min(piece, n - done);
+        // (from pageable memory the runtime stages the copy and returns when the source may be reused)
+        HIP_TRY(e, hipMemcpyAsync(e->q_rays.ptr, rays + done, m * sizeof(rb_ray), hipMemcpyHostToDevice, e->stream));
+        rb::QueryArgs q{};
+        q.rays = e->q_rays.ptr;
+        q.n = static_cast<uint32_t>(m);
+        rc = query_piece(e, p, q, m, hits_out + done, surf_out ? surf_out + done : nullptr, hits_pinned, surf_pinned);
+        if (rc) return rc;
+    }
+    return RB_OK;
+}
+
+// the pixel centres of rows [0, rows) x the whole width (global = image rows, else this shard's local rows), or of one pixel
+int pixel_hits_locked(rb_engine* e, uint32_t x0, uint32_t y0, uint32_t w, uint32_t rows, bool global, rb_hit* hits_out, rb_surface* surf_out) {
+    rb::KParams p{};
+    const uint32_t piece_rows = w == 0 ? 8u : std::max<uint32_t>(8u, (rb::kQueryPiece / w) & ~7u);   // whole 8-row tiles
+    int rc = query_begin(e, &p, static_cast<size_t>(std::min(piece_rows, rows)) * w, false, surf_out != nullptr);
+    if (rc || w == 0 || rows == 0) return rc;
+    const bool hits_pinned = page_locked(hits_out), surf_pinned = page_locked(surf_out);
+    for (uint32_t r0 = 0; r0 < rows; r0 += piece_rows) {
+        const uint32_t h = std::min(piece_rows, rows - r0);
+        rb::QueryArgs q{};
+        q.win_x = x0;
+        q.win_y = y0 + r0;
+        q.win_w = w;
+        q.win_h = h;
+        q.win_global = global ? 1u : 0u;
+        const size_t off = static_cast<size_t>(r0) * w;
+        rc = query_piece(e, p, q, static_cast<size_t>(h) * w, hits_out + off, surf_out ? surf_out + off : nullptr, hits_pinned, surf_pinned);
+        if (rc) return rc;
+    }
+    return RB_OK;
+}
+
 }  // namespace
 
 // ============================================================== C ABI ======
@@ -1002,6 +1101,8 @@ void rb_destroy(rb_engine* e) {
     for (rb::FrameSlot& s : e->slot)
         if (s.done) (void)hipEventDestroy(s.done);
     for (hipEvent_t x : e->ev_pool) (void)hipEventDestroy(x);
+    for (hipEvent_t x : e->ev_q)
+        if (x) (void)hipEventDestroy(x);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
 }
@@ -1383,6 +1484,62 @@ int rb_last_dispatch_ms(rb_engine* e, float* ms) {
 }
 
 const char* rb_version(void) { return "renderbaby-hip 0.3 (gfx950)"; }
+
+int rb_cast_rays(rb_engine* e, const rb_ray* rays, size_t n, rb_hit* hits_out, rb_surface* surf_out) {
+    if (!e) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (n > 0x7FFFFFFFull - 63ull) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "rb_cast_rays takes at most 2^31 - 64 rays per call");
+    if (n > 0 && (!rays || !hits_out)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "rays / hits_out is NULL");
+    if (rb::is_group(e)) {   // every part holds the whole scene
+        rb_engine* p0 = e->parts[0].get();
+        PART_TRY(e, p0, cast_rays_locked(p0, rays, n, hits_out, surf_out));
+        return RB_OK;
+    }
+    rb::set_device(e);
+    return cast_rays_locked(e, rays, n, hits_out, surf_out);
+}
+
+int rb_render_hits(rb_engine* e, rb_hit* hits_out, rb_surface* surf_out) {
+    if (!e) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (!hits_out) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "hits_out is NULL");
+    if (rb::is_group(e)) {   // the whole frame on devices[0]: one ray per pixel is not worth a gather
+        rb_engine* p0 = e->parts[0].get();
+        PART_TRY(e, p0, require_ready(p0));
+        PART_TRY(e, p0, pixel_hits_locked(p0, 0, 0, p0->width, p0->height, true, hits_out, surf_out));
+        return RB_OK;
+    }
+    rb::set_device(e);
+    int rc = require_ready(e);
+    if (rc) return rc;
+    const bool sharded = e->opt.shard_count > 1;
+    return pixel_hits_locked(e, 0, 0, e->width, sharded ? e->padded_rows : e->height, !sharded, hits_out, surf_out);
+}
+
+int rb_pick(rb_engine* e, uint32_t px, uint32_t py, rb_hit* hit_out, rb_surface* surf_out) {
+    if (!e) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (!hit_out) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "hit_out is NULL");
+    rb_engine* t = rb::is_group(e) ? e->parts[0].get() : e;
+    rb::set_device(t);
+    int rc = require_ready(t);
+    if (!rc && (px >= t->width || py >= t->height)) rc = rb::fail(t, RB_ERR_INVALID_OPTIONS, "pixel (%u, %u) is outside the %u x %u image", px, py, t->width, t->height);
+    if (!rc) rc = pixel_hits_locked(t, px, py, 1, 1, true, hit_out, surf_out);
+    if (rc && t != e) copy_error(e, t);
+    return rc;
+}
+
+const char* rb_last_query_kernel_name(const rb_engine* e) {
+    if (!e) return "";
+    return rb::is_group(e) ? e->parts[0]->last_query_kernel_name : e->last_query_kernel_name;
+}
+
+int rb_last_query_ms(rb_engine* e, float* ms) {
+    if (!e || !ms) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    *ms = rb::is_group(e) ? e->parts[0]->last_query_ms : e->last_query_ms;
+    return RB_OK;
+}
 
 const char* rb_last_kernel_name(const rb_engine* e) {
     if (!e) return "";

@@ -363,6 +363,54 @@ class Engine:
     def last_kernel_name(self):
         return (self._lib.rb_last_kernel_name(self._h) or b"").decode()
 
+    # ---- closest-hit queries (rb_abi.h)
+    def cast_rays(self, origins, dirs, surfaces=False, hits_out=None, surfaces_out=None):
+        """rb_cast_rays: (n, 3) origins and directions (any length: the device normalises) -> abi.HIT[n], or
+        (abi.HIT[n], abi.SURFACE[n]) with ``surfaces``.  ``hits_out`` / ``surfaces_out``: arrays to fill instead of new
+        ones (page-locked ones are filled by DMA)."""
+        o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.asarray(dirs, dtype=np.float32).reshape(-1, 3)
+        if len(o) != len(d):
+            raise ValueError("origins and dirs differ in length")
+        rays = np.zeros(len(o), dtype=abi.RAY)
+        rays["origin"], rays["dir"] = o, d
+        return self.cast_ray_records(rays, surfaces, hits_out, surfaces_out)
+
+    def cast_ray_records(self, rays, surfaces=False, hits_out=None, surfaces_out=None):
+        """rb_cast_rays on an abi.RAY array as it stands (no copy when it is contiguous)."""
+        rays = np.ascontiguousarray(rays, dtype=abi.RAY)
+        n = len(rays)
+        hits = np.empty(n, dtype=abi.HIT) if hits_out is None else hits_out
+        surf = (np.empty(n, dtype=abi.SURFACE) if surfaces_out is None else surfaces_out) if (surfaces or surfaces_out is not None) else None
+        self._check(self._lib.rb_cast_rays(self._h, rays.ctypes.data if n else None, n, hits.ctypes.data if n else None,
+                                           surf.ctypes.data if (surf is not None and n) else None))
+        return hits if surf is None else (hits, surf)
+
+    def render_hits(self, surfaces=False):
+        """rb_render_hits: the first hit of every pixel centre as abi.HIT[rows, width] (and abi.SURFACE with ``surfaces``) in
+        the orientation of the delivered frame; a sharded engine: its padded local rows, like read_accumulation."""
+        w, h = self.size()
+        if self.shard_count > 1:   # (a multi-device handle delivers whole frames: its shard_count is 1 here)
+            h = self.local_rows()[1]
+        hits = np.empty((h, w), dtype=abi.HIT)
+        surf = np.empty((h, w), dtype=abi.SURFACE) if surfaces else None
+        self._check(self._lib.rb_render_hits(self._h, hits.ctypes.data, surf.ctypes.data if surfaces else None))
+        return (hits, surf) if surfaces else hits
+
+    def pick(self, px, py):
+        """rb_pick: (abi.HIT, abi.SURFACE) scalars of displayed pixel (px from the left, py from the top)."""
+        hit, surf = np.empty(1, dtype=abi.HIT), np.empty(1, dtype=abi.SURFACE)
+        self._check(self._lib.rb_pick(self._h, int(px), int(py), hit.ctypes.data, surf.ctypes.data))
+        return hit[0], surf[0]
+
+    def last_query_kernel_name(self):
+        return (self._lib.rb_last_query_kernel_name(self._h) or b"").decode()
+
+    def last_query_ms(self):
+        ms = C.c_float()
+        self._check(self._lib.rb_last_query_ms(self._h, C.byref(ms)))
+        return ms.value
+
     def fast_bvh_builder(self):
         """("host-sah" | "device-lbvh" | "", build milliseconds) of the tree RB_FLAG_FAST_BVH walks."""
         ms = C.c_float()

@@ -12,6 +12,6 @@ cp -r renderbaby_amd/csrc $W/renderbaby_amd/csrc; cp -r include $W/include
 FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -fno-fast-math -fno-slp-vectorize"
 C=$W/renderbaby_amd/csrc
 for n in 0 1 2 3 4; do
-  /opt/rocm/bin/hipcc $FLAGS -DRB_ABLATE=$n -shared -o renderbaby_amd/variants/lib_ablate$n.so $C/rb_kernels.hip $C/rb_build.hip $C/rb_runtime.cpp $C/rb_accel.cpp $C/rb_bvh.cpp $C/rb_rccl.cpp -ldl 2>/dev/null
+  /opt/rocm/bin/hipcc $FLAGS -DRB_ABLATE=$n -shared -o renderbaby_amd/variants/lib_ablate$n.so $C/rb_kernels.hip $C/rb_query.hip $C/rb_build.hip $C/rb_runtime.cpp $C/rb_accel.cpp $C/rb_bvh.cpp $C/rb_rccl.cpp -ldl 2>/dev/null
   echo "ABLATE=$n $(RB_LIBRARY_PATH=renderbaby_amd/variants/lib_ablate$n.so python tools/one_dispatch.py c2 64 3 3)"
 done

@@ -3,7 +3,7 @@
 # Builds a second library with -DRB_COLOR_COMBINE=0 into /tmp and selects it with RB_LIBRARY_PATH.
 cd "$(dirname "$0")/.."
 R=$(pwd)
-/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -fno-fast-math -DRB_COLOR_COMBINE=0 -shared -o /tmp/lib_comb0.so renderbaby_amd/csrc/rb_kernels.hip renderbaby_amd/csrc/rb_build.hip renderbaby_amd/csrc/rb_runtime.cpp renderbaby_amd/csrc/rb_accel.cpp renderbaby_amd/csrc/rb_bvh.cpp renderbaby_amd/csrc/rb_rccl.cpp -ldl 2>/dev/null || exit 1
+/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -fno-fast-math -DRB_COLOR_COMBINE=0 -shared -o /tmp/lib_comb0.so renderbaby_amd/csrc/rb_kernels.hip renderbaby_amd/csrc/rb_query.hip renderbaby_amd/csrc/rb_build.hip renderbaby_amd/csrc/rb_runtime.cpp renderbaby_amd/csrc/rb_accel.cpp renderbaby_amd/csrc/rb_bvh.cpp renderbaby_amd/csrc/rb_rccl.cpp -ldl 2>/dev/null || exit 1
 for v in "" /tmp/lib_comb0.so; do
   export RB_LIBRARY_PATH=$v
   tag=$([ -z "$v" ] && echo ring || echo direct)
