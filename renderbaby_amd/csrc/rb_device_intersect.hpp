@@ -154,6 +154,36 @@ DEV void test_slot(const v4f a, const v4f b, const v4f c, uint32_t slot, f3 o, f
     }
 }
 
+// test_slot for the wave-uniform triangle list of the single-node walk (intersect_bvh): isect_triangle's operations on the
+// same operands in the same order and test_slot's acceptance (|a| >= 1e-6, 0 <= u <= 1, v >= 0, u + v <= 1, t > 0,
+// t > 0.001, t < h.t, all as written there, so a NaN takes the same way), but the hit is taken where t is computed:
+// no -1 is handed back through the four early-outs to be compared with 0.001 and h.t once more.  hit.hit is left alone:
+// carried through the loop it is a lane mask in two scalar registers that every join of the early-outs merges again;
+// the caller sets it once from hit.t, which leaves its initial 1e20 exactly when a triangle is accepted (t < hit.t).
+DEV void accept_slot(const v4f a, const v4f b, const v4f c, uint32_t slot, f3 o, f3 d, TriHit& hit) {
+    const f3 v0 = mk(a.x, a.y, a.z), edge1 = mk(b.x, b.y, b.z), edge2 = mk(c.x, c.y, c.z);
+    const f3 h = cross(d, edge2);
+    const float det = dot(edge1, h);
+    if (!(fabsf(det) < 1e-6f)) {
+        const float f = rcp_tri(det);
+        const f3 s = o - v0;
+        const float u = f * dot(s, h);
+        if (!(u < 0.0f || u > 1.0f)) {
+            const f3 q = cross(s, edge1);
+            const float v = f * dot(d, q);
+            if (!(v < 0.0f || u + v > 1.0f)) {
+                const float t = f * dot(edge2, q);
+                if (t > 0.0f && t > 0.001f && t < hit.t) {
+                    hit.t = t;
+                    hit.u = u;
+                    hit.v = v;
+                    hit.slot = slot;
+                }
+            }
+        }
+    }
+}
+
 // (One triangle per step.  r01-r02 tested two per step with packed f32 math: on gfx950 a packed f32 instruction issues at
 // half the rate of a plain one (MI355X_MICROARCH.md), so the pairing bought no throughput and paid for the register
 // pairs -- 4.9 % slower on C2, profiles/r03_noslp.txt.  That arm lives in tools/ablate/rb_forks.patch.)
@@ -514,23 +544,36 @@ DEV TriHit intersect_bvh(const KParams& p, f3 o, f3 d, uint32_t* stack, uint32_t
     if (node_count == 1u) {
         // Single-node tree (the Cornell box): no stack; the node and its triangles are
         // wave-uniform, so they are fetched with scalar loads and every lane that is
-        // inside the box walks the same primitive list.  Same tests, same order.  The next
-        // triangle's record is requested before the current one is tested.
+        // inside the box walks the same primitive list.  Same tests, same order.  The record of
+        // the next triangle (the last one again at the end of the list: the address stays inside
+        // the table) is requested at the top of a trip, before the current one is tested, into
+        // scalar registers of its own, and is only waited for when the trip is over.
         const v4f n0 = nodes[0], n1 = nodes[1];
         const v4u n2 = ((cu4p)p.nodes)[2];
         if constexpr (STATS) tl.nodes++;
         const uint32_t first = n2.z, count = n2.w;
         const uint32_t end = (first + count < p.index_len) ? first + count : p.index_len;  // guard :331
         if (first < end && isect_aabb(o, inv, mk(n0.x, n0.y, n0.z), mk(n1.x, n1.y, n1.z))) {
-            for (uint32_t slot = first; slot < end; slot++) {
-                const v4f a = ptris[slot * 4u], b = ptris[slot * 4u + 1u], c = ptris[slot * 4u + 2u];
-                if (__float_as_uint(c.w) != 0u) {  // guard :336
+            const uint32_t last = end - 1u;
+            cf4p rec = ptris + (size_t)first * 4u;
+            v4f a = rec[0], b = rec[1], c = rec[2];
+            bool live = __float_as_uint(c.w) != 0u;  // guard :336
+            for (uint32_t slot = first;; slot++) {
+                if (slot < last) rec += 4;
+                const v4f na = rec[0], nb = rec[1], nc = rec[2];
+                if (live) {
                     if constexpr (STATS) tl.tris++;
                     const float before = h.t;
-                    test_slot(a, b, c, slot, o, d, h);
+                    accept_slot(a, b, c, slot, o, d, h);
                     if constexpr (STATS) tl.mesh_hits += (h.t != before) ? 1u : 0u;
                 }
+                if (slot == last) break;
+                a = na;
+                b = nb;
+                c = nc;
+                live = __float_as_uint(nc.w) != 0u;
             }
+            h.hit = h.t < 1e20f;
         }
         return h;
     }

@@ -398,10 +398,6 @@ __global__ void __launch_bounds__(kTraceBlock, WAVES) k_trace(const KParams p) {
     Tally<STATS> tl;
     __shared__ __attribute__((aligned(16))) v4f s_ring[(kTraceBlock / 64u) * kRingRows * 64u];
     ColorRing cring(s_ring, tid >> 6, lane);
-    // rows follow each other through the ring's slices only if every reservation starts on a multiple of
-    // kRingRows rows; the launcher arranges that for frames large enough, the others store directly
-    const uint32_t direct_mask = (p.queue_batch % (kRingRows * 64u)) ? kDirect : 0u;
-
     bool active = false, exhausted = false;
     uint32_t item = 0;
     uint32_t loc_next = 0, loc_end = 0;  // this wave's reserved item range (wave-uniform)
@@ -439,6 +435,9 @@ __global__ void __launch_bounds__(kTraceBlock, WAVES) k_trace(const KParams p) {
             const KParams& rp = fresh_params(p);
             const uint32_t rS = rp.n_passes * rp.samples_per_pass, r_tiles_x = (rp.u.width + 7u) / 8u;
             const uint32_t r_sample_base = rp.first_pass * rp.samples_per_pass, r_width = rp.u.width;
+            // rows follow each other through the ring's slices only if every reservation starts on a multiple of
+            // kRingRows rows; the launcher arranges that for frames large enough, the others store directly
+            const uint32_t direct_mask = (rp.queue_batch % (kRingRows * 64u)) ? kDirect : 0u;
             const ItemRows rows = item_rows(rp, loc_next, rS, r_tiles_x, r_sample_base);
             const uint32_t avail = loc_end - loc_next;
             const uint32_t rank = (uint32_t)__popcll(idle & ((1ull << lane) - 1ull));
@@ -455,7 +454,7 @@ __global__ void __launch_bounds__(kTraceBlock, WAVES) k_trace(const KParams p) {
                 if (item_pixel(rp, rows, rank, x, y, sample_hash)) {
                     start_path_hashed(rp, x, y, y * r_width + x, sample_hash, pt);
                     item = it | direct_mask;
-                    if (p.u.max_depth > 0u) {
+                    if (rp.u.max_depth > 0u) {
                         active = true;
                     } else {
                         colors[it] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
