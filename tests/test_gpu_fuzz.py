@@ -33,6 +33,33 @@ def test_random_scenes_all_variants(first):
             assert st["segments"] == o_st["segments"] and st["paths"] == o_st["paths"], (seed, name)
 
 
+def _every_variant_matches_the_oracle(s, label):
+    o_acc, _, o_rgba, o_st = _oracle.render(s)
+    rc = RenderConfig.from_scene(s)
+    for name, kw in fuzz.variants(s):
+        e = Engine.new(rc, stats=True, **kw)
+        frame = e.render(rc)
+        acc, st = e.read_accumulation(), e.stats()
+        e.close()
+        assert np.array_equal(acc.view(np.uint32), o_acc.view(np.uint32)), (label, name)
+        assert np.array_equal(frame.pixels, o_rgba), (label, name)
+        assert st["segments"] == o_st["segments"] and st["paths"] == o_st["paths"], (label, name)
+
+
+@pytest.mark.parametrize("first", [3000, 3020])
+def test_random_scenes_with_several_textures(first):
+    # 40 small scenes with 2 to 5 textures of odd shapes (1 to 17 texels a side), a texture index per mesh group and per sphere from
+    # -1 to n_tex (one past the end: black) and uv scales of 1, -3 and 1000: the texture offsets, the clamps and the wrap of
+    # sample_texture under every variant
+    textured = 0
+    for seed in range(first, first + 20):
+        s = fuzz.random_scene(seed, rich_textures=True)
+        assert 2 <= len(s.textures) <= 5
+        textured += int((s.meshes["material"]["texture_index"] > 0).any() or (s.spheres["material"]["texture_index"] > 0).any())
+        _every_variant_matches_the_oracle(s, seed)
+    assert textured >= 10, textured   # a texture other than the first is in use
+
+
 @pytest.mark.parametrize("first", [500180, 603375, 700000])
 def test_random_large_frames_all_variants(first, monkeypatch):
     # Both parity bugs of r02 (a tie between a sphere and an earlier category, seed 500188; large triangles behind a

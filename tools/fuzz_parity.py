@@ -19,7 +19,10 @@ from renderbaby_amd import Engine, RenderConfig, abi, bvh, scenes
 from tests import _oracle
 
 
-def random_scene(seed):
+def random_scene(seed, rich_textures=False):
+    """rich_textures: 2 to 5 textures of odd shapes, a texture index per mesh group and per sphere from -1 to n_tex (the upper
+    value is out of range on purpose) and a uv scale per group, all drawn from a stream of their own: the scene's other arrays
+    are those of random_scene(seed)."""
     rng = np.random.default_rng(seed)
     big = bool(os.environ.get("FUZZ_BIG"))   # larger frames / more samples: several queue reservations per wave
     slivers = bool(os.environ.get("FUZZ_SLIVERS"))   # a different stream of scenes: mid-sized thin triangles, grazed more often
@@ -90,6 +93,17 @@ def random_scene(seed):
             m = scenes.material(diffuse=f(0, 1, 3), specular=f(0, 1, 3) * (rng.random() < 0.5), shininess=float(f(0, 1100)),
                                 emissive=f(0, 5, 3) * (rng.random() < 0.3), texture_index=0 if (use_tex and g == 0) else -1)
             groups.append((m, tris)); uv_groups.append(uvs)
+    if rich_textures:
+        r2 = np.random.default_rng((seed, 0x7e7))
+        tex = []
+        for _ in range(int(r2.integers(2, 6))):
+            tw, th = (int(r2.choice([1, 2, 3, 5, 8, 17])) for _ in range(2))
+            tex.append((tw, th, r2.integers(0, 1 << 32, tw * th, dtype=np.uint32)))
+        for g, (m, _) in enumerate(groups):
+            m["texture_index"] = int(r2.integers(-1, len(tex) + 1))
+            uv_groups[g] = (np.asarray(uv_groups[g], np.float32) * np.float32(r2.choice([1.0, -3.0, 1e3]))).astype(np.float32)
+        for i in range(ns):
+            sp[i]["material"]["texture_index"] = int(r2.integers(-1, len(tex) + 1))
     sc = scenes._finish(f"fuzz{seed}", u, sp, lights, groups, uv_groups, tex)
     if nt and rng.random() < (0.6 if slivers else 0.25):
         graze(sc, rng)
