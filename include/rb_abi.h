@@ -562,6 +562,34 @@ const char* rb_last_query_kernel_name(const rb_engine* e);
  * recent query, HIP events around its launches, summed over the pieces, ms. */
 int rb_last_query_ms(rb_engine* e, float* ms);
 
+/* ---- Any-hit occlusion queries and device-resident ray buffers (no reference counterpart).  One bit per
+ * ray: is anything between here and there?  out[i] is RB_OCCL_OCCLUDED exactly when the closest-hit search above would record a
+ * hit if it were restricted to the stages named in `mask` and started with closest_hit.t = min(tmax[i], 1e20f) instead of 1e20f.
+ * Everything else is that search's: `t > 0.001`, strict `<`, the device's normalisation of `dir`, the phantom light of an empty
+ * light buffer (part of RB_MASK_LIGHTS), kept counts, numerics contract.  The reference's tree walk decides which triangles it
+ * tests from boolean box tests only (shader.wgsl:282-392), so with RB_MASK_ALL the answer is rb_cast_rays(...).t < tmax[i].
+ * The walk stops at the first accepted hit; the stages run ground, lights, spheres, triangles (the answer is existential).
+ * The side effects are a query's: none on the accumulation, the frames, the colour buffer, the work counters or the random
+ * sequence; rb_last_query_kernel_name reports "k_occl", "k_occl_bvh" or "k_occl_chunk", rb_last_query_ms their time. */
+enum { RB_OCCL_VISIBLE = 0, RB_OCCL_OCCLUDED = 1, RB_OCCL_INVALID = 255 };
+enum { RB_MASK_GROUND = 1, RB_MASK_TRIANGLES = 2, RB_MASK_SPHERES = 4, RB_MASK_LIGHTS = 8, RB_MASK_ALL = 15 };
+/* n rays from host memory, tmax[n] (NULL: 1e20f for every ray), out[n] bytes (pageable or page-locked).  A ray rb_cast_rays
+ * would mark RB_HIT_INVALID, or one whose tmax is NaN, is RB_OCCL_INVALID; tmax <= 0.001f (negative and -Inf included) is
+ * VISIBLE and not walked; tmax >= 1e20f or +Inf is walked as 1e20f; mask == 0 makes every valid ray VISIBLE; mask bits above
+ * RB_MASK_ALL and n > 2^31 - 64 are RB_ERR_INVALID_OPTIONS; n == 0 is RB_OK.  Pieces of at most 2^22 rays through the scratch
+ * of rb_cast_rays' rays plus 16 MiB of bounds and 4 MiB of result bytes; the read-back is 1 B per ray. */
+int rb_occluded(rb_engine* e, const rb_ray* rays, const float* tmax, size_t n, uint32_t mask, uint8_t* out);
+/* The same with every pointer in device memory of the engine's device (a multi-device handle: devices[0]); a host pointer or
+ * memory of another device is RB_ERR_INVALID_OPTIONS, and so are a d_rays that is not 16-byte aligned and a buffer whose
+ * allocation (hipMemGetAddressRange) ends before its n elements.  The kernels are queued
+ * on the engine's stream and read and write the caller's buffers directly -- no scratch, no copy, one launch unless the grid
+ * limit demands more -- and the call returns without waiting: rb_sync is the wait.  The caller orders its own writes of the
+ * buffers before the call.  rb_last_query_ms waits for the kernels it reports. */
+int rb_occluded_device(rb_engine* e, const rb_ray* d_rays, const float* d_tmax, size_t n, uint32_t mask, uint8_t* d_out);
+/* rb_cast_rays with d_rays, d_hits and d_surf (may be NULL) in device memory, 16-byte aligned; otherwise as rb_occluded_device.
+ * On a sharded engine rays are whole-scene rays, as for rb_cast_rays. */
+int rb_cast_rays_device(rb_engine* e, const rb_ray* d_rays, size_t n, rb_hit* d_hits, rb_surface* d_surf);
+
 /* Which builder produced the library's own tree: "host-sah", "device-ploc", "device-lbvh", or "" when
  * there is none (flag not set, single-node tree, or the scene keeps the exact walk).  Valid after the
  * first rb_dispatch / rb_render that follows an update.  `build_ms`, if not NULL, receives the wall

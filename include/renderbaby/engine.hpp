@@ -194,6 +194,22 @@ class Engine final : public Renderer {
         check(h_->e, rb_render_hits(h_->e, r.hits.data(), surfaces ? r.surfaces.data() : nullptr));
         return r;
     }
+    // ---- any-hit occlusion and device-resident buffers (extension; rb_abi.h)
+    // RB_OCCL_* per ray: is anything within (0.001, tmax) among the stages of `mask`?  tmax: empty (no bound) or one per ray
+    std::vector<uint8_t> occluded(const std::vector<rb_ray>& rays, const std::vector<float>& tmax = {}, uint32_t mask = RB_MASK_ALL) {
+        if (!tmax.empty() && tmax.size() != rays.size()) throw std::invalid_argument("rays and tmax differ in length");
+        std::vector<uint8_t> out(rays.size());
+        check(h_->e, rb_occluded(h_->e, rays.data(), tmax.empty() ? nullptr : tmax.data(), rays.size(), mask, out.data()));
+        return out;
+    }
+    // the same on buffers in the engine's device memory: queued on the engine's stream, no copy; sync() is the wait
+    void occluded_device(const rb_ray* d_rays, const float* d_tmax, size_t n, uint8_t* d_out, uint32_t mask = RB_MASK_ALL) {
+        check(h_->e, rb_occluded_device(h_->e, d_rays, d_tmax, n, mask, d_out));
+    }
+    void cast_rays_device(const rb_ray* d_rays, size_t n, rb_hit* d_hits, rb_surface* d_surf = nullptr) {
+        check(h_->e, rb_cast_rays_device(h_->e, d_rays, n, d_hits, d_surf));
+    }
+    void sync() { check(h_->e, rb_sync(h_->e)); }
     // the displayed pixel (px from the left, py from the top): "sphere 3" / "mesh 2, triangle 517" for a click
     rb_hit pick(uint32_t px, uint32_t py, rb_surface* surface = nullptr) {
         rb_hit hit{};

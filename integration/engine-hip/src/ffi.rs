@@ -34,6 +34,13 @@ pub const RB_FLAG_CHUNK_TREE_HOST: u32 = 8192;    // the chunked walk's tree: bu
 pub const RB_FLAG_CHUNK_TREE_DEVICE: u32 = 16384; // ... or on the device whatever the size (default: the device from 16 384 triangle slots up)
 pub const RB_COMM_ID_BYTES: usize = 128;
 
+/// rb_ray (32 bytes) and the any-hit occlusion query's result bytes and stage masks
+#[repr(C)] #[derive(Default, Clone, Copy)]
+pub struct RbRay { pub origin: [f32; 3], pub _pad0: f32, pub dir: [f32; 3], pub _pad1: f32 }
+pub const RB_OCCL_VISIBLE: u8 = 0; pub const RB_OCCL_OCCLUDED: u8 = 1; pub const RB_OCCL_INVALID: u8 = 255;
+pub const RB_MASK_GROUND: u32 = 1; pub const RB_MASK_TRIANGLES: u32 = 2; pub const RB_MASK_SPHERES: u32 = 4;
+pub const RB_MASK_LIGHTS: u32 = 8; pub const RB_MASK_ALL: u32 = 15;
+
 unsafe extern "C" {
     pub fn rb_create(cfg: *const RbConfig) -> *mut RbEngine;
     pub fn rb_create_ex(cfg: *const RbConfig, opt: *const RbOptions) -> *mut RbEngine;
@@ -62,5 +69,12 @@ unsafe extern "C" {
     /// BVH::new (engine-bvh/src/bvh.rs:87-150) restated, its top levels forked onto threads: the tree the adapter rebuilds per render
     /// (scene_engine_adapter.rs:435-440) in a tenth of the time.  Two calls: nodes_out = null asks for the sizes.
     pub fn rb_bvh_build(tris: *const c_void, n_tris: usize, nodes_out: *mut c_void, nodes_capacity: usize, n_nodes: *mut usize, indices_out: *mut u32) -> c_int;
+    /// any-hit: out[i] = RB_OCCL_OCCLUDED iff a stage of `mask` reports a hit with 0.001 < t < tmax[i] (tmax null: no bound)
+    pub fn rb_occluded(e: *mut RbEngine, rays: *const RbRay, tmax: *const f32, n: usize, mask: u32, out: *mut u8) -> c_int;
+    /// the same, and closest-hit records (rb_hit / rb_surface, 48 bytes each), on buffers in the engine's device memory:
+    /// queued on the engine's stream, no copy, no wait (rb_sync waits)
+    pub fn rb_occluded_device(e: *mut RbEngine, d_rays: *const RbRay, d_tmax: *const f32, n: usize, mask: u32, d_out: *mut u8) -> c_int;
+    pub fn rb_cast_rays_device(e: *mut RbEngine, d_rays: *const RbRay, n: usize, d_hits: *mut c_void, d_surf: *mut c_void) -> c_int;
+    pub fn rb_sync(e: *mut RbEngine) -> c_int;
     pub fn rb_last_error(e: *const RbEngine) -> *const c_char;
 }

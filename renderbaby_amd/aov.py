@@ -1,5 +1,5 @@
 """First-hit buffers as images: pure numpy over the records of ``Engine.render_hits`` / ``Engine.cast_rays``
-(abi.HIT, abi.SURFACE).  No device, no library.
+(abi.HIT, abi.SURFACE).  No device, no library -- except ``ambient_occlusion``, which asks the engine one any-hit query.
 
 The records are already in the orientation of the delivered RGBA8 frame (row-major, top row first, x mirrored), so every
 function here maps record [row, column] to pixel [row, column] and nothing is flipped.  Pixels whose ray hit nothing
@@ -92,6 +92,81 @@ def primitive_id(hits):
 def mesh_id(hits):
     """hash_to_color(mesh + 1) for triangle hits; everything else black."""
     return _id_image(hits, hits["mesh"])
+
+
+def pixel_centre_dirs(uniforms):
+    """[row, displayed column] -> the direction of the pixel-centre ray (shader.wgsl:690-709 with both offsets 0, x mirrored
+    like the frame), numpy float32.  ``uniforms``: abi.UNIFORMS."""
+    f32 = np.float32
+    u = np.asarray(uniforms, dtype=abi.UNIFORMS).reshape(-1)[0]
+    w, h = int(u["width"]), int(u["height"])
+
+    def unit(v):
+        v = np.asarray(v, f32)
+        return (v / np.sqrt((v[..., 0:1] * v[..., 0:1] + v[..., 1:2] * v[..., 1:2]) + v[..., 2:3] * v[..., 2:3], dtype=f32)).astype(f32)
+    aspect = f32(w) / f32(h)
+    fwd = unit(u["camera"]["dir"])
+    right = unit(np.cross(np.array([0, 1, 0], f32), fwd).astype(f32))
+    up = np.cross(fwd, right).astype(f32)
+    fov = f32(u["camera"]["pane_width"]) / (f32(2.0) * f32(u["camera"]["pane_distance"]) * aspect)
+    x = (f32(w - 1) - np.arange(w, dtype=f32)) / f32(max(w - 1, 1))
+    y = np.arange(h, dtype=f32) / f32(max(h - 1, 1))
+    su = ((x * f32(2.0) - f32(1.0)) * aspect)[None, :, None]
+    sv = (f32(1.0) - y * f32(2.0))[:, None, None]
+    return unit((fov * su) * right + (fov * sv) * up + fwd)
+
+
+def ambient_occlusion_rays(uniforms, hits, n_dirs=16, seed=0):
+    """The rays of ``ambient_occlusion``: for every pixel whose centre ray hit something, ``n_dirs`` cosine-weighted
+    directions about the normal turned towards the camera, from the hit point ``pos + t d`` moved off the surface along that
+    normal.  Returns (pixel mask [rows, width], origins (m * n_dirs, 3), directions (m * n_dirs, 3)), numpy float32."""
+    f32 = np.float32
+    u = np.asarray(uniforms, dtype=abi.UNIFORMS).reshape(-1)[0]
+    m = _hit_mask(hits)
+    d = pixel_centre_dirs(u)
+    if d.shape[:2] != hits.shape:
+        raise ValueError(f"the records are {hits.shape}, the uniforms' frame {d.shape[:2]}")
+    d, t, n = d[m], hits["t"][m].astype(f32)[:, None], hits["normal"][m].astype(f32)
+    n = np.where((n * d).sum(-1, keepdims=True) > 0, -n, n).astype(f32)
+    pos = (np.asarray(u["camera"]["pos"], f32) + t * d).astype(f32)
+    org = (pos + n * (f32(1e-3) * np.maximum(f32(1.0), t))).astype(f32)   # off the surface: beyond the rounding of pos
+    rng = np.random.Generator(np.random.PCG64(seed))
+    r1, r2 = rng.random((len(org), n_dirs), dtype=f32), rng.random((len(org), n_dirs), dtype=f32)
+    phi, r = f32(2.0 * np.pi) * r1, np.sqrt(r2, dtype=f32)
+    # a tangent frame about n (any: the distribution is symmetric about n)
+    a = np.where(np.abs(n[:, 0:1]) > f32(0.5), np.array([0, 1, 0], f32), np.array([1, 0, 0], f32))
+    tx = np.cross(a, n).astype(f32)
+    tx /= np.sqrt((tx * tx).sum(-1, keepdims=True), dtype=f32)
+    ty = np.cross(n, tx).astype(f32)
+    dirs = ((r * np.cos(phi))[..., None] * tx[:, None, :] + (r * np.sin(phi))[..., None] * ty[:, None, :]
+            + np.sqrt(np.maximum(f32(1.0) - r2, f32(0)), dtype=f32)[..., None] * n[:, None, :]).astype(f32)
+    return m, np.repeat(org, n_dirs, axis=0), dirs.reshape(-1, 3)
+
+
+def ambient_occlusion(engine, hits, n_dirs=16, radius=1.0, seed=0, uniforms=None):
+    """Ambient occlusion of the first hits ``engine.render_hits()`` returned: the share of ``n_dirs`` cosine-weighted
+    directions per hit along which nothing lies within ``radius`` -- ONE any-hit query (Engine.occluded with tmax = radius;
+    point lights are no occluders).  float32 [rows, width] in [0, 1] in the orientation of the frame: 1 = open, 0 = enclosed;
+    1 where nothing was hit.  ``uniforms``: the camera, by default the uniforms the engine last accepted in an ``update``, ``render`` or ``frame_iterator``
+    call -- creating an engine sends it no scene, so one of them must come first (``render_hits`` needs it anyway) or
+    ``uniforms`` must be given."""
+    u = engine.uniforms if uniforms is None else uniforms
+    if u is None:
+        raise ValueError("the engine has accepted no update yet: call update() / render() first, or pass uniforms=")
+    m, org, dirs = ambient_occlusion_rays(u, hits, n_dirs, seed)
+    ao = np.ones(hits.shape, dtype=np.float32)
+    if len(org):
+        tmax = np.full(len(org), radius, dtype=np.float32)
+        occ = engine.occluded(org, dirs, tmax, abi.MASK_ALL & ~abi.MASK_LIGHTS)
+        blocked = (occ.reshape(-1, n_dirs) == abi.OCCL_OCCLUDED).sum(1)
+        ao[m] = np.float32(1.0) - blocked.astype(np.float32) / np.float32(n_dirs)
+    return ao
+
+
+def ao_u8(ao):
+    """an AO image as RGBA8 grey (rounded to nearest)"""
+    g = np.rint(np.clip(ao, 0, 1) * 255.0).astype(np.uint8)
+    return _rgba(np.stack([g, g, g], axis=-1))
 
 
 NAMES = ("depth", "normal", "albedo", "emission", "id")

@@ -169,9 +169,12 @@ struct rb_engine {
     rb::DevBuf<rb_ray> q_rays;
     rb::DevBuf<rb_hit> q_hits;
     rb::DevBuf<rb_surface> q_surf;
+    rb::DevBuf<float> q_tmax;        // rb_occluded: the piece's bounds and its result bytes
+    rb::DevBuf<uint8_t> q_occl;
     hipEvent_t ev_q[2] = {nullptr, nullptr};
     const char* last_query_kernel_name = "";
     float last_query_ms = 0.0f;
+    bool query_ms_pending = false;   // the device forms return without waiting: rb_last_query_ms reads ev_q when asked
 
     rb_stats stats{};
     float last_dispatch_ms = 0.0f;

@@ -385,6 +385,15 @@ struct QueryArgs {
 // the piece before has pushed the tree out of L2 (five times the render's L2 misses per frame; profiles/r06_query_rate.txt)
 constexpr uint32_t kQueryPiece = 1u << RB_QUERY_PIECE_LOG2;
 int launch_query(const KParams& p, const QueryArgs& q, void* stream, LaunchInfo* info);
+// ---- any-hit occlusion queries: the ray source of a QueryArgs (`hits` / `surf` unused) plus one bound
+// per ray and one result byte per ray.  `tmax` may be nullptr (every ray: 1e20f); `mask`: RB_MASK_* stages that may occlude.
+struct OcclArgs {
+    QueryArgs q;
+    const float* tmax;
+    uint8_t* out;
+    uint32_t mask;
+};
+int launch_occluded(const KParams& p, const OcclArgs& a, void* stream, LaunchInfo* info);
 Cam host_cam(const rb_uniforms& u);   // rb_kernels.hip: the camera of a launch, shader.wgsl:690,702-708
 
 // ---- rb_kernels.hip

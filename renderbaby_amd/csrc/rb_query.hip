@@ -5,6 +5,7 @@
 //   k_query        trees of at most one node and at most 64 spheres: the scans
 //   k_query_bvh    the per-lane reference walk (intersect_bvh) and, inside it, the per-lane sphere tree walk
 //   k_query_chunk  the chunked walk: k_trace_chunk's node and pooled leaf phases, then the same finish per lane
+// and their any-hit forms k_occl / k_occl_bvh / k_occl_chunk (rb_occluded) at the end of the file.
 // One ray per lane on a plain grid sized to the piece.  Measured against a depth-1 render of the same frame -- the persistent
 // grid with its item queue -- this form issues 15 % fewer vector instructions at a higher lane utilisation and, with pieces of
 // 2^22 rays, takes 14-17 % less time on the mesh scenes (profiles/r06_query_rate.txt); what did cost time was many small launches.
@@ -295,6 +296,315 @@ __global__ void __launch_bounds__(kQueryBlock) k_query_chunk(const KParams p, co
     query_finish(p, q, ql, th, stack, kQueryBlock, wave, lane, (lds_v4f*)wl);
 }
 
+// ================================================================= any-hit occlusion ====
+// out[i] = is there a hit with 0.001 < t < tmax[i] in the stages of `mask`?  The closest-hit search with its running bound fixed
+// at tmax: every test is the same device function on the same operands, a lane leaves at the first one that accepts.  The
+// stages run cheapest first -- ground, lights, spheres, triangles -- which an existential answer allows.
+constexpr uint32_t kOcclVisible = RB_OCCL_VISIBLE, kOcclOccluded = RB_OCCL_OCCLUDED, kOcclInvalid = RB_OCCL_INVALID;
+
+struct OcclLane {
+    QueryLane ql;
+    float tmax;     // min(tmax[i], 1e20f)
+    uint32_t res;   // the byte so far: INVALID, or VISIBLE
+    bool walk;      // valid, a bound above 0.001 and a stage to ask
+};
+
+DEV OcclLane occl_lane(const KParams& p, const OcclArgs& a, uint32_t wave, uint32_t lane) {
+    OcclLane r;
+    r.ql = query_lane(p, a.q, wave, lane);
+    r.tmax = 1e20f;
+    r.res = kOcclInvalid;
+    r.walk = false;
+    if (r.ql.live) {
+        const float tm = a.tmax != nullptr ? a.tmax[(size_t)wave * 64u + lane] : 1e20f;
+        if (r.ql.valid && tm == tm) {
+            r.res = kOcclVisible;
+            r.tmax = fminf(tm, 1e20f);
+            r.walk = r.tmax > 0.001f && a.mask != 0u;
+        }
+    }
+    return r;
+}
+
+// one result byte per lane: a wave's 64 consecutive bytes
+DEV void occl_store(const OcclArgs& a, const OcclLane& ol, uint32_t wave, uint32_t lane, bool occluded) {
+    if (ol.ql.live) a.out[(size_t)wave * 64u + lane] = (uint8_t)(occluded ? kOcclOccluded : ol.res);
+}
+
+// segment_spheres' / segment_resolve's scan of 96-byte {centre, radius | material} records with the bound fixed at tmax
+DEV bool occl_scan(cf4p rec, uint32_t count, f3 o, f3 d, float a, float tmax) {
+    for (uint32_t base = 0; base < count; base += 32u) {
+        const uint32_t n = (count - base < 32u) ? count - base : 32u;
+        uint32_t cand = 0u;
+        for (uint32_t k = 0; k < n; k++) {
+            const v4f cr = rec[(size_t)(base + k) * 6u];
+            const f3 oc = o - mk(cr.x, cr.y, cr.z);
+            const float half_b = dot(oc, d);
+            const float c = dot(oc, oc) - cr.w * cr.w;
+            const float disc = half_b * half_b - a * c;
+            cand |= (disc < 0.0f) ? 0u : (1u << k);
+        }
+        while (cand != 0u) {
+            const uint32_t k = (uint32_t)__ffs((int)cand) - 1u;
+            cand &= cand - 1u;
+            const v4f cr = rec[(size_t)(base + k) * 6u];
+            const float t = isect_sphere(o, d, a, mk(cr.x, cr.y, cr.z), cr.w);
+            if (t > 0.001f && t < tmax) return true;
+        }
+    }
+    return false;
+}
+
+// intersect_spheres_bvh with the bound fixed at tmax: sphere_child's cull `tn - dt > best` is argued for any best that bounds
+// the reported t of a hit that matters, and every hit that matters here is below tmax
+DEV bool occl_spheres_bvh(const KParams& p, f3 o, f3 d, float a, float tmax, uint32_t* stack, uint32_t stride) {
+    const f3 inv = mk(__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y), __builtin_amdgcn_rcpf(d.z));
+    const uint32_t dneg = sph_dir_signs(d);
+    const cf4p leafs = (cf4p)p.sph_leaf;
+    uint32_t cur = p.sph_root;
+    int sp = 0;
+    for (;;) {
+        if (cur != kSphNone && (cur & 0x80000000u) == 0u) {
+            cur = sphere_node_step(p, cur, o, inv, dneg, tmax, [&](uint32_t ref) {
+                stack[sp * stride] = ref;
+                sp++;
+            });
+            if (cur != kSphNone) continue;
+        } else if (cur != kSphNone) {
+            const uint32_t first = sph_leaf_first(cur), count = sph_leaf_count(cur);
+            for (uint32_t j = first; j < first + count; j++) {
+                const v4f cr = leafs[j];
+                const float t = isect_sphere(o, d, a, mk(cr.x, cr.y, cr.z), cr.w);
+                if (t > 0.001f && t < tmax) return true;
+            }
+        }
+        if (sp == 0) return false;
+        sp--;
+        cur = stack[sp * stride];
+    }
+}
+
+// ground, lights, spheres (shader.wgsl:552-565, :590-601, :574-586)
+template <bool SPHTREE>
+DEV bool occl_early(const KParams& p, uint32_t mask, f3 o, f3 d, float tmax, uint32_t* stack, uint32_t stride) {
+    if ((mask & RB_MASK_GROUND) != 0u && p.u.ground_enabled > 0u) {
+        const float t = isect_ground(o, d, p.u.ground_height);
+        if (t > 0.001f && t < tmax) return true;
+    }
+    const float a = dot(d, d);
+    if ((mask & RB_MASK_LIGHTS) != 0u && occl_scan((cf4p)p.lights, p.n_lights, o, d, a, tmax)) return true;
+    if ((mask & RB_MASK_SPHERES) != 0u) {
+        if constexpr (SPHTREE) {
+            if (p.sph_nodes != nullptr) return occl_spheres_bvh(p, o, d, a, tmax, stack, stride);
+        }
+        return occl_scan((cf4p)p.spheres, p.u.spheres_count, o, d, a, tmax);
+    }
+    return false;
+}
+
+// intersect_bvh's reference walk (never the library's own tree: launch_occluded clears fast_nodes as launch_query does): the
+// same nodes entered by the same boolean box tests, the same triangles tested, test_slot's acceptance against tmax
+template <bool MULTI>
+DEV bool occl_bvh(const KParams& p, f3 o, f3 d, float tmax, uint32_t* stack, uint32_t stride) {
+    const uint32_t node_count = p.u.bvh_node_count;
+    if (node_count == 0u) return false;
+    const f3 inv = mk(rcp_exact(d.x), rcp_exact(d.y), rcp_exact(d.z));
+    const cf4p nodes = (cf4p)p.nodes;
+    const cf4p ptris = (cf4p)p.ptris;
+    float u, v;
+    if (node_count == 1u) {
+        const v4f n0 = nodes[0], n1 = nodes[1];
+        const v4u n2 = ((cu4p)p.nodes)[2];
+        const uint32_t first = n2.z, count = n2.w;
+        const uint32_t end = (first + count < p.index_len) ? first + count : p.index_len;  // guard :331
+        if (first < end && isect_aabb(o, inv, mk(n0.x, n0.y, n0.z), mk(n1.x, n1.y, n1.z))) {
+            for (uint32_t slot = first; slot < end; slot++) {
+                const v4f a = ptris[(size_t)slot * 4u], b = ptris[(size_t)slot * 4u + 1u], c = ptris[(size_t)slot * 4u + 2u];
+                if (__float_as_uint(c.w) == 0u) continue;  // guard :336
+                const float t = isect_triangle(o, d, mk(a.x, a.y, a.z), mk(b.x, b.y, b.z), mk(c.x, c.y, c.z), u, v);
+                if (t > 0.001f && t < tmax) return true;
+            }
+        }
+        return false;
+    }
+    if constexpr (!MULTI) return false;
+    int sp = 1;
+    stack[0] = 0u;
+    while (sp > 0) {
+        sp--;
+        const uint32_t node_idx = stack[sp * stride];
+        if (node_idx >= node_count) continue;
+        const v4f n0 = nodes[node_idx * 3u], n1 = nodes[node_idx * 3u + 1u];
+        const v4u n2 = ((cu4p)p.nodes)[node_idx * 3u + 2u];
+        if (!isect_aabb(o, inv, mk(n0.x, n0.y, n0.z), mk(n1.x, n1.y, n1.z))) continue;
+        const uint32_t left = n2.x, right = n2.y, first = n2.z, count = n2.w;
+        if (count > 0u) {
+            for (uint32_t i = 0; i < count; i++) {
+                const uint32_t slot = first + i;
+                if (slot >= p.index_len) continue;
+                const v4f a = ptris[slot * 4u], b = ptris[slot * 4u + 1u], c = ptris[slot * 4u + 2u];
+                if (__float_as_uint(c.w) == 0u) continue;  // guard :336
+                const float t = isect_triangle(o, d, mk(a.x, a.y, a.z), mk(b.x, b.y, b.z), mk(c.x, c.y, c.z), u, v);
+                if (t > 0.001f && t < tmax) return true;
+            }
+        } else {
+            if (left < node_count) {
+                stack[sp * stride] = left;
+                sp++;
+            }
+            if (right < node_count) {
+                stack[sp * stride] = right;
+                sp++;
+            }
+        }
+    }
+    return false;
+}
+
+// ---- the per-lane walks.  MULTI = false: trees of at most one node and at most 64 spheres, no stack.
+template <bool MULTI>
+__global__ void __launch_bounds__(kQueryBlock) k_occl(const KParams p, const OcclArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_stack[];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t wave = blockIdx.x * (kQueryBlock / 64u) + (tid >> 6);
+    uint32_t* const stack = stack_column(s_stack, tid);
+    const OcclLane ol = occl_lane(fresh_params(p), a, wave, lane);
+    bool occluded = false;
+    if (ol.walk) {
+        occluded = occl_early<MULTI>(fresh_params(p), a.mask, ol.ql.o, ol.ql.d, ol.tmax, stack, kQueryBlock);
+        if (!occluded && (a.mask & RB_MASK_TRIANGLES) != 0u)
+            occluded = occl_bvh<MULTI>(fresh_params(p), ol.ql.o, ol.ql.d, ol.tmax, stack, kQueryBlock);
+    }
+    occl_store(a, ol, wave, lane, occluded);
+}
+
+// ---- the chunked walk: k_query_chunk's node and pooled leaf phases with the key starting at (bits(tmax) << 32), so that
+// chunk_node_step culls on tmax with the section 4.2 margin from the first step: that margin bounds the reference's reported t
+// of any accepted hit below a child, so no triangle with a reported t < tmax is culled.  The pooled lanes fold their t into
+// best[ray] as before; a ray whose best t has come below tmax after a round is answered and leaves the walk.
+__global__ void __launch_bounds__(kQueryBlock) k_occl_chunk(const KParams p, const OcclArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_stack[];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t wave = blockIdx.x * (kQueryBlock / 64u) + (tid >> 6);
+    uint32_t* const stack = stack_column(s_stack, tid);
+    unsigned char* const wl = reinterpret_cast<unsigned char*>(s_stack + p.stack_depth * kQueryBlock) + (tid >> 6) * kChunkWaveLds;
+    lds_v4f* const rayrec = (lds_v4f*)wl;                    // [64][2]: {o, chunk put aside}, {d, chunk stood at}
+    lds_u64* const best = (lds_u64*)(wl + 64u * 32u);        // [64]: (t bits) << 32 | rank
+    lds_u32* const units = (lds_u32*)(wl + 64u * 40u);       // [128]: ray lane (| 64: its second chunk) of every pooled (ray, chunk) pair
+    Tally<false> tl;
+
+    const OcclLane ol = occl_lane(fresh_params(p), a, wave, lane);
+    const f3 o = ol.ql.o, d = ol.ql.d;
+    bool occluded = false;
+    if (ol.walk) occluded = occl_early<true>(fresh_params(p), a.mask, o, d, ol.tmax, stack, kQueryBlock);
+    const uint32_t tmax_bits = __float_as_uint(ol.tmax);     // (positive: bit patterns order like the values)
+    const unsigned long long key = (unsigned long long)tmax_bits << 32;
+    bool trav = false;
+    uint32_t cur = kChunkNone, pend = kChunkNone;
+    int sp = 0;
+    const f3 inv = mk(rcp_exact(d.x), rcp_exact(d.y), rcp_exact(d.z));
+    if (ol.walk && !occluded && (a.mask & RB_MASK_TRIANGLES) != 0u) {   // the root's own box (shader.wgsl:283-315)
+        const KParams& fp = fresh_params(p);
+        const cf4p rn = (cf4p)fp.nodes;
+        const v4f n0 = rn[0], n1 = rn[1];
+        if (isect_aabb(o, inv, mk(n0.x, n0.y, n0.z), mk(n1.x, n1.y, n1.z))) {
+            cur = fp.chunk_root;
+            trav = true;
+        }
+    }
+    auto set_aside = [&]() {
+        if (trav && cur != kChunkNone && (cur & kChunkLeaf) != 0u && pend == kChunkNone) {
+            pend = cur;
+            if (sp == 0) {
+                cur = kChunkNone;
+            } else {
+                sp--;
+                cur = stack[sp * kQueryBlock];
+            }
+        }
+    };
+    set_aside();   // (a root that is one chunk)
+
+    while (__ballot(trav) != 0ull) {
+        // ---- tree: a few node steps while enough lanes are at a node
+#pragma unroll 1
+        for (int it = 0; it < RB_CHUNK_NODE_STEPS; ++it) {
+            const bool at_node = trav && cur != kChunkNone && (cur & kChunkLeaf) == 0u;
+            const uint32_t n = (uint32_t)__popcll(__ballot(at_node));
+            if (n == 0u || (it > 0 && n < (uint32_t)RB_CHUNK_NODE_LANES)) break;
+            if (at_node) {
+                if (!chunk_node_step<false>(p, stack, kQueryBlock, o, d, inv, ol.tmax, cur, sp, tl)) {
+                    if (pend != kChunkNone) cur = kChunkNone;   // nothing left to walk, one chunk still to be tested
+                    else trav = false;
+                }
+                set_aside();
+            }
+        }
+        // ---- leaves: pool the (ray, chunk) pairs of the lanes that hold a chunk, kChunkTris lanes per pair
+        const bool lf = trav && cur != kChunkNone && (cur & kChunkLeaf) != 0u;   // waits at a chunk
+        const bool lp = trav && pend != kChunkNone;                              // holds one aside
+        const unsigned long long m = __ballot(lf), mp = __ballot(lp);
+        const uint32_t n_pend = (uint32_t)__popcll(mp), n_units = n_pend + (uint32_t)__popcll(m);
+        const uint32_t n_node = (uint32_t)__popcll(__ballot(trav && cur != kChunkNone && !lf));
+        if (n_units != 0u && (n_units >= (uint32_t)RB_CHUNK_LEAF_LANES || n_node == 0u)) {
+            const unsigned long long below = (1ull << lane) - 1ull;
+            if (lp) units[(uint32_t)__popcll(mp & below)] = lane;
+            if (lf) units[n_pend + (uint32_t)__popcll(m & below)] = lane | 64u;
+            if (lf || lp) {
+                const v4f r0 = {o.x, o.y, o.z, __uint_as_float(pend)}, r1 = {d.x, d.y, d.z, __uint_as_float(cur)};
+                rayrec[lane * 2u] = r0;
+                rayrec[lane * 2u + 1u] = r1;
+                best[lane] = key;
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            const cf4p ca = (cf4p)p.chunk_a, cb = (cf4p)p.chunk_b, cc = (cf4p)p.chunk_c;
+            constexpr uint32_t kPairsPerRound = 64u / kChunkTris;
+#pragma unroll 1
+            for (uint32_t g0 = 0; g0 < n_units; g0 += kPairsPerRound) {
+                const uint32_t g = g0 + lane / kChunkTris;
+                const bool ok = g < n_units;
+                const uint32_t e = units[ok ? g : 0u];   // (entry 0 exists: n_units != 0)
+                const uint32_t rl = e & 63u;
+                const v4f r0 = rayrec[rl * 2u], r1 = rayrec[rl * 2u + 1u];
+                const uint32_t ref = __float_as_uint((e & 64u) ? r1.w : r0.w), first = ref & 0x03FFFFFFu, cnt = ((ref >> 26) & 31u) + 1u;
+                const uint32_t j = lane & (kChunkTris - 1u);
+                const bool valid = ok && j < cnt;
+                const uint32_t pos = first + (j < cnt ? j : 0u);   // (position `first` exists: a chunk holds at least one triangle)
+                const v4f ta = ca[pos], tb = cb[pos], tc = cc[pos];
+                float u, v;
+                const float t = isect_triangle(mk(r0.x, r0.y, r0.z), mk(r1.x, r1.y, r1.z), mk(ta.x, ta.y, ta.z), mk(tb.x, tb.y, tb.z),
+                                               mk(tc.x, tc.y, tc.z), u, v);
+                if (valid && t > 0.001f) {   // (the bound is the ray lane's: it compares after the round)
+                    const unsigned long long k = (unsigned long long)__float_as_uint(t) << 32;
+                    __hip_atomic_fetch_min(&best[rl], k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            if (lf || lp) {
+                if ((uint32_t)(best[lane] >> 32) < tmax_bits) {   // a reported t with 0.001 < t < tmax: answered
+                    occluded = true;
+                    trav = false;
+                    cur = kChunkNone;
+                    sp = 0;
+                }
+                pend = kChunkNone;
+                if (trav && (lf || cur == kChunkNone)) {   // the chunk the lane stood at is done, or there was nothing left to walk
+                    if (sp == 0) {
+                        trav = false;
+                    } else {
+                        sp--;
+                        cur = stack[sp * kQueryBlock];
+                    }
+                }
+                set_aside();
+            }
+        }
+    }
+    occl_store(a, ol, wave, lane, occluded);
+}
+
 }  // namespace
 
 int launch_query(const KParams& p_, const QueryArgs& q, void* stream_, LaunchInfo* info) {
@@ -321,6 +631,38 @@ int launch_query(const KParams& p_, const QueryArgs& q, void* stream_, LaunchInf
         } else {
             li.kernel_name = "k_query";
             hipLaunchKernelGGL(k_query<false>, grid, block, li.lds_bytes, stream, p, q);
+        }
+    }
+    if (info) *info = li;
+    return (int)hipGetLastError();
+}
+
+int launch_occluded(const KParams& p_, const OcclArgs& a, void* stream_, LaunchInfo* info) {
+    KParams p = p_;
+    p.cam = host_cam(p.u);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    LaunchInfo li{};
+    li.block = kQueryBlock;
+    const uint64_t waves = ((uint64_t)a.q.n + 63u) / 64u;
+    if (a.q.rays == nullptr || a.out == nullptr || waves > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
+    if (waves == 0u) return 0;
+    li.grid = (uint32_t)((waves + kQueryBlock / 64u - 1u) / (kQueryBlock / 64u));
+    li.lds_bytes = (size_t)kStackEntryBytes * p.stack_depth * kQueryBlock;
+    // the walk, by launch_query's rule
+    const bool multi = p.u.bvh_node_count > 1u && !p.no_leaf_stepping;
+    const dim3 grid(li.grid), block(li.block);
+    if (multi && p.chunk_nodes != nullptr) {
+        li.kernel_name = "k_occl_chunk";
+        li.lds_bytes += (kQueryBlock / 64u) * kChunkWaveLds;
+        hipLaunchKernelGGL(k_occl_chunk, grid, block, li.lds_bytes, stream, p, a);
+    } else {
+        p.fast_nodes = nullptr;   // own-tree engines: the reference walk over the caller's tree, as k_query_bvh answers them
+        if (p.u.bvh_node_count > 1u || p.sph_nodes != nullptr) {
+            li.kernel_name = "k_occl_bvh";
+            hipLaunchKernelGGL(k_occl<true>, grid, block, li.lds_bytes, stream, p, a);
+        } else {
+            li.kernel_name = "k_occl";
+            hipLaunchKernelGGL(k_occl<false>, grid, block, li.lds_bytes, stream, p, a);
         }
     }
     if (info) *info = li;

@@ -910,7 +910,8 @@ int query_copy_out(rb_engine* e, void* dst, const void* src, size_t bytes, bool 
     return RB_OK;
 }
 
-int query_begin(rb_engine* e, rb::KParams* p, size_t records, bool rays, bool surf) {
+// the scene as a query's kernels see it, and the query's two events
+int query_params(rb_engine* e, rb::KParams* p) {
     int rc = require_ready(e);
     if (!rc) rc = ensure_prepared(e);
     if (rc) return rc;
@@ -918,6 +919,13 @@ int query_begin(rb_engine* e, rb::KParams* p, size_t records, bool rays, bool su
     if (!e->stack_depth_covers) return rb::fail(e, RB_ERR_DEVICE, "internal: a traversal is deeper than its LDS stack column (%u entries)", p->stack_depth);
     for (hipEvent_t& x : e->ev_q)
         if (!x) HIP_TRY(e, hipEventCreate(&x));
+    e->query_ms_pending = false;
+    return RB_OK;
+}
+
+int query_begin(rb_engine* e, rb::KParams* p, size_t records, bool rays, bool surf) {
+    const int rc = query_params(e, p);
+    if (rc) return rc;
     if (rays) HIP_TRY(e, e->q_rays.reserve(records));
     HIP_TRY(e, e->q_hits.reserve(records));
     if (surf) HIP_TRY(e, e->q_surf.reserve(records));
@@ -985,6 +993,122 @@ int pixel_hits_locked(rb_engine* e, uint32_t x0, uint32_t y0, uint32_t w, uint32
         if (rc) return rc;
     }
     return RB_OK;
+}
+
+// ---- any-hit occlusion and the device forms (rb_abi.h)
+int occluded_locked(rb_engine* e, const rb_ray* rays, const float* tmax, size_t n, uint32_t mask, uint8_t* out) {
+    rb::KParams p{};
+    int rc = query_params(e, &p);
+    e->last_query_ms = 0.0f;
+    if (rc || n == 0) return rc;
+    const size_t piece = std::min<size_t>(n, rb::kQueryPiece);
+    HIP_TRY(e, e->q_rays.reserve(piece));
+    if (tmax) HIP_TRY(e, e->q_tmax.reserve(piece));
+    HIP_TRY(e, e->q_occl.reserve(piece));
+    const bool pinned = page_locked(out);
+    for (size_t done = 0; done < n; done += piece) {
+        const size_t m = std::min(piece, n - done);
+        HIP_TRY(e, hipMemcpyAsync(e->q_rays.ptr, rays + done, m * sizeof(rb_ray), hipMemcpyHostToDevice, e->stream));
+        if (tmax) HIP_TRY(e, hipMemcpyAsync(e->q_tmax.ptr, tmax + done, m * sizeof(float), hipMemcpyHostToDevice, e->stream));
+        rb::OcclArgs a{};
+        a.q.rays = e->q_rays.ptr;
+        a.q.n = static_cast<uint32_t>(m);
+        a.tmax = tmax ? e->q_tmax.ptr : nullptr;
+        a.out = e->q_occl.ptr;
+        a.mask = mask;
+        rb::LaunchInfo li{};
+        HIP_TRY(e, hipEventRecord(e->ev_q[0], e->stream));
+        const int st = rb::launch_occluded(p, a, e->stream, &li);
+        if (st) return rb::fail(e, RB_ERR_DEVICE, "occlusion kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
+        HIP_TRY(e, hipEventRecord(e->ev_q[1], e->stream));
+        if (li.kernel_name) e->last_query_kernel_name = li.kernel_name;
+        rc = query_copy_out(e, out + done, e->q_occl.ptr, m, pinned);
+        if (rc) return rc;
+        HIP_TRY(e, hipStreamSynchronize(e->stream));   // the scratch is the next piece's
+        float ms = 0.0f;
+        HIP_TRY(e, hipEventElapsedTime(&ms, e->ev_q[0], e->ev_q[1]));
+        e->last_query_ms += ms;
+    }
+    return RB_OK;
+}
+
+// `bytes` of device memory of the engine's device at p, aligned to `align`?
+int device_range(rb_engine* e, const void* p, size_t bytes, size_t align, const char* what) {
+    hipPointerAttribute_t attr{};
+    const hipError_t st = hipPointerGetAttributes(&attr, p);
+    if (st != hipSuccess) (void)hipGetLastError();   // a pointer the runtime does not know: pageable host memory
+    if (st != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != e->device)
+        return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s is not device memory of device %d", what, e->device);
+    if (reinterpret_cast<uintptr_t>(p) % align != 0u) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s is not %zu-byte aligned", what, align);
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) {
+        (void)hipGetLastError();
+        return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: its allocation is unknown to the runtime", what);
+    }
+    const size_t off = static_cast<size_t>(static_cast<const char*>(p) - static_cast<const char*>(base));
+    if (off > size || bytes > size - off) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: its allocation ends before %zu bytes", what, bytes);
+    return RB_OK;
+}
+
+// queue one launch between the query's events on the caller's buffers; nothing is waited for
+template <class Launch>
+int device_query_locked(rb_engine* e, Launch&& launch) {
+    rb::KParams p{};
+    const int rc = query_params(e, &p);
+    e->last_query_ms = 0.0f;
+    if (rc) return rc;
+    rb::LaunchInfo li{};
+    HIP_TRY(e, hipEventRecord(e->ev_q[0], e->stream));
+    const int st = launch(p, &li);
+    if (st) return rb::fail(e, RB_ERR_DEVICE, "query kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
+    HIP_TRY(e, hipEventRecord(e->ev_q[1], e->stream));
+    if (li.kernel_name) e->last_query_kernel_name = li.kernel_name;
+    e->query_ms_pending = true;   // rb_last_query_ms reads the events when it is asked
+    return RB_OK;
+}
+
+int occluded_device_locked(rb_engine* e, const rb_ray* d_rays, const float* d_tmax, size_t n, uint32_t mask, uint8_t* d_out) {
+    int rc = device_range(e, d_rays, n * sizeof(rb_ray), 16, "d_rays");
+    if (!rc && d_tmax) rc = device_range(e, d_tmax, n * sizeof(float), 4, "d_tmax");
+    if (!rc) rc = device_range(e, d_out, n, 1, "d_out");
+    if (rc) return rc;
+    return device_query_locked(e, [&](const rb::KParams& p, rb::LaunchInfo* li) {
+        rb::OcclArgs a{};
+        a.q.rays = d_rays;
+        a.q.n = static_cast<uint32_t>(n);
+        a.tmax = d_tmax;
+        a.out = d_out;
+        a.mask = mask;
+        return rb::launch_occluded(p, a, e->stream, li);
+    });
+}
+
+int cast_rays_device_locked(rb_engine* e, const rb_ray* d_rays, size_t n, rb_hit* d_hits, rb_surface* d_surf) {
+    int rc = device_range(e, d_rays, n * sizeof(rb_ray), 16, "d_rays");
+    if (!rc) rc = device_range(e, d_hits, n * sizeof(rb_hit), 16, "d_hits");
+    if (!rc && d_surf) rc = device_range(e, d_surf, n * sizeof(rb_surface), 16, "d_surf");
+    if (rc) return rc;
+    return device_query_locked(e, [&](const rb::KParams& p, rb::LaunchInfo* li) {
+        rb::QueryArgs q{};
+        q.rays = d_rays;
+        q.n = static_cast<uint32_t>(n);
+        q.hits = d_hits;
+        q.surf = d_surf;
+        return rb::launch_query(p, q, e->stream, li);
+    });
+}
+
+// the engine that answers a query (a multi-device handle: devices[0], which holds the whole scene), made current
+rb_engine* answering(rb_engine* e) {
+    rb_engine* const t = rb::is_group(e) ? e->parts[0].get() : e;
+    rb::set_device(t);
+    return t;
+}
+
+int answered(rb_engine* e, rb_engine* t, int rc) {
+    if (rc && t != e) copy_error(e, t);
+    return rc;
 }
 
 }  // namespace
@@ -1529,6 +1653,37 @@ int rb_pick(rb_engine* e, uint32_t px, uint32_t py, rb_hit* hit_out, rb_surface*
     return rc;
 }
 
+int rb_occluded(rb_engine* e, const rb_ray* rays, const float* tmax, size_t n, uint32_t mask, uint8_t* out) {
+    if (!e) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (n > 0x7FFFFFFFull - 63ull) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "rb_occluded takes at most 2^31 - 64 rays per call");
+    if (mask > RB_MASK_ALL) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "mask has bits above RB_MASK_ALL");
+    if (n > 0 && (!rays || !out)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "rays / out is NULL");
+    rb_engine* const t = answering(e);
+    return answered(e, t, occluded_locked(t, rays, tmax, n, mask, out));
+}
+
+int rb_occluded_device(rb_engine* e, const rb_ray* d_rays, const float* d_tmax, size_t n, uint32_t mask, uint8_t* d_out) {
+    if (!e) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (n > 0x7FFFFFFFull - 63ull) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "rb_occluded_device takes at most 2^31 - 64 rays per call");
+    if (mask > RB_MASK_ALL) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "mask has bits above RB_MASK_ALL");
+    if (n > 0 && (!d_rays || !d_out)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "d_rays / d_out is NULL");
+    rb_engine* const t = answering(e);
+    if (n == 0) return answered(e, t, require_ready(t));
+    return answered(e, t, occluded_device_locked(t, d_rays, d_tmax, n, mask, d_out));
+}
+
+int rb_cast_rays_device(rb_engine* e, const rb_ray* d_rays, size_t n, rb_hit* d_hits, rb_surface* d_surf) {
+    if (!e) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (n > 0x7FFFFFFFull - 63ull) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "rb_cast_rays_device takes at most 2^31 - 64 rays per call");
+    if (n > 0 && (!d_rays || !d_hits)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "d_rays / d_hits is NULL");
+    rb_engine* const t = answering(e);
+    if (n == 0) return answered(e, t, require_ready(t));
+    return answered(e, t, cast_rays_device_locked(t, d_rays, n, d_hits, d_surf));
+}
+
 const char* rb_last_query_kernel_name(const rb_engine* e) {
     if (!e) return "";
     return rb::is_group(e) ? e->parts[0]->last_query_kernel_name : e->last_query_kernel_name;
@@ -1537,7 +1692,14 @@ const char* rb_last_query_kernel_name(const rb_engine* e) {
 int rb_last_query_ms(rb_engine* e, float* ms) {
     if (!e || !ms) return RB_ERR_NULL_ARGUMENT;
     std::lock_guard<std::mutex> lock(e->mu);
-    *ms = rb::is_group(e) ? e->parts[0]->last_query_ms : e->last_query_ms;
+    rb_engine* const t = rb::is_group(e) ? e->parts[0].get() : e;
+    if (t->query_ms_pending) {   // a device form returned without waiting: its events are read here
+        rb::set_device(t);
+        HIP_TRY(e, hipEventSynchronize(t->ev_q[1]));
+        HIP_TRY(e, hipEventElapsedTime(&t->last_query_ms, t->ev_q[0], t->ev_q[1]));
+        t->query_ms_pending = false;
+    }
+    *ms = t->last_query_ms;
     return RB_OK;
 }
 

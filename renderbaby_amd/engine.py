@@ -167,6 +167,11 @@ class Frame:
             raise RenderError(0, f"Frame pixel size mismatch: expected {self.expected_size()} bytes, got {self.pixels.size}")
 
 
+def _is_tensor(x):
+    """a torch tensor?  (without importing torch for callers that never pass one)"""
+    return type(x).__module__.split(".")[0] == "torch" and hasattr(x, "data_ptr")
+
+
 class Engine:
     """``engine_pathtracer::Engine`` for the HIP backend."""
 
@@ -182,6 +187,7 @@ class Engine:
         (RB_FLAG_BUILD_TREE): send configs with ``RenderConfig.from_scene(scene, with_tree=False)``."""
         self._lib = load()
         cfg, keep = rc.to_c()
+        self.uniforms = None   # set by the first update that succeeds (_remember)
         opt = abi.Options()
         opt.device = device
         opt.shard_rank, opt.shard_count, opt.stripe_rows = shard_rank, shard_count, stripe_rows
@@ -205,6 +211,14 @@ class Engine:
         opt._reserved[2] = queue_batch   # items a wave reserves per queue atomic (0 = the launcher's choice)
         opt._reserved[3] = 1 if no_leaf_stepping else 0   # ablation: per-segment traversal for multi-node trees
         opt._reserved[4] = int(lds_mode)   # LDS staging of small meshes: 0 = when it fits, 1 = never
+        # who answers queries: devices[0], `device`, or for -1 the device that is current now, which is the one the library
+        # takes in rb_create_ex just below (hipGetDevice of the one HIP runtime of this process)
+        self.query_device = int(devices[0]) if devices is not None else int(device)
+        if self.query_device < 0:
+            cur = C.c_int(-1)
+            if self._lib.hipGetDevice(C.byref(cur)) != 0 or cur.value < 0:
+                raise RenderError(16, "device=-1: hipGetDevice names no current device")
+            self.query_device = cur.value
         if devices is not None:
             devs = (C.c_int32 * len(devices))(*[int(d) for d in devices])
             self._h = self._lib.rb_create_multi(C.byref(cfg), C.byref(opt), devs, len(devices))
@@ -232,6 +246,11 @@ class Engine:
         except Exception:
             pass
 
+    def _remember(self, rc):
+        """the uniforms the engine last accepted (abi.UNIFORMS[1]; called after the update succeeded): the camera of the pixel-centre rays, for aov.ambient_occlusion"""
+        if rc.uniforms.tag in (abi.CREATE, abi.UPDATE):
+            self.uniforms = np.array(np.atleast_1d(rc.uniforms.value), dtype=abi.UNIFORMS).reshape(-1)[:1].copy()
+
     def _check(self, rc):
         if rc != abi.RB_OK:
             raise RenderError(rc, (self._lib.rb_last_error(self._h) or b"").decode())
@@ -240,6 +259,7 @@ class Engine:
     def update(self, rc: RenderConfig):
         cfg, keep = rc.to_c()
         self._check(self._lib.rb_update(self._h, C.byref(cfg)))
+        self._remember(rc)
         del keep
 
     def size(self):
@@ -284,6 +304,7 @@ class Engine:
     def render(self, rc: RenderConfig) -> Frame:
         cfg, keep = rc.to_c()
         self._check(self._lib.rb_update(self._h, C.byref(cfg)))
+        self._remember(rc)
         del keep
         w, h = self._frame_shape()
         if self.comm_rank not in (None, 0):   # a non-root rank of a process group: its stripes go to rank 0
@@ -307,6 +328,7 @@ class Engine:
         """``passes_per_frame`` > 1 (extension): one frame per that many samples instead of per sample."""
         cfg, keep = rc.to_c()
         self._check(self._lib.rb_iter_begin(self._h, C.byref(cfg)))
+        self._remember(rc)
         del keep
         self._check(self._lib.rb_iter_set_passes_per_frame(self._h, passes_per_frame))
         return FrameIterator(self)
@@ -368,16 +390,69 @@ class Engine:
         """rb_cast_rays: (n, 3) origins and directions (any length: the device normalises) -> abi.HIT[n], or
         (abi.HIT[n], abi.SURFACE[n]) with ``surfaces``.  ``hits_out`` / ``surfaces_out``: arrays to fill instead of new
         ones (page-locked ones are filled by DMA)."""
+        return self.cast_ray_records(self._ray_records(origins, dirs), surfaces, hits_out, surfaces_out)
+
+    @staticmethod
+    def _ray_records(origins, dirs):
+        """abi.RAY[n] from (n, 3) numpy origins and directions, or an (n, 8) float32 tensor from (n, 3) torch tensors"""
+        if _is_tensor(origins) or _is_tensor(dirs):
+            import torch
+            if not (_is_tensor(origins) and _is_tensor(dirs)) or origins.dtype != torch.float32 or dirs.dtype != torch.float32 \
+                    or origins.device != dirs.device:
+                raise ValueError("origins and dirs must both be float32 tensors on one device")
+            o, d = origins.reshape(-1, 3), dirs.reshape(-1, 3)
+            if len(o) != len(d):
+                raise ValueError("origins and dirs differ in length")
+            rays = torch.zeros((len(o), 8), dtype=torch.float32, device=o.device)
+            rays[:, 0:3], rays[:, 4:7] = o, d
+            return rays
         o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
         d = np.asarray(dirs, dtype=np.float32).reshape(-1, 3)
         if len(o) != len(d):
             raise ValueError("origins and dirs differ in length")
         rays = np.zeros(len(o), dtype=abi.RAY)
         rays["origin"], rays["dir"] = o, d
-        return self.cast_ray_records(rays, surfaces, hits_out, surfaces_out)
+        return rays
+
+    def _device_tensor(self, t, dtype, row, what):
+        """data_ptr() of a tensor the device forms may read or write: on the engine's device, contiguous, of `dtype`, rows of
+        `row` elements (None: one element per ray); anything else is a ValueError.  Returns (pointer, rows)."""
+        import torch
+        want = torch.device("cuda", self.query_device)
+        if not _is_tensor(t) or t.device != want:
+            raise ValueError(f"{what}: a torch tensor on {want} is needed (the engine's device)")
+        if t.dtype != dtype or not t.is_contiguous():
+            raise ValueError(f"{what}: a contiguous {dtype} tensor is needed")
+        if row is None:
+            if t.dim() != 1:
+                raise ValueError(f"{what}: one element per ray is needed")
+        elif t.dim() != 2 or t.shape[1] != row:
+            raise ValueError(f"{what}: shape (n, {row}) is needed")
+        return (t.data_ptr() if t.numel() else None), t.shape[0]
+
+    def _device_call(self, fn, *args):
+        """a device form between torch's stream and the engine's: torch's queued work first, rb_sync after"""
+        import torch
+        torch.cuda.current_stream(self.query_device).synchronize()
+        self._check(fn(self._h, *args))
+        self._check(self._lib.rb_sync(self._h))
 
     def cast_ray_records(self, rays, surfaces=False, hits_out=None, surfaces_out=None):
-        """rb_cast_rays on an abi.RAY array as it stands (no copy when it is contiguous)."""
+        """rb_cast_rays on an abi.RAY array as it stands (no copy when it is contiguous).  A float32 tensor of shape (n, 8) on
+        the engine's device goes to rb_cast_rays_device instead: the records come back as float32 tensors of shape (n, 12) on
+        the device (``.cpu().numpy().view(abi.HIT)`` names their fields), and nothing crosses to the host."""
+        if _is_tensor(rays) or _is_tensor(hits_out) or _is_tensor(surfaces_out):
+            import torch
+            rp, n = self._device_tensor(rays, torch.float32, 8, "rays")
+            hits = torch.empty((n, 12), dtype=torch.float32, device=rays.device) if hits_out is None else hits_out
+            want_surf = surfaces or surfaces_out is not None
+            surf = (torch.empty((n, 12), dtype=torch.float32, device=rays.device) if surfaces_out is None else surfaces_out) if want_surf else None
+            hp, nh = self._device_tensor(hits, torch.float32, 12, "hits_out")
+            sp, ns = self._device_tensor(surf, torch.float32, 12, "surfaces_out") if want_surf else (None, n)
+            if nh != n or ns != n:
+                raise ValueError("rays, hits_out and surfaces_out differ in length")
+            self._device_call(self._lib.rb_cast_rays_device, rp, n, hp, sp)
+            return hits if surf is None else (hits, surf)
         rays = np.ascontiguousarray(rays, dtype=abi.RAY)
         n = len(rays)
         hits = np.empty(n, dtype=abi.HIT) if hits_out is None else hits_out
@@ -385,6 +460,38 @@ class Engine:
         self._check(self._lib.rb_cast_rays(self._h, rays.ctypes.data if n else None, n, hits.ctypes.data if n else None,
                                            surf.ctypes.data if (surf is not None and n) else None))
         return hits if surf is None else (hits, surf)
+
+    # ---- any-hit occlusion (rb_abi.h)
+    def occluded(self, origins, dirs, tmax=None, mask=abi.MASK_ALL, out=None):
+        """rb_occluded: is anything within (0.001, tmax) along each ray, among the stages of ``mask``?  (n, 3) origins and
+        directions (any length: the device normalises), ``tmax`` n float32 or None (no bound) -> uint8[n] of abi.OCCL_*.
+        Torch tensors on the engine's device go to rb_occluded_device and a uint8 tensor on the device comes back."""
+        return self.occluded_records(self._ray_records(origins, dirs), tmax, mask, out)
+
+    def occluded_records(self, rays, tmax=None, mask=abi.MASK_ALL, out=None):
+        """rb_occluded on an abi.RAY array, or rb_occluded_device on a float32 tensor of shape (n, 8)."""
+        if _is_tensor(rays) or _is_tensor(tmax) or _is_tensor(out):
+            import torch
+            rp, n = self._device_tensor(rays, torch.float32, 8, "rays")
+            tp, nt = self._device_tensor(tmax, torch.float32, None, "tmax") if tmax is not None else (None, n)
+            res = torch.empty(n, dtype=torch.uint8, device=rays.device) if out is None else out
+            op, no = self._device_tensor(res, torch.uint8, None, "out")
+            if nt != n or no != n:
+                raise ValueError("rays, tmax and out differ in length")
+            self._device_call(self._lib.rb_occluded_device, rp, tp, n, int(mask), op)
+            return res
+        rays = np.ascontiguousarray(rays, dtype=abi.RAY)
+        n = len(rays)
+        if tmax is not None:
+            tmax = np.ascontiguousarray(tmax, dtype=np.float32).reshape(-1)
+            if len(tmax) != n:
+                raise ValueError("rays and tmax differ in length")
+        res = np.empty(n, dtype=np.uint8) if out is None else out
+        if res.dtype != np.uint8 or res.shape != (n,) or not res.flags.c_contiguous:
+            raise ValueError("out: a contiguous uint8 array of n elements is needed")
+        self._check(self._lib.rb_occluded(self._h, rays.ctypes.data if n else None, tmax.ctypes.data if (tmax is not None and n) else None,
+                                          n, int(mask), res.ctypes.data if n else None))
+        return res
 
     def render_hits(self, surfaces=False):
         """rb_render_hits: the first hit of every pixel centre as abi.HIT[rows, width] (and abi.SURFACE with ``surfaces``) in

@@ -2,12 +2,13 @@
 
     python tools/render_scene.py scene.rscn out.png [--spp N] [--max-depth D] [--fast-bvh] [--device-bvh]
                                  [--width W --height H] [--included-root DIR] [--every N]
-                                 [--aov depth,normal,albedo,emission,id]
+                                 [--aov depth,normal,albedo,emission,id,ao] [--ao-radius R]
 
 scene file -> scene_io.load_scene (the importer's and the Scene->RenderConfig adapter's rules) ->
 RenderConfig -> librenderbaby_hip.so -> Frame -> PNG.  With --every N the progressive iterator is used
 and a frame is written every N samples (out_0001.png, ...).  --aov writes the first-hit buffers of the pixel centres
-(Engine.render_hits -> renderbaby_amd.aov) next to the frame as out.<name>.png.
+(Engine.render_hits -> renderbaby_amd.aov) next to the frame as out.<name>.png; `ao` is ambient occlusion over those hits
+(aov.ambient_occlusion: 16 directions per hit, one any-hit query).
 """
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -20,12 +21,13 @@ ap.add_argument("--width", type=int, default=0); ap.add_argument("--height", typ
 ap.add_argument("--fast-bvh", action="store_true"); ap.add_argument("--device-bvh", action="store_true")
 ap.add_argument("--build-tree", action="store_true", help="send triangles only: the engine builds the mesh's tree on the device")
 ap.add_argument("--included-root", default=None); ap.add_argument("--every", type=int, default=0)
-ap.add_argument("--aov", default="", help="comma-separated first-hit buffers to write as out.<name>.png: " + ", ".join(aov.NAMES))
+ap.add_argument("--aov", default="", help="comma-separated first-hit buffers to write as out.<name>.png: " + ", ".join(aov.NAMES) + ", ao")
+ap.add_argument("--ao-radius", type=float, default=1.0, help="how far an occluder may be for --aov ao")
 a = ap.parse_args()
 aovs = [n for n in a.aov.split(",") if n]
 for n in aovs:
-    if n not in aov.NAMES:
-        ap.error(f"unknown AOV {n!r}: one of {', '.join(aov.NAMES)}")
+    if n not in aov.NAMES + ("ao",):
+        ap.error(f"unknown AOV {n!r}: one of {', '.join(aov.NAMES)}, ao")
 
 t0 = time.time()
 s = scene_io.load_scene(a.scene, total_samples=a.spp, max_depth=a.max_depth, included_root=a.included_root)
@@ -51,7 +53,7 @@ if aovs:
     hits, surf = eng.render_hits(surfaces=True)
     base, ext = os.path.splitext(a.png)
     for n in aovs:
-        img = aov.image(n, hits, surf)
+        img = aov.ao_u8(aov.ambient_occlusion(eng, hits, radius=a.ao_radius)) if n == "ao" else aov.image(n, hits, surf)
         scene_io.export_png(f"{base}.{n}{ext}", Frame(img.shape[1], img.shape[0], img))
     print(f"first-hit buffers with {eng.last_query_kernel_name()} in {eng.last_query_ms():.3f} ms: {', '.join(aovs)}")
 eng.close()
