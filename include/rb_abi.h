@@ -590,6 +590,54 @@ int rb_occluded_device(rb_engine* e, const rb_ray* d_rays, const float* d_tmax, 
  * On a sharded engine rays are whole-scene rays, as for rb_cast_rays. */
 int rb_cast_rays_device(rb_engine* e, const rb_ray* d_rays, size_t n, rb_hit* d_hits, rb_surface* d_surf);
 
+/* ---- Edge-avoiding denoiser over the first-hit buffers (no reference counterpart).  An a-trous wavelet
+ * filter (Dammertz et al. 2010) on the albedo-demodulated mean radiance, guided by the first hit of every pixel-centre ray.
+ * Section 13 is the normative definition: every step one IEEE binary32 operation in a fixed order, so that the device's result
+ * equals the numpy model renderbaby_amd/denoise.py bit for bit.  All buffers are in the orientation of the delivered frame
+ * (row-major, top row first, x mirrored). */
+typedef struct rb_guide {                                                                           /* 48 B */
+    float normal[3];    /* the first hit's rb_hit.normal, unchanged */
+    float t;            /* its rb_hit.t */
+    float pos[3];       /* origin + t * d, one multiply and one add per component; d: the direction the query kernel normalised */
+    uint32_t cls;       /* the hit's RB_HIT_* kind if the pixel is filterable; 0 = pass-through: NONE, INVALID, LIGHT, any emissive component > 0 */
+    float albedo[3];    /* its rb_surface.albedo, unchanged */
+    float _pad;
+} rb_guide;
+typedef struct rb_denoise_params {                                                                  /* 32 B */
+    uint32_t iterations;         /* 0..8; iteration i taps at distance 2^i; 0: the mean radiance passes through, no demodulation */
+    uint32_t normal_power_log2;  /* 0..10: max(0, n_p . n_q) is squared this many times */
+    float sigma_depth;           /* > 0: plane distance |n_p . (P_q - P_p)| at which a tap's weight reaches 0, as a share of t_p */
+    float sigma_color;           /* colour edge-stopping width of iteration 0 (halved per iteration); <= 0 switches the term off */
+    float albedo_floor;          /* > 0: demodulation divides by max(albedo, albedo_floor) */
+    uint32_t flags;              /* must be 0 */
+    uint32_t _reserved[2];       /* must be 0 */
+} rb_denoise_params;
+/* The defaults (DESIGN.md section 13 records the measurements that chose them). */
+int rb_denoise_default_params(rb_denoise_params* p);
+/* The filter on its own, no engine: host arrays in and out, the work on `device` (-1 = current).  color4: the mean radiance,
+ * w * h vec4 (the fourth component is ignored); guides: w * h records; out4 (w * h vec4, w = 1) and rgba_out (w * h RGBA8,
+ * color_map(out / (out + 1))): either may be NULL, not both.  NULL params / color4 / guides: RB_ERR_NULL_ARGUMENT before any
+ * device is touched; parameters out of range or non-finite, or w * h >= 2^31: RB_ERR_INVALID_OPTIONS; w * h == 0 is RB_OK. */
+int rb_denoise_buffers(int32_t device, const rb_denoise_params* params, uint32_t w, uint32_t h, const float* color4,
+                       const rb_guide* guides, float* out4, uint8_t* rgba_out);
+/* The filter over the engine's committed accumulation (what rb_read_accumulation reads), guided by the engine's guide buffer:
+ * made on the device by the first denoise after an accepted rb_update -- the pixel-centre rays through the query kernels of
+ * the walk the scene takes, packed by one kernel -- and kept until the next accepted rb_update.  rgba_out (w * h * 4 bytes)
+ * and linear_out (w * h vec4): either may be NULL, not both; page-locked destinations are recognised as by rb_render.  The
+ * side effects are a query's: none on the accumulation, the frames, the colour buffer, rb_get_stats or the random sequence; a
+ * pass the iterator has started ahead stays valid.  A sharded engine and a multi-device handle are RB_ERR_INVALID_OPTIONS (a
+ * tap would cross a stripe boundary); before the first update: RB_ERR_NOT_INITIALIZED. */
+int rb_denoise(rb_engine* e, const rb_denoise_params* params, uint8_t* rgba_out, float* linear_out);
+/* The same with the outputs in device memory of the engine's device (validated like rb_cast_rays_device's buffers: a host
+ * pointer, another device's memory, a misaligned pointer -- 4 bytes for d_rgba_out, 16 for d_linear_out -- or an allocation
+ * that ends early is RB_ERR_INVALID_OPTIONS).  Queued on the engine's stream; returns without waiting: rb_sync is the wait. */
+int rb_denoise_device(rb_engine* e, const rb_denoise_params* params, uint8_t* d_rgba_out, float* d_linear_out);
+/* The guide buffer the engine filters with (w * h records; made now if the engine has none since its last update). */
+int rb_denoise_guides(rb_engine* e, rb_guide* guides_out);
+/* Measurement aid for tools/denoise_rate.py (it may change or go): kernel time of the most recent denoise -- prepare, iterations
+ * and finish, HIP events on the engine's stream, ms -- and, if not NULL, of the guide build it had to make (0: it had the guides). */
+int rb_last_denoise_ms(rb_engine* e, float* ms, float* guide_build_ms);
+
 /* Which builder produced the library's own tree: "host-sah", "device-ploc", "device-lbvh", or "" when
  * there is none (flag not set, single-node tree, or the scene keeps the exact walk).  Valid after the
  * first rb_dispatch / rb_render that follows an update.  `build_ms`, if not NULL, receives the wall
@@ -644,6 +692,14 @@ static_assert(offsetof(rb_surface, flags) == 12, "flags @12");
 static_assert(offsetof(rb_surface, emissive) == 16, "emissive @16");
 static_assert(offsetof(rb_surface, texture_index) == 28, "texture_index @28");
 static_assert(offsetof(rb_surface, uv) == 32, "uv @32");
+static_assert(sizeof(rb_guide) == 48, "rb_guide is 48 B");
+static_assert(sizeof(rb_denoise_params) == 32, "rb_denoise_params is 32 B");
+static_assert(offsetof(rb_guide, t) == 12, "t @12");
+static_assert(offsetof(rb_guide, pos) == 16, "pos @16");
+static_assert(offsetof(rb_guide, cls) == 28, "cls @28");
+static_assert(offsetof(rb_guide, albedo) == 32, "albedo @32");
+static_assert(offsetof(rb_denoise_params, sigma_depth) == 8, "sigma_depth @8");
+static_assert(offsetof(rb_denoise_params, flags) == 20, "flags @20");
 #else
 _Static_assert(sizeof(rb_camera) == 48, "Camera is 48 B");
 _Static_assert(sizeof(rb_uniforms) == 144, "Uniforms is 144 B");
@@ -658,6 +714,8 @@ _Static_assert(sizeof(rb_progressive) == 16, "ProgressiveRenderHelper is 16 B");
 _Static_assert(sizeof(rb_ray) == 32, "rb_ray is 32 B");
 _Static_assert(sizeof(rb_hit) == 48, "rb_hit is 48 B");
 _Static_assert(sizeof(rb_surface) == 48, "rb_surface is 48 B");
+_Static_assert(sizeof(rb_guide) == 48, "rb_guide is 48 B");
+_Static_assert(sizeof(rb_denoise_params) == 32, "rb_denoise_params is 32 B");
 #endif
 
 #endif /* RB_ABI_H */

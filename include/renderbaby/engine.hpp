@@ -210,6 +210,32 @@ class Engine final : public Renderer {
         check(h_->e, rb_cast_rays_device(h_->e, d_rays, n, d_hits, d_surf));
     }
     void sync() { check(h_->e, rb_sync(h_->e)); }
+    // ---- the denoiser (rb_abi.h): the a-trous filter over the committed accumulation
+    static rb_denoise_params denoise_defaults() {
+        rb_denoise_params p{};
+        (void)rb_denoise_default_params(&p);
+        return p;
+    }
+    // the RGBA8 frame (w * h * 4 bytes) and, if linear_out is not null, the linear vec4 output (w * h * 4 floats)
+    std::vector<uint8_t> denoise(const rb_denoise_params& p = denoise_defaults(), std::vector<float>* linear_out = nullptr) {
+        uint32_t w = 0, h = 0;
+        check(h_->e, rb_get_size(h_->e, &w, &h));
+        std::vector<uint8_t> rgba(static_cast<size_t>(w) * h * 4);
+        if (linear_out) linear_out->resize(static_cast<size_t>(w) * h * 4);
+        check(h_->e, rb_denoise(h_->e, &p, rgba.data(), linear_out ? linear_out->data() : nullptr));
+        return rgba;
+    }
+    // outputs in the engine's device memory (either may be null, not both): queued, not waited for -- sync() waits
+    void denoise_device(const rb_denoise_params& p, uint8_t* d_rgba_out, float* d_linear_out = nullptr) {
+        check(h_->e, rb_denoise_device(h_->e, &p, d_rgba_out, d_linear_out));
+    }
+    std::vector<rb_guide> denoise_guides() {
+        uint32_t w = 0, h = 0;
+        check(h_->e, rb_get_size(h_->e, &w, &h));
+        std::vector<rb_guide> g(static_cast<size_t>(w) * h);
+        check(h_->e, rb_denoise_guides(h_->e, g.data()));
+        return g;
+    }
     // the displayed pixel (px from the left, py from the top): "sphere 3" / "mesh 2, triangle 517" for a click
     rb_hit pick(uint32_t px, uint32_t py, rb_surface* surface = nullptr) {
         rb_hit hit{};

@@ -41,6 +41,13 @@ pub const RB_OCCL_VISIBLE: u8 = 0; pub const RB_OCCL_OCCLUDED: u8 = 1; pub const
 pub const RB_MASK_GROUND: u32 = 1; pub const RB_MASK_TRIANGLES: u32 = 2; pub const RB_MASK_SPHERES: u32 = 4;
 pub const RB_MASK_LIGHTS: u32 = 8; pub const RB_MASK_ALL: u32 = 15;
 
+/// rb_guide (48 B): what the denoiser knows of a pixel's first hit; cls 0 = pass-through
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct RbGuide { pub normal: [f32; 3], pub t: f32, pub pos: [f32; 3], pub cls: u32, pub albedo: [f32; 3], pub _pad: f32 }
+/// rb_denoise_params (32 B); fill with rb_denoise_default_params
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct RbDenoiseParams { pub iterations: u32, pub normal_power_log2: u32, pub sigma_depth: f32, pub sigma_color: f32, pub albedo_floor: f32, pub flags: u32, pub _reserved: [u32; 2] }
+
 unsafe extern "C" {
     pub fn rb_create(cfg: *const RbConfig) -> *mut RbEngine;
     pub fn rb_create_ex(cfg: *const RbConfig, opt: *const RbOptions) -> *mut RbEngine;
@@ -75,6 +82,14 @@ unsafe extern "C" {
     /// queued on the engine's stream, no copy, no wait (rb_sync waits)
     pub fn rb_occluded_device(e: *mut RbEngine, d_rays: *const RbRay, d_tmax: *const f32, n: usize, mask: u32, d_out: *mut u8) -> c_int;
     pub fn rb_cast_rays_device(e: *mut RbEngine, d_rays: *const RbRay, n: usize, d_hits: *mut c_void, d_surf: *mut c_void) -> c_int;
+    /// the edge-avoiding a-trous denoiser over the committed accumulation: RGBA8 and / or linear vec4 out
+    pub fn rb_denoise_default_params(p: *mut RbDenoiseParams) -> c_int;
+    pub fn rb_denoise(e: *mut RbEngine, params: *const RbDenoiseParams, rgba_out: *mut u8, linear_out: *mut f32) -> c_int;
+    /// the same into the engine's device memory: queued on the engine's stream, no wait (rb_sync waits)
+    pub fn rb_denoise_device(e: *mut RbEngine, params: *const RbDenoiseParams, d_rgba_out: *mut u8, d_linear_out: *mut f32) -> c_int;
+    pub fn rb_denoise_guides(e: *mut RbEngine, guides_out: *mut RbGuide) -> c_int;
+    /// the filter on its own: host arrays in and out, the work on `device`, no engine
+    pub fn rb_denoise_buffers(device: i32, params: *const RbDenoiseParams, w: u32, h: u32, color4: *const f32, guides: *const RbGuide, out4: *mut f32, rgba_out: *mut u8) -> c_int;
     pub fn rb_sync(e: *mut RbEngine) -> c_int;
     pub fn rb_last_error(e: *const RbEngine) -> *const c_char;
 }

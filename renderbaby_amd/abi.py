@@ -52,11 +52,16 @@ NO_INDEX = 0xFFFFFFFF
 # any-hit occlusion (rb_occluded): result bytes and stage masks
 OCCL_VISIBLE, OCCL_OCCLUDED, OCCL_INVALID = 0, 1, 255
 MASK_GROUND, MASK_TRIANGLES, MASK_SPHERES, MASK_LIGHTS, MASK_ALL = 1, 2, 4, 8, 15
+# the denoiser (rb_denoise*): the guide record of a pixel and the filter's parameters
+GUIDE = np.dtype([("normal", f4, (3,)), ("t", f4), ("pos", f4, (3,)), ("cls", u4), ("albedo", f4, (3,)), ("_pad", f4)])
+DENOISE_PARAMS = np.dtype([("iterations", u4), ("normal_power_log2", u4), ("sigma_depth", f4), ("sigma_color", f4),
+                           ("albedo_floor", f4), ("flags", u4), ("_reserved", u4, (2,))])
 
 SIZES = {"camera": (CAMERA, 48), "uniforms": (UNIFORMS, 144), "material": (MATERIAL, 80),
          "sphere": (SPHERE, 96), "point_light": (POINT_LIGHT, 96), "mesh": (MESH, 96),
          "bvh_node": (BVH_NODE, 48), "gpu_triangle": (GPU_TRIANGLE, 64),
-         "ray": (RAY, 32), "hit": (HIT, 48), "surface": (SURFACE, 48)}
+         "ray": (RAY, 32), "hit": (HIT, 48), "surface": (SURFACE, 48),
+         "guide": (GUIDE, 48), "denoise_params": (DENOISE_PARAMS, 32)}
 for _n, (_dt, _sz) in SIZES.items():
     assert _dt.itemsize == _sz, (_n, _dt.itemsize, _sz)
 

@@ -176,6 +176,17 @@ struct rb_engine {
     float last_query_ms = 0.0f;
     bool query_ms_pending = false;   // the device forms return without waiting: rb_last_query_ms reads ev_q when asked
 
+    // the denoiser (rb_denoise*): the guide planes of the scene and camera of the last accepted update (made
+    // by the first denoise after it), the two colour buffers the iterations ping-pong between, staging for host outputs, and
+    // events of its own: like a query it moves neither the work counters nor the timing of a launch group
+    rb::DevBuf<float> dn_nt, dn_pc, dn_al;
+    bool dn_guides_valid = false;
+    rb::DevBuf<float> dn_r[2], dn_linear;
+    rb::DevBuf<uint32_t> dn_rgba;
+    hipEvent_t ev_dn[4] = {nullptr, nullptr, nullptr, nullptr};   // guide build begin / end, filter begin / end
+    float last_denoise_ms = 0.0f, last_guide_ms = 0.0f;
+    bool denoise_ms_pending = false;   // rb_denoise_device returns without waiting: rb_last_denoise_ms reads the events when asked
+
     rb_stats stats{};
     float last_dispatch_ms = 0.0f;
     uint32_t last_launches = 0;

@@ -396,6 +396,33 @@ struct OcclArgs {
 int launch_occluded(const KParams& p, const OcclArgs& a, void* stream, LaunchInfo* info);
 Cam host_cam(const rb_uniforms& u);   // rb_kernels.hip: the camera of a launch, shader.wgsl:690,702-708
 
+// ---- rb_denoise.hip: the edge-avoiding a-trous filter.  Everything is in the orientation of the delivered
+// frame.  What a tap reads lies in three planes of 16-byte quads -- colour | class, normal | t, position | class of the guide --
+// and the albedo, read by the prepare and finish steps only, in a fourth.
+struct GuidePlanes {
+    float* nt;    // float4 per pixel: normal, t
+    float* pc;    // float4: pos, cls (as bits; the guide's class, before the prepare step's non-finite rule)
+    float* al;    // float4: albedo, 0
+};
+enum : uint32_t { kDenoisePlain = 1, kDenoiseLds = 2 };   // the iteration kernel of steps 1 and 2: taps through L1 / L2, or a tile with its halo staged in LDS
+struct DenoiseArgs {
+    uint32_t w, h;
+    const float* accum;     // the f32 accumulation (vec4 per pixel, shader x order: mirrored here), or nullptr ...
+    const float* color4;    // ... then the mean radiance itself, vec4 per pixel
+    GuidePlanes g;
+    float* r[2];            // the two colour | class buffers the iterations ping-pong between, w * h float4 each
+    float* linear_out;      // either may be nullptr
+    uint32_t* rgba_out;
+    uint32_t variant;       // 0 = the default (kDenoiseDefaultVariant), or RB_DENOISE_VARIANT in the environment (measurements)
+};
+bool denoise_params_valid(const rb_denoise_params& p, const char** why);
+// prepare, the iterations, finish: asynchronous on `stream`; returns a hipError_t
+int launch_denoise(const rb_denoise_params& prm, const DenoiseArgs& a, void* stream);
+// first-hit records of the w x h pixel centres (displayed orientation) -> the guide planes; u: the scene's uniforms (the camera)
+int launch_guide_pack(const rb_uniforms& u, const rb_hit* hits, const rb_surface* surf, uint32_t w, uint32_t h, const GuidePlanes& g, void* stream);
+int launch_guide_split(const rb_guide* guides, size_t n, const GuidePlanes& g, void* stream);   // ABI records -> planes
+int launch_guide_join(const GuidePlanes& g, size_t n, rb_guide* guides, void* stream);          // and back
+
 // ---- rb_kernels.hip
 // All return hipError_t as int (0 = success); launches are asynchronous on `stream`.
 int launch_render(const KParams& p, uint32_t kernel, bool stats, void* stream, LaunchInfo* info,

@@ -17,6 +17,7 @@
 // copy, into page-locked caller memory a DMA with no host pass.  (Three planes of quads would coalesce as well but leave the
 // interleaving to the host.)
 #include "rb_device_chunk.hpp"
+#include "rb_device_centre.hpp"
 
 #pragma clang fp contract(off)
 
@@ -39,23 +40,6 @@ struct QueryLane {
     bool live;    // there is a ray (ray source: index < n; pixel source: inside the window)
     bool valid;   // ... and it is finite after normalisation, and for a pixel inside the image
 };
-
-// shader.wgsl:693-709 for the pixel CENTRE: start_path_hashed's arithmetic with both offsets 0.0f
-DEV f3 centre_ray_dir(const KParams& p, uint32_t x, uint32_t y) {
-    const Cam& c = p.cam;
-    const float ax = (float)x + 0.0f, ay = (float)y + 0.0f;
-    float qx, qy;
-    if (c.fast_wh) {
-        qx = __builtin_copysignf(div_newton(ax, c.wm1, c.inv_wm1), ax);
-        qy = __builtin_copysignf(div_newton(ay, c.hm1, c.inv_hm1), ay);
-    } else {
-        qx = ax / c.wm1;
-        qy = ay / c.hm1;
-    }
-    const float u = ((qx * 2.0f) - 1.0f) * c.aspect;
-    const float v = 1.0f - qy * 2.0f;
-    return normalize(((c.fov * u) * ld3(c.right) + (c.fov * v) * ld3(c.up)) + ld3(c.fwd));
-}
 
 DEV bool finite3(f3 a) {
     const uint32_t m = 0x7F800000u;
@@ -90,7 +74,7 @@ DEV QueryLane query_lane(const KParams& p, const QueryArgs q, uint32_t wave, uin
     r.valid = r.live && xd < p.u.width && y < p.u.height;
     if (r.valid) {
         r.o = ld3(p.cam.pos);
-        r.d = centre_ray_dir(p, p.u.width - 1u - xd, y);
+        r.d = centre_ray_dir(p.cam, p.u.width - 1u - xd, y);
         r.valid = finite3(r.o) && usable_dir(r.d);
     }
     return r;

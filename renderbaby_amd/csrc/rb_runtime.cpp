@@ -605,6 +605,7 @@ int update_fields(rb_engine* e, const rb_config* cfg) {
     e->scene_valid = false;
     e->spec_valid = false;
     e->color_budget = 0;
+    e->dn_guides_valid = false;   // the denoiser's guides are this scene's and this camera's
     // uniforms (gpu_wrapper.rs:122-136 / :165-192)
     const bool take_uniforms = first ? (cfg->uniforms.change == RB_CREATE) : (cfg->uniforms.change == RB_UPDATE);
     if (take_uniforms) {
@@ -1099,6 +1100,139 @@ int cast_rays_device_locked(rb_engine* e, const rb_ray* d_rays, size_t n, rb_hit
     });
 }
 
+// ---- the denoiser (rb_abi.h).  Like a query it is queued on the engine's stream behind whatever runs
+// there, reads the scene and the committed accumulation, and writes buffers of its own.
+rb::GuidePlanes guide_planes(rb_engine* e) { return rb::GuidePlanes{e->dn_nt.ptr, e->dn_pc.ptr, e->dn_al.ptr}; }
+
+int denoise_ready(rb_engine* e) {
+    if (rb::is_group(e)) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "the denoiser does not take a multi-device handle: a tap would cross a stripe boundary");
+    rb::set_device(e);
+    if (e->opt.shard_count > 1) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "the denoiser does not take a sharded engine: a tap would cross a stripe boundary");
+    const int rc = require_ready(e);
+    if (rc) return rc;
+    for (hipEvent_t& x : e->ev_dn)
+        if (!x) HIP_TRY(e, hipEventCreate(&x));
+    return RB_OK;
+}
+
+// the guide planes of the current scene: the pixel-centre rays through the query kernels straight into device memory, one pack
+int ensure_guides(rb_engine* e) {
+    e->last_guide_ms = 0.0f;
+    if (e->dn_guides_valid) return RB_OK;
+    int rc = ensure_prepared(e);
+    if (rc) return rc;
+    rb::KParams p = make_params(e, 0, 0, e->cur, e->cur);
+    if (!e->stack_depth_covers) return rb::fail(e, RB_ERR_DEVICE, "internal: a traversal is deeper than its LDS stack column (%u entries)", p.stack_depth);
+    const uint32_t w = e->width, h = e->height;
+    const size_t n = static_cast<size_t>(w) * h;
+    rb::DevBuf<rb_hit> hits;       // the records live until the pack has read them
+    rb::DevBuf<rb_surface> surf;
+    HIP_TRY(e, hits.resize(n));
+    HIP_TRY(e, surf.resize(n));
+    HIP_TRY(e, e->dn_nt.resize(n * 4));
+    HIP_TRY(e, e->dn_pc.resize(n * 4));
+    HIP_TRY(e, e->dn_al.resize(n * 4));
+    if (n) {
+        HIP_TRY(e, hipEventRecord(e->ev_dn[0], e->stream));
+        const uint32_t piece_rows = std::max<uint32_t>(8u, (rb::kQueryPiece / w) & ~7u);   // whole 8-row tiles, as rb_render_hits
+        for (uint32_t r0 = 0; r0 < h; r0 += piece_rows) {
+            rb::QueryArgs q{};
+            q.win_y = r0;
+            q.win_w = w;
+            q.win_h = std::min(piece_rows, h - r0);
+            q.win_global = 1u;
+            q.hits = hits.ptr + static_cast<size_t>(r0) * w;
+            q.surf = surf.ptr + static_cast<size_t>(r0) * w;
+            const int st = rb::launch_query(p, q, e->stream, nullptr);
+            if (st) return rb::fail(e, RB_ERR_DEVICE, "query kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
+        }
+        const int st = rb::launch_guide_pack(p.u, hits.ptr, surf.ptr, w, h, guide_planes(e), e->stream);
+        if (st) return rb::fail(e, RB_ERR_DEVICE, "guide pack launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
+        HIP_TRY(e, hipEventRecord(e->ev_dn[1], e->stream));
+        HIP_TRY(e, hipStreamSynchronize(e->stream));
+        HIP_TRY(e, hipEventElapsedTime(&e->last_guide_ms, e->ev_dn[0], e->ev_dn[1]));
+    }
+    e->dn_guides_valid = true;
+    return RB_OK;
+}
+
+int denoise_params_check(const rb_engine* e, const rb_denoise_params* prm) {
+    const char* why = nullptr;
+    if (!rb::denoise_params_valid(*prm, &why)) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "rb_denoise_params: %s", why);
+    return RB_OK;
+}
+
+// device == true: the outputs are the caller's device buffers and nothing is waited for
+int denoise_locked(rb_engine* e, const rb_denoise_params* prm, uint8_t* rgba_out, float* linear_out, bool device) {
+    int rc = denoise_ready(e);
+    if (!rc) rc = denoise_params_check(e, prm);
+    if (rc) return rc;
+    if (!rgba_out && !linear_out) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "rgba_out and linear_out are both NULL");
+    const size_t n = static_cast<size_t>(e->width) * e->height;
+    if (device) {
+        if (rgba_out) rc = device_range(e, rgba_out, n * 4, 4, "d_rgba_out");
+        if (!rc && linear_out) rc = device_range(e, linear_out, n * 16, 16, "d_linear_out");
+        if (rc) return rc;
+    }
+    rc = ensure_guides(e);
+    if (rc) return rc;
+    e->denoise_ms_pending = false;
+    e->last_denoise_ms = 0.0f;
+    if (n == 0) return RB_OK;
+    rb::DenoiseArgs a{};
+    a.w = e->width;
+    a.h = e->height;
+    a.accum = e->slot[e->cur].accum.ptr;
+    a.g = guide_planes(e);
+    for (int k = 0; k < 2; ++k) {
+        HIP_TRY(e, e->dn_r[k].resize(n * 4));
+        a.r[k] = e->dn_r[k].ptr;
+    }
+    if (device) {
+        a.rgba_out = reinterpret_cast<uint32_t*>(rgba_out);
+        a.linear_out = linear_out;
+    } else {
+        if (rgba_out) {
+            HIP_TRY(e, e->dn_rgba.resize(n));
+            a.rgba_out = e->dn_rgba.ptr;
+        }
+        if (linear_out) {
+            HIP_TRY(e, e->dn_linear.resize(n * 4));
+            a.linear_out = e->dn_linear.ptr;
+        }
+    }
+    HIP_TRY(e, hipEventRecord(e->ev_dn[2], e->stream));
+    const int st = rb::launch_denoise(*prm, a, e->stream);
+    if (st) return rb::fail(e, RB_ERR_DEVICE, "denoise kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
+    HIP_TRY(e, hipEventRecord(e->ev_dn[3], e->stream));
+    if (device) {
+        e->denoise_ms_pending = true;
+        return RB_OK;
+    }
+    if (rgba_out) rc = query_copy_out(e, rgba_out, e->dn_rgba.ptr, n * 4, page_locked(rgba_out));
+    if (!rc && linear_out) rc = query_copy_out(e, linear_out, e->dn_linear.ptr, n * 16, page_locked(linear_out));
+    if (rc) return rc;
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    HIP_TRY(e, hipEventElapsedTime(&e->last_denoise_ms, e->ev_dn[2], e->ev_dn[3]));
+    return RB_OK;
+}
+
+int denoise_guides_locked(rb_engine* e, rb_guide* guides_out) {
+    int rc = denoise_ready(e);
+    if (!rc) rc = ensure_guides(e);
+    if (rc) return rc;
+    const size_t n = static_cast<size_t>(e->width) * e->height;
+    if (n == 0) return RB_OK;
+    rb::DevBuf<rb_guide> joined;
+    HIP_TRY(e, joined.resize(n));
+    const int st = rb::launch_guide_join(guide_planes(e), n, joined.ptr, e->stream);
+    if (st) return rb::fail(e, RB_ERR_DEVICE, "guide join launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
+    rc = query_copy_out(e, guides_out, joined.ptr, n * sizeof(rb_guide), page_locked(guides_out));
+    if (rc) return rc;
+    HIP_TRY(e, hipStreamSynchronize(e->stream));   // `joined` is freed on return
+    return RB_OK;
+}
+
 // the engine that answers a query (a multi-device handle: devices[0], which holds the whole scene), made current
 rb_engine* answering(rb_engine* e) {
     rb_engine* const t = rb::is_group(e) ? e->parts[0].get() : e;
@@ -1226,6 +1360,8 @@ void rb_destroy(rb_engine* e) {
         if (s.done) (void)hipEventDestroy(s.done);
     for (hipEvent_t x : e->ev_pool) (void)hipEventDestroy(x);
     for (hipEvent_t x : e->ev_q)
+        if (x) (void)hipEventDestroy(x);
+    for (hipEvent_t x : e->ev_dn)
         if (x) (void)hipEventDestroy(x);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
@@ -1682,6 +1818,91 @@ int rb_cast_rays_device(rb_engine* e, const rb_ray* d_rays, size_t n, rb_hit* d_
     rb_engine* const t = answering(e);
     if (n == 0) return answered(e, t, require_ready(t));
     return answered(e, t, cast_rays_device_locked(t, d_rays, n, d_hits, d_surf));
+}
+
+int rb_denoise_default_params(rb_denoise_params* p) {
+    if (!p) return RB_ERR_NULL_ARGUMENT;
+    *p = rb_denoise_params{};
+    p->iterations = 3;   // chosen on the quality test: DESIGN.md section 13.4
+    p->normal_power_log2 = 3;
+    p->sigma_depth = 0.02f;
+    p->sigma_color = 0.0f;   // the colour term is off: at a few samples per pixel it takes fireflies for edges
+    p->albedo_floor = 0.01f;
+    return RB_OK;
+}
+
+int rb_denoise(rb_engine* e, const rb_denoise_params* params, uint8_t* rgba_out, float* linear_out) {
+    if (!e || !params) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    return denoise_locked(e, params, rgba_out, linear_out, false);
+}
+
+int rb_denoise_device(rb_engine* e, const rb_denoise_params* params, uint8_t* d_rgba_out, float* d_linear_out) {
+    if (!e || !params) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    return denoise_locked(e, params, d_rgba_out, d_linear_out, true);
+}
+
+int rb_denoise_guides(rb_engine* e, rb_guide* guides_out) {
+    if (!e) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (!guides_out) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "guides_out is NULL");
+    return denoise_guides_locked(e, guides_out);
+}
+
+int rb_last_denoise_ms(rb_engine* e, float* ms, float* guide_build_ms) {
+    if (!e || !ms) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (e->denoise_ms_pending) {   // rb_denoise_device returned without waiting: its events are read here
+        rb::set_device(e);
+        HIP_TRY(e, hipEventSynchronize(e->ev_dn[3]));
+        HIP_TRY(e, hipEventElapsedTime(&e->last_denoise_ms, e->ev_dn[2], e->ev_dn[3]));
+        e->denoise_ms_pending = false;
+    }
+    *ms = e->last_denoise_ms;
+    if (guide_build_ms) *guide_build_ms = e->last_guide_ms;
+    return RB_OK;
+}
+
+int rb_denoise_buffers(int32_t device, const rb_denoise_params* params, uint32_t w, uint32_t h, const float* color4,
+                       const rb_guide* guides, float* out4, uint8_t* rgba_out) {
+    if (!params || !color4 || !guides) return rb::fail(nullptr, RB_ERR_NULL_ARGUMENT, "params / color4 / guides is NULL");
+    if (!out4 && !rgba_out) return rb::fail(nullptr, RB_ERR_NULL_ARGUMENT, "out4 and rgba_out are both NULL");
+    if (const int rc = denoise_params_check(nullptr, params)) return rc;
+    const size_t n = static_cast<size_t>(w) * h;
+    if (n >= (1ull << 31)) return rb::fail(nullptr, RB_ERR_INVALID_OPTIONS, "a frame of %u x %u pixels is too large", w, h);
+    if (n == 0) return RB_OK;
+    if (device >= 0 && hipSetDevice(device) != hipSuccess) return rb::fail(nullptr, RB_ERR_DEVICE, "hipSetDevice(%d) failed", device);
+    rb::DevBuf<float> d_color, d_nt, d_pc, d_al, d_r0, d_r1, d_linear;
+    rb::DevBuf<rb_guide> d_guides;
+    rb::DevBuf<uint32_t> d_rgba;
+    hipStream_t stream = nullptr;
+    hipError_t st = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
+    for (rb::DevBuf<float>* b : {&d_color, &d_nt, &d_pc, &d_al, &d_r0, &d_r1})
+        if (st == hipSuccess) st = b->resize(n * 4);
+    if (st == hipSuccess) st = d_guides.resize(n);
+    if (st == hipSuccess && out4) st = d_linear.resize(n * 4);
+    if (st == hipSuccess && rgba_out) st = d_rgba.resize(n);
+    if (st == hipSuccess) st = hipMemcpyAsync(d_color.ptr, color4, n * 16, hipMemcpyHostToDevice, stream);
+    if (st == hipSuccess) st = hipMemcpyAsync(d_guides.ptr, guides, n * sizeof(rb_guide), hipMemcpyHostToDevice, stream);
+    rb::DenoiseArgs a{};
+    a.w = w;
+    a.h = h;
+    a.color4 = d_color.ptr;
+    a.g = rb::GuidePlanes{d_nt.ptr, d_pc.ptr, d_al.ptr};
+    a.r[0] = d_r0.ptr;
+    a.r[1] = d_r1.ptr;
+    a.linear_out = d_linear.ptr;
+    a.rgba_out = d_rgba.ptr;
+    if (st == hipSuccess) st = static_cast<hipError_t>(rb::launch_guide_split(d_guides.ptr, n, a.g, stream));
+    if (st == hipSuccess) st = static_cast<hipError_t>(rb::launch_denoise(*params, a, stream));
+    if (st == hipSuccess && out4) st = hipMemcpyAsync(out4, d_linear.ptr, n * 16, hipMemcpyDeviceToHost, stream);
+    if (st == hipSuccess && rgba_out) st = hipMemcpyAsync(rgba_out, d_rgba.ptr, n * 4, hipMemcpyDeviceToHost, stream);
+    if (st == hipSuccess) st = hipStreamSynchronize(stream);
+    if (stream) (void)hipStreamSynchronize(stream);   // (the buffers are freed on return, after this)
+    if (stream) (void)hipStreamDestroy(stream);
+    if (st != hipSuccess) return rb::fail(nullptr, RB_ERR_DEVICE, "rb_denoise_buffers failed: %s", hipGetErrorString(st));
+    return RB_OK;
 }
 
 const char* rb_last_query_kernel_name(const rb_engine* e) {

@@ -518,6 +518,44 @@ class Engine:
         self._check(self._lib.rb_last_query_ms(self._h, C.byref(ms)))
         return ms.value
 
+    # ---- the denoiser (rb_abi.h)
+    def denoise(self, params=None, linear=False, out=None):
+        """rb_denoise: the edge-avoiding a-trous filter over the committed accumulation, guided by the first hits of the pixel
+        centres.  ``params``: an abi.DENOISE_PARAMS scalar (``denoise.params(...)``), by default the library's.  Returns the
+        RGBA8 frame, uint8 (h, w, 4) -- with ``linear`` the linear output, float32 (h, w, 4), w = 1.  ``out``: an array of that
+        shape to fill instead (a page-locked one is filled by DMA), or a torch tensor on the engine's device (uint8 or float32,
+        (h, w, 4), contiguous): rb_denoise_device writes it there and nothing crosses to the host."""
+        p = np.ascontiguousarray(denoise_defaults() if params is None else params, dtype=abi.DENOISE_PARAMS).reshape(1)
+        w, h = self.size()
+        if _is_tensor(out):
+            import torch
+            dtype = torch.float32 if linear else torch.uint8
+            if out.device != torch.device("cuda", self.query_device) or out.dtype != dtype or not out.is_contiguous() \
+                    or tuple(out.shape) != (h, w, 4):
+                raise ValueError(f"out: a contiguous {dtype} tensor of shape ({h}, {w}, 4) on cuda:{self.query_device} is needed")
+            ptr = out.data_ptr() if out.numel() else None
+            self._device_call(self._lib.rb_denoise_device, p.ctypes.data, None if linear else ptr, ptr if linear else None)
+            return out
+        dtype = np.float32 if linear else np.uint8
+        res = np.empty((h, w, 4), dtype=dtype) if out is None else out
+        if res.dtype != dtype or res.shape != (h, w, 4) or not res.flags.c_contiguous:
+            raise ValueError(f"out: a contiguous {np.dtype(dtype)} array of shape ({h}, {w}, 4) is needed")
+        self._check(self._lib.rb_denoise(self._h, p.ctypes.data, None if linear else res.ctypes.data, res.ctypes.data if linear else None))
+        return res
+
+    def denoise_guides(self):
+        """rb_denoise_guides: the guide buffer the engine filters with, abi.GUIDE[h, w] in the orientation of the frame."""
+        w, h = self.size()
+        g = np.empty((h, w), dtype=abi.GUIDE)
+        self._check(self._lib.rb_denoise_guides(self._h, g.ctypes.data))
+        return g
+
+    def last_denoise_ms(self):
+        """(kernel ms of the most recent denoise, ms of the guide build it had to make -- 0 when it had the guides)"""
+        ms, gms = C.c_float(), C.c_float()
+        self._check(self._lib.rb_last_denoise_ms(self._h, C.byref(ms), C.byref(gms)))
+        return ms.value, gms.value
+
     def fast_bvh_builder(self):
         """("host-sah" | "device-lbvh" | "", build milliseconds) of the tree RB_FLAG_FAST_BVH walks."""
         ms = C.c_float()
@@ -620,3 +658,31 @@ def device_name(device=-1):
     buf = C.create_string_buffer(256)
     rc = load().rb_device_name(device, buf, 256)
     return buf.value.decode() if rc == 0 else "unknown"
+
+
+def denoise_defaults():
+    """rb_denoise_default_params as an abi.DENOISE_PARAMS scalar."""
+    p = np.zeros(1, dtype=abi.DENOISE_PARAMS)
+    rc = load().rb_denoise_default_params(p.ctypes.data)
+    if rc != abi.RB_OK:
+        raise RenderError(rc, "rb_denoise_default_params")
+    return p[0]
+
+
+def denoise_buffers(color, guides, params=None, device=-1):
+    """rb_denoise_buffers: the filter on its own -- (h, w, 3 or 4) float32 mean radiance and abi.GUIDE[h, w] in, the linear
+    output (h, w, 4) float32 and the RGBA8 frame (h, w, 4) uint8 out; host arrays, the work on the GPU, no engine."""
+    g = np.ascontiguousarray(guides, dtype=abi.GUIDE)
+    c = np.asarray(color, dtype=np.float32)
+    if c.ndim != 3 or c.shape[:2] != g.shape or c.shape[2] not in (3, 4):
+        raise ValueError(f"colour {c.shape} and guides {g.shape} differ")
+    h, w = g.shape
+    c4 = np.zeros((h, w, 4), dtype=np.float32)
+    c4[..., :c.shape[2]] = c
+    p = np.ascontiguousarray(denoise_defaults() if params is None else params, dtype=abi.DENOISE_PARAMS).reshape(1)
+    lin, img = np.empty((h, w, 4), dtype=np.float32), np.empty((h, w, 4), dtype=np.uint8)
+    lib = load()
+    rc = lib.rb_denoise_buffers(int(device), p.ctypes.data, w, h, c4.ctypes.data, g.ctypes.data, lin.ctypes.data, img.ctypes.data)
+    if rc != abi.RB_OK:
+        raise RenderError(rc, (lib.rb_last_error(None) or b"").decode())
+    return lin, img

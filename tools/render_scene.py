@@ -3,16 +3,19 @@
     python tools/render_scene.py scene.rscn out.png [--spp N] [--max-depth D] [--fast-bvh] [--device-bvh]
                                  [--width W --height H] [--included-root DIR] [--every N]
                                  [--aov depth,normal,albedo,emission,id,ao] [--ao-radius R]
+                                 [--denoise [--denoise-iterations N]]
 
 scene file -> scene_io.load_scene (the importer's and the Scene->RenderConfig adapter's rules) ->
 RenderConfig -> librenderbaby_hip.so -> Frame -> PNG.  With --every N the progressive iterator is used
 and a frame is written every N samples (out_0001.png, ...).  --aov writes the first-hit buffers of the pixel centres
 (Engine.render_hits -> renderbaby_amd.aov) next to the frame as out.<name>.png; `ao` is ambient occlusion over those hits
-(aov.ambient_occlusion: 16 directions per hit, one any-hit query).
+(aov.ambient_occlusion: 16 directions per hit, one any-hit query).  --denoise writes the frame through the edge-avoiding
+a-trous filter (Engine.denoise) as out.denoised.png -- with --every, every delivered frame next to the raw
+one (out_0001.denoised.png, ...).
 """
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from renderbaby_amd import Engine, Frame, RenderConfig, aov, scene_io  # noqa: E402
+from renderbaby_amd import Engine, Frame, RenderConfig, aov, denoise, scene_io  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("scene"); ap.add_argument("png")
@@ -23,6 +26,8 @@ ap.add_argument("--build-tree", action="store_true", help="send triangles only: 
 ap.add_argument("--included-root", default=None); ap.add_argument("--every", type=int, default=0)
 ap.add_argument("--aov", default="", help="comma-separated first-hit buffers to write as out.<name>.png: " + ", ".join(aov.NAMES) + ", ao")
 ap.add_argument("--ao-radius", type=float, default=1.0, help="how far an occluder may be for --aov ao")
+ap.add_argument("--denoise", action="store_true", help="also write every frame filtered, as <name>.denoised.png")
+ap.add_argument("--denoise-iterations", type=int, default=None, help="a-trous iterations, 0..8 (default: the library's)")
 a = ap.parse_args()
 aovs = [n for n in a.aov.split(",") if n]
 for n in aovs:
@@ -37,18 +42,36 @@ print(f"loaded {a.scene}: {len(s.bvh_triangles)} triangles, {len(s.spheres)} sph
       f"{len(s.textures)} textures, {s.width}x{s.height}, {s.total_samples} spp ({time.time() - t0:.2f} s)")
 rc = RenderConfig.from_scene(s, with_tree=not a.build_tree)
 eng = Engine.new(rc, fast_bvh=a.fast_bvh, device_bvh=a.device_bvh, build_tree="device" if a.build_tree else None)
+dn_params = denoise.params(**({} if a.denoise_iterations is None else dict(iterations=a.denoise_iterations)))
+dn_ms = []
+
+
+def export_denoised(path):
+    """the committed frame through the filter, next to `path`"""
+    img = eng.denoise(dn_params)
+    dn_ms.append(eng.last_denoise_ms()[0])
+    b, x = os.path.splitext(path)
+    scene_io.export_png(f"{b}.denoised{x}", Frame(img.shape[1], img.shape[0], img))
+
+
 t0 = time.time()
 if a.every > 0:
     base, ext = os.path.splitext(a.png)
     for i, frame in enumerate(eng.frame_iterator(rc, passes_per_frame=a.every)):
         scene_io.export_png(f"{base}_{i + 1:04d}{ext}", frame)
+        if a.denoise:
+            export_denoised(f"{base}_{i + 1:04d}{ext}")
     scene_io.export_png(a.png, frame)
 else:
     frame = eng.render(rc)
     scene_io.export_png(a.png, frame)
+if a.denoise:
+    export_denoised(a.png)
 dt = time.time() - t0
 st = eng.stats()
 print(f"rendered with {eng.last_kernel_name()} in {dt:.3f} s: {st['segments'] / dt / 1e6:.0f} M ray-segments/s -> {a.png}")
+if a.denoise:
+    print(f"denoised {len(dn_ms)} frame(s), {int(dn_params['iterations'])} iterations: {sum(dn_ms) / len(dn_ms):.3f} ms of kernels per frame")
 if aovs:
     hits, surf = eng.render_hits(surfaces=True)
     base, ext = os.path.splitext(a.png)
