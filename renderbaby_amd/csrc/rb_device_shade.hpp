@@ -590,6 +590,30 @@ DEV void start_path_hashed(const KParams& p, uint32_t x, uint32_t y, uint32_t pi
     pt.depth = 0;
 }
 
+// The part of start_path_hashed that depends on the item -- the primary ray's direction and the seed after its two draws --
+// on its own: k_trace works it out a whole 64-item row at a time (ColorRing::stage_row).  Operation for operation the lines
+// above; start_path_hashed keeps its own copy because calling this one from it moves the register allocation of the stepped
+// kernels (k_trace_sph, k_trace_chunk: two spilled scalar registers each).
+DEV void start_ray_hashed(const KParams& p, uint32_t x, uint32_t y, uint32_t pixel_index, uint32_t sample_hash, f3& d, uint32_t& seed_out) {
+    const Cam& c = p.cam;
+    uint32_t seed = pcg(pixel_index + sample_hash);
+    const float off_x = rnd(seed) - 0.5f;
+    const float off_y = rnd(seed) - 0.5f;
+    const float ax = (float)x + off_x, ay = (float)y + off_y;
+    float qx, qy;
+    if (c.fast_wh) {
+        qx = __builtin_copysignf(div_newton(ax, c.wm1, c.inv_wm1), ax);
+        qy = __builtin_copysignf(div_newton(ay, c.hm1, c.inv_hm1), ay);
+    } else {
+        qx = ax / c.wm1;
+        qy = ay / c.hm1;
+    }
+    const float u = ((qx * 2.0f) - 1.0f) * c.aspect;
+    const float v = 1.0f - qy * 2.0f;
+    d = normalize(((c.fov * u) * ld3(c.right) + (c.fov * v) * ld3(c.up)) + ld3(c.fwd));
+    seed_out = seed;
+}
+
 DEV void start_path(const KParams& p, uint32_t x, uint32_t y, uint32_t pixel_index, uint32_t sample_offset, Path& pt) {
     start_path_hashed(p, x, y, pixel_index, pcg(sample_offset), pt);
 }

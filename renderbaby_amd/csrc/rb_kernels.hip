@@ -218,7 +218,25 @@ DEV void store_color(float4* __restrict__ colors, uint32_t item, f3 c) {
 // slice is marked (kDirect in its item word) and stores on its own when it finishes, as every lane used to.
 // Nothing is ever parked in an occupied entry: the slice was emptied before its row's first item went out, and
 // the stragglers of the previous row were marked in the same step.
+//
+// Staged row starts (k_trace<..., STAGED = true>: every launch whose reservations are whole multiples of kRingRows rows).
+// Between the moment a slice is emptied and the moment an item's path finishes, the item's entry holds nothing: the same
+// full-width step that empties the slice therefore starts all 64 paths of the row, lane l that of pixel l of the tile,
+// and parks what depends on the item -- the primary ray's direction and the seed after its two draws, {d.x, d.y, d.z,
+// seed}: one entry -- in entry l (stage_row).  The lane that is later handed the item reads the entry and clears its tag
+// word (take), instead of running the 95 instructions of a path start with the dozen lanes that happen to be idle.  A
+// padding pixel of an edge tile or stripe is staged as {kNoPath, 0, 0, 0}.  What this rests on:
+//  * a row is opened exactly once, before any of its items is handed out (a round takes at least one item, so the
+//    `in0 == 0` and the `in0 + taken > 64` cases of the refill exclude each other for one row);
+//  * a wave consumes its rows in order and to the end (reservations end on row boundaries, total_items is a multiple of
+//    64), so a slice is reopened only after every staged entry of its previous row was taken, and the final drain at the
+//    kernel's exit finds no staged entry;
+//  * a taken entry has tag 0 until its own path parks there, so drain never mistakes a seed for a radiance tag;
+//  * stragglers of the slice's previous row are marked kDirect in the step that restages it and never park there;
+//  * writes and reads of one wave reach LDS in program order: the staged entries are complete when another lane reads
+//    them, with no more than the usual wait on the LDS counter (the fence in k_trace only orders the compiler).
 constexpr uint32_t kRingRows = 4u, kDirect = 0x80000000u;
+constexpr float kNoPath = 2.0f;  // in .x of a staged entry: a padding pixel (no component of a normalised direction is 2)
 // LDS-qualified pointers: with generic ones the compiler folds "park or store directly" into one FLAT store through a
 // selected address, which is slower than either and loses the streaming hint
 struct ColorRing {
@@ -244,6 +262,30 @@ struct ColorRing {
         const uint32_t slice = row & (kRingRows - 1u);
         drain(colors, lane, slice);
         if (active && ((item >> 6) & (kRingRows - 1u)) == slice) item |= kDirect;
+    }
+    // all 64 lanes, after open_row(row): the path starts of the row's 64 items (tile (tx, ty), sample hash hs)
+    DEV void stage_row(const KParams& p, uint32_t lane, uint32_t row, uint32_t tx, uint32_t ty, uint32_t hs) const {
+        const uint32_t x = tx * 8u + (lane & 7u), ly = ty * 8u + (lane >> 3);   // item_pixel's coordinates for pixel `lane`
+        v4f v = {kNoPath, 0.0f, 0.0f, 0.0f};
+        if ((x < p.u.width) && (ly < p.local_rows)) {
+            const uint32_t y = global_row(p, ly);
+            if (y < p.u.height) {
+                f3 d;
+                uint32_t seed;
+                start_ray_hashed(p, x, y, y * p.u.width + x, hs, d, seed);
+                v = v4f{d.x, d.y, d.z, __uint_as_float(seed)};
+            }
+        }
+        ring[(row & (kRingRows - 1u)) * 64u + lane] = v;
+    }
+    // the lane that is handed `item`: its staged start; false for a padding pixel.  The entry is left with tag 0.
+    DEV bool take(uint32_t item, f3& d, uint32_t& seed) const {
+        const uint32_t e = item & (kRingRows * 64u - 1u);
+        const v4f v = ring[e];
+        tag(e) = 0u;
+        d = mk(v.x, v.y, v.z);
+        seed = __float_as_uint(v.w);
+        return v.x != kNoPath;
     }
     DEV void drain(float4* __restrict__ colors, uint32_t lane, uint32_t slice) const {
         const uint32_t e = slice * 64u + lane;
@@ -385,8 +427,14 @@ struct ItemQueue {
 // WAVES = resident waves per SIMD the register allocation aims for: 6 (80 registers, nothing spilled) except for the
 // large launches of the default instantiation, which run 3 % faster with 8 (64 registers, 9 spilled outside the
 // segment code) -- and 2-3 % slower on one-sample frames, hence two instantiations.
-template <bool STATS, bool MULTI, int WAVES = RB_TRACE_WAVES>
-__global__ void __launch_bounds__(kTraceBlock, WAVES) k_trace(const KParams p) {
+// STAGED = true: the paths of a 64-item row are started in one full-width pass when the row is opened, and handed out from
+// the colour ring (ColorRing); needs queue_batch % (kRingRows * 64) == 0, which launch_render checks.  STAGED = false:
+// every lane starts its own path when it is handed the item -- the launches whose reservations are finer (small frames,
+// forced batches), and MULTI, which keeps that form whatever the batch (its segment code leaves the start no registers
+// to win).  The choice is made at compile time so that no instantiation carries both start codes; the two forms are two
+// kernels, k_trace and k_trace_direct, around this one body.
+template <bool STATS, bool MULTI, bool STAGED>
+DEV void trace_body(const KParams& p, v4f* s_ring) {
     extern __shared__ __attribute__((aligned(16))) uint32_t s_stack[];
     const uint32_t tid = threadIdx.x;
     const uint32_t lane = tid & 63u;
@@ -396,7 +444,6 @@ __global__ void __launch_bounds__(kTraceBlock, WAVES) k_trace(const KParams p) {
     const uint32_t total_items = tiles_x * tiles_y * S * 64u;  // host keeps this < 2^31
     float4* __restrict__ colors = reinterpret_cast<float4*>(p.colors);
     Tally<STATS> tl;
-    __shared__ __attribute__((aligned(16))) v4f s_ring[(kTraceBlock / 64u) * kRingRows * 64u];
     ColorRing cring(s_ring, tid >> 6, lane);
     bool active = false, exhausted = false;
     uint32_t item = 0;
@@ -444,21 +491,48 @@ __global__ void __launch_bounds__(kTraceBlock, WAVES) k_trace(const KParams p) {
             const bool take = !active && rank < avail;
             const uint32_t n_idle = (uint32_t)__popcll(idle);
             const uint32_t taken = n_idle < avail ? n_idle : avail;
-            if (direct_mask == 0u) {
-                if (rows.in0 == 0u) cring.open_row(colors, lane, loc_next >> 6, active, item);
-                else if (rows.in0 + taken > 64u) cring.open_row(colors, lane, (loc_next >> 6) + 1u, active, item);
-            }
-            if (take) {
-                const uint32_t it = loc_next + rank;
-                uint32_t x = 0, y = 0, sample_hash = 0;
-                if (item_pixel(rp, rows, rank, x, y, sample_hash)) {
-                    start_path_hashed(rp, x, y, y * r_width + x, sample_hash, pt);
-                    item = it | direct_mask;
-                    if (rp.u.max_depth > 0u) {
-                        active = true;
-                    } else {
-                        colors[it] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                        tl.paths++;
+            if constexpr (STAGED) {
+                // a row whose first item goes out in this round -- the one at loc_next, or the next one when the takes
+                // run over the end of the current row -- is opened and its 64 paths are started, by all lanes
+                if (rows.in0 == 0u || rows.in0 + taken > 64u) {
+                    const uint32_t nx = rows.in0 != 0u ? 1u : 0u, row = (loc_next >> 6) + nx;
+                    cring.open_row(colors, lane, row, active, item);
+                    cring.stage_row(rp, lane, row, rows.tx[nx], rows.ty[nx], rows.hs[nx]);
+                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // other lanes read these entries below
+                }
+                if (take) {
+                    const uint32_t it = loc_next + rank;
+                    if (cring.take(it, pt.d, pt.seed)) {
+                        pt.o = ld3(rp.cam.pos);
+                        pt.color = mk(0, 0, 0);
+                        pt.att = mk(1, 1, 1);
+                        pt.depth = 0;
+                        item = it;
+                        if (rp.u.max_depth > 0u) {
+                            active = true;
+                        } else {
+                            colors[it] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                            tl.paths++;
+                        }
+                    }
+                }
+            } else {
+                if (direct_mask == 0u) {
+                    if (rows.in0 == 0u) cring.open_row(colors, lane, loc_next >> 6, active, item);
+                    else if (rows.in0 + taken > 64u) cring.open_row(colors, lane, (loc_next >> 6) + 1u, active, item);
+                }
+                if (take) {
+                    const uint32_t it = loc_next + rank;
+                    uint32_t x = 0, y = 0, sample_hash = 0;
+                    if (item_pixel(rp, rows, rank, x, y, sample_hash)) {
+                        start_path_hashed(rp, x, y, y * r_width + x, sample_hash, pt);
+                        item = it | direct_mask;
+                        if (rp.u.max_depth > 0u) {
+                            active = true;
+                        } else {
+                            colors[it] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                            tl.paths++;
+                        }
                     }
                 }
             }
@@ -480,7 +554,17 @@ __global__ void __launch_bounds__(kTraceBlock, WAVES) k_trace(const KParams p) {
         }
     }
     for (uint32_t k = 0; k < kRingRows; k++) cring.drain(colors, lane, k);
-    flush_tally<STATS>(tl, p.counters);
+    flush_tally<STATS>(tl, fresh_params(p).counters);   // not held in scalar registers across the loop either
+}
+template <bool STATS, bool MULTI, int WAVES = RB_TRACE_WAVES>
+__global__ void __launch_bounds__(kTraceBlock, WAVES) k_trace(const KParams p) {
+    __shared__ __attribute__((aligned(16))) v4f s_ring[(kTraceBlock / 64u) * kRingRows * 64u];
+    trace_body<STATS, MULTI, !MULTI>(p, s_ring);
+}
+template <bool STATS, bool MULTI, int WAVES = RB_TRACE_WAVES>
+__global__ void __launch_bounds__(kTraceBlock, WAVES) k_trace_direct(const KParams p) {
+    __shared__ __attribute__((aligned(16))) v4f s_ring[(kTraceBlock / 64u) * kRingRows * 64u];
+    trace_body<STATS, MULTI, false>(p, s_ring);
 }
 
 // k_trace for multi-node BVHs.  With 128-triangle leaves and no t-culling (the reference's
@@ -1706,9 +1790,17 @@ int launch_render(const KParams& p_, uint32_t kernel, bool stats, void* stream_,
                     if (stats) hipLaunchKernelGGL((k_trace<true, true>), grid, block, lds, stream, q);
                     else hipLaunchKernelGGL((k_trace<false, true>), grid, block, lds, stream, q);
                 } else {
-                    if (stats) hipLaunchKernelGGL((k_trace<true, false>), grid, block, lds, stream, q);
-                    else if (items >= kTraceManyItems) hipLaunchKernelGGL((k_trace<false, false, RB_TRACE_WAVES_BIG>), grid, block, lds, stream, q);
-                    else hipLaunchKernelGGL((k_trace<false, false>), grid, block, lds, stream, q);
+                    // reservations of whole multiples of kRingRows rows: the rows' paths are started a row at a time (ColorRing)
+                    const bool staged = q.queue_batch % (kRingRows * 64u) == 0u;
+                    if (staged) {
+                        if (stats) hipLaunchKernelGGL((k_trace<true, false>), grid, block, lds, stream, q);
+                        else if (items >= kTraceManyItems) hipLaunchKernelGGL((k_trace<false, false, RB_TRACE_WAVES_BIG>), grid, block, lds, stream, q);
+                        else hipLaunchKernelGGL((k_trace<false, false>), grid, block, lds, stream, q);
+                    } else {
+                        if (stats) hipLaunchKernelGGL((k_trace_direct<true, false>), grid, block, lds, stream, q);
+                        else if (items >= kTraceManyItems) hipLaunchKernelGGL((k_trace_direct<false, false, RB_TRACE_WAVES_BIG>), grid, block, lds, stream, q);
+                        else hipLaunchKernelGGL((k_trace_direct<false, false>), grid, block, lds, stream, q);
+                    }
                 }
                 break;
         }
