@@ -590,6 +590,37 @@ int rb_occluded_device(rb_engine* e, const rb_ray* d_rays, const float* d_tmax, 
  * On a sharded engine rays are whole-scene rays, as for rb_cast_rays. */
 int rb_cast_rays_device(rb_engine* e, const rb_ray* d_rays, size_t n, rb_hit* d_hits, rb_surface* d_surf);
 
+/* ---- Path-traced radiance along caller-given rays (the oracle's rbo_trace_ray).  For ray i of n and
+ * sample k of `samples`:
+ *   d_i       = normalize(dir_i) on the device, exactly as rb_cast_rays does it (the walks' margins need |d| = 1 +- 4 ulp);
+ *   sid_i     = seeds ? seeds[i] : (uint32_t)i;
+ *   seed(i,k) = pcg(sid_i + pcg(first_sample + k)) with u32 wrap-around: the first line of the shader's main with sid_i in
+ *               place of pixel_index.  No jitter draws follow: the ray is the caller's;
+ *   c(i,k)    = trace_ray(scene, origin_i, d_i, seed(i,k)), shader.wgsl:522-662: same max_depth, category order and strict
+ *               `<`, phantom light, kept counts, colour hash and numerics contract as a render of the uploaded scene;
+ *   out[i]    = {sum r, sum g, sum b, w}: the sum starts at +0.0f and adds c(i,0), c(i,1), ... in ascending k, one binary32
+ *               add per component per sample; w = (float)samples.
+ * A ray rb_cast_rays would mark RB_HIT_INVALID is not walked and yields {0, 0, 0, 0}; max_depth == 0 yields {0, 0, 0, samples}.
+ * The side effects are a query's: none on the accumulation, the frames or the work counters (rb_get_stats does not move),
+ * rb_last_kernel_name is unchanged and a pass the iterator has started ahead stays valid.  rb_last_query_kernel_name reports
+ * "k_rad", "k_rad_bvh" or "k_rad_chunk" -- the walk by rb_cast_rays' rule -- and rb_last_query_ms their time with the sums'. */
+typedef struct rb_radiance { float sum[3]; float weight; } rb_radiance;                              /* 16 B */
+/* (ray, sample) items per launch: the colour scratch is 16 B x this (256 MiB) whatever n and samples are: a launch of this size
+ * runs for milliseconds, so the tail every piece ends in stays a few per cent */
+#define RB_TRACE_PIECE_ITEMS (1u << 24)
+/* n rays and, unless NULL, n seeds from host memory; out[n] (pageable or page-locked).  RB_ERR_INVALID_OPTIONS, before any
+ * launch: samples == 0 or > 65536, first_sample + samples beyond 2^32 - 1, n > 2^31 - 64, NULL rays or out with n > 0.
+ * n == 0 is RB_OK.  The rays go through the device in pieces of at most RB_TRACE_PIECE_ITEMS items -- whole rays: a piece
+ * never splits one ray's samples -- each launched, summed and copied out before the next.  The result does not depend on
+ * the piece size, the launch shape or the form of the call.  Sharded engines and multi-device handles as rb_cast_rays. */
+int rb_trace_rays(rb_engine* e, const rb_ray* rays, const uint32_t* seeds, size_t n, uint32_t first_sample, uint32_t samples,
+                  rb_radiance* out);
+/* The same with every pointer in device memory of the engine's device, validated as rb_occluded_device validates its buffers
+ * (d_rays and d_out 16-byte aligned, d_seeds 4-byte).  Every launch is queued on the engine's stream and the call returns
+ * without waiting: rb_sync is the wait. */
+int rb_trace_rays_device(rb_engine* e, const rb_ray* d_rays, const uint32_t* d_seeds, size_t n, uint32_t first_sample,
+                         uint32_t samples, rb_radiance* d_out);
+
 /* ---- Edge-avoiding denoiser over the first-hit buffers (no reference counterpart).  An a-trous wavelet
  * filter (Dammertz et al. 2010) on the albedo-demodulated mean radiance, guided by the first hit of every pixel-centre ray.
  * Section 13 is the normative definition: every step one IEEE binary32 operation in a fixed order, so that the device's result
@@ -692,6 +723,7 @@ static_assert(offsetof(rb_surface, flags) == 12, "flags @12");
 static_assert(offsetof(rb_surface, emissive) == 16, "emissive @16");
 static_assert(offsetof(rb_surface, texture_index) == 28, "texture_index @28");
 static_assert(offsetof(rb_surface, uv) == 32, "uv @32");
+static_assert(sizeof(rb_radiance) == 16, "rb_radiance is 16 B");
 static_assert(sizeof(rb_guide) == 48, "rb_guide is 48 B");
 static_assert(sizeof(rb_denoise_params) == 32, "rb_denoise_params is 32 B");
 static_assert(offsetof(rb_guide, t) == 12, "t @12");
@@ -714,6 +746,7 @@ _Static_assert(sizeof(rb_progressive) == 16, "ProgressiveRenderHelper is 16 B");
 _Static_assert(sizeof(rb_ray) == 32, "rb_ray is 32 B");
 _Static_assert(sizeof(rb_hit) == 48, "rb_hit is 48 B");
 _Static_assert(sizeof(rb_surface) == 48, "rb_surface is 48 B");
+_Static_assert(sizeof(rb_radiance) == 16, "rb_radiance is 16 B");
 _Static_assert(sizeof(rb_guide) == 48, "rb_guide is 48 B");
 _Static_assert(sizeof(rb_denoise_params) == 32, "rb_denoise_params is 32 B");
 #endif

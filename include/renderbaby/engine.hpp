@@ -209,6 +209,20 @@ class Engine final : public Renderer {
     void cast_rays_device(const rb_ray* d_rays, size_t n, rb_hit* d_hits, rb_surface* d_surf = nullptr) {
         check(h_->e, rb_cast_rays_device(h_->e, d_rays, n, d_hits, d_surf));
     }
+    // ---- path-traced radiance along given rays (extension; rb_abi.h): per ray the ordered sum of
+    // `samples` evaluations of trace_ray and the weight; seeds: empty (the ray's index) or one id per ray
+    std::vector<rb_radiance> trace_rays(const std::vector<rb_ray>& rays, const std::vector<uint32_t>& seeds = {}, uint32_t samples = 1,
+                                        uint32_t first_sample = 0) {
+        if (!seeds.empty() && seeds.size() != rays.size()) throw std::invalid_argument("rays and seeds differ in length");
+        std::vector<rb_radiance> out(rays.size());
+        check(h_->e, rb_trace_rays(h_->e, rays.data(), seeds.empty() ? nullptr : seeds.data(), rays.size(), first_sample, samples, out.data()));
+        return out;
+    }
+    // the same on buffers in the engine's device memory: queued on the engine's stream, not waited for -- sync() waits
+    void trace_rays_device(const rb_ray* d_rays, const uint32_t* d_seeds, size_t n, rb_radiance* d_out, uint32_t samples = 1,
+                           uint32_t first_sample = 0) {
+        check(h_->e, rb_trace_rays_device(h_->e, d_rays, d_seeds, n, first_sample, samples, d_out));
+    }
     void sync() { check(h_->e, rb_sync(h_->e)); }
     // ---- the denoiser (rb_abi.h): the a-trous filter over the committed accumulation
     static rb_denoise_params denoise_defaults() {

@@ -49,6 +49,9 @@ SURFACE = np.dtype([("albedo", f4, (3,)), ("flags", u4), ("emissive", f4, (3,)),
 HIT_NONE, HIT_GROUND, HIT_TRIANGLE, HIT_SPHERE, HIT_LIGHT, HIT_INVALID = 0, 1, 2, 3, 4, 0xFFFFFFFF
 SURFACE_IS_METAL, SURFACE_USE_TEXTURE = 1, 2
 NO_INDEX = 0xFFFFFFFF
+# path-traced radiance along given rays (rb_trace_rays): the per-ray sum and the items of one launch
+RADIANCE = np.dtype([("sum", f4, (3,)), ("weight", f4)])
+TRACE_PIECE_ITEMS = 1 << 24
 # any-hit occlusion (rb_occluded): result bytes and stage masks
 OCCL_VISIBLE, OCCL_OCCLUDED, OCCL_INVALID = 0, 1, 255
 MASK_GROUND, MASK_TRIANGLES, MASK_SPHERES, MASK_LIGHTS, MASK_ALL = 1, 2, 4, 8, 15

@@ -130,17 +130,24 @@ def ambient_occlusion_rays(uniforms, hits, n_dirs=16, seed=0):
     n = np.where((n * d).sum(-1, keepdims=True) > 0, -n, n).astype(f32)
     pos = (np.asarray(u["camera"]["pos"], f32) + t * d).astype(f32)
     org = (pos + n * (f32(1e-3) * np.maximum(f32(1.0), t))).astype(f32)   # off the surface: beyond the rounding of pos
+    return m, np.repeat(org, n_dirs, axis=0), cosine_directions(n, n_dirs, seed).reshape(-1, 3)
+
+
+def cosine_directions(normals, n_dirs, seed=0):
+    """``n_dirs`` cosine-weighted directions about each of the (m, 3) unit ``normals``: (m, n_dirs, 3), numpy float32 -- the ray
+    generator of ``ambient_occlusion`` and of ``bake.irradiance``."""
+    f32 = np.float32
+    n = np.asarray(normals, f32).reshape(-1, 3)
     rng = np.random.Generator(np.random.PCG64(seed))
-    r1, r2 = rng.random((len(org), n_dirs), dtype=f32), rng.random((len(org), n_dirs), dtype=f32)
+    r1, r2 = rng.random((len(n), n_dirs), dtype=f32), rng.random((len(n), n_dirs), dtype=f32)
     phi, r = f32(2.0 * np.pi) * r1, np.sqrt(r2, dtype=f32)
     # a tangent frame about n (any: the distribution is symmetric about n)
     a = np.where(np.abs(n[:, 0:1]) > f32(0.5), np.array([0, 1, 0], f32), np.array([1, 0, 0], f32))
     tx = np.cross(a, n).astype(f32)
     tx /= np.sqrt((tx * tx).sum(-1, keepdims=True), dtype=f32)
     ty = np.cross(n, tx).astype(f32)
-    dirs = ((r * np.cos(phi))[..., None] * tx[:, None, :] + (r * np.sin(phi))[..., None] * ty[:, None, :]
+    return ((r * np.cos(phi))[..., None] * tx[:, None, :] + (r * np.sin(phi))[..., None] * ty[:, None, :]
             + np.sqrt(np.maximum(f32(1.0) - r2, f32(0)), dtype=f32)[..., None] * n[:, None, :]).astype(f32)
-    return m, np.repeat(org, n_dirs, axis=0), dirs.reshape(-1, 3)
 
 
 def ambient_occlusion(engine, hits, n_dirs=16, radius=1.0, seed=0, uniforms=None):

@@ -1,0 +1,114 @@
+"""Baking and free cameras on top of ``Engine.trace_rays`` (rb_trace_rays): the engine answers
+"what radiance does trace_ray return along this ray?", everything else here is numpy on the caller's side.
+
+``irradiance``   mean radiance over cosine-weighted directions about a normal: lightmap texels, vertices, probes
+``camera_rays``  the rays of cameras the reference's Camera struct cannot express: equirect, ortho, thin_lens
+``render_rays``  rays -> tone-mapped RGBA8 pixels, the reference's colour mapping applied to sum / weight
+"""
+import numpy as np
+
+from . import aov
+
+f32 = np.float32
+KINDS = ("equirect", "ortho", "thin_lens")
+
+
+def _unit(v):
+    v = np.asarray(v, f32)
+    return (v / np.sqrt((v[..., 0:1] * v[..., 0:1] + v[..., 1:2] * v[..., 1:2]) + v[..., 2:3] * v[..., 2:3], dtype=f32)).astype(f32)
+
+
+def irradiance_rays(points, normals, samples, seed=0):
+    """The rays of ``irradiance``: ``samples`` cosine-weighted directions about each unit normal (aov.cosine_directions, the
+    generator of ``aov.ambient_occlusion``), from the point moved off the surface along the normal as it is there.  Returns
+    (origins (m * samples, 3), directions (m * samples, 3)), numpy float32, a point's rays next to each other."""
+    p = np.asarray(points, f32).reshape(-1, 3)
+    n = _unit(np.asarray(normals, f32).reshape(-1, 3))
+    if len(p) != len(n):
+        raise ValueError("points and normals differ in length")
+    reach = np.sqrt((p * p).sum(-1, keepdims=True), dtype=f32)
+    org = (p + n * (f32(1e-3) * np.maximum(f32(1.0), reach))).astype(f32)   # off the surface: beyond the rounding of the point
+    return np.repeat(org, samples, axis=0), aov.cosine_directions(n, samples, seed).reshape(-1, 3)
+
+
+def irradiance(engine, points, normals, samples, seed=0):
+    """Mean radiance arriving at each point over the cosine-weighted hemisphere about its normal -- the irradiance divided by
+    pi -- as float32 (m, 3).  One ray per (point, sample), each traced once (``samples=1`` per ray) with an id of its own
+    (``seed`` * m * samples + its index, 32 bits), averaged here in float32 in sample order."""
+    samples = int(samples)
+    if samples < 1:
+        raise ValueError("samples must be at least 1")
+    org, dirs = irradiance_rays(points, normals, samples, seed)
+    m = len(org) // samples
+    ids = ((np.arange(len(org), dtype=np.uint64) + np.uint64(seed) * np.uint64(len(org))) & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+    rad = engine.trace_rays(org, dirs, seeds=ids, samples=1)
+    c = rad["sum"].reshape(m, samples, 3)
+    total = np.zeros((m, 3), f32)
+    for k in range(samples):
+        total = (total + c[:, k]).astype(f32)
+    return (total / f32(samples)).astype(f32)
+
+
+def camera_rays(kind, width, height, pos, dir=(0.0, 0.0, -1.0), up=(0.0, 1.0, 0.0), ortho_width=2.0, fov_deg=60.0,
+                aperture=0.0, focus_distance=1.0, seed=0):
+    """(origins, directions) of a ``width`` x ``height`` image, float32 (height, width, 3), row 0 on top, column 0 on the left
+    as the viewer sees it; unit directions.  ``kind``:
+
+    equirect   the full sphere from ``pos``: column -> longitude (the centre column looks along ``dir``, longitude grows to
+               the right), row -> latitude (top row up); pixel centres, so no ray points exactly at a pole
+    ortho      parallel rays along ``dir`` from a window ``ortho_width`` wide centred on ``pos``
+    thin_lens  a pinhole of vertical field of view ``fov_deg`` whose rays start on a lens of diameter ``aperture`` (seeded
+               uniform samples on the disc, one per pixel) and meet their pixel's pinhole ray at ``focus_distance`` along it
+    """
+    w, h = int(width), int(height)
+    if w < 1 or h < 1:
+        raise ValueError("width and height must be at least 1")
+    if kind not in KINDS:
+        raise ValueError(f"unknown camera {kind!r}: one of {', '.join(KINDS)}")
+    pos = np.asarray(pos, f32).reshape(3)
+    fwd = _unit(np.asarray(dir, f32).reshape(3))
+    right = np.cross(fwd, np.asarray(up, f32).reshape(3)).astype(f32)
+    if not np.any(right):
+        raise ValueError("dir and up are parallel")
+    right = _unit(right)
+    upv = np.cross(right, fwd).astype(f32)
+    sx = ((np.arange(w, dtype=f32) + f32(0.5)) / f32(w) * f32(2.0) - f32(1.0))[None, :, None]    # -1 .. 1, left to right
+    sy = (f32(1.0) - (np.arange(h, dtype=f32) + f32(0.5)) / f32(h) * f32(2.0))[:, None, None]    # 1 .. -1, top to bottom
+    if kind == "equirect":
+        lon, lat = sx * f32(np.pi), sy * f32(np.pi / 2)
+        d = (np.cos(lat) * np.sin(lon)) * right + np.sin(lat) * upv + (np.cos(lat) * np.cos(lon)) * fwd
+        return np.broadcast_to(pos, (h, w, 3)).astype(f32), _unit(d.astype(f32))
+    if kind == "ortho":
+        half_w = f32(ortho_width) / f32(2.0)
+        half_h = half_w * f32(h) / f32(w)
+        org = pos + (sx * half_w) * right + (sy * half_h) * upv
+        return org.astype(f32), np.broadcast_to(fwd, (h, w, 3)).astype(f32)
+    th = f32(np.tan(np.radians(fov_deg) / 2.0))
+    d = _unit(((sx * th * f32(w) / f32(h)) * right + (sy * th) * upv + fwd).astype(f32))
+    focus = pos + f32(focus_distance) * d
+    rng = np.random.Generator(np.random.PCG64(seed))
+    r = (f32(aperture) / f32(2.0)) * np.sqrt(rng.random((h, w, 1), dtype=f32), dtype=f32)
+    phi = f32(2.0 * np.pi) * rng.random((h, w, 1), dtype=f32)
+    org = (pos + (r * np.cos(phi)) * right + (r * np.sin(phi)) * upv).astype(f32)
+    return org, _unit((focus - org).astype(f32))
+
+
+def tone_map(radiance):
+    """sum / weight per ray -> RGBA8: the reference's x / (x + 1) and colour mapping (shader.wgsl:716-722, aov.color_map);
+    a ray without weight (an invalid one) is black.  ``radiance``: abi.RADIANCE of any shape."""
+    w = radiance["weight"][..., None].astype(f32)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = np.where(w > 0, radiance["sum"].astype(f32) / w, f32(0)).astype(f32)
+        mapped = (mean / (mean + f32(1.0))).astype(f32)
+    out = np.empty(mean.shape[:-1] + (4,), dtype=np.uint8)
+    out[..., :3] = aov.color_map(mapped)
+    out[..., 3] = 255
+    return out
+
+
+def render_rays(engine, origins, dirs, samples, first_sample=0):
+    """The image of a ray per pixel: (h, w, 3) origins and directions -> uint8 (h, w, 4); pixel (row, column) gets the id
+    row * w + column, so two renders of one size draw the same random numbers."""
+    o = np.asarray(origins, f32)
+    rad = engine.trace_rays(o.reshape(-1, 3), np.asarray(dirs, f32).reshape(-1, 3), samples=samples, first_sample=first_sample)
+    return tone_map(rad.reshape(o.shape[:-1]))

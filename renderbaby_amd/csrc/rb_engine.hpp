@@ -171,6 +171,9 @@ struct rb_engine {
     rb::DevBuf<rb_surface> q_surf;
     rb::DevBuf<float> q_tmax;        // rb_occluded: the piece's bounds and its result bytes
     rb::DevBuf<uint8_t> q_occl;
+    rb::DevBuf<float> rad_colors;    // rb_trace_rays: float4 per (ray, sample) of one piece, the piece's ids and sums, the queue word
+    rb::DevBuf<uint32_t> rad_seeds, rad_queue;
+    rb::DevBuf<rb_radiance> rad_out;
     hipEvent_t ev_q[2] = {nullptr, nullptr};
     const char* last_query_kernel_name = "";
     float last_query_ms = 0.0f;

@@ -394,6 +394,20 @@ struct OcclArgs {
     uint32_t mask;
 };
 int launch_occluded(const KParams& p, const OcclArgs& a, void* stream, LaunchInfo* info);
+// ---- rb_radiance.hip: path-traced radiance along given rays.  One launch answers one piece: `n` rays of a
+// device buffer, `samples` samples each, n x samples <= RB_TRACE_PIECE_ITEMS (rounded up to whole blocks of 64 rays).
+struct RadArgs {
+    const rb_ray* rays;       // the piece's rays
+    const uint32_t* seeds;    // the piece's ray ids, or nullptr: seed_base + index in the piece
+    float* colors;            // scratch: float4 per (ray, sample), [block of 64 rays][sample][64]
+    rb_radiance* out;         // the piece's sums
+    uint32_t* queue;          // one work-queue word
+    uint32_t n;               // rays in this piece
+    uint32_t seed_base;       // index of the piece's first ray in the call
+    uint32_t first_sample, samples;
+    uint32_t batch, magic_S;  // set by launch_radiance: items per reservation, floor(2^32 / samples)
+};
+int launch_radiance(const KParams& p, const RadArgs& a, void* stream, LaunchInfo* info);
 Cam host_cam(const rb_uniforms& u);   // rb_kernels.hip: the camera of a launch, shader.wgsl:690,702-708
 
 // ---- rb_denoise.hip: the edge-avoiding a-trous filter.  Everything is in the orientation of the delivered

@@ -749,6 +749,8 @@ __global__ void __launch_bounds__(BLOCK, RB_BVH_WAVES) k_trace_bvh(const KParams
 #ifndef RB_CHUNK_FINISH_LANES
 #define RB_CHUNK_FINISH_LANES 32 // shade once this many lanes have finished their walk (or nobody walks)
 #endif
+// (Twins of this body: k_query_chunk / k_occl_chunk, rb_query.hip, and k_rad_chunk, rb_radiance.hip, which starts its paths from a
+// ray buffer -- a fix to phases 2-5 here belongs there too; k_trace_bvh's walk likewise has k_rad_bvh.)
 // SPHTREE: the instantiation for scenes that also have a sphere tree (more than 64 spheres), whose per-lane walk runs inside
 // segment_finish; the other one leaves that walk out of its register allocation
 template <bool STATS, bool SPHTREE>

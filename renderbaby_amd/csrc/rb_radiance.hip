@@ -1,0 +1,571 @@
+// rb_radiance.hip -- path-traced radiance along caller-given rays (rb_trace_rays): trace_ray
+// (shader.wgsl:522-662) for a GIVEN ray and a seed made from the caller's id of the ray, summed over `samples` samples.
+// Same numerics contract as rb_kernels.hip (no FMA contraction, correctly rounded / and sqrt), the same device functions
+// for every test and for the shading, and the walk a render of the scene would take:
+//   k_rad        trees of at most one node and at most 64 spheres: k_trace_direct's per-segment loop
+//   k_rad_bvh    k_trace_bvh's stepped reference walk and, inside segment_finish, the per-lane sphere tree walk
+//   k_rad_chunk  the chunked walk: k_trace_chunk's node and pooled leaf phases
+// Like the render's stream kernels these are persistent wavefronts over a queue of (ray, sample) items with path
+// regeneration -- a lane whose path ends takes the next item while its neighbours keep walking -- and like them they
+// work in two phases ("Why two phases"): a finished path stores its colour (16 B) into a scratch
+// laid out [block of 64 rays][sample][64 rays], and k_rad_sum, one lane per ray, adds a ray's samples IN SAMPLE ORDER.
+// What differs from the render is where a path starts (two 16-byte loads of the ray, its normalisation, the seed; no
+// camera, no jitter draws) and where its colour ends up (a per-ray sum instead of the frame's accumulation).  Only
+// non-STATS forms exist: the work counters do not move.
+#include "rb_device_chunk.hpp"
+
+#pragma clang fp contract(off)
+
+namespace rb {
+namespace {
+
+constexpr uint32_t kRadBlock = 256;
+#ifndef RB_RAD_WAVES
+#define RB_RAD_WAVES 6         // k_trace's: 80 registers
+#endif
+#ifndef RB_RAD_BVH_WAVES
+#define RB_RAD_BVH_WAVES 1     // k_trace_bvh's
+#endif
+#ifndef RB_RAD_CHUNK_WAVES
+#define RB_RAD_CHUNK_WAVES 5   // k_trace_chunk's: 96 registers
+#endif
+#ifndef RB_RAD_FINISH_LANES
+#define RB_RAD_FINISH_LANES 32 // k_trace_chunk's RB_CHUNK_FINISH_LANES
+#endif
+
+DEV bool rad_finite3(f3 a) {
+    const uint32_t m = 0x7F800000u;
+    return (__float_as_uint(a.x) & m) != m && (__float_as_uint(a.y) & m) != m && (__float_as_uint(a.z) & m) != m;
+}
+
+// ---- (ray, sample) items.  Item = (block * S + sample) * 64 + ray-in-block, block = 64 consecutive rays of the piece.
+// A refill round hands out at most 64 consecutive items starting at the wave-uniform `base`, so a lane's item lies in the
+// 64-item row of `base` or in the next one (item_rows' argument, rb_device_shade.hpp).
+struct RadRows {
+    uint32_t in0;
+    uint32_t blk[2], hs[2];   // the row's block of rays and pcg(first_sample + its sample)
+};
+DEV RadRows rad_rows(const RadArgs& a, uint32_t base) {
+    RadRows r;
+    r.in0 = base & 63u;
+    uint32_t smp;
+    const uint32_t blk = udiv_magic(base >> 6, a.samples, a.magic_S, smp);
+    r.blk[0] = blk;
+    r.hs[0] = pcg(a.first_sample + smp);
+    uint32_t smp1 = smp + 1u, blk1 = blk;
+    if (smp1 == a.samples) {
+        smp1 = 0u;
+        blk1++;
+    }
+    r.blk[1] = blk1;
+    r.hs[1] = pcg(a.first_sample + smp1);
+    return r;
+}
+
+// The start of item `it`'s path on the calling lane: the ray as rb_cast_rays reads it (query_lane, rb_query.hip: two
+// 16-byte loads, the device's normalize), seed(i, k) = pcg(sid_i + pcg(first_sample + k)) -- the first line of the
+// shader's main with sid_i in place of pixel_index; no jitter draws follow.  False for a ray that is not walked: an invalid
+// one (its colour slot becomes {0, 0, 0, 0}: weight 0) or any ray at max_depth = 0 ({0, 0, 0, 1}).
+DEV bool rad_start(const KParams& p, const RadArgs& a, uint32_t it, uint32_t ray, uint32_t hs, Path& pt) {
+    const v4f ra = ((const v4f*)a.rays)[(size_t)ray * 2u], rd = ((const v4f*)a.rays)[(size_t)ray * 2u + 1u];
+    pt.o = mk(ra.x, ra.y, ra.z);
+    pt.d = normalize(mk(rd.x, rd.y, rd.z));
+    const bool valid = rad_finite3(pt.o) && rad_finite3(pt.d) && !(pt.d.x == 0.0f && pt.d.y == 0.0f && pt.d.z == 0.0f);
+    const uint32_t sid = a.seeds != nullptr ? a.seeds[ray] : a.seed_base + ray;
+    pt.seed = pcg(sid + hs);
+    pt.color = mk(0, 0, 0);
+    pt.att = mk(1, 1, 1);
+    pt.depth = 0;
+    if (valid && p.u.max_depth > 0u) return true;
+    const v4f v = {0.0f, 0.0f, 0.0f, valid ? 1.0f : 0.0f};
+    reinterpret_cast<v4f*>(a.colors)[it] = v;
+    return false;
+}
+
+// a finished path: its colour and weight 1 into its (ray, sample) slot, read once by k_rad_sum (a streaming store, as
+// store_color of rb_kernels.hip)
+DEV void rad_store(const RadArgs& a, uint32_t it, f3 c) {
+    const v4f v = {c.x, c.y, c.z, 1.0f};
+    __builtin_nontemporal_store(v, reinterpret_cast<v4f*>(a.colors) + it);
+}
+
+// The work queue, one instance per wavefront: ItemQueue of rb_kernels.hip with one queue word and no bands.  The first
+// reservation is the wave's own -- wave w starts on items [w * batch, (w + 1) * batch) and the queue word starts at
+// waves * batch (launch_radiance) --, later ones are one atomic per `batch` items; inside a reservation the wave hands
+// items to its idle lanes with ballot + prefix count.
+struct RadQueue {
+    uint32_t loc_next = 0, loc_end = 0;   // this wave's reserved item range (wave-uniform)
+    uint32_t batch, total;
+    bool exhausted = false;
+
+    DEV RadQueue(const RadArgs& a, uint32_t total_items) : batch(a.batch), total(total_items) {
+        const uint64_t first = (uint64_t)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * batch;
+        if (first < total) {
+            loc_next = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)first);
+            loc_end = (total - loc_next < batch) ? total : loc_next + batch;
+        }
+    }
+    DEV bool drained() const { return exhausted && loc_next == loc_end; }
+
+    // on_item(item, ray, sample_hash) starts a path on the calling lane; the padding rays of the last block are skipped here
+    template <class IsIdle, class OnItem>
+    DEV void refill(const RadArgs& a, uint32_t lane, IsIdle&& is_idle, OnItem&& on_item) {
+        unsigned long long idle = __ballot(is_idle());
+        for (int round = 0; round < 2 && idle != 0ull; round++) {
+            if (loc_next == loc_end) {
+                if (exhausted) break;
+                uint32_t b = 0;
+                if (lane == 0u) b = atomicAdd(a.queue, batch);
+                b = (uint32_t)__builtin_amdgcn_readfirstlane((int)b);
+                if (b >= total) {
+                    exhausted = true;
+                    break;
+                }
+                loc_next = b;
+                loc_end = (total - b < batch) ? total : b + batch;
+            }
+            const RadRows rows = rad_rows(a, loc_next);
+            const uint32_t avail = loc_end - loc_next;
+            const uint32_t rank = (uint32_t)__popcll(idle & ((1ull << lane) - 1ull));
+            const bool take = ((idle >> lane) & 1ull) != 0ull && rank < avail;
+            const uint32_t n_idle = (uint32_t)__popcll(idle);
+            const uint32_t taken = n_idle < avail ? n_idle : avail;
+            if (take) {
+                const uint32_t idx = rows.in0 + rank;
+                const bool next = idx >= 64u;
+                const uint32_t ray = (next ? rows.blk[1] : rows.blk[0]) * 64u + (idx & 63u);
+                if (ray < a.n) on_item(loc_next + rank, ray, next ? rows.hs[1] : rows.hs[0]);
+            }
+            loc_next += taken;
+            idle = __ballot(is_idle());
+            if (taken == n_idle) break;   // everyone who asked was served (or got a padding item)
+        }
+    }
+};
+
+DEV uint32_t rad_total_items(const RadArgs& a) { return ((a.n + 63u) / 64u) * a.samples * 64u; }   // host keeps this < 2^31
+
+// ============================================================== k_rad ====
+// k_trace_direct's loop (rb_kernels.hip, trace_body<.., MULTI = false, STAGED = false>): every lane starts its own path
+// when it is handed the item and stores its colour directly; no ColorRing staging.
+__global__ void __launch_bounds__(kRadBlock, RB_RAD_WAVES) k_rad(const KParams p, const RadArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_stack[];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t lane = tid & 63u;
+    Tally<false> tl;
+    bool active = false;
+    uint32_t item = 0;
+    RadQueue iq(a, rad_total_items(a));
+    Path pt;
+    pt.depth = 0;
+
+    for (;;) {
+        iq.refill(a, lane, [&] { return !active; },
+                  [&](uint32_t it, uint32_t ray, uint32_t hs) {
+                      item = it;
+                      active = rad_start(fresh_params(p), a, it, ray, hs, pt);
+                  });
+        if (__ballot(active) == 0ull) {
+            if (iq.drained()) break;
+            continue;
+        }
+        if (active) {
+            const bool alive = segment<false, false>(p, pt, &s_stack[tid], kRadBlock, tl);
+            if (!alive) {
+                rad_store(a, item, pt.color);
+                active = false;
+            }
+        }
+    }
+}
+
+// ========================================================== k_rad_bvh ====
+// k_trace_bvh's stepped reference walk (rb_kernels.hip; the form that reads the tree through L1 / L2): the scheduling unit
+// is one leaf, the visit order per ray is the reference's, so the winner is the same triangle.  segment_finish carries the
+// per-lane sphere tree walk for scenes with more than 64 spheres.
+__global__ void __launch_bounds__(kRadBlock, RB_RAD_BVH_WAVES) k_rad_bvh(const KParams p, const RadArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_stack[];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t lane = tid & 63u;
+    const uint32_t node_count = p.u.bvh_node_count;
+    const cf4p nodes = (cf4p)p.nodes;
+    const cf4p ptris = (cf4p)p.ptris;
+    uint32_t* const stack = stack_column(s_stack, tid);
+    Tally<false> tl;
+
+    enum : uint32_t { IDLE = 0, BEGIN = 1, TRAV = 2, FINISH = 3 };
+    uint32_t state = IDLE;
+    uint32_t item = 0;
+    RadQueue iq(a, rad_total_items(a));
+    Path pt;
+    pt.depth = 0;
+    TriHit th;
+    th.hit = false;
+    th.t = 1e20f;
+    th.u = th.v = 0.0f;
+    th.slot = 0u;
+    f3 inv = mk(0, 0, 0);
+    int sp = 0;
+
+    for (;;) {
+        // ---- (1) hand items to idle lanes
+        iq.refill(a, lane, [&] { return state == IDLE; },
+                  [&](uint32_t it, uint32_t ray, uint32_t hs) {
+                      item = it;
+                      if (rad_start(fresh_params(p), a, it, ray, hs, pt)) state = BEGIN;
+                  });
+        if (__ballot(state != IDLE) == 0ull) {
+            if (iq.drained()) break;
+            continue;
+        }
+
+        // ---- (2) start of a segment: reset the traversal (shader.wgsl:283-307)
+        if (state == BEGIN) {
+            th.hit = false;
+            th.t = 1e20f;
+            th.u = th.v = 0.0f;
+            th.slot = 0u;
+            inv = mk(rcp_exact(pt.d.x), rcp_exact(pt.d.y), rcp_exact(pt.d.z));
+            stack[0] = 0u;
+            sp = 1;
+            state = TRAV;
+        }
+
+        // ---- (3) node phase: pop until this lane has a leaf to test or its stack is empty
+        uint32_t first = 0, count = 0;
+        while (state == TRAV && count == 0u) {
+            if (sp == 0) {
+                state = FINISH;
+                break;
+            }
+            sp--;
+            const uint32_t node_idx = stack[sp * kRadBlock];
+            if (node_idx >= node_count) continue;
+            const v4f n0 = nodes[node_idx * 3u], n1 = nodes[node_idx * 3u + 1u], n2f = nodes[node_idx * 3u + 2u];
+            const uint32_t n_left = __float_as_uint(n2f.x), n_right = __float_as_uint(n2f.y),
+                           n_first = __float_as_uint(n2f.z), n_count = __float_as_uint(n2f.w);
+            if (!isect_aabb(pt.o, inv, mk(n0.x, n0.y, n0.z), mk(n1.x, n1.y, n1.z))) continue;
+            if (n_count > 0u) {
+                first = n_first;
+                count = n_count;
+            } else {
+                if (n_left < node_count) {
+                    stack[sp * kRadBlock] = n_left;
+                    sp++;
+                }
+                if (n_right < node_count) {
+                    stack[sp * kRadBlock] = n_right;
+                    sp++;
+                }
+            }
+        }
+
+        // ---- (4) leaf phase: this lane's leaf (shader.wgsl:327-374); candidates are offered in slot order
+        {
+            const uint32_t end = (first + count < p.index_len) ? first + count : p.index_len;  // guard :331
+            for (uint32_t slot = first; slot < end; slot++) {
+                const v4f ta = ptris[slot * 4u], tb = ptris[slot * 4u + 1u], tc = ptris[slot * 4u + 2u];
+                if (__float_as_uint(tc.w) == 0u) continue;  // guard :336
+                test_slot(ta, tb, tc, slot, pt.o, pt.d, th);
+            }
+        }
+
+        // ---- (5) traversal complete: ground, spheres, lights, shading, next ray
+        if (state == FINISH) {
+            const bool alive = segment_finish<false>(p, pt, th, stack, kRadBlock, tl);
+            if (alive) {
+                state = BEGIN;
+            } else {
+                rad_store(a, item, pt.color);
+                state = IDLE;
+            }
+        }
+    }
+}
+
+// ======================================================== k_rad_chunk ====
+// k_trace_chunk's phases 2-5 (rb_kernels.hip): lane = ray down the two-box nodes (chunk_node_step),
+// lane = triangle for the pooled 16-triangle chunks with one LDS atomic min on (t, rank) per hit, segment_finish for the
+// lanes whose walk is complete.  SPHTREE: the instantiation for scenes that also have a sphere tree.
+template <bool SPHTREE>
+__global__ void __launch_bounds__(kRadBlock, RB_RAD_CHUNK_WAVES) k_rad_chunk(const KParams p, const RadArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_stack[];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t lane = tid & 63u;
+    uint32_t* const stack = stack_column(s_stack, tid);
+    Tally<false> tl;
+    // this wave's corner of LDS behind the traversal stacks
+    unsigned char* const wl = reinterpret_cast<unsigned char*>(s_stack + p.stack_depth * kRadBlock) + (tid >> 6) * kChunkWaveLds;
+    lds_v4f* const rayrec = (lds_v4f*)wl;                    // [64][2]: {o, chunk put aside}, {d, chunk stood at}
+    lds_u64* const best = (lds_u64*)(wl + 64u * 32u);        // [64]: (t bits) << 32 | rank
+    lds_u32* const units = (lds_u32*)(wl + 64u * 40u);       // [128]: ray lane (| 64: its second chunk) of every pooled (ray, chunk) pair
+
+    enum : uint32_t { IDLE = 0, BEGIN = 1, TRAV = 2, FINISH = 3 };
+    uint32_t state = IDLE;
+    uint32_t item = 0, cur = 0;
+    uint32_t pend = kChunkNone;   // the chunk this lane has put aside (cur == kChunkNone: nothing else left to walk)
+    RadQueue iq(a, rad_total_items(a));
+    Path pt;
+    pt.depth = 0;
+    f3 inv = mk(0, 0, 0);
+    unsigned long long key = kChunkNoHit;
+    int sp = 0;
+    auto set_aside = [&]() {
+        if (state == TRAV && cur != kChunkNone && (cur & kChunkLeaf) != 0u && pend == kChunkNone) {
+            pend = cur;
+            if (sp == 0) {
+                cur = kChunkNone;
+            } else {
+                sp--;
+                cur = stack[sp * kRadBlock];
+            }
+        }
+    };
+
+    for (;;) {
+        // ---- (1) hand items to idle lanes
+        iq.refill(a, lane, [&] { return state == IDLE; },
+                  [&](uint32_t it, uint32_t ray, uint32_t hs) {
+                      item = it;
+                      if (rad_start(fresh_params(p), a, it, ray, hs, pt)) state = BEGIN;
+                  });
+        if (__ballot(state != IDLE) == 0ull) {
+            if (iq.drained()) break;
+            continue;
+        }
+
+        // ---- (2) start of a segment: the root's own box (shader.wgsl:283-315), then its two children
+        if (state == BEGIN) {
+            const KParams& fp = fresh_params(p);
+            inv = mk(rcp_exact(pt.d.x), rcp_exact(pt.d.y), rcp_exact(pt.d.z));
+            key = kChunkNoHit;
+            sp = 0;
+            const cf4p rn = (cf4p)fp.nodes;
+            const v4f n0 = rn[0], n1 = rn[1];
+            if (isect_aabb(pt.o, inv, mk(n0.x, n0.y, n0.z), mk(n1.x, n1.y, n1.z))) {
+                cur = fp.chunk_root;
+                state = TRAV;
+            } else {
+                state = FINISH;
+            }
+        }
+
+        // ---- (3) tree: a few node steps while enough lanes are at a node
+#pragma unroll 1
+        for (int it = 0; it < RB_CHUNK_NODE_STEPS; ++it) {
+            const bool at_node = state == TRAV && cur != kChunkNone && (cur & kChunkLeaf) == 0u;
+            const uint32_t n = (uint32_t)__popcll(__ballot(at_node));
+            if (n == 0u || (it > 0 && n < (uint32_t)RB_CHUNK_NODE_LANES)) break;
+            if (at_node) {
+                if (!chunk_node_step<false>(p, stack, kRadBlock, pt.o, pt.d, inv, __uint_as_float((uint32_t)(key >> 32)), cur, sp, tl)) {
+                    if (pend != kChunkNone) cur = kChunkNone;   // nothing left to walk, one chunk still to be tested
+                    else state = FINISH;
+                }
+                set_aside();
+            }
+        }
+
+        // ---- (4) leaves: pool the (ray, chunk) pairs of the lanes that hold a chunk, kChunkTris lanes per pair
+        {
+            const bool lf = state == TRAV && cur != kChunkNone && (cur & kChunkLeaf) != 0u;   // waits at a chunk
+            const bool lp = state == TRAV && pend != kChunkNone;                              // holds one aside
+            const unsigned long long m = __ballot(lf), mp = __ballot(lp);
+            const uint32_t n_pend = (uint32_t)__popcll(mp), n_units = n_pend + (uint32_t)__popcll(m);
+            const uint32_t n_node = (uint32_t)__popcll(__ballot(state == TRAV && cur != kChunkNone && !lf));
+            if (n_units != 0u && (n_units >= (uint32_t)RB_CHUNK_LEAF_LANES || n_node == 0u)) {
+                const unsigned long long below = (1ull << lane) - 1ull;
+                if (lp) units[(uint32_t)__popcll(mp & below)] = lane;
+                if (lf) units[n_pend + (uint32_t)__popcll(m & below)] = lane | 64u;
+                if (lf || lp) {
+                    const v4f r0 = {pt.o.x, pt.o.y, pt.o.z, __uint_as_float(pend)}, r1 = {pt.d.x, pt.d.y, pt.d.z, __uint_as_float(cur)};
+                    rayrec[lane * 2u] = r0;
+                    rayrec[lane * 2u + 1u] = r1;
+                    best[lane] = key;
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                const cf4p ca = (cf4p)p.chunk_a, cb = (cf4p)p.chunk_b, cc = (cf4p)p.chunk_c;
+                // one round = four pairs; the next round's ray records and triangle pieces are requested before
+                // this round's are tested
+                constexpr uint32_t kPairsPerRound = 64u / kChunkTris;
+                struct Round {
+                    v4f r0, r1, a, b, c;
+                    uint32_t rl;
+                    bool valid;
+                };
+                auto fetch = [&](uint32_t g0) {
+                    Round r;
+                    const uint32_t g = g0 + lane / kChunkTris;
+                    const bool ok = g < n_units;
+                    const uint32_t e = units[ok ? g : 0u];   // (entry 0 exists: n_units != 0)
+                    r.rl = e & 63u;
+                    r.r0 = rayrec[r.rl * 2u];
+                    r.r1 = rayrec[r.rl * 2u + 1u];
+                    const uint32_t ref = __float_as_uint((e & 64u) ? r.r1.w : r.r0.w), first = ref & 0x03FFFFFFu, cnt = ((ref >> 26) & 31u) + 1u;
+                    const uint32_t j = lane & (kChunkTris - 1u);
+                    r.valid = ok && j < cnt;
+                    const uint32_t pos = first + (j < cnt ? j : 0u);   // (position `first` exists: a chunk holds at least one triangle)
+                    r.a = ca[pos];
+                    r.b = cb[pos];
+                    r.c = cc[pos];
+                    return r;
+                };
+                Round nx = fetch(0u);
+#pragma unroll 1
+                for (uint32_t g0 = 0; g0 < n_units; g0 += kPairsPerRound) {
+                    const Round r = nx;
+                    if (g0 + kPairsPerRound < n_units) nx = fetch(g0 + kPairsPerRound);
+                    float u, v;
+                    const float t = isect_triangle(mk(r.r0.x, r.r0.y, r.r0.z), mk(r.r1.x, r.r1.y, r.r1.z), mk(r.a.x, r.a.y, r.a.z),
+                                                   mk(r.b.x, r.b.y, r.b.z), mk(r.c.x, r.c.y, r.c.z), u, v);
+                    if (r.valid && t > 0.001f) {
+                        const unsigned long long k = ((unsigned long long)__float_as_uint(t) << 32) | __float_as_uint(r.a.w);
+                        __hip_atomic_fetch_min(&best[r.rl], k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                    }
+                }
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                if (lf || lp) {
+                    key = best[lane];
+                    pend = kChunkNone;
+                    if (lf || cur == kChunkNone) {   // the chunk the lane stood at is done, or there was nothing left to walk
+                        if (sp == 0) {
+                            state = FINISH;
+                        } else {
+                            sp--;
+                            cur = stack[sp * kRadBlock];
+                        }
+                    }
+                    set_aside();
+                }
+            }
+        }
+
+        // ---- (5) finished walks: the winner's record, the rest of the segment (shading), next ray
+        {
+            const uint32_t n_fin = (uint32_t)__popcll(__ballot(state == FINISH));
+            const uint32_t n_trav = (uint32_t)__popcll(__ballot(state == TRAV));
+            if (n_fin != 0u && (n_fin >= (uint32_t)RB_RAD_FINISH_LANES || n_trav == 0u) && state == FINISH) {
+                TriHit th;
+                th.hit = key != kChunkNoHit;
+                th.t = 1e20f;
+                th.u = th.v = 0.0f;
+                th.slot = 0u;
+                if (th.hit) {
+                    // (t, u, v) of the winner again from its prepared record: the same operations on the same values
+                    const KParams& fp = fresh_params(p);
+                    th.slot = cptr(fp.chunk_rank_slot)[(uint32_t)key];
+                    const cf4p tp = (cf4p)fp.ptris + (size_t)th.slot * 4u;
+                    const v4f ta = tp[0], tb = tp[1], tc = tp[2];
+                    th.t = isect_triangle(pt.o, pt.d, mk(ta.x, ta.y, ta.z), mk(tb.x, tb.y, tb.z), mk(tc.x, tc.y, tc.z), th.u, th.v);
+                }
+                const bool alive = segment_finish<false, SPHTREE>(p, pt, th, stack, kRadBlock, tl);
+                if (alive) {
+                    state = BEGIN;
+                } else {
+                    rad_store(a, item, pt.color);
+                    state = IDLE;
+                }
+            }
+        }
+    }
+}
+
+// ========================================================== k_rad_sum ====
+// Phase 2, shaped like k_accumulate: one wavefront per block of 64 rays, lane = ray; each sample row is a contiguous 1 KiB
+// read.  The sum starts at +0 and adds the samples in ascending order, one binary32 add per component; the weights (1 per
+// sample of a valid ray, 0 of an invalid one) add up to (float)samples or 0 exactly (samples <= 65536).
+__global__ void __launch_bounds__(256) k_rad_sum(const RadArgs a) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t blk = blockIdx.x * 4u + (threadIdx.x >> 6);
+    const uint32_t ray = blk * 64u + lane;
+    if (ray >= a.n) return;
+    const uint32_t S = a.samples;
+    const nt_f4* __restrict__ c = reinterpret_cast<const nt_f4*>(a.colors) + ((size_t)blk * S) * 64u + lane;
+    f3 acc = mk(0, 0, 0);
+    float w = 0.0f;
+    uint32_t s = 0;
+    for (; s + 8u <= S; s += 8u) {
+        nt_f4 v[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) v[k] = __builtin_nontemporal_load(&c[(size_t)(s + k) * 64u]);
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            acc = acc + mk(v[k].x, v[k].y, v[k].z);
+            w = w + v[k].w;
+        }
+    }
+    for (; s < S; s++) {
+        const nt_f4 v = __builtin_nontemporal_load(&c[(size_t)s * 64u]);
+        acc = acc + mk(v.x, v.y, v.z);
+        w = w + v.w;
+    }
+    const v4f r = {acc.x, acc.y, acc.z, w};
+    reinterpret_cast<v4f*>(a.out)[ray] = r;
+}
+
+}  // namespace
+
+// One piece: a.n rays x a.samples samples, at most RB_TRACE_PIECE_ITEMS items (the caller cuts; a.colors holds them all).
+// Queue word, trace kernel and sum are queued on `stream`; nothing is waited for.
+int launch_radiance(const KParams& p_, const RadArgs& a_, void* stream_, LaunchInfo* info) {
+    KParams p = p_;
+    p.cam = host_cam(p.u);
+    RadArgs a = a_;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    LaunchInfo li{};
+    li.block = kRadBlock;
+    if (a.n == 0u) return 0;
+    const uint64_t blocks64 = ((uint64_t)a.n + 63u) / 64u;
+    const uint64_t items = blocks64 * 64u * a.samples;
+    if (a.rays == nullptr || a.out == nullptr || a.colors == nullptr || a.queue == nullptr || a.samples == 0u || items > RB_TRACE_PIECE_ITEMS)
+        return (int)hipErrorInvalidValue;
+    // the walk, by launch_query's rule
+    enum Variant { PLAIN, BVH, CHUNK };
+    const bool multi = p.u.bvh_node_count > 1u && !p.no_leaf_stepping;
+    Variant v = PLAIN;
+    if (multi && p.chunk_nodes != nullptr) v = CHUNK;
+    else {
+        p.fast_nodes = nullptr;   // own-tree engines: the reference walk over the caller's tree, as k_query_bvh answers them
+        if (p.u.bvh_node_count > 1u || p.sph_nodes != nullptr) v = BVH;
+    }
+    static const char* const names[] = {"k_rad", "k_rad_bvh", "k_rad_chunk"};
+    li.kernel_name = names[v];
+    li.lds_bytes = (size_t)kStackEntryBytes * p.stack_depth * kRadBlock + (v == CHUNK ? (kRadBlock / 64u) * kChunkWaveLds : 0u);
+    // the grid as launch_render sizes it: residency by registers, fewer blocks for a launch of few items
+    const uint32_t max_blocks8 = stream_kernel_max_threads(8u) / 256u;   // 8 blocks per CU
+    const uint32_t dense = (items >= (uint64_t)max_blocks8 * 4u * 1024u) ? 8u : 4u;
+    const uint32_t blocks_per_cu = p.blocks_per_cu ? p.blocks_per_cu : v == CHUNK ? (uint32_t)RB_RAD_CHUNK_WAVES : dense;
+    uint64_t grid = (uint64_t)(max_blocks8 / 8u) * blocks_per_cu;
+    const uint64_t needed = (items + kRadBlock - 1u) / kRadBlock;
+    if (needed < grid) grid = needed;
+    li.grid = (uint32_t)grid;
+    const uint64_t waves = grid * (kRadBlock / 64u);
+    // reservations as launch_render makes them: about 8 (the plain kernel) or 64 per wave, whole 64-item rows
+    uint64_t batch = items / (waves * (v == PLAIN ? 8u : 64u));
+    batch = (batch / 64u) * 64u;
+    if (batch < 64u) batch = 64u;
+    if (batch > (v == PLAIN ? 512u : 4096u)) batch = (v == PLAIN ? 512u : 4096u);
+    if (p.queue_batch) batch = p.queue_batch;
+    a.batch = (uint32_t)batch;
+    a.magic_S = a.samples > 1u ? (uint32_t)((1ull << 32) / a.samples) : 0xFFFFFFFFu;
+    // the queue starts behind the waves' own first reservations
+    hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(a.queue), (int)(uint32_t)(waves * batch), 1, stream);
+    if (e != hipSuccess) return (int)e;
+    const dim3 g(li.grid), b(li.block);
+    switch (v) {
+        case PLAIN: hipLaunchKernelGGL(k_rad, g, b, li.lds_bytes, stream, p, a); break;
+        case BVH: hipLaunchKernelGGL(k_rad_bvh, g, b, li.lds_bytes, stream, p, a); break;
+        case CHUNK:
+            if (p.sph_nodes != nullptr) hipLaunchKernelGGL(k_rad_chunk<true>, g, b, li.lds_bytes, stream, p, a);
+            else hipLaunchKernelGGL(k_rad_chunk<false>, g, b, li.lds_bytes, stream, p, a);
+            break;
+    }
+    e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(k_rad_sum, dim3((uint32_t)((blocks64 + 3u) / 4u)), dim3(256), 0, stream, a);
+    if (info) *info = li;
+    return (int)hipGetLastError();
+}
+
+}  // namespace rb

@@ -1100,6 +1100,87 @@ int cast_rays_device_locked(rb_engine* e, const rb_ray* d_rays, size_t n, rb_hit
     });
 }
 
+// ---- path-traced radiance along given rays (rb_abi.h)
+// rays per piece: whole blocks of 64 rays, never a part of one ray's samples (samples <= 65536: at least one block)
+size_t trace_piece_rays(uint32_t samples) { return std::max<size_t>((RB_TRACE_PIECE_ITEMS / samples) & ~size_t(63), 64); }
+
+// the scratch of one piece: colours and the queue word
+int trace_scratch(rb_engine* e, size_t piece, uint32_t samples) {
+    HIP_TRY(e, e->rad_colors.reserve(((piece + 63) / 64) * 64 * samples * 4));
+    HIP_TRY(e, e->rad_queue.reserve(16));
+    return RB_OK;
+}
+
+rb::RadArgs trace_args(rb_engine* e, const rb_ray* rays, const uint32_t* seeds, rb_radiance* out, size_t done, size_t m,
+                       uint32_t first_sample, uint32_t samples) {
+    rb::RadArgs a{};
+    a.rays = rays;
+    a.seeds = seeds;
+    a.colors = e->rad_colors.ptr;
+    a.out = out;
+    a.queue = e->rad_queue.ptr;
+    a.n = static_cast<uint32_t>(m);
+    a.seed_base = static_cast<uint32_t>(done);
+    a.first_sample = first_sample;
+    a.samples = samples;
+    return a;
+}
+
+int trace_rays_locked(rb_engine* e, const rb_ray* rays, const uint32_t* seeds, size_t n, uint32_t first_sample, uint32_t samples,
+                      rb_radiance* out) {
+    rb::KParams p{};
+    int rc = query_params(e, &p);
+    e->last_query_ms = 0.0f;
+    if (rc || n == 0) return rc;
+    const size_t piece = std::min(n, trace_piece_rays(samples));
+    rc = trace_scratch(e, piece, samples);
+    if (rc) return rc;
+    HIP_TRY(e, e->q_rays.reserve(piece));
+    if (seeds) HIP_TRY(e, e->rad_seeds.reserve(piece));
+    HIP_TRY(e, e->rad_out.reserve(piece));
+    const bool pinned = page_locked(out);
+    for (size_t done = 0; done < n; done += piece) {
+        const size_t m = std::min(piece, n - done);
+        HIP_TRY(e, hipMemcpyAsync(e->q_rays.ptr, rays + done, m * sizeof(rb_ray), hipMemcpyHostToDevice, e->stream));
+        if (seeds) HIP_TRY(e, hipMemcpyAsync(e->rad_seeds.ptr, seeds + done, m * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+        const rb::RadArgs a = trace_args(e, e->q_rays.ptr, seeds ? e->rad_seeds.ptr : nullptr, e->rad_out.ptr, done, m, first_sample, samples);
+        rb::LaunchInfo li{};
+        HIP_TRY(e, hipEventRecord(e->ev_q[0], e->stream));
+        const int st = rb::launch_radiance(p, a, e->stream, &li);
+        if (st) return rb::fail(e, RB_ERR_DEVICE, "radiance kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
+        HIP_TRY(e, hipEventRecord(e->ev_q[1], e->stream));
+        if (li.kernel_name) e->last_query_kernel_name = li.kernel_name;
+        rc = query_copy_out(e, out + done, e->rad_out.ptr, m * sizeof(rb_radiance), pinned);
+        if (rc) return rc;
+        HIP_TRY(e, hipStreamSynchronize(e->stream));   // the scratch is the next piece's
+        float ms = 0.0f;
+        HIP_TRY(e, hipEventElapsedTime(&ms, e->ev_q[0], e->ev_q[1]));
+        e->last_query_ms += ms;
+    }
+    return RB_OK;
+}
+
+// every piece queued between the query's two events on the caller's buffers (the pieces share the colour scratch in stream
+// order); nothing is waited for
+int trace_rays_device_locked(rb_engine* e, const rb_ray* d_rays, const uint32_t* d_seeds, size_t n, uint32_t first_sample,
+                             uint32_t samples, rb_radiance* d_out) {
+    int rc = device_range(e, d_rays, n * sizeof(rb_ray), 16, "d_rays");
+    if (!rc && d_seeds) rc = device_range(e, d_seeds, n * sizeof(uint32_t), 4, "d_seeds");
+    if (!rc) rc = device_range(e, d_out, n * sizeof(rb_radiance), 16, "d_out");
+    if (rc) return rc;
+    const size_t piece = std::min(n, trace_piece_rays(samples));
+    return device_query_locked(e, [&](const rb::KParams& p, rb::LaunchInfo* li) {
+        if (trace_scratch(e, piece, samples)) return static_cast<int>(hipErrorOutOfMemory);
+        for (size_t done = 0; done < n; done += piece) {
+            const size_t m = std::min(piece, n - done);
+            const rb::RadArgs a = trace_args(e, d_rays + done, d_seeds ? d_seeds + done : nullptr, d_out + done, done, m, first_sample, samples);
+            const int st = rb::launch_radiance(p, a, e->stream, li);
+            if (st) return st;
+        }
+        return 0;
+    });
+}
+
 // ---- the denoiser (rb_abi.h).  Like a query it is queued on the engine's stream behind whatever runs
 // there, reads the scene and the committed accumulation, and writes buffers of its own.
 rb::GuidePlanes guide_planes(rb_engine* e) { return rb::GuidePlanes{e->dn_nt.ptr, e->dn_pc.ptr, e->dn_al.ptr}; }
@@ -1818,6 +1899,35 @@ int rb_cast_rays_device(rb_engine* e, const rb_ray* d_rays, size_t n, rb_hit* d_
     rb_engine* const t = answering(e);
     if (n == 0) return answered(e, t, require_ready(t));
     return answered(e, t, cast_rays_device_locked(t, d_rays, n, d_hits, d_surf));
+}
+
+// the refusals the two forms of rb_trace_rays share; before any launch
+static int trace_rays_check(rb_engine* e, const char* who, const void* rays, size_t n, uint32_t first_sample, uint32_t samples, const void* out) {
+    if (samples == 0 || samples > 65536u) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s takes 1 .. 65536 samples per ray, not %u", who, samples);
+    if (static_cast<uint64_t>(first_sample) + samples > 0xFFFFFFFFull)
+        return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: first_sample + samples = %u + %u does not fit 32 bits", who, first_sample, samples);
+    if (n > 0x7FFFFFFFull - 63ull) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s takes at most 2^31 - 64 rays per call", who);
+    if (n > 0 && (!rays || !out)) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: rays / out is NULL", who);
+    return RB_OK;
+}
+
+int rb_trace_rays(rb_engine* e, const rb_ray* rays, const uint32_t* seeds, size_t n, uint32_t first_sample, uint32_t samples,
+                  rb_radiance* out) {
+    if (!e) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (const int rc = trace_rays_check(e, "rb_trace_rays", rays, n, first_sample, samples, out)) return rc;
+    rb_engine* const t = answering(e);
+    return answered(e, t, trace_rays_locked(t, rays, seeds, n, first_sample, samples, out));
+}
+
+int rb_trace_rays_device(rb_engine* e, const rb_ray* d_rays, const uint32_t* d_seeds, size_t n, uint32_t first_sample,
+                         uint32_t samples, rb_radiance* d_out) {
+    if (!e) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (const int rc = trace_rays_check(e, "rb_trace_rays_device", d_rays, n, first_sample, samples, d_out)) return rc;
+    rb_engine* const t = answering(e);
+    if (n == 0) return answered(e, t, require_ready(t));
+    return answered(e, t, trace_rays_device_locked(t, d_rays, d_seeds, n, first_sample, samples, d_out));
 }
 
 int rb_denoise_default_params(rb_denoise_params* p) {

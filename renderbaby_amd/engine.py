@@ -493,6 +493,48 @@ class Engine:
                                           n, int(mask), res.ctypes.data if n else None))
         return res
 
+    # ---- path-traced radiance along given rays (rb_abi.h)
+    def trace_rays(self, origins, dirs, seeds=None, samples=1, first_sample=0, out=None):
+        """rb_trace_rays: the radiance trace_ray returns along each ray, summed over ``samples`` samples in sample order.
+        (n, 3) origins and directions (any length: the device normalises), ``seeds`` n uint32 ids or None (the ray's index)
+        -> abi.RADIANCE[n] (``sum``, ``weight`` = samples; an invalid ray: zeros).  Torch tensors on the engine's device go
+        to rb_trace_rays_device and an (n, 4) float32 tensor on the device comes back."""
+        return self.trace_ray_records(self._ray_records(origins, dirs), seeds, samples, first_sample, out)
+
+    def trace_ray_records(self, rays, seeds=None, samples=1, first_sample=0, out=None):
+        """rb_trace_rays on an abi.RAY array, or rb_trace_rays_device on a float32 tensor of shape (n, 8) (``seeds``: an int32
+        or uint32 tensor of n elements, its bits are the ids; ``out``: a float32 tensor of shape (n, 4))."""
+        samples, first_sample = int(samples), int(first_sample)
+        if not (0 <= samples < 2 ** 32 and 0 <= first_sample < 2 ** 32):
+            raise ValueError("samples and first_sample are 32-bit unsigned numbers")
+        if _is_tensor(rays) or _is_tensor(seeds) or _is_tensor(out):
+            import torch
+            rp, n = self._device_tensor(rays, torch.float32, 8, "rays")
+            sp, ns = (None, n)
+            if seeds is not None:   # 32-bit ids, signed or unsigned: the bits are what counts
+                unsigned = _is_tensor(seeds) and seeds.dtype == getattr(torch, "uint32", None)
+                sp, ns = self._device_tensor(seeds, torch.uint32 if unsigned else torch.int32, None, "seeds")
+            res = torch.empty((n, 4), dtype=torch.float32, device=rays.device) if out is None else out
+            op, no = self._device_tensor(res, torch.float32, 4, "out")
+            if ns != n or no != n:
+                raise ValueError("rays, seeds and out differ in length")
+            self._device_call(self._lib.rb_trace_rays_device, rp, sp, n, first_sample, samples, op)
+            return res
+        if not isinstance(rays, np.ndarray):
+            raise ValueError("rays: an abi.RAY array or a float32 tensor of shape (n, 8) is needed")
+        rays = np.ascontiguousarray(rays, dtype=abi.RAY)
+        n = len(rays)
+        if seeds is not None:
+            seeds = np.ascontiguousarray(seeds, dtype=np.uint32).reshape(-1)
+            if len(seeds) != n:
+                raise ValueError("rays and seeds differ in length")
+        res = np.empty(n, dtype=abi.RADIANCE) if out is None else out
+        if not isinstance(res, np.ndarray) or res.dtype != abi.RADIANCE or res.shape != (n,) or not res.flags.c_contiguous:
+            raise ValueError("out: a contiguous abi.RADIANCE array of n elements is needed")
+        self._check(self._lib.rb_trace_rays(self._h, rays.ctypes.data if n else None, seeds.ctypes.data if (seeds is not None and n) else None,
+                                            n, first_sample, samples, res.ctypes.data if n else None))
+        return res
+
     def render_hits(self, surfaces=False):
         """rb_render_hits: the first hit of every pixel centre as abi.HIT[rows, width] (and abi.SURFACE with ``surfaces``) in
         the orientation of the delivered frame; a sharded engine: its padded local rows, like read_accumulation."""

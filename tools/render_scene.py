@@ -4,6 +4,8 @@
                                  [--width W --height H] [--included-root DIR] [--every N]
                                  [--aov depth,normal,albedo,emission,id,ao] [--ao-radius R]
                                  [--denoise [--denoise-iterations N]]
+                                 [--camera equirect|ortho|thin-lens [--ortho-width W] [--aperture A --focus-distance F]]
+                                 [--probe x,y,z [--probe-normal x,y,z]]
 
 scene file -> scene_io.load_scene (the importer's and the Scene->RenderConfig adapter's rules) ->
 RenderConfig -> librenderbaby_hip.so -> Frame -> PNG.  With --every N the progressive iterator is used
@@ -11,11 +13,14 @@ and a frame is written every N samples (out_0001.png, ...).  --aov writes the fi
 (Engine.render_hits -> renderbaby_amd.aov) next to the frame as out.<name>.png; `ao` is ambient occlusion over those hits
 (aov.ambient_occlusion: 16 directions per hit, one any-hit query).  --denoise writes the frame through the edge-avoiding
 a-trous filter (Engine.denoise) as out.denoised.png -- with --every, every delivered frame next to the raw
-one (out_0001.denoised.png, ...).
+one (out_0001.denoised.png, ...).  --camera renders the scene a second time through a camera the scene file cannot express, at
+the scene camera's position and direction (bake.camera_rays -> bake.render_rays: Engine.trace_rays on one ray per pixel, spp
+samples each), as out.<camera>.png.  --probe prints the mean radiance over the cosine-weighted hemisphere at a point
+(bake.irradiance, spp rays; normal +y unless --probe-normal says otherwise).
 """
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from renderbaby_amd import Engine, Frame, RenderConfig, aov, denoise, scene_io  # noqa: E402
+from renderbaby_amd import Engine, Frame, RenderConfig, aov, bake, denoise, scene_io  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("scene"); ap.add_argument("png")
@@ -28,6 +33,11 @@ ap.add_argument("--aov", default="", help="comma-separated first-hit buffers to 
 ap.add_argument("--ao-radius", type=float, default=1.0, help="how far an occluder may be for --aov ao")
 ap.add_argument("--denoise", action="store_true", help="also write every frame filtered, as <name>.denoised.png")
 ap.add_argument("--denoise-iterations", type=int, default=None, help="a-trous iterations, 0..8 (default: the library's)")
+ap.add_argument("--camera", choices=["equirect", "ortho", "thin-lens"], default=None, help="also write out.<camera>.png through bake.render_rays")
+ap.add_argument("--ortho-width", type=float, default=10.0); ap.add_argument("--aperture", type=float, default=0.1)
+ap.add_argument("--focus-distance", type=float, default=5.0)
+ap.add_argument("--probe", default=None, help="x,y,z: print the mean radiance arriving at this point (bake.irradiance)")
+ap.add_argument("--probe-normal", default="0,1,0")
 a = ap.parse_args()
 aovs = [n for n in a.aov.split(",") if n]
 for n in aovs:
@@ -79,4 +89,17 @@ if aovs:
         img = aov.ao_u8(aov.ambient_occlusion(eng, hits, radius=a.ao_radius)) if n == "ao" else aov.image(n, hits, surf)
         scene_io.export_png(f"{base}.{n}{ext}", Frame(img.shape[1], img.shape[0], img))
     print(f"first-hit buffers with {eng.last_query_kernel_name()} in {eng.last_query_ms():.3f} ms: {', '.join(aovs)}")
+if a.camera:
+    kind = a.camera.replace("-", "_")
+    cam = s.uniforms["camera"][0]
+    O, D = bake.camera_rays(kind, s.width, s.height, cam["pos"], dir=cam["dir"], ortho_width=a.ortho_width, aperture=a.aperture,
+                            focus_distance=a.focus_distance)
+    img = bake.render_rays(eng, O, D, min(max(s.total_samples, 1), 65536))
+    base, ext = os.path.splitext(a.png)
+    scene_io.export_png(f"{base}.{kind}{ext}", Frame(img.shape[1], img.shape[0], img))
+    print(f"{a.camera} camera with {eng.last_query_kernel_name()} in {eng.last_query_ms():.3f} ms -> {base}.{kind}{ext}")
+if a.probe:
+    point, normal = [[float(v) for v in t.split(",")] for t in (a.probe, a.probe_normal)]
+    rgb = bake.irradiance(eng, [point], [normal], max(s.total_samples, 1))[0]
+    print(f"probe at {tuple(point)}, normal {tuple(normal)}, {max(s.total_samples, 1)} rays: mean radiance {rgb[0]:.6g} {rgb[1]:.6g} {rgb[2]:.6g}")
 eng.close()
