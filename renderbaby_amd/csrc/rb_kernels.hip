@@ -540,10 +540,11 @@ DEV void trace_body(const KParams& p, v4f* s_ring) {
             idle = __ballot(!active) & ~0ull;
             if (taken == n_idle) break;  // everyone who asked was served (or got a padding item)
         }
-        if (__ballot(active) == 0ull) {
-            if (exhausted && loc_next == loc_end) break;
-            continue;
-        }
+        // The segment below is the loop's only join.  With no lane active it is skipped as a whole, so there is no `continue`
+        // in front of it: that edge met the end of `if (active)` in a block that branched again, the path state was kept in
+        // two sets of registers around it, and every exit of a segment copied the whole state from one to the other
+        // (53 v_mov_b32 per iteration; profiles/r12_ktrace_moves_before.txt).
+        if (__ballot(active) == 0ull && exhausted && loc_next == loc_end) break;
         if (active) {
             const bool alive = segment<STATS, MULTI>(p, pt, &s_stack[tid], kTraceBlock, tl);
             if (!alive) {
