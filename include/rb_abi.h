@@ -624,8 +624,9 @@ int rb_trace_rays_device(rb_engine* e, const rb_ray* d_rays, const uint32_t* d_s
 /* ---- Edge-avoiding denoiser over the first-hit buffers (no reference counterpart).  An a-trous wavelet
  * filter (Dammertz et al. 2010) on the albedo-demodulated mean radiance, guided by the first hit of every pixel-centre ray.
  * Section 13 is the normative definition: every step one IEEE binary32 operation in a fixed order, so that the device's result
- * equals the numpy model renderbaby_amd/denoise.py bit for bit.  All buffers are in the orientation of the delivered frame
- * (row-major, top row first, x mirrored). */
+ * equals the numpy model renderbaby_amd/denoise.py bit for bit.  The one exception: a NaN the filter itself generates (0 * inf,
+ * inf - inf, 0 / 0, inf / inf) has unspecified sign and payload; everything else, including which words are NaN, is as written.
+ * All buffers are in the orientation of the delivered frame (row-major, top row first, x mirrored). */
 typedef struct rb_guide {                                                                           /* 48 B */
     float normal[3];    /* the first hit's rb_hit.normal, unchanged */
     float t;            /* its rb_hit.t */
