@@ -621,6 +621,69 @@ int rb_trace_rays(rb_engine* e, const rb_ray* rays, const uint32_t* seeds, size_
 int rb_trace_rays_device(rb_engine* e, const rb_ray* d_rays, const uint32_t* d_seeds, size_t n, uint32_t first_sample,
                          uint32_t samples, rb_radiance* d_out);
 
+/* ---- Camera rays made on the device (the normative definition; no reference counterpart).  A device stage
+ * makes the ray of every (pixel, sample) item from the item's own random stream -- sub-pixel jitter, a fresh lens point per
+ * sample -- and the kernels of rb_trace_rays trace it.  Every step is one IEEE binary32 operation in the order written, no
+ * contraction, / and sqrt correctly rounded: the numpy model renderbaby_amd/camera.py equals the device bit for bit.
+ * Pixel p = row * width + col, row 0 on top, column 0 on the left as the viewer sees it (no x mirror).  For pixel p and
+ * sample k of `samples`:
+ *   seed   = pcg(p + pcg(first_sample + k)), u32 wrap-around;
+ *   jx, jy = random_float(&seed) - 0.5, twice; both always drawn, under RB_CAM_NO_JITTER both replaced by +0 after the draw;
+ *   sx     = ((((float)col + 0.5f) + jx) / (float)width) * 2.0f - 1.0f;
+ *   sy     = 1.0f - ((((float)row + 0.5f) + jy) / (float)height) * 2.0f;
+ *   PERSPECTIVE  a = tan_half_fov * ((float)width / (float)height);  d0 = ((sx a) right + (sy tan_half_fov) up) + forward;
+ *                lens_radius == 0: origin pos, direction d0, no further draw.  Otherwise lx = random_float 2 - 1, ly likewise,
+ *                drawn again until lx lx + ly ly < 1;  o = (pos + (lens_radius lx) right) + (lens_radius ly) up;
+ *                f = pos + focus_distance d0 (a focal PLANE: d0's forward part is 1);  direction f - o;
+ *   ORTHO        o = (pos + (sx half_width) right) + (sy half_height) up;  direction forward;
+ *   EQUIRECT     origin pos; (sin, cos) of longitude pi sx and latitude (pi / 2) sy from sincos_turn(sx) and
+ *                sincos_turn(0.5f sy), the fixed polynomial routine of section 15.3 (within 2^-22 of the true values);
+ *                d = ((cl sin lon) right + (sin lat) up) + (cl cos lon) forward, cl = cos lat;
+ *   the direction is normalised as rb_cast_rays does it and the ray is invalid by rb_cast_rays' rule;
+ *   c(p,k) = trace_ray(scene, o, d, seed) with the seed as the generator's draws left it;
+ *   out[p - first_pixel] = {sum r, sum g, sum b, w}: from +0.0f in ascending k; w counts the valid samples; an invalid sample
+ *   adds {0, 0, 0} with weight 0; max_depth == 0 gives {0, 0, 0, w}.
+ * right, up and forward are used as given (the caller builds the basis).  The side effects are a query's.  The result does not
+ * depend on the piece size, the launch shape or the form of the call. */
+enum { RB_CAM_PERSPECTIVE = 1, RB_CAM_ORTHO = 2, RB_CAM_EQUIRECT = 3 };
+enum { RB_CAM_NO_JITTER = 1u };
+typedef struct rb_camera_ex {                                                                       /* 96 B */
+    uint32_t kind, width, height, flags;
+    float pos[3];     float tan_half_fov;    /* PERSPECTIVE: tan(fov_y / 2), made by the caller */
+    float right[3];   float half_width;      /* ORTHO: half the window's width ... */
+    float up[3];      float half_height;     /* ... and height */
+    float forward[3]; float lens_radius;     /* PERSPECTIVE: 0 = pinhole */
+    float focus_distance;                    /* PERSPECTIVE with a lens: distance of the focal plane along forward */
+    uint32_t _reserved[3];                   /* must be 0 */
+} rb_camera_ex;
+/* (pixel, sample) items per launch of rb_trace_camera: 32 B of ray record and 16 B of colour each, 384 MiB of scratch */
+#define RB_CAMERA_PIECE_ITEMS (1u << 23)
+/* The generator alone, no engine, on `device` (-1 = current): rays_out / seeds_out[(p - first_pixel) * samples + k] in host
+ * memory; rays_out[i].dir is normalised, an invalid ray has dir {0, 0, 0}; seeds_out[i] is the seed trace_ray starts with.
+ * RB_ERR_INVALID_OPTIONS, before any device is touched: an unknown kind or flag bit; width or height 0 or above 2^24;
+ * width * height >= 2^31; a pixel range that leaves the image; samples 0 or above 65536; first_sample + samples beyond
+ * 2^32 - 1; n_pixels * samples above 2^31 - 64; a non-finite field; tan_half_fov <= 0, lens_radius < 0, focus_distance <= 0
+ * with a lens (PERSPECTIVE); half_width or half_height <= 0 (ORTHO); non-zero _reserved.  NULL cam, rays_out or seeds_out with
+ * n_pixels > 0: RB_ERR_NULL_ARGUMENT.  n_pixels == 0 is RB_OK. */
+int rb_camera_rays(int32_t device, const rb_camera_ex* cam, uint64_t first_pixel, size_t n_pixels, uint32_t first_sample,
+                   uint32_t samples, rb_ray* rays_out, uint32_t* seeds_out);
+/* Radiance through the camera: out[n_pixels] in host memory (pageable or page-locked), pixels [first_pixel, first_pixel +
+ * n_pixels) -- a tile or a region of the image.  Refusals as rb_camera_rays (NULL cam or out with n_pixels > 0:
+ * RB_ERR_NULL_ARGUMENT); a refused call leaves the engine as it was.  Pieces of at most RB_CAMERA_PIECE_ITEMS items, whole
+ * blocks of 64 pixels, never a part of one pixel's samples.  Sharded engines and multi-device handles as rb_trace_rays.
+ * rb_last_query_kernel_name reports "k_cam", "k_cam_bvh" or "k_cam_chunk" -- the walk by rb_cast_rays' rule --,
+ * rb_last_query_ms the generator, the trace and the sum together. */
+int rb_trace_camera(rb_engine* e, const rb_camera_ex* cam, uint64_t first_pixel, size_t n_pixels, uint32_t first_sample,
+                    uint32_t samples, rb_radiance* out);
+/* The same with d_out in device memory of the engine's device, validated as rb_trace_rays_device validates its d_out; queued
+ * on the engine's stream, returns without waiting: rb_sync is the wait. */
+int rb_trace_camera_device(rb_engine* e, const rb_camera_ex* cam, uint64_t first_pixel, size_t n_pixels, uint32_t first_sample,
+                           uint32_t samples, rb_radiance* d_out);
+/* Measurement aid for tools/camera_rate.py (it may change or go): the share of k_cam_rays in the kernel time of the most recent
+ * rb_trace_camera / rb_trace_camera_device, HIP events around the generator's launches, summed over the pieces, ms.  It waits
+ * for the launches it reports. */
+int rb_last_camera_rays_ms(rb_engine* e, float* ms);
+
 /* ---- Edge-avoiding denoiser over the first-hit buffers (no reference counterpart).  An a-trous wavelet
  * filter (Dammertz et al. 2010) on the albedo-demodulated mean radiance, guided by the first hit of every pixel-centre ray.
  * Section 13 is the normative definition: every step one IEEE binary32 operation in a fixed order, so that the device's result
@@ -725,6 +788,10 @@ static_assert(offsetof(rb_surface, emissive) == 16, "emissive @16");
 static_assert(offsetof(rb_surface, texture_index) == 28, "texture_index @28");
 static_assert(offsetof(rb_surface, uv) == 32, "uv @32");
 static_assert(sizeof(rb_radiance) == 16, "rb_radiance is 16 B");
+static_assert(sizeof(rb_camera_ex) == 96, "rb_camera_ex is 96 B");
+static_assert(offsetof(rb_camera_ex, pos) == 16, "pos @16");
+static_assert(offsetof(rb_camera_ex, forward) == 64, "forward @64");
+static_assert(offsetof(rb_camera_ex, focus_distance) == 80, "focus_distance @80");
 static_assert(sizeof(rb_guide) == 48, "rb_guide is 48 B");
 static_assert(sizeof(rb_denoise_params) == 32, "rb_denoise_params is 32 B");
 static_assert(offsetof(rb_guide, t) == 12, "t @12");
@@ -748,6 +815,7 @@ _Static_assert(sizeof(rb_ray) == 32, "rb_ray is 32 B");
 _Static_assert(sizeof(rb_hit) == 48, "rb_hit is 48 B");
 _Static_assert(sizeof(rb_surface) == 48, "rb_surface is 48 B");
 _Static_assert(sizeof(rb_radiance) == 16, "rb_radiance is 16 B");
+_Static_assert(sizeof(rb_camera_ex) == 96, "rb_camera_ex is 96 B");
 _Static_assert(sizeof(rb_guide) == 48, "rb_guide is 48 B");
 _Static_assert(sizeof(rb_denoise_params) == 32, "rb_denoise_params is 32 B");
 #endif

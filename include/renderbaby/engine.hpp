@@ -223,6 +223,20 @@ class Engine final : public Renderer {
                            uint32_t first_sample = 0) {
         check(h_->e, rb_trace_rays_device(h_->e, d_rays, d_seeds, n, first_sample, samples, d_out));
     }
+    // ---- camera rays made on the device (extension; rb_abi.h): per pixel of [first_pixel, first_pixel +
+    // n_pixels) the ordered sum over `samples` rays, each made from its own random stream; n_pixels = 0: the whole image
+    std::vector<rb_radiance> trace_camera(const rb_camera_ex& cam, uint32_t samples, uint32_t first_sample = 0, uint64_t first_pixel = 0,
+                                          size_t n_pixels = 0) {
+        if (n_pixels == 0 && first_pixel == 0) n_pixels = static_cast<size_t>(cam.width) * cam.height;
+        std::vector<rb_radiance> out(n_pixels);
+        check(h_->e, rb_trace_camera(h_->e, &cam, first_pixel, n_pixels, first_sample, samples, out.data()));
+        return out;
+    }
+    // the same into the engine's device memory: queued on the engine's stream, not waited for -- sync() waits
+    void trace_camera_device(const rb_camera_ex& cam, uint64_t first_pixel, size_t n_pixels, rb_radiance* d_out, uint32_t samples,
+                             uint32_t first_sample = 0) {
+        check(h_->e, rb_trace_camera_device(h_->e, &cam, first_pixel, n_pixels, first_sample, samples, d_out));
+    }
     void sync() { check(h_->e, rb_sync(h_->e)); }
     // ---- the denoiser (rb_abi.h): the a-trous filter over the committed accumulation
     static rb_denoise_params denoise_defaults() {

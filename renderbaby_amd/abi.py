@@ -52,6 +52,14 @@ NO_INDEX = 0xFFFFFFFF
 # path-traced radiance along given rays (rb_trace_rays): the per-ray sum and the items of one launch
 RADIANCE = np.dtype([("sum", f4, (3,)), ("weight", f4)])
 TRACE_PIECE_ITEMS = 1 << 24
+# camera rays made on the device (rb_camera_rays / rb_trace_camera): the camera record, kinds and flags
+CAMERA_EX = np.dtype([("kind", u4), ("width", u4), ("height", u4), ("flags", u4),
+                      ("pos", f4, (3,)), ("tan_half_fov", f4), ("right", f4, (3,)), ("half_width", f4),
+                      ("up", f4, (3,)), ("half_height", f4), ("forward", f4, (3,)), ("lens_radius", f4),
+                      ("focus_distance", f4), ("_reserved", u4, (3,))])
+CAM_PERSPECTIVE, CAM_ORTHO, CAM_EQUIRECT = 1, 2, 3
+CAM_NO_JITTER = 1
+CAMERA_PIECE_ITEMS = 1 << 23
 # any-hit occlusion (rb_occluded): result bytes and stage masks
 OCCL_VISIBLE, OCCL_OCCLUDED, OCCL_INVALID = 0, 1, 255
 MASK_GROUND, MASK_TRIANGLES, MASK_SPHERES, MASK_LIGHTS, MASK_ALL = 1, 2, 4, 8, 15
@@ -64,7 +72,7 @@ SIZES = {"camera": (CAMERA, 48), "uniforms": (UNIFORMS, 144), "material": (MATER
          "sphere": (SPHERE, 96), "point_light": (POINT_LIGHT, 96), "mesh": (MESH, 96),
          "bvh_node": (BVH_NODE, 48), "gpu_triangle": (GPU_TRIANGLE, 64),
          "ray": (RAY, 32), "hit": (HIT, 48), "surface": (SURFACE, 48),
-         "guide": (GUIDE, 48), "denoise_params": (DENOISE_PARAMS, 32)}
+         "guide": (GUIDE, 48), "denoise_params": (DENOISE_PARAMS, 32), "camera_ex": (CAMERA_EX, 96)}
 for _n, (_dt, _sz) in SIZES.items():
     assert _dt.itemsize == _sz, (_n, _dt.itemsize, _sz)
 

@@ -4,10 +4,12 @@
 ``irradiance``   mean radiance over cosine-weighted directions about a normal: lightmap texels, vertices, probes
 ``camera_rays``  the rays of cameras the reference's Camera struct cannot express: equirect, ortho, thin_lens
 ``render_rays``  rays -> tone-mapped RGBA8 pixels, the reference's colour mapping applied to sum / weight
+``render_camera``  an abi.CAMERA_EX camera (camera.make) -> RGBA8 pixels, every sample's ray made on the device with jitter and
+                 a lens point of its own (Engine.trace_camera, rb_trace_camera)
 """
 import numpy as np
 
-from . import aov
+from . import abi, aov
 
 f32 = np.float32
 KINDS = ("equirect", "ortho", "thin_lens")
@@ -112,3 +114,12 @@ def render_rays(engine, origins, dirs, samples, first_sample=0):
     o = np.asarray(origins, f32)
     rad = engine.trace_rays(o.reshape(-1, 3), np.asarray(dirs, f32).reshape(-1, 3), samples=samples, first_sample=first_sample)
     return tone_map(rad.reshape(o.shape[:-1]))
+
+
+def render_camera(engine, cam, samples, first_sample=0):
+    """The image of an abi.CAMERA_EX camera: uint8 (height, width, 4), row 0 on top, column 0 on the left.  Unlike
+    ``camera_rays`` + ``render_rays``, which trace one fixed ray per pixel ``samples`` times, every sample has a ray of its own:
+    edges are anti-aliased and a thin lens blurs what is off its focal plane."""
+    c = np.asarray(cam, dtype=abi.CAMERA_EX).reshape(())
+    rad = engine.trace_camera(c, samples, first_sample=first_sample)
+    return tone_map(rad.reshape(int(c["height"]), int(c["width"])))

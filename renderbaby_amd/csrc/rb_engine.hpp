@@ -175,6 +175,8 @@ struct rb_engine {
     rb::DevBuf<uint32_t> rad_seeds, rad_queue;
     rb::DevBuf<rb_radiance> rad_out;
     hipEvent_t ev_q[2] = {nullptr, nullptr};
+    std::vector<hipEvent_t> ev_cam;  // rb_trace_camera*: a pair around every piece's k_cam_rays (rb_last_camera_rays_ms)
+    size_t cam_pieces = 0;           // pairs the most recent call recorded
     const char* last_query_kernel_name = "";
     float last_query_ms = 0.0f;
     bool query_ms_pending = false;   // the device forms return without waiting: rb_last_query_ms reads ev_q when asked

@@ -407,7 +407,21 @@ struct RadArgs {
     uint32_t first_sample, samples;
     uint32_t batch, magic_S;  // set by launch_radiance: items per reservation, floor(2^32 / samples)
 };
-int launch_radiance(const KParams& p, const RadArgs& a, void* stream, LaunchInfo* info);
+// `records`: a.rays holds one record per (ray, sample) item in item order, made by launch_camera_rays (the k_cam kernels)
+int launch_radiance(const KParams& p, const RadArgs& a, void* stream, LaunchInfo* info, bool records = false);
+// ---- rb_camera.hip: camera rays made on the device.  One launch of k_cam_rays writes the records of one
+// piece, 32 B each: {origin, seed after the generator's draws}, {normalised direction or 0 0 0 for an invalid ray, 0}.
+struct CamGenArgs {
+    rb_camera_ex cam;
+    rb_ray* recs;             // item order: record (block * samples + sample) * 64 + pixel-in-block; linear: record i
+    uint32_t* seeds;          // linear order only: seed i beside record i, whose fourth word is then 0
+    uint32_t first_pixel;     // item order: the piece's first pixel; linear: the call's
+    uint32_t n;               // item order: pixels in this piece; linear: items in this piece
+    uint32_t item_base;       // linear: index in the call of the piece's first item, (pixel - first_pixel) * samples + sample
+    uint32_t first_sample, samples;
+    uint32_t linear;
+};
+int launch_camera_rays(const CamGenArgs& g, void* stream);
 Cam host_cam(const rb_uniforms& u);   // rb_kernels.hip: the camera of a launch, shader.wgsl:690,702-708
 
 // ---- rb_denoise.hip: the edge-avoiding a-trous filter.  Everything is in the orientation of the delivered

@@ -12,6 +12,8 @@
 // What differs from the render is where a path starts (two 16-byte loads of the ray, its normalisation, the seed; no
 // camera, no jitter draws) and where its colour ends up (a per-ray sum instead of the frame's accumulation).  Only
 // non-STATS forms exist: the work counters do not move.
+// Each body is a template on where a path starts: k_rad* start on the caller's ray (RayStart), k_cam* on the record the camera
+// generator made for the item (CamStart; rb_camera.hip) -- the same queue, walks and sum behind both.
 #include "rb_device_chunk.hpp"
 
 #pragma clang fp contract(off)
@@ -82,6 +84,31 @@ DEV bool rad_start(const KParams& p, const RadArgs& a, uint32_t it, uint32_t ray
     return false;
 }
 
+// Where a kernel's paths start.  RayStart: the caller's ray (rb_trace_rays).  CamStart: the item's own record as k_cam_rays
+// (rb_camera.hip) left it in item order -- {o, seed bits}, {d, 0}: two 16-byte loads.  The generator has
+// normalised d, drawn from the seed and zeroed the direction of an invalid ray, so nothing is normalised or hashed here.
+struct RayStart {
+    static DEV bool start(const KParams& p, const RadArgs& a, uint32_t it, uint32_t ray, uint32_t hs, Path& pt) {
+        return rad_start(p, a, it, ray, hs, pt);
+    }
+};
+struct CamStart {
+    static DEV bool start(const KParams& p, const RadArgs& a, uint32_t it, uint32_t, uint32_t, Path& pt) {
+        const v4f ra = ((const v4f*)a.rays)[(size_t)it * 2u], rd = ((const v4f*)a.rays)[(size_t)it * 2u + 1u];
+        pt.o = mk(ra.x, ra.y, ra.z);
+        pt.d = mk(rd.x, rd.y, rd.z);
+        const bool valid = !(pt.d.x == 0.0f && pt.d.y == 0.0f && pt.d.z == 0.0f);
+        pt.seed = __float_as_uint(ra.w);
+        pt.color = mk(0, 0, 0);
+        pt.att = mk(1, 1, 1);
+        pt.depth = 0;
+        if (valid && p.u.max_depth > 0u) return true;
+        const v4f v = {0.0f, 0.0f, 0.0f, valid ? 1.0f : 0.0f};
+        reinterpret_cast<v4f*>(a.colors)[it] = v;
+        return false;
+    }
+};
+
 // a finished path: its colour and weight 1 into its (ray, sample) slot, read once by k_rad_sum (a streaming store, as
 // store_color of rb_kernels.hip)
 DEV void rad_store(const RadArgs& a, uint32_t it, f3 c) {
@@ -148,7 +175,8 @@ DEV uint32_t rad_total_items(const RadArgs& a) { return ((a.n + 63u) / 64u) * a.
 // ============================================================== k_rad ====
 // k_trace_direct's loop (rb_kernels.hip, trace_body<.., MULTI = false, STAGED = false>): every lane starts its own path
 // when it is handed the item and stores its colour directly; no ColorRing staging.
-__global__ void __launch_bounds__(kRadBlock, RB_RAD_WAVES) k_rad(const KParams p, const RadArgs a) {
+template <class Start>
+DEV void rad_body(const KParams& p, const RadArgs& a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t s_stack[];
     const uint32_t tid = threadIdx.x;
     const uint32_t lane = tid & 63u;
@@ -163,7 +191,7 @@ __global__ void __launch_bounds__(kRadBlock, RB_RAD_WAVES) k_rad(const KParams p
         iq.refill(a, lane, [&] { return !active; },
                   [&](uint32_t it, uint32_t ray, uint32_t hs) {
                       item = it;
-                      active = rad_start(fresh_params(p), a, it, ray, hs, pt);
+                      active = Start::start(fresh_params(p), a, it, ray, hs, pt);
                   });
         if (__ballot(active) == 0ull) {
             if (iq.drained()) break;
@@ -178,12 +206,15 @@ __global__ void __launch_bounds__(kRadBlock, RB_RAD_WAVES) k_rad(const KParams p
         }
     }
 }
+__global__ void __launch_bounds__(kRadBlock, RB_RAD_WAVES) k_rad(const KParams p, const RadArgs a) { rad_body<RayStart>(p, a); }
+__global__ void __launch_bounds__(kRadBlock, RB_RAD_WAVES) k_cam(const KParams p, const RadArgs a) { rad_body<CamStart>(p, a); }
 
 // ========================================================== k_rad_bvh ====
 // k_trace_bvh's stepped reference walk (rb_kernels.hip; the form that reads the tree through L1 / L2): the scheduling unit
 // is one leaf, the visit order per ray is the reference's, so the winner is the same triangle.  segment_finish carries the
 // per-lane sphere tree walk for scenes with more than 64 spheres.
-__global__ void __launch_bounds__(kRadBlock, RB_RAD_BVH_WAVES) k_rad_bvh(const KParams p, const RadArgs a) {
+template <class Start>
+DEV void rad_bvh_body(const KParams& p, const RadArgs& a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t s_stack[];
     const uint32_t tid = threadIdx.x;
     const uint32_t lane = tid & 63u;
@@ -212,7 +243,7 @@ __global__ void __launch_bounds__(kRadBlock, RB_RAD_BVH_WAVES) k_rad_bvh(const K
         iq.refill(a, lane, [&] { return state == IDLE; },
                   [&](uint32_t it, uint32_t ray, uint32_t hs) {
                       item = it;
-                      if (rad_start(fresh_params(p), a, it, ray, hs, pt)) state = BEGIN;
+                      if (Start::start(fresh_params(p), a, it, ray, hs, pt)) state = BEGIN;
                   });
         if (__ballot(state != IDLE) == 0ull) {
             if (iq.drained()) break;
@@ -282,13 +313,15 @@ __global__ void __launch_bounds__(kRadBlock, RB_RAD_BVH_WAVES) k_rad_bvh(const K
         }
     }
 }
+__global__ void __launch_bounds__(kRadBlock, RB_RAD_BVH_WAVES) k_rad_bvh(const KParams p, const RadArgs a) { rad_bvh_body<RayStart>(p, a); }
+__global__ void __launch_bounds__(kRadBlock, RB_RAD_BVH_WAVES) k_cam_bvh(const KParams p, const RadArgs a) { rad_bvh_body<CamStart>(p, a); }
 
 // ======================================================== k_rad_chunk ====
 // k_trace_chunk's phases 2-5 (rb_kernels.hip): lane = ray down the two-box nodes (chunk_node_step),
 // lane = triangle for the pooled 16-triangle chunks with one LDS atomic min on (t, rank) per hit, segment_finish for the
 // lanes whose walk is complete.  SPHTREE: the instantiation for scenes that also have a sphere tree.
-template <bool SPHTREE>
-__global__ void __launch_bounds__(kRadBlock, RB_RAD_CHUNK_WAVES) k_rad_chunk(const KParams p, const RadArgs a) {
+template <bool SPHTREE, class Start>
+DEV void rad_chunk_body(const KParams& p, const RadArgs& a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t s_stack[];
     const uint32_t tid = threadIdx.x;
     const uint32_t lane = tid & 63u;
@@ -327,7 +360,7 @@ __global__ void __launch_bounds__(kRadBlock, RB_RAD_CHUNK_WAVES) k_rad_chunk(con
         iq.refill(a, lane, [&] { return state == IDLE; },
                   [&](uint32_t it, uint32_t ray, uint32_t hs) {
                       item = it;
-                      if (rad_start(fresh_params(p), a, it, ray, hs, pt)) state = BEGIN;
+                      if (Start::start(fresh_params(p), a, it, ray, hs, pt)) state = BEGIN;
                   });
         if (__ballot(state != IDLE) == 0ull) {
             if (iq.drained()) break;
@@ -470,6 +503,14 @@ __global__ void __launch_bounds__(kRadBlock, RB_RAD_CHUNK_WAVES) k_rad_chunk(con
         }
     }
 }
+template <bool SPHTREE>
+__global__ void __launch_bounds__(kRadBlock, RB_RAD_CHUNK_WAVES) k_rad_chunk(const KParams p, const RadArgs a) {
+    rad_chunk_body<SPHTREE, RayStart>(p, a);
+}
+template <bool SPHTREE>
+__global__ void __launch_bounds__(kRadBlock, RB_RAD_CHUNK_WAVES) k_cam_chunk(const KParams p, const RadArgs a) {
+    rad_chunk_body<SPHTREE, CamStart>(p, a);
+}
 
 // ========================================================== k_rad_sum ====
 // Phase 2, shaped like k_accumulate: one wavefront per block of 64 rays, lane = ray; each sample row is a contiguous 1 KiB
@@ -507,8 +548,9 @@ __global__ void __launch_bounds__(256) k_rad_sum(const RadArgs a) {
 }  // namespace
 
 // One piece: a.n rays x a.samples samples, at most RB_TRACE_PIECE_ITEMS items (the caller cuts; a.colors holds them all).
-// Queue word, trace kernel and sum are queued on `stream`; nothing is waited for.
-int launch_radiance(const KParams& p_, const RadArgs& a_, void* stream_, LaunchInfo* info) {
+// Queue word, trace kernel and sum are queued on `stream`; nothing is waited for.  `records`: a.rays holds one record per ITEM,
+// in item order, as k_cam_rays writes them (rb_camera.hip) -- the k_cam kernels; a.seeds and a.seed_base are not read.
+int launch_radiance(const KParams& p_, const RadArgs& a_, void* stream_, LaunchInfo* info, bool records) {
     KParams p = p_;
     p.cam = host_cam(p.u);
     RadArgs a = a_;
@@ -529,8 +571,8 @@ int launch_radiance(const KParams& p_, const RadArgs& a_, void* stream_, LaunchI
         p.fast_nodes = nullptr;   // own-tree engines: the reference walk over the caller's tree, as k_query_bvh answers them
         if (p.u.bvh_node_count > 1u || p.sph_nodes != nullptr) v = BVH;
     }
-    static const char* const names[] = {"k_rad", "k_rad_bvh", "k_rad_chunk"};
-    li.kernel_name = names[v];
+    static const char* const names[2][3] = {{"k_rad", "k_rad_bvh", "k_rad_chunk"}, {"k_cam", "k_cam_bvh", "k_cam_chunk"}};
+    li.kernel_name = names[records ? 1 : 0][v];
     li.lds_bytes = (size_t)kStackEntryBytes * p.stack_depth * kRadBlock + (v == CHUNK ? (kRadBlock / 64u) * kChunkWaveLds : 0u);
     // the grid as launch_render sizes it: residency by registers, fewer blocks for a launch of few items
     const uint32_t max_blocks8 = stream_kernel_max_threads(8u) / 256u;   // 8 blocks per CU
@@ -553,12 +595,13 @@ int launch_radiance(const KParams& p_, const RadArgs& a_, void* stream_, LaunchI
     hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(a.queue), (int)(uint32_t)(waves * batch), 1, stream);
     if (e != hipSuccess) return (int)e;
     const dim3 g(li.grid), b(li.block);
+    const bool sph = p.sph_nodes != nullptr;
     switch (v) {
-        case PLAIN: hipLaunchKernelGGL(k_rad, g, b, li.lds_bytes, stream, p, a); break;
-        case BVH: hipLaunchKernelGGL(k_rad_bvh, g, b, li.lds_bytes, stream, p, a); break;
+        case PLAIN: hipLaunchKernelGGL(records ? k_cam : k_rad, g, b, li.lds_bytes, stream, p, a); break;
+        case BVH: hipLaunchKernelGGL(records ? k_cam_bvh : k_rad_bvh, g, b, li.lds_bytes, stream, p, a); break;
         case CHUNK:
-            if (p.sph_nodes != nullptr) hipLaunchKernelGGL(k_rad_chunk<true>, g, b, li.lds_bytes, stream, p, a);
-            else hipLaunchKernelGGL(k_rad_chunk<false>, g, b, li.lds_bytes, stream, p, a);
+            if (records) hipLaunchKernelGGL(sph ? k_cam_chunk<true> : k_cam_chunk<false>, g, b, li.lds_bytes, stream, p, a);
+            else hipLaunchKernelGGL(sph ? k_rad_chunk<true> : k_rad_chunk<false>, g, b, li.lds_bytes, stream, p, a);
             break;
     }
     e = hipGetLastError();

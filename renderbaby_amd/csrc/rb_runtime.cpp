@@ -1181,6 +1181,122 @@ int trace_rays_device_locked(rb_engine* e, const rb_ray* d_rays, const uint32_t*
     });
 }
 
+// ---- camera rays made on the device (rb_abi.h)
+// pixels per piece: whole blocks of 64 pixels, never a part of one pixel's samples (samples <= 65536: at least one block)
+size_t camera_piece_pixels(uint32_t samples) { return std::max<size_t>((RB_CAMERA_PIECE_ITEMS / samples) & ~size_t(63), 64); }
+
+// the scratch of one piece: a record and a colour per item, the queue word
+int camera_scratch(rb_engine* e, size_t piece, uint32_t samples) {
+    const size_t items = ((piece + 63) / 64) * 64 * samples;
+    HIP_TRY(e, e->q_rays.reserve(items));
+    HIP_TRY(e, e->rad_colors.reserve(items * 4));
+    HIP_TRY(e, e->rad_queue.reserve(16));
+    return RB_OK;
+}
+
+// one piece, queued: the generator into the record scratch, the k_cam kernel of the scene's walk over it, the sum into `out`
+int camera_piece(rb_engine* e, const rb::KParams& p, const rb_camera_ex& cam, uint64_t first_pixel, size_t done, size_t m,
+                 uint32_t first_sample, uint32_t samples, rb_radiance* out, rb::LaunchInfo* li) {
+    while (e->ev_cam.size() < 2 * (e->cam_pieces + 1)) {
+        hipEvent_t x = nullptr;
+        if (const hipError_t st = hipEventCreate(&x)) return static_cast<int>(st);
+        e->ev_cam.push_back(x);
+    }
+    hipEvent_t* const ev = &e->ev_cam[2 * e->cam_pieces];
+    rb::CamGenArgs g{};
+    g.cam = cam;
+    g.recs = e->q_rays.ptr;
+    g.first_pixel = static_cast<uint32_t>(first_pixel + done);
+    g.n = static_cast<uint32_t>(m);
+    g.first_sample = first_sample;
+    g.samples = samples;
+    if (const hipError_t st = hipEventRecord(ev[0], e->stream)) return static_cast<int>(st);
+    const int st = rb::launch_camera_rays(g, e->stream);
+    if (st) return st;
+    if (const hipError_t st1 = hipEventRecord(ev[1], e->stream)) return static_cast<int>(st1);
+    e->cam_pieces++;
+    return rb::launch_radiance(p, trace_args(e, e->q_rays.ptr, nullptr, out, done, m, first_sample, samples), e->stream, li, true);
+}
+
+int trace_camera_locked(rb_engine* e, const rb_camera_ex& cam, uint64_t first_pixel, size_t n, uint32_t first_sample, uint32_t samples,
+                        rb_radiance* out) {
+    rb::KParams p{};
+    int rc = query_params(e, &p);
+    e->last_query_ms = 0.0f;
+    e->cam_pieces = 0;
+    if (rc || n == 0) return rc;
+    const size_t piece = std::min(n, camera_piece_pixels(samples));
+    rc = camera_scratch(e, piece, samples);
+    if (rc) return rc;
+    HIP_TRY(e, e->rad_out.reserve(piece));
+    const bool pinned = page_locked(out);
+    for (size_t done = 0; done < n; done += piece) {
+        const size_t m = std::min(piece, n - done);
+        rb::LaunchInfo li{};
+        HIP_TRY(e, hipEventRecord(e->ev_q[0], e->stream));
+        const int st = camera_piece(e, p, cam, first_pixel, done, m, first_sample, samples, e->rad_out.ptr, &li);
+        if (st) return rb::fail(e, RB_ERR_DEVICE, "camera kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
+        HIP_TRY(e, hipEventRecord(e->ev_q[1], e->stream));
+        if (li.kernel_name) e->last_query_kernel_name = li.kernel_name;
+        rc = query_copy_out(e, out + done, e->rad_out.ptr, m * sizeof(rb_radiance), pinned);
+        if (rc) return rc;
+        HIP_TRY(e, hipStreamSynchronize(e->stream));   // the scratch is the next piece's
+        float ms = 0.0f;
+        HIP_TRY(e, hipEventElapsedTime(&ms, e->ev_q[0], e->ev_q[1]));
+        e->last_query_ms += ms;
+    }
+    return RB_OK;
+}
+
+// every piece queued between the query's two events (the pieces share the scratch in stream order); nothing is waited for
+int trace_camera_device_locked(rb_engine* e, const rb_camera_ex& cam, uint64_t first_pixel, size_t n, uint32_t first_sample,
+                               uint32_t samples, rb_radiance* d_out) {
+    const int rc = device_range(e, d_out, n * sizeof(rb_radiance), 16, "d_out");
+    if (rc) return rc;
+    const size_t piece = std::min(n, camera_piece_pixels(samples));
+    e->cam_pieces = 0;
+    return device_query_locked(e, [&](const rb::KParams& p, rb::LaunchInfo* li) {
+        if (camera_scratch(e, piece, samples)) return static_cast<int>(hipErrorOutOfMemory);
+        for (size_t done = 0; done < n; done += piece) {
+            const int st = camera_piece(e, p, cam, first_pixel, done, std::min(piece, n - done), first_sample, samples, d_out + done, li);
+            if (st) return st;
+        }
+        return 0;
+    });
+}
+
+// the refusals every camera entry point shares; before a device is touched (e may be NULL: rb_camera_rays)
+int camera_check(rb_engine* e, const char* who, const rb_camera_ex* cam, uint64_t first_pixel, size_t n, uint32_t first_sample, uint32_t samples) {
+    const rb_camera_ex& c = *cam;
+    if (c.kind != RB_CAM_PERSPECTIVE && c.kind != RB_CAM_ORTHO && c.kind != RB_CAM_EQUIRECT)
+        return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: unknown camera kind %u", who, c.kind);
+    if ((c.flags & ~static_cast<uint32_t>(RB_CAM_NO_JITTER)) != 0u) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: unknown flag bits 0x%x", who, c.flags);
+    if (c._reserved[0] || c._reserved[1] || c._reserved[2]) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: _reserved must be 0", who);
+    if (c.width == 0u || c.height == 0u || c.width > (1u << 24) || c.height > (1u << 24))
+        return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: width and height are 1 .. 2^24, not %u x %u", who, c.width, c.height);
+    const uint64_t pixels = static_cast<uint64_t>(c.width) * c.height;
+    if (pixels >= (1ull << 31)) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: an image of %u x %u pixels is too large", who, c.width, c.height);
+    if (first_pixel > pixels || n > pixels - first_pixel)
+        return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: pixels [%llu, +%zu) leave the image of %llu pixels", who,
+                        static_cast<unsigned long long>(first_pixel), n, static_cast<unsigned long long>(pixels));
+    if (samples == 0 || samples > 65536u) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s takes 1 .. 65536 samples per pixel, not %u", who, samples);
+    if (static_cast<uint64_t>(first_sample) + samples > 0xFFFFFFFFull)
+        return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: first_sample + samples = %u + %u does not fit 32 bits", who, first_sample, samples);
+    if (static_cast<uint64_t>(n) * samples > 0x7FFFFFFFull - 63ull)
+        return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s takes at most 2^31 - 64 (pixel, sample) items per call", who);
+    // (pos may be non-finite: its rays are invalid by rb_cast_rays' rule and weigh 0)
+    const float* const basis[] = {c.right, c.up, c.forward};
+    bool finite = std::isfinite(c.tan_half_fov) && std::isfinite(c.half_width) && std::isfinite(c.half_height) &&
+                  std::isfinite(c.lens_radius) && std::isfinite(c.focus_distance);
+    for (const float* v : basis) finite = finite && std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]);
+    if (!finite) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: a field of the camera other than pos is not finite", who);
+    if (c.kind == RB_CAM_PERSPECTIVE && (!(c.tan_half_fov > 0.0f) || c.lens_radius < 0.0f || (c.lens_radius > 0.0f && !(c.focus_distance > 0.0f))))
+        return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: a perspective camera needs tan_half_fov > 0, lens_radius >= 0 and, with a lens, focus_distance > 0", who);
+    if (c.kind == RB_CAM_ORTHO && (!(c.half_width > 0.0f) || !(c.half_height > 0.0f)))
+        return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: an orthographic camera needs half_width > 0 and half_height > 0", who);
+    return RB_OK;
+}
+
 // ---- the denoiser (rb_abi.h).  Like a query it is queued on the engine's stream behind whatever runs
 // there, reads the scene and the committed accumulation, and writes buffers of its own.
 rb::GuidePlanes guide_planes(rb_engine* e) { return rb::GuidePlanes{e->dn_nt.ptr, e->dn_pc.ptr, e->dn_al.ptr}; }
@@ -1440,6 +1556,7 @@ void rb_destroy(rb_engine* e) {
     for (rb::FrameSlot& s : e->slot)
         if (s.done) (void)hipEventDestroy(s.done);
     for (hipEvent_t x : e->ev_pool) (void)hipEventDestroy(x);
+    for (hipEvent_t x : e->ev_cam) (void)hipEventDestroy(x);
     for (hipEvent_t x : e->ev_q)
         if (x) (void)hipEventDestroy(x);
     for (hipEvent_t x : e->ev_dn)
@@ -1930,6 +2047,67 @@ int rb_trace_rays_device(rb_engine* e, const rb_ray* d_rays, const uint32_t* d_s
     return answered(e, t, trace_rays_device_locked(t, d_rays, d_seeds, n, first_sample, samples, d_out));
 }
 
+int rb_camera_rays(int32_t device, const rb_camera_ex* cam, uint64_t first_pixel, size_t n_pixels, uint32_t first_sample,
+                   uint32_t samples, rb_ray* rays_out, uint32_t* seeds_out) {
+    if (n_pixels > 0 && (!cam || !rays_out || !seeds_out)) return rb::fail(nullptr, RB_ERR_NULL_ARGUMENT, "cam / rays_out / seeds_out is NULL");
+    if (cam)
+        if (const int rc = camera_check(nullptr, "rb_camera_rays", cam, first_pixel, n_pixels, first_sample, samples)) return rc;
+    if (n_pixels == 0) return RB_OK;
+    if (device >= 0 && hipSetDevice(device) != hipSuccess) return rb::fail(nullptr, RB_ERR_DEVICE, "hipSetDevice(%d) failed", device);
+    const size_t items = n_pixels * samples, piece = std::min<size_t>(items, size_t(1) << 22);   // 128 + 16 MiB of scratch
+    rb::DevBuf<rb_ray> d_rays;
+    rb::DevBuf<uint32_t> d_seeds;
+    hipStream_t stream = nullptr;
+    hipError_t st = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
+    if (st == hipSuccess) st = d_rays.resize(piece);
+    if (st == hipSuccess) st = d_seeds.resize(piece);
+    for (size_t done = 0; done < items && st == hipSuccess; done += piece) {
+        const size_t m = std::min(piece, items - done);
+        rb::CamGenArgs g{};
+        g.cam = *cam;
+        g.recs = d_rays.ptr;
+        g.seeds = d_seeds.ptr;
+        g.first_pixel = static_cast<uint32_t>(first_pixel);
+        g.n = static_cast<uint32_t>(m);
+        g.item_base = static_cast<uint32_t>(done);
+        g.first_sample = first_sample;
+        g.samples = samples;
+        g.linear = 1u;
+        st = static_cast<hipError_t>(rb::launch_camera_rays(g, stream));
+        if (st == hipSuccess) st = hipMemcpyAsync(rays_out + done, d_rays.ptr, m * sizeof(rb_ray), hipMemcpyDeviceToHost, stream);
+        if (st == hipSuccess) st = hipMemcpyAsync(seeds_out + done, d_seeds.ptr, m * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
+        if (st == hipSuccess) st = hipStreamSynchronize(stream);   // the scratch is the next piece's
+    }
+    if (stream) (void)hipStreamSynchronize(stream);   // (the buffers are freed on return, after this)
+    if (stream) (void)hipStreamDestroy(stream);
+    if (st != hipSuccess) return rb::fail(nullptr, RB_ERR_DEVICE, "rb_camera_rays failed: %s", hipGetErrorString(st));
+    return RB_OK;
+}
+
+int rb_trace_camera(rb_engine* e, const rb_camera_ex* cam, uint64_t first_pixel, size_t n_pixels, uint32_t first_sample,
+                    uint32_t samples, rb_radiance* out) {
+    if (!e) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (n_pixels > 0 && (!cam || !out)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "rb_trace_camera: cam / out is NULL");
+    if (cam)
+        if (const int rc = camera_check(e, "rb_trace_camera", cam, first_pixel, n_pixels, first_sample, samples)) return rc;
+    rb_engine* const t = answering(e);
+    if (n_pixels == 0) return answered(e, t, require_ready(t));
+    return answered(e, t, trace_camera_locked(t, *cam, first_pixel, n_pixels, first_sample, samples, out));
+}
+
+int rb_trace_camera_device(rb_engine* e, const rb_camera_ex* cam, uint64_t first_pixel, size_t n_pixels, uint32_t first_sample,
+                           uint32_t samples, rb_radiance* d_out) {
+    if (!e) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (n_pixels > 0 && (!cam || !d_out)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "rb_trace_camera_device: cam / d_out is NULL");
+    if (cam)
+        if (const int rc = camera_check(e, "rb_trace_camera_device", cam, first_pixel, n_pixels, first_sample, samples)) return rc;
+    rb_engine* const t = answering(e);
+    if (n_pixels == 0) return answered(e, t, require_ready(t));
+    return answered(e, t, trace_camera_device_locked(t, *cam, first_pixel, n_pixels, first_sample, samples, d_out));
+}
+
 int rb_denoise_default_params(rb_denoise_params* p) {
     if (!p) return RB_ERR_NULL_ARGUMENT;
     *p = rb_denoise_params{};
@@ -2031,6 +2209,22 @@ int rb_last_query_ms(rb_engine* e, float* ms) {
         t->query_ms_pending = false;
     }
     *ms = t->last_query_ms;
+    return RB_OK;
+}
+
+int rb_last_camera_rays_ms(rb_engine* e, float* ms) {
+    if (!e || !ms) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    rb_engine* const t = rb::is_group(e) ? e->parts[0].get() : e;
+    *ms = 0.0f;
+    if (t->cam_pieces == 0) return RB_OK;
+    rb::set_device(t);
+    HIP_TRY(e, hipEventSynchronize(t->ev_cam[2 * t->cam_pieces - 1]));
+    for (size_t i = 0; i < t->cam_pieces; i++) {
+        float piece_ms = 0.0f;
+        HIP_TRY(e, hipEventElapsedTime(&piece_ms, t->ev_cam[2 * i], t->ev_cam[2 * i + 1]));
+        *ms += piece_ms;
+    }
     return RB_OK;
 }
 

@@ -535,6 +535,39 @@ class Engine:
                                             n, first_sample, samples, res.ctypes.data if n else None))
         return res
 
+    # ---- camera rays made on the device (rb_abi.h)
+    def trace_camera(self, cam, samples, first_sample=0, region=None, out=None):
+        """rb_trace_camera: the radiance through an abi.CAMERA_EX camera (``camera.make``), every (pixel, sample) ray made on
+        the device from its own random stream, summed over ``samples`` samples -> abi.RADIANCE[n] (``weight``: the valid
+        samples).  ``region``: (first_pixel, n_pixels) of the row-major image, by default all of it.  ``out``: an
+        abi.RADIANCE array of n elements to fill, or a float32 tensor of shape (n, 4) on the engine's device, which selects
+        rb_trace_camera_device (nothing crosses to the host)."""
+        c = np.ascontiguousarray(cam, dtype=abi.CAMERA_EX).reshape(1)
+        samples, first_sample = int(samples), int(first_sample)
+        if not (0 <= samples < 2 ** 32 and 0 <= first_sample < 2 ** 32):
+            raise ValueError("samples and first_sample are 32-bit unsigned numbers")
+        first, n = (0, int(c["width"][0]) * int(c["height"][0])) if region is None else (int(region[0]), int(region[1]))
+        if first < 0 or n < 0:
+            raise ValueError("region: (first_pixel, n_pixels), both at least 0")
+        if _is_tensor(out):
+            import torch
+            op, no = self._device_tensor(out, torch.float32, 4, "out")
+            if no != n:
+                raise ValueError("out and the region differ in length")
+            self._device_call(self._lib.rb_trace_camera_device, c.ctypes.data, first, n, first_sample, samples, op)
+            return out
+        res = np.empty(n, dtype=abi.RADIANCE) if out is None else out
+        if not isinstance(res, np.ndarray) or res.dtype != abi.RADIANCE or res.shape != (n,) or not res.flags.c_contiguous:
+            raise ValueError("out: a contiguous abi.RADIANCE array of n elements is needed")
+        self._check(self._lib.rb_trace_camera(self._h, c.ctypes.data, first, n, first_sample, samples, res.ctypes.data if n else None))
+        return res
+
+    def last_camera_rays_ms(self):
+        """kernel ms of the generator (k_cam_rays) in the most recent trace_camera: its share of last_query_ms()"""
+        ms = C.c_float()
+        self._check(self._lib.rb_last_camera_rays_ms(self._h, C.byref(ms)))
+        return ms.value
+
     def render_hits(self, surfaces=False):
         """rb_render_hits: the first hit of every pixel centre as abi.HIT[rows, width] (and abi.SURFACE with ``surfaces``) in
         the orientation of the delivered frame; a sharded engine: its padded local rows, like read_accumulation."""
@@ -700,6 +733,24 @@ def device_name(device=-1):
     buf = C.create_string_buffer(256)
     rc = load().rb_device_name(device, buf, 256)
     return buf.value.decode() if rc == 0 else "unknown"
+
+
+def camera_rays_device(cam, samples, first_sample=0, region=None, device=-1):
+    """rb_camera_rays: the generator alone, no engine -- (abi.RAY[n * samples], uint32 seeds[n * samples]) of the pixels of
+    ``region`` ((first_pixel, n_pixels); by default the whole image), item (pixel - first_pixel) * samples + k: the origin, the
+    normalised direction (0 0 0: an invalid ray) and the seed trace_ray starts with.  ``camera.rays`` is its numpy model."""
+    c = np.ascontiguousarray(cam, dtype=abi.CAMERA_EX).reshape(1)
+    samples = int(samples)
+    first, n = (0, int(c["width"][0]) * int(c["height"][0])) if region is None else (int(region[0]), int(region[1]))
+    if first < 0 or n < 0 or not 0 <= samples < 2 ** 32:
+        raise ValueError("region: (first_pixel, n_pixels), both at least 0; samples: a 32-bit unsigned number")
+    rays, seeds = np.zeros(n * samples, dtype=abi.RAY), np.zeros(n * samples, dtype=np.uint32)
+    lib = load()
+    rc = lib.rb_camera_rays(int(device), c.ctypes.data, first, n, int(first_sample), samples, rays.ctypes.data if len(rays) else None,
+                            seeds.ctypes.data if len(rays) else None)
+    if rc != abi.RB_OK:
+        raise RenderError(rc, (lib.rb_last_error(None) or b"").decode())
+    return rays, seeds
 
 
 def denoise_defaults():

@@ -4,7 +4,7 @@
                                  [--width W --height H] [--included-root DIR] [--every N]
                                  [--aov depth,normal,albedo,emission,id,ao] [--ao-radius R]
                                  [--denoise [--denoise-iterations N]]
-                                 [--camera equirect|ortho|thin-lens [--ortho-width W] [--aperture A --focus-distance F]]
+                                 [--camera equirect|ortho|thin-lens [--ortho-width W] [--aperture A --focus-distance F] [--jitter]]
                                  [--probe x,y,z [--probe-normal x,y,z]]
 
 scene file -> scene_io.load_scene (the importer's and the Scene->RenderConfig adapter's rules) ->
@@ -15,12 +15,14 @@ and a frame is written every N samples (out_0001.png, ...).  --aov writes the fi
 a-trous filter (Engine.denoise) as out.denoised.png -- with --every, every delivered frame next to the raw
 one (out_0001.denoised.png, ...).  --camera renders the scene a second time through a camera the scene file cannot express, at
 the scene camera's position and direction (bake.camera_rays -> bake.render_rays: Engine.trace_rays on one ray per pixel, spp
-samples each), as out.<camera>.png.  --probe prints the mean radiance over the cosine-weighted hemisphere at a point
+samples each), as out.<camera>.png; with --jitter every sample's ray is made on the device instead -- sub-pixel jitter and, for the
+thin lens, a lens point per sample, focused on a plane at the focus distance (camera.make -> bake.render_camera:
+Engine.trace_camera).  --probe prints the mean radiance over the cosine-weighted hemisphere at a point
 (bake.irradiance, spp rays; normal +y unless --probe-normal says otherwise).
 """
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from renderbaby_amd import Engine, Frame, RenderConfig, aov, bake, denoise, scene_io  # noqa: E402
+from renderbaby_amd import Engine, Frame, RenderConfig, aov, bake, camera, denoise, scene_io  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("scene"); ap.add_argument("png")
@@ -36,6 +38,7 @@ ap.add_argument("--denoise-iterations", type=int, default=None, help="a-trous it
 ap.add_argument("--camera", choices=["equirect", "ortho", "thin-lens"], default=None, help="also write out.<camera>.png through bake.render_rays")
 ap.add_argument("--ortho-width", type=float, default=10.0); ap.add_argument("--aperture", type=float, default=0.1)
 ap.add_argument("--focus-distance", type=float, default=5.0)
+ap.add_argument("--jitter", action="store_true", help="--camera with a ray per sample, made on the device: anti-aliased, and a thin lens that blurs")
 ap.add_argument("--probe", default=None, help="x,y,z: print the mean radiance arriving at this point (bake.irradiance)")
 ap.add_argument("--probe-normal", default="0,1,0")
 a = ap.parse_args()
@@ -92,9 +95,15 @@ if aovs:
 if a.camera:
     kind = a.camera.replace("-", "_")
     cam = s.uniforms["camera"][0]
-    O, D = bake.camera_rays(kind, s.width, s.height, cam["pos"], dir=cam["dir"], ortho_width=a.ortho_width, aperture=a.aperture,
-                            focus_distance=a.focus_distance)
-    img = bake.render_rays(eng, O, D, min(max(s.total_samples, 1), 65536))
+    spp = min(max(s.total_samples, 1), 65536)
+    if a.jitter:
+        cam_ex = camera.make("perspective" if kind == "thin_lens" else kind, s.width, s.height, cam["pos"], dir=cam["dir"],
+                             ortho_width=a.ortho_width, aperture=a.aperture, focus_distance=a.focus_distance)
+        img = bake.render_camera(eng, cam_ex, spp)
+    else:
+        O, D = bake.camera_rays(kind, s.width, s.height, cam["pos"], dir=cam["dir"], ortho_width=a.ortho_width, aperture=a.aperture,
+                                focus_distance=a.focus_distance)
+        img = bake.render_rays(eng, O, D, spp)
     base, ext = os.path.splitext(a.png)
     scene_io.export_png(f"{base}.{kind}{ext}", Frame(img.shape[1], img.shape[0], img))
     print(f"{a.camera} camera with {eng.last_query_kernel_name()} in {eng.last_query_ms():.3f} ms -> {base}.{kind}{ext}")
