@@ -1,5 +1,5 @@
-// rb_engine.hpp -- the engine's state, shared by the runtime (rb_runtime.cpp) and the acceleration structures it builds
-// (rb_accel.cpp).  Host code only: not part of the ABI, and no .hip file includes it.
+// rb_engine.hpp -- the engine's state, shared by the runtime (rb_runtime.cpp), the acceleration structures it builds
+// (rb_accel.cpp) and the queries over them (rb_queries.cpp).  Host code only: not part of the ABI, and no .hip file includes it.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -237,6 +237,14 @@ int upload(rb_engine* e, DevBuf<T>& buf, const void* src, size_t count, uint32_t
 inline bool is_group(const rb_engine* e) { return !e->parts.empty(); }
 inline void set_device(const rb_engine* e) { (void)hipSetDevice(e->device); }
 inline uint32_t kernel_of(const rb_options& opt) { return opt.kernel ? opt.kernel : RB_KERNEL_STREAM; }
+
+// ---- rb_runtime.cpp, for rb_queries.cpp (hidden: the library's dynamic symbols stay what they were)
+#define RB_HIDDEN __attribute__((visibility("hidden")))
+RB_HIDDEN int require_ready(rb_engine* e);      // the engine holds a scene that a launch may read, or the refusal
+RB_HIDDEN int ensure_prepared(rb_engine* e);    // the prepared triangles and the mesh walk's tree of the current scene
+RB_HIDDEN KParams make_params(rb_engine* e, uint32_t first_pass, uint32_t n_passes, int src, int dst);
+RB_HIDDEN void copy_error(rb_engine* g, const rb_engine* part);
+#undef RB_HIDDEN
 
 // ---- rb_accel.cpp
 constexpr uint32_t kBuildTreeFlags = RB_FLAG_BUILD_TREE | RB_FLAG_BUILD_TREE_HOST;          // the engine builds the reference-layout tree

@@ -1,5 +1,5 @@
-// rb_internal.hpp -- declarations shared by the runtime (rb_runtime.cpp), the
-// BVH helper (rb_bvh.cpp) and the kernels (rb_kernels.hip).  Not part of the ABI.
+// rb_internal.hpp -- declarations shared by the runtime (rb_runtime.cpp), the queries (rb_queries.cpp), the
+// BVH helper (rb_bvh.cpp) and the kernels (rb_kernels.hip and the other .hip files).  Not part of the ABI.
 #pragma once
 
 #include <cstddef>
@@ -363,6 +363,17 @@ struct LaunchInfo {
     const char* kernel_name;
 };
 
+// The walk of a query over this scene with these flags -- rb_cast_rays' rule, which launch_query, launch_occluded and
+// launch_radiance all ask: the chunked walk where its tree exists and leaf stepping is on; else the reference walk over the
+// caller's tree (the library's own tree has no query form, so fast_nodes is dropped), stepped if there is a tree to step
+// through -- a multi-node mesh tree or the spheres' -- and the plain per-ray kernel if there is none.
+enum QueryWalk : uint32_t { kWalkPlain, kWalkBvh, kWalkChunk };
+inline QueryWalk query_walk(KParams& p) {
+    if (p.u.bvh_node_count > 1u && !p.no_leaf_stepping && p.chunk_nodes != nullptr) return kWalkChunk;
+    p.fast_nodes = nullptr;
+    return (p.u.bvh_node_count > 1u || p.sph_nodes != nullptr) ? kWalkBvh : kWalkPlain;
+}
+
 // ---- rb_query.hip: closest-hit queries.  One launch answers one piece: `n` rays of a device buffer, or
 // the pixel centres of a window of the frame in DISPLAYED coordinates (x mirrored like the RGBA8 frame).  `hits` / `surf` are
 // device buffers in the ABI's layout (record i = ray i, or window pixel (row, column) = row * win_w + column).
@@ -377,9 +388,6 @@ struct QueryArgs {
 #ifndef RB_QUERY_PIECE_LOG2
 #define RB_QUERY_PIECE_LOG2 22
 #endif
-// rays per launch: the query scratch is 128 + 192 + 192 MiB whatever n is (a frame piece: whole 8-row bands, so max(2^22, 8 x width)
-// records).  2^20 cost the lamp fixture 1.76 instead of 1.22 ms of kernel time: every piece ends in a tail, and the copy-out of
-// the piece before has pushed the tree out of L2 (five times the render's L2 misses per frame; profiles/r06_query_rate.txt)
 // rays per launch: the query scratch is 128 + 192 + 192 MiB whatever n is (a frame piece: whole 8-row bands, so max(2^22, 8 x width)
 // records).  2^20 cost the lamp fixture 1.76 instead of 1.22 ms of kernel time: every piece ends in a tail, and the copy-out of
 // the piece before has pushed the tree out of L2 (five times the render's L2 misses per frame; profiles/r06_query_rate.txt)

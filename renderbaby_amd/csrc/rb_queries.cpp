@@ -1,0 +1,820 @@
+// rb_queries.cpp -- what an engine answers besides frames: closest-hit queries (rb_cast_rays / rb_render_hits / rb_pick), any-hit
+// occlusion, path-traced radiance along given rays, camera rays made on the device and the denoiser over the first-hit buffers,
+// with their device forms, their getters and their C entry points (rb_abi.h; DESIGN.md sections 11-15).  Every family shares
+// one prologue (query_prologue), one timed launch (timed_launch) and one runner per form: run_pieces for the host forms,
+// device_query_locked for the device forms.  The engine's state is rb_engine.hpp's; the launchers are
+// rb_internal.hpp's.
+#include <cmath>
+#include <initializer_list>
+
+#include "rb_engine.hpp"
+
+namespace {
+
+using rb::copy_error, rb::ensure_prepared, rb::make_params, rb::require_ready;
+
+// ------------------------------------------------------------------ closest-hit queries ----
+// (rb_abi.h)  A query reads the scene and writes its own scratch: it is queued on the engine's stream
+// behind whatever runs there -- a pass the iterator has started ahead included, which stays valid -- and uses events of its
+// own, so neither the work counters nor the timing of a launch group move.
+bool page_locked(const void* p) {
+    hipPointerAttribute_t attr{};
+    if (p && hipPointerGetAttributes(&attr, p) == hipSuccess && attr.type == hipMemoryTypeHost) return true;
+    (void)hipGetLastError();   // an unregistered pointer makes the query fail: that is the ordinary case
+    return false;
+}
+
+// device -> caller memory behind the stream's work: a DMA into page-locked memory, a blocking copy otherwise
+int query_copy_out(rb_engine* e, void* dst, const void* src, size_t bytes, bool pinned) {
+    if (pinned) {
+        HIP_TRY(e, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, e->stream));
+        return RB_OK;
+    }
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    HIP_TRY(e, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+    return RB_OK;
+}
+
+// the scene as a kernel of this module sees it, or the refusal of a traversal that its LDS stack column cannot hold
+int scene_params(rb_engine* e, rb::KParams* p) {
+    *p = make_params(e, 0, 0, e->cur, e->cur);
+    if (!e->stack_depth_covers) return rb::fail(e, RB_ERR_DEVICE, "internal: a traversal is deeper than its LDS stack column (%u entries)", p->stack_depth);
+    return RB_OK;
+}
+
+// what every query begins with; the kernel time of the query before is gone from here on, however far this one gets
+int query_prologue(rb_engine* e, rb::KParams* p) {
+    e->last_query_ms = 0.0f;
+    int rc = require_ready(e);
+    if (!rc) rc = ensure_prepared(e);
+    if (!rc) rc = scene_params(e, p);
+    if (rc) return rc;
+    for (hipEvent_t& x : e->ev_q)
+        if (!x) HIP_TRY(e, hipEventCreate(&x));
+    e->query_ms_pending = false;
+    return RB_OK;
+}
+
+// what both runners time: `launch(li)` queues a query's kernels between its two events and returns a HIP status
+template <class Launch>
+int timed_launch(rb_engine* e, const char* kind, Launch&& launch) {
+    rb::LaunchInfo li{};
+    HIP_TRY(e, hipEventRecord(e->ev_q[0], e->stream));
+    const int st = launch(&li);
+    if (st) return rb::fail(e, RB_ERR_DEVICE, "%s kernel launch failed: %s", kind, hipGetErrorString(static_cast<hipError_t>(st)));
+    HIP_TRY(e, hipEventRecord(e->ev_q[1], e->stream));
+    if (li.kernel_name) e->last_query_kernel_name = li.kernel_name;
+    return RB_OK;
+}
+
+// One array of a host form: item i of the call lies at host + i * stride in the caller's memory, item i of a piece at
+// dev + i * stride in the scratch.  host == nullptr: the caller left this array out.
+struct PieceIn { const void* host; void* dev; size_t stride; };
+struct PieceOut { void* host; const void* dev; size_t stride; bool pinned; };   // pinned: host is page-locked (the runner finds out)
+
+// The host forms' runner: n items in pieces of `piece`.  A piece's inputs are uploaded ahead of the events (the time between them
+// stays the kernels'), `launch(done, m, li)` queues the kernels of items [done, done + m) over the scratch and returns a HIP
+// status, the results are copied out behind them and waited for.  `kind` names the family where a launch fails.
+template <size_t N, class Launch>
+int run_pieces(rb_engine* e, const char* kind, size_t piece, size_t n, std::initializer_list<PieceIn> ins, PieceOut (&&outs)[N],
+               Launch&& launch) {
+    if (n == 0) return RB_OK;
+    for (PieceOut& o : outs) o.pinned = page_locked(o.host);
+    for (size_t done = 0; done < n; done += piece) {
+        const size_t m = std::min(piece, n - done);
+        // (from pageable memory the runtime stages the copy and returns when the source may be reused)
+        for (const PieceIn& in : ins)
+            if (in.host) HIP_TRY(e, hipMemcpyAsync(in.dev, static_cast<const char*>(in.host) + done * in.stride, m * in.stride, hipMemcpyHostToDevice, e->stream));
+        int rc = timed_launch(e, kind, [&](rb::LaunchInfo* li) { return launch(done, m, li); });
+        for (const PieceOut& o : outs)
+            if (!rc && o.host) rc = query_copy_out(e, static_cast<char*>(o.host) + done * o.stride, o.dev, m * o.stride, o.pinned);
+        if (rc) return rc;
+        HIP_TRY(e, hipStreamSynchronize(e->stream));   // the scratch is the next piece's
+        float ms = 0.0f;
+        HIP_TRY(e, hipEventElapsedTime(&ms, e->ev_q[0], e->ev_q[1]));
+        e->last_query_ms += ms;
+    }
+    return RB_OK;
+}
+
+// the device forms' runner: one timed launch on the caller's buffers; nothing is waited for
+template <class Launch>
+int device_query_locked(rb_engine* e, Launch&& launch) {
+    rb::KParams p{};
+    int rc = query_prologue(e, &p);
+    if (!rc) rc = timed_launch(e, "query", [&](rb::LaunchInfo* li) { return launch(p, li); });
+    if (!rc) e->query_ms_pending = true;   // rb_last_query_ms reads the events when it is asked
+    return rc;
+}
+
+int cast_rays_locked(rb_engine* e, const rb_ray* rays, size_t n, rb_hit* hits_out, rb_surface* surf_out) {
+    rb::KParams p{};
+    const size_t piece = std::min<size_t>(n, rb::kQueryPiece);
+    const int rc = query_prologue(e, &p);
+    if (rc) return rc;
+    HIP_TRY(e, e->q_rays.reserve(piece));
+    HIP_TRY(e, e->q_hits.reserve(piece));
+    if (surf_out) HIP_TRY(e, e->q_surf.reserve(piece));
+    return run_pieces(e, "query", piece, n, {{rays, e->q_rays.ptr, sizeof(rb_ray)}},
+                      {{hits_out, e->q_hits.ptr, sizeof(rb_hit)}, {surf_out, e->q_surf.ptr, sizeof(rb_surface)}},
+                      [&](size_t, size_t m, rb::LaunchInfo* li) {
+                          rb::QueryArgs q{};
+                          q.rays = e->q_rays.ptr;
+                          q.n = static_cast<uint32_t>(m);
+                          q.hits = e->q_hits.ptr;
+                          q.surf = surf_out ? e->q_surf.ptr : nullptr;
+                          return rb::launch_query(p, q, e->stream, li);
+                      });
+}
+
+// rows of a frame of width w in one piece: whole 8-row tiles, about rb::kQueryPiece records, at least one band of tiles
+uint32_t frame_piece_rows(uint32_t w) { return w == 0 ? 8u : std::max<uint32_t>(8u, (rb::kQueryPiece / w) & ~7u); }
+
+// the pixel centres of rows [0, rows) x the whole width (global = image rows, else this shard's local rows), or of one pixel:
+// rows * w items, of which piece `done` begins at row done / w
+int pixel_hits_locked(rb_engine* e, uint32_t x0, uint32_t y0, uint32_t w, uint32_t rows, bool global, rb_hit* hits_out, rb_surface* surf_out) {
+    rb::KParams p{};
+    const uint32_t piece_rows = frame_piece_rows(w);
+    const int rc = query_prologue(e, &p);
+    if (rc) return rc;
+    HIP_TRY(e, e->q_hits.reserve(static_cast<size_t>(std::min(piece_rows, rows)) * w));
+    if (surf_out) HIP_TRY(e, e->q_surf.reserve(static_cast<size_t>(std::min(piece_rows, rows)) * w));
+    return run_pieces(e, "query", static_cast<size_t>(piece_rows) * w, static_cast<size_t>(rows) * w, {},
+                      {{hits_out, e->q_hits.ptr, sizeof(rb_hit)}, {surf_out, e->q_surf.ptr, sizeof(rb_surface)}},
+                      [&](size_t done, size_t m, rb::LaunchInfo* li) {
+                          rb::QueryArgs q{};
+                          q.win_x = x0;
+                          q.win_y = y0 + static_cast<uint32_t>(done / w);
+                          q.win_w = w;
+                          q.win_h = static_cast<uint32_t>(m / w);
+                          q.win_global = global ? 1u : 0u;
+                          q.hits = e->q_hits.ptr;
+                          q.surf = surf_out ? e->q_surf.ptr : nullptr;
+                          return rb::launch_query(p, q, e->stream, li);
+                      });
+}
+
+// ---- any-hit occlusion and the device forms (rb_abi.h)
+int occluded_locked(rb_engine* e, const rb_ray* rays, const float* tmax, size_t n, uint32_t mask, uint8_t* out) {
+    rb::KParams p{};
+    const int rc = query_prologue(e, &p);
+    if (rc || n == 0) return rc;
+    const size_t piece = std::min<size_t>(n, rb::kQueryPiece);
+    HIP_TRY(e, e->q_rays.reserve(piece));
+    if (tmax) HIP_TRY(e, e->q_tmax.reserve(piece));
+    HIP_TRY(e, e->q_occl.reserve(piece));
+    return run_pieces(e, "occlusion", piece, n, {{rays, e->q_rays.ptr, sizeof(rb_ray)}, {tmax, e->q_tmax.ptr, sizeof(float)}},
+                      {{out, e->q_occl.ptr, 1}}, [&](size_t, size_t m, rb::LaunchInfo* li) {
+                          rb::OcclArgs a{};
+                          a.q.rays = e->q_rays.ptr;
+                          a.q.n = static_cast<uint32_t>(m);
+                          a.tmax = tmax ? e->q_tmax.ptr : nullptr;
+                          a.out = e->q_occl.ptr;
+                          a.mask = mask;
+                          return rb::launch_occluded(p, a, e->stream, li);
+                      });
+}
+
+// `bytes` of device memory of the engine's device at p, aligned to `align`?
+int device_range(rb_engine* e, const void* p, size_t bytes, size_t align, const char* what) {
+    hipPointerAttribute_t attr{};
+    const hipError_t st = hipPointerGetAttributes(&attr, p);
+    if (st != hipSuccess) (void)hipGetLastError();   // a pointer the runtime does not know: pageable host memory
+    if (st != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != e->device)
+        return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s is not device memory of device %d", what, e->device);
+    if (reinterpret_cast<uintptr_t>(p) % align != 0u) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s is not %zu-byte aligned", what, align);
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) {
+        (void)hipGetLastError();
+        return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: its allocation is unknown to the runtime", what);
+    }
+    const size_t off = static_cast<size_t>(static_cast<const char*>(p) - static_cast<const char*>(base));
+    if (off > size || bytes > size - off) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: its allocation ends before %zu bytes", what, bytes);
+    return RB_OK;
+}
+
+int occluded_device_locked(rb_engine* e, const rb_ray* d_rays, const float* d_tmax, size_t n, uint32_t mask, uint8_t* d_out) {
+    int rc = device_range(e, d_rays, n * sizeof(rb_ray), 16, "d_rays");
+    if (!rc && d_tmax) rc = device_range(e, d_tmax, n * sizeof(float), 4, "d_tmax");
+    if (!rc) rc = device_range(e, d_out, n, 1, "d_out");
+    if (rc) return rc;
+    return device_query_locked(e, [&](const rb::KParams& p, rb::LaunchInfo* li) {
+        rb::OcclArgs a{};
+        a.q.rays = d_rays;
+        a.q.n = static_cast<uint32_t>(n);
+        a.tmax = d_tmax;
+        a.out = d_out;
+        a.mask = mask;
+        return rb::launch_occluded(p, a, e->stream, li);
+    });
+}
+
+int cast_rays_device_locked(rb_engine* e, const rb_ray* d_rays, size_t n, rb_hit* d_hits, rb_surface* d_surf) {
+    int rc = device_range(e, d_rays, n * sizeof(rb_ray), 16, "d_rays");
+    if (!rc) rc = device_range(e, d_hits, n * sizeof(rb_hit), 16, "d_hits");
+    if (!rc && d_surf) rc = device_range(e, d_surf, n * sizeof(rb_surface), 16, "d_surf");
+    if (rc) return rc;
+    return device_query_locked(e, [&](const rb::KParams& p, rb::LaunchInfo* li) {
+        rb::QueryArgs q{};
+        q.rays = d_rays;
+        q.n = static_cast<uint32_t>(n);
+        q.hits = d_hits;
+        q.surf = d_surf;
+        return rb::launch_query(p, q, e->stream, li);
+    });
+}
+
+// ---- path-traced radiance along given rays (rb_abi.h)
+// rays or pixels per piece of at most `limit` (ray or pixel, sample) items: whole blocks of 64, never a part of one's samples
+// (samples <= 65536: at least one block)
+size_t radiance_piece(size_t limit, uint32_t samples) { return std::max<size_t>((limit / samples) & ~size_t(63), 64); }
+
+// the scratch of one piece: a colour per item and the queue word; `records`: a ray record per item too (rays made on the device)
+int radiance_scratch(rb_engine* e, size_t piece, uint32_t samples, bool records) {
+    const size_t items = ((piece + 63) / 64) * 64 * samples;
+    if (records) HIP_TRY(e, e->q_rays.reserve(items));
+    HIP_TRY(e, e->rad_colors.reserve(items * 4));
+    HIP_TRY(e, e->rad_queue.reserve(16));
+    return RB_OK;
+}
+
+rb::RadArgs trace_args(rb_engine* e, const rb_ray* rays, const uint32_t* seeds, rb_radiance* out, size_t done, size_t m,
+                       uint32_t first_sample, uint32_t samples) {
+    rb::RadArgs a{};
+    a.rays = rays;
+    a.seeds = seeds;
+    a.colors = e->rad_colors.ptr;
+    a.out = out;
+    a.queue = e->rad_queue.ptr;
+    a.n = static_cast<uint32_t>(m);
+    a.seed_base = static_cast<uint32_t>(done);
+    a.first_sample = first_sample;
+    a.samples = samples;
+    return a;
+}
+
+int trace_rays_locked(rb_engine* e, const rb_ray* rays, const uint32_t* seeds, size_t n, uint32_t first_sample, uint32_t samples,
+                      rb_radiance* out) {
+    rb::KParams p{};
+    int rc = query_prologue(e, &p);
+    if (rc || n == 0) return rc;
+    const size_t piece = std::min(n, radiance_piece(RB_TRACE_PIECE_ITEMS, samples));
+    rc = radiance_scratch(e, piece, samples, false);
+    if (rc) return rc;
+    HIP_TRY(e, e->q_rays.reserve(piece));
+    if (seeds) HIP_TRY(e, e->rad_seeds.reserve(piece));
+    HIP_TRY(e, e->rad_out.reserve(piece));
+    return run_pieces(e, "radiance", piece, n, {{rays, e->q_rays.ptr, sizeof(rb_ray)}, {seeds, e->rad_seeds.ptr, sizeof(uint32_t)}},
+                      {{out, e->rad_out.ptr, sizeof(rb_radiance)}}, [&](size_t done, size_t m, rb::LaunchInfo* li) {
+                          const rb::RadArgs a = trace_args(e, e->q_rays.ptr, seeds ? e->rad_seeds.ptr : nullptr, e->rad_out.ptr, done, m, first_sample, samples);
+                          return rb::launch_radiance(p, a, e->stream, li);
+                      });
+}
+
+// every piece queued between the query's two events on the caller's buffers (the pieces share the colour scratch in stream
+// order); nothing is waited for
+int trace_rays_device_locked(rb_engine* e, const rb_ray* d_rays, const uint32_t* d_seeds, size_t n, uint32_t first_sample,
+                             uint32_t samples, rb_radiance* d_out) {
+    int rc = device_range(e, d_rays, n * sizeof(rb_ray), 16, "d_rays");
+    if (!rc && d_seeds) rc = device_range(e, d_seeds, n * sizeof(uint32_t), 4, "d_seeds");
+    if (!rc) rc = device_range(e, d_out, n * sizeof(rb_radiance), 16, "d_out");
+    if (rc) return rc;
+    const size_t piece = std::min(n, radiance_piece(RB_TRACE_PIECE_ITEMS, samples));
+    return device_query_locked(e, [&](const rb::KParams& p, rb::LaunchInfo* li) {
+        if (radiance_scratch(e, piece, samples, false)) return static_cast<int>(hipErrorOutOfMemory);
+        for (size_t done = 0; done < n; done += piece) {
+            const size_t m = std::min(piece, n - done);
+            const rb::RadArgs a = trace_args(e, d_rays + done, d_seeds ? d_seeds + done : nullptr, d_out + done, done, m, first_sample, samples);
+            const int st = rb::launch_radiance(p, a, e->stream, li);
+            if (st) return st;
+        }
+        return 0;
+    });
+}
+
+// ---- camera rays made on the device (rb_abi.h)
+// one piece, queued: the generator into the record scratch, the k_cam kernel of the scene's walk over it, the sum into `out`
+int camera_piece(rb_engine* e, const rb::KParams& p, const rb_camera_ex& cam, uint64_t first_pixel, size_t done, size_t m,
+                 uint32_t first_sample, uint32_t samples, rb_radiance* out, rb::LaunchInfo* li) {
+    while (e->ev_cam.size() < 2 * (e->cam_pieces + 1)) {
+        hipEvent_t x = nullptr;
+        if (const hipError_t st = hipEventCreate(&x)) return static_cast<int>(st);
+        e->ev_cam.push_back(x);
+    }
+    hipEvent_t* const ev = &e->ev_cam[2 * e->cam_pieces];
+    rb::CamGenArgs g{};
+    g.cam = cam;
+    g.recs = e->q_rays.ptr;
+    g.first_pixel = static_cast<uint32_t>(first_pixel + done);
+    g.n = static_cast<uint32_t>(m);
+    g.first_sample = first_sample;
+    g.samples = samples;
+    if (const hipError_t st = hipEventRecord(ev[0], e->stream)) return static_cast<int>(st);
+    const int st = rb::launch_camera_rays(g, e->stream);
+    if (st) return st;
+    if (const hipError_t st1 = hipEventRecord(ev[1], e->stream)) return static_cast<int>(st1);
+    e->cam_pieces++;
+    return rb::launch_radiance(p, trace_args(e, e->q_rays.ptr, nullptr, out, done, m, first_sample, samples), e->stream, li, true);
+}
+
+int trace_camera_locked(rb_engine* e, const rb_camera_ex& cam, uint64_t first_pixel, size_t n, uint32_t first_sample, uint32_t samples,
+                        rb_radiance* out) {
+    rb::KParams p{};
+    e->cam_pieces = 0;
+    int rc = query_prologue(e, &p);
+    if (rc || n == 0) return rc;
+    const size_t piece = std::min(n, radiance_piece(RB_CAMERA_PIECE_ITEMS, samples));
+    rc = radiance_scratch(e, piece, samples, true);
+    if (rc) return rc;
+    HIP_TRY(e, e->rad_out.reserve(piece));
+    return run_pieces(e, "camera", piece, n, {}, {{out, e->rad_out.ptr, sizeof(rb_radiance)}}, [&](size_t done, size_t m, rb::LaunchInfo* li) {
+        return camera_piece(e, p, cam, first_pixel, done, m, first_sample, samples, e->rad_out.ptr, li);
+    });
+}
+
+// every piece queued between the query's two events (the pieces share the scratch in stream order); nothing is waited for
+int trace_camera_device_locked(rb_engine* e, const rb_camera_ex& cam, uint64_t first_pixel, size_t n, uint32_t first_sample,
+                               uint32_t samples, rb_radiance* d_out) {
+    const int rc = device_range(e, d_out, n * sizeof(rb_radiance), 16, "d_out");
+    if (rc) return rc;
+    const size_t piece = std::min(n, radiance_piece(RB_CAMERA_PIECE_ITEMS, samples));
+    e->cam_pieces = 0;
+    return device_query_locked(e, [&](const rb::KParams& p, rb::LaunchInfo* li) {
+        if (radiance_scratch(e, piece, samples, true)) return static_cast<int>(hipErrorOutOfMemory);
+        for (size_t done = 0; done < n; done += piece) {
+            const int st = camera_piece(e, p, cam, first_pixel, done, std::min(piece, n - done), first_sample, samples, d_out + done, li);
+            if (st) return st;
+        }
+        return 0;
+    });
+}
+
+// ---- refusals that several entry points share, each under the entry point's own name `who`; before a device is touched
+int ray_count_check(rb_engine* e, const char* who, size_t n) {
+    if (n > 0x7FFFFFFFull - 63ull) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s takes at most 2^31 - 64 rays per call", who);
+    return RB_OK;
+}
+
+// `per`: what the samples are taken of, "ray" or "pixel"
+int samples_check(rb_engine* e, const char* who, const char* per, uint32_t first_sample, uint32_t samples) {
+    if (samples == 0 || samples > 65536u) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s takes 1 .. 65536 samples per %s, not %u", who, per, samples);
+    if (static_cast<uint64_t>(first_sample) + samples > 0xFFFFFFFFull)
+        return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: first_sample + samples = %u + %u does not fit 32 bits", who, first_sample, samples);
+    return RB_OK;
+}
+
+// the refusals the two forms of rb_trace_rays share
+int trace_rays_check(rb_engine* e, const char* who, const void* rays, size_t n, uint32_t first_sample, uint32_t samples, const void* out) {
+    int rc = samples_check(e, who, "ray", first_sample, samples);
+    if (!rc) rc = ray_count_check(e, who, n);
+    if (rc) return rc;
+    if (n > 0 && (!rays || !out)) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: rays / out is NULL", who);
+    return RB_OK;
+}
+
+// the refusals every camera entry point shares; before a device is touched (e may be NULL: rb_camera_rays)
+int camera_check(rb_engine* e, const char* who, const rb_camera_ex* cam, uint64_t first_pixel, size_t n, uint32_t first_sample, uint32_t samples) {
+    const rb_camera_ex& c = *cam;
+    if (c.kind != RB_CAM_PERSPECTIVE && c.kind != RB_CAM_ORTHO && c.kind != RB_CAM_EQUIRECT)
+        return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: unknown camera kind %u", who, c.kind);
+    if ((c.flags & ~static_cast<uint32_t>(RB_CAM_NO_JITTER)) != 0u) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: unknown flag bits 0x%x", who, c.flags);
+    if (c._reserved[0] || c._reserved[1] || c._reserved[2]) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: _reserved must be 0", who);
+    if (c.width == 0u || c.height == 0u || c.width > (1u << 24) || c.height > (1u << 24))
+        return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: width and height are 1 .. 2^24, not %u x %u", who, c.width, c.height);
+    const uint64_t pixels = static_cast<uint64_t>(c.width) * c.height;
+    if (pixels >= (1ull << 31)) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: an image of %u x %u pixels is too large", who, c.width, c.height);
+    if (first_pixel > pixels || n > pixels - first_pixel)
+        return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: pixels [%llu, +%zu) leave the image of %llu pixels", who,
+                        static_cast<unsigned long long>(first_pixel), n, static_cast<unsigned long long>(pixels));
+    if (const int rc = samples_check(e, who, "pixel", first_sample, samples)) return rc;
+    if (static_cast<uint64_t>(n) * samples > 0x7FFFFFFFull - 63ull)
+        return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s takes at most 2^31 - 64 (pixel, sample) items per call", who);
+    // (pos may be non-finite: its rays are invalid by rb_cast_rays' rule and weigh 0)
+    const float* const basis[] = {c.right, c.up, c.forward};
+    bool finite = std::isfinite(c.tan_half_fov) && std::isfinite(c.half_width) && std::isfinite(c.half_height) &&
+                  std::isfinite(c.lens_radius) && std::isfinite(c.focus_distance);
+    for (const float* v : basis) finite = finite && std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]);
+    if (!finite) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: a field of the camera other than pos is not finite", who);
+    if (c.kind == RB_CAM_PERSPECTIVE && (!(c.tan_half_fov > 0.0f) || c.lens_radius < 0.0f || (c.lens_radius > 0.0f && !(c.focus_distance > 0.0f))))
+        return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: a perspective camera needs tan_half_fov > 0, lens_radius >= 0 and, with a lens, focus_distance > 0", who);
+    if (c.kind == RB_CAM_ORTHO && (!(c.half_width > 0.0f) || !(c.half_height > 0.0f)))
+        return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: an orthographic camera needs half_width > 0 and half_height > 0", who);
+    return RB_OK;
+}
+
+// ---- the denoiser (rb_abi.h).  Like a query it is queued on the engine's stream behind whatever runs
+// there, reads the scene and the committed accumulation, and writes buffers of its own.
+rb::GuidePlanes guide_planes(rb_engine* e) { return rb::GuidePlanes{e->dn_nt.ptr, e->dn_pc.ptr, e->dn_al.ptr}; }
+
+int denoise_ready(rb_engine* e) {
+    if (rb::is_group(e)) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "the denoiser does not take a multi-device handle: a tap would cross a stripe boundary");
+    rb::set_device(e);
+    if (e->opt.shard_count > 1) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "the denoiser does not take a sharded engine: a tap would cross a stripe boundary");
+    const int rc = require_ready(e);
+    if (rc) return rc;
+    for (hipEvent_t& x : e->ev_dn)
+        if (!x) HIP_TRY(e, hipEventCreate(&x));
+    return RB_OK;
+}
+
+// the guide planes of the current scene: the pixel-centre rays through the query kernels straight into device memory, one pack
+int ensure_guides(rb_engine* e) {
+    e->last_guide_ms = 0.0f;
+    if (e->dn_guides_valid) return RB_OK;
+    rb::KParams p{};
+    int rc = ensure_prepared(e);
+    if (!rc) rc = scene_params(e, &p);
+    if (rc) return rc;
+    const uint32_t w = e->width, h = e->height;
+    const size_t n = static_cast<size_t>(w) * h;
+    rb::DevBuf<rb_hit> hits;       // the records live until the pack has read them
+    rb::DevBuf<rb_surface> surf;
+    HIP_TRY(e, hits.resize(n));
+    HIP_TRY(e, surf.resize(n));
+    HIP_TRY(e, e->dn_nt.resize(n * 4));
+    HIP_TRY(e, e->dn_pc.resize(n * 4));
+    HIP_TRY(e, e->dn_al.resize(n * 4));
+    if (n) {
+        HIP_TRY(e, hipEventRecord(e->ev_dn[0], e->stream));
+        const uint32_t piece_rows = frame_piece_rows(w);   // as rb_render_hits
+        for (uint32_t r0 = 0; r0 < h; r0 += piece_rows) {
+            rb::QueryArgs q{};
+            q.win_y = r0;
+            q.win_w = w;
+            q.win_h = std::min(piece_rows, h - r0);
+            q.win_global = 1u;
+            q.hits = hits.ptr + static_cast<size_t>(r0) * w;
+            q.surf = surf.ptr + static_cast<size_t>(r0) * w;
+            const int st = rb::launch_query(p, q, e->stream, nullptr);
+            if (st) return rb::fail(e, RB_ERR_DEVICE, "query kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
+        }
+        const int st = rb::launch_guide_pack(p.u, hits.ptr, surf.ptr, w, h, guide_planes(e), e->stream);
+        if (st) return rb::fail(e, RB_ERR_DEVICE, "guide pack launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
+        HIP_TRY(e, hipEventRecord(e->ev_dn[1], e->stream));
+        HIP_TRY(e, hipStreamSynchronize(e->stream));
+        HIP_TRY(e, hipEventElapsedTime(&e->last_guide_ms, e->ev_dn[0], e->ev_dn[1]));
+    }
+    e->dn_guides_valid = true;
+    return RB_OK;
+}
+
+int denoise_params_check(const rb_engine* e, const rb_denoise_params* prm) {
+    const char* why = nullptr;
+    if (!rb::denoise_params_valid(*prm, &why)) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "rb_denoise_params: %s", why);
+    return RB_OK;
+}
+
+// device == true: the outputs are the caller's device buffers and nothing is waited for
+int denoise_locked(rb_engine* e, const rb_denoise_params* prm, uint8_t* rgba_out, float* linear_out, bool device) {
+    int rc = denoise_ready(e);
+    if (!rc) rc = denoise_params_check(e, prm);
+    if (rc) return rc;
+    if (!rgba_out && !linear_out) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "rgba_out and linear_out are both NULL");
+    const size_t n = static_cast<size_t>(e->width) * e->height;
+    if (device) {
+        if (rgba_out) rc = device_range(e, rgba_out, n * 4, 4, "d_rgba_out");
+        if (!rc && linear_out) rc = device_range(e, linear_out, n * 16, 16, "d_linear_out");
+        if (rc) return rc;
+    }
+    rc = ensure_guides(e);
+    if (rc) return rc;
+    e->denoise_ms_pending = false;
+    e->last_denoise_ms = 0.0f;
+    if (n == 0) return RB_OK;
+    rb::DenoiseArgs a{};
+    a.w = e->width;
+    a.h = e->height;
+    a.accum = e->slot[e->cur].accum.ptr;
+    a.g = guide_planes(e);
+    for (int k = 0; k < 2; ++k) {
+        HIP_TRY(e, e->dn_r[k].resize(n * 4));
+        a.r[k] = e->dn_r[k].ptr;
+    }
+    if (device) {
+        a.rgba_out = reinterpret_cast<uint32_t*>(rgba_out);
+        a.linear_out = linear_out;
+    } else {
+        if (rgba_out) {
+            HIP_TRY(e, e->dn_rgba.resize(n));
+            a.rgba_out = e->dn_rgba.ptr;
+        }
+        if (linear_out) {
+            HIP_TRY(e, e->dn_linear.resize(n * 4));
+            a.linear_out = e->dn_linear.ptr;
+        }
+    }
+    HIP_TRY(e, hipEventRecord(e->ev_dn[2], e->stream));
+    const int st = rb::launch_denoise(*prm, a, e->stream);
+    if (st) return rb::fail(e, RB_ERR_DEVICE, "denoise kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
+    HIP_TRY(e, hipEventRecord(e->ev_dn[3], e->stream));
+    if (device) {
+        e->denoise_ms_pending = true;
+        return RB_OK;
+    }
+    if (rgba_out) rc = query_copy_out(e, rgba_out, e->dn_rgba.ptr, n * 4, page_locked(rgba_out));
+    if (!rc && linear_out) rc = query_copy_out(e, linear_out, e->dn_linear.ptr, n * 16, page_locked(linear_out));
+    if (rc) return rc;
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    HIP_TRY(e, hipEventElapsedTime(&e->last_denoise_ms, e->ev_dn[2], e->ev_dn[3]));
+    return RB_OK;
+}
+
+int denoise_guides_locked(rb_engine* e, rb_guide* guides_out) {
+    int rc = denoise_ready(e);
+    if (!rc) rc = ensure_guides(e);
+    if (rc) return rc;
+    const size_t n = static_cast<size_t>(e->width) * e->height;
+    if (n == 0) return RB_OK;
+    rb::DevBuf<rb_guide> joined;
+    HIP_TRY(e, joined.resize(n));
+    const int st = rb::launch_guide_join(guide_planes(e), n, joined.ptr, e->stream);
+    if (st) return rb::fail(e, RB_ERR_DEVICE, "guide join launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
+    rc = query_copy_out(e, guides_out, joined.ptr, n * sizeof(rb_guide), page_locked(guides_out));
+    if (rc) return rc;
+    HIP_TRY(e, hipStreamSynchronize(e->stream));   // `joined` is freed on return
+    return RB_OK;
+}
+
+// the engine that answers a query (a multi-device handle: devices[0], which holds the whole scene), made current
+rb_engine* answering(rb_engine* e) {
+    rb_engine* const t = rb::is_group(e) ? e->parts[0].get() : e;
+    rb::set_device(t);
+    return t;
+}
+
+int answered(rb_engine* e, rb_engine* t, int rc) {
+    if (rc && t != e) copy_error(e, t);
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rb_cast_rays(rb_engine* e, const rb_ray* rays, size_t n, rb_hit* hits_out, rb_surface* surf_out) {
+    if (!e) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (const int rc = ray_count_check(e, "rb_cast_rays", n)) return rc;
+    if (n > 0 && (!rays || !hits_out)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "rays / hits_out is NULL");
+    rb_engine* const t = answering(e);
+    return answered(e, t, cast_rays_locked(t, rays, n, hits_out, surf_out));
+}
+
+int rb_render_hits(rb_engine* e, rb_hit* hits_out, rb_surface* surf_out) {
+    if (!e) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (!hits_out) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "hits_out is NULL");
+    rb_engine* const t = answering(e);
+    int rc = require_ready(t);
+    if (!rc) {
+        // a multi-device handle: the whole frame on devices[0] (one ray per pixel is not worth a gather); a sharded engine: its own rows
+        const bool sharded = t == e && t->opt.shard_count > 1;
+        rc = pixel_hits_locked(t, 0, 0, t->width, sharded ? t->padded_rows : t->height, !sharded, hits_out, surf_out);
+    }
+    return answered(e, t, rc);
+}
+
+int rb_pick(rb_engine* e, uint32_t px, uint32_t py, rb_hit* hit_out, rb_surface* surf_out) {
+    if (!e) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (!hit_out) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "hit_out is NULL");
+    rb_engine* const t = answering(e);
+    int rc = require_ready(t);
+    if (!rc && (px >= t->width || py >= t->height)) rc = rb::fail(t, RB_ERR_INVALID_OPTIONS, "pixel (%u, %u) is outside the %u x %u image", px, py, t->width, t->height);
+    if (!rc) rc = pixel_hits_locked(t, px, py, 1, 1, true, hit_out, surf_out);
+    return answered(e, t, rc);
+}
+
+int rb_occluded(rb_engine* e, const rb_ray* rays, const float* tmax, size_t n, uint32_t mask, uint8_t* out) {
+    if (!e) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (const int rc = ray_count_check(e, "rb_occluded", n)) return rc;
+    if (mask > RB_MASK_ALL) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "mask has bits above RB_MASK_ALL");
+    if (n > 0 && (!rays || !out)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "rays / out is NULL");
+    rb_engine* const t = answering(e);
+    return answered(e, t, occluded_locked(t, rays, tmax, n, mask, out));
+}
+
+int rb_occluded_device(rb_engine* e, const rb_ray* d_rays, const float* d_tmax, size_t n, uint32_t mask, uint8_t* d_out) {
+    if (!e) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (const int rc = ray_count_check(e, "rb_occluded_device", n)) return rc;
+    if (mask > RB_MASK_ALL) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "mask has bits above RB_MASK_ALL");
+    if (n > 0 && (!d_rays || !d_out)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "d_rays / d_out is NULL");
+    rb_engine* const t = answering(e);
+    if (n == 0) return answered(e, t, require_ready(t));
+    return answered(e, t, occluded_device_locked(t, d_rays, d_tmax, n, mask, d_out));
+}
+
+int rb_cast_rays_device(rb_engine* e, const rb_ray* d_rays, size_t n, rb_hit* d_hits, rb_surface* d_surf) {
+    if (!e) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (const int rc = ray_count_check(e, "rb_cast_rays_device", n)) return rc;
+    if (n > 0 && (!d_rays || !d_hits)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "d_rays / d_hits is NULL");
+    rb_engine* const t = answering(e);
+    if (n == 0) return answered(e, t, require_ready(t));
+    return answered(e, t, cast_rays_device_locked(t, d_rays, n, d_hits, d_surf));
+}
+
+int rb_trace_rays(rb_engine* e, const rb_ray* rays, const uint32_t* seeds, size_t n, uint32_t first_sample, uint32_t samples,
+                  rb_radiance* out) {
+    if (!e) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (const int rc = trace_rays_check(e, "rb_trace_rays", rays, n, first_sample, samples, out)) return rc;
+    rb_engine* const t = answering(e);
+    return answered(e, t, trace_rays_locked(t, rays, seeds, n, first_sample, samples, out));
+}
+
+int rb_trace_rays_device(rb_engine* e, const rb_ray* d_rays, const uint32_t* d_seeds, size_t n, uint32_t first_sample,
+                         uint32_t samples, rb_radiance* d_out) {
+    if (!e) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (const int rc = trace_rays_check(e, "rb_trace_rays_device", d_rays, n, first_sample, samples, d_out)) return rc;
+    rb_engine* const t = answering(e);
+    if (n == 0) return answered(e, t, require_ready(t));
+    return answered(e, t, trace_rays_device_locked(t, d_rays, d_seeds, n, first_sample, samples, d_out));
+}
+
+int rb_camera_rays(int32_t device, const rb_camera_ex* cam, uint64_t first_pixel, size_t n_pixels, uint32_t first_sample,
+                   uint32_t samples, rb_ray* rays_out, uint32_t* seeds_out) {
+    if (n_pixels > 0 && (!cam || !rays_out || !seeds_out)) return rb::fail(nullptr, RB_ERR_NULL_ARGUMENT, "cam / rays_out / seeds_out is NULL");
+    if (cam)
+        if (const int rc = camera_check(nullptr, "rb_camera_rays", cam, first_pixel, n_pixels, first_sample, samples)) return rc;
+    if (n_pixels == 0) return RB_OK;
+    if (device >= 0 && hipSetDevice(device) != hipSuccess) return rb::fail(nullptr, RB_ERR_DEVICE, "hipSetDevice(%d) failed", device);
+    const size_t items = n_pixels * samples, piece = std::min<size_t>(items, size_t(1) << 22);   // 128 + 16 MiB of scratch
+    rb::DevBuf<rb_ray> d_rays;
+    rb::DevBuf<uint32_t> d_seeds;
+    hipStream_t stream = nullptr;
+    hipError_t st = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
+    if (st == hipSuccess) st = d_rays.resize(piece);
+    if (st == hipSuccess) st = d_seeds.resize(piece);
+    for (size_t done = 0; done < items && st == hipSuccess; done += piece) {
+        const size_t m = std::min(piece, items - done);
+        rb::CamGenArgs g{};
+        g.cam = *cam;
+        g.recs = d_rays.ptr;
+        g.seeds = d_seeds.ptr;
+        g.first_pixel = static_cast<uint32_t>(first_pixel);
+        g.n = static_cast<uint32_t>(m);
+        g.item_base = static_cast<uint32_t>(done);
+        g.first_sample = first_sample;
+        g.samples = samples;
+        g.linear = 1u;
+        st = static_cast<hipError_t>(rb::launch_camera_rays(g, stream));
+        if (st == hipSuccess) st = hipMemcpyAsync(rays_out + done, d_rays.ptr, m * sizeof(rb_ray), hipMemcpyDeviceToHost, stream);
+        if (st == hipSuccess) st = hipMemcpyAsync(seeds_out + done, d_seeds.ptr, m * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
+        if (st == hipSuccess) st = hipStreamSynchronize(stream);   // the scratch is the next piece's
+    }
+    if (stream) (void)hipStreamSynchronize(stream);   // (the buffers are freed on return, after this)
+    if (stream) (void)hipStreamDestroy(stream);
+    if (st != hipSuccess) return rb::fail(nullptr, RB_ERR_DEVICE, "rb_camera_rays failed: %s", hipGetErrorString(st));
+    return RB_OK;
+}
+
+int rb_trace_camera(rb_engine* e, const rb_camera_ex* cam, uint64_t first_pixel, size_t n_pixels, uint32_t first_sample,
+                    uint32_t samples, rb_radiance* out) {
+    if (!e) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (n_pixels > 0 && (!cam || !out)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "rb_trace_camera: cam / out is NULL");
+    if (cam)
+        if (const int rc = camera_check(e, "rb_trace_camera", cam, first_pixel, n_pixels, first_sample, samples)) return rc;
+    rb_engine* const t = answering(e);
+    if (n_pixels == 0) return answered(e, t, require_ready(t));
+    return answered(e, t, trace_camera_locked(t, *cam, first_pixel, n_pixels, first_sample, samples, out));
+}
+
+int rb_trace_camera_device(rb_engine* e, const rb_camera_ex* cam, uint64_t first_pixel, size_t n_pixels, uint32_t first_sample,
+                           uint32_t samples, rb_radiance* d_out) {
+    if (!e) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (n_pixels > 0 && (!cam || !d_out)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "rb_trace_camera_device: cam / d_out is NULL");
+    if (cam)
+        if (const int rc = camera_check(e, "rb_trace_camera_device", cam, first_pixel, n_pixels, first_sample, samples)) return rc;
+    rb_engine* const t = answering(e);
+    if (n_pixels == 0) return answered(e, t, require_ready(t));
+    return answered(e, t, trace_camera_device_locked(t, *cam, first_pixel, n_pixels, first_sample, samples, d_out));
+}
+
+int rb_denoise_default_params(rb_denoise_params* p) {
+    if (!p) return RB_ERR_NULL_ARGUMENT;
+    *p = rb_denoise_params{};
+    p->iterations = 3;   // chosen on the quality test: DESIGN.md section 13.4
+    p->normal_power_log2 = 3;
+    p->sigma_depth = 0.02f;
+    p->sigma_color = 0.0f;   // the colour term is off: at a few samples per pixel it takes fireflies for edges
+    p->albedo_floor = 0.01f;
+    return RB_OK;
+}
+
+int rb_denoise(rb_engine* e, const rb_denoise_params* params, uint8_t* rgba_out, float* linear_out) {
+    if (!e || !params) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    return denoise_locked(e, params, rgba_out, linear_out, false);
+}
+
+int rb_denoise_device(rb_engine* e, const rb_denoise_params* params, uint8_t* d_rgba_out, float* d_linear_out) {
+    if (!e || !params) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    return denoise_locked(e, params, d_rgba_out, d_linear_out, true);
+}
+
+int rb_denoise_guides(rb_engine* e, rb_guide* guides_out) {
+    if (!e) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (!guides_out) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "guides_out is NULL");
+    return denoise_guides_locked(e, guides_out);
+}
+
+int rb_last_denoise_ms(rb_engine* e, float* ms, float* guide_build_ms) {
+    if (!e || !ms) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (e->denoise_ms_pending) {   // rb_denoise_device returned without waiting: its events are read here
+        rb::set_device(e);
+        HIP_TRY(e, hipEventSynchronize(e->ev_dn[3]));
+        HIP_TRY(e, hipEventElapsedTime(&e->last_denoise_ms, e->ev_dn[2], e->ev_dn[3]));
+        e->denoise_ms_pending = false;
+    }
+    *ms = e->last_denoise_ms;
+    if (guide_build_ms) *guide_build_ms = e->last_guide_ms;
+    return RB_OK;
+}
+
+int rb_denoise_buffers(int32_t device, const rb_denoise_params* params, uint32_t w, uint32_t h, const float* color4,
+                       const rb_guide* guides, float* out4, uint8_t* rgba_out) {
+    if (!params || !color4 || !guides) return rb::fail(nullptr, RB_ERR_NULL_ARGUMENT, "params / color4 / guides is NULL");
+    if (!out4 && !rgba_out) return rb::fail(nullptr, RB_ERR_NULL_ARGUMENT, "out4 and rgba_out are both NULL");
+    if (const int rc = denoise_params_check(nullptr, params)) return rc;
+    const size_t n = static_cast<size_t>(w) * h;
+    if (n >= (1ull << 31)) return rb::fail(nullptr, RB_ERR_INVALID_OPTIONS, "a frame of %u x %u pixels is too large", w, h);
+    if (n == 0) return RB_OK;
+    if (device >= 0 && hipSetDevice(device) != hipSuccess) return rb::fail(nullptr, RB_ERR_DEVICE, "hipSetDevice(%d) failed", device);
+    rb::DevBuf<float> d_color, d_nt, d_pc, d_al, d_r0, d_r1, d_linear;
+    rb::DevBuf<rb_guide> d_guides;
+    rb::DevBuf<uint32_t> d_rgba;
+    hipStream_t stream = nullptr;
+    hipError_t st = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
+    for (rb::DevBuf<float>* b : {&d_color, &d_nt, &d_pc, &d_al, &d_r0, &d_r1})
+        if (st == hipSuccess) st = b->resize(n * 4);
+    if (st == hipSuccess) st = d_guides.resize(n);
+    if (st == hipSuccess && out4) st = d_linear.resize(n * 4);
+    if (st == hipSuccess && rgba_out) st = d_rgba.resize(n);
+    if (st == hipSuccess) st = hipMemcpyAsync(d_color.ptr, color4, n * 16, hipMemcpyHostToDevice, stream);
+    if (st == hipSuccess) st = hipMemcpyAsync(d_guides.ptr, guides, n * sizeof(rb_guide), hipMemcpyHostToDevice, stream);
+    rb::DenoiseArgs a{};
+    a.w = w;
+    a.h = h;
+    a.color4 = d_color.ptr;
+    a.g = rb::GuidePlanes{d_nt.ptr, d_pc.ptr, d_al.ptr};
+    a.r[0] = d_r0.ptr;
+    a.r[1] = d_r1.ptr;
+    a.linear_out = d_linear.ptr;
+    a.rgba_out = d_rgba.ptr;
+    if (st == hipSuccess) st = static_cast<hipError_t>(rb::launch_guide_split(d_guides.ptr, n, a.g, stream));
+    if (st == hipSuccess) st = static_cast<hipError_t>(rb::launch_denoise(*params, a, stream));
+    if (st == hipSuccess && out4) st = hipMemcpyAsync(out4, d_linear.ptr, n * 16, hipMemcpyDeviceToHost, stream);
+    if (st == hipSuccess && rgba_out) st = hipMemcpyAsync(rgba_out, d_rgba.ptr, n * 4, hipMemcpyDeviceToHost, stream);
+    if (st == hipSuccess) st = hipStreamSynchronize(stream);
+    if (stream) (void)hipStreamSynchronize(stream);   // (the buffers are freed on return, after this)
+    if (stream) (void)hipStreamDestroy(stream);
+    if (st != hipSuccess) return rb::fail(nullptr, RB_ERR_DEVICE, "rb_denoise_buffers failed: %s", hipGetErrorString(st));
+    return RB_OK;
+}
+
+const char* rb_last_query_kernel_name(const rb_engine* e) {
+    if (!e) return "";
+    return rb::is_group(e) ? e->parts[0]->last_query_kernel_name : e->last_query_kernel_name;
+}
+
+int rb_last_query_ms(rb_engine* e, float* ms) {
+    if (!e || !ms) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    rb_engine* const t = rb::is_group(e) ? e->parts[0].get() : e;
+    if (t->query_ms_pending) {   // a device form returned without waiting: its events are read here
+        rb::set_device(t);
+        HIP_TRY(e, hipEventSynchronize(t->ev_q[1]));
+        HIP_TRY(e, hipEventElapsedTime(&t->last_query_ms, t->ev_q[0], t->ev_q[1]));
+        t->query_ms_pending = false;
+    }
+    *ms = t->last_query_ms;
+    return RB_OK;
+}
+
+int rb_last_camera_rays_ms(rb_engine* e, float* ms) {
+    if (!e || !ms) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    rb_engine* const t = rb::is_group(e) ? e->parts[0].get() : e;
+    *ms = 0.0f;
+    if (t->cam_pieces == 0) return RB_OK;
+    rb::set_device(t);
+    HIP_TRY(e, hipEventSynchronize(t->ev_cam[2 * t->cam_pieces - 1]));
+    for (size_t i = 0; i < t->cam_pieces; i++) {
+        float piece_ms = 0.0f;
+        HIP_TRY(e, hipEventElapsedTime(&piece_ms, t->ev_cam[2 * i], t->ev_cam[2 * i + 1]));
+        *ms += piece_ms;
+    }
+    return RB_OK;
+}
+
+}  // extern "C"

@@ -386,7 +386,7 @@ DEV bool occl_early(const KParams& p, uint32_t mask, f3 o, f3 d, float tmax, uin
     return false;
 }
 
-// intersect_bvh's reference walk (never the library's own tree: launch_occluded clears fast_nodes as launch_query does): the
+// intersect_bvh's reference walk (never the library's own tree: query_walk clears fast_nodes for every query): the
 // same nodes entered by the same boolean box tests, the same triangles tested, test_slot's acceptance against tmax
 template <bool MULTI>
 DEV bool occl_bvh(const KParams& p, f3 o, f3 d, float tmax, uint32_t* stack, uint32_t stride) {
@@ -601,21 +601,20 @@ int launch_query(const KParams& p_, const QueryArgs& q, void* stream_, LaunchInf
     if (waves == 0u || waves > 0x7FFFFFFFull) return waves == 0u ? 0 : (int)hipErrorInvalidValue;
     li.grid = (uint32_t)((waves + kQueryBlock / 64u - 1u) / (kQueryBlock / 64u));
     li.lds_bytes = (size_t)kStackEntryBytes * p.stack_depth * kQueryBlock + (kQueryBlock / 64u) * kQueryWaveLds;
-    // the walk, by launch_render's rule for a render of this scene with these flags
-    const bool multi = p.u.bvh_node_count > 1u && !p.no_leaf_stepping;
     const dim3 grid(li.grid), block(li.block);
-    if (multi && p.chunk_nodes != nullptr) {
-        li.kernel_name = "k_query_chunk";
-        hipLaunchKernelGGL(k_query_chunk, grid, block, li.lds_bytes, stream, p, q);
-    } else {
-        p.fast_nodes = nullptr;   // the library's own tree has no query form: the reference walk over the caller's tree
-        if (p.u.bvh_node_count > 1u || p.sph_nodes != nullptr) {
+    switch (query_walk(p)) {
+        case kWalkChunk:
+            li.kernel_name = "k_query_chunk";
+            hipLaunchKernelGGL(k_query_chunk, grid, block, li.lds_bytes, stream, p, q);
+            break;
+        case kWalkBvh:
             li.kernel_name = "k_query_bvh";
             hipLaunchKernelGGL(k_query<true>, grid, block, li.lds_bytes, stream, p, q);
-        } else {
+            break;
+        case kWalkPlain:
             li.kernel_name = "k_query";
             hipLaunchKernelGGL(k_query<false>, grid, block, li.lds_bytes, stream, p, q);
-        }
+            break;
     }
     if (info) *info = li;
     return (int)hipGetLastError();
@@ -632,22 +631,21 @@ int launch_occluded(const KParams& p_, const OcclArgs& a, void* stream_, LaunchI
     if (waves == 0u) return 0;
     li.grid = (uint32_t)((waves + kQueryBlock / 64u - 1u) / (kQueryBlock / 64u));
     li.lds_bytes = (size_t)kStackEntryBytes * p.stack_depth * kQueryBlock;
-    // the walk, by launch_query's rule
-    const bool multi = p.u.bvh_node_count > 1u && !p.no_leaf_stepping;
     const dim3 grid(li.grid), block(li.block);
-    if (multi && p.chunk_nodes != nullptr) {
-        li.kernel_name = "k_occl_chunk";
-        li.lds_bytes += (kQueryBlock / 64u) * kChunkWaveLds;
-        hipLaunchKernelGGL(k_occl_chunk, grid, block, li.lds_bytes, stream, p, a);
-    } else {
-        p.fast_nodes = nullptr;   // own-tree engines: the reference walk over the caller's tree, as k_query_bvh answers them
-        if (p.u.bvh_node_count > 1u || p.sph_nodes != nullptr) {
+    switch (query_walk(p)) {
+        case kWalkChunk:
+            li.kernel_name = "k_occl_chunk";
+            li.lds_bytes += (kQueryBlock / 64u) * kChunkWaveLds;
+            hipLaunchKernelGGL(k_occl_chunk, grid, block, li.lds_bytes, stream, p, a);
+            break;
+        case kWalkBvh:
             li.kernel_name = "k_occl_bvh";
             hipLaunchKernelGGL(k_occl<true>, grid, block, li.lds_bytes, stream, p, a);
-        } else {
+            break;
+        case kWalkPlain:
             li.kernel_name = "k_occl";
             hipLaunchKernelGGL(k_occl<false>, grid, block, li.lds_bytes, stream, p, a);
-        }
+            break;
     }
     if (info) *info = li;
     return (int)hipGetLastError();

@@ -562,32 +562,24 @@ int launch_radiance(const KParams& p_, const RadArgs& a_, void* stream_, LaunchI
     const uint64_t items = blocks64 * 64u * a.samples;
     if (a.rays == nullptr || a.out == nullptr || a.colors == nullptr || a.queue == nullptr || a.samples == 0u || items > RB_TRACE_PIECE_ITEMS)
         return (int)hipErrorInvalidValue;
-    // the walk, by launch_query's rule
-    enum Variant { PLAIN, BVH, CHUNK };
-    const bool multi = p.u.bvh_node_count > 1u && !p.no_leaf_stepping;
-    Variant v = PLAIN;
-    if (multi && p.chunk_nodes != nullptr) v = CHUNK;
-    else {
-        p.fast_nodes = nullptr;   // own-tree engines: the reference walk over the caller's tree, as k_query_bvh answers them
-        if (p.u.bvh_node_count > 1u || p.sph_nodes != nullptr) v = BVH;
-    }
+    const QueryWalk v = query_walk(p);
     static const char* const names[2][3] = {{"k_rad", "k_rad_bvh", "k_rad_chunk"}, {"k_cam", "k_cam_bvh", "k_cam_chunk"}};
     li.kernel_name = names[records ? 1 : 0][v];
-    li.lds_bytes = (size_t)kStackEntryBytes * p.stack_depth * kRadBlock + (v == CHUNK ? (kRadBlock / 64u) * kChunkWaveLds : 0u);
+    li.lds_bytes = (size_t)kStackEntryBytes * p.stack_depth * kRadBlock + (v == kWalkChunk ? (kRadBlock / 64u) * kChunkWaveLds : 0u);
     // the grid as launch_render sizes it: residency by registers, fewer blocks for a launch of few items
     const uint32_t max_blocks8 = stream_kernel_max_threads(8u) / 256u;   // 8 blocks per CU
     const uint32_t dense = (items >= (uint64_t)max_blocks8 * 4u * 1024u) ? 8u : 4u;
-    const uint32_t blocks_per_cu = p.blocks_per_cu ? p.blocks_per_cu : v == CHUNK ? (uint32_t)RB_RAD_CHUNK_WAVES : dense;
+    const uint32_t blocks_per_cu = p.blocks_per_cu ? p.blocks_per_cu : v == kWalkChunk ? (uint32_t)RB_RAD_CHUNK_WAVES : dense;
     uint64_t grid = (uint64_t)(max_blocks8 / 8u) * blocks_per_cu;
     const uint64_t needed = (items + kRadBlock - 1u) / kRadBlock;
     if (needed < grid) grid = needed;
     li.grid = (uint32_t)grid;
     const uint64_t waves = grid * (kRadBlock / 64u);
     // reservations as launch_render makes them: about 8 (the plain kernel) or 64 per wave, whole 64-item rows
-    uint64_t batch = items / (waves * (v == PLAIN ? 8u : 64u));
+    uint64_t batch = items / (waves * (v == kWalkPlain ? 8u : 64u));
     batch = (batch / 64u) * 64u;
     if (batch < 64u) batch = 64u;
-    if (batch > (v == PLAIN ? 512u : 4096u)) batch = (v == PLAIN ? 512u : 4096u);
+    if (batch > (v == kWalkPlain ? 512u : 4096u)) batch = (v == kWalkPlain ? 512u : 4096u);
     if (p.queue_batch) batch = p.queue_batch;
     a.batch = (uint32_t)batch;
     a.magic_S = a.samples > 1u ? (uint32_t)((1ull << 32) / a.samples) : 0xFFFFFFFFu;
@@ -597,9 +589,9 @@ int launch_radiance(const KParams& p_, const RadArgs& a_, void* stream_, LaunchI
     const dim3 g(li.grid), b(li.block);
     const bool sph = p.sph_nodes != nullptr;
     switch (v) {
-        case PLAIN: hipLaunchKernelGGL(records ? k_cam : k_rad, g, b, li.lds_bytes, stream, p, a); break;
-        case BVH: hipLaunchKernelGGL(records ? k_cam_bvh : k_rad_bvh, g, b, li.lds_bytes, stream, p, a); break;
-        case CHUNK:
+        case kWalkPlain: hipLaunchKernelGGL(records ? k_cam : k_rad, g, b, li.lds_bytes, stream, p, a); break;
+        case kWalkBvh: hipLaunchKernelGGL(records ? k_cam_bvh : k_rad_bvh, g, b, li.lds_bytes, stream, p, a); break;
+        case kWalkChunk:
             if (records) hipLaunchKernelGGL(sph ? k_cam_chunk<true> : k_cam_chunk<false>, g, b, li.lds_bytes, stream, p, a);
             else hipLaunchKernelGGL(sph ? k_rad_chunk<true> : k_rad_chunk<false>, g, b, li.lds_bytes, stream, p, a);
             break;
