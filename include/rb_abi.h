@@ -502,6 +502,9 @@ int rb_debug_walk_profile(uint64_t out64[64], int reset);
 /* Test hook: checks the kernels' fast exact reciprocal against the compiler's correctly rounded
  * 1/b for all 2^23 significands (both signs) at one biased exponent; out16[0] = mismatch count. */
 int rb_debug_rcp_exhaustive(uint32_t biased_exponent, uint32_t* out16);
+/* Test hook: checks the kernels' one-rounding `rnd(seed) * 2 - 1` (one fma) against the shader's three operations on all
+ * 2^32 seeds; out16[0] = number of seeds whose value differs, out16[1..15] = some of them. */
+int rb_debug_rnd_pm1_exhaustive(uint32_t* out16);
 /* Test hook: the same for the fast exact division a/b over a block of significand pairs
  * (denominators [b_begin, +b_count) x numerators [a_begin, +a_count), biased exponents ea, eb);
  * out16[0] = mismatch count, then up to 7 (a, b) bit patterns. */

@@ -84,8 +84,8 @@ __global__ void __launch_bounds__(256) k_cam_rays(const CamGenArgs g) {
         if (c.lens_radius != 0.0f) {
             float lx, ly;
             for (;;) {
-                lx = rnd(seed) * 2.0f - 1.0f;
-                ly = rnd(seed) * 2.0f - 1.0f;
+                lx = rnd_pm1(seed);
+                ly = rnd_pm1(seed);
                 if (lx * lx + ly * ly < 1.0f) break;
             }
             o = (pos + (c.lens_radius * lx) * right) + (c.lens_radius * ly) * up;

@@ -160,17 +160,62 @@ DEV float rnd(uint32_t& seed) {
     seed = pcg(seed);
     return (float)seed / 4294967296.0f;
 }
-// shader.wgsl:429-446
+// rnd(seed) * 2.0f - 1.0f in one rounding: with c = (float)seed that expression is RN(RN(RN(c * 2^-32) * 2) - 1); both scalings
+// are exact (c is 0 or >= 1: nothing comes near the subnormal range), so it equals RN(c * 2^-31 - 1), one fma.  Checked for every
+// float value c can take (tests/test_rnd_fused.py) and for all 2^32 seeds on the device (rb_debug_rnd_pm1_exhaustive).
+DEV float rnd_pm1(uint32_t& seed) {
+    seed = pcg(seed);
+    return __builtin_fmaf((float)seed, 0x1p-31f, -1.0f);
+}
+// shader.wgsl:429-446.  The wave loops until its slowest lane has a vector.  A lane that has its vector does not sit the
+// remaining rounds out: it goes on trying from the seed it is left with.  A rejected try has no effect but three hashes of the
+// seed, so those may be run early; at the first accepted one the lane puts the seed back to where that try began and stops
+// ("parks"), so the first try of its next call is the accepting one.  Every path draws the vectors it always drew; the wave
+// runs fewer rounds (the model is tools/unit_vector_rounds.py).  PARK = false is the function as it was,
+// three roundings per coordinate included, for a kernel whose register allocation must not move (k_trace_fast<true>).
+#ifndef RB_PARK_SEED
+#define RB_PARK_SEED 1   // 0: the plain loop around the fused try, for A/B builds (profiles/r15_c2_bench_ab.txt)
+#endif
+template <bool PARK = true>
 DEV f3 random_unit_vector(uint32_t& seed) {
-    f3 p;
-    for (;;) {
-        float px = rnd(seed) * 2.0f - 1.0f;
-        float py = rnd(seed) * 2.0f - 1.0f;
-        float pz = rnd(seed) * 2.0f - 1.0f;
-        p = mk(px, py, pz);
-        if (dot(p, p) < 1.0f) break;
+    if constexpr (!PARK) {
+        f3 p;
+        for (;;) {
+            const float px = rnd(seed) * 2.0f - 1.0f;
+            const float py = rnd(seed) * 2.0f - 1.0f;
+            const float pz = rnd(seed) * 2.0f - 1.0f;
+            p = mk(px, py, pz);
+            if (dot(p, p) < 1.0f) break;
+        }
+        return normalize(p);
+    } else if constexpr (RB_PARK_SEED == 0) {
+        float x, y, z;
+        do {
+            x = rnd_pm1(seed), y = rnd_pm1(seed), z = rnd_pm1(seed);
+        } while (!(dot(mk(x, y, z), mk(x, y, z)) < 1.0f));
+        return normalize(mk(x, y, z));
+    } else {
+        // The first try, which every lane is owed: nothing to select, nobody to park.  After it the two predicates are kept
+        // one bit per lane in scalar register pairs -- who is still owed a vector, whose try landed inside the sphere -- so
+        // that a round costs the vector unit the try and four selects (three coordinates and the seed) and nothing else.
+        uint32_t s = seed;
+        float x = rnd_pm1(s), y = rnd_pm1(s), z = rnd_pm1(s);
+        uint64_t owed = __builtin_amdgcn_ballot_w64(!(dot(mk(x, y, z), mk(x, y, z)) < 1.0f));
+        while (owed != 0ull) {
+            uint32_t t = s;
+            const float qx = rnd_pm1(t), qy = rnd_pm1(t), qz = rnd_pm1(t);
+            const uint64_t inside = __builtin_amdgcn_ballot_w64(dot(mk(qx, qy, qz), mk(qx, qy, qz)) < 1.0f);
+            const bool take = __builtin_amdgcn_inverse_ballot_w64(inside & owed);
+            const bool park = __builtin_amdgcn_inverse_ballot_w64(inside & ~owed);
+            x = take ? qx : x;
+            y = take ? qy : y;
+            z = take ? qz : z;
+            s = park ? s : t;   // a parked lane stays in front of its accepting try, whatever rounds follow
+            owed &= ~inside;
+        }
+        seed = s;
+        return normalize(mk(x, y, z));
     }
-    return normalize(p);
 }
 
 // --------------------------------------------------------- colour output --

@@ -284,7 +284,8 @@ DEV void segment_spheres(const KParams& p, f3 o, f3 d, float a, float& closest_t
 }
 
 // Point lights, sky, the winner's HitRecord, shading and scatter, shader.wgsl:590-660
-template <bool STATS>
+// PARK: the rejection loop parks the seed (random_unit_vector); false keeps the loop as it was, same vectors.
+template <bool STATS, bool PARK = true>
 DEV bool segment_post(const KParams& p, Path& pt, const TriHit th, const SegState st, float closest_t, uint32_t sphere_idx,
                       Tally<STATS>& tl) {
     const f3 o = pt.o, d = pt.d;
@@ -395,7 +396,7 @@ DEV bool segment_post(const KParams& p, Path& pt, const TriHit th, const SegStat
     // Both scatter branches draw exactly one random unit vector (:472, :488) and nothing else
     // touches the seed, so the rejection loop runs once for the whole wavefront instead of once
     // per branch; likewise the final normalize below is shared.
-    const f3 ruv = random_unit_vector(pt.seed);
+    const f3 ruv = random_unit_vector<PARK>(pt.seed);
     f3 scattered, albedo;
     bool absorbed = false;
     if (is_metal) {
@@ -542,14 +543,14 @@ DEV void segment_resolve(const KParams& p, f3 o, f3 d, const TriHit th, const Se
 }
 
 // One iteration of the bounce loop after the triangle traversal (`th`: its winner).
-template <bool STATS, bool SPHTREE = true>
+template <bool STATS, bool SPHTREE = true, bool PARK = true>
 DEV bool segment_finish(const KParams& p, Path& pt, const TriHit th, uint32_t* stack, uint32_t stride,
                         Tally<STATS>& tl) {
     const SegState st = segment_pre<STATS>(fresh_params(p), pt, th, tl);
     float closest_t = st.closest_t;
     uint32_t sphere_idx = 0xFFFFFFFFu;
     segment_spheres<STATS, SPHTREE>(fresh_params(p), pt.o, pt.d, dot(pt.d, pt.d), closest_t, sphere_idx, stack, stride, tl);
-    return segment_post<STATS>(fresh_params(p), pt, th, st, closest_t, sphere_idx, tl);
+    return segment_post<STATS, PARK>(fresh_params(p), pt, th, st, closest_t, sphere_idx, tl);
 }
 
 // One whole iteration of the bounce loop: traversal + everything else.  MULTI = false: trees of at most one node AND no

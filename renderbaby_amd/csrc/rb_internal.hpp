@@ -478,6 +478,7 @@ size_t max_dynamic_lds(int device);   // hipDeviceAttributeMaxSharedMemoryPerBlo
 int launch_div_exhaustive(uint32_t b_begin, uint32_t b_count, uint32_t ea, uint32_t eb, uint32_t a_begin,
                           uint32_t a_count, unsigned long long* mismatch16, void* stream);
 int launch_rcp_exhaustive(uint32_t expo, uint32_t* mismatch16, void* stream);
+int launch_rnd_pm1_exhaustive(uint32_t* mismatch16, void* stream);
 int launch_debug_math(const float* a, const float* b, float* out, uint32_t n, void* stream);
 int debug_walk_profile(unsigned long long* out64, int reset);   // pass occupancy counters of a profiling build, tools/ablate/rb_profile.patch (-1 otherwise)
 double measure_l1_gather(size_t table_bytes, uint32_t rounds);   // divergent 16-byte gathers from an L2-resident table: lane accesses / s

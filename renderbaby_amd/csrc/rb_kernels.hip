@@ -986,7 +986,8 @@ struct TriangleWalkPolicy {
     DEV void init(const KParams& p) { w.begin(p, mk(0, 0, 0), mk(0, 0, 1)); }
     DEV void begin(const KParams& p, const Path& pt, uint32_t*, Tally<STATS>&) { w.begin(p, pt.o, pt.d); }
     DEV bool finish(const KParams& p, Path& pt, uint32_t* stack, Tally<STATS>& tl) {
-        return segment_finish<STATS>(p, pt, w.h, stack, kTraceBlock, tl);
+        // the counting build keeps the rejection loop as it was: any change to the try costs it 6 more spilled registers (4 B of scratch)
+        return segment_finish<STATS, true, !STATS>(p, pt, w.h, stack, kTraceBlock, tl);
     }
 };
 template <bool STATS, class Walk>
@@ -1514,6 +1515,28 @@ __global__ void k_rcp_exhaustive(uint32_t expo, uint32_t* mismatch) {
     }
 }
 
+// Exhaustive check of rnd_pm1 against `rnd(seed) * 2.0f - 1.0f` (the shader's three roundings): all 2^32 seeds, 256 per
+// thread of a 2^16 x 256 grid.  pcg is a bijection, so every word the conversion can meet is met.  mismatch[0] counts the
+// seeds whose value or whose seed afterwards differs; mismatch[1..] records up to 15 of them.
+__global__ void __launch_bounds__(256) k_rnd_pm1_exhaustive(uint32_t* mismatch) {
+    const uint32_t first = blockIdx.x * 256u + threadIdx.x;   // < 2^24
+    uint32_t bad = 0u, first_bad = 0u;
+    for (uint32_t k = 0; k < 256u; k++) {
+        const uint32_t seed = first + (k << 24);
+        uint32_t sa = seed, sb = seed;
+        const float want = rnd(sa) * 2.0f - 1.0f;
+        const float got = rnd_pm1(sb);
+        if (__float_as_uint(want) != __float_as_uint(got) || sa != sb) {
+            if (bad == 0u) first_bad = seed;
+            bad++;
+        }
+    }
+    if (bad != 0u) {
+        const uint32_t n = atomicAdd(&mismatch[0], bad);
+        if (n < 15u) mismatch[1u + n] = first_bad;
+    }
+}
+
 // Exhaustive check of div_newton: thread = one denominator significand (biased exponent eb),
 // loop over `a_count` numerator significands starting at a_begin (biased exponent ea).
 __global__ void k_div_exhaustive(uint32_t b_begin, uint32_t ea, uint32_t eb, uint32_t a_begin, uint32_t a_count,
@@ -1870,6 +1893,12 @@ int launch_div_exhaustive(uint32_t b_begin, uint32_t b_count, uint32_t ea, uint3
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     hipLaunchKernelGGL(k_div_exhaustive, dim3((b_count + 255) / 256), dim3(256), 0, stream, b_begin, ea, eb, a_begin,
                        a_count, mismatch);
+    return (int)hipGetLastError();
+}
+
+int launch_rnd_pm1_exhaustive(uint32_t* mismatch, void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    hipLaunchKernelGGL(k_rnd_pm1_exhaustive, dim3(1u << 16), dim3(256), 0, stream, mismatch);
     return (int)hipGetLastError();
 }
 

@@ -1427,6 +1427,20 @@ int rb_debug_rcp_exhaustive(uint32_t biased_exponent, uint32_t* out16) {
     return (rc || st != hipSuccess) ? RB_ERR_DEVICE : RB_OK;
 }
 
+// Test hook: device check of the one-rounding form of `rnd(seed) * 2 - 1` (rnd_pm1) against the three-operation form on all
+// 2^32 seeds.  out16[0] = number of differing seeds, out16[1..15] = some of them.
+int rb_debug_rnd_pm1_exhaustive(uint32_t* out16) {
+    if (!out16) return RB_ERR_NULL_ARGUMENT;
+    uint32_t* d = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&d), 64) != hipSuccess) return RB_ERR_DEVICE;
+    (void)hipMemset(d, 0, 64);
+    int rc = rb::launch_rnd_pm1_exhaustive(d, nullptr);
+    hipError_t st = hipDeviceSynchronize();
+    (void)hipMemcpy(out16, d, 64, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    return (rc || st != hipSuccess) ? RB_ERR_DEVICE : RB_OK;
+}
+
 // Test hook: device check of the fast exact division over denominators [b_begin, b_begin+b_count)
 // x numerators [a_begin, a_begin+a_count) (significands; biased exponents ea / eb).
 // out16[0] = mismatch count, then up to 7 (a, b) bit-pattern pairs.

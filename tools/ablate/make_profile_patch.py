@@ -26,13 +26,31 @@ static __device__ unsigned long long g_walk_prof[64];
 #define KPROF(i) do { const unsigned long long m_ = __ballot(1); \\
     if (__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == (unsigned)(__ffsll((long long)m_) - 1)) { \\
         atomicAdd(&g_walk_prof[2 * (i)], 1ull); atomicAdd(&g_walk_prof[2 * (i) + 1], (unsigned long long)__popcll(m_)); } } while (0)
+// the same, counting only the active lanes named in `mask` (uniform)
+#define KPROF_LANES(i, mask) do { const unsigned long long m_ = __ballot(1); \\
+    if (__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == (unsigned)(__ffsll((long long)m_) - 1)) { \\
+        atomicAdd(&g_walk_prof[2 * (i)], 1ull); atomicAdd(&g_walk_prof[2 * (i) + 1], (unsigned long long)__popcll(m_ & (mask))); } } while (0)
 ''', 1)])
 # k_trace's phases.  pairs of slots: 8 path start, 9 segment, 10 triangle test, 11 past |a|, 12 past u, 13 past v, 14 sphere pass 1,
-# 15 sphere pass 2, 16 light pass 1, 17 light pass 2, 18 shading, 19 one try of the rejection loop, 20 metal, 21 lambert, 22 texture, 23 path end
-edit("rb_device_math.hpp", [('''    for (;;) {
-        float px = rnd(seed) * 2.0f - 1.0f;''', '''    for (;;) {
-        KPROF(19);
-        float px = rnd(seed) * 2.0f - 1.0f;''')])
+# 15 sphere pass 2, 16 light pass 1, 17 light pass 2, 18 shading, 19 one try of the rejection loop (7: the first try of the loop that parks
+# seeds, which stands in front of the loop), 20 metal, 21 lambert, 22 texture, 23 path end
+# (the parked loop computes in every lane that reached the draw; the lanes counted are those whose try is wanted: the owed ones
+# and the served ones still searching, not the parked ones, which repeat their accepting try.  -DRB_PARK_SEED=0: the plain loop)
+edit("rb_device_math.hpp", [('''        do {
+            x = rnd_pm1(seed), y = rnd_pm1(seed), z = rnd_pm1(seed);''', '''        do {
+            KPROF(19);
+            x = rnd_pm1(seed), y = rnd_pm1(seed), z = rnd_pm1(seed);'''),
+                            ('''        uint32_t s = seed;
+        float x = rnd_pm1(s), y = rnd_pm1(s), z = rnd_pm1(s);''', '''        uint32_t s = seed;
+        unsigned long long prof_parked = 0ull;
+        KPROF(7);
+        float x = rnd_pm1(s), y = rnd_pm1(s), z = rnd_pm1(s);'''),
+                            ('''        while (owed != 0ull) {
+            uint32_t t = s;''', '''        while (owed != 0ull) {
+            KPROF_LANES(19, ~prof_parked);
+            uint32_t t = s;'''),
+                            ('''            owed &= ~inside;''', '''            prof_parked |= inside & ~owed;
+            owed &= ~inside;''')])
 edit("rb_device_intersect.hpp", [('''    const f3 h = cross(d, edge2);
     const float a = dot(edge1, h);
     if (fabsf(a) < 1e-6f) return -1.0f;
