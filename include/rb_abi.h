@@ -687,6 +687,65 @@ int rb_trace_camera_device(rb_engine* e, const rb_camera_ex* cam, uint64_t first
  * for the launches it reports. */
 int rb_last_camera_rays_ms(rb_engine* e, float* ms);
 
+/* ---- Hemisphere rays made on the device (the normative definition; no reference counterpart).  m surface
+ * points in, m answers out: a device stage makes the cosine-weighted ray of every (surfel, sample) item from the item's own
+ * random stream, and the kernels of rb_trace_rays (radiance) or rb_occluded (openness) walk it.  Every step is one IEEE binary32
+ * operation in the order written, no contraction, / and sqrt correctly rounded: the numpy model renderbaby_amd/hemisphere.py
+ * equals the device bit for bit.  For surfel i of n and sample k of `samples`:
+ *   nrm    = normalize(normal_i) as rb_cast_rays normalises a direction; the surfel is invalid if pos_i or nrm has a non-finite
+ *            component or nrm is all zero, and then so is every sample of it;
+ *   sid    = seeds ? seeds[i] : (uint32_t)i;  seed = pcg(sid + pcg(first_sample + k)), u32 wrap-around: rb_trace_rays' rule;
+ *   u1, u2 = random_float(&seed), twice: always exactly two draws, either may be exactly 1.0f;
+ *   (s, c) = sincos_turn(u1 * 2.0f - 1.0f) (section 15.3);  r = sqrt(u2);  z = sqrt(1.0f - u2);
+ *   sg = copysignf(1.0f, nrm.z);  a = -1.0f / (sg + nrm.z);  b = (nrm.x * nrm.y) * a;      (Duff et al. 2017; |sg + nrm.z| >= 1)
+ *   t1 = (1.0f + (sg * (nrm.x * nrm.x)) * a,  sg * b,  (-sg) * nrm.x);   t2 = (b,  sg + (nrm.y * nrm.y) * a,  -nrm.y);
+ *   d  = ((r * c) t1 + (r * s) t2) + z nrm, component-wise, then normalised as rb_cast_rays does it;
+ *   reach = sqrt((px px + py py) + pz pz);  o = pos + (offset * max(1.0f, reach)) nrm;
+ *   a sample is also invalid if o or d is non-finite or d is all zero.  An invalid item's record is {pos_i as given, 0 0 0};
+ *   RADIANCE  c(i,k) = trace_ray(scene, o, d, seed) with the seed as the two draws left it; out[i] = {sum r, sum g, sum b, w}:
+ *             from +0.0f in ascending k; w counts the valid samples; an invalid sample adds nothing; max_depth == 0 gives
+ *             {0, 0, 0, w}.  The mean radiance sum / w is the irradiance over pi;
+ *   OPENNESS  valid = the valid samples; open = those of them whose ray rb_occluded reports RB_OCCL_VISIBLE with tmax = radius
+ *             and `mask` (radius <= 0.001f: every valid sample is open and nothing is walked).
+ * The side effects are a query's.  The result does not depend on the piece size, the launch shape or the form of the call. */
+typedef struct rb_surfel { float pos[3]; float _pad0; float normal[3]; float _pad1; } rb_surfel;    /* 32 B, rb_ray's layout */
+/* (surfel, sample) items per launch, as RB_CAMERA_PIECE_ITEMS */
+enum { RB_HEMI_PIECE_ITEMS = 1u << 23 };
+typedef struct rb_hemi_params {                                                                     /* 32 B */
+    float offset;      /* >= 0, finite: the origin leaves the surface by offset * max(1, |pos|) along the normal */
+    float radius;      /* openness only: the any-hit bound, rb_occluded's tmax rules (NaN refused here) */
+    uint32_t mask;     /* openness only: RB_MASK_* */
+    uint32_t flags;    /* must be 0 */
+    uint32_t _reserved[4];
+} rb_hemi_params;
+typedef struct rb_openness { uint32_t open; uint32_t valid; } rb_openness;                          /* 8 B */
+/* The generator alone, no engine, on `device` (-1 = current): host arrays; rays_out / seeds_out[i * samples + k] as
+ * rb_camera_rays writes them (dir normalised, an invalid ray {0, 0, 0}; the seed trace_ray starts with); `radius` and `mask`
+ * are not read.  RB_ERR_INVALID_OPTIONS, before any device is touched: samples 0 or above 65536; first_sample + samples beyond
+ * 2^32 - 1; n > 2^31 - 64 or n * samples above 2^31 - 64; offset negative or non-finite; non-zero flags or _reserved.  NULL
+ * surfels, params, rays_out or seeds_out with n > 0: RB_ERR_NULL_ARGUMENT.  n == 0 is RB_OK. */
+int rb_hemisphere_rays(int32_t device, const rb_surfel* surfels, const uint32_t* seeds, size_t n, const rb_hemi_params* params,
+                       uint32_t first_sample, uint32_t samples, rb_ray* rays_out, uint32_t* seeds_out);
+/* Radiance over the hemisphere: surfels[n], seeds[n] (may be NULL) and out[n] in host memory (pageable or page-locked).
+ * Refusals as rb_hemisphere_rays; a refused call leaves the engine as it was.  Pieces of at most RB_HEMI_PIECE_ITEMS items,
+ * whole blocks of 64 surfels, never a part of one surfel's samples.  Sharded engines and multi-device handles as
+ * rb_trace_rays.  rb_last_query_kernel_name reports "k_cam", "k_cam_bvh" or "k_cam_chunk" -- the walk by rb_cast_rays' rule --,
+ * rb_last_query_ms the generator, the trace and the sum together, rb_last_camera_rays_ms the generator's share. */
+int rb_trace_hemisphere(rb_engine* e, const rb_surfel* surfels, const uint32_t* seeds, size_t n, const rb_hemi_params* params,
+                        uint32_t first_sample, uint32_t samples, rb_radiance* out);
+/* The same with d_surfels (16-byte aligned), d_seeds (may be NULL) and d_out in device memory of the engine's device, validated
+ * as rb_trace_rays_device validates its buffers; queued on the engine's stream, returns without waiting: rb_sync is the wait. */
+int rb_trace_hemisphere_device(rb_engine* e, const rb_surfel* d_surfels, const uint32_t* d_seeds, size_t n,
+                               const rb_hemi_params* params, uint32_t first_sample, uint32_t samples, rb_radiance* d_out);
+/* Openness: out[n] = {open, valid}.  As rb_trace_hemisphere, and RB_ERR_INVALID_OPTIONS for a NaN radius or mask bits above
+ * RB_MASK_ALL.  The records, 4 B of bound and 1 B of result per item go through the engine's query scratch;
+ * rb_last_query_kernel_name reports "k_occl", "k_occl_bvh" or "k_occl_chunk". */
+int rb_openness_hemisphere(rb_engine* e, const rb_surfel* surfels, const uint32_t* seeds, size_t n, const rb_hemi_params* params,
+                           uint32_t first_sample, uint32_t samples, rb_openness* out);
+/* The same on device memory, as rb_trace_hemisphere_device (d_out: 8-byte aligned). */
+int rb_openness_hemisphere_device(rb_engine* e, const rb_surfel* d_surfels, const uint32_t* d_seeds, size_t n,
+                                  const rb_hemi_params* params, uint32_t first_sample, uint32_t samples, rb_openness* d_out);
+
 /* ---- Edge-avoiding denoiser over the first-hit buffers (no reference counterpart).  An a-trous wavelet
  * filter (Dammertz et al. 2010) on the albedo-demodulated mean radiance, guided by the first hit of every pixel-centre ray.
  * Section 13 is the normative definition: every step one IEEE binary32 operation in a fixed order, so that the device's result
@@ -795,6 +854,10 @@ static_assert(sizeof(rb_camera_ex) == 96, "rb_camera_ex is 96 B");
 static_assert(offsetof(rb_camera_ex, pos) == 16, "pos @16");
 static_assert(offsetof(rb_camera_ex, forward) == 64, "forward @64");
 static_assert(offsetof(rb_camera_ex, focus_distance) == 80, "focus_distance @80");
+static_assert(sizeof(rb_surfel) == 32, "rb_surfel is 32 B");
+static_assert(offsetof(rb_surfel, normal) == 16, "normal @16");
+static_assert(sizeof(rb_hemi_params) == 32, "rb_hemi_params is 32 B");
+static_assert(sizeof(rb_openness) == 8, "rb_openness is 8 B");
 static_assert(sizeof(rb_guide) == 48, "rb_guide is 48 B");
 static_assert(sizeof(rb_denoise_params) == 32, "rb_denoise_params is 32 B");
 static_assert(offsetof(rb_guide, t) == 12, "t @12");
@@ -819,6 +882,9 @@ _Static_assert(sizeof(rb_hit) == 48, "rb_hit is 48 B");
 _Static_assert(sizeof(rb_surface) == 48, "rb_surface is 48 B");
 _Static_assert(sizeof(rb_radiance) == 16, "rb_radiance is 16 B");
 _Static_assert(sizeof(rb_camera_ex) == 96, "rb_camera_ex is 96 B");
+_Static_assert(sizeof(rb_surfel) == 32, "rb_surfel is 32 B");
+_Static_assert(sizeof(rb_hemi_params) == 32, "rb_hemi_params is 32 B");
+_Static_assert(sizeof(rb_openness) == 8, "rb_openness is 8 B");
 _Static_assert(sizeof(rb_guide) == 48, "rb_guide is 48 B");
 _Static_assert(sizeof(rb_denoise_params) == 32, "rb_denoise_params is 32 B");
 #endif

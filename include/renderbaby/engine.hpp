@@ -237,6 +237,39 @@ class Engine final : public Renderer {
                              uint32_t first_sample = 0) {
         check(h_->e, rb_trace_camera_device(h_->e, &cam, first_pixel, n_pixels, first_sample, samples, d_out));
     }
+    // ---- hemisphere rays made on the device (extension; rb_abi.h): per surfel the ordered sum over
+    // `samples` cosine-weighted rays about its normal, or the count of those that meet nothing within `radius`
+    static rb_hemi_params hemi_params(float offset = 1e-3f, float radius = 0.0f, uint32_t mask = 0) {
+        rb_hemi_params p{};
+        p.offset = offset;
+        p.radius = radius;
+        p.mask = mask;
+        return p;
+    }
+    std::vector<rb_radiance> trace_hemisphere(const std::vector<rb_surfel>& surfels, uint32_t samples, uint32_t first_sample = 0,
+                                              const uint32_t* seeds = nullptr, float offset = 1e-3f) {
+        const rb_hemi_params p = hemi_params(offset);
+        std::vector<rb_radiance> out(surfels.size());
+        check(h_->e, rb_trace_hemisphere(h_->e, surfels.data(), seeds, surfels.size(), &p, first_sample, samples, out.data()));
+        return out;
+    }
+    std::vector<rb_openness> openness(const std::vector<rb_surfel>& surfels, uint32_t samples, float radius,
+                                      uint32_t mask = RB_MASK_ALL & ~RB_MASK_LIGHTS, uint32_t first_sample = 0,
+                                      const uint32_t* seeds = nullptr, float offset = 1e-3f) {
+        const rb_hemi_params p = hemi_params(offset, radius, mask);
+        std::vector<rb_openness> out(surfels.size());
+        check(h_->e, rb_openness_hemisphere(h_->e, surfels.data(), seeds, surfels.size(), &p, first_sample, samples, out.data()));
+        return out;
+    }
+    // the same on the engine's device memory: queued on the engine's stream, not waited for -- sync() waits
+    void trace_hemisphere_device(const rb_surfel* d_surfels, const uint32_t* d_seeds, size_t n, const rb_hemi_params& p, rb_radiance* d_out,
+                                 uint32_t samples, uint32_t first_sample = 0) {
+        check(h_->e, rb_trace_hemisphere_device(h_->e, d_surfels, d_seeds, n, &p, first_sample, samples, d_out));
+    }
+    void openness_device(const rb_surfel* d_surfels, const uint32_t* d_seeds, size_t n, const rb_hemi_params& p, rb_openness* d_out,
+                         uint32_t samples, uint32_t first_sample = 0) {
+        check(h_->e, rb_openness_hemisphere_device(h_->e, d_surfels, d_seeds, n, &p, first_sample, samples, d_out));
+    }
     void sync() { check(h_->e, rb_sync(h_->e)); }
     // ---- the denoiser (rb_abi.h): the a-trous filter over the committed accumulation
     static rb_denoise_params denoise_defaults() {

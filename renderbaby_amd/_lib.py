@@ -96,6 +96,11 @@ def load():
         "rb_trace_camera": (i32, [vp, vp, C.c_uint64, sz, u32, u32, vp]),
         "rb_trace_camera_device": (i32, [vp, vp, C.c_uint64, sz, u32, u32, vp]),
         "rb_last_camera_rays_ms": (i32, [vp, P(C.c_float)]),
+        "rb_hemisphere_rays": (i32, [i32, vp, vp, sz, vp, u32, u32, vp, vp]),
+        "rb_trace_hemisphere": (i32, [vp, vp, vp, sz, vp, u32, u32, vp]),
+        "rb_trace_hemisphere_device": (i32, [vp, vp, vp, sz, vp, u32, u32, vp]),
+        "rb_openness_hemisphere": (i32, [vp, vp, vp, sz, vp, u32, u32, vp]),
+        "rb_openness_hemisphere_device": (i32, [vp, vp, vp, sz, vp, u32, u32, vp]),
         "rb_last_query_kernel_name": (C.c_char_p, [vp]),
         "rb_last_query_ms": (i32, [vp, P(C.c_float)]),
         "rb_denoise_default_params": (i32, [vp]),
@@ -139,4 +144,5 @@ EXPORTS = ["rb_create", "rb_create_ex", "rb_create_multi", "rb_comm_available", 
            "rb_device_rgba", "rb_host_alloc", "rb_host_free", "rb_local_rows", "rb_global_row", "rb_shard_layout", "rb_shard_global_row", "rb_get_stats", "rb_reset_stats",
            "rb_last_dispatch_ms", "rb_bvh_build", "rb_bvh_build_canonical", "rb_bvh_build_device", "rb_engine_tree", "rb_tree_builder", "rb_debug_chunk_tree", "rb_measure_l1_gather", "rb_debug_math", "rb_debug_walk_profile", "rb_debug_rcp_exhaustive", "rb_debug_rnd_pm1_exhaustive", "rb_debug_div_exhaustive", "rb_last_kernel_name", "rb_cast_rays", "rb_render_hits", "rb_pick", "rb_occluded", "rb_occluded_device", "rb_cast_rays_device", "rb_trace_rays", "rb_trace_rays_device", "rb_last_query_kernel_name", "rb_last_query_ms",
            "rb_camera_rays", "rb_trace_camera", "rb_trace_camera_device", "rb_last_camera_rays_ms",
+           "rb_hemisphere_rays", "rb_trace_hemisphere", "rb_trace_hemisphere_device", "rb_openness_hemisphere", "rb_openness_hemisphere_device",
            "rb_denoise_default_params", "rb_denoise_buffers", "rb_denoise", "rb_denoise_device", "rb_denoise_guides", "rb_last_denoise_ms", "rb_fast_bvh_builder", "rb_sphere_tree_builder", "rb_chunk_tree_builder", "rb_debug_engine_chunk_tree", "rb_version", "rb_device_name"]

@@ -60,6 +60,12 @@ CAMERA_EX = np.dtype([("kind", u4), ("width", u4), ("height", u4), ("flags", u4)
 CAM_PERSPECTIVE, CAM_ORTHO, CAM_EQUIRECT = 1, 2, 3
 CAM_NO_JITTER = 1
 CAMERA_PIECE_ITEMS = 1 << 23
+# hemisphere rays made on the device (rb_hemisphere_rays / rb_trace_hemisphere / rb_openness_hemisphere):
+# a surface point with its normal, the parameters of a call and the counts of a surfel's samples
+SURFEL = np.dtype([("pos", f4, (3,)), ("_pad0", f4), ("normal", f4, (3,)), ("_pad1", f4)])
+HEMI_PARAMS = np.dtype([("offset", f4), ("radius", f4), ("mask", u4), ("flags", u4), ("_reserved", u4, (4,))])
+OPENNESS = np.dtype([("open", u4), ("valid", u4)])
+HEMI_PIECE_ITEMS = 1 << 23
 # any-hit occlusion (rb_occluded): result bytes and stage masks
 OCCL_VISIBLE, OCCL_OCCLUDED, OCCL_INVALID = 0, 1, 255
 MASK_GROUND, MASK_TRIANGLES, MASK_SPHERES, MASK_LIGHTS, MASK_ALL = 1, 2, 4, 8, 15
@@ -72,7 +78,8 @@ SIZES = {"camera": (CAMERA, 48), "uniforms": (UNIFORMS, 144), "material": (MATER
          "sphere": (SPHERE, 96), "point_light": (POINT_LIGHT, 96), "mesh": (MESH, 96),
          "bvh_node": (BVH_NODE, 48), "gpu_triangle": (GPU_TRIANGLE, 64),
          "ray": (RAY, 32), "hit": (HIT, 48), "surface": (SURFACE, 48),
-         "guide": (GUIDE, 48), "denoise_params": (DENOISE_PARAMS, 32), "camera_ex": (CAMERA_EX, 96)}
+         "guide": (GUIDE, 48), "denoise_params": (DENOISE_PARAMS, 32), "camera_ex": (CAMERA_EX, 96),
+         "surfel": (SURFEL, 32), "hemi_params": (HEMI_PARAMS, 32), "openness": (OPENNESS, 8)}
 for _n, (_dt, _sz) in SIZES.items():
     assert _dt.itemsize == _sz, (_n, _dt.itemsize, _sz)
 

@@ -1,5 +1,6 @@
 """First-hit buffers as images: pure numpy over the records of ``Engine.render_hits`` / ``Engine.cast_rays``
-(abi.HIT, abi.SURFACE).  No device, no library -- except ``ambient_occlusion``, which asks the engine one any-hit query.
+(abi.HIT, abi.SURFACE).  No device, no library -- except ``ambient_occlusion``, which asks the engine one any-hit query, and
+``ambient_occlusion_device``, which asks it for the openness of one surfel per hit.
 
 The records are already in the orientation of the delivered RGBA8 frame (row-major, top row first, x mirrored), so every
 function here maps record [row, column] to pixel [row, column] and nothing is flipped.  Pixels whose ray hit nothing
@@ -167,6 +168,39 @@ def ambient_occlusion(engine, hits, n_dirs=16, radius=1.0, seed=0, uniforms=None
         occ = engine.occluded(org, dirs, tmax, abi.MASK_ALL & ~abi.MASK_LIGHTS)
         blocked = (occ.reshape(-1, n_dirs) == abi.OCCL_OCCLUDED).sum(1)
         ao[m] = np.float32(1.0) - blocked.astype(np.float32) / np.float32(n_dirs)
+    return ao
+
+
+def ambient_occlusion_surfels(uniforms, hits):
+    """The surfels of ``ambient_occlusion_device``: for every pixel whose centre ray hit something, the hit point
+    ``pos + t d`` and the normal turned towards the camera, as ``ambient_occlusion_rays`` turns it.  Returns (pixel mask
+    [rows, width], points (m, 3), normals (m, 3)), numpy float32."""
+    f32 = np.float32
+    u = np.asarray(uniforms, dtype=abi.UNIFORMS).reshape(-1)[0]
+    m = _hit_mask(hits)
+    d = pixel_centre_dirs(u)
+    if d.shape[:2] != hits.shape:
+        raise ValueError(f"the records are {hits.shape}, the uniforms' frame {d.shape[:2]}")
+    d, t, n = d[m], hits["t"][m].astype(f32)[:, None], hits["normal"][m].astype(f32)
+    n = np.where((n * d).sum(-1, keepdims=True) > 0, -n, n).astype(f32)
+    return m, (np.asarray(u["camera"]["pos"], f32) + t * d).astype(f32), n
+
+
+def ambient_occlusion_device(engine, hits, samples=16, radius=1.0, first_sample=0, uniforms=None):
+    """``ambient_occlusion`` with the directions made on the device (Engine.openness, rb_openness_hemisphere; DESIGN.md
+    section 16): one surfel per hit goes up, 32 B, and two counts per hit come back -- no ray exists on the host.  The
+    directions are those of the device's generator (``hemisphere.rays``), not ``cosine_directions``', so the image agrees with
+    ``ambient_occlusion``'s within the noise of ``samples`` directions, not bit for bit.  float32 [rows, width]: open / valid;
+    1 where nothing was hit or no sample was valid."""
+    u = engine.uniforms if uniforms is None else uniforms
+    if u is None:
+        raise ValueError("the engine has accepted no update yet: call update() / render() first, or pass uniforms=")
+    m, pts, nrm = ambient_occlusion_surfels(u, hits)
+    ao = np.ones(hits.shape, dtype=np.float32)
+    if len(pts):
+        res = engine.openness(pts, nrm, samples, radius, first_sample=first_sample)
+        valid = res["valid"].astype(np.float32)
+        ao[m] = np.where(valid > 0, res["open"].astype(np.float32) / np.maximum(valid, np.float32(1)), np.float32(1)).astype(np.float32)
     return ao
 
 

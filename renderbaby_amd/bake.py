@@ -2,6 +2,7 @@
 "what radiance does trace_ray return along this ray?", everything else here is numpy on the caller's side.
 
 ``irradiance``   mean radiance over cosine-weighted directions about a normal: lightmap texels, vertices, probes
+``irradiance_device``  the same with the rays made and the samples summed on the device (Engine.trace_hemisphere; section 16)
 ``camera_rays``  the rays of cameras the reference's Camera struct cannot express: equirect, ortho, thin_lens
 ``render_rays``  rays -> tone-mapped RGBA8 pixels, the reference's colour mapping applied to sum / weight
 ``render_camera``  an abi.CAMERA_EX camera (camera.make) -> RGBA8 pixels, every sample's ray made on the device with jitter and
@@ -49,6 +50,21 @@ def irradiance(engine, points, normals, samples, seed=0):
     for k in range(samples):
         total = (total + c[:, k]).astype(f32)
     return (total / f32(samples)).astype(f32)
+
+
+def irradiance_device(engine, points, normals, samples, first_sample=0, seeds=None, offset=1e-3):
+    """``irradiance`` with the rays made on the device (Engine.trace_hemisphere, rb_trace_hemisphere):
+    m points and normals in, m sums out, summed on the device in sample order.  The directions are those of the device's
+    generator (``hemisphere.rays``), not ``aov.cosine_directions``', so the result agrees with ``irradiance`` within
+    Monte-Carlo noise, not bit for bit.  numpy arrays -> float32 (m, 3); torch tensors on the engine's device -> an (m, 3)
+    tensor there, and nothing crosses to the host.  A point without a valid sample is 0 0 0."""
+    rad = engine.trace_hemisphere(points, normals, samples, first_sample=first_sample, seeds=seeds, offset=offset)
+    if isinstance(rad, np.ndarray):
+        w = rad["weight"][:, None].astype(f32)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(w > 0, rad["sum"].astype(f32) / w, f32(0)).astype(f32)
+    w = rad[:, 3:4]
+    return (rad[:, 0:3] / w.clamp(min=1.0)) * (w > 0)
 
 
 def camera_rays(kind, width, height, pos, dir=(0.0, 0.0, -1.0), up=(0.0, 1.0, 0.0), ortho_width=2.0, fov_deg=60.0,

@@ -5,7 +5,7 @@
 // done inside their refill it would run at the dozen lanes a refill serves (section 15.4: what that cost k_trace's much shorter
 // path start).  Same numerics contract as rb_kernels.hip: every step one binary32 operation in the order written,
 // no FMA contraction, correctly rounded / and sqrt, so that renderbaby_amd/camera.py equals this file bit for bit.
-#include "rb_device_math.hpp"
+#include "rb_device_sincos.hpp"
 
 #pragma clang fp contract(off)
 
@@ -15,35 +15,6 @@ namespace {
 DEV bool cam_finite3(f3 a) {
     const uint32_t m = 0x7F800000u;
     return (__float_as_uint(a.x) & m) != m && (__float_as_uint(a.y) & m) != m && (__float_as_uint(a.z) & m) != m;
-}
-
-// sin and cos of pi * s for s in [-1, 1] (section 15.3): q = the nearest quarter turn, r = s - q / 2 exactly, x = r * (float)pi
-// with |x| <= pi / 4, the two Taylor polynomials in Horner form -- one multiply, then one add per step --, the result by the
-// quadrant q mod 4.  Within 2^-22 of the true values; the coefficients are the binary64 quotients rounded to binary32.
-struct SinCos {
-    float s, c;
-};
-DEV SinCos sincos_turn(float s) {
-    const float q = __builtin_rintf(2.0f * s);
-    const float r = s - 0.5f * q;
-    const float x = r * 3.14159274101257324f;
-    const float x2 = x * x;
-    float ps = (float)(1.0 / 362880.0);
-    ps = ps * x2 + (float)(-1.0 / 5040.0);
-    ps = ps * x2 + (float)(1.0 / 120.0);
-    ps = ps * x2 + (float)(-1.0 / 6.0);
-    ps = ps * x2 + 1.0f;
-    const float sn = x * ps;
-    float pc = (float)(1.0 / 40320.0);
-    pc = pc * x2 + (float)(-1.0 / 720.0);
-    pc = pc * x2 + (float)(1.0 / 24.0);
-    pc = pc * x2 + (float)(-1.0 / 2.0);
-    pc = pc * x2 + 1.0f;
-    const uint32_t quad = (uint32_t)(int)q & 3u;
-    SinCos o;
-    o.s = quad == 0u ? sn : quad == 1u ? pc : quad == 2u ? -sn : -pc;
-    o.c = quad == 0u ? pc : quad == 1u ? -sn : quad == 2u ? -pc : sn;
-    return o;
 }
 
 // ========================================================= k_cam_rays ====

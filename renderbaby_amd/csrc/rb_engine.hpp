@@ -174,8 +174,10 @@ struct rb_engine {
     rb::DevBuf<float> rad_colors;    // rb_trace_rays: float4 per (ray, sample) of one piece, the piece's ids and sums, the queue word
     rb::DevBuf<uint32_t> rad_seeds, rad_queue;
     rb::DevBuf<rb_radiance> rad_out;
+    rb::DevBuf<rb_surfel> hemi_surfels;   // rb_trace_hemisphere / rb_openness_hemisphere: the piece's surfels and its counts
+    rb::DevBuf<rb_openness> hemi_open;
     hipEvent_t ev_q[2] = {nullptr, nullptr};
-    std::vector<hipEvent_t> ev_cam;  // rb_trace_camera*: a pair around every piece's k_cam_rays (rb_last_camera_rays_ms)
+    std::vector<hipEvent_t> ev_cam;  // rb_trace_camera*, rb_*_hemisphere*: a pair around every piece's generator (rb_last_camera_rays_ms)
     size_t cam_pieces = 0;           // pairs the most recent call recorded
     const char* last_query_kernel_name = "";
     float last_query_ms = 0.0f;

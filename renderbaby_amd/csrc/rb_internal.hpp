@@ -430,6 +430,22 @@ struct CamGenArgs {
     uint32_t linear;
 };
 int launch_camera_rays(const CamGenArgs& g, void* stream);
+// ---- rb_hemisphere.hip: hemisphere rays made on the device.  One launch of k_hemi_rays writes the
+// records of one piece of whole surfels, in k_cam_rays' format; k_hemi_count turns a piece's any-hit bytes into counts.
+struct HemiGenArgs {
+    const rb_surfel* surfels; // the piece's surfels
+    const uint32_t* ids;      // the piece's surfel ids, or nullptr: id_base + index in the piece
+    rb_ray* recs;             // item order: record (block * samples + sample) * 64 + surfel-in-block; linear: index * samples + sample
+    uint32_t* seeds;          // linear order only, may be nullptr: seed i beside record i, whose fourth word is then 0
+    float* tmax;              // linear order only, may be nullptr: `radius` per item, the bounds k_occl* read
+    float offset, radius;
+    uint32_t n;               // surfels in this piece
+    uint32_t id_base;         // index of the piece's first surfel in the call
+    uint32_t first_sample, samples;
+    uint32_t linear;
+};
+int launch_hemisphere_rays(const HemiGenArgs& g, void* stream);
+int launch_hemisphere_count(const uint8_t* occl, uint32_t n, uint32_t samples, rb_openness* out, void* stream);
 Cam host_cam(const rb_uniforms& u);   // rb_kernels.hip: the camera of a launch, shader.wgsl:690,702-708
 
 // ---- rb_denoise.hip: the edge-avoiding a-trous filter.  Everything is in the orientation of the delivered

@@ -1,6 +1,6 @@
 // rb_queries.cpp -- what an engine answers besides frames: closest-hit queries (rb_cast_rays / rb_render_hits / rb_pick), any-hit
-// occlusion, path-traced radiance along given rays, camera rays made on the device and the denoiser over the first-hit buffers,
-// with their device forms, their getters and their C entry points (rb_abi.h; DESIGN.md sections 11-15).  Every family shares
+// occlusion, path-traced radiance along given rays, camera and hemisphere rays made on the device and the denoiser over the
+// first-hit buffers, with their device forms, their getters and their C entry points (rb_abi.h; DESIGN.md sections 11-16).  Every family shares
 // one prologue (query_prologue), one timed launch (timed_launch) and one runner per form: run_pieces for the host forms,
 // device_query_locked for the device forms.  The engine's state is rb_engine.hpp's; the launchers are
 // rb_internal.hpp's.
@@ -294,15 +294,25 @@ int trace_rays_device_locked(rb_engine* e, const rb_ray* d_rays, const uint32_t*
 }
 
 // ---- camera rays made on the device (rb_abi.h)
-// one piece, queued: the generator into the record scratch, the k_cam kernel of the scene's walk over it, the sum into `out`
-int camera_piece(rb_engine* e, const rb::KParams& p, const rb_camera_ex& cam, uint64_t first_pixel, size_t done, size_t m,
-                 uint32_t first_sample, uint32_t samples, rb_radiance* out, rb::LaunchInfo* li) {
+// a piece's generator between an event pair of its own (rb_last_camera_rays_ms): `gen()` queues it and returns a HIP status
+template <class Gen>
+int timed_generator(rb_engine* e, Gen&& gen) {
     while (e->ev_cam.size() < 2 * (e->cam_pieces + 1)) {
         hipEvent_t x = nullptr;
         if (const hipError_t st = hipEventCreate(&x)) return static_cast<int>(st);
         e->ev_cam.push_back(x);
     }
     hipEvent_t* const ev = &e->ev_cam[2 * e->cam_pieces];
+    if (const hipError_t st = hipEventRecord(ev[0], e->stream)) return static_cast<int>(st);
+    if (const int st = gen()) return st;
+    if (const hipError_t st = hipEventRecord(ev[1], e->stream)) return static_cast<int>(st);
+    e->cam_pieces++;
+    return 0;
+}
+
+// one piece, queued: the generator into the record scratch, the k_cam kernel of the scene's walk over it, the sum into `out`
+int camera_piece(rb_engine* e, const rb::KParams& p, const rb_camera_ex& cam, uint64_t first_pixel, size_t done, size_t m,
+                 uint32_t first_sample, uint32_t samples, rb_radiance* out, rb::LaunchInfo* li) {
     rb::CamGenArgs g{};
     g.cam = cam;
     g.recs = e->q_rays.ptr;
@@ -310,11 +320,7 @@ int camera_piece(rb_engine* e, const rb::KParams& p, const rb_camera_ex& cam, ui
     g.n = static_cast<uint32_t>(m);
     g.first_sample = first_sample;
     g.samples = samples;
-    if (const hipError_t st = hipEventRecord(ev[0], e->stream)) return static_cast<int>(st);
-    const int st = rb::launch_camera_rays(g, e->stream);
-    if (st) return st;
-    if (const hipError_t st1 = hipEventRecord(ev[1], e->stream)) return static_cast<int>(st1);
-    e->cam_pieces++;
+    if (const int st = timed_generator(e, [&] { return rb::launch_camera_rays(g, e->stream); })) return st;
     return rb::launch_radiance(p, trace_args(e, e->q_rays.ptr, nullptr, out, done, m, first_sample, samples), e->stream, li, true);
 }
 
@@ -344,6 +350,111 @@ int trace_camera_device_locked(rb_engine* e, const rb_camera_ex& cam, uint64_t f
         if (radiance_scratch(e, piece, samples, true)) return static_cast<int>(hipErrorOutOfMemory);
         for (size_t done = 0; done < n; done += piece) {
             const int st = camera_piece(e, p, cam, first_pixel, done, std::min(piece, n - done), first_sample, samples, d_out + done, li);
+            if (st) return st;
+        }
+        return 0;
+    });
+}
+
+// ---- hemisphere rays made on the device (rb_abi.h)
+// what a call of the family is, beside its buffers
+struct HemiCall {
+    rb_hemi_params prm;
+    uint32_t first_sample, samples;
+    bool openness;
+};
+
+rb::HemiGenArgs hemi_gen_args(const HemiCall& c, const rb_surfel* surfels, const uint32_t* ids, rb_ray* recs, size_t done, size_t m) {
+    rb::HemiGenArgs g{};
+    g.surfels = surfels;
+    g.ids = ids;
+    g.recs = recs;
+    g.offset = c.prm.offset;
+    g.radius = c.prm.radius;
+    g.n = static_cast<uint32_t>(m);
+    g.id_base = static_cast<uint32_t>(done);
+    g.first_sample = c.first_sample;
+    g.samples = c.samples;
+    return g;
+}
+
+// the scratch of one piece of `piece` surfels beside the caller's arrays: records and colours (radiance), or records, bounds
+// and result bytes in linear order (openness)
+int hemi_scratch(rb_engine* e, const HemiCall& c, size_t piece) {
+    if (!c.openness) return radiance_scratch(e, piece, c.samples, true);
+    const size_t items = piece * c.samples;
+    HIP_TRY(e, e->q_rays.reserve(items));
+    HIP_TRY(e, e->q_tmax.reserve(items));
+    HIP_TRY(e, e->q_occl.reserve(items));
+    return RB_OK;
+}
+
+// one piece, queued: surfels [done, done + m) of the call, at `surfels` / `ids` in device memory, into `out` (rb_radiance or
+// rb_openness records).  Radiance: the generator in item order, the k_cam kernel of the scene's walk, the sum.  Openness: the
+// generator in linear order with the bounds beside, the k_occl kernel, the count.
+int hemi_piece(rb_engine* e, const rb::KParams& p, const HemiCall& c, const rb_surfel* surfels, const uint32_t* ids, size_t done,
+               size_t m, void* out, rb::LaunchInfo* li) {
+    rb::HemiGenArgs g = hemi_gen_args(c, surfels, ids, e->q_rays.ptr, done, m);
+    if (c.openness) {
+        g.tmax = e->q_tmax.ptr;
+        g.linear = 1u;
+    }
+    if (const int st = timed_generator(e, [&] { return rb::launch_hemisphere_rays(g, e->stream); })) return st;
+    if (!c.openness)
+        return rb::launch_radiance(p, trace_args(e, e->q_rays.ptr, nullptr, static_cast<rb_radiance*>(out), done, m, c.first_sample, c.samples),
+                                   e->stream, li, true);
+    rb::OcclArgs a{};
+    a.q.rays = e->q_rays.ptr;
+    a.q.n = static_cast<uint32_t>(m * c.samples);
+    a.tmax = e->q_tmax.ptr;
+    a.out = e->q_occl.ptr;
+    a.mask = c.prm.mask;
+    if (const int st = rb::launch_occluded(p, a, e->stream, li)) return st;
+    return rb::launch_hemisphere_count(e->q_occl.ptr, static_cast<uint32_t>(m), c.samples, static_cast<rb_openness*>(out), e->stream);
+}
+
+size_t hemi_piece_surfels(size_t n, uint32_t samples) { return std::min(n, radiance_piece(RB_HEMI_PIECE_ITEMS, samples)); }
+
+int hemisphere_locked(rb_engine* e, const HemiCall& c, const rb_surfel* surfels, const uint32_t* seeds, size_t n, void* out) {
+    rb::KParams p{};
+    e->cam_pieces = 0;
+    int rc = query_prologue(e, &p);
+    if (rc || n == 0) return rc;
+    const size_t piece = hemi_piece_surfels(n, c.samples);
+    rc = hemi_scratch(e, c, piece);
+    if (rc) return rc;
+    HIP_TRY(e, e->hemi_surfels.reserve(piece));
+    if (seeds) HIP_TRY(e, e->rad_seeds.reserve(piece));
+    void* d_out = nullptr;
+    if (c.openness) {
+        HIP_TRY(e, e->hemi_open.reserve(piece));
+        d_out = e->hemi_open.ptr;
+    } else {
+        HIP_TRY(e, e->rad_out.reserve(piece));
+        d_out = e->rad_out.ptr;
+    }
+    const size_t out_stride = c.openness ? sizeof(rb_openness) : sizeof(rb_radiance);
+    return run_pieces(e, "hemisphere", piece, n, {{surfels, e->hemi_surfels.ptr, sizeof(rb_surfel)}, {seeds, e->rad_seeds.ptr, sizeof(uint32_t)}},
+                      {{out, d_out, out_stride}}, [&](size_t done, size_t m, rb::LaunchInfo* li) {
+                          return hemi_piece(e, p, c, e->hemi_surfels.ptr, seeds ? e->rad_seeds.ptr : nullptr, done, m, d_out, li);
+                      });
+}
+
+// every piece queued between the query's two events on the caller's buffers (the pieces share the scratch in stream order);
+// nothing is waited for
+int hemisphere_device_locked(rb_engine* e, const HemiCall& c, const rb_surfel* d_surfels, const uint32_t* d_seeds, size_t n, void* d_out) {
+    const size_t out_stride = c.openness ? sizeof(rb_openness) : sizeof(rb_radiance);
+    int rc = device_range(e, d_surfels, n * sizeof(rb_surfel), 16, "d_surfels");
+    if (!rc && d_seeds) rc = device_range(e, d_seeds, n * sizeof(uint32_t), 4, "d_seeds");
+    if (!rc) rc = device_range(e, d_out, n * out_stride, c.openness ? 8 : 16, "d_out");
+    if (rc) return rc;
+    const size_t piece = hemi_piece_surfels(n, c.samples);
+    e->cam_pieces = 0;
+    return device_query_locked(e, [&](const rb::KParams& p, rb::LaunchInfo* li) {
+        if (hemi_scratch(e, c, piece)) return static_cast<int>(hipErrorOutOfMemory);
+        for (size_t done = 0; done < n; done += piece) {
+            const int st = hemi_piece(e, p, c, d_surfels + done, d_seeds ? d_seeds + done : nullptr, done, std::min(piece, n - done),
+                                      static_cast<char*>(d_out) + done * out_stride, li);
             if (st) return st;
         }
         return 0;
@@ -400,6 +511,20 @@ int camera_check(rb_engine* e, const char* who, const rb_camera_ex* cam, uint64_
         return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: a perspective camera needs tan_half_fov > 0, lens_radius >= 0 and, with a lens, focus_distance > 0", who);
     if (c.kind == RB_CAM_ORTHO && (!(c.half_width > 0.0f) || !(c.half_height > 0.0f)))
         return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: an orthographic camera needs half_width > 0 and half_height > 0", who);
+    return RB_OK;
+}
+
+// the refusals every hemisphere entry point shares; before a device is touched (e may be NULL: rb_hemisphere_rays)
+int hemi_check(rb_engine* e, const char* who, const rb_hemi_params* prm, size_t n, uint32_t first_sample, uint32_t samples, bool openness) {
+    if (const int rc = samples_check(e, who, "surfel", first_sample, samples)) return rc;
+    if (n > 0x7FFFFFFFull - 63ull || static_cast<uint64_t>(n) * samples > 0x7FFFFFFFull - 63ull)
+        return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s takes at most 2^31 - 64 surfels and (surfel, sample) items per call", who);
+    if (!std::isfinite(prm->offset) || prm->offset < 0.0f) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: offset must be finite and at least 0", who);
+    if (prm->flags != 0u) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: unknown flag bits 0x%x", who, prm->flags);
+    for (const uint32_t r : prm->_reserved)
+        if (r != 0u) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: _reserved must be 0", who);
+    if (openness && std::isnan(prm->radius)) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: radius is NaN", who);
+    if (openness && prm->mask > RB_MASK_ALL) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: mask has bits above RB_MASK_ALL", who);
     return RB_OK;
 }
 
@@ -546,6 +671,21 @@ rb_engine* answering(rb_engine* e) {
 int answered(rb_engine* e, rb_engine* t, int rc) {
     if (rc && t != e) copy_error(e, t);
     return rc;
+}
+
+
+// the four engine entry points of the hemisphere family
+int hemisphere_entry(rb_engine* e, const char* who, bool openness, bool device, const rb_surfel* surfels, const uint32_t* seeds, size_t n,
+                     const rb_hemi_params* prm, uint32_t first_sample, uint32_t samples, void* out) {
+    if (!e) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (n > 0 && (!surfels || !prm || !out)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "%s: surfels / params / out is NULL", who);
+    if (prm)
+        if (const int rc = hemi_check(e, who, prm, n, first_sample, samples, openness)) return rc;
+    rb_engine* const t = answering(e);
+    if (n == 0) return answered(e, t, require_ready(t));
+    const HemiCall c{*prm, first_sample, samples, openness};
+    return answered(e, t, device ? hemisphere_device_locked(t, c, surfels, seeds, n, out) : hemisphere_locked(t, c, surfels, seeds, n, out));
 }
 
 }  // namespace
@@ -695,6 +835,63 @@ int rb_trace_camera_device(rb_engine* e, const rb_camera_ex* cam, uint64_t first
     rb_engine* const t = answering(e);
     if (n_pixels == 0) return answered(e, t, require_ready(t));
     return answered(e, t, trace_camera_device_locked(t, *cam, first_pixel, n_pixels, first_sample, samples, d_out));
+}
+
+int rb_hemisphere_rays(int32_t device, const rb_surfel* surfels, const uint32_t* seeds, size_t n, const rb_hemi_params* params,
+                       uint32_t first_sample, uint32_t samples, rb_ray* rays_out, uint32_t* seeds_out) {
+    if (n > 0 && (!surfels || !params || !rays_out || !seeds_out))
+        return rb::fail(nullptr, RB_ERR_NULL_ARGUMENT, "surfels / params / rays_out / seeds_out is NULL");
+    if (params)
+        if (const int rc = hemi_check(nullptr, "rb_hemisphere_rays", params, n, first_sample, samples, false)) return rc;
+    if (n == 0) return RB_OK;
+    if (device >= 0 && hipSetDevice(device) != hipSuccess) return rb::fail(nullptr, RB_ERR_DEVICE, "hipSetDevice(%d) failed", device);
+    const size_t piece = std::min(n, std::max<size_t>((size_t(1) << 22) / samples, 1));   // whole surfels, about 2^22 items
+    rb::DevBuf<rb_surfel> d_surfels;
+    rb::DevBuf<uint32_t> d_ids, d_seeds;
+    rb::DevBuf<rb_ray> d_rays;
+    hipStream_t stream = nullptr;
+    hipError_t st = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
+    if (st == hipSuccess) st = d_surfels.resize(piece);
+    if (st == hipSuccess && seeds) st = d_ids.resize(piece);
+    if (st == hipSuccess) st = d_rays.resize(piece * samples);
+    if (st == hipSuccess) st = d_seeds.resize(piece * samples);
+    const HemiCall c{*params, first_sample, samples, false};
+    for (size_t done = 0; done < n && st == hipSuccess; done += piece) {
+        const size_t m = std::min(piece, n - done), items = m * samples;
+        st = hipMemcpyAsync(d_surfels.ptr, surfels + done, m * sizeof(rb_surfel), hipMemcpyHostToDevice, stream);
+        if (st == hipSuccess && seeds) st = hipMemcpyAsync(d_ids.ptr, seeds + done, m * sizeof(uint32_t), hipMemcpyHostToDevice, stream);
+        rb::HemiGenArgs g = hemi_gen_args(c, d_surfels.ptr, seeds ? d_ids.ptr : nullptr, d_rays.ptr, done, m);
+        g.seeds = d_seeds.ptr;
+        g.linear = 1u;
+        if (st == hipSuccess) st = static_cast<hipError_t>(rb::launch_hemisphere_rays(g, stream));
+        if (st == hipSuccess) st = hipMemcpyAsync(rays_out + done * samples, d_rays.ptr, items * sizeof(rb_ray), hipMemcpyDeviceToHost, stream);
+        if (st == hipSuccess) st = hipMemcpyAsync(seeds_out + done * samples, d_seeds.ptr, items * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
+        if (st == hipSuccess) st = hipStreamSynchronize(stream);   // the scratch is the next piece's
+    }
+    if (stream) (void)hipStreamSynchronize(stream);   // (the buffers are freed on return, after this)
+    if (stream) (void)hipStreamDestroy(stream);
+    if (st != hipSuccess) return rb::fail(nullptr, RB_ERR_DEVICE, "rb_hemisphere_rays failed: %s", hipGetErrorString(st));
+    return RB_OK;
+}
+
+int rb_trace_hemisphere(rb_engine* e, const rb_surfel* surfels, const uint32_t* seeds, size_t n, const rb_hemi_params* params,
+                        uint32_t first_sample, uint32_t samples, rb_radiance* out) {
+    return hemisphere_entry(e, "rb_trace_hemisphere", false, false, surfels, seeds, n, params, first_sample, samples, out);
+}
+
+int rb_trace_hemisphere_device(rb_engine* e, const rb_surfel* d_surfels, const uint32_t* d_seeds, size_t n,
+                               const rb_hemi_params* params, uint32_t first_sample, uint32_t samples, rb_radiance* d_out) {
+    return hemisphere_entry(e, "rb_trace_hemisphere_device", false, true, d_surfels, d_seeds, n, params, first_sample, samples, d_out);
+}
+
+int rb_openness_hemisphere(rb_engine* e, const rb_surfel* surfels, const uint32_t* seeds, size_t n, const rb_hemi_params* params,
+                           uint32_t first_sample, uint32_t samples, rb_openness* out) {
+    return hemisphere_entry(e, "rb_openness_hemisphere", true, false, surfels, seeds, n, params, first_sample, samples, out);
+}
+
+int rb_openness_hemisphere_device(rb_engine* e, const rb_surfel* d_surfels, const uint32_t* d_seeds, size_t n,
+                                  const rb_hemi_params* params, uint32_t first_sample, uint32_t samples, rb_openness* d_out) {
+    return hemisphere_entry(e, "rb_openness_hemisphere_device", true, true, d_surfels, d_seeds, n, params, first_sample, samples, d_out);
 }
 
 int rb_denoise_default_params(rb_denoise_params* p) {

@@ -562,8 +562,65 @@ class Engine:
         self._check(self._lib.rb_trace_camera(self._h, c.ctypes.data, first, n, first_sample, samples, res.ctypes.data if n else None))
         return res
 
+    # ---- hemisphere rays made on the device (rb_abi.h)
+    @staticmethod
+    def _hemi_params(offset, radius=0.0, mask=0):
+        prm = np.zeros(1, dtype=abi.HEMI_PARAMS)
+        prm["offset"], prm["radius"], prm["mask"] = offset, radius, int(mask)
+        return prm
+
+    def _hemisphere(self, host_fn, device_fn, out_dtype, out_row, points, normals, samples, first_sample, seeds, prm, out):
+        """the two forms of a hemisphere query: surfels (abi.RAY's layout) from the points and normals, the call, the result"""
+        samples, first_sample = int(samples), int(first_sample)
+        if not (0 <= samples < 2 ** 32 and 0 <= first_sample < 2 ** 32):
+            raise ValueError("samples and first_sample are 32-bit unsigned numbers")
+        surf = self._ray_records(points, normals)
+        if _is_tensor(surf) or _is_tensor(seeds) or _is_tensor(out):
+            import torch
+            fp, n = self._device_tensor(surf, torch.float32, 8, "points / normals")
+            sp, ns = (None, n)
+            if seeds is not None:   # 32-bit ids, signed or unsigned: the bits are what counts
+                unsigned = _is_tensor(seeds) and seeds.dtype == getattr(torch, "uint32", None)
+                sp, ns = self._device_tensor(seeds, torch.uint32 if unsigned else torch.int32, None, "seeds")
+            t_dtype = torch.float32 if out_dtype is abi.RADIANCE else torch.int32
+            res = torch.empty((n, out_row), dtype=t_dtype, device=surf.device) if out is None else out
+            op, no = self._device_tensor(res, t_dtype, out_row, "out")
+            if ns != n or no != n:
+                raise ValueError("points, seeds and out differ in length")
+            self._device_call(device_fn, fp, sp, n, prm.ctypes.data, first_sample, samples, op)
+            return res
+        n = len(surf)
+        if seeds is not None:
+            seeds = np.ascontiguousarray(seeds, dtype=np.uint32).reshape(-1)
+            if len(seeds) != n:
+                raise ValueError("points and seeds differ in length")
+        res = np.empty(n, dtype=out_dtype) if out is None else out
+        if not isinstance(res, np.ndarray) or res.dtype != out_dtype or res.shape != (n,) or not res.flags.c_contiguous:
+            raise ValueError(f"out: a contiguous array of n {out_dtype} elements is needed")
+        self._check(host_fn(self._h, surf.ctypes.data if n else None, seeds.ctypes.data if (seeds is not None and n) else None, n,
+                            prm.ctypes.data, first_sample, samples, res.ctypes.data if n else None))
+        return res
+
+    def trace_hemisphere(self, points, normals, samples, first_sample=0, seeds=None, offset=1e-3, out=None):
+        """rb_trace_hemisphere: the radiance arriving at (m, 3) surface points over the cosine-weighted hemisphere of their
+        normals (any length: the device normalises), every (point, sample) ray made on the device from its own random
+        stream -> abi.RADIANCE[m] (``sum`` over the samples, ``weight``: the valid samples; sum / weight is the irradiance
+        over pi).  ``seeds``: m uint32 ids or None (the point's index).  Torch tensors on the engine's device for the points
+        and normals, or for ``out`` ((m, 4) float32), go to rb_trace_hemisphere_device: nothing crosses to the host."""
+        return self._hemisphere(self._lib.rb_trace_hemisphere, self._lib.rb_trace_hemisphere_device, abi.RADIANCE, 4, points, normals,
+                                samples, first_sample, seeds, self._hemi_params(offset), out)
+
+    def openness(self, points, normals, samples, radius, mask=abi.MASK_ALL & ~abi.MASK_LIGHTS, first_sample=0, seeds=None, offset=1e-3,
+                 out=None):
+        """rb_openness_hemisphere: of ``samples`` cosine-weighted rays from each point, how many meet nothing of the stages of
+        ``mask`` within ``radius`` (rb_occluded's tmax rules) -> abi.OPENNESS[m] (``open``, ``valid``; open / valid is the
+        ambient-occlusion value).  Torch tensors select rb_openness_hemisphere_device and an (m, 2) int32 tensor comes back."""
+        return self._hemisphere(self._lib.rb_openness_hemisphere, self._lib.rb_openness_hemisphere_device, abi.OPENNESS, 2, points, normals,
+                                samples, first_sample, seeds, self._hemi_params(offset, radius, mask), out)
+
     def last_camera_rays_ms(self):
-        """kernel ms of the generator (k_cam_rays) in the most recent trace_camera: its share of last_query_ms()"""
+        """kernel ms of the generator (k_cam_rays, k_hemi_rays) in the most recent trace_camera, trace_hemisphere or openness:
+        its share of last_query_ms()"""
         ms = C.c_float()
         self._check(self._lib.rb_last_camera_rays_ms(self._h, C.byref(ms)))
         return ms.value
@@ -751,6 +808,29 @@ def camera_rays_device(cam, samples, first_sample=0, region=None, device=-1):
     if rc != abi.RB_OK:
         raise RenderError(rc, (lib.rb_last_error(None) or b"").decode())
     return rays, seeds
+
+
+def hemisphere_rays_device(points, normals, samples, first_sample=0, seeds=None, offset=1e-3, device=-1):
+    """rb_hemisphere_rays: the generator alone, no engine -- (abi.RAY[m * samples], uint32 seeds[m * samples]) of (m, 3)
+    points and normals, item i * samples + k: the origin, the normalised direction (0 0 0: an invalid item) and the seed
+    trace_ray starts with.  ``hemisphere.rays`` is its numpy model."""
+    surf = Engine._ray_records(np.asarray(points, np.float32), np.asarray(normals, np.float32))
+    m, samples = len(surf), int(samples)
+    if not 0 <= samples < 2 ** 32:
+        raise ValueError("samples: a 32-bit unsigned number")
+    if seeds is not None:
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint32).reshape(-1)
+        if len(seeds) != m:
+            raise ValueError("points and seeds differ in length")
+    prm = Engine._hemi_params(offset)
+    items = m * samples if samples <= 65536 else 0   # (a refused call writes nothing)
+    rays, seeds_out = np.zeros(items, dtype=abi.RAY), np.zeros(items, dtype=np.uint32)
+    lib = load()
+    rc = lib.rb_hemisphere_rays(int(device), surf.ctypes.data if m else None, seeds.ctypes.data if (seeds is not None and m) else None, m,
+                                prm.ctypes.data, int(first_sample), samples, rays.ctypes.data, seeds_out.ctypes.data)
+    if rc != abi.RB_OK:
+        raise RenderError(rc, (lib.rb_last_error(None) or b"").decode())
+    return rays, seeds_out
 
 
 def denoise_defaults():

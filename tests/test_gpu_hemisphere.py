@@ -1,0 +1,502 @@
+"""Hemisphere rays made on the device (rb_hemisphere_rays / rb_trace_hemisphere / rb_openness_hemisphere and their device forms;
+DESIGN.md section 16), bit for bit on uint32 views:
+
+  the generator = the numpy model renderbaby_amd/hemisphere.py: origin, direction, seed and pad words of every record;
+  the radiance  = the ordered float32 sum of the unmodified oracle's rbo_trace_ray(scene, o, d, seed) over the very records
+                  rb_hemisphere_rays returned, no surfel left out, for every k_cam kernel;
+  the openness  = the counts of rb_occluded's bytes over those records, and on the feature scene the oracle's closest hit;
+  the forms and the pieces give the same answers, and a call has a query's side effects: none.
+"""
+
+import numpy as np
+import pytest
+
+from renderbaby_amd import Engine, RenderConfig, abi, aov, bake, engine, hemisphere, scenes
+from tests import _oracle
+from tests.conftest import has_gpu
+from tests.test_gpu_camera import oracle_sums
+from tests.test_gpu_query import FAR_LIGHT, SKY_ID, _copy, _engine, _identical_spheres, _normalize, id_scene, oracle_emissive
+from tests.test_gpu_radiance import _mesh, _u32, given_seeds
+from tests.test_hemisphere_abi import INVALID_OPTIONS, NULL_ARGUMENT, OPENNESS_REFUSALS, REFUSALS, _params
+
+pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not has_gpu(), reason="needs a GPU")]
+
+f32 = np.float32
+PIECE = abi.HEMI_PIECE_ITEMS
+NO_LIGHTS = abi.MASK_ALL & ~abi.MASK_LIGHTS
+AXES = [(1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 1), (0, 0, -1)]
+
+
+def model_surfels(m, seed=4):
+    """m surfels for the generator: random points and normals, then from the front the six axes, z = -0, z = -1 beside a tiny
+    x, unnormalised normals of lengths 1e-20 and 1e18, and invalid ones (an Inf and a NaN in pos, a zero normal, a normal
+    whose squared length overflows, a point so far out that the origin overflows); position 0 keeps a valid one"""
+    rng = np.random.default_rng(seed)
+    pts = (rng.normal(size=(m, 3)) * 3.0).astype(f32)
+    nrm = rng.normal(size=(m, 3)).astype(f32)
+    unit = _normalize(rng.normal(size=(4, 3)).astype(f32))
+    special = [((1, 2, 3), a) for a in AXES] + [((1, 2, 3), (0.6, 0.8, -0.0)), ((0, 0, 0), (1e-5, 0.0, -1.0)),
+                                                 ((-4, 5, 6), unit[0] * f32(1e-20)), ((7, -8, 9), unit[1] * f32(1e18)),
+                                                 ((np.inf, 0, 0), (0, 1, 0)), ((0, np.nan, 0), (0, 1, 0)), ((1, 1, 1), (0, 0, 0)),
+                                                 ((1, 1, 1), unit[2] * f32(3e19)), ((3e38, 3e38, 0), (0, 1, 0))]
+    for j, (p, n) in enumerate(special):
+        i = 1 + 3 * j   # spread over the first blocks of 64 where m allows it
+        if i < m:
+            pts[i], nrm[i] = p, n
+    return pts, nrm
+
+
+# ---- 1. the generator against the model
+@pytest.mark.parametrize("offset", [0.0, 1e-3])
+@pytest.mark.parametrize("with_seeds", [False, True], ids=["index", "seeds"])
+def test_generator_equals_the_model(with_seeds, offset):
+    n_invalid = 0
+    for m in (1, 63, 65, 130):
+        pts, nrm = model_surfels(m)
+        ids = given_seeds(m) if (with_seeds and m >= 7) else (np.arange(m, dtype=np.uint32) * np.uint32(2654435761) if with_seeds else None)
+        ranges = [(0, m)] + ([(70, 60), (127, 2), (64, 64)] if m == 130 else [])   # 70 .. 129: starts and ends inside a block of 64
+        for first, n in ranges:
+            for samples, first_sample in ((1, 0), (2, 7), (5, 0), (5, 7)):
+                sl = slice(first, first + n)
+                sid = None if ids is None else ids[sl]
+                rays, seeds = engine.hemisphere_rays_device(pts[sl], nrm[sl], samples, first_sample, seeds=sid, offset=offset, device=0)
+                o, d, s = hemisphere.rays(hemisphere.surfels(pts[sl], nrm[sl]), first_sample, samples, seeds=sid, offset=offset)
+                where = (with_seeds, offset, m, first, n, samples, first_sample)
+                assert rays.shape == (n * samples,) and seeds.shape == (n * samples,), where
+                assert np.array_equal(seeds, s), where
+                bad = np.nonzero((_u32(rays["origin"]) != _u32(o)).any(1))[0]
+                assert len(bad) == 0, (where, bad[:5], rays["origin"][bad[:5]], o[bad[:5]])
+                bad = np.nonzero((_u32(rays["dir"]) != _u32(d)).any(1))[0]
+                assert len(bad) == 0, (where, bad[:5], rays["dir"][bad[:5]], d[bad[:5]])
+                assert (_u32(rays["_pad0"]) == 0).all() and (_u32(rays["_pad1"]) == 0).all(), where
+                n_invalid += int((d == 0).all(1).sum())
+                if ids is None and first > 0:   # seeds = NULL names a surfel by its index in the CALL
+                    whole = hemisphere.rays(hemisphere.surfels(pts, nrm), first_sample, samples, offset=offset)[2]
+                    assert not np.array_equal(s, whole[first * samples:(first + n) * samples])
+    assert n_invalid > 0, "no invalid surfel was mixed in"
+
+
+# ---- 2. the radiance against the oracle on the generated rays
+def scene_surfels(e, scene, m=130):
+    """the first m hit points of render_hits with their normals turned towards the camera"""
+    hits = e.render_hits()
+    _, pts, nrm = aov.ambient_occlusion_surfels(scene.uniforms, hits)
+    assert len(pts) >= m, (scene.name, len(pts))
+    return np.ascontiguousarray(pts[:m]), np.ascontiguousarray(nrm[:m])
+
+
+def check_trace(scene, kernel, **kw):
+    e = _engine(scene, **kw)
+    try:
+        pts, nrm = scene_surfels(e, scene)
+        st0, lit = e.stats(), 0
+        for samples, first_sample, ids in ((5, 7, None), (1, 0, given_seeds(len(pts)))):
+            got = e.trace_hemisphere(pts, nrm, samples, first_sample, seeds=ids)
+            assert e.last_query_kernel_name() == kernel, e.last_query_kernel_name()
+            assert e.last_query_ms() > 0 and 0 < e.last_camera_rays_ms() <= e.last_query_ms()
+            rays, seeds = engine.hemisphere_rays_device(pts, nrm, samples, first_sample, seeds=ids, device=0)
+            want = oracle_sums(scene, rays, seeds, samples)
+            bad = np.nonzero((_u32(got).reshape(-1, 4) != _u32(want).reshape(-1, 4)).any(1))[0]
+            assert len(bad) == 0, (scene.name, kernel, samples, len(bad), bad[:5], got[bad[:5]], want[bad[:5]])
+            assert (got["weight"] == samples).all()
+            lit += int((want["sum"] != 0).any(1).sum())
+        assert lit > 0, "no surfel of the scene carried any light"
+        assert e.stats() == st0, "hemisphere queries moved rb_get_stats"
+    finally:
+        e.close()
+
+
+@pytest.mark.parametrize("color_hash", [0, 1])
+def test_feature_scene(color_hash):
+    check_trace(scenes.feature_scene(width=24, height=16, color_hash=color_hash), "k_cam")
+
+
+@pytest.mark.parametrize("kw,kernel", [(dict(), "k_cam_chunk"), (dict(reference_walk=True), "k_cam_bvh")])
+def test_multi_node_mesh(kw, kernel):
+    s = _mesh()
+    assert len(s.bvh_triangles) == 578
+    check_trace(s, kernel, **kw)
+
+
+def test_identical_spheres():
+    check_trace(_identical_spheres().with_params(width=24, height=24), "k_cam_bvh")
+
+
+def _mesh_beside_spheres():
+    m = _mesh()
+    b = scenes.spheres_scene(n=150, width=32, height=20, spp=1, max_depth=4, extent=5.0)
+    sp = b.spheres.copy()
+    sp["center"][:, 1] += f32(1.0)
+    s = _copy(m, spheres=sp)
+    s.uniforms["spheres_count"] = len(sp)
+    return s
+
+
+def test_mesh_beside_a_sphere_tree():
+    check_trace(_mesh_beside_spheres(), "k_cam_chunk")
+
+
+def test_depth_zero_and_one_and_invalid_surfels():
+    s = scenes.feature_scene(width=24, height=16)
+    for depth in (0, 1):
+        sd = s.with_params(max_depth=depth)
+        e = _engine(sd)
+        try:
+            pts, nrm = scene_surfels(e, sd)
+            bad_p, bad_n = model_surfels(130)
+            mixed = np.arange(130) % 3 == 1   # the special surfels of model_surfels, the invalid ones among them
+            pts[mixed], nrm[mixed] = bad_p[mixed], bad_n[mixed]
+            got = e.trace_hemisphere(pts, nrm, 3)
+            rays, seeds = engine.hemisphere_rays_device(pts, nrm, 3, device=0)
+            want = oracle_sums(sd, rays, seeds, 3)
+            assert np.array_equal(_u32(got), _u32(want))
+            gone = (rays["dir"] == 0).all(1).reshape(130, 3).all(1)
+            assert 3 <= gone.sum() < 130 and (_u32(got[gone]) == 0).all() and (got["weight"][~gone] == 3).all()   # {+0, +0, +0, +0}
+            if depth == 0:
+                assert (_u32(got["sum"]) == 0).all()
+            else:
+                assert (got["sum"] != 0).any(1).sum() > 20   # the winner's emission, the sky for a miss
+        finally:
+            e.close()
+
+
+# ---- 3. openness
+OPEN_SCENES = {"feature": (lambda: scenes.feature_scene(width=24, height=16), dict(), "k_occl"),
+               "mesh chunk": (_mesh, dict(), "k_occl_chunk"), "mesh bvh": (_mesh, dict(reference_walk=True), "k_occl_bvh"),
+               "spheres": (lambda: _identical_spheres().with_params(width=24, height=24), dict(), "k_occl_bvh"),
+               "mesh + spheres": (_mesh_beside_spheres, dict(), "k_occl_chunk")}
+
+
+def counts_of(occ, samples):
+    """abi.OPENNESS[m] from rb_occluded's bytes"""
+    b = occ.reshape(-1, samples)
+    out = np.zeros(len(b), dtype=abi.OPENNESS)
+    out["open"], out["valid"] = (b == abi.OCCL_VISIBLE).sum(1), (b != abi.OCCL_INVALID).sum(1)
+    return out
+
+
+@pytest.mark.parametrize("name", list(OPEN_SCENES))
+def test_openness_equals_the_counts_of_rb_occluded(name):
+    make, kw, kernel = OPEN_SCENES[name]
+    s = make()
+    e = _engine(s, **kw)
+    try:
+        pts, nrm = scene_surfels(e, s)
+        bad_p, bad_n = model_surfels(130)
+        mixed = np.arange(130) % 3 == 1   # the special surfels of model_surfels, the invalid ones among them
+        pts[mixed], nrm[mixed] = bad_p[mixed], bad_n[mixed]
+        st0, blocked = e.stats(), 0
+        for samples, first_sample, radius, mask in ((5, 7, 1.5, NO_LIGHTS), (4, 0, 4.0, abi.MASK_ALL), (16, 3, 0.5, NO_LIGHTS),
+                                                    (3, 0, 0.001, abi.MASK_ALL), (3, 0, np.inf, abi.MASK_ALL), (3, 0, 1e20, abi.MASK_ALL),
+                                                    (3, 0, 0.0, abi.MASK_ALL), (3, 0, -np.inf, abi.MASK_ALL), (4, 0, 4.0, 0),
+                                                    (4, 0, 4.0, abi.MASK_GROUND), (4, 0, 4.0, abi.MASK_SPHERES | abi.MASK_TRIANGLES)):
+            got = e.openness(pts, nrm, samples, radius, mask, first_sample=first_sample)
+            assert e.last_query_kernel_name() == kernel, e.last_query_kernel_name()
+            assert e.last_query_ms() > 0 and 0 < e.last_camera_rays_ms() <= e.last_query_ms()
+            rays, _ = engine.hemisphere_rays_device(pts, nrm, samples, first_sample, device=0)
+            occ = e.occluded_records(rays, np.full(len(rays), radius, f32), mask)
+            want = counts_of(occ, samples)
+            where = (name, samples, first_sample, radius, mask)
+            assert got.dtype == abi.OPENNESS and np.array_equal(got["open"], want["open"]) and np.array_equal(got["valid"], want["valid"]), where
+            gone = (rays["dir"] == 0).all(1).reshape(130, samples).all(1)
+            assert gone.sum() >= 3 and (got["valid"][gone] == 0).all() and (got["open"][gone] == 0).all() and (got["valid"][~gone] == samples).all(), where
+            if radius <= 0.001 or mask == 0:
+                assert np.array_equal(got["open"], got["valid"]), where   # everything open
+            if radius == np.inf:
+                assert np.array_equal(want["open"], counts_of(e.occluded_records(rays, None, mask), samples)["open"])
+                again = e.openness(pts, nrm, samples, 1e20, mask, first_sample=first_sample)
+                assert np.array_equal(_u32(got), _u32(again))
+            blocked += int((got["valid"] - got["open"]).sum())
+        assert blocked > 0, "nothing in the scene occluded anything"
+        assert e.stats() == st0, "openness queries moved rb_get_stats"
+    finally:
+        e.close()
+
+
+def test_openness_against_the_oracle_walk():
+    """rbo_trace_ray with max_depth = 1 on the emissive-tagged copy names the winner of the oracle's own closest-hit search;
+    rbo_intersect_* on that primitive gives its t; a sample is open exactly when not t < radius (RB_MASK_ALL: rb_abi.h's
+    relation, as tests/test_gpu_occlusion.py checks it).  The oracle walks the direction as k_occl* normalise it again."""
+    s = scenes.feature_scene(width=24, height=16)
+    ids = id_scene(s, per_triangle=True)
+    e = _engine(s)
+    try:
+        pts, nrm = scene_surfels(e, s)
+        samples = 4
+        rays, _ = engine.hemisphere_rays_device(pts, nrm, samples, 7, device=0)
+        O, D = np.ascontiguousarray(rays["origin"]), _normalize(rays["dir"])
+        assert np.isfinite(D).all()
+        em = oracle_emissive(ids, O, D)
+        t = np.full(len(O), 1e20, f32)
+        gh = float(s.uniforms["ground_height"][0])
+        for i in range(len(O)):
+            k = em[i]
+            if tuple(k) == SKY_ID:
+                continue
+            if k[0] == 0:
+                t[i] = _oracle.isect_ground(O[i], D[i], gh)
+            elif int(k[0]) == abi.HIT_TRIANGLE:
+                tri = s.bvh_triangles[int(k[1]) - 1]
+                t[i] = _oracle.isect_triangle(O[i], D[i], tri["v0"], tri["v1"], tri["v2"])[0]
+            else:
+                p = (s.spheres if int(k[0]) == abi.HIT_SPHERE else s.lights)[int(k[1]) - 1]
+                t[i] = _oracle.isect_sphere(O[i], D[i], p["center"], float(p["radius"]))
+        assert (t < f32(1e20)).any()
+        for radius in (0.5, 1.5, 4.0, 100.0, np.inf):
+            got = e.openness(pts, nrm, samples, radius, abi.MASK_ALL, first_sample=7)
+            want = (~(t < f32(min(radius, 1e20)))).reshape(-1, samples).sum(1)
+            assert np.array_equal(got["open"], want) and (got["valid"] == samples).all(), radius
+        assert 0 < got["open"].sum() < got["valid"].sum()
+    finally:
+        e.close()
+
+
+# ---- 4. forms and pieces
+def test_device_forms_and_a_forced_launch_shape_equal_the_host_forms():
+    import torch
+    s = _mesh()
+    e = _engine(s)
+    try:
+        pts, nrm = scene_surfels(e, s)
+        bad_p, bad_n = model_surfels(130)
+        pts[1::3], nrm[1::3] = bad_p[1::3], bad_n[1::3]
+        ids = given_seeds(130)
+        tp, tn = torch.from_numpy(pts).cuda(), torch.from_numpy(nrm).cuda()
+        tids = torch.from_numpy(ids.view(np.int32)).cuda()
+        for sid, tsid in ((None, None), (ids, tids)):
+            rad = e.trace_hemisphere(pts, nrm, 5, 7, seeds=sid)
+            opn = e.openness(pts, nrm, 5, 2.0, first_sample=7, seeds=sid)
+            d_rad = e.trace_hemisphere(tp, tn, 5, 7, seeds=tsid)
+            assert e.last_query_kernel_name() == "k_cam_chunk" and e.last_query_ms() > 0
+            d_opn = e.openness(tp, tn, 5, 2.0, first_sample=7, seeds=tsid)
+            assert e.last_query_kernel_name() == "k_occl_chunk" and e.last_query_ms() > 0
+            assert d_rad.shape == (130, 4) and d_rad.is_cuda and d_opn.shape == (130, 2) and d_opn.dtype == torch.int32
+            assert np.array_equal(_u32(d_rad.cpu().numpy()), _u32(rad).reshape(-1, 4))
+            assert np.array_equal(_u32(d_opn.cpu().numpy()), _u32(opn).reshape(-1, 2))
+        # out= : an array or a tensor to fill
+        filled = np.zeros(130, dtype=abi.RADIANCE)
+        assert e.trace_hemisphere(pts, nrm, 5, 7, seeds=ids, out=filled) is filled and np.array_equal(_u32(filled), _u32(rad))
+        out = torch.full((130, 4), -1.0, dtype=torch.float32, device="cuda")
+        assert e.trace_hemisphere(tp, tn, 5, 7, seeds=tids, out=out) is out and np.array_equal(_u32(out.cpu().numpy()), _u32(rad).reshape(-1, 4))
+        # sub-ranges with their ids equal the whole call's records
+        for first, n in ((70, 60), (127, 2), (64, 64), (0, 1), (129, 1)):
+            sl = slice(first, first + n)
+            assert np.array_equal(_u32(e.trace_hemisphere(pts[sl], nrm[sl], 5, 7, seeds=ids[sl])), _u32(rad[sl])), (first, n)
+            assert np.array_equal(_u32(e.openness(pts[sl], nrm[sl], 5, 2.0, first_sample=7, seeds=ids[sl])), _u32(opn[sl])), (first, n)
+        assert len(e.trace_hemisphere(pts[:0], nrm[:0], 5)) == 0 and len(e.openness(pts[:0], nrm[:0], 5, 1.0)) == 0
+        # bake.irradiance_device on tensors stays on the device and equals the host form's mean
+        mean = bake.irradiance_device(e, pts, nrm, 5, first_sample=7, seeds=ids)
+        d_mean = bake.irradiance_device(e, tp, tn, 5, first_sample=7, seeds=tids)
+        assert mean.shape == (130, 3) and d_mean.is_cuda and np.allclose(d_mean.cpu().numpy(), mean, rtol=1e-6, atol=0)   # (torch divides there)
+        # the launch shape: reservations of 64 items on a grid of one block per CU
+        o = _engine(s, queue_batch=64, blocks_per_cu=1)
+        try:
+            assert np.array_equal(_u32(o.trace_hemisphere(pts, nrm, 5, 7, seeds=ids)), _u32(rad))
+            assert np.array_equal(_u32(o.openness(pts, nrm, 5, 2.0, first_sample=7, seeds=ids)), _u32(opn))
+        finally:
+            o.close()
+        for bad in (dict(out=np.zeros(130, f32)), dict(out=out[:5]), dict(out=out[:, :3]), dict(samples=-1), dict(seeds=ids[:5])):
+            with pytest.raises(ValueError):
+                e.trace_hemisphere(pts, nrm, **dict(dict(samples=1), **bad))
+    finally:
+        e.close()
+
+
+def test_a_call_across_a_piece_boundary():
+    """RB_HEMI_PIECE_ITEMS + 77 * samples items at samples = 64 on the feature scene: two pieces.  Every surfel against two
+    calls split at the piece boundary (seeds carry the indices on); the last 77 surfels and the 32 before the boundary
+    against the oracle; the openness of the same call against its two halves."""
+    samples = 64
+    b = PIECE // samples
+    n = b + 77
+    s = scenes.feature_scene(width=24, height=16)
+    e = _engine(s)
+    try:
+        p0, n0 = scene_surfels(e, s, 200)
+        idx = np.arange(n) % 200
+        pts, nrm = np.ascontiguousarray(p0[idx]), np.ascontiguousarray(n0[idx])
+        ids = np.arange(n, dtype=np.uint32)
+        one = e.trace_hemisphere(pts, nrm, samples, 7)
+        assert e.last_query_kernel_name() == "k_cam" and e.last_query_ms() > 0
+        two = np.concatenate([e.trace_hemisphere(pts[:b], nrm[:b], samples, 7), e.trace_hemisphere(pts[b:], nrm[b:], samples, 7, seeds=ids[b:])])
+        assert np.array_equal(_u32(one), _u32(two))
+        assert (one["weight"] == samples).all() and (one["sum"] != 0).any(1).sum() > 1000
+        assert not np.array_equal(_u32(one[:200]), _u32(one[200:400]))   # the same surfels under other ids
+        tail = slice(b - 32, n)
+        rays, seeds = engine.hemisphere_rays_device(pts[tail], nrm[tail], samples, 7, seeds=ids[tail], device=0)
+        assert np.array_equal(_u32(one[tail]), _u32(oracle_sums(s, rays, seeds, samples)))
+        opn = e.openness(pts, nrm, samples, 2.0)
+        assert e.last_query_kernel_name() == "k_occl"
+        halves = np.concatenate([e.openness(pts[:b], nrm[:b], samples, 2.0), e.openness(pts[b:], nrm[b:], samples, 2.0, seeds=ids[b:])])
+        assert np.array_equal(_u32(opn), _u32(halves)) and (opn["valid"] == samples).all() and 0 < opn["open"].sum() < opn["valid"].sum()
+        rays, _ = engine.hemisphere_rays_device(pts[tail], nrm[tail], samples, 0, seeds=ids[tail], device=0)
+        want = counts_of(e.occluded_records(rays, np.full(len(rays), 2.0, f32), NO_LIGHTS), samples)
+        assert np.array_equal(_u32(opn[tail]), _u32(want))
+    finally:
+        e.close()
+
+
+def test_a_hemisphere_query_between_iterator_frames():
+    s = scenes.feature_scene(width=48, height=32, spp=4)
+    rc = RenderConfig.from_scene(s)
+    small = scenes.feature_scene(width=24, height=16)
+    probe = _engine(small)
+    pts, nrm = scene_surfels(probe, small)
+    probe.close()
+
+    def frames(query):
+        e = Engine.new(rc, device=0)
+        it = e.frame_iterator(rc)
+        out, answers = [], []
+        while it.has_next():
+            out.append(it.next().pixels.copy())
+            if query:
+                kernel = e.last_kernel_name()
+                answers.append((e.trace_hemisphere(pts, nrm, 3), e.openness(pts, nrm, 3, 2.0)))
+                assert e.last_kernel_name() == kernel and e.last_query_kernel_name() == "k_occl"
+        acc, st = e.read_accumulation(), e.stats()
+        e.close()
+        return out, acc, st, answers
+    plain, acc0, st0, _ = frames(False)
+    asked, acc1, st1, answers = frames(True)
+    assert len(plain) == len(asked) == 4
+    for a, b in zip(plain, asked):
+        assert np.array_equal(a, b)
+    assert np.array_equal(_u32(acc0), _u32(acc1))
+    assert all(st0[k] == st1[k] for k in st0 if not k.endswith("_ms")), (st0, st1)
+    for rad, opn in answers[1:]:
+        assert np.array_equal(_u32(rad), _u32(answers[0][0])) and np.array_equal(_u32(opn), _u32(answers[0][1]))
+
+
+def test_refusals_leave_the_engine_rendering_the_golden_frame():
+    import torch
+    from renderbaby_amd._lib import load
+    lib = load()
+    s = scenes.cornell(32, 32, 2, 4)
+    rc = RenderConfig.from_scene(s)
+    e = Engine.new(rc, device=0)
+    pts = np.array([(0.0, 0.1 * i, 0.0) for i in range(4)], f32)
+    nrm = np.tile(f32([0, 1, 0]), (4, 1))
+    surf = hemisphere.surfels(pts, nrm)
+    try:
+        e.update(rc)
+        h = e._h
+        base = _params(radius=2.0, mask=NO_LIGHTS)
+        before = e.trace_hemisphere(pts, nrm, 2), e.openness(pts, nrm, 2, 2.0)
+        d_surf = torch.from_numpy(surf.view(f32).reshape(-1, 8)).cuda()
+        forms = []
+        for host_fn, dev_fn, dtype, t_dtype, row, extra in ((lib.rb_trace_hemisphere, lib.rb_trace_hemisphere_device, abi.RADIANCE, torch.float32, 4, []),
+                                                            (lib.rb_openness_hemisphere, lib.rb_openness_hemisphere_device, abi.OPENNESS, torch.int32, 2,
+                                                             OPENNESS_REFUSALS)):
+            out = np.full(64, 7, dtype=np.uint32).view(dtype) if dtype is abi.OPENNESS else np.full(64, 7, dtype=dtype)
+            d_out = torch.full((64, row), 7, dtype=t_dtype, device="cuda")
+            forms.append((dev_fn, d_out))
+            for fn, sp, o in ((host_fn, surf.ctypes.data, out.ctypes.data), (dev_fn, d_surf.data_ptr(), d_out.data_ptr())):
+                for name, kw in REFUSALS:
+                    args = dict(n=4, first_sample=0, samples=2, params=base)
+                    args.update(kw)
+                    prm = args["params"]
+                    assert fn(h, sp, None, args["n"], prm.ctypes.data, args["first_sample"], args["samples"], o) == INVALID_OPTIONS, name
+                    assert lib.rb_last_error(h)
+                for name, fields in extra:
+                    assert fn(h, sp, None, 4, _params(**dict(dict(radius=2.0, mask=NO_LIGHTS), **fields)).ctypes.data, 0, 2, o) == INVALID_OPTIONS, name
+                assert fn(h, None, None, 4, base.ctypes.data, 0, 2, o) == NULL_ARGUMENT and fn(h, sp, None, 4, None, 0, 2, o) == NULL_ARGUMENT
+                assert fn(h, sp, None, 4, base.ctypes.data, 0, 2, None) == NULL_ARGUMENT
+                assert fn(h, None, None, 0, base.ctypes.data, 0, 2, None) == 0 and fn(h, None, None, 0, None, 0, 2, None) == 0   # n == 0
+            lib.rb_sync(h)
+            assert (out.view(np.uint32) == (7 if dtype is abi.OPENNESS else np.float32(7).view(np.uint32))).all() and (d_out == 7).all().item()
+            # the device form's buffers: a host pointer, a misaligned one, an allocation that ends before n elements
+            bp = base.ctypes.data
+            assert dev_fn(h, surf.ctypes.data, None, 4, bp, 0, 2, d_out.data_ptr()) == INVALID_OPTIONS
+            assert dev_fn(h, d_surf.data_ptr(), None, 4, bp, 0, 2, out.ctypes.data) == INVALID_OPTIONS
+            assert dev_fn(h, d_surf.data_ptr() + 4, None, 3, bp, 0, 2, d_out.data_ptr()) == INVALID_OPTIONS
+            assert dev_fn(h, d_surf.data_ptr(), None, 4, bp, 0, 2, d_out.data_ptr() + 4) == INVALID_OPTIONS
+            assert dev_fn(h, d_surf.data_ptr(), None, 1 << 20, bp, 0, 1, d_out.data_ptr()) == INVALID_OPTIONS
+            assert dev_fn(h, d_surf.data_ptr(), d_out.data_ptr() + 2, 4, bp, 0, 2, d_out.data_ptr()) == INVALID_OPTIONS   # d_seeds
+            assert (d_out == 7).all().item()
+        for (dev_fn, d_out), want in zip(forms, before):
+            assert dev_fn(h, d_surf.data_ptr(), None, 4, base.ctypes.data, 0, 2, d_out.data_ptr()) == 0 and lib.rb_sync(h) == 0
+            assert np.array_equal(_u32(d_out.cpu().numpy()[:4]), _u32(want).reshape(4, -1)) and (d_out[4:] == 7).all().item()
+        assert np.array_equal(_u32(e.trace_hemisphere(pts, nrm, 2)), _u32(before[0]))
+        assert np.array_equal(_u32(e.openness(pts, nrm, 2, 2.0)), _u32(before[1]))
+        assert np.array_equal(e.render(rc).pixels, _oracle.render(s)[2])
+    finally:
+        e.close()
+    cold = Engine.new(rc, device=0)   # no update yet: not ready, and still a refusal first
+    try:
+        out = np.zeros(4, dtype=abi.RADIANCE)
+        assert lib.rb_trace_hemisphere(cold._h, surf.ctypes.data, None, 4, base.ctypes.data, 0, 2, out.ctypes.data) not in (0, INVALID_OPTIONS)
+        assert lib.rb_trace_hemisphere(cold._h, surf.ctypes.data, None, 4, base.ctypes.data, 0, 0, out.ctypes.data) == INVALID_OPTIONS
+        assert np.array_equal(cold.render(rc).pixels, _oracle.render(s)[2])
+    finally:
+        cold.close()
+
+
+def test_sharded_engine_and_multi_device_handle():
+    """both forms on a sharded engine (a surfel sees the whole scene) and on a multi-device handle on one device"""
+    import torch
+    s = scenes.feature_scene(width=24, height=16)
+    e = _engine(s)
+    pts, nrm = scene_surfels(e, s)
+    want = e.trace_hemisphere(pts, nrm, 2, 7), e.openness(pts, nrm, 2, 2.0, first_sample=7)
+    e.close()
+    tp, tn = torch.from_numpy(pts).cuda(), torch.from_numpy(nrm).cuda()
+    for kw in (dict(shard_rank=1, shard_count=3, stripe_rows=8), dict(devices=[0, 0], gather_peer_copy=True)):
+        p = _engine(s, **kw)
+        try:
+            assert np.array_equal(_u32(p.trace_hemisphere(pts, nrm, 2, 7)), _u32(want[0])), kw
+            assert np.array_equal(_u32(p.openness(pts, nrm, 2, 2.0, first_sample=7)), _u32(want[1])), kw
+            dev = p.trace_hemisphere(tp, tn, 2, 7)
+            assert np.array_equal(_u32(dev.cpu().numpy()), _u32(want[0]).reshape(-1, 4)), kw
+            assert p.last_query_kernel_name() == "k_cam" and p.last_query_ms() > 0
+            dev = p.openness(tp, tn, 2, 2.0, first_sample=7)
+            assert np.array_equal(_u32(dev.cpu().numpy()), _u32(want[1]).reshape(-1, 2)), kw
+            assert p.last_query_kernel_name() == "k_occl" and p.last_query_ms() > 0
+        finally:
+            p.close()
+
+
+# ---- 5. the point of it
+def test_open_ground_a_sphere_overhead_and_the_two_bakers():
+    """The checkerboard ground under a uniform sky with an emissive sphere overhead and a large sphere resting on the ground.
+    A surfel on the open ground is open in every direction (the emissive sphere is beyond the radius); one beside the point
+    where the large sphere touches the ground sees the sphere in most directions.  bake.irradiance_device agrees with
+    bake.irradiance at 256 samples within 5 standard errors of the difference of the two means, from the per-sample values:
+    the host path's own (one rb_trace_rays item per sample), the device path's from the oracle on its records."""
+    u = scenes.make_uniforms(16, 16, 1, 4, cam_pos=(0, 3, 8), cam_dir=(0, -0.3, -1), ground_enabled=1, ground_height=0.0,
+                             checkerboard_enabled=1, sky=(0.5, 0.7, 1.0))
+    sp = np.zeros(2, dtype=abi.SPHERE)
+    sp[0]["center"], sp[0]["radius"], sp[0]["material"] = (0.0, 9.0, 0.0), 3.0, scenes.material(diffuse=(0, 0, 0), emissive=(4.0, 3.0, 2.0))
+    sp[1]["center"], sp[1]["radius"], sp[1]["material"] = (10.0, 2.0, 0.0), 2.0, scenes.sphere_material("plastic", (0.8, 0.3, 0.2))
+    s = scenes._finish("bake", u, sp, FAR_LIGHT.copy(), [])
+    pts = np.array([(0, 0, 0), (1.5, 0, -1), (-3, 0, 2), (10.3, 0, 0.2), (-5, 0, 0), (0.5, 0, 0.5)], f32)
+    nrm = np.tile(f32([0, 1, 0]), (len(pts), 1))
+    samples = 256
+    e = _engine(s)
+    try:
+        opn = e.openness(pts, nrm, samples, 5.0)   # the emissive sphere begins 6 above the ground; the resting one is 4 across
+        assert (opn["valid"] == samples).all()
+        assert all(opn["open"][i] == samples for i in (0, 1, 2, 4, 5)), opn
+        assert opn["open"][3] * 2 < samples, opn
+        ao = opn["open"] / opn["valid"]
+        print("openness:", ao)
+        # the host path, per sample
+        org, dirs = bake.irradiance_rays(pts, nrm, samples)
+        host = e.trace_rays(org, dirs, seeds=np.arange(len(org), dtype=np.uint32), samples=1)["sum"].reshape(len(pts), samples, 3).astype(np.float64)
+        host_mean = bake.irradiance(e, pts, nrm, samples)
+        assert np.allclose(host_mean, host.mean(1), rtol=1e-4, atol=1e-6)
+        # the device path, per sample: the oracle on the generator's records, whose ordered sum is the device's
+        dev_mean = bake.irradiance_device(e, pts, nrm, samples)
+        rays, seeds = engine.hemisphere_rays_device(pts, nrm, samples, device=0)
+        per = oracle_sums(s, rays, seeds, 1)["sum"].reshape(len(pts), samples, 3).astype(np.float64)
+        rad = e.trace_hemisphere(pts, nrm, samples)
+        assert np.array_equal(_u32(rad), _u32(oracle_sums(s, rays, seeds, samples)))
+        assert np.array_equal(_u32(dev_mean), _u32((rad["sum"] / rad["weight"][:, None]).astype(f32)))
+        se = np.sqrt(host.var(1, ddof=1) / samples + per.var(1, ddof=1) / samples)
+        diff = np.abs(dev_mean.astype(np.float64) - host_mean.astype(np.float64))
+        print("mean radiance, host:", host_mean, "device:", dev_mean, "difference / standard error:", diff / np.maximum(se, 1e-30))
+        assert (se > 0).all() and (diff <= 5.0 * se).all(), (diff, se)
+        # under the resting sphere far less light arrives than on the open ground below the emissive one
+        assert 0 < dev_mean[3].sum() < dev_mean[0].sum()
+    finally:
+        e.close()

@@ -5,7 +5,7 @@
                                  [--aov depth,normal,albedo,emission,id,ao] [--ao-radius R]
                                  [--denoise [--denoise-iterations N]]
                                  [--camera equirect|ortho|thin-lens [--ortho-width W] [--aperture A --focus-distance F] [--jitter]]
-                                 [--probe x,y,z [--probe-normal x,y,z]]
+                                 [--probe x,y,z [--probe-normal x,y,z]] [--device-rays]
 
 scene file -> scene_io.load_scene (the importer's and the Scene->RenderConfig adapter's rules) ->
 RenderConfig -> librenderbaby_hip.so -> Frame -> PNG.  With --every N the progressive iterator is used
@@ -18,7 +18,9 @@ the scene camera's position and direction (bake.camera_rays -> bake.render_rays:
 samples each), as out.<camera>.png; with --jitter every sample's ray is made on the device instead -- sub-pixel jitter and, for the
 thin lens, a lens point per sample, focused on a plane at the focus distance (camera.make -> bake.render_camera:
 Engine.trace_camera).  --probe prints the mean radiance over the cosine-weighted hemisphere at a point
-(bake.irradiance, spp rays; normal +y unless --probe-normal says otherwise).
+(bake.irradiance, spp rays; normal +y unless --probe-normal says otherwise).  --device-rays makes the hemisphere rays of
+--aov ao and --probe on the device (aov.ambient_occlusion_device, bake.irradiance_device): other
+directions than the host generators', the same estimate.
 """
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -41,6 +43,7 @@ ap.add_argument("--focus-distance", type=float, default=5.0)
 ap.add_argument("--jitter", action="store_true", help="--camera with a ray per sample, made on the device: anti-aliased, and a thin lens that blurs")
 ap.add_argument("--probe", default=None, help="x,y,z: print the mean radiance arriving at this point (bake.irradiance)")
 ap.add_argument("--probe-normal", default="0,1,0")
+ap.add_argument("--device-rays", action="store_true", help="--aov ao and --probe with their hemisphere rays made on the device (DESIGN.md section 16)")
 a = ap.parse_args()
 aovs = [n for n in a.aov.split(",") if n]
 for n in aovs:
@@ -89,7 +92,8 @@ if aovs:
     hits, surf = eng.render_hits(surfaces=True)
     base, ext = os.path.splitext(a.png)
     for n in aovs:
-        img = aov.ao_u8(aov.ambient_occlusion(eng, hits, radius=a.ao_radius)) if n == "ao" else aov.image(n, hits, surf)
+        ao = aov.ambient_occlusion_device if a.device_rays else aov.ambient_occlusion
+        img = aov.ao_u8(ao(eng, hits, radius=a.ao_radius)) if n == "ao" else aov.image(n, hits, surf)
         scene_io.export_png(f"{base}.{n}{ext}", Frame(img.shape[1], img.shape[0], img))
     print(f"first-hit buffers with {eng.last_query_kernel_name()} in {eng.last_query_ms():.3f} ms: {', '.join(aovs)}")
 if a.camera:
@@ -109,6 +113,11 @@ if a.camera:
     print(f"{a.camera} camera with {eng.last_query_kernel_name()} in {eng.last_query_ms():.3f} ms -> {base}.{kind}{ext}")
 if a.probe:
     point, normal = [[float(v) for v in t.split(",")] for t in (a.probe, a.probe_normal)]
-    rgb = bake.irradiance(eng, [point], [normal], max(s.total_samples, 1))[0]
-    print(f"probe at {tuple(point)}, normal {tuple(normal)}, {max(s.total_samples, 1)} rays: mean radiance {rgb[0]:.6g} {rgb[1]:.6g} {rgb[2]:.6g}")
+    rays = max(s.total_samples, 1)
+    if a.device_rays:
+        rays = min(rays, 65536)   # rb_trace_hemisphere's limit for one call
+        rgb = bake.irradiance_device(eng, [point], [normal], rays)[0]
+    else:
+        rgb = bake.irradiance(eng, [point], [normal], rays)[0]
+    print(f"probe at {tuple(point)}, normal {tuple(normal)}, {rays} rays: mean radiance {rgb[0]:.6g} {rgb[1]:.6g} {rgb[2]:.6g}")
 eng.close()
