@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 
+#include "rb_color_plan.hpp"
 #include "rb_internal.hpp"
 #include "rb_rccl.hpp"
 
@@ -38,10 +39,8 @@ struct DevBuf {
         count = n;
     }
     // scratch that is sized per launch: keep an allocation that is large enough and not wastefully so
-    hipError_t reserve(size_t n) {
-        if (ptr && n <= count && count <= 4 * std::max<size_t>(n, 1)) return hipSuccess;
-        return resize(n);
-    }
+    bool serves(size_t n) const { return ptr && n <= count && count <= 4 * std::max<size_t>(n, 1); }
+    hipError_t reserve(size_t n) { return serves(n) ? hipSuccess : resize(n); }
 };
 
 // One frame: the accumulation (vec4<f32> per pixel: sum of radiance, sample count) and the packed RGBA8
@@ -105,8 +104,16 @@ struct rb_engine {
     int device = 0;
     hipStream_t stream = nullptr;
     hipStream_t copy_stream = nullptr;   // read-backs into page-locked caller memory
+    // A launch group in two colour parts (dispatch): odd trace launches go to `trace_stream`, so that a launch fills the wave slots
+    // the one before it vacates, and every k_accumulate to `accum_stream`, underneath the next launch's trace.  Both non-blocking,
+    // both joined into `stream` before a dispatch returns, so nothing else in the library needs to know of them.
+    hipStream_t accum_stream = nullptr;
+    hipStream_t trace_stream = nullptr;
     hipEvent_t ev_begin = nullptr, ev_end = nullptr;
-    std::vector<hipEvent_t> ev_pool;   // per launch chunk: begin, after-trace, end
+    hipEvent_t ev_top = nullptr;                          // the top of a launch group on `stream` (no timing)
+    hipEvent_t ev_traced[2] = {nullptr, nullptr};         // per colour part: its trace launch is over (no timing)
+    hipEvent_t ev_accumulated[2] = {nullptr, nullptr};    // per colour part: its accumulate is over, the part is free (no timing)
+    std::vector<hipEvent_t> ev_pool;   // per launch chunk: trace begin, trace end, accumulate begin, accumulate end
     uint32_t ev_used = 0;
     const char* last_kernel_name = "";
     rb_options opt{};
@@ -144,7 +151,7 @@ struct rb_engine {
     bool spec_valid = false;         // slot[1 - cur] holds passes [spec_first, +spec_n) run ahead on top of slot[cur]
     uint32_t spec_first = 0, spec_n = 0;
     rb::DevBuf<unsigned long long> counters;
-    rb::DevBuf<uint32_t> queue;
+    rb::DevBuf<uint32_t> queue;      // two sets of rb::kQueueWords: two trace launches may be in flight (dispatch)
     rb::SphereAccel sph;
     rb::ChunkAccel chunk;
     rb::OwnAccel own;
@@ -157,7 +164,8 @@ struct rb_engine {
     size_t host_tri_len = 0, host_index_len = 0;   // what the vectors hold, or would hold (0: the engine keeps no copy)
     bool host_tris_stale = false, host_indices_stale = false;
     bool stack_depth_covers = true;    // set with KParams::stack_depth: every walk in use fits its LDS column
-    rb::DevBuf<float> colors;        // RB_KERNEL_STREAM: float4 per (pixel, sample) of one launch chunk
+    rb::DevBuf<float> colors;        // RB_KERNEL_STREAM: float4 per (pixel, sample) of one launch chunk, times the parts of the plan
+    size_t color_part_floats = 0;    // part k of the last reservation starts at colors.ptr + k * color_part_floats
     uint64_t color_budget = 0;       // bytes `colors` may take (0 = ask the device at the next dispatch)
     uint32_t bvh_stack = 0;          // traversal-stack entries the current tree needs
 

@@ -477,8 +477,10 @@ int launch_guide_join(const GuidePlanes& g, size_t n, rb_guide* guides, void* st
 
 // ---- rb_kernels.hip
 // All return hipError_t as int (0 = success); launches are asynchronous on `stream`.
-int launch_render(const KParams& p, uint32_t kernel, bool stats, void* stream, LaunchInfo* info,
-                  void* ev_after_trace = nullptr);
+// launch_render: k_pixel and k_queue whole; of the stream kernels the trace launch alone.  Its colours are summed by
+// launch_accumulate (same KParams), on `stream` or on any stream that is ordered behind the trace launch.
+int launch_render(const KParams& p, uint32_t kernel, bool stats, void* stream, LaunchInfo* info);
+int launch_accumulate(const KParams& p, void* stream);
 int launch_prep_tris(const rb_gpu_triangle* tris, uint32_t tri_count, const uint32_t* indices,
                      uint32_t index_len, PrepTri* out, PrepTriShade* shade, void* stream);
 int launch_prep_materials(void* first_material, uint32_t stride, uint32_t n, void* stream);

@@ -1673,7 +1673,7 @@ Cam host_cam(const rb_uniforms& u) {
     return c;
 }
 
-int launch_render(const KParams& p_, uint32_t kernel, bool stats, void* stream_, LaunchInfo* info, void* ev_after_trace) {
+int launch_render(const KParams& p_, uint32_t kernel, bool stats, void* stream_, LaunchInfo* info) {
     KParams p = p_;
     p.cam = host_cam(p.u);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
@@ -1830,12 +1830,16 @@ int launch_render(const KParams& p_, uint32_t kernel, bool stats, void* stream_,
                 }
                 break;
         }
-        e = hipGetLastError();
-        if (e != hipSuccess) return (int)e;
-        if (ev_after_trace) (void)hipEventRecord(static_cast<hipEvent_t>(ev_after_trace), stream);
-        hipLaunchKernelGGL(k_accumulate, dim3((uint32_t)((tiles + 3u) / 4u)), dim3(256), 0, stream, p);
     }
     if (info) *info = li;
+    return (int)hipGetLastError();
+}
+
+// Phase 2 of a stream-kernel launch: the colours that launch_render's trace kernel stored for `p`, summed in sample order.
+int launch_accumulate(const KParams& p, void* stream_) {
+    const uint64_t tiles = (uint64_t)((p.u.width + 7u) / 8u) * ((p.local_rows + 7u) / 8u);
+    if (tiles == 0 || p.n_passes * p.samples_per_pass == 0) return 0;
+    hipLaunchKernelGGL(k_accumulate, dim3((uint32_t)((tiles + 3u) / 4u)), dim3(256), 0, static_cast<hipStream_t>(stream_), p);
     return (int)hipGetLastError();
 }
 

@@ -143,6 +143,9 @@ int resize_frame(rb_engine* e, uint32_t w, uint32_t h) {
     const StripeGeometry g = stripe_geometry(e->opt, h);
     const uint64_t px = static_cast<uint64_t>(w) * g.padded;
     if (px >= (1ull << 31)) return rb::fail(e, RB_ERR_INVALID_UNIFORMS, "frame of %u x %u pixels is too large", w, h);
+    // the frame's buffers are about to be replaced: launches queued on the engine's stream and, joined into it, on the
+    // accumulate stream may still use them
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
     e->spec_valid = false;
     e->cur = 0;
     e->slot[1].accum.release();   // the run-ahead slot is (re)allocated when the iterator first needs it
@@ -463,16 +466,16 @@ int clear_accum(rb_engine* e) {
 int accumulate_timing(rb_engine* e) {
     float ms = 0.0f;
     if (e->last_launches > 0) {
-        HIP_TRY(e, hipEventSynchronize(e->ev_end));
+        HIP_TRY(e, hipEventSynchronize(e->ev_end));   // behind the join: every event of the group, on either stream, is over
         HIP_TRY(e, hipEventElapsedTime(&ms, e->ev_begin, e->ev_end));
     }
     e->last_dispatch_ms = ms;
     if (e->timing_pending) {
         e->stats.kernel_ms += ms;
-        for (uint32_t i = 0; i + 3 <= e->ev_used; i += 3) {
+        for (uint32_t i = 0; i + 4 <= e->ev_used; i += 4) {
             float t = 0.0f, a = 0.0f;
             HIP_TRY(e, hipEventElapsedTime(&t, e->ev_pool[i], e->ev_pool[i + 1]));
-            HIP_TRY(e, hipEventElapsedTime(&a, e->ev_pool[i + 1], e->ev_pool[i + 2]));
+            HIP_TRY(e, hipEventElapsedTime(&a, e->ev_pool[i + 2], e->ev_pool[i + 3]));
             e->stats.trace_ms += t;
             e->stats.accumulate_ms += a;
         }
@@ -482,8 +485,9 @@ int accumulate_timing(rb_engine* e) {
 }
 
 // Colour-buffer budget of the stream kernels (one float4 per (pixel, sample) of a launch chunk): the caller's
-// figure, else 4 GiB but never more than half of what the device has free right now -- eight launches per C2
-// frame instead of one cost 0.4 %, and a library that sits behind a GUI should not take 34 GB for a 1080p frame.
+// figure, else 4 GiB but never more than half of what the device has free right now -- a library that sits behind a GUI
+// should not take 34 GB for a 1080p frame.  A frame that does not fit is traced in two halves of the budget by turns
+// (rb_color_plan.hpp): sixteen launches per C2 frame, each accumulated underneath the next one's trace.
 uint64_t color_budget_bytes(rb_engine* e) {
     if (e->opt._reserved[1]) return static_cast<uint64_t>(e->opt._reserved[1]) << 20;
     if (e->color_budget == 0) {   // asked once per update: hipMemGetInfo is a driver round trip, and the iterator dispatches per pass
@@ -495,31 +499,124 @@ uint64_t color_budget_bytes(rb_engine* e) {
     return e->color_budget;
 }
 
-// The stream kernels' colour buffer for a group of n_passes passes, and the passes per launch it allows: one float4 per
-// (pixel, sample) of a launch chunk.  Keeps the item count below 2^31 and, unless the caller fixed the chunk, the buffer
-// within the budget; if the device cannot give even that, halves.  Allocates (lazily: the first dispatch, or rb_reserve).
-int reserve_colors(rb_engine* e, uint32_t n_passes, uint32_t* chunk_out) {
-    const uint32_t kernel = rb::kernel_of(e->opt);
-    uint32_t chunk = e->opt.passes_per_launch ? e->opt.passes_per_launch : n_passes;
-    if (kernel == RB_KERNEL_STREAM && n_passes != 0 && e->width != 0 && e->local_rows != 0) {
+// The stream kernels' colour buffer for a group of n_passes passes and the plan it serves (rb_color_plan.hpp): passes per
+// launch and one or two parts of one float4 per (pixel, sample) of a launch.  If the device cannot give that, halves the
+// launch.  Allocates (lazily: the first dispatch, or rb_reserve).  k_queue and k_pixel have no colour buffer: their plan is
+// the caller's passes per launch.
+int reserve_colors(rb_engine* e, uint32_t n_passes, rb::ColorPlan* plan_out) {
+    rb::ColorPlan pl;
+    pl.chunk = e->opt.passes_per_launch ? e->opt.passes_per_launch : n_passes;
+    if (rb::kernel_of(e->opt) == RB_KERNEL_STREAM && n_passes != 0 && e->width != 0 && e->local_rows != 0) {
         const uint64_t tiles = static_cast<uint64_t>((e->width + 7) / 8) * ((e->local_rows + 7) / 8);
         const uint64_t per_pass = tiles * 64ull * e->prh.samples_per_pass;  // items per pass
-        const uint64_t budget_items = color_budget_bytes(e) / 16ull;
-        uint64_t max_chunk = std::min<uint64_t>((1ull << 31) / std::max<uint64_t>(per_pass, 1) , 0xFFFFFFFFull);
-        if (!e->opt.passes_per_launch) max_chunk = std::min(max_chunk, std::max<uint64_t>(budget_items / std::max<uint64_t>(per_pass, 1), 1));
-        if (max_chunk == 0) return rb::fail(e, RB_ERR_INVALID_UNIFORMS, "frame too large for one launch");
-        chunk = static_cast<uint32_t>(std::min<uint64_t>(chunk, max_chunk));
+        pl = rb::plan_colors(per_pass, n_passes, e->opt.passes_per_launch, color_budget_bytes(e) / 16ull);
+        if (pl.chunk == 0) return rb::fail(e, RB_ERR_INVALID_UNIFORMS, "frame too large for one launch");
         for (;;) {
-            const hipError_t st = e->colors.reserve(per_pass * chunk * 4);
+            // a buffer about to be replaced may still be read by the accumulate stream: every group ends joined into the
+            // engine's stream, so that one is the one to wait for
+            if (e->colors.ptr && !e->colors.serves(pl.floats(per_pass))) HIP_TRY(e, hipStreamSynchronize(e->stream));
+            const hipError_t st = e->colors.reserve(pl.floats(per_pass));
             if (st == hipSuccess) break;
             (void)hipGetLastError();  // clear the sticky out-of-memory status
-            if (st != hipErrorOutOfMemory || chunk == 1)
-                return rb::fail(e, RB_ERR_DEVICE, "colour buffer of %llu bytes: %s", static_cast<unsigned long long>(per_pass * chunk * 16ull),
+            if (st != hipErrorOutOfMemory || !rb::halve(pl))
+                return rb::fail(e, RB_ERR_DEVICE, "colour buffer of %llu bytes: %s", static_cast<unsigned long long>(pl.floats(per_pass) * 4ull),
                             hipGetErrorString(st));
-            chunk = (chunk + 1) / 2;
         }
+        e->color_part_floats = static_cast<size_t>(per_pass * pl.chunk * 4ull);
     }
-    *chunk_out = chunk;
+    *plan_out = pl;
+    return RB_OK;
+}
+
+// One launch group: passes [first_pass, first_pass + n_passes) on top of slot `src`, into slot `dst`, cut into launches by
+// `pl`.  k_queue and k_pixel: one kernel per launch on the engine's stream.  The stream kernels: launch i is k_trace(i),
+// which fills a colour part, and k_accumulate(i), which sums that part into the accumulation in sample order.  With one
+// part both follow each other on the engine's stream.  With two parts launch i uses part i % 2, and three streams share the
+// work: k_trace(i) goes to the engine's stream (even i) or to trace_stream (odd i), each with its own queue words, so that
+// the persistent grid of launch i + 1 fills the wave slots the tail of launch i vacates; k_accumulate(i) goes to
+// accum_stream, where it runs underneath k_trace(i + 1) in the slots that one leaves.  What must hold:
+//  1. Part reuse.  k_trace(i + 2) starts after k_accumulate(i) has finished: its stream waits on ev_accumulated[i % 2]
+//     before it is launched.  (It is also behind k_trace(i) on the same stream: the queue words are free.)
+//  2. The accumulation chain.  k_accumulate(i) reads the accumulation k_accumulate(i - 1) wrote (`src` for the first launch,
+//     `dst` after): both are on accum_stream, in order, each behind ev_traced of its own launch.  Before the first launch
+//     accum_stream and trace_stream wait on ev_top, recorded on the engine's stream at the top of the group: the memset of a
+//     clear, uploads, ensure_prepared's kernels, the previous group and whatever else was queued earlier come first.
+//  3. The join.  After the last launch the engine's stream waits on the last accumulate's event, which is behind every
+//     accumulate and hence every trace launch of the group; ev_end and the slot's `done` are recorded behind that wait.  So
+//     everything that follows a dispatch on the engine's stream -- read-backs, rb_sync, the queries, the denoiser's guide
+//     build, the RCCL gather, the next dispatch (also the run-ahead one into the other slot), rb_clear, rb_update -- stays
+//     ordered without knowing that other streams exist.
+//  4. Buffers.  No colour part, accumulation or RGBA buffer is freed or reallocated while another stream may touch it:
+//     reserve_colors, resize_frame and rb_destroy wait for the engine's stream (hence, by 3, for the others) first.  A
+//     launch that fails mid-group leaves all three streams idle before dispatch returns its error.
+//  5. Timing keeps its meaning.  trace_ms: the sum of begin -> end of each trace launch on its stream (consecutive launches
+//     overlap by their tails, so the sum can exceed the group's time); accumulate_ms: the sum of begin -> end of each
+//     accumulate on its stream, the begin recorded behind the wait, so that waiting for the trace is not counted -- an
+//     accumulate that shares the device with the next trace takes as long as that lets it; last_dispatch_ms: ev_begin ->
+//     ev_end across the join.
+//  6. RB_FLAG_STATS.  Only the trace kernels count, with atomics: concurrency changes nothing.
+// Host side, k_accumulate(i) is queued before k_trace(i + 1).
+int queue_group(rb_engine* e, uint32_t first_pass, uint32_t n_passes, int src, int dst, const rb::ColorPlan& pl) {
+    const uint32_t kernel = rb::kernel_of(e->opt);
+    const bool stats = (e->opt.flags & RB_FLAG_STATS) != 0;
+    const bool two_phase = kernel == RB_KERNEL_STREAM;
+    const bool overlap = two_phase && pl.parts == 2;
+    hipStream_t acc = overlap ? e->accum_stream : e->stream;
+    HIP_TRY(e, hipEventRecord(e->ev_begin, e->stream));
+    if (overlap) {   // (2)
+        HIP_TRY(e, hipEventRecord(e->ev_top, e->stream));
+        HIP_TRY(e, hipStreamWaitEvent(acc, e->ev_top, 0));
+        HIP_TRY(e, hipStreamWaitEvent(e->trace_stream, e->ev_top, 0));
+    }
+    uint32_t launches = 0;
+    e->ev_used = 0;
+    for (uint32_t done = 0; done < n_passes;) {
+        const uint32_t n = std::min(pl.chunk, n_passes - done);
+        const uint32_t part = overlap ? launches % 2u : 0u;   // the colour part, the trace stream and the queue words of this launch
+        hipStream_t ts = part ? e->trace_stream : e->stream;
+        // the first chunk resumes `src`; later chunks of the same group continue in `dst`
+        rb::KParams p = make_params(e, first_pass + done, n, done == 0 ? src : dst, dst);
+        if (!e->stack_depth_covers) return rb::fail(e, RB_ERR_DEVICE, "internal: a traversal is deeper than its LDS stack column (%u entries)", p.stack_depth);
+        if (two_phase) p.colors = e->colors.ptr + part * e->color_part_floats;
+        p.queue = e->queue.ptr + part * rb::kQueueWords;
+        rb::LaunchInfo li{};
+        // per-chunk timing events (first 256 chunks of a group; later ones only count in the total)
+        hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+        if (e->ev_used + 4 <= 1024) {
+            while (e->ev_pool.size() < e->ev_used + 4) {
+                hipEvent_t x;
+                HIP_TRY(e, hipEventCreate(&x));
+                e->ev_pool.push_back(x);
+            }
+            for (int i = 0; i < 4; ++i) ev[i] = e->ev_pool[e->ev_used + i];
+            e->ev_used += 4;
+        }
+        if (overlap && launches >= 2) HIP_TRY(e, hipStreamWaitEvent(ts, e->ev_accumulated[part], 0));   // (1)
+        if (ev[0]) HIP_TRY(e, hipEventRecord(ev[0], ts));
+        int rc = rb::launch_render(p, kernel, stats, ts, &li);
+        if (rc) return rb::fail(e, RB_ERR_DEVICE, "render kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(rc)));
+        if (ev[1]) HIP_TRY(e, hipEventRecord(ev[1], ts));
+        if (overlap) {
+            HIP_TRY(e, hipEventRecord(e->ev_traced[part], ts));
+            HIP_TRY(e, hipStreamWaitEvent(acc, e->ev_traced[part], 0));
+        }
+        if (ev[2]) HIP_TRY(e, hipEventRecord(ev[2], acc));
+        if (two_phase) {
+            rc = rb::launch_accumulate(p, acc);
+            if (rc) return rb::fail(e, RB_ERR_DEVICE, "accumulate kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(rc)));
+        }
+        if (ev[3]) HIP_TRY(e, hipEventRecord(ev[3], acc));
+        if (overlap) HIP_TRY(e, hipEventRecord(e->ev_accumulated[part], acc));
+        if (li.kernel_name) e->last_kernel_name = li.kernel_name;
+        done += n;
+        launches++;
+    }
+    if (overlap) HIP_TRY(e, hipStreamWaitEvent(e->stream, e->ev_accumulated[(launches - 1u) % 2u], 0));   // (3)
+    HIP_TRY(e, hipEventRecord(e->ev_end, e->stream));
+    HIP_TRY(e, hipEventRecord(e->slot[dst].done, e->stream));
+    e->last_launches = launches;
+    e->timing_pending = true;
+    e->stats.launches += launches;
     return RB_OK;
 }
 
@@ -537,48 +634,18 @@ int dispatch(rb_engine* e, uint32_t first_pass, uint32_t n_passes, int src, int 
         rc = accumulate_timing(e);
         if (rc) return rc;
     }
-    const uint32_t kernel = rb::kernel_of(e->opt);
-    const bool stats = (e->opt.flags & RB_FLAG_STATS) != 0;
-    uint32_t chunk = 0;
-    rc = reserve_colors(e, n_passes, &chunk);
+    rb::ColorPlan pl;
+    rc = reserve_colors(e, n_passes, &pl);
     if (rc) return rc;
-    HIP_TRY(e, hipEventRecord(e->ev_begin, e->stream));
-    uint32_t launches = 0;
-    e->ev_used = 0;
-    for (uint32_t done = 0; done < n_passes;) {
-        const uint32_t n = std::min(chunk, n_passes - done);
-        // the first chunk resumes `src`; later chunks of the same group continue in `dst`
-        rb::KParams p = make_params(e, first_pass + done, n, done == 0 ? src : dst, dst);
-        if (!e->stack_depth_covers) return rb::fail(e, RB_ERR_DEVICE, "internal: a traversal is deeper than its LDS stack column (%u entries)", p.stack_depth);
-        rb::LaunchInfo li{};
-        // per-chunk timing events (first 256 chunks of a group; later ones only count in the total)
-        hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-        if (e->ev_used + 3 <= 768) {
-            while (e->ev_pool.size() < e->ev_used + 3) {
-                hipEvent_t x;
-                HIP_TRY(e, hipEventCreate(&x));
-                e->ev_pool.push_back(x);
-            }
-            for (int i = 0; i < 3; ++i) ev[i] = e->ev_pool[e->ev_used + i];
-            e->ev_used += 3;
-            HIP_TRY(e, hipEventRecord(ev[0], e->stream));
-        }
-        rc = rb::launch_render(p, kernel, stats, e->stream, &li, ev[1]);
-        if (rc) return rb::fail(e, RB_ERR_DEVICE, "render kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(rc)));
-        if (ev[2]) {
-            if (kernel != RB_KERNEL_STREAM) HIP_TRY(e, hipEventRecord(ev[1], e->stream));
-            HIP_TRY(e, hipEventRecord(ev[2], e->stream));
-        }
-        if (li.kernel_name) e->last_kernel_name = li.kernel_name;
-        done += n;
-        launches++;
+    rc = queue_group(e, first_pass, n_passes, src, dst, pl);
+    if (rc) {   // (4) a group cut short: nothing of it is left running, on either stream, when the caller sees the error
+        (void)hipStreamSynchronize(e->accum_stream);
+        (void)hipStreamSynchronize(e->trace_stream);
+        (void)hipStreamSynchronize(e->stream);
+        e->last_launches = 0;
+        e->timing_pending = false;
     }
-    HIP_TRY(e, hipEventRecord(e->ev_end, e->stream));
-    HIP_TRY(e, hipEventRecord(e->slot[dst].done, e->stream));
-    e->last_launches = launches;
-    e->timing_pending = true;
-    e->stats.launches += launches;
-    return RB_OK;
+    return rc;
 }
 
 // Copies the committed frame's RGBA8 rows (local stripe order when sharded) to caller memory: the host waits
@@ -805,12 +872,16 @@ rb_engine* create_single(const rb_config* cfg, const rb_options& opt) {
     hipError_t st;
     if ((st = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", st);
     if ((st = hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", st);
+    if ((st = hipStreamCreateWithFlags(&e->accum_stream, hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", st);
+    if ((st = hipStreamCreateWithFlags(&e->trace_stream, hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", st);
+    for (hipEvent_t* x : {&e->ev_top, &e->ev_traced[0], &e->ev_traced[1], &e->ev_accumulated[0], &e->ev_accumulated[1]})
+        if ((st = hipEventCreateWithFlags(x, hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", st);
     if ((st = hipEventCreate(&e->ev_begin)) != hipSuccess) return bail("hipEventCreate", st);
     if ((st = hipEventCreate(&e->ev_end)) != hipSuccess) return bail("hipEventCreate", st);
     for (rb::FrameSlot& s : e->slot)
         if ((st = hipEventCreateWithFlags(&s.done, hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", st);
     if ((st = e->counters.resize(rb::C_COUNT)) != hipSuccess) return bail("hipMalloc(counters)", st);
-    if ((st = e->queue.resize(rb::kQueueWords)) != hipSuccess) return bail("hipMalloc(queue)", st);
+    if ((st = e->queue.resize(2 * rb::kQueueWords)) != hipSuccess) return bail("hipMalloc(queue)", st);
     if ((st = hipMemsetAsync(e->counters.ptr, 0, sizeof(unsigned long long) * rb::C_COUNT, e->stream)) != hipSuccess)
         return bail("hipMemset(counters)", st);
     // sRGB -> linear table for sample_texture's pow(c, 2.2) (shader.wgsl:185-190)
@@ -999,9 +1070,18 @@ void rb_destroy(rb_engine* e) {
         return;
     }
     rb::set_device(e);
-    // every launch, copy and event record of this engine was queued on its one stream: when that has
-    // drained nothing on the device refers to the buffers, events or communicator any more
+    // every launch, copy and event record of this engine was queued on its stream or, joined into it before the
+    // dispatch returned, on the accumulate stream: when they have drained nothing on the device refers to the buffers,
+    // events or communicator any more
     if (e->stream) (void)hipStreamSynchronize(e->stream);
+    if (e->accum_stream) {
+        (void)hipStreamSynchronize(e->accum_stream);
+        (void)hipStreamDestroy(e->accum_stream);
+    }
+    if (e->trace_stream) {
+        (void)hipStreamSynchronize(e->trace_stream);
+        (void)hipStreamDestroy(e->trace_stream);
+    }
     if (e->copy_stream) {
         (void)hipStreamSynchronize(e->copy_stream);
         (void)hipStreamDestroy(e->copy_stream);
@@ -1009,6 +1089,8 @@ void rb_destroy(rb_engine* e) {
     rb::gather_destroy(e->net);
     if (e->ev_begin) (void)hipEventDestroy(e->ev_begin);
     if (e->ev_end) (void)hipEventDestroy(e->ev_end);
+    for (hipEvent_t x : {e->ev_top, e->ev_traced[0], e->ev_traced[1], e->ev_accumulated[0], e->ev_accumulated[1]})
+        if (x) (void)hipEventDestroy(x);
     for (rb::FrameSlot& s : e->slot)
         if (s.done) (void)hipEventDestroy(s.done);
     for (hipEvent_t x : e->ev_pool) (void)hipEventDestroy(x);
@@ -1161,8 +1243,8 @@ int rb_reserve(rb_engine* e, uint32_t n_passes) {
         rb::set_device(p);
         int rc = require_ready(p);
         if (!rc) rc = ensure_prepared(p);
-        uint32_t chunk = 0;
-        if (!rc) rc = reserve_colors(p, n_passes, &chunk);
+        rb::ColorPlan pl;
+        if (!rc) rc = reserve_colors(p, n_passes, &pl);
         if (!rc && hipStreamSynchronize(p->stream) != hipSuccess) rc = rb::fail(p, RB_ERR_DEVICE, "synchronise failed");
         return rc;
     };
