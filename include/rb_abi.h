@@ -746,6 +746,72 @@ int rb_openness_hemisphere(rb_engine* e, const rb_surfel* surfels, const uint32_
 int rb_openness_hemisphere_device(rb_engine* e, const rb_surfel* d_surfels, const uint32_t* d_seeds, size_t n,
                                   const rb_hemi_params* params, uint32_t first_sample, uint32_t samples, rb_openness* d_out);
 
+/* ---- Lightmap texels made on the device (the normative definition; no reference counterpart).  The
+ * triangles of a mesh are rasterised in uv space into an atlas of width x height texels, texel (x, y) = index y * width + x,
+ * row 0 on TOP (sample_texture flips v, shader.wgsl:178-179); every owned texel becomes a surfel, the surfels are traced by
+ * rb_trace_hemisphere's kernels and the sums resolved into a map in sample_texture's own layout.  Every step is one IEEE
+ * binary32 operation in the order written, no contraction, / correctly rounded: the numpy model renderbaby_amd/lightmap.py
+ * equals the device bit for bit.  For triangle t of bvh_triangles with uv indices i0, i1, i2:
+ *   uv_k  = (uv_at(2 i_k), uv_at(2 i_k + 1)), u32 index arithmetic, out of range reads 0.0f (shader.wgsl:357-359);
+ *   A, B, C = (u_k * float(width), (1.0f - v_k) * float(height));  P = (float(x) + 0.5f, float(y) + 0.5f);
+ *   edge(S, T) at P: (a, b) = (S, T) if S.x < T.x || (S.x == T.x && S.y <= T.y), else (T, S);
+ *            E = (b.x - a.x) * (P.y - a.y) - (b.y - a.y) * (P.x - a.x);  the value is E for ends in order, else -E;
+ *   area = edge(A, B) at C;  w0 = edge(B, C), w1 = edge(C, A), w2 = edge(A, B) at P;
+ *   box   x in [floor(min(A.x, B.x, C.x)), floor(max(A.x, B.x, C.x))], y likewise, cut to the atlas;
+ *   COVER t covers nothing if the walks skip it (t >= bvh_triangle_count), its mesh_index is not params.mesh (unless that is
+ *         RB_LIGHTMAP_ALL_MESHES), a coordinate of A, B, C is non-finite, or area is zero or non-finite; else it covers the
+ *         texels of its box with w0, w1, w2 all >= 0 (area > 0) or all <= 0 (area < 0): zero counts as inside;
+ *   OWNER the lowest covering triangle index, or RB_LIGHTMAP_NO_OWNER;
+ *   SURFEL of an owned texel: u = w1 / area; v = w2 / area; pos = (v0 + u e1) + v e2, component-wise, e1 = v1 - v0,
+ *         e2 = v2 - v0; normal = normalize(cross(e1, e2)) as the walks report it, every component negated with
+ *         RB_LIGHTMAP_FLIP; pad words 0.  An unowned texel's surfel is all zero bits: rb_trace_hemisphere's invalid surfel;
+ *   RESOLVE sums[n] -> rgba[n]: pass 0: sums.w > 0 ? {r / w, g / w, b / w, 1.0f} : {0, 0, 0, 0}; then `dilate` passes, each
+ *         reading the pass before only: a texel whose fourth component is 0 sums, from +0.0f and in the order (-1,-1) (0,-1)
+ *         (1,-1) (-1,0) (1,0) (-1,1) (0,1) (1,1) of (dx, dy), its neighbours inside the atlas with a non-zero fourth
+ *         component; c > 0 of them make it {sum r / float(c), sum g / float(c), sum b / float(c), 2.0f}.
+ *         Fourth component: 0 = empty, 1 = baked, 2 = filled.
+ * The result depends on neither the launch shape nor the form of the call. */
+enum { RB_LIGHTMAP_ALL_MESHES = 0xFFFFFFFFu, RB_LIGHTMAP_NO_OWNER = 0xFFFFFFFFu, RB_LIGHTMAP_FLIP = 1u };
+enum { RB_LIGHTMAP_MAX_SIDE = 16384u, RB_LIGHTMAP_MAX_DILATE = 64u };
+typedef struct rb_lightmap_params {   /* 32 B */
+    uint32_t width, height;   /* 1 .. 16384 each; width * height <= 2^31 - 64 */
+    uint32_t mesh;            /* mesh index or RB_LIGHTMAP_ALL_MESHES */
+    uint32_t flags;           /* RB_LIGHTMAP_FLIP or 0 */
+    float    offset;          /* handed to rb_hemi_params.offset: >= 0, finite */
+    uint32_t dilate;          /* 0 .. 64 passes */
+    uint32_t _reserved[2];    /* must be 0 */
+} rb_lightmap_params;
+/* The generator alone, no engine, on `device` (-1 = current): host arrays.  The triangles are prepared by the device code of
+ * the engine's upload, so the normals are the engine's; every triangle counts as valid.  surfels_out[width * height],
+ * owners_out[width * height] (may be NULL).  RB_ERR_NULL_ARGUMENT: NULL params or surfels_out, NULL tris with n_tris > 0, NULL
+ * uvs with n_uv_floats > 0.  RB_ERR_INVALID_OPTIONS, before any device is touched: width or height 0 or above 16384; width *
+ * height above 2^31 - 64; dilate above 64; unknown flags; non-zero _reserved; offset negative or non-finite; n_tris above
+ * 2^31 - 64 or n_uv_floats above 2^32 - 1.  n_tris == 0 is RB_OK with an all-empty map, and no device is touched. */
+int rb_lightmap_surfels(int32_t device, const rb_gpu_triangle* tris, size_t n_tris, const float* uvs, size_t n_uv_floats,
+                        const rb_lightmap_params* params, rb_surfel* surfels_out, uint32_t* owners_out);
+/* From the engine's uploaded scene into device memory of the engine's device (d_surfels: 16-byte aligned, width * height
+ * records; d_owners: may be NULL), validated as rb_trace_rays_device validates its buffers.  Queued on the engine's stream; the
+ * call waits once, for the 8 bytes that size the cover launches, and returns without waiting for the rest: rb_sync is the wait.
+ * The result is what rb_trace_hemisphere_device and rb_openness_hemisphere_device take.  The side effects are a query's. */
+int rb_lightmap_surfels_device(rb_engine* e, const rb_lightmap_params* params, rb_surfel* d_surfels, uint32_t* d_owners);
+/* The resolve alone, no engine, on `device` (-1 = current): sums[width * height] -> rgba_out[width * height * 4], host arrays.
+ * Refusals as above for width, height and dilate; NULL sums or rgba_out: RB_ERR_NULL_ARGUMENT. */
+int rb_lightmap_resolve(int32_t device, uint32_t width, uint32_t height, const rb_radiance* sums, uint32_t dilate, float* rgba_out);
+/* The bake: surfels (in the engine's query scratch), rb_trace_hemisphere's pieces over them with seeds = NULL -- the stream id
+ * is the texel index --, resolve.  rgba_out[width * height * 4] and sums_out[width * height] (the raw sums, for a caller who
+ * accumulates over calls with first_sample and resolves later) in host memory; either may be NULL, not both.  The limits on
+ * width * height * samples are rb_trace_hemisphere's and refuse the same way.  An engine without triangles, or an atlas no
+ * triangle covers, is RB_OK with an all-empty map.  Sharded engines and multi-device handles as rb_trace_rays.
+ * rb_last_query_ms reports all three stages, rb_last_lightmap_ms the first and the last. */
+int rb_bake_lightmap(rb_engine* e, const rb_lightmap_params* params, uint32_t first_sample, uint32_t samples, float* rgba_out,
+                     rb_radiance* sums_out);
+/* The same into device memory of the engine's device (16-byte aligned), as rb_lightmap_surfels_device. */
+int rb_bake_lightmap_device(rb_engine* e, const rb_lightmap_params* params, uint32_t first_sample, uint32_t samples,
+                            float* d_rgba_out, rb_radiance* d_sums_out);
+/* Kernel ms of the surfel stage (prepare, count, scan, cover, surfels) and of the resolve (with its dilate passes) in the most
+ * recent lightmap call; a stage the call did not run reports 0.  Either pointer may be NULL. */
+int rb_last_lightmap_ms(rb_engine* e, float* surfels_ms, float* resolve_ms);
+
 /* ---- Edge-avoiding denoiser over the first-hit buffers (no reference counterpart).  An a-trous wavelet
  * filter (Dammertz et al. 2010) on the albedo-demodulated mean radiance, guided by the first hit of every pixel-centre ray.
  * Section 13 is the normative definition: every step one IEEE binary32 operation in a fixed order, so that the device's result
@@ -858,6 +924,8 @@ static_assert(sizeof(rb_surfel) == 32, "rb_surfel is 32 B");
 static_assert(offsetof(rb_surfel, normal) == 16, "normal @16");
 static_assert(sizeof(rb_hemi_params) == 32, "rb_hemi_params is 32 B");
 static_assert(sizeof(rb_openness) == 8, "rb_openness is 8 B");
+static_assert(sizeof(rb_lightmap_params) == 32, "rb_lightmap_params is 32 B");
+static_assert(offsetof(rb_lightmap_params, offset) == 16, "offset @16");
 static_assert(sizeof(rb_guide) == 48, "rb_guide is 48 B");
 static_assert(sizeof(rb_denoise_params) == 32, "rb_denoise_params is 32 B");
 static_assert(offsetof(rb_guide, t) == 12, "t @12");
@@ -885,6 +953,7 @@ _Static_assert(sizeof(rb_camera_ex) == 96, "rb_camera_ex is 96 B");
 _Static_assert(sizeof(rb_surfel) == 32, "rb_surfel is 32 B");
 _Static_assert(sizeof(rb_hemi_params) == 32, "rb_hemi_params is 32 B");
 _Static_assert(sizeof(rb_openness) == 8, "rb_openness is 8 B");
+_Static_assert(sizeof(rb_lightmap_params) == 32, "rb_lightmap_params is 32 B");
 _Static_assert(sizeof(rb_guide) == 48, "rb_guide is 48 B");
 _Static_assert(sizeof(rb_denoise_params) == 32, "rb_denoise_params is 32 B");
 #endif

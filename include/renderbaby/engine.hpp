@@ -270,6 +270,33 @@ class Engine final : public Renderer {
                          uint32_t samples, uint32_t first_sample = 0) {
         check(h_->e, rb_openness_hemisphere_device(h_->e, d_surfels, d_seeds, n, &p, first_sample, samples, d_out));
     }
+    // ---- lightmap texels made on the device (extension; rb_abi.h): the surfel of every texel of an atlas
+    // over the scene's uvs, and the bake of the whole map in one call (rgba in sample_texture's layout, row 0 on top)
+    static rb_lightmap_params lightmap_params(uint32_t width, uint32_t height, uint32_t mesh = RB_LIGHTMAP_ALL_MESHES, bool flip = false,
+                                              float offset = 1e-3f, uint32_t dilate = 2) {
+        rb_lightmap_params p{};
+        p.width = width;
+        p.height = height;
+        p.mesh = mesh;
+        p.flags = flip ? RB_LIGHTMAP_FLIP : 0u;
+        p.offset = offset;
+        p.dilate = dilate;
+        return p;
+    }
+    std::vector<float> bake_lightmap(const rb_lightmap_params& p, uint32_t samples, uint32_t first_sample = 0, std::vector<rb_radiance>* sums = nullptr) {
+        const size_t n = static_cast<size_t>(p.width) * p.height;
+        std::vector<float> rgba(n * 4);
+        if (sums) sums->resize(n);
+        check(h_->e, rb_bake_lightmap(h_->e, &p, first_sample, samples, rgba.data(), sums ? sums->data() : nullptr));
+        return rgba;
+    }
+    // the same on the engine's device memory: queued on the engine's stream -- sync() waits
+    void lightmap_surfels_device(const rb_lightmap_params& p, rb_surfel* d_surfels, uint32_t* d_owners = nullptr) {
+        check(h_->e, rb_lightmap_surfels_device(h_->e, &p, d_surfels, d_owners));
+    }
+    void bake_lightmap_device(const rb_lightmap_params& p, float* d_rgba, rb_radiance* d_sums, uint32_t samples, uint32_t first_sample = 0) {
+        check(h_->e, rb_bake_lightmap_device(h_->e, &p, first_sample, samples, d_rgba, d_sums));
+    }
     void sync() { check(h_->e, rb_sync(h_->e)); }
     // ---- the denoiser (rb_abi.h): the a-trous filter over the committed accumulation
     static rb_denoise_params denoise_defaults() {

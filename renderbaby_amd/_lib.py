@@ -101,6 +101,12 @@ def load():
         "rb_trace_hemisphere_device": (i32, [vp, vp, vp, sz, vp, u32, u32, vp]),
         "rb_openness_hemisphere": (i32, [vp, vp, vp, sz, vp, u32, u32, vp]),
         "rb_openness_hemisphere_device": (i32, [vp, vp, vp, sz, vp, u32, u32, vp]),
+        "rb_lightmap_surfels": (i32, [i32, vp, sz, vp, sz, vp, vp, vp]),
+        "rb_lightmap_surfels_device": (i32, [vp, vp, vp, vp]),
+        "rb_lightmap_resolve": (i32, [i32, u32, u32, vp, u32, vp]),
+        "rb_bake_lightmap": (i32, [vp, vp, u32, u32, vp, vp]),
+        "rb_bake_lightmap_device": (i32, [vp, vp, u32, u32, vp, vp]),
+        "rb_last_lightmap_ms": (i32, [vp, P(C.c_float), P(C.c_float)]),
         "rb_last_query_kernel_name": (C.c_char_p, [vp]),
         "rb_last_query_ms": (i32, [vp, P(C.c_float)]),
         "rb_denoise_default_params": (i32, [vp]),
@@ -145,4 +151,5 @@ EXPORTS = ["rb_create", "rb_create_ex", "rb_create_multi", "rb_comm_available", 
            "rb_last_dispatch_ms", "rb_bvh_build", "rb_bvh_build_canonical", "rb_bvh_build_device", "rb_engine_tree", "rb_tree_builder", "rb_debug_chunk_tree", "rb_measure_l1_gather", "rb_debug_math", "rb_debug_walk_profile", "rb_debug_rcp_exhaustive", "rb_debug_rnd_pm1_exhaustive", "rb_debug_div_exhaustive", "rb_last_kernel_name", "rb_cast_rays", "rb_render_hits", "rb_pick", "rb_occluded", "rb_occluded_device", "rb_cast_rays_device", "rb_trace_rays", "rb_trace_rays_device", "rb_last_query_kernel_name", "rb_last_query_ms",
            "rb_camera_rays", "rb_trace_camera", "rb_trace_camera_device", "rb_last_camera_rays_ms",
            "rb_hemisphere_rays", "rb_trace_hemisphere", "rb_trace_hemisphere_device", "rb_openness_hemisphere", "rb_openness_hemisphere_device",
+           "rb_lightmap_surfels", "rb_lightmap_surfels_device", "rb_lightmap_resolve", "rb_bake_lightmap", "rb_bake_lightmap_device", "rb_last_lightmap_ms",
            "rb_denoise_default_params", "rb_denoise_buffers", "rb_denoise", "rb_denoise_device", "rb_denoise_guides", "rb_last_denoise_ms", "rb_fast_bvh_builder", "rb_sphere_tree_builder", "rb_chunk_tree_builder", "rb_debug_engine_chunk_tree", "rb_version", "rb_device_name"]

@@ -66,6 +66,11 @@ SURFEL = np.dtype([("pos", f4, (3,)), ("_pad0", f4), ("normal", f4, (3,)), ("_pa
 HEMI_PARAMS = np.dtype([("offset", f4), ("radius", f4), ("mask", u4), ("flags", u4), ("_reserved", u4, (4,))])
 OPENNESS = np.dtype([("open", u4), ("valid", u4)])
 HEMI_PIECE_ITEMS = 1 << 23
+# lightmap texels made on the device (rb_lightmap_surfels / rb_lightmap_resolve / rb_bake_lightmap)
+LIGHTMAP_PARAMS = np.dtype([("width", u4), ("height", u4), ("mesh", u4), ("flags", u4), ("offset", f4), ("dilate", u4),
+                            ("_reserved", u4, (2,))])
+LIGHTMAP_ALL_MESHES, LIGHTMAP_NO_OWNER, LIGHTMAP_FLIP = 0xFFFFFFFF, 0xFFFFFFFF, 1
+LIGHTMAP_MAX_SIDE, LIGHTMAP_MAX_DILATE = 16384, 64
 # any-hit occlusion (rb_occluded): result bytes and stage masks
 OCCL_VISIBLE, OCCL_OCCLUDED, OCCL_INVALID = 0, 1, 255
 MASK_GROUND, MASK_TRIANGLES, MASK_SPHERES, MASK_LIGHTS, MASK_ALL = 1, 2, 4, 8, 15
@@ -79,7 +84,8 @@ SIZES = {"camera": (CAMERA, 48), "uniforms": (UNIFORMS, 144), "material": (MATER
          "bvh_node": (BVH_NODE, 48), "gpu_triangle": (GPU_TRIANGLE, 64),
          "ray": (RAY, 32), "hit": (HIT, 48), "surface": (SURFACE, 48),
          "guide": (GUIDE, 48), "denoise_params": (DENOISE_PARAMS, 32), "camera_ex": (CAMERA_EX, 96),
-         "surfel": (SURFEL, 32), "hemi_params": (HEMI_PARAMS, 32), "openness": (OPENNESS, 8)}
+         "surfel": (SURFEL, 32), "hemi_params": (HEMI_PARAMS, 32), "openness": (OPENNESS, 8),
+         "lightmap_params": (LIGHTMAP_PARAMS, 32)}
 for _n, (_dt, _sz) in SIZES.items():
     assert _dt.itemsize == _sz, (_n, _dt.itemsize, _sz)
 

@@ -204,6 +204,23 @@ def ambient_occlusion_device(engine, hits, samples=16, radius=1.0, first_sample=
     return ao
 
 
+def ambient_occlusion_map(engine, width, height, samples, radius, mesh=None, flip=False, first_sample=0, offset=1e-3):
+    """The ambient occlusion of a mesh as a map over its uvs: the surfel of every texel of a ``width`` x
+    ``height`` atlas (Engine.lightmap_surfels), then the openness of every surfel (Engine.openness) -- torch tensors on the
+    engine's device from the first call to the second, so no surfel exists on the host.  float32 (height, width), row 0 on top
+    as sample_texture reads a texture: open / valid; NaN where no triangle owns the texel or no sample was valid."""
+    import torch
+    n = int(width) * int(height)
+    dev = torch.device("cuda", engine.query_device)
+    surf = torch.empty((n, 8), dtype=torch.float32, device=dev)
+    engine.lightmap_surfels(width, height, mesh=mesh, flip=flip, out=(surf, None))
+    res = engine.openness(surf[:, 0:3].contiguous(), surf[:, 4:7].contiguous(), samples, radius, first_sample=first_sample, offset=offset)
+    res = res.cpu().numpy().astype(np.float32)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        ao = np.where(res[:, 1] > 0, res[:, 0] / res[:, 1], np.float32(np.nan)).astype(np.float32)
+    return ao.reshape(int(height), int(width))
+
+
 def ao_u8(ao):
     """an AO image as RGBA8 grey (rounded to nearest)"""
     g = np.rint(np.clip(ao, 0, 1) * 255.0).astype(np.uint8)

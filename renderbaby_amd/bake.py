@@ -3,6 +3,8 @@
 
 ``irradiance``   mean radiance over cosine-weighted directions about a normal: lightmap texels, vertices, probes
 ``irradiance_device``  the same with the rays made and the samples summed on the device (Engine.trace_hemisphere; section 16)
+``lightmap``     a mesh's lightmap in one call: surfels from its uvs, traced and resolved on the device (Engine.bake_lightmap; section 17)
+``lightmap_texture``  a baked map as an RGBA8 texture that sample_texture decodes back
 ``camera_rays``  the rays of cameras the reference's Camera struct cannot express: equirect, ortho, thin_lens
 ``render_rays``  rays -> tone-mapped RGBA8 pixels, the reference's colour mapping applied to sum / weight
 ``render_camera``  an abi.CAMERA_EX camera (camera.make) -> RGBA8 pixels, every sample's ray made on the device with jitter and
@@ -65,6 +67,26 @@ def irradiance_device(engine, points, normals, samples, first_sample=0, seeds=No
             return np.where(w > 0, rad["sum"].astype(f32) / w, f32(0)).astype(f32)
     w = rad[:, 3:4]
     return (rad[:, 0:3] / w.clamp(min=1.0)) * (w > 0)
+
+
+def lightmap(engine, width, height, samples, first_sample=0, mesh=None, flip=False, offset=1e-3, dilate=2):
+    """The lightmap of the engine's scene over its uvs (Engine.bake_lightmap, rb_bake_lightmap): float32
+    (height, width, 4), row 0 on top as sample_texture reads a texture; rgb = the mean radiance over the cosine-weighted
+    hemisphere of every texel's surfel (the irradiance over pi), fourth component 0 = empty, 1 = baked, 2 = filled from its
+    neighbours.  No surfel and no ray exists on the host."""
+    return engine.bake_lightmap(width, height, samples, first_sample=first_sample, mesh=mesh, flip=flip, offset=offset, dilate=dilate)
+
+
+def lightmap_texture(rgba):
+    """A baked map (height, width, 4) as an RGBA8 texture, uint32 (height, width), that sample_texture (shader.wgsl:181-190)
+    decodes back: byte = round(255 c^(1 / 2.2)) of c clipped to 0 .. 1, R in the low byte; alpha 255 where the texel is baked
+    or filled, 0 where it is empty.  Host numpy, not bit-pinned."""
+    m = np.asarray(rgba, f32)
+    if m.ndim != 3 or m.shape[2] != 4:
+        raise ValueError("rgba: a (height, width, 4) map is needed")
+    c = np.rint(255.0 * np.clip(np.nan_to_num(m[..., :3].astype(np.float64)), 0.0, 1.0) ** (1.0 / 2.2)).astype(np.uint32)
+    a = np.where(m[..., 3] != 0, np.uint32(255), np.uint32(0)).astype(np.uint32)
+    return (c[..., 0] | (c[..., 1] << np.uint32(8)) | (c[..., 2] << np.uint32(16)) | (a << np.uint32(24))).astype(np.uint32)
 
 
 def camera_rays(kind, width, height, pos, dir=(0.0, 0.0, -1.0), up=(0.0, 1.0, 0.0), ortho_width=2.0, fov_deg=60.0,

@@ -184,6 +184,17 @@ struct rb_engine {
     rb::DevBuf<rb_radiance> rad_out;
     rb::DevBuf<rb_surfel> hemi_surfels;   // rb_trace_hemisphere / rb_openness_hemisphere: the piece's surfels and its counts
     rb::DevBuf<rb_openness> hemi_open;
+    // lightmap texels made on the device (rb_lightmap_surfels_device / rb_bake_lightmap*): the triangles
+    // prepared in triangle order, the cover pass's scratch, and what a bake keeps between its stages
+    rb::DevBuf<rb::PrepTri> lm_ptris;
+    rb::DevBuf<rb::PrepTriShade> lm_pshade;
+    rb::DevBuf<uint32_t> lm_iota, lm_owners;
+    rb::DevBuf<unsigned char> lm_work;
+    rb::DevBuf<rb_surfel> lm_surfels;
+    rb::DevBuf<rb_radiance> lm_sums;
+    rb::DevBuf<float> lm_rgba[2];
+    hipEvent_t ev_lm[4] = {nullptr, nullptr, nullptr, nullptr};   // surfel stage begin / end, resolve begin / end
+    bool lm_timed[2] = {false, false};   // the most recent lightmap call recorded the pair (rb_last_lightmap_ms)
     hipEvent_t ev_q[2] = {nullptr, nullptr};
     std::vector<hipEvent_t> ev_cam;  // rb_trace_camera*, rb_*_hemisphere*: a pair around every piece's generator (rb_last_camera_rays_ms)
     size_t cam_pieces = 0;           // pairs the most recent call recorded

@@ -446,6 +446,26 @@ struct HemiGenArgs {
 };
 int launch_hemisphere_rays(const HemiGenArgs& g, void* stream);
 int launch_hemisphere_count(const uint8_t* occl, uint32_t n, uint32_t samples, rb_openness* out, void* stream);
+// ---- rb_lightmap.hip: lightmap texels made on the device.  The triangles are PrepTri / PrepTriShade
+// records in TRIANGLE order (launch_prep_tris over the identity order, launch_lightmap_iota), so that an owner is an index into
+// bvh_triangles whatever bvh_indices hold.
+struct LmArgs {
+    const PrepTri* ptris;        // n_tris records, record t = triangle t
+    const PrepTriShade* pshade;
+    const float* uvs;
+    uint32_t n_tris, n_uvs;
+    uint32_t width, height, mesh, flags;
+};
+constexpr uint32_t kLmTile = 8;                    // a cover unit is one (triangle, 8 x 8-texel tile of the atlas inside its box)
+constexpr uint64_t kLmPieceUnits = 1ull << 20;     // units per cover launch: 2^18 blocks of four waves, whatever the total
+int launch_lightmap_iota(uint32_t* out, uint32_t n, void* stream);   // out[i] = i
+size_t lightmap_work_bytes(uint32_t n_tris);       // the scratch lightmap_surfels needs at `work` (256-byte aligned)
+// owners[width * height] and surfels[width * height] of the atlas, queued on `stream`; waits once, for the unit total that sizes
+// the cover launches of at most `piece_units` units (0: kLmPieceUnits).  Returns a hipError_t.
+int lightmap_surfels(const LmArgs& g, rb_surfel* surfels, uint32_t* owners, void* work, uint64_t piece_units, void* stream);
+// sums[width * height] -> rgba: pass 0 and `dilate` passes that ping-pong between `out` and `tmp` (width * height float4 each;
+// tmp may be nullptr when dilate is 0) and end in `out`
+int launch_lightmap_resolve(const rb_radiance* sums, uint32_t width, uint32_t height, uint32_t dilate, float* out, float* tmp, void* stream);
 Cam host_cam(const rb_uniforms& u);   // rb_kernels.hip: the camera of a launch, shader.wgsl:690,702-708
 
 // ---- rb_denoise.hip: the edge-avoiding a-trous filter.  Everything is in the orientation of the delivered

@@ -1,10 +1,13 @@
 // rb_queries.cpp -- what an engine answers besides frames: closest-hit queries (rb_cast_rays / rb_render_hits / rb_pick), any-hit
-// occlusion, path-traced radiance along given rays, camera and hemisphere rays made on the device and the denoiser over the
-// first-hit buffers, with their device forms, their getters and their C entry points (rb_abi.h; DESIGN.md sections 11-16).  Every family shares
+// occlusion, path-traced radiance along given rays, camera and hemisphere rays and lightmap texels made on the device and the
+// denoiser over the first-hit buffers, with their device forms, their getters and their C entry points (rb_abi.h; DESIGN.md
+// sections 11-17).  Every family shares
 // one prologue (query_prologue), one timed launch (timed_launch) and one runner per form: run_pieces for the host forms,
 // device_query_locked for the device forms.  The engine's state is rb_engine.hpp's; the launchers are
 // rb_internal.hpp's.
 #include <cmath>
+#include <cstdlib>
+#include <cstring>
 #include <initializer_list>
 
 #include "rb_engine.hpp"
@@ -688,6 +691,169 @@ int hemisphere_entry(rb_engine* e, const char* who, bool openness, bool device, 
     return answered(e, t, device ? hemisphere_device_locked(t, c, surfels, seeds, n, out) : hemisphere_locked(t, c, surfels, seeds, n, out));
 }
 
+
+// ---- lightmap texels made on the device (rb_abi.h)
+// the refusals every lightmap entry point shares; before a device is touched (e may be NULL: the engine-less forms)
+int lightmap_size_check(rb_engine* e, const char* who, uint32_t width, uint32_t height, uint32_t dilate) {
+    if (width == 0u || height == 0u || width > RB_LIGHTMAP_MAX_SIDE || height > RB_LIGHTMAP_MAX_SIDE)
+        return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: an atlas of %u x %u texels; 1 .. %u each are taken", who, width, height, RB_LIGHTMAP_MAX_SIDE);
+    if (static_cast<uint64_t>(width) * height > 0x7FFFFFFFull - 63ull)
+        return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s takes at most 2^31 - 64 texels per call", who);
+    if (dilate > RB_LIGHTMAP_MAX_DILATE) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: dilate is %u; at most %u passes are taken", who, dilate, RB_LIGHTMAP_MAX_DILATE);
+    return RB_OK;
+}
+
+int lightmap_check(rb_engine* e, const char* who, const rb_lightmap_params* prm) {
+    if (const int rc = lightmap_size_check(e, who, prm->width, prm->height, prm->dilate)) return rc;
+    if (!std::isfinite(prm->offset) || prm->offset < 0.0f) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: offset must be finite and at least 0", who);
+    if ((prm->flags & ~static_cast<uint32_t>(RB_LIGHTMAP_FLIP)) != 0u) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: unknown flag bits 0x%x", who, prm->flags);
+    for (const uint32_t r : prm->_reserved)
+        if (r != 0u) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: _reserved must be 0", who);
+    return RB_OK;
+}
+
+// units per cover launch: RB_LIGHTMAP_PIECE_UNITS in the environment (tests: a piece boundary at a small atlas), else the default
+uint64_t lightmap_piece_units() {
+    const char* const s = std::getenv("RB_LIGHTMAP_PIECE_UNITS");
+    return s ? std::strtoull(s, nullptr, 10) : 0ull;
+}
+
+rb::LmArgs lightmap_args(const rb_lightmap_params& prm, const rb::PrepTri* ptris, const rb::PrepTriShade* pshade, uint32_t n_tris,
+                         const float* uvs, uint32_t n_uvs) {
+    rb::LmArgs g{};
+    g.ptris = ptris;
+    g.pshade = pshade;
+    g.uvs = uvs;
+    g.n_tris = n_tris;
+    g.n_uvs = n_uvs;
+    g.width = prm.width;
+    g.height = prm.height;
+    g.mesh = prm.mesh;
+    g.flags = prm.flags;
+    return g;
+}
+
+// triangles -> records in triangle order by the upload's own kernel, then the atlas; returns a HIP status
+int lightmap_generate(const rb_lightmap_params& prm, const rb_gpu_triangle* d_tris, uint32_t n_tris, uint32_t tri_count, const float* d_uvs,
+                      uint32_t n_uvs, uint32_t* d_iota, rb::PrepTri* d_ptris, rb::PrepTriShade* d_pshade, void* d_work, rb_surfel* d_surfels,
+                      uint32_t* d_owners, hipStream_t stream) {
+    if (n_tris > 0u) {
+        if (const int st = rb::launch_lightmap_iota(d_iota, n_tris, stream)) return st;
+        if (const int st = rb::launch_prep_tris(d_tris, tri_count, d_iota, n_tris, d_ptris, d_pshade, stream)) return st;
+    }
+    return rb::lightmap_surfels(lightmap_args(prm, d_ptris, d_pshade, n_tris, d_uvs, n_uvs), d_surfels, d_owners, d_work, lightmap_piece_units(), stream);
+}
+
+int lightmap_events(rb_engine* e) {
+    for (hipEvent_t& x : e->ev_lm)
+        if (!x) HIP_TRY(e, hipEventCreate(&x));
+    e->lm_timed[0] = e->lm_timed[1] = false;
+    return RB_OK;
+}
+
+// the surfel stage over the engine's scene between its own event pair, queued on the engine's stream
+int lightmap_stage_surfels(rb_engine* e, const rb::KParams& p, const rb_lightmap_params& prm, rb_surfel* d_surfels, uint32_t* d_owners) {
+    const uint32_t n_tris = e->n_tris;
+    if (const hipError_t st = hipEventRecord(e->ev_lm[0], e->stream)) return static_cast<int>(st);
+    const int st = lightmap_generate(prm, e->tris.ptr, n_tris, p.u.bvh_triangle_count, e->uvs.ptr, e->n_uvs, e->lm_iota.ptr, e->lm_ptris.ptr,
+                                     e->lm_pshade.ptr, e->lm_work.ptr, d_surfels, d_owners, e->stream);
+    if (st) return st;
+    if (const hipError_t st1 = hipEventRecord(e->ev_lm[1], e->stream)) return static_cast<int>(st1);
+    e->lm_timed[0] = true;
+    return 0;
+}
+
+// the scratch of the surfel stage beside the caller's buffers
+int lightmap_scratch(rb_engine* e, size_t n, bool owners) {
+    const uint32_t n_tris = e->n_tris;
+    HIP_TRY(e, e->lm_iota.reserve(n_tris));
+    HIP_TRY(e, e->lm_ptris.reserve(n_tris));
+    HIP_TRY(e, e->lm_pshade.reserve(n_tris));
+    HIP_TRY(e, e->lm_work.reserve(rb::lightmap_work_bytes(n_tris)));
+    if (owners) HIP_TRY(e, e->lm_owners.reserve(n));
+    return RB_OK;
+}
+
+int lightmap_surfels_device_locked(rb_engine* e, const rb_lightmap_params& prm, rb_surfel* d_surfels, uint32_t* d_owners) {
+    const size_t n = static_cast<size_t>(prm.width) * prm.height;
+    int rc = device_range(e, d_surfels, n * sizeof(rb_surfel), 16, "d_surfels");
+    if (!rc && d_owners) rc = device_range(e, d_owners, n * sizeof(uint32_t), 4, "d_owners");
+    if (!rc) rc = lightmap_events(e);
+    if (rc) return rc;
+    e->cam_pieces = 0;
+    return device_query_locked(e, [&](const rb::KParams& p, rb::LaunchInfo* li) {
+        if (lightmap_scratch(e, n, d_owners == nullptr)) return static_cast<int>(hipErrorOutOfMemory);
+        li->kernel_name = "k_lm_surfels";
+        return lightmap_stage_surfels(e, p, prm, d_surfels, d_owners ? d_owners : e->lm_owners.ptr);
+    });
+}
+
+// the three stages on the engine's stream into device buffers (either may be nullptr: the engine's scratch stands in); nothing
+// is waited for but the surfel stage's unit total
+int bake_lightmap_queue(rb_engine* e, const rb_lightmap_params& prm, uint32_t first_sample, uint32_t samples, float* d_rgba, rb_radiance* d_sums) {
+    const size_t n = static_cast<size_t>(prm.width) * prm.height;
+    rb_hemi_params hp{};
+    hp.offset = prm.offset;
+    const HemiCall c{hp, first_sample, samples, false};
+    const size_t piece = hemi_piece_surfels(n, samples);
+    if (const int rc = lightmap_events(e)) return rc;
+    e->cam_pieces = 0;
+    return device_query_locked(e, [&](const rb::KParams& p, rb::LaunchInfo* li) {
+        hipError_t st = hipSuccess;
+        if (lightmap_scratch(e, n, true) || hemi_scratch(e, c, piece)) return static_cast<int>(hipErrorOutOfMemory);
+        st = e->lm_surfels.reserve(n);
+        if (st == hipSuccess && !d_sums) st = e->lm_sums.reserve(n);
+        if (st == hipSuccess && d_rgba && prm.dilate > 0u) st = e->lm_rgba[1].reserve(n * 4);
+        if (st != hipSuccess) return static_cast<int>(st);
+        rb_radiance* const sums = d_sums ? d_sums : e->lm_sums.ptr;
+        if (const int s = lightmap_stage_surfels(e, p, prm, e->lm_surfels.ptr, e->lm_owners.ptr)) return s;
+        for (size_t done = 0; done < n; done += piece)
+            if (const int s = hemi_piece(e, p, c, e->lm_surfels.ptr + done, nullptr, done, std::min(piece, n - done), sums + done, li)) return s;
+        if (!d_rgba) return 0;
+        if (const hipError_t s = hipEventRecord(e->ev_lm[2], e->stream)) return static_cast<int>(s);
+        if (const int s = rb::launch_lightmap_resolve(sums, prm.width, prm.height, prm.dilate, d_rgba, e->lm_rgba[1].ptr, e->stream)) return s;
+        if (const hipError_t s = hipEventRecord(e->ev_lm[3], e->stream)) return static_cast<int>(s);
+        e->lm_timed[1] = true;
+        return 0;
+    });
+}
+
+int bake_lightmap_device_locked(rb_engine* e, const rb_lightmap_params& prm, uint32_t first_sample, uint32_t samples, float* d_rgba, rb_radiance* d_sums) {
+    const size_t n = static_cast<size_t>(prm.width) * prm.height;
+    int rc = RB_OK;
+    if (d_rgba) rc = device_range(e, d_rgba, n * 16, 16, "d_rgba_out");
+    if (!rc && d_sums) rc = device_range(e, d_sums, n * sizeof(rb_radiance), 16, "d_sums_out");
+    return rc ? rc : bake_lightmap_queue(e, prm, first_sample, samples, d_rgba, d_sums);
+}
+
+// the host form: the device form into the engine's own buffers, then the copies out and the wait
+int bake_lightmap_locked(rb_engine* e, const rb_lightmap_params& prm, uint32_t first_sample, uint32_t samples, float* rgba_out, rb_radiance* sums_out) {
+    const size_t n = static_cast<size_t>(prm.width) * prm.height;
+    if (rgba_out) HIP_TRY(e, e->lm_rgba[0].reserve(n * 4));
+    int rc = bake_lightmap_queue(e, prm, first_sample, samples, rgba_out ? e->lm_rgba[0].ptr : nullptr, nullptr);
+    if (!rc && rgba_out) rc = query_copy_out(e, rgba_out, e->lm_rgba[0].ptr, n * 16, page_locked(rgba_out));
+    if (!rc && sums_out) rc = query_copy_out(e, sums_out, e->lm_sums.ptr, n * sizeof(rb_radiance), page_locked(sums_out));
+    if (rc) return rc;
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    HIP_TRY(e, hipEventElapsedTime(&e->last_query_ms, e->ev_q[0], e->ev_q[1]));
+    e->query_ms_pending = false;
+    return RB_OK;
+}
+
+int bake_lightmap_entry(rb_engine* e, const char* who, bool device, const rb_lightmap_params* prm, uint32_t first_sample, uint32_t samples,
+                        float* rgba, rb_radiance* sums) {
+    if (!e) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (!prm || (!rgba && !sums)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "%s: params is NULL, or rgba_out and sums_out both are", who);
+    if (const int rc = lightmap_check(e, who, prm)) return rc;
+    rb_hemi_params hp{};
+    hp.offset = prm->offset;
+    if (const int rc = hemi_check(e, who, &hp, static_cast<size_t>(prm->width) * prm->height, first_sample, samples, false)) return rc;
+    rb_engine* const t = answering(e);
+    return answered(e, t, device ? bake_lightmap_device_locked(t, *prm, first_sample, samples, rgba, sums)
+                                 : bake_lightmap_locked(t, *prm, first_sample, samples, rgba, sums));
+}
+
 }  // namespace
 
 extern "C" {
@@ -892,6 +1058,109 @@ int rb_openness_hemisphere(rb_engine* e, const rb_surfel* surfels, const uint32_
 int rb_openness_hemisphere_device(rb_engine* e, const rb_surfel* d_surfels, const uint32_t* d_seeds, size_t n,
                                   const rb_hemi_params* params, uint32_t first_sample, uint32_t samples, rb_openness* d_out) {
     return hemisphere_entry(e, "rb_openness_hemisphere_device", true, true, d_surfels, d_seeds, n, params, first_sample, samples, d_out);
+}
+
+int rb_lightmap_surfels(int32_t device, const rb_gpu_triangle* tris, size_t n_tris, const float* uvs, size_t n_uv_floats,
+                        const rb_lightmap_params* params, rb_surfel* surfels_out, uint32_t* owners_out) {
+    if (!params || !surfels_out || (n_tris > 0 && !tris) || (n_uv_floats > 0 && !uvs))
+        return rb::fail(nullptr, RB_ERR_NULL_ARGUMENT, "rb_lightmap_surfels: params / surfels_out / tris / uvs is NULL");
+    if (const int rc = lightmap_check(nullptr, "rb_lightmap_surfels", params)) return rc;
+    if (n_tris > 0x7FFFFFFFull - 63ull || n_uv_floats > 0xFFFFFFFFull)
+        return rb::fail(nullptr, RB_ERR_INVALID_OPTIONS, "rb_lightmap_surfels takes at most 2^31 - 64 triangles and 2^32 - 1 uv floats");
+    const size_t n = static_cast<size_t>(params->width) * params->height;
+    if (n_tris == 0) {   // nothing covers anything: no device is needed to say so
+        std::memset(surfels_out, 0, n * sizeof(rb_surfel));
+        if (owners_out) std::memset(owners_out, 0xFF, n * sizeof(uint32_t));
+        return RB_OK;
+    }
+    if (device >= 0 && hipSetDevice(device) != hipSuccess) return rb::fail(nullptr, RB_ERR_DEVICE, "hipSetDevice(%d) failed", device);
+    const uint32_t nt = static_cast<uint32_t>(n_tris), nu = static_cast<uint32_t>(n_uv_floats);
+    rb::DevBuf<rb_gpu_triangle> d_tris;
+    rb::DevBuf<float> d_uvs;
+    rb::DevBuf<uint32_t> d_iota, d_owners;
+    rb::DevBuf<rb::PrepTri> d_ptris;
+    rb::DevBuf<rb::PrepTriShade> d_pshade;
+    rb::DevBuf<unsigned char> d_work;
+    rb::DevBuf<rb_surfel> d_surfels;
+    hipStream_t stream = nullptr;
+    hipError_t st = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
+    if (st == hipSuccess) st = d_tris.resize(nt);
+    if (st == hipSuccess) st = d_uvs.resize(nu);
+    if (st == hipSuccess) st = d_iota.resize(nt);
+    if (st == hipSuccess) st = d_ptris.resize(nt);
+    if (st == hipSuccess) st = d_pshade.resize(nt);
+    if (st == hipSuccess) st = d_work.resize(rb::lightmap_work_bytes(nt));
+    if (st == hipSuccess) st = d_owners.resize(n);
+    if (st == hipSuccess) st = d_surfels.resize(n);
+    if (st == hipSuccess) st = hipMemcpyAsync(d_tris.ptr, tris, n_tris * sizeof(rb_gpu_triangle), hipMemcpyHostToDevice, stream);
+    if (st == hipSuccess && nu) st = hipMemcpyAsync(d_uvs.ptr, uvs, n_uv_floats * sizeof(float), hipMemcpyHostToDevice, stream);
+    if (st == hipSuccess)   // every triangle counts as valid: tri_count = n_tris
+        st = static_cast<hipError_t>(lightmap_generate(*params, d_tris.ptr, nt, nt, d_uvs.ptr, nu, d_iota.ptr, d_ptris.ptr, d_pshade.ptr, d_work.ptr,
+                                                       d_surfels.ptr, d_owners.ptr, stream));
+    if (st == hipSuccess) st = hipMemcpyAsync(surfels_out, d_surfels.ptr, n * sizeof(rb_surfel), hipMemcpyDeviceToHost, stream);
+    if (st == hipSuccess && owners_out) st = hipMemcpyAsync(owners_out, d_owners.ptr, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
+    if (st == hipSuccess) st = hipStreamSynchronize(stream);
+    if (stream) (void)hipStreamSynchronize(stream);   // (the buffers are freed on return, after this)
+    if (stream) (void)hipStreamDestroy(stream);
+    if (st != hipSuccess) return rb::fail(nullptr, RB_ERR_DEVICE, "rb_lightmap_surfels failed: %s", hipGetErrorString(st));
+    return RB_OK;
+}
+
+int rb_lightmap_surfels_device(rb_engine* e, const rb_lightmap_params* params, rb_surfel* d_surfels, uint32_t* d_owners) {
+    if (!e) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (!params || !d_surfels) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "rb_lightmap_surfels_device: params / d_surfels is NULL");
+    if (const int rc = lightmap_check(e, "rb_lightmap_surfels_device", params)) return rc;
+    rb_engine* const t = answering(e);
+    return answered(e, t, lightmap_surfels_device_locked(t, *params, d_surfels, d_owners));
+}
+
+int rb_lightmap_resolve(int32_t device, uint32_t width, uint32_t height, const rb_radiance* sums, uint32_t dilate, float* rgba_out) {
+    if (!sums || !rgba_out) return rb::fail(nullptr, RB_ERR_NULL_ARGUMENT, "rb_lightmap_resolve: sums / rgba_out is NULL");
+    if (const int rc = lightmap_size_check(nullptr, "rb_lightmap_resolve", width, height, dilate)) return rc;
+    if (device >= 0 && hipSetDevice(device) != hipSuccess) return rb::fail(nullptr, RB_ERR_DEVICE, "hipSetDevice(%d) failed", device);
+    const size_t n = static_cast<size_t>(width) * height;
+    rb::DevBuf<rb_radiance> d_sums;
+    rb::DevBuf<float> d_out, d_tmp;
+    hipStream_t stream = nullptr;
+    hipError_t st = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
+    if (st == hipSuccess) st = d_sums.resize(n);
+    if (st == hipSuccess) st = d_out.resize(n * 4);
+    if (st == hipSuccess && dilate > 0u) st = d_tmp.resize(n * 4);
+    if (st == hipSuccess) st = hipMemcpyAsync(d_sums.ptr, sums, n * sizeof(rb_radiance), hipMemcpyHostToDevice, stream);
+    if (st == hipSuccess) st = static_cast<hipError_t>(rb::launch_lightmap_resolve(d_sums.ptr, width, height, dilate, d_out.ptr, d_tmp.ptr, stream));
+    if (st == hipSuccess) st = hipMemcpyAsync(rgba_out, d_out.ptr, n * 16, hipMemcpyDeviceToHost, stream);
+    if (st == hipSuccess) st = hipStreamSynchronize(stream);
+    if (stream) (void)hipStreamSynchronize(stream);   // (the buffers are freed on return, after this)
+    if (stream) (void)hipStreamDestroy(stream);
+    if (st != hipSuccess) return rb::fail(nullptr, RB_ERR_DEVICE, "rb_lightmap_resolve failed: %s", hipGetErrorString(st));
+    return RB_OK;
+}
+
+int rb_bake_lightmap(rb_engine* e, const rb_lightmap_params* params, uint32_t first_sample, uint32_t samples, float* rgba_out,
+                     rb_radiance* sums_out) {
+    return bake_lightmap_entry(e, "rb_bake_lightmap", false, params, first_sample, samples, rgba_out, sums_out);
+}
+
+int rb_bake_lightmap_device(rb_engine* e, const rb_lightmap_params* params, uint32_t first_sample, uint32_t samples,
+                            float* d_rgba_out, rb_radiance* d_sums_out) {
+    return bake_lightmap_entry(e, "rb_bake_lightmap_device", true, params, first_sample, samples, d_rgba_out, d_sums_out);
+}
+
+int rb_last_lightmap_ms(rb_engine* e, float* surfels_ms, float* resolve_ms) {
+    if (!e) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    rb_engine* const t = rb::is_group(e) ? e->parts[0].get() : e;
+    float* const out[2] = {surfels_ms, resolve_ms};
+    for (int k = 0; k < 2; k++) {
+        if (!out[k]) continue;
+        *out[k] = 0.0f;
+        if (!t->lm_timed[k]) continue;
+        rb::set_device(t);
+        HIP_TRY(e, hipEventSynchronize(t->ev_lm[2 * k + 1]));
+        HIP_TRY(e, hipEventElapsedTime(out[k], t->ev_lm[2 * k], t->ev_lm[2 * k + 1]));
+    }
+    return RB_OK;
 }
 
 int rb_denoise_default_params(rb_denoise_params* p) {

@@ -1099,6 +1099,8 @@ void rb_destroy(rb_engine* e) {
         if (x) (void)hipEventDestroy(x);
     for (hipEvent_t x : e->ev_dn)
         if (x) (void)hipEventDestroy(x);
+    for (hipEvent_t x : e->ev_lm)
+        if (x) (void)hipEventDestroy(x);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
 }

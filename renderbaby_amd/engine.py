@@ -618,6 +618,80 @@ class Engine:
         return self._hemisphere(self._lib.rb_openness_hemisphere, self._lib.rb_openness_hemisphere_device, abi.OPENNESS, 2, points, normals,
                                 samples, first_sample, seeds, self._hemi_params(offset, radius, mask), out)
 
+    # ---- lightmap texels made on the device (rb_abi.h)
+    @staticmethod
+    def _lightmap_params(width, height, mesh=None, flip=False, offset=0.0, dilate=0):
+        for name, v in (("width", width), ("height", height), ("dilate", dilate)):
+            if not 0 <= int(v) < 2 ** 32:
+                raise ValueError(f"{name}: a 32-bit unsigned number")
+        prm = np.zeros(1, dtype=abi.LIGHTMAP_PARAMS)
+        prm["width"], prm["height"], prm["dilate"], prm["offset"] = int(width), int(height), int(dilate), offset
+        prm["mesh"] = abi.LIGHTMAP_ALL_MESHES if mesh is None else int(mesh)
+        prm["flags"] = abi.LIGHTMAP_FLIP if flip else 0
+        return prm
+
+    def lightmap_surfels(self, width, height, mesh=None, flip=False, out=None):
+        """rb_lightmap_surfels_device: the surfel of every texel of a ``width`` x ``height`` atlas over the uploaded scene's uvs
+        -- texel (x, y) at y * width + x, row 0 on top -- and the triangle that owns it (abi.LIGHTMAP_NO_OWNER: none; its surfel
+        is all zero, which trace_hemisphere and openness call invalid).  ``mesh``: a mesh index, or None for every mesh;
+        ``flip``: the normals negated.  ``out`` = (surfels, owners) torch tensors on the engine's device, (n, 8) float32 and
+        (n,) int32 or None: filled and returned, and nothing crosses to the host -- what trace_hemisphere and openness take
+        as ``surfels[:, 0:3]``, ``surfels[:, 4:7]``.  Without ``out``: (abi.SURFEL[n], uint32 owners[n]) numpy arrays."""
+        import torch
+        prm = self._lightmap_params(width, height, mesh, flip)
+        n = int(width) * int(height)
+        dev = torch.device("cuda", self.query_device)
+        if out is None:
+            surf = torch.empty((n, 8), dtype=torch.float32, device=dev)
+            own = torch.empty((n,), dtype=torch.int32, device=dev)
+        else:
+            surf, own = out
+        sp, ns = self._device_tensor(surf, torch.float32, 8, "surfels")
+        op, no = self._device_tensor(own, torch.int32, None, "owners") if own is not None else (None, n)
+        if ns != n or no != n:
+            raise ValueError("surfels and owners need width * height rows")
+        self._device_call(self._lib.rb_lightmap_surfels_device, prm.ctypes.data, sp, op)
+        if out is not None:
+            return surf, own
+        return surf.cpu().numpy().view(abi.SURFEL).reshape(-1), own.cpu().numpy().view(np.uint32)
+
+    def bake_lightmap(self, width, height, samples, first_sample=0, mesh=None, flip=False, offset=1e-3, dilate=2, out=None, sums=None):
+        """rb_bake_lightmap: the lightmap of the uploaded scene's uvs in one call -- surfels, ``samples`` cosine-weighted rays
+        per texel traced as trace_hemisphere traces them (the stream id is the texel index), sum / weight, ``dilate`` fill
+        passes round the charts -> float32 (height, width, 4) in sample_texture's layout (row 0 on top); fourth component
+        0 = empty, 1 = baked, 2 = filled.  ``sums``: an abi.RADIANCE[height * width] array that receives the raw sums, for
+        accumulating over calls with ``first_sample`` and resolving later (lightmap_resolve).  Torch tensors on the engine's
+        device for ``out`` ((n, 4) float32) or ``sums`` ((n, 4) float32) select rb_bake_lightmap_device: nothing crosses to the
+        host, and ``out`` (or, with sums alone, ``sums``) is returned."""
+        samples, first_sample = int(samples), int(first_sample)
+        if not (0 <= samples < 2 ** 32 and 0 <= first_sample < 2 ** 32):
+            raise ValueError("samples and first_sample are 32-bit unsigned numbers")
+        prm = self._lightmap_params(width, height, mesh, flip, offset, dilate)
+        n = int(width) * int(height)
+        if _is_tensor(out) or _is_tensor(sums):
+            import torch
+            op, no = self._device_tensor(out, torch.float32, 4, "out") if out is not None else (None, n)
+            sp, ns = self._device_tensor(sums, torch.float32, 4, "sums") if sums is not None else (None, n)
+            if no != n or ns != n:
+                raise ValueError("out and sums need width * height rows")
+            self._device_call(self._lib.rb_bake_lightmap_device, prm.ctypes.data, first_sample, samples, op, sp)
+            return out if out is not None else sums
+        res = np.empty((int(height), int(width), 4), dtype=np.float32) if out is None else out
+        if not isinstance(res, np.ndarray) or res.dtype != np.float32 or res.size != n * 4 or not res.flags.c_contiguous:
+            raise ValueError("out: a contiguous float32 array of height x width x 4 elements is needed")
+        if sums is not None and (not isinstance(sums, np.ndarray) or sums.dtype != abi.RADIANCE or sums.size != n or not sums.flags.c_contiguous):
+            raise ValueError("sums: a contiguous abi.RADIANCE array of height * width elements is needed")
+        self._check(self._lib.rb_bake_lightmap(self._h, prm.ctypes.data, first_sample, samples, res.ctypes.data if n else None,
+                                               sums.ctypes.data if (sums is not None and n) else None))
+        return res
+
+    def last_lightmap_ms(self):
+        """(surfels_ms, resolve_ms): kernel ms of the surfel stage and of the resolve in the most recent lightmap_surfels or
+        bake_lightmap; both lie inside last_query_ms()"""
+        a, b = C.c_float(), C.c_float()
+        self._check(self._lib.rb_last_lightmap_ms(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def last_camera_rays_ms(self):
         """kernel ms of the generator (k_cam_rays, k_hemi_rays) in the most recent trace_camera, trace_hemisphere or openness:
         its share of last_query_ms()"""
@@ -831,6 +905,40 @@ def hemisphere_rays_device(points, normals, samples, first_sample=0, seeds=None,
     if rc != abi.RB_OK:
         raise RenderError(rc, (lib.rb_last_error(None) or b"").decode())
     return rays, seeds_out
+
+
+def lightmap_surfels_device(tris, uvs, width, height, mesh=None, flip=False, device=-1):
+    """rb_lightmap_surfels: the generator alone, no engine -- (abi.SURFEL[height * width], uint32 owners[height * width]) of
+    abi.GPU_TRIANGLE triangles and their uv floats; every triangle counts as valid.  ``lightmap.surfels`` is its numpy model."""
+    tris = np.ascontiguousarray(tris, dtype=abi.GPU_TRIANGLE).reshape(-1)
+    uvs = np.ascontiguousarray(uvs, dtype=np.float32).reshape(-1)
+    prm = Engine._lightmap_params(width, height, mesh, flip)
+    n = int(width) * int(height) if (0 < int(width) <= abi.LIGHTMAP_MAX_SIDE and 0 < int(height) <= abi.LIGHTMAP_MAX_SIDE) else 0
+    surf, own = np.zeros(n, dtype=abi.SURFEL), np.zeros(n, dtype=np.uint32)   # (a refused call writes nothing)
+    lib = load()
+    rc = lib.rb_lightmap_surfels(int(device), tris.ctypes.data if len(tris) else None, len(tris), uvs.ctypes.data if len(uvs) else None,
+                                 len(uvs), prm.ctypes.data, surf.ctypes.data, own.ctypes.data)
+    if rc != abi.RB_OK:
+        raise RenderError(rc, (lib.rb_last_error(None) or b"").decode())
+    return surf, own
+
+
+def lightmap_resolve(sums, width, height, dilate=2, device=-1):
+    """rb_lightmap_resolve: the resolve alone, no engine -- abi.RADIANCE[height * width] sums -> float32 (height, width, 4):
+    sum / weight and ``dilate`` fill passes.  ``lightmap.resolve`` is its numpy model."""
+    sums = np.ascontiguousarray(sums, dtype=abi.RADIANCE).reshape(-1)
+    width, height, dilate = int(width), int(height), int(dilate)
+    for v in (width, height, dilate):
+        if not 0 <= v < 2 ** 32:
+            raise ValueError("width, height and dilate are 32-bit unsigned numbers")
+    if len(sums) != width * height:
+        raise ValueError("sums: width * height records are needed")
+    out = np.zeros((height, width, 4), dtype=np.float32)
+    lib = load()
+    rc = lib.rb_lightmap_resolve(int(device), width, height, sums.ctypes.data, dilate, out.ctypes.data)
+    if rc != abi.RB_OK:
+        raise RenderError(rc, (lib.rb_last_error(None) or b"").decode())
+    return out
 
 
 def denoise_defaults():

@@ -6,6 +6,7 @@
                                  [--denoise [--denoise-iterations N]]
                                  [--camera equirect|ortho|thin-lens [--ortho-width W] [--aperture A --focus-distance F] [--jitter]]
                                  [--probe x,y,z [--probe-normal x,y,z]] [--device-rays]
+                                 [--lightmap W H [--lightmap-mesh i] [--lightmap-flip]]
 
 scene file -> scene_io.load_scene (the importer's and the Scene->RenderConfig adapter's rules) ->
 RenderConfig -> librenderbaby_hip.so -> Frame -> PNG.  With --every N the progressive iterator is used
@@ -20,7 +21,10 @@ thin lens, a lens point per sample, focused on a plane at the focus distance (ca
 Engine.trace_camera).  --probe prints the mean radiance over the cosine-weighted hemisphere at a point
 (bake.irradiance, spp rays; normal +y unless --probe-normal says otherwise).  --device-rays makes the hemisphere rays of
 --aov ao and --probe on the device (aov.ambient_occlusion_device, bake.irradiance_device): other
-directions than the host generators', the same estimate.
+directions than the host generators', the same estimate.  --lightmap W H bakes the scene's lightmap over its uvs on the device
+(bake.lightmap -> Engine.bake_lightmap, spp samples per texel) and writes it as out.lightmap.png in the
+texture's own encoding (bake.lightmap_texture), for one mesh with --lightmap-mesh; with --aov ao also the ambient-occlusion map
+of the same texels (aov.ambient_occlusion_map) as out.lightmap.ao.png.
 """
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -44,6 +48,9 @@ ap.add_argument("--jitter", action="store_true", help="--camera with a ray per s
 ap.add_argument("--probe", default=None, help="x,y,z: print the mean radiance arriving at this point (bake.irradiance)")
 ap.add_argument("--probe-normal", default="0,1,0")
 ap.add_argument("--device-rays", action="store_true", help="--aov ao and --probe with their hemisphere rays made on the device (DESIGN.md section 16)")
+ap.add_argument("--lightmap", type=int, nargs=2, metavar=("W", "H"), default=None, help="also bake the lightmap over the scene's uvs, as out.lightmap.png")
+ap.add_argument("--lightmap-mesh", type=int, default=None, help="--lightmap for the triangles of this mesh index only")
+ap.add_argument("--lightmap-flip", action="store_true", help="--lightmap with the triangles' normals negated")
 a = ap.parse_args()
 aovs = [n for n in a.aov.split(",") if n]
 for n in aovs:
@@ -120,4 +127,19 @@ if a.probe:
     else:
         rgb = bake.irradiance(eng, [point], [normal], rays)[0]
     print(f"probe at {tuple(point)}, normal {tuple(normal)}, {rays} rays: mean radiance {rgb[0]:.6g} {rgb[1]:.6g} {rgb[2]:.6g}")
+if a.lightmap:
+    import numpy as np
+    w, h = a.lightmap
+    spp = min(max(s.total_samples, 1), 65536)
+    base, ext = os.path.splitext(a.png)
+    rgba = bake.lightmap(eng, w, h, spp, mesh=a.lightmap_mesh, flip=a.lightmap_flip)
+    surfels_ms, resolve_ms = eng.last_lightmap_ms()
+    scene_io.export_png(f"{base}.lightmap{ext}", Frame(w, h, bake.lightmap_texture(rgba)))
+    print(f"lightmap {w} x {h}, {spp} samples per texel, {int((rgba[..., 3] == 1).sum())} baked and {int((rgba[..., 3] == 2).sum())} filled texels, "
+          f"with {eng.last_query_kernel_name()} in {eng.last_query_ms():.3f} ms (surfels {surfels_ms:.3f}, resolve {resolve_ms:.3f}) -> {base}.lightmap{ext}")
+    if "ao" in aovs:
+        ao = aov.ambient_occlusion_map(eng, w, h, 16, a.ao_radius, mesh=a.lightmap_mesh, flip=a.lightmap_flip)
+        img = aov.ao_u8(np.where(np.isnan(ao), np.float32(0), ao))
+        scene_io.export_png(f"{base}.lightmap.ao{ext}", Frame(w, h, img))
+        print(f"ambient-occlusion map with {eng.last_query_kernel_name()} in {eng.last_query_ms():.3f} ms -> {base}.lightmap.ao{ext}")
 eng.close()
