@@ -285,7 +285,12 @@ DEV void segment_spheres(const KParams& p, f3 o, f3 d, float a, float& closest_t
 
 // Point lights, sky, the winner's HitRecord, shading and scatter, shader.wgsl:590-660
 // PARK: the rejection loop parks the seed (random_unit_vector); false keeps the loop as it was, same vectors.
-template <bool STATS, bool PARK = true>
+// JOINED: the two scatter branches share one normalize (below); false keeps one in each branch, same
+// values, for a kernel whose register allocation would move for the worse (rb_kernels.hip names them).
+#ifndef RB_ONE_NORMALIZE
+#define RB_ONE_NORMALIZE 1   // 0: normalize(d) in the metal branch, normalize(normal + ruv) in the other, for the A/B builds of profiles/r19_c2_bench_ab.txt
+#endif
+template <bool STATS, bool PARK = true, bool JOINED = true>
 DEV bool segment_post(const KParams& p, Path& pt, const TriHit th, const SegState st, float closest_t, uint32_t sphere_idx,
                       Tally<STATS>& tl) {
     const f3 o = pt.o, d = pt.d;
@@ -399,14 +404,20 @@ DEV bool segment_post(const KParams& p, Path& pt, const TriHit th, const SegStat
     const f3 ruv = random_unit_vector<PARK>(pt.seed);
     f3 scattered, albedo;
     bool absorbed = false;
+    // A lane normalizes d (metal) or normal + ruv (the other branch), never both, and the wave paid for both sites: one
+    // normalize of the lane's own operand in front of the branch is the same operations on the same values (what it gives
+    // a lane whose normal + ruv is near zero is dropped by the select, as the branch dropped it).
+    constexpr bool one_norm = JOINED && RB_ONE_NORMALIZE != 0;
+    const f3 sd = normal + ruv;
+    f3 nin = sd;
+    if constexpr (one_norm) nin = normalize(is_metal ? d : sd);
     if (is_metal) {
-        const f3 reflected = reflect_vector(normalize(d), normal);
+        const f3 reflected = reflect_vector(one_norm ? nin : normalize(d), normal);
         scattered = reflected + m.fuzz * ruv;
         absorbed = dot(scattered, normal) <= 0.0f;  // :640-642
         albedo = m.specular;
     } else {
-        const f3 sd = normal + ruv;
-        scattered = near_zero(sd) ? normal : normalize(sd);
+        scattered = near_zero(sd) ? normal : (one_norm ? nin : normalize(sd));
         albedo = m.diffuse;
         if (use_tex) {
             if (tri_won_a) tri_uv(p, th, uvx, uvy);
@@ -543,22 +554,22 @@ DEV void segment_resolve(const KParams& p, f3 o, f3 d, const TriHit th, const Se
 }
 
 // One iteration of the bounce loop after the triangle traversal (`th`: its winner).
-template <bool STATS, bool SPHTREE = true, bool PARK = true>
+template <bool STATS, bool SPHTREE = true, bool PARK = true, bool JOINED = true>
 DEV bool segment_finish(const KParams& p, Path& pt, const TriHit th, uint32_t* stack, uint32_t stride,
                         Tally<STATS>& tl) {
     const SegState st = segment_pre<STATS>(fresh_params(p), pt, th, tl);
     float closest_t = st.closest_t;
     uint32_t sphere_idx = 0xFFFFFFFFu;
     segment_spheres<STATS, SPHTREE>(fresh_params(p), pt.o, pt.d, dot(pt.d, pt.d), closest_t, sphere_idx, stack, stride, tl);
-    return segment_post<STATS, PARK>(fresh_params(p), pt, th, st, closest_t, sphere_idx, tl);
+    return segment_post<STATS, PARK, JOINED>(fresh_params(p), pt, th, st, closest_t, sphere_idx, tl);
 }
 
 // One whole iteration of the bounce loop: traversal + everything else.  MULTI = false: trees of at most one node AND no
 // sphere tree (k_trace's default instantiations).
-template <bool STATS, bool MULTI = true>
+template <bool STATS, bool MULTI = true, bool JOINED = true>
 DEV bool segment(const KParams& p, Path& pt, uint32_t* stack, uint32_t stride, Tally<STATS>& tl) {
     const TriHit th = intersect_bvh<STATS, MULTI>(fresh_params(p), pt.o, pt.d, stack, stride, tl);
-    return segment_finish<STATS, MULTI>(p, pt, th, stack, stride, tl);
+    return segment_finish<STATS, MULTI, true, JOINED>(p, pt, th, stack, stride, tl);
 }
 
 // ----------------------------------------------------------------- camera --

@@ -433,7 +433,7 @@ struct ItemQueue {
 // forced batches), and MULTI, which keeps that form whatever the batch (its segment code leaves the start no registers
 // to win).  The choice is made at compile time so that no instantiation carries both start codes; the two forms are two
 // kernels, k_trace and k_trace_direct, around this one body.
-template <bool STATS, bool MULTI, bool STAGED>
+template <bool STATS, bool MULTI, bool STAGED, bool JOINED>
 DEV void trace_body(const KParams& p, v4f* s_ring) {
     extern __shared__ __attribute__((aligned(16))) uint32_t s_stack[];
     const uint32_t tid = threadIdx.x;
@@ -546,7 +546,7 @@ DEV void trace_body(const KParams& p, v4f* s_ring) {
         // (53 v_mov_b32 per iteration; profiles/r12_ktrace_moves_before.txt).
         if (__ballot(active) == 0ull && exhausted && loc_next == loc_end) break;
         if (active) {
-            const bool alive = segment<STATS, MULTI>(p, pt, &s_stack[tid], kTraceBlock, tl);
+            const bool alive = segment<STATS, MULTI, JOINED>(p, pt, &s_stack[tid], kTraceBlock, tl);
             if (!alive) {
                 cring.finish(colors, item, pt.color);
                 tl.paths++;
@@ -560,12 +560,15 @@ DEV void trace_body(const KParams& p, v4f* s_ring) {
 template <bool STATS, bool MULTI, int WAVES = RB_TRACE_WAVES>
 __global__ void __launch_bounds__(kTraceBlock, WAVES) k_trace(const KParams p) {
     __shared__ __attribute__((aligned(16))) v4f s_ring[(kTraceBlock / 64u) * kRingRows * 64u];
-    trace_body<STATS, MULTI, !MULTI>(p, s_ring);
+    // the counting build of the per-segment ablation keeps the two scatter normalizes: one costs it 6 more spilled registers
+    trace_body<STATS, MULTI, !MULTI, !(STATS && MULTI)>(p, s_ring);
 }
 template <bool STATS, bool MULTI, int WAVES = RB_TRACE_WAVES>
 __global__ void __launch_bounds__(kTraceBlock, WAVES) k_trace_direct(const KParams p) {
     __shared__ __attribute__((aligned(16))) v4f s_ring[(kTraceBlock / 64u) * kRingRows * 64u];
-    trace_body<STATS, MULTI, false>(p, s_ring);
+    // the default instantiations keep the two scatter normalizes: with one, the 8-wave one spills 4 registers where it spilled
+    // none, and the 6-wave one goes from 64 registers (8 waves resident) to 68 (7)
+    trace_body<STATS, MULTI, false, STATS || MULTI>(p, s_ring);
 }
 
 // k_trace for multi-node BVHs.  With 128-triangle leaves and no t-culling (the reference's
@@ -986,8 +989,9 @@ struct TriangleWalkPolicy {
     DEV void init(const KParams& p) { w.begin(p, mk(0, 0, 0), mk(0, 0, 1)); }
     DEV void begin(const KParams& p, const Path& pt, uint32_t*, Tally<STATS>&) { w.begin(p, pt.o, pt.d); }
     DEV bool finish(const KParams& p, Path& pt, uint32_t* stack, Tally<STATS>& tl) {
-        // the counting build keeps the rejection loop as it was: any change to the try costs it 6 more spilled registers (4 B of scratch)
-        return segment_finish<STATS, true, !STATS>(p, pt, w.h, stack, kTraceBlock, tl);
+        // the counting build keeps the rejection loop as it was: any change to the try costs it 6 more spilled registers (4 B of scratch);
+        // likewise the two scatter normalizes (one: 6 more)
+        return segment_finish<STATS, true, !STATS, !STATS>(p, pt, w.h, stack, kTraceBlock, tl);
     }
 };
 template <bool STATS, class Walk>
