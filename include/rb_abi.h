@@ -502,6 +502,10 @@ int rb_debug_walk_profile(uint64_t out64[64], int reset);
 /* Test hook: checks the kernels' fast exact reciprocal against the compiler's correctly rounded
  * 1/b for all 2^23 significands (both signs) at one biased exponent; out16[0] = mismatch count. */
 int rb_debug_rcp_exhaustive(uint32_t biased_exponent, uint32_t* out16);
+/* Test hook: the same sweep for the reciprocal of the single-node walk's triangle test with its guard (both of its ways):
+ * all 2^23 significands and both signs at one biased exponent (0..255) against 1.0f / x, bit patterns compared, a NaN equal to
+ * a NaN; out16[0] = mismatch count, out16[1..15] = some offending bit patterns. */
+int rb_debug_rcp_det_exhaustive(uint32_t biased_exponent, uint32_t* out16);
 /* Test hook: checks the kernels' one-rounding `rnd(seed) * 2 - 1` (one fma) against the shader's three operations on all
  * 2^32 seeds; out16[0] = number of seeds whose value differs, out16[1..15] = some of them. */
 int rb_debug_rnd_pm1_exhaustive(uint32_t* out16);

@@ -81,6 +81,7 @@ def load():
         "rb_debug_math": (i32, [vp, vp, vp, u32]),
         "rb_debug_walk_profile": (i32, [vp, i32]),
         "rb_debug_rcp_exhaustive": (i32, [u32, vp]),
+        "rb_debug_rcp_det_exhaustive": (i32, [u32, vp]),
         "rb_debug_rnd_pm1_exhaustive": (i32, [vp]),
         "rb_debug_div_exhaustive": (i32, [u32, u32, u32, u32, u32, u32, vp]),
         "rb_last_kernel_name": (C.c_char_p, [vp]),
@@ -148,7 +149,7 @@ EXPORTS = ["rb_create", "rb_create_ex", "rb_create_multi", "rb_comm_available", 
            "rb_iter_begin", "rb_iter_has_next", "rb_iter_next", "rb_iter_destroy", "rb_iter_set_passes_per_frame", "rb_last_error",
            "rb_get_size", "rb_clear", "rb_dispatch", "rb_reserve", "rb_sync", "rb_read_rgba", "rb_read_accumulation",
            "rb_device_rgba", "rb_host_alloc", "rb_host_free", "rb_local_rows", "rb_global_row", "rb_shard_layout", "rb_shard_global_row", "rb_get_stats", "rb_reset_stats",
-           "rb_last_dispatch_ms", "rb_bvh_build", "rb_bvh_build_canonical", "rb_bvh_build_device", "rb_engine_tree", "rb_tree_builder", "rb_debug_chunk_tree", "rb_measure_l1_gather", "rb_debug_math", "rb_debug_walk_profile", "rb_debug_rcp_exhaustive", "rb_debug_rnd_pm1_exhaustive", "rb_debug_div_exhaustive", "rb_last_kernel_name", "rb_cast_rays", "rb_render_hits", "rb_pick", "rb_occluded", "rb_occluded_device", "rb_cast_rays_device", "rb_trace_rays", "rb_trace_rays_device", "rb_last_query_kernel_name", "rb_last_query_ms",
+           "rb_last_dispatch_ms", "rb_bvh_build", "rb_bvh_build_canonical", "rb_bvh_build_device", "rb_engine_tree", "rb_tree_builder", "rb_debug_chunk_tree", "rb_measure_l1_gather", "rb_debug_math", "rb_debug_walk_profile", "rb_debug_rcp_exhaustive", "rb_debug_rcp_det_exhaustive", "rb_debug_rnd_pm1_exhaustive", "rb_debug_div_exhaustive", "rb_last_kernel_name", "rb_cast_rays", "rb_render_hits", "rb_pick", "rb_occluded", "rb_occluded_device", "rb_cast_rays_device", "rb_trace_rays", "rb_trace_rays_device", "rb_last_query_kernel_name", "rb_last_query_ms",
            "rb_camera_rays", "rb_trace_camera", "rb_trace_camera_device", "rb_last_camera_rays_ms",
            "rb_hemisphere_rays", "rb_trace_hemisphere", "rb_trace_hemisphere_device", "rb_openness_hemisphere", "rb_openness_hemisphere_device",
            "rb_lightmap_surfels", "rb_lightmap_surfels_device", "rb_lightmap_resolve", "rb_bake_lightmap", "rb_bake_lightmap_device", "rb_last_lightmap_ms",

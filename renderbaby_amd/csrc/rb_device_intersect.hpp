@@ -160,12 +160,15 @@ DEV void test_slot(const v4f a, const v4f b, const v4f c, uint32_t slot, f3 o, f
 // no -1 is handed back through the four early-outs to be compared with 0.001 and h.t once more.  hit.hit is left alone:
 // carried through the loop it is a lane mask in two scalar registers that every join of the early-outs merges again;
 // the caller sets it once from hit.t, which leaves its initial 1e20 exactly when a triangle is accepted (t < hit.t).
+// DET: 1/det through rcp_det's two-compare guard (the kernels of single-node trees); false keeps rcp_tri, same bits, so that
+// the register allocation of the multi-node kernels, which carry this loop too, does not move.
+template <bool DET = false>
 DEV void accept_slot(const v4f a, const v4f b, const v4f c, uint32_t slot, f3 o, f3 d, TriHit& hit) {
     const f3 v0 = mk(a.x, a.y, a.z), edge1 = mk(b.x, b.y, b.z), edge2 = mk(c.x, c.y, c.z);
     const f3 h = cross(d, edge2);
     const float det = dot(edge1, h);
     if (!(fabsf(det) < 1e-6f)) {
-        const float f = rcp_tri(det);
+        const float f = DET ? rcp_det(det) : rcp_tri(det);
         const f3 s = o - v0;
         const float u = f * dot(s, h);
         if (!(u < 0.0f || u > 1.0f)) {
@@ -564,7 +567,7 @@ DEV TriHit intersect_bvh(const KParams& p, f3 o, f3 d, uint32_t* stack, uint32_t
                 if (live) {
                     if constexpr (STATS) tl.tris++;
                     const float before = h.t;
-                    accept_slot(a, b, c, slot, o, d, h);
+                    accept_slot<!MULTI>(a, b, c, slot, o, d, h);
                     if constexpr (STATS) tl.mesh_hits += (h.t != before) ? 1u : 0u;
                 }
                 if (slot == last) break;

@@ -135,6 +135,29 @@ DEV float rcp_tri(float a) {
     return 1.0f / a;
 }
 
+// rcp_tri for the single-node walk's triangle loop (accept_slot), where its guard is issued for every lane of every trip: the
+// same two ways to the same bits, chosen by two compares without a mask.  |a| < 2^100 as a float compare (the abs is an
+// operand modifier; a NaN fails it and takes the division), and the low half of the bits not all ones as a 16-bit compare:
+// that sends one significand in 65 536 to `1.0f / a` where rcp_tri sends one in 2^23, which is the value either way.  The
+// 16-bit compare is written as the plain VOPC instruction on the register's low half: for `(uint16_t)bits != 0xFFFF` the
+// compiler picks the SDWA form of the 32-bit compare, which measured slower than the two masks it replaces
+// (profiles/r20_c2_bench_ab.txt).  Both lane masks are joined by the scalar unit and handed back as the branch's condition,
+// so the exec mask is split once.  Checked against `1.0f / a` by rb_debug_rcp_det_exhaustive.
+#ifndef RB_RCP_DET
+#define RB_RCP_DET 1   // 0: accept_slot calls rcp_tri, for the A/B builds of profiles/r20_c2_bench_ab.txt
+#endif
+DEV float rcp_det(float a) {
+#if RB_FAST_RCP && RB_RCP_DET
+    uint64_t ones;
+    asm("v_cmp_eq_u16_e64 %0, -1, %1" : "=s"(ones) : "v"(__float_as_uint(a)));
+    const uint64_t large = __builtin_amdgcn_fcmpf(__builtin_fabsf(a), 0x1p100f, 11 /* FCMP_UGE: !(|a| < 2^100) */);
+    if (__builtin_amdgcn_inverse_ballot_w64(large | ones)) return 1.0f / a;
+    return rcp_newton(a);
+#else
+    return rcp_tri(a);
+#endif
+}
+
 // WGSL u32(f32) / i32(f32): truncate + saturate, NaN -> 0
 DEV uint32_t f2u(float f) {
     if (!(f > 0.0f)) return 0u;

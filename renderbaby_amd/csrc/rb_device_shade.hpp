@@ -244,7 +244,34 @@ DEV SegState segment_pre(const KParams& p, const Path& pt, const TriHit th, Tall
 // Spheres, shader.wgsl:574-586 -- per-segment form (the sphere tree run to completion, or the scan)
 // SPHTREE = false: an instantiation for launches without a sphere tree (at most 64 spheres): the tree's walk, with its 32
 // registers of node, stays out of the kernel's register allocation (k_trace for C2: 32 spilled registers with it, 4 without)
-template <bool STATS, bool SPHTREE = true>
+// LEAN (the kernels of single-node trees; DESIGN.md sections 4 and 9, r20): the same scan without the bookkeeping the vector unit
+// paid per sphere.  The trip count sits in a scalar register, so the loop's compare is a scalar one; a block's spheres are
+// walked from the last to the first and each one's bit is shifted in at the bottom (cand = 2 * cand + bit: one add with
+// carry), which leaves sphere k at bit k as before, so pass 2 below is the same ascending walk with the same strict `<`;
+// {centre, radius^2} comes from the 16-byte scan records (KParams::sph_scan: radius * radius rounded once, when the
+// spheres were uploaded, to the value the product below rounds to).  Pass 2 and the shading read the caller's records.
+#ifndef RB_SCAN_LEAN
+#define RB_SCAN_LEAN 1     // 0: every kernel keeps the ascending scan, for the A/B builds of profiles/r20_c2_bench_ab.txt
+#endif
+#ifndef RB_SCAN_RECORD
+#define RB_SCAN_RECORD 1   // 0: the lean scan reads the caller's {centre, radius} and squares the radius itself
+#endif
+#ifndef RB_PASS2_MAD24
+#define RB_PASS2_MAD24 1   // 0: pass 2 forms index * 6 with the 32-bit multiplier
+#endif
+// cand = 2 * cand + !(disc < 0) in one vector instruction: the compare's lane mask is the add's carry-in.  (Written as
+// C++ the compiler selects 0 / 1 into a register first and shifts-and-ors it in: two instructions.)
+// The discriminant's sign is taken from its two terms: x - y < 0 exactly when x < y (subnormals are kept, so a difference
+// rounds to zero only from equal terms; inf - inf and a NaN term fail both), which is also how the compiler tests the
+// ascending scan's `disc < 0`.
+DEV uint32_t shift_in_ge0(uint32_t cand, float x, float y) {
+    const uint64_t ge = __builtin_amdgcn_fcmpf(x, y, 11 /* FCMP_UGE: !(x - y < 0) */);
+    uint32_t out;
+    uint64_t carry;
+    asm("v_addc_co_u32 %0, %1, %2, %2, %3" : "=v"(out), "=s"(carry) : "v"(cand), "s"(ge));
+    return out;
+}
+template <bool STATS, bool SPHTREE = true, bool LEAN = false>
 DEV void segment_spheres(const KParams& p, f3 o, f3 d, float a, float& closest_t, uint32_t& sphere_idx, uint32_t* stack,
                          uint32_t stride, Tally<STATS>& tl) {
     const uint32_t ns = p.u.spheres_count;
@@ -257,23 +284,42 @@ DEV void segment_spheres(const KParams& p, f3 o, f3 d, float a, float& closest_t
             return;
         }
     }
+    constexpr bool lean = LEAN && RB_SCAN_LEAN != 0;
+    constexpr bool record = lean && RB_SCAN_RECORD != 0;
     for (uint32_t base = 0; base < ns; base += 32u) {
-        const uint32_t n = (ns - base < 32u) ? ns - base : 32u;
         uint32_t cand = 0u;
-        cf4p sp_ = sph4 + (size_t)base * 6u;
-        for (uint32_t k = 0; k < n; k++, sp_ += 6) {
-            const v4f cr = sp_[0];
-            if constexpr (STATS) tl.spheres++;
-            const f3 oc = o - mk(cr.x, cr.y, cr.z);
-            const float half_b = dot(oc, d);
-            const float c = dot(oc, oc) - cr.w * cr.w;
-            const float disc = half_b * half_b - a * c;
-            cand |= (disc < 0.0f) ? 0u : (1u << k);
+        if constexpr (lean) {
+            const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)((ns - base < 32u) ? ns - base : 32u));
+            constexpr uint32_t step = record ? 1u : 6u;
+            cf4p sp_ = (record ? (cf4p)p.sph_scan : sph4) + (size_t)(base + n) * step;   // one past the block's last sphere
+            for (uint32_t k = n; k != 0u; k--) {
+                sp_ -= step;
+                const v4f cr = sp_[0];
+                if constexpr (STATS) tl.spheres++;
+                const f3 oc = o - mk(cr.x, cr.y, cr.z);
+                const float half_b = dot(oc, d);
+                const float c = dot(oc, oc) - (record ? cr.w : cr.w * cr.w);
+                cand = shift_in_ge0(cand, half_b * half_b, a * c);   // disc = half_b * half_b - a * c; bit = !(disc < 0)
+            }
+        } else {
+            const uint32_t n = (ns - base < 32u) ? ns - base : 32u;
+            cf4p sp_ = sph4 + (size_t)base * 6u;
+            for (uint32_t k = 0; k < n; k++, sp_ += 6) {
+                const v4f cr = sp_[0];
+                if constexpr (STATS) tl.spheres++;
+                const f3 oc = o - mk(cr.x, cr.y, cr.z);
+                const float half_b = dot(oc, d);
+                const float c = dot(oc, oc) - cr.w * cr.w;
+                const float disc = half_b * half_b - a * c;
+                cand |= (disc < 0.0f) ? 0u : (1u << k);
+            }
         }
         while (cand != 0u) {
             const uint32_t k = (uint32_t)__ffs((int)cand) - 1u;
             cand &= cand - 1u;
-            const v4f cr = sph4[(base + k) * 6u];
+            // index * 6 without the quarter-rate 32-bit multiplier: k < 32 goes through the 24-bit one, the block's records
+            // start at a scalar address
+            const v4f cr = (LEAN && RB_PASS2_MAD24 != 0) ? (sph4 + (size_t)base * 6u)[__umul24(k, 6u)] : sph4[(base + k) * 6u];
             const float t = isect_sphere(o, d, a, mk(cr.x, cr.y, cr.z), cr.w);
             if (t > 0.001f && t < closest_t) {
                 closest_t = t;
@@ -554,13 +600,13 @@ DEV void segment_resolve(const KParams& p, f3 o, f3 d, const TriHit th, const Se
 }
 
 // One iteration of the bounce loop after the triangle traversal (`th`: its winner).
-template <bool STATS, bool SPHTREE = true, bool PARK = true, bool JOINED = true>
+template <bool STATS, bool SPHTREE = true, bool PARK = true, bool JOINED = true, bool LEAN = false>
 DEV bool segment_finish(const KParams& p, Path& pt, const TriHit th, uint32_t* stack, uint32_t stride,
                         Tally<STATS>& tl) {
     const SegState st = segment_pre<STATS>(fresh_params(p), pt, th, tl);
     float closest_t = st.closest_t;
     uint32_t sphere_idx = 0xFFFFFFFFu;
-    segment_spheres<STATS, SPHTREE>(fresh_params(p), pt.o, pt.d, dot(pt.d, pt.d), closest_t, sphere_idx, stack, stride, tl);
+    segment_spheres<STATS, SPHTREE, LEAN>(fresh_params(p), pt.o, pt.d, dot(pt.d, pt.d), closest_t, sphere_idx, stack, stride, tl);
     return segment_post<STATS, PARK, JOINED>(fresh_params(p), pt, th, st, closest_t, sphere_idx, tl);
 }
 
@@ -569,7 +615,7 @@ DEV bool segment_finish(const KParams& p, Path& pt, const TriHit th, uint32_t* s
 template <bool STATS, bool MULTI = true, bool JOINED = true>
 DEV bool segment(const KParams& p, Path& pt, uint32_t* stack, uint32_t stride, Tally<STATS>& tl) {
     const TriHit th = intersect_bvh<STATS, MULTI>(fresh_params(p), pt.o, pt.d, stack, stride, tl);
-    return segment_finish<STATS, MULTI, true, JOINED>(p, pt, th, stack, stride, tl);
+    return segment_finish<STATS, MULTI, true, JOINED, !MULTI>(p, pt, th, stack, stride, tl);
 }
 
 // ----------------------------------------------------------------- camera --

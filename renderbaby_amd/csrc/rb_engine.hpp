@@ -135,6 +135,7 @@ struct rb_engine {
     uint32_t prep_tri_count = 0xFFFFFFFFu;  // uniforms.bvh_triangle_count (patched) the prepared triangles were made for
 
     rb::DevBuf<rb_sphere> spheres;
+    rb::DevBuf<float> sph_scan;      // float4 {centre, radius * radius} per sphere of `spheres`, remade whenever those are taken (KParams::sph_scan)
     rb::DevBuf<rb_point_light> lights;
     rb::DevBuf<rb_mesh> meshes;
     rb::DevBuf<rb_bvh_node> nodes;

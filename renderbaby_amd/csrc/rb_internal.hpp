@@ -355,6 +355,7 @@ struct KParams {
     uint32_t magic_S, magic_tiles_x; // floor(2^32 / d) for the item decode of the stream kernels (set by launch_render)
     uint32_t* stack_overflow;      // fast walk: entries beyond kStackDepth, [entry][grid * block] (nullptr if never needed)
     Cam cam;                       // set by launch_render
+    const float* sph_scan;         // float4 {centre, radius * radius} per sphere, caller's order: pass 1 of the lean sphere scan
 };
 
 struct LaunchInfo {
@@ -504,6 +505,7 @@ int launch_accumulate(const KParams& p, void* stream);
 int launch_prep_tris(const rb_gpu_triangle* tris, uint32_t tri_count, const uint32_t* indices,
                      uint32_t index_len, PrepTri* out, PrepTriShade* shade, void* stream);
 int launch_prep_materials(void* first_material, uint32_t stride, uint32_t n, void* stream);
+int launch_prep_sphere_scan(const rb_sphere* spheres, uint32_t n, float* out, void* stream);   // float4 {centre, radius^2} per sphere
 int launch_gather_tris(const PrepTri* ptris, const uint32_t* slots, uint32_t n, PrepTri* out, void* stream);
 // prepared triangles -> the chunked walk's three float4 arrays in chunk order (A: v0 | rank, B: e1, C: e2)
 int launch_chunk_gather(const PrepTri* ptris, const uint32_t* pos_slot, const uint32_t* pos_rank, uint32_t n, float* a,
@@ -516,6 +518,7 @@ size_t max_dynamic_lds(int device);   // hipDeviceAttributeMaxSharedMemoryPerBlo
 int launch_div_exhaustive(uint32_t b_begin, uint32_t b_count, uint32_t ea, uint32_t eb, uint32_t a_begin,
                           uint32_t a_count, unsigned long long* mismatch16, void* stream);
 int launch_rcp_exhaustive(uint32_t expo, uint32_t* mismatch16, void* stream);
+int launch_rcp_det_exhaustive(uint32_t expo, uint32_t* mismatch16, void* stream);
 int launch_rnd_pm1_exhaustive(uint32_t* mismatch16, void* stream);
 int launch_debug_math(const float* a, const float* b, float* out, uint32_t n, void* stream);
 int debug_walk_profile(unsigned long long* out64, int reset);   // pass occupancy counters of a profiling build, tools/ablate/rb_profile.patch (-1 otherwise)

@@ -1461,6 +1461,15 @@ __global__ void k_prep_materials(unsigned char* first_material, uint32_t stride,
     m->_pad2 = is_metal ? 1u : 0u;
 }
 
+// The lean sphere scan's records (segment_spheres, pass 1): {centre, radius * radius} per sphere, 16 bytes each, in the
+// caller's order.  The product is the one f32 multiply every lane used to make per sphere and segment.
+__global__ void k_prep_sphere_scan(const rb_sphere* spheres, uint32_t n, float4* out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const v4f cr = ((cf4p)(spheres + i))[0];
+    out[i] = make_float4(cr.x, cr.y, cr.z, cr.w * cr.w);
+}
+
 // Copies prepared triangles into the fast tree's leaf order.
 __global__ void k_gather_tris(const PrepTri* ptris, const uint32_t* slots, uint32_t n, PrepTri* out) {
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1513,6 +1522,23 @@ __global__ void k_rcp_exhaustive(uint32_t expo, uint32_t* mismatch) {
             got = rcp_newton(b);
         }
         if (__float_as_uint(want) != __float_as_uint(got)) {
+            const uint32_t k = atomicAdd(&mismatch[0], 1u);
+            if (k < 15u) mismatch[1u + k] = bits;
+        }
+    }
+}
+
+// Exhaustive check of rcp_det, guard and both of its ways, against the compiler's correctly rounded 1/b: every one of the
+// 2^23 significands at biased exponent `expo`, both signs.  A NaN equals a NaN.  mismatch[0] counts differing results;
+// mismatch[1..] records up to 15 offending bit patterns.
+__global__ void k_rcp_det_exhaustive(uint32_t expo, uint32_t* mismatch) {
+    const uint32_t m = blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= (1u << 23)) return;
+    for (uint32_t sign = 0; sign < 2; sign++) {
+        const uint32_t bits = (sign << 31) | ((expo & 0xFFu) << 23) | m;
+        const float b = __uint_as_float(bits);
+        const float want = 1.0f / b, got = rcp_det(b);
+        if (__float_as_uint(want) != __float_as_uint(got) && !(want != want && got != got)) {
             const uint32_t k = atomicAdd(&mismatch[0], 1u);
             if (k < 15u) mismatch[1u + k] = bits;
         }
@@ -1865,6 +1891,13 @@ int launch_prep_materials(void* first_material, uint32_t stride, uint32_t n, voi
     return (int)hipGetLastError();
 }
 
+int launch_prep_sphere_scan(const rb_sphere* spheres, uint32_t n, float* out, void* stream_) {
+    if (n == 0) return 0;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    hipLaunchKernelGGL(k_prep_sphere_scan, dim3((n + 255) / 256), dim3(256), 0, stream, spheres, n, reinterpret_cast<float4*>(out));
+    return (int)hipGetLastError();
+}
+
 int launch_gather_tris(const PrepTri* ptris, const uint32_t* slots, uint32_t n, PrepTri* out, void* stream_) {
     if (n == 0) return 0;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
@@ -1913,6 +1946,12 @@ int launch_rnd_pm1_exhaustive(uint32_t* mismatch, void* stream_) {
 int launch_rcp_exhaustive(uint32_t expo, uint32_t* mismatch, void* stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     hipLaunchKernelGGL(k_rcp_exhaustive, dim3((1u << 23) / 256), dim3(256), 0, stream, expo, mismatch);
+    return (int)hipGetLastError();
+}
+
+int launch_rcp_det_exhaustive(uint32_t expo, uint32_t* mismatch, void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    hipLaunchKernelGGL(k_rcp_det_exhaustive, dim3((1u << 23) / 256), dim3(256), 0, stream, expo, mismatch);
     return (int)hipGetLastError();
 }
 

@@ -184,6 +184,16 @@ int upload_textures(rb_engine* e, const rb_field& f) {
     return RB_OK;
 }
 
+// The lean scan's records of the spheres just uploaded (one per element of e->spheres, the zero-filled element of an
+// empty field included, so that no count a launch may carry reads past them).
+int prep_sphere_scan(rb_engine* e) {
+    const size_t n = e->spheres.count;
+    HIP_TRY(e, e->sph_scan.resize(n * 4));
+    int rc = rb::launch_prep_sphere_scan(e->spheres.ptr, static_cast<uint32_t>(n), e->sph_scan.ptr, e->stream);
+    if (rc) return rb::fail(e, RB_ERR_DEVICE, "sphere scan prep launch failed: %s", hipGetErrorString(static_cast<hipError_t>(rc)));
+    return RB_OK;
+}
+
 int prep_materials(rb_engine* e, rb_material* first, size_t stride, size_t n) {
     if (!first || n == 0) return RB_OK;
     int rc = rb::launch_prep_materials(first, static_cast<uint32_t>(stride), static_cast<uint32_t>(n), e->stream);
@@ -215,6 +225,7 @@ int apply_field(rb_engine* e, int idx, const rb_field& f, bool first) {
             rc = rb::upload(e, e->spheres, src, n, nullptr, true);
             e->n_spheres = static_cast<uint32_t>(n);
             if (!rc) rc = prep_materials(e, e->spheres.ptr ? &e->spheres.ptr->material : nullptr, sizeof(rb_sphere), n);
+            if (!rc) rc = prep_sphere_scan(e);
             if (!rc) rc = rb::build_sphere_bvh(e, static_cast<const rb_sphere*>(src), n);
             break;
         case 2: rc = rb::upload(e, e->uvs, src, n, nullptr, true); e->n_uvs = static_cast<uint32_t>(n); break;
@@ -395,6 +406,7 @@ rb::KParams rb::make_params(rb_engine* e, uint32_t first_pass, uint32_t n_passes
     p.u.bvh_node_count = patch_count(e->last_change_nodes, e->uniforms.bvh_node_count, e->n_nodes);
     p.u.bvh_triangle_count = patch_count(e->last_change_tris, e->uniforms.bvh_triangle_count, e->n_tris);
     p.spheres = e->spheres.ptr;
+    p.sph_scan = e->sph_scan.ptr;
     p.lights = e->lights.ptr;
     p.meshes = e->meshes.ptr;
     p.nodes = e->nodes.ptr;
@@ -1505,6 +1517,21 @@ int rb_debug_rcp_exhaustive(uint32_t biased_exponent, uint32_t* out16) {
     if (hipMalloc(reinterpret_cast<void**>(&d), 64) != hipSuccess) return RB_ERR_DEVICE;
     (void)hipMemset(d, 0, 64);
     int rc = rb::launch_rcp_exhaustive(biased_exponent, d, nullptr);
+    hipError_t st = hipDeviceSynchronize();
+    (void)hipMemcpy(out16, d, 64, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    return (rc || st != hipSuccess) ? RB_ERR_DEVICE : RB_OK;
+}
+
+// Test hook: the same sweep for rcp_det, the reciprocal of the single-node walk's triangle test, guard included: every
+// significand and both signs at one biased exponent against `1.0f / x`, bit patterns compared (a NaN equals a NaN).
+int rb_debug_rcp_det_exhaustive(uint32_t biased_exponent, uint32_t* out16) {
+    if (!out16) return RB_ERR_NULL_ARGUMENT;
+    if (biased_exponent > 255u) return RB_ERR_INVALID_OPTIONS;
+    uint32_t* d = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&d), 64) != hipSuccess) return RB_ERR_DEVICE;
+    (void)hipMemset(d, 0, 64);
+    int rc = rb::launch_rcp_det_exhaustive(biased_exponent, d, nullptr);
     hipError_t st = hipDeviceSynchronize();
     (void)hipMemcpy(out16, d, 64, hipMemcpyDeviceToHost);
     (void)hipFree(d);
