@@ -816,6 +816,58 @@ int rb_bake_lightmap_device(rb_engine* e, const rb_lightmap_params* params, uint
  * recent lightmap call; a stage the call did not run reports 0.  Either pointer may be NULL. */
 int rb_last_lightmap_ms(rb_engine* e, float* surfels_ms, float* resolve_ms);
 
+/* ---- Irradiance probes made on the device (the normative definition; no reference counterpart).  n points
+ * in free space in, n records of SH9 sums out -- nine real spherical-harmonic coefficients (bands 0-2) per colour channel of
+ * the radiance arriving from every direction: a device stage makes the uniform-sphere ray of every (probe, sample) item from
+ * the item's own random stream, the kernels of rb_trace_rays walk it, and a second stage folds each item's colour with the
+ * basis of the item's own direction.  Every step is one IEEE binary32 operation in the order written, no contraction, / and
+ * sqrt correctly rounded: the numpy model renderbaby_amd/probes.py equals the device bit for bit.  For probe i of n and sample
+ * k of `samples`:
+ *   pos    = probes[i].pos; the probe is invalid if a component is non-finite, and then so is every sample of it;
+ *   sid    = seeds ? seeds[i] : (uint32_t)i;  seed = pcg(sid + pcg(first_sample + k)), u32 wrap-around: rb_trace_rays' rule;
+ *   u1, u2 = random_float(&seed), twice: always exactly two draws, either may be exactly 1.0f;
+ *   (s, c) = sincos_turn(u1 * 2.0f - 1.0f) (section 15.3);  z = 1.0f - (u2 + u2);  r = sqrt(1.0f - z * z);
+ *   d      = (r * c, r * s, z) normalised as rb_cast_rays does it: world axes, no frame;  the origin is pos, no offset;
+ *   a sample is invalid by rb_cast_rays' rule, and its record is {pos as given, 0 0 0};
+ *   c(i,k) = trace_ray(scene, pos, d, seed) with the seed as the two draws left it;
+ *   Y0 = 0.282094792f;  Y1 = 0.488602512f * d.y;  Y2 = 0.488602512f * d.z;  Y3 = 0.488602512f * d.x;
+ *   Y4 = 1.09254843f * (d.x * d.y);  Y5 = 1.09254843f * (d.y * d.z);  Y6 = 0.315391565f * (3.0f * (d.z * d.z) - 1.0f);
+ *   Y7 = 1.09254843f * (d.x * d.z);  Y8 = 0.546274215f * (d.x * d.x - d.y * d.y), d as stored in the item's record;
+ *   out[i].sum[j][ch]: from +0.0f in ascending k, += c(i,k)[ch] * Yj (one multiply, one add); out[i].weight counts the valid
+ *   samples; an invalid sample leaves every sum's bits as they were; max_depth == 0 gives all-zero sums with the weight set.
+ * The radiance coefficient is L_j = (4 pi / weight) sum[j]: the division is the caller's, so that sums can be accumulated over
+ * calls with first_sample.  The side effects are a query's.  The result does not depend on the piece size, the launch shape or
+ * the form of the call. */
+typedef struct rb_probe { float pos[3]; float _pad; } rb_probe;                                     /* 16 B */
+typedef struct rb_sh9 { float sum[9][3]; float weight; } rb_sh9;                                    /* 112 B */
+/* (probe, sample) items per launch, as RB_HEMI_PIECE_ITEMS */
+enum { RB_PROBE_PIECE_ITEMS = 1u << 23 };
+/* The generator alone, no engine, on `device` (-1 = current): host arrays; rays_out[i * samples + k] as rb_hemisphere_rays
+ * writes it, and the seed trace_ray starts with in seeds_out[i * samples + k] or, with seeds_out NULL, as the bits of the
+ * record's fourth word.  RB_ERR_INVALID_OPTIONS, before any device is touched: samples 0 or above 65536; first_sample + samples
+ * beyond 2^32 - 1; n > 2^31 - 64 or n * samples above 2^31 - 64.  NULL probes or rays_out with n > 0: RB_ERR_NULL_ARGUMENT.
+ * n == 0 is RB_OK. */
+int rb_probe_rays(int32_t device, const rb_probe* probes, const uint32_t* seeds, size_t n, uint32_t first_sample, uint32_t samples,
+                  rb_ray* rays_out, uint32_t* seeds_out);
+/* The bake: probes[n], seeds[n] (may be NULL) and out[n] in host memory (pageable or page-locked).  Refusals as rb_probe_rays
+ * (NULL probes or out with n > 0: RB_ERR_NULL_ARGUMENT); a refused call leaves the engine as it was.  Pieces of at most
+ * RB_PROBE_PIECE_ITEMS items, whole blocks of 64 probes, never a part of one probe's samples.  Sharded engines and multi-device
+ * handles as rb_trace_rays.  rb_last_query_kernel_name reports "k_cam", "k_cam_bvh" or "k_cam_chunk" -- the walk by
+ * rb_cast_rays' rule --, rb_last_query_ms the generator, the trace and the projection together, rb_last_camera_rays_ms the
+ * generator's share. */
+int rb_bake_probes(rb_engine* e, const rb_probe* probes, const uint32_t* seeds, size_t n, uint32_t first_sample, uint32_t samples,
+                   rb_sh9* out);
+/* The same with d_probes and d_out (16-byte aligned) and d_seeds (may be NULL) in device memory of the engine's device,
+ * validated as rb_trace_rays_device validates its buffers; queued on the engine's stream, returns without waiting: rb_sync is
+ * the wait. */
+int rb_bake_probes_device(rb_engine* e, const rb_probe* d_probes, const uint32_t* d_seeds, size_t n, uint32_t first_sample,
+                          uint32_t samples, rb_sh9* d_out);
+
+/* Measurement aid for tools/probe_rate.py (it may change or go): the share of the projection in the kernel time of the most
+ * recent rb_bake_probes / rb_bake_probes_device, HIP events around its launches, summed over the pieces, ms.  It waits for the
+ * launches it reports. */
+int rb_last_probe_project_ms(rb_engine* e, float* ms);
+
 /* ---- Edge-avoiding denoiser over the first-hit buffers (no reference counterpart).  An a-trous wavelet
  * filter (Dammertz et al. 2010) on the albedo-demodulated mean radiance, guided by the first hit of every pixel-centre ray.
  * Section 13 is the normative definition: every step one IEEE binary32 operation in a fixed order, so that the device's result
@@ -930,6 +982,9 @@ static_assert(sizeof(rb_hemi_params) == 32, "rb_hemi_params is 32 B");
 static_assert(sizeof(rb_openness) == 8, "rb_openness is 8 B");
 static_assert(sizeof(rb_lightmap_params) == 32, "rb_lightmap_params is 32 B");
 static_assert(offsetof(rb_lightmap_params, offset) == 16, "offset @16");
+static_assert(sizeof(rb_probe) == 16, "rb_probe is 16 B");
+static_assert(sizeof(rb_sh9) == 112, "rb_sh9 is 112 B");
+static_assert(offsetof(rb_sh9, weight) == 108, "weight @108");
 static_assert(sizeof(rb_guide) == 48, "rb_guide is 48 B");
 static_assert(sizeof(rb_denoise_params) == 32, "rb_denoise_params is 32 B");
 static_assert(offsetof(rb_guide, t) == 12, "t @12");
@@ -958,6 +1013,8 @@ _Static_assert(sizeof(rb_surfel) == 32, "rb_surfel is 32 B");
 _Static_assert(sizeof(rb_hemi_params) == 32, "rb_hemi_params is 32 B");
 _Static_assert(sizeof(rb_openness) == 8, "rb_openness is 8 B");
 _Static_assert(sizeof(rb_lightmap_params) == 32, "rb_lightmap_params is 32 B");
+_Static_assert(sizeof(rb_probe) == 16, "rb_probe is 16 B");
+_Static_assert(sizeof(rb_sh9) == 112, "rb_sh9 is 112 B");
 _Static_assert(sizeof(rb_guide) == 48, "rb_guide is 48 B");
 _Static_assert(sizeof(rb_denoise_params) == 32, "rb_denoise_params is 32 B");
 #endif

@@ -297,6 +297,19 @@ class Engine final : public Renderer {
     void bake_lightmap_device(const rb_lightmap_params& p, float* d_rgba, rb_radiance* d_sums, uint32_t samples, uint32_t first_sample = 0) {
         check(h_->e, rb_bake_lightmap_device(h_->e, &p, first_sample, samples, d_rgba, d_sums));
     }
+    // ---- irradiance probes made on the device (extension; rb_abi.h): per probe the ordered SH9 sums over
+    // `samples` uniform-sphere rays; the radiance coefficient j is (4 pi / weight) * sum[j]
+    std::vector<rb_sh9> bake_probes(const std::vector<rb_probe>& probes, uint32_t samples, uint32_t first_sample = 0,
+                                    const uint32_t* seeds = nullptr) {
+        std::vector<rb_sh9> out(probes.size());
+        check(h_->e, rb_bake_probes(h_->e, probes.data(), seeds, probes.size(), first_sample, samples, out.data()));
+        return out;
+    }
+    // the same on the engine's device memory: queued on the engine's stream -- sync() waits
+    void bake_probes_device(const rb_probe* d_probes, const uint32_t* d_seeds, size_t n, rb_sh9* d_out, uint32_t samples,
+                            uint32_t first_sample = 0) {
+        check(h_->e, rb_bake_probes_device(h_->e, d_probes, d_seeds, n, first_sample, samples, d_out));
+    }
     void sync() { check(h_->e, rb_sync(h_->e)); }
     // ---- the denoiser (rb_abi.h): the a-trous filter over the committed accumulation
     static rb_denoise_params denoise_defaults() {

@@ -71,6 +71,11 @@ LIGHTMAP_PARAMS = np.dtype([("width", u4), ("height", u4), ("mesh", u4), ("flags
                             ("_reserved", u4, (2,))])
 LIGHTMAP_ALL_MESHES, LIGHTMAP_NO_OWNER, LIGHTMAP_FLIP = 0xFFFFFFFF, 0xFFFFFFFF, 1
 LIGHTMAP_MAX_SIDE, LIGHTMAP_MAX_DILATE = 16384, 64
+# irradiance probes made on the device (rb_probe_rays / rb_bake_probes): a point in free space and the
+# ordered SH9 sums of its samples, sum[j][channel], with the number of valid samples behind
+PROBE = np.dtype([("pos", f4, (3,)), ("_pad", f4)])
+SH9 = np.dtype([("sum", f4, (9, 3)), ("weight", f4)])
+PROBE_PIECE_ITEMS = 1 << 23
 # any-hit occlusion (rb_occluded): result bytes and stage masks
 OCCL_VISIBLE, OCCL_OCCLUDED, OCCL_INVALID = 0, 1, 255
 MASK_GROUND, MASK_TRIANGLES, MASK_SPHERES, MASK_LIGHTS, MASK_ALL = 1, 2, 4, 8, 15
@@ -85,7 +90,7 @@ SIZES = {"camera": (CAMERA, 48), "uniforms": (UNIFORMS, 144), "material": (MATER
          "ray": (RAY, 32), "hit": (HIT, 48), "surface": (SURFACE, 48),
          "guide": (GUIDE, 48), "denoise_params": (DENOISE_PARAMS, 32), "camera_ex": (CAMERA_EX, 96),
          "surfel": (SURFEL, 32), "hemi_params": (HEMI_PARAMS, 32), "openness": (OPENNESS, 8),
-         "lightmap_params": (LIGHTMAP_PARAMS, 32)}
+         "lightmap_params": (LIGHTMAP_PARAMS, 32), "probe": (PROBE, 16), "sh9": (SH9, 112)}
 for _n, (_dt, _sz) in SIZES.items():
     assert _dt.itemsize == _sz, (_n, _dt.itemsize, _sz)
 

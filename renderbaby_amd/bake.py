@@ -4,6 +4,8 @@
 ``irradiance``   mean radiance over cosine-weighted directions about a normal: lightmap texels, vertices, probes
 ``irradiance_device``  the same with the rays made and the samples summed on the device (Engine.trace_hemisphere; section 16)
 ``lightmap``     a mesh's lightmap in one call: surfels from its uvs, traced and resolved on the device (Engine.bake_lightmap; section 17)
+``probes``       irradiance probes: the SH9 radiance coefficients at points in free space, traced and projected on the device
+                 (Engine.bake_probes; section 18)
 ``lightmap_texture``  a baked map as an RGBA8 texture that sample_texture decodes back
 ``camera_rays``  the rays of cameras the reference's Camera struct cannot express: equirect, ortho, thin_lens
 ``render_rays``  rays -> tone-mapped RGBA8 pixels, the reference's colour mapping applied to sum / weight
@@ -75,6 +77,16 @@ def lightmap(engine, width, height, samples, first_sample=0, mesh=None, flip=Fal
     hemisphere of every texel's surfel (the irradiance over pi), fourth component 0 = empty, 1 = baked, 2 = filled from its
     neighbours.  No surfel and no ray exists on the host."""
     return engine.bake_lightmap(width, height, samples, first_sample=first_sample, mesh=mesh, flip=flip, offset=offset, dilate=dilate)
+
+
+def probes(engine, pos, samples, first_sample=0, seeds=None):
+    """Irradiance probes at (n, 3) points in free space (Engine.bake_probes, rb_bake_probes): the
+    radiance arriving from every direction as nine spherical-harmonic coefficients per colour channel, float64 (n, 9, 3), from
+    ``samples`` uniform-sphere rays per probe made, traced and projected on the device.  ``probes.irradiance`` evaluates them
+    for any normal; a moving object is lit from the probes around it."""
+    from . import probes as model
+    sh = engine.bake_probes(pos, samples, first_sample=first_sample, seeds=seeds)
+    return model.radiance_coefficients(sh if isinstance(sh, np.ndarray) else sh.cpu().numpy())
 
 
 def lightmap_texture(rgba):

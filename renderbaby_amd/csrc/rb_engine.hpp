@@ -185,6 +185,8 @@ struct rb_engine {
     rb::DevBuf<rb_radiance> rad_out;
     rb::DevBuf<rb_surfel> hemi_surfels;   // rb_trace_hemisphere / rb_openness_hemisphere: the piece's surfels and its counts
     rb::DevBuf<rb_openness> hemi_open;
+    rb::DevBuf<rb_probe> probe_pos;       // rb_bake_probes: the piece's probes and its SH9 sums
+    rb::DevBuf<rb_sh9> probe_out;
     // lightmap texels made on the device (rb_lightmap_surfels_device / rb_bake_lightmap*): the triangles
     // prepared in triangle order, the cover pass's scratch, and what a bake keeps between its stages
     rb::DevBuf<rb::PrepTri> lm_ptris;
@@ -199,6 +201,8 @@ struct rb_engine {
     hipEvent_t ev_q[2] = {nullptr, nullptr};
     std::vector<hipEvent_t> ev_cam;  // rb_trace_camera*, rb_*_hemisphere*: a pair around every piece's generator (rb_last_camera_rays_ms)
     size_t cam_pieces = 0;           // pairs the most recent call recorded
+    std::vector<hipEvent_t> ev_sh;   // rb_bake_probes*: a pair around every piece's projection (rb_last_probe_project_ms)
+    size_t sh_pieces = 0;
     const char* last_query_kernel_name = "";
     float last_query_ms = 0.0f;
     bool query_ms_pending = false;   // the device forms return without waiting: rb_last_query_ms reads ev_q when asked

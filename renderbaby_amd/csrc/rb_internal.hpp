@@ -447,6 +447,23 @@ struct HemiGenArgs {
 };
 int launch_hemisphere_rays(const HemiGenArgs& g, void* stream);
 int launch_hemisphere_count(const uint8_t* occl, uint32_t n, uint32_t samples, rb_openness* out, void* stream);
+// ---- rb_probe.hip: irradiance probes made on the device.  One launch of k_probe_rays writes the records
+// of one piece of whole probes, in k_cam_rays' format and k_hemi_rays' two orders; k_sh_project folds the colours launch_radiance
+// left in RadArgs::colors with the SH9 basis of each record's direction.
+struct ProbeGenArgs {
+    const rb_probe* probes;   // the piece's probes
+    const uint32_t* ids;      // the piece's probe ids, or nullptr: id_base + index in the piece
+    rb_ray* recs;             // item order: record (block * samples + sample) * 64 + probe-in-block; linear: index * samples + sample
+    uint32_t* seeds;          // linear order only, may be nullptr: seed i beside record i, whose fourth word is then 0
+    uint32_t n;               // probes in this piece
+    uint32_t id_base;         // index of the piece's first probe in the call
+    uint32_t first_sample, samples;
+    uint32_t linear;
+};
+enum : uint32_t { kProbeShapePlain = 1, kProbeShapeSplit = 2 };   // k_sh_project: one wave per 64 probes, or three with three coefficients each
+constexpr uint32_t kProbeShapeDefault = kProbeShapePlain;
+int launch_probe_rays(const ProbeGenArgs& g, void* stream);
+int launch_sh_project(const float* colors, const rb_ray* recs, uint32_t n, uint32_t samples, rb_sh9* out, uint32_t shape, void* stream);
 // ---- rb_lightmap.hip: lightmap texels made on the device.  The triangles are PrepTri / PrepTriShade
 // records in TRIANGLE order (launch_prep_tris over the identity order, launch_lightmap_iota), so that an owner is an index into
 // bvh_triangles whatever bvh_indices hold.

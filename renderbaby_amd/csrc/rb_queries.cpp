@@ -1,7 +1,7 @@
 // rb_queries.cpp -- what an engine answers besides frames: closest-hit queries (rb_cast_rays / rb_render_hits / rb_pick), any-hit
-// occlusion, path-traced radiance along given rays, camera and hemisphere rays and lightmap texels made on the device and the
-// denoiser over the first-hit buffers, with their device forms, their getters and their C entry points (rb_abi.h; DESIGN.md
-// sections 11-17).  Every family shares
+// occlusion, path-traced radiance along given rays, camera and hemisphere rays, lightmap texels and irradiance probes made on the
+// device and the denoiser over the first-hit buffers, with their device forms, their getters and their C entry points (rb_abi.h;
+// DESIGN.md sections 11-18).  Every family shares
 // one prologue (query_prologue), one timed launch (timed_launch) and one runner per form: run_pieces for the host forms,
 // device_query_locked for the device forms.  The engine's state is rb_engine.hpp's; the launchers are
 // rb_internal.hpp's.
@@ -297,20 +297,40 @@ int trace_rays_device_locked(rb_engine* e, const rb_ray* d_rays, const uint32_t*
 }
 
 // ---- camera rays made on the device (rb_abi.h)
+// `stage()` between the next event pair of `ev`, of which the call has recorded `pieces` so far: it queues a piece's stage and
+// returns a HIP status
+template <class Stage>
+int timed_pair(rb_engine* e, std::vector<hipEvent_t>& ev_all, size_t& pieces, Stage&& stage) {
+    while (ev_all.size() < 2 * (pieces + 1)) {
+        hipEvent_t x = nullptr;
+        if (const hipError_t st = hipEventCreate(&x)) return static_cast<int>(st);
+        ev_all.push_back(x);
+    }
+    hipEvent_t* const ev = &ev_all[2 * pieces];
+    if (const hipError_t st = hipEventRecord(ev[0], e->stream)) return static_cast<int>(st);
+    if (const int st = stage()) return st;
+    if (const hipError_t st = hipEventRecord(ev[1], e->stream)) return static_cast<int>(st);
+    pieces++;
+    return 0;
+}
+
 // a piece's generator between an event pair of its own (rb_last_camera_rays_ms): `gen()` queues it and returns a HIP status
 template <class Gen>
 int timed_generator(rb_engine* e, Gen&& gen) {
-    while (e->ev_cam.size() < 2 * (e->cam_pieces + 1)) {
-        hipEvent_t x = nullptr;
-        if (const hipError_t st = hipEventCreate(&x)) return static_cast<int>(st);
-        e->ev_cam.push_back(x);
+    return timed_pair(e, e->ev_cam, e->cam_pieces, gen);
+}
+
+// the kernel ms between the `pieces` event pairs of `ev`; waits for the last of them
+int pairs_ms(rb_engine* e, const std::vector<hipEvent_t>& ev, size_t pieces, float* ms) {
+    *ms = 0.0f;
+    if (pieces == 0) return RB_OK;
+    HIP_TRY(e, hipEventSynchronize(ev[2 * pieces - 1]));
+    for (size_t i = 0; i < pieces; i++) {
+        float piece_ms = 0.0f;
+        HIP_TRY(e, hipEventElapsedTime(&piece_ms, ev[2 * i], ev[2 * i + 1]));
+        *ms += piece_ms;
     }
-    hipEvent_t* const ev = &e->ev_cam[2 * e->cam_pieces];
-    if (const hipError_t st = hipEventRecord(ev[0], e->stream)) return static_cast<int>(st);
-    if (const int st = gen()) return st;
-    if (const hipError_t st = hipEventRecord(ev[1], e->stream)) return static_cast<int>(st);
-    e->cam_pieces++;
-    return 0;
+    return RB_OK;
 }
 
 // one piece, queued: the generator into the record scratch, the k_cam kernel of the scene's walk over it, the sum into `out`
@@ -464,6 +484,83 @@ int hemisphere_device_locked(rb_engine* e, const HemiCall& c, const rb_surfel* d
     });
 }
 
+// ---- irradiance probes made on the device (rb_abi.h)
+rb::ProbeGenArgs probe_gen_args(const rb_probe* probes, const uint32_t* ids, rb_ray* recs, size_t done, size_t m, uint32_t first_sample,
+                                uint32_t samples) {
+    rb::ProbeGenArgs g{};
+    g.probes = probes;
+    g.ids = ids;
+    g.recs = recs;
+    g.n = static_cast<uint32_t>(m);
+    g.id_base = static_cast<uint32_t>(done);
+    g.first_sample = first_sample;
+    g.samples = samples;
+    return g;
+}
+
+// the scratch of one piece of `piece` probes beside the caller's arrays: records, colours and the plain sums launch_radiance
+// leaves beside them (not read)
+int probe_scratch(rb_engine* e, size_t piece, uint32_t samples) {
+    if (const int rc = radiance_scratch(e, piece, samples, true)) return rc;
+    HIP_TRY(e, e->rad_out.reserve(piece));
+    return RB_OK;
+}
+
+// one piece, queued: probes [done, done + m) of the call, at `probes` / `ids` in device memory, into out[m].  The generator in
+// item order, the k_cam kernel of the scene's walk -- launch_radiance as every caller has it, its k_rad_sum included --, then
+// the projection over the colour scratch and the records, which both stand until the next piece's generator.
+int probe_piece(rb_engine* e, const rb::KParams& p, const rb_probe* probes, const uint32_t* ids, size_t done, size_t m,
+                uint32_t first_sample, uint32_t samples, rb_sh9* out, rb::LaunchInfo* li) {
+    const rb::ProbeGenArgs g = probe_gen_args(probes, ids, e->q_rays.ptr, done, m, first_sample, samples);
+    if (const int st = timed_generator(e, [&] { return rb::launch_probe_rays(g, e->stream); })) return st;
+    if (const int st = rb::launch_radiance(p, trace_args(e, e->q_rays.ptr, nullptr, e->rad_out.ptr, done, m, first_sample, samples), e->stream, li, true))
+        return st;
+    return timed_pair(e, e->ev_sh, e->sh_pieces, [&] {
+        return rb::launch_sh_project(e->rad_colors.ptr, e->q_rays.ptr, static_cast<uint32_t>(m), samples, out, 0u, e->stream);
+    });
+}
+
+size_t probe_piece_probes(size_t n, uint32_t samples) { return std::min(n, radiance_piece(RB_PROBE_PIECE_ITEMS, samples)); }
+
+int probes_locked(rb_engine* e, const rb_probe* probes, const uint32_t* seeds, size_t n, uint32_t first_sample, uint32_t samples, rb_sh9* out) {
+    rb::KParams p{};
+    e->cam_pieces = e->sh_pieces = 0;
+    int rc = query_prologue(e, &p);
+    if (rc || n == 0) return rc;
+    const size_t piece = probe_piece_probes(n, samples);
+    rc = probe_scratch(e, piece, samples);
+    if (rc) return rc;
+    HIP_TRY(e, e->probe_pos.reserve(piece));
+    if (seeds) HIP_TRY(e, e->rad_seeds.reserve(piece));
+    HIP_TRY(e, e->probe_out.reserve(piece));
+    return run_pieces(e, "probe", piece, n, {{probes, e->probe_pos.ptr, sizeof(rb_probe)}, {seeds, e->rad_seeds.ptr, sizeof(uint32_t)}},
+                      {{out, e->probe_out.ptr, sizeof(rb_sh9)}}, [&](size_t done, size_t m, rb::LaunchInfo* li) {
+                          return probe_piece(e, p, e->probe_pos.ptr, seeds ? e->rad_seeds.ptr : nullptr, done, m, first_sample, samples,
+                                             e->probe_out.ptr, li);
+                      });
+}
+
+// every piece queued between the query's two events on the caller's buffers (the pieces share the scratch in stream order);
+// nothing is waited for
+int probes_device_locked(rb_engine* e, const rb_probe* d_probes, const uint32_t* d_seeds, size_t n, uint32_t first_sample, uint32_t samples,
+                         rb_sh9* d_out) {
+    int rc = device_range(e, d_probes, n * sizeof(rb_probe), 16, "d_probes");
+    if (!rc && d_seeds) rc = device_range(e, d_seeds, n * sizeof(uint32_t), 4, "d_seeds");
+    if (!rc) rc = device_range(e, d_out, n * sizeof(rb_sh9), 16, "d_out");
+    if (rc) return rc;
+    const size_t piece = probe_piece_probes(n, samples);
+    e->cam_pieces = e->sh_pieces = 0;
+    return device_query_locked(e, [&](const rb::KParams& p, rb::LaunchInfo* li) {
+        if (probe_scratch(e, piece, samples)) return static_cast<int>(hipErrorOutOfMemory);
+        for (size_t done = 0; done < n; done += piece) {
+            const int st = probe_piece(e, p, d_probes + done, d_seeds ? d_seeds + done : nullptr, done, std::min(piece, n - done), first_sample,
+                                       samples, d_out + done, li);
+            if (st) return st;
+        }
+        return 0;
+    });
+}
+
 // ---- refusals that several entry points share, each under the entry point's own name `who`; before a device is touched
 int ray_count_check(rb_engine* e, const char* who, size_t n) {
     if (n > 0x7FFFFFFFull - 63ull) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s takes at most 2^31 - 64 rays per call", who);
@@ -528,6 +625,14 @@ int hemi_check(rb_engine* e, const char* who, const rb_hemi_params* prm, size_t 
         if (r != 0u) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: _reserved must be 0", who);
     if (openness && std::isnan(prm->radius)) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: radius is NaN", who);
     if (openness && prm->mask > RB_MASK_ALL) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: mask has bits above RB_MASK_ALL", who);
+    return RB_OK;
+}
+
+// the refusals every probe entry point shares; before a device is touched (e may be NULL: rb_probe_rays)
+int probe_check(rb_engine* e, const char* who, size_t n, uint32_t first_sample, uint32_t samples) {
+    if (const int rc = samples_check(e, who, "probe", first_sample, samples)) return rc;
+    if (n > 0x7FFFFFFFull - 63ull || static_cast<uint64_t>(n) * samples > 0x7FFFFFFFull - 63ull)
+        return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s takes at most 2^31 - 64 probes and (probe, sample) items per call", who);
     return RB_OK;
 }
 
@@ -689,6 +794,20 @@ int hemisphere_entry(rb_engine* e, const char* who, bool openness, bool device, 
     if (n == 0) return answered(e, t, require_ready(t));
     const HemiCall c{*prm, first_sample, samples, openness};
     return answered(e, t, device ? hemisphere_device_locked(t, c, surfels, seeds, n, out) : hemisphere_locked(t, c, surfels, seeds, n, out));
+}
+
+
+// the two engine entry points of the probe family
+int probes_entry(rb_engine* e, const char* who, bool device, const rb_probe* probes, const uint32_t* seeds, size_t n, uint32_t first_sample,
+                 uint32_t samples, rb_sh9* out) {
+    if (!e) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (n > 0 && (!probes || !out)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "%s: probes / out is NULL", who);
+    if (const int rc = probe_check(e, who, n, first_sample, samples)) return rc;
+    rb_engine* const t = answering(e);
+    if (n == 0) return answered(e, t, require_ready(t));
+    return answered(e, t, device ? probes_device_locked(t, probes, seeds, n, first_sample, samples, out)
+                                 : probes_locked(t, probes, seeds, n, first_sample, samples, out));
 }
 
 
@@ -1060,6 +1179,50 @@ int rb_openness_hemisphere_device(rb_engine* e, const rb_surfel* d_surfels, cons
     return hemisphere_entry(e, "rb_openness_hemisphere_device", true, true, d_surfels, d_seeds, n, params, first_sample, samples, d_out);
 }
 
+int rb_probe_rays(int32_t device, const rb_probe* probes, const uint32_t* seeds, size_t n, uint32_t first_sample, uint32_t samples,
+                  rb_ray* rays_out, uint32_t* seeds_out) {
+    if (n > 0 && (!probes || !rays_out)) return rb::fail(nullptr, RB_ERR_NULL_ARGUMENT, "probes / rays_out is NULL");
+    if (const int rc = probe_check(nullptr, "rb_probe_rays", n, first_sample, samples)) return rc;
+    if (n == 0) return RB_OK;
+    if (device >= 0 && hipSetDevice(device) != hipSuccess) return rb::fail(nullptr, RB_ERR_DEVICE, "hipSetDevice(%d) failed", device);
+    const size_t piece = std::min(n, std::max<size_t>((size_t(1) << 22) / samples, 1));   // whole probes, about 2^22 items
+    rb::DevBuf<rb_probe> d_probes;
+    rb::DevBuf<uint32_t> d_ids, d_seeds;
+    rb::DevBuf<rb_ray> d_rays;
+    hipStream_t stream = nullptr;
+    hipError_t st = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
+    if (st == hipSuccess) st = d_probes.resize(piece);
+    if (st == hipSuccess && seeds) st = d_ids.resize(piece);
+    if (st == hipSuccess) st = d_rays.resize(piece * samples);
+    if (st == hipSuccess && seeds_out) st = d_seeds.resize(piece * samples);
+    for (size_t done = 0; done < n && st == hipSuccess; done += piece) {
+        const size_t m = std::min(piece, n - done), items = m * samples;
+        st = hipMemcpyAsync(d_probes.ptr, probes + done, m * sizeof(rb_probe), hipMemcpyHostToDevice, stream);
+        if (st == hipSuccess && seeds) st = hipMemcpyAsync(d_ids.ptr, seeds + done, m * sizeof(uint32_t), hipMemcpyHostToDevice, stream);
+        rb::ProbeGenArgs g = probe_gen_args(d_probes.ptr, seeds ? d_ids.ptr : nullptr, d_rays.ptr, done, m, first_sample, samples);
+        g.seeds = seeds_out ? d_seeds.ptr : nullptr;
+        g.linear = 1u;
+        if (st == hipSuccess) st = static_cast<hipError_t>(rb::launch_probe_rays(g, stream));
+        if (st == hipSuccess) st = hipMemcpyAsync(rays_out + done * samples, d_rays.ptr, items * sizeof(rb_ray), hipMemcpyDeviceToHost, stream);
+        if (st == hipSuccess && seeds_out)
+            st = hipMemcpyAsync(seeds_out + done * samples, d_seeds.ptr, items * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
+        if (st == hipSuccess) st = hipStreamSynchronize(stream);   // the scratch is the next piece's
+    }
+    if (stream) (void)hipStreamSynchronize(stream);   // (the buffers are freed on return, after this)
+    if (stream) (void)hipStreamDestroy(stream);
+    if (st != hipSuccess) return rb::fail(nullptr, RB_ERR_DEVICE, "rb_probe_rays failed: %s", hipGetErrorString(st));
+    return RB_OK;
+}
+
+int rb_bake_probes(rb_engine* e, const rb_probe* probes, const uint32_t* seeds, size_t n, uint32_t first_sample, uint32_t samples, rb_sh9* out) {
+    return probes_entry(e, "rb_bake_probes", false, probes, seeds, n, first_sample, samples, out);
+}
+
+int rb_bake_probes_device(rb_engine* e, const rb_probe* d_probes, const uint32_t* d_seeds, size_t n, uint32_t first_sample,
+                          uint32_t samples, rb_sh9* d_out) {
+    return probes_entry(e, "rb_bake_probes_device", true, d_probes, d_seeds, n, first_sample, samples, d_out);
+}
+
 int rb_lightmap_surfels(int32_t device, const rb_gpu_triangle* tris, size_t n_tris, const float* uvs, size_t n_uv_floats,
                         const rb_lightmap_params* params, rb_surfel* surfels_out, uint32_t* owners_out) {
     if (!params || !surfels_out || (n_tris > 0 && !tris) || (n_uv_floats > 0 && !uvs))
@@ -1274,13 +1437,17 @@ int rb_last_camera_rays_ms(rb_engine* e, float* ms) {
     *ms = 0.0f;
     if (t->cam_pieces == 0) return RB_OK;
     rb::set_device(t);
-    HIP_TRY(e, hipEventSynchronize(t->ev_cam[2 * t->cam_pieces - 1]));
-    for (size_t i = 0; i < t->cam_pieces; i++) {
-        float piece_ms = 0.0f;
-        HIP_TRY(e, hipEventElapsedTime(&piece_ms, t->ev_cam[2 * i], t->ev_cam[2 * i + 1]));
-        *ms += piece_ms;
-    }
-    return RB_OK;
+    return answered(e, t, pairs_ms(t, t->ev_cam, t->cam_pieces, ms));
+}
+
+int rb_last_probe_project_ms(rb_engine* e, float* ms) {
+    if (!e || !ms) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    rb_engine* const t = rb::is_group(e) ? e->parts[0].get() : e;
+    *ms = 0.0f;
+    if (t->sh_pieces == 0) return RB_OK;
+    rb::set_device(t);
+    return answered(e, t, pairs_ms(t, t->ev_sh, t->sh_pieces, ms));
 }
 
 }  // extern "C"

@@ -1107,6 +1107,7 @@ void rb_destroy(rb_engine* e) {
         if (s.done) (void)hipEventDestroy(s.done);
     for (hipEvent_t x : e->ev_pool) (void)hipEventDestroy(x);
     for (hipEvent_t x : e->ev_cam) (void)hipEventDestroy(x);
+    for (hipEvent_t x : e->ev_sh) (void)hipEventDestroy(x);
     for (hipEvent_t x : e->ev_q)
         if (x) (void)hipEventDestroy(x);
     for (hipEvent_t x : e->ev_dn)

@@ -685,6 +685,56 @@ class Engine:
                                                sums.ctypes.data if (sums is not None and n) else None))
         return res
 
+    # ---- irradiance probes made on the device (rb_abi.h)
+    def bake_probes(self, pos, samples, first_sample=0, seeds=None, out=None):
+        """rb_bake_probes: the SH9 sums of the radiance arriving at (n, 3) points in free space from every direction,
+        ``samples`` uniform-sphere rays per probe made on the device from the probe's own random stream -> abi.SH9[n] (``sum``
+        [j][channel] over the samples, ``weight``: the valid samples; ``probes.radiance_coefficients`` and
+        ``probes.irradiance`` read them).  ``seeds``: n uint32 ids or None (the probe's index).  A torch tensor on the engine's
+        device for the positions, the seeds or ``out`` ((n, 28) float32) goes to rb_bake_probes_device: an (n, 28) tensor comes
+        back and nothing crosses to the host."""
+        samples, first_sample = int(samples), int(first_sample)
+        if not (0 <= samples < 2 ** 32 and 0 <= first_sample < 2 ** 32):
+            raise ValueError("samples and first_sample are 32-bit unsigned numbers")
+        if _is_tensor(pos) or _is_tensor(seeds) or _is_tensor(out):
+            import torch
+            if not _is_tensor(pos) or pos.dtype != torch.float32:
+                raise ValueError("pos: a float32 tensor is needed beside tensor seeds or out")
+            p3 = pos.reshape(-1, 3)
+            rec = torch.zeros((len(p3), 4), dtype=torch.float32, device=p3.device)
+            rec[:, 0:3] = p3
+            pp, n = self._device_tensor(rec, torch.float32, 4, "pos")
+            sp, ns = (None, n)
+            if seeds is not None:   # 32-bit ids, signed or unsigned: the bits are what counts
+                unsigned = _is_tensor(seeds) and seeds.dtype == getattr(torch, "uint32", None)
+                sp, ns = self._device_tensor(seeds, torch.uint32 if unsigned else torch.int32, None, "seeds")
+            res = torch.empty((n, 28), dtype=torch.float32, device=rec.device) if out is None else out
+            op, no = self._device_tensor(res, torch.float32, 28, "out")
+            if ns != n or no != n:
+                raise ValueError("pos, seeds and out differ in length")
+            self._device_call(self._lib.rb_bake_probes_device, pp, sp, n, first_sample, samples, op)
+            return res
+        p3 = np.asarray(pos, dtype=np.float32).reshape(-1, 3)
+        n = len(p3)
+        rec = np.zeros(n, dtype=abi.PROBE)
+        rec["pos"] = p3
+        if seeds is not None:
+            seeds = np.ascontiguousarray(seeds, dtype=np.uint32).reshape(-1)
+            if len(seeds) != n:
+                raise ValueError("pos and seeds differ in length")
+        res = np.empty(n, dtype=abi.SH9) if out is None else out
+        if not isinstance(res, np.ndarray) or res.dtype != abi.SH9 or res.shape != (n,) or not res.flags.c_contiguous:
+            raise ValueError("out: a contiguous abi.SH9 array of n elements is needed")
+        self._check(self._lib.rb_bake_probes(self._h, rec.ctypes.data if n else None, seeds.ctypes.data if (seeds is not None and n) else None, n,
+                                             first_sample, samples, res.ctypes.data if n else None))
+        return res
+
+    def last_probe_project_ms(self):
+        """kernel ms of the projection (k_sh_project) in the most recent bake_probes: its share of last_query_ms()"""
+        ms = C.c_float()
+        self._check(self._lib.rb_last_probe_project_ms(self._h, C.byref(ms)))
+        return ms.value
+
     def last_lightmap_ms(self):
         """(surfels_ms, resolve_ms): kernel ms of the surfel stage and of the resolve in the most recent lightmap_surfels or
         bake_lightmap; both lie inside last_query_ms()"""
@@ -693,7 +743,7 @@ class Engine:
         return a.value, b.value
 
     def last_camera_rays_ms(self):
-        """kernel ms of the generator (k_cam_rays, k_hemi_rays) in the most recent trace_camera, trace_hemisphere or openness:
+        """kernel ms of the generator (k_cam_rays, k_hemi_rays, k_probe_rays) in the most recent trace_camera, trace_hemisphere, openness or bake_probes:
         its share of last_query_ms()"""
         ms = C.c_float()
         self._check(self._lib.rb_last_camera_rays_ms(self._h, C.byref(ms)))
@@ -902,6 +952,30 @@ def hemisphere_rays_device(points, normals, samples, first_sample=0, seeds=None,
     lib = load()
     rc = lib.rb_hemisphere_rays(int(device), surf.ctypes.data if m else None, seeds.ctypes.data if (seeds is not None and m) else None, m,
                                 prm.ctypes.data, int(first_sample), samples, rays.ctypes.data, seeds_out.ctypes.data)
+    if rc != abi.RB_OK:
+        raise RenderError(rc, (lib.rb_last_error(None) or b"").decode())
+    return rays, seeds_out
+
+
+def probe_rays_device(pos, samples, first_sample=0, seeds=None, device=-1):
+    """rb_probe_rays: the generator alone, no engine -- (abi.RAY[n * samples], uint32 seeds[n * samples]) of (n, 3) probe
+    positions, item i * samples + k: the position, the normalised direction (0 0 0: an invalid item) and the seed trace_ray
+    starts with.  ``probes.rays`` is its numpy model."""
+    p3 = np.asarray(pos, dtype=np.float32).reshape(-1, 3)
+    n, samples = len(p3), int(samples)
+    if not 0 <= samples < 2 ** 32:
+        raise ValueError("samples: a 32-bit unsigned number")
+    rec = np.zeros(n, dtype=abi.PROBE)
+    rec["pos"] = p3
+    if seeds is not None:
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint32).reshape(-1)
+        if len(seeds) != n:
+            raise ValueError("pos and seeds differ in length")
+    items = n * samples if samples <= 65536 else 0   # (a refused call writes nothing)
+    rays, seeds_out = np.zeros(items, dtype=abi.RAY), np.zeros(items, dtype=np.uint32)
+    lib = load()
+    rc = lib.rb_probe_rays(int(device), rec.ctypes.data if n else None, seeds.ctypes.data if (seeds is not None and n) else None, n,
+                           int(first_sample), samples, rays.ctypes.data, seeds_out.ctypes.data)
     if rc != abi.RB_OK:
         raise RenderError(rc, (lib.rb_last_error(None) or b"").decode())
     return rays, seeds_out

@@ -7,6 +7,7 @@
                                  [--camera equirect|ortho|thin-lens [--ortho-width W] [--aperture A --focus-distance F] [--jitter]]
                                  [--probe x,y,z [--probe-normal x,y,z]] [--device-rays]
                                  [--lightmap W H [--lightmap-mesh i] [--lightmap-flip]]
+                                 [--probe-grid NX NY NZ]
 
 scene file -> scene_io.load_scene (the importer's and the Scene->RenderConfig adapter's rules) ->
 RenderConfig -> librenderbaby_hip.so -> Frame -> PNG.  With --every N the progressive iterator is used
@@ -24,11 +25,14 @@ Engine.trace_camera).  --probe prints the mean radiance ov
 directions than the host generators', the same estimate.  --lightmap W H bakes the scene's lightmap over its uvs on the device
 (bake.lightmap -> Engine.bake_lightmap, spp samples per texel) and writes it as out.lightmap.png in the
 texture's own encoding (bake.lightmap_texture), for one mesh with --lightmap-mesh; with --aov ao also the ambient-occlusion map
-of the same texels (aov.ambient_occlusion_map) as out.lightmap.ao.png.
+of the same texels (aov.ambient_occlusion_map) as out.lightmap.ao.png.  --probe-grid NX NY NZ bakes a grid of irradiance probes
+over the bounding box of the scene's triangles and spheres (probes.grid -> bake.probes: Engine.bake_probes, spp uniform-sphere
+rays per probe, traced and projected onto SH9 on the device) and writes out.probes.npz with `positions`
+(n, 3) and `coefficients` (n, 9, 3), which probes.irradiance evaluates for any normal.
 """
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from renderbaby_amd import Engine, Frame, RenderConfig, aov, bake, camera, denoise, scene_io  # noqa: E402
+from renderbaby_amd import Engine, Frame, RenderConfig, aov, bake, camera, denoise, probes, scene_io  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("scene"); ap.add_argument("png")
@@ -51,6 +55,8 @@ ap.add_argument("--device-rays", action="store_true", help="--aov ao and --probe
 ap.add_argument("--lightmap", type=int, nargs=2, metavar=("W", "H"), default=None, help="also bake the lightmap over the scene's uvs, as out.lightmap.png")
 ap.add_argument("--lightmap-mesh", type=int, default=None, help="--lightmap for the triangles of this mesh index only")
 ap.add_argument("--lightmap-flip", action="store_true", help="--lightmap with the triangles' normals negated")
+ap.add_argument("--probe-grid", type=int, nargs=3, metavar=("NX", "NY", "NZ"), default=None,
+                help="also bake a grid of irradiance probes over the scene's bounding box, as out.probes.npz")
 a = ap.parse_args()
 aovs = [n for n in a.aov.split(",") if n]
 for n in aovs:
@@ -142,4 +148,19 @@ if a.lightmap:
         img = aov.ao_u8(np.where(np.isnan(ao), np.float32(0), ao))
         scene_io.export_png(f"{base}.lightmap.ao{ext}", Frame(w, h, img))
         print(f"ambient-occlusion map with {eng.last_query_kernel_name()} in {eng.last_query_ms():.3f} ms -> {base}.lightmap.ao{ext}")
+if a.probe_grid:
+    import numpy as np
+    tri = s.bvh_triangles
+    lo = [tri[k].reshape(-1, 3) for k in ("v0", "v1", "v2")] + [s.spheres["center"] - s.spheres["radius"][:, None]]
+    hi = lo[:3] + [s.spheres["center"] + s.spheres["radius"][:, None]]
+    if not len(tri) and not len(s.spheres):
+        ap.error("--probe-grid: the scene has neither triangles nor spheres to span a box")
+    lo, hi = np.concatenate(lo).min(0), np.concatenate(hi).max(0)
+    pos = probes.grid(lo, hi, a.probe_grid)
+    spp = min(max(s.total_samples, 1), 65536)
+    coeff = bake.probes(eng, pos, spp)
+    base, _ = os.path.splitext(a.png)
+    np.savez(f"{base}.probes.npz", positions=pos, coefficients=coeff)
+    print(f"{len(pos)} probes over {tuple(float(v) for v in lo)} .. {tuple(float(v) for v in hi)}, {spp} rays each, with {eng.last_query_kernel_name()} in {eng.last_query_ms():.3f} ms "
+          f"(generator {eng.last_camera_rays_ms():.3f}, projection {eng.last_probe_project_ms():.3f}) -> {base}.probes.npz")
 eng.close()
