@@ -12,11 +12,6 @@
 namespace rb {
 namespace {
 
-DEV bool cam_finite3(f3 a) {
-    const uint32_t m = 0x7F800000u;
-    return (__float_as_uint(a.x) & m) != m && (__float_as_uint(a.y) & m) != m && (__float_as_uint(a.z) & m) != m;
-}
-
 // ========================================================= k_cam_rays ====
 // lane = item.  Item order (the trace's scratch): item = (block * samples + sample) * 64 + pixel-in-block, block = 64
 // consecutive pixels of the piece -- the order the k_cam kernels hand items out in, so a wave's 64 records are one contiguous
@@ -71,14 +66,9 @@ __global__ void __launch_bounds__(256) k_cam_rays(const CamGenArgs g) {
     }
     d = normalize(d);
     // rb_cast_rays' rule; an invalid ray is marked by a zero direction
-    if (!(cam_finite3(o) && cam_finite3(d)) || (d.x == 0.0f && d.y == 0.0f && d.z == 0.0f)) d = mk(0, 0, 0);
+    if (!(finite3(o) && finite3(d)) || zero3(d)) d = mk(0, 0, 0);
 
-    const bool beside = g.seeds != nullptr;
-    const v4f r0 = {o.x, o.y, o.z, __uint_as_float(beside ? 0u : seed)}, r1 = {d.x, d.y, d.z, 0.0f};
-    v4f* const rec = reinterpret_cast<v4f*>(g.recs) + (size_t)t * 2u;
-    rec[0] = r0;
-    rec[1] = r1;
-    if (beside) g.seeds[t] = seed;
+    store_record(g.recs, g.seeds, t, o, d, seed);
 }
 
 }  // namespace

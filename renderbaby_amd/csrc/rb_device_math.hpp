@@ -24,6 +24,12 @@ DEV f3 cross(f3 a, f3 b) { return mk(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.
 DEV f3 div3_exact(f3 a, float b);
 DEV float sqrt_exact(float x);
 DEV f3 normalize(f3 a) { return div3_exact(a, sqrt_exact(dot(a, a))); }
+// no component is an infinity or a NaN (rb_cast_rays' rule for a ray's origin and direction); every component is +-0
+DEV bool finite3(f3 a) {
+    const uint32_t m = 0x7F800000u;
+    return (__float_as_uint(a.x) & m) != m && (__float_as_uint(a.y) & m) != m && (__float_as_uint(a.z) & m) != m;
+}
+DEV bool zero3(f3 a) { return a.x == 0.0f && a.y == 0.0f && a.z == 0.0f; }
 
 // ---- IEEE-exact 1/b in 3-5 instructions instead of the 12-instruction a/b expansion.
 // v_rcp_f32 is accurate to 1 ulp; one (RB_RCP_STEPS=1) or two Newton steps with FMA give the

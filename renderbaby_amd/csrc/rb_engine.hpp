@@ -200,7 +200,7 @@ struct rb_engine {
     bool lm_timed[2] = {false, false};   // the most recent lightmap call recorded the pair (rb_last_lightmap_ms)
     hipEvent_t ev_q[2] = {nullptr, nullptr};
     std::vector<hipEvent_t> ev_cam;  // rb_trace_camera*, rb_*_hemisphere*: a pair around every piece's generator (rb_last_camera_rays_ms)
-    size_t cam_pieces = 0;           // pairs the most recent call recorded
+    size_t cam_pieces = 0;           // pairs the most recent query recorded; 0 from every query's prologue on
     std::vector<hipEvent_t> ev_sh;   // rb_bake_probes*: a pair around every piece's projection (rb_last_probe_project_ms)
     size_t sh_pieces = 0;
     const char* last_query_kernel_name = "";

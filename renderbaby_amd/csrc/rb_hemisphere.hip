@@ -12,12 +12,6 @@
 namespace rb {
 namespace {
 
-DEV bool hemi_finite3(f3 a) {
-    const uint32_t m = 0x7F800000u;
-    return (__float_as_uint(a.x) & m) != m && (__float_as_uint(a.y) & m) != m && (__float_as_uint(a.z) & m) != m;
-}
-DEV bool hemi_zero3(f3 a) { return a.x == 0.0f && a.y == 0.0f && a.z == 0.0f; }
-
 // ========================================================= k_hemi_rays ====
 // lane = item.  Item order (the trace's scratch): item = (block * samples + sample) * 64 + surfel-in-block, block = 64
 // consecutive surfels of the piece -- the order the k_cam kernels hand items out in, so a wave's 64 records are one contiguous
@@ -27,23 +21,15 @@ DEV bool hemi_zero3(f3 a) { return a.x == 0.0f && a.y == 0.0f && a.z == 0.0f; }
 // beside 64 B of record traffic per item).
 __global__ void __launch_bounds__(256) k_hemi_rays(const HemiGenArgs g) {
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-    const uint32_t S = g.samples;
-    uint32_t sf, smp;
-    if (g.linear != 0u) {
-        sf = t / S;
-        smp = t - sf * S;
-    } else {
-        const uint32_t row = t >> 6, blk = row / S;
-        smp = row - blk * S;
-        sf = blk * 64u + (t & 63u);
-    }
+    const GenItem it = gen_item(t, g.samples, g.linear);
+    const uint32_t sf = it.idx, smp = it.smp;
     if (sf >= g.n) return;   // the padding of the last block, and the lanes behind the last item
 
     const v4f* const sp = reinterpret_cast<const v4f*>(g.surfels) + (size_t)sf * 2u;
     const v4f s0 = sp[0], s1 = sp[1];
     const f3 pos = mk(s0.x, s0.y, s0.z);
     const f3 nrm = normalize(mk(s1.x, s1.y, s1.z));
-    bool ok = hemi_finite3(pos) && hemi_finite3(nrm) && !hemi_zero3(nrm);
+    bool ok = finite3(pos) && finite3(nrm) && !zero3(nrm);
 
     const uint32_t sid = g.ids != nullptr ? g.ids[sf] : g.id_base + sf;
     uint32_t seed = pcg(sid + pcg(g.first_sample + smp));
@@ -63,18 +49,13 @@ __global__ void __launch_bounds__(256) k_hemi_rays(const HemiGenArgs g) {
     f3 o = pos + (g.offset * fmaxf(1.0f, reach)) * nrm;
     // rb_cast_rays' rule.  An invalid item is marked by a zero direction and keeps the surfel's position as it was given: a
     // NaN made here has no defined sign or payload and stays out of the record.
-    ok = ok && hemi_finite3(o) && hemi_finite3(d) && !hemi_zero3(d);
+    ok = ok && finite3(o) && finite3(d) && !zero3(d);
     if (!ok) {
         o = pos;
         d = mk(0, 0, 0);
     }
 
-    const bool beside = g.seeds != nullptr;
-    const v4f r0 = {o.x, o.y, o.z, __uint_as_float(beside ? 0u : seed)}, r1 = {d.x, d.y, d.z, 0.0f};
-    v4f* const rec = reinterpret_cast<v4f*>(g.recs) + (size_t)t * 2u;
-    rec[0] = r0;
-    rec[1] = r1;
-    if (beside) g.seeds[t] = seed;
+    store_record(g.recs, g.seeds, t, o, d, seed);
     if (g.tmax != nullptr) g.tmax[t] = g.radius;
 }
 
@@ -116,8 +97,8 @@ int launch_hemisphere_rays(const HemiGenArgs& g, void* stream_) {
     if (g.n == 0u) return 0;
     if (g.surfels == nullptr || g.recs == nullptr || g.samples == 0u) return (int)hipErrorInvalidValue;
     if (g.linear == 0u && (g.seeds != nullptr || g.tmax != nullptr)) return (int)hipErrorInvalidValue;
-    const uint64_t lanes = g.linear != 0u ? (uint64_t)g.n * g.samples : (((uint64_t)g.n + 63u) / 64u) * 64u * g.samples;
-    if (lanes > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
+    const uint64_t lanes = gen_lanes(g.n, g.samples, g.linear);
+    if (lanes == 0u) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(k_hemi_rays, dim3((uint32_t)((lanes + 255u) / 256u)), dim3(256), 0, static_cast<hipStream_t>(stream_), g);
     return (int)hipGetLastError();
 }

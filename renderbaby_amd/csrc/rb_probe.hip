@@ -14,28 +14,14 @@
 namespace rb {
 namespace {
 
-DEV bool probe_finite3(f3 a) {
-    const uint32_t m = 0x7F800000u;
-    return (__float_as_uint(a.x) & m) != m && (__float_as_uint(a.y) & m) != m && (__float_as_uint(a.z) & m) != m;
-}
-DEV bool probe_zero3(f3 a) { return a.x == 0.0f && a.y == 0.0f && a.z == 0.0f; }
-
 // ======================================================== k_probe_rays ====
 // lane = item, in k_hemi_rays' two orders.  Item order (the trace's scratch): item = (block * samples + sample) * 64 +
 // probe-in-block, block = 64 consecutive probes of the piece.  Linear order (rb_probe_rays): item = probe-in-piece * samples +
 // sample.  The record is k_cam_rays': {origin, seed after the two draws}, {direction, 0}, or the seed beside it.
 __global__ void __launch_bounds__(256) k_probe_rays(const ProbeGenArgs g) {
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-    const uint32_t S = g.samples;
-    uint32_t pr, smp;
-    if (g.linear != 0u) {
-        pr = t / S;
-        smp = t - pr * S;
-    } else {
-        const uint32_t row = t >> 6, blk = row / S;
-        smp = row - blk * S;
-        pr = blk * 64u + (t & 63u);
-    }
+    const GenItem it = gen_item(t, g.samples, g.linear);
+    const uint32_t pr = it.idx, smp = it.smp;
     if (pr >= g.n) return;   // the padding of the last block, and the lanes behind the last item
 
     const v4f p0 = reinterpret_cast<const v4f*>(g.probes)[pr];
@@ -50,14 +36,9 @@ __global__ void __launch_bounds__(256) k_probe_rays(const ProbeGenArgs g) {
     f3 d = normalize(mk(r * az.c, r * az.s, z));
 
     // rb_cast_rays' rule; an invalid item keeps the probe's position as it was given beside a zero direction
-    if (!(probe_finite3(pos) && probe_finite3(d) && !probe_zero3(d))) d = mk(0, 0, 0);
+    if (!(finite3(pos) && finite3(d) && !zero3(d))) d = mk(0, 0, 0);
 
-    const bool beside = g.seeds != nullptr;
-    const v4f r0 = {pos.x, pos.y, pos.z, __uint_as_float(beside ? 0u : seed)}, r1 = {d.x, d.y, d.z, 0.0f};
-    v4f* const rec = reinterpret_cast<v4f*>(g.recs) + (size_t)t * 2u;
-    rec[0] = r0;
-    rec[1] = r1;
-    if (beside) g.seeds[t] = seed;
+    store_record(g.recs, g.seeds, t, pos, d, seed);
 }
 
 // ======================================================== k_sh_project ====
@@ -155,8 +136,8 @@ int launch_probe_rays(const ProbeGenArgs& g, void* stream_) {
     if (g.n == 0u) return 0;
     if (g.probes == nullptr || g.recs == nullptr || g.samples == 0u) return (int)hipErrorInvalidValue;
     if (g.linear == 0u && g.seeds != nullptr) return (int)hipErrorInvalidValue;
-    const uint64_t lanes = g.linear != 0u ? (uint64_t)g.n * g.samples : (((uint64_t)g.n + 63u) / 64u) * 64u * g.samples;
-    if (lanes > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
+    const uint64_t lanes = gen_lanes(g.n, g.samples, g.linear);
+    if (lanes == 0u) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(k_probe_rays, dim3((uint32_t)((lanes + 255u) / 256u)), dim3(256), 0, static_cast<hipStream_t>(stream_), g);
     return (int)hipGetLastError();
 }

@@ -1,10 +1,11 @@
 // rb_queries.cpp -- what an engine answers besides frames: closest-hit queries (rb_cast_rays / rb_render_hits / rb_pick), any-hit
 // occlusion, path-traced radiance along given rays, camera and hemisphere rays, lightmap texels and irradiance probes made on the
 // device and the denoiser over the first-hit buffers, with their device forms, their getters and their C entry points (rb_abi.h;
-// DESIGN.md sections 11-18).  Every family shares
-// one prologue (query_prologue), one timed launch (timed_launch) and one runner per form: run_pieces for the host forms,
-// device_query_locked for the device forms.  The engine's state is rb_engine.hpp's; the launchers are
-// rb_internal.hpp's.
+// DESIGN.md sections 11-18).  Every sequence is here once: one prologue (query_prologue), one timed
+// launch (timed_launch), one runner per form -- run_pieces for the host forms, device_query_locked for the device forms --, over
+// them one runner for the families of "n items, `samples` each" in both forms (run_family: radiance, camera, hemisphere,
+// probes), one shape for the engine entry points (engine_entry) and one scope for the engine-less forms (DeviceScope).  The
+// engine's state is rb_engine.hpp's; the launchers are rb_internal.hpp's.
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -45,9 +46,11 @@ int scene_params(rb_engine* e, rb::KParams* p) {
     return RB_OK;
 }
 
-// what every query begins with; the kernel time of the query before is gone from here on, however far this one gets
+// what every query begins with; the kernel times of the query before -- rb_last_query_ms and the event pairs of its generator
+// and projection stages -- are gone from here on, however far this one gets
 int query_prologue(rb_engine* e, rb::KParams* p) {
     e->last_query_ms = 0.0f;
+    e->cam_pieces = e->sh_pieces = 0;
     int rc = require_ready(e);
     if (!rc) rc = ensure_prepared(e);
     if (!rc) rc = scene_params(e, p);
@@ -232,6 +235,7 @@ int cast_rays_device_locked(rb_engine* e, const rb_ray* d_rays, size_t n, rb_hit
 // rays or pixels per piece of at most `limit` (ray or pixel, sample) items: whole blocks of 64, never a part of one's samples
 // (samples <= 65536: at least one block)
 size_t radiance_piece(size_t limit, uint32_t samples) { return std::max<size_t>((limit / samples) & ~size_t(63), 64); }
+size_t piece_items(size_t limit, size_t n, uint32_t samples) { return std::min(n, radiance_piece(limit, samples)); }
 
 // the scratch of one piece: a colour per item and the queue word; `records`: a ray record per item too (rays made on the device)
 int radiance_scratch(rb_engine* e, size_t piece, uint32_t samples, bool records) {
@@ -257,43 +261,92 @@ rb::RadArgs trace_args(rb_engine* e, const rb_ray* rays, const uint32_t* seeds, 
     return a;
 }
 
-int trace_rays_locked(rb_engine* e, const rb_ray* rays, const uint32_t* seeds, size_t n, uint32_t first_sample, uint32_t samples,
-                      rb_radiance* out) {
-    rb::KParams p{};
-    int rc = query_prologue(e, &p);
-    if (rc || n == 0) return rc;
-    const size_t piece = std::min(n, radiance_piece(RB_TRACE_PIECE_ITEMS, samples));
-    rc = radiance_scratch(e, piece, samples, false);
-    if (rc) return rc;
-    HIP_TRY(e, e->q_rays.reserve(piece));
-    if (seeds) HIP_TRY(e, e->rad_seeds.reserve(piece));
-    HIP_TRY(e, e->rad_out.reserve(piece));
-    return run_pieces(e, "radiance", piece, n, {{rays, e->q_rays.ptr, sizeof(rb_ray)}, {seeds, e->rad_seeds.ptr, sizeof(uint32_t)}},
-                      {{out, e->rad_out.ptr, sizeof(rb_radiance)}}, [&](size_t done, size_t m, rb::LaunchInfo* li) {
-                          const rb::RadArgs a = trace_args(e, e->q_rays.ptr, seeds ? e->rad_seeds.ptr : nullptr, e->rad_out.ptr, done, m, first_sample, samples);
-                          return rb::launch_radiance(p, a, e->stream, li);
-                      });
+// `each(done, m)` for every piece [done, done + m) of n items; it returns a HIP status, and the first bad one ends the loop
+template <class Each>
+int for_pieces(size_t n, size_t piece, Each&& each) {
+    for (size_t done = 0; done < n; done += piece)
+        if (const int st = each(done, std::min(piece, n - done))) return st;
+    return 0;
 }
 
-// every piece queued between the query's two events on the caller's buffers (the pieces share the colour scratch in stream
-// order); nothing is waited for
-int trace_rays_device_locked(rb_engine* e, const rb_ray* d_rays, const uint32_t* d_seeds, size_t n, uint32_t first_sample,
-                             uint32_t samples, rb_radiance* d_out) {
-    int rc = device_range(e, d_rays, n * sizeof(rb_ray), 16, "d_rays");
-    if (!rc && d_seeds) rc = device_range(e, d_seeds, n * sizeof(uint32_t), 4, "d_seeds");
-    if (!rc) rc = device_range(e, d_out, n * sizeof(rb_radiance), 16, "d_out");
+// One array of a family's call, item i at caller + i * stride: host memory in the host form, where a piece of it goes through
+// the engine's staging buffer `stage`, device memory in the device form, where device_range asks for `align` under `name`.
+// caller == nullptr: the caller left this array out.
+struct FamilyArray {
+    const void* caller;
+    size_t stride, align;
+    const char* name;
+    const char* stage_name;                               // the buffer as a failed reservation names it
+    void* stage;
+    hipError_t (*reserve)(void* stage, size_t n, void** ptr);   // room for n items in `stage`; *ptr: where they begin
+};
+template <class T>
+FamilyArray family_array(const void* caller, rb::DevBuf<T>& stage, const char* stage_name, size_t align, const char* name) {
+    return {caller, sizeof(T), align, name, stage_name, &stage, [](void* b, size_t n, void** ptr) {
+                rb::DevBuf<T>* const buf = static_cast<rb::DevBuf<T>*>(b);
+                const hipError_t st = buf->reserve(n);
+                *ptr = buf->ptr;
+                return st;
+            }};
+}
+#define FAMILY_ARRAY(caller, stage, align, name) family_array(caller, stage, #stage, align, name)
+
+// The runner of the families of "n > 0 items, `samples` samples each": pieces of whole blocks of 64 items and at most `limit`
+// (item, sample) pairs.  `ins`: up to two input arrays, `out`: the result array.  `scratch(piece)` reserves what a piece needs
+// beside them and returns an rb code; `piece_fn(p, in, out, done, m, li)` queues items [done, done + m) of the call, whose
+// arrays begin at in[0], in[1] (nullptr: left out) and out in device memory, and returns a HIP status.
+// Device form: the caller's buffers are checked, then every piece is queued on them between the query's two events (the pieces
+// share the scratch in stream order); nothing is waited for.  Host form: run_pieces over the staging buffers.
+template <class Scratch, class Piece>
+int run_family(rb_engine* e, bool device, const char* kind, size_t limit, size_t n, uint32_t samples, const FamilyArray (&ins)[2],
+               const FamilyArray& out, Scratch&& scratch, Piece&& piece_fn) {
+    const size_t piece = piece_items(limit, n, samples);
+    const void* in[2] = {nullptr, nullptr};
+    if (device) {
+        for (const FamilyArray& a : ins)
+            if (a.caller)
+                if (const int rc = device_range(e, a.caller, n * a.stride, a.align, a.name)) return rc;
+        if (const int rc = device_range(e, out.caller, n * out.stride, out.align, out.name)) return rc;
+        return device_query_locked(e, [&](const rb::KParams& p, rb::LaunchInfo* li) {
+            if (scratch(piece)) return static_cast<int>(hipErrorOutOfMemory);
+            return for_pieces(n, piece, [&](size_t done, size_t m) {
+                for (int k = 0; k < 2; k++) in[k] = ins[k].caller ? static_cast<const char*>(ins[k].caller) + done * ins[k].stride : nullptr;
+                return piece_fn(p, in, static_cast<char*>(const_cast<void*>(out.caller)) + done * out.stride, done, m, li);
+            });
+        });
+    }
+    rb::KParams p{};
+    int rc = query_prologue(e, &p);
+    if (!rc) rc = scratch(piece);
     if (rc) return rc;
-    const size_t piece = std::min(n, radiance_piece(RB_TRACE_PIECE_ITEMS, samples));
-    return device_query_locked(e, [&](const rb::KParams& p, rb::LaunchInfo* li) {
-        if (radiance_scratch(e, piece, samples, false)) return static_cast<int>(hipErrorOutOfMemory);
-        for (size_t done = 0; done < n; done += piece) {
-            const size_t m = std::min(piece, n - done);
-            const rb::RadArgs a = trace_args(e, d_rays + done, d_seeds ? d_seeds + done : nullptr, d_out + done, done, m, first_sample, samples);
-            const int st = rb::launch_radiance(p, a, e->stream, li);
-            if (st) return st;
-        }
-        return 0;
-    });
+    PieceIn staged[2] = {};
+    void* d_out = nullptr;
+    const auto reserve = [&](const FamilyArray& a, void** ptr) {
+        const hipError_t st = a.reserve(a.stage, piece, ptr);
+        return st == hipSuccess ? RB_OK : rb::fail(e, RB_ERR_DEVICE, "%s.reserve(piece) failed: %s", a.stage_name, hipGetErrorString(st));
+    };
+    for (int k = 0; k < 2; k++) {
+        if (!ins[k].caller) continue;
+        void* ptr = nullptr;
+        if ((rc = reserve(ins[k], &ptr)) != RB_OK) return rc;
+        staged[k] = PieceIn{ins[k].caller, ptr, ins[k].stride};
+        in[k] = ptr;
+    }
+    if ((rc = reserve(out, &d_out)) != RB_OK) return rc;
+    return run_pieces(e, kind, piece, n, {staged[0], staged[1]}, {{const_cast<void*>(out.caller), d_out, out.stride}},
+                      [&](size_t done, size_t m, rb::LaunchInfo* li) { return piece_fn(p, in, d_out, done, m, li); });
+}
+
+int trace_rays_locked(rb_engine* e, bool device, const rb_ray* rays, const uint32_t* seeds, size_t n, uint32_t first_sample, uint32_t samples,
+                      rb_radiance* out) {
+    return run_family(e, device, "radiance", RB_TRACE_PIECE_ITEMS, n, samples,
+                      {FAMILY_ARRAY(rays, e->q_rays, 16, "d_rays"), FAMILY_ARRAY(seeds, e->rad_seeds, 4, "d_seeds")},
+                      FAMILY_ARRAY(out, e->rad_out, 16, "d_out"), [&](size_t piece) { return radiance_scratch(e, piece, samples, false); },
+                      [&](const rb::KParams& p, const void* const* in, void* o, size_t done, size_t m, rb::LaunchInfo* li) {
+                          const rb::RadArgs a = trace_args(e, static_cast<const rb_ray*>(in[0]), static_cast<const uint32_t*>(in[1]),
+                                                           static_cast<rb_radiance*>(o), done, m, first_sample, samples);
+                          return rb::launch_radiance(p, a, e->stream, li);
+                      });
 }
 
 // ---- camera rays made on the device (rb_abi.h)
@@ -347,36 +400,13 @@ int camera_piece(rb_engine* e, const rb::KParams& p, const rb_camera_ex& cam, ui
     return rb::launch_radiance(p, trace_args(e, e->q_rays.ptr, nullptr, out, done, m, first_sample, samples), e->stream, li, true);
 }
 
-int trace_camera_locked(rb_engine* e, const rb_camera_ex& cam, uint64_t first_pixel, size_t n, uint32_t first_sample, uint32_t samples,
-                        rb_radiance* out) {
-    rb::KParams p{};
-    e->cam_pieces = 0;
-    int rc = query_prologue(e, &p);
-    if (rc || n == 0) return rc;
-    const size_t piece = std::min(n, radiance_piece(RB_CAMERA_PIECE_ITEMS, samples));
-    rc = radiance_scratch(e, piece, samples, true);
-    if (rc) return rc;
-    HIP_TRY(e, e->rad_out.reserve(piece));
-    return run_pieces(e, "camera", piece, n, {}, {{out, e->rad_out.ptr, sizeof(rb_radiance)}}, [&](size_t done, size_t m, rb::LaunchInfo* li) {
-        return camera_piece(e, p, cam, first_pixel, done, m, first_sample, samples, e->rad_out.ptr, li);
-    });
-}
-
-// every piece queued between the query's two events (the pieces share the scratch in stream order); nothing is waited for
-int trace_camera_device_locked(rb_engine* e, const rb_camera_ex& cam, uint64_t first_pixel, size_t n, uint32_t first_sample,
-                               uint32_t samples, rb_radiance* d_out) {
-    const int rc = device_range(e, d_out, n * sizeof(rb_radiance), 16, "d_out");
-    if (rc) return rc;
-    const size_t piece = std::min(n, radiance_piece(RB_CAMERA_PIECE_ITEMS, samples));
-    e->cam_pieces = 0;
-    return device_query_locked(e, [&](const rb::KParams& p, rb::LaunchInfo* li) {
-        if (radiance_scratch(e, piece, samples, true)) return static_cast<int>(hipErrorOutOfMemory);
-        for (size_t done = 0; done < n; done += piece) {
-            const int st = camera_piece(e, p, cam, first_pixel, done, std::min(piece, n - done), first_sample, samples, d_out + done, li);
-            if (st) return st;
-        }
-        return 0;
-    });
+int trace_camera_locked(rb_engine* e, bool device, const rb_camera_ex& cam, uint64_t first_pixel, size_t n, uint32_t first_sample,
+                        uint32_t samples, rb_radiance* out) {
+    return run_family(e, device, "camera", RB_CAMERA_PIECE_ITEMS, n, samples, {}, FAMILY_ARRAY(out, e->rad_out, 16, "d_out"),
+                      [&](size_t piece) { return radiance_scratch(e, piece, samples, true); },
+                      [&](const rb::KParams& p, const void* const*, void* o, size_t done, size_t m, rb::LaunchInfo* li) {
+                          return camera_piece(e, p, cam, first_pixel, done, m, first_sample, samples, static_cast<rb_radiance*>(o), li);
+                      });
 }
 
 // ---- hemisphere rays made on the device (rb_abi.h)
@@ -436,52 +466,14 @@ int hemi_piece(rb_engine* e, const rb::KParams& p, const HemiCall& c, const rb_s
     return rb::launch_hemisphere_count(e->q_occl.ptr, static_cast<uint32_t>(m), c.samples, static_cast<rb_openness*>(out), e->stream);
 }
 
-size_t hemi_piece_surfels(size_t n, uint32_t samples) { return std::min(n, radiance_piece(RB_HEMI_PIECE_ITEMS, samples)); }
-
-int hemisphere_locked(rb_engine* e, const HemiCall& c, const rb_surfel* surfels, const uint32_t* seeds, size_t n, void* out) {
-    rb::KParams p{};
-    e->cam_pieces = 0;
-    int rc = query_prologue(e, &p);
-    if (rc || n == 0) return rc;
-    const size_t piece = hemi_piece_surfels(n, c.samples);
-    rc = hemi_scratch(e, c, piece);
-    if (rc) return rc;
-    HIP_TRY(e, e->hemi_surfels.reserve(piece));
-    if (seeds) HIP_TRY(e, e->rad_seeds.reserve(piece));
-    void* d_out = nullptr;
-    if (c.openness) {
-        HIP_TRY(e, e->hemi_open.reserve(piece));
-        d_out = e->hemi_open.ptr;
-    } else {
-        HIP_TRY(e, e->rad_out.reserve(piece));
-        d_out = e->rad_out.ptr;
-    }
-    const size_t out_stride = c.openness ? sizeof(rb_openness) : sizeof(rb_radiance);
-    return run_pieces(e, "hemisphere", piece, n, {{surfels, e->hemi_surfels.ptr, sizeof(rb_surfel)}, {seeds, e->rad_seeds.ptr, sizeof(uint32_t)}},
-                      {{out, d_out, out_stride}}, [&](size_t done, size_t m, rb::LaunchInfo* li) {
-                          return hemi_piece(e, p, c, e->hemi_surfels.ptr, seeds ? e->rad_seeds.ptr : nullptr, done, m, d_out, li);
+int hemisphere_locked(rb_engine* e, bool device, const HemiCall& c, const rb_surfel* surfels, const uint32_t* seeds, size_t n, void* out) {
+    return run_family(e, device, "hemisphere", RB_HEMI_PIECE_ITEMS, n, c.samples,
+                      {FAMILY_ARRAY(surfels, e->hemi_surfels, 16, "d_surfels"), FAMILY_ARRAY(seeds, e->rad_seeds, 4, "d_seeds")},
+                      c.openness ? FAMILY_ARRAY(out, e->hemi_open, 8, "d_out") : FAMILY_ARRAY(out, e->rad_out, 16, "d_out"),
+                      [&](size_t piece) { return hemi_scratch(e, c, piece); },
+                      [&](const rb::KParams& p, const void* const* in, void* o, size_t done, size_t m, rb::LaunchInfo* li) {
+                          return hemi_piece(e, p, c, static_cast<const rb_surfel*>(in[0]), static_cast<const uint32_t*>(in[1]), done, m, o, li);
                       });
-}
-
-// every piece queued between the query's two events on the caller's buffers (the pieces share the scratch in stream order);
-// nothing is waited for
-int hemisphere_device_locked(rb_engine* e, const HemiCall& c, const rb_surfel* d_surfels, const uint32_t* d_seeds, size_t n, void* d_out) {
-    const size_t out_stride = c.openness ? sizeof(rb_openness) : sizeof(rb_radiance);
-    int rc = device_range(e, d_surfels, n * sizeof(rb_surfel), 16, "d_surfels");
-    if (!rc && d_seeds) rc = device_range(e, d_seeds, n * sizeof(uint32_t), 4, "d_seeds");
-    if (!rc) rc = device_range(e, d_out, n * out_stride, c.openness ? 8 : 16, "d_out");
-    if (rc) return rc;
-    const size_t piece = hemi_piece_surfels(n, c.samples);
-    e->cam_pieces = 0;
-    return device_query_locked(e, [&](const rb::KParams& p, rb::LaunchInfo* li) {
-        if (hemi_scratch(e, c, piece)) return static_cast<int>(hipErrorOutOfMemory);
-        for (size_t done = 0; done < n; done += piece) {
-            const int st = hemi_piece(e, p, c, d_surfels + done, d_seeds ? d_seeds + done : nullptr, done, std::min(piece, n - done),
-                                      static_cast<char*>(d_out) + done * out_stride, li);
-            if (st) return st;
-        }
-        return 0;
-    });
 }
 
 // ---- irradiance probes made on the device (rb_abi.h)
@@ -520,45 +512,15 @@ int probe_piece(rb_engine* e, const rb::KParams& p, const rb_probe* probes, cons
     });
 }
 
-size_t probe_piece_probes(size_t n, uint32_t samples) { return std::min(n, radiance_piece(RB_PROBE_PIECE_ITEMS, samples)); }
-
-int probes_locked(rb_engine* e, const rb_probe* probes, const uint32_t* seeds, size_t n, uint32_t first_sample, uint32_t samples, rb_sh9* out) {
-    rb::KParams p{};
-    e->cam_pieces = e->sh_pieces = 0;
-    int rc = query_prologue(e, &p);
-    if (rc || n == 0) return rc;
-    const size_t piece = probe_piece_probes(n, samples);
-    rc = probe_scratch(e, piece, samples);
-    if (rc) return rc;
-    HIP_TRY(e, e->probe_pos.reserve(piece));
-    if (seeds) HIP_TRY(e, e->rad_seeds.reserve(piece));
-    HIP_TRY(e, e->probe_out.reserve(piece));
-    return run_pieces(e, "probe", piece, n, {{probes, e->probe_pos.ptr, sizeof(rb_probe)}, {seeds, e->rad_seeds.ptr, sizeof(uint32_t)}},
-                      {{out, e->probe_out.ptr, sizeof(rb_sh9)}}, [&](size_t done, size_t m, rb::LaunchInfo* li) {
-                          return probe_piece(e, p, e->probe_pos.ptr, seeds ? e->rad_seeds.ptr : nullptr, done, m, first_sample, samples,
-                                             e->probe_out.ptr, li);
+int probes_locked(rb_engine* e, bool device, const rb_probe* probes, const uint32_t* seeds, size_t n, uint32_t first_sample, uint32_t samples,
+                  rb_sh9* out) {
+    return run_family(e, device, "probe", RB_PROBE_PIECE_ITEMS, n, samples,
+                      {FAMILY_ARRAY(probes, e->probe_pos, 16, "d_probes"), FAMILY_ARRAY(seeds, e->rad_seeds, 4, "d_seeds")},
+                      FAMILY_ARRAY(out, e->probe_out, 16, "d_out"), [&](size_t piece) { return probe_scratch(e, piece, samples); },
+                      [&](const rb::KParams& p, const void* const* in, void* o, size_t done, size_t m, rb::LaunchInfo* li) {
+                          return probe_piece(e, p, static_cast<const rb_probe*>(in[0]), static_cast<const uint32_t*>(in[1]), done, m,
+                                             first_sample, samples, static_cast<rb_sh9*>(o), li);
                       });
-}
-
-// every piece queued between the query's two events on the caller's buffers (the pieces share the scratch in stream order);
-// nothing is waited for
-int probes_device_locked(rb_engine* e, const rb_probe* d_probes, const uint32_t* d_seeds, size_t n, uint32_t first_sample, uint32_t samples,
-                         rb_sh9* d_out) {
-    int rc = device_range(e, d_probes, n * sizeof(rb_probe), 16, "d_probes");
-    if (!rc && d_seeds) rc = device_range(e, d_seeds, n * sizeof(uint32_t), 4, "d_seeds");
-    if (!rc) rc = device_range(e, d_out, n * sizeof(rb_sh9), 16, "d_out");
-    if (rc) return rc;
-    const size_t piece = probe_piece_probes(n, samples);
-    e->cam_pieces = e->sh_pieces = 0;
-    return device_query_locked(e, [&](const rb::KParams& p, rb::LaunchInfo* li) {
-        if (probe_scratch(e, piece, samples)) return static_cast<int>(hipErrorOutOfMemory);
-        for (size_t done = 0; done < n; done += piece) {
-            const int st = probe_piece(e, p, d_probes + done, d_seeds ? d_seeds + done : nullptr, done, std::min(piece, n - done), first_sample,
-                                       samples, d_out + done, li);
-            if (st) return st;
-        }
-        return 0;
-    });
 }
 
 // ---- refusals that several entry points share, each under the entry point's own name `who`; before a device is touched
@@ -572,6 +534,14 @@ int samples_check(rb_engine* e, const char* who, const char* per, uint32_t first
     if (samples == 0 || samples > 65536u) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s takes 1 .. 65536 samples per %s, not %u", who, per, samples);
     if (static_cast<uint64_t>(first_sample) + samples > 0xFFFFFFFFull)
         return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: first_sample + samples = %u + %u does not fit 32 bits", who, first_sample, samples);
+    return RB_OK;
+}
+
+// the refusals the two forms of rb_occluded share, the device form's under its own argument names
+int occluded_check(rb_engine* e, const char* who, const char* null_text, const void* rays, size_t n, uint32_t mask, const void* out) {
+    if (const int rc = ray_count_check(e, who, n)) return rc;
+    if (mask > RB_MASK_ALL) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "mask has bits above RB_MASK_ALL");
+    if (n > 0 && (!rays || !out)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "%s", null_text);
     return RB_OK;
 }
 
@@ -612,6 +582,13 @@ int camera_check(rb_engine* e, const char* who, const rb_camera_ex* cam, uint64_
     if (c.kind == RB_CAM_ORTHO && (!(c.half_width > 0.0f) || !(c.half_height > 0.0f)))
         return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: an orthographic camera needs half_width > 0 and half_height > 0", who);
     return RB_OK;
+}
+
+// the refusals the two engine forms of rb_trace_camera share
+int trace_camera_check(rb_engine* e, const char* who, const char* out_name, const rb_camera_ex* cam, uint64_t first_pixel, size_t n_pixels,
+                       uint32_t first_sample, uint32_t samples, const void* out) {
+    if (n_pixels > 0 && (!cam || !out)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "%s: cam / %s is NULL", who, out_name);
+    return cam ? camera_check(e, who, cam, first_pixel, n_pixels, first_sample, samples) : RB_OK;
 }
 
 // the refusals every hemisphere entry point shares; before a device is touched (e may be NULL: rb_hemisphere_rays)
@@ -781,35 +758,46 @@ int answered(rb_engine* e, rb_engine* t, int rc) {
     return rc;
 }
 
+// The one shape of an engine entry point: a NULL handle, the lock, `check()` -- the refusals that need no device, recorded on
+// the handle --, the answering engine t made current, `run(t)`, its error copied to the handle.
+template <class Check, class Run>
+int engine_entry(rb_engine* e, Check&& check, Run&& run) {
+    if (!e) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (const int rc = check()) return rc;
+    rb_engine* const t = answering(e);
+    return answered(e, t, run(t));
+}
+
+// ... of n items: an empty call asks for a ready engine and does nothing else, in every form (section 11.1)
+template <class Check, class Run>
+int engine_entry(rb_engine* e, size_t n, Check&& check, Run&& run) {
+    return engine_entry(e, check, [&](rb_engine* t) { return n == 0 ? require_ready(t) : run(t); });
+}
 
 // the four engine entry points of the hemisphere family
 int hemisphere_entry(rb_engine* e, const char* who, bool openness, bool device, const rb_surfel* surfels, const uint32_t* seeds, size_t n,
                      const rb_hemi_params* prm, uint32_t first_sample, uint32_t samples, void* out) {
-    if (!e) return RB_ERR_NULL_ARGUMENT;
-    std::lock_guard<std::mutex> lock(e->mu);
-    if (n > 0 && (!surfels || !prm || !out)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "%s: surfels / params / out is NULL", who);
-    if (prm)
-        if (const int rc = hemi_check(e, who, prm, n, first_sample, samples, openness)) return rc;
-    rb_engine* const t = answering(e);
-    if (n == 0) return answered(e, t, require_ready(t));
-    const HemiCall c{*prm, first_sample, samples, openness};
-    return answered(e, t, device ? hemisphere_device_locked(t, c, surfels, seeds, n, out) : hemisphere_locked(t, c, surfels, seeds, n, out));
+    return engine_entry(
+        e, n,
+        [&] {
+            if (n > 0 && (!surfels || !prm || !out)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "%s: surfels / params / out is NULL", who);
+            return prm ? hemi_check(e, who, prm, n, first_sample, samples, openness) : RB_OK;
+        },
+        [&](rb_engine* t) { return hemisphere_locked(t, device, HemiCall{*prm, first_sample, samples, openness}, surfels, seeds, n, out); });
 }
-
 
 // the two engine entry points of the probe family
 int probes_entry(rb_engine* e, const char* who, bool device, const rb_probe* probes, const uint32_t* seeds, size_t n, uint32_t first_sample,
                  uint32_t samples, rb_sh9* out) {
-    if (!e) return RB_ERR_NULL_ARGUMENT;
-    std::lock_guard<std::mutex> lock(e->mu);
-    if (n > 0 && (!probes || !out)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "%s: probes / out is NULL", who);
-    if (const int rc = probe_check(e, who, n, first_sample, samples)) return rc;
-    rb_engine* const t = answering(e);
-    if (n == 0) return answered(e, t, require_ready(t));
-    return answered(e, t, device ? probes_device_locked(t, probes, seeds, n, first_sample, samples, out)
-                                 : probes_locked(t, probes, seeds, n, first_sample, samples, out));
+    return engine_entry(
+        e, n,
+        [&] {
+            if (n > 0 && (!probes || !out)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "%s: probes / out is NULL", who);
+            return probe_check(e, who, n, first_sample, samples);
+        },
+        [&](rb_engine* t) { return probes_locked(t, device, probes, seeds, n, first_sample, samples, out); });
 }
-
 
 // ---- lightmap texels made on the device (rb_abi.h)
 // the refusals every lightmap entry point shares; before a device is touched (e may be NULL: the engine-less forms)
@@ -899,7 +887,6 @@ int lightmap_surfels_device_locked(rb_engine* e, const rb_lightmap_params& prm, 
     if (!rc && d_owners) rc = device_range(e, d_owners, n * sizeof(uint32_t), 4, "d_owners");
     if (!rc) rc = lightmap_events(e);
     if (rc) return rc;
-    e->cam_pieces = 0;
     return device_query_locked(e, [&](const rb::KParams& p, rb::LaunchInfo* li) {
         if (lightmap_scratch(e, n, d_owners == nullptr)) return static_cast<int>(hipErrorOutOfMemory);
         li->kernel_name = "k_lm_surfels";
@@ -914,9 +901,8 @@ int bake_lightmap_queue(rb_engine* e, const rb_lightmap_params& prm, uint32_t fi
     rb_hemi_params hp{};
     hp.offset = prm.offset;
     const HemiCall c{hp, first_sample, samples, false};
-    const size_t piece = hemi_piece_surfels(n, samples);
+    const size_t piece = piece_items(RB_HEMI_PIECE_ITEMS, n, samples);
     if (const int rc = lightmap_events(e)) return rc;
-    e->cam_pieces = 0;
     return device_query_locked(e, [&](const rb::KParams& p, rb::LaunchInfo* li) {
         hipError_t st = hipSuccess;
         if (lightmap_scratch(e, n, true) || hemi_scratch(e, c, piece)) return static_cast<int>(hipErrorOutOfMemory);
@@ -926,8 +912,10 @@ int bake_lightmap_queue(rb_engine* e, const rb_lightmap_params& prm, uint32_t fi
         if (st != hipSuccess) return static_cast<int>(st);
         rb_radiance* const sums = d_sums ? d_sums : e->lm_sums.ptr;
         if (const int s = lightmap_stage_surfels(e, p, prm, e->lm_surfels.ptr, e->lm_owners.ptr)) return s;
-        for (size_t done = 0; done < n; done += piece)
-            if (const int s = hemi_piece(e, p, c, e->lm_surfels.ptr + done, nullptr, done, std::min(piece, n - done), sums + done, li)) return s;
+        if (const int s = for_pieces(n, piece, [&](size_t done, size_t m) {
+                return hemi_piece(e, p, c, e->lm_surfels.ptr + done, nullptr, done, m, sums + done, li);
+            }))
+            return s;
         if (!d_rgba) return 0;
         if (const hipError_t s = hipEventRecord(e->ev_lm[2], e->stream)) return static_cast<int>(s);
         if (const int s = rb::launch_lightmap_resolve(sums, prm.width, prm.height, prm.dilate, d_rgba, e->lm_rgba[1].ptr, e->stream)) return s;
@@ -961,104 +949,146 @@ int bake_lightmap_locked(rb_engine* e, const rb_lightmap_params& prm, uint32_t f
 
 int bake_lightmap_entry(rb_engine* e, const char* who, bool device, const rb_lightmap_params* prm, uint32_t first_sample, uint32_t samples,
                         float* rgba, rb_radiance* sums) {
-    if (!e) return RB_ERR_NULL_ARGUMENT;
-    std::lock_guard<std::mutex> lock(e->mu);
-    if (!prm || (!rgba && !sums)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "%s: params is NULL, or rgba_out and sums_out both are", who);
-    if (const int rc = lightmap_check(e, who, prm)) return rc;
-    rb_hemi_params hp{};
-    hp.offset = prm->offset;
-    if (const int rc = hemi_check(e, who, &hp, static_cast<size_t>(prm->width) * prm->height, first_sample, samples, false)) return rc;
-    rb_engine* const t = answering(e);
-    return answered(e, t, device ? bake_lightmap_device_locked(t, *prm, first_sample, samples, rgba, sums)
-                                 : bake_lightmap_locked(t, *prm, first_sample, samples, rgba, sums));
+    return engine_entry(
+        e,
+        [&] {
+            if (!prm || (!rgba && !sums)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "%s: params is NULL, or rgba_out and sums_out both are", who);
+            if (const int rc = lightmap_check(e, who, prm)) return rc;
+            rb_hemi_params hp{};
+            hp.offset = prm->offset;
+            return hemi_check(e, who, &hp, static_cast<size_t>(prm->width) * prm->height, first_sample, samples, false);
+        },
+        [&](rb_engine* t) {
+            return device ? bake_lightmap_device_locked(t, *prm, first_sample, samples, rgba, sums)
+                          : bake_lightmap_locked(t, *prm, first_sample, samples, rgba, sums);
+        });
 }
+
+// The scope of an engine-less form: `device` made current (below 0: the current one stays) and a non-blocking stream of the
+// call's own, with one sticky HIP status: once it is bad every member does nothing, so a call is its steps in order and none
+// of them runs on a buffer that was not allocated.  It does not own the call's DevBufs: DECLARE IT AFTER THEM, so that on every
+// path -- finish(), or the destructor where a return comes earlier -- the stream is synchronised before any of them is freed.
+struct DeviceScope {
+    hipStream_t stream = nullptr;
+    hipError_t st = hipSuccess;
+    int32_t refused = -1;   // the device hipSetDevice did not take
+    explicit DeviceScope(int32_t device) {
+        if (device >= 0 && hipSetDevice(device) != hipSuccess) {
+            refused = device;
+            st = hipErrorInvalidDevice;
+        } else {
+            st = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
+        }
+    }
+    DeviceScope(const DeviceScope&) = delete;
+    DeviceScope& operator=(const DeviceScope&) = delete;
+    ~DeviceScope() { close(); }
+    bool ok() const { return st == hipSuccess; }
+    template <class T>
+    void alloc(rb::DevBuf<T>& buf, size_t count) {
+        if (ok()) st = buf.resize(count);
+    }
+    void upload(void* dst, const void* src, size_t bytes) {
+        if (ok() && bytes) st = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream);
+    }
+    void download(void* dst, const void* src, size_t bytes) {
+        if (ok() && bytes) st = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream);
+    }
+    // `launch()` queues kernels on `stream` and returns a HIP status.  A callable, not the status: the launch itself must not
+    // happen once a step before it has failed.
+    template <class Launch>
+    void run(Launch&& launch) {
+        if (ok()) st = static_cast<hipError_t>(launch());
+    }
+    void sync() {
+        if (ok()) st = hipStreamSynchronize(stream);
+    }
+    void close() {
+        if (!stream) return;
+        const hipError_t s = hipStreamSynchronize(stream);   // whatever st is: the call's buffers are freed after this
+        if (ok()) st = s;
+        (void)hipStreamDestroy(stream);
+        stream = nullptr;
+    }
+    int finish(const char* who) {
+        close();
+        if (refused >= 0) return rb::fail(nullptr, RB_ERR_DEVICE, "hipSetDevice(%d) failed", refused);
+        return ok() ? RB_OK : rb::fail(nullptr, RB_ERR_DEVICE, "%s failed: %s", who, hipGetErrorString(st));
+    }
+};
 
 }  // namespace
 
 extern "C" {
 
 int rb_cast_rays(rb_engine* e, const rb_ray* rays, size_t n, rb_hit* hits_out, rb_surface* surf_out) {
-    if (!e) return RB_ERR_NULL_ARGUMENT;
-    std::lock_guard<std::mutex> lock(e->mu);
-    if (const int rc = ray_count_check(e, "rb_cast_rays", n)) return rc;
-    if (n > 0 && (!rays || !hits_out)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "rays / hits_out is NULL");
-    rb_engine* const t = answering(e);
-    return answered(e, t, cast_rays_locked(t, rays, n, hits_out, surf_out));
+    return engine_entry(
+        e, n,
+        [&]() -> int {
+            if (const int rc = ray_count_check(e, "rb_cast_rays", n)) return rc;
+            if (n > 0 && (!rays || !hits_out)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "rays / hits_out is NULL");
+            return RB_OK;
+        },
+        [&](rb_engine* t) { return cast_rays_locked(t, rays, n, hits_out, surf_out); });
 }
 
 int rb_render_hits(rb_engine* e, rb_hit* hits_out, rb_surface* surf_out) {
-    if (!e) return RB_ERR_NULL_ARGUMENT;
-    std::lock_guard<std::mutex> lock(e->mu);
-    if (!hits_out) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "hits_out is NULL");
-    rb_engine* const t = answering(e);
-    int rc = require_ready(t);
-    if (!rc) {
-        // a multi-device handle: the whole frame on devices[0] (one ray per pixel is not worth a gather); a sharded engine: its own rows
-        const bool sharded = t == e && t->opt.shard_count > 1;
-        rc = pixel_hits_locked(t, 0, 0, t->width, sharded ? t->padded_rows : t->height, !sharded, hits_out, surf_out);
-    }
-    return answered(e, t, rc);
+    return engine_entry(
+        e, [&]() -> int { return hits_out ? RB_OK : rb::fail(e, RB_ERR_NULL_ARGUMENT, "hits_out is NULL"); },
+        [&](rb_engine* t) {
+            if (const int rc = require_ready(t)) return rc;
+            // a multi-device handle: the whole frame on devices[0] (one ray per pixel is not worth a gather); a sharded engine: its own rows
+            const bool sharded = t == e && t->opt.shard_count > 1;
+            return pixel_hits_locked(t, 0, 0, t->width, sharded ? t->padded_rows : t->height, !sharded, hits_out, surf_out);
+        });
 }
 
 int rb_pick(rb_engine* e, uint32_t px, uint32_t py, rb_hit* hit_out, rb_surface* surf_out) {
-    if (!e) return RB_ERR_NULL_ARGUMENT;
-    std::lock_guard<std::mutex> lock(e->mu);
-    if (!hit_out) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "hit_out is NULL");
-    rb_engine* const t = answering(e);
-    int rc = require_ready(t);
-    if (!rc && (px >= t->width || py >= t->height)) rc = rb::fail(t, RB_ERR_INVALID_OPTIONS, "pixel (%u, %u) is outside the %u x %u image", px, py, t->width, t->height);
-    if (!rc) rc = pixel_hits_locked(t, px, py, 1, 1, true, hit_out, surf_out);
-    return answered(e, t, rc);
+    return engine_entry(
+        e, [&]() -> int { return hit_out ? RB_OK : rb::fail(e, RB_ERR_NULL_ARGUMENT, "hit_out is NULL"); },
+        [&](rb_engine* t) {
+            if (const int rc = require_ready(t)) return rc;
+            if (px >= t->width || py >= t->height)
+                return rb::fail(t, RB_ERR_INVALID_OPTIONS, "pixel (%u, %u) is outside the %u x %u image", px, py, t->width, t->height);
+            return pixel_hits_locked(t, px, py, 1, 1, true, hit_out, surf_out);
+        });
 }
 
 int rb_occluded(rb_engine* e, const rb_ray* rays, const float* tmax, size_t n, uint32_t mask, uint8_t* out) {
-    if (!e) return RB_ERR_NULL_ARGUMENT;
-    std::lock_guard<std::mutex> lock(e->mu);
-    if (const int rc = ray_count_check(e, "rb_occluded", n)) return rc;
-    if (mask > RB_MASK_ALL) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "mask has bits above RB_MASK_ALL");
-    if (n > 0 && (!rays || !out)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "rays / out is NULL");
-    rb_engine* const t = answering(e);
-    return answered(e, t, occluded_locked(t, rays, tmax, n, mask, out));
+    return engine_entry(
+        e, n, [&] { return occluded_check(e, "rb_occluded", "rays / out is NULL", rays, n, mask, out); },
+        [&](rb_engine* t) { return occluded_locked(t, rays, tmax, n, mask, out); });
 }
 
 int rb_occluded_device(rb_engine* e, const rb_ray* d_rays, const float* d_tmax, size_t n, uint32_t mask, uint8_t* d_out) {
-    if (!e) return RB_ERR_NULL_ARGUMENT;
-    std::lock_guard<std::mutex> lock(e->mu);
-    if (const int rc = ray_count_check(e, "rb_occluded_device", n)) return rc;
-    if (mask > RB_MASK_ALL) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "mask has bits above RB_MASK_ALL");
-    if (n > 0 && (!d_rays || !d_out)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "d_rays / d_out is NULL");
-    rb_engine* const t = answering(e);
-    if (n == 0) return answered(e, t, require_ready(t));
-    return answered(e, t, occluded_device_locked(t, d_rays, d_tmax, n, mask, d_out));
+    return engine_entry(
+        e, n, [&] { return occluded_check(e, "rb_occluded_device", "d_rays / d_out is NULL", d_rays, n, mask, d_out); },
+        [&](rb_engine* t) { return occluded_device_locked(t, d_rays, d_tmax, n, mask, d_out); });
 }
 
 int rb_cast_rays_device(rb_engine* e, const rb_ray* d_rays, size_t n, rb_hit* d_hits, rb_surface* d_surf) {
-    if (!e) return RB_ERR_NULL_ARGUMENT;
-    std::lock_guard<std::mutex> lock(e->mu);
-    if (const int rc = ray_count_check(e, "rb_cast_rays_device", n)) return rc;
-    if (n > 0 && (!d_rays || !d_hits)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "d_rays / d_hits is NULL");
-    rb_engine* const t = answering(e);
-    if (n == 0) return answered(e, t, require_ready(t));
-    return answered(e, t, cast_rays_device_locked(t, d_rays, n, d_hits, d_surf));
+    return engine_entry(
+        e, n,
+        [&]() -> int {
+            if (const int rc = ray_count_check(e, "rb_cast_rays_device", n)) return rc;
+            if (n > 0 && (!d_rays || !d_hits)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "d_rays / d_hits is NULL");
+            return RB_OK;
+        },
+        [&](rb_engine* t) { return cast_rays_device_locked(t, d_rays, n, d_hits, d_surf); });
 }
 
 int rb_trace_rays(rb_engine* e, const rb_ray* rays, const uint32_t* seeds, size_t n, uint32_t first_sample, uint32_t samples,
                   rb_radiance* out) {
-    if (!e) return RB_ERR_NULL_ARGUMENT;
-    std::lock_guard<std::mutex> lock(e->mu);
-    if (const int rc = trace_rays_check(e, "rb_trace_rays", rays, n, first_sample, samples, out)) return rc;
-    rb_engine* const t = answering(e);
-    return answered(e, t, trace_rays_locked(t, rays, seeds, n, first_sample, samples, out));
+    return engine_entry(
+        e, n, [&] { return trace_rays_check(e, "rb_trace_rays", rays, n, first_sample, samples, out); },
+        [&](rb_engine* t) { return trace_rays_locked(t, false, rays, seeds, n, first_sample, samples, out); });
 }
 
 int rb_trace_rays_device(rb_engine* e, const rb_ray* d_rays, const uint32_t* d_seeds, size_t n, uint32_t first_sample,
                          uint32_t samples, rb_radiance* d_out) {
-    if (!e) return RB_ERR_NULL_ARGUMENT;
-    std::lock_guard<std::mutex> lock(e->mu);
-    if (const int rc = trace_rays_check(e, "rb_trace_rays_device", d_rays, n, first_sample, samples, d_out)) return rc;
-    rb_engine* const t = answering(e);
-    if (n == 0) return answered(e, t, require_ready(t));
-    return answered(e, t, trace_rays_device_locked(t, d_rays, d_seeds, n, first_sample, samples, d_out));
+    return engine_entry(
+        e, n, [&] { return trace_rays_check(e, "rb_trace_rays_device", d_rays, n, first_sample, samples, d_out); },
+        [&](rb_engine* t) { return trace_rays_locked(t, true, d_rays, d_seeds, n, first_sample, samples, d_out); });
 }
 
 int rb_camera_rays(int32_t device, const rb_camera_ex* cam, uint64_t first_pixel, size_t n_pixels, uint32_t first_sample,
@@ -1067,15 +1097,13 @@ int rb_camera_rays(int32_t device, const rb_camera_ex* cam, uint64_t first_pixel
     if (cam)
         if (const int rc = camera_check(nullptr, "rb_camera_rays", cam, first_pixel, n_pixels, first_sample, samples)) return rc;
     if (n_pixels == 0) return RB_OK;
-    if (device >= 0 && hipSetDevice(device) != hipSuccess) return rb::fail(nullptr, RB_ERR_DEVICE, "hipSetDevice(%d) failed", device);
     const size_t items = n_pixels * samples, piece = std::min<size_t>(items, size_t(1) << 22);   // 128 + 16 MiB of scratch
     rb::DevBuf<rb_ray> d_rays;
     rb::DevBuf<uint32_t> d_seeds;
-    hipStream_t stream = nullptr;
-    hipError_t st = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
-    if (st == hipSuccess) st = d_rays.resize(piece);
-    if (st == hipSuccess) st = d_seeds.resize(piece);
-    for (size_t done = 0; done < items && st == hipSuccess; done += piece) {
+    DeviceScope s(device);
+    s.alloc(d_rays, piece);
+    s.alloc(d_seeds, piece);
+    for (size_t done = 0; done < items && s.ok(); done += piece) {
         const size_t m = std::min(piece, items - done);
         rb::CamGenArgs g{};
         g.cam = *cam;
@@ -1087,39 +1115,27 @@ int rb_camera_rays(int32_t device, const rb_camera_ex* cam, uint64_t first_pixel
         g.first_sample = first_sample;
         g.samples = samples;
         g.linear = 1u;
-        st = static_cast<hipError_t>(rb::launch_camera_rays(g, stream));
-        if (st == hipSuccess) st = hipMemcpyAsync(rays_out + done, d_rays.ptr, m * sizeof(rb_ray), hipMemcpyDeviceToHost, stream);
-        if (st == hipSuccess) st = hipMemcpyAsync(seeds_out + done, d_seeds.ptr, m * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
-        if (st == hipSuccess) st = hipStreamSynchronize(stream);   // the scratch is the next piece's
+        s.run([&] { return rb::launch_camera_rays(g, s.stream); });
+        s.download(rays_out + done, d_rays.ptr, m * sizeof(rb_ray));
+        s.download(seeds_out + done, d_seeds.ptr, m * sizeof(uint32_t));
+        s.sync();   // the scratch is the next piece's
     }
-    if (stream) (void)hipStreamSynchronize(stream);   // (the buffers are freed on return, after this)
-    if (stream) (void)hipStreamDestroy(stream);
-    if (st != hipSuccess) return rb::fail(nullptr, RB_ERR_DEVICE, "rb_camera_rays failed: %s", hipGetErrorString(st));
-    return RB_OK;
+    return s.finish("rb_camera_rays");
 }
 
 int rb_trace_camera(rb_engine* e, const rb_camera_ex* cam, uint64_t first_pixel, size_t n_pixels, uint32_t first_sample,
                     uint32_t samples, rb_radiance* out) {
-    if (!e) return RB_ERR_NULL_ARGUMENT;
-    std::lock_guard<std::mutex> lock(e->mu);
-    if (n_pixels > 0 && (!cam || !out)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "rb_trace_camera: cam / out is NULL");
-    if (cam)
-        if (const int rc = camera_check(e, "rb_trace_camera", cam, first_pixel, n_pixels, first_sample, samples)) return rc;
-    rb_engine* const t = answering(e);
-    if (n_pixels == 0) return answered(e, t, require_ready(t));
-    return answered(e, t, trace_camera_locked(t, *cam, first_pixel, n_pixels, first_sample, samples, out));
+    return engine_entry(
+        e, n_pixels, [&] { return trace_camera_check(e, "rb_trace_camera", "out", cam, first_pixel, n_pixels, first_sample, samples, out); },
+        [&](rb_engine* t) { return trace_camera_locked(t, false, *cam, first_pixel, n_pixels, first_sample, samples, out); });
 }
 
 int rb_trace_camera_device(rb_engine* e, const rb_camera_ex* cam, uint64_t first_pixel, size_t n_pixels, uint32_t first_sample,
                            uint32_t samples, rb_radiance* d_out) {
-    if (!e) return RB_ERR_NULL_ARGUMENT;
-    std::lock_guard<std::mutex> lock(e->mu);
-    if (n_pixels > 0 && (!cam || !d_out)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "rb_trace_camera_device: cam / d_out is NULL");
-    if (cam)
-        if (const int rc = camera_check(e, "rb_trace_camera_device", cam, first_pixel, n_pixels, first_sample, samples)) return rc;
-    rb_engine* const t = answering(e);
-    if (n_pixels == 0) return answered(e, t, require_ready(t));
-    return answered(e, t, trace_camera_device_locked(t, *cam, first_pixel, n_pixels, first_sample, samples, d_out));
+    return engine_entry(
+        e, n_pixels,
+        [&] { return trace_camera_check(e, "rb_trace_camera_device", "d_out", cam, first_pixel, n_pixels, first_sample, samples, d_out); },
+        [&](rb_engine* t) { return trace_camera_locked(t, true, *cam, first_pixel, n_pixels, first_sample, samples, d_out); });
 }
 
 int rb_hemisphere_rays(int32_t device, const rb_surfel* surfels, const uint32_t* seeds, size_t n, const rb_hemi_params* params,
@@ -1129,34 +1145,29 @@ int rb_hemisphere_rays(int32_t device, const rb_surfel* surfels, const uint32_t*
     if (params)
         if (const int rc = hemi_check(nullptr, "rb_hemisphere_rays", params, n, first_sample, samples, false)) return rc;
     if (n == 0) return RB_OK;
-    if (device >= 0 && hipSetDevice(device) != hipSuccess) return rb::fail(nullptr, RB_ERR_DEVICE, "hipSetDevice(%d) failed", device);
     const size_t piece = std::min(n, std::max<size_t>((size_t(1) << 22) / samples, 1));   // whole surfels, about 2^22 items
     rb::DevBuf<rb_surfel> d_surfels;
     rb::DevBuf<uint32_t> d_ids, d_seeds;
     rb::DevBuf<rb_ray> d_rays;
-    hipStream_t stream = nullptr;
-    hipError_t st = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
-    if (st == hipSuccess) st = d_surfels.resize(piece);
-    if (st == hipSuccess && seeds) st = d_ids.resize(piece);
-    if (st == hipSuccess) st = d_rays.resize(piece * samples);
-    if (st == hipSuccess) st = d_seeds.resize(piece * samples);
+    DeviceScope s(device);
+    s.alloc(d_surfels, piece);
+    if (seeds) s.alloc(d_ids, piece);
+    s.alloc(d_rays, piece * samples);
+    s.alloc(d_seeds, piece * samples);
     const HemiCall c{*params, first_sample, samples, false};
-    for (size_t done = 0; done < n && st == hipSuccess; done += piece) {
+    for (size_t done = 0; done < n && s.ok(); done += piece) {
         const size_t m = std::min(piece, n - done), items = m * samples;
-        st = hipMemcpyAsync(d_surfels.ptr, surfels + done, m * sizeof(rb_surfel), hipMemcpyHostToDevice, stream);
-        if (st == hipSuccess && seeds) st = hipMemcpyAsync(d_ids.ptr, seeds + done, m * sizeof(uint32_t), hipMemcpyHostToDevice, stream);
+        s.upload(d_surfels.ptr, surfels + done, m * sizeof(rb_surfel));
+        if (seeds) s.upload(d_ids.ptr, seeds + done, m * sizeof(uint32_t));
         rb::HemiGenArgs g = hemi_gen_args(c, d_surfels.ptr, seeds ? d_ids.ptr : nullptr, d_rays.ptr, done, m);
         g.seeds = d_seeds.ptr;
         g.linear = 1u;
-        if (st == hipSuccess) st = static_cast<hipError_t>(rb::launch_hemisphere_rays(g, stream));
-        if (st == hipSuccess) st = hipMemcpyAsync(rays_out + done * samples, d_rays.ptr, items * sizeof(rb_ray), hipMemcpyDeviceToHost, stream);
-        if (st == hipSuccess) st = hipMemcpyAsync(seeds_out + done * samples, d_seeds.ptr, items * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
-        if (st == hipSuccess) st = hipStreamSynchronize(stream);   // the scratch is the next piece's
+        s.run([&] { return rb::launch_hemisphere_rays(g, s.stream); });
+        s.download(rays_out + done * samples, d_rays.ptr, items * sizeof(rb_ray));
+        s.download(seeds_out + done * samples, d_seeds.ptr, items * sizeof(uint32_t));
+        s.sync();   // the scratch is the next piece's
     }
-    if (stream) (void)hipStreamSynchronize(stream);   // (the buffers are freed on return, after this)
-    if (stream) (void)hipStreamDestroy(stream);
-    if (st != hipSuccess) return rb::fail(nullptr, RB_ERR_DEVICE, "rb_hemisphere_rays failed: %s", hipGetErrorString(st));
-    return RB_OK;
+    return s.finish("rb_hemisphere_rays");
 }
 
 int rb_trace_hemisphere(rb_engine* e, const rb_surfel* surfels, const uint32_t* seeds, size_t n, const rb_hemi_params* params,
@@ -1184,34 +1195,28 @@ int rb_probe_rays(int32_t device, const rb_probe* probes, const uint32_t* seeds,
     if (n > 0 && (!probes || !rays_out)) return rb::fail(nullptr, RB_ERR_NULL_ARGUMENT, "probes / rays_out is NULL");
     if (const int rc = probe_check(nullptr, "rb_probe_rays", n, first_sample, samples)) return rc;
     if (n == 0) return RB_OK;
-    if (device >= 0 && hipSetDevice(device) != hipSuccess) return rb::fail(nullptr, RB_ERR_DEVICE, "hipSetDevice(%d) failed", device);
     const size_t piece = std::min(n, std::max<size_t>((size_t(1) << 22) / samples, 1));   // whole probes, about 2^22 items
     rb::DevBuf<rb_probe> d_probes;
     rb::DevBuf<uint32_t> d_ids, d_seeds;
     rb::DevBuf<rb_ray> d_rays;
-    hipStream_t stream = nullptr;
-    hipError_t st = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
-    if (st == hipSuccess) st = d_probes.resize(piece);
-    if (st == hipSuccess && seeds) st = d_ids.resize(piece);
-    if (st == hipSuccess) st = d_rays.resize(piece * samples);
-    if (st == hipSuccess && seeds_out) st = d_seeds.resize(piece * samples);
-    for (size_t done = 0; done < n && st == hipSuccess; done += piece) {
+    DeviceScope s(device);
+    s.alloc(d_probes, piece);
+    if (seeds) s.alloc(d_ids, piece);
+    s.alloc(d_rays, piece * samples);
+    if (seeds_out) s.alloc(d_seeds, piece * samples);
+    for (size_t done = 0; done < n && s.ok(); done += piece) {
         const size_t m = std::min(piece, n - done), items = m * samples;
-        st = hipMemcpyAsync(d_probes.ptr, probes + done, m * sizeof(rb_probe), hipMemcpyHostToDevice, stream);
-        if (st == hipSuccess && seeds) st = hipMemcpyAsync(d_ids.ptr, seeds + done, m * sizeof(uint32_t), hipMemcpyHostToDevice, stream);
+        s.upload(d_probes.ptr, probes + done, m * sizeof(rb_probe));
+        if (seeds) s.upload(d_ids.ptr, seeds + done, m * sizeof(uint32_t));
         rb::ProbeGenArgs g = probe_gen_args(d_probes.ptr, seeds ? d_ids.ptr : nullptr, d_rays.ptr, done, m, first_sample, samples);
         g.seeds = seeds_out ? d_seeds.ptr : nullptr;
         g.linear = 1u;
-        if (st == hipSuccess) st = static_cast<hipError_t>(rb::launch_probe_rays(g, stream));
-        if (st == hipSuccess) st = hipMemcpyAsync(rays_out + done * samples, d_rays.ptr, items * sizeof(rb_ray), hipMemcpyDeviceToHost, stream);
-        if (st == hipSuccess && seeds_out)
-            st = hipMemcpyAsync(seeds_out + done * samples, d_seeds.ptr, items * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
-        if (st == hipSuccess) st = hipStreamSynchronize(stream);   // the scratch is the next piece's
+        s.run([&] { return rb::launch_probe_rays(g, s.stream); });
+        s.download(rays_out + done * samples, d_rays.ptr, items * sizeof(rb_ray));
+        if (seeds_out) s.download(seeds_out + done * samples, d_seeds.ptr, items * sizeof(uint32_t));
+        s.sync();   // the scratch is the next piece's
     }
-    if (stream) (void)hipStreamSynchronize(stream);   // (the buffers are freed on return, after this)
-    if (stream) (void)hipStreamDestroy(stream);
-    if (st != hipSuccess) return rb::fail(nullptr, RB_ERR_DEVICE, "rb_probe_rays failed: %s", hipGetErrorString(st));
-    return RB_OK;
+    return s.finish("rb_probe_rays");
 }
 
 int rb_bake_probes(rb_engine* e, const rb_probe* probes, const uint32_t* seeds, size_t n, uint32_t first_sample, uint32_t samples, rb_sh9* out) {
@@ -1236,7 +1241,6 @@ int rb_lightmap_surfels(int32_t device, const rb_gpu_triangle* tris, size_t n_tr
         if (owners_out) std::memset(owners_out, 0xFF, n * sizeof(uint32_t));
         return RB_OK;
     }
-    if (device >= 0 && hipSetDevice(device) != hipSuccess) return rb::fail(nullptr, RB_ERR_DEVICE, "hipSetDevice(%d) failed", device);
     const uint32_t nt = static_cast<uint32_t>(n_tris), nu = static_cast<uint32_t>(n_uv_floats);
     rb::DevBuf<rb_gpu_triangle> d_tris;
     rb::DevBuf<float> d_uvs;
@@ -1245,59 +1249,50 @@ int rb_lightmap_surfels(int32_t device, const rb_gpu_triangle* tris, size_t n_tr
     rb::DevBuf<rb::PrepTriShade> d_pshade;
     rb::DevBuf<unsigned char> d_work;
     rb::DevBuf<rb_surfel> d_surfels;
-    hipStream_t stream = nullptr;
-    hipError_t st = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
-    if (st == hipSuccess) st = d_tris.resize(nt);
-    if (st == hipSuccess) st = d_uvs.resize(nu);
-    if (st == hipSuccess) st = d_iota.resize(nt);
-    if (st == hipSuccess) st = d_ptris.resize(nt);
-    if (st == hipSuccess) st = d_pshade.resize(nt);
-    if (st == hipSuccess) st = d_work.resize(rb::lightmap_work_bytes(nt));
-    if (st == hipSuccess) st = d_owners.resize(n);
-    if (st == hipSuccess) st = d_surfels.resize(n);
-    if (st == hipSuccess) st = hipMemcpyAsync(d_tris.ptr, tris, n_tris * sizeof(rb_gpu_triangle), hipMemcpyHostToDevice, stream);
-    if (st == hipSuccess && nu) st = hipMemcpyAsync(d_uvs.ptr, uvs, n_uv_floats * sizeof(float), hipMemcpyHostToDevice, stream);
-    if (st == hipSuccess)   // every triangle counts as valid: tri_count = n_tris
-        st = static_cast<hipError_t>(lightmap_generate(*params, d_tris.ptr, nt, nt, d_uvs.ptr, nu, d_iota.ptr, d_ptris.ptr, d_pshade.ptr, d_work.ptr,
-                                                       d_surfels.ptr, d_owners.ptr, stream));
-    if (st == hipSuccess) st = hipMemcpyAsync(surfels_out, d_surfels.ptr, n * sizeof(rb_surfel), hipMemcpyDeviceToHost, stream);
-    if (st == hipSuccess && owners_out) st = hipMemcpyAsync(owners_out, d_owners.ptr, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
-    if (st == hipSuccess) st = hipStreamSynchronize(stream);
-    if (stream) (void)hipStreamSynchronize(stream);   // (the buffers are freed on return, after this)
-    if (stream) (void)hipStreamDestroy(stream);
-    if (st != hipSuccess) return rb::fail(nullptr, RB_ERR_DEVICE, "rb_lightmap_surfels failed: %s", hipGetErrorString(st));
-    return RB_OK;
+    DeviceScope s(device);
+    s.alloc(d_tris, nt);
+    s.alloc(d_uvs, nu);
+    s.alloc(d_iota, nt);
+    s.alloc(d_ptris, nt);
+    s.alloc(d_pshade, nt);
+    s.alloc(d_work, rb::lightmap_work_bytes(nt));
+    s.alloc(d_owners, n);
+    s.alloc(d_surfels, n);
+    s.upload(d_tris.ptr, tris, n_tris * sizeof(rb_gpu_triangle));
+    s.upload(d_uvs.ptr, uvs, n_uv_floats * sizeof(float));
+    s.run([&] {   // every triangle counts as valid: tri_count = n_tris
+        return lightmap_generate(*params, d_tris.ptr, nt, nt, d_uvs.ptr, nu, d_iota.ptr, d_ptris.ptr, d_pshade.ptr, d_work.ptr, d_surfels.ptr,
+                                 d_owners.ptr, s.stream);
+    });
+    s.download(surfels_out, d_surfels.ptr, n * sizeof(rb_surfel));
+    if (owners_out) s.download(owners_out, d_owners.ptr, n * sizeof(uint32_t));
+    return s.finish("rb_lightmap_surfels");
 }
 
 int rb_lightmap_surfels_device(rb_engine* e, const rb_lightmap_params* params, rb_surfel* d_surfels, uint32_t* d_owners) {
-    if (!e) return RB_ERR_NULL_ARGUMENT;
-    std::lock_guard<std::mutex> lock(e->mu);
-    if (!params || !d_surfels) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "rb_lightmap_surfels_device: params / d_surfels is NULL");
-    if (const int rc = lightmap_check(e, "rb_lightmap_surfels_device", params)) return rc;
-    rb_engine* const t = answering(e);
-    return answered(e, t, lightmap_surfels_device_locked(t, *params, d_surfels, d_owners));
+    return engine_entry(
+        e,
+        [&] {
+            if (!params || !d_surfels) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "rb_lightmap_surfels_device: params / d_surfels is NULL");
+            return lightmap_check(e, "rb_lightmap_surfels_device", params);
+        },
+        [&](rb_engine* t) { return lightmap_surfels_device_locked(t, *params, d_surfels, d_owners); });
 }
 
 int rb_lightmap_resolve(int32_t device, uint32_t width, uint32_t height, const rb_radiance* sums, uint32_t dilate, float* rgba_out) {
     if (!sums || !rgba_out) return rb::fail(nullptr, RB_ERR_NULL_ARGUMENT, "rb_lightmap_resolve: sums / rgba_out is NULL");
     if (const int rc = lightmap_size_check(nullptr, "rb_lightmap_resolve", width, height, dilate)) return rc;
-    if (device >= 0 && hipSetDevice(device) != hipSuccess) return rb::fail(nullptr, RB_ERR_DEVICE, "hipSetDevice(%d) failed", device);
     const size_t n = static_cast<size_t>(width) * height;
     rb::DevBuf<rb_radiance> d_sums;
     rb::DevBuf<float> d_out, d_tmp;
-    hipStream_t stream = nullptr;
-    hipError_t st = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
-    if (st == hipSuccess) st = d_sums.resize(n);
-    if (st == hipSuccess) st = d_out.resize(n * 4);
-    if (st == hipSuccess && dilate > 0u) st = d_tmp.resize(n * 4);
-    if (st == hipSuccess) st = hipMemcpyAsync(d_sums.ptr, sums, n * sizeof(rb_radiance), hipMemcpyHostToDevice, stream);
-    if (st == hipSuccess) st = static_cast<hipError_t>(rb::launch_lightmap_resolve(d_sums.ptr, width, height, dilate, d_out.ptr, d_tmp.ptr, stream));
-    if (st == hipSuccess) st = hipMemcpyAsync(rgba_out, d_out.ptr, n * 16, hipMemcpyDeviceToHost, stream);
-    if (st == hipSuccess) st = hipStreamSynchronize(stream);
-    if (stream) (void)hipStreamSynchronize(stream);   // (the buffers are freed on return, after this)
-    if (stream) (void)hipStreamDestroy(stream);
-    if (st != hipSuccess) return rb::fail(nullptr, RB_ERR_DEVICE, "rb_lightmap_resolve failed: %s", hipGetErrorString(st));
-    return RB_OK;
+    DeviceScope s(device);
+    s.alloc(d_sums, n);
+    s.alloc(d_out, n * 4);
+    if (dilate > 0u) s.alloc(d_tmp, n * 4);
+    s.upload(d_sums.ptr, sums, n * sizeof(rb_radiance));
+    s.run([&] { return rb::launch_lightmap_resolve(d_sums.ptr, width, height, dilate, d_out.ptr, d_tmp.ptr, s.stream); });
+    s.download(rgba_out, d_out.ptr, n * 16);
+    return s.finish("rb_lightmap_resolve");
 }
 
 int rb_bake_lightmap(rb_engine* e, const rb_lightmap_params* params, uint32_t first_sample, uint32_t samples, float* rgba_out,
@@ -1378,19 +1373,16 @@ int rb_denoise_buffers(int32_t device, const rb_denoise_params* params, uint32_t
     const size_t n = static_cast<size_t>(w) * h;
     if (n >= (1ull << 31)) return rb::fail(nullptr, RB_ERR_INVALID_OPTIONS, "a frame of %u x %u pixels is too large", w, h);
     if (n == 0) return RB_OK;
-    if (device >= 0 && hipSetDevice(device) != hipSuccess) return rb::fail(nullptr, RB_ERR_DEVICE, "hipSetDevice(%d) failed", device);
     rb::DevBuf<float> d_color, d_nt, d_pc, d_al, d_r0, d_r1, d_linear;
     rb::DevBuf<rb_guide> d_guides;
     rb::DevBuf<uint32_t> d_rgba;
-    hipStream_t stream = nullptr;
-    hipError_t st = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
-    for (rb::DevBuf<float>* b : {&d_color, &d_nt, &d_pc, &d_al, &d_r0, &d_r1})
-        if (st == hipSuccess) st = b->resize(n * 4);
-    if (st == hipSuccess) st = d_guides.resize(n);
-    if (st == hipSuccess && out4) st = d_linear.resize(n * 4);
-    if (st == hipSuccess && rgba_out) st = d_rgba.resize(n);
-    if (st == hipSuccess) st = hipMemcpyAsync(d_color.ptr, color4, n * 16, hipMemcpyHostToDevice, stream);
-    if (st == hipSuccess) st = hipMemcpyAsync(d_guides.ptr, guides, n * sizeof(rb_guide), hipMemcpyHostToDevice, stream);
+    DeviceScope s(device);
+    for (rb::DevBuf<float>* b : {&d_color, &d_nt, &d_pc, &d_al, &d_r0, &d_r1}) s.alloc(*b, n * 4);
+    s.alloc(d_guides, n);
+    if (out4) s.alloc(d_linear, n * 4);
+    if (rgba_out) s.alloc(d_rgba, n);
+    s.upload(d_color.ptr, color4, n * 16);
+    s.upload(d_guides.ptr, guides, n * sizeof(rb_guide));
     rb::DenoiseArgs a{};
     a.w = w;
     a.h = h;
@@ -1400,15 +1392,11 @@ int rb_denoise_buffers(int32_t device, const rb_denoise_params* params, uint32_t
     a.r[1] = d_r1.ptr;
     a.linear_out = d_linear.ptr;
     a.rgba_out = d_rgba.ptr;
-    if (st == hipSuccess) st = static_cast<hipError_t>(rb::launch_guide_split(d_guides.ptr, n, a.g, stream));
-    if (st == hipSuccess) st = static_cast<hipError_t>(rb::launch_denoise(*params, a, stream));
-    if (st == hipSuccess && out4) st = hipMemcpyAsync(out4, d_linear.ptr, n * 16, hipMemcpyDeviceToHost, stream);
-    if (st == hipSuccess && rgba_out) st = hipMemcpyAsync(rgba_out, d_rgba.ptr, n * 4, hipMemcpyDeviceToHost, stream);
-    if (st == hipSuccess) st = hipStreamSynchronize(stream);
-    if (stream) (void)hipStreamSynchronize(stream);   // (the buffers are freed on return, after this)
-    if (stream) (void)hipStreamDestroy(stream);
-    if (st != hipSuccess) return rb::fail(nullptr, RB_ERR_DEVICE, "rb_denoise_buffers failed: %s", hipGetErrorString(st));
-    return RB_OK;
+    s.run([&] { return rb::launch_guide_split(d_guides.ptr, n, a.g, s.stream); });
+    s.run([&] { return rb::launch_denoise(*params, a, s.stream); });
+    if (out4) s.download(out4, d_linear.ptr, n * 16);
+    if (rgba_out) s.download(rgba_out, d_rgba.ptr, n * 4);
+    return s.finish("rb_denoise_buffers");
 }
 
 const char* rb_last_query_kernel_name(const rb_engine* e) {

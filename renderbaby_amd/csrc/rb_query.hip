@@ -41,10 +41,6 @@ struct QueryLane {
     bool valid;   // ... and it is finite after normalisation, and for a pixel inside the image
 };
 
-DEV bool finite3(f3 a) {
-    const uint32_t m = 0x7F800000u;
-    return (__float_as_uint(a.x) & m) != m && (__float_as_uint(a.y) & m) != m && (__float_as_uint(a.z) & m) != m;
-}
 // a direction the walks can take: finite and not zero (a vector whose squared length overflows normalises to (0, 0, 0): every
 // slab test would say "enter", and |d| = 1 +- 4 ulp, what the culling margins are derived for, would not hold)
 DEV bool usable_dir(f3 d) { return finite3(d) && !(d.x == 0.0f && d.y == 0.0f && d.z == 0.0f); }

@@ -35,11 +35,6 @@ constexpr uint32_t kRadBlock = 256;
 #define RB_RAD_FINISH_LANES 32 // k_trace_chunk's RB_CHUNK_FINISH_LANES
 #endif
 
-DEV bool rad_finite3(f3 a) {
-    const uint32_t m = 0x7F800000u;
-    return (__float_as_uint(a.x) & m) != m && (__float_as_uint(a.y) & m) != m && (__float_as_uint(a.z) & m) != m;
-}
-
 // ---- (ray, sample) items.  Item = (block * S + sample) * 64 + ray-in-block, block = 64 consecutive rays of the piece.
 // A refill round hands out at most 64 consecutive items starting at the wave-uniform `base`, so a lane's item lies in the
 // 64-item row of `base` or in the next one (item_rows' argument, rb_device_shade.hpp).
@@ -72,7 +67,7 @@ DEV bool rad_start(const KParams& p, const RadArgs& a, uint32_t it, uint32_t ray
     const v4f ra = ((const v4f*)a.rays)[(size_t)ray * 2u], rd = ((const v4f*)a.rays)[(size_t)ray * 2u + 1u];
     pt.o = mk(ra.x, ra.y, ra.z);
     pt.d = normalize(mk(rd.x, rd.y, rd.z));
-    const bool valid = rad_finite3(pt.o) && rad_finite3(pt.d) && !(pt.d.x == 0.0f && pt.d.y == 0.0f && pt.d.z == 0.0f);
+    const bool valid = finite3(pt.o) && finite3(pt.d) && !(pt.d.x == 0.0f && pt.d.y == 0.0f && pt.d.z == 0.0f);
     const uint32_t sid = a.seeds != nullptr ? a.seeds[ray] : a.seed_base + ray;
     pt.seed = pcg(sid + hs);
     pt.color = mk(0, 0, 0);

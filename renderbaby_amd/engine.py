@@ -172,6 +172,32 @@ def _is_tensor(x):
     return type(x).__module__.split(".")[0] == "torch" and hasattr(x, "data_ptr")
 
 
+def _sample_range(samples, first_sample):
+    """(samples, first_sample) as the 32-bit unsigned numbers the ABI takes"""
+    samples, first_sample = int(samples), int(first_sample)
+    if not (0 <= samples < 2 ** 32 and 0 <= first_sample < 2 ** 32):
+        raise ValueError("samples and first_sample are 32-bit unsigned numbers")
+    return samples, first_sample
+
+
+def _seed_array(seeds, n, what):
+    """the ``seeds`` of a host form of n items (`what`: what the items are called) as contiguous uint32, or None"""
+    if seeds is None:
+        return None
+    seeds = np.ascontiguousarray(seeds, dtype=np.uint32).reshape(-1)
+    if len(seeds) != n:
+        raise ValueError(f"{what} and seeds differ in length")
+    return seeds
+
+
+def _host_out(out, n, dtype, what):
+    """the result array of a host form: ``out``, which must be n contiguous `dtype` records (`what` says so), or a new one"""
+    res = np.empty(n, dtype=dtype) if out is None else out
+    if not isinstance(res, np.ndarray) or res.dtype != dtype or res.shape != (n,) or not res.flags.c_contiguous:
+        raise ValueError(f"out: a contiguous {what} is needed")
+    return res
+
+
 class Engine:
     """``engine_pathtracer::Engine`` for the HIP backend."""
 
@@ -430,6 +456,15 @@ class Engine:
             raise ValueError(f"{what}: shape (n, {row}) is needed")
         return (t.data_ptr() if t.numel() else None), t.shape[0]
 
+    def _seed_tensor(self, seeds, n):
+        """(pointer, length) of the ``seeds`` of a device form of n items -- a tensor of 32-bit ids, signed or unsigned: the bits
+        are what counts --, (None, n) without seeds"""
+        if seeds is None:
+            return None, n
+        import torch
+        unsigned = _is_tensor(seeds) and seeds.dtype == getattr(torch, "uint32", None)
+        return self._device_tensor(seeds, torch.uint32 if unsigned else torch.int32, None, "seeds")
+
     def _device_call(self, fn, *args):
         """a device form between torch's stream and the engine's: torch's queued work first, rb_sync after"""
         import torch
@@ -504,16 +539,11 @@ class Engine:
     def trace_ray_records(self, rays, seeds=None, samples=1, first_sample=0, out=None):
         """rb_trace_rays on an abi.RAY array, or rb_trace_rays_device on a float32 tensor of shape (n, 8) (``seeds``: an int32
         or uint32 tensor of n elements, its bits are the ids; ``out``: a float32 tensor of shape (n, 4))."""
-        samples, first_sample = int(samples), int(first_sample)
-        if not (0 <= samples < 2 ** 32 and 0 <= first_sample < 2 ** 32):
-            raise ValueError("samples and first_sample are 32-bit unsigned numbers")
+        samples, first_sample = _sample_range(samples, first_sample)
         if _is_tensor(rays) or _is_tensor(seeds) or _is_tensor(out):
             import torch
             rp, n = self._device_tensor(rays, torch.float32, 8, "rays")
-            sp, ns = (None, n)
-            if seeds is not None:   # 32-bit ids, signed or unsigned: the bits are what counts
-                unsigned = _is_tensor(seeds) and seeds.dtype == getattr(torch, "uint32", None)
-                sp, ns = self._device_tensor(seeds, torch.uint32 if unsigned else torch.int32, None, "seeds")
+            sp, ns = self._seed_tensor(seeds, n)
             res = torch.empty((n, 4), dtype=torch.float32, device=rays.device) if out is None else out
             op, no = self._device_tensor(res, torch.float32, 4, "out")
             if ns != n or no != n:
@@ -524,13 +554,8 @@ class Engine:
             raise ValueError("rays: an abi.RAY array or a float32 tensor of shape (n, 8) is needed")
         rays = np.ascontiguousarray(rays, dtype=abi.RAY)
         n = len(rays)
-        if seeds is not None:
-            seeds = np.ascontiguousarray(seeds, dtype=np.uint32).reshape(-1)
-            if len(seeds) != n:
-                raise ValueError("rays and seeds differ in length")
-        res = np.empty(n, dtype=abi.RADIANCE) if out is None else out
-        if not isinstance(res, np.ndarray) or res.dtype != abi.RADIANCE or res.shape != (n,) or not res.flags.c_contiguous:
-            raise ValueError("out: a contiguous abi.RADIANCE array of n elements is needed")
+        seeds = _seed_array(seeds, n, "rays")
+        res = _host_out(out, n, abi.RADIANCE, "abi.RADIANCE array of n elements")
         self._check(self._lib.rb_trace_rays(self._h, rays.ctypes.data if n else None, seeds.ctypes.data if (seeds is not None and n) else None,
                                             n, first_sample, samples, res.ctypes.data if n else None))
         return res
@@ -543,9 +568,7 @@ class Engine:
         abi.RADIANCE array of n elements to fill, or a float32 tensor of shape (n, 4) on the engine's device, which selects
         rb_trace_camera_device (nothing crosses to the host)."""
         c = np.ascontiguousarray(cam, dtype=abi.CAMERA_EX).reshape(1)
-        samples, first_sample = int(samples), int(first_sample)
-        if not (0 <= samples < 2 ** 32 and 0 <= first_sample < 2 ** 32):
-            raise ValueError("samples and first_sample are 32-bit unsigned numbers")
+        samples, first_sample = _sample_range(samples, first_sample)
         first, n = (0, int(c["width"][0]) * int(c["height"][0])) if region is None else (int(region[0]), int(region[1]))
         if first < 0 or n < 0:
             raise ValueError("region: (first_pixel, n_pixels), both at least 0")
@@ -556,9 +579,7 @@ class Engine:
                 raise ValueError("out and the region differ in length")
             self._device_call(self._lib.rb_trace_camera_device, c.ctypes.data, first, n, first_sample, samples, op)
             return out
-        res = np.empty(n, dtype=abi.RADIANCE) if out is None else out
-        if not isinstance(res, np.ndarray) or res.dtype != abi.RADIANCE or res.shape != (n,) or not res.flags.c_contiguous:
-            raise ValueError("out: a contiguous abi.RADIANCE array of n elements is needed")
+        res = _host_out(out, n, abi.RADIANCE, "abi.RADIANCE array of n elements")
         self._check(self._lib.rb_trace_camera(self._h, c.ctypes.data, first, n, first_sample, samples, res.ctypes.data if n else None))
         return res
 
@@ -571,17 +592,12 @@ class Engine:
 
     def _hemisphere(self, host_fn, device_fn, out_dtype, out_row, points, normals, samples, first_sample, seeds, prm, out):
         """the two forms of a hemisphere query: surfels (abi.RAY's layout) from the points and normals, the call, the result"""
-        samples, first_sample = int(samples), int(first_sample)
-        if not (0 <= samples < 2 ** 32 and 0 <= first_sample < 2 ** 32):
-            raise ValueError("samples and first_sample are 32-bit unsigned numbers")
+        samples, first_sample = _sample_range(samples, first_sample)
         surf = self._ray_records(points, normals)
         if _is_tensor(surf) or _is_tensor(seeds) or _is_tensor(out):
             import torch
             fp, n = self._device_tensor(surf, torch.float32, 8, "points / normals")
-            sp, ns = (None, n)
-            if seeds is not None:   # 32-bit ids, signed or unsigned: the bits are what counts
-                unsigned = _is_tensor(seeds) and seeds.dtype == getattr(torch, "uint32", None)
-                sp, ns = self._device_tensor(seeds, torch.uint32 if unsigned else torch.int32, None, "seeds")
+            sp, ns = self._seed_tensor(seeds, n)
             t_dtype = torch.float32 if out_dtype is abi.RADIANCE else torch.int32
             res = torch.empty((n, out_row), dtype=t_dtype, device=surf.device) if out is None else out
             op, no = self._device_tensor(res, t_dtype, out_row, "out")
@@ -590,13 +606,8 @@ class Engine:
             self._device_call(device_fn, fp, sp, n, prm.ctypes.data, first_sample, samples, op)
             return res
         n = len(surf)
-        if seeds is not None:
-            seeds = np.ascontiguousarray(seeds, dtype=np.uint32).reshape(-1)
-            if len(seeds) != n:
-                raise ValueError("points and seeds differ in length")
-        res = np.empty(n, dtype=out_dtype) if out is None else out
-        if not isinstance(res, np.ndarray) or res.dtype != out_dtype or res.shape != (n,) or not res.flags.c_contiguous:
-            raise ValueError(f"out: a contiguous array of n {out_dtype} elements is needed")
+        seeds = _seed_array(seeds, n, "points")
+        res = _host_out(out, n, out_dtype, f"array of n {out_dtype} elements")
         self._check(host_fn(self._h, surf.ctypes.data if n else None, seeds.ctypes.data if (seeds is not None and n) else None, n,
                             prm.ctypes.data, first_sample, samples, res.ctypes.data if n else None))
         return res
@@ -663,9 +674,7 @@ class Engine:
         accumulating over calls with ``first_sample`` and resolving later (lightmap_resolve).  Torch tensors on the engine's
         device for ``out`` ((n, 4) float32) or ``sums`` ((n, 4) float32) select rb_bake_lightmap_device: nothing crosses to the
         host, and ``out`` (or, with sums alone, ``sums``) is returned."""
-        samples, first_sample = int(samples), int(first_sample)
-        if not (0 <= samples < 2 ** 32 and 0 <= first_sample < 2 ** 32):
-            raise ValueError("samples and first_sample are 32-bit unsigned numbers")
+        samples, first_sample = _sample_range(samples, first_sample)
         prm = self._lightmap_params(width, height, mesh, flip, offset, dilate)
         n = int(width) * int(height)
         if _is_tensor(out) or _is_tensor(sums):
@@ -693,9 +702,7 @@ class Engine:
         ``probes.irradiance`` read them).  ``seeds``: n uint32 ids or None (the probe's index).  A torch tensor on the engine's
         device for the positions, the seeds or ``out`` ((n, 28) float32) goes to rb_bake_probes_device: an (n, 28) tensor comes
         back and nothing crosses to the host."""
-        samples, first_sample = int(samples), int(first_sample)
-        if not (0 <= samples < 2 ** 32 and 0 <= first_sample < 2 ** 32):
-            raise ValueError("samples and first_sample are 32-bit unsigned numbers")
+        samples, first_sample = _sample_range(samples, first_sample)
         if _is_tensor(pos) or _is_tensor(seeds) or _is_tensor(out):
             import torch
             if not _is_tensor(pos) or pos.dtype != torch.float32:
@@ -704,10 +711,7 @@ class Engine:
             rec = torch.zeros((len(p3), 4), dtype=torch.float32, device=p3.device)
             rec[:, 0:3] = p3
             pp, n = self._device_tensor(rec, torch.float32, 4, "pos")
-            sp, ns = (None, n)
-            if seeds is not None:   # 32-bit ids, signed or unsigned: the bits are what counts
-                unsigned = _is_tensor(seeds) and seeds.dtype == getattr(torch, "uint32", None)
-                sp, ns = self._device_tensor(seeds, torch.uint32 if unsigned else torch.int32, None, "seeds")
+            sp, ns = self._seed_tensor(seeds, n)
             res = torch.empty((n, 28), dtype=torch.float32, device=rec.device) if out is None else out
             op, no = self._device_tensor(res, torch.float32, 28, "out")
             if ns != n or no != n:
@@ -718,13 +722,8 @@ class Engine:
         n = len(p3)
         rec = np.zeros(n, dtype=abi.PROBE)
         rec["pos"] = p3
-        if seeds is not None:
-            seeds = np.ascontiguousarray(seeds, dtype=np.uint32).reshape(-1)
-            if len(seeds) != n:
-                raise ValueError("pos and seeds differ in length")
-        res = np.empty(n, dtype=abi.SH9) if out is None else out
-        if not isinstance(res, np.ndarray) or res.dtype != abi.SH9 or res.shape != (n,) or not res.flags.c_contiguous:
-            raise ValueError("out: a contiguous abi.SH9 array of n elements is needed")
+        seeds = _seed_array(seeds, n, "pos")
+        res = _host_out(out, n, abi.SH9, "abi.SH9 array of n elements")
         self._check(self._lib.rb_bake_probes(self._h, rec.ctypes.data if n else None, seeds.ctypes.data if (seeds is not None and n) else None, n,
                                              first_sample, samples, res.ctypes.data if n else None))
         return res
@@ -942,10 +941,7 @@ def hemisphere_rays_device(points, normals, samples, first_sample=0, seeds=None,
     m, samples = len(surf), int(samples)
     if not 0 <= samples < 2 ** 32:
         raise ValueError("samples: a 32-bit unsigned number")
-    if seeds is not None:
-        seeds = np.ascontiguousarray(seeds, dtype=np.uint32).reshape(-1)
-        if len(seeds) != m:
-            raise ValueError("points and seeds differ in length")
+    seeds = _seed_array(seeds, m, "points")
     prm = Engine._hemi_params(offset)
     items = m * samples if samples <= 65536 else 0   # (a refused call writes nothing)
     rays, seeds_out = np.zeros(items, dtype=abi.RAY), np.zeros(items, dtype=np.uint32)
@@ -967,10 +963,7 @@ def probe_rays_device(pos, samples, first_sample=0, seeds=None, device=-1):
         raise ValueError("samples: a 32-bit unsigned number")
     rec = np.zeros(n, dtype=abi.PROBE)
     rec["pos"] = p3
-    if seeds is not None:
-        seeds = np.ascontiguousarray(seeds, dtype=np.uint32).reshape(-1)
-        if len(seeds) != n:
-            raise ValueError("pos and seeds differ in length")
+    seeds = _seed_array(seeds, n, "pos")
     items = n * samples if samples <= 65536 else 0   # (a refused call writes nothing)
     rays, seeds_out = np.zeros(items, dtype=abi.RAY), np.zeros(items, dtype=np.uint32)
     lib = load()

@@ -240,7 +240,9 @@ def test_device_form_and_regions_equal_the_whole_host_call():
 
 def test_a_call_across_a_piece_boundary():
     """RB_CAMERA_PIECE_ITEMS + 77 * samples items on the Cornell scene at max_depth = 2: two pieces.  Every pixel against two
-    calls split at the piece boundary; the last 77 pixels and the 64 around the boundary against the oracle."""
+    calls split at the piece boundary; the last 77 pixels and the 64 around the boundary against the oracle; every pixel against
+    the device form's answer, whose two pieces go through the same loop on the caller's buffer."""
+    import torch
     samples = 4
     b = PIECE // samples
     n = b + 77
@@ -257,6 +259,9 @@ def test_a_call_across_a_piece_boundary():
         rays, seeds = engine.camera_rays_device(cam, samples, 7, region=(b - 32, 32 + 77), device=0)
         want = oracle_sums(s, rays, seeds, samples)
         assert np.array_equal(_u32(one[b - 32:]), _u32(want))
+        dev = e.trace_camera(cam, samples, 7, region=(0, n), out=torch.empty((n, 4), dtype=torch.float32, device=f"cuda:{e.query_device}"))
+        assert e.last_camera_rays_ms() > 0   # both pieces' event pairs were recorded and are read
+        assert np.array_equal(_u32(dev.cpu().numpy()), _u32(one).reshape(n, 4))
     finally:
         e.close()
 

@@ -305,7 +305,9 @@ def test_device_forms_and_a_forced_launch_shape_equal_the_host_forms():
 def test_a_call_across_a_piece_boundary():
     """RB_HEMI_PIECE_ITEMS + 77 * samples items at samples = 64 on the feature scene: two pieces.  Every surfel against two
     calls split at the piece boundary (seeds carry the indices on); the last 77 surfels and the 32 before the boundary
-    against the oracle; the openness of the same call against its two halves."""
+    against the oracle; the openness of the same call against its two halves.  Both against the device forms' answers, whose two
+    pieces go through the same loop on the caller's buffers."""
+    import torch
     samples = 64
     b = PIECE // samples
     n = b + 77
@@ -332,6 +334,13 @@ def test_a_call_across_a_piece_boundary():
         rays, _ = engine.hemisphere_rays_device(pts[tail], nrm[tail], samples, 0, seeds=ids[tail], device=0)
         want = counts_of(e.occluded_records(rays, np.full(len(rays), 2.0, f32), NO_LIGHTS), samples)
         assert np.array_equal(_u32(opn[tail]), _u32(want))
+        d_pts, d_nrm = (torch.from_numpy(a).to(f"cuda:{e.query_device}") for a in (pts, nrm))
+        dev = e.trace_hemisphere(d_pts, d_nrm, samples, 7)
+        assert e.last_camera_rays_ms() > 0   # both pieces' event pairs were recorded and are read
+        assert np.array_equal(_u32(dev.cpu().numpy()), _u32(one).reshape(n, 4))
+        dev = e.openness(d_pts, d_nrm, samples, 2.0)
+        assert e.last_camera_rays_ms() > 0
+        assert np.array_equal(dev.cpu().numpy().view(np.uint32), _u32(opn).reshape(n, 2))
     finally:
         e.close()
 

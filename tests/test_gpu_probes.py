@@ -233,7 +233,8 @@ def test_both_projection_shapes_give_the_same_words(monkeypatch):
 def test_a_call_across_a_piece_boundary():
     """RB_PROBE_PIECE_ITEMS + 77 * samples items at samples = 64 on the feature scene: two pieces.  Every probe against two
     calls split at the piece boundary (seeds carry the indices on); the last 77 probes and the 32 before the boundary against
-    the oracle."""
+    the oracle; every probe against the device form's answer, whose two pieces go through the same loop on the caller's buffers."""
+    import torch
     samples = 64
     b = PIECE // samples
     n = b + 77
@@ -252,6 +253,9 @@ def test_a_call_across_a_piece_boundary():
         tail = slice(b - 32, n)
         rays, seeds = engine.probe_rays_device(pos[tail], samples, 7, seeds=ids[tail], device=0)
         assert np.array_equal(words(one[tail]), words(oracle_sh(s, rays, seeds, samples)))
+        dev = e.bake_probes(torch.from_numpy(pos).to(f"cuda:{e.query_device}"), samples, 7)
+        assert e.last_camera_rays_ms() > 0 and e.last_probe_project_ms() > 0   # both pieces' event pairs were recorded and are read
+        assert np.array_equal(words(dev.cpu().numpy()), words(one))
     finally:
         e.close()
 
