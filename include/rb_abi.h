@@ -868,6 +868,65 @@ int rb_bake_probes_device(rb_engine* e, const rb_probe* d_probes, const uint32_t
  * launches it reports. */
 int rb_last_probe_project_ms(rb_engine* e, float* ms);
 
+/* ---- Light points from a baked probe grid (the normative definition; no reference counterpart).  The
+ * way back in for what rb_bake_probes makes: a regular axis-aligned grid of probes and m points with normals in, m lit values
+ * out.  Every step is one IEEE binary32 operation in the order written, no contraction, / and sqrt correctly rounded: the numpy
+ * model renderbaby_amd/probes.py (coefficients, light) equals the device bit for bit -- but for the sign and payload of a NaN
+ * the arithmetic itself generates.  max(x, 0.0f) is x > 0.0f ? x : 0.0f and min(x, y) is x < y ? x : y.
+ *   GRID   probe (ix, iy, iz) sits at origin + i * step, its record at index (iz * ny + iy) * nx + ix, x fastest.
+ *   COEFFS (stage 1, one record each): a probe is valid if its weight is finite and > 0.  Valid: coeff[j][ch] = (sum[j][ch] *
+ *          K_j) / weight with K_0 = 12.566371f (4 pi), K_1..3 = 8.37758f (8 pi / 3), K_4..8 = 3.1415927f (pi) -- 4 A_l, the
+ *          cosine lobe's zonal factors, so that sum_j coeff_j Y_j(n) is the irradiance over pi --, and the weight word becomes
+ *          1.0f.  Invalid: all-zero bits.  The output may be the input.
+ *   LIGHT  (stage 2) for point i with pos and nrm:
+ *          invalid point: a non-finite component of pos or nrm, nrm all zero, or (nx nx + ny ny) + nz nz not finite: {0, 0, 0, 0};
+ *          n = nrm / sqrt((nx nx + ny ny) + nz nz), as rb_cast_rays normalises;  Y0..Y8 = rb_bake_probes' basis of n;
+ *          per axis a: f = (pos_a - origin_a) / step_a;  f = min(max(f, 0.0f), float(count_a - 1));
+ *                      i_a = min(uint(floor(f)), count_a >= 2 ? count_a - 2 : 0);  t_a = f - float(i_a);
+ *          the corners (ix + dx, iy + dy, iz + dz) in the order dz, dy, dx ascending, dx fastest; a corner with d_a = 1 on an
+ *          axis with count_a == 1 does not exist;  w_c = ((wx * wy) * wz) * coeff[c].weight, w_a = d_a ? t_a : 1.0f - t_a;
+ *          a corner that does not exist or whose w_c == 0 is skipped: no value of its record enters the arithmetic;
+ *          e_c[ch]: from +0.0f, j ascending, += coeff[c][j][ch] * Yj (one multiply, one add);
+ *          E[ch] += w_c * e_c[ch] and W += w_c, from +0.0f in corner order;
+ *          out = W > 0 ? {max(E.r / W, 0.0f), max(E.g / W, 0.0f), max(E.b / W, 0.0f), W} : {0, 0, 0, 0}.
+ * `value` is the irradiance over pi -- what rb_trace_hemisphere's sum / weight estimates --, so albedo x value is a lambert
+ * surface's outgoing radiance.  A point outside the grid takes the values at the nearest cell's edge.  A caller rejects a probe
+ * (one inside geometry, say) by zeroing its weight before stage 1: the blend renormalises over the rest.  Not here: visibility
+ * or backface weights against leaks, and anything but a regular axis-aligned grid. */
+typedef struct rb_probe_grid {                                                                      /* 48 B */
+    float origin[3];      /* finite */
+    uint32_t _pad0;       /* must be 0 */
+    float step[3];        /* finite, > 0 */
+    uint32_t _pad1;       /* must be 0 */
+    uint32_t counts[3];   /* nx, ny, nz: each >= 1, nx * ny * nz <= 2^31 - 64 */
+    uint32_t flags;       /* must be 0 */
+} rb_probe_grid;
+typedef struct rb_lit { float value[3]; float weight; } rb_lit;                                     /* 16 B */
+/* Stage 1 alone, no engine, on `device` (-1 = current): sums[n] -> coeffs_out[n], host arrays (coeffs_out may be sums).  n above
+ * 2^31 - 64: RB_ERR_INVALID_OPTIONS; NULL sums or coeffs_out with n > 0: RB_ERR_NULL_ARGUMENT; both before any device is
+ * touched.  n == 0 is RB_OK. */
+int rb_probe_coefficients(int32_t device, const rb_sh9* sums, size_t n, rb_sh9* coeffs_out);
+/* The same with d_sums and d_coeffs_out (16-byte aligned; they may be the same buffer) in device memory of the engine's device,
+ * validated as rb_trace_rays_device validates its buffers; queued on the engine's stream, returns without waiting: rb_sync is
+ * the wait.  The engine lends its device and its stream: no scene is read, and the side effects are a query's -- none.  Like
+ * every engine entry point it asks for an engine that holds a scene: before the first rb_update it is RB_ERR_NOT_INITIALIZED,
+ * with n == 0 too.  Sharded engines and multi-device handles as rb_trace_rays (a multi-device handle answers on devices[0]).
+ * rb_last_query_ms reports the kernel, rb_last_query_kernel_name "k_probe_coeffs". */
+int rb_probe_coefficients_device(rb_engine* e, const rb_sh9* d_sums, size_t n, rb_sh9* d_coeffs_out);
+/* Stage 2, no engine, on `device` (-1 = current): the grid, its nx * ny * nz coefficient records, points[m] and out[m] in host
+ * memory.  The records are uploaded once; the points go through the device in pieces of 2^22 (RB_LIGHT_PIECE_POINTS in the
+ * environment, read per call: another piece size, for tests); the result does not depend on it.  RB_ERR_NULL_ARGUMENT: a NULL
+ * grid; NULL coeffs, points or out with m > 0.  RB_ERR_INVALID_OPTIONS, before any device is touched: a count of 0; nx * ny * nz
+ * above 2^31 - 64; m above 2^31 - 64; a step that is not finite or not > 0; a non-finite origin; non-zero flags or pad words.
+ * m == 0 is RB_OK. */
+int rb_light_points(int32_t device, const rb_probe_grid* grid, const rb_sh9* coeffs, const rb_surfel* points, size_t m, rb_lit* out);
+/* The same with d_coeffs, d_points and d_out (16-byte aligned) in device memory of the engine's device; the grid itself is host
+ * memory and is read before the call returns.  One launch, as rb_probe_coefficients_device in every other respect;
+ * rb_last_query_kernel_name reports "k_probe_light" (or "k_probe_light_wide": RB_LIGHT_SHAPE=wide in the environment chooses the
+ * other launch shape for a measurement; the result does not depend on it). */
+int rb_light_points_device(rb_engine* e, const rb_probe_grid* grid, const rb_sh9* d_coeffs, const rb_surfel* d_points, size_t m,
+                           rb_lit* d_out);
+
 /* ---- Edge-avoiding denoiser over the first-hit buffers (no reference counterpart).  An a-trous wavelet
  * filter (Dammertz et al. 2010) on the albedo-demodulated mean radiance, guided by the first hit of every pixel-centre ray.
  * Section 13 is the normative definition: every step one IEEE binary32 operation in a fixed order, so that the device's result
@@ -985,6 +1044,11 @@ static_assert(offsetof(rb_lightmap_params, offset) == 16, "offset @16");
 static_assert(sizeof(rb_probe) == 16, "rb_probe is 16 B");
 static_assert(sizeof(rb_sh9) == 112, "rb_sh9 is 112 B");
 static_assert(offsetof(rb_sh9, weight) == 108, "weight @108");
+static_assert(sizeof(rb_probe_grid) == 48, "rb_probe_grid is 48 B");
+static_assert(offsetof(rb_probe_grid, step) == 16, "step @16");
+static_assert(offsetof(rb_probe_grid, counts) == 32, "counts @32");
+static_assert(offsetof(rb_probe_grid, flags) == 44, "flags @44");
+static_assert(sizeof(rb_lit) == 16, "rb_lit is 16 B");
 static_assert(sizeof(rb_guide) == 48, "rb_guide is 48 B");
 static_assert(sizeof(rb_denoise_params) == 32, "rb_denoise_params is 32 B");
 static_assert(offsetof(rb_guide, t) == 12, "t @12");
@@ -1015,6 +1079,8 @@ _Static_assert(sizeof(rb_openness) == 8, "rb_openness is 8 B");
 _Static_assert(sizeof(rb_lightmap_params) == 32, "rb_lightmap_params is 32 B");
 _Static_assert(sizeof(rb_probe) == 16, "rb_probe is 16 B");
 _Static_assert(sizeof(rb_sh9) == 112, "rb_sh9 is 112 B");
+_Static_assert(sizeof(rb_probe_grid) == 48, "rb_probe_grid is 48 B");
+_Static_assert(sizeof(rb_lit) == 16, "rb_lit is 16 B");
 _Static_assert(sizeof(rb_guide) == 48, "rb_guide is 48 B");
 _Static_assert(sizeof(rb_denoise_params) == 32, "rb_denoise_params is 32 B");
 #endif

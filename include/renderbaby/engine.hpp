@@ -310,6 +310,27 @@ class Engine final : public Renderer {
                             uint32_t first_sample = 0) {
         check(h_->e, rb_bake_probes_device(h_->e, d_probes, d_seeds, n, first_sample, samples, d_out));
     }
+    // ---- light points from a baked probe grid (extension; rb_abi.h): the sums of bake_probes scaled to
+    // irradiance-over-pi coefficients, and the blend of the eight probes of a regular grid round every point.  The host forms
+    // need no engine: the work runs on `device` (-1: the current one).
+    static std::vector<rb_sh9> probe_coefficients(const std::vector<rb_sh9>& sums, int32_t device = -1) {
+        std::vector<rb_sh9> out(sums.size());
+        check(nullptr, rb_probe_coefficients(device, sums.data(), sums.size(), out.data()));
+        return out;
+    }
+    static std::vector<rb_lit> light_points(const rb_probe_grid& grid, const std::vector<rb_sh9>& coeffs, const std::vector<rb_surfel>& points,
+                                            int32_t device = -1) {
+        std::vector<rb_lit> out(points.size());
+        check(nullptr, rb_light_points(device, &grid, coeffs.data(), points.data(), points.size(), out.data()));
+        return out;
+    }
+    // the same on the engine's device memory (d_coeffs_out may be d_sums): queued on the engine's stream -- sync() waits
+    void probe_coefficients_device(const rb_sh9* d_sums, size_t n, rb_sh9* d_coeffs_out) {
+        check(h_->e, rb_probe_coefficients_device(h_->e, d_sums, n, d_coeffs_out));
+    }
+    void light_points_device(const rb_probe_grid& grid, const rb_sh9* d_coeffs, const rb_surfel* d_points, size_t m, rb_lit* d_out) {
+        check(h_->e, rb_light_points_device(h_->e, &grid, d_coeffs, d_points, m, d_out));
+    }
     void sync() { check(h_->e, rb_sync(h_->e)); }
     // ---- the denoiser (rb_abi.h): the a-trous filter over the committed accumulation
     static rb_denoise_params denoise_defaults() {

@@ -76,6 +76,11 @@ LIGHTMAP_MAX_SIDE, LIGHTMAP_MAX_DILATE = 16384, 64
 PROBE = np.dtype([("pos", f4, (3,)), ("_pad", f4)])
 SH9 = np.dtype([("sum", f4, (9, 3)), ("weight", f4)])
 PROBE_PIECE_ITEMS = 1 << 23
+# light points from a baked probe grid (rb_probe_coefficients / rb_light_points): the regular grid the
+# coefficient records (abi.SH9's layout, the weight 1 or 0) belong to, x fastest, and a point's lit value with its blend weight
+PROBE_GRID = np.dtype([("origin", f4, (3,)), ("_pad0", u4), ("step", f4, (3,)), ("_pad1", u4), ("counts", u4, (3,)), ("flags", u4)])
+LIT = np.dtype([("value", f4, (3,)), ("weight", f4)])
+LIGHT_PIECE_POINTS = 1 << 22
 # any-hit occlusion (rb_occluded): result bytes and stage masks
 OCCL_VISIBLE, OCCL_OCCLUDED, OCCL_INVALID = 0, 1, 255
 MASK_GROUND, MASK_TRIANGLES, MASK_SPHERES, MASK_LIGHTS, MASK_ALL = 1, 2, 4, 8, 15
@@ -90,7 +95,8 @@ SIZES = {"camera": (CAMERA, 48), "uniforms": (UNIFORMS, 144), "material": (MATER
          "ray": (RAY, 32), "hit": (HIT, 48), "surface": (SURFACE, 48),
          "guide": (GUIDE, 48), "denoise_params": (DENOISE_PARAMS, 32), "camera_ex": (CAMERA_EX, 96),
          "surfel": (SURFEL, 32), "hemi_params": (HEMI_PARAMS, 32), "openness": (OPENNESS, 8),
-         "lightmap_params": (LIGHTMAP_PARAMS, 32), "probe": (PROBE, 16), "sh9": (SH9, 112)}
+         "lightmap_params": (LIGHTMAP_PARAMS, 32), "probe": (PROBE, 16), "sh9": (SH9, 112),
+         "probe_grid": (PROBE_GRID, 48), "lit": (LIT, 16)}
 for _n, (_dt, _sz) in SIZES.items():
     assert _dt.itemsize == _sz, (_n, _dt.itemsize, _sz)
 

@@ -1,6 +1,7 @@
 """First-hit buffers as images: pure numpy over the records of ``Engine.render_hits`` / ``Engine.cast_rays``
-(abi.HIT, abi.SURFACE).  No device, no library -- except ``ambient_occlusion``, which asks the engine one any-hit query, and
-``ambient_occlusion_device``, which asks it for the openness of one surfel per hit.
+(abi.HIT, abi.SURFACE).  No device, no library -- except ``ambient_occlusion``, which asks the engine one any-hit query,
+``ambient_occlusion_device``, which asks it for the openness of one surfel per hit, and ``probe_lit``, which asks it to light
+one surfel per hit from a baked probe grid.
 
 The records are already in the orientation of the delivered RGBA8 frame (row-major, top row first, x mirrored), so every
 function here maps record [row, column] to pixel [row, column] and nothing is flipped.  Pixels whose ray hit nothing
@@ -202,6 +203,28 @@ def ambient_occlusion_device(engine, hits, samples=16, radius=1.0, first_sample=
         valid = res["valid"].astype(np.float32)
         ao[m] = np.where(valid > 0, res["open"].astype(np.float32) / np.maximum(valid, np.float32(1)), np.float32(1)).astype(np.float32)
     return ao
+
+
+def probe_lit(engine, grid, coeffs, hits, surfaces, uniforms=None):
+    """What a baked probe grid looks like on the scene (Engine.light_points, rb_light_points_device): the
+    first hits ``engine.render_hits(surfaces=True)`` returned, lit from the grid in one launch -- ``grid``: an abi.PROBE_GRID
+    scalar, ``coeffs``: its coefficient records (``bake.probe_grid`` makes both).  Linear RGB float32 [rows, width, 3] in the
+    orientation of the frame, for ``color_map``: a filterable hit (the denoiser's rule: a surface that emits nothing) gives
+    emission + albedo x value with the normal turned towards the camera; a light or an emitting surface its emission; a miss
+    the sky, as the records hold it; a pixel the grid does not reach (weight 0) albedo x 0.  No shadows, no leaks held back:
+    it shows the probes, not the scene's light."""
+    u = engine.uniforms if uniforms is None else uniforms
+    if u is None:
+        raise ValueError("the engine has accepted no update yet: call update() / render() first, or pass uniforms=")
+    m, pts, nrm = ambient_occlusion_surfels(u, hits)
+    img = surfaces["emissive"].astype(np.float32).copy()
+    lit = m & (hits["kind"] != abi.HIT_LIGHT) & ~(surfaces["emissive"] > 0).any(-1)
+    if len(pts):
+        res = engine.light_points(grid, coeffs, pts, nrm)
+        value = np.zeros(hits.shape + (3,), dtype=np.float32)
+        value[m] = np.where(res["weight"][:, None] > 0, res["value"], np.float32(0))
+        img[lit] = (img[lit] + surfaces["albedo"][lit].astype(np.float32) * value[lit]).astype(np.float32)
+    return img
 
 
 def ambient_occlusion_map(engine, width, height, samples, radius, mesh=None, flip=False, first_sample=0, offset=1e-3):

@@ -6,6 +6,7 @@
 ``lightmap``     a mesh's lightmap in one call: surfels from its uvs, traced and resolved on the device (Engine.bake_lightmap; section 17)
 ``probes``       irradiance probes: the SH9 radiance coefficients at points in free space, traced and projected on the device
                  (Engine.bake_probes; section 18)
+``probe_grid``   a regular grid of probes baked and turned into the coefficients Engine.light_points blends (section 19)
 ``lightmap_texture``  a baked map as an RGBA8 texture that sample_texture decodes back
 ``camera_rays``  the rays of cameras the reference's Camera struct cannot express: equirect, ortho, thin_lens
 ``render_rays``  rays -> tone-mapped RGBA8 pixels, the reference's colour mapping applied to sum / weight
@@ -87,6 +88,18 @@ def probes(engine, pos, samples, first_sample=0, seeds=None):
     from . import probes as model
     sh = engine.bake_probes(pos, samples, first_sample=first_sample, seeds=seeds)
     return model.radiance_coefficients(sh if isinstance(sh, np.ndarray) else sh.cpu().numpy())
+
+
+def probe_grid(engine, lo, hi, counts, samples, first_sample=0, seeds=None):
+    """A regular grid of irradiance probes over the box ``lo`` .. ``hi``, ``counts`` = (nx, ny, nz) cell centres along the axes
+    (``probes.grid``), baked with ``samples`` rays per probe (Engine.bake_probes) and scaled to coefficients
+    (Engine.probe_coefficients).  Returns (grid, coeffs): an abi.PROBE_GRID scalar and abi.SH9[nx * ny * nz],
+    x fastest -- what ``Engine.light_points`` and ``aov.probe_lit`` take.  To accumulate over calls with ``first_sample``, add
+    ``Engine.bake_probes``' sums and call ``Engine.probe_coefficients`` once at the end."""
+    from . import probes as model
+    grid = model.grid_params(lo, hi, counts)
+    sh = engine.bake_probes(model.grid(lo, hi, counts), samples, first_sample=first_sample, seeds=seeds)
+    return grid, engine.probe_coefficients(sh)
 
 
 def lightmap_texture(rgba):

@@ -464,6 +464,20 @@ enum : uint32_t { kProbeShapePlain = 1, kProbeShapeSplit = 2 };   // k_sh_projec
 constexpr uint32_t kProbeShapeDefault = kProbeShapePlain;
 int launch_probe_rays(const ProbeGenArgs& g, void* stream);
 int launch_sh_project(const float* colors, const rb_ray* recs, uint32_t n, uint32_t samples, rb_sh9* out, uint32_t shape, void* stream);
+// ---- rb_probe_light.hip: light points from a baked probe grid.  k_probe_coeffs scales the sums of
+// rb_bake_probes to coefficients, one lane per probe, in place if asked; k_probe_light blends the eight probes round each
+// point, one lane per point.
+struct ProbeLightArgs {
+    rb_probe_grid grid;       // checked by the caller: counts >= 1, nx ny nz <= 2^31 - 64
+    const rb_sh9* coeffs;     // nx ny nz records, x fastest
+    const rb_surfel* points;
+    rb_lit* out;
+    uint32_t m;               // points in this launch
+};
+int launch_probe_coeffs(const rb_sh9* sums, uint32_t n, rb_sh9* out, void* stream);
+enum : uint32_t { kLightShapePairs = 1, kLightShapeWide = 2 };   // k_probe_light: two corners' loads in flight, or all eight
+constexpr uint32_t kLightShapeDefault = kLightShapePairs;
+int launch_probe_light(const ProbeLightArgs& a, uint32_t shape, void* stream, const char** kernel_name = nullptr);
 // ---- rb_lightmap.hip: lightmap texels made on the device.  The triangles are PrepTri / PrepTriShade
 // records in TRIANGLE order (launch_prep_tris over the identity order, launch_lightmap_iota), so that an owner is an index into
 // bvh_triangles whatever bvh_indices hold.

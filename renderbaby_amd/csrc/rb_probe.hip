@@ -7,6 +7,7 @@
 // correctly rounded / and sqrt, so that renderbaby_amd/probes.py equals this file bit for bit.
 #include <cstdlib>
 
+#include "rb_device_sh.hpp"
 #include "rb_device_sincos.hpp"
 
 #pragma clang fp contract(off)
@@ -47,24 +48,7 @@ __global__ void __launch_bounds__(256) k_probe_rays(const ProbeGenArgs g) {
 // k_sh_project_split: three waves per block of probes, wave g folds coefficients 3g .. 3g + 2 and the last one the weight --
 // three times the waves for reading the rows three times (section 18.4 has the measurement that chose).  Every sum starts at
 // +0 and takes its samples in ascending order, one multiply and one add each, whichever wave holds it.
-struct ShBasis {
-    float y[9];
-};
-// the basis of the direction AS STORED in the record: one operation per step, section 18.1's grouping
-DEV ShBasis sh_basis(float x, float y, float z) {
-    ShBasis b;
-    b.y[0] = 0.282094792f;
-    b.y[1] = 0.488602512f * y;
-    b.y[2] = 0.488602512f * z;
-    b.y[3] = 0.488602512f * x;
-    b.y[4] = 1.09254843f * (x * y);
-    b.y[5] = 1.09254843f * (y * z);
-    b.y[6] = 0.315391565f * (3.0f * (z * z) - 1.0f);
-    b.y[7] = 1.09254843f * (x * z);
-    b.y[8] = 0.546274215f * (x * x - y * y);
-    return b;
-}
-
+// The basis is sh_basis (rb_device_sh.hpp) of the direction AS STORED in the record.
 // the sums of coefficients J0 .. J0 + COEFS - 1 of block `blk`'s probes on the calling wave; the weight goes with coefficient 8
 template <int J0, int COEFS>
 DEV void sh_project_body(const float* __restrict__ colors, const rb_ray* __restrict__ recs, uint32_t n, uint32_t S, rb_sh9* __restrict__ out,

@@ -1,7 +1,8 @@
 // rb_queries.cpp -- what an engine answers besides frames: closest-hit queries (rb_cast_rays / rb_render_hits / rb_pick), any-hit
 // occlusion, path-traced radiance along given rays, camera and hemisphere rays, lightmap texels and irradiance probes made on the
-// device and the denoiser over the first-hit buffers, with their device forms, their getters and their C entry points (rb_abi.h;
-// DESIGN.md sections 11-18).  Every sequence is here once: one prologue (query_prologue), one timed
+// device, light points from a baked probe grid and the denoiser over the first-hit buffers, with their device forms, their
+// getters and their C entry points (rb_abi.h; DESIGN.md sections 11-19).
+// Every sequence is here once: one prologue (query_prologue), one timed
 // launch (timed_launch), one runner per form -- run_pieces for the host forms, device_query_locked for the device forms --, over
 // them one runner for the families of "n items, `samples` each" in both forms (run_family: radiance, camera, hemisphere,
 // probes), one shape for the engine entry points (engine_entry) and one scope for the engine-less forms (DeviceScope).  The
@@ -47,13 +48,14 @@ int scene_params(rb_engine* e, rb::KParams* p) {
 }
 
 // what every query begins with; the kernel times of the query before -- rb_last_query_ms and the event pairs of its generator
-// and projection stages -- are gone from here on, however far this one gets
+// and projection stages -- are gone from here on, however far this one gets.  p == nullptr: a query that reads no scene
+// (section 19) -- nothing is prepared for it.
 int query_prologue(rb_engine* e, rb::KParams* p) {
     e->last_query_ms = 0.0f;
     e->cam_pieces = e->sh_pieces = 0;
     int rc = require_ready(e);
-    if (!rc) rc = ensure_prepared(e);
-    if (!rc) rc = scene_params(e, p);
+    if (!rc && p) rc = ensure_prepared(e);
+    if (!rc && p) rc = scene_params(e, p);
     if (rc) return rc;
     for (hipEvent_t& x : e->ev_q)
         if (!x) HIP_TRY(e, hipEventCreate(&x));
@@ -110,6 +112,15 @@ int device_query_locked(rb_engine* e, Launch&& launch) {
     int rc = query_prologue(e, &p);
     if (!rc) rc = timed_launch(e, "query", [&](rb::LaunchInfo* li) { return launch(p, li); });
     if (!rc) e->query_ms_pending = true;   // rb_last_query_ms reads the events when it is asked
+    return rc;
+}
+
+// ... of a query that reads no scene: the engine lends its device and its stream; `launch(li)` returns a HIP status
+template <class Launch>
+int device_stream_locked(rb_engine* e, Launch&& launch) {
+    int rc = query_prologue(e, nullptr);
+    if (!rc) rc = timed_launch(e, "query", launch);
+    if (!rc) e->query_ms_pending = true;
     return rc;
 }
 
@@ -611,6 +622,61 @@ int probe_check(rb_engine* e, const char* who, size_t n, uint32_t first_sample, 
     if (n > 0x7FFFFFFFull - 63ull || static_cast<uint64_t>(n) * samples > 0x7FFFFFFFull - 63ull)
         return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s takes at most 2^31 - 64 probes and (probe, sample) items per call", who);
     return RB_OK;
+}
+
+// ---- light points from a baked probe grid (rb_abi.h)
+// the refusals the forms of rb_probe_coefficients share; before a device is touched (e may be NULL: the engine-less form)
+int probe_coeffs_check(rb_engine* e, const char* who, const void* sums, size_t n, const void* out) {
+    if (n > 0x7FFFFFFFull - 63ull) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s takes at most 2^31 - 64 probes per call", who);
+    if (n > 0 && (!sums || !out)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "%s: sums / coeffs_out is NULL", who);
+    return RB_OK;
+}
+
+// ... and those of rb_light_points
+int light_points_check(rb_engine* e, const char* who, const rb_probe_grid* g, const void* coeffs, const void* points, size_t m, const void* out) {
+    if (!g) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "%s: grid is NULL", who);
+    if (g->flags != 0u || g->_pad0 != 0u || g->_pad1 != 0u) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: the grid's flags and pad words must be 0", who);
+    uint64_t probes = 1;
+    for (int a = 0; a < 3; a++) {
+        if (g->counts[a] == 0u) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: the grid has a count of 0", who);
+        probes *= g->counts[a];   // (each factor is below 2^32 and the product is checked before the next: no wrap-around)
+        if (probes > 0x7FFFFFFFull - 63ull) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s takes a grid of at most 2^31 - 64 probes", who);
+        if (!std::isfinite(g->origin[a])) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: the grid's origin is not finite", who);
+        if (!std::isfinite(g->step[a]) || !(g->step[a] > 0.0f)) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: the grid's step must be finite and greater than 0", who);
+    }
+    if (m > 0x7FFFFFFFull - 63ull) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s takes at most 2^31 - 64 points per call", who);
+    if (m > 0 && (!coeffs || !points || !out)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "%s: coeffs / points / out is NULL", who);
+    return RB_OK;
+}
+
+size_t grid_probes(const rb_probe_grid& g) { return static_cast<size_t>(g.counts[0]) * g.counts[1] * g.counts[2]; }
+
+// points per launch of the engine-less rb_light_points: RB_LIGHT_PIECE_POINTS in the environment (tests: a piece boundary at
+// a few points), else 2^22 -- 128 + 64 MiB of scratch
+size_t light_piece_points() {
+    const char* const s = std::getenv("RB_LIGHT_PIECE_POINTS");
+    const unsigned long long v = s ? std::strtoull(s, nullptr, 10) : 0ull;
+    return v ? static_cast<size_t>(std::min<unsigned long long>(v, 0x7FFFFFFFull - 63ull)) : size_t(1) << 22;
+}
+
+int probe_coeffs_device_locked(rb_engine* e, const rb_sh9* d_sums, size_t n, rb_sh9* d_out) {
+    int rc = device_range(e, d_sums, n * sizeof(rb_sh9), 16, "d_sums");
+    if (!rc) rc = device_range(e, d_out, n * sizeof(rb_sh9), 16, "d_coeffs_out");
+    if (rc) return rc;
+    return device_stream_locked(e, [&](rb::LaunchInfo* li) {
+        li->kernel_name = "k_probe_coeffs";
+        return rb::launch_probe_coeffs(d_sums, static_cast<uint32_t>(n), d_out, e->stream);
+    });
+}
+
+int light_points_device_locked(rb_engine* e, const rb_probe_grid& g, const rb_sh9* d_coeffs, const rb_surfel* d_points, size_t m, rb_lit* d_out) {
+    int rc = device_range(e, d_coeffs, grid_probes(g) * sizeof(rb_sh9), 16, "d_coeffs");
+    if (!rc) rc = device_range(e, d_points, m * sizeof(rb_surfel), 16, "d_points");
+    if (!rc) rc = device_range(e, d_out, m * sizeof(rb_lit), 16, "d_out");
+    if (rc) return rc;
+    return device_stream_locked(e, [&](rb::LaunchInfo* li) {
+        return rb::launch_probe_light(rb::ProbeLightArgs{g, d_coeffs, d_points, d_out, static_cast<uint32_t>(m)}, 0u, e->stream, &li->kernel_name);
+    });
 }
 
 // ---- the denoiser (rb_abi.h).  Like a query it is queued on the engine's stream behind whatever runs
@@ -1226,6 +1292,58 @@ int rb_bake_probes(rb_engine* e, const rb_probe* probes, const uint32_t* seeds, 
 int rb_bake_probes_device(rb_engine* e, const rb_probe* d_probes, const uint32_t* d_seeds, size_t n, uint32_t first_sample,
                           uint32_t samples, rb_sh9* d_out) {
     return probes_entry(e, "rb_bake_probes_device", true, d_probes, d_seeds, n, first_sample, samples, d_out);
+}
+
+int rb_probe_coefficients(int32_t device, const rb_sh9* sums, size_t n, rb_sh9* coeffs_out) {
+    if (const int rc = probe_coeffs_check(nullptr, "rb_probe_coefficients", sums, n, coeffs_out)) return rc;
+    if (n == 0) return RB_OK;
+    const size_t piece = std::min(n, size_t(1) << 22);   // 448 MiB of scratch at the most
+    rb::DevBuf<rb_sh9> d_recs;
+    DeviceScope s(device);
+    s.alloc(d_recs, piece);
+    for (size_t done = 0; done < n && s.ok(); done += piece) {
+        const size_t m = std::min(piece, n - done);
+        s.upload(d_recs.ptr, sums + done, m * sizeof(rb_sh9));
+        s.run([&] { return rb::launch_probe_coeffs(d_recs.ptr, static_cast<uint32_t>(m), d_recs.ptr, s.stream); });
+        s.download(coeffs_out + done, d_recs.ptr, m * sizeof(rb_sh9));
+        s.sync();   // the scratch is the next piece's
+    }
+    return s.finish("rb_probe_coefficients");
+}
+
+int rb_probe_coefficients_device(rb_engine* e, const rb_sh9* d_sums, size_t n, rb_sh9* d_coeffs_out) {
+    return engine_entry(
+        e, n, [&] { return probe_coeffs_check(e, "rb_probe_coefficients_device", d_sums, n, d_coeffs_out); },
+        [&](rb_engine* t) { return probe_coeffs_device_locked(t, d_sums, n, d_coeffs_out); });
+}
+
+int rb_light_points(int32_t device, const rb_probe_grid* grid, const rb_sh9* coeffs, const rb_surfel* points, size_t m, rb_lit* out) {
+    if (const int rc = light_points_check(nullptr, "rb_light_points", grid, coeffs, points, m, out)) return rc;
+    if (m == 0) return RB_OK;
+    const size_t probes = grid_probes(*grid), piece = std::min(m, light_piece_points());
+    rb::DevBuf<rb_sh9> d_coeffs;
+    rb::DevBuf<rb_surfel> d_points;
+    rb::DevBuf<rb_lit> d_out;
+    DeviceScope s(device);
+    s.alloc(d_coeffs, probes);
+    s.alloc(d_points, piece);
+    s.alloc(d_out, piece);
+    s.upload(d_coeffs.ptr, coeffs, probes * sizeof(rb_sh9));   // once per call
+    for (size_t done = 0; done < m && s.ok(); done += piece) {
+        const size_t k = std::min(piece, m - done);
+        s.upload(d_points.ptr, points + done, k * sizeof(rb_surfel));
+        s.run([&] { return rb::launch_probe_light(rb::ProbeLightArgs{*grid, d_coeffs.ptr, d_points.ptr, d_out.ptr, static_cast<uint32_t>(k)}, 0u, s.stream); });
+        s.download(out + done, d_out.ptr, k * sizeof(rb_lit));
+        s.sync();   // the scratch is the next piece's
+    }
+    return s.finish("rb_light_points");
+}
+
+int rb_light_points_device(rb_engine* e, const rb_probe_grid* grid, const rb_sh9* d_coeffs, const rb_surfel* d_points, size_t m,
+                           rb_lit* d_out) {
+    return engine_entry(
+        e, m, [&] { return light_points_check(e, "rb_light_points_device", grid, d_coeffs, d_points, m, d_out); },
+        [&](rb_engine* t) { return light_points_device_locked(t, *grid, d_coeffs, d_points, m, d_out); });
 }
 
 int rb_lightmap_surfels(int32_t device, const rb_gpu_triangle* tris, size_t n_tris, const float* uvs, size_t n_uv_floats,

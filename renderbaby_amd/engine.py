@@ -728,6 +728,59 @@ class Engine:
                                              first_sample, samples, res.ctypes.data if n else None))
         return res
 
+    # ---- light points from a baked probe grid (rb_abi.h)
+    def probe_coefficients(self, sh, out=None):
+        """rb_probe_coefficients_device: abi.SH9 sums (``bake_probes``' result) -> irradiance-over-pi coefficients in the same
+        layout, the weight 1 (a valid probe) or 0 (its record all zero) -- what ``light_points`` blends.  A numpy array in
+        gives abi.SH9[n] out.  An (n, 28) float32 tensor on the engine's device is read where it lies and an (n, 28) tensor
+        comes back: ``out`` if given -- it may be ``sh`` itself, the work is then in place -- or a new one."""
+        import torch
+        if _is_tensor(sh) or _is_tensor(out):
+            src = sh
+        else:
+            host = np.ascontiguousarray(sh, dtype=abi.SH9).reshape(-1)
+            src = torch.from_numpy(host.view(np.float32).reshape(-1, 28).copy()).to(torch.device("cuda", self.query_device))
+        sp, n = self._device_tensor(src, torch.float32, 28, "sh")
+        res = torch.empty_like(src) if out is None else out
+        op, no = self._device_tensor(res, torch.float32, 28, "out")
+        if no != n:
+            raise ValueError("sh and out differ in length")
+        self._device_call(self._lib.rb_probe_coefficients_device, sp, n, op)
+        return res if src is sh else res.cpu().numpy().view(abi.SH9).reshape(-1)
+
+    def light_points(self, grid, coeffs, points, normals=None, out=None):
+        """rb_light_points_device: the lit value of m points from a regular grid of baked probes -- ``grid``: an abi.PROBE_GRID
+        scalar (``probes.grid_params``), ``coeffs``: its nx * ny * nz coefficient records, x fastest (``probe_coefficients``)
+        -- for the points' normals (any length: the device normalises).  ``points`` and ``normals``: (m, 3) each, or
+        ``points`` alone as surfel records (abi.SURFEL[m], or an (m, 8) float32 tensor: pos, 0, normal, 0 -- what
+        ``lightmap_surfels`` makes).  numpy in gives abi.LIT[m] out (``value``: the irradiance over pi, albedo x value is a
+        lambert surface's radiance; ``weight``: the blend weight, 0 where nothing lit the point).  With a torch tensor on the
+        engine's device for the coefficients ((n, 28) float32), the points or ``out`` ((m, 4) float32), every tensor is used
+        where it lies, an (m, 4) tensor comes back and nothing crosses to the host."""
+        import torch
+        g = np.ascontiguousarray(grid, dtype=abi.PROBE_GRID).reshape(1)
+        tensors = _is_tensor(coeffs) or _is_tensor(points) or _is_tensor(normals) or _is_tensor(out)
+        dev = torch.device("cuda", self.query_device)
+        if normals is None:
+            surf = points if _is_tensor(points) else np.ascontiguousarray(points, dtype=abi.SURFEL).reshape(-1)
+        else:
+            surf = self._ray_records(points, normals)
+        if not _is_tensor(surf):
+            surf = torch.from_numpy(surf.view(np.float32).reshape(-1, 8)).to(dev)
+        if not _is_tensor(coeffs):
+            host = np.ascontiguousarray(coeffs, dtype=abi.SH9).reshape(-1)
+            coeffs = torch.from_numpy(host.view(np.float32).reshape(-1, 28)).to(dev)
+        cp, nc = self._device_tensor(coeffs, torch.float32, 28, "coeffs")
+        pp, m = self._device_tensor(surf, torch.float32, 8, "points")
+        res = torch.empty((m, 4), dtype=torch.float32, device=dev) if out is None else out
+        op, no = self._device_tensor(res, torch.float32, 4, "out")
+        if no != m:
+            raise ValueError("points and out differ in length")
+        if nc != int(np.prod(g["counts"][0].astype(np.uint64))):
+            raise ValueError("coeffs: nx * ny * nz records are needed")
+        self._device_call(self._lib.rb_light_points_device, g.ctypes.data, cp, pp, m, op)
+        return res if tensors else res.cpu().numpy().view(abi.LIT).reshape(-1)
+
     def last_probe_project_ms(self):
         """kernel ms of the projection (k_sh_project) in the most recent bake_probes: its share of last_query_ms()"""
         ms = C.c_float()
@@ -972,6 +1025,37 @@ def probe_rays_device(pos, samples, first_sample=0, seeds=None, device=-1):
     if rc != abi.RB_OK:
         raise RenderError(rc, (lib.rb_last_error(None) or b"").decode())
     return rays, seeds_out
+
+
+def probe_coefficients(sh, device=-1):
+    """rb_probe_coefficients: stage 1 alone, no engine -- abi.SH9[n] sums -> abi.SH9[n] coefficients.  ``probes.coefficients``
+    is its numpy model."""
+    sh = np.ascontiguousarray(sh, dtype=abi.SH9).reshape(-1)
+    out = np.zeros(len(sh), dtype=abi.SH9)
+    lib = load()
+    rc = lib.rb_probe_coefficients(int(device), sh.ctypes.data if len(sh) else None, len(sh), out.ctypes.data if len(sh) else None)
+    if rc != abi.RB_OK:
+        raise RenderError(rc, (lib.rb_last_error(None) or b"").decode())
+    return out
+
+
+def light_points(grid, coeffs, points, normals=None, device=-1):
+    """rb_light_points: stage 2, no engine -- abi.LIT[m] of m points from an abi.PROBE_GRID scalar and its nx * ny * nz
+    coefficient records; ``points`` and ``normals`` (m, 3) each, or ``points`` alone as abi.SURFEL[m].  ``probes.light`` is its
+    numpy model."""
+    g = np.ascontiguousarray(grid, dtype=abi.PROBE_GRID).reshape(1)
+    coeffs = np.ascontiguousarray(coeffs, dtype=abi.SH9).reshape(-1)
+    surf = np.ascontiguousarray(points, dtype=abi.SURFEL).reshape(-1) if normals is None else Engine._ray_records(points, normals)
+    if len(coeffs) != int(np.prod(g["counts"][0].astype(np.uint64))):
+        raise ValueError("coeffs: nx * ny * nz records are needed")
+    m = len(surf)
+    out = np.zeros(m, dtype=abi.LIT)
+    lib = load()
+    rc = lib.rb_light_points(int(device), g.ctypes.data, coeffs.ctypes.data if len(coeffs) else None, surf.ctypes.data if m else None, m,
+                             out.ctypes.data if m else None)
+    if rc != abi.RB_OK:
+        raise RenderError(rc, (lib.rb_last_error(None) or b"").decode())
+    return out
 
 
 def lightmap_surfels_device(tris, uvs, width, height, mesh=None, flip=False, device=-1):

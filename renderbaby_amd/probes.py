@@ -1,18 +1,23 @@
-"""The numpy model of the device's irradiance probes (k_probe_rays, k_sh_project, csrc/rb_probe.hip): the
-same binary32 operations in the same order, so ``rays`` equals ``rb_probe_rays`` and ``project`` over the traced colours equals
-``rb_bake_probes`` bit for bit.
+"""The numpy model of the device's irradiance probes (k_probe_rays, k_sh_project, csrc/rb_probe.hip) and
+of the way back in from a baked grid (k_probe_coeffs, k_probe_light, csrc/rb_probe_light.hip; section 19): the same binary32
+operations in the same order, so ``rays`` equals ``rb_probe_rays``, ``project`` over the traced colours equals
+``rb_bake_probes``, ``coefficients`` equals ``rb_probe_coefficients`` and ``light`` equals ``rb_light_points`` bit for bit.
 
 ``records``  abi.PROBE records from (n, 3) positions
 ``direction``  the direction of an item from its two draws
 ``rays``     (origins, normalised directions, seeds) of the (probe, sample) items: uniform on the sphere, world axes
 ``basis``    the nine real spherical harmonics of bands 0-2 of every direction, (m, 9) float32
 ``project``  abi.SH9[n]: per probe the ordered sums of colour x basis over its samples, and the valid samples
+``coefficients``  abi.SH9[n] sums -> abi.SH9[n] irradiance-over-pi coefficients, the weight 1 (a valid probe) or 0
+``light``    abi.LIT[m]: the blend of the eight probes of a regular grid round each point, for the point's normal
+``grid_params``  the abi.PROBE_GRID whose probes are ``grid``'s positions
 
 Host-only conveniences in float64, not part of the bit contract:
 
 ``radiance_coefficients``  L_j = (4 pi / weight) sum[j], (n, 9, 3)
 ``irradiance``             E(n) of Ramamoorthi and Hanrahan 2001 from the coefficients, for any normals
 ``grid``                   the positions of a regular grid of probes inside a box
+``blend64``                ``light``'s blend in float64 with the size of its terms: what tests measure ``light`` against
 """
 import numpy as np
 
@@ -28,6 +33,8 @@ Y20 = f32(0.315391565)
 Y22 = f32(0.546274215)
 # the cosine lobe's zonal factors A_l of bands 0, 1, 2 (Ramamoorthi and Hanrahan 2001, eq. 8) per coefficient
 LOBE = np.array([np.pi] + [2.0 * np.pi / 3.0] * 3 + [np.pi / 4.0] * 5)
+# sums -> coefficients (section 19): K_j = 4 A_l, LOBE times 4 pi / pi, so that sum_j coeff_j Y_j(n) is the irradiance over pi
+K_BAND = np.array([f32(12.566371)] + [f32(8.37758)] * 3 + [f32(3.1415927)] * 5, dtype=f32)
 
 
 def records(pos):
@@ -132,3 +139,141 @@ def grid(lo, hi, counts):
     ax = [lo[a] + (np.arange(counts[a]) + 0.5) / counts[a] * (hi[a] - lo[a]) for a in range(3)]
     z, y, x = np.meshgrid(ax[2], ax[1], ax[0], indexing="ij")
     return np.stack([x.ravel(), y.ravel(), z.ravel()], axis=1).astype(f32)
+
+
+# ---- the way back in: a baked grid lights points
+def _sh_floats(sh, what):
+    """(n, 28) float32 of abi.SH9 records or of an array of their floats, a copy"""
+    a = np.asarray(sh)
+    a = a.view(f32) if a.dtype == abi.SH9 else np.asarray(a, f32)
+    if a.size % 28:
+        raise ValueError(f"{what}: abi.SH9 records or (n, 28) floats are needed")
+    return a.reshape(-1, 28).copy()
+
+
+def coefficients(sh):
+    """abi.SH9[n] coefficients of abi.SH9[n] sums (or (n, 28) floats): a probe is valid if its weight is finite and > 0; then
+    coeff[j][ch] = (sum[j][ch] * K_j) / weight and the weight word is 1.0; an invalid probe is all-zero bits."""
+    a = _sh_floats(sh, "sh")
+    w = a[:, 27]
+    with np.errstate(all="ignore"):
+        valid = (w > 0) & (w < np.inf)
+        c = ((a[:, :27].reshape(-1, 9, 3) * K_BAND[None, :, None]).astype(f32) / w[:, None, None]).astype(f32)
+    out = np.zeros(len(a), dtype=abi.SH9)
+    out["sum"][valid] = c[valid]
+    out["weight"][valid] = f32(1.0)
+    return out
+
+
+def grid_params(lo, hi, counts):
+    """The abi.PROBE_GRID scalar of ``grid(lo, hi, counts)``: origin = the first cell centre, step = the cell size (a count of
+    1: the box size, which nothing reads).  Its probe positions origin + i * step agree with ``grid``'s to rounding."""
+    lo, hi = np.asarray(lo, f64).reshape(3), np.asarray(hi, f64).reshape(3)
+    counts = [int(c) for c in counts]
+    if len(counts) != 3 or min(counts) < 1:
+        raise ValueError("counts: three numbers of at least 1")
+    g = np.zeros(1, dtype=abi.PROBE_GRID)
+    cell = (hi - lo) / np.array(counts, f64)
+    g["origin"], g["step"], g["counts"] = lo + 0.5 * cell, cell, counts
+    return g[0]
+
+
+def _cell(grid, pos):
+    """per axis the lower probe's index (m, 3) uint32 and the share t (m, 3) float32 of the way to the upper one"""
+    g = np.asarray(grid, dtype=abi.PROBE_GRID).reshape(())
+    org, step, cnt = g["origin"].astype(f32), g["step"].astype(f32), g["counts"].astype(np.int64)
+    with np.errstate(all="ignore"):
+        f = ((pos - org[None, :]).astype(f32) / step[None, :]).astype(f32)
+        f = np.where(f > 0, f, f32(0.0)).astype(f32)
+        top = (cnt - 1).astype(f32)[None, :]
+        f = np.where(f < top, f, top).astype(f32)
+        i0 = np.minimum(np.floor(f).astype(np.int64), np.maximum(cnt - 2, 0)[None, :])
+        t = (f - i0.astype(f32)).astype(f32)
+    return i0, t, cnt
+
+
+def _corners(i0, t, cnt):
+    """the eight corners in the definition's order: (record index (m,), geometric weight (m,) float32, exists) each"""
+    one = f32(1.0)
+    u = (one - t).astype(f32)
+    for c in range(8):
+        d = (c & 1, (c >> 1) & 1, c >> 2)
+        exists = all(cnt[a] >= 2 for a in range(3) if d[a])
+        w = [t[:, a] if d[a] else u[:, a] for a in range(3)]
+        ii = [i0[:, a] + (d[a] if cnt[a] >= 2 else 0) for a in range(3)]
+        yield (ii[2] * cnt[1] + ii[1]) * cnt[0] + ii[0], ((w[0] * w[1]).astype(f32) * w[2]).astype(f32), exists
+
+
+def _points(pos, normals):
+    pos, nrm = np.asarray(pos, f32).reshape(-1, 3), np.asarray(normals, f32).reshape(-1, 3)
+    if len(pos) != len(nrm):
+        raise ValueError("pos and normals differ in length")
+    with np.errstate(all="ignore"):
+        len2 = ((nrm[:, 0] * nrm[:, 0] + nrm[:, 1] * nrm[:, 1]).astype(f32) + nrm[:, 2] * nrm[:, 2]).astype(f32)
+    valid = np.isfinite(pos).all(1) & np.isfinite(nrm).all(1) & (nrm != 0).any(1) & np.isfinite(len2)
+    return pos, nrm, valid
+
+
+def light(grid, coeffs, pos, normals):
+    """abi.LIT[m] of (m, 3) points and normals from an abi.PROBE_GRID and its coefficient records (``coefficients``' output,
+    ``grid``'s order): section 19's stage 2, operation for operation.  ``value`` is the irradiance over pi; ``weight`` the
+    blend weight W that was left after invalid probes dropped out (0: nothing lit the point, or the point is invalid)."""
+    pos, nrm, valid = _points(pos, normals)
+    co = _sh_floats(coeffs, "coeffs")
+    i0, t, cnt = _cell(grid, pos)
+    if len(co) != int(cnt[0] * cnt[1] * cnt[2]):
+        raise ValueError("coeffs: nx * ny * nz records are needed")
+    m = len(pos)
+    y = basis(_unit(nrm))
+    E, W = np.zeros((m, 3), f32), np.zeros(m, f32)
+    with np.errstate(all="ignore"):
+        for idx, wg, exists in _corners(i0, t, cnt):
+            if not exists:
+                continue
+            rec = co[idx]
+            w = (wg * rec[:, 27]).astype(f32)
+            e = np.zeros((m, 3), f32)
+            for j in range(9):
+                e = (e + (rec[:, 3 * j:3 * j + 3] * y[:, j:j + 1]).astype(f32)).astype(f32)
+            take = ~(w == 0)   # (a NaN weight is not 0: it is taken, as on the device)
+            E = np.where(take[:, None], (E + (w[:, None] * e).astype(f32)).astype(f32), E)
+            W = np.where(take, (W + w).astype(f32), W)
+        q = (E / W[:, None]).astype(f32)
+        lit = valid & (W > 0)
+    out = np.zeros(m, dtype=abi.LIT)
+    out["value"][lit] = np.where(q > 0, q, f32(0.0)).astype(f32)[lit]
+    out["weight"][lit] = W[lit]
+    return out
+
+
+def blend64(grid, coeffs, pos, normals, corner_values=None):
+    """``light``'s blend in float64 from the same binary32 cell indices and shares: (value (m, 3) before the clamp at 0,
+    W (m,), size (m, 3) = sum |w_c coeff Y| / W, the yardstick of a rounding-error bound).  ``corner_values(idx, unit
+    normals)`` -> (m, 3) replaces the nine-term dot product of a corner (a reference that evaluates the probes another way)."""
+    pos, nrm, valid = _points(pos, normals)
+    co = _sh_floats(coeffs, "coeffs").astype(f64)
+    i0, t, cnt = _cell(grid, pos)
+    m = len(pos)
+    n64 = nrm.astype(f64)
+    with np.errstate(all="ignore"):
+        n64 = n64 / np.sqrt((n64 * n64).sum(1))[:, None]
+    x, yy, z = n64[:, 0], n64[:, 1], n64[:, 2]
+    y = np.stack([np.full(m, f64(Y0)), f64(Y1) * yy, f64(Y1) * z, f64(Y1) * x, f64(Y2A) * x * yy, f64(Y2A) * yy * z,
+                  f64(Y20) * (3.0 * z * z - 1.0), f64(Y2A) * x * z, f64(Y22) * (x * x - yy * yy)], axis=1)
+    E, S, W = np.zeros((m, 3)), np.zeros((m, 3)), np.zeros(m)
+    t64 = t.astype(f64)
+    for c, (idx, _, exists) in enumerate(_corners(i0, t, cnt)):
+        if not exists:
+            continue
+        d = (c & 1, (c >> 1) & 1, c >> 2)
+        wg = np.prod([t64[:, a] if d[a] else 1.0 - t64[:, a] for a in range(3)], axis=0)
+        rec = co[idx]
+        w = wg * rec[:, 27]
+        terms = rec[:, :27].reshape(m, 9, 3) * y[:, :, None]
+        e = terms.sum(1) if corner_values is None else np.asarray(corner_values(idx, n64), f64)
+        take = w != 0
+        E += np.where(take[:, None], w[:, None] * e, 0.0)
+        S += np.where(take[:, None], np.abs(w)[:, None] * np.abs(terms).sum(1), 0.0)
+        W += np.where(take, w, 0.0)
+    with np.errstate(all="ignore"):
+        return E / W[:, None], W, S / W[:, None]

@@ -7,7 +7,7 @@
                                  [--camera equirect|ortho|thin-lens [--ortho-width W] [--aperture A --focus-distance F] [--jitter]]
                                  [--probe x,y,z [--probe-normal x,y,z]] [--device-rays]
                                  [--lightmap W H [--lightmap-mesh i] [--lightmap-flip]]
-                                 [--probe-grid NX NY NZ]
+                                 [--probe-grid NX NY NZ] [--lit-by-probes NX NY NZ]
 
 scene file -> scene_io.load_scene (the importer's and the Scene->RenderConfig adapter's rules) ->
 RenderConfig -> librenderbaby_hip.so -> Frame -> PNG.  With --every N the progressive iterator is used
@@ -28,7 +28,10 @@ texture's own encoding (bake.lightmap_texture), for one mesh with --lightmap-mes
 of the same texels (aov.ambient_occlusion_map) as out.lightmap.ao.png.  --probe-grid NX NY NZ bakes a grid of irradiance probes
 over the bounding box of the scene's triangles and spheres (probes.grid -> bake.probes: Engine.bake_probes, spp uniform-sphere
 rays per probe, traced and projected onto SH9 on the device) and writes out.probes.npz with `positions`
-(n, 3) and `coefficients` (n, 9, 3), which probes.irradiance evaluates for any normal.
+(n, 3) and `coefficients` (n, 9, 3), which probes.irradiance evaluates for any normal.  --lit-by-probes NX NY NZ bakes the same
+grid (bake.probe_grid, spp rays per probe) and lights the first hits of the pixel centres from it in one launch
+(aov.probe_lit -> Engine.light_points): out.probe_lit.png through aov.color_map shows what the grid holds --
+emission + albedo x the blended irradiance over pi, no shadows --, so a bake can be judged before anything consumes it.
 """
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -57,6 +60,8 @@ ap.add_argument("--lightmap-mesh", type=int, default=None, help="--lightmap for 
 ap.add_argument("--lightmap-flip", action="store_true", help="--lightmap with the triangles' normals negated")
 ap.add_argument("--probe-grid", type=int, nargs=3, metavar=("NX", "NY", "NZ"), default=None,
                 help="also bake a grid of irradiance probes over the scene's bounding box, as out.probes.npz")
+ap.add_argument("--lit-by-probes", type=int, nargs=3, metavar=("NX", "NY", "NZ"), default=None,
+                help="also light the first hits from a grid of probes baked over the scene's bounding box, as out.probe_lit.png")
 a = ap.parse_args()
 aovs = [n for n in a.aov.split(",") if n]
 for n in aovs:
@@ -148,14 +153,22 @@ if a.lightmap:
         img = aov.ao_u8(np.where(np.isnan(ao), np.float32(0), ao))
         scene_io.export_png(f"{base}.lightmap.ao{ext}", Frame(w, h, img))
         print(f"ambient-occlusion map with {eng.last_query_kernel_name()} in {eng.last_query_ms():.3f} ms -> {base}.lightmap.ao{ext}")
-if a.probe_grid:
+
+
+def scene_box(option):
+    """the bounding box of the scene's triangles and spheres, for the options that span a grid of probes over it"""
     import numpy as np
     tri = s.bvh_triangles
     lo = [tri[k].reshape(-1, 3) for k in ("v0", "v1", "v2")] + [s.spheres["center"] - s.spheres["radius"][:, None]]
     hi = lo[:3] + [s.spheres["center"] + s.spheres["radius"][:, None]]
     if not len(tri) and not len(s.spheres):
-        ap.error("--probe-grid: the scene has neither triangles nor spheres to span a box")
-    lo, hi = np.concatenate(lo).min(0), np.concatenate(hi).max(0)
+        ap.error(f"{option}: the scene has neither triangles nor spheres to span a box")
+    return np.concatenate(lo).min(0), np.concatenate(hi).max(0)
+
+
+if a.probe_grid:
+    import numpy as np
+    lo, hi = scene_box("--probe-grid")
     pos = probes.grid(lo, hi, a.probe_grid)
     spp = min(max(s.total_samples, 1), 65536)
     coeff = bake.probes(eng, pos, spp)
@@ -163,4 +176,16 @@ if a.probe_grid:
     np.savez(f"{base}.probes.npz", positions=pos, coefficients=coeff)
     print(f"{len(pos)} probes over {tuple(float(v) for v in lo)} .. {tuple(float(v) for v in hi)}, {spp} rays each, with {eng.last_query_kernel_name()} in {eng.last_query_ms():.3f} ms "
           f"(generator {eng.last_camera_rays_ms():.3f}, projection {eng.last_probe_project_ms():.3f}) -> {base}.probes.npz")
+if a.lit_by_probes:
+    lo, hi = scene_box("--lit-by-probes")
+    spp = min(max(s.total_samples, 1), 65536)
+    grid, coeffs = bake.probe_grid(eng, lo, hi, a.lit_by_probes, spp)
+    hits, surf = eng.render_hits(surfaces=True)
+    import numpy as np
+    rgb = aov.color_map(aov.probe_lit(eng, grid, coeffs, hits, surf))
+    img = np.concatenate([rgb, np.full(rgb.shape[:2] + (1,), 255, np.uint8)], axis=-1)
+    base, ext = os.path.splitext(a.png)
+    scene_io.export_png(f"{base}.probe_lit{ext}", Frame(img.shape[1], img.shape[0], img))
+    print(f"{len(coeffs)} probes over {tuple(float(v) for v in lo)} .. {tuple(float(v) for v in hi)}, {spp} rays each ({int((coeffs['weight'] > 0).sum())} valid); "
+          f"the first hits of {s.width}x{s.height} pixels lit with {eng.last_query_kernel_name()} in {eng.last_query_ms():.3f} ms -> {base}.probe_lit{ext}")
 eng.close()
