@@ -891,8 +891,9 @@ int rb_last_probe_project_ms(rb_engine* e, float* ms);
  *          out = W > 0 ? {max(E.r / W, 0.0f), max(E.g / W, 0.0f), max(E.b / W, 0.0f), W} : {0, 0, 0, 0}.
  * `value` is the irradiance over pi -- what rb_trace_hemisphere's sum / weight estimates --, so albedo x value is a lambert
  * surface's outgoing radiance.  A point outside the grid takes the values at the nearest cell's edge.  A caller rejects a probe
- * (one inside geometry, say) by zeroing its weight before stage 1: the blend renormalises over the rest.  Not here: visibility
- * or backface weights against leaks, and anything but a regular axis-aligned grid. */
+ * (one inside geometry, say) by zeroing its weight before stage 1: the blend renormalises over the rest.  Visibility and backface
+ * weights against leaks, and what finds such a probe: rb_light_points_visible below (section 20).  Not here: anything but a
+ * regular axis-aligned grid. */
 typedef struct rb_probe_grid {                                                                      /* 48 B */
     float origin[3];      /* finite */
     uint32_t _pad0;       /* must be 0 */
@@ -926,6 +927,81 @@ int rb_light_points(int32_t device, const rb_probe_grid* grid, const rb_sh9* coe
  * other launch shape for a measurement; the result does not depend on it). */
 int rb_light_points_device(rb_engine* e, const rb_probe_grid* grid, const rb_sh9* d_coeffs, const rb_surfel* d_points, size_t m,
                            rb_lit* d_out);
+
+/* ---- Probe visibility: depth moments baked on the device, a leak-free blend (the normative definition;
+ * no reference counterpart; after Majercik et al. 2019, "Dynamic Diffuse Global Illumination with Ray-Traced Irradiance
+ * Fields").  Each probe keeps an 8 x 8 octahedral map of the mean and the mean square of the distance to the first hit; the
+ * blend weighs every corner by a Chebyshev bound of the point's distance against them and by a wrapped cosine of the point's
+ * normal towards the probe; the share of a probe's rays that met a back face tells which probes sit inside geometry.  Every
+ * step is one IEEE binary32 operation in the order written, no contraction, / and sqrt correctly rounded: the numpy model
+ * renderbaby_amd/probes.py (oct_texel, depth_project, moments, light_visible) equals the device bit for bit -- but for the sign
+ * and payload of a NaN the arithmetic itself generates.  max(x, y) is x > y ? x : y and min(x, y) is x < y ? x : y.  Points so
+ * far from the grid that a difference of positions overflows are outside the contract (nothing is read out of bounds).
+ *   TEXEL  oct_texel(v), v any non-zero vector, not normalised:
+ *          s = (|vx| + |vy|) + |vz|;  px = vx / s;  py = vy / s;
+ *          if vz < 0.0f: (px, py) = ((1.0f - |py|) * sgn(px), (1.0f - |px|) * sgn(py)) with the old px, py on the right,
+ *          sgn(x) = x >= 0.0f ? 1.0f : -1.0f  (vz == -0.0f stays in the upper half);
+ *          tx = min(uint(floor((px * 0.5f + 0.5f) * 8.0f)), 7), ty likewise from py;  T = ty * 8 + tx.  Nearest texel only.
+ *   BAKE   probe i, sample k: the ray is rb_bake_probes' (same ids, first_sample and samples: the same record), the hit
+ *          rb_cast_rays' of that record.  From all-zero bits, in ascending k: a sample whose stored direction is 0 0 0 or whose
+ *          hit kind is RB_HIT_INVALID is skipped; else T = oct_texel(d as stored), r = min(hit.t, max_distance) (a miss has
+ *          t = 1e20f: max_distance), texel[T] += {r, r * r, 1.0f, back} with back = 1.0f if the kind is RB_HIT_TRIANGLE or
+ *          RB_HIT_SPHERE and (n.x d.x + n.y d.y) + n.z d.z > 0.0f, n = hit.normal, else the word stays as it is.
+ *   MOMENTS per texel {sum_r, sum_r2, count, back}: count > 0 and finite: {sum_r / count, sum_r2 / count, 1.0f, back / count};
+ *          else all-zero bits.  backface_share[i] = C == 0 ? 0.0f : B / C, B and C the sums of `back` and `count` over the
+ *          texels in ascending order from +0.0f (sums of integers: below 2^24 samples any order gives the same bits).
+ *   BLEND  rb_light_points' stage 2 with every existing corner's weight extended: tl = ((wx * wy) * wz) * coeff[c].weight;
+ *          a corner with tl == 0 is skipped as there; else, per axis a, P_a = origin_a + float(i_a + d_a) * step_a;
+ *          q = P - pos;  l = sqrt((qx qx + qy qy) + qz qz);  cw = l > 0.0f ? ((qx n.x + qy n.y) + qz n.z) / l : 1.0f;
+ *          h = (cw + 1.0f) * 0.5f;  wb = h * h + 0.2f  (RB_VIS_NO_WRAP: wb = 1.0f);
+ *          b_a = pos_a + n_a * normal_bias;  v = b - P;  r = sqrt((vx vx + vy vy) + vz vz);
+ *          vis = 1.0f if RB_VIS_NO_DEPTH or r == 0.0f; else (mean, mean2, valid, _) = moments[c].texel[oct_texel(v)] and
+ *          vis = 1.0f if valid == 0.0f or !(r > mean), else var = |mean2 - mean * mean|;  dl = r - mean;  den = var + dl * dl;
+ *          ch = den > 0.0f ? var / den : 1.0f;  vis = (ch * ch) * ch;
+ *          vis = max(vis, min_visibility);  w_c = (tl * wb) * vis;  a corner with w_c == 0 is skipped like one that does not
+ *          exist.  E, W and the output are rb_light_points'.  With both flags w_c = tl: rb_light_points' result bit for bit. */
+typedef struct rb_probe_depth { float texel[64][4]; } rb_probe_depth;     /* 1024 B; a texel: {sum_r, sum_r2, count, back} */
+enum { RB_VIS_NO_WRAP = 1, RB_VIS_NO_DEPTH = 2 };
+typedef struct rb_light_visibility {                                                                /* 16 B */
+    float normal_bias;      /* finite: the point moves this far along its unit normal before the depth test */
+    float min_visibility;   /* 0 .. 1: the floor of the depth weight */
+    uint32_t flags;         /* RB_VIS_* */
+    uint32_t _pad;          /* must be 0 */
+} rb_light_visibility;
+/* The depth bake: rb_bake_probes' arguments and max_distance in, out[n] raw sums (a caller may accumulate them over calls).
+ * Refusals, pieces of whole probes (at most 2^22 items, whole blocks of 64 probes: the hit scratch is rb_cast_rays';
+ * RB_DEPTH_PIECE_ITEMS in the environment, read per call: fewer items, for tests; the result does not depend on it), sharded
+ * engines, multi-device handles and side effects (a query's: none) as rb_bake_probes; max_distance not finite or not > 0:
+ * RB_ERR_INVALID_OPTIONS before any device is touched.  rb_last_query_kernel_name reports "k_query", "k_query_bvh" or
+ * "k_query_chunk", rb_last_query_ms the generator, the query and the projection together, rb_last_camera_rays_ms the
+ * generator's share.  RB_DEPTH_SHAPE=lds|readlane in the environment chooses the projection's other fold for a measurement;
+ * the result does not depend on it. */
+int rb_bake_probe_depth(rb_engine* e, const rb_probe* probes, const uint32_t* seeds, size_t n, uint32_t first_sample, uint32_t samples,
+                        float max_distance, rb_probe_depth* out);
+/* The same with d_probes and d_out (16-byte aligned) and d_seeds (may be NULL) in device memory of the engine's device; queued
+ * on the engine's stream, returns without waiting: rb_sync is the wait. */
+int rb_bake_probe_depth_device(rb_engine* e, const rb_probe* d_probes, const uint32_t* d_seeds, size_t n, uint32_t first_sample,
+                               uint32_t samples, float max_distance, rb_probe_depth* d_out);
+/* Measurement aid for tools/probe_visibility_rate.py (it may change or go): the projection's share of the kernel time of the
+ * most recent rb_bake_probe_depth / _device, as rb_last_probe_project_ms. */
+int rb_last_probe_depth_project_ms(rb_engine* e, float* ms);
+/* MOMENTS, no engine, on `device` (-1 = current): sums[n] -> moments_out[n] (it may be sums) and, unless NULL,
+ * backface_share_out[n]; host arrays.  n above 2^31 - 64: RB_ERR_INVALID_OPTIONS; NULL sums or moments_out with n > 0:
+ * RB_ERR_NULL_ARGUMENT; both before any device is touched.  n == 0 is RB_OK. */
+int rb_probe_moments(int32_t device, const rb_probe_depth* sums, size_t n, rb_probe_depth* moments_out, float* backface_share_out);
+/* The same in device memory of the engine's device (16-byte aligned, the share 4-byte; d_moments_out may be d_sums), as
+ * rb_probe_coefficients_device in every other respect; rb_last_query_kernel_name reports "k_probe_moments". */
+int rb_probe_moments_device(rb_engine* e, const rb_probe_depth* d_sums, size_t n, rb_probe_depth* d_moments_out, float* d_backface_share_out);
+/* BLEND, no engine: rb_light_points with the grid's nx * ny * nz moment maps (the records' order) and the parameters.  Refusals
+ * as rb_light_points, and RB_ERR_NULL_ARGUMENT: NULL params; NULL moments with m > 0 unless RB_VIS_NO_DEPTH is set (they are not
+ * read then); RB_ERR_INVALID_OPTIONS: normal_bias not finite, min_visibility outside [0, 1] or NaN, flag bits other than
+ * RB_VIS_*, a non-zero pad.  Maps and records are uploaded once, the points go in rb_light_points' pieces. */
+int rb_light_points_visible(int32_t device, const rb_probe_grid* grid, const rb_sh9* coeffs, const rb_probe_depth* moments,
+                            const rb_surfel* points, size_t m, const rb_light_visibility* params, rb_lit* out);
+/* The same in device memory of the engine's device, as rb_light_points_device; rb_last_query_kernel_name reports
+ * "k_probe_light_vis". */
+int rb_light_points_visible_device(rb_engine* e, const rb_probe_grid* grid, const rb_sh9* d_coeffs, const rb_probe_depth* d_moments,
+                                   const rb_surfel* d_points, size_t m, const rb_light_visibility* params, rb_lit* d_out);
 
 /* ---- Edge-avoiding denoiser over the first-hit buffers (no reference counterpart).  An a-trous wavelet
  * filter (Dammertz et al. 2010) on the albedo-demodulated mean radiance, guided by the first hit of every pixel-centre ray.
@@ -1049,6 +1125,9 @@ static_assert(offsetof(rb_probe_grid, step) == 16, "step @16");
 static_assert(offsetof(rb_probe_grid, counts) == 32, "counts @32");
 static_assert(offsetof(rb_probe_grid, flags) == 44, "flags @44");
 static_assert(sizeof(rb_lit) == 16, "rb_lit is 16 B");
+static_assert(sizeof(rb_probe_depth) == 1024, "rb_probe_depth is 1024 B");
+static_assert(sizeof(rb_light_visibility) == 16, "rb_light_visibility is 16 B");
+static_assert(offsetof(rb_light_visibility, flags) == 8, "flags @8");
 static_assert(sizeof(rb_guide) == 48, "rb_guide is 48 B");
 static_assert(sizeof(rb_denoise_params) == 32, "rb_denoise_params is 32 B");
 static_assert(offsetof(rb_guide, t) == 12, "t @12");
@@ -1081,6 +1160,8 @@ _Static_assert(sizeof(rb_probe) == 16, "rb_probe is 16 B");
 _Static_assert(sizeof(rb_sh9) == 112, "rb_sh9 is 112 B");
 _Static_assert(sizeof(rb_probe_grid) == 48, "rb_probe_grid is 48 B");
 _Static_assert(sizeof(rb_lit) == 16, "rb_lit is 16 B");
+_Static_assert(sizeof(rb_probe_depth) == 1024, "rb_probe_depth is 1024 B");
+_Static_assert(sizeof(rb_light_visibility) == 16, "rb_light_visibility is 16 B");
 _Static_assert(sizeof(rb_guide) == 48, "rb_guide is 48 B");
 _Static_assert(sizeof(rb_denoise_params) == 32, "rb_denoise_params is 32 B");
 #endif

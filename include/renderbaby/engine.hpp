@@ -331,6 +331,43 @@ class Engine final : public Renderer {
     void light_points_device(const rb_probe_grid& grid, const rb_sh9* d_coeffs, const rb_surfel* d_points, size_t m, rb_lit* d_out) {
         check(h_->e, rb_light_points_device(h_->e, &grid, d_coeffs, d_points, m, d_out));
     }
+    // ---- probe visibility (extension; rb_abi.h): per probe an 8 x 8 octahedral map of the sums of the
+    // first-hit distance, its square, the samples and the back faces among them; the moments of the sums with the share of
+    // back faces per probe (above a quarter or so: the probe sits inside geometry); the blend with every corner weighed by
+    // the map and by the wrapped cosine of the point's normal.  The forms without an engine run on `device` (-1: the current one).
+    std::vector<rb_probe_depth> bake_probe_depth(const std::vector<rb_probe>& probes, uint32_t samples, float max_distance,
+                                                 uint32_t first_sample = 0, const uint32_t* seeds = nullptr) {
+        std::vector<rb_probe_depth> out(probes.size());
+        check(h_->e, rb_bake_probe_depth(h_->e, probes.data(), seeds, probes.size(), first_sample, samples, max_distance, out.data()));
+        return out;
+    }
+    void bake_probe_depth_device(const rb_probe* d_probes, const uint32_t* d_seeds, size_t n, rb_probe_depth* d_out, uint32_t samples,
+                                 float max_distance, uint32_t first_sample = 0) {
+        check(h_->e, rb_bake_probe_depth_device(h_->e, d_probes, d_seeds, n, first_sample, samples, max_distance, d_out));
+    }
+    static std::vector<rb_probe_depth> probe_moments(const std::vector<rb_probe_depth>& sums, std::vector<float>* backface_share = nullptr,
+                                                     int32_t device = -1) {
+        std::vector<rb_probe_depth> out(sums.size());
+        if (backface_share) backface_share->assign(sums.size(), 0.0f);
+        check(nullptr, rb_probe_moments(device, sums.data(), sums.size(), out.data(), backface_share ? backface_share->data() : nullptr));
+        return out;
+    }
+    static std::vector<rb_lit> light_points_visible(const rb_probe_grid& grid, const std::vector<rb_sh9>& coeffs,
+                                                    const std::vector<rb_probe_depth>& moments, const std::vector<rb_surfel>& points,
+                                                    const rb_light_visibility& params, int32_t device = -1) {
+        std::vector<rb_lit> out(points.size());
+        check(nullptr, rb_light_points_visible(device, &grid, coeffs.data(), moments.empty() ? nullptr : moments.data(), points.data(),
+                                               points.size(), &params, out.data()));
+        return out;
+    }
+    // the same on the engine's device memory (d_moments_out may be d_sums, d_backface_share_out nullptr)
+    void probe_moments_device(const rb_probe_depth* d_sums, size_t n, rb_probe_depth* d_moments_out, float* d_backface_share_out = nullptr) {
+        check(h_->e, rb_probe_moments_device(h_->e, d_sums, n, d_moments_out, d_backface_share_out));
+    }
+    void light_points_visible_device(const rb_probe_grid& grid, const rb_sh9* d_coeffs, const rb_probe_depth* d_moments, const rb_surfel* d_points,
+                                     size_t m, const rb_light_visibility& params, rb_lit* d_out) {
+        check(h_->e, rb_light_points_visible_device(h_->e, &grid, d_coeffs, d_moments, d_points, m, &params, d_out));
+    }
     void sync() { check(h_->e, rb_sync(h_->e)); }
     // ---- the denoiser (rb_abi.h): the a-trous filter over the committed accumulation
     static rb_denoise_params denoise_defaults() {

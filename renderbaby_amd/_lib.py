@@ -116,6 +116,13 @@ def load():
         "rb_probe_coefficients_device": (i32, [vp, vp, sz, vp]),
         "rb_light_points": (i32, [i32, vp, vp, vp, sz, vp]),
         "rb_light_points_device": (i32, [vp, vp, vp, vp, sz, vp]),
+        "rb_bake_probe_depth": (i32, [vp, vp, vp, sz, u32, u32, C.c_float, vp]),
+        "rb_bake_probe_depth_device": (i32, [vp, vp, vp, sz, u32, u32, C.c_float, vp]),
+        "rb_last_probe_depth_project_ms": (i32, [vp, P(C.c_float)]),
+        "rb_probe_moments": (i32, [i32, vp, sz, vp, vp]),
+        "rb_probe_moments_device": (i32, [vp, vp, sz, vp, vp]),
+        "rb_light_points_visible": (i32, [i32, vp, vp, vp, vp, sz, vp, vp]),
+        "rb_light_points_visible_device": (i32, [vp, vp, vp, vp, vp, sz, vp, vp]),
         "rb_last_query_kernel_name": (C.c_char_p, [vp]),
         "rb_last_query_ms": (i32, [vp, P(C.c_float)]),
         "rb_denoise_default_params": (i32, [vp]),
@@ -163,4 +170,6 @@ EXPORTS = ["rb_create", "rb_create_ex", "rb_create_multi", "rb_comm_available", 
            "rb_lightmap_surfels", "rb_lightmap_surfels_device", "rb_lightmap_resolve", "rb_bake_lightmap", "rb_bake_lightmap_device", "rb_last_lightmap_ms",
            "rb_probe_rays", "rb_bake_probes", "rb_bake_probes_device", "rb_last_probe_project_ms",
            "rb_probe_coefficients", "rb_probe_coefficients_device", "rb_light_points", "rb_light_points_device",
+           "rb_bake_probe_depth", "rb_bake_probe_depth_device", "rb_last_probe_depth_project_ms", "rb_probe_moments", "rb_probe_moments_device",
+           "rb_light_points_visible", "rb_light_points_visible_device",
            "rb_denoise_default_params", "rb_denoise_buffers", "rb_denoise", "rb_denoise_device", "rb_denoise_guides", "rb_last_denoise_ms", "rb_fast_bvh_builder", "rb_sphere_tree_builder", "rb_chunk_tree_builder", "rb_debug_engine_chunk_tree", "rb_version", "rb_device_name"]

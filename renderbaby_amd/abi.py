@@ -81,6 +81,12 @@ PROBE_PIECE_ITEMS = 1 << 23
 PROBE_GRID = np.dtype([("origin", f4, (3,)), ("_pad0", u4), ("step", f4, (3,)), ("_pad1", u4), ("counts", u4, (3,)), ("flags", u4)])
 LIT = np.dtype([("value", f4, (3,)), ("weight", f4)])
 LIGHT_PIECE_POINTS = 1 << 22
+# probe visibility (rb_bake_probe_depth / rb_probe_moments / rb_light_points_visible): a probe's 8 x 8
+# octahedral map, texel ty * 8 + tx = {sum_r, sum_r2, count, back} (sums) or {mean, mean2, valid, back share} (moments), and
+# the blend's parameters
+PROBE_DEPTH = np.dtype([("texel", f4, (64, 4))])
+LIGHT_VISIBILITY = np.dtype([("normal_bias", f4), ("min_visibility", f4), ("flags", u4), ("_pad", u4)])
+VIS_NO_WRAP, VIS_NO_DEPTH = 1, 2
 # any-hit occlusion (rb_occluded): result bytes and stage masks
 OCCL_VISIBLE, OCCL_OCCLUDED, OCCL_INVALID = 0, 1, 255
 MASK_GROUND, MASK_TRIANGLES, MASK_SPHERES, MASK_LIGHTS, MASK_ALL = 1, 2, 4, 8, 15
@@ -96,7 +102,8 @@ SIZES = {"camera": (CAMERA, 48), "uniforms": (UNIFORMS, 144), "material": (MATER
          "guide": (GUIDE, 48), "denoise_params": (DENOISE_PARAMS, 32), "camera_ex": (CAMERA_EX, 96),
          "surfel": (SURFEL, 32), "hemi_params": (HEMI_PARAMS, 32), "openness": (OPENNESS, 8),
          "lightmap_params": (LIGHTMAP_PARAMS, 32), "probe": (PROBE, 16), "sh9": (SH9, 112),
-         "probe_grid": (PROBE_GRID, 48), "lit": (LIT, 16)}
+         "probe_grid": (PROBE_GRID, 48), "lit": (LIT, 16),
+         "probe_depth": (PROBE_DEPTH, 1024), "light_visibility": (LIGHT_VISIBILITY, 16)}
 for _n, (_dt, _sz) in SIZES.items():
     assert _dt.itemsize == _sz, (_n, _dt.itemsize, _sz)
 

@@ -205,14 +205,16 @@ def ambient_occlusion_device(engine, hits, samples=16, radius=1.0, first_sample=
     return ao
 
 
-def probe_lit(engine, grid, coeffs, hits, surfaces, uniforms=None):
+def probe_lit(engine, grid, coeffs, hits, surfaces, uniforms=None, moments=None, visibility=None):
     """What a baked probe grid looks like on the scene (Engine.light_points, rb_light_points_device): the
     first hits ``engine.render_hits(surfaces=True)`` returned, lit from the grid in one launch -- ``grid``: an abi.PROBE_GRID
     scalar, ``coeffs``: its coefficient records (``bake.probe_grid`` makes both).  Linear RGB float32 [rows, width, 3] in the
     orientation of the frame, for ``color_map``: a filterable hit (the denoiser's rule: a surface that emits nothing) gives
     emission + albedo x value with the normal turned towards the camera; a light or an emitting surface its emission; a miss
     the sky, as the records hold it; a pixel the grid does not reach (weight 0) albedo x 0.  No shadows, no leaks held back:
-    it shows the probes, not the scene's light."""
+    it shows the probes, not the scene's light.  With ``moments`` (``bake.probe_grid(visibility=True)``'s maps) the blend is
+    Engine.light_points_visible's (section 20), which holds the leaks back; ``visibility``: its keyword arguments (normal_bias,
+    min_visibility, wrap, depth), None for the defaults."""
     u = engine.uniforms if uniforms is None else uniforms
     if u is None:
         raise ValueError("the engine has accepted no update yet: call update() / render() first, or pass uniforms=")
@@ -220,7 +222,10 @@ def probe_lit(engine, grid, coeffs, hits, surfaces, uniforms=None):
     img = surfaces["emissive"].astype(np.float32).copy()
     lit = m & (hits["kind"] != abi.HIT_LIGHT) & ~(surfaces["emissive"] > 0).any(-1)
     if len(pts):
-        res = engine.light_points(grid, coeffs, pts, nrm)
+        if moments is None and visibility is None:
+            res = engine.light_points(grid, coeffs, pts, nrm)
+        else:
+            res = engine.light_points_visible(grid, coeffs, moments, pts, nrm, **(visibility or {}))
         value = np.zeros(hits.shape + (3,), dtype=np.float32)
         value[m] = np.where(res["weight"][:, None] > 0, res["value"], np.float32(0))
         img[lit] = (img[lit] + surfaces["albedo"][lit].astype(np.float32) * value[lit]).astype(np.float32)

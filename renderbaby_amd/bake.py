@@ -90,16 +90,27 @@ def probes(engine, pos, samples, first_sample=0, seeds=None):
     return model.radiance_coefficients(sh if isinstance(sh, np.ndarray) else sh.cpu().numpy())
 
 
-def probe_grid(engine, lo, hi, counts, samples, first_sample=0, seeds=None):
+def probe_grid(engine, lo, hi, counts, samples, first_sample=0, seeds=None, visibility=False, backface_limit=0.25):
     """A regular grid of irradiance probes over the box ``lo`` .. ``hi``, ``counts`` = (nx, ny, nz) cell centres along the axes
     (``probes.grid``), baked with ``samples`` rays per probe (Engine.bake_probes) and scaled to coefficients
     (Engine.probe_coefficients).  Returns (grid, coeffs): an abi.PROBE_GRID scalar and abi.SH9[nx * ny * nz],
     x fastest -- what ``Engine.light_points`` and ``aov.probe_lit`` take.  To accumulate over calls with ``first_sample``, add
-    ``Engine.bake_probes``' sums and call ``Engine.probe_coefficients`` once at the end."""
+    ``Engine.bake_probes``' sums and call ``Engine.probe_coefficients`` once at the end.
+
+    ``visibility=True`` (section 20) bakes the probes' depth maps from the same rays as well (Engine.bake_probe_depth, distances
+    clipped at 1.5 cell diagonals; Engine.probe_moments), gives every probe more than ``backface_limit`` of whose rays met a
+    back face -- one inside geometry -- the weight 0 before the coefficients are made, and returns (grid, coeffs, moments):
+    what ``Engine.light_points_visible`` takes."""
     from . import probes as model
     grid = model.grid_params(lo, hi, counts)
-    sh = engine.bake_probes(model.grid(lo, hi, counts), samples, first_sample=first_sample, seeds=seeds)
-    return grid, engine.probe_coefficients(sh)
+    pos = model.grid(lo, hi, counts)
+    sh = engine.bake_probes(pos, samples, first_sample=first_sample, seeds=seeds)
+    if not visibility:
+        return grid, engine.probe_coefficients(sh)
+    reach = 1.5 * float(np.sqrt((grid["step"].astype(np.float64) ** 2).sum()))
+    maps, share = engine.probe_moments(engine.bake_probe_depth(pos, samples, reach, first_sample=first_sample, seeds=seeds))
+    sh["weight"][share > np.float32(backface_limit)] = 0
+    return grid, engine.probe_coefficients(sh), maps
 
 
 def lightmap_texture(rgba):

@@ -187,6 +187,7 @@ struct rb_engine {
     rb::DevBuf<rb_openness> hemi_open;
     rb::DevBuf<rb_probe> probe_pos;       // rb_bake_probes: the piece's probes and its SH9 sums
     rb::DevBuf<rb_sh9> probe_out;
+    rb::DevBuf<rb_probe_depth> depth_out; // rb_bake_probe_depth: the piece's maps (its records and hits: q_rays, q_hits)
     // lightmap texels made on the device (rb_lightmap_surfels_device / rb_bake_lightmap*): the triangles
     // prepared in triangle order, the cover pass's scratch, and what a bake keeps between its stages
     rb::DevBuf<rb::PrepTri> lm_ptris;
@@ -203,6 +204,8 @@ struct rb_engine {
     size_t cam_pieces = 0;           // pairs the most recent query recorded; 0 from every query's prologue on
     std::vector<hipEvent_t> ev_sh;   // rb_bake_probes*: a pair around every piece's projection (rb_last_probe_project_ms)
     size_t sh_pieces = 0;
+    std::vector<hipEvent_t> ev_depth;   // rb_bake_probe_depth*: a pair around every piece's projection (rb_last_probe_depth_project_ms)
+    size_t depth_pieces = 0;
     const char* last_query_kernel_name = "";
     float last_query_ms = 0.0f;
     bool query_ms_pending = false;   // the device forms return without waiting: rb_last_query_ms reads ev_q when asked

@@ -1,7 +1,7 @@
 // rb_queries.cpp -- what an engine answers besides frames: closest-hit queries (rb_cast_rays / rb_render_hits / rb_pick), any-hit
 // occlusion, path-traced radiance along given rays, camera and hemisphere rays, lightmap texels and irradiance probes made on the
-// device, light points from a baked probe grid and the denoiser over the first-hit buffers, with their device forms, their
-// getters and their C entry points (rb_abi.h; DESIGN.md sections 11-19).
+// device, light points from a baked probe grid with or without the probes' depth moments, and the denoiser over the first-hit
+// buffers, with their device forms, their getters and their C entry points (rb_abi.h; DESIGN.md sections 11-20).
 // Every sequence is here once: one prologue (query_prologue), one timed
 // launch (timed_launch), one runner per form -- run_pieces for the host forms, device_query_locked for the device forms --, over
 // them one runner for the families of "n items, `samples` each" in both forms (run_family: radiance, camera, hemisphere,
@@ -52,7 +52,7 @@ int scene_params(rb_engine* e, rb::KParams* p) {
 // (section 19) -- nothing is prepared for it.
 int query_prologue(rb_engine* e, rb::KParams* p) {
     e->last_query_ms = 0.0f;
-    e->cam_pieces = e->sh_pieces = 0;
+    e->cam_pieces = e->sh_pieces = e->depth_pieces = 0;
     int rc = require_ready(e);
     if (!rc && p) rc = ensure_prepared(e);
     if (!rc && p) rc = scene_params(e, p);
@@ -534,6 +534,48 @@ int probes_locked(rb_engine* e, bool device, const rb_probe* probes, const uint3
                       });
 }
 
+// ---- probe visibility: the depth bake (rb_abi.h)
+// one piece, queued: probes [done, done + m) of the call into out[m], as hemi_piece's openness branch has it: the generator in
+// linear order, the k_query kernel of the scene's walk over the records, the fold of the hits into the probes' maps
+int depth_piece(rb_engine* e, const rb::KParams& p, const rb_probe* probes, const uint32_t* ids, size_t done, size_t m, uint32_t first_sample,
+                uint32_t samples, float max_distance, rb_probe_depth* out, rb::LaunchInfo* li) {
+    rb::ProbeGenArgs g = probe_gen_args(probes, ids, e->q_rays.ptr, done, m, first_sample, samples);
+    g.linear = 1u;
+    if (const int st = timed_generator(e, [&] { return rb::launch_probe_rays(g, e->stream); })) return st;
+    rb::QueryArgs q{};
+    q.rays = e->q_rays.ptr;
+    q.n = static_cast<uint32_t>(m * samples);
+    q.hits = e->q_hits.ptr;
+    if (const int st = rb::launch_query(p, q, e->stream, li)) return st;
+    return timed_pair(e, e->ev_depth, e->depth_pieces, [&] {
+        return rb::launch_depth_project(e->q_rays.ptr, e->q_hits.ptr, static_cast<uint32_t>(m), samples, max_distance, out, 0u, e->stream);
+    });
+}
+
+// (probe, sample) items per piece: RB_DEPTH_PIECE_ITEMS in the environment (tests: a piece boundary at a few probes), else and
+// at the most rb::kQueryPiece -- the records and the hits are rb_cast_rays' scratch
+size_t depth_piece_items() {
+    const char* const s = std::getenv("RB_DEPTH_PIECE_ITEMS");
+    const unsigned long long v = s ? std::strtoull(s, nullptr, 10) : 0ull;
+    return v ? static_cast<size_t>(std::min<unsigned long long>(v, rb::kQueryPiece)) : rb::kQueryPiece;
+}
+
+int probe_depth_locked(rb_engine* e, bool device, const rb_probe* probes, const uint32_t* seeds, size_t n, uint32_t first_sample, uint32_t samples,
+                       float max_distance, rb_probe_depth* out) {
+    return run_family(e, device, "probe depth", depth_piece_items(), n, samples,
+                      {FAMILY_ARRAY(probes, e->probe_pos, 16, "d_probes"), FAMILY_ARRAY(seeds, e->rad_seeds, 4, "d_seeds")},
+                      FAMILY_ARRAY(out, e->depth_out, 16, "d_out"),
+                      [&](size_t piece) -> int {
+                          HIP_TRY(e, e->q_rays.reserve(piece * samples));
+                          HIP_TRY(e, e->q_hits.reserve(piece * samples));
+                          return RB_OK;
+                      },
+                      [&](const rb::KParams& p, const void* const* in, void* o, size_t done, size_t m, rb::LaunchInfo* li) {
+                          return depth_piece(e, p, static_cast<const rb_probe*>(in[0]), static_cast<const uint32_t*>(in[1]), done, m,
+                                             first_sample, samples, max_distance, static_cast<rb_probe_depth*>(o), li);
+                      });
+}
+
 // ---- refusals that several entry points share, each under the entry point's own name `who`; before a device is touched
 int ray_count_check(rb_engine* e, const char* who, size_t n) {
     if (n > 0x7FFFFFFFull - 63ull) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s takes at most 2^31 - 64 rays per call", who);
@@ -676,6 +718,51 @@ int light_points_device_locked(rb_engine* e, const rb_probe_grid& g, const rb_sh
     if (rc) return rc;
     return device_stream_locked(e, [&](rb::LaunchInfo* li) {
         return rb::launch_probe_light(rb::ProbeLightArgs{g, d_coeffs, d_points, d_out, static_cast<uint32_t>(m)}, 0u, e->stream, &li->kernel_name);
+    });
+}
+
+// ---- probe visibility: moments and the blend (rb_abi.h)
+// the refusals the forms of rb_probe_moments share; before a device is touched (e may be NULL: the engine-less form)
+int probe_moments_check(rb_engine* e, const char* who, const void* sums, size_t n, const void* out) {
+    if (n > 0x7FFFFFFFull - 63ull) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s takes at most 2^31 - 64 probes per call", who);
+    if (n > 0 && (!sums || !out)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "%s: sums / moments_out is NULL", who);
+    return RB_OK;
+}
+
+// ... and those of rb_light_points_visible: its own, then rb_light_points'
+int light_visible_check(rb_engine* e, const char* who, const rb_probe_grid* g, const void* coeffs, const void* moments, const void* points,
+                        size_t m, const rb_light_visibility* prm, const void* out) {
+    if (!prm) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "%s: params is NULL", who);
+    if (!std::isfinite(prm->normal_bias)) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: normal_bias is not finite", who);
+    if (!(prm->min_visibility >= 0.0f && prm->min_visibility <= 1.0f)) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: min_visibility must be 0 .. 1", who);
+    if ((prm->flags & ~static_cast<uint32_t>(RB_VIS_NO_WRAP | RB_VIS_NO_DEPTH)) != 0u) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: unknown flag bits 0x%x", who, prm->flags);
+    if (prm->_pad != 0u) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: _pad must be 0", who);
+    if (const int rc = light_points_check(e, who, g, coeffs, points, m, out)) return rc;
+    if (m > 0 && !moments && (prm->flags & RB_VIS_NO_DEPTH) == 0u) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "%s: moments is NULL without RB_VIS_NO_DEPTH", who);
+    return RB_OK;
+}
+
+int probe_moments_device_locked(rb_engine* e, const rb_probe_depth* d_sums, size_t n, rb_probe_depth* d_out, float* d_share) {
+    int rc = device_range(e, d_sums, n * sizeof(rb_probe_depth), 16, "d_sums");
+    if (!rc) rc = device_range(e, d_out, n * sizeof(rb_probe_depth), 16, "d_moments_out");
+    if (!rc && d_share) rc = device_range(e, d_share, n * sizeof(float), 4, "d_backface_share_out");
+    if (rc) return rc;
+    return device_stream_locked(e, [&](rb::LaunchInfo* li) {
+        li->kernel_name = "k_probe_moments";
+        return rb::launch_probe_moments(d_sums, static_cast<uint32_t>(n), d_out, d_share, e->stream);
+    });
+}
+
+int light_visible_device_locked(rb_engine* e, const rb_probe_grid& g, const rb_sh9* d_coeffs, const rb_probe_depth* d_moments,
+                                const rb_surfel* d_points, size_t m, const rb_light_visibility& prm, rb_lit* d_out) {
+    int rc = device_range(e, d_coeffs, grid_probes(g) * sizeof(rb_sh9), 16, "d_coeffs");
+    if (!rc && d_moments) rc = device_range(e, d_moments, grid_probes(g) * sizeof(rb_probe_depth), 16, "d_moments");
+    if (!rc) rc = device_range(e, d_points, m * sizeof(rb_surfel), 16, "d_points");
+    if (!rc) rc = device_range(e, d_out, m * sizeof(rb_lit), 16, "d_out");
+    if (rc) return rc;
+    return device_stream_locked(e, [&](rb::LaunchInfo* li) {
+        li->kernel_name = "k_probe_light_vis";
+        return rb::launch_probe_light_vis(rb::ProbeLightArgs{g, d_coeffs, d_points, d_out, static_cast<uint32_t>(m)}, d_moments, prm, e->stream);
     });
 }
 
@@ -863,6 +950,19 @@ int probes_entry(rb_engine* e, const char* who, bool device, const rb_probe* pro
             return probe_check(e, who, n, first_sample, samples);
         },
         [&](rb_engine* t) { return probes_locked(t, device, probes, seeds, n, first_sample, samples, out); });
+}
+
+// the two engine entry points of the depth bake
+int probe_depth_entry(rb_engine* e, const char* who, bool device, const rb_probe* probes, const uint32_t* seeds, size_t n, uint32_t first_sample,
+                      uint32_t samples, float max_distance, rb_probe_depth* out) {
+    return engine_entry(
+        e, n,
+        [&] {
+            if (n > 0 && (!probes || !out)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "%s: probes / out is NULL", who);
+            if (!std::isfinite(max_distance) || !(max_distance > 0.0f)) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: max_distance must be finite and greater than 0", who);
+            return probe_check(e, who, n, first_sample, samples);
+        },
+        [&](rb_engine* t) { return probe_depth_locked(t, device, probes, seeds, n, first_sample, samples, max_distance, out); });
 }
 
 // ---- lightmap texels made on the device (rb_abi.h)
@@ -1346,6 +1446,78 @@ int rb_light_points_device(rb_engine* e, const rb_probe_grid* grid, const rb_sh9
         [&](rb_engine* t) { return light_points_device_locked(t, *grid, d_coeffs, d_points, m, d_out); });
 }
 
+int rb_bake_probe_depth(rb_engine* e, const rb_probe* probes, const uint32_t* seeds, size_t n, uint32_t first_sample, uint32_t samples,
+                        float max_distance, rb_probe_depth* out) {
+    return probe_depth_entry(e, "rb_bake_probe_depth", false, probes, seeds, n, first_sample, samples, max_distance, out);
+}
+
+int rb_bake_probe_depth_device(rb_engine* e, const rb_probe* d_probes, const uint32_t* d_seeds, size_t n, uint32_t first_sample,
+                               uint32_t samples, float max_distance, rb_probe_depth* d_out) {
+    return probe_depth_entry(e, "rb_bake_probe_depth_device", true, d_probes, d_seeds, n, first_sample, samples, max_distance, d_out);
+}
+
+int rb_probe_moments(int32_t device, const rb_probe_depth* sums, size_t n, rb_probe_depth* moments_out, float* backface_share_out) {
+    if (const int rc = probe_moments_check(nullptr, "rb_probe_moments", sums, n, moments_out)) return rc;
+    if (n == 0) return RB_OK;
+    const size_t piece = std::min(n, size_t(1) << 18);   // 256 + 1 MiB of scratch at the most
+    rb::DevBuf<rb_probe_depth> d_maps;
+    rb::DevBuf<float> d_share;
+    DeviceScope s(device);
+    s.alloc(d_maps, piece);
+    if (backface_share_out) s.alloc(d_share, piece);
+    for (size_t done = 0; done < n && s.ok(); done += piece) {
+        const size_t m = std::min(piece, n - done);
+        s.upload(d_maps.ptr, sums + done, m * sizeof(rb_probe_depth));
+        s.run([&] { return rb::launch_probe_moments(d_maps.ptr, static_cast<uint32_t>(m), d_maps.ptr, backface_share_out ? d_share.ptr : nullptr, s.stream); });
+        s.download(moments_out + done, d_maps.ptr, m * sizeof(rb_probe_depth));
+        if (backface_share_out) s.download(backface_share_out + done, d_share.ptr, m * sizeof(float));
+        s.sync();   // the scratch is the next piece's
+    }
+    return s.finish("rb_probe_moments");
+}
+
+int rb_probe_moments_device(rb_engine* e, const rb_probe_depth* d_sums, size_t n, rb_probe_depth* d_moments_out, float* d_backface_share_out) {
+    return engine_entry(
+        e, n, [&] { return probe_moments_check(e, "rb_probe_moments_device", d_sums, n, d_moments_out); },
+        [&](rb_engine* t) { return probe_moments_device_locked(t, d_sums, n, d_moments_out, d_backface_share_out); });
+}
+
+int rb_light_points_visible(int32_t device, const rb_probe_grid* grid, const rb_sh9* coeffs, const rb_probe_depth* moments,
+                            const rb_surfel* points, size_t m, const rb_light_visibility* params, rb_lit* out) {
+    if (const int rc = light_visible_check(nullptr, "rb_light_points_visible", grid, coeffs, moments, points, m, params, out)) return rc;
+    if (m == 0) return RB_OK;
+    const size_t probes = grid_probes(*grid), piece = std::min(m, light_piece_points());
+    rb::DevBuf<rb_sh9> d_coeffs;
+    rb::DevBuf<rb_probe_depth> d_moments;
+    rb::DevBuf<rb_surfel> d_points;
+    rb::DevBuf<rb_lit> d_out;
+    DeviceScope s(device);
+    s.alloc(d_coeffs, probes);
+    if (moments) s.alloc(d_moments, probes);
+    s.alloc(d_points, piece);
+    s.alloc(d_out, piece);
+    s.upload(d_coeffs.ptr, coeffs, probes * sizeof(rb_sh9));   // once per call, like the maps
+    if (moments) s.upload(d_moments.ptr, moments, probes * sizeof(rb_probe_depth));
+    for (size_t done = 0; done < m && s.ok(); done += piece) {
+        const size_t k = std::min(piece, m - done);
+        s.upload(d_points.ptr, points + done, k * sizeof(rb_surfel));
+        s.run([&] {
+            return rb::launch_probe_light_vis(rb::ProbeLightArgs{*grid, d_coeffs.ptr, d_points.ptr, d_out.ptr, static_cast<uint32_t>(k)},
+                                              moments ? d_moments.ptr : nullptr, *params, s.stream);
+        });
+        s.download(out + done, d_out.ptr, k * sizeof(rb_lit));
+        s.sync();   // the scratch is the next piece's
+    }
+    return s.finish("rb_light_points_visible");
+}
+
+int rb_light_points_visible_device(rb_engine* e, const rb_probe_grid* grid, const rb_sh9* d_coeffs, const rb_probe_depth* d_moments,
+                                   const rb_surfel* d_points, size_t m, const rb_light_visibility* params, rb_lit* d_out) {
+    return engine_entry(
+        e, m, [&] { return light_visible_check(e, "rb_light_points_visible_device", grid, d_coeffs, d_moments, d_points, m, params, d_out); },
+        [&](rb_engine* t) { return light_visible_device_locked(t, *grid, d_coeffs, d_moments, d_points, m, *params, d_out); });
+}
+
 int rb_lightmap_surfels(int32_t device, const rb_gpu_triangle* tris, size_t n_tris, const float* uvs, size_t n_uv_floats,
                         const rb_lightmap_params* params, rb_surfel* surfels_out, uint32_t* owners_out) {
     if (!params || !surfels_out || (n_tris > 0 && !tris) || (n_uv_floats > 0 && !uvs))
@@ -1554,6 +1726,16 @@ int rb_last_probe_project_ms(rb_engine* e, float* ms) {
     if (t->sh_pieces == 0) return RB_OK;
     rb::set_device(t);
     return answered(e, t, pairs_ms(t, t->ev_sh, t->sh_pieces, ms));
+}
+
+int rb_last_probe_depth_project_ms(rb_engine* e, float* ms) {
+    if (!e || !ms) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    rb_engine* const t = rb::is_group(e) ? e->parts[0].get() : e;
+    *ms = 0.0f;
+    if (t->depth_pieces == 0) return RB_OK;
+    rb::set_device(t);
+    return answered(e, t, pairs_ms(t, t->ev_depth, t->depth_pieces, ms));
 }
 
 }  // extern "C"

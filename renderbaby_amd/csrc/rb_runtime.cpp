@@ -1108,6 +1108,7 @@ void rb_destroy(rb_engine* e) {
     for (hipEvent_t x : e->ev_pool) (void)hipEventDestroy(x);
     for (hipEvent_t x : e->ev_cam) (void)hipEventDestroy(x);
     for (hipEvent_t x : e->ev_sh) (void)hipEventDestroy(x);
+    for (hipEvent_t x : e->ev_depth) (void)hipEventDestroy(x);
     for (hipEvent_t x : e->ev_q)
         if (x) (void)hipEventDestroy(x);
     for (hipEvent_t x : e->ev_dn)

@@ -781,6 +781,105 @@ class Engine:
         self._device_call(self._lib.rb_light_points_device, g.ctypes.data, cp, pp, m, op)
         return res if tensors else res.cpu().numpy().view(abi.LIT).reshape(-1)
 
+    # ---- probe visibility: depth moments and the leak-free blend (rb_abi.h)
+    def bake_probe_depth(self, pos, samples, max_distance, first_sample=0, seeds=None, out=None):
+        """rb_bake_probe_depth: per probe an 8 x 8 octahedral map of the first-hit distances of ``bake_probes``' own rays (same
+        ``seeds``, ``first_sample`` and ``samples``: the same rays), clipped at ``max_distance`` -> abi.PROBE_DEPTH[n], texel
+        ty * 8 + tx = {sum r, sum r r, samples, back faces among them}; ``probe_moments`` turns the sums into what
+        ``light_points_visible`` reads.  A torch tensor on the engine's device for the positions, the seeds or ``out``
+        ((n, 256) float32) goes to rb_bake_probe_depth_device: an (n, 256) tensor comes back and nothing crosses to the host."""
+        samples, first_sample = _sample_range(samples, first_sample)
+        max_distance = float(max_distance)
+        if _is_tensor(pos) or _is_tensor(seeds) or _is_tensor(out):
+            import torch
+            if not _is_tensor(pos) or pos.dtype != torch.float32:
+                raise ValueError("pos: a float32 tensor is needed beside tensor seeds or out")
+            p3 = pos.reshape(-1, 3)
+            rec = torch.zeros((len(p3), 4), dtype=torch.float32, device=p3.device)
+            rec[:, 0:3] = p3
+            pp, n = self._device_tensor(rec, torch.float32, 4, "pos")
+            sp, ns = self._seed_tensor(seeds, n)
+            res = torch.empty((n, 256), dtype=torch.float32, device=rec.device) if out is None else out
+            op, no = self._device_tensor(res, torch.float32, 256, "out")
+            if ns != n or no != n:
+                raise ValueError("pos, seeds and out differ in length")
+            self._device_call(self._lib.rb_bake_probe_depth_device, pp, sp, n, first_sample, samples, max_distance, op)
+            return res
+        p3 = np.asarray(pos, dtype=np.float32).reshape(-1, 3)
+        n = len(p3)
+        rec = np.zeros(n, dtype=abi.PROBE)
+        rec["pos"] = p3
+        seeds = _seed_array(seeds, n, "pos")
+        res = _host_out(out, n, abi.PROBE_DEPTH, "abi.PROBE_DEPTH array of n elements")
+        self._check(self._lib.rb_bake_probe_depth(self._h, rec.ctypes.data if n else None, seeds.ctypes.data if (seeds is not None and n) else None,
+                                                  n, first_sample, samples, max_distance, res.ctypes.data if n else None))
+        return res
+
+    def probe_moments(self, sums, out=None):
+        """rb_probe_moments_device: abi.PROBE_DEPTH sums (``bake_probe_depth``'s result) -> (moments, back-face share per probe):
+        a texel with samples becomes {mean r, mean r r, 1, its back-face share}, one without all zero.  A numpy array in gives
+        (abi.PROBE_DEPTH[n], float32 (n,)) out.  An (n, 256) float32 tensor on the engine's device is read where it lies and
+        tensors come back: ``out`` if given -- it may be ``sums`` itself, the work is then in place -- or a new one."""
+        import torch
+        if _is_tensor(sums) or _is_tensor(out):
+            src = sums
+        else:
+            host = np.ascontiguousarray(sums, dtype=abi.PROBE_DEPTH).reshape(-1)
+            src = torch.from_numpy(host.view(np.float32).reshape(-1, 256).copy()).to(torch.device("cuda", self.query_device))
+        sp, n = self._device_tensor(src, torch.float32, 256, "sums")
+        res = torch.empty_like(src) if out is None else out
+        op, no = self._device_tensor(res, torch.float32, 256, "out")
+        if no != n:
+            raise ValueError("sums and out differ in length")
+        share = torch.empty((n,), dtype=torch.float32, device=src.device)
+        self._device_call(self._lib.rb_probe_moments_device, sp, n, op, share.data_ptr() if n else None)
+        if src is sums:
+            return res, share
+        return res.cpu().numpy().view(abi.PROBE_DEPTH).reshape(-1), share.cpu().numpy()
+
+    def light_points_visible(self, grid, coeffs, moments, points, normals=None, normal_bias=0.0, min_visibility=0.0, wrap=True, depth=True,
+                             out=None):
+        """rb_light_points_visible_device: ``light_points`` with every probe's weight times a wrapped cosine of the point's normal
+        towards the probe (``wrap``) and the Chebyshev bound of the point's distance -- the point moved ``normal_bias`` along
+        its normal first -- against the probe's depth moments (``depth``; ``moments``: ``probe_moments``' maps, abi.PROBE_DEPTH
+        [nx * ny * nz] or an (n, 256) float32 tensor; None with ``depth=False``), never below ``min_visibility``.  Everything
+        else, tensors included, as ``light_points``; with both weights off the result is ``light_points``' bit for bit."""
+        import torch
+        from .probes import visibility_params
+        g = np.ascontiguousarray(grid, dtype=abi.PROBE_GRID).reshape(1)
+        prm = np.array([visibility_params(normal_bias, min_visibility, wrap, depth)], dtype=abi.LIGHT_VISIBILITY)
+        tensors = _is_tensor(coeffs) or _is_tensor(moments) or _is_tensor(points) or _is_tensor(normals) or _is_tensor(out)
+        dev = torch.device("cuda", self.query_device)
+        if normals is None:
+            surf = points if _is_tensor(points) else np.ascontiguousarray(points, dtype=abi.SURFEL).reshape(-1)
+        else:
+            surf = self._ray_records(points, normals)
+        if not _is_tensor(surf):
+            surf = torch.from_numpy(surf.view(np.float32).reshape(-1, 8)).to(dev)
+        if not _is_tensor(coeffs):
+            host = np.ascontiguousarray(coeffs, dtype=abi.SH9).reshape(-1)
+            coeffs = torch.from_numpy(host.view(np.float32).reshape(-1, 28)).to(dev)
+        if moments is not None and not _is_tensor(moments):
+            host = np.ascontiguousarray(moments, dtype=abi.PROBE_DEPTH).reshape(-1)
+            moments = torch.from_numpy(host.view(np.float32).reshape(-1, 256)).to(dev)
+        cp, nc = self._device_tensor(coeffs, torch.float32, 28, "coeffs")
+        mp, nm = self._device_tensor(moments, torch.float32, 256, "moments") if moments is not None else (None, nc)
+        pp, m = self._device_tensor(surf, torch.float32, 8, "points")
+        res = torch.empty((m, 4), dtype=torch.float32, device=dev) if out is None else out
+        op, no = self._device_tensor(res, torch.float32, 4, "out")
+        if no != m:
+            raise ValueError("points and out differ in length")
+        if nc != int(np.prod(g["counts"][0].astype(np.uint64))) or nm != nc:
+            raise ValueError("coeffs and moments: nx * ny * nz records each are needed")
+        self._device_call(self._lib.rb_light_points_visible_device, g.ctypes.data, cp, mp, pp, m, prm.ctypes.data, op)
+        return res if tensors else res.cpu().numpy().view(abi.LIT).reshape(-1)
+
+    def last_probe_depth_project_ms(self):
+        """kernel ms of the projection (k_depth_project) in the most recent bake_probe_depth: its share of last_query_ms()"""
+        ms = C.c_float()
+        self._check(self._lib.rb_last_probe_depth_project_ms(self._h, C.byref(ms)))
+        return ms.value
+
     def last_probe_project_ms(self):
         """kernel ms of the projection (k_sh_project) in the most recent bake_probes: its share of last_query_ms()"""
         ms = C.c_float()
@@ -1053,6 +1152,41 @@ def light_points(grid, coeffs, points, normals=None, device=-1):
     lib = load()
     rc = lib.rb_light_points(int(device), g.ctypes.data, coeffs.ctypes.data if len(coeffs) else None, surf.ctypes.data if m else None, m,
                              out.ctypes.data if m else None)
+    if rc != abi.RB_OK:
+        raise RenderError(rc, (lib.rb_last_error(None) or b"").decode())
+    return out
+
+
+def probe_moments(sums, device=-1):
+    """rb_probe_moments, no engine -- abi.PROBE_DEPTH[n] sums -> (abi.PROBE_DEPTH[n] moments, float32 (n,) back-face shares).
+    ``probes.moments`` is its numpy model."""
+    sums = np.ascontiguousarray(sums, dtype=abi.PROBE_DEPTH).reshape(-1)
+    n = len(sums)
+    out, share = np.zeros(n, dtype=abi.PROBE_DEPTH), np.zeros(n, dtype=np.float32)
+    lib = load()
+    rc = lib.rb_probe_moments(int(device), sums.ctypes.data if n else None, n, out.ctypes.data if n else None, share.ctypes.data if n else None)
+    if rc != abi.RB_OK:
+        raise RenderError(rc, (lib.rb_last_error(None) or b"").decode())
+    return out, share
+
+
+def light_points_visible(grid, coeffs, moments, points, normals=None, normal_bias=0.0, min_visibility=0.0, wrap=True, depth=True, device=-1):
+    """rb_light_points_visible, no engine -- abi.LIT[m] as ``light_points`` with the visibility weights of
+    ``Engine.light_points_visible``.  ``probes.light_visible`` is its numpy model."""
+    from .probes import visibility_params
+    g = np.ascontiguousarray(grid, dtype=abi.PROBE_GRID).reshape(1)
+    prm = np.array([visibility_params(normal_bias, min_visibility, wrap, depth)], dtype=abi.LIGHT_VISIBILITY)
+    coeffs = np.ascontiguousarray(coeffs, dtype=abi.SH9).reshape(-1)
+    maps = None if moments is None else np.ascontiguousarray(moments, dtype=abi.PROBE_DEPTH).reshape(-1)
+    surf = np.ascontiguousarray(points, dtype=abi.SURFEL).reshape(-1) if normals is None else Engine._ray_records(points, normals)
+    if len(coeffs) != int(np.prod(g["counts"][0].astype(np.uint64))) or (maps is not None and len(maps) != len(coeffs)):
+        raise ValueError("coeffs and moments: nx * ny * nz records each are needed")
+    m = len(surf)
+    out = np.zeros(m, dtype=abi.LIT)
+    lib = load()
+    rc = lib.rb_light_points_visible(int(device), g.ctypes.data, coeffs.ctypes.data if len(coeffs) else None,
+                                     maps.ctypes.data if maps is not None and len(maps) else None, surf.ctypes.data if m else None, m,
+                                     prm.ctypes.data, out.ctypes.data if m else None)
     if rc != abi.RB_OK:
         raise RenderError(rc, (lib.rb_last_error(None) or b"").decode())
     return out

@@ -12,6 +12,15 @@ operations in the same order, so ``rays`` equals ``rb_probe_rays``, ``project`` 
 ``light``    abi.LIT[m]: the blend of the eight probes of a regular grid round each point, for the point's normal
 ``grid_params``  the abi.PROBE_GRID whose probes are ``grid``'s positions
 
+Probe visibility (k_depth_project, k_probe_moments, csrc/rb_probe_depth.hip; k_probe_light_vis, csrc/rb_probe_visibility.hip;
+section 20), bit for bit as well:
+
+``oct_texel``      the texel ty * 8 + tx of every vector in the 8 x 8 octahedral map
+``depth_project``  abi.PROBE_DEPTH[n]: per probe and texel the ordered sums {r, r r, 1, back face} over its samples' hits
+``moments``        sums -> (abi.PROBE_DEPTH[n] moments, the back-face share of every probe)
+``light_visible``  ``light`` with every corner's weight times the wrapped cosine and the Chebyshev bound of its map
+``oct_centres``    the unit directions through the 64 texel centres, for tests and plots
+
 Host-only conveniences in float64, not part of the bit contract:
 
 ``radiance_coefficients``  L_j = (4 pi / weight) sum[j], (n, 9, 3)
@@ -214,24 +223,26 @@ def _points(pos, normals):
     return pos, nrm, valid
 
 
-def light(grid, coeffs, pos, normals):
-    """abi.LIT[m] of (m, 3) points and normals from an abi.PROBE_GRID and its coefficient records (``coefficients``' output,
-    ``grid``'s order): section 19's stage 2, operation for operation.  ``value`` is the irradiance over pi; ``weight`` the
-    blend weight W that was left after invalid probes dropped out (0: nothing lit the point, or the point is invalid)."""
+def _blend(grid, coeffs, pos, normals, corner_weight):
+    """section 19's stage 2; ``corner_weight(tl, c, idx, pos, unit normals, i0)`` -> (m,) float32 extends a corner's weight
+    (section 20), None leaves it"""
     pos, nrm, valid = _points(pos, normals)
     co = _sh_floats(coeffs, "coeffs")
     i0, t, cnt = _cell(grid, pos)
     if len(co) != int(cnt[0] * cnt[1] * cnt[2]):
         raise ValueError("coeffs: nx * ny * nz records are needed")
     m = len(pos)
-    y = basis(_unit(nrm))
+    n = _unit(nrm)
+    y = basis(n)
     E, W = np.zeros((m, 3), f32), np.zeros(m, f32)
     with np.errstate(all="ignore"):
-        for idx, wg, exists in _corners(i0, t, cnt):
+        for c, (idx, wg, exists) in enumerate(_corners(i0, t, cnt)):
             if not exists:
                 continue
             rec = co[idx]
             w = (wg * rec[:, 27]).astype(f32)
+            if corner_weight is not None:   # (a corner with tl == 0 stays 0 or becomes NaN * 0: skipped either way ...
+                w = np.where(w == 0, w, corner_weight(w, c, idx, pos, n, i0)).astype(f32)   # ... so it is left as it is)
             e = np.zeros((m, 3), f32)
             for j in range(9):
                 e = (e + (rec[:, 3 * j:3 * j + 3] * y[:, j:j + 1]).astype(f32)).astype(f32)
@@ -244,6 +255,13 @@ def light(grid, coeffs, pos, normals):
     out["value"][lit] = np.where(q > 0, q, f32(0.0)).astype(f32)[lit]
     out["weight"][lit] = W[lit]
     return out
+
+
+def light(grid, coeffs, pos, normals):
+    """abi.LIT[m] of (m, 3) points and normals from an abi.PROBE_GRID and its coefficient records (``coefficients``' output,
+    ``grid``'s order): section 19's stage 2, operation for operation.  ``value`` is the irradiance over pi; ``weight`` the
+    blend weight W that was left after invalid probes dropped out (0: nothing lit the point, or the point is invalid)."""
+    return _blend(grid, coeffs, pos, normals, None)
 
 
 def blend64(grid, coeffs, pos, normals, corner_values=None):
@@ -277,3 +295,161 @@ def blend64(grid, coeffs, pos, normals, corner_values=None):
         W += np.where(take, w, 0.0)
     with np.errstate(all="ignore"):
         return E / W[:, None], W, S / W[:, None]
+
+
+# ---- probe visibility
+def _vec3(v):
+    return np.asarray(v, f32).reshape(-1, 3)
+
+
+def oct_texel(v):
+    """(m,) int64 texels ty * 8 + tx of (m, 3) vectors of any length: s = (|x| + |y|) + |z|, p = (x, y) / s, the lower half
+    (z < 0; -0 is not) folded over the diagonals, t = min(uint(floor((p 0.5 + 0.5) 8)), 7).  The zero vector and non-finite
+    vectors have no texel by the definition; here they get texel 0."""
+    v = _vec3(v)
+    with np.errstate(all="ignore"):
+        a = np.abs(v)
+        s = ((a[:, 0] + a[:, 1]).astype(f32) + a[:, 2]).astype(f32)
+        px, py = (v[:, 0] / s).astype(f32), (v[:, 1] / s).astype(f32)
+        one = f32(1.0)
+        fx = ((one - np.abs(py)).astype(f32) * np.where(px >= 0, one, -one).astype(f32)).astype(f32)
+        fy = ((one - np.abs(px)).astype(f32) * np.where(py >= 0, one, -one).astype(f32)).astype(f32)
+        low = v[:, 2] < 0
+        px, py = np.where(low, fx, px).astype(f32), np.where(low, fy, py).astype(f32)
+
+        def axis(p):
+            f = np.floor((((p * f32(0.5)).astype(f32) + f32(0.5)).astype(f32) * f32(8.0)).astype(f32))
+            return np.minimum(np.nan_to_num(f, nan=0.0, posinf=7.0, neginf=0.0).clip(0, 7).astype(np.int64), 7)
+        return axis(py) * 8 + axis(px)
+
+
+def oct_centres():
+    """(64, 3) float32 unit directions through the texel centres, texel T = ty * 8 + tx at row T: the inverse of the octahedral
+    map at p = ((tx + 0.5) / 4 - 1, (ty + 0.5) / 4 - 1).  Host float64, not part of the bit contract; ``oct_texel`` of row T
+    is T."""
+    t = (np.arange(8, dtype=f64) + 0.5) / 4.0 - 1.0
+    py, px = np.meshgrid(t, t, indexing="ij")
+    z = 1.0 - np.abs(px) - np.abs(py)
+    low = z < 0
+    x = np.where(low, (1.0 - np.abs(py)) * np.where(px >= 0, 1.0, -1.0), px)
+    y = np.where(low, (1.0 - np.abs(px)) * np.where(py >= 0, 1.0, -1.0), py)
+    d = np.stack([x.ravel(), y.ravel(), z.ravel()], axis=1)
+    return (d / np.sqrt((d * d).sum(1))[:, None]).astype(f32)
+
+
+def depth_project(dirs, hits, samples, max_distance):
+    """abi.PROBE_DEPTH[n] from the items' directions as their records store them ((n * samples, 3), probe-major as ``rays``
+    and rb_probe_rays return them) and their abi.HIT records (rb_cast_rays of those records): from all-zero bits in ascending
+    sample order, a sample with a zero direction or an invalid hit skipped, texel[oct_texel(d)] += {r, r r, 1, back} with
+    r = min(t, max_distance) and back = 1 where a triangle's or a sphere's normal looks along the ray, (n.x d.x + n.y d.y) +
+    n.z d.z > 0."""
+    samples = int(samples)
+    d = _vec3(dirs)
+    hits = np.asarray(hits, dtype=abi.HIT).reshape(-1)
+    if samples < 1 or len(d) % samples or len(hits) != len(d):
+        raise ValueError("dirs and hits: (n * samples, 3) and abi.HIT[n * samples] are needed")
+    n = len(d) // samples
+    md = f32(max_distance)
+    with np.errstate(all="ignore"):
+        T = oct_texel(d)
+        r = np.where(hits["t"] < md, hits["t"], md).astype(f32)
+        r2 = (r * r).astype(f32)
+        nr = hits["normal"].astype(f32)
+        dt = ((nr[:, 0] * d[:, 0] + nr[:, 1] * d[:, 1]).astype(f32) + nr[:, 2] * d[:, 2]).astype(f32)
+    surface = (hits["kind"] == abi.HIT_TRIANGLE) | (hits["kind"] == abi.HIT_SPHERE)
+    back = np.where(surface & (dt > 0), f32(1.0), f32(0.0)).astype(f32)
+    take = (d != 0).any(1) & (hits["kind"] != abi.HIT_INVALID)
+    acc = np.zeros((n, 64, 4), f32)
+    rows = np.arange(n)
+    T, take = T.reshape(n, samples), take.reshape(n, samples)
+    terms = np.stack([r, r2, np.ones_like(r), back], axis=1).reshape(n, samples, 4)
+    for k in range(samples):   # one sample of every probe at a time: a texel takes its samples in ascending order
+        i = rows[take[:, k]]
+        acc[i, T[i, k]] = (acc[i, T[i, k]] + terms[i, k]).astype(f32)
+    out = np.zeros(n, dtype=abi.PROBE_DEPTH)
+    out["texel"] = acc
+    return out
+
+
+def _depth_floats(maps, what):
+    a = np.asarray(maps)
+    a = a.view(f32) if a.dtype == abi.PROBE_DEPTH else np.asarray(a, f32)
+    if a.size % 256:
+        raise ValueError(f"{what}: abi.PROBE_DEPTH records or (n, 256) floats are needed")
+    return a.reshape(-1, 64, 4).copy()
+
+
+def moments(sums):
+    """(abi.PROBE_DEPTH[n] moments, (n,) float32 back-face shares) of abi.PROBE_DEPTH[n] sums: a texel whose count is finite
+    and > 0 becomes {sum_r / count, sum_r2 / count, 1, back / count}, any other all-zero bits; the share is B / C, 0 where
+    C == 0, B and C the sums of ``back`` and ``count`` over the texels in ascending order from +0."""
+    a = _depth_floats(sums, "sums")
+    cnt = a[:, :, 2]
+    with np.errstate(all="ignore"):
+        valid = (cnt > 0) & (cnt < np.inf)
+        q = (a / cnt[:, :, None]).astype(f32)
+        q[:, :, 2] = f32(1.0)
+        B, C = np.zeros(len(a), f32), np.zeros(len(a), f32)
+        for t in range(64):
+            B, C = (B + a[:, t, 3]).astype(f32), (C + a[:, t, 2]).astype(f32)
+        share = np.where(C == 0, f32(0.0), (B / C).astype(f32)).astype(f32)
+    out = np.zeros(len(a), dtype=abi.PROBE_DEPTH)
+    out["texel"] = np.where(valid[:, :, None], q, f32(0.0))
+    return out, share
+
+
+def visibility_params(normal_bias=0.0, min_visibility=0.0, wrap=True, depth=True):
+    """the abi.LIGHT_VISIBILITY scalar of these settings"""
+    p = np.zeros(1, dtype=abi.LIGHT_VISIBILITY)
+    p["normal_bias"], p["min_visibility"] = normal_bias, min_visibility
+    p["flags"] = (0 if wrap else abi.VIS_NO_WRAP) | (0 if depth else abi.VIS_NO_DEPTH)
+    return p[0]
+
+
+def _dot3(a, b):
+    return ((a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1]).astype(f32) + a[:, 2] * b[:, 2]).astype(f32)
+
+
+def light_visible(grid, coeffs, moment_maps, pos, normals, params):
+    """abi.LIT[m] as ``light``, every corner's weight tl extended to (tl * wb) * vis (section 20): wb = h h + 0.2 with
+    h = (cos + 1) 0.5 of the angle between the unit normal and the direction to the probe (1 at the probe itself; 1 under
+    VIS_NO_WRAP), vis = max(Chebyshev bound cubed, min_visibility) of the distance r from the probe to the point moved
+    ``normal_bias`` along its normal against the moments of texel oct_texel(point - probe) -- 1 where r is 0, the texel has no
+    sample or r is not beyond the mean, and under VIS_NO_DEPTH, where ``moment_maps`` may be None.  ``params``: an
+    abi.LIGHT_VISIBILITY scalar (``visibility_params``)."""
+    g = np.asarray(grid, dtype=abi.PROBE_GRID).reshape(())
+    prm = np.asarray(params, dtype=abi.LIGHT_VISIBILITY).reshape(())
+    org, step = g["origin"].astype(f32), g["step"].astype(f32)
+    flags, bias, floor = int(prm["flags"]), f32(prm["normal_bias"]), f32(prm["min_visibility"])
+    depth = not flags & abi.VIS_NO_DEPTH
+    mm = _depth_floats(moment_maps, "moments") if depth else None
+    one = f32(1.0)
+
+    def corner_weight(tl, c, idx, p, n, i0):
+        d = (c & 1, (c >> 1) & 1, c >> 2)
+        P = np.stack([(org[a] + ((i0[:, a] + d[a]).astype(f32) * step[a]).astype(f32)).astype(f32) for a in range(3)], axis=1)
+        wb = np.ones(len(p), f32)
+        if not flags & abi.VIS_NO_WRAP:
+            q = (P - p).astype(f32)
+            l = np.sqrt(_dot3(q, q), dtype=f32)
+            cw = np.where(l > 0, (_dot3(q, n) / l).astype(f32), one).astype(f32)
+            h = ((cw + one).astype(f32) * f32(0.5)).astype(f32)
+            wb = ((h * h).astype(f32) + f32(0.2)).astype(f32)
+        vis = np.ones(len(p), f32)
+        if depth:
+            v = ((p + (n * bias).astype(f32)).astype(f32) - P).astype(f32)
+            r = np.sqrt(_dot3(v, v), dtype=f32)
+            tex = mm[idx, oct_texel(v)]
+            mean, mean2 = tex[:, 0], tex[:, 1]
+            var = np.abs((mean2 - (mean * mean).astype(f32)).astype(f32))
+            dl = (r - mean).astype(f32)
+            den = (var + (dl * dl).astype(f32)).astype(f32)
+            ch = np.where(den > 0, (var / den).astype(f32), one).astype(f32)
+            open_ = (r == 0) | (tex[:, 2] == 0) | ~(r > mean)
+            vis = np.where(open_, one, ((ch * ch).astype(f32) * ch).astype(f32)).astype(f32)
+        vis = np.where(vis > floor, vis, floor).astype(f32)
+        return ((tl * wb).astype(f32) * vis).astype(f32)
+
+    if mm is not None and len(mm) != int(np.prod(g["counts"].astype(np.int64))):
+        raise ValueError("moments: nx * ny * nz maps are needed")
+    return _blend(grid, coeffs, pos, normals, corner_weight)

@@ -7,7 +7,7 @@
                                  [--camera equirect|ortho|thin-lens [--ortho-width W] [--aperture A --focus-distance F] [--jitter]]
                                  [--probe x,y,z [--probe-normal x,y,z]] [--device-rays]
                                  [--lightmap W H [--lightmap-mesh i] [--lightmap-flip]]
-                                 [--probe-grid NX NY NZ] [--lit-by-probes NX NY NZ]
+                                 [--probe-grid NX NY NZ] [--lit-by-probes NX NY NZ [--probe-visibility]]
 
 scene file -> scene_io.load_scene (the importer's and the Scene->RenderConfig adapter's rules) ->
 RenderConfig -> librenderbaby_hip.so -> Frame -> PNG.  With --every N the progressive iterator is used
@@ -32,6 +32,9 @@ rays per probe, traced and projected onto SH9 on the device; DESIGN.md section 1
 grid (bake.probe_grid, spp rays per probe) and lights the first hits of the pixel centres from it in one launch
 (aov.probe_lit -> Engine.light_points): out.probe_lit.png through aov.color_map shows what the grid holds --
 emission + albedo x the blended irradiance over pi, no shadows --, so a bake can be judged before anything consumes it.
+--probe-visibility bakes the probes' depth maps beside them and blends with the visibility weights (bake.probe_grid(visibility=
+True) -> Engine.bake_probe_depth, Engine.probe_moments; Engine.light_points_visible): probes inside geometry
+drop out and light no longer leaks through walls.
 """
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -62,6 +65,7 @@ ap.add_argument("--probe-grid", type=int, nargs=3, metavar=("NX", "NY", "NZ"), d
                 help="also bake a grid of irradiance probes over the scene's bounding box, as out.probes.npz")
 ap.add_argument("--lit-by-probes", type=int, nargs=3, metavar=("NX", "NY", "NZ"), default=None,
                 help="also light the first hits from a grid of probes baked over the scene's bounding box, as out.probe_lit.png")
+ap.add_argument("--probe-visibility", action="store_true", help="--lit-by-probes with the probes' depth maps and the leak-free blend (DESIGN.md section 20)")
 a = ap.parse_args()
 aovs = [n for n in a.aov.split(",") if n]
 for n in aovs:
@@ -179,10 +183,10 @@ if a.probe_grid:
 if a.lit_by_probes:
     lo, hi = scene_box("--lit-by-probes")
     spp = min(max(s.total_samples, 1), 65536)
-    grid, coeffs = bake.probe_grid(eng, lo, hi, a.lit_by_probes, spp)
+    grid, coeffs, *maps = bake.probe_grid(eng, lo, hi, a.lit_by_probes, spp, visibility=a.probe_visibility)
     hits, surf = eng.render_hits(surfaces=True)
     import numpy as np
-    rgb = aov.color_map(aov.probe_lit(eng, grid, coeffs, hits, surf))
+    rgb = aov.color_map(aov.probe_lit(eng, grid, coeffs, hits, surf, moments=maps[0] if maps else None))
     img = np.concatenate([rgb, np.full(rgb.shape[:2] + (1,), 255, np.uint8)], axis=-1)
     base, ext = os.path.splitext(a.png)
     scene_io.export_png(f"{base}.probe_lit{ext}", Frame(img.shape[1], img.shape[0], img))
