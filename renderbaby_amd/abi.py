@@ -119,6 +119,7 @@ ERR = {
     11: "UniformsNotInitialized", 12: "NoMoreFrames", 13: "InvalidBVH", 14: "UnsupportedDelete",
     15: "NullArgument", 16: "Device", 17: "NotInitialized", 18: "InvalidOptions"}
 RB_ERR_NO_MORE_FRAMES = 12
+RB_ERR_DEVICE = 16   # HIP runtime failure
 
 KERNEL_DEFAULT, KERNEL_PIXEL, KERNEL_QUEUE, KERNEL_STREAM = 0, 1, 2, 3
 FLAG_STATS = 1

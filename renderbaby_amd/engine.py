@@ -13,12 +13,15 @@ Everything that computes is in librenderbaby_hip.so; this file only marshals.
 """
 import ctypes as C
 from dataclasses import dataclass
+from functools import partial
 from typing import Any, List, Optional
 
 import numpy as np
 
 from . import abi
 from ._lib import load
+from ._marshal import (SEEDS, Form, device_new, device_tensor, download, grid_records, host_out, host_ptr, is_tensor, probe_records,
+                       ray_records, surfel_records, torch_device)
 
 
 class RenderError(RuntimeError):
@@ -110,7 +113,7 @@ class RenderConfig:
                 else:
                     a = np.ascontiguousarray(np.atleast_1d(ch.value), dtype=_DTYPES[f])
                     keep.append(a)
-                    fld.ptr = a.ctypes.data if a.size else None
+                    fld.ptr = host_ptr(a)
                     fld.count = a.size
             setattr(cfg, f, fld)
         return cfg, keep
@@ -167,11 +170,6 @@ class Frame:
             raise RenderError(0, f"Frame pixel size mismatch: expected {self.expected_size()} bytes, got {self.pixels.size}")
 
 
-def _is_tensor(x):
-    """a torch tensor?  (without importing torch for callers that never pass one)"""
-    return type(x).__module__.split(".")[0] == "torch" and hasattr(x, "data_ptr")
-
-
 def _sample_range(samples, first_sample):
     """(samples, first_sample) as the 32-bit unsigned numbers the ABI takes"""
     samples, first_sample = int(samples), int(first_sample)
@@ -180,22 +178,70 @@ def _sample_range(samples, first_sample):
     return samples, first_sample
 
 
-def _seed_array(seeds, n, what):
-    """the ``seeds`` of a host form of n items (`what`: what the items are called) as contiguous uint32, or None"""
-    if seeds is None:
-        return None
-    seeds = np.ascontiguousarray(seeds, dtype=np.uint32).reshape(-1)
-    if len(seeds) != n:
-        raise ValueError(f"{what} and seeds differ in length")
-    return seeds
+def _global_error():
+    """the library's message for a call without an engine (comm_*, the engine-less forms, a create that failed)"""
+    return (load().rb_last_error(None) or b"").decode()
 
 
-def _host_out(out, n, dtype, what):
-    """the result array of a host form: ``out``, which must be n contiguous `dtype` records (`what` says so), or a new one"""
-    res = np.empty(n, dtype=dtype) if out is None else out
-    if not isinstance(res, np.ndarray) or res.dtype != dtype or res.shape != (n,) or not res.flags.c_contiguous:
-        raise ValueError(f"out: a contiguous {what} is needed")
-    return res
+def _check_global(rc):
+    """raise the RenderError of a call without an engine that returned `rc`"""
+    if rc != abi.RB_OK:
+        raise RenderError(rc, _global_error())
+
+
+_HOST = Form(None)   # the form of the engine-less calls: host arrays only
+
+
+def _engineless(device):
+    """(form, call) of an engine-less form on `device`: call(name, *args) makes the library's call and raises its error"""
+    lib = load()
+    return _HOST, lambda name, *args: _check_global(getattr(lib, name)(int(device), *args))
+
+
+def _camera_region(cam, region):
+    """(abi.CAMERA_EX[1], first_pixel, n_pixels) of a camera and a ``region`` of its image, by default all of it"""
+    c = np.ascontiguousarray(cam, dtype=abi.CAMERA_EX).reshape(1)
+    first, n = (0, int(c["width"][0]) * int(c["height"][0])) if region is None else (int(region[0]), int(region[1]))
+    if first < 0 or n < 0:
+        raise ValueError("region: (first_pixel, n_pixels), both at least 0")
+    return c, first, n
+
+
+def _visibility(normal_bias, min_visibility, wrap, depth):
+    """abi.LIGHT_VISIBILITY[1] of light_points_visible's parameters"""
+    from .probes import visibility_params
+    return np.array([visibility_params(normal_bias, min_visibility, wrap, depth)], dtype=abi.LIGHT_VISIBILITY)
+
+
+def _probe_stage(f, call, name, dtype, what, src, out=None, share=False):
+    """a per-probe stage in the form `f`, made by `call` (Engine._staged or _engineless): the records `src` (`what` names the
+    argument) -> ``out``, and with ``share`` one float32 per probe beside it"""
+    if f.tensors and not is_tensor(src):
+        raise ValueError(f"{what}: a tensor is needed beside a tensor out")
+    src, sp = f.input(what, src, dtype)
+    n = len(src)
+    res, op = f.output("out", out, dtype, n)
+    if not share:
+        call(name, sp, n, op)
+        return f.result(res, dtype)
+    per_probe, pp = f.output("share", None, np.float32, n)
+    call(name, sp, n, op, pp)
+    return f.result(res, dtype), f.result(per_probe, np.float32)
+
+
+def _light_points(f, call, grid, coeffs, points, normals, out=None, moments=None, visibility=None):
+    """light_points, and with ``visibility`` (an abi.LIGHT_VISIBILITY[1]) light_points_visible, in the form `f`, made by `call`"""
+    g, cells = grid_records(grid)
+    coeffs, cp = f.input("coeffs", coeffs, abi.SH9, cells)
+    moments, mp = f.optional("moments", moments, abi.PROBE_DEPTH, cells)
+    surf, pp = f.input("points", surfel_records(points, normals), abi.SURFEL)
+    m = len(surf)
+    res, op = f.output("out", out, abi.LIT, m)
+    if visibility is None:
+        call("rb_light_points", g.ctypes.data, cp, pp, m, op)
+    else:
+        call("rb_light_points_visible", g.ctypes.data, cp, mp, pp, m, visibility.ctypes.data, op)
+    return f.result(res, abi.LIT)
 
 
 class Engine:
@@ -243,7 +289,7 @@ class Engine:
         if self.query_device < 0:
             cur = C.c_int(-1)
             if self._lib.hipGetDevice(C.byref(cur)) != 0 or cur.value < 0:
-                raise RenderError(16, "device=-1: hipGetDevice names no current device")
+                raise RenderError(abi.RB_ERR_DEVICE, "device=-1: hipGetDevice names no current device")
             self.query_device = cur.value
         if devices is not None:
             devs = (C.c_int32 * len(devices))(*[int(d) for d in devices])
@@ -251,9 +297,8 @@ class Engine:
         else:
             self._h = self._lib.rb_create_ex(C.byref(cfg), C.byref(opt))
         del keep
-        if not self._h:
-            msg = self._lib.rb_last_error(None)
-            raise RenderError(abi.ERR and 16, (msg or b"rb_create failed").decode())
+        if not self._h:   # no handle to ask: the device error code with the library's message
+            raise RenderError(abi.RB_ERR_DEVICE, _global_error() or "rb_create failed")
         self.shard_count = max(shard_count, 1)
         self.comm_rank = None   # set by comm_init_rank: rank 0 then receives whole frames
 
@@ -303,16 +348,12 @@ class Engine:
     @staticmethod
     def comm_available():
         """Raises unless this process can load RCCL (no communicator id is made: rb_comm_available)."""
-        rc = load().rb_comm_available()
-        if rc:
-            raise RenderError(rc, (load().rb_last_error(None) or b"").decode())
+        _check_global(load().rb_comm_available())
 
     @staticmethod
     def comm_unique_id() -> bytes:
         buf = (C.c_uint8 * abi.COMM_ID_BYTES)()
-        rc = load().rb_comm_unique_id(buf)
-        if rc:
-            raise RenderError(rc, (load().rb_last_error(None) or b"").decode())
+        _check_global(load().rb_comm_unique_id(buf))
         return bytes(buf)
 
     def comm_init_rank(self, comm_id: bytes, rank: int, nranks: int):
@@ -328,22 +369,13 @@ class Engine:
         return {"rccl_ranks": n.value, "rccl_rank": r.value, "gather_ms": ms.value}
 
     def render(self, rc: RenderConfig) -> Frame:
-        cfg, keep = rc.to_c()
-        self._check(self._lib.rb_update(self._h, C.byref(cfg)))
-        self._remember(rc)
-        del keep
-        w, h = self._frame_shape()
-        if self.comm_rank not in (None, 0):   # a non-root rank of a process group: its stripes go to rank 0
-            self._check(self._lib.rb_render(self._h, None))
-            return None
-        out = np.empty((h, w, 4), dtype=np.uint8)
-        self._check(self._lib.rb_render(self._h, out.ctypes.data))
-        return Frame(w, h, out)
+        self.update(rc)
+        return self.render_current()
 
     def render_current(self) -> Frame:
         """rb_render without an update: all passes of the scene the engine already holds."""
         w, h = self._frame_shape()
-        if self.comm_rank not in (None, 0):
+        if self.comm_rank not in (None, 0):   # a non-root rank of a process group: its stripes go to rank 0
             self._check(self._lib.rb_render(self._h, None))
             return None
         out = np.empty((h, w, 4), dtype=np.uint8)
@@ -411,59 +443,8 @@ class Engine:
     def last_kernel_name(self):
         return (self._lib.rb_last_kernel_name(self._h) or b"").decode()
 
-    # ---- closest-hit queries (rb_abi.h)
-    def cast_rays(self, origins, dirs, surfaces=False, hits_out=None, surfaces_out=None):
-        """rb_cast_rays: (n, 3) origins and directions (any length: the device normalises) -> abi.HIT[n], or
-        (abi.HIT[n], abi.SURFACE[n]) with ``surfaces``.  ``hits_out`` / ``surfaces_out``: arrays to fill instead of new
-        ones (page-locked ones are filled by DMA)."""
-        return self.cast_ray_records(self._ray_records(origins, dirs), surfaces, hits_out, surfaces_out)
-
-    @staticmethod
-    def _ray_records(origins, dirs):
-        """abi.RAY[n] from (n, 3) numpy origins and directions, or an (n, 8) float32 tensor from (n, 3) torch tensors"""
-        if _is_tensor(origins) or _is_tensor(dirs):
-            import torch
-            if not (_is_tensor(origins) and _is_tensor(dirs)) or origins.dtype != torch.float32 or dirs.dtype != torch.float32 \
-                    or origins.device != dirs.device:
-                raise ValueError("origins and dirs must both be float32 tensors on one device")
-            o, d = origins.reshape(-1, 3), dirs.reshape(-1, 3)
-            if len(o) != len(d):
-                raise ValueError("origins and dirs differ in length")
-            rays = torch.zeros((len(o), 8), dtype=torch.float32, device=o.device)
-            rays[:, 0:3], rays[:, 4:7] = o, d
-            return rays
-        o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
-        d = np.asarray(dirs, dtype=np.float32).reshape(-1, 3)
-        if len(o) != len(d):
-            raise ValueError("origins and dirs differ in length")
-        rays = np.zeros(len(o), dtype=abi.RAY)
-        rays["origin"], rays["dir"] = o, d
-        return rays
-
-    def _device_tensor(self, t, dtype, row, what):
-        """data_ptr() of a tensor the device forms may read or write: on the engine's device, contiguous, of `dtype`, rows of
-        `row` elements (None: one element per ray); anything else is a ValueError.  Returns (pointer, rows)."""
-        import torch
-        want = torch.device("cuda", self.query_device)
-        if not _is_tensor(t) or t.device != want:
-            raise ValueError(f"{what}: a torch tensor on {want} is needed (the engine's device)")
-        if t.dtype != dtype or not t.is_contiguous():
-            raise ValueError(f"{what}: a contiguous {dtype} tensor is needed")
-        if row is None:
-            if t.dim() != 1:
-                raise ValueError(f"{what}: one element per ray is needed")
-        elif t.dim() != 2 or t.shape[1] != row:
-            raise ValueError(f"{what}: shape (n, {row}) is needed")
-        return (t.data_ptr() if t.numel() else None), t.shape[0]
-
-    def _seed_tensor(self, seeds, n):
-        """(pointer, length) of the ``seeds`` of a device form of n items -- a tensor of 32-bit ids, signed or unsigned: the bits
-        are what counts --, (None, n) without seeds"""
-        if seeds is None:
-            return None, n
-        import torch
-        unsigned = _is_tensor(seeds) and seeds.dtype == getattr(torch, "uint32", None)
-        return self._device_tensor(seeds, torch.uint32 if unsigned else torch.int32, None, "seeds")
+    # ---- the queries (rb_abi.h): every array argument goes through _marshal.Form, every call through _query
+    _ray_records = staticmethod(ray_records)
 
     def _device_call(self, fn, *args):
         """a device form between torch's stream and the engine's: torch's queued work first, rb_sync after"""
@@ -472,28 +453,48 @@ class Engine:
         self._check(fn(self._h, *args))
         self._check(self._lib.rb_sync(self._h))
 
+    def _query(self, form, name, *args):
+        """the call of a query in the form `form`: the entry point `name`, or ``name_device`` as _device_call makes it"""
+        if form.on_device:
+            self._device_call(getattr(self._lib, name + "_device"), *args)
+        else:
+            self._check(getattr(self._lib, name)(self._h, *args))
+
+    def _staged(self, *arrays):
+        """(form, call) of a query over `arrays` that has a device form only (_marshal.Form's ``staged``)"""
+        f = Form(self.query_device, *arrays, staged=True)
+        return f, partial(self._query, f)
+
+    def _last_ms(self, fn, count=1):
+        """the `count` float32 milliseconds the getter `fn` reports: one as a float, several as a tuple"""
+        ms = [C.c_float() for _ in range(count)]
+        self._check(fn(self._h, *[C.byref(m) for m in ms]))
+        return ms[0].value if count == 1 else tuple(m.value for m in ms)
+
+    def _builder(self, fn):
+        """(name, build milliseconds) as the getter `fn` reports them"""
+        ms = C.c_float()
+        name = (fn(self._h, C.byref(ms)) or b"").decode()
+        return name, ms.value
+
+    # ---- closest-hit queries (rb_abi.h; DESIGN.md section 11)
+    def cast_rays(self, origins, dirs, surfaces=False, hits_out=None, surfaces_out=None):
+        """rb_cast_rays: (n, 3) origins and directions (any length: the device normalises) -> abi.HIT[n], or
+        (abi.HIT[n], abi.SURFACE[n]) with ``surfaces``.  ``hits_out`` / ``surfaces_out``: arrays to fill instead of new
+        ones (page-locked ones are filled by DMA): contiguous abi.HIT[n] / abi.SURFACE[n], anything else is a ValueError."""
+        return self.cast_ray_records(ray_records(origins, dirs), surfaces, hits_out, surfaces_out)
+
     def cast_ray_records(self, rays, surfaces=False, hits_out=None, surfaces_out=None):
         """rb_cast_rays on an abi.RAY array as it stands (no copy when it is contiguous).  A float32 tensor of shape (n, 8) on
         the engine's device goes to rb_cast_rays_device instead: the records come back as float32 tensors of shape (n, 12) on
-        the device (``.cpu().numpy().view(abi.HIT)`` names their fields), and nothing crosses to the host."""
-        if _is_tensor(rays) or _is_tensor(hits_out) or _is_tensor(surfaces_out):
-            import torch
-            rp, n = self._device_tensor(rays, torch.float32, 8, "rays")
-            hits = torch.empty((n, 12), dtype=torch.float32, device=rays.device) if hits_out is None else hits_out
-            want_surf = surfaces or surfaces_out is not None
-            surf = (torch.empty((n, 12), dtype=torch.float32, device=rays.device) if surfaces_out is None else surfaces_out) if want_surf else None
-            hp, nh = self._device_tensor(hits, torch.float32, 12, "hits_out")
-            sp, ns = self._device_tensor(surf, torch.float32, 12, "surfaces_out") if want_surf else (None, n)
-            if nh != n or ns != n:
-                raise ValueError("rays, hits_out and surfaces_out differ in length")
-            self._device_call(self._lib.rb_cast_rays_device, rp, n, hp, sp)
-            return hits if surf is None else (hits, surf)
-        rays = np.ascontiguousarray(rays, dtype=abi.RAY)
+        the device (``.cpu().numpy().view(abi.HIT)`` names their fields), and nothing crosses to the host.  A ``hits_out`` or
+        ``surfaces_out`` that is not n contiguous records of its dtype is a ValueError in either form."""
+        f = Form(self.query_device, rays, hits_out, surfaces_out)
+        rays, rp = f.input("rays", rays, abi.RAY, flat=False)
         n = len(rays)
-        hits = np.empty(n, dtype=abi.HIT) if hits_out is None else hits_out
-        surf = (np.empty(n, dtype=abi.SURFACE) if surfaces_out is None else surfaces_out) if (surfaces or surfaces_out is not None) else None
-        self._check(self._lib.rb_cast_rays(self._h, rays.ctypes.data if n else None, n, hits.ctypes.data if n else None,
-                                           surf.ctypes.data if (surf is not None and n) else None))
+        hits, hp = f.output("hits_out", hits_out, abi.HIT, n)
+        surf, sp = f.output("surfaces_out", surfaces_out, abi.SURFACE, n) if (surfaces or surfaces_out is not None) else (None, None)
+        self._query(f, "rb_cast_rays", rp, n, hp, sp)
         return hits if surf is None else (hits, surf)
 
     # ---- any-hit occlusion (rb_abi.h; DESIGN.md section 12)
@@ -501,31 +502,16 @@ class Engine:
         """rb_occluded: is anything within (0.001, tmax) along each ray, among the stages of ``mask``?  (n, 3) origins and
         directions (any length: the device normalises), ``tmax`` n float32 or None (no bound) -> uint8[n] of abi.OCCL_*.
         Torch tensors on the engine's device go to rb_occluded_device and a uint8 tensor on the device comes back."""
-        return self.occluded_records(self._ray_records(origins, dirs), tmax, mask, out)
+        return self.occluded_records(ray_records(origins, dirs), tmax, mask, out)
 
     def occluded_records(self, rays, tmax=None, mask=abi.MASK_ALL, out=None):
         """rb_occluded on an abi.RAY array, or rb_occluded_device on a float32 tensor of shape (n, 8)."""
-        if _is_tensor(rays) or _is_tensor(tmax) or _is_tensor(out):
-            import torch
-            rp, n = self._device_tensor(rays, torch.float32, 8, "rays")
-            tp, nt = self._device_tensor(tmax, torch.float32, None, "tmax") if tmax is not None else (None, n)
-            res = torch.empty(n, dtype=torch.uint8, device=rays.device) if out is None else out
-            op, no = self._device_tensor(res, torch.uint8, None, "out")
-            if nt != n or no != n:
-                raise ValueError("rays, tmax and out differ in length")
-            self._device_call(self._lib.rb_occluded_device, rp, tp, n, int(mask), op)
-            return res
-        rays = np.ascontiguousarray(rays, dtype=abi.RAY)
+        f = Form(self.query_device, rays, tmax, out)
+        rays, rp = f.input("rays", rays, abi.RAY, flat=False)
         n = len(rays)
-        if tmax is not None:
-            tmax = np.ascontiguousarray(tmax, dtype=np.float32).reshape(-1)
-            if len(tmax) != n:
-                raise ValueError("rays and tmax differ in length")
-        res = np.empty(n, dtype=np.uint8) if out is None else out
-        if res.dtype != np.uint8 or res.shape != (n,) or not res.flags.c_contiguous:
-            raise ValueError("out: a contiguous uint8 array of n elements is needed")
-        self._check(self._lib.rb_occluded(self._h, rays.ctypes.data if n else None, tmax.ctypes.data if (tmax is not None and n) else None,
-                                          n, int(mask), res.ctypes.data if n else None))
+        tmax, tp = f.optional("tmax", tmax, np.float32, n)
+        res, op = f.output("out", out, np.uint8, n)
+        self._query(f, "rb_occluded", rp, tp, n, int(mask), op)
         return res
 
     # ---- path-traced radiance along given rays (rb_abi.h; DESIGN.md section 14)
@@ -534,30 +520,20 @@ class Engine:
         (n, 3) origins and directions (any length: the device normalises), ``seeds`` n uint32 ids or None (the ray's index)
         -> abi.RADIANCE[n] (``sum``, ``weight`` = samples; an invalid ray: zeros).  Torch tensors on the engine's device go
         to rb_trace_rays_device and an (n, 4) float32 tensor on the device comes back."""
-        return self.trace_ray_records(self._ray_records(origins, dirs), seeds, samples, first_sample, out)
+        return self.trace_ray_records(ray_records(origins, dirs), seeds, samples, first_sample, out)
 
     def trace_ray_records(self, rays, seeds=None, samples=1, first_sample=0, out=None):
         """rb_trace_rays on an abi.RAY array, or rb_trace_rays_device on a float32 tensor of shape (n, 8) (``seeds``: an int32
         or uint32 tensor of n elements, its bits are the ids; ``out``: a float32 tensor of shape (n, 4))."""
         samples, first_sample = _sample_range(samples, first_sample)
-        if _is_tensor(rays) or _is_tensor(seeds) or _is_tensor(out):
-            import torch
-            rp, n = self._device_tensor(rays, torch.float32, 8, "rays")
-            sp, ns = self._seed_tensor(seeds, n)
-            res = torch.empty((n, 4), dtype=torch.float32, device=rays.device) if out is None else out
-            op, no = self._device_tensor(res, torch.float32, 4, "out")
-            if ns != n or no != n:
-                raise ValueError("rays, seeds and out differ in length")
-            self._device_call(self._lib.rb_trace_rays_device, rp, sp, n, first_sample, samples, op)
-            return res
-        if not isinstance(rays, np.ndarray):
-            raise ValueError("rays: an abi.RAY array or a float32 tensor of shape (n, 8) is needed")
-        rays = np.ascontiguousarray(rays, dtype=abi.RAY)
+        f = Form(self.query_device, rays, seeds, out)
+        if not f.on_device and not isinstance(rays, np.ndarray):
+            raise ValueError("rays: an abi.RAY array, or a float32 tensor of ray records, is needed")
+        rays, rp = f.input("rays", rays, abi.RAY, flat=False)
         n = len(rays)
-        seeds = _seed_array(seeds, n, "rays")
-        res = _host_out(out, n, abi.RADIANCE, "abi.RADIANCE array of n elements")
-        self._check(self._lib.rb_trace_rays(self._h, rays.ctypes.data if n else None, seeds.ctypes.data if (seeds is not None and n) else None,
-                                            n, first_sample, samples, res.ctypes.data if n else None))
+        seeds, sp = f.optional("seeds", seeds, SEEDS, n)
+        res, op = f.output("out", out, abi.RADIANCE, n)
+        self._query(f, "rb_trace_rays", rp, sp, n, first_sample, samples, op)
         return res
 
     # ---- camera rays made on the device (rb_abi.h; DESIGN.md section 15)
@@ -567,20 +543,11 @@ class Engine:
         samples).  ``region``: (first_pixel, n_pixels) of the row-major image, by default all of it.  ``out``: an
         abi.RADIANCE array of n elements to fill, or a float32 tensor of shape (n, 4) on the engine's device, which selects
         rb_trace_camera_device (nothing crosses to the host)."""
-        c = np.ascontiguousarray(cam, dtype=abi.CAMERA_EX).reshape(1)
+        c, first, n = _camera_region(cam, region)
         samples, first_sample = _sample_range(samples, first_sample)
-        first, n = (0, int(c["width"][0]) * int(c["height"][0])) if region is None else (int(region[0]), int(region[1]))
-        if first < 0 or n < 0:
-            raise ValueError("region: (first_pixel, n_pixels), both at least 0")
-        if _is_tensor(out):
-            import torch
-            op, no = self._device_tensor(out, torch.float32, 4, "out")
-            if no != n:
-                raise ValueError("out and the region differ in length")
-            self._device_call(self._lib.rb_trace_camera_device, c.ctypes.data, first, n, first_sample, samples, op)
-            return out
-        res = _host_out(out, n, abi.RADIANCE, "abi.RADIANCE array of n elements")
-        self._check(self._lib.rb_trace_camera(self._h, c.ctypes.data, first, n, first_sample, samples, res.ctypes.data if n else None))
+        f = Form(self.query_device, out)
+        res, op = f.output("out", out, abi.RADIANCE, n)
+        self._query(f, "rb_trace_camera", c.ctypes.data, first, n, first_sample, samples, op)
         return res
 
     # ---- hemisphere rays made on the device (rb_abi.h; DESIGN.md section 16)
@@ -590,26 +557,16 @@ class Engine:
         prm["offset"], prm["radius"], prm["mask"] = offset, radius, int(mask)
         return prm
 
-    def _hemisphere(self, host_fn, device_fn, out_dtype, out_row, points, normals, samples, first_sample, seeds, prm, out):
-        """the two forms of a hemisphere query: surfels (abi.RAY's layout) from the points and normals, the call, the result"""
+    def _hemisphere(self, name, out_dtype, points, normals, samples, first_sample, seeds, prm, out):
+        """the two forms of a hemisphere query: surfels from the points and normals, the call, the result"""
         samples, first_sample = _sample_range(samples, first_sample)
-        surf = self._ray_records(points, normals)
-        if _is_tensor(surf) or _is_tensor(seeds) or _is_tensor(out):
-            import torch
-            fp, n = self._device_tensor(surf, torch.float32, 8, "points / normals")
-            sp, ns = self._seed_tensor(seeds, n)
-            t_dtype = torch.float32 if out_dtype is abi.RADIANCE else torch.int32
-            res = torch.empty((n, out_row), dtype=t_dtype, device=surf.device) if out is None else out
-            op, no = self._device_tensor(res, t_dtype, out_row, "out")
-            if ns != n or no != n:
-                raise ValueError("points, seeds and out differ in length")
-            self._device_call(device_fn, fp, sp, n, prm.ctypes.data, first_sample, samples, op)
-            return res
+        surf = surfel_records(points, normals)
+        f = Form(self.query_device, surf, seeds, out)
+        surf, fp = f.input("points / normals", surf, abi.SURFEL)
         n = len(surf)
-        seeds = _seed_array(seeds, n, "points")
-        res = _host_out(out, n, out_dtype, f"array of n {out_dtype} elements")
-        self._check(host_fn(self._h, surf.ctypes.data if n else None, seeds.ctypes.data if (seeds is not None and n) else None, n,
-                            prm.ctypes.data, first_sample, samples, res.ctypes.data if n else None))
+        seeds, sp = f.optional("seeds", seeds, SEEDS, n)
+        res, op = f.output("out", out, out_dtype, n)
+        self._query(f, name, fp, sp, n, prm.ctypes.data, first_sample, samples, op)
         return res
 
     def trace_hemisphere(self, points, normals, samples, first_sample=0, seeds=None, offset=1e-3, out=None):
@@ -618,16 +575,16 @@ class Engine:
         stream -> abi.RADIANCE[m] (``sum`` over the samples, ``weight``: the valid samples; sum / weight is the irradiance
         over pi).  ``seeds``: m uint32 ids or None (the point's index).  Torch tensors on the engine's device for the points
         and normals, or for ``out`` ((m, 4) float32), go to rb_trace_hemisphere_device: nothing crosses to the host."""
-        return self._hemisphere(self._lib.rb_trace_hemisphere, self._lib.rb_trace_hemisphere_device, abi.RADIANCE, 4, points, normals,
-                                samples, first_sample, seeds, self._hemi_params(offset), out)
+        return self._hemisphere("rb_trace_hemisphere", abi.RADIANCE, points, normals, samples, first_sample, seeds,
+                                self._hemi_params(offset), out)
 
     def openness(self, points, normals, samples, radius, mask=abi.MASK_ALL & ~abi.MASK_LIGHTS, first_sample=0, seeds=None, offset=1e-3,
                  out=None):
         """rb_openness_hemisphere: of ``samples`` cosine-weighted rays from each point, how many meet nothing of the stages of
         ``mask`` within ``radius`` (rb_occluded's tmax rules) -> abi.OPENNESS[m] (``open``, ``valid``; open / valid is the
         ambient-occlusion value).  Torch tensors select rb_openness_hemisphere_device and an (m, 2) int32 tensor comes back."""
-        return self._hemisphere(self._lib.rb_openness_hemisphere, self._lib.rb_openness_hemisphere_device, abi.OPENNESS, 2, points, normals,
-                                samples, first_sample, seeds, self._hemi_params(offset, radius, mask), out)
+        return self._hemisphere("rb_openness_hemisphere", abi.OPENNESS, points, normals, samples, first_sample, seeds,
+                                self._hemi_params(offset, radius, mask), out)
 
     # ---- lightmap texels made on the device (rb_abi.h; DESIGN.md section 17)
     @staticmethod
@@ -648,23 +605,16 @@ class Engine:
         ``flip``: the normals negated.  ``out`` = (surfels, owners) torch tensors on the engine's device, (n, 8) float32 and
         (n,) int32 or None: filled and returned, and nothing crosses to the host -- what trace_hemisphere and openness take
         as ``surfels[:, 0:3]``, ``surfels[:, 4:7]``.  Without ``out``: (abi.SURFEL[n], uint32 owners[n]) numpy arrays."""
-        import torch
         prm = self._lightmap_params(width, height, mesh, flip)
         n = int(width) * int(height)
-        dev = torch.device("cuda", self.query_device)
-        if out is None:
-            surf = torch.empty((n, 8), dtype=torch.float32, device=dev)
-            own = torch.empty((n,), dtype=torch.int32, device=dev)
-        else:
-            surf, own = out
-        sp, ns = self._device_tensor(surf, torch.float32, 8, "surfels")
-        op, no = self._device_tensor(own, torch.int32, None, "owners") if own is not None else (None, n)
-        if ns != n or no != n:
-            raise ValueError("surfels and owners need width * height rows")
+        dev = self.query_device
+        surf, own = (device_new(abi.SURFEL, n, dev), device_new(np.int32, n, dev)) if out is None else out
+        surf, sp = device_tensor("surfels", surf, abi.SURFEL, dev, n)
+        own, op = (None, None) if own is None else device_tensor("owners", own, np.int32, dev, n)
         self._device_call(self._lib.rb_lightmap_surfels_device, prm.ctypes.data, sp, op)
         if out is not None:
             return surf, own
-        return surf.cpu().numpy().view(abi.SURFEL).reshape(-1), own.cpu().numpy().view(np.uint32)
+        return download(surf, abi.SURFEL), download(own, np.uint32)
 
     def bake_lightmap(self, width, height, samples, first_sample=0, mesh=None, flip=False, offset=1e-3, dilate=2, out=None, sums=None):
         """rb_bake_lightmap: the lightmap of the uploaded scene's uvs in one call -- surfels, ``samples`` cosine-weighted rays
@@ -677,24 +627,28 @@ class Engine:
         samples, first_sample = _sample_range(samples, first_sample)
         prm = self._lightmap_params(width, height, mesh, flip, offset, dilate)
         n = int(width) * int(height)
-        if _is_tensor(out) or _is_tensor(sums):
-            import torch
-            op, no = self._device_tensor(out, torch.float32, 4, "out") if out is not None else (None, n)
-            sp, ns = self._device_tensor(sums, torch.float32, 4, "sums") if sums is not None else (None, n)
-            if no != n or ns != n:
-                raise ValueError("out and sums need width * height rows")
-            self._device_call(self._lib.rb_bake_lightmap_device, prm.ctypes.data, first_sample, samples, op, sp)
-            return out if out is not None else sums
-        res = np.empty((int(height), int(width), 4), dtype=np.float32) if out is None else out
-        if not isinstance(res, np.ndarray) or res.dtype != np.float32 or res.size != n * 4 or not res.flags.c_contiguous:
-            raise ValueError("out: a contiguous float32 array of height x width x 4 elements is needed")
-        if sums is not None and (not isinstance(sums, np.ndarray) or sums.dtype != abi.RADIANCE or sums.size != n or not sums.flags.c_contiguous):
-            raise ValueError("sums: a contiguous abi.RADIANCE array of height * width elements is needed")
-        self._check(self._lib.rb_bake_lightmap(self._h, prm.ctypes.data, first_sample, samples, res.ctypes.data if n else None,
-                                               sums.ctypes.data if (sums is not None and n) else None))
-        return res
+        f = Form(self.query_device, out, sums)
+        if f.on_device:   # rgba rows in abi.RADIANCE's layout, and none where ``out`` is None
+            res, op = (None, None) if out is None else f.output("out", out, abi.RADIANCE, n)
+        else:
+            res, op = host_out("out", out, np.float32, (int(height), int(width), 4), any_shape=True)
+        sums, sp = (None, None) if sums is None else f.output("sums", sums, abi.RADIANCE, n, any_shape=True)
+        self._query(f, "rb_bake_lightmap", prm.ctypes.data, first_sample, samples, op, sp)
+        return res if res is not None else sums
 
     # ---- irradiance probes made on the device (rb_abi.h)
+    def _bake_probes(self, name, out_dtype, pos, samples, first_sample, seeds, out, *params):
+        """the two forms of a bake over probes: probe records from the positions, the call -- `params` go between the sample
+        range and the result --, the result"""
+        samples, first_sample = _sample_range(samples, first_sample)
+        f = Form(self.query_device, pos, seeds, out)
+        rec, pp = f.input("pos", probe_records(pos), abi.PROBE)
+        n = len(rec)
+        seeds, sp = f.optional("seeds", seeds, SEEDS, n)
+        res, op = f.output("out", out, out_dtype, n)
+        self._query(f, name, pp, sp, n, first_sample, samples, *params, op)
+        return res
+
     def bake_probes(self, pos, samples, first_sample=0, seeds=None, out=None):
         """rb_bake_probes: the SH9 sums of the radiance arriving at (n, 3) points in free space from every direction,
         ``samples`` uniform-sphere rays per probe made on the device from the probe's own random stream -> abi.SH9[n] (``sum``
@@ -702,31 +656,7 @@ class Engine:
         ``probes.irradiance`` read them).  ``seeds``: n uint32 ids or None (the probe's index).  A torch tensor on the engine's
         device for the positions, the seeds or ``out`` ((n, 28) float32) goes to rb_bake_probes_device: an (n, 28) tensor comes
         back and nothing crosses to the host."""
-        samples, first_sample = _sample_range(samples, first_sample)
-        if _is_tensor(pos) or _is_tensor(seeds) or _is_tensor(out):
-            import torch
-            if not _is_tensor(pos) or pos.dtype != torch.float32:
-                raise ValueError("pos: a float32 tensor is needed beside tensor seeds or out")
-            p3 = pos.reshape(-1, 3)
-            rec = torch.zeros((len(p3), 4), dtype=torch.float32, device=p3.device)
-            rec[:, 0:3] = p3
-            pp, n = self._device_tensor(rec, torch.float32, 4, "pos")
-            sp, ns = self._seed_tensor(seeds, n)
-            res = torch.empty((n, 28), dtype=torch.float32, device=rec.device) if out is None else out
-            op, no = self._device_tensor(res, torch.float32, 28, "out")
-            if ns != n or no != n:
-                raise ValueError("pos, seeds and out differ in length")
-            self._device_call(self._lib.rb_bake_probes_device, pp, sp, n, first_sample, samples, op)
-            return res
-        p3 = np.asarray(pos, dtype=np.float32).reshape(-1, 3)
-        n = len(p3)
-        rec = np.zeros(n, dtype=abi.PROBE)
-        rec["pos"] = p3
-        seeds = _seed_array(seeds, n, "pos")
-        res = _host_out(out, n, abi.SH9, "abi.SH9 array of n elements")
-        self._check(self._lib.rb_bake_probes(self._h, rec.ctypes.data if n else None, seeds.ctypes.data if (seeds is not None and n) else None, n,
-                                             first_sample, samples, res.ctypes.data if n else None))
-        return res
+        return self._bake_probes("rb_bake_probes", abi.SH9, pos, samples, first_sample, seeds, out)
 
     # ---- light points from a baked probe grid (rb_abi.h; DESIGN.md section 19)
     def probe_coefficients(self, sh, out=None):
@@ -734,19 +664,7 @@ class Engine:
         layout, the weight 1 (a valid probe) or 0 (its record all zero) -- what ``light_points`` blends.  A numpy array in
         gives abi.SH9[n] out.  An (n, 28) float32 tensor on the engine's device is read where it lies and an (n, 28) tensor
         comes back: ``out`` if given -- it may be ``sh`` itself, the work is then in place -- or a new one."""
-        import torch
-        if _is_tensor(sh) or _is_tensor(out):
-            src = sh
-        else:
-            host = np.ascontiguousarray(sh, dtype=abi.SH9).reshape(-1)
-            src = torch.from_numpy(host.view(np.float32).reshape(-1, 28).copy()).to(torch.device("cuda", self.query_device))
-        sp, n = self._device_tensor(src, torch.float32, 28, "sh")
-        res = torch.empty_like(src) if out is None else out
-        op, no = self._device_tensor(res, torch.float32, 28, "out")
-        if no != n:
-            raise ValueError("sh and out differ in length")
-        self._device_call(self._lib.rb_probe_coefficients_device, sp, n, op)
-        return res if src is sh else res.cpu().numpy().view(abi.SH9).reshape(-1)
+        return _probe_stage(*self._staged(sh, out), "rb_probe_coefficients", abi.SH9, "sh", sh, out)
 
     def light_points(self, grid, coeffs, points, normals=None, out=None):
         """rb_light_points_device: the lit value of m points from a regular grid of baked probes -- ``grid``: an abi.PROBE_GRID
@@ -757,29 +675,7 @@ class Engine:
         lambert surface's radiance; ``weight``: the blend weight, 0 where nothing lit the point).  With a torch tensor on the
         engine's device for the coefficients ((n, 28) float32), the points or ``out`` ((m, 4) float32), every tensor is used
         where it lies, an (m, 4) tensor comes back and nothing crosses to the host."""
-        import torch
-        g = np.ascontiguousarray(grid, dtype=abi.PROBE_GRID).reshape(1)
-        tensors = _is_tensor(coeffs) or _is_tensor(points) or _is_tensor(normals) or _is_tensor(out)
-        dev = torch.device("cuda", self.query_device)
-        if normals is None:
-            surf = points if _is_tensor(points) else np.ascontiguousarray(points, dtype=abi.SURFEL).reshape(-1)
-        else:
-            surf = self._ray_records(points, normals)
-        if not _is_tensor(surf):
-            surf = torch.from_numpy(surf.view(np.float32).reshape(-1, 8)).to(dev)
-        if not _is_tensor(coeffs):
-            host = np.ascontiguousarray(coeffs, dtype=abi.SH9).reshape(-1)
-            coeffs = torch.from_numpy(host.view(np.float32).reshape(-1, 28)).to(dev)
-        cp, nc = self._device_tensor(coeffs, torch.float32, 28, "coeffs")
-        pp, m = self._device_tensor(surf, torch.float32, 8, "points")
-        res = torch.empty((m, 4), dtype=torch.float32, device=dev) if out is None else out
-        op, no = self._device_tensor(res, torch.float32, 4, "out")
-        if no != m:
-            raise ValueError("points and out differ in length")
-        if nc != int(np.prod(g["counts"][0].astype(np.uint64))):
-            raise ValueError("coeffs: nx * ny * nz records are needed")
-        self._device_call(self._lib.rb_light_points_device, g.ctypes.data, cp, pp, m, op)
-        return res if tensors else res.cpu().numpy().view(abi.LIT).reshape(-1)
+        return _light_points(*self._staged(coeffs, points, normals, out), grid, coeffs, points, normals, out)
 
     # ---- probe visibility: depth moments and the leak-free blend (rb_abi.h; DESIGN.md section 20)
     def bake_probe_depth(self, pos, samples, max_distance, first_sample=0, seeds=None, out=None):
@@ -788,54 +684,14 @@ class Engine:
         ty * 8 + tx = {sum r, sum r r, samples, back faces among them}; ``probe_moments`` turns the sums into what
         ``light_points_visible`` reads.  A torch tensor on the engine's device for the positions, the seeds or ``out``
         ((n, 256) float32) goes to rb_bake_probe_depth_device: an (n, 256) tensor comes back and nothing crosses to the host."""
-        samples, first_sample = _sample_range(samples, first_sample)
-        max_distance = float(max_distance)
-        if _is_tensor(pos) or _is_tensor(seeds) or _is_tensor(out):
-            import torch
-            if not _is_tensor(pos) or pos.dtype != torch.float32:
-                raise ValueError("pos: a float32 tensor is needed beside tensor seeds or out")
-            p3 = pos.reshape(-1, 3)
-            rec = torch.zeros((len(p3), 4), dtype=torch.float32, device=p3.device)
-            rec[:, 0:3] = p3
-            pp, n = self._device_tensor(rec, torch.float32, 4, "pos")
-            sp, ns = self._seed_tensor(seeds, n)
-            res = torch.empty((n, 256), dtype=torch.float32, device=rec.device) if out is None else out
-            op, no = self._device_tensor(res, torch.float32, 256, "out")
-            if ns != n or no != n:
-                raise ValueError("pos, seeds and out differ in length")
-            self._device_call(self._lib.rb_bake_probe_depth_device, pp, sp, n, first_sample, samples, max_distance, op)
-            return res
-        p3 = np.asarray(pos, dtype=np.float32).reshape(-1, 3)
-        n = len(p3)
-        rec = np.zeros(n, dtype=abi.PROBE)
-        rec["pos"] = p3
-        seeds = _seed_array(seeds, n, "pos")
-        res = _host_out(out, n, abi.PROBE_DEPTH, "abi.PROBE_DEPTH array of n elements")
-        self._check(self._lib.rb_bake_probe_depth(self._h, rec.ctypes.data if n else None, seeds.ctypes.data if (seeds is not None and n) else None,
-                                                  n, first_sample, samples, max_distance, res.ctypes.data if n else None))
-        return res
+        return self._bake_probes("rb_bake_probe_depth", abi.PROBE_DEPTH, pos, samples, first_sample, seeds, out, float(max_distance))
 
     def probe_moments(self, sums, out=None):
         """rb_probe_moments_device: abi.PROBE_DEPTH sums (``bake_probe_depth``'s result) -> (moments, back-face share per probe):
         a texel with samples becomes {mean r, mean r r, 1, its back-face share}, one without all zero.  A numpy array in gives
         (abi.PROBE_DEPTH[n], float32 (n,)) out.  An (n, 256) float32 tensor on the engine's device is read where it lies and
         tensors come back: ``out`` if given -- it may be ``sums`` itself, the work is then in place -- or a new one."""
-        import torch
-        if _is_tensor(sums) or _is_tensor(out):
-            src = sums
-        else:
-            host = np.ascontiguousarray(sums, dtype=abi.PROBE_DEPTH).reshape(-1)
-            src = torch.from_numpy(host.view(np.float32).reshape(-1, 256).copy()).to(torch.device("cuda", self.query_device))
-        sp, n = self._device_tensor(src, torch.float32, 256, "sums")
-        res = torch.empty_like(src) if out is None else out
-        op, no = self._device_tensor(res, torch.float32, 256, "out")
-        if no != n:
-            raise ValueError("sums and out differ in length")
-        share = torch.empty((n,), dtype=torch.float32, device=src.device)
-        self._device_call(self._lib.rb_probe_moments_device, sp, n, op, share.data_ptr() if n else None)
-        if src is sums:
-            return res, share
-        return res.cpu().numpy().view(abi.PROBE_DEPTH).reshape(-1), share.cpu().numpy()
+        return _probe_stage(*self._staged(sums, out), "rb_probe_moments", abi.PROBE_DEPTH, "sums", sums, out, share=True)
 
     def light_points_visible(self, grid, coeffs, moments, points, normals=None, normal_bias=0.0, min_visibility=0.0, wrap=True, depth=True,
                              out=None):
@@ -844,61 +700,26 @@ class Engine:
         its normal first -- against the probe's depth moments (``depth``; ``moments``: ``probe_moments``' maps, abi.PROBE_DEPTH
         [nx * ny * nz] or an (n, 256) float32 tensor; None with ``depth=False``), never below ``min_visibility``.  Everything
         else, tensors included, as ``light_points``; with both weights off the result is ``light_points``' bit for bit."""
-        import torch
-        from .probes import visibility_params
-        g = np.ascontiguousarray(grid, dtype=abi.PROBE_GRID).reshape(1)
-        prm = np.array([visibility_params(normal_bias, min_visibility, wrap, depth)], dtype=abi.LIGHT_VISIBILITY)
-        tensors = _is_tensor(coeffs) or _is_tensor(moments) or _is_tensor(points) or _is_tensor(normals) or _is_tensor(out)
-        dev = torch.device("cuda", self.query_device)
-        if normals is None:
-            surf = points if _is_tensor(points) else np.ascontiguousarray(points, dtype=abi.SURFEL).reshape(-1)
-        else:
-            surf = self._ray_records(points, normals)
-        if not _is_tensor(surf):
-            surf = torch.from_numpy(surf.view(np.float32).reshape(-1, 8)).to(dev)
-        if not _is_tensor(coeffs):
-            host = np.ascontiguousarray(coeffs, dtype=abi.SH9).reshape(-1)
-            coeffs = torch.from_numpy(host.view(np.float32).reshape(-1, 28)).to(dev)
-        if moments is not None and not _is_tensor(moments):
-            host = np.ascontiguousarray(moments, dtype=abi.PROBE_DEPTH).reshape(-1)
-            moments = torch.from_numpy(host.view(np.float32).reshape(-1, 256)).to(dev)
-        cp, nc = self._device_tensor(coeffs, torch.float32, 28, "coeffs")
-        mp, nm = self._device_tensor(moments, torch.float32, 256, "moments") if moments is not None else (None, nc)
-        pp, m = self._device_tensor(surf, torch.float32, 8, "points")
-        res = torch.empty((m, 4), dtype=torch.float32, device=dev) if out is None else out
-        op, no = self._device_tensor(res, torch.float32, 4, "out")
-        if no != m:
-            raise ValueError("points and out differ in length")
-        if nc != int(np.prod(g["counts"][0].astype(np.uint64))) or nm != nc:
-            raise ValueError("coeffs and moments: nx * ny * nz records each are needed")
-        self._device_call(self._lib.rb_light_points_visible_device, g.ctypes.data, cp, mp, pp, m, prm.ctypes.data, op)
-        return res if tensors else res.cpu().numpy().view(abi.LIT).reshape(-1)
+        return _light_points(*self._staged(coeffs, moments, points, normals, out), grid, coeffs, points, normals, out, moments,
+                             _visibility(normal_bias, min_visibility, wrap, depth))
 
     def last_probe_depth_project_ms(self):
         """kernel ms of the projection (k_depth_project) in the most recent bake_probe_depth: its share of last_query_ms()"""
-        ms = C.c_float()
-        self._check(self._lib.rb_last_probe_depth_project_ms(self._h, C.byref(ms)))
-        return ms.value
+        return self._last_ms(self._lib.rb_last_probe_depth_project_ms)
 
     def last_probe_project_ms(self):
         """kernel ms of the projection (k_sh_project) in the most recent bake_probes: its share of last_query_ms()"""
-        ms = C.c_float()
-        self._check(self._lib.rb_last_probe_project_ms(self._h, C.byref(ms)))
-        return ms.value
+        return self._last_ms(self._lib.rb_last_probe_project_ms)
 
     def last_lightmap_ms(self):
         """(surfels_ms, resolve_ms): kernel ms of the surfel stage and of the resolve in the most recent lightmap_surfels or
         bake_lightmap; both lie inside last_query_ms()"""
-        a, b = C.c_float(), C.c_float()
-        self._check(self._lib.rb_last_lightmap_ms(self._h, C.byref(a), C.byref(b)))
-        return a.value, b.value
+        return self._last_ms(self._lib.rb_last_lightmap_ms, 2)
 
     def last_camera_rays_ms(self):
         """kernel ms of the generator (k_cam_rays, k_hemi_rays, k_probe_rays) in the most recent trace_camera, trace_hemisphere, openness or bake_probes:
         its share of last_query_ms()"""
-        ms = C.c_float()
-        self._check(self._lib.rb_last_camera_rays_ms(self._h, C.byref(ms)))
-        return ms.value
+        return self._last_ms(self._lib.rb_last_camera_rays_ms)
 
     def render_hits(self, surfaces=False):
         """rb_render_hits: the first hit of every pixel centre as abi.HIT[rows, width] (and abi.SURFACE with ``surfaces``) in
@@ -908,7 +729,7 @@ class Engine:
             h = self.local_rows()[1]
         hits = np.empty((h, w), dtype=abi.HIT)
         surf = np.empty((h, w), dtype=abi.SURFACE) if surfaces else None
-        self._check(self._lib.rb_render_hits(self._h, hits.ctypes.data, surf.ctypes.data if surfaces else None))
+        self._check(self._lib.rb_render_hits(self._h, hits.ctypes.data, None if surf is None else surf.ctypes.data))
         return (hits, surf) if surfaces else hits
 
     def pick(self, px, py):
@@ -921,9 +742,7 @@ class Engine:
         return (self._lib.rb_last_query_kernel_name(self._h) or b"").decode()
 
     def last_query_ms(self):
-        ms = C.c_float()
-        self._check(self._lib.rb_last_query_ms(self._h, C.byref(ms)))
-        return ms.value
+        return self._last_ms(self._lib.rb_last_query_ms)
 
     # ---- the denoiser (rb_abi.h)
     def denoise(self, params=None, linear=False, out=None):
@@ -934,20 +753,18 @@ class Engine:
         (h, w, 4), contiguous): rb_denoise_device writes it there and nothing crosses to the host."""
         p = np.ascontiguousarray(denoise_defaults() if params is None else params, dtype=abi.DENOISE_PARAMS).reshape(1)
         w, h = self.size()
-        if _is_tensor(out):
+        if is_tensor(out):
             import torch
             dtype = torch.float32 if linear else torch.uint8
-            if out.device != torch.device("cuda", self.query_device) or out.dtype != dtype or not out.is_contiguous() \
+            if out.device != torch_device(self.query_device) or out.dtype != dtype or not out.is_contiguous() \
                     or tuple(out.shape) != (h, w, 4):
                 raise ValueError(f"out: a contiguous {dtype} tensor of shape ({h}, {w}, 4) on cuda:{self.query_device} is needed")
             ptr = out.data_ptr() if out.numel() else None
-            self._device_call(self._lib.rb_denoise_device, p.ctypes.data, None if linear else ptr, ptr if linear else None)
+            self._device_call(self._lib.rb_denoise_device, p.ctypes.data, *((None, ptr) if linear else (ptr, None)))
             return out
-        dtype = np.float32 if linear else np.uint8
-        res = np.empty((h, w, 4), dtype=dtype) if out is None else out
-        if res.dtype != dtype or res.shape != (h, w, 4) or not res.flags.c_contiguous:
-            raise ValueError(f"out: a contiguous {np.dtype(dtype)} array of shape ({h}, {w}, 4) is needed")
-        self._check(self._lib.rb_denoise(self._h, p.ctypes.data, None if linear else res.ctypes.data, res.ctypes.data if linear else None))
+        res, _ = host_out("out", out, np.float32 if linear else np.uint8, (h, w, 4))
+        ptr = res.ctypes.data
+        self._check(self._lib.rb_denoise(self._h, p.ctypes.data, *((None, ptr) if linear else (ptr, None))))
         return res
 
     def denoise_guides(self):
@@ -959,27 +776,19 @@ class Engine:
 
     def last_denoise_ms(self):
         """(kernel ms of the most recent denoise, ms of the guide build it had to make -- 0 when it had the guides)"""
-        ms, gms = C.c_float(), C.c_float()
-        self._check(self._lib.rb_last_denoise_ms(self._h, C.byref(ms), C.byref(gms)))
-        return ms.value, gms.value
+        return self._last_ms(self._lib.rb_last_denoise_ms, 2)
 
     def fast_bvh_builder(self):
         """("host-sah" | "device-lbvh" | "", build milliseconds) of the tree RB_FLAG_FAST_BVH walks."""
-        ms = C.c_float()
-        name = (self._lib.rb_fast_bvh_builder(self._h, C.byref(ms)) or b"").decode()
-        return name, ms.value
+        return self._builder(self._lib.rb_fast_bvh_builder)
 
     def sphere_tree_builder(self):
         """("device-median" | "host-median" | "", build milliseconds) of the library's sphere tree (> 64 spheres)."""
-        ms = C.c_float()
-        name = (self._lib.rb_sphere_tree_builder(self._h, C.byref(ms)) or b"").decode()
-        return name, ms.value
+        return self._builder(self._lib.rb_sphere_tree_builder)
 
     def chunk_tree_builder(self):
         """("device" | "host" | "", build milliseconds) of the chunked walk's tree (multi-node meshes, the default walk)."""
-        ms = C.c_float()
-        name = (self._lib.rb_chunk_tree_builder(self._h, C.byref(ms)) or b"").decode()
-        return name, ms.value
+        return self._builder(self._lib.rb_chunk_tree_builder)
 
     def tree(self):
         """(abi.BVH_NODE[], uint32[] indices) of the reference-layout tree the engine walks (rb_engine_tree): the caller's,
@@ -988,15 +797,12 @@ class Engine:
         self._check(self._lib.rb_engine_tree(self._h, None, 0, C.byref(nn), None, 0, C.byref(ni)))
         nodes = np.zeros(nn.value, dtype=abi.BVH_NODE)
         indices = np.zeros(ni.value, dtype=np.uint32)
-        self._check(self._lib.rb_engine_tree(self._h, nodes.ctypes.data if nn.value else None, len(nodes), C.byref(nn),
-                                             indices.ctypes.data if ni.value else None, len(indices), C.byref(ni)))
+        self._check(self._lib.rb_engine_tree(self._h, host_ptr(nodes), len(nodes), C.byref(nn), host_ptr(indices), len(indices), C.byref(ni)))
         return nodes, indices
 
     def tree_builder(self):
         """("device" | "host" | "caller" | "", build milliseconds) of the reference-layout tree the engine walks."""
-        ms = C.c_float()
-        name = (self._lib.rb_tree_builder(self._h, C.byref(ms)) or b"").decode()
-        return name, ms.value
+        return self._builder(self._lib.rb_tree_builder)
 
     def debug_chunk_tree(self):
         """The tree the engine walks, read back and checked (rb_debug_engine_chunk_tree): dict of its census, or None."""
@@ -1007,9 +813,7 @@ class Engine:
         return dict(nodes=out[1], positions=out[2], depth=out[3], chunks=out[4], unbounded=out[5])
 
     def last_dispatch_ms(self):
-        ms = C.c_float()
-        self._check(self._lib.rb_last_dispatch_ms(self._h, C.byref(ms)))
-        return ms.value
+        return self._last_ms(self._lib.rb_last_dispatch_ms)
 
 
 class FrameIterator:
@@ -1067,21 +871,26 @@ def device_name(device=-1):
     return buf.value.decode() if rc == 0 else "unknown"
 
 
+def _generated(items, samples):
+    """(abi.RAY[items * samples], uint32 seeds[items * samples]) for a generator to fill: of 0 items where it refuses the
+    samples (a refused call writes nothing)"""
+    if not 0 <= samples < 2 ** 32:
+        raise ValueError("samples: a 32-bit unsigned number")
+    n = items * samples if samples <= 65536 else 0
+    return np.zeros(n, dtype=abi.RAY), np.zeros(n, dtype=np.uint32)
+
+
 def camera_rays_device(cam, samples, first_sample=0, region=None, device=-1):
     """rb_camera_rays: the generator alone, no engine -- (abi.RAY[n * samples], uint32 seeds[n * samples]) of the pixels of
     ``region`` ((first_pixel, n_pixels); by default the whole image), item (pixel - first_pixel) * samples + k: the origin, the
     normalised direction (0 0 0: an invalid ray) and the seed trace_ray starts with.  ``camera.rays`` is its numpy model."""
-    c = np.ascontiguousarray(cam, dtype=abi.CAMERA_EX).reshape(1)
+    _, call = _engineless(device)
+    c, first, n = _camera_region(cam, region)
     samples = int(samples)
-    first, n = (0, int(c["width"][0]) * int(c["height"][0])) if region is None else (int(region[0]), int(region[1]))
-    if first < 0 or n < 0 or not 0 <= samples < 2 ** 32:
-        raise ValueError("region: (first_pixel, n_pixels), both at least 0; samples: a 32-bit unsigned number")
+    if not 0 <= samples < 2 ** 32:
+        raise ValueError("samples: a 32-bit unsigned number")
     rays, seeds = np.zeros(n * samples, dtype=abi.RAY), np.zeros(n * samples, dtype=np.uint32)
-    lib = load()
-    rc = lib.rb_camera_rays(int(device), c.ctypes.data, first, n, int(first_sample), samples, rays.ctypes.data if len(rays) else None,
-                            seeds.ctypes.data if len(rays) else None)
-    if rc != abi.RB_OK:
-        raise RenderError(rc, (lib.rb_last_error(None) or b"").decode())
+    call("rb_camera_rays", c.ctypes.data, first, n, int(first_sample), samples, host_ptr(rays), host_ptr(seeds))
     return rays, seeds
 
 
@@ -1089,19 +898,12 @@ def hemisphere_rays_device(points, normals, samples, first_sample=0, seeds=None,
     """rb_hemisphere_rays: the generator alone, no engine -- (abi.RAY[m * samples], uint32 seeds[m * samples]) of (m, 3)
     points and normals, item i * samples + k: the origin, the normalised direction (0 0 0: an invalid item) and the seed
     trace_ray starts with.  ``hemisphere.rays`` is its numpy model."""
-    surf = Engine._ray_records(np.asarray(points, np.float32), np.asarray(normals, np.float32))
-    m, samples = len(surf), int(samples)
-    if not 0 <= samples < 2 ** 32:
-        raise ValueError("samples: a 32-bit unsigned number")
-    seeds = _seed_array(seeds, m, "points")
+    f, call = _engineless(device)
+    surf, fp = f.input("points", surfel_records(np.asarray(points, np.float32), np.asarray(normals, np.float32)), abi.SURFEL)
+    rays, seeds_out = _generated(len(surf), int(samples))
+    seeds, sp = f.optional("seeds", seeds, SEEDS, len(surf))
     prm = Engine._hemi_params(offset)
-    items = m * samples if samples <= 65536 else 0   # (a refused call writes nothing)
-    rays, seeds_out = np.zeros(items, dtype=abi.RAY), np.zeros(items, dtype=np.uint32)
-    lib = load()
-    rc = lib.rb_hemisphere_rays(int(device), surf.ctypes.data if m else None, seeds.ctypes.data if (seeds is not None and m) else None, m,
-                                prm.ctypes.data, int(first_sample), samples, rays.ctypes.data, seeds_out.ctypes.data)
-    if rc != abi.RB_OK:
-        raise RenderError(rc, (lib.rb_last_error(None) or b"").decode())
+    call("rb_hemisphere_rays", fp, sp, len(surf), prm.ctypes.data, int(first_sample), int(samples), rays.ctypes.data, seeds_out.ctypes.data)
     return rays, seeds_out
 
 
@@ -1109,120 +911,64 @@ def probe_rays_device(pos, samples, first_sample=0, seeds=None, device=-1):
     """rb_probe_rays: the generator alone, no engine -- (abi.RAY[n * samples], uint32 seeds[n * samples]) of (n, 3) probe
     positions, item i * samples + k: the position, the normalised direction (0 0 0: an invalid item) and the seed trace_ray
     starts with.  ``probes.rays`` is its numpy model."""
-    p3 = np.asarray(pos, dtype=np.float32).reshape(-1, 3)
-    n, samples = len(p3), int(samples)
-    if not 0 <= samples < 2 ** 32:
-        raise ValueError("samples: a 32-bit unsigned number")
-    rec = np.zeros(n, dtype=abi.PROBE)
-    rec["pos"] = p3
-    seeds = _seed_array(seeds, n, "pos")
-    items = n * samples if samples <= 65536 else 0   # (a refused call writes nothing)
-    rays, seeds_out = np.zeros(items, dtype=abi.RAY), np.zeros(items, dtype=np.uint32)
-    lib = load()
-    rc = lib.rb_probe_rays(int(device), rec.ctypes.data if n else None, seeds.ctypes.data if (seeds is not None and n) else None, n,
-                           int(first_sample), samples, rays.ctypes.data, seeds_out.ctypes.data)
-    if rc != abi.RB_OK:
-        raise RenderError(rc, (lib.rb_last_error(None) or b"").decode())
+    f, call = _engineless(device)
+    rec, pp = f.input("pos", probe_records(np.asarray(pos, np.float32)), abi.PROBE)
+    rays, seeds_out = _generated(len(rec), int(samples))
+    seeds, sp = f.optional("seeds", seeds, SEEDS, len(rec))
+    call("rb_probe_rays", pp, sp, len(rec), int(first_sample), int(samples), rays.ctypes.data, seeds_out.ctypes.data)
     return rays, seeds_out
 
 
 def probe_coefficients(sh, device=-1):
     """rb_probe_coefficients: stage 1 alone, no engine -- abi.SH9[n] sums -> abi.SH9[n] coefficients.  ``probes.coefficients``
     is its numpy model."""
-    sh = np.ascontiguousarray(sh, dtype=abi.SH9).reshape(-1)
-    out = np.zeros(len(sh), dtype=abi.SH9)
-    lib = load()
-    rc = lib.rb_probe_coefficients(int(device), sh.ctypes.data if len(sh) else None, len(sh), out.ctypes.data if len(sh) else None)
-    if rc != abi.RB_OK:
-        raise RenderError(rc, (lib.rb_last_error(None) or b"").decode())
-    return out
+    return _probe_stage(*_engineless(device), "rb_probe_coefficients", abi.SH9, "sh", sh)
 
 
 def light_points(grid, coeffs, points, normals=None, device=-1):
     """rb_light_points: stage 2, no engine -- abi.LIT[m] of m points from an abi.PROBE_GRID scalar and its nx * ny * nz
     coefficient records; ``points`` and ``normals`` (m, 3) each, or ``points`` alone as abi.SURFEL[m].  ``probes.light`` is its
     numpy model."""
-    g = np.ascontiguousarray(grid, dtype=abi.PROBE_GRID).reshape(1)
-    coeffs = np.ascontiguousarray(coeffs, dtype=abi.SH9).reshape(-1)
-    surf = np.ascontiguousarray(points, dtype=abi.SURFEL).reshape(-1) if normals is None else Engine._ray_records(points, normals)
-    if len(coeffs) != int(np.prod(g["counts"][0].astype(np.uint64))):
-        raise ValueError("coeffs: nx * ny * nz records are needed")
-    m = len(surf)
-    out = np.zeros(m, dtype=abi.LIT)
-    lib = load()
-    rc = lib.rb_light_points(int(device), g.ctypes.data, coeffs.ctypes.data if len(coeffs) else None, surf.ctypes.data if m else None, m,
-                             out.ctypes.data if m else None)
-    if rc != abi.RB_OK:
-        raise RenderError(rc, (lib.rb_last_error(None) or b"").decode())
-    return out
+    return _light_points(*_engineless(device), grid, coeffs, points, normals)
 
 
 def probe_moments(sums, device=-1):
     """rb_probe_moments, no engine -- abi.PROBE_DEPTH[n] sums -> (abi.PROBE_DEPTH[n] moments, float32 (n,) back-face shares).
     ``probes.moments`` is its numpy model."""
-    sums = np.ascontiguousarray(sums, dtype=abi.PROBE_DEPTH).reshape(-1)
-    n = len(sums)
-    out, share = np.zeros(n, dtype=abi.PROBE_DEPTH), np.zeros(n, dtype=np.float32)
-    lib = load()
-    rc = lib.rb_probe_moments(int(device), sums.ctypes.data if n else None, n, out.ctypes.data if n else None, share.ctypes.data if n else None)
-    if rc != abi.RB_OK:
-        raise RenderError(rc, (lib.rb_last_error(None) or b"").decode())
-    return out, share
+    return _probe_stage(*_engineless(device), "rb_probe_moments", abi.PROBE_DEPTH, "sums", sums, share=True)
 
 
 def light_points_visible(grid, coeffs, moments, points, normals=None, normal_bias=0.0, min_visibility=0.0, wrap=True, depth=True, device=-1):
     """rb_light_points_visible, no engine -- abi.LIT[m] as ``light_points`` with the visibility weights of
     ``Engine.light_points_visible``.  ``probes.light_visible`` is its numpy model."""
-    from .probes import visibility_params
-    g = np.ascontiguousarray(grid, dtype=abi.PROBE_GRID).reshape(1)
-    prm = np.array([visibility_params(normal_bias, min_visibility, wrap, depth)], dtype=abi.LIGHT_VISIBILITY)
-    coeffs = np.ascontiguousarray(coeffs, dtype=abi.SH9).reshape(-1)
-    maps = None if moments is None else np.ascontiguousarray(moments, dtype=abi.PROBE_DEPTH).reshape(-1)
-    surf = np.ascontiguousarray(points, dtype=abi.SURFEL).reshape(-1) if normals is None else Engine._ray_records(points, normals)
-    if len(coeffs) != int(np.prod(g["counts"][0].astype(np.uint64))) or (maps is not None and len(maps) != len(coeffs)):
-        raise ValueError("coeffs and moments: nx * ny * nz records each are needed")
-    m = len(surf)
-    out = np.zeros(m, dtype=abi.LIT)
-    lib = load()
-    rc = lib.rb_light_points_visible(int(device), g.ctypes.data, coeffs.ctypes.data if len(coeffs) else None,
-                                     maps.ctypes.data if maps is not None and len(maps) else None, surf.ctypes.data if m else None, m,
-                                     prm.ctypes.data, out.ctypes.data if m else None)
-    if rc != abi.RB_OK:
-        raise RenderError(rc, (lib.rb_last_error(None) or b"").decode())
-    return out
+    return _light_points(*_engineless(device), grid, coeffs, points, normals, None, moments,
+                         _visibility(normal_bias, min_visibility, wrap, depth))
 
 
 def lightmap_surfels_device(tris, uvs, width, height, mesh=None, flip=False, device=-1):
     """rb_lightmap_surfels: the generator alone, no engine -- (abi.SURFEL[height * width], uint32 owners[height * width]) of
     abi.GPU_TRIANGLE triangles and their uv floats; every triangle counts as valid.  ``lightmap.surfels`` is its numpy model."""
-    tris = np.ascontiguousarray(tris, dtype=abi.GPU_TRIANGLE).reshape(-1)
-    uvs = np.ascontiguousarray(uvs, dtype=np.float32).reshape(-1)
+    f, call = _engineless(device)
+    tris, tp = f.input("tris", tris, abi.GPU_TRIANGLE)
+    uvs, up = f.input("uvs", uvs, np.float32)
     prm = Engine._lightmap_params(width, height, mesh, flip)
     n = int(width) * int(height) if (0 < int(width) <= abi.LIGHTMAP_MAX_SIDE and 0 < int(height) <= abi.LIGHTMAP_MAX_SIDE) else 0
     surf, own = np.zeros(n, dtype=abi.SURFEL), np.zeros(n, dtype=np.uint32)   # (a refused call writes nothing)
-    lib = load()
-    rc = lib.rb_lightmap_surfels(int(device), tris.ctypes.data if len(tris) else None, len(tris), uvs.ctypes.data if len(uvs) else None,
-                                 len(uvs), prm.ctypes.data, surf.ctypes.data, own.ctypes.data)
-    if rc != abi.RB_OK:
-        raise RenderError(rc, (lib.rb_last_error(None) or b"").decode())
+    call("rb_lightmap_surfels", tp, len(tris), up, len(uvs), prm.ctypes.data, surf.ctypes.data, own.ctypes.data)
     return surf, own
 
 
 def lightmap_resolve(sums, width, height, dilate=2, device=-1):
     """rb_lightmap_resolve: the resolve alone, no engine -- abi.RADIANCE[height * width] sums -> float32 (height, width, 4):
     sum / weight and ``dilate`` fill passes.  ``lightmap.resolve`` is its numpy model."""
-    sums = np.ascontiguousarray(sums, dtype=abi.RADIANCE).reshape(-1)
+    f, call = _engineless(device)
     width, height, dilate = int(width), int(height), int(dilate)
     for v in (width, height, dilate):
         if not 0 <= v < 2 ** 32:
             raise ValueError("width, height and dilate are 32-bit unsigned numbers")
-    if len(sums) != width * height:
-        raise ValueError("sums: width * height records are needed")
+    sums, _ = f.input("sums", sums, abi.RADIANCE, width * height)
     out = np.zeros((height, width, 4), dtype=np.float32)
-    lib = load()
-    rc = lib.rb_lightmap_resolve(int(device), width, height, sums.ctypes.data, dilate, out.ctypes.data)
-    if rc != abi.RB_OK:
-        raise RenderError(rc, (lib.rb_last_error(None) or b"").decode())
+    call("rb_lightmap_resolve", width, height, sums.ctypes.data, dilate, out.ctypes.data)
     return out
 
 
@@ -1247,8 +993,6 @@ def denoise_buffers(color, guides, params=None, device=-1):
     c4[..., :c.shape[2]] = c
     p = np.ascontiguousarray(denoise_defaults() if params is None else params, dtype=abi.DENOISE_PARAMS).reshape(1)
     lin, img = np.empty((h, w, 4), dtype=np.float32), np.empty((h, w, 4), dtype=np.uint8)
-    lib = load()
-    rc = lib.rb_denoise_buffers(int(device), p.ctypes.data, w, h, c4.ctypes.data, g.ctypes.data, lin.ctypes.data, img.ctypes.data)
-    if rc != abi.RB_OK:
-        raise RenderError(rc, (lib.rb_last_error(None) or b"").decode())
+    _, call = _engineless(device)
+    call("rb_denoise_buffers", p.ctypes.data, w, h, c4.ctypes.data, g.ctypes.data, lin.ctypes.data, img.ctypes.data)
     return lin, img

@@ -370,7 +370,9 @@ def test_device_forms_equal_the_host_forms():
             assert lib.rb_cast_rays_device(e._h, None, 0, None, None) == 0 and lib.rb_occluded_device(e._h, None, None, 0, 0, None) == 0
             for bad in (lambda: e.occluded(tO.double(), tD.double()), lambda: e.occluded(tO.cpu(), tD.cpu(), torch.ones(n)),
                         lambda: e.occluded_records(rays.t().contiguous().t()), lambda: e.occluded_records(rays, out=torch.empty(n, device=rays.device)),
-                        lambda: e.cast_ray_records(rays, hits_out=np.empty(n, dtype=abi.HIT))):
+                        lambda: e.cast_ray_records(rays, hits_out=np.empty(n, dtype=abi.HIT)),
+                        lambda: e.cast_ray_records(np.zeros(n, abi.RAY), hits_out=np.empty(n - 1, abi.HIT)),
+                        lambda: e.cast_ray_records(np.zeros(n, abi.RAY), hits_out=np.empty(n, abi.RADIANCE))):
                 with pytest.raises(ValueError):
                     bad()
         finally:
