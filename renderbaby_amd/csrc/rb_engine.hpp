@@ -131,6 +131,9 @@ struct rb_engine {
              n_tex = 0;
     // Change of the last update for the three patched counts (gpu_wrapper.rs:475-495)
     uint32_t last_change_spheres = RB_KEEP, last_change_nodes = RB_KEEP, last_change_tris = RB_KEEP;
+    // length of the spheres vector the last update carried: a Create after the first update is not acted on, but :476 still
+    // takes spheres_count from the vector it was handed (the BVH fields' Create is acted on: their vector is the buffer)
+    uint32_t last_spheres_sent = 0;
     bool prep_dirty = true;
     uint32_t prep_tri_count = 0xFFFFFFFFu;  // uniforms.bvh_triangle_count (patched) the prepared triangles were made for
 

@@ -402,7 +402,7 @@ int rb::ensure_prepared(rb_engine* e) {
 rb::KParams rb::make_params(rb_engine* e, uint32_t first_pass, uint32_t n_passes, int src, int dst) {
     rb::KParams p{};
     p.u = e->uniforms;
-    p.u.spheres_count = patch_count(e->last_change_spheres, e->uniforms.spheres_count, e->n_spheres);
+    p.u.spheres_count = patch_count(e->last_change_spheres, e->uniforms.spheres_count, std::min(e->n_spheres, e->last_spheres_sent));
     p.u.bvh_node_count = patch_count(e->last_change_nodes, e->uniforms.bvh_node_count, e->n_nodes);
     p.u.bvh_triangle_count = patch_count(e->last_change_tris, e->uniforms.bvh_triangle_count, e->n_tris);
     p.spheres = e->spheres.ptr;
@@ -733,6 +733,8 @@ int update_fields(rb_engine* e, const rb_config* cfg) {
         }
     }
     e->last_change_spheres = cfg->spheres.change;
+    // the vector's length where it was acted on is the buffer's; where a Create was ignored it is the count all the same (:476)
+    e->last_spheres_sent = has_data(cfg->spheres) ? static_cast<uint32_t>(std::min<size_t>(cfg->spheres.count, 0xFFFFFFFFu)) : 0xFFFFFFFFu;
     e->last_change_nodes = rb::builds_tree(e) ? cfg->bvh_triangles.change : cfg->bvh_nodes.change;
     e->last_change_tris = cfg->bvh_triangles.change;
     e->bvh_stack = plan.bvh_stack;
