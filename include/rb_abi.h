@@ -506,6 +506,16 @@ int rb_debug_rcp_exhaustive(uint32_t biased_exponent, uint32_t* out16);
  * all 2^23 significands and both signs at one biased exponent (0..255) against 1.0f / x, bit patterns compared, a NaN equal to
  * a NaN; out16[0] = mismatch count, out16[1..15] = some offending bit patterns. */
 int rb_debug_rcp_det_exhaustive(uint32_t biased_exponent, uint32_t* out16);
+/* Test hook: the hand-laid triangle trip of the single-node trace kernels against the compiler-laid form of the same test on
+ * `n` seeded (ray, triangle, incoming hit) triples plus constructed edge cases (determinant at its guards, u, v, u + v and t at
+ * their bounds, NaN and infinity in the ray, lanes off on entry).  out32[0] = number of triples whose {t, u, v, slot} differ
+ * in any bit (must be 0), out32[1] = index of one such triple, out32[2..17] = its o, d, v0, edge1, edge2, incoming hit.t,
+ * out32[18..21] / out32[22..25] = the two results. */
+int rb_debug_triangle_trip(uint32_t n, uint32_t seed, uint32_t* out32);
+/* Measurement aid (tools/salu_mix.py): a loop of independent v_fma_f32 at 8 waves per SIMD on every CU with `scalar_per_16`
+ * (0, 4, 8, 12 or 16) independent scalar adds among each 16 of them and, if `branch` is not 0, one never-taken
+ * s_cbranch_execz per 16.  out3 = {shader clocks per vector instruction and SIMD, shader clock in GHz, milliseconds}. */
+int rb_measure_salu_mix(int32_t device, uint32_t scalar_per_16, uint32_t branch, double* out3);
 /* Test hook: checks the kernels' one-rounding `rnd(seed) * 2 - 1` (one fma) against the shader's three operations on all
  * 2^32 seeds; out16[0] = number of seeds whose value differs, out16[1..15] = some of them. */
 int rb_debug_rnd_pm1_exhaustive(uint32_t* out16);

@@ -187,6 +187,143 @@ DEV void accept_slot(const v4f a, const v4f b, const v4f c, uint32_t slot, f3 o,
     }
 }
 
+// The triangle trip of k_trace / k_trace_direct on single-node trees (intersect_bvh<.., MULTI = false, TRIP = true>; DESIGN.md
+// section 4, "The triangle trip's flow by hand", and section 9, r25).  Knobs, each 0 for the A/B builds of
+// profiles/r25_c2_bench_ab.txt:
+#ifndef RB_TRIP_PLAIN
+#define RB_TRIP_PLAIN 1   // the record loaded at the top of its own trip into the registers the arithmetic reads, one latch; 0: the double buffer
+#endif
+#ifndef RB_TRIP_ASM
+#define RB_TRIP_ASM 3     // accept_trip below: 1 without a skip, 2 with one skip after the u test, 3 with another after the v test; 0: accept_slot as the compiler lays it out
+#endif
+// accept_trip writes out rcp_det's fast form; a build that switches that form off (the A/B knobs of earlier rounds) gets accept_slot back
+#define RB_TRIP_BLOCK (RB_TRIP_ASM != 0 && RB_FAST_RCP && RB_RCP_DET)
+
+// accept_slot<true> with the exec flow laid out by hand.  The vector instructions are the ones the compiler emits for
+// accept_slot<true> -- the same operations on the same operands in the same order, the operand order of every commutative
+// add and multiply included -- so t, u, v are the same bits.  What differs is the flow between them.  The compiler nests four
+// early-outs: each joins two compares in a scalar pair, saves the mask, narrows it, tests it, and all four are restored one after
+// the other at the same point.  Here the mask on entry is kept in one scalar pair and every early-out narrows exec with v_cmpx,
+// which writes the compare's lanes -- 0 for a lane that is off -- into exec.  A compound test is two of them in a row:
+// narrowing by one and then by the other leaves exactly the lanes that pass both, which is the conjunction the source writes
+// (!(u < 0 || u > 1) is !(u < 0) && !(u > 1)).  The compares are the compiler's: nlt / ngt where the source negates a `<` / `>`
+// (true for a NaN, so a NaN goes on as it does in accept_slot), lt where it does not (false for a NaN).  `t > 0.0f` has no
+// instruction, as in the compiler's code: `t > 0.001f` is an ordered compare too, false for a NaN like `t > 0.0f`, and every
+// other t above 0.001 is above 0.  A lane outside rcp_det's guard takes the division under one more mask, put back before u is
+// formed.  The accepted hit's four moves run under the last mask, and one move restores the entry mask: exec leaves the block
+// as it entered it, whichever lanes were on, none included (every instruction between is a vector one, which an empty mask
+// turns into nothing, or touches only the block's own scalar temporaries).
+// SKIP: 1 = one branch over the rest of the trip when no lane passes the u test, 2 = another one after the v test.  big: 2^100 (the caller holds it in a scalar register).
+template <int SKIP>
+DEV void accept_trip(const v4f a, const v4f b, const v4f c, uint32_t slot, f3 o, f3 d, float big, TriHit& hit) {
+    float r8, r10, r11, r12, r13, r14, r15, r16, r17;
+    uint64_t entry, keep, m, ds;
+#define RB_TRIP_HEAD                                                                                                     \
+    "s_mov_b64 %[entry], exec\n\t"                                                                                       \
+    "v_mul_f32_e32 %[r8], %[cz], %[dy]\n\t"                                                                              \
+    "v_mul_f32_e32 %[r10], %[cy], %[dz]\n\t"                                                                             \
+    "v_sub_f32_e32 %[r10], %[r8], %[r10]\n\t"                                                                            \
+    "v_mul_f32_e32 %[r8], %[cx], %[dz]\n\t"                                                                              \
+    "v_mul_f32_e32 %[r11], %[cz], %[dx]\n\t"                                                                             \
+    "v_sub_f32_e32 %[r11], %[r8], %[r11]\n\t"                                                                            \
+    "v_mul_f32_e32 %[r8], %[cy], %[dx]\n\t"                                                                              \
+    "v_mul_f32_e32 %[r12], %[cx], %[dy]\n\t"                                                                             \
+    "v_sub_f32_e32 %[r12], %[r8], %[r12]\n\t"                                                                            \
+    "v_mul_f32_e32 %[r8], %[bx], %[r10]\n\t"                                                                             \
+    "v_mul_f32_e32 %[r13], %[by], %[r11]\n\t"                                                                            \
+    "v_add_f32_e32 %[r8], %[r8], %[r13]\n\t"                                                                             \
+    "v_mul_f32_e32 %[r13], %[bz], %[r12]\n\t"                                                                            \
+    "v_add_f32_e32 %[r13], %[r13], %[r8]\n\t"                                                                            \
+    "v_cmpx_nlt_f32_e64 vcc, |%[r13]|, %[eps]\n\t"           /* !(|det| < 1e-6) */                                       \
+    "v_cmp_eq_u16_e64 %[m], -1, %[r13]\n\t"                  /* rcp_det's guard: low half all ones, */                   \
+    "v_cmp_nlt_f32_e64 vcc, |%[r13]|, %[big]\n\t"            /* or !(|det| < 2^100) */                                   \
+    "v_rcp_f32_e32 %[r8], %[r13]\n\t"                                                                                    \
+    "s_or_b64 %[m], vcc, %[m]\n\t"                                                                                       \
+    "v_fma_f32 %[r14], -%[r13], %[r8], 1.0\n\t"                                                                          \
+    "v_fmac_f32_e32 %[r8], %[r14], %[r8]\n\t"                                                                            \
+    "s_and_saveexec_b64 %[keep], %[m]\n\t"                                                                               \
+    "s_cbranch_execz .Ltrip_rcp_%=\n\t"                                                                                  \
+    "v_div_scale_f32 %[r8], %[ds], %[r13], %[r13], 1.0\n\t"  /* 1.0f / det as the compiler expands it */                 \
+    "v_rcp_f32_e32 %[r14], %[r8]\n\t"                                                                                    \
+    "v_div_scale_f32 %[r15], vcc, 1.0, %[r13], 1.0\n\t"                                                                  \
+    "v_fma_f32 %[r16], -%[r8], %[r14], 1.0\n\t"                                                                          \
+    "v_fmac_f32_e32 %[r14], %[r16], %[r14]\n\t"                                                                          \
+    "v_mul_f32_e32 %[r16], %[r15], %[r14]\n\t"                                                                           \
+    "v_fma_f32 %[r17], -%[r8], %[r16], %[r15]\n\t"                                                                       \
+    "v_fmac_f32_e32 %[r16], %[r17], %[r14]\n\t"                                                                          \
+    "v_fma_f32 %[r8], -%[r8], %[r16], %[r15]\n\t"                                                                        \
+    "v_div_fmas_f32 %[r8], %[r8], %[r14], %[r16]\n\t"                                                                    \
+    "v_div_fixup_f32 %[r8], %[r8], %[r13], 1.0\n"                                                                        \
+    ".Ltrip_rcp_%=:\n\t"                                                                                                 \
+    "s_mov_b64 exec, %[keep]\n\t"                                                                                        \
+    "v_subrev_f32_e32 %[r13], %[ax], %[ox]\n\t"                                                                          \
+    "v_subrev_f32_e32 %[r14], %[ay], %[oy]\n\t"                                                                          \
+    "v_subrev_f32_e32 %[r15], %[az], %[oz]\n\t"                                                                          \
+    "v_mul_f32_e32 %[r10], %[r13], %[r10]\n\t"                                                                           \
+    "v_mul_f32_e32 %[r11], %[r14], %[r11]\n\t"                                                                           \
+    "v_add_f32_e32 %[r10], %[r10], %[r11]\n\t"                                                                           \
+    "v_mul_f32_e32 %[r11], %[r15], %[r12]\n\t"                                                                           \
+    "v_add_f32_e32 %[r10], %[r11], %[r10]\n\t"                                                                           \
+    "v_mul_f32_e32 %[r10], %[r10], %[r8]\n\t"                /* u */                                                     \
+    "v_cmpx_ngt_f32_e32 vcc, 0, %[r10]\n\t"                  /* !(u < 0) */                                              \
+    "v_cmpx_nlt_f32_e32 vcc, 1.0, %[r10]\n\t"                /* !(u > 1) */
+#define RB_TRIP_TAIL                                                                                                     \
+    "v_mul_f32_e32 %[r11], %[bz], %[r14]\n\t"                                                                            \
+    "v_mul_f32_e32 %[r12], %[by], %[r15]\n\t"                                                                            \
+    "v_sub_f32_e32 %[r12], %[r11], %[r12]\n\t"                                                                           \
+    "v_mul_f32_e32 %[r11], %[bx], %[r15]\n\t"                                                                            \
+    "v_mul_f32_e32 %[r15], %[bz], %[r13]\n\t"                                                                            \
+    "v_sub_f32_e32 %[r15], %[r11], %[r15]\n\t"                                                                           \
+    "v_mul_f32_e32 %[r11], %[by], %[r13]\n\t"                                                                            \
+    "v_mul_f32_e32 %[r13], %[bx], %[r14]\n\t"                                                                            \
+    "v_sub_f32_e32 %[r13], %[r11], %[r13]\n\t"                                                                           \
+    "v_mul_f32_e32 %[r11], %[dx], %[r12]\n\t"                                                                            \
+    "v_mul_f32_e32 %[r14], %[dy], %[r15]\n\t"                                                                            \
+    "v_add_f32_e32 %[r11], %[r11], %[r14]\n\t"                                                                           \
+    "v_mul_f32_e32 %[r14], %[dz], %[r13]\n\t"                                                                            \
+    "v_add_f32_e32 %[r11], %[r14], %[r11]\n\t"                                                                           \
+    "v_mul_f32_e32 %[r11], %[r11], %[r8]\n\t"                /* v */                                                     \
+    "v_add_f32_e32 %[r14], %[r10], %[r11]\n\t"                                                                           \
+    "v_cmpx_ngt_f32_e32 vcc, 0, %[r11]\n\t"                  /* !(v < 0) */                                              \
+    "v_cmpx_nlt_f32_e32 vcc, 1.0, %[r14]\n\t"                /* !(u + v > 1) */
+#define RB_TRIP_LAST                                                                                                     \
+    "v_mul_f32_e32 %[r12], %[cx], %[r12]\n\t"                                                                            \
+    "v_mul_f32_e32 %[r14], %[cy], %[r15]\n\t"                                                                            \
+    "v_add_f32_e32 %[r12], %[r12], %[r14]\n\t"                                                                           \
+    "v_mul_f32_e32 %[r13], %[cz], %[r13]\n\t"                                                                            \
+    "v_add_f32_e32 %[r12], %[r13], %[r12]\n\t"                                                                           \
+    "v_mul_f32_e32 %[r8], %[r12], %[r8]\n\t"                 /* t */                                                     \
+    "v_cmpx_lt_f32_e32 vcc, %[tmin], %[r8]\n\t"              /* t > 0.001 */                                             \
+    "v_cmpx_lt_f32_e32 vcc, %[r8], %[ht]\n\t"                /* t < hit.t */                                             \
+    "v_mov_b32_e32 %[hs], %[slot]\n\t"                                                                                   \
+    "v_mov_b32_e32 %[hv], %[r11]\n\t"                                                                                    \
+    "v_mov_b32_e32 %[ht], %[r8]\n\t"                                                                                     \
+    "v_mov_b32_e32 %[hu], %[r10]\n"
+#define RB_TRIP_OPERANDS                                                                                                 \
+    : [ht] "+v"(hit.t), [hu] "+v"(hit.u), [hv] "+v"(hit.v), [hs] "+v"(hit.slot), [r8] "=&v"(r8), [r10] "=&v"(r10),        \
+      [r11] "=&v"(r11), [r12] "=&v"(r12), [r13] "=&v"(r13), [r14] "=&v"(r14), [r15] "=&v"(r15), [r16] "=&v"(r16),         \
+      [r17] "=&v"(r17), [entry] "=&s"(entry), [keep] "=&s"(keep), [m] "=&s"(m), [ds] "=&s"(ds)                            \
+    : [ax] "s"(a.x), [ay] "s"(a.y), [az] "s"(a.z), [bx] "s"(b.x), [by] "s"(b.y), [bz] "s"(b.z), [cx] "s"(c.x),            \
+      [cy] "s"(c.y), [cz] "s"(c.z), [slot] "s"(slot), [ox] "v"(o.x), [oy] "v"(o.y), [oz] "v"(o.z), [dx] "v"(d.x),         \
+      [dy] "v"(d.y), [dz] "v"(d.z), [eps] "s"(1e-6f), [big] "s"(big), [tmin] "s"(0.001f)                             \
+    : "vcc", "scc"   /* s_or_b64 and s_and_saveexec_b64 write scc */
+#define RB_TRIP_SKIP "s_cbranch_execz .Ltrip_end_%=\n\t"
+    if constexpr (SKIP == 2) {
+        asm volatile(RB_TRIP_HEAD RB_TRIP_SKIP RB_TRIP_TAIL RB_TRIP_SKIP RB_TRIP_LAST ".Ltrip_end_%=:\n\t"
+                     "s_mov_b64 exec, %[entry]" RB_TRIP_OPERANDS);
+    } else if constexpr (SKIP == 1) {
+        asm volatile(RB_TRIP_HEAD RB_TRIP_SKIP RB_TRIP_TAIL RB_TRIP_LAST ".Ltrip_end_%=:\n\t"
+                     "s_mov_b64 exec, %[entry]" RB_TRIP_OPERANDS);
+    } else {
+        asm volatile(RB_TRIP_HEAD RB_TRIP_TAIL RB_TRIP_LAST "\ts_mov_b64 exec, %[entry]" RB_TRIP_OPERANDS);
+    }
+#undef RB_TRIP_SKIP
+#undef RB_TRIP_HEAD
+#undef RB_TRIP_TAIL
+#undef RB_TRIP_LAST
+#undef RB_TRIP_OPERANDS
+}
+
 // (One triangle per step.  r01-r02 tested two per step with packed f32 math: on gfx950 a packed f32 instruction issues at
 // half the rate of a plain one (MI355X_MICROARCH.md), so the pairing bought no throughput and paid for the register
 // pairs -- 4.9 % slower on C2, profiles/r03_noslp.txt.  That arm lives in tools/ablate/rb_forks.patch.)
@@ -527,7 +664,9 @@ DEV TriHit intersect_bvh_fast(const KParams& p, f3 o, f3 d, uint32_t* stack, uin
 // MULTI = false: the caller only ever sees trees of at most one node (k_trace, the Cornell kernel): the walks of
 // multi-node trees are left out of its code altogether -- inlined there they cost the hot loop registers (their
 // live ranges pushed 73 VGPRs of k_trace into scratch: 74 B of HBM traffic per segment, -10 %).
-template <bool STATS, bool MULTI = true>
+// TRIP (with MULTI = false; k_trace and k_trace_direct only): the triangle loop in the form the RB_TRIP_* knobs above choose.
+// Every other caller of the single-node walk keeps the double-buffered loop and accept_slot as they were.
+template <bool STATS, bool MULTI = true, bool TRIP = false>
 DEV TriHit intersect_bvh(const KParams& p, f3 o, f3 d, uint32_t* stack, uint32_t stride, Tally<STATS>& tl) {
     TriHit h;
     h.hit = false;
@@ -557,24 +696,45 @@ DEV TriHit intersect_bvh(const KParams& p, f3 o, f3 d, uint32_t* stack, uint32_t
         const uint32_t first = n2.z, count = n2.w;
         const uint32_t end = (first + count < p.index_len) ? first + count : p.index_len;  // guard :331
         if (first < end && isect_aabb(o, inv, mk(n0.x, n0.y, n0.z), mk(n1.x, n1.y, n1.z))) {
-            const uint32_t last = end - 1u;
-            cf4p rec = ptris + (size_t)first * 4u;
-            v4f a = rec[0], b = rec[1], c = rec[2];
-            bool live = __float_as_uint(c.w) != 0u;  // guard :336
-            for (uint32_t slot = first;; slot++) {
-                if (slot < last) rec += 4;
-                const v4f na = rec[0], nb = rec[1], nc = rec[2];
-                if (live) {
-                    if constexpr (STATS) tl.tris++;
-                    const float before = h.t;
-                    accept_slot<!MULTI>(a, b, c, slot, o, d, h);
-                    if constexpr (STATS) tl.mesh_hits += (h.t != before) ? 1u : 0u;
+            constexpr bool trip = TRIP && !MULTI;
+            float big = 0x1p100f;
+            if constexpr (trip && RB_TRIP_BLOCK) asm("s_mov_b32 %0, 0x71800000" : "=s"(big));   // not re-made in every trip
+            auto test = [&](const v4f a, const v4f b, const v4f c, uint32_t slot) {
+                if constexpr (STATS) tl.tris++;
+                const float before = h.t;
+                if constexpr (trip && RB_TRIP_BLOCK) accept_trip<RB_TRIP_ASM - 1>(a, b, c, slot, o, d, big, h);
+                else accept_slot<!MULTI>(a, b, c, slot, o, d, h);
+                if constexpr (STATS) tl.mesh_hits += (h.t != before) ? 1u : 0u;
+            };
+            if constexpr (trip && RB_TRIP_PLAIN != 0) {
+                // The record is requested at the top of its own trip, into the registers the arithmetic reads, and waited for
+                // there: no second register set, no copies, no clamped address of a next record, and one compare at the bottom.
+                // (Eight waves per SIMD cover the scalar load: profiles/r25_c2_bench_ab.txt.)
+                // The empty asm statements pin what the compiler would otherwise move into the trip: the whole record is asked
+                // for in the header block (it would fetch a and b only once c.w has said `live`, a second wait), and the guard's
+                // 2^100 sits in a register set once per segment.
+                cf4p rec = ptris + (size_t)first * 4u;
+                for (uint32_t slot = first; slot != end; slot++, rec += 4) {
+                    v4f a = rec[0], b = rec[1], c = rec[2];
+                    uint32_t live = __float_as_uint(c.w);
+                    asm volatile("" : "+s"(a.x), "+s"(b.x), "+s"(live));
+                    if (live != 0u) test(a, b, c, slot);  // guard :336
                 }
-                if (slot == last) break;
-                a = na;
-                b = nb;
-                c = nc;
-                live = __float_as_uint(nc.w) != 0u;
+            } else {
+                const uint32_t last = end - 1u;
+                cf4p rec = ptris + (size_t)first * 4u;
+                v4f a = rec[0], b = rec[1], c = rec[2];
+                bool live = __float_as_uint(c.w) != 0u;  // guard :336
+                for (uint32_t slot = first;; slot++) {
+                    if (slot < last) rec += 4;
+                    const v4f na = rec[0], nb = rec[1], nc = rec[2];
+                    if (live) test(a, b, c, slot);
+                    if (slot == last) break;
+                    a = na;
+                    b = nb;
+                    c = nc;
+                    live = __float_as_uint(nc.w) != 0u;
+                }
             }
             h.hit = h.t < 1e20f;
         }

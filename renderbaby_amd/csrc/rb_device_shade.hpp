@@ -612,9 +612,10 @@ DEV bool segment_finish(const KParams& p, Path& pt, const TriHit th, uint32_t* s
 
 // One whole iteration of the bounce loop: traversal + everything else.  MULTI = false: trees of at most one node AND no
 // sphere tree (k_trace's default instantiations).
-template <bool STATS, bool MULTI = true, bool JOINED = true>
+// TRIP: intersect_bvh's (k_trace and k_trace_direct pass it for their single-node instantiations).
+template <bool STATS, bool MULTI = true, bool JOINED = true, bool TRIP = false>
 DEV bool segment(const KParams& p, Path& pt, uint32_t* stack, uint32_t stride, Tally<STATS>& tl) {
-    const TriHit th = intersect_bvh<STATS, MULTI>(fresh_params(p), pt.o, pt.d, stack, stride, tl);
+    const TriHit th = intersect_bvh<STATS, MULTI, TRIP>(fresh_params(p), pt.o, pt.d, stack, stride, tl);
     return segment_finish<STATS, MULTI, true, JOINED, !MULTI>(p, pt, th, stack, stride, tl);
 }
 

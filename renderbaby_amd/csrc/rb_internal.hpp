@@ -562,6 +562,8 @@ int launch_div_exhaustive(uint32_t b_begin, uint32_t b_count, uint32_t ea, uint3
 int launch_rcp_exhaustive(uint32_t expo, uint32_t* mismatch16, void* stream);
 int launch_rcp_det_exhaustive(uint32_t expo, uint32_t* mismatch16, void* stream);
 int launch_rnd_pm1_exhaustive(uint32_t* mismatch16, void* stream);
+int launch_triangle_trip(uint32_t n, uint32_t seed, uint32_t* mismatch32, void* stream);   // k_trace's triangle trip against accept_slot<true>
+bool measure_salu_mix(uint32_t scalar_per_16, bool branch, uint32_t rounds, double out[3]);   // clocks per vector instruction with scalar ones among them
 int launch_debug_math(const float* a, const float* b, float* out, uint32_t n, void* stream);
 int debug_walk_profile(unsigned long long* out64, int reset);   // pass occupancy counters of a profiling build, tools/ablate/rb_profile.patch (-1 otherwise)
 double measure_l1_gather(size_t table_bytes, uint32_t rounds);   // divergent 16-byte gathers from an L2-resident table: lane accesses / s

@@ -546,7 +546,7 @@ DEV void trace_body(const KParams& p, v4f* s_ring) {
         // (53 v_mov_b32 per iteration; profiles/r12_ktrace_moves_before.txt).
         if (__ballot(active) == 0ull && exhausted && loc_next == loc_end) break;
         if (active) {
-            const bool alive = segment<STATS, MULTI, JOINED>(p, pt, &s_stack[tid], kTraceBlock, tl);
+            const bool alive = segment<STATS, MULTI, JOINED, !MULTI>(p, pt, &s_stack[tid], kTraceBlock, tl);
             if (!alive) {
                 cring.finish(colors, item, pt.color);
                 tl.paths++;
@@ -1545,6 +1545,196 @@ __global__ void k_rcp_det_exhaustive(uint32_t expo, uint32_t* mismatch) {
     }
 }
 
+// The triangle trip of k_trace (intersect_bvh<.., TRIP = true>: accept_trip; a build with RB_TRIP_ASM = 0 compares accept_slot<true>
+// with itself) against the form every other caller keeps, accept_slot<true>, on the same (ray, triangle, incoming hit):
+// {t, u, v, slot} afterwards, bit for bit.  The record is wave-uniform as in the walk (it reaches the trip in scalar registers),
+// so a wave is one triangle and 64 rays.  Waves [0, n_waves) draw both from `seed`: rays aimed at and around the triangle, with
+// scales that reach the determinant's guards now and then, and an incoming hit.t of 1e20 or near the triangle.  The waves
+// behind them are the constructed cases, one per wave (trip_case), each lane one of four incoming hits -- 1e20, 0.5, the case's
+// own t and the float above it -- with lanes 8..15 of every 16 switched off on entry, which must leave their hit as it came.
+// mismatch[0] counts differing triples; mismatch[1] is the index of one and mismatch[2..] its 16 input and 8 output words.
+constexpr uint32_t kTripCases = 44u;
+DEV void trip_case(uint32_t k, f3& o, f3& d, f3& v0, f3& e1, f3& e2) {
+    // d = +z, e1 = (0, A, 0), e2 = (1, 0, 0), v0 = 0: every product with a zero is exact, so det = A, and with A = 1 the ray
+    // from o has u = o.y, v = o.x, t = -o.z exactly
+    o = mk(0.25f, 0.25f, -1.0f);
+    d = mk(0.0f, 0.0f, 1.0f);
+    v0 = mk(0.0f, 0.0f, 0.0f);
+    e1 = mk(0.0f, 1.0f, 0.0f);
+    e2 = mk(1.0f, 0.0f, 0.0f);
+    const uint32_t eps = 0x358637BDu, big = 0x71800000u, one = 0x3F800000u, tmin = 0x3A83126Fu;   // 1e-6f, 2^100, 1, 0.001f
+    const float nan = __uint_as_float(0x7FC00000u), inf = __uint_as_float(0x7F800000u);
+    switch (k) {
+        case 0: case 1: case 2: e1.y = __uint_as_float(eps - 1u + k); break;                  // |det| below, at, above 1e-6
+        case 3: case 4: case 5: e1.y = -__uint_as_float(eps - 1u + (k - 3u)); break;
+        case 6: case 7: case 8: e1.y = __uint_as_float(big - 1u + (k - 6u)); break;           // |det| below, at, above 2^100
+        case 9: e1.y = -0x1p100f; break;
+        case 10: e1.y = 0x1p120f; break;
+        case 11: e1.y = __uint_as_float(0x3F80FFFFu); break;                                  // low 16 bits all ones
+        case 12: e1.y = __uint_as_float(0xC123FFFFu); break;
+        case 13: e1.y = __uint_as_float(0x3FFFFFFFu); break;                                  // the one significand rcp_tri excludes
+        case 14: o.y = 0.0f; break;                                                           // u = 0, -0, 1, the floats around them
+        case 15: o.y = -0.0f; break;
+        case 16: o.y = -0x1p-149f; break;
+        case 17: o.y = 1.0f; o.x = 0.0f; break;
+        case 18: o.y = __uint_as_float(one + 1u); o.x = 0.0f; break;
+        case 19: o.x = 0.0f; break;                                                           // v = 0, -0, below 0
+        case 20: o.x = -0.0f; break;
+        case 21: o.x = -0x1p-149f; break;
+        case 22: o.x = 0.75f; break;                                                          // u + v = 1 and the float above
+        case 23: o.x = 0.75f; o.y = __uint_as_float(0x3E800001u); break;
+        case 24: o.z = -__uint_as_float(tmin); break;                                         // t = 0.001 and around, 0, below 0
+        case 25: o.z = -__uint_as_float(tmin + 1u); break;
+        case 26: o.z = -__uint_as_float(tmin - 1u); break;
+        case 27: o.z = 0.0f; break;
+        case 28: o.z = 1.0f; break;
+        case 29: o.x = nan; break;                                                            // a NaN and an infinity in o and in d
+        case 30: o.y = nan; break;
+        case 31: o.z = nan; break;
+        case 32: d.x = nan; break;
+        case 33: d.y = nan; break;
+        case 34: d.z = nan; break;
+        case 35: o.x = inf; break;
+        case 36: o.y = -inf; break;
+        case 37: o.z = -inf; break;
+        case 38: d.x = inf; break;
+        case 39: d.y = -inf; break;
+        case 40: d.z = inf; break;
+        case 41: e1.y = 0.0f; break;                                                          // det = 0, a NaN and an infinite edge
+        case 42: e1.y = nan; break;
+        default: e2.x = inf; break;
+    }
+}
+DEV float trip_unit(uint32_t& s) {   // [-1, 1)
+    s = pcg(s);
+    return (float)(int32_t)s * 0x1p-31f;
+}
+__global__ void __launch_bounds__(256) k_triangle_trip(uint32_t n_waves, uint32_t seed, uint32_t* mismatch) {
+    const uint32_t wave = (blockIdx.x * 256u + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
+    if (wave >= n_waves + kTripCases) return;
+    f3 o, d, v0, e1, e2;
+    float hit_t = 1e20f;
+    bool on = true;
+    if (wave < n_waves) {
+        uint32_t sw = pcg(seed ^ (wave * 0x9E3779B9u)), sl = pcg(sw + lane * 0x85EBCA6Bu + 1u);
+        const uint32_t kind = pcg(sw) & 15u;   // 0: tiny triangle (|det| around 1e-6), 1: huge (|det| >= 2^100), else ordinary
+        const float scale = kind == 0u ? 0x1p-10f : kind == 1u ? 0x1p52f : 1.0f;
+        v0 = mk(trip_unit(sw), trip_unit(sw), trip_unit(sw));
+        e1 = scale * mk(trip_unit(sw), trip_unit(sw), trip_unit(sw));
+        e2 = scale * mk(trip_unit(sw), trip_unit(sw), trip_unit(sw));
+        o = 2.0f * mk(trip_unit(sl), trip_unit(sl), trip_unit(sl));
+        const float a = 0.7f * trip_unit(sl) + 0.5f, b = 0.7f * trip_unit(sl) + 0.5f;        // in and around the triangle
+        const f3 to = (v0 + a * e1 + b * e2) - o;
+        d = __builtin_amdgcn_rsqf(dot(to, to) + 1e-30f) * to;
+        const uint32_t r = pcg(sl);
+        if (r & 1u) hit_t = 2.0f * (float)(r >> 8) * 0x1p-24f;
+        on = (r & 6u) != 0u;   // a quarter of the lanes are off on entry
+    } else {
+        trip_case(wave - n_waves, o, d, v0, e1, e2);
+        on = (lane & 8u) == 0u;
+    }
+    // the record as the walk hands it over: wave-uniform, in scalar registers
+    auto uni = [](float x) { return __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(x))); };
+    const v4f ra = {uni(v0.x), uni(v0.y), uni(v0.z), 0.0f}, rb_ = {uni(e1.x), uni(e1.y), uni(e1.z), 0.0f},
+              rc = {uni(e2.x), uni(e2.y), uni(e2.z), 1.0f};
+    const uint32_t slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)(wave + 1u));
+    if (wave >= n_waves) {
+        TriHit own;
+        own.t = 1e20f, own.u = 0.0f, own.v = 0.0f, own.slot = 0u, own.hit = false;
+        accept_slot<true>(ra, rb_, rc, slot, o, d, own);
+        const uint32_t v = lane & 3u;
+        hit_t = v == 0u ? 1e20f : v == 1u ? 0.5f : v == 2u ? own.t : __uint_as_float(__float_as_uint(own.t) + 1u);
+    }
+    TriHit want, got;
+    want.t = hit_t, want.u = -2.0f, want.v = -3.0f, want.slot = 0xABCDu, want.hit = false;
+    got = want;
+    float big = 0x1p100f;
+    if constexpr (RB_TRIP_BLOCK) asm("s_mov_b32 %0, 0x71800000" : "=s"(big));
+    if (on) {
+        accept_slot<true>(ra, rb_, rc, slot, o, d, want);
+        if constexpr (RB_TRIP_BLOCK) accept_trip<RB_TRIP_ASM - 1>(ra, rb_, rc, slot, o, d, big, got);
+        else accept_slot<true>(ra, rb_, rc, slot, o, d, got);
+    }
+    if (__float_as_uint(want.t) != __float_as_uint(got.t) || __float_as_uint(want.u) != __float_as_uint(got.u) ||
+        __float_as_uint(want.v) != __float_as_uint(got.v) || want.slot != got.slot) {
+        if (atomicAdd(&mismatch[0], 1u) == 0u) {
+            mismatch[1] = wave * 64u + lane;
+            const float in[16] = {o.x, o.y, o.z, d.x, d.y, d.z, ra.x, ra.y, ra.z, rb_.x, rb_.y, rb_.z, rc.x, rc.y, rc.z, hit_t};
+            for (int k = 0; k < 16; k++) mismatch[2 + k] = __float_as_uint(in[k]);
+            mismatch[18] = __float_as_uint(got.t), mismatch[19] = __float_as_uint(got.u), mismatch[20] = __float_as_uint(got.v);
+            mismatch[21] = got.slot;
+            mismatch[22] = __float_as_uint(want.t), mismatch[23] = __float_as_uint(want.u), mismatch[24] = __float_as_uint(want.v);
+            mismatch[25] = want.slot;
+        }
+    }
+}
+
+// What the scalar unit sustains next to the vector units (rb_measure_salu_mix, tools/salu_mix.py):
+// every wave runs a loop of 64 independent v_fma_f32 in their two-operand encoding, v_fmac_f32 (16 registers, four rounds), with SALU scalar adds spread among each 16 of
+// them -- four registers, so neighbours are independent -- and, with BRANCH, one s_cbranch_execz per 16 that is never taken
+// (exec is never empty in a wave that runs).  The loop's own three scalar instructions come on top of the 4 * SALU.
+// stamp[0..1]: the shader clock and the 100 MHz clock over the first wave's loop, for the clock the run had.
+template <int SALU, bool BRANCH>
+__global__ void __launch_bounds__(256, 8) k_salu_mix(uint32_t rounds, float c, float* sink, unsigned long long* stamp) {
+    float v[16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) v[k] = (float)(threadIdx.x + k) * 0x1p-20f;
+    const float c2 = c * 0x1p-20f;   // an accumulator gains c * c2 a time: nothing overflows
+    uint32_t s0 = rounds, s1 = rounds + 1u, s2 = rounds + 2u, s3 = rounds + 3u;
+    const unsigned long long t0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
+#define RB_MIX_F(k) "v_fmac_f32_e32 %" #k ", %[c], %[c2]\n\t"
+#define RB_MIX_S(j) "s_add_u32 %[s" #j "], %[s" #j "], 1\n\t"
+    // four vector instructions with 0 .. 4 scalar adds among them
+#define RB_MIX_Q0(a, b, c, d) RB_MIX_F(a) RB_MIX_F(b) RB_MIX_F(c) RB_MIX_F(d)
+#define RB_MIX_Q1(a, b, c, d) RB_MIX_F(a) RB_MIX_F(b) RB_MIX_S(0) RB_MIX_F(c) RB_MIX_F(d)
+#define RB_MIX_Q2(a, b, c, d) RB_MIX_F(a) RB_MIX_S(0) RB_MIX_F(b) RB_MIX_F(c) RB_MIX_S(1) RB_MIX_F(d)
+#define RB_MIX_Q3(a, b, c, d) RB_MIX_F(a) RB_MIX_S(0) RB_MIX_F(b) RB_MIX_S(1) RB_MIX_F(c) RB_MIX_S(2) RB_MIX_F(d)
+#define RB_MIX_Q4(a, b, c, d) RB_MIX_F(a) RB_MIX_S(0) RB_MIX_F(b) RB_MIX_S(1) RB_MIX_F(c) RB_MIX_S(2) RB_MIX_F(d) RB_MIX_S(3)
+#define RB_MIX_BR "s_cbranch_execz .Lmix_out_%=\n\t"
+#define RB_MIX_GROUP(Q, BR) Q(0, 1, 2, 3) Q(4, 5, 6, 7) Q(8, 9, 10, 11) Q(12, 13, 14, 15) BR
+#define RB_MIX_ASM(Q, BR)                                                                                                 \
+    asm volatile(RB_MIX_GROUP(Q, BR) RB_MIX_GROUP(Q, BR) RB_MIX_GROUP(Q, BR) RB_MIX_GROUP(Q, BR) ".Lmix_out_%=:"          \
+                 : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]), "+v"(v[8]), \
+                   "+v"(v[9]), "+v"(v[10]), "+v"(v[11]), "+v"(v[12]), "+v"(v[13]), "+v"(v[14]), "+v"(v[15]), [s0] "+s"(s0), \
+                   [s1] "+s"(s1), [s2] "+s"(s2), [s3] "+s"(s3)                                                            \
+                 : [c] "v"(c), [c2] "v"(c2)                                                                                             \
+                 : "scc")
+    for (uint32_t r = rounds; r != 0u; r--) {
+        if constexpr (BRANCH) {
+            if constexpr (SALU == 0) RB_MIX_ASM(RB_MIX_Q0, RB_MIX_BR);
+            else if constexpr (SALU == 4) RB_MIX_ASM(RB_MIX_Q1, RB_MIX_BR);
+            else if constexpr (SALU == 8) RB_MIX_ASM(RB_MIX_Q2, RB_MIX_BR);
+            else if constexpr (SALU == 12) RB_MIX_ASM(RB_MIX_Q3, RB_MIX_BR);
+            else RB_MIX_ASM(RB_MIX_Q4, RB_MIX_BR);
+        } else {
+            if constexpr (SALU == 0) RB_MIX_ASM(RB_MIX_Q0, "");
+            else if constexpr (SALU == 4) RB_MIX_ASM(RB_MIX_Q1, "");
+            else if constexpr (SALU == 8) RB_MIX_ASM(RB_MIX_Q2, "");
+            else if constexpr (SALU == 12) RB_MIX_ASM(RB_MIX_Q3, "");
+            else RB_MIX_ASM(RB_MIX_Q4, "");
+        }
+    }
+#undef RB_MIX_F
+#undef RB_MIX_S
+#undef RB_MIX_Q0
+#undef RB_MIX_Q1
+#undef RB_MIX_Q2
+#undef RB_MIX_Q3
+#undef RB_MIX_Q4
+#undef RB_MIX_BR
+#undef RB_MIX_GROUP
+#undef RB_MIX_ASM
+    const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
+    float acc = (float)(s0 ^ s1 ^ s2 ^ s3);
+#pragma unroll
+    for (int k = 0; k < 16; k++) acc += v[k];
+    if (acc == 12345.678f) sink[0] = acc;   // keeps the loop's values alive
+    if (blockIdx.x == 0u && threadIdx.x == 0u) {
+        stamp[0] = t1 - t0;
+        stamp[1] = r1 - r0;
+    }
+}
+
 // Exhaustive check of rnd_pm1 against `rnd(seed) * 2.0f - 1.0f` (the shader's three roundings): all 2^32 seeds, 256 per
 // thread of a 2^16 x 256 grid.  pcg is a bijection, so every word the conversion can meet is met.  mismatch[0] counts the
 // seeds whose value or whose seed afterwards differs; mismatch[1..] records up to 15 of them.
@@ -1953,6 +2143,62 @@ int launch_rcp_det_exhaustive(uint32_t expo, uint32_t* mismatch, void* stream_) 
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     hipLaunchKernelGGL(k_rcp_det_exhaustive, dim3((1u << 23) / 256), dim3(256), 0, stream, expo, mismatch);
     return (int)hipGetLastError();
+}
+
+int launch_triangle_trip(uint32_t n, uint32_t seed, uint32_t* mismatch32, void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const uint32_t n_waves = (n + 63u) / 64u, waves = n_waves + kTripCases;
+    hipLaunchKernelGGL(k_triangle_trip, dim3((waves + 3u) / 4u), dim3(256), 0, stream, n_waves, seed, mismatch32);
+    return (int)hipGetLastError();
+}
+
+// out[0] = shader clocks per vector instruction and SIMD (8 waves on each), out[1] = the shader clock in GHz the first wave saw,
+// out[2] = the launch's milliseconds; the better of two launches.  scalar_per_16 in {0, 4, 8, 12, 16}.  false on failure.
+bool measure_salu_mix(uint32_t scalar_per_16, bool branch, uint32_t rounds, double out[3]) {
+    float* sink = nullptr;
+    unsigned long long* stamp = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&sink), 16) != hipSuccess) return false;
+    if (hipMalloc(reinterpret_cast<void**>(&stamp), 16) != hipSuccess) { (void)hipFree(sink); return false; }
+    hipEvent_t t0, t1;
+    (void)hipEventCreate(&t0);
+    (void)hipEventCreate(&t1);
+    const uint32_t blocks = device_cu_count_cached() * 8u;   // 4 waves a block: 8 waves on every SIMD
+    float best = 0.0f;
+    unsigned long long st[2] = {0, 0};
+    bool ok = true;
+    for (int rep = 0; rep < 3 && ok; rep++) {   // the first launch warms up
+        (void)hipEventRecord(t0, nullptr);
+#define RB_MIX_LAUNCH(S)                                                                                                         \
+    if (branch) hipLaunchKernelGGL((k_salu_mix<S, true>), dim3(blocks), dim3(256), 0, nullptr, rounds, 0.5f, sink, stamp);      \
+    else hipLaunchKernelGGL((k_salu_mix<S, false>), dim3(blocks), dim3(256), 0, nullptr, rounds, 0.5f, sink, stamp)
+        switch (scalar_per_16) {
+            case 0u: RB_MIX_LAUNCH(0); break;
+            case 4u: RB_MIX_LAUNCH(4); break;
+            case 8u: RB_MIX_LAUNCH(8); break;
+            case 12u: RB_MIX_LAUNCH(12); break;
+            case 16u: RB_MIX_LAUNCH(16); break;
+            default: ok = false; break;
+        }
+#undef RB_MIX_LAUNCH
+        (void)hipEventRecord(t1, nullptr);
+        if (!ok || hipGetLastError() != hipSuccess || hipEventSynchronize(t1) != hipSuccess) { ok = false; break; }
+        float ms = 0.0f;
+        (void)hipEventElapsedTime(&ms, t0, t1);
+        if (rep > 0 && ms > 0.0f && (best == 0.0f || ms < best)) {
+            best = ms;
+            (void)hipMemcpy(st, stamp, 16, hipMemcpyDeviceToHost);
+        }
+    }
+    (void)hipEventDestroy(t0);
+    (void)hipEventDestroy(t1);
+    (void)hipFree(sink);
+    (void)hipFree(stamp);
+    if (!ok || best <= 0.0f || st[1] == 0ull) return false;
+    const double ghz = (double)st[0] / (double)st[1] * 0.1;   // the second counter runs at 100 MHz
+    out[0] = (best * 1e-3) * (ghz * 1e9) / ((double)rounds * 64.0 * 8.0);
+    out[1] = ghz;
+    out[2] = best;
+    return true;
 }
 
 // -> lane accesses per second (0 on failure): the best of a few shapes (8 or 16 loads in flight per lane, 4 or 8 waves

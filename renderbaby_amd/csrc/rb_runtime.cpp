@@ -1542,6 +1542,34 @@ int rb_debug_rcp_det_exhaustive(uint32_t biased_exponent, uint32_t* out16) {
     return (rc || st != hipSuccess) ? RB_ERR_DEVICE : RB_OK;
 }
 
+// Test hook: the triangle trip of k_trace / k_trace_direct against the form the other kernels keep (accept_slot<true>) on n
+// seeded (ray, triangle, incoming hit) triples and the constructed edge cases behind them (k_triangle_trip).
+// out32[0] = number of triples whose {t, u, v, slot} differ in any bit, out32[1] = the index of one, out32[2..17] its
+// o, d, v0, edge1, edge2 and incoming hit.t, out32[18..21] the trip's {t, u, v, slot}, out32[22..25] accept_slot's.
+int rb_debug_triangle_trip(uint32_t n, uint32_t seed, uint32_t* out32) {
+    if (!out32) return RB_ERR_NULL_ARGUMENT;
+    if (n > (1u << 26)) return RB_ERR_INVALID_OPTIONS;
+    uint32_t* d = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&d), 128) != hipSuccess) return RB_ERR_DEVICE;
+    (void)hipMemset(d, 0, 128);
+    int rc = rb::launch_triangle_trip(n, seed, d, nullptr);
+    hipError_t st = hipDeviceSynchronize();
+    (void)hipMemcpy(out32, d, 128, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    return (rc || st != hipSuccess) ? RB_ERR_DEVICE : RB_OK;
+}
+
+// Measurement aid (tools/salu_mix.py): what a vector instruction costs with scalar ones among them (k_salu_mix).
+int rb_measure_salu_mix(int32_t device, uint32_t scalar_per_16, uint32_t branch, double* out3) {
+    if (!out3) return RB_ERR_NULL_ARGUMENT;
+    if (scalar_per_16 > 16u || (scalar_per_16 & 3u) != 0u) return RB_ERR_INVALID_OPTIONS;
+    int before = -1;
+    if (device >= 0 && (hipGetDevice(&before) != hipSuccess || hipSetDevice(device) != hipSuccess)) return RB_ERR_DEVICE;
+    const bool ok = rb::measure_salu_mix(scalar_per_16, branch != 0u, 4096u, out3);
+    if (before >= 0) (void)hipSetDevice(before);   // the caller's device is current again
+    return ok ? RB_OK : RB_ERR_DEVICE;
+}
+
 // Test hook: device check of the one-rounding form of `rnd(seed) * 2 - 1` (rnd_pm1) against the three-operation form on all
 // 2^32 seeds.  out16[0] = number of differing seeds, out16[1..15] = some of them.
 int rb_debug_rnd_pm1_exhaustive(uint32_t* out16) {

@@ -13,6 +13,8 @@ FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fhip-fp32-c
 /opt/rocm/bin/hipcc $FLAGS "$@" -c -o build/obj/rb_bvh.$name.o renderbaby_amd/csrc/rb_bvh.cpp          # (host-side knobs: RB_CHUNK_TRIS ...)
 /opt/rocm/bin/hipcc $FLAGS "$@" -c -o build/obj/rb_runtime.$name.o renderbaby_amd/csrc/rb_runtime.cpp
 /opt/rocm/bin/hipcc $FLAGS "$@" -c -o build/obj/rb_accel.$name.o renderbaby_amd/csrc/rb_accel.cpp
+# every other object is the last `make`'s
+rest=$(ls build/obj/*.hip.o build/obj/*.cpp.o | grep -v -E '/rb_(kernels|query|build|bvh|runtime|accel)\.(hip|cpp)\.o$')
 /opt/rocm/bin/hipcc -fPIC --offload-arch=gfx950 -shared -o renderbaby_amd/variants/lib_$name.so build/obj/rb_kernels.$name.o build/obj/rb_query.$name.o \
-    build/obj/rb_build.$name.o build/obj/rb_runtime.$name.o build/obj/rb_accel.$name.o build/obj/rb_bvh.$name.o build/obj/rb_rccl.cpp.o -ldl
+    build/obj/rb_build.$name.o build/obj/rb_runtime.$name.o build/obj/rb_accel.$name.o build/obj/rb_bvh.$name.o $rest -ldl
 echo "renderbaby_amd/variants/lib_$name.so"

@@ -18,6 +18,7 @@ DPP_WORDS = ("quad_perm:", "row_shl:", "row_shr:", "row_ror:", "row_bcast:", "wa
 
 Instr = namedtuple("Instr", "line op args text")
 _LABEL = re.compile(r"^(\.LBB\d+_\d+):")
+_ASM_LABEL = re.compile(r"^(\.L\w+):")
 _FALL = re.compile(r"^; (%bb\.\d+):")
 _INLOOP = re.compile(r"in Loop: Header=(BB\d+_\d+) Depth=(\d+)")
 _HEADER = re.compile(r"This (Inner )?Loop Header: Depth=(\d+)")
@@ -84,7 +85,19 @@ def parse_blocks(asm_path, kernel):
     """The function's basic blocks in text order: a block starts at a label (.LBBx_y) or at a fall-through mark (; %bb.n)."""
     first, lines = kernel_lines(asm_path, kernel)
     blocks = [Block("entry", first)]
+    in_asm = False
     for k, l in enumerate(lines[1:], 1):
+        # an inline-asm statement (#ASMSTART .. #ASMEND) can hold branches and labels of its own (accept_trip): a label in it
+        # starts a block like any other, which belongs to the loop of the block the statement stands in
+        if l.strip().startswith(";;#ASM"):
+            in_asm = "#ASMSTART" in l
+            continue
+        am = _ASM_LABEL.match(l) if in_asm else None
+        if am:
+            b = Block(am.group(1)[2:], first + k)
+            b.loop, b.depth = blocks[-1].loop, blocks[-1].depth
+            blocks.append(b)
+            continue
         m = _LABEL.match(l) or _FALL.match(l)
         if m:
             b = Block(m.group(1)[2:] if m.group(1).startswith(".L") else m.group(1), first + k)   # .LBB29_5 -> BB29_5, as in the loop comments
@@ -106,6 +119,10 @@ def parse_blocks(asm_path, kernel):
             continue
         parts = text.split(None, 1)
         b.instrs.append(Instr(first + k, parts[0], parts[1] if len(parts) > 1 else "", text))
+        if in_asm and parts[0].startswith("s_cbranch"):   # what follows a branch of the statement's own is the fall-through block
+            nb = Block(b.name + ".fall", first + k + 1)
+            nb.loop, nb.depth = b.loop, b.depth
+            blocks.append(nb)
     # a header written on the label's own line ("; =>This Inner Loop Header: Depth=1")
     for b in blocks:
         l = lines[b.line - first]

@@ -7,7 +7,8 @@ assembly (tools/isa_blocks.py) times the trip structure of the contract workload
    book     bookkeeping: moves, selects, masks, guards, address arithmetic, lane operations
    slow     the instructions that issue over 8 cycles instead of 2 (isa_blocks.QUARTER_RATE: v_rcp, v_sqrt, v_mul_lo_u32 ...)
 
-and priced at 2 cycles an instruction, 8 for the slow ones.  Trip counts: the two intersection loops are data-independent (12
+and priced at 2 cycles an instruction, 8 for the slow ones.  `salu` is the other stream: the scalar instructions of a trip
+(isa_blocks' count: everything s_* but loads, waits and nops), which the four SIMDs of a CU hand to one scalar unit.  Trip counts: the two intersection loops are data-independent (12
 triangles, 8 spheres, the phantom point light); the data-dependent ones are the phase counts of profiles/r15_ktrace_phases.txt
 (executions per segment x 64, which is executions per iteration of a wavefront that enters with 63.6 lanes).  A trip of the
 triangle loop does not run the compiler's division fallback (the blocks with v_div_scale), which the guard of the reciprocal
@@ -92,23 +93,25 @@ def rejection_loop(blocks):
 
 
 def rows(blocks):
-    """(name, trips per iteration, instructions of one trip, hash loop?) for every loop of the table"""
+    """(name, trips per iteration, instructions of one trip, hash loop?, scalar instructions of one trip) for every loop of the table"""
     tri_h, tri_body = isa_blocks.triangle_loop(blocks)
     fallback = [b for b in tri_body if any(i.op.startswith("v_div_scale") for i in b.instrs)]
     trip = [i for b in tri_body if b not in fallback for i in b.valu]
     scans = scan_loops(blocks)
-    out = [(f"triangle loop {tri_h.name}, a trip", TRIANGLES, trip, False),
-           (f"  its division fallback ({len(fallback)} blocks, branched over)", 0, [i for b in fallback for i in b.valu], False)]
+    salu = lambda body: sum(b.counts()["salu"] for b in body)
+    out = [(f"triangle loop {tri_h.name}, a trip", TRIANGLES, trip, False, salu([b for b in tri_body if b not in fallback])),
+           (f"  its division fallback ({len(fallback)} blocks, branched over)", 0, [i for b in fallback for i in b.valu], False, salu(fallback))]
     names = ("sphere", "light")
     trips = ((SPHERES, PASS2_TRIPS), (LIGHTS, LIGHT_PASS2_TRIPS))
     for k, ((h1, b1), (h2, b2)) in enumerate(scans[:2]):
-        out.append((f"{names[k]} scan pass 1 {h1.name}", trips[k][0], [i for b in b1 for i in b.valu], False))
-        out.append((f"{names[k]} scan pass 2 {h2.name}", trips[k][1], [i for b in b2 for i in b.valu], False))
+        out.append((f"{names[k]} scan pass 1 {h1.name}", trips[k][0], [i for b in b1 for i in b.valu], False, salu(b1)))
+        out.append((f"{names[k]} scan pass 2 {h2.name}", trips[k][1], [i for b in b2 for i in b.valu], False, salu(b2)))
     rh, rbody = rejection_loop(blocks)
-    out.append((f"rejection loop {rh.name}, a round", REJECTION_ROUNDS, [i for b in rbody for i in b.valu], True))
-    counted = {id(i) for _, _, ins, _ in out for i in ins}
+    out.append((f"rejection loop {rh.name}, a round", REJECTION_ROUNDS, [i for b in rbody for i in b.valu], True, salu(rbody)))
+    counted = {id(i) for _, _, ins, _, _ in out for i in ins}
+    in_loops = sum(r[4] for r in out)
     rest = [i for b in blocks for i in b.valu if id(i) not in counted]
-    out.append(("everything else (static, every block once)", None, rest, True))
+    out.append(("everything else (static, every block once)", None, rest, True, salu(blocks) - in_loops))
     return out
 
 
@@ -117,21 +120,21 @@ def main():
     kernel = sys.argv[2] if len(sys.argv) > 2 else "k_traceILb0ELb0ELi8"
     blocks = isa_blocks.parse_blocks(asm, kernel)
     print(f"# {kernel}: vector instructions per iteration of the persistent loop on C2, loop by loop (static count x trips)")
-    print(f"{'loop':58s} {'trips':>6s} {'valu':>5s} {'arith':>6s} {'cmp':>5s} {'book':>5s} {'slow':>5s} | {'valu/it':>8s} {'book/it':>8s} {'slow/it':>8s} {'cycles/it':>10s}")
-    tot = [0.0, 0.0, 0.0, 0.0]
-    for name, trips, instrs, hashes in rows(blocks):
+    print(f"{'loop':58s} {'trips':>6s} {'valu':>5s} {'arith':>6s} {'cmp':>5s} {'book':>5s} {'slow':>5s} {'salu':>5s} | {'valu/it':>8s} {'book/it':>8s} {'slow/it':>8s} {'cycles/it':>10s} {'salu/it':>8s}")
+    tot = [0.0, 0.0, 0.0, 0.0, 0.0]
+    for name, trips, instrs, hashes, salu in rows(blocks):
         c = split(instrs, hashes)
         n = sum(c.values())
         if trips is None:
-            print(f"{name:58s} {'-':>6s} {n:5d} {c['arith']:6d} {c['cmp']:5d} {c['book']:5d} {c['slow']:5d} |")
+            print(f"{name:58s} {'-':>6s} {n:5d} {c['arith']:6d} {c['cmp']:5d} {c['book']:5d} {c['slow']:5d} {salu:5d} |")
             continue
-        per = [n * trips, c["book"] * trips, c["slow"] * trips, (2 * (n - c["slow"]) + 8 * c["slow"]) * trips]
+        per = [n * trips, c["book"] * trips, c["slow"] * trips, (2 * (n - c["slow"]) + 8 * c["slow"]) * trips, salu * trips]
         tot = [a + b for a, b in zip(tot, per)]
-        print(f"{name:58s} {trips:6.2f} {n:5d} {c['arith']:6d} {c['cmp']:5d} {c['book']:5d} {c['slow']:5d} | {per[0]:8.1f} {per[1]:8.1f} {per[2]:8.1f} {per[3]:10.1f}")
-    print(f"{'the loops above':58s} {'':6s} {'':5s} {'':6s} {'':5s} {'':5s} {'':5s} | {tot[0]:8.1f} {tot[1]:8.1f} {tot[2]:8.1f} {tot[3]:10.1f}")
+        print(f"{name:58s} {trips:6.2f} {n:5d} {c['arith']:6d} {c['cmp']:5d} {c['book']:5d} {c['slow']:5d} {salu:5d} | {per[0]:8.1f} {per[1]:8.1f} {per[2]:8.1f} {per[3]:10.1f} {per[4]:8.1f}")
+    print(f"{'the loops above':58s} {'':6s} {'':5s} {'':6s} {'':5s} {'':5s} {'':5s} {'':5s} | {tot[0]:8.1f} {tot[1]:8.1f} {tot[2]:8.1f} {tot[3]:10.1f} {tot[4]:8.1f}")
     tri_h, tri_body = isa_blocks.triangle_loop(blocks)
     print("# bookkeeping and slow instructions of the intersection loops, by opcode (static, one trip):")
-    for name, _, instrs, hashes in rows(blocks)[:4]:
+    for name, _, instrs, hashes, _ in rows(blocks)[:4]:
         if name.lstrip().startswith("its division"):
             continue
         ops = {}
