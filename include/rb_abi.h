@@ -482,6 +482,53 @@ int rb_debug_chunk_tree(const rb_gpu_triangle* tris, size_t n_tris, const rb_bvh
  * chunked walk's arrays are read back from the device -- whichever builder made them -- and checked against the engine's
  * copy of the mesh.  out6 as above (built = 0: the engine has no chunked tree). */
 int rb_debug_engine_chunk_tree(rb_engine* e, uint64_t out6[6]);
+/* Test aids: the library's own triangle tree (RB_FLAG_FAST_BVH / _DEVICE_BVH / _DEVICE_LBVH / _HOST_BVH)
+ * and its sphere tree, handed out as they are so that a test can hold them to their invariants (tests/_tree_model.py); nothing
+ * is checked here.  One node of the triangle tree decides both children: their boxes, their references (node index, or leaf =
+ * 0x80000000 | (count - 1) << 28 | first position in `slots`, count 1 or 2) and per child FA, the largest F_k below it (+inf:
+ * always enter). */
+typedef struct rb_debug_own_node {
+    float lmin[3];
+    uint32_t left;
+    float lmax[3];
+    uint32_t right;
+    float rmin[3];
+    float left_fa;
+    float rmax[3];
+    float right_fa;
+} rb_debug_own_node;
+/* One 4-wide node of the sphere tree: child k's box is (cx[k], cy[k], cz[k]) -+ (hx[k], hy[k], hz[k]); ref[k] is 0xFFFFFFFF
+ * (no child), a node index, or leaf = 0x80000000 | (count - 1) << 27 | first position in the leaf order (count <= 16).
+ * Children 0, 1 are the lower half of the split along axis (axes & 3), cut along (axes >> 2) & 3; children 2, 3 the upper
+ * half, cut along (axes >> 4) & 3. */
+typedef struct rb_debug_sphere_node {
+    float cx[4], cy[4], cz[4], hx[4], hy[4], hz[4];
+    uint32_t ref[4];
+    uint32_t axes;
+    uint32_t _pad[3];
+} rb_debug_sphere_node;
+/* Host only, no device: the host builder's triangle tree (fast_bvh_build) for this mesh and this caller tree.  Two calls:
+ * with every out array NULL, counts3 = {nodes, slots (valid slots, in leaf order), slot_meta words (2 per index slot)} --
+ * all 0 when this tree is left to another walk; then with arrays of at least those sizes.  root_depth = {root reference,
+ * depth: the stack entries the walk is given}, bounds6 = the mesh bounds {min xyz, max xyz}.  slot_meta[2 * slot] is the
+ * caller's leaf of the slot (0xFFFFFFFF: not a valid slot), slot_meta[2 * slot + 1] its rank, bit 31 = "large" triangle. */
+int rb_debug_own_tree(const rb_gpu_triangle* tris, size_t n_tris, const rb_bvh_node* nodes, size_t n_nodes, const uint32_t* indices,
+                      size_t n_indices, rb_debug_own_node* nodes_out, size_t nodes_capacity, uint32_t* slots_out, size_t slots_capacity,
+                      uint32_t* slot_meta_out, size_t slot_meta_capacity, uint64_t counts3[3], uint32_t root_depth[2], float bounds6[6]);
+/* The same arrays of the tree an engine walks, read back from the device whichever builder made them (after the first
+ * rb_dispatch / rb_render that follows an update; a group handle answers with its first part).  The device builders leave
+ * the nodes they collapsed into two-triangle leaves unreferenced and unwritten.  counts3 = {0, 0, 0}: no such tree. */
+int rb_debug_engine_own_tree(rb_engine* e, rb_debug_own_node* nodes_out, size_t nodes_capacity, uint32_t* slots_out, size_t slots_capacity,
+                             uint32_t* slot_meta_out, size_t slot_meta_capacity, uint64_t counts3[3], uint32_t root_depth[2], float bounds6[6]);
+/* Host only, no device: the host builder's sphere tree (sphere_bvh_build) over n spheres.  Two calls as above: counts2 =
+ * {nodes, spheres}; leaf_out takes 4 floats per sphere ({centre, radius} in leaf order), id_out the original index of each;
+ * root_depth = {root reference, depth: stack entries = 3 per level of nodes}. */
+int rb_debug_sphere_tree(const rb_sphere* spheres, size_t n, rb_debug_sphere_node* nodes_out, size_t nodes_capacity, float* leaf_out,
+                         uint32_t* id_out, size_t spheres_capacity, uint64_t counts2[2], uint32_t root_depth[2]);
+/* The same arrays of the sphere tree an engine walks (more than 64 spheres), read back from the device.  counts2 = {0, 0}:
+ * the engine scans its spheres. */
+int rb_debug_engine_sphere_tree(rb_engine* e, rb_debug_sphere_node* nodes_out, size_t nodes_capacity, float* leaf_out, uint32_t* id_out,
+                                size_t spheres_capacity, uint64_t counts2[2], uint32_t root_depth[2]);
 /* Which builder produced the chunked walk's tree: "device", "host", or "" when the engine walks another way.  Valid after the
  * first rb_dispatch / rb_render that follows an update; `build_ms`, if not NULL, receives the wall time of that build with
  * its uploads and the gather of the chunks' triangle records. */

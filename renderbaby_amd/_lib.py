@@ -121,6 +121,10 @@ SIGNATURES = {
     "rb_sphere_tree_builder": (C.c_char_p, [vp, vp]),
     "rb_chunk_tree_builder": (C.c_char_p, [vp, vp]),
     "rb_debug_engine_chunk_tree": (i32, [vp, vp]),
+    "rb_debug_own_tree": (i32, [vp, sz, vp, sz, vp, sz, vp, sz, vp, sz, vp, sz, vp, vp, vp]),
+    "rb_debug_engine_own_tree": (i32, [vp, vp, sz, vp, sz, vp, sz, vp, vp, vp]),
+    "rb_debug_sphere_tree": (i32, [vp, sz, vp, sz, vp, vp, sz, vp, vp]),
+    "rb_debug_engine_sphere_tree": (i32, [vp, vp, sz, vp, vp, sz, vp, vp]),
     "rb_version": (C.c_char_p, []),
     "rb_device_name": (i32, [i32, C.c_char_p, sz]),
 }

@@ -94,6 +94,11 @@ MASK_GROUND, MASK_TRIANGLES, MASK_SPHERES, MASK_LIGHTS, MASK_ALL = 1, 2, 4, 8, 1
 GUIDE = np.dtype([("normal", f4, (3,)), ("t", f4), ("pos", f4, (3,)), ("cls", u4), ("albedo", f4, (3,)), ("_pad", f4)])
 DENOISE_PARAMS = np.dtype([("iterations", u4), ("normal_power_log2", u4), ("sigma_depth", f4), ("sigma_color", f4),
                            ("albedo_floor", f4), ("flags", u4), ("_reserved", u4, (2,))])
+# test aids (rb_debug_*own_tree / rb_debug_*sphere_tree): a node of the library's own triangle tree and of its sphere tree
+OWN_NODE = np.dtype([("lmin", f4, (3,)), ("left", u4), ("lmax", f4, (3,)), ("right", u4),
+                     ("rmin", f4, (3,)), ("left_fa", f4), ("rmax", f4, (3,)), ("right_fa", f4)])
+SPHERE_NODE = np.dtype([("cx", f4, (4,)), ("cy", f4, (4,)), ("cz", f4, (4,)), ("hx", f4, (4,)), ("hy", f4, (4,)), ("hz", f4, (4,)),
+                        ("ref", u4, (4,)), ("axes", u4), ("_pad", u4, (3,))])
 
 SIZES = {"camera": (CAMERA, 48), "uniforms": (UNIFORMS, 144), "material": (MATERIAL, 80),
          "sphere": (SPHERE, 96), "point_light": (POINT_LIGHT, 96), "mesh": (MESH, 96),
@@ -103,7 +108,8 @@ SIZES = {"camera": (CAMERA, 48), "uniforms": (UNIFORMS, 144), "material": (MATER
          "surfel": (SURFEL, 32), "hemi_params": (HEMI_PARAMS, 32), "openness": (OPENNESS, 8),
          "lightmap_params": (LIGHTMAP_PARAMS, 32), "probe": (PROBE, 16), "sh9": (SH9, 112),
          "probe_grid": (PROBE_GRID, 48), "lit": (LIT, 16),
-         "probe_depth": (PROBE_DEPTH, 1024), "light_visibility": (LIGHT_VISIBILITY, 16)}
+         "probe_depth": (PROBE_DEPTH, 1024), "light_visibility": (LIGHT_VISIBILITY, 16),
+         "own_node": (OWN_NODE, 64), "sphere_node": (SPHERE_NODE, 128)}
 for _n, (_dt, _sz) in SIZES.items():
     assert _dt.itemsize == _sz, (_n, _dt.itemsize, _sz)
 

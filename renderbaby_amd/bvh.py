@@ -54,6 +54,56 @@ def build_device(tris, device=-1):
     return _two_call(load().rb_bvh_build_device, (int(device),), tris)
 
 
+def own_tree_readback(check, fn, *prefix):
+    """The two calls of rb_debug_own_tree / rb_debug_engine_own_tree (`prefix`: the arguments before the out arrays): dict of
+    nodes (abi.OWN_NODE[]), slots, slot_meta, root, depth, bmin, bmax -- or None when there is no such tree."""
+    counts, rd, b6 = (C.c_uint64 * 3)(), (C.c_uint32 * 2)(), (C.c_float * 6)()
+    check(fn(*prefix, None, 0, None, 0, None, 0, counts, rd, b6))
+    if not counts[1]:
+        return None
+    nodes = np.zeros(counts[0], dtype=abi.OWN_NODE)
+    slots, meta = np.zeros(counts[1], dtype=np.uint32), np.zeros(counts[2], dtype=np.uint32)
+    check(fn(*prefix, nodes.ctypes.data, len(nodes), slots.ctypes.data, len(slots), meta.ctypes.data, len(meta), counts, rd, b6))
+    assert (counts[0], counts[1], counts[2]) == (len(nodes), len(slots), len(meta)), "the tree changed between the two calls"
+    b = np.array(list(b6), dtype=np.float32)
+    return dict(nodes=nodes, slots=slots, slot_meta=meta, root=int(rd[0]), depth=int(rd[1]), bmin=b[:3], bmax=b[3:])
+
+
+def sphere_tree_readback(check, fn, *prefix):
+    """The two calls of rb_debug_sphere_tree / rb_debug_engine_sphere_tree: dict of nodes (abi.SPHERE_NODE[]), leaf
+    (float32[n, 4]: centre, radius in leaf order), ids, root, depth (stack entries) -- or None when there is no tree."""
+    counts, rd = (C.c_uint64 * 2)(), (C.c_uint32 * 2)()
+    check(fn(*prefix, None, 0, None, None, 0, counts, rd))
+    if not counts[1]:
+        return None
+    nodes = np.zeros(counts[0], dtype=abi.SPHERE_NODE)
+    leaf, ids = np.zeros((counts[1], 4), dtype=np.float32), np.zeros(counts[1], dtype=np.uint32)
+    check(fn(*prefix, nodes.ctypes.data, len(nodes), leaf.ctypes.data, ids.ctypes.data, len(ids), counts, rd))
+    assert (counts[0], counts[1]) == (len(nodes), len(ids)), "the tree changed between the two calls"
+    return dict(nodes=nodes, leaf=leaf, ids=ids, root=int(rd[0]), depth=int(rd[1]))
+
+
+def _check_global(rc):
+    from .engine import RenderError
+    if rc:
+        raise RenderError(rc, (load().rb_last_error(None) or b"").decode())
+
+
+def debug_own_tree(tris, nodes, indices):
+    """Test aid, host only (rb_debug_own_tree): the host builder's own triangle tree over this mesh and caller tree, unchecked."""
+    tris = np.ascontiguousarray(tris, dtype=abi.GPU_TRIANGLE)
+    nodes = np.ascontiguousarray(nodes, dtype=abi.BVH_NODE)
+    indices = np.ascontiguousarray(indices, dtype=np.uint32)
+    return own_tree_readback(_check_global, load().rb_debug_own_tree, tris.ctypes.data, len(tris), nodes.ctypes.data, len(nodes),
+                             indices.ctypes.data, len(indices))
+
+
+def debug_sphere_tree(spheres):
+    """Test aid, host only (rb_debug_sphere_tree): the host builder's sphere tree over abi.SPHERE[], unchecked."""
+    spheres = np.ascontiguousarray(spheres, dtype=abi.SPHERE)
+    return sphere_tree_readback(_check_global, load().rb_debug_sphere_tree, spheres.ctypes.data, len(spheres))
+
+
 def node_count(n_tris):
     """Nodes of the reference-layout tree over n_tris triangles (follows from the count alone; touches no device)."""
     lib = load()

@@ -2,6 +2,7 @@
 // chunked walk's tree and the library's own triangle tree.  Each has one build function, one build record and its own KParams
 // fields.  Which mesh walks an engine may build follows from its options (mesh_walks); which builder runs, from device_builder.
 #include <chrono>
+#include <cstddef>
 #include <cstring>
 
 #include "rb_engine.hpp"
@@ -110,6 +111,47 @@ int check_and_count(const rb_engine* e, const char* what, const ChunkTree& t, co
     }
     const uint64_t census[6] = {1, t.nodes.size(), t.pos_slot.size(), t.depth, chunks, unbounded};
     std::copy(census, census + 6, out6);
+    return RB_OK;
+}
+
+// rb_debug_*own_tree / rb_debug_*sphere_tree: the header words of a tree and the capacity checks, before anything is copied.
+// The ABI's node records are the library's own, field for field.
+static_assert(sizeof(rb_debug_own_node) == sizeof(SphereNode) && offsetof(rb_debug_own_node, left_fa) == offsetof(SphereNode, _pad0) &&
+              offsetof(rb_debug_own_node, right_fa) == offsetof(SphereNode, _pad1), "rb_debug_own_node is SphereNode");
+static_assert(sizeof(rb_debug_sphere_node) == sizeof(SphereNode4) && offsetof(rb_debug_sphere_node, ref) == offsetof(SphereNode4, ref) &&
+              offsetof(rb_debug_sphere_node, axes) == offsetof(SphereNode4, axes), "rb_debug_sphere_node is SphereNode4");
+struct OwnTreeCopy {
+    size_t n_nodes = 0, n_slots = 0, n_meta = 0;
+    uint32_t root = 0, depth = 0;
+    const float *bmin = nullptr, *bmax = nullptr;
+};
+int own_tree_header(const rb_engine* e, const OwnTreeCopy& c, const void* nodes_out, size_t nodes_capacity, const void* slots_out,
+                    size_t slots_capacity, const void* slot_meta_out, size_t slot_meta_capacity, uint64_t counts3[3], uint32_t root_depth[2],
+                    float bounds6[6]) {
+    counts3[0] = c.n_nodes;
+    counts3[1] = c.n_slots;
+    counts3[2] = c.n_meta;
+    root_depth[0] = c.root;
+    root_depth[1] = c.depth;
+    for (int a = 0; a < 3; ++a) {
+        bounds6[a] = c.bmin ? c.bmin[a] : 0.0f;
+        bounds6[3 + a] = c.bmax ? c.bmax[a] : 0.0f;
+    }
+    if (nodes_out && nodes_capacity < c.n_nodes) return fail(e, RB_ERR_INVALID_BVH, "nodes_out holds %zu of %zu nodes", nodes_capacity, c.n_nodes);
+    if (slots_out && slots_capacity < c.n_slots) return fail(e, RB_ERR_INVALID_BVH, "slots_out holds %zu of %zu slots", slots_capacity, c.n_slots);
+    if (slot_meta_out && slot_meta_capacity < c.n_meta)
+        return fail(e, RB_ERR_INVALID_BVH, "slot_meta_out holds %zu of %zu words", slot_meta_capacity, c.n_meta);
+    return RB_OK;
+}
+int sphere_tree_header(const rb_engine* e, size_t n_nodes, size_t n, uint32_t root, uint32_t depth, const void* nodes_out, size_t nodes_capacity,
+                       const void* leaf_out, const void* id_out, size_t spheres_capacity, uint64_t counts2[2], uint32_t root_depth[2]) {
+    counts2[0] = n_nodes;
+    counts2[1] = n;
+    root_depth[0] = root;
+    root_depth[1] = depth;
+    if (nodes_out && nodes_capacity < n_nodes) return fail(e, RB_ERR_INVALID_BVH, "nodes_out holds %zu of %zu nodes", nodes_capacity, n_nodes);
+    if ((leaf_out || id_out) && spheres_capacity < n)
+        return fail(e, RB_ERR_INVALID_BVH, "leaf_out / id_out hold %zu of %zu spheres", spheres_capacity, n);
     return RB_OK;
 }
 
@@ -477,6 +519,84 @@ int rb_debug_engine_chunk_tree(rb_engine* e, uint64_t out6[6]) {
     const uint32_t n_tris = std::min<uint32_t>(e->prep_tri_count, static_cast<uint32_t>(e->host_tris.size()));
     const std::string what = std::string("chunk tree (") + c.rec.builder + " builder)";
     return rb::check_and_count(e, what.c_str(), t, e->host_tris.data(), n_tris, e->host_indices.data(), static_cast<uint32_t>(e->host_indices.size()), out6);
+}
+
+// Test aids: the library's own triangle tree and the sphere tree, handed out unchecked (tests/_tree_model.py judges them).
+int rb_debug_own_tree(const rb_gpu_triangle* tris, size_t n_tris, const rb_bvh_node* nodes, size_t n_nodes, const uint32_t* indices,
+                      size_t n_indices, rb_debug_own_node* nodes_out, size_t nodes_capacity, uint32_t* slots_out, size_t slots_capacity,
+                      uint32_t* slot_meta_out, size_t slot_meta_capacity, uint64_t counts3[3], uint32_t root_depth[2], float bounds6[6]) {
+    if (!tris || !nodes || !indices || !counts3 || !root_depth || !bounds6) return RB_ERR_NULL_ARGUMENT;
+    if (n_tris >= (1ull << 31) || n_nodes >= (1ull << 31) || n_indices >= (1ull << 31)) return RB_ERR_INVALID_BVH;
+    std::string why;
+    if (!rb::bvh_validate(nodes, static_cast<uint32_t>(n_nodes), rb::kStackDepth, why, nullptr)) return rb::fail(nullptr, RB_ERR_INVALID_BVH, "%s", why.c_str());
+    rb::FastTree ft;
+    const bool built = rb::fast_bvh_build(tris, static_cast<uint32_t>(n_tris), indices, static_cast<uint32_t>(n_indices), nodes,
+                                          static_cast<uint32_t>(n_nodes), rb::kStackDepth, ft);
+    rb::OwnTreeCopy c;
+    if (built) c = {ft.nodes.size(), ft.slots.size(), ft.slot_meta.size(), ft.root, ft.depth, ft.bmin, ft.bmax};
+    if (const int rc = rb::own_tree_header(nullptr, c, nodes_out, nodes_capacity, slots_out, slots_capacity, slot_meta_out, slot_meta_capacity,
+                                           counts3, root_depth, bounds6))
+        return rc;
+    if (nodes_out && c.n_nodes) std::memcpy(nodes_out, ft.nodes.data(), sizeof(rb::SphereNode) * c.n_nodes);
+    if (slots_out && c.n_slots) std::memcpy(slots_out, ft.slots.data(), 4u * c.n_slots);
+    if (slot_meta_out && c.n_meta) std::memcpy(slot_meta_out, ft.slot_meta.data(), 4u * c.n_meta);
+    return RB_OK;
+}
+
+int rb_debug_engine_own_tree(rb_engine* e, rb_debug_own_node* nodes_out, size_t nodes_capacity, uint32_t* slots_out, size_t slots_capacity,
+                             uint32_t* slot_meta_out, size_t slot_meta_capacity, uint64_t counts3[3], uint32_t root_depth[2], float bounds6[6]) {
+    if (!e || !counts3 || !root_depth || !bounds6) return RB_ERR_NULL_ARGUMENT;
+    if (rb::is_group(e)) e = e->parts[0].get();
+    std::lock_guard<std::mutex> lock(e->mu);
+    rb::set_device(e);
+    const rb::OwnAccel& o = e->own;
+    rb::OwnTreeCopy c;
+    if (o.rec.built()) c = {o.nodes.count, o.slots.count, o.slot_meta.count, o.info.root, o.info.depth, o.info.bmin, o.info.bmax};
+    if (const int rc = rb::own_tree_header(e, c, nodes_out, nodes_capacity, slots_out, slots_capacity, slot_meta_out, slot_meta_capacity,
+                                           counts3, root_depth, bounds6))
+        return rc;
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    if (nodes_out && c.n_nodes) HIP_TRY(e, hipMemcpy(nodes_out, o.nodes.ptr, sizeof(rb::SphereNode) * c.n_nodes, hipMemcpyDeviceToHost));
+    if (slots_out && c.n_slots) HIP_TRY(e, hipMemcpy(slots_out, o.slots.ptr, 4u * c.n_slots, hipMemcpyDeviceToHost));
+    if (slot_meta_out && c.n_meta) HIP_TRY(e, hipMemcpy(slot_meta_out, o.slot_meta.ptr, 4u * c.n_meta, hipMemcpyDeviceToHost));
+    return RB_OK;
+}
+
+int rb_debug_sphere_tree(const rb_sphere* spheres, size_t n, rb_debug_sphere_node* nodes_out, size_t nodes_capacity, float* leaf_out,
+                         uint32_t* id_out, size_t spheres_capacity, uint64_t counts2[2], uint32_t root_depth[2]) {
+    if (!spheres || !counts2 || !root_depth) return RB_ERR_NULL_ARGUMENT;
+    if (n == 0 || n >= (1u << 27)) return rb::fail(nullptr, RB_ERR_INVALID_BVH, "a sphere tree takes 1 to 2^27 - 1 spheres");
+    std::vector<rb::SphereNode4> nodes;
+    std::vector<uint32_t> order;
+    uint32_t root = 0, levels4 = 0;
+    rb::sphere_bvh_build(spheres, n, nodes, order, &root, &levels4);
+    if (const int rc = rb::sphere_tree_header(nullptr, nodes.size(), n, root, rb::sphere_stack_entries(levels4), nodes_out, nodes_capacity,
+                                              leaf_out, id_out, spheres_capacity, counts2, root_depth))
+        return rc;
+    if (nodes_out && !nodes.empty()) std::memcpy(nodes_out, nodes.data(), sizeof(rb::SphereNode4) * nodes.size());
+    if (id_out) std::memcpy(id_out, order.data(), 4u * n);
+    if (leaf_out)   // {centre, radius} = the first 16 bytes of an rb_sphere, as build_sphere_bvh uploads them
+        for (size_t j = 0; j < n; ++j) std::memcpy(&leaf_out[j * 4], &spheres[order[j]], 4 * sizeof(float));
+    return RB_OK;
+}
+
+int rb_debug_engine_sphere_tree(rb_engine* e, rb_debug_sphere_node* nodes_out, size_t nodes_capacity, float* leaf_out, uint32_t* id_out,
+                                size_t spheres_capacity, uint64_t counts2[2], uint32_t root_depth[2]) {
+    if (!e || !counts2 || !root_depth) return RB_ERR_NULL_ARGUMENT;
+    if (rb::is_group(e)) e = e->parts[0].get();
+    std::lock_guard<std::mutex> lock(e->mu);
+    rb::set_device(e);
+    const rb::SphereAccel& s = e->sph;
+    const bool built = s.rec.built();
+    const size_t nn = built ? s.nodes.count : 0, n = built ? s.id.count : 0;
+    if (const int rc = rb::sphere_tree_header(e, nn, n, built ? s.root : 0u, built ? s.depth : 0u, nodes_out, nodes_capacity, leaf_out, id_out,
+                                              spheres_capacity, counts2, root_depth))
+        return rc;
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    if (nodes_out && nn) HIP_TRY(e, hipMemcpy(nodes_out, s.nodes.ptr, sizeof(rb::SphereNode4) * nn, hipMemcpyDeviceToHost));
+    if (leaf_out && n) HIP_TRY(e, hipMemcpy(leaf_out, s.leaf.ptr, 16u * n, hipMemcpyDeviceToHost));
+    if (id_out && n) HIP_TRY(e, hipMemcpy(id_out, s.id.ptr, 4u * n, hipMemcpyDeviceToHost));
+    return RB_OK;
 }
 
 }  // extern "C"

@@ -77,8 +77,10 @@ __global__ void __launch_bounds__(256) k_lbvh_prims(const rb_gpu_triangle* __res
         const double nn = sqrt(nx * nx + ny * ny + nz * nz), ll = fmax(l1, l2);
         const bool large = (slot_meta[(size_t)slots[i] * 2u + 1u] & kSlotLarge) != 0u;
         float q = inf;
-        if (!large) q = static_cast<float>(ll * 1e6 * (1.0 + 1e-5) * (1.0 + 1e-6));
-        else if (nn > 0.0 && nn < 1e300) q = static_cast<float>(ll / nn / (0.95 * double(kFastGrazeCos)) * (1.0 + 1e-5));
+        // (converted as the host's tri_bound_hd converts them: never below the bound, rb_chunk_math.hpp f32_not_below)
+        const double cap = ll * 1e6 * (1.0 + 1e-5), graze = ll / nn / (0.95 * double(kFastGrazeCos));
+        if (!large) q = chunkmath::f32_not_below(cap * (1.0 + 1e-6), cap);
+        else if (nn > 0.0 && nn < 1e300) q = chunkmath::f32_not_below(graze * (1.0 + 1e-5), graze * (1.0 + 1e-6));
         pmin[i] = make_float4(mn[0], mn[1], mn[2], q);
         pmax[i] = make_float4(mx[0], mx[1], mx[2], 0.0f);
     }

@@ -19,6 +19,21 @@ RB_HD inline double dmax(double a, double b) { return a > b ? a : b; }
 constexpr float kBig = 3.402823466e38f;   // boxes start at +-inf in the host builder; +-FLT_MAX would do, inf is kept
 RB_HD inline float f_inf() { return __builtin_huge_valf(); }
 
+// v >= floor >= 0 as an f32 that is not below `floor`.  v is a bound with its outward factor, floor the bound with a smaller one:
+// in f32's normal range the factors between them (1e-6 and up) exceed the half ulp a conversion to nearest can lose, and this
+// is the plain conversion.  Where f32 is subnormal or underflows (edges below ~1e-23) they do not, and FA must never be under the
+// F_k it stands for: one step up there.
+RB_HD inline float f32_not_below(double v, double floor) {
+    float f = static_cast<float>(v);
+    if (double(f) < floor) {
+        uint32_t b;
+        __builtin_memcpy(&b, &f, 4);
+        ++b;   // f >= 0 and finite here: the next f32 up (0 -> the smallest subnormal, FLT_MAX -> +inf)
+        __builtin_memcpy(&f, &b, 4);
+    }
+    return f;
+}
+
 // F_k of one triangle and whether it is "large" (see the comment above FBuilder in rb_bvh.cpp), from the f32 edges the
 // kernels use (k_prep_tris subtracts in f32, so do these).
 RB_HD inline TriBound tri_bound_hd(const float v0[3], const float v1[3], const float v2[3], float small_cap) {
@@ -38,8 +53,9 @@ RB_HD inline TriBound tri_bound_hd(const float v0[3], const float v1[3], const f
         b.n[0] = nx / nn; b.n[1] = ny / nn; b.n[2] = nz / nn;
     }
     b.large = !(cap <= double(small_cap));
-    if (!b.large) b.f = static_cast<float>(cap * (1.0 + 1e-6));
-    else if (b.has_normal) b.f = static_cast<float>(ll / nn / (0.95 * double(kFastGrazeCos)) * (1.0 + 1e-5));   // 0.95: |a^| >= 0.95 |a| in the bound's range
+    const double graze = ll / nn / (0.95 * double(kFastGrazeCos));   // 0.95: |a^| >= 0.95 |a| in the bound's range
+    if (!b.large) b.f = f32_not_below(cap * (1.0 + 1e-6), cap);
+    else if (b.has_normal) b.f = f32_not_below(graze * (1.0 + 1e-5), graze * (1.0 + 1e-6));
     else b.f = f_inf();
     return b;
 }

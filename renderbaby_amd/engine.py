@@ -20,6 +20,7 @@ import numpy as np
 
 from . import abi
 from ._lib import load
+from .bvh import own_tree_readback, sphere_tree_readback
 from ._marshal import (SEEDS, Form, device_new, device_tensor, download, grid_records, host_out, host_ptr, is_tensor, probe_records,
                        ray_records, surfel_records, torch_device)
 
@@ -811,6 +812,16 @@ class Engine:
         if not out[0]:
             return None
         return dict(nodes=out[1], positions=out[2], depth=out[3], chunks=out[4], unbounded=out[5])
+
+    def debug_own_tree(self):
+        """The library's own triangle tree as the engine walks it, read back unchecked (rb_debug_engine_own_tree): dict of
+        nodes (abi.OWN_NODE[]), slots, slot_meta, root, depth, bmin, bmax -- or None when the engine has no such tree."""
+        return own_tree_readback(self._check, self._lib.rb_debug_engine_own_tree, self._h)
+
+    def debug_sphere_tree(self):
+        """The sphere tree as the engine walks it, read back unchecked (rb_debug_engine_sphere_tree): dict of nodes
+        (abi.SPHERE_NODE[]), leaf (float32[n, 4]), ids, root, depth (stack entries) -- or None when the engine scans."""
+        return sphere_tree_readback(self._check, self._lib.rb_debug_engine_sphere_tree, self._h)
 
     def last_dispatch_ms(self):
         return self._last_ms(self._lib.rb_last_dispatch_ms)

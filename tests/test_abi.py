@@ -87,6 +87,13 @@ def test_entry_points_reject_a_null_engine_without_touching_the_gpu():
     assert (lib.rb_sphere_tree_builder(null, C.byref(ms)) or b"") == b"" and ms.value == 0.0
     assert (lib.rb_chunk_tree_builder(null, C.byref(ms)) or b"") == b"" and ms.value == 0.0
     assert lib.rb_debug_engine_chunk_tree(null, None) != 0
+    c3, c2, rd, b6 = (C.c_uint64 * 3)(), (C.c_uint64 * 2)(), (C.c_uint32 * 2)(), (C.c_float * 6)()
+    assert lib.rb_debug_engine_own_tree(null, None, 0, None, 0, None, 0, c3, rd, b6) == 15       # RB_ERR_NULL_ARGUMENT
+    assert lib.rb_debug_engine_sphere_tree(null, None, 0, None, None, 0, c2, rd) == 15
+    assert lib.rb_debug_own_tree(None, 0, None, 0, None, 0, None, 0, None, 0, None, 0, c3, rd, b6) == 15
+    assert lib.rb_debug_own_tree(buf, 0, buf, 0, buf, 0, None, 0, None, 0, None, 0, None, rd, b6) == 15
+    assert lib.rb_debug_sphere_tree(None, 1, None, 0, None, None, 0, c2, rd) == 15
+    assert lib.rb_debug_sphere_tree(buf, 1, None, 0, None, None, 0, None, rd) == 15
     assert lib.rb_reserve(null, 1) != 0
     assert lib.rb_debug_walk_profile(None, 0) != 0
     lib.rb_iter_destroy(null)
