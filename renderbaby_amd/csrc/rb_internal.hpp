@@ -557,17 +557,10 @@ int launch_chunk_gather(const PrepTri* ptris, const uint32_t* pos_slot, const ui
 int launch_deinterleave(const uint32_t* gathered, uint32_t* frame, uint32_t width, uint32_t height, uint32_t padded_rows,
                         uint32_t stripe_rows, uint32_t shard_count, void* stream);
 size_t max_dynamic_lds(int device);   // hipDeviceAttributeMaxSharedMemoryPerBlock
-int launch_div_exhaustive(uint32_t b_begin, uint32_t b_count, uint32_t ea, uint32_t eb, uint32_t a_begin,
-                          uint32_t a_count, unsigned long long* mismatch16, void* stream);
-int launch_rcp_exhaustive(uint32_t expo, uint32_t* mismatch16, void* stream);
-int launch_rcp_det_exhaustive(uint32_t expo, uint32_t* mismatch16, void* stream);
-int launch_rnd_pm1_exhaustive(uint32_t* mismatch16, void* stream);
-int launch_triangle_trip(uint32_t n, uint32_t seed, uint32_t* mismatch32, void* stream);   // k_trace's triangle trip against accept_slot<true>
-bool measure_salu_mix(uint32_t scalar_per_16, bool branch, uint32_t rounds, double out[3]);   // clocks per vector instruction with scalar ones among them
-int launch_debug_math(const float* a, const float* b, float* out, uint32_t n, void* stream);
 int debug_walk_profile(unsigned long long* out64, int reset);   // pass occupancy counters of a profiling build, tools/ablate/rb_profile.patch (-1 otherwise)
-double measure_l1_gather(size_t table_bytes, uint32_t rounds);   // divergent 16-byte gathers from an L2-resident table: lane accesses / s
 int device_cu_count(int device);
+uint32_t device_cu_count_cached();   // of the current device; asked once per device
 uint32_t stream_kernel_max_threads(uint32_t blocks_per_cu);  // upper bound of grid * block of the stream kernels
+// (the test hooks and measurement kernels -- rb_debug_*, rb_measure_* -- are whole in rb_debug.hip: kernel, launch and entry point)
 
 }  // namespace rb

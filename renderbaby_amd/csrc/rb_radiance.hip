@@ -15,6 +15,7 @@
 // Each body is a template on where a path starts: k_rad* start on the caller's ray (RayStart), k_cam* on the record the camera
 // generator made for the item (CamStart; rb_camera.hip) -- the same queue, walks and sum behind both.
 #include "rb_device_chunk.hpp"
+#include "rb_launch_plan.hpp"
 
 #pragma clang fp contract(off)
 
@@ -561,25 +562,15 @@ int launch_radiance(const KParams& p_, const RadArgs& a_, void* stream_, LaunchI
     static const char* const names[2][3] = {{"k_rad", "k_rad_bvh", "k_rad_chunk"}, {"k_cam", "k_cam_bvh", "k_cam_chunk"}};
     li.kernel_name = names[records ? 1 : 0][v];
     li.lds_bytes = (size_t)kStackEntryBytes * p.stack_depth * kRadBlock + (v == kWalkChunk ? (kRadBlock / 64u) * kChunkWaveLds : 0u);
-    // the grid as launch_render sizes it: residency by registers, fewer blocks for a launch of few items
-    const uint32_t max_blocks8 = stream_kernel_max_threads(8u) / 256u;   // 8 blocks per CU
-    const uint32_t dense = (items >= (uint64_t)max_blocks8 * 4u * 1024u) ? 8u : 4u;
-    const uint32_t blocks_per_cu = p.blocks_per_cu ? p.blocks_per_cu : v == kWalkChunk ? (uint32_t)RB_RAD_CHUNK_WAVES : dense;
-    uint64_t grid = (uint64_t)(max_blocks8 / 8u) * blocks_per_cu;
-    const uint64_t needed = (items + kRadBlock - 1u) / kRadBlock;
-    if (needed < grid) grid = needed;
-    li.grid = (uint32_t)grid;
-    const uint64_t waves = grid * (kRadBlock / 64u);
-    // reservations as launch_render makes them: about 8 (the plain kernel) or 64 per wave, whole 64-item rows
-    uint64_t batch = items / (waves * (v == kWalkPlain ? 8u : 64u));
-    batch = (batch / 64u) * 64u;
-    if (batch < 64u) batch = 64u;
-    if (batch > (v == kWalkPlain ? 512u : 4096u)) batch = (v == kWalkPlain ? 512u : 4096u);
-    if (p.queue_batch) batch = p.queue_batch;
-    a.batch = (uint32_t)batch;
-    a.magic_S = a.samples > 1u ? (uint32_t)((1ull << 32) / a.samples) : 0xFFFFFFFFu;
+    // grid and reservations by the trace launch's rules (rb_launch_plan.hpp): residency by registers, fewer blocks for a launch of few items
+    const uint32_t cus = device_cu_count_cached();
+    const uint32_t blocks_per_cu = p.blocks_per_cu ? p.blocks_per_cu : v == kWalkChunk ? (uint32_t)RB_RAD_CHUNK_WAVES : dense_blocks_per_cu(items, cus);
+    li.grid = persistent_blocks(items, kRadBlock, cus, blocks_per_cu);
+    const uint64_t waves = (uint64_t)li.grid * (kRadBlock / 64u);
+    a.batch = p.queue_batch ? p.queue_batch : (uint32_t)reservation(items, waves, v == kWalkPlain);
+    a.magic_S = magic_of(a.samples);
     // the queue starts behind the waves' own first reservations
-    hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(a.queue), (int)(uint32_t)(waves * batch), 1, stream);
+    hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(a.queue), (int)(uint32_t)(waves * a.batch), 1, stream);
     if (e != hipSuccess) return (int)e;
     const dim3 g(li.grid), b(li.block);
     const bool sph = p.sph_nodes != nullptr;

@@ -1513,121 +1513,11 @@ int rb_device_name(int device, char* buf, size_t buf_len) {
     return RB_OK;
 }
 
-// Test hook: exhaustive device check of the fast reciprocal (all 2^23 significands, both signs)
-// at one biased exponent.  out16[0] = number of mismatches, out16[1..15] = offending bit patterns.
-int rb_debug_rcp_exhaustive(uint32_t biased_exponent, uint32_t* out16) {
-    if (!out16) return RB_ERR_NULL_ARGUMENT;
-    uint32_t* d = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&d), 64) != hipSuccess) return RB_ERR_DEVICE;
-    (void)hipMemset(d, 0, 64);
-    int rc = rb::launch_rcp_exhaustive(biased_exponent, d, nullptr);
-    hipError_t st = hipDeviceSynchronize();
-    (void)hipMemcpy(out16, d, 64, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    return (rc || st != hipSuccess) ? RB_ERR_DEVICE : RB_OK;
-}
-
-// Test hook: the same sweep for rcp_det, the reciprocal of the single-node walk's triangle test, guard included: every
-// significand and both signs at one biased exponent against `1.0f / x`, bit patterns compared (a NaN equals a NaN).
-int rb_debug_rcp_det_exhaustive(uint32_t biased_exponent, uint32_t* out16) {
-    if (!out16) return RB_ERR_NULL_ARGUMENT;
-    if (biased_exponent > 255u) return RB_ERR_INVALID_OPTIONS;
-    uint32_t* d = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&d), 64) != hipSuccess) return RB_ERR_DEVICE;
-    (void)hipMemset(d, 0, 64);
-    int rc = rb::launch_rcp_det_exhaustive(biased_exponent, d, nullptr);
-    hipError_t st = hipDeviceSynchronize();
-    (void)hipMemcpy(out16, d, 64, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    return (rc || st != hipSuccess) ? RB_ERR_DEVICE : RB_OK;
-}
-
-// Test hook: the triangle trip of k_trace / k_trace_direct against the form the other kernels keep (accept_slot<true>) on n
-// seeded (ray, triangle, incoming hit) triples and the constructed edge cases behind them (k_triangle_trip).
-// out32[0] = number of triples whose {t, u, v, slot} differ in any bit, out32[1] = the index of one, out32[2..17] its
-// o, d, v0, edge1, edge2 and incoming hit.t, out32[18..21] the trip's {t, u, v, slot}, out32[22..25] accept_slot's.
-int rb_debug_triangle_trip(uint32_t n, uint32_t seed, uint32_t* out32) {
-    if (!out32) return RB_ERR_NULL_ARGUMENT;
-    if (n > (1u << 26)) return RB_ERR_INVALID_OPTIONS;
-    uint32_t* d = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&d), 128) != hipSuccess) return RB_ERR_DEVICE;
-    (void)hipMemset(d, 0, 128);
-    int rc = rb::launch_triangle_trip(n, seed, d, nullptr);
-    hipError_t st = hipDeviceSynchronize();
-    (void)hipMemcpy(out32, d, 128, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    return (rc || st != hipSuccess) ? RB_ERR_DEVICE : RB_OK;
-}
-
-// Measurement aid (tools/salu_mix.py): what a vector instruction costs with scalar ones among them (k_salu_mix).
-int rb_measure_salu_mix(int32_t device, uint32_t scalar_per_16, uint32_t branch, double* out3) {
-    if (!out3) return RB_ERR_NULL_ARGUMENT;
-    if (scalar_per_16 > 16u || (scalar_per_16 & 3u) != 0u) return RB_ERR_INVALID_OPTIONS;
-    int before = -1;
-    if (device >= 0 && (hipGetDevice(&before) != hipSuccess || hipSetDevice(device) != hipSuccess)) return RB_ERR_DEVICE;
-    const bool ok = rb::measure_salu_mix(scalar_per_16, branch != 0u, 4096u, out3);
-    if (before >= 0) (void)hipSetDevice(before);   // the caller's device is current again
-    return ok ? RB_OK : RB_ERR_DEVICE;
-}
-
-// Test hook: device check of the one-rounding form of `rnd(seed) * 2 - 1` (rnd_pm1) against the three-operation form on all
-// 2^32 seeds.  out16[0] = number of differing seeds, out16[1..15] = some of them.
-int rb_debug_rnd_pm1_exhaustive(uint32_t* out16) {
-    if (!out16) return RB_ERR_NULL_ARGUMENT;
-    uint32_t* d = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&d), 64) != hipSuccess) return RB_ERR_DEVICE;
-    (void)hipMemset(d, 0, 64);
-    int rc = rb::launch_rnd_pm1_exhaustive(d, nullptr);
-    hipError_t st = hipDeviceSynchronize();
-    (void)hipMemcpy(out16, d, 64, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    return (rc || st != hipSuccess) ? RB_ERR_DEVICE : RB_OK;
-}
-
-// Test hook: device check of the fast exact division over denominators [b_begin, b_begin+b_count)
-// x numerators [a_begin, a_begin+a_count) (significands; biased exponents ea / eb).
-// out16[0] = mismatch count, then up to 7 (a, b) bit-pattern pairs.
-int rb_debug_div_exhaustive(uint32_t b_begin, uint32_t b_count, uint32_t ea, uint32_t eb, uint32_t a_begin,
-                            uint32_t a_count, unsigned long long* out16) {
-    if (!out16) return RB_ERR_NULL_ARGUMENT;
-    unsigned long long* d = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&d), 128) != hipSuccess) return RB_ERR_DEVICE;
-    (void)hipMemset(d, 0, 128);
-    int rc = rb::launch_div_exhaustive(b_begin, b_count, ea, eb, a_begin, a_count, d, nullptr);
-    hipError_t st = hipDeviceSynchronize();
-    (void)hipMemcpy(out16, d, 128, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    return (rc || st != hipSuccess) ? RB_ERR_DEVICE : RB_OK;
-}
-
-int rb_measure_l1_gather(int32_t device, uint64_t table_bytes, double* accesses_per_s) {
-    if (!accesses_per_s) return RB_ERR_NULL_ARGUMENT;
-    if (device >= 0 && hipSetDevice(device) != hipSuccess) return RB_ERR_DEVICE;
-    *accesses_per_s = rb::measure_l1_gather(table_bytes ? static_cast<size_t>(table_bytes) : (2u << 20), 512u);
-    return *accesses_per_s > 0.0 ? RB_OK : RB_ERR_DEVICE;
-}
-
 int rb_debug_walk_profile(uint64_t out64[64], int reset) {
     if (!out64) return RB_ERR_NULL_ARGUMENT;
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "counter width");
     if (hipDeviceSynchronize() != hipSuccess) return RB_ERR_DEVICE;
     return rb::debug_walk_profile(reinterpret_cast<unsigned long long*>(out64), reset) == 0 ? RB_OK : RB_ERR_DEVICE;
-}
-
-// Debug hook for tests/test_gpu_parity.py: device /, sqrt, normalize, u32->f32, min/max, dot.
-int rb_debug_math(const float* a, const float* b, float* out8n, uint32_t n) {
-    if (!a || !b || !out8n) return RB_ERR_NULL_ARGUMENT;
-    float *da = nullptr, *db = nullptr, *dout = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&da), n * 4) != hipSuccess) return RB_ERR_DEVICE;
-    if (hipMalloc(reinterpret_cast<void**>(&db), n * 4) != hipSuccess) return RB_ERR_DEVICE;
-    if (hipMalloc(reinterpret_cast<void**>(&dout), static_cast<size_t>(n) * 32) != hipSuccess) return RB_ERR_DEVICE;
-    (void)hipMemcpy(da, a, n * 4, hipMemcpyHostToDevice);
-    (void)hipMemcpy(db, b, n * 4, hipMemcpyHostToDevice);
-    int rc = rb::launch_debug_math(da, db, dout, n, nullptr);
-    hipError_t st = hipDeviceSynchronize();
-    (void)hipMemcpy(out8n, dout, static_cast<size_t>(n) * 32, hipMemcpyDeviceToHost);
-    (void)hipFree(da); (void)hipFree(db); (void)hipFree(dout);
-    return (rc || st != hipSuccess) ? RB_ERR_DEVICE : RB_OK;
 }
 
 }  // extern "C"

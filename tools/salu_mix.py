@@ -1,4 +1,4 @@
-"""What the scalar unit sustains next to the vector units on this device (rb_measure_salu_mix, k_salu_mix in rb_kernels.hip):
+"""What the scalar unit sustains next to the vector units on this device (rb_measure_salu_mix, k_salu_mix in rb_debug.hip):
 a loop of independent v_fma_f32 at 8 waves per SIMD on every CU with 0, 4, 8, 12 or 16 independent scalar adds among each 16 of
 them, without and with one never-taken s_cbranch_execz per 16.  Prints the table DESIGN.md section 9 quotes
 (profiles/rNN_salu_mix.txt): shader clocks per vector instruction and SIMD -- 2 is the vector unit's own limit at one wave64

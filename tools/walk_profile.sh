@@ -11,5 +11,5 @@ cp -r renderbaby_amd/csrc $W/renderbaby_amd/csrc; cp -r include $W/include
 (cd $W && patch -p0 -s < $R/tools/ablate/rb_profile.patch)
 FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -fno-fast-math -fno-slp-vectorize"
 C=$W/renderbaby_amd/csrc
-/opt/rocm/bin/hipcc $FLAGS "$@" -shared -o renderbaby_amd/variants/lib_walkprof.so $C/rb_kernels.hip $C/rb_query.hip $C/rb_denoise.hip $C/rb_radiance.hip $C/rb_camera.hip $C/rb_build.hip $C/rb_runtime.cpp $C/rb_queries.cpp $C/rb_accel.cpp $C/rb_bvh.cpp $C/rb_rccl.cpp -ldl
+/opt/rocm/bin/hipcc $FLAGS "$@" -shared -o renderbaby_amd/variants/lib_walkprof.so $C/rb_kernels.hip $C/rb_debug.hip $C/rb_query.hip $C/rb_denoise.hip $C/rb_radiance.hip $C/rb_camera.hip $C/rb_build.hip $C/rb_runtime.cpp $C/rb_queries.cpp $C/rb_accel.cpp $C/rb_bvh.cpp $C/rb_rccl.cpp -ldl
 echo renderbaby_amd/variants/lib_walkprof.so
