@@ -559,6 +559,14 @@ int rb_debug_rcp_det_exhaustive(uint32_t biased_exponent, uint32_t* out16);
  * in any bit (must be 0), out32[1] = index of one such triple, out32[2..17] = its o, d, v0, edge1, edge2, incoming hit.t,
  * out32[18..21] / out32[22..25] = the two results. */
 int rb_debug_triangle_trip(uint32_t n, uint32_t seed, uint32_t* out32);
+/* Test hook: the normalize of the single-node trace kernels (its general form and the form for the rejection loop's unit
+ * vectors) against v / sqrt(dot(v, v)) with the correctly rounded / and sqrt, bit patterns compared, a NaN equal to a NaN.
+ * xyz = n + n_unit vectors of three floats: the first n go through the general form, the next n_unit through the unit-vector
+ * form (they must be points the rejection loop can accept: coordinates on its grid, 0 < dot < 1); then the unit-vector form
+ * runs on the first try of the loop from each of the seeds seed0 .. seed0 + n_seeds - 1 where that try is accepted.
+ * out16[0..2] = vectors that differ in the three groups (must be 0), out16[3] = accepted tries, out16[4] = 1 + index of one
+ * differing vector (0: none), out16[5..7] = it, out16[8..10] = the form's result, out16[11..13] = the quotient's. */
+int rb_debug_normalize_sites(const float* xyz, uint32_t n, uint32_t n_unit, uint32_t seed0, uint32_t n_seeds, uint32_t* out16);
 /* Measurement aid (tools/salu_mix.py): a loop of independent v_fma_f32 at 8 waves per SIMD on every CU with `scalar_per_16`
  * (0, 4, 8, 12 or 16) independent scalar adds among each 16 of them and, if `branch` is not 0, one never-taken
  * s_cbranch_execz per 16.  out3 = {shader clocks per vector instruction and SIMD, shader clock in GHz, milliseconds}. */

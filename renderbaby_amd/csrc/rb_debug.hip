@@ -1,5 +1,5 @@
 // rb_debug.hip -- the kernels that render nothing: the exhaustive device checks of the exact-arithmetic helpers (rcp_newton,
-// rcp_det, rnd_pm1, div_newton), the triangle trip of k_trace against accept_slot, the device math the parity tests ask for, and
+// rcp_det, rnd_pm1, div_newton, normalize_trim), the triangle trip of k_trace against accept_slot, the device math the parity tests ask for, and
 // the two measurement kernels (k_salu_mix, k_l1_gather) -- each with its launch and its C entry point, so that the hot-path
 // translation unit (rb_kernels.hip) holds the render kernels alone.  They need nothing of the engine.
 //
@@ -53,6 +53,41 @@ __global__ void k_rcp_det_exhaustive(uint32_t expo, uint32_t* mismatch) {
         if (__float_as_uint(want) != __float_as_uint(got) && !(want != want && got != got)) {
             const uint32_t k = atomicAdd(&mismatch[0], 1u);
             if (k < 15u) mismatch[1u + k] = bits;
+        }
+    }
+}
+
+// normalize_trim, both forms (rb_device_math.hpp: what k_trace and k_trace_direct normalize with), against the compiler's
+// v / sqrt(dot(v, v)) with its correctly rounded / and sqrt.  Lanes [0, n): the general form on the caller's vectors.  Lanes
+// [n, n + n_unit): the rejection loop's form on the caller's points, which must be ones the loop can accept.  Lanes behind
+// them: the same form on the first try of random_unit_vector from seed0 + k, where that try is accepted.  A NaN equals a NaN.
+// out[0..2] = differing vectors in the three ranges, out[3] = accepted tries, out[4] = 1 + the lane of one differing vector,
+// out[5..7] = its components, out[8..10] = the form's result, out[11..13] = the compiler's.
+DEV bool same_or_both_nan(float a, float b) { return __float_as_uint(a) == __float_as_uint(b) || (a != a && b != b); }
+__global__ void k_normalize_sites(const float* __restrict__ xyz, uint32_t n, uint32_t n_unit, uint32_t seed0, uint32_t n_seeds, uint32_t* out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n + n_unit + n_seeds) return;
+    f3 v;
+    uint32_t range = 0u;
+    if (i < n + n_unit) {
+        v = mk(xyz[3u * i], xyz[3u * i + 1u], xyz[3u * i + 2u]);
+        range = i < n ? 0u : 1u;
+    } else {
+        uint32_t s = seed0 + (i - n - n_unit);
+        const float x = rnd_pm1(s), y = rnd_pm1(s), z = rnd_pm1(s);
+        v = mk(x, y, z);
+        if (!(dot(v, v) < 1.0f)) return;
+        atomicAdd(&out[3], 1u);
+        range = 2u;
+    }
+    const f3 got = range == 0u ? normalize_trim<false>(v) : normalize_trim<true>(v);
+    const float len = sqrtf(dot(v, v));
+    const f3 want = mk(v.x / len, v.y / len, v.z / len);
+    if (!(same_or_both_nan(got.x, want.x) && same_or_both_nan(got.y, want.y) && same_or_both_nan(got.z, want.z))) {
+        if (atomicAdd(&out[range], 1u) == 0u && atomicExch(&out[4], i + 1u) == 0u) {
+            out[5] = __float_as_uint(v.x), out[6] = __float_as_uint(v.y), out[7] = __float_as_uint(v.z);
+            out[8] = __float_as_uint(got.x), out[9] = __float_as_uint(got.y), out[10] = __float_as_uint(got.z);
+            out[11] = __float_as_uint(want.x), out[12] = __float_as_uint(want.y), out[13] = __float_as_uint(want.z);
         }
     }
 }
@@ -470,6 +505,23 @@ int rb_debug_triangle_trip(uint32_t n, uint32_t seed, uint32_t* out32) {
     return rb::round_trip(out32, 128, 128, [&](uint32_t* d) {
         const uint32_t n_waves = (n + 63u) / 64u, waves = n_waves + rb::kTripCases;
         hipLaunchKernelGGL(rb::k_triangle_trip, dim3((waves + 3u) / 4u), dim3(256), 0, nullptr, n_waves, seed, d);
+    });
+}
+
+// Test hook: the normalize of k_trace / k_trace_direct (normalize_trim, general and unit-vector form) against the compiler's
+// v / sqrt(dot(v, v)) on the caller's vectors and on the accepted first tries of n_seeds seeds (k_normalize_sites).
+int rb_debug_normalize_sites(const float* xyz, uint32_t n, uint32_t n_unit, uint32_t seed0, uint32_t n_seeds, uint32_t* out16) {
+    if (!out16 || (!xyz && n + n_unit != 0u)) return RB_ERR_NULL_ARGUMENT;
+    if (n > (1u << 26) || n_unit > (1u << 26) || n_seeds > (1u << 26)) return RB_ERR_INVALID_OPTIONS;
+    const size_t total = (size_t)n + n_unit + n_seeds, in_bytes = ((size_t)n + n_unit) * 12u;
+    if (total == 0u) {
+        std::fill(out16, out16 + 16, 0u);
+        return RB_OK;
+    }
+    return rb::round_trip(out16, 64, 64 + in_bytes, [&](uint32_t* d) {   // one buffer: the 16 result words, then the vectors
+        float* dv = reinterpret_cast<float*>(d + 16);
+        if (in_bytes) (void)hipMemcpy(dv, xyz, in_bytes, hipMemcpyHostToDevice);
+        hipLaunchKernelGGL(rb::k_normalize_sites, dim3((uint32_t)((total + 255u) / 256u)), dim3(256), 0, nullptr, dv, n, n_unit, seed0, n_seeds, d);
     });
 }
 

@@ -131,6 +131,84 @@ DEV float sqrt_exact(float x) {
     return sqrtf(x);
 }
 
+// ---- normalize for the kernels of single-node trees (k_trace and k_trace_direct with MULTI = false):
+// normalize() bit for bit, with the guards of its two fast paths joined.  Each arm has a knob for the A/B builds of
+// profiles/r27_c2_bench_ab.txt; with all three at 0 it carries the guards normalize() has.
+//
+// RB_NORM_ONE_RANGE -- one range test.  sqrt_exact's fast path takes L = dot(v, v) in [2^-60, 2^60) (bits 0x21800000 up to
+//   0x5D800000).  The correctly rounded root of such an L lies in [2^-30, 2^30]: the square root is monotonic and 2^-30 and 2^30
+//   are floats, so rounding cannot cross them.  div3_exact asks its denominator to lie in [2^-60, 2^59) (bits 0x21800000 up to
+//   0x5D000000), which holds all of [2^-30, 2^30]: after the root's fast path the denominator's range test cannot fail and is
+//   dropped.  What is left of that guard is the significand test of the reciprocal (all ones: not cleared by the exhaustive check).
+// RB_NORM_MIN3_ABS -- the numerators by magnitude.  div3_exact lets a zero numerator through its fast path, which costs a shift
+//   per component in front of the unsigned minimum and a copysign per quotient behind the division (a -0 comes out of
+//   div_newton as +0).  Here the test is on min(|x|, |y|, |z|) as floats: a zero component fails it and takes the compiler's
+//   division, which gives the same value, and a quotient of non-zero operands has its sign from the multiply, so the three
+//   copysigns go as well.  The bound is 2^-30 where div3_exact needs 2^-100: with every |component| >= 2^-30 each square is at
+//   least 2^-60 and so is L (rounding is monotonic), which makes the lower half of L's range test redundant; the upper half is
+//   one float compare, L < 2^60.  A component in (0, 2^-30) now takes the compiler's path, same value.  A NaN component can pass
+//   the minimum (the minimum of a NaN and a number is the number) but makes L a NaN, and an infinity makes L an infinity or a
+//   NaN: neither is below 2^60.
+// RB_NORM_UNIT -- the rejection loop's vector (UNIT = true) needs no range test.  A coordinate is RN(c * 2^-31 - 1) with
+//   c = (float)seed in [0, 2^32]: a float in [-1, 1], and every float there is a multiple of 2^-24 or 0 -- c * 2^-31 - 1 reaches
+//   no further down than that grid, since c * 2^-31 is a multiple of 2^-24 from c = 2^30 on, where the difference is exact, and
+//   below it the difference is in [-1, -1/2], where floats are 2^-24 apart; so it is 0, or its magnitude is in [2^-24, 1].  An accepted point has
+//   L = (xx + yy) + zz < 1 with every term 0 or >= 2^-48, all of them multiples of 2^-48 below 1: the sums are exact or round
+//   on a coarser grid, and L is 0 -- only for the point (0, 0, 0) -- or in [2^-48, 1), inside the root's fast range.  (0, 0, 0)
+//   needs three consecutive outputs of pcg that convert to c = 2^31, the seeds 2^31 - 64 .. 2^31 + 128; no seed in that window
+//   is followed by another one (tests/test_normalize_ranges.py walks them), so L = 0 is never accepted.  s = RN(sqrt(L)) is in
+//   [2^-24, 1).  div_newton's obligation is that operands, q0 and the remainder stay clear of the subnormal range: a numerator
+//   is 0 (q0 = r = 0 exactly; the copysign, kept at this site, restores a -0) or in [2^-24, 1); y = RN(1 / s) in (1, 2^24];
+//   q0 = RN(a * y) in [2^-24, 2^24]; r = a - s * q0 is a multiple of ulp(s) * ulp(q0) >= 2^-47 * 2^-47 = 2^-94, exact in the
+//   fused multiply-add, zero or at least 2^-94 in magnitude; the quotient is within an ulp of q0.  Every input meets it.
+#ifndef RB_NORM_ONE_RANGE
+#define RB_NORM_ONE_RANGE 1
+#endif
+#ifndef RB_NORM_MIN3_ABS
+#define RB_NORM_MIN3_ABS 1
+#endif
+#ifndef RB_NORM_UNIT
+#define RB_NORM_UNIT 1
+#endif
+template <bool UNIT = false>
+DEV f3 normalize_trim(f3 a) {
+#if RB_FAST_DIV && RB_FAST_SQRT
+    constexpr bool unit = UNIT && RB_NORM_UNIT != 0;
+    const float L = dot(a, a);
+    bool ok = true;   // L in the root's fast range, the numerators in the division's
+    if constexpr (!unit) {
+        if constexpr (RB_NORM_MIN3_ABS != 0) {
+            ok = L < 0x1p60f && fminf(fminf(fabsf(a.x), fabsf(a.y)), fabsf(a.z)) >= 0x1p-30f;
+        } else {
+            ok = (__float_as_uint(L) - 0x21800000u) < 0x3C000000u;
+            const uint32_t tx = (__float_as_uint(a.x) << 1) - 2u, ty = (__float_as_uint(a.y) << 1) - 2u, tz = (__float_as_uint(a.z) << 1) - 2u;
+            ok = ok && min(min(tx, ty), tz) >= (0x0D800000u << 1) - 2u;
+        }
+    }
+    float b;
+    if (ok) b = sqrt_newton(L);
+    else b = sqrtf(L);
+    const uint32_t xb = __float_as_uint(b);
+    bool fast = ok && (xb & 0x007FFFFFu) != 0x007FFFFFu;
+    if constexpr (!unit && RB_NORM_ONE_RANGE == 0) fast = fast && (xb - 0x21800000u) < 0x3B800000u;
+    if (fast) {
+        const float y = rcp_newton(b);
+        const float qx = div_newton(a.x, b, y), qy = div_newton(a.y, b, y), qz = div_newton(a.z, b, y);
+        if constexpr (!unit && RB_NORM_MIN3_ABS != 0) return mk(qx, qy, qz);
+        else return mk(__builtin_copysignf(qx, a.x), __builtin_copysignf(qy, a.y), __builtin_copysignf(qz, a.z));
+    }
+    return mk(a.x / b, a.y / b, a.z / b);
+#else
+    return normalize(a);
+#endif
+}
+// TRIM selects it at compile time: the kernels that do not ask for it keep normalize() and the code they have.
+template <bool TRIM, bool UNIT = false>
+DEV f3 normalize_for(f3 a) {
+    if constexpr (TRIM) return normalize_trim<UNIT>(a);
+    else return normalize(a);
+}
+
 // 1/a for the triangle test: the reference rejects |a| < 1e-6 first (its reciprocal is never used),
 // so only the upper range and the significand need checking.
 DEV float rcp_tri(float a) {
@@ -205,7 +283,8 @@ DEV float rnd_pm1(uint32_t& seed) {
 #ifndef RB_PARK_SEED
 #define RB_PARK_SEED 1   // 0: the plain loop around the fused try, for A/B builds (profiles/r15_c2_bench_ab.txt)
 #endif
-template <bool PARK = true>
+// TRIM: the accepted point goes through normalize_trim<true> (above), which needs none of normalize()'s range tests for it.
+template <bool PARK = true, bool TRIM = false>
 DEV f3 random_unit_vector(uint32_t& seed) {
     if constexpr (!PARK) {
         f3 p;
@@ -243,7 +322,7 @@ DEV f3 random_unit_vector(uint32_t& seed) {
             owed &= ~inside;
         }
         seed = s;
-        return normalize(mk(x, y, z));
+        return normalize_for<TRIM, true>(mk(x, y, z));
     }
 }
 

@@ -336,7 +336,9 @@ DEV void segment_spheres(const KParams& p, f3 o, f3 d, float a, float& closest_t
 #ifndef RB_ONE_NORMALIZE
 #define RB_ONE_NORMALIZE 1   // 0: normalize(d) in the metal branch, normalize(normal + ruv) in the other, for the A/B builds of profiles/r19_c2_bench_ab.txt
 #endif
-template <bool STATS, bool PARK = true, bool JOINED = true>
+// TRIM (the kernels of single-node trees that also pass TRIP: k_trace and k_trace_direct): the four
+// normalizes of an iteration are normalize_trim (rb_device_math.hpp), same values with fewer guards.
+template <bool STATS, bool PARK = true, bool JOINED = true, bool TRIM = false>
 DEV bool segment_post(const KParams& p, Path& pt, const TriHit th, const SegState st, float closest_t, uint32_t sphere_idx,
                       Tally<STATS>& tl) {
     const f3 o = pt.o, d = pt.d;
@@ -425,7 +427,7 @@ DEV bool segment_post(const KParams& p, Path& pt, const TriHit th, const SegStat
                 m = load_mat(&s->material);
                 use_tex = m.tex >= 0;
                 const v4f cr = ((cf4p)s)[0];
-                normal = normalize(pos - mk(cr.x, cr.y, cr.z));
+                normal = normalize_for<TRIM>(pos - mk(cr.x, cr.y, cr.z));
             } else {
                 use_tex = load_tex_index(&s->material) >= 0;
             }
@@ -434,7 +436,7 @@ DEV bool segment_post(const KParams& p, Path& pt, const TriHit th, const SegStat
             const rb_point_light* l = p.lights + light_idx;
             m = load_mat(&l->material);
             const v4f cr = ((cf4p)l)[0];
-            normal = normalize(pos - mk(cr.x, cr.y, cr.z));
+            normal = normalize_for<TRIM>(pos - mk(cr.x, cr.y, cr.z));
         }
     }
 
@@ -447,7 +449,7 @@ DEV bool segment_post(const KParams& p, Path& pt, const TriHit th, const SegStat
     // Both scatter branches draw exactly one random unit vector (:472, :488) and nothing else
     // touches the seed, so the rejection loop runs once for the whole wavefront instead of once
     // per branch; likewise the final normalize below is shared.
-    const f3 ruv = random_unit_vector<PARK>(pt.seed);
+    const f3 ruv = random_unit_vector<PARK, TRIM && PARK>(pt.seed);
     f3 scattered, albedo;
     bool absorbed = false;
     // A lane normalizes d (metal) or normal + ruv (the other branch), never both, and the wave paid for both sites: one
@@ -456,14 +458,14 @@ DEV bool segment_post(const KParams& p, Path& pt, const TriHit th, const SegStat
     constexpr bool one_norm = JOINED && RB_ONE_NORMALIZE != 0;
     const f3 sd = normal + ruv;
     f3 nin = sd;
-    if constexpr (one_norm) nin = normalize(is_metal ? d : sd);
+    if constexpr (one_norm) nin = normalize_for<TRIM>(is_metal ? d : sd);
     if (is_metal) {
-        const f3 reflected = reflect_vector(one_norm ? nin : normalize(d), normal);
+        const f3 reflected = reflect_vector(one_norm ? nin : normalize_for<TRIM>(d), normal);
         scattered = reflected + m.fuzz * ruv;
         absorbed = dot(scattered, normal) <= 0.0f;  // :640-642
         albedo = m.specular;
     } else {
-        scattered = near_zero(sd) ? normal : (one_norm ? nin : normalize(sd));
+        scattered = near_zero(sd) ? normal : (one_norm ? nin : normalize_for<TRIM>(sd));
         albedo = m.diffuse;
         if (use_tex) {
             if (tri_won_a) tri_uv(p, th, uvx, uvy);
@@ -473,7 +475,7 @@ DEV bool segment_post(const KParams& p, Path& pt, const TriHit th, const SegStat
     if (absorbed) return false;
     pt.att = pt.att * albedo;
     pt.o = pos + 0.001f * normal;
-    pt.d = normalize(scattered);
+    pt.d = normalize_for<TRIM>(scattered);
     pt.depth++;
     return pt.depth < p.u.max_depth;
 }
@@ -600,23 +602,23 @@ DEV void segment_resolve(const KParams& p, f3 o, f3 d, const TriHit th, const Se
 }
 
 // One iteration of the bounce loop after the triangle traversal (`th`: its winner).
-template <bool STATS, bool SPHTREE = true, bool PARK = true, bool JOINED = true, bool LEAN = false>
+template <bool STATS, bool SPHTREE = true, bool PARK = true, bool JOINED = true, bool LEAN = false, bool TRIM = false>
 DEV bool segment_finish(const KParams& p, Path& pt, const TriHit th, uint32_t* stack, uint32_t stride,
                         Tally<STATS>& tl) {
     const SegState st = segment_pre<STATS>(fresh_params(p), pt, th, tl);
     float closest_t = st.closest_t;
     uint32_t sphere_idx = 0xFFFFFFFFu;
     segment_spheres<STATS, SPHTREE, LEAN>(fresh_params(p), pt.o, pt.d, dot(pt.d, pt.d), closest_t, sphere_idx, stack, stride, tl);
-    return segment_post<STATS, PARK, JOINED>(fresh_params(p), pt, th, st, closest_t, sphere_idx, tl);
+    return segment_post<STATS, PARK, JOINED, TRIM>(fresh_params(p), pt, th, st, closest_t, sphere_idx, tl);
 }
 
 // One whole iteration of the bounce loop: traversal + everything else.  MULTI = false: trees of at most one node AND no
 // sphere tree (k_trace's default instantiations).
-// TRIP: intersect_bvh's (k_trace and k_trace_direct pass it for their single-node instantiations).
+// TRIP: intersect_bvh's (k_trace and k_trace_direct pass it for their single-node instantiations), and segment_post's TRIM.
 template <bool STATS, bool MULTI = true, bool JOINED = true, bool TRIP = false>
 DEV bool segment(const KParams& p, Path& pt, uint32_t* stack, uint32_t stride, Tally<STATS>& tl) {
     const TriHit th = intersect_bvh<STATS, MULTI, TRIP>(fresh_params(p), pt.o, pt.d, stack, stride, tl);
-    return segment_finish<STATS, MULTI, true, JOINED, !MULTI>(p, pt, th, stack, stride, tl);
+    return segment_finish<STATS, MULTI, true, JOINED, !MULTI, TRIP && !MULTI>(p, pt, th, stack, stride, tl);
 }
 
 // ----------------------------------------------------------------- camera --

@@ -14,7 +14,17 @@ triangles, 8 spheres, the phantom point light); the data-dependent ones are the 
 triangle loop does not run the compiler's division fallback (the blocks with v_div_scale), which the guard of the reciprocal
 branches over; they are counted apart.
 
-   python tools/ktrace_budget.py [build/rb_kernels.s] [kernel substring, default k_traceILb0ELb0ELi8]
+Below the loops, the rest: every block on the once-per-iteration path of the persistent loop (depth 1, and the scaffolding of
+the scans' block loops), grouped by the source region it comes from, with its static vector / scalar / slow counts and the
+executions per iteration; the loops and the groups together are held against what the counters measured, 26.89 vector
+wave-instructions per segment at 63.6 active lanes (profiles/r25_c2_pmc.json).  The regions are found from anchors in the
+assembly, not from line tables: the loops above; the normalize sites (a block with three v_div_fixup_f32 -- the compiler's
+division of three numerators -- and the root and reciprocal blocks around it); LDS and memory instructions (the colour ring's
+drain, store and take; the texture lookup).  What an anchor cannot separate stays together and the group's name says so.
+Executions are the phase rows of profiles/r15_ktrace_phases.txt where one exists ("measured"); everything else is marked
+"assumed" with its reason.
+
+   python tools/ktrace_budget.py [build/rb_kernels.s] [kernel substring, default k_traceILb0ELb0ELi8] [measured VALU per segment, default 26.89]
 """
 import os
 import sys
@@ -115,6 +125,188 @@ def rows(blocks):
     return out
 
 
+# ---------------------------------------------------------------------------------------------- the once-per-iteration path
+MEASURED_VALU_PER_SEGMENT, ACTIVE_LANES, SEGMENTS_PER_PATH = 26.89, 63.6, 5.155   # profiles/r25_c2_pmc.json; profiles/r15_ktrace_phases.txt
+
+
+def _has(b, *prefixes):
+    return any(i.op.startswith(prefixes) for i in b.instrs)
+
+
+def _n(b, prefix):
+    return sum(i.op.startswith(prefix) for i in b.instrs)
+
+
+def _memory(b):
+    return _has(b, "ds_", "global_", "flat_", "buffer_", "scratch_")
+
+
+def normalize_sites(blocks):
+    """[(first index, last index, index of the slow division)] of every normalize in text order.  A site's own blocks: the
+    compiler's division of the three numerators (three v_div_fixup_f32), behind it the fast division (a v_rcp_f32, no
+    v_div_scale_f32), in front of it the blocks of the two square roots, the guard of the division and the empty blocks of the
+    exec-mask joins.  The dot product and the compares of the first guard sit in the block in front, with other code."""
+    out = []
+    for k, b in enumerate(blocks):
+        if _n(b, "v_div_fixup_f32") != 3 or _has(b, "v_cvt_f32_u32"):   # (hash_to_color divides three converted integers)
+            continue
+        first = k
+        while first > 0:
+            q = blocks[first - 1]
+            nv = len(q.valu)
+            fast_div = _has(q, "v_rcp_f32") and not _has(q, "v_div_scale_f32") and nv <= 20          # (laid out in front at some sites)
+            if nv <= 4 or fast_div or (_has(q, "v_sqrt_f32") and nv <= 25) or (_has(q, "v_min3_u32") and nv <= 12):   # (<= 4: the significand test alone)
+                first -= 1
+            else:
+                break
+        last = k
+        for j in range(k + 1, min(k + 3, len(blocks))):
+            if _has(blocks[j], "v_rcp_f32") and not _has(blocks[j], "v_div_scale_f32") and len(blocks[j].valu) <= 20:
+                last = j
+                break
+        out.append((first, last, k))
+    return out
+
+
+def _slow_path(b):
+    """a block only lanes outside a guard run: the compiler's division, or its square root (the one that tests the class)"""
+    return (_n(b, "v_div_fixup_f32") == 3 and not _has(b, "v_cvt_f32_u32")) or (_has(b, "v_sqrt_f32") and _has(b, "v_cmp_class_f32"))
+
+
+def once_groups(blocks):
+    """[(group name, blocks, executions per iteration, 'measured' | 'assumed', why)] covering every block of the persistent
+    loop that no row of rows() counts, each block once; blocks outside the loop (set-up, the final drain) are not listed."""
+    idx = {id(b): k for k, b in enumerate(blocks)}
+    outer = next(b for b in blocks if b.depth == 1 and b.loop == b.name)
+    tri_h, tri_body = isa_blocks.triangle_loop(blocks)
+    scans = scan_loops(blocks)
+    rh, rbody = rejection_loop(blocks)
+    in_rows = {id(b) for body in [tri_body, rbody] + [l[1] for pair in scans[:2] for l in pair] for b in body}
+    todo = [b for b in blocks if b.depth >= 1 and id(b) not in in_rows and (b.loop == outer.name or b.depth >= 2)]
+    sites = normalize_sites(blocks)
+    site_of = {}
+    for n, (a, z, _) in enumerate(sites):
+        for k in range(a, z + 1):
+            site_of[k] = n
+    h, t = idx[id(outer)], idx[id(tri_h)]
+    s1, l2 = idx[id(scans[0][0][0])], idx[id(scans[min(1, len(scans) - 1)][1][0])]
+    r = idx[id(rh)]
+    pre = [n for n, (a, z, _) in enumerate(sites) if h <= a < t]          # stage_row's, one per unrolled refill round
+    mid = [n for n, (a, z, _) in enumerate(sites) if l2 < a < r]          # the sphere's normal, then the light's
+    post = [n for n, (a, z, _) in enumerate(sites) if a > r and blocks[a].depth >= 1 and blocks[a].loop == outer.name]
+    # stage_row around its site: back to the last block with a memory or LDS access (open_row's drain), on to the ring store
+    rows_span = []
+    for n in pre:
+        a, z, _ = sites[n]
+        lo = a
+        while lo - 1 > h and not _memory(blocks[lo - 1]):
+            lo -= 1
+        hi = z
+        while hi + 1 < t and not _has(blocks[hi], "ds_"):
+            hi += 1
+        rows_span.append((lo, hi))
+    # the second unrolled round starts as far in front of its stage_row as the first one does behind the loop's header
+    round2 = rows_span[1][0] - (rows_span[0][0] - h) if len(rows_span) > 1 else t
+    # segment entry: from the last memory access in front of the triangle loop on
+    entry = t
+    while entry - 1 > h and not _memory(blocks[entry - 1]) and not any(lo <= entry - 1 <= hi for lo, hi in rows_span):
+        entry -= 1
+    tail_first = sites[post[-1]][1] + 1 if post else r + 1                # behind the last normalize: the path's end
+    scatter = (sites[post[1]][1] + 1, sites[post[-1]][0] - 1) if len(post) >= 3 else (0, -1)
+    tex = [k for k in range(scatter[0], scatter[1] + 1) if _has(blocks[k], "global_load", "flat_load", "buffer_load")]
+    names = {0: "normalize: random_unit_vector", 1: "normalize: is_metal ? d : normal + ruv", 2: "normalize: pt.d = scattered"}
+    groups, order = {}, []
+
+    def put(name, b, ex, kind, why):
+        if name not in groups:
+            groups[name] = [[], ex, kind, why]
+            order.append(name)
+        groups[name][0].append(b)
+
+    row_ex = 1.0 / SEGMENTS_PER_PATH
+    for b in todo:
+        k = idx[id(b)]
+        if k in site_of and site_of[k] in pre + mid + post:
+            n = site_of[k]
+            if n in pre:
+                which, ex, kind, why = f"normalize: stage_row, refill round {pre.index(n) + 1}", row_ex if pre.index(n) == 0 else 0.0, "assumed", \
+                    "a row of 64 paths is opened per 64 paths of 5.155 segments" if pre.index(n) == 0 else "a reservation ends once in queue_batch items"
+            elif n in mid:
+                which = ("normalize: sphere normal", "normalize: light normal")[min(mid.index(n), 1)]
+                ex, kind, why = (1.0, "assumed", "a wave with no sphere winner skips it; 8.4 lanes have candidates") if mid.index(n) == 0 else \
+                    (LIGHT_PASS2_TRIPS, "measured", "light pass 2: C2's phantom light is never a candidate")
+            else:
+                which = names.get(post.index(n) if post.index(n) < 2 else (2 if n == post[-1] else 9), "normalize: scatter branch")
+                ex, kind, why = 1.01, "measured", "shading / scatter rows"
+            if _slow_path(b):
+                put(which + ", compiler's path", b, 0.0, "assumed", "every lane inside the guards; a zero component or an all-ones significand would enter")
+            else:
+                put(which, b, ex, kind, why)
+        elif k < h:
+            put("blocks laid out in front of the loop's header (the join behind a finished path)", b, 1.0, "assumed", "the loop's latch")
+        elif _n(b, "v_div_fixup_f32") == 3:
+            put("resolve and material: hash_to_color", b, 0.0, "assumed", "C2 renders without the colour hash")
+        elif h <= k < t:
+            in_row = [n for n, (lo, hi) in enumerate(rows_span) if lo <= k <= hi]
+            if in_row:
+                first = in_row[0] == 0
+                put(f"row opening: stage_row to the ring store, refill round {in_row[0] + 1}", b, row_ex if first else 0.0, "assumed",
+                    "1 / 5.155" if first else "second round: not reached")
+            elif k >= entry:
+                put("segment entry and box test (from the refill's last memory access on: a new path's moves included)", b, 1.01, "measured", "segment entry row")
+            elif k >= round2:
+                put("refill round 2, open_row's drain, ColorRing::take", b, 0.0, "assumed", "runs when a reservation ends inside a round: once in queue_batch items")
+            else:
+                put("refill round 1, open_row's drain, ColorRing::take", b, 1.0, "assumed", "12.3 lanes end a path per iteration: some lane is idle")
+        elif t < k < s1:
+            put("segment_pre: ground, triangle winner", b, 1.01, "measured", "segment entry row")
+        elif s1 <= k <= l2 + 8 and b.depth >= 2:
+            put("scan block loops and pass 2 set-up (depth 2 and 3)", b, 1.0, "assumed", "one block of 32 spheres, one of lights")
+        elif k < r and (not mid or k < sites[mid[0]][0]):
+            put("resolve and material", b, 1.01, "measured", "shading row")
+        elif k < r and mid and k <= sites[mid[-1]][1]:
+            put("resolve and material: between the two normal sites", b, 1.0, "assumed", "load_mat of a sphere; the light's is never entered")
+        elif k < r:
+            put("emission and the first try of random_unit_vector", b, 1.01, "measured", "unit vector: the first try")
+        elif post and k < sites[post[0]][0]:
+            put("rejection loop exit: dot product of the accepted point", b, 1.01, "measured", "unit vector row")
+        elif len(post) >= 2 and k < sites[post[1]][0]:
+            put("scatter operand: normal + ruv, select, dot product, guards", b, 1.01, "measured", "shading row")
+        elif scatter[0] <= k <= scatter[1]:
+            if tex and tex[0] <= k <= tex[-1]:
+                put("lambert branch: texture lookup", b, 0.0, "assumed", "C2 has no texture")
+            else:
+                put("metal branch and lambert branch (arithmetic; the layout does not separate them)", b, 1.0, "assumed", "metal 0.93 and lambert 1.01 measured, the split is not")
+        elif k >= tail_first:
+            put("path end", b, 1.01, "measured", "path end row")
+        else:
+            put("unplaced", b, 1.0, "assumed", "no anchor")
+    return [(name, *groups[name]) for name in order]
+
+
+def print_once(blocks, loops_valu, measured=MEASURED_VALU_PER_SEGMENT):
+    print("# the once-per-iteration path, by source region (static counts; executions per iteration, measured = a phase row of profiles/r15_ktrace_phases.txt)")
+    print(f"{'group':108s} {'blocks':>6s} {'valu':>5s} {'salu':>5s} {'slow':>5s} {'exec/it':>8s} {'':9s} | {'valu/it':>8s}")
+    total = 0.0
+    for name, bs, ex, kind, why in once_groups(blocks):
+        valu = sum(len(b.valu) for b in bs)
+        salu = sum(b.counts()["salu"] for b in bs)
+        slow = sum(b.counts()["quarter"] for b in bs)
+        total += valu * ex
+        print(f"{name[:108]:108s} {len(bs):6d} {valu:5d} {salu:5d} {slow:5d} {ex:8.3f} {kind:9s} | {valu * ex:8.1f}   # {bs[0].name}..{bs[-1].name}: {why}")
+    want = measured * ACTIVE_LANES
+    have = loops_valu + total
+    print(f"{'the groups above':108s} {'':6s} {'':5s} {'':5s} {'':5s} {'':8s} {'':9s} | {total:8.1f}")
+    print(f"# loops {loops_valu:.1f} + groups {total:.1f} = {have:.1f} vector instructions per iteration; measured {measured} x {ACTIVE_LANES} = {want:.1f}: "
+          f"{100.0 * (have - want) / want:+.1f} %")
+    if abs(have - want) > 0.05 * want:
+        loose = sorted(((sum(len(b.valu) for b in bs) * ex, name) for name, bs, ex, kind, _ in once_groups(blocks) if ex > 0 and "normalize" not in name), reverse=True)[:5]
+        print(f"# OUTSIDE 5 %: {have - want:+.1f} instructions are unexplained.  The groups that can hold them are the ones whose blocks are not all run by every")
+        print("# iteration and which the anchors cannot split further (ground test, the light's material, the `use_tex` and padding ways, the take of a lane):")
+        for v, name in loose:
+            print(f"#   {v:7.1f}  {name}")
+
+
 def main():
     asm = sys.argv[1] if len(sys.argv) > 1 else "build/rb_kernels.s"
     kernel = sys.argv[2] if len(sys.argv) > 2 else "k_traceILb0ELb0ELi8"
@@ -142,6 +334,7 @@ def main():
             if classify(i, hashes) in ("book", "slow"):
                 ops[i.op] = ops.get(i.op, 0) + 1
         print(f"#   {name}: " + ", ".join(f"{o} {n}" for o, n in sorted(ops.items())))
+    print_once(blocks, tot[0], float(sys.argv[3]) if len(sys.argv) > 3 else MEASURED_VALU_PER_SEGMENT)
 
 
 if __name__ == "__main__":
