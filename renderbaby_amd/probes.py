@@ -363,9 +363,10 @@ def depth_project(dirs, hits, samples, max_distance):
     rows = np.arange(n)
     T, take = T.reshape(n, samples), take.reshape(n, samples)
     terms = np.stack([r, r2, np.ones_like(r), back], axis=1).reshape(n, samples, 4)
-    for k in range(samples):   # one sample of every probe at a time: a texel takes its samples in ascending order
-        i = rows[take[:, k]]
-        acc[i, T[i, k]] = (acc[i, T[i, k]] + terms[i, k]).astype(f32)
+    with np.errstate(all="ignore"):   # (distances near 1e19 and beyond: r r and the sums overflow to inf, as on the device)
+        for k in range(samples):   # one sample of every probe at a time: a texel takes its samples in ascending order
+            i = rows[take[:, k]]
+            acc[i, T[i, k]] = (acc[i, T[i, k]] + terms[i, k]).astype(f32)
     out = np.zeros(n, dtype=abi.PROBE_DEPTH)
     out["texel"] = acc
     return out
