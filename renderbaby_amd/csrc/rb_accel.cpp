@@ -35,7 +35,7 @@ hipError_t read_back(std::vector<T>& v, const T* dev, size_t n) {
 
 // a mesh that a tree of the library's can go with: a multi-node caller tree, triangles and indices, a positive count
 bool mesh_takes_tree(const rb_engine* e, uint32_t tri_count) {
-    return e->host_nodes.size() > 1 && e->host_tri_len > 0 && e->host_index_len > 0 && tri_count > 0;
+    return e->sc.host_nodes.size() > 1 && e->host_tri_len > 0 && e->host_index_len > 0 && tri_count > 0;
 }
 
 // Each structure's KParams fields, and the stack entries its walk needs (0: not in use).
@@ -216,9 +216,9 @@ int build_sphere_bvh(rb_engine* e, const rb_sphere* s, size_t n) {
     t.depth = sphere_stack_entries(levels4);
     std::vector<float> leaf(n * 4);   // {centre, radius} = the first 16 bytes of an rb_sphere (rb_abi.h)
     for (size_t j = 0; j < n; ++j) std::memcpy(&leaf[j * 4], &s[order[j]], 4 * sizeof(float));
-    int rc = upload(e, t.nodes, nodes.data(), nodes.size(), nullptr, true);
-    if (!rc) rc = upload(e, t.leaf, leaf.data(), leaf.size(), nullptr, true);
-    if (!rc) rc = upload(e, t.id, order.data(), order.size(), nullptr, true);
+    int rc = upload(e, t.nodes, nodes.data(), nodes.size(), true);
+    if (!rc) rc = upload(e, t.leaf, leaf.data(), leaf.size(), true);
+    if (!rc) rc = upload(e, t.id, order.data(), order.size(), true);
     if (rc) return rc;
     HIP_TRY(e, hipStreamSynchronize(e->stream));  // the vectors above are locals
     t.rec = {"host-median", ms_since(t_begin)};
@@ -248,20 +248,18 @@ int build_engine_tree(rb_engine* e, const rb_gpu_triangle* src, size_t n) {
             nodes.resize(nn);
             HIP_TRY(e, hipMemcpyAsync(nodes.data(), e->nodes.ptr, sizeof(rb_bvh_node) * nn, hipMemcpyDeviceToHost, e->stream));
             HIP_TRY(e, hipStreamSynchronize(e->stream));
-            e->n_indices = static_cast<uint32_t>(n);
             builder = "device";
         }
     }
     const bool on_device = builder[0] == 'd';
     if (!on_device) {   // the host builder, or the empty tree
         if (n) bvh_build_canonical(src, n, nodes, idx);
-        int rc = upload(e, e->nodes, nodes.data(), nodes.size(), nullptr, true);
-        if (!rc) rc = upload(e, e->indices, idx.data(), idx.size(), &e->n_indices, true);
+        int rc = upload(e, e->nodes, nodes.data(), nodes.size(), true);
+        if (!rc) rc = upload(e, e->indices, idx.data(), idx.size(), true);
         if (rc) return rc;
         if (n) HIP_TRY(e, hipStreamSynchronize(e->stream));   // `nodes` / `idx` are moved below, but the copies read them now
     }
-    e->n_nodes = static_cast<uint32_t>(nodes.size());
-    e->host_nodes = std::move(nodes);
+    commit_own_tree(e->sc, std::move(nodes), n);
     if (n == 0 || mesh_walks(e->opt).host_mesh) {   // the device builder's indices stay on the device until a host builder asks
         e->host_index_len = n;
         e->host_indices_stale = on_device;
@@ -277,12 +275,12 @@ int build_chunk_tree(rb_engine* e, uint32_t tri_count) {
     if (!mesh_walks(e->opt).chunk || !mesh_takes_tree(e, tri_count)) return RB_OK;
     const auto t_begin = Clock::now();
     const uint32_t n_tris = std::min<uint32_t>(tri_count, static_cast<uint32_t>(e->host_tri_len));
-    const uint32_t n_idx = static_cast<uint32_t>(e->host_index_len), n_nodes = static_cast<uint32_t>(e->host_nodes.size());
+    const uint32_t n_idx = static_cast<uint32_t>(e->host_index_len), n_nodes = static_cast<uint32_t>(e->sc.host_nodes.size());
     const char* builder = "";
     size_t n = 0;
     if (chunk_tree_on_device(e, n_idx) && n_idx <= e->indices.count && n_tris <= e->tris.count) {
         DeviceChunkTree dt;
-        const int brc = device_chunk_tree_build(e->tris.ptr, n_tris, e->indices.ptr, n_idx, e->host_nodes.data(), n_nodes, kStackDepth, &dt, e->stream);
+        const int brc = device_chunk_tree_build(e->tris.ptr, n_tris, e->indices.ptr, n_idx, e->sc.host_nodes.data(), n_nodes, kStackDepth, &dt, e->stream);
         if (brc > 0) return fail(e, RB_ERR_DEVICE, "chunk tree build failed: %s", hipGetErrorString(static_cast<hipError_t>(brc)));
         if (brc == 0) {   // (-1: not for this builder, the host's decides)
             t.nodes.adopt(dt.nodes, dt.nodes_capacity);
@@ -299,13 +297,13 @@ int build_chunk_tree(rb_engine* e, uint32_t tri_count) {
     if (!builder[0]) {
         ChunkTree ct;
         if (const int rc = ensure_host_mesh(e)) return rc;
-        if (!chunk_tree_build(e->host_tris.data(), n_tris, e->host_indices.data(), n_idx, e->host_nodes.data(), n_nodes, kStackDepth, ct))
+        if (!chunk_tree_build(e->host_tris.data(), n_tris, e->host_indices.data(), n_idx, e->sc.host_nodes.data(), n_nodes, kStackDepth, ct))
             return RB_OK;   // another walk takes this mesh
         n = ct.pos_slot.size();
-        int rc = upload(e, t.nodes, ct.nodes.data(), ct.nodes.size(), nullptr, true);
-        if (!rc) rc = upload(e, t.rank_slot, ct.rank_slot.data(), ct.rank_slot.size(), nullptr, true);
-        if (!rc) rc = upload(e, t.pos_slot, ct.pos_slot.data(), n, nullptr, true);
-        if (!rc) rc = upload(e, t.pos_rank, ct.pos_rank.data(), n, nullptr, true);
+        int rc = upload(e, t.nodes, ct.nodes.data(), ct.nodes.size(), true);
+        if (!rc) rc = upload(e, t.rank_slot, ct.rank_slot.data(), ct.rank_slot.size(), true);
+        if (!rc) rc = upload(e, t.pos_slot, ct.pos_slot.data(), n, true);
+        if (!rc) rc = upload(e, t.pos_rank, ct.pos_rank.data(), n, true);
         if (rc) return rc;
         HIP_TRY(e, hipStreamSynchronize(e->stream));  // `ct` is a local
         t.n_nodes = ct.nodes.size();
@@ -330,20 +328,20 @@ int build_own_tree(rb_engine* e, uint32_t tri_count) {
     if (rc) return rc;
     FastTree ft;
     const auto t_begin = Clock::now();
-    const uint32_t n_idx = static_cast<uint32_t>(e->host_indices.size()), n_nodes = static_cast<uint32_t>(e->host_nodes.size());
+    const uint32_t n_idx = static_cast<uint32_t>(e->host_indices.size()), n_nodes = static_cast<uint32_t>(e->sc.host_nodes.size());
     const uint32_t n_tris = std::min<uint32_t>(tri_count, static_cast<uint32_t>(e->host_tris.size()));
     const float small_cap = (e->opt.flags & RB_FLAG_SKIP_NEAR_DEGENERATE) ? 0.0f : kFastSmallCap;
     const char* builder = "";
     DeviceTreeInfo info{};
     if (device_builder(e, RB_FLAG_HOST_BVH, RB_FLAG_DEVICE_BVH, n_tris >= kDeviceBuildMinTriangles)) {
         // reference-order metadata on the host (one pass over the caller's tree), the tree on the device
-        if (fast_bvh_prepare(e->host_tris.data(), n_tris, e->host_indices.data(), n_idx, e->host_nodes.data(), n_nodes, ft, small_cap) &&
+        if (fast_bvh_prepare(e->host_tris.data(), n_tris, e->host_indices.data(), n_idx, e->sc.host_nodes.data(), n_nodes, ft, small_cap) &&
             ft.slots.size() >= 1024) {
             const uint32_t n = static_cast<uint32_t>(ft.slots.size());
             const bool lbvh = (e->opt.flags & RB_FLAG_DEVICE_LBVH) != 0u;
             DevBuf<uint32_t> visit_slots;
-            rc = upload(e, visit_slots, ft.slots.data(), ft.slots.size(), nullptr, true);
-            if (!rc) rc = upload(e, t.slot_meta, ft.slot_meta.data(), ft.slot_meta.size(), nullptr, true);
+            rc = upload(e, visit_slots, ft.slots.data(), ft.slots.size(), true);
+            if (!rc) rc = upload(e, t.slot_meta, ft.slot_meta.data(), ft.slot_meta.size(), true);
             if (rc) return rc;
             HIP_TRY(e, t.nodes.resize(n - 1));
             HIP_TRY(e, t.slots.resize(n));
@@ -364,18 +362,18 @@ int build_own_tree(rb_engine* e, uint32_t tri_count) {
         }
     }
     if (!builder[0]) {
-        if (!fast_bvh_build(e->host_tris.data(), n_tris, e->host_indices.data(), n_idx, e->host_nodes.data(), n_nodes, kStackDepth, ft, small_cap))
+        if (!fast_bvh_build(e->host_tris.data(), n_tris, e->host_indices.data(), n_idx, e->sc.host_nodes.data(), n_nodes, kStackDepth, ft, small_cap))
             return RB_OK;  // keep the reference walk
-        rc = upload(e, t.nodes, ft.nodes.data(), ft.nodes.size(), nullptr, true);
-        if (!rc) rc = upload(e, t.slots, ft.slots.data(), ft.slots.size(), nullptr, true);
+        rc = upload(e, t.nodes, ft.nodes.data(), ft.nodes.size(), true);
+        if (!rc) rc = upload(e, t.slots, ft.slots.data(), ft.slots.size(), true);
         if (rc) return rc;
         info = DeviceTreeInfo{ft.root, ft.depth, ft.margin, ft.root_amax, {ft.bmin[0], ft.bmin[1], ft.bmin[2]}, {ft.bmax[0], ft.bmax[1], ft.bmax[2]}};
         builder = "host-sah";
     }
-    rc = upload(e, t.slot_meta, ft.slot_meta.data(), ft.slot_meta.size(), nullptr, true);
-    if (!rc) rc = upload(e, t.ref_parent, ft.ref_parent.data(), ft.ref_parent.size(), nullptr, true);
-    if (!rc) rc = upload(e, t.gnodes, ft.gnodes.data(), ft.gnodes.size(), nullptr, true);
-    if (!rc) rc = upload(e, t.gslots, ft.gslots.data(), ft.gslots.size(), nullptr, true);
+    rc = upload(e, t.slot_meta, ft.slot_meta.data(), ft.slot_meta.size(), true);
+    if (!rc) rc = upload(e, t.ref_parent, ft.ref_parent.data(), ft.ref_parent.size(), true);
+    if (!rc) rc = upload(e, t.gnodes, ft.gnodes.data(), ft.gnodes.size(), true);
+    if (!rc) rc = upload(e, t.gslots, ft.gslots.data(), ft.gslots.size(), true);
     if (rc) return rc;
     HIP_TRY(e, t.tris.resize(t.slots.count));
     if (launch_gather_tris(e->ptris.ptr, t.slots.ptr, static_cast<uint32_t>(t.slots.count), t.tris.ptr, e->stream))
@@ -390,12 +388,12 @@ uint32_t accel_params(const rb_engine* e, KParams& p) {
     // a single-node reference-layout tree is walked without a stack (rb_kernels.hip, intersect_bvh); the mesh walks' trees go
     // with the caller's tree they were built over
     const bool multi_node = p.u.bvh_node_count > 1u;
-    const bool tree_current = multi_node && p.u.bvh_node_count == e->n_nodes;
+    const bool tree_current = multi_node && p.u.bvh_node_count == e->sc.n_nodes;
     const bool use_chunk = e->chunk.rec.built() && tree_current;
     // (the caller's tree's need counts too: with no_leaf_stepping the launch falls to the per-segment kernel, which walks it)
-    return std::max({multi_node ? std::max(e->bvh_stack, 1u) : 0u, params(e->chunk, use_chunk, p),
+    return std::max({multi_node ? std::max(e->sc.bvh_stack, 1u) : 0u, params(e->chunk, use_chunk, p),
                      params(e->own, !use_chunk && e->own.rec.built() && tree_current, (e->opt.flags & RB_FLAG_SKIP_NEAR_DEGENERATE) != 0u, p),
-                     params(e->sph, e->sph.rec.built() && p.u.spheres_count == e->n_spheres, p)});
+                     params(e->sph, e->sph.rec.built() && p.u.spheres_count == e->sc.n_spheres, p)});
 }
 
 }  // namespace rb
@@ -462,12 +460,12 @@ int rb_engine_tree(rb_engine* e, rb_bvh_node* nodes_out, size_t nodes_capacity, 
         e = e->parts[0].get();
     }
     std::lock_guard<std::mutex> lock(e->mu);
-    const size_t nn = e->host_nodes.size(), ni = nn ? e->n_indices : 0;
+    const size_t nn = e->sc.host_nodes.size(), ni = nn ? e->sc.n_indices : 0;
     *n_nodes = nn;
     *n_indices = ni;
     if (nodes_out) {
         if (nodes_capacity < nn) return rb::fail(g, RB_ERR_INVALID_BVH, "nodes_out holds %zu of %zu nodes", nodes_capacity, nn);
-        if (nn) std::memcpy(nodes_out, e->host_nodes.data(), sizeof(rb_bvh_node) * nn);
+        if (nn) std::memcpy(nodes_out, e->sc.host_nodes.data(), sizeof(rb_bvh_node) * nn);
     }
     if (indices_out && ni) {
         if (indices_capacity < ni) return rb::fail(g, RB_ERR_INVALID_BVH, "indices_out holds %zu of %zu indices", indices_capacity, ni);

@@ -12,6 +12,7 @@
 #include "rb_color_plan.hpp"
 #include "rb_internal.hpp"
 #include "rb_rccl.hpp"
+#include "rb_update_plan.hpp"
 
 namespace rb {
 
@@ -118,22 +119,12 @@ struct rb_engine {
     const char* last_kernel_name = "";
     rb_options opt{};
 
-    bool initialized = false;        // GpuWrapper::initialized (gpu_wrapper.rs:69,117)
-    bool have_uniforms = false;      // last update carried Create/Update uniforms (:303-329)
-    bool scene_valid = false;        // the buffers hold a scene that passed validate_scene (set by the last update)
-    rb_uniforms uniforms{};          // as handed over (before count patch-up)
+    rb::SceneFacts sc;               // what rb_update decides on (rb_update_plan.hpp): lengths, uniforms, frame size; changed by commit_* only
+    bool scene_valid = false;        // the buffers hold a scene that passed plan_update (set by the last update)
     rb_progressive prh{};            // gpu_wrapper.rs:19-53
     bool iter_initialized = false;   // RaytracerFrameIterator::initialized (lib.rs:131)
     uint32_t iter_passes_per_frame = 1;  // rb_iter_set_passes_per_frame (1 = the reference's one frame per pass)
 
-    // element counts = what arrayLength() / the patched uniforms see
-    uint32_t n_spheres = 0, n_lights = 0, n_meshes = 0, n_nodes = 0, n_indices = 0, n_tris = 0, n_uvs = 0,
-             n_tex = 0;
-    // Change of the last update for the three patched counts (gpu_wrapper.rs:475-495)
-    uint32_t last_change_spheres = RB_KEEP, last_change_nodes = RB_KEEP, last_change_tris = RB_KEEP;
-    // length of the spheres vector the last update carried: a Create after the first update is not acted on, but :476 still
-    // takes spheres_count from the vector it was handed (the BVH fields' Create is acted on: their vector is the buffer)
-    uint32_t last_spheres_sent = 0;
     bool prep_dirty = true;
     uint32_t prep_tri_count = 0xFFFFFFFFu;  // uniforms.bvh_triangle_count (patched) the prepared triangles were made for
 
@@ -171,10 +162,6 @@ struct rb_engine {
     rb::DevBuf<float> colors;        // RB_KERNEL_STREAM: float4 per (pixel, sample) of one launch chunk, times the parts of the plan
     size_t color_part_floats = 0;    // part k of the last reservation starts at colors.ptr + k * color_part_floats
     uint64_t color_budget = 0;       // bytes `colors` may take (0 = ask the device at the next dispatch)
-    uint32_t bvh_stack = 0;          // traversal-stack entries the current tree needs
-
-    std::vector<rb_bvh_node> host_nodes;  // kept for validation when nodes/indices change separately
-    uint32_t width = 0, height = 0, local_rows = 0, padded_rows = 0;
 
     // closest-hit queries (rb_cast_rays / rb_render_hits / rb_pick): scratch for one piece of at most rb::kQueryPiece rays (a
     // frame piece: whole 8-row bands, so at least 8 x width records), the kernel and the kernel time of the last one; nothing of a render is touched
@@ -228,7 +215,6 @@ struct rb_engine {
     float last_dispatch_ms = 0.0f;
     uint32_t last_launches = 0;
     bool timing_pending = false;
-    uint32_t max_mesh_index = 0;  // over the uploaded triangles
 
     // ---- several devices behind one handle (rb_create_multi): this engine only coordinates; every part is a
     // complete engine for one shard on one device.  Or one process per device (rb_comm_init_rank): this engine
@@ -254,7 +240,7 @@ int fail(const rb_engine* e, int code, const char* fmt, ...);
 // The copy is queued on the engine's stream from caller memory: every path that calls this ends in
 // update_locked's hipStreamSynchronize (or an earlier one) before the caller gets its buffers back.
 template <typename T>
-int upload(rb_engine* e, DevBuf<T>& buf, const void* src, size_t count, uint32_t* visible_len, bool pad_empty) {
+int upload(rb_engine* e, DevBuf<T>& buf, const void* src, size_t count, bool pad_empty) {
     const size_t alloc = (count == 0 && pad_empty) ? 1 : count;
     HIP_TRY(e, buf.resize(alloc));
     if (count > 0) {
@@ -262,7 +248,6 @@ int upload(rb_engine* e, DevBuf<T>& buf, const void* src, size_t count, uint32_t
     } else if (alloc > 0) {
         HIP_TRY(e, hipMemsetAsync(buf.ptr, 0, alloc * sizeof(T), e->stream));
     }
-    if (visible_len) *visible_len = static_cast<uint32_t>(alloc);
     return RB_OK;
 }
 
@@ -281,7 +266,7 @@ RB_HIDDEN void copy_error(rb_engine* g, const rb_engine* part);
 // ---- rb_accel.cpp
 constexpr uint32_t kBuildTreeFlags = RB_FLAG_BUILD_TREE | RB_FLAG_BUILD_TREE_HOST;          // the engine builds the reference-layout tree
 constexpr uint32_t kOwnTreeFlags = RB_FLAG_FAST_BVH | RB_FLAG_DEVICE_BVH | RB_FLAG_HOST_BVH;  // they name the own tree as the walk
-inline bool builds_tree(const rb_engine* e) { return (e->opt.flags & kBuildTreeFlags) != 0u; }
+inline bool builds_tree(const rb_options& opt) { return (opt.flags & kBuildTreeFlags) != 0u; }
 MeshWalks mesh_walks(const rb_options& opt);
 bool host_copy_can_wait(const rb_engine* e, size_t n);   // may a mesh field of n elements leave its host copy to ensure_host_mesh?
 int ensure_host_mesh(rb_engine* e);

@@ -789,7 +789,7 @@ int ensure_guides(rb_engine* e) {
     int rc = ensure_prepared(e);
     if (!rc) rc = scene_params(e, &p);
     if (rc) return rc;
-    const uint32_t w = e->width, h = e->height;
+    const uint32_t w = e->sc.width, h = e->sc.height;
     const size_t n = static_cast<size_t>(w) * h;
     rb::DevBuf<rb_hit> hits;       // the records live until the pack has read them
     rb::DevBuf<rb_surface> surf;
@@ -834,7 +834,7 @@ int denoise_locked(rb_engine* e, const rb_denoise_params* prm, uint8_t* rgba_out
     if (!rc) rc = denoise_params_check(e, prm);
     if (rc) return rc;
     if (!rgba_out && !linear_out) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "rgba_out and linear_out are both NULL");
-    const size_t n = static_cast<size_t>(e->width) * e->height;
+    const size_t n = static_cast<size_t>(e->sc.width) * e->sc.height;
     if (device) {
         if (rgba_out) rc = device_range(e, rgba_out, n * 4, 4, "d_rgba_out");
         if (!rc && linear_out) rc = device_range(e, linear_out, n * 16, 16, "d_linear_out");
@@ -846,8 +846,8 @@ int denoise_locked(rb_engine* e, const rb_denoise_params* prm, uint8_t* rgba_out
     e->last_denoise_ms = 0.0f;
     if (n == 0) return RB_OK;
     rb::DenoiseArgs a{};
-    a.w = e->width;
-    a.h = e->height;
+    a.w = e->sc.width;
+    a.h = e->sc.height;
     a.accum = e->slot[e->cur].accum.ptr;
     a.g = guide_planes(e);
     for (int k = 0; k < 2; ++k) {
@@ -887,7 +887,7 @@ int denoise_guides_locked(rb_engine* e, rb_guide* guides_out) {
     int rc = denoise_ready(e);
     if (!rc) rc = ensure_guides(e);
     if (rc) return rc;
-    const size_t n = static_cast<size_t>(e->width) * e->height;
+    const size_t n = static_cast<size_t>(e->sc.width) * e->sc.height;
     if (n == 0) return RB_OK;
     rb::DevBuf<rb_guide> joined;
     HIP_TRY(e, joined.resize(n));
@@ -1026,9 +1026,9 @@ int lightmap_events(rb_engine* e) {
 
 // the surfel stage over the engine's scene between its own event pair, queued on the engine's stream
 int lightmap_stage_surfels(rb_engine* e, const rb::KParams& p, const rb_lightmap_params& prm, rb_surfel* d_surfels, uint32_t* d_owners) {
-    const uint32_t n_tris = e->n_tris;
+    const uint32_t n_tris = e->sc.n_tris;
     if (const hipError_t st = hipEventRecord(e->ev_lm[0], e->stream)) return static_cast<int>(st);
-    const int st = lightmap_generate(prm, e->tris.ptr, n_tris, p.u.bvh_triangle_count, e->uvs.ptr, e->n_uvs, e->lm_iota.ptr, e->lm_ptris.ptr,
+    const int st = lightmap_generate(prm, e->tris.ptr, n_tris, p.u.bvh_triangle_count, e->uvs.ptr, e->sc.n_uvs, e->lm_iota.ptr, e->lm_ptris.ptr,
                                      e->lm_pshade.ptr, e->lm_work.ptr, d_surfels, d_owners, e->stream);
     if (st) return st;
     if (const hipError_t st1 = hipEventRecord(e->ev_lm[1], e->stream)) return static_cast<int>(st1);
@@ -1038,7 +1038,7 @@ int lightmap_stage_surfels(rb_engine* e, const rb::KParams& p, const rb_lightmap
 
 // the scratch of the surfel stage beside the caller's buffers
 int lightmap_scratch(rb_engine* e, size_t n, bool owners) {
-    const uint32_t n_tris = e->n_tris;
+    const uint32_t n_tris = e->sc.n_tris;
     HIP_TRY(e, e->lm_iota.reserve(n_tris));
     HIP_TRY(e, e->lm_ptris.reserve(n_tris));
     HIP_TRY(e, e->lm_pshade.reserve(n_tris));
@@ -1205,7 +1205,7 @@ int rb_render_hits(rb_engine* e, rb_hit* hits_out, rb_surface* surf_out) {
             if (const int rc = require_ready(t)) return rc;
             // a multi-device handle: the whole frame on devices[0] (one ray per pixel is not worth a gather); a sharded engine: its own rows
             const bool sharded = t == e && t->opt.shard_count > 1;
-            return pixel_hits_locked(t, 0, 0, t->width, sharded ? t->padded_rows : t->height, !sharded, hits_out, surf_out);
+            return pixel_hits_locked(t, 0, 0, t->sc.width, sharded ? t->sc.padded_rows : t->sc.height, !sharded, hits_out, surf_out);
         });
 }
 
@@ -1214,8 +1214,8 @@ int rb_pick(rb_engine* e, uint32_t px, uint32_t py, rb_hit* hit_out, rb_surface*
         e, [&]() -> int { return hit_out ? RB_OK : rb::fail(e, RB_ERR_NULL_ARGUMENT, "hit_out is NULL"); },
         [&](rb_engine* t) {
             if (const int rc = require_ready(t)) return rc;
-            if (px >= t->width || py >= t->height)
-                return rb::fail(t, RB_ERR_INVALID_OPTIONS, "pixel (%u, %u) is outside the %u x %u image", px, py, t->width, t->height);
+            if (px >= t->sc.width || py >= t->sc.height)
+                return rb::fail(t, RB_ERR_INVALID_OPTIONS, "pixel (%u, %u) is outside the %u x %u image", px, py, t->sc.width, t->sc.height);
             return pixel_hits_locked(t, px, py, 1, 1, true, hit_out, surf_out);
         });
 }

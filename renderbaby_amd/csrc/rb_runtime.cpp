@@ -47,101 +47,9 @@ namespace {
 
 using rb::copy_error, rb::ensure_prepared, rb::make_params, rb::require_ready;   // declared in rb_engine.hpp: rb_queries.cpp calls them too
 
-const char* kFieldNames[9] = {"uniforms", "spheres", "uvs", "meshes", "lights",
-                              "bvh_nodes", "bvh_indices", "bvh_triangles", "textures"};
-
-const rb_field* field_at(const rb_config* c, int i) {
-    const rb_field* f[9] = {&c->uniforms, &c->spheres, &c->uvs, &c->meshes, &c->lights,
-                            &c->bvh_nodes, &c->bvh_indices, &c->bvh_triangles, &c->textures};
-    return f[i];
-}
-
-int check_fields(rb_engine* e, const rb_config* cfg) {
-    if (!cfg) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "config is NULL");
-    for (int i = 0; i < 9; ++i) {
-        const rb_field* f = field_at(cfg, i);
-        if (f->change > RB_DELETE) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "%s: bad change tag %u", kFieldNames[i], f->change);
-        if ((f->change == RB_CREATE || f->change == RB_UPDATE) && f->count > 0 && !f->ptr)
-            return rb::fail(e, RB_ERR_NULL_ARGUMENT, "%s: count %zu with NULL pointer", kFieldNames[i], f->count);
-    }
-    if ((cfg->uniforms.change == RB_CREATE || cfg->uniforms.change == RB_UPDATE) && cfg->uniforms.count != 1)
-        return rb::fail(e, RB_ERR_INVALID_UNIFORMS, "uniforms: expected exactly one rb_uniforms, got %zu", cfg->uniforms.count);
-    return RB_OK;
-}
-
-// RenderConfig::validate_init -- render_config.rs:163-185
-int validate_init(rb_engine* e, const rb_config* c) {
-    if (c->uniforms.change != RB_CREATE) return rb::fail(e, RB_ERR_INVALID_UNIFORMS, "Invalid Uniforms");
-    if (c->spheres.change != RB_CREATE) return rb::fail(e, RB_ERR_INVALID_SPHERES, "Invalid Spheres");
-    if (c->uvs.change != RB_CREATE) return rb::fail(e, RB_ERR_INVALID_UVS, "Invalid UVs");
-    if (c->meshes.change != RB_CREATE) return rb::fail(e, RB_ERR_INVALID_MESHES, "Invalid Meshes");
-    if (c->lights.change != RB_CREATE) return rb::fail(e, RB_ERR_INVALID_LIGHTS, "Invalid Lights");
-    if (c->textures.change != RB_CREATE) return rb::fail(e, RB_ERR_INVALID_TEXTURES, "Invalid Textures");
-    return RB_OK;
-}
-
-bool has_data(const rb_field& f) { return f.change == RB_CREATE || f.change == RB_UPDATE; }
-
-// RenderConfig::validate -- render_config.rs:187-268
-int validate(rb_engine* e, const rb_config* c) {
-    if (has_data(c->uniforms)) {
-        const rb_uniforms* u = static_cast<const rb_uniforms*>(c->uniforms.ptr);
-        if (!(u->camera.pane_distance >= 0.0f && u->camera.pane_distance <= 100.0f))
-            return rb::fail(e, RB_ERR_PANE_DISTANCE_OUT_OF_BOUNDS, "Pane-Distance is out of bounds");
-        if (!(u->camera.pane_width >= 0.0f && u->camera.pane_width <= 1000.0f))
-            return rb::fail(e, RB_ERR_PANE_WIDTH_OUT_OF_BOUNDS, "Pane-Distance is out of bounds");  // sic, :631-633
-        const float* d = u->camera.dir;
-        const float len_sq = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
-        if (len_sq < 1.1920929e-07f) return rb::fail(e, RB_ERR_INVALID_CAMERA_DIRECTION, "Invalid camera direction");
-    } else if (c->uniforms.change == RB_DELETE) {
-        return rb::fail(e, RB_ERR_CANNOT_DELETE_NONEXISTENT, "Cannot delete none existent");
-    }
-    if (has_data(c->spheres)) {
-        const rb_sphere* s = static_cast<const rb_sphere*>(c->spheres.ptr);
-        for (size_t i = 0; i < c->spheres.count; ++i)
-            if (s[i].radius <= 0.0f) return rb::fail(e, RB_ERR_INVALID_SPHERES, "Invalid Spheres");
-    }
-    if (has_data(c->uvs)) {
-        if (c->uvs.count % 2 != 0) return rb::fail(e, RB_ERR_INVALID_UVS, "Invalid UVs");
-    } else if (c->uvs.change == RB_DELETE) {
-        return rb::fail(e, RB_ERR_UNSUPPORTED_DELETE, "not yet implemented: Implement UVs Deletion");
-    }
-    if (c->meshes.change == RB_DELETE)
-        return rb::fail(e, RB_ERR_UNSUPPORTED_DELETE, "not yet implemented: Implement meshes Deletion");
-    if (has_data(c->lights)) {
-        const rb_point_light* l = static_cast<const rb_point_light*>(c->lights.ptr);
-        for (size_t i = 0; i < c->lights.count; ++i)
-            if (l[i].radius <= 0.0f) return rb::fail(e, RB_ERR_INVALID_LIGHTS, "Invalid Lights");
-    } else if (c->lights.change == RB_DELETE) {
-        return rb::fail(e, RB_ERR_UNSUPPORTED_DELETE, "not yet implemented: Implement lights Deletion");
-    }
-    if (c->textures.change == RB_DELETE)
-        return rb::fail(e, RB_ERR_UNSUPPORTED_DELETE, "not yet implemented: Implement textures Deletion");
-    return RB_OK;
-}
-
-struct StripeGeometry {
-    uint32_t local = 0, padded = 0;
-};
-StripeGeometry stripe_geometry(const rb_options& opt, uint32_t h) {
-    const uint32_t sc = opt.shard_count > 1 ? opt.shard_count : 1;
-    const uint32_t sr = opt.stripe_rows ? opt.stripe_rows : rb::kDefaultStripeRows;
-    StripeGeometry g{h, h};
-    if (sc > 1) {
-        const uint32_t stripes = (h + sr - 1) / sr;
-        const uint32_t per_rank = (stripes + sc - 1) / sc;  // equal on every rank (padded)
-        g.padded = per_rank * sr;
-        uint32_t owned = 0;  // stripes this rank renders
-        for (uint32_t s = opt.shard_rank; s < stripes; s += sc) owned++;
-        g.local = owned * sr;  // the kernels additionally bound rows by global y < height
-    }
-    return g;
-}
-
 // grow_resolution -- buffers.rs:171-180 (+ the stripe geometry of the sharded case)
-int resize_frame(rb_engine* e, uint32_t w, uint32_t h) {
-    const StripeGeometry g = stripe_geometry(e->opt, h);
-    const uint64_t px = static_cast<uint64_t>(w) * g.padded;
+int resize_frame(rb_engine* e, uint32_t w, uint32_t h, const rb::ShardLayout& rows) {
+    const uint64_t px = static_cast<uint64_t>(w) * rows.padded;
     if (px >= (1ull << 31)) return rb::fail(e, RB_ERR_INVALID_UNIFORMS, "frame of %u x %u pixels is too large", w, h);
     // the frame's buffers are about to be replaced: launches queued on the engine's stream and, joined into it, on the
     // accumulate stream may still use them
@@ -157,30 +65,24 @@ int resize_frame(rb_engine* e, uint32_t w, uint32_t h) {
         HIP_TRY(e, hipMemsetAsync(s.accum.ptr, 0, px * 16, e->stream));
         HIP_TRY(e, hipMemsetAsync(s.rgba.ptr, 0, px * 4, e->stream));
     }
-    e->width = w;
-    e->height = h;
-    e->local_rows = g.local;
-    e->padded_rows = g.padded;
     return RB_OK;
 }
 
-int upload_textures(rb_engine* e, const rb_field& f) {
-    const rb_texture* t = static_cast<const rb_texture*>(f.ptr);
+int upload_textures(rb_engine* e, const rb_texture* t, size_t count) {
     std::vector<uint32_t> data;
     std::vector<rb_texture_info> info;
     uint32_t offset = 0;
-    for (size_t i = 0; i < f.count; ++i) {  // process_textures, buffers.rs:151-168
+    for (size_t i = 0; i < count; ++i) {  // process_textures, buffers.rs:151-168
         const size_t n = static_cast<size_t>(t[i].width) * t[i].height;
         info.push_back(rb_texture_info{offset, t[i].width, t[i].height, 0});
         data.insert(data.end(), t[i].rgba_data, t[i].rgba_data + n);
         offset += t[i].width * t[i].height;
     }
-    int rc = rb::upload(e, e->tex_data, data.data(), data.size(), nullptr, true);
+    int rc = rb::upload(e, e->tex_data, data.data(), data.size(), true);
     if (rc) return rc;
-    rc = rb::upload(e, e->tex_info, info.data(), info.size(), nullptr, true);
+    rc = rb::upload(e, e->tex_info, info.data(), info.size(), true);
     if (rc) return rc;
     HIP_TRY(e, hipStreamSynchronize(e->stream));  // `data`/`info` are locals
-    e->n_tex = static_cast<uint32_t>(f.count);
     return RB_OK;
 }
 
@@ -201,181 +103,72 @@ int prep_materials(rb_engine* e, rb_material* first, size_t stride, size_t n) {
     return RB_OK;
 }
 
-// What an update does with one non-uniform field.  `first` = the engine's first update
-// (gpu_wrapper.rs:117-163: only Create is acted on); otherwise :196-294.
-enum class Act { None, Take, Delete };
-Act field_action(int idx, const rb_field& f, bool first) {
-    const bool bvh_field = (idx >= 5 && idx <= 7);
-    if (first) return f.change == RB_CREATE ? Act::Take : Act::None;
-    if (f.change == RB_UPDATE) return Act::Take;
-    if (f.change == RB_DELETE) return Act::Delete;
-    if (f.change == RB_CREATE) return bvh_field ? Act::Take : Act::None;  // "Create not allowed after initialization" except BVH (:242-280)
-    return Act::None;
+// the host's copy of a mesh field of n elements just uploaded, or its staleness (ensure_host_mesh fetches it if need be)
+template <typename T>
+void keep_host_copy(rb_engine* e, const void* src, size_t n, std::vector<T>& copy, size_t& len, bool& stale) {
+    if (!rb::mesh_walks(e->opt).host_mesh) return;
+    len = n;
+    stale = rb::host_copy_can_wait(e, n);
+    if (stale) std::vector<T>().swap(copy);
+    else copy.assign(static_cast<const T*>(src), static_cast<const T*>(src) + n);
 }
 
-int apply_field(rb_engine* e, int idx, const rb_field& f, bool first) {
-    const Act act = field_action(idx, f, first);
-    if (act == Act::None) return RB_OK;
-    const bool del = act == Act::Delete;
-    const void* src = del ? nullptr : f.ptr;
-    const size_t n = del ? 0 : f.count;
+// One field of an update as the plan decides it (rb_update_plan.hpp): what needs the device or the engine.  The field's
+// facts change when its buffer has been written.
+int apply_field(rb_engine* e, rb::Field f, const rb::UpdatePlan& pl, const rb_config* cfg) {
+    using namespace rb;
+    if (f == kUniforms) {   // gpu_wrapper.rs:122-136 / :165-192
+        if (pl.act[f] == Act::Take) {
+            const rb_uniforms* u = static_cast<const rb_uniforms*>(cfg->uniforms.ptr);
+            if (pl.resize || e->slot[0].accum.ptr == nullptr)
+                if (const int rc = resize_frame(e, u->width, u->height, pl.frame)) return rc;
+            e->prh.total_samples = u->total_samples;  // ProgressiveRenderHelper::update (:47-52)
+            e->prh.total_passes = (u->total_samples + e->prh.samples_per_pass - 1) / e->prh.samples_per_pass;
+        }
+        commit_field(e->sc, pl, cfg, f);
+        return RB_OK;
+    }
+    if (pl.act[f] == Act::None) return RB_OK;
+    const bool del = pl.act[f] == Act::Delete;
+    const void* src = del ? nullptr : field_of(cfg, f).ptr;
+    const size_t n = del ? 0 : field_of(cfg, f).count;
     int rc = RB_OK;
-    switch (idx) {
-        case 1:
-            rc = rb::upload(e, e->spheres, src, n, nullptr, true);
-            e->n_spheres = static_cast<uint32_t>(n);
-            if (!rc) rc = prep_materials(e, e->spheres.ptr ? &e->spheres.ptr->material : nullptr, sizeof(rb_sphere), n);
+    switch (f) {
+        case kSpheres: rc = upload(e, e->spheres, src, n, true); break;
+        case kUvs: rc = upload(e, e->uvs, src, n, true); break;
+        case kMeshes: rc = upload(e, e->meshes, src, n, true); break;
+        case kLights: rc = upload(e, e->lights, src, n, !del); break;   // delete_lights: no element at all (buffers.rs:389-391)
+        case kNodes: rc = upload(e, e->nodes, src, n, true); break;
+        case kIndices: rc = upload(e, e->indices, src, n, true); break;
+        case kTriangles: rc = upload(e, e->tris, src, n, true); break;
+        case kTextures: rc = upload_textures(e, static_cast<const rb_texture*>(src), n); break;
+        default: break;
+    }
+    if (rc) return rc;
+    commit_field(e->sc, pl, cfg, f);
+    switch (f) {
+        case kSpheres:
+            rc = prep_materials(e, &e->spheres.ptr->material, sizeof(rb_sphere), n);
             if (!rc) rc = prep_sphere_scan(e);
-            if (!rc) rc = rb::build_sphere_bvh(e, static_cast<const rb_sphere*>(src), n);
+            if (!rc) rc = build_sphere_bvh(e, static_cast<const rb_sphere*>(src), n);
             break;
-        case 2: rc = rb::upload(e, e->uvs, src, n, nullptr, true); e->n_uvs = static_cast<uint32_t>(n); break;
-        case 3:
-            rc = rb::upload(e, e->meshes, src, n, nullptr, true);
-            e->n_meshes = static_cast<uint32_t>(n);
-            if (!rc) rc = prep_materials(e, e->meshes.ptr ? &e->meshes.ptr->material : nullptr, sizeof(rb_mesh), n);
-            break;
-        case 4:
-            // delete_lights creates a 4-byte buffer (buffers.rs:389-391): arrayLength() == 0
-            rc = rb::upload(e, e->lights, src, n, &e->n_lights, !del);
-            if (del) e->n_lights = 0;
-            if (!rc) rc = prep_materials(e, e->lights.ptr ? &e->lights.ptr->material : nullptr, sizeof(rb_point_light), e->n_lights);
-            break;
-        case 5:
-            rc = rb::upload(e, e->nodes, src, n, nullptr, true);
-            e->n_nodes = static_cast<uint32_t>(n);
-            e->host_nodes.assign(static_cast<const rb_bvh_node*>(src), static_cast<const rb_bvh_node*>(src) + n);
+        case kMeshes: rc = prep_materials(e, &e->meshes.ptr->material, sizeof(rb_mesh), n); break;
+        case kLights: rc = prep_materials(e, e->lights.ptr ? &e->lights.ptr->material : nullptr, sizeof(rb_point_light), e->sc.n_lights); break;
+        case kNodes:
             e->prep_dirty = true;
             e->tree = {n ? "caller" : "", 0.0f};
             break;
-        case 6:
-            rc = rb::upload(e, e->indices, src, n, &e->n_indices, true);
+        case kIndices:
             e->prep_dirty = true;
-            if (rb::mesh_walks(e->opt).host_mesh) {
-                e->host_index_len = n;
-                e->host_indices_stale = rb::host_copy_can_wait(e, n);
-                if (e->host_indices_stale) std::vector<uint32_t>().swap(e->host_indices);
-                else e->host_indices.assign(static_cast<const uint32_t*>(src), static_cast<const uint32_t*>(src) + n);
-            }
+            keep_host_copy(e, src, n, e->host_indices, e->host_index_len, e->host_indices_stale);
             break;
-        case 7:
-            rc = rb::upload(e, e->tris, src, n, nullptr, true);
-            e->n_tris = static_cast<uint32_t>(n);
+        case kTriangles:
             e->prep_dirty = true;
-            if (rb::mesh_walks(e->opt).host_mesh) {
-                e->host_tri_len = n;
-                e->host_tris_stale = rb::host_copy_can_wait(e, n);
-                if (e->host_tris_stale) std::vector<rb_gpu_triangle>().swap(e->host_tris);
-                else e->host_tris.assign(static_cast<const rb_gpu_triangle*>(src), static_cast<const rb_gpu_triangle*>(src) + n);
-            }
-            break;
-        case 8:
-            if (del) { rb_field empty{RB_UPDATE, nullptr, 0}; rc = upload_textures(e, empty); }
-            else rc = upload_textures(e, f);
+            keep_host_copy(e, src, n, e->host_tris, e->host_tri_len, e->host_tris_stale);
             break;
         default: break;
     }
     return rc;
-}
-
-// Host-side checks that stand in for WGSL's robust buffer access: anything that would make a HIP kernel
-// read out of bounds or loop forever is refused.  They run on the scene the update WOULD produce -- the
-// incoming fields merged with the kept host copies -- before a single buffer is touched, so a refused
-// rb_update leaves the previous scene live and renderable.
-struct ScenePlan {
-    uint32_t bvh_stack = 0, max_mesh_index = 0;
-};
-int validate_scene(rb_engine* e, const rb_config* cfg, bool first, ScenePlan& plan) {
-    const Act a_nodes = field_action(5, cfg->bvh_nodes, first), a_idx = field_action(6, cfg->bvh_indices, first),
-              a_tris = field_action(7, cfg->bvh_triangles, first), a_meshes = field_action(3, cfg->meshes, first);
-    const bool take_uniforms = first ? (cfg->uniforms.change == RB_CREATE) : (cfg->uniforms.change == RB_UPDATE);
-    // ---- the tree the kernels would walk
-    const rb_bvh_node* nodes = e->host_nodes.data();
-    uint32_t n_nodes = static_cast<uint32_t>(e->host_nodes.size());
-    rb::TreeSkeleton own;   // RB_FLAG_BUILD_TREE: the tree the engine will build -- its shape follows from the triangle count
-    const bool own_tree = rb::builds_tree(e);
-    if (own_tree && (cfg->bvh_nodes.change != RB_KEEP || cfg->bvh_indices.change != RB_KEEP))
-        return rb::fail(e, RB_ERR_INVALID_BVH, "the engine builds the tree itself (RB_FLAG_BUILD_TREE): bvh_nodes and bvh_indices must be Keep");
-    if (own_tree && a_tris == Act::Take) {
-        const rb_gpu_triangle* t = static_cast<const rb_gpu_triangle*>(cfg->bvh_triangles.ptr);
-        if (cfg->bvh_triangles.count >= (1ull << 31)) return rb::fail(e, RB_ERR_INVALID_BVH, "too many triangles");
-        const size_t bad = rb::first_non_finite(t, cfg->bvh_triangles.count);
-        if (bad < cfg->bvh_triangles.count)
-            return rb::fail(e, RB_ERR_INVALID_BVH, "triangle %zu has a non-finite vertex coordinate", bad);
-        rb::bvh_skeleton(cfg->bvh_triangles.count, own);
-        nodes = own.nodes.data();
-        n_nodes = static_cast<uint32_t>(own.nodes.size());
-    } else if (own_tree && a_tris == Act::Delete) {
-        n_nodes = 0;
-    } else if (a_nodes == Act::Take) {
-        nodes = static_cast<const rb_bvh_node*>(cfg->bvh_nodes.ptr);
-        if (cfg->bvh_nodes.count >= (1ull << 31)) return rb::fail(e, RB_ERR_INVALID_BVH, "too many BVH nodes");
-        n_nodes = static_cast<uint32_t>(cfg->bvh_nodes.count);
-    } else if (a_nodes == Act::Delete) {
-        n_nodes = 0;
-    }
-    uint64_t index_len = e->n_indices;  // arrayLength(&bvh_indices): an empty vector still has one element
-    if (a_idx == Act::Take) index_len = std::max<uint64_t>(cfg->bvh_indices.count, 1);
-    else if (a_idx == Act::Delete) index_len = 1;
-    if (own_tree && a_tris == Act::Take) index_len = std::max<uint64_t>(cfg->bvh_triangles.count, 1);
-    else if (own_tree && a_tris == Act::Delete) index_len = 1;
-    if (index_len >= (1ull << 31)) return rb::fail(e, RB_ERR_INVALID_BVH, "too many BVH indices");
-    plan.bvh_stack = e->bvh_stack;
-    if (n_nodes > 0) {
-        std::string why;
-        uint32_t depth = 0;
-        if (!rb::bvh_validate(nodes, n_nodes, rb::kStackDepth, why, &depth)) return rb::fail(e, RB_ERR_INVALID_BVH, "%s", why.c_str());
-        plan.bvh_stack = depth;
-        for (uint32_t i = 0; i < n_nodes; ++i) {
-            const rb_bvh_node& n = nodes[i];
-            if (n.primitive_count > 0 && static_cast<uint64_t>(n.first_primitive) + n.primitive_count > index_len)
-                return rb::fail(e, RB_ERR_INVALID_BVH, "leaf %u covers [%u, +%u) of %llu bvh_indices", i, n.first_primitive,
-                            n.primitive_count, static_cast<unsigned long long>(index_len));
-        }
-    }
-    // ---- every triangle's material must exist (shader.wgsl:370 reads meshes[tri.mesh_index])
-    uint64_t n_tris = e->n_tris;
-    plan.max_mesh_index = e->max_mesh_index;
-    if (a_tris == Act::Take) {
-        const rb_gpu_triangle* t = static_cast<const rb_gpu_triangle*>(cfg->bvh_triangles.ptr);
-        uint32_t mx = 0;
-        for (size_t i = 0; i < cfg->bvh_triangles.count; ++i) mx = std::max(mx, t[i].mesh_index);
-        plan.max_mesh_index = mx;
-        n_tris = cfg->bvh_triangles.count;
-        if (n_tris >= (1ull << 31)) return rb::fail(e, RB_ERR_INVALID_BVH, "too many triangles");
-    } else if (a_tris == Act::Delete) {
-        n_tris = 0;
-        plan.max_mesh_index = 0;
-    }
-    uint64_t n_meshes = e->n_meshes;
-    if (a_meshes == Act::Take) n_meshes = cfg->meshes.count;
-    const uint32_t color_hash = take_uniforms ? static_cast<const rb_uniforms*>(cfg->uniforms.ptr)->color_hash_enabled
-                                              : e->uniforms.color_hash_enabled;
-    if (n_tris > 0 && color_hash == 0 && plan.max_mesh_index >= n_meshes)
-        return rb::fail(e, RB_ERR_INVALID_MESHES, "a triangle references mesh %u of %llu", plan.max_mesh_index,
-                    static_cast<unsigned long long>(n_meshes));
-    // ---- textures and the frame
-    if (field_action(8, cfg->textures, first) == Act::Take) {
-        const rb_texture* t = static_cast<const rb_texture*>(cfg->textures.ptr);
-        for (size_t i = 0; i < cfg->textures.count; ++i) {
-            if (t[i].width == 0 || t[i].height == 0) return rb::fail(e, RB_ERR_INVALID_TEXTURES, "texture %zu is empty", i);
-            if (!t[i].rgba_data) return rb::fail(e, RB_ERR_INVALID_TEXTURES, "texture %zu has no data", i);
-        }
-    }
-    if (take_uniforms) {
-        const rb_uniforms* u = static_cast<const rb_uniforms*>(cfg->uniforms.ptr);
-        const uint64_t px = static_cast<uint64_t>(u->width) * stripe_geometry(e->opt, u->height).padded;
-        if (px >= (1ull << 31)) return rb::fail(e, RB_ERR_INVALID_UNIFORMS, "frame of %u x %u pixels is too large", u->width, u->height);
-    }
-    return RB_OK;
-}
-
-// update_uniforms count patch-up -- gpu_wrapper.rs:475-495: Create/Update overwrite the count with the
-// vector length, Delete zeroes it, Keep leaves the caller's value (clamped to the buffer here so that a
-// stale count cannot read out of bounds; the WGSL relies on robust buffer access for that).
-uint32_t patch_count(uint32_t change, uint32_t given, uint32_t len) {
-    if (change == RB_CREATE || change == RB_UPDATE) return len;
-    if (change == RB_DELETE) return 0u;
-    return std::min(given, len);
 }
 
 }  // namespace
@@ -384,9 +177,9 @@ uint32_t patch_count(uint32_t change, uint32_t given, uint32_t len) {
 int rb::ensure_prepared(rb_engine* e) {
     // shader.wgsl:336 skips triangle ids >= uniforms.bvh_triangle_count: the prepared triangles carry that
     // guard as their `valid` word, so they depend on the (patched) count as well as on the buffers
-    const uint32_t tri_count = patch_count(e->last_change_tris, e->uniforms.bvh_triangle_count, e->n_tris);
+    const uint32_t tri_count = rb::triangle_count(e->sc);
     if (!e->prep_dirty && e->prep_tri_count == tri_count) return RB_OK;
-    const uint32_t len = e->n_indices;  // arrayLength(&bvh_indices) >= 1
+    const uint32_t len = e->sc.n_indices;  // arrayLength(&bvh_indices) >= 1
     HIP_TRY(e, e->ptris.resize(len));
     HIP_TRY(e, e->pshade.resize(len));
     int rc = rb::launch_prep_tris(e->tris.ptr, tri_count, e->indices.ptr, len, e->ptris.ptr, e->pshade.ptr, e->stream);
@@ -401,10 +194,10 @@ int rb::ensure_prepared(rb_engine* e) {
 
 rb::KParams rb::make_params(rb_engine* e, uint32_t first_pass, uint32_t n_passes, int src, int dst) {
     rb::KParams p{};
-    p.u = e->uniforms;
-    p.u.spheres_count = patch_count(e->last_change_spheres, e->uniforms.spheres_count, std::min(e->n_spheres, e->last_spheres_sent));
-    p.u.bvh_node_count = patch_count(e->last_change_nodes, e->uniforms.bvh_node_count, e->n_nodes);
-    p.u.bvh_triangle_count = patch_count(e->last_change_tris, e->uniforms.bvh_triangle_count, e->n_tris);
+    p.u = e->sc.uniforms;
+    p.u.spheres_count = rb::spheres_count(e->sc);
+    p.u.bvh_node_count = rb::node_count(e->sc);
+    p.u.bvh_triangle_count = rb::triangle_count(e->sc);
     p.spheres = e->spheres.ptr;
     p.sph_scan = e->sph_scan.ptr;
     p.lights = e->lights.ptr;
@@ -423,18 +216,19 @@ rb::KParams rb::make_params(rb_engine* e, uint32_t first_pass, uint32_t n_passes
     p.out_rgba = e->slot[dst].rgba.ptr;
     p.counters = e->counters.ptr;
     p.queue = e->queue.ptr;
-    p.n_lights = e->n_lights;
-    p.n_meshes = e->n_meshes;
-    p.index_len = e->n_indices;
-    p.n_uvs = e->n_uvs;
-    p.n_tex = e->n_tex;
+    p.n_lights = e->sc.n_lights;
+    p.n_meshes = e->sc.n_meshes;
+    p.index_len = e->sc.n_indices;
+    p.n_uvs = e->sc.n_uvs;
+    p.n_tex = e->sc.n_tex;
     p.first_pass = first_pass;
     p.n_passes = n_passes;
     p.samples_per_pass = e->prh.samples_per_pass;
-    p.shard_rank = e->opt.shard_rank;
-    p.shard_count = e->opt.shard_count > 1 ? e->opt.shard_count : 1;
-    p.stripe_rows = e->opt.stripe_rows ? e->opt.stripe_rows : rb::kDefaultStripeRows;
-    p.local_rows = e->local_rows;
+    const rb::ShardLayout rows = e->sc.layout(e->sc.height);
+    p.shard_rank = rows.rank;
+    p.shard_count = rows.count;
+    p.stripe_rows = rows.stripe;
+    p.local_rows = e->sc.local_rows;
     p.colors = e->colors.ptr;
     // stack_depth: the largest need of the walks a launch can run, each of which must fit the column (rb_internal.hpp)
     p.stack_depth = rb::accel_params(e, p);
@@ -449,9 +243,9 @@ rb::KParams rb::make_params(rb_engine* e, uint32_t first_pass, uint32_t n_passes
 }
 
 int rb::require_ready(rb_engine* e) {
-    if (!e->initialized) return rb::fail(e, RB_ERR_NOT_INITIALIZED, "engine has not received its first update");
+    if (!e->sc.initialized) return rb::fail(e, RB_ERR_NOT_INITIALIZED, "engine has not received its first update");
     if (!e->scene_valid) return rb::fail(e, RB_ERR_DEVICE, "the last update failed half-way on the device; send the scene again");
-    if (!e->have_uniforms) return rb::fail(e, RB_ERR_UNIFORMS_NOT_INITIALIZED, "Uniforms must be initialized");
+    if (!e->sc.have_uniforms) return rb::fail(e, RB_ERR_UNIFORMS_NOT_INITIALIZED, "Uniforms must be initialized");
     return RB_OK;
 }
 
@@ -469,7 +263,7 @@ void rb::copy_error(rb_engine* g, const rb_engine* part) {
 namespace {
 
 int clear_accum(rb_engine* e) {
-    const size_t px = static_cast<size_t>(e->width) * e->padded_rows;
+    const size_t px = static_cast<size_t>(e->sc.width) * e->sc.padded_rows;
     e->spec_valid = false;
     if (px) HIP_TRY(e, hipMemsetAsync(e->slot[e->cur].accum.ptr, 0, px * 16, e->stream));
     return RB_OK;
@@ -518,8 +312,8 @@ uint64_t color_budget_bytes(rb_engine* e) {
 int reserve_colors(rb_engine* e, uint32_t n_passes, rb::ColorPlan* plan_out) {
     rb::ColorPlan pl;
     pl.chunk = e->opt.passes_per_launch ? e->opt.passes_per_launch : n_passes;
-    if (rb::kernel_of(e->opt) == RB_KERNEL_STREAM && n_passes != 0 && e->width != 0 && e->local_rows != 0) {
-        const uint64_t tiles = static_cast<uint64_t>((e->width + 7) / 8) * ((e->local_rows + 7) / 8);
+    if (rb::kernel_of(e->opt) == RB_KERNEL_STREAM && n_passes != 0 && e->sc.width != 0 && e->sc.local_rows != 0) {
+        const uint64_t tiles = static_cast<uint64_t>((e->sc.width + 7) / 8) * ((e->sc.local_rows + 7) / 8);
         const uint64_t per_pass = tiles * 64ull * e->prh.samples_per_pass;  // items per pass
         pl = rb::plan_colors(per_pass, n_passes, e->opt.passes_per_launch, color_budget_bytes(e) / 16ull);
         if (pl.chunk == 0) return rb::fail(e, RB_ERR_INVALID_UNIFORMS, "frame too large for one launch");
@@ -638,7 +432,7 @@ int queue_group(rb_engine* e, uint32_t first_pass, uint32_t n_passes, int src, i
 int dispatch(rb_engine* e, uint32_t first_pass, uint32_t n_passes, int src, int dst) {
     int rc = ensure_prepared(e);
     if (rc) return rc;
-    if (n_passes == 0 || e->width == 0 || e->local_rows == 0) {
+    if (n_passes == 0 || e->sc.width == 0 || e->sc.local_rows == 0) {
         e->last_launches = 0;
         return RB_OK;
     }
@@ -666,7 +460,7 @@ int dispatch(rb_engine* e, uint32_t first_pass, uint32_t n_passes, int src, int 
 int read_slot_rgba(rb_engine* e, int slot, uint8_t* out) {
     if (!out) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "rgba_out is NULL");
     const uint32_t sc = e->opt.shard_count > 1 ? e->opt.shard_count : 1;
-    const size_t bytes = static_cast<size_t>(e->width) * 4 * (sc == 1 ? e->height : e->padded_rows);
+    const size_t bytes = static_cast<size_t>(e->sc.width) * 4 * (sc == 1 ? e->sc.height : e->sc.padded_rows);
     if (bytes == 0) return RB_OK;
     // Page-locked destination (rb_host_alloc, or memory the caller registered with HIP): a DMA on the copy
     // stream straight into it, behind the slot's event -- no staging, no host-side copy.
@@ -690,56 +484,24 @@ int read_rgba(rb_engine* e, uint8_t* out) {
 }
 
 int update_fields(rb_engine* e, const rb_config* cfg) {
-    int rc = check_fields(e, cfg);
-    if (rc) return rc;
-    const bool first = !e->initialized;
-    rc = first ? validate_init(e, cfg) : validate(e, cfg);
-    if (rc) return rc;
-    ScenePlan plan;
-    rc = validate_scene(e, cfg, first, plan);
-    if (rc) return rc;   // nothing has been touched: the previous scene stays live
+    rb::UpdatePlan plan;
+    std::string why;
+    if (const int rc = rb::plan_update(e->sc, cfg, plan, why)) return rb::fail(e, rc, "%s", why.c_str());   // nothing has been touched: the previous scene stays live
 
     // ---- from here on the buffers change; a device failure half-way leaves the engine refusing to render
     e->scene_valid = false;
     e->spec_valid = false;
     e->color_budget = 0;
     e->dn_guides_valid = false;   // the denoiser's guides are this scene's and this camera's
-    // uniforms (gpu_wrapper.rs:122-136 / :165-192)
-    const bool take_uniforms = first ? (cfg->uniforms.change == RB_CREATE) : (cfg->uniforms.change == RB_UPDATE);
-    if (take_uniforms) {
-        const rb_uniforms* u = static_cast<const rb_uniforms*>(cfg->uniforms.ptr);
-        if (u->width != e->width || u->height != e->height || e->slot[0].accum.ptr == nullptr) {
-            rc = resize_frame(e, u->width, u->height);
-            if (rc) return rc;
-        }
-        e->uniforms = *u;
-        e->prh.total_samples = u->total_samples;  // ProgressiveRenderHelper::update (:47-52)
-        e->prh.total_passes = (u->total_samples + e->prh.samples_per_pass - 1) / e->prh.samples_per_pass;
+    for (uint32_t f = 0; f < rb::kFieldCount; ++f)
+        if (const int rc = apply_field(e, static_cast<rb::Field>(f), plan, cfg)) return rc;
+    if (plan.own_tree != rb::OwnTree::Keep) {   // the tree follows the triangles field (RB_FLAG_BUILD_TREE)
+        const bool rebuild = plan.own_tree == rb::OwnTree::Rebuild;
+        if (const int rc = rb::build_engine_tree(e, static_cast<const rb_gpu_triangle*>(rebuild ? cfg->bvh_triangles.ptr : nullptr),
+                                                 rebuild ? cfg->bvh_triangles.count : 0))
+            return rc;
     }
-    // self.rc = new_rc (:298): width()/height()/update_uniforms panic unless the *latest*
-    // config carried Create/Update uniforms (:303-329,470-473).
-    e->have_uniforms = has_data(cfg->uniforms);
-
-    for (int i = 1; i < 9; ++i) {
-        rc = apply_field(e, i, *field_at(cfg, i), first);
-        if (rc) return rc;
-    }
-    if (rb::builds_tree(e)) {   // the tree follows the triangles field (RB_FLAG_BUILD_TREE)
-        const Act a_tris = field_action(7, cfg->bvh_triangles, first);
-        if (a_tris != Act::None) {
-            rc = rb::build_engine_tree(e, static_cast<const rb_gpu_triangle*>(a_tris == Act::Take ? cfg->bvh_triangles.ptr : nullptr),
-                                   a_tris == Act::Take ? cfg->bvh_triangles.count : 0);
-            if (rc) return rc;
-        }
-    }
-    e->last_change_spheres = cfg->spheres.change;
-    // the vector's length where it was acted on is the buffer's; where a Create was ignored it is the count all the same (:476)
-    e->last_spheres_sent = has_data(cfg->spheres) ? static_cast<uint32_t>(std::min<size_t>(cfg->spheres.count, 0xFFFFFFFFu)) : 0xFFFFFFFFu;
-    e->last_change_nodes = rb::builds_tree(e) ? cfg->bvh_triangles.change : cfg->bvh_nodes.change;
-    e->last_change_tris = cfg->bvh_triangles.change;
-    e->bvh_stack = plan.bvh_stack;
-    e->max_mesh_index = plan.max_mesh_index;
-    e->initialized = true;
+    rb::commit_end(e->sc, plan);
     e->scene_valid = true;
     return RB_OK;
 }
@@ -775,8 +537,8 @@ int render_locked(rb_engine* e, uint8_t* rgba_out) {
     if (rc) return rc;
     if (e->net.nranks > 1) {  // one process per device: the frame is assembled on rank 0
         std::string why;
-        if (rb::gather_process(e->net, e->slot[e->cur].rgba.ptr, e->width, e->height, e->padded_rows,
-                               e->opt.stripe_rows ? e->opt.stripe_rows : rb::kDefaultStripeRows, e->copy_stream, e->slot[e->cur].done,
+        if (rb::gather_process(e->net, e->slot[e->cur].rgba.ptr, e->sc.width, e->sc.height, e->sc.padded_rows,
+                               e->sc.layout(e->sc.height).stripe, e->copy_stream, e->slot[e->cur].done,
                                rgba_out, why))
             return rb::fail(e, RB_ERR_DEVICE, "%s", why.c_str());
     } else {
@@ -817,7 +579,7 @@ int iter_advance(rb_engine* e, uint32_t per_frame) {
     // ---- run ahead: the next group on the other slot
     if (!(e->opt.flags & RB_FLAG_NO_RUN_AHEAD) && e->prh.current_pass < e->prh.total_passes) {
         rb::FrameSlot& o = e->slot[1 - e->cur];
-        const size_t px = static_cast<size_t>(e->width) * e->padded_rows;
+        const size_t px = static_cast<size_t>(e->sc.width) * e->sc.padded_rows;
         if (o.accum.count != px * 4 || o.rgba.count != px) {
             HIP_TRY(e, o.accum.resize(px * 4));
             HIP_TRY(e, o.rgba.resize(px));
@@ -845,8 +607,8 @@ int iter_next_locked(rb_engine* e, uint8_t* rgba_out) {
     if (rc) return rc;
     if (multiproc) {
         std::string why;
-        if (rb::gather_process(e->net, e->slot[e->cur].rgba.ptr, e->width, e->height, e->padded_rows,
-                               e->opt.stripe_rows ? e->opt.stripe_rows : rb::kDefaultStripeRows, e->copy_stream, e->slot[e->cur].done,
+        if (rb::gather_process(e->net, e->slot[e->cur].rgba.ptr, e->sc.width, e->sc.height, e->sc.padded_rows,
+                               e->sc.layout(e->sc.height).stripe, e->copy_stream, e->slot[e->cur].done,
                                rgba_out, why))
             return rb::fail(e, RB_ERR_DEVICE, "%s", why.c_str());
         return RB_OK;
@@ -872,6 +634,8 @@ rb_engine* create_single(const rb_config* cfg, const rb_options& opt) {
     rb_engine* e = new rb_engine();
     e->device = dev;
     e->opt = opt;
+    e->sc.own_tree = rb::builds_tree(opt);
+    e->sc.shard_rank = opt.shard_rank, e->sc.shard_count = opt.shard_count, e->sc.stripe_rows = opt.stripe_rows;
     // RB_REFERENCE_WALK=1 in the environment: every engine of this process walks meshes exactly as shader.wgsl:282-392 does,
     // whatever the host program's flags say -- the escape hatch from the culled walks (whose exactness is derived and fuzzed,
     // DESIGN.md section 4.2) that needs no rebuild of the host
@@ -914,11 +678,10 @@ rb_engine* create_single(const rb_config* cfg, const rb_options& opt) {
 
 bool check_create(const rb_config* cfg) {
     g_create_error.clear();
-    if (!cfg) { rb::fail(nullptr, RB_ERR_NULL_ARGUMENT, "config is NULL"); return false; }
-    if (check_fields(nullptr, cfg)) return false;
     // GpuBuffers::new panics unless these are Create (buffers.rs:74-97)
-    if (validate_init(nullptr, cfg)) return false;
-    return true;
+    int rc = rb::check_tags(cfg, g_create_error);
+    if (!rc) rc = rb::check_first_config(cfg, g_create_error);
+    return rc == RB_OK;
 }
 
 rb_engine* create_impl(const rb_config* cfg, const rb_options* opt_in) {
@@ -943,10 +706,10 @@ rb_engine* create_impl(const rb_config* cfg, const rb_options* opt_in) {
 int group_update(rb_engine* g, const rb_config* cfg) {
     for (auto& p : g->parts) PART_TRY(g, p.get(), update_locked(p.get(), cfg));
     rb_engine* p0 = g->parts[0].get();
-    g->width = p0->width;
-    g->height = p0->height;
-    g->have_uniforms = p0->have_uniforms;
-    g->initialized = p0->initialized;
+    g->sc.width = p0->sc.width;
+    g->sc.height = p0->sc.height;
+    g->sc.have_uniforms = p0->sc.have_uniforms;
+    g->sc.initialized = p0->sc.initialized;
     g->prh = p0->prh;
     return RB_OK;
 }
@@ -956,9 +719,8 @@ int group_deliver(rb_engine* g, uint8_t* rgba_out, bool fold_timing) {
     std::vector<rb::GatherSource> src;
     for (auto& p : g->parts) src.push_back(rb::GatherSource{p->device, p->copy_stream, p->slot[p->cur].done, p->slot[p->cur].rgba.ptr});
     rb_engine* p0 = g->parts[0].get();
-    const uint32_t sr = p0->opt.stripe_rows ? p0->opt.stripe_rows : rb::kDefaultStripeRows;
     std::string why;
-    if (rb::gather_group(g->net, src, p0->width, p0->height, p0->padded_rows, sr, rgba_out, why))
+    if (rb::gather_group(g->net, src, p0->sc.width, p0->sc.height, p0->sc.padded_rows, p0->sc.layout(p0->sc.height).stripe, rgba_out, why))
         return rb::fail(g, RB_ERR_DEVICE, "%s", why.c_str());
     // (the iterator folds a group's timing when it commits it: waiting for the events here would wait for the pass
     // that has just been started ahead)
@@ -1214,9 +976,9 @@ int rb_iter_set_passes_per_frame(rb_engine* e, uint32_t n) {
 int rb_get_size(const rb_engine* e, uint32_t* width, uint32_t* height) {
     if (!e) return RB_ERR_NULL_ARGUMENT;
     std::lock_guard<std::mutex> lock(const_cast<rb_engine*>(e)->mu);
-    if (!e->have_uniforms) return rb::fail(e, RB_ERR_UNIFORMS_NOT_INITIALIZED, "Uniforms must be initialized");  // gpu_wrapper.rs:313,321
-    if (width) *width = e->width;
-    if (height) *height = e->height;
+    if (!e->sc.have_uniforms) return rb::fail(e, RB_ERR_UNIFORMS_NOT_INITIALIZED, "Uniforms must be initialized");  // gpu_wrapper.rs:313,321
+    if (width) *width = e->sc.width;
+    if (height) *height = e->sc.height;
     return RB_OK;
 }
 
@@ -1308,16 +1070,16 @@ int rb_read_accumulation(rb_engine* e, float* accum_out) {
     if (rb::is_group(e)) {
         // debugging / checkpoint path: every part's rows through the host, in image order
         rb_engine* p0 = e->parts[0].get();
-        const uint32_t w = p0->width, h = p0->height, sr = p0->opt.stripe_rows ? p0->opt.stripe_rows : rb::kDefaultStripeRows;
-        const uint32_t n = static_cast<uint32_t>(e->parts.size());
-        std::vector<float> tmp(static_cast<size_t>(w) * p0->padded_rows * 4);
-        for (uint32_t r = 0; r < n; ++r) {
-            rb_engine* p = e->parts[r].get();
+        const uint32_t w = p0->sc.width, h = p0->sc.height;
+        std::vector<float> tmp(static_cast<size_t>(w) * p0->sc.padded_rows * 4);
+        for (auto& part : e->parts) {
+            rb_engine* p = part.get();
+            const rb::ShardLayout rows = p->sc.layout(h);
             PART_TRY(e, p, require_ready(p));
             HIP_TRY(e, hipStreamSynchronize(p->stream));
             HIP_TRY(e, hipMemcpy(tmp.data(), p->slot[p->cur].accum.ptr, tmp.size() * sizeof(float), hipMemcpyDeviceToHost));
-            for (uint32_t lr = 0; lr < p->padded_rows; ++lr) {
-                const uint32_t y = ((lr / sr) * n + r) * sr + lr % sr;
+            for (uint32_t lr = 0; lr < p->sc.padded_rows; ++lr) {
+                const uint32_t y = rows.global_row(lr);
                 if (y < h) std::memcpy(accum_out + static_cast<size_t>(y) * w * 4, tmp.data() + static_cast<size_t>(lr) * w * 4, static_cast<size_t>(w) * 16);
             }
         }
@@ -1326,9 +1088,9 @@ int rb_read_accumulation(rb_engine* e, float* accum_out) {
     rb::set_device(e);
     int rc = require_ready(e);
     if (rc) return rc;
-    const uint32_t rows = (e->opt.shard_count > 1) ? e->padded_rows : e->height;
+    const uint32_t rows = (e->opt.shard_count > 1) ? e->sc.padded_rows : e->sc.height;
     HIP_TRY(e, hipStreamSynchronize(e->stream));
-    HIP_TRY(e, hipMemcpy(accum_out, e->slot[e->cur].accum.ptr, static_cast<size_t>(e->width) * rows * 16, hipMemcpyDeviceToHost));
+    HIP_TRY(e, hipMemcpy(accum_out, e->slot[e->cur].accum.ptr, static_cast<size_t>(e->sc.width) * rows * 16, hipMemcpyDeviceToHost));
     return RB_OK;
 }
 
@@ -1350,66 +1112,39 @@ int rb_device_rgba(rb_engine* e, void** d_ptr, size_t* bytes) {
     std::lock_guard<std::mutex> lock(e->mu);
     if (rb::is_group(e)) {  // the assembled frame on the root device (valid after a render / iterator step)
         if (d_ptr) *d_ptr = rb::gather_frame_ptr(e->net);
-        if (bytes) *bytes = static_cast<size_t>(e->width) * e->height * 4;
+        if (bytes) *bytes = static_cast<size_t>(e->sc.width) * e->sc.height * 4;
         return RB_OK;
     }
     if (d_ptr) *d_ptr = e->slot[e->cur].rgba.ptr;
-    if (bytes) *bytes = static_cast<size_t>(e->width) * e->padded_rows * 4;
+    if (bytes) *bytes = static_cast<size_t>(e->sc.width) * e->sc.padded_rows * 4;
     return RB_OK;
 }
 
 int rb_local_rows(const rb_engine* e, uint32_t* rows, uint32_t* padded_rows) {
     if (!e) return RB_ERR_NULL_ARGUMENT;
-    if (rb::is_group(e)) {  // the handle delivers whole frames
-        if (rows) *rows = e->height;
-        if (padded_rows) *padded_rows = e->height;
-        return RB_OK;
-    }
-    const uint32_t sc = e->opt.shard_count > 1 ? e->opt.shard_count : 1;
-    const uint32_t sr = e->opt.stripe_rows ? e->opt.stripe_rows : rb::kDefaultStripeRows;
-    uint32_t owned = e->height;
-    if (sc > 1) {
-        owned = 0;
-        const uint32_t stripes = (e->height + sr - 1) / sr;
-        for (uint32_t s = e->opt.shard_rank; s < stripes; s += sc) owned += std::min(sr, e->height - s * sr);
-    }
-    if (rows) *rows = owned;
-    if (padded_rows) *padded_rows = e->padded_rows;
+    const rb::ShardLayout l = e->sc.layout(e->sc.height);   // a group handle delivers whole frames: its facts name no shard
+    if (rows) *rows = l.owned;
+    if (padded_rows) *padded_rows = l.padded;
     return RB_OK;
 }
 
 int rb_global_row(const rb_engine* e, uint32_t local_row, uint32_t* global_row) {
     if (!e || !global_row) return RB_ERR_NULL_ARGUMENT;
-    if (rb::is_group(e)) { *global_row = local_row; return RB_OK; }
-    const uint32_t sc = e->opt.shard_count > 1 ? e->opt.shard_count : 1;
-    const uint32_t sr = e->opt.stripe_rows ? e->opt.stripe_rows : rb::kDefaultStripeRows;
-    if (sc == 1) { *global_row = local_row; return RB_OK; }
-    *global_row = ((local_row / sr) * sc + e->opt.shard_rank) * sr + local_row % sr;
+    *global_row = e->sc.layout(e->sc.height).global_row(local_row);
     return RB_OK;
 }
 
 int rb_shard_layout(uint32_t height, uint32_t shard_rank, uint32_t shard_count, uint32_t stripe_rows,
                     uint32_t* owned_rows, uint32_t* padded_rows) {
-    const uint32_t sc = shard_count > 1 ? shard_count : 1;
-    const uint32_t sr = stripe_rows ? stripe_rows : rb::kDefaultStripeRows;
-    if (shard_rank >= sc) return RB_ERR_INVALID_OPTIONS;
-    uint32_t owned = height, padded = height;
-    if (sc > 1) {
-        const uint32_t stripes = (height + sr - 1) / sr;
-        padded = ((stripes + sc - 1) / sc) * sr;
-        owned = 0;
-        for (uint32_t s = shard_rank; s < stripes; s += sc) owned += std::min(sr, height - s * sr);
-    }
-    if (owned_rows) *owned_rows = owned;
-    if (padded_rows) *padded_rows = padded;
+    const rb::ShardLayout l = rb::shard_layout(height, shard_rank, shard_count, stripe_rows);
+    if (shard_rank >= l.count) return RB_ERR_INVALID_OPTIONS;
+    if (owned_rows) *owned_rows = l.owned;
+    if (padded_rows) *padded_rows = l.padded;
     return RB_OK;
 }
 
 uint32_t rb_shard_global_row(uint32_t shard_rank, uint32_t shard_count, uint32_t stripe_rows, uint32_t local_row) {
-    const uint32_t sc = shard_count > 1 ? shard_count : 1;
-    const uint32_t sr = stripe_rows ? stripe_rows : rb::kDefaultStripeRows;
-    if (sc == 1) return local_row;
-    return ((local_row / sr) * sc + shard_rank) * sr + local_row % sr;
+    return rb::shard_layout(0, shard_rank, shard_count, stripe_rows).global_row(local_row);
 }
 
 static int part_stats(rb_engine* e, rb_stats* out);
