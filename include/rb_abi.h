@@ -1068,6 +1068,80 @@ int rb_light_points_visible(int32_t device, const rb_probe_grid* grid, const rb_
 int rb_light_points_visible_device(rb_engine* e, const rb_probe_grid* grid, const rb_sh9* d_coeffs, const rb_probe_depth* d_moments,
                                    const rb_surfel* d_points, size_t m, const rb_light_visibility* params, rb_lit* d_out);
 
+/* ---- Direct light at surface points: shadow rays to the scene's emitters, made on the device (the
+ * normative definition; no reference counterpart).  rb_trace_hemisphere finds a light only when a cosine-weighted ray happens
+ * to hit it; here every sample picks an emitter, draws a point on it and asks rb_occluded whether the segment is free.  Every
+ * step is one IEEE binary32 operation in the order written, no contraction, / and sqrt correctly rounded: the numpy model
+ * renderbaby_amd/direct.py (scene_emitters, rays, fold) equals the device bit for bit.
+ *   TABLE  the scene's emitters: triangles t < bvh_triangle_count (the patched, clamped count a render sees) with mesh_index <
+ *          the number of meshes, ascending; then spheres k < spheres_count; then lights k < arrayLength(lights).
+ *          Triangle: a = v0, b = v1 - v0, c = v2 - v0, cr = cross(b, c), area = 0.5f * sqrt((cr.x cr.x + cr.y cr.y) + cr.z cr.z).
+ *          Sphere or light: a = center, b = {radius, 0, 0}, c = 0, area = 12.566371f * (radius * radius), radius > 0.
+ *          emissive = what rb_cast_rays reports in rb_surface.emissive for a hit on the primitive (a triangle under
+ *          color_hash_enabled: 0).  A primitive qualifies when emissive is finite with its largest component > 0, a, b, c are
+ *          finite and area is finite and > 0.  The phantom light of an empty light buffer never qualifies.
+ *   ITEM   surfel i, sample k, N emitters.  nrm, sid, the validity of the surfel and o = pos + (offset * max(1.0f, reach)) nrm
+ *          are rb_trace_hemisphere's; seed = pcg(sid + pcg(first_sample + k)); u0, u1, u2 = random_float(&seed), always three.
+ *          j = min(uint(u0 * float(N)), N - 1), E = emitters[j]; E is bad if a, b, c, area or emissive is not finite, area <= 0
+ *          or kind is none of RB_HIT_TRIANGLE / _SPHERE / _LIGHT.
+ *          Triangle: su = sqrt(u1), bv = u2 * su, bu = su - bv, Q = (a + bu b) + bv c, ne = normalize(cross(b, c)).
+ *          Else: (s, c) = sincos_turn(u1 * 2.0f - 1.0f), z = 1.0f - (u2 + u2), r = sqrt(1.0f - z * z), ne = (r * c, r * s, z),
+ *          Q = a + b.x ne.
+ *          v = Q - o, d2 = (v.x v.x + v.y v.y) + v.z v.z, dist = sqrt(d2), d = v / dist, cs = (nrm.x d.x + nrm.y d.y) + nrm.z d.z,
+ *          ce likewise with ne, then |ce| for a triangle (it emits on both sides) and -ce otherwise (a sphere from outside only).
+ *          The item is lit when the surfel is valid, N > 0, E is good, d is finite and not 0 0 0, cs > 0, ce > 0, d2 > 0 and
+ *          contrib = emissive * g, g = ((((cs * ce) * area) / d2) * float(N)) * 0.318309886f, is finite in every component.
+ *   OUT    per item the record {o, d} (pad words 0), the bound dist * (1.0f - shorten) if lit, else 0.0f (rb_occluded answers
+ *          VISIBLE without walking), and {contrib if lit else +0, valid ? 1.0f : 0.0f}.  A valid item whose d is not finite
+ *          stores d = 0 0 0; an invalid item stores {pos as given, 0 0 0}: rb_occluded marks both RB_OCCL_INVALID.
+ *   FOLD   out[i].sum from +0, in ascending k: + contrib of every item whose byte is RB_OCCL_VISIBLE, one add per component;
+ *          out[i].weight = the number of valid items.  sum / weight is the direct irradiance over pi: rb_trace_hemisphere's
+ *          convention, so the two add and compare. */
+typedef struct rb_emitter {                                                                        /* 64 B */
+    float a[3]; uint32_t kind;    /* RB_HIT_TRIANGLE, RB_HIT_SPHERE or RB_HIT_LIGHT */
+    float b[3]; uint32_t prim;    /* index into bvh_triangles / spheres / lights */
+    float c[3]; float area;
+    float emissive[3]; float _pad;
+} rb_emitter;
+typedef struct rb_light_params {                                                                   /* 32 B */
+    float offset;           /* as rb_hemi_params' */
+    float shorten;          /* finite, 0 .. 0.5: the shadow ray ends this fraction short of the sampled point */
+    uint32_t mask;          /* RB_MASK_*: what may occlude */
+    uint32_t flags;         /* must be 0 */
+    uint32_t _reserved[4];  /* must be 0 */
+} rb_light_params;
+/* more emitters than this in a table: RB_ERR_INVALID_OPTIONS, so that float(N) is exact */
+#define RB_MAX_EMITTERS (1u << 24)
+/* TABLE of the engine's scene into host memory: min(*count, capacity) records are written (out may be NULL with capacity 0),
+ * *count is always the total.  The table is made on the device -- flag, exclusive scan, scatter over the raw scene arrays --
+ * by the first call that needs it after an rb_update and kept until the next one; that first call waits once, for the total
+ * that sizes it.  A query in every other respect (rb_cast_rays' side effects: none; a multi-device handle: devices[0]);
+ * rb_last_query_ms reports the kernel time of the build, 0 when the table stood.  NULL count: RB_ERR_NULL_ARGUMENT; more than
+ * 2^31 - 64 candidates or more than RB_MAX_EMITTERS emitters: RB_ERR_INVALID_OPTIONS. */
+int rb_scene_emitters(rb_engine* e, rb_emitter* out, size_t capacity, size_t* count);
+/* The same into device memory of the engine's device: d_out (16-byte aligned, capacity records; may be NULL with capacity 0)
+ * and d_count (one uint32_t, 4-byte aligned); queued on the engine's stream, nothing is waited for once the table stands. */
+int rb_scene_emitters_device(rb_engine* e, rb_emitter* d_out, size_t capacity, uint32_t* d_count);
+/* ITEM and OUT alone, no engine, on `device` (-1 = current), host arrays in LINEAR order: item i * samples + k is sample
+ * first_sample + k of surfels[i]; rays_out, tmax_out and contrib_out (float4 per item) hold n * samples items each.  `seeds`:
+ * the surfels' ids, or NULL: their indices.  Refusals as rb_hemisphere_rays (it reads no mask), and RB_ERR_INVALID_OPTIONS:
+ * shorten not finite or outside [0, 0.5], n_emit > RB_MAX_EMITTERS; RB_ERR_NULL_ARGUMENT: NULL emitters with n_emit > 0, and
+ * with n > 0 NULL surfels, params or outputs; all before any device is touched.  n == 0 is RB_OK. */
+int rb_light_rays(int32_t device, const rb_emitter* emitters, size_t n_emit, const rb_surfel* surfels, const uint32_t* seeds, size_t n,
+                  const rb_light_params* params, uint32_t first_sample, uint32_t samples, rb_ray* rays_out, float* tmax_out, float* contrib_out);
+/* ITEM, rb_occluded over the records and bounds with params->mask, FOLD: out[n].  emitters == NULL: the scene's own table
+ * (n_emit is ignored); else n_emit records of the caller's -- one light, or one group of lights, gets a map of its own.
+ * Refusals (rb_light_rays', and a mask above RB_MASK_ALL), side effects, pieces of whole blocks of 64 surfels and at most
+ * RB_HEMI_PIECE_ITEMS items, sharded engines and multi-device handles as rb_openness_hemisphere.  rb_last_query_kernel_name
+ * reports "k_occl", "k_occl_bvh" or "k_occl_chunk", rb_last_query_ms the three stages together, rb_last_camera_rays_ms the
+ * generator's share. */
+int rb_direct_light(rb_engine* e, const rb_emitter* emitters, size_t n_emit, const rb_surfel* surfels, const uint32_t* seeds, size_t n,
+                    const rb_light_params* params, uint32_t first_sample, uint32_t samples, rb_radiance* out);
+/* The same with d_surfels, d_out and, when given, d_emitters (16-byte aligned) and d_seeds (may be NULL) in device memory of
+ * the engine's device; validated and queued as rb_trace_hemisphere_device, returns without waiting: rb_sync is the wait. */
+int rb_direct_light_device(rb_engine* e, const rb_emitter* d_emitters, size_t n_emit, const rb_surfel* d_surfels, const uint32_t* d_seeds,
+                           size_t n, const rb_light_params* params, uint32_t first_sample, uint32_t samples, rb_radiance* d_out);
+
 /* ---- Edge-avoiding denoiser over the first-hit buffers (no reference counterpart).  An a-trous wavelet
  * filter (Dammertz et al. 2010) on the albedo-demodulated mean radiance, guided by the first hit of every pixel-centre ray.
  * Section 13 is the normative definition: every step one IEEE binary32 operation in a fixed order, so that the device's result
@@ -1193,6 +1267,12 @@ static_assert(sizeof(rb_lit) == 16, "rb_lit is 16 B");
 static_assert(sizeof(rb_probe_depth) == 1024, "rb_probe_depth is 1024 B");
 static_assert(sizeof(rb_light_visibility) == 16, "rb_light_visibility is 16 B");
 static_assert(offsetof(rb_light_visibility, flags) == 8, "flags @8");
+static_assert(sizeof(rb_emitter) == 64, "rb_emitter is 64 B");
+static_assert(offsetof(rb_emitter, b) == 16, "b @16");
+static_assert(offsetof(rb_emitter, area) == 44, "area @44");
+static_assert(offsetof(rb_emitter, emissive) == 48, "emissive @48");
+static_assert(sizeof(rb_light_params) == 32, "rb_light_params is 32 B");
+static_assert(offsetof(rb_light_params, mask) == 8, "mask @8");
 static_assert(sizeof(rb_guide) == 48, "rb_guide is 48 B");
 static_assert(sizeof(rb_denoise_params) == 32, "rb_denoise_params is 32 B");
 static_assert(offsetof(rb_guide, t) == 12, "t @12");
@@ -1227,6 +1307,8 @@ _Static_assert(sizeof(rb_probe_grid) == 48, "rb_probe_grid is 48 B");
 _Static_assert(sizeof(rb_lit) == 16, "rb_lit is 16 B");
 _Static_assert(sizeof(rb_probe_depth) == 1024, "rb_probe_depth is 1024 B");
 _Static_assert(sizeof(rb_light_visibility) == 16, "rb_light_visibility is 16 B");
+_Static_assert(sizeof(rb_emitter) == 64, "rb_emitter is 64 B");
+_Static_assert(sizeof(rb_light_params) == 32, "rb_light_params is 32 B");
 _Static_assert(sizeof(rb_guide) == 48, "rb_guide is 48 B");
 _Static_assert(sizeof(rb_denoise_params) == 32, "rb_denoise_params is 32 B");
 #endif

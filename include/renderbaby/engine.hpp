@@ -270,6 +270,38 @@ class Engine final : public Renderer {
                          uint32_t samples, uint32_t first_sample = 0) {
         check(h_->e, rb_openness_hemisphere_device(h_->e, d_surfels, d_seeds, n, &p, first_sample, samples, d_out));
     }
+    // ---- direct light at surface points (extension; rb_abi.h): the scene's emitter table, and per surfel
+    // the ordered sum over `samples` shadow rays towards points drawn on its emitters (an empty `emitters`: the scene's own)
+    static rb_light_params light_params(float offset = 1e-3f, float shorten = 1e-3f, uint32_t mask = RB_MASK_ALL) {
+        rb_light_params p{};
+        p.offset = offset;
+        p.shorten = shorten;
+        p.mask = mask;
+        return p;
+    }
+    std::vector<rb_emitter> scene_emitters() {
+        size_t count = 0;
+        check(h_->e, rb_scene_emitters(h_->e, nullptr, 0, &count));
+        std::vector<rb_emitter> out(count);
+        check(h_->e, rb_scene_emitters(h_->e, out.data(), out.size(), &count));
+        return out;
+    }
+    std::vector<rb_radiance> direct_light(const std::vector<rb_surfel>& surfels, uint32_t samples, uint32_t first_sample = 0,
+                                          const uint32_t* seeds = nullptr, const rb_light_params& p = light_params(),
+                                          const std::vector<rb_emitter>& emitters = {}) {
+        std::vector<rb_radiance> out(surfels.size());
+        check(h_->e, rb_direct_light(h_->e, emitters.empty() ? nullptr : emitters.data(), emitters.size(), surfels.data(), seeds, surfels.size(), &p,
+                                     first_sample, samples, out.data()));
+        return out;
+    }
+    // the same on the engine's device memory (d_emitters == nullptr: the scene's own table): queued, not waited for -- sync() waits
+    void scene_emitters_device(rb_emitter* d_out, size_t capacity, uint32_t* d_count) {
+        check(h_->e, rb_scene_emitters_device(h_->e, d_out, capacity, d_count));
+    }
+    void direct_light_device(const rb_emitter* d_emitters, size_t n_emit, const rb_surfel* d_surfels, const uint32_t* d_seeds, size_t n,
+                             const rb_light_params& p, rb_radiance* d_out, uint32_t samples, uint32_t first_sample = 0) {
+        check(h_->e, rb_direct_light_device(h_->e, d_emitters, n_emit, d_surfels, d_seeds, n, &p, first_sample, samples, d_out));
+    }
     // ---- lightmap texels made on the device (extension; rb_abi.h): the surfel of every texel of an atlas
     // over the scene's uvs, and the bake of the whole map in one call (rgba in sample_texture's layout, row 0 on top)
     static rb_lightmap_params lightmap_params(uint32_t width, uint32_t height, uint32_t mesh = RB_LIGHTMAP_ALL_MESHES, bool flip = false,

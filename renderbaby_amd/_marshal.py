@@ -13,6 +13,8 @@ from . import abi
 RECORDS = {rec: (np.dtype(elem), rec.itemsize // np.dtype(elem).itemsize) for rec, elem in (
     (abi.RAY, np.float32), (abi.SURFEL, np.float32), (abi.PROBE, np.float32), (abi.HIT, np.float32), (abi.SURFACE, np.float32),
     (abi.RADIANCE, np.float32), (abi.LIT, np.float32), (abi.OPENNESS, np.int32), (abi.SH9, np.float32), (abi.PROBE_DEPTH, np.float32))}
+# ... and a table a call reads whole, beside its per-item arrays: the emitters of direct_light, (n, 16) float32
+TABLES = {abi.EMITTER: (np.dtype(np.float32), abi.EMITTER.itemsize // 4)}
 # the ids of random streams: uint32 on the host; as a tensor int32 or uint32, only the bits count
 SEEDS = np.dtype(np.uint32)
 
@@ -20,7 +22,7 @@ SEEDS = np.dtype(np.uint32)
 def layout(dtype):
     """(element dtype, elements per row) of `dtype` as a tensor; the row of a scalar (uint8, float32, the seeds) is None"""
     dtype = np.dtype(dtype)
-    return RECORDS.get(dtype, (dtype, None))
+    return RECORDS.get(dtype) or TABLES.get(dtype, (dtype, None))
 
 
 def is_tensor(x):

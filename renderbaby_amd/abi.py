@@ -87,6 +87,13 @@ LIGHT_PIECE_POINTS = 1 << 22
 PROBE_DEPTH = np.dtype([("texel", f4, (64, 4))])
 LIGHT_VISIBILITY = np.dtype([("normal_bias", f4), ("min_visibility", f4), ("flags", u4), ("_pad", u4)])
 VIS_NO_WRAP, VIS_NO_DEPTH = 1, 2
+# direct light at surface points (rb_scene_emitters / rb_light_rays / rb_direct_light): an emitter of the
+# table -- a triangle as {v0, e1, e2}, a sphere or light as {centre, (radius, 0, 0), 0} --, the parameters of a call and the most
+# emitters a table may hold
+EMITTER = np.dtype([("a", f4, (3,)), ("kind", u4), ("b", f4, (3,)), ("prim", u4), ("c", f4, (3,)), ("area", f4),
+                    ("emissive", f4, (3,)), ("_pad", f4)])
+LIGHT_PARAMS = np.dtype([("offset", f4), ("shorten", f4), ("mask", u4), ("flags", u4), ("_reserved", u4, (4,))])
+MAX_EMITTERS = 1 << 24
 # any-hit occlusion (rb_occluded): result bytes and stage masks
 OCCL_VISIBLE, OCCL_OCCLUDED, OCCL_INVALID = 0, 1, 255
 MASK_GROUND, MASK_TRIANGLES, MASK_SPHERES, MASK_LIGHTS, MASK_ALL = 1, 2, 4, 8, 15
@@ -109,6 +116,7 @@ SIZES = {"camera": (CAMERA, 48), "uniforms": (UNIFORMS, 144), "material": (MATER
          "lightmap_params": (LIGHTMAP_PARAMS, 32), "probe": (PROBE, 16), "sh9": (SH9, 112),
          "probe_grid": (PROBE_GRID, 48), "lit": (LIT, 16),
          "probe_depth": (PROBE_DEPTH, 1024), "light_visibility": (LIGHT_VISIBILITY, 16),
+         "emitter": (EMITTER, 64), "light_params": (LIGHT_PARAMS, 32),
          "own_node": (OWN_NODE, 64), "sphere_node": (SPHERE_NODE, 128)}
 for _n, (_dt, _sz) in SIZES.items():
     assert _dt.itemsize == _sz, (_n, _dt.itemsize, _sz)

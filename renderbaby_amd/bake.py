@@ -4,6 +4,8 @@
 ``irradiance``   mean radiance over cosine-weighted directions about a normal: lightmap texels, vertices, probes
 ``irradiance_device``  the same with the rays made and the samples summed on the device (Engine.trace_hemisphere; section 16)
 ``lightmap``     a mesh's lightmap in one call: surfels from its uvs, traced and resolved on the device (Engine.bake_lightmap; section 17)
+``direct_irradiance``  what reaches points directly from the lights, by shadow rays to the scene's emitters (Engine.direct_light; section 21)
+``lightmap_direct``    a lightmap of that direct light alone: surfels and shadow rays on the device, then the resolve
 ``probes``       irradiance probes: the SH9 radiance coefficients at points in free space, traced and projected on the device
                  (Engine.bake_probes; section 18)
 ``probe_grid``   a regular grid of probes baked and turned into the coefficients Engine.light_points blends (section 19)
@@ -78,6 +80,40 @@ def lightmap(engine, width, height, samples, first_sample=0, mesh=None, flip=Fal
     hemisphere of every texel's surfel (the irradiance over pi), fourth component 0 = empty, 1 = baked, 2 = filled from its
     neighbours.  No surfel and no ray exists on the host."""
     return engine.bake_lightmap(width, height, samples, first_sample=first_sample, mesh=mesh, flip=flip, offset=offset, dilate=dilate)
+
+
+def _mean(rad):
+    """sum / weight of abi.RADIANCE records or of an (m, 4) tensor of them; a record without weight is 0 0 0"""
+    if isinstance(rad, np.ndarray):
+        w = rad["weight"][:, None].astype(f32)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(w > 0, rad["sum"].astype(f32) / w, f32(0)).astype(f32)
+    w = rad[:, 3:4]
+    return (rad[:, 0:3] / w.clamp(min=1.0)) * (w > 0)
+
+
+def direct_irradiance(engine, points, normals, samples, emitters=None, first_sample=0, seeds=None, offset=1e-3, shorten=1e-3,
+                      mask=abi.MASK_ALL):
+    """What reaches each point directly from the lights, over pi, as float32 (m, 3): ``samples`` shadow rays per point towards
+    points drawn on the scene's emitters (Engine.direct_light, rb_direct_light) -- the first bounce of
+    ``irradiance_device`` with far less noise where the lights are small, and none of its further bounces or its sky.
+    ``emitters``: an abi.EMITTER table of the caller's instead of the scene's.  numpy arrays -> float32 (m, 3); torch tensors on
+    the engine's device -> an (m, 3) tensor there.  A point without a valid sample is 0 0 0."""
+    return _mean(engine.direct_light(points, normals, samples, emitters=emitters, first_sample=first_sample, seeds=seeds, offset=offset,
+                                     shorten=shorten, mask=mask))
+
+
+def lightmap_direct(engine, width, height, samples, emitters=None, first_sample=0, mesh=None, flip=False, offset=1e-3, shorten=1e-3,
+                    mask=abi.MASK_ALL, dilate=2):
+    """``lightmap`` with direct light alone: the surfels of the engine's scene over its uvs (Engine.lightmap_surfels on the
+    device), ``samples`` shadow rays per texel (Engine.direct_light on the device; the stream id is the texel index), the
+    resolve of the sums (lightmap_resolve) -> float32 (height, width, 4) in ``lightmap``'s layout.  No surfel is ever on the
+    host; the sums cross once."""
+    from . import engine as _engine
+    surf, _ = engine.lightmap_surfels(width, height, mesh=mesh, flip=flip, out=(_engine.device_new(abi.SURFEL, int(width) * int(height),
+                                                                                                     engine.query_device), None))
+    sums = engine.direct_light(surf, None, samples, emitters=emitters, first_sample=first_sample, offset=offset, shorten=shorten, mask=mask)
+    return _engine.lightmap_resolve(_engine.download(sums, abi.RADIANCE), width, height, dilate=dilate, device=engine.query_device)
 
 
 def probes(engine, pos, samples, first_sample=0, seeds=None):

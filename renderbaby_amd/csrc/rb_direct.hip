@@ -1,0 +1,277 @@
+// rb_direct.hip -- direct light at surface points (rb_scene_emitters, rb_light_rays, rb_direct_light; DESIGN.md section 21, the
+// normative definition): the scene's emitter table by an order-preserving compaction -- flag, exclusive scan, scatter -- over the
+// raw scene arrays; the shadow ray of every (surfel, sample) item towards a point drawn on a uniformly picked emitter, with its
+// bound and its unoccluded contribution; and the ordered sum of a surfel's contributions under the any-hit bytes of those rays.
+// The generator runs before the kernels that walk the records (k_occl*, rb_query.hip), as k_hemi_rays does (section 16).  Same
+// numerics contract as rb_kernels.hip: every step one binary32 operation in the order written, no FMA contraction, correctly
+// rounded / and sqrt, so that renderbaby_amd/direct.py equals this file bit for bit.
+#include <hip/hip_runtime.h>
+
+#include <rocprim/device/device_scan.hpp>
+
+#include "rb_device_sincos.hpp"
+
+#pragma clang fp contract(off)
+
+namespace rb {
+namespace {
+
+DEV bool finite1(float x) { return (__float_as_uint(x) & 0x7F800000u) != 0x7F800000u; }
+
+// ===================================================== the emitter table ====
+// Candidate i of the scene, in the table's order: triangles t < n_tris, then spheres, then lights.  The record is written whole
+// whether or not the candidate qualifies; `ok` says whether it does (section 21.1).
+struct Candidate {
+    v4f q0, q1, q2, q3;   // the rb_emitter as four quads
+    bool ok;
+};
+DEV Candidate emit_candidate(const EmitArgs& s, uint32_t i) {
+    Candidate r;
+    f3 a, b, c = mk(0, 0, 0), em = mk(0, 0, 0);
+    uint32_t kind, prim;
+    float area;
+    bool geom;
+    if (i < s.n_tris) {
+        kind = RB_HIT_TRIANGLE;
+        prim = i;
+        const v4f* const t = reinterpret_cast<const v4f*>(s.tris + i);
+        const v4f t0 = t[0], t1 = t[1], t2 = t[2];
+        const uint32_t mesh = reinterpret_cast<const uint32_t*>(s.tris + i)[12];
+        a = mk(t0.x, t0.y, t0.z);
+        b = mk(t1.x, t1.y, t1.z) - a;
+        c = mk(t2.x, t2.y, t2.z) - a;
+        const f3 cr = cross(b, c);
+        area = 0.5f * sqrt_exact((cr.x * cr.x + cr.y * cr.y) + cr.z * cr.z);
+        geom = mesh < s.n_meshes;
+        // rb_cast_rays' emissive of a triangle hit: the mesh's material, or nothing under the colour hash
+        if (geom && s.color_hash == 0u) em = ld3(s.meshes[mesh].material.emissive);
+    } else {
+        const bool sphere = i - s.n_tris < s.n_spheres;
+        kind = sphere ? RB_HIT_SPHERE : RB_HIT_LIGHT;
+        prim = sphere ? i - s.n_tris : i - s.n_tris - s.n_spheres;
+        // rb_sphere and rb_point_light share their layout: {centre, radius | material}
+        const rb_sphere* const rec = sphere ? s.spheres + prim : reinterpret_cast<const rb_sphere*>(s.lights + prim);
+        const v4f cr = reinterpret_cast<const v4f*>(rec)[0];
+        a = mk(cr.x, cr.y, cr.z);
+        b = mk(cr.w, 0.0f, 0.0f);
+        area = 12.566371f * (cr.w * cr.w);
+        geom = cr.w > 0.0f;
+        em = ld3(rec->material.emissive);
+    }
+    r.ok = geom && finite3(em) && fmaxf(fmaxf(em.x, em.y), em.z) > 0.0f && finite3(a) && finite3(b) && finite3(c) && finite1(area) && area > 0.0f;
+    r.q0 = v4f{a.x, a.y, a.z, __uint_as_float(kind)};
+    r.q1 = v4f{b.x, b.y, b.z, __uint_as_float(prim)};
+    r.q2 = v4f{c.x, c.y, c.z, area};
+    r.q3 = v4f{em.x, em.y, em.z, 0.0f};
+    return r;
+}
+
+__global__ void __launch_bounds__(256) k_emit_flag(const EmitArgs s, uint32_t total, uint32_t* __restrict__ flags) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < total) flags[i] = emit_candidate(s, i).ok ? 1u : 0u;
+}
+
+// candidate i goes to out[offs[i]] if it qualifies and the table has room; the last lane leaves the total
+__global__ void __launch_bounds__(256) k_emit_scatter(const EmitArgs s, uint32_t total, const uint32_t* __restrict__ flags,
+                                                      const uint32_t* __restrict__ offs, rb_emitter* __restrict__ out, uint32_t capacity,
+                                                      uint32_t* __restrict__ count) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= total) return;
+    const uint32_t off = offs[i], flag = flags[i];
+    if (count != nullptr && i == total - 1u) *count = off + flag;
+    if (flag == 0u || off >= capacity) return;
+    const Candidate r = emit_candidate(s, i);
+    v4f* const o = reinterpret_cast<v4f*>(out + off);
+    o[0] = r.q0;
+    o[1] = r.q1;
+    o[2] = r.q2;
+    o[3] = r.q3;
+}
+
+// ======================================================== k_light_rays ====
+// lane = item, in k_hemi_rays' two orders (gen_item).  Item order (the engine's scratch): item = (block * samples + sample) * 64 +
+// surfel-in-block, so that the fold's lanes -- one per surfel -- read a sample row as contiguous bytes, bounds and colours; the
+// padding of the last block is written as invalid items, since k_occl* walk every record of the piece.  Linear order
+// (rb_light_rays): item = surfel-in-piece * samples + sample.
+// The lanes of a wave hold 64 different emitters: each lane fetches its own 64-byte record as four 16-byte loads (a record is
+// one whole 64-byte segment, so no fetched byte is wasted), and the triangle and sphere arms are a branch, not selects -- a
+// table of one kind, which is the common one (a mesh's emissive quads, or lamps only), then pays for one arm, and a mixed wave
+// pays for both either way (section 21.3; argued from the instruction counts, not measured against selects).
+__global__ void __launch_bounds__(256) k_light_rays(const LightGenArgs g) {
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    const GenItem it = gen_item(t, g.samples, g.linear);
+    const uint32_t sf = it.idx, smp = it.smp;
+    if (sf >= g.n) {
+        // linear order: the lanes behind the last item; item order: those, and the padding of the last block
+        if (g.linear != 0u || sf >= ((g.n + 63u) & ~63u)) return;
+        store_record(g.recs, nullptr, t, mk(0, 0, 0), mk(0, 0, 0), 0u);
+        g.tmax[t] = 0.0f;
+        reinterpret_cast<v4f*>(g.contrib)[t] = v4f{0.0f, 0.0f, 0.0f, 0.0f};
+        return;
+    }
+
+    const v4f* const sp = reinterpret_cast<const v4f*>(g.surfels) + (size_t)sf * 2u;
+    const v4f s0 = sp[0], s1 = sp[1];
+    const f3 pos = mk(s0.x, s0.y, s0.z);
+    const f3 nrm = normalize(mk(s1.x, s1.y, s1.z));
+    const float reach = sqrt_exact((pos.x * pos.x + pos.y * pos.y) + pos.z * pos.z);
+    f3 o = pos + (g.offset * fmaxf(1.0f, reach)) * nrm;
+    const bool valid = finite3(pos) && finite3(nrm) && !zero3(nrm) && finite3(o);
+
+    const uint32_t sid = g.ids != nullptr ? g.ids[sf] : g.id_base + sf;
+    uint32_t seed = pcg(sid + pcg(g.first_sample + smp));
+    const float u0 = rnd(seed), u1 = rnd(seed), u2 = rnd(seed);
+
+    const uint32_t N = g.n_emit;
+    f3 d = mk(0, 0, 0);
+    float tmax = 0.0f;
+    v4f contrib = v4f{0.0f, 0.0f, 0.0f, valid ? 1.0f : 0.0f};
+    if (valid && N != 0u) {
+        const float fn = (float)N;   // N <= 2^24: exact
+        const uint32_t j = min((uint32_t)(u0 * fn), N - 1u);
+        const v4f* const ep = reinterpret_cast<const v4f*>(g.emitters) + (size_t)j * 4u;
+        const v4f e0 = ep[0], e1 = ep[1], e2 = ep[2], e3 = ep[3];
+        const f3 a = mk(e0.x, e0.y, e0.z), b = mk(e1.x, e1.y, e1.z), c = mk(e2.x, e2.y, e2.z), em = mk(e3.x, e3.y, e3.z);
+        const uint32_t kind = __float_as_uint(e0.w);
+        const float area = e2.w;
+        const bool good = finite3(a) && finite3(b) && finite3(c) && finite3(em) && finite1(area) && area > 0.0f &&
+                          (kind == (uint32_t)RB_HIT_TRIANGLE || kind == (uint32_t)RB_HIT_SPHERE || kind == (uint32_t)RB_HIT_LIGHT);
+        f3 Q, ne;
+        if (kind == (uint32_t)RB_HIT_TRIANGLE) {
+            const float su = sqrt_exact(u1);
+            const float bv = u2 * su;
+            const float bu = su - bv;
+            Q = (a + bu * b) + bv * c;
+            ne = normalize(cross(b, c));
+        } else {
+            const SinCos az = sincos_turn(u1 * 2.0f - 1.0f);
+            const float z = 1.0f - (u2 + u2);
+            const float r = sqrt_exact(1.0f - z * z);   // |z| <= 1: the radicand is >= 0
+            ne = mk(r * az.c, r * az.s, z);
+            Q = a + b.x * ne;
+        }
+        const f3 v = Q - o;
+        const float d2 = (v.x * v.x + v.y * v.y) + v.z * v.z;
+        const float dist = sqrt_exact(d2);
+        d = divs(v, dist);
+        const float cs = dot(nrm, d);
+        float ce = dot(ne, d);
+        ce = kind == (uint32_t)RB_HIT_TRIANGLE ? fabsf(ce) : -ce;
+        // a NaN made here has no defined sign or payload and stays out of the record
+        const bool aimed = finite3(d) && !zero3(d);
+        if (!aimed) d = mk(0, 0, 0);
+        if (good && aimed && cs > 0.0f && ce > 0.0f && d2 > 0.0f) {
+            const float gm = ((((cs * ce) * area) / d2) * fn) * 0.318309886f;
+            const f3 lit = mk(em.x * gm, em.y * gm, em.z * gm);
+            if (finite3(lit)) {
+                contrib = v4f{lit.x, lit.y, lit.z, 1.0f};
+                tmax = dist * (1.0f - g.shorten);
+            }
+        }
+    }
+    if (!valid) o = pos;   // an invalid item keeps the surfel's position as it was given beside a zero direction
+
+    store_record(g.recs, nullptr, t, o, d, 0u);
+    g.tmax[t] = tmax;
+    reinterpret_cast<v4f*>(g.contrib)[t] = contrib;
+}
+
+// ======================================================= k_direct_fold ====
+// lane = surfel, a block of 64 surfels per wavefront as k_rad_sum has it: sample row s of the block is 64 contiguous result
+// bytes and 1 KiB of colours.  `linear`: the items lie surfel by surfel instead (a piece of fewer than 64 surfels, which would
+// otherwise be padded to a whole block).  From +0, in ascending sample order: the colour of every item whose byte is RB_OCCL_VISIBLE, one
+// add per component; the weight is the sum of the items' fourth words (1 = a valid item).
+__global__ void __launch_bounds__(256) k_direct_fold(const uint8_t* __restrict__ occl, const float* __restrict__ contrib, uint32_t n,
+                                                     uint32_t S, uint32_t linear, rb_radiance* __restrict__ out) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const size_t row0 = linear != 0u ? (size_t)i * S : ((size_t)(i >> 6) * S) * 64u + (i & 63u);
+    const size_t step = linear != 0u ? 1u : 64u;
+    const uint8_t* const ob = occl + row0;
+    const v4f* const cb = reinterpret_cast<const v4f*>(contrib) + row0;
+    float r = 0.0f, gr = 0.0f, b = 0.0f, w = 0.0f;
+    for (uint32_t s = 0; s < S; s++) {
+        const uint32_t byte = ob[(size_t)s * step];
+        const v4f c = cb[(size_t)s * step];
+        if (byte == (uint32_t)RB_OCCL_VISIBLE) {
+            r = r + c.x;
+            gr = gr + c.y;
+            b = b + c.z;
+        }
+        w = w + c.w;
+    }
+    reinterpret_cast<v4f*>(out)[i] = v4f{r, gr, b, w};
+}
+
+size_t align256(size_t x) { return (x + 255u) & ~size_t(255); }
+
+hipError_t scan_bytes_for(uint32_t total, size_t* bytes) {
+    *bytes = 0;
+    return rocprim::exclusive_scan(nullptr, *bytes, static_cast<uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr), 0u, total,
+                                   rocprim::plus<uint32_t>(), static_cast<hipStream_t>(nullptr));
+}
+
+}  // namespace
+
+uint64_t emitter_candidates(const EmitArgs& s) { return (uint64_t)s.n_tris + s.n_spheres + s.n_lights; }
+
+// flags and offsets of every candidate, the scan's own scratch behind them; 0: the scan could not be sized
+size_t emitter_work_bytes(uint32_t total) {
+    size_t scan = 0;
+    if (scan_bytes_for(total, &scan) != hipSuccess) return 0;
+    return 2u * align256(4u * (size_t)total) + align256(scan) + 256u;
+}
+
+// the flags and the exclusive offsets of the scene's candidates into `work`, and the number that qualify into *count
+int launch_emitter_count(const EmitArgs& s, void* work, uint32_t* count, void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const uint32_t total = (uint32_t)emitter_candidates(s);
+    if (total == 0u) return (int)hipMemsetAsync(count, 0, sizeof(uint32_t), stream);
+    size_t scan = 0;
+    if (const hipError_t st = scan_bytes_for(total, &scan)) return (int)st;
+    char* const base = static_cast<char*>(work);
+    uint32_t* const flags = reinterpret_cast<uint32_t*>(base);
+    uint32_t* const offs = reinterpret_cast<uint32_t*>(base + align256(4u * (size_t)total));
+    void* const tmp = base + 2u * align256(4u * (size_t)total);
+    hipLaunchKernelGGL(k_emit_flag, dim3((total + 255u) / 256u), dim3(256), 0, stream, s, total, flags);
+    if (const hipError_t st = hipGetLastError()) return (int)st;
+    if (const hipError_t st = rocprim::exclusive_scan(tmp, scan, flags, offs, 0u, total, rocprim::plus<uint32_t>(), stream)) return (int)st;
+    // (no record is written: capacity 0)
+    hipLaunchKernelGGL(k_emit_scatter, dim3((total + 255u) / 256u), dim3(256), 0, stream, s, total, flags, offs, static_cast<rb_emitter*>(nullptr), 0u, count);
+    return (int)hipGetLastError();
+}
+
+// ... and the records of those that qualify, in candidate order, into out[capacity], from the flags and offsets `work` holds
+int launch_emitter_scatter(const EmitArgs& s, const void* work, rb_emitter* out, uint32_t capacity, void* stream_) {
+    const uint32_t total = (uint32_t)emitter_candidates(s);
+    if (total == 0u || capacity == 0u) return 0;
+    const char* const base = static_cast<const char*>(work);
+    const uint32_t* const flags = reinterpret_cast<const uint32_t*>(base);
+    const uint32_t* const offs = reinterpret_cast<const uint32_t*>(base + align256(4u * (size_t)total));
+    hipLaunchKernelGGL(k_emit_scatter, dim3((total + 255u) / 256u), dim3(256), 0, static_cast<hipStream_t>(stream_), s, total, flags, offs, out, capacity,
+                       static_cast<uint32_t*>(nullptr));
+    return (int)hipGetLastError();
+}
+
+// One piece: every record, bound and colour of it, queued on `stream`; nothing is waited for.  Item order: g.n surfels rounded
+// up to whole blocks of 64, the padding written as invalid items; linear order: g.n surfels' g.n * samples items.
+int launch_light_rays(const LightGenArgs& g, void* stream_) {
+    if (g.n == 0u) return 0;
+    if (g.surfels == nullptr || g.recs == nullptr || g.tmax == nullptr || g.contrib == nullptr || g.samples == 0u) return (int)hipErrorInvalidValue;
+    if (g.emitters == nullptr && (g.n_emit != 0u)) return (int)hipErrorInvalidValue;
+    if (g.n_emit > RB_MAX_EMITTERS) return (int)hipErrorInvalidValue;
+    const uint64_t lanes = gen_lanes(g.n, g.samples, g.linear);
+    if (lanes == 0u) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_light_rays, dim3((uint32_t)((lanes + 255u) / 256u)), dim3(256), 0, static_cast<hipStream_t>(stream_), g);
+    return (int)hipGetLastError();
+}
+
+// out[i] = the ordered sum of surfel i < n over its `samples` items, in item order or (`linear`) in linear order
+int launch_direct_fold(const uint8_t* occl, const float* contrib, uint32_t n, uint32_t samples, uint32_t linear, rb_radiance* out, void* stream_) {
+    if (n == 0u) return 0;
+    if (occl == nullptr || contrib == nullptr || out == nullptr || samples == 0u) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_direct_fold, dim3((n + 255u) / 256u), dim3(256), 0, static_cast<hipStream_t>(stream_), occl, contrib, n, samples, linear, out);
+    return (int)hipGetLastError();
+}
+
+}  // namespace rb

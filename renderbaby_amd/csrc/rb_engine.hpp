@@ -178,6 +178,14 @@ struct rb_engine {
     rb::DevBuf<rb_probe> probe_pos;       // rb_bake_probes: the piece's probes and its SH9 sums
     rb::DevBuf<rb_sh9> probe_out;
     rb::DevBuf<rb_probe_depth> depth_out; // rb_bake_probe_depth: the piece's maps (its records and hits: q_rays, q_hits)
+    // direct light (rb_scene_emitters / rb_direct_light): the emitter table of the scene of the last
+    // accepted update (made by the first call that needs it after it) with its length on both sides, the compaction's
+    // scratch, and a caller's table as the host form stages it
+    rb::DevBuf<rb_emitter> emit_table, emit_given;
+    rb::DevBuf<uint32_t> emit_count;
+    rb::DevBuf<unsigned char> emit_work;
+    uint32_t emit_n = 0;
+    bool emit_valid = false;
     // lightmap texels made on the device (rb_lightmap_surfels_device / rb_bake_lightmap*): the triangles
     // prepared in triangle order, the cover pass's scratch, and what a bake keeps between its stages
     rb::DevBuf<rb::PrepTri> lm_ptris;

@@ -447,6 +447,39 @@ struct HemiGenArgs {
 };
 int launch_hemisphere_rays(const HemiGenArgs& g, void* stream);
 int launch_hemisphere_count(const uint8_t* occl, uint32_t n, uint32_t samples, rb_openness* out, void* stream);
+// ---- rb_direct.hip: direct light at surface points.  The scene's emitter table is a compaction of its
+// candidates -- triangles, then spheres, then lights -- in two steps, so that the caller can size the table between them:
+// launch_emitter_count leaves every candidate's flag and exclusive offset in `work` (emitter_work_bytes) and the number that
+// qualify in *count, launch_emitter_scatter writes their records.  One launch of k_light_rays writes the shadow rays of one
+// piece of whole surfels with their bounds and contributions; k_direct_fold sums a piece's contributions under its any-hit bytes.
+struct EmitArgs {
+    const rb_gpu_triangle* tris;
+    const rb_mesh* meshes;
+    const rb_sphere* spheres;
+    const rb_point_light* lights;
+    uint32_t n_tris, n_meshes, n_spheres, n_lights;   // the counts a render sees: patched, clamped to the buffers
+    uint32_t color_hash;                              // uniforms.color_hash_enabled: a triangle hit then reports no emission
+};
+uint64_t emitter_candidates(const EmitArgs& s);
+size_t emitter_work_bytes(uint32_t total);   // 0: the scan could not be sized
+int launch_emitter_count(const EmitArgs& s, void* work, uint32_t* count, void* stream);
+int launch_emitter_scatter(const EmitArgs& s, const void* work, rb_emitter* out, uint32_t capacity, void* stream);
+struct LightGenArgs {
+    const rb_surfel* surfels; // the piece's surfels
+    const uint32_t* ids;      // the piece's surfel ids, or nullptr: id_base + index in the piece
+    const rb_emitter* emitters;   // n_emit records (<= RB_MAX_EMITTERS)
+    rb_ray* recs;            // item order: record (block * samples + sample) * 64 + surfel-in-block; linear: index * samples + sample
+    float* tmax;              // one bound per item, beside the record
+    float* contrib;           // float4 per item: the unoccluded contribution, 1 or 0 for a valid or an invalid item
+    float offset, shorten;
+    uint32_t n_emit;
+    uint32_t n;               // surfels in this piece
+    uint32_t id_base;         // index of the piece's first surfel in the call
+    uint32_t first_sample, samples;
+    uint32_t linear;
+};
+int launch_light_rays(const LightGenArgs& g, void* stream);
+int launch_direct_fold(const uint8_t* occl, const float* contrib, uint32_t n, uint32_t samples, uint32_t linear, rb_radiance* out, void* stream);
 // ---- rb_probe.hip: irradiance probes made on the device.  One launch of k_probe_rays writes the records
 // of one piece of whole probes, in k_cam_rays' format and k_hemi_rays' two orders; k_sh_project folds the colours launch_radiance
 // left in RadArgs::colors with the SH9 basis of each record's direction.

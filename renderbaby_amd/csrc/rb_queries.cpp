@@ -1,7 +1,8 @@
 // rb_queries.cpp -- what an engine answers besides frames: closest-hit queries (rb_cast_rays / rb_render_hits / rb_pick), any-hit
 // occlusion, path-traced radiance along given rays, camera and hemisphere rays, lightmap texels and irradiance probes made on the
-// device, light points from a baked probe grid with or without the probes' depth moments, and the denoiser over the first-hit
-// buffers, with their device forms, their getters and their C entry points (rb_abi.h; DESIGN.md sections 11-20).
+// device, light points from a baked probe grid with or without the probes' depth moments, direct light by shadow rays to the
+// scene's emitters, and the denoiser over the first-hit buffers, with their device forms, their getters and their C entry points
+// (rb_abi.h; DESIGN.md sections 11-21).
 // Every sequence is here once: one prologue (query_prologue), one timed
 // launch (timed_launch), one runner per form -- run_pieces for the host forms, device_query_locked for the device forms --, over
 // them one runner for the families of "n items, `samples` each" in both forms (run_family: radiance, camera, hemisphere,
@@ -487,6 +488,174 @@ int hemisphere_locked(rb_engine* e, bool device, const HemiCall& c, const rb_sur
                       });
 }
 
+// ---- direct light at surface points (rb_abi.h)
+rb::EmitArgs emit_args(const rb::KParams& p) {
+    rb::EmitArgs s{};
+    s.tris = p.tris;
+    s.meshes = p.meshes;
+    s.spheres = p.spheres;
+    s.lights = p.lights;
+    s.n_tris = p.u.bvh_triangle_count;
+    s.n_meshes = p.n_meshes;
+    s.n_spheres = p.u.spheres_count;
+    s.n_lights = p.n_lights;
+    s.color_hash = p.u.color_hash_enabled;
+    return s;
+}
+
+// The emitter table of the current scene, made if the last update left none: flags, offsets and the total on the engine's
+// stream, one wait for the total that sizes the table, the scatter.  *built: this call made it.
+int ensure_emitters(rb_engine* e, const rb::KParams& p, bool* built) {
+    *built = false;
+    if (e->emit_valid) return RB_OK;
+    const rb::EmitArgs s = emit_args(p);
+    const uint64_t total = rb::emitter_candidates(s);
+    if (total > 0x7FFFFFFFull - 63ull) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "the emitter table takes at most 2^31 - 64 candidate primitives");
+    HIP_TRY(e, e->emit_count.reserve(1));
+    if (total > 0u) {
+        const size_t bytes = rb::emitter_work_bytes(static_cast<uint32_t>(total));
+        if (bytes == 0) return rb::fail(e, RB_ERR_DEVICE, "the emitter table's scan could not be sized");
+        HIP_TRY(e, e->emit_work.reserve(bytes));
+    }
+    int st = rb::launch_emitter_count(s, e->emit_work.ptr, e->emit_count.ptr, e->stream);
+    if (st) return rb::fail(e, RB_ERR_DEVICE, "emitter count launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
+    uint32_t n = 0;
+    HIP_TRY(e, hipMemcpyAsync(&n, e->emit_count.ptr, sizeof(n), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    if (n > RB_MAX_EMITTERS) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "the scene has %u emitters; at most 2^24 are taken", n);
+    HIP_TRY(e, e->emit_table.reserve(std::max<size_t>(n, 1)));
+    st = rb::launch_emitter_scatter(s, e->emit_work.ptr, e->emit_table.ptr, n, e->stream);
+    if (st) return rb::fail(e, RB_ERR_DEVICE, "emitter scatter launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
+    e->emit_n = n;
+    e->emit_valid = true;
+    *built = true;
+    return RB_OK;
+}
+
+// rb_scene_emitters in both forms: the build, if there is one, between the query's two events; then the copies
+int scene_emitters_locked(rb_engine* e, bool device, rb_emitter* out, size_t capacity, size_t* count, uint32_t* d_count) {
+    if (device) {
+        int rc = capacity ? device_range(e, out, capacity * sizeof(rb_emitter), 16, "d_out") : RB_OK;
+        if (!rc) rc = device_range(e, d_count, sizeof(uint32_t), 4, "d_count");
+        if (rc) return rc;
+    }
+    rb::KParams p{};
+    if (const int rc = query_prologue(e, &p)) return rc;
+    bool built = false;
+    HIP_TRY(e, hipEventRecord(e->ev_q[0], e->stream));
+    if (const int rc = ensure_emitters(e, p, &built)) return rc;
+    HIP_TRY(e, hipEventRecord(e->ev_q[1], e->stream));
+    e->last_query_kernel_name = "k_emit_scatter";
+    const size_t m = std::min<size_t>(e->emit_n, capacity);
+    if (device) {
+        if (m) HIP_TRY(e, hipMemcpyAsync(out, e->emit_table.ptr, m * sizeof(rb_emitter), hipMemcpyDeviceToDevice, e->stream));
+        HIP_TRY(e, hipMemcpyAsync(d_count, e->emit_count.ptr, sizeof(uint32_t), hipMemcpyDeviceToDevice, e->stream));
+        e->query_ms_pending = built;
+        return RB_OK;
+    }
+    if (m) {
+        if (const int rc = query_copy_out(e, out, e->emit_table.ptr, m * sizeof(rb_emitter), page_locked(out))) return rc;
+    }
+    *count = e->emit_n;
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    if (built) HIP_TRY(e, hipEventElapsedTime(&e->last_query_ms, e->ev_q[0], e->ev_q[1]));
+    return RB_OK;
+}
+
+// what a call of rb_direct_light is, beside its buffers: the table is in device memory by now
+struct DirectCall {
+    rb_light_params prm;
+    uint32_t first_sample, samples;
+    const rb_emitter* emitters;
+    uint32_t n_emit;
+};
+
+rb::LightGenArgs light_gen_args(const DirectCall& c, const rb_surfel* surfels, const uint32_t* ids, rb_ray* recs, float* tmax, float* contrib,
+                                size_t done, size_t m) {
+    rb::LightGenArgs g{};
+    g.surfels = surfels;
+    g.ids = ids;
+    g.emitters = c.emitters;
+    g.recs = recs;
+    g.tmax = tmax;
+    g.contrib = contrib;
+    g.offset = c.prm.offset;
+    g.shorten = c.prm.shorten;
+    g.n_emit = c.n_emit;
+    g.n = static_cast<uint32_t>(m);
+    g.id_base = static_cast<uint32_t>(done);
+    g.first_sample = c.first_sample;
+    g.samples = c.samples;
+    return g;
+}
+
+// A piece of fewer than 64 surfels is laid out in linear order: item order would pad it to a whole block, and one surfel at
+// 4096 samples would generate, store and walk 64 times its items.
+bool direct_linear(size_t m) { return m < 64; }
+// the items of a piece of `piece` surfels: whole blocks of 64 in item order
+size_t direct_items(size_t piece, uint32_t samples) { return (direct_linear(piece) ? piece : ((piece + 63) / 64) * 64) * samples; }
+
+// the scratch of one piece beside the caller's arrays: records, bounds, result bytes and the radiance family's colours
+int direct_scratch(rb_engine* e, size_t piece, uint32_t samples) {
+    const size_t items = direct_items(piece, samples);
+    HIP_TRY(e, e->q_rays.reserve(items));
+    HIP_TRY(e, e->q_tmax.reserve(items));
+    HIP_TRY(e, e->q_occl.reserve(items));
+    HIP_TRY(e, e->rad_colors.reserve(items * 4));
+    return RB_OK;
+}
+
+// one piece, queued: surfels [done, done + m) of the call, at `surfels` / `ids` in device memory, into out[m], as hemi_piece's
+// openness branch has it but in item order (direct_linear: linear order): the generator, the k_occl kernel of the scene's walk
+// over every record of the piece's blocks, the fold
+int direct_piece(rb_engine* e, const rb::KParams& p, const DirectCall& c, const rb_surfel* surfels, const uint32_t* ids, size_t done, size_t m,
+                 rb_radiance* out, rb::LaunchInfo* li) {
+    rb::LightGenArgs g = light_gen_args(c, surfels, ids, e->q_rays.ptr, e->q_tmax.ptr, e->rad_colors.ptr, done, m);
+    g.linear = direct_linear(m) ? 1u : 0u;
+    if (const int st = timed_generator(e, [&] { return rb::launch_light_rays(g, e->stream); })) return st;
+    rb::OcclArgs a{};
+    a.q.rays = e->q_rays.ptr;
+    a.q.n = static_cast<uint32_t>(direct_items(m, c.samples));
+    a.tmax = e->q_tmax.ptr;
+    a.out = e->q_occl.ptr;
+    a.mask = c.prm.mask;
+    if (const int st = rb::launch_occluded(p, a, e->stream, li)) return st;
+    return rb::launch_direct_fold(e->q_occl.ptr, e->rad_colors.ptr, static_cast<uint32_t>(m), c.samples, g.linear, out, e->stream);
+}
+
+int direct_light_locked(rb_engine* e, bool device, const rb_emitter* emitters, size_t n_emit, const rb_surfel* surfels, const uint32_t* seeds,
+                        size_t n, const rb_light_params& prm, uint32_t first_sample, uint32_t samples, rb_radiance* out) {
+    DirectCall c{prm, first_sample, samples, emitters, static_cast<uint32_t>(n_emit)};
+    if (device) {   // every buffer of the caller's before anything is queued or the table is made: a refused call has done nothing
+        int rc = device_range(e, surfels, n * sizeof(rb_surfel), 16, "d_surfels");
+        if (!rc && seeds) rc = device_range(e, seeds, n * sizeof(uint32_t), 4, "d_seeds");
+        if (!rc) rc = device_range(e, out, n * sizeof(rb_radiance), 16, "d_out");
+        if (!rc && emitters && n_emit > 0) rc = device_range(e, emitters, n_emit * sizeof(rb_emitter), 16, "d_emitters");
+        if (rc) return rc;
+    }
+    if (!emitters) {   // the scene's own table
+        rb::KParams p{};
+        bool built = false;
+        int rc = query_prologue(e, &p);
+        if (!rc) rc = ensure_emitters(e, p, &built);
+        if (rc) return rc;
+        c.emitters = e->emit_table.ptr;
+        c.n_emit = e->emit_n;
+    } else if (!device) {   // a caller's table in host memory: staged once per call
+        if (const int rc = require_ready(e)) return rc;
+        HIP_TRY(e, e->emit_given.reserve(std::max<size_t>(n_emit, 1)));
+        if (n_emit > 0) HIP_TRY(e, hipMemcpyAsync(e->emit_given.ptr, emitters, n_emit * sizeof(rb_emitter), hipMemcpyHostToDevice, e->stream));
+        c.emitters = e->emit_given.ptr;
+    }
+    return run_family(e, device, "direct light", RB_HEMI_PIECE_ITEMS, n, samples,
+                      {FAMILY_ARRAY(surfels, e->hemi_surfels, 16, "d_surfels"), FAMILY_ARRAY(seeds, e->rad_seeds, 4, "d_seeds")},
+                      FAMILY_ARRAY(out, e->rad_out, 16, "d_out"), [&](size_t piece) { return direct_scratch(e, piece, samples); },
+                      [&](const rb::KParams& p, const void* const* in, void* o, size_t done, size_t m, rb::LaunchInfo* li) {
+                          return direct_piece(e, p, c, static_cast<const rb_surfel*>(in[0]), static_cast<const uint32_t*>(in[1]), done, m,
+                                              static_cast<rb_radiance*>(o), li);
+                      });
+}
+
 // ---- irradiance probes made on the device (rb_abi.h)
 rb::ProbeGenArgs probe_gen_args(const rb_probe* probes, const uint32_t* ids, rb_ray* recs, size_t done, size_t m, uint32_t first_sample,
                                 uint32_t samples) {
@@ -655,6 +824,21 @@ int hemi_check(rb_engine* e, const char* who, const rb_hemi_params* prm, size_t 
         if (r != 0u) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: _reserved must be 0", who);
     if (openness && std::isnan(prm->radius)) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: radius is NaN", who);
     if (openness && prm->mask > RB_MASK_ALL) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: mask has bits above RB_MASK_ALL", who);
+    return RB_OK;
+}
+
+// the refusals every direct-light entry point shares; before a device is touched (e may be NULL: rb_light_rays, which reads no mask)
+int light_check(rb_engine* e, const char* who, const rb_light_params* prm, size_t n_emit, size_t n, uint32_t first_sample, uint32_t samples,
+                bool engine) {
+    rb_hemi_params hp{};
+    hp.offset = prm->offset;
+    hp.flags = prm->flags;
+    for (int k = 0; k < 4; k++) hp._reserved[k] = prm->_reserved[k];
+    if (const int rc = hemi_check(e, who, &hp, n, first_sample, samples, false)) return rc;
+    if (!std::isfinite(prm->shorten) || prm->shorten < 0.0f || prm->shorten > 0.5f)
+        return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: shorten must be finite and 0 .. 0.5", who);
+    if (engine && prm->mask > RB_MASK_ALL) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: mask has bits above RB_MASK_ALL", who);
+    if (n_emit > RB_MAX_EMITTERS) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s takes at most 2^24 emitters", who);
     return RB_OK;
 }
 
@@ -938,6 +1122,18 @@ int hemisphere_entry(rb_engine* e, const char* who, bool openness, bool device, 
             return prm ? hemi_check(e, who, prm, n, first_sample, samples, openness) : RB_OK;
         },
         [&](rb_engine* t) { return hemisphere_locked(t, device, HemiCall{*prm, first_sample, samples, openness}, surfels, seeds, n, out); });
+}
+
+// the two engine entry points of rb_direct_light; emitters == nullptr: the scene's own table, and n_emit is not looked at
+int direct_light_entry(rb_engine* e, const char* who, bool device, const rb_emitter* emitters, size_t n_emit, const rb_surfel* surfels,
+                       const uint32_t* seeds, size_t n, const rb_light_params* prm, uint32_t first_sample, uint32_t samples, rb_radiance* out) {
+    return engine_entry(
+        e, n,
+        [&] {
+            if (n > 0 && (!surfels || !prm || !out)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "%s: surfels / params / out is NULL", who);
+            return prm ? light_check(e, who, prm, emitters ? n_emit : 0, n, first_sample, samples, true) : RB_OK;
+        },
+        [&](rb_engine* t) { return direct_light_locked(t, device, emitters, n_emit, surfels, seeds, n, *prm, first_sample, samples, out); });
 }
 
 // the two engine entry points of the probe family
@@ -1354,6 +1550,74 @@ int rb_openness_hemisphere(rb_engine* e, const rb_surfel* surfels, const uint32_
 int rb_openness_hemisphere_device(rb_engine* e, const rb_surfel* d_surfels, const uint32_t* d_seeds, size_t n,
                                   const rb_hemi_params* params, uint32_t first_sample, uint32_t samples, rb_openness* d_out) {
     return hemisphere_entry(e, "rb_openness_hemisphere_device", true, true, d_surfels, d_seeds, n, params, first_sample, samples, d_out);
+}
+
+int rb_scene_emitters(rb_engine* e, rb_emitter* out, size_t capacity, size_t* count) {
+    return engine_entry(
+        e,
+        [&]() -> int {
+            if (!count || (capacity > 0 && !out)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "rb_scene_emitters: count is NULL, or out with a capacity above 0");
+            return RB_OK;
+        },
+        [&](rb_engine* t) { return scene_emitters_locked(t, false, out, capacity, count, nullptr); });
+}
+
+int rb_scene_emitters_device(rb_engine* e, rb_emitter* d_out, size_t capacity, uint32_t* d_count) {
+    return engine_entry(
+        e,
+        [&]() -> int {
+            if (!d_count || (capacity > 0 && !d_out))
+                return rb::fail(e, RB_ERR_NULL_ARGUMENT, "rb_scene_emitters_device: d_count is NULL, or d_out with a capacity above 0");
+            return RB_OK;
+        },
+        [&](rb_engine* t) { return scene_emitters_locked(t, true, d_out, capacity, nullptr, d_count); });
+}
+
+int rb_light_rays(int32_t device, const rb_emitter* emitters, size_t n_emit, const rb_surfel* surfels, const uint32_t* seeds, size_t n,
+                  const rb_light_params* params, uint32_t first_sample, uint32_t samples, rb_ray* rays_out, float* tmax_out, float* contrib_out) {
+    if ((n_emit > 0 && !emitters) || (n > 0 && (!surfels || !params || !rays_out || !tmax_out || !contrib_out)))
+        return rb::fail(nullptr, RB_ERR_NULL_ARGUMENT, "rb_light_rays: emitters / surfels / params / rays_out / tmax_out / contrib_out is NULL");
+    if (params)
+        if (const int rc = light_check(nullptr, "rb_light_rays", params, n_emit, n, first_sample, samples, false)) return rc;
+    if (n == 0) return RB_OK;
+    const size_t piece = std::min(n, std::max<size_t>((size_t(1) << 22) / samples, 1));   // whole surfels, about 2^22 items
+    rb::DevBuf<rb_emitter> d_emit;
+    rb::DevBuf<rb_surfel> d_surfels;
+    rb::DevBuf<uint32_t> d_ids;
+    rb::DevBuf<rb_ray> d_rays;
+    rb::DevBuf<float> d_tmax, d_contrib;
+    DeviceScope s(device);
+    s.alloc(d_emit, std::max<size_t>(n_emit, 1));
+    s.alloc(d_surfels, piece);
+    if (seeds) s.alloc(d_ids, piece);
+    s.alloc(d_rays, piece * samples);
+    s.alloc(d_tmax, piece * samples);
+    s.alloc(d_contrib, piece * samples * 4);
+    s.upload(d_emit.ptr, emitters, n_emit * sizeof(rb_emitter));   // once per call
+    const DirectCall c{*params, first_sample, samples, d_emit.ptr, static_cast<uint32_t>(n_emit)};
+    for (size_t done = 0; done < n && s.ok(); done += piece) {
+        const size_t m = std::min(piece, n - done), items = m * samples;
+        s.upload(d_surfels.ptr, surfels + done, m * sizeof(rb_surfel));
+        if (seeds) s.upload(d_ids.ptr, seeds + done, m * sizeof(uint32_t));
+        rb::LightGenArgs g = light_gen_args(c, d_surfels.ptr, seeds ? d_ids.ptr : nullptr, d_rays.ptr, d_tmax.ptr, d_contrib.ptr, done, m);
+        g.linear = 1u;
+        s.run([&] { return rb::launch_light_rays(g, s.stream); });
+        s.download(rays_out + done * samples, d_rays.ptr, items * sizeof(rb_ray));
+        s.download(tmax_out + done * samples, d_tmax.ptr, items * sizeof(float));
+        s.download(contrib_out + done * samples * 4, d_contrib.ptr, items * 4 * sizeof(float));
+        s.sync();   // the scratch is the next piece's
+    }
+    return s.finish("rb_light_rays");
+}
+
+int rb_direct_light(rb_engine* e, const rb_emitter* emitters, size_t n_emit, const rb_surfel* surfels, const uint32_t* seeds, size_t n,
+                    const rb_light_params* params, uint32_t first_sample, uint32_t samples, rb_radiance* out) {
+    return direct_light_entry(e, "rb_direct_light", false, emitters, n_emit, surfels, seeds, n, params, first_sample, samples, out);
+}
+
+int rb_direct_light_device(rb_engine* e, const rb_emitter* d_emitters, size_t n_emit, const rb_surfel* d_surfels, const uint32_t* d_seeds,
+                           size_t n, const rb_light_params* params, uint32_t first_sample, uint32_t samples, rb_radiance* d_out) {
+    return direct_light_entry(e, "rb_direct_light_device", true, d_emitters, n_emit, d_surfels, d_seeds, n, params, first_sample, samples, d_out);
 }
 
 int rb_probe_rays(int32_t device, const rb_probe* probes, const uint32_t* seeds, size_t n, uint32_t first_sample, uint32_t samples,

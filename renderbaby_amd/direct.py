@@ -1,0 +1,207 @@
+"""The numpy model of direct light at surface points (csrc/rb_direct.hip): the same binary32 operations
+in the same order, so ``scene_emitters`` equals ``rb_scene_emitters``, ``rays`` equals ``rb_light_rays`` and ``fold`` the sums
+of ``rb_direct_light`` bit for bit.
+
+``scene_emitters``  abi.EMITTER[] of a scene: its emissive triangles, then spheres, then lights, each in ascending order
+``emitter_records`` the records of given triangles and spheres, whether or not they would qualify (a table of the caller's own)
+``qualifies``       which of such records are emitters
+``draws``           what the generator draws for every (surfel, sample) item: three numbers, always
+``pick``            the emitter an item's first draw picks
+``barycentrics``, ``points``  the point an item's second and third draws make on its emitter, and the emitter's normal there
+``rays``          (origins, directions, bounds, contributions) of the items: what ``rb_light_rays`` returns
+``fold``            abi.RADIANCE[m] from the contributions and the any-hit bytes of the items' shadow rays
+"""
+import numpy as np
+
+from . import abi
+from .camera import _unit, pcg, random_float, sincos_turn
+
+f32, u32, u64 = np.float32, np.uint32, np.uint64
+INV_PI = f32(0.318309886)
+FOUR_PI = f32(12.566371)
+KINDS = (abi.HIT_TRIANGLE, abi.HIT_SPHERE, abi.HIT_LIGHT)
+
+
+def _dot(a, b):
+    return ((a[..., 0] * b[..., 0]).astype(f32) + (a[..., 1] * b[..., 1]).astype(f32)).astype(f32) + (a[..., 2] * b[..., 2]).astype(f32)
+
+
+def _cross(a, b):
+    """each component two multiplies and one subtraction"""
+    return np.stack([(a[..., 1] * b[..., 2]).astype(f32) - (a[..., 2] * b[..., 1]).astype(f32),
+                     (a[..., 2] * b[..., 0]).astype(f32) - (a[..., 0] * b[..., 2]).astype(f32),
+                     (a[..., 0] * b[..., 1]).astype(f32) - (a[..., 1] * b[..., 0]).astype(f32)], axis=-1).astype(f32)
+
+
+def emitter_records(kind, prim, a, b, c, emissive):
+    """abi.EMITTER[n] from per-record arrays; the area by the table's rule: half the length of cross(b, c) for a triangle,
+    12.566371 (radius radius) with radius = b.x otherwise"""
+    n = len(np.asarray(prim).reshape(-1))
+    e = np.zeros(n, dtype=abi.EMITTER)
+    e["kind"], e["prim"] = kind, prim
+    e["a"], e["b"], e["c"], e["emissive"] = (np.asarray(x, f32).reshape(n, 3) for x in (a, b, c, emissive))
+    with np.errstate(all="ignore"):
+        cr = _cross(e["b"], e["c"])
+        tri = (f32(0.5) * np.sqrt(_dot(cr, cr), dtype=f32)).astype(f32)
+        sph = (FOUR_PI * (e["b"][:, 0] * e["b"][:, 0]).astype(f32)).astype(f32)
+    e["area"] = np.where(e["kind"] == abi.HIT_TRIANGLE, tri, sph)
+    return e
+
+
+def qualifies(e):
+    """which records of a table built by the table's rule are emitters (section 21.1); a sphere's radius is b.x"""
+    with np.errstate(all="ignore"):
+        fin = np.isfinite(e["emissive"]).all(1) & np.isfinite(e["a"]).all(1) & np.isfinite(e["b"]).all(1) & np.isfinite(e["c"]).all(1)
+        ok = fin & (e["emissive"].max(1) > 0) & np.isfinite(e["area"]) & (e["area"] > 0)
+        return ok & ((e["kind"] == abi.HIT_TRIANGLE) | (e["b"][:, 0] > 0))
+
+
+def scene_emitters(scene, triangle_count=None, spheres_count=None):
+    """abi.EMITTER[] of a scenes.Scene as an engine that has just taken it sees it.  ``triangle_count`` / ``spheres_count``:
+    the counts of a later update that kept the arrays (uniforms.bvh_triangle_count / spheres_count, clamped to the arrays as the
+    engine clamps them); by default every triangle and sphere counts."""
+    tris, meshes = scene.bvh_triangles, scene.meshes
+    nt = len(tris) if triangle_count is None else min(int(triangle_count), len(tris))
+    ns = len(scene.spheres) if spheres_count is None else min(int(spheres_count), len(scene.spheres))
+    t = tris[:nt]
+    t = t[t["mesh_index"] < len(meshes)]
+    prim_t = np.nonzero(tris[:nt]["mesh_index"] < len(meshes))[0]
+    em_t = meshes["material"]["emissive"][t["mesh_index"]] if len(t) else np.zeros((0, 3), f32)
+    if int(scene.uniforms["color_hash_enabled"][0]) != 0:
+        em_t = np.zeros_like(em_t)   # a triangle hit under the colour hash reports no emission
+    parts = [emitter_records(abi.HIT_TRIANGLE, prim_t, t["v0"], (t["v1"] - t["v0"]).astype(f32), (t["v2"] - t["v0"]).astype(f32), em_t)]
+    for kind, rec in ((abi.HIT_SPHERE, scene.spheres[:ns]), (abi.HIT_LIGHT, scene.lights)):
+        b = np.zeros((len(rec), 3), f32)
+        b[:, 0] = rec["radius"]
+        parts.append(emitter_records(kind, np.arange(len(rec)), rec["center"], b, np.zeros((len(rec), 3), f32), rec["material"]["emissive"]))
+    e = np.concatenate(parts)
+    return np.ascontiguousarray(e[qualifies(e)])
+
+
+def draws(m, first_sample, samples, seeds=None):
+    """What the generator draws for the items (surfel, sample) of ``m`` surfels, surfel-major: dict of ``u0``, ``u1``, ``u2``
+    and ``surfel`` (the item's surfel).  ``seeds``: the surfels' ids, by default their indices -- rb_trace_rays' rule."""
+    sid = np.arange(m, dtype=u64) if seeds is None else np.asarray(seeds, u32).reshape(-1).astype(u64)
+    if len(sid) != m:
+        raise ValueError("seeds: one id per surfel is needed")
+    surfel = np.repeat(np.arange(m, dtype=np.int64), samples)
+    k = np.tile(np.arange(samples, dtype=u64), m)
+    hs = pcg((u64(first_sample) + k) & u64(0xFFFFFFFF))
+    seed = pcg((sid[surfel] + hs.astype(u64)) & u64(0xFFFFFFFF))
+    seed, u0 = random_float(seed)
+    seed, u1 = random_float(seed)
+    seed, u2 = random_float(seed)
+    return dict(u0=u0, u1=u1, u2=u2, surfel=surfel)
+
+
+def pick(u0, n_emit):
+    """j = min(uint(u0 float(N)), N - 1)"""
+    return np.minimum((np.asarray(u0, f32) * f32(n_emit)).astype(f32).astype(u32), u32(n_emit - 1)).astype(np.int64)
+
+
+def barycentrics(u1, u2):
+    """(bu, bv) of a triangle's point: su = sqrt(u1), bv = u2 su, bu = su - bv; the point is (a + bu b) + bv c"""
+    u1, u2 = np.asarray(u1, f32), np.asarray(u2, f32)
+    su = np.sqrt(u1, dtype=f32)
+    bv = (u2 * su).astype(f32)
+    return (su - bv).astype(f32), bv
+
+
+def points(E, u1, u2):
+    """(Q, ne) of the emitters ``E`` (one record per item) and the items' second and third draws: the sampled point and the
+    emitter's normal there -- a triangle's normalised as rb_cast_rays normalises, a sphere's as drawn"""
+    a, b, c = E["a"], E["b"], E["c"]
+    u1, u2 = np.asarray(u1, f32), np.asarray(u2, f32)
+    with np.errstate(all="ignore"):
+        bu, bv = barycentrics(u1, u2)
+        q_tri = ((a + (bu[:, None] * b).astype(f32)).astype(f32) + (bv[:, None] * c).astype(f32)).astype(f32)
+        ne_tri = _unit(_cross(b, c))
+        # a sphere or a light: rb_probe_rays' lines
+        s, cz = sincos_turn((u1 * f32(2.0) - f32(1.0)).astype(f32))
+        z = (f32(1.0) - (u2 + u2).astype(f32)).astype(f32)
+        r = np.sqrt((f32(1.0) - (z * z).astype(f32)).astype(f32), dtype=f32)
+        ne_sph = np.stack([(r * cz).astype(f32), (r * s).astype(f32), z], axis=1)
+        q_sph = (a + (b[:, 0:1] * ne_sph).astype(f32)).astype(f32)
+    tri = (E["kind"] == abi.HIT_TRIANGLE)[:, None]
+    return np.where(tri, q_tri, q_sph).astype(f32), np.where(tri, ne_tri, ne_sph).astype(f32)
+
+
+def rays(emitters, surf, first_sample, samples, seeds=None, offset=1e-3, shorten=1e-3):
+    """(origins (n, 3), directions (n, 3), bounds (n,), contributions (n, 4)) of the items (surfel, sample), surfel-major -- item
+    i * samples + k is sample ``first_sample`` + k of ``surf[i]`` --: what rb_light_rays returns.  A lit item has a bound above
+    0 and its unoccluded contribution; a dark one the bound 0 and +0 +0 +0; the fourth component is 1 for a valid item.  An
+    invalid item (an invalid surfel, section 16.1) has its surfel's position as given and direction 0 0 0."""
+    em = np.asarray(emitters, dtype=abi.EMITTER).reshape(-1)
+    n_emit = len(em)
+    if n_emit > abi.MAX_EMITTERS:
+        raise ValueError("at most 2^24 emitters are taken")
+    surf = np.asarray(surf, dtype=abi.SURFEL).reshape(-1)
+    pos = surf["pos"].astype(f32)
+    dr = draws(len(surf), first_sample, samples, seeds)
+    i = dr["surfel"]
+    n = len(i)
+    with np.errstate(all="ignore"):
+        nrm = _unit(surf["normal"].astype(f32))
+        px, py, pz = pos[:, 0], pos[:, 1], pos[:, 2]
+        reach = np.sqrt((((px * px).astype(f32) + (py * py).astype(f32)).astype(f32) + (pz * pz).astype(f32)).astype(f32), dtype=f32)
+        step = (f32(offset) * np.where(reach > f32(1.0), reach, f32(1.0)).astype(f32)).astype(f32)
+        o = (pos + (step[:, None] * nrm).astype(f32)).astype(f32)
+        ok = np.isfinite(pos).all(1) & np.isfinite(nrm).all(1) & (nrm != 0).any(1) & np.isfinite(o).all(1)
+    valid = ok[i]
+    org = o[i]
+    org[~valid] = pos[i][~valid]
+    d = np.zeros((n, 3), f32)
+    tmax = np.zeros(n, f32)
+    contrib = np.zeros((n, 4), f32)
+    contrib[:, 3] = valid
+    if n_emit == 0 or n == 0:
+        return org, d, tmax, contrib
+    with np.errstate(all="ignore"):
+        fn = f32(n_emit)
+        E = em[pick(dr["u0"], n_emit)]
+        area = E["area"]
+        tri = E["kind"] == abi.HIT_TRIANGLE
+        good = (np.isfinite(E["a"]).all(1) & np.isfinite(E["b"]).all(1) & np.isfinite(E["c"]).all(1) & np.isfinite(E["emissive"]).all(1)
+                & np.isfinite(area) & (area > 0) & np.isin(E["kind"], KINDS))
+        Q, ne = points(E, dr["u1"], dr["u2"])
+        v = (Q - o[i]).astype(f32)
+        d2 = _dot(v, v).astype(f32)
+        dist = np.sqrt(d2, dtype=f32)
+        dd = (v / dist[:, None]).astype(f32)
+        cs = _dot(nrm[i], dd).astype(f32)
+        ce = _dot(ne, dd).astype(f32)
+        ce = np.where(tri, np.abs(ce), -ce).astype(f32)
+        aimed = np.isfinite(dd).all(1) & (dd != 0).any(1)
+        g = ((((cs * ce).astype(f32) * area).astype(f32) / d2).astype(f32) * fn).astype(f32)
+        g = (g * INV_PI).astype(f32)
+        lit3 = (E["emissive"] * g[:, None]).astype(f32)
+        lit = valid & good & aimed & (cs > 0) & (ce > 0) & (d2 > 0) & np.isfinite(lit3).all(1)
+        bound = (dist * (f32(1.0) - f32(shorten))).astype(f32)
+    keep = valid & aimed
+    d[keep] = dd[keep]
+    tmax[lit] = bound[lit]
+    contrib[lit, :3] = lit3[lit]
+    return org, d, tmax, contrib
+
+
+def fold(contrib, occl, samples):
+    """abi.RADIANCE[m] of m * samples items, surfel-major: ``sum`` from +0, in ascending sample order, the contribution of
+    every item whose byte is abi.OCCL_VISIBLE, one float32 add per component; ``weight`` the number of valid items."""
+    c = np.asarray(contrib, f32).reshape(-1, samples, 4)
+    seen = np.asarray(occl, np.uint8).reshape(-1, samples) == abi.OCCL_VISIBLE
+    out = np.zeros(len(c), dtype=abi.RADIANCE)
+    total = np.zeros((len(c), 3), f32)
+    weight = np.zeros(len(c), f32)
+    with np.errstate(all="ignore"):
+        for k in range(samples):
+            total = np.where(seen[:, k, None], (total + c[:, k, :3]).astype(f32), total)
+            weight = (weight + c[:, k, 3]).astype(f32)
+    out["sum"], out["weight"] = total, weight
+    return out
+
+
+def params(offset=1e-3, shorten=1e-3, mask=abi.MASK_ALL):
+    """abi.LIGHT_PARAMS[1] of a call"""
+    p = np.zeros(1, dtype=abi.LIGHT_PARAMS)
+    p["offset"], p["shorten"], p["mask"] = offset, shorten, int(mask)
+    return p

@@ -21,8 +21,8 @@ import numpy as np
 from . import abi
 from ._lib import load
 from .bvh import own_tree_readback, sphere_tree_readback
-from ._marshal import (SEEDS, Form, device_new, device_tensor, download, grid_records, host_out, host_ptr, is_tensor, probe_records,
-                       ray_records, surfel_records, torch_device)
+from ._marshal import (SEEDS, Form, device_new, device_tensor, download, grid_records, host_in, host_out, host_ptr, is_tensor, probe_records,
+                       ray_records, surfel_records, torch_device, upload)
 
 
 class RenderError(RuntimeError):
@@ -587,6 +587,60 @@ class Engine:
         return self._hemisphere("rb_openness_hemisphere", abi.OPENNESS, points, normals, samples, first_sample, seeds,
                                 self._hemi_params(offset, radius, mask), out)
 
+    # ---- direct light at surface points (rb_abi.h)
+    def scene_emitters(self, out=None):
+        """rb_scene_emitters: the emitter table of the uploaded scene -- its emissive triangles, then spheres, then lights, as
+        ``direct.scene_emitters`` models it -- made on the device by the first call after an update -> abi.EMITTER[count].
+        ``out``: an (capacity, 16) float32 tensor on the engine's device selects rb_scene_emitters_device: its first
+        min(count, capacity) rows are filled and (out, count) is returned; nothing but the count crosses to the host."""
+        if out is not None:
+            dev = self.query_device
+            out, op = device_tensor("out", out, abi.EMITTER, dev)
+            cnt = device_new(np.int32, 1, dev)
+            self._device_call(self._lib.rb_scene_emitters_device, op, len(out), cnt.data_ptr())
+            return out, int(cnt.cpu().numpy().view(np.uint32)[0])
+        count = C.c_size_t(0)
+        self._check(self._lib.rb_scene_emitters(self._h, None, 0, C.byref(count)))
+        table = np.zeros(count.value, dtype=abi.EMITTER)
+        self._check(self._lib.rb_scene_emitters(self._h, host_ptr(table), len(table), C.byref(count)))
+        return table
+
+    @staticmethod
+    def _light_params(offset, shorten, mask=abi.MASK_ALL):
+        prm = np.zeros(1, dtype=abi.LIGHT_PARAMS)
+        prm["offset"], prm["shorten"], prm["mask"] = offset, shorten, int(mask)
+        return prm
+
+    def direct_light(self, points, normals, samples, emitters=None, first_sample=0, seeds=None, offset=1e-3, shorten=1e-3,
+                     mask=abi.MASK_ALL, out=None):
+        """rb_direct_light: what reaches (m, 3) surface points directly from the lights, by ``samples`` shadow rays per point,
+        each aimed at a point drawn on a uniformly picked emitter and walked by rb_occluded among the stages of ``mask`` ->
+        abi.RADIANCE[m] (``sum`` over the samples, ``weight``: the valid samples; sum / weight is the direct irradiance over
+        pi -- trace_hemisphere's convention, so the two add and compare).  ``emitters``: None for the scene's own table
+        (``scene_emitters``), or an abi.EMITTER table of the caller's -- one light, or one group of lights, gets a map of its
+        own.  ``shorten``: the fraction of its length a shadow ray ends short of the sampled point.  Torch tensors on the
+        engine's device for the points and normals, the table ((n, 16) float32) or ``out`` ((m, 4) float32) go to
+        rb_direct_light_device: nothing crosses to the host."""
+        samples, first_sample = _sample_range(samples, first_sample)
+        surf = surfel_records(points, normals)
+        f = Form(self.query_device, surf, seeds, emitters, out)
+        surf, fp = f.input("points / normals", surf, abi.SURFEL)
+        n = len(surf)
+        table, tp, n_emit = None, None, 0
+        if emitters is not None:
+            if f.on_device and not is_tensor(emitters):
+                emitters = upload(host_in("emitters", emitters, abi.EMITTER)[0], abi.EMITTER, self.query_device)
+            table, tp = f.input("emitters", emitters, abi.EMITTER)
+            n_emit = len(table)
+            if n_emit == 0:   # an empty table of the caller's is not the scene's: a record that is never read stands in
+                table, tp = f.input("emitters", device_new(abi.EMITTER, 1, self.query_device) if f.on_device else np.zeros(1, dtype=abi.EMITTER),
+                                    abi.EMITTER)
+        seeds, sp = f.optional("seeds", seeds, SEEDS, n)
+        res, op = f.output("out", out, abi.RADIANCE, n)
+        prm = self._light_params(offset, shorten, mask)
+        self._query(f, "rb_direct_light", tp, n_emit, fp, sp, n, prm.ctypes.data, first_sample, samples, op)
+        return res
+
     # ---- lightmap texels made on the device (rb_abi.h; DESIGN.md section 17)
     @staticmethod
     def _lightmap_params(width, height, mesh=None, flip=False, offset=0.0, dilate=0):
@@ -916,6 +970,23 @@ def hemisphere_rays_device(points, normals, samples, first_sample=0, seeds=None,
     prm = Engine._hemi_params(offset)
     call("rb_hemisphere_rays", fp, sp, len(surf), prm.ctypes.data, int(first_sample), int(samples), rays.ctypes.data, seeds_out.ctypes.data)
     return rays, seeds_out
+
+
+def light_rays(emitters, points, normals, samples, first_sample=0, seeds=None, offset=1e-3, shorten=1e-3, device=-1):
+    """rb_light_rays: the generator of direct_light alone, no engine -- (abi.RAY[m * samples], float32 bounds[m * samples],
+    float32 contributions (m * samples, 4)) of an abi.EMITTER table and (m, 3) points and normals, item i * samples + k: the
+    shadow ray's origin and direction (0 0 0: an invalid item), the bound rb_occluded walks it to (0: a dark item) and the
+    unoccluded contribution with 1 for a valid item behind it.  ``direct.rays`` is its numpy model."""
+    f, call = _engineless(device)
+    table, tp = f.input("emitters", emitters, abi.EMITTER)
+    surf, fp = f.input("points", surfel_records(np.asarray(points, np.float32), np.asarray(normals, np.float32)), abi.SURFEL)
+    rays, _ = _generated(len(surf), int(samples))
+    tmax, contrib = np.zeros(len(rays), dtype=np.float32), np.zeros((len(rays), 4), dtype=np.float32)
+    seeds, sp = f.optional("seeds", seeds, SEEDS, len(surf))
+    prm = Engine._light_params(offset, shorten)
+    call("rb_light_rays", tp, len(table), fp, sp, len(surf), prm.ctypes.data, int(first_sample), int(samples), host_ptr(rays), host_ptr(tmax),
+         host_ptr(contrib))
+    return rays, tmax, contrib
 
 
 def probe_rays_device(pos, samples, first_sample=0, seeds=None, device=-1):
