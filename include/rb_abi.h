@@ -559,6 +559,11 @@ int rb_debug_rcp_det_exhaustive(uint32_t biased_exponent, uint32_t* out16);
  * in any bit (must be 0), out32[1] = index of one such triple, out32[2..17] = its o, d, v0, edge1, edge2, incoming hit.t,
  * out32[18..21] / out32[22..25] = the two results. */
 int rb_debug_triangle_trip(uint32_t n, uint32_t seed, uint32_t* out32);
+/* Test hook: the root box of the single-node walk on `n` (at most 2^24) rays of six floats {origin, direction} and the box
+ * box6 = {bmin, bmax}: out[i] bit 0 = the walk's slab test on its own reciprocals, bit 1 = the rule by which the single-node
+ * trace kernels go past that test says the answer is known to be true (origin strictly inside a finite box, no NaN in the
+ * direction).  Bit 1 must never be set without bit 0. */
+int rb_debug_root_box(const float* rays, uint32_t n, const float* box6, uint32_t* out);
 /* Test hook: the normalize of the single-node trace kernels (its general form and the form for the rejection loop's unit
  * vectors) against v / sqrt(dot(v, v)) with the correctly rounded / and sqrt, bit patterns compared, a NaN equal to a NaN.
  * xyz = n + n_unit vectors of three floats: the first n go through the general form, the next n_unit through the unit-vector

@@ -100,6 +100,19 @@ __global__ void k_normalize_sites(const float* __restrict__ xyz, uint32_t n, uin
 // behind them are the constructed cases, one per wave (trip_case), each lane one of four incoming hits -- 1e20, 0.5, the case's
 // own t and the float above it -- with lanes 8..15 of every 16 switched off on entry, which must leave their hit as it came.
 // mismatch[0] counts differing triples; mismatch[1] is the index of one and mismatch[2..] its 16 input and 8 output words.
+// The root box of the single-node walk (rb_device_intersect.hpp, RB_ROOT_INSIDE): for n rays {o, d} and one box, the slab test as
+// the walk runs it -- isect_aabb on rcp_exact's reciprocals -- and the rule that lets k_trace go past it, root_inside with
+// box_finite.  out[i] = (slab test true ? 1 : 0) | (rule says "known" ? 2 : 0).  The box is a kernel argument: wave-uniform, as
+// the node is in the walk.
+__global__ void __launch_bounds__(256) k_root_box(const float* rays, uint32_t n, f3 bmin, f3 bmax, uint32_t* out) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const f3 o = mk(rays[i * 6u], rays[i * 6u + 1u], rays[i * 6u + 2u]), d = mk(rays[i * 6u + 3u], rays[i * 6u + 4u], rays[i * 6u + 5u]);
+    const bool slab = isect_aabb(o, mk(rcp_exact(d.x), rcp_exact(d.y), rcp_exact(d.z)), bmin, bmax);
+    const bool known = root_inside(o, d, bmin, bmax) && box_finite(bmin, bmax);
+    out[i] = (slab ? 1u : 0u) | (known ? 2u : 0u);
+}
+
 constexpr uint32_t kTripCases = 44u;
 DEV void trip_case(uint32_t k, f3& o, f3& d, f3& v0, f3& e1, f3& e2) {
     // d = +z, e1 = (0, A, 0), e2 = (1, 0, 0), v0 = 0: every product with a zero is exact, so det = A, and with A = 1 the ray
@@ -505,6 +518,21 @@ int rb_debug_triangle_trip(uint32_t n, uint32_t seed, uint32_t* out32) {
     return rb::round_trip(out32, 128, 128, [&](uint32_t* d) {
         const uint32_t n_waves = (n + 63u) / 64u, waves = n_waves + rb::kTripCases;
         hipLaunchKernelGGL(rb::k_triangle_trip, dim3((waves + 3u) / 4u), dim3(256), 0, nullptr, n_waves, seed, d);
+    });
+}
+
+// Test hook: the root box of the single-node walk on the caller's n rays (six floats each: o, d) and box (bmin, bmax): the slab
+// test on the walk's own reciprocals and the rule k_trace skips it by (k_root_box).  out[i] = slab | known << 1.
+int rb_debug_root_box(const float* rays, uint32_t n, const float* box6, uint32_t* out) {
+    if (!rays || !box6 || !out) return RB_ERR_NULL_ARGUMENT;
+    if (n == 0u) return RB_OK;
+    if (n > (1u << 24)) return RB_ERR_INVALID_OPTIONS;
+    const size_t out_bytes = (size_t)n * 4u, in_bytes = (size_t)n * 24u;   // one buffer: the n result words, then the rays
+    const rb::f3 bmin = {box6[0], box6[1], box6[2]}, bmax = {box6[3], box6[4], box6[5]};
+    return rb::round_trip(out, out_bytes, out_bytes + in_bytes, [&](uint32_t* d) {
+        float* dr = reinterpret_cast<float*>(d + n);
+        (void)hipMemcpy(dr, rays, in_bytes, hipMemcpyHostToDevice);
+        hipLaunchKernelGGL(rb::k_root_box, dim3((n + 255u) / 256u), dim3(256), 0, nullptr, dr, n, bmin, bmax, d);
     });
 }
 

@@ -85,6 +85,44 @@ DEV bool isect_aabb(f3 o, f3 inv, f3 bmin, f3 bmax) {
     return tmax >= fmaxf(tmin, 0.0f);
 }
 
+// The root box of the single-node walk without its slab test (k_trace / k_trace_direct; DESIGN.md section 4, "The root box
+// where a ray starts inside it").  RB_ROOT_INSIDE = 0 gives the slab test in every segment, as before r29.
+#ifndef RB_ROOT_INSIDE
+#define RB_ROOT_INSIDE 1
+#endif
+// The rule: an origin strictly inside [bmin, bmax] in all three components and a direction without a NaN component make
+// isect_aabb(o, 1 / d, bmin, bmax) true, if the box's six bounds are finite (box_finite; they are wave-uniform, so that part is
+// scalar work).  Every compare is ordered: a NaN anywhere says "not known".  v_cmp_o takes two components at a time.
+// The bounds must be wave-uniform.
+// (the largest of the six magnitudes' bit patterns, as integers: written with float compares it becomes six vector compares)
+DEV bool box_finite(f3 bmin, f3 bmax) {
+    const uint32_t m = 0x7FFFFFFFu;
+    // (... and the empty asm statements keep each maximum a scalar one: three at a time they are matched to v_max3_u32)
+    uint32_t a = max(__float_as_uint(bmin.x) & m, __float_as_uint(bmin.y) & m);
+    asm("" : "+s"(a));
+    a = max(a, __float_as_uint(bmin.z) & m);
+    asm("" : "+s"(a));
+    a = max(a, __float_as_uint(bmax.x) & m);
+    asm("" : "+s"(a));
+    a = max(a, __float_as_uint(bmax.y) & m);
+    asm("" : "+s"(a));
+    a = max(a, __float_as_uint(bmax.z) & m);
+    asm("" : "+s"(a));
+    return a < 0x7F800000u;
+}
+// root_inside_mask: the wave's lanes for which the per-lane part holds, as a lane mask (0 for a lane that is off).  The compares
+// are asked for as masks so that they are joined with scalar instructions and tested as one word: as bools, the compiler turns
+// the joined bool back into a 0 / 1 register and compares that once more.  2 = ordered >, 4 = ordered <, 7 = ordered.
+DEV uint64_t root_inside_mask(f3 o, f3 d, f3 bmin, f3 bmax) {
+    return __builtin_amdgcn_fcmpf(o.x, bmin.x, 2) & __builtin_amdgcn_fcmpf(o.x, bmax.x, 4) & __builtin_amdgcn_fcmpf(o.y, bmin.y, 2) &
+           __builtin_amdgcn_fcmpf(o.y, bmax.y, 4) & __builtin_amdgcn_fcmpf(o.z, bmin.z, 2) & __builtin_amdgcn_fcmpf(o.z, bmax.z, 4) &
+           __builtin_amdgcn_fcmpf(d.x, d.y, 7) & __builtin_amdgcn_fcmpf(d.z, d.z, 7);
+}
+DEV bool root_inside(f3 o, f3 d, f3 bmin, f3 bmax) { return ((root_inside_mask(o, d, bmin, bmax) >> __lane_id()) & 1ull) != 0ull; }
+// What a lane knows about its ray and the root box before the segment starts: nothing, or the slab test's answer that
+// ColorRing::stage_row worked out for the primary ray it was handed in this iteration's refill.
+constexpr uint32_t kBoxUnknown = 0u, kBoxMiss = 1u, kBoxHit = 2u;
+
 // shader.wgsl:402-414
 DEV float isect_ground(f3 o, f3 d, float ground_height) {
     if (fabsf(d.y) < 1e-6f) return -1.0f;
@@ -666,8 +704,9 @@ DEV TriHit intersect_bvh_fast(const KParams& p, f3 o, f3 d, uint32_t* stack, uin
 // live ranges pushed 73 VGPRs of k_trace into scratch: 74 B of HBM traffic per segment, -10 %).
 // TRIP (with MULTI = false; k_trace and k_trace_direct only): the triangle loop in the form the RB_TRIP_* knobs above choose.
 // Every other caller of the single-node walk keeps the double-buffered loop and accept_slot as they were.
+// box (TRIP only): kBoxUnknown, or the staged answer of the root box's slab test for this lane's ray.
 template <bool STATS, bool MULTI = true, bool TRIP = false>
-DEV TriHit intersect_bvh(const KParams& p, f3 o, f3 d, uint32_t* stack, uint32_t stride, Tally<STATS>& tl) {
+DEV TriHit intersect_bvh(const KParams& p, f3 o, f3 d, uint32_t* stack, uint32_t stride, Tally<STATS>& tl, uint32_t box = kBoxUnknown) {
     TriHit h;
     h.hit = false;
     h.t = 1e20f;
@@ -679,7 +718,9 @@ DEV TriHit intersect_bvh(const KParams& p, f3 o, f3 d, uint32_t* stack, uint32_t
     if constexpr (MULTI) {
         if (p.fast_nodes != nullptr) return intersect_bvh_fast<STATS>(p, o, d, stack, stride, tl);
     }
-    const f3 inv = mk(rcp_exact(d.x), rcp_exact(d.y), rcp_exact(d.z));
+    constexpr bool skip_box = TRIP && !MULTI && RB_ROOT_INSIDE != 0;
+    // (the TRIP instantiations make the reciprocals where the root box still needs them, below)
+    const f3 inv = skip_box ? d : mk(rcp_exact(d.x), rcp_exact(d.y), rcp_exact(d.z));
     const cf4p nodes = (cf4p)p.nodes;
     const cf4p ptris = (cf4p)p.ptris;  // 4 x float4 per triangle
 
@@ -695,7 +736,20 @@ DEV TriHit intersect_bvh(const KParams& p, f3 o, f3 d, uint32_t* stack, uint32_t
         if constexpr (STATS) tl.nodes++;
         const uint32_t first = n2.z, count = n2.w;
         const uint32_t end = (first + count < p.index_len) ? first + count : p.index_len;  // guard :331
-        if (first < end && isect_aabb(o, inv, mk(n0.x, n0.y, n0.z), mk(n1.x, n1.y, n1.z))) {
+        auto in_box = [&]() {
+            const f3 b0 = mk(n0.x, n0.y, n0.z), b1 = mk(n1.x, n1.y, n1.z);
+            if constexpr (skip_box) {
+                // A lane has its answer if its primary's was staged or if it starts strictly inside the box.  One scalar
+                // branch takes a wave whose active lanes all have theirs past the three reciprocals and the slab arithmetic;
+                // any other wave runs them as before, all lanes, and uses what they say (the same bits where both exist).
+                const uint64_t unknown = __builtin_amdgcn_uicmp(box, kBoxUnknown, 32) & ~root_inside_mask(o, d, b0, b1);   // 32: ==
+                if (__builtin_expect(unknown == 0ull && box_finite(b0, b1), 1)) return box != kBoxMiss;
+                return isect_aabb(o, mk(rcp_exact(d.x), rcp_exact(d.y), rcp_exact(d.z)), b0, b1);
+            } else {
+                return isect_aabb(o, inv, b0, b1);
+            }
+        };
+        if (first < end && in_box()) {
             constexpr bool trip = TRIP && !MULTI;
             float big = 0x1p100f;
             if constexpr (trip && RB_TRIP_BLOCK) asm("s_mov_b32 %0, 0x71800000" : "=s"(big));   // not re-made in every trip

@@ -615,9 +615,10 @@ DEV bool segment_finish(const KParams& p, Path& pt, const TriHit th, uint32_t* s
 // One whole iteration of the bounce loop: traversal + everything else.  MULTI = false: trees of at most one node AND no
 // sphere tree (k_trace's default instantiations).
 // TRIP: intersect_bvh's (k_trace and k_trace_direct pass it for their single-node instantiations), and segment_post's TRIM.
+// box: intersect_bvh's (k_trace hands over the staged answer of a primary ray it has just taken).
 template <bool STATS, bool MULTI = true, bool JOINED = true, bool TRIP = false>
-DEV bool segment(const KParams& p, Path& pt, uint32_t* stack, uint32_t stride, Tally<STATS>& tl) {
-    const TriHit th = intersect_bvh<STATS, MULTI, TRIP>(fresh_params(p), pt.o, pt.d, stack, stride, tl);
+DEV bool segment(const KParams& p, Path& pt, uint32_t* stack, uint32_t stride, Tally<STATS>& tl, uint32_t box = kBoxUnknown) {
+    const TriHit th = intersect_bvh<STATS, MULTI, TRIP>(fresh_params(p), pt.o, pt.d, stack, stride, tl, box);
     return segment_finish<STATS, MULTI, true, JOINED, !MULTI, TRIP && !MULTI>(p, pt, th, stack, stride, tl);
 }
 

@@ -236,18 +236,30 @@ DEV void store_color(float4* __restrict__ colors, uint32_t item, f3 c) {
 //  * stragglers of the slice's previous row are marked kDirect in the step that restages it and never park there;
 //  * writes and reads of one wave reach LDS in program order: the staged entries are complete when another lane reads
 //    them, with no more than the usual wait on the LDS counter (the fence in k_trace only orders the compiler).
+//
+// The root box of a staged primary (RB_ROOT_INSIDE, rb_device_intersect.hpp).  The camera may stand outside the root box of a
+// single-node tree, so a primary ray is the one ray of a closed scene that needs the slab test.  stage_row runs it for the row's
+// 64 primaries at full width -- the present isect_aabb on 1 / d, which is rcp_exact's value, origin cam.pos -- and parks the
+// answer as one byte per item (kBoxMiss / kBoxHit) behind the wave's ring entries, so the entry keeps its 16 bytes and every
+// bit pattern of d and seed.  take hands the byte to the lane with the item, and the segment entry of the same iteration
+// consumes it: it lives from the refill to there and in no register across a segment.
 constexpr uint32_t kRingRows = 4u, kDirect = 0x80000000u;
+constexpr uint32_t kRingWave = kRingRows * 64u;                    // entries of one wave's ring
+constexpr uint32_t kRingWaveStaged = kRingWave + (RB_ROOT_INSIDE ? kRingWave / 16u : 0u);  // ... and one byte per entry behind them (k_trace)
 constexpr float kNoPath = 2.0f;  // in .x of a staged entry: a padding pixel (no component of a normalised direction is 2)
 // LDS-qualified pointers: with generic ones the compiler folds "park or store directly" into one FLAT store through a
 // selected address, which is slower than either and loses the streaming hint
 struct ColorRing {
     lds_v4f* ring;  // this wave's kRingRows * 64 entries
 
-    DEV ColorRing(v4f* block_rings, uint32_t wave, uint32_t lane)
-        : ring((lds_v4f*)(block_rings + wave * (kRingRows * 64u))) {
+    // wave_entries: kRingWave, or kRingWaveStaged where stage_row parks the root-box bytes
+    DEV ColorRing(v4f* block_rings, uint32_t wave, uint32_t lane, uint32_t wave_entries = kRingWave)
+        : ring((lds_v4f*)(block_rings + wave * wave_entries)) {
         for (uint32_t k = 0; k < kRingRows; k++) tag(k * 64u + lane) = 0u;
     }
     DEV lds_u32& tag(uint32_t e) const { return ((lds_u32*)ring)[e * 4u + 3u]; }
+    typedef __attribute__((address_space(3))) uint8_t lds_u8;
+    DEV lds_u8& box(uint32_t e) const { return ((lds_u8*)(ring + kRingWave))[e]; }
 
     // a finished path; `item` may carry kDirect
     DEV void finish(float4* __restrict__ colors, uint32_t item, f3 c) const {
@@ -268,6 +280,7 @@ struct ColorRing {
     DEV void stage_row(const KParams& p, uint32_t lane, uint32_t row, uint32_t tx, uint32_t ty, uint32_t hs) const {
         const uint32_t x = tx * 8u + (lane & 7u), ly = ty * 8u + (lane >> 3);   // item_pixel's coordinates for pixel `lane`
         v4f v = {kNoPath, 0.0f, 0.0f, 0.0f};
+        const uint32_t e = (row & (kRingRows - 1u)) * 64u + lane;
         if ((x < p.u.width) && (ly < p.local_rows)) {
             const uint32_t y = global_row(p, ly);
             if (y < p.u.height) {
@@ -275,15 +288,33 @@ struct ColorRing {
                 uint32_t seed;
                 start_ray_hashed(p, x, y, y * p.u.width + x, hs, d, seed);
                 v = v4f{d.x, d.y, d.z, __uint_as_float(seed)};
+#if RB_ROOT_INSIDE
+                if (p.u.bvh_node_count == 1u) {   // the single-node walk's own test, on its own reciprocals
+                    const v4f n0 = ((cf4p)p.nodes)[0], n1 = ((cf4p)p.nodes)[1];
+                    // 1.0f / x is what rcp_exact returns, bit for bit, with or without its fast way (rb_device_math.hpp); written
+                    // as the division the two unrolled copies of this pass stay within the kernel's static instruction ceiling
+                    // (tests/test_ktrace_valu_count.py), and at 64 of 64 lanes once per row the guards would save nothing to speak of
+                    const f3 inv = mk(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+                    // (stored here, by the lanes that have a path: the byte of a padding pixel is never used -- take() says "no
+                    // path" -- and a launch without a single-node tree never looks at any: intersect_bvh returns in front of the box)
+                    box(e) = isect_aabb(ld3(p.cam.pos), inv, mk(n0.x, n0.y, n0.z), mk(n1.x, n1.y, n1.z)) ? (uint8_t)kBoxHit : (uint8_t)kBoxMiss;
+                }
+#endif
             }
         }
-        ring[(row & (kRingRows - 1u)) * 64u + lane] = v;
+        ring[e] = v;
     }
     // the lane that is handed `item`: its staged start; false for a padding pixel.  The entry is left with tag 0.
-    DEV bool take(uint32_t item, f3& d, uint32_t& seed) const {
+    // known: what stage_row found for the primary and the root box (kBoxUnknown in a build without RB_ROOT_INSIDE).
+    DEV bool take(uint32_t item, f3& d, uint32_t& seed, uint32_t& known) const {
         const uint32_t e = item & (kRingRows * 64u - 1u);
         const v4f v = ring[e];
         tag(e) = 0u;
+#if RB_ROOT_INSIDE
+        known = box(e);
+#else
+        known = kBoxUnknown;
+#endif
         d = mk(v.x, v.y, v.z);
         seed = __float_as_uint(v.w);
         return v.x != kNoPath;
@@ -445,7 +476,7 @@ DEV void trace_body(const KParams& p, v4f* s_ring) {
     const uint32_t total_items = tiles_x * tiles_y * S * 64u;  // host keeps this < 2^31
     float4* __restrict__ colors = reinterpret_cast<float4*>(p.colors);
     Tally<STATS> tl;
-    ColorRing cring(s_ring, tid >> 6, lane);
+    ColorRing cring(s_ring, tid >> 6, lane, STAGED ? kRingWaveStaged : kRingWave);
     bool active = false, exhausted = false;
     uint32_t item = 0;
     uint32_t loc_next = 0, loc_end = 0;  // this wave's reserved item range (wave-uniform)
@@ -464,6 +495,7 @@ DEV void trace_body(const KParams& p, v4f* s_ring) {
         // ---- hand items to idle lanes: ItemQueue::refill spelled out (in this kernel, the hottest one,
         // the helper form changes the register allocation and costs 0.8 %)
         unsigned long long idle = __ballot(!active);
+        uint32_t box = kBoxUnknown;   // a lane that takes a staged primary below: its root-box answer, for this iteration's segment
         for (int round = 0; round < 2 && idle != 0ull; round++) {
             if (loc_next == loc_end) {
                 if (exhausted) break;
@@ -503,7 +535,7 @@ DEV void trace_body(const KParams& p, v4f* s_ring) {
                 }
                 if (take) {
                     const uint32_t it = loc_next + rank;
-                    if (cring.take(it, pt.d, pt.seed)) {
+                    if (cring.take(it, pt.d, pt.seed, box)) {
                         pt.o = ld3(rp.cam.pos);
                         pt.color = mk(0, 0, 0);
                         pt.att = mk(1, 1, 1);
@@ -547,7 +579,7 @@ DEV void trace_body(const KParams& p, v4f* s_ring) {
         // (53 v_mov_b32 per iteration; profiles/r12_ktrace_moves_before.txt).
         if (__ballot(active) == 0ull && exhausted && loc_next == loc_end) break;
         if (active) {
-            const bool alive = segment<STATS, MULTI, JOINED, !MULTI>(p, pt, &s_stack[tid], kTraceBlock, tl);
+            const bool alive = segment<STATS, MULTI, JOINED, !MULTI>(p, pt, &s_stack[tid], kTraceBlock, tl, box);
             if (!alive) {
                 cring.finish(colors, item, pt.color);
                 tl.paths++;
@@ -560,7 +592,7 @@ DEV void trace_body(const KParams& p, v4f* s_ring) {
 }
 template <bool STATS, bool MULTI, int WAVES = RB_TRACE_WAVES>
 __global__ void __launch_bounds__(kTraceBlock, WAVES) k_trace(const KParams p) {
-    __shared__ __attribute__((aligned(16))) v4f s_ring[(kTraceBlock / 64u) * kRingRows * 64u];
+    __shared__ __attribute__((aligned(16))) v4f s_ring[(kTraceBlock / 64u) * (MULTI ? kRingWave : kRingWaveStaged)];
     // the counting build of the per-segment ablation keeps the two scatter normalizes: one costs it 6 more spilled registers
     trace_body<STATS, MULTI, !MULTI, !(STATS && MULTI)>(p, s_ring);
 }

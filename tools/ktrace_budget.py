@@ -127,6 +127,9 @@ def rows(blocks):
 
 # ---------------------------------------------------------------------------------------------- the once-per-iteration path
 MEASURED_VALU_PER_SEGMENT, ACTIVE_LANES, SEGMENTS_PER_PATH = 26.89, 63.6, 5.155   # profiles/r25_c2_pmc.json; profiles/r15_ktrace_phases.txt
+# iterations of C2 that still run the root box's slab path where a wave can branch past it (RB_ROOT_INSIDE): expected under 1 %
+# (origins rounded onto a face, points under a resting sphere whose offset origin falls below the floor); not measured yet
+ROOT_BOX_SLAB_EXEC = 0.0
 
 
 def _has(b, *prefixes):
@@ -141,6 +144,18 @@ def _memory(b):
     return _has(b, "ds_", "global_", "flat_", "buffer_", "scratch_")
 
 
+def _three_quotients(b):
+    """the compiler's division of three numerators by one denominator in one block (a normalize) -- not three reciprocals, whose
+    v_div_fixup_f32 all end in the numerator 1.0 (stage_row's 1 / d for the root box of the row's primaries)"""
+    fix = [i for i in b.instrs if i.op.startswith("v_div_fixup_f32")]
+    return len(fix) == 3 and not all(i.args.replace(" ", "").endswith(",1.0") for i in fix)
+
+
+def _three_reciprocals(b):
+    fix = [i for i in b.instrs if i.op.startswith("v_div_fixup_f32")]
+    return len(fix) == 3 and all(i.args.replace(" ", "").endswith(",1.0") for i in fix)
+
+
 def normalize_sites(blocks):
     """[(first index, last index, index of the slow division)] of every normalize in text order.  A site's own blocks: the
     compiler's division of the three numerators (three v_div_fixup_f32), behind it the fast division (a v_rcp_f32, no
@@ -148,7 +163,7 @@ def normalize_sites(blocks):
     exec-mask joins.  The dot product and the compares of the first guard sit in the block in front, with other code."""
     out = []
     for k, b in enumerate(blocks):
-        if _n(b, "v_div_fixup_f32") != 3 or _has(b, "v_cvt_f32_u32"):   # (hash_to_color divides three converted integers)
+        if not _three_quotients(b) or _has(b, "v_cvt_f32_u32"):   # (hash_to_color divides three converted integers)
             continue
         first = k
         while first > 0:
@@ -168,9 +183,42 @@ def normalize_sites(blocks):
     return out
 
 
+def _is_slab(b):
+    """the slab arithmetic of isect_aabb: six subtractions, six multiplies and the min / max chains in one block"""
+    return _n(b, "v_sub_f32") + _n(b, "v_subrev_f32") >= 6 and _has(b, "v_min_f32") and _has(b, "v_max_f32") and _has(b, "v_min3_f32", "v_max3_f32")
+
+
+def root_box_span(blocks, lo, hi):
+    """(first, last) index of the root box's blocks among blocks[lo:hi] -- the three rcp_exact sites (each a guard, the compiler's
+    division of ONE numerator behind it, v_rcp_f32 and two fma beside it) and the slab arithmetic -- or None.  The division blocks
+    hold one v_div_fixup_f32 each, so normalize_sites, which wants three in a block, does not take them for an anchor.  The guard
+    of the first site belongs to the span where it has a block of its own (a build that branches past the box); where it shares
+    its block with the code in front, it stays there."""
+    slab = [k for k in range(lo, hi) if _is_slab(blocks[k])]
+    if not slab:
+        return None
+    z = slab[0]
+    if _three_reciprocals(blocks[z]):        # stage_row: 1 / d as three plain divisions, in the slab test's own block
+        return (z, z)
+    a = z
+    while a - 1 >= lo:
+        q = blocks[a - 1]
+        one_div = _n(q, "v_div_fixup_f32") == 1 and _n(q, "v_div_scale_f32") == 2
+        newton = _has(q, "v_rcp_f32") and not _has(q, "v_div_scale_f32") and len(q.valu) <= 4
+        guard = _has(q, "v_and_b32") and _has(q, "v_cmp_") and len(q.valu) <= 6 and not _memory(q) and not _has(q, "v_cmp_o_f32", "v_cmp_u_f32")
+        if one_div or newton or guard or not q.valu:
+            a -= 1
+        else:
+            break
+    while a < z and not blocks[a].valu:      # (scalar-only blocks in front belong to what branches here)
+        a += 1
+    sites = sum(_n(blocks[k], "v_div_fixup_f32") == 1 for k in range(a, z + 1))
+    return (a, z) if sites == 3 else None
+
+
 def _slow_path(b):
     """a block only lanes outside a guard run: the compiler's division, or its square root (the one that tests the class)"""
-    return (_n(b, "v_div_fixup_f32") == 3 and not _has(b, "v_cvt_f32_u32")) or (_has(b, "v_sqrt_f32") and _has(b, "v_cmp_class_f32"))
+    return (_three_quotients(b) and not _has(b, "v_cvt_f32_u32")) or (_has(b, "v_sqrt_f32") and _has(b, "v_cmp_class_f32"))
 
 
 def once_groups(blocks):
@@ -211,6 +259,11 @@ def once_groups(blocks):
     entry = t
     while entry - 1 > h and not _memory(blocks[entry - 1]) and not any(lo <= entry - 1 <= hi for lo, hi in rows_span):
         entry -= 1
+    # the root box: in segment entry, and (a build that stages the primaries' answer) in each stage_row behind its normalize
+    box_entry = root_box_span(blocks, entry, t)
+    box_rows = [root_box_span(blocks, sites[n][1] + 1, hi + 1) for n, (lo, hi) in zip(pre, rows_span)]
+    # ... which a wave whose lanes all have their answer branches past, where the rule's NaN test stands in front of it
+    box_skipped = box_entry is not None and any(_has(blocks[k], "v_cmp_o_f32", "v_cmp_u_f32") for k in range(entry, box_entry[0]))
     tail_first = sites[post[-1]][1] + 1 if post else r + 1                # behind the last normalize: the path's end
     scatter = (sites[post[1]][1] + 1, sites[post[-1]][0] - 1) if len(post) >= 3 else (0, -1)
     tex = [k for k in range(scatter[0], scatter[1] + 1) if _has(blocks[k], "global_load", "flat_load", "buffer_load")]
@@ -244,14 +297,25 @@ def once_groups(blocks):
                 put(which, b, ex, kind, why)
         elif k < h:
             put("blocks laid out in front of the loop's header (the join behind a finished path)", b, 1.0, "assumed", "the loop's latch")
-        elif _n(b, "v_div_fixup_f32") == 3:
+        elif _three_quotients(b):
             put("resolve and material: hash_to_color", b, 0.0, "assumed", "C2 renders without the colour hash")
         elif h <= k < t:
             in_row = [n for n, (lo, hi) in enumerate(rows_span) if lo <= k <= hi]
             if in_row:
                 first = in_row[0] == 0
-                put(f"row opening: stage_row to the ring store, refill round {in_row[0] + 1}", b, row_ex if first else 0.0, "assumed",
-                    "1 / 5.155" if first else "second round: not reached")
+                staged = box_rows[in_row[0]]
+                if staged and staged[0] <= k <= staged[1]:
+                    put(f"row opening: root box of the row's 64 primaries (reciprocals, slab test), refill round {in_row[0] + 1}", b, row_ex if first else 0.0,
+                        "assumed", "1 / 5.155; the divisions behind the reciprocals' guards are branched over" if first else "second round: not reached")
+                else:
+                    put(f"row opening: stage_row to the ring store, refill round {in_row[0] + 1}", b, row_ex if first else 0.0, "assumed",
+                        "1 / 5.155" if first else "second round: not reached")
+            elif box_entry and box_entry[0] <= k <= box_entry[1]:
+                if box_skipped:
+                    put("root box: reciprocals and slab test", b, ROOT_BOX_SLAB_EXEC, "assumed",
+                        "only a wave with a lane that has no answer: C2's secondary rays start inside the box, its primaries' answers are staged")
+                else:
+                    put("root box: reciprocals and slab test", b, 1.01, "measured", "segment entry row; the divisions are branched over")
             elif k >= entry:
                 put("segment entry and box test (from the refill's last memory access on: a new path's moves included)", b, 1.01, "measured", "segment entry row")
             elif k >= round2:
