@@ -1196,6 +1196,80 @@ int rb_denoise_guides(rb_engine* e, rb_guide* guides_out);
  * and finish, HIP events on the engine's stream, ms -- and, if not NULL, of the guide build it had to make (0: it had the guides). */
 int rb_last_denoise_ms(rb_engine* e, float* ms, float* guide_build_ms);
 
+/* ---- Temporal reprojection: the previous frame's history carried across a camera move (the normative
+ * definition; no reference counterpart).  The history half of a real-time path-tracing denoiser (Schied et al. 2017): every
+ * pixel's first hit is projected into the previous camera, the previous frame's colour and sample count are taken along where
+ * it saw the same surface there, and the current accumulation is merged onto them.  No variance, no filter: rb_denoise's
+ * bits stay as they are.  Every step is one IEEE binary32 operation in the order section 22.1 fixes -- max / min are
+ * `a > b ? a : b` / `a < b ? a : b` --, so the device equals the numpy model renderbaby_amd/temporal.py bit for bit, with
+ * section 13's one exception for the sign and payload of a NaN the arithmetic itself generates.  All buffers are in the
+ * orientation of the delivered frame (row-major, top row first, x mirrored), as rb_guide buffers and rb_denoise_buffers.
+ * A frame record is a float[4]: {mean r, g, b, count}; count: the samples the mean stands for.  Its output feeds the next call
+ * as prev4 and rb_denoise_buffers as color4.
+ * REPROJECT, pixel p at displayed column Xp, row Yp; G = cur_guides[p], V the previous view, NONE = four +0.0f, a dot is
+ * (x x + y y) + z z:  G.cls == 0 -> NONE.  e = G.pos - V.pos, z = e . V.fwd, a = e . V.right, b = e . V.up; !(z > 0) -> NONE.
+ * X = V.cx - (a / z) * V.sx, Y = V.cy - (b / z) * V.sy; !(X > -1 && X < (float)w && Y > -1 && Y < (float)h) -> NONE.
+ * X0 = floorf(X), fx = X - X0, ix = (int)X0 (the same for Y).  m_p[k] = max(G.albedo[k], albedo_floor), den = sigma_depth * G.t.
+ * Taps dy = 0, 1 (outer), dx = 0, 1 (inner), q = (ix + dx, iy + dy), bw = (dx ? fx : 1 - fx) * (dy ? fy : 1 - fy); a tap is
+ * skipped when q is outside the frame, !(bw > 0), prev_guides[q].cls != G.cls, a word of prev4[q] is non-finite or
+ * !(prev4[q].count > 0), !(G.normal . Gq.normal >= normal_min), !(|G.normal . (Gq.pos - G.pos)| <= den).  An accepted tap:
+ * hs[k] += bw * (prev4[q][k] / max(Gq.albedo[k], albedo_floor)), hn += bw * prev4[q].count, bs += bw.  !(bs > 0) -> NONE.
+ * hist[k] = (hs[k] / bs) * m_p[k], hl = min(hn / bs, max_history); a non-finite word -> NONE, else {hist, hl}.
+ * MERGE of hst (REPROJECT's result) and cur4[p] = {c, n}: out = cur4[p], the bits, if G.cls == 0, a word of cur4[p] is
+ * non-finite, !(n >= 0) or hst.count == 0; else tot = hst.count + n, out[k] = (hst[k] * hst.count + c[k] * n) / tot, out.count = tot. */
+typedef struct rb_view {            /* 64 B: a render camera as the inverse of the pixel-centre ray needs it */
+    float pos[3];   float cx;       /* cx = wm1 * 0.5f */
+    float right[3]; float cy;       /* cy = hm1 * 0.5f */
+    float up[3];    float sx;       /* sx = cx / (fov * aspect) */
+    float fwd[3];   float sy;       /* sy = cy / fov */
+} rb_view;
+typedef struct rb_reproject_params {   /* 32 B */
+    float sigma_depth;    /* finite, > 0: a tap is the same surface if |n_p . (P_q - P_p)| <= sigma_depth * t_p  (section 13's plane distance) */
+    float normal_min;     /* finite, -1 .. 1: ... and n_p . n_q >= normal_min */
+    float albedo_floor;   /* finite, > 0: section 13's demodulation floor */
+    float max_history;    /* finite, >= 1: cap of the carried sample count */
+    uint32_t flags;       /* must be 0 */
+    uint32_t _reserved[3];/* must be 0 */
+} rb_reproject_params;
+/* The view of a render camera at w x h: aspect, fwd, right, up, fov, wm1 and hm1 by the steps of a render launch, in its order,
+ * then the four scalars as the comments above state, one operation each.  Host only: no device is touched.  NULL: RB_ERR_NULL_ARGUMENT. */
+int rb_view_from_camera(const rb_camera* cam, uint32_t w, uint32_t h, rb_view* out);
+/* sigma_depth 0.02 and albedo_floor 0.01 (the denoiser's), normal_min 0.9 and max_history 32. */
+int rb_reproject_default_params(rb_reproject_params* p);
+/* REPROJECT, and with cur4 MERGE on top, no engine: host arrays of w * h records in and out, the work on `device` (-1 =
+ * current).  cur4 == NULL: REPROJECT alone.  Before any device is touched: NULL params / prev_view / prev4 / prev_guides /
+ * cur_guides / out4: RB_ERR_NULL_ARGUMENT; a parameter out of range or non-finite, a non-finite word in the view, non-zero
+ * flags or reserved words, w * h >= 2^31: RB_ERR_INVALID_OPTIONS; w * h == 0 is RB_OK. */
+int rb_reproject_buffers(int32_t device, const rb_reproject_params* params, uint32_t w, uint32_t h, const rb_view* prev_view,
+                         const float* prev4, const rb_guide* prev_guides, const rb_guide* cur_guides, const float* cur4, float* out4);
+/* The same with every buffer in device memory of the engine's device, 16-byte aligned, validated as rb_cast_rays_device's;
+ * d_cur4 may be NULL.  The engine lends its device and its stream, as to rb_light_points_device: queued there, not waited for
+ * (rb_sync is the wait); RB_ERR_NOT_INITIALIZED before the first update; a multi-device handle answers on devices[0];
+ * rb_last_query_kernel_name reports "k_reproject", rb_last_query_ms its time. */
+int rb_reproject_device(rb_engine* e, const rb_reproject_params* params, uint32_t w, uint32_t h, const rb_view* prev_view,
+                        const float* d_prev4, const rb_guide* d_prev_guides, const rb_guide* d_cur_guides, const float* d_cur4, float* d_out4);
+/* What a viewer calls once per displayed frame, after its passes.  The engine keeps a history H (a frame-record plane, a copy
+ * of the guide planes, their rb_view and size, a valid flag) and a base B (one frame-record plane, valid until the next
+ * accepted rb_update).  A call: the guides (as rb_denoise); if B is not valid, B = REPROJECT(H -> the current guides) -- every
+ * record NONE if H is invalid, of another size or has a non-finite view --; F = MERGE(B, {the mean radiance of section 13.1,
+ * acc.w}); H = {F, the current guide planes, the current view}; rb_denoise's filter on F with dparams into the outputs.
+ * B keeps repeated calls within one update from counting their own samples twice.  rparams / dparams NULL:
+ * RB_ERR_NULL_ARGUMENT.  Outputs, side effects and refusals are rb_denoise's; a refused call changes nothing, H included;
+ * with no valid history the outputs are rb_denoise's bit for bit. */
+int rb_denoise_history(rb_engine* e, const rb_reproject_params* rparams, const rb_denoise_params* dparams, uint8_t* rgba_out,
+                       float* linear_out);
+/* ... with the outputs in device memory, as rb_denoise_device. */
+int rb_denoise_history_device(rb_engine* e, const rb_reproject_params* rparams, const rb_denoise_params* dparams, uint8_t* d_rgba_out,
+                              float* d_linear_out);
+/* F of the most recent rb_denoise_history (w * h frame records), for tests and tools; no history, or one of another
+ * size than the current frame: RB_ERR_NOT_INITIALIZED. */
+int rb_history_read(rb_engine* e, float* out4);
+/* Drops H and B: the next rb_denoise_history starts without history. */
+int rb_history_reset(rb_engine* e);
+/* Measurement aid for tools/reproject_rate.py (it may change or go): kernel time of REPROJECT (0: the base was valid) plus MERGE
+ * in the most recent rb_denoise_history, HIP events on the engine's stream, ms. */
+int rb_last_reproject_ms(rb_engine* e, float* ms);
+
 /* Which builder produced the library's own tree: "host-sah", "device-ploc", "device-lbvh", or "" when
  * there is none (flag not set, single-node tree, or the scene keeps the exact walk).  Valid after the
  * first rb_dispatch / rb_render that follows an update.  `build_ms`, if not NULL, receives the wall
@@ -1286,6 +1360,15 @@ static_assert(offsetof(rb_guide, cls) == 28, "cls @28");
 static_assert(offsetof(rb_guide, albedo) == 32, "albedo @32");
 static_assert(offsetof(rb_denoise_params, sigma_depth) == 8, "sigma_depth @8");
 static_assert(offsetof(rb_denoise_params, flags) == 20, "flags @20");
+static_assert(sizeof(rb_view) == 64, "rb_view is 64 B");
+static_assert(offsetof(rb_view, cx) == 12, "cx @12");
+static_assert(offsetof(rb_view, right) == 16, "right @16");
+static_assert(offsetof(rb_view, up) == 32, "up @32");
+static_assert(offsetof(rb_view, fwd) == 48, "fwd @48");
+static_assert(offsetof(rb_view, sy) == 60, "sy @60");
+static_assert(sizeof(rb_reproject_params) == 32, "rb_reproject_params is 32 B");
+static_assert(offsetof(rb_reproject_params, max_history) == 12, "max_history @12");
+static_assert(offsetof(rb_reproject_params, flags) == 16, "flags @16");
 #else
 _Static_assert(sizeof(rb_camera) == 48, "Camera is 48 B");
 _Static_assert(sizeof(rb_uniforms) == 144, "Uniforms is 144 B");
@@ -1316,6 +1399,8 @@ _Static_assert(sizeof(rb_emitter) == 64, "rb_emitter is 64 B");
 _Static_assert(sizeof(rb_light_params) == 32, "rb_light_params is 32 B");
 _Static_assert(sizeof(rb_guide) == 48, "rb_guide is 48 B");
 _Static_assert(sizeof(rb_denoise_params) == 32, "rb_denoise_params is 32 B");
+_Static_assert(sizeof(rb_view) == 64, "rb_view is 64 B");
+_Static_assert(sizeof(rb_reproject_params) == 32, "rb_reproject_params is 32 B");
 #endif
 
 #endif /* RB_ABI_H */

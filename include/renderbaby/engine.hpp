@@ -427,6 +427,58 @@ class Engine final : public Renderer {
         check(h_->e, rb_denoise_guides(h_->e, g.data()));
         return g;
     }
+    // ---- temporal reprojection (rb_abi.h): the previous frame's history carried across a camera move
+    static rb_view view_from_camera(const rb_camera& cam, uint32_t w, uint32_t h) {
+        rb_view v{};
+        check(nullptr, rb_view_from_camera(&cam, w, h, &v));
+        return v;
+    }
+    static rb_reproject_params reproject_defaults() {
+        rb_reproject_params p{};
+        (void)rb_reproject_default_params(&p);
+        return p;
+    }
+    // REPROJECT, with cur4 MERGE on top, on host arrays of w * h records; no engine
+    static std::vector<float> reproject_buffers(const rb_reproject_params& p, uint32_t w, uint32_t h, const rb_view& prev_view,
+                                                const std::vector<float>& prev4, const std::vector<rb_guide>& prev_guides,
+                                                const std::vector<rb_guide>& cur_guides, const std::vector<float>* cur4 = nullptr, int32_t device = -1) {
+        std::vector<float> out(static_cast<size_t>(w) * h * 4);
+        check(nullptr, rb_reproject_buffers(device, &p, w, h, &prev_view, prev4.data(), prev_guides.data(), cur_guides.data(),
+                                            cur4 ? cur4->data() : nullptr, out.data()));
+        return out;
+    }
+    // the same on the engine's device memory (d_cur4 may be null): queued on the engine's stream -- sync() waits
+    void reproject(const rb_reproject_params& p, uint32_t w, uint32_t h, const rb_view& prev_view, const float* d_prev4, const rb_guide* d_prev_guides,
+                   const rb_guide* d_cur_guides, const float* d_cur4, float* d_out4) {
+        check(h_->e, rb_reproject_device(h_->e, &p, w, h, &prev_view, d_prev4, d_prev_guides, d_cur_guides, d_cur4, d_out4));
+    }
+    // denoise() on the frame with its history; call once per displayed frame, after its passes
+    std::vector<uint8_t> denoise_history(const rb_reproject_params& rp = reproject_defaults(), const rb_denoise_params& dp = denoise_defaults(),
+                                         std::vector<float>* linear_out = nullptr) {
+        uint32_t w = 0, h = 0;
+        check(h_->e, rb_get_size(h_->e, &w, &h));
+        std::vector<uint8_t> rgba(static_cast<size_t>(w) * h * 4);
+        if (linear_out) linear_out->resize(static_cast<size_t>(w) * h * 4);
+        check(h_->e, rb_denoise_history(h_->e, &rp, &dp, rgba.data(), linear_out ? linear_out->data() : nullptr));
+        return rgba;
+    }
+    void denoise_history_device(const rb_reproject_params& rp, const rb_denoise_params& dp, uint8_t* d_rgba_out, float* d_linear_out = nullptr) {
+        check(h_->e, rb_denoise_history_device(h_->e, &rp, &dp, d_rgba_out, d_linear_out));
+    }
+    // the frame records {mean r, g, b, count} of the most recent denoise_history, before the filter
+    std::vector<float> history() {
+        uint32_t w = 0, h = 0;
+        check(h_->e, rb_get_size(h_->e, &w, &h));
+        std::vector<float> f(static_cast<size_t>(w) * h * 4);
+        check(h_->e, rb_history_read(h_->e, f.data()));
+        return f;
+    }
+    void history_reset() { check(h_->e, rb_history_reset(h_->e)); }
+    float last_reproject_ms() {
+        float ms = 0.0f;
+        check(h_->e, rb_last_reproject_ms(h_->e, &ms));
+        return ms;
+    }
     // the displayed pixel (px from the left, py from the top): "sphere 3" / "mesh 2, triangle 517" for a click
     rb_hit pick(uint32_t px, uint32_t py, rb_surface* surface = nullptr) {
         rb_hit hit{};

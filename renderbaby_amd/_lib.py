@@ -124,6 +124,15 @@ SIGNATURES = {
     "rb_denoise_device": (i32, [vp, vp, vp, vp]),
     "rb_denoise_guides": (i32, [vp, vp]),
     "rb_last_denoise_ms": (i32, [vp, P(C.c_float), P(C.c_float)]),
+    "rb_view_from_camera": (i32, [vp, u32, u32, vp]),
+    "rb_reproject_default_params": (i32, [vp]),
+    "rb_reproject_buffers": (i32, [i32, vp, u32, u32, vp, vp, vp, vp, vp, vp]),
+    "rb_reproject_device": (i32, [vp, vp, u32, u32, vp, vp, vp, vp, vp, vp]),
+    "rb_denoise_history": (i32, [vp, vp, vp, vp, vp]),
+    "rb_denoise_history_device": (i32, [vp, vp, vp, vp, vp]),
+    "rb_history_read": (i32, [vp, vp]),
+    "rb_history_reset": (i32, [vp]),
+    "rb_last_reproject_ms": (i32, [vp, P(C.c_float)]),
     "rb_fast_bvh_builder": (C.c_char_p, [vp, vp]),
     "rb_sphere_tree_builder": (C.c_char_p, [vp, vp]),
     "rb_chunk_tree_builder": (C.c_char_p, [vp, vp]),

@@ -14,7 +14,8 @@ RECORDS = {rec: (np.dtype(elem), rec.itemsize // np.dtype(elem).itemsize) for re
     (abi.RAY, np.float32), (abi.SURFEL, np.float32), (abi.PROBE, np.float32), (abi.HIT, np.float32), (abi.SURFACE, np.float32),
     (abi.RADIANCE, np.float32), (abi.LIT, np.float32), (abi.OPENNESS, np.int32), (abi.SH9, np.float32), (abi.PROBE_DEPTH, np.float32))}
 # ... and a table a call reads whole, beside its per-item arrays: the emitters of direct_light, (n, 16) float32
-TABLES = {abi.EMITTER: (np.dtype(np.float32), abi.EMITTER.itemsize // 4)}
+# ... and the per-pixel planes of ``Engine.reproject``: guide records, (n, 12) float32, and frame records, (n, 4)
+TABLES = {rec: (np.dtype(np.float32), rec.itemsize // 4) for rec in (abi.EMITTER, abi.GUIDE, abi.FRAME_RECORD)}
 # the ids of random streams: uint32 on the host; as a tensor int32 or uint32, only the bits count
 SEEDS = np.dtype(np.uint32)
 

@@ -101,6 +101,12 @@ MASK_GROUND, MASK_TRIANGLES, MASK_SPHERES, MASK_LIGHTS, MASK_ALL = 1, 2, 4, 8, 1
 GUIDE = np.dtype([("normal", f4, (3,)), ("t", f4), ("pos", f4, (3,)), ("cls", u4), ("albedo", f4, (3,)), ("_pad", f4)])
 DENOISE_PARAMS = np.dtype([("iterations", u4), ("normal_power_log2", u4), ("sigma_depth", f4), ("sigma_color", f4),
                            ("albedo_floor", f4), ("flags", u4), ("_reserved", u4, (2,))])
+# temporal reprojection (rb_reproject* / rb_denoise_history): a render camera as the inverse of the
+# pixel-centre ray needs it, the parameters, and a frame record {mean r, g, b, count}
+VIEW = np.dtype([("pos", f4, (3,)), ("cx", f4), ("right", f4, (3,)), ("cy", f4), ("up", f4, (3,)), ("sx", f4), ("fwd", f4, (3,)), ("sy", f4)])
+REPROJECT_PARAMS = np.dtype([("sigma_depth", f4), ("normal_min", f4), ("albedo_floor", f4), ("max_history", f4), ("flags", u4),
+                             ("_reserved", u4, (3,))])
+FRAME_RECORD = np.dtype([("mean", f4, (3,)), ("count", f4)])
 # test aids (rb_debug_*own_tree / rb_debug_*sphere_tree): a node of the library's own triangle tree and of its sphere tree
 OWN_NODE = np.dtype([("lmin", f4, (3,)), ("left", u4), ("lmax", f4, (3,)), ("right", u4),
                      ("rmin", f4, (3,)), ("left_fa", f4), ("rmax", f4, (3,)), ("right_fa", f4)])
@@ -111,7 +117,8 @@ SIZES = {"camera": (CAMERA, 48), "uniforms": (UNIFORMS, 144), "material": (MATER
          "sphere": (SPHERE, 96), "point_light": (POINT_LIGHT, 96), "mesh": (MESH, 96),
          "bvh_node": (BVH_NODE, 48), "gpu_triangle": (GPU_TRIANGLE, 64),
          "ray": (RAY, 32), "hit": (HIT, 48), "surface": (SURFACE, 48),
-         "guide": (GUIDE, 48), "denoise_params": (DENOISE_PARAMS, 32), "camera_ex": (CAMERA_EX, 96),
+         "guide": (GUIDE, 48), "denoise_params": (DENOISE_PARAMS, 32), "view": (VIEW, 64),
+         "reproject_params": (REPROJECT_PARAMS, 32), "frame_record": (FRAME_RECORD, 16), "camera_ex": (CAMERA_EX, 96),
          "surfel": (SURFEL, 32), "hemi_params": (HEMI_PARAMS, 32), "openness": (OPENNESS, 8),
          "lightmap_params": (LIGHTMAP_PARAMS, 32), "probe": (PROBE, 16), "sh9": (SH9, 112),
          "probe_grid": (PROBE_GRID, 48), "lit": (LIT, 16),

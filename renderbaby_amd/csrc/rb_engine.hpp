@@ -211,13 +211,29 @@ struct rb_engine {
     // the denoiser (rb_denoise*): the guide planes of the scene and camera of the last accepted update (made
     // by the first denoise after it), the two colour buffers the iterations ping-pong between, staging for host outputs, and
     // events of its own: like a query it moves neither the work counters nor the timing of a launch group
-    rb::DevBuf<float> dn_nt, dn_pc, dn_al;
+    // (two sets of planes: the history of section 22 keeps the set its frame was made with while the next update's guides are
+    // built into the other one; dn_set is the current one)
+    rb::DevBuf<float> dn_nt[2], dn_pc[2], dn_al[2];
+    int dn_set = 0;
     bool dn_guides_valid = false;
     rb::DevBuf<float> dn_r[2], dn_linear;
     rb::DevBuf<uint32_t> dn_rgba;
     hipEvent_t ev_dn[4] = {nullptr, nullptr, nullptr, nullptr};   // guide build begin / end, filter begin / end
     float last_denoise_ms = 0.0f, last_guide_ms = 0.0f;
     bool denoise_ms_pending = false;   // rb_denoise_device returns without waiting: rb_last_denoise_ms reads the events when asked
+
+    // temporal reprojection (rb_denoise_history): the history H -- the frame records F of the most recent
+    // call, the set of guide planes they belong to (hist_set), their view and size --, and the base B: H carried into the current
+    // guides, made by the first call after an accepted update, so that repeated calls do not count their own samples twice
+    rb::DevBuf<float> hist_frame, hist_base;
+    int hist_set = 0;
+    rb::DevBuf<float> rp_planes;   // rb_reproject_device: the six planes of its two guide arrays
+    rb_view hist_view{};
+    uint32_t hist_w = 0, hist_h = 0;
+    bool hist_valid = false, hist_base_valid = false;
+    hipEvent_t ev_rp[2] = {nullptr, nullptr};   // REPROJECT (if made) and MERGE begin / end
+    float last_reproject_ms = 0.0f;
+    bool reproject_ms_pending = false;
 
     rb_stats stats{};
     float last_dispatch_ms = 0.0f;

@@ -571,6 +571,24 @@ int launch_guide_pack(const rb_uniforms& u, const rb_hit* hits, const rb_surface
 int launch_guide_split(const rb_guide* guides, size_t n, const GuidePlanes& g, void* stream);   // ABI records -> planes
 int launch_guide_join(const GuidePlanes& g, size_t n, rb_guide* guides, void* stream);          // and back
 
+// ---- rb_reproject.hip: temporal reprojection.  Frame records are float4 {mean r, g, b, count} per pixel;
+// the guides are rb_denoise.hip's planes.
+struct ReprojectArgs {
+    uint32_t w, h;
+    rb_view view;           // the previous camera
+    const float* prev4;     // the previous frame's records ...
+    GuidePlanes prev;       // ... and guides (read only)
+    GuidePlanes cur;        // the current guides (read only)
+    const float* cur4;      // nullptr: REPROJECT alone; else MERGE onto these records
+    float* out4;
+};
+bool reproject_params_valid(const rb_reproject_params& p, const char** why);
+bool view_finite(const rb_view& v);
+// k_reproject, asynchronous on `stream`; returns a hipError_t
+int launch_reproject(const rb_reproject_params& prm, const ReprojectArgs& a, void* stream);
+// k_history_merge: out4 = MERGE(base, {mean radiance of the accumulation (shader x order: mirrored here), acc.w}) by g's classes
+int launch_history_merge(uint32_t w, uint32_t h, const float* accum, const float* base, const GuidePlanes& g, float* out4, void* stream);
+
 // ---- rb_kernels.hip
 // All return hipError_t as int (0 = success); launches are asynchronous on `stream`.
 // launch_render: k_pixel and k_queue whole; of the stream kernels the trace launch alone.  Its colours are summed by

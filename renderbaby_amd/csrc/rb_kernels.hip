@@ -29,6 +29,7 @@ constexpr float kChunkKD = 16.0f * 5.9604645e-8f * 1.01f;   // along, the relati
 #define RB_CHUNK_MARGINS_DEFINED
 #include "rb_device_chunk.hpp"
 #include "rb_launch_plan.hpp"
+#include "rb_host_cam.hpp"
 
 #pragma clang fp contract(off)
 
@@ -1561,12 +1562,6 @@ uint32_t stream_kernel_max_threads(uint32_t blocks_per_cu) {
 // with the same -ffp-contract=off, and +, -, *, /, sqrt of binary32 are correctly rounded on both sides, so these
 // are the values the kernels used to work out for themselves (the parity suite compares every frame with the oracle).
 Cam host_cam(const rb_uniforms& u) {
-    struct V { float x, y, z; };
-    auto cross = [](V a, V b) { return V{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; };
-    auto normalize = [](V a) {
-        const float len = __builtin_sqrtf((a.x * a.x + a.y * a.y) + a.z * a.z);
-        return V{a.x / len, a.y / len, a.z / len};
-    };
     // ranges of rb_device_math.hpp's rcp_safe / div_safe_den
     auto fast_den = [](float b) {
         uint32_t x;
@@ -1575,17 +1570,12 @@ Cam host_cam(const rb_uniforms& u) {
         return (x - 0x0D800000u) < 0x64000000u && (x - 0x21800000u) < 0x3C000000u && (x & 0x007FFFFFu) != 0x007FFFFFu;
     };
     Cam c{};
-    c.aspect = (float)u.width / (float)u.height;
-    const V fwd = normalize(V{u.camera.dir[0], u.camera.dir[1], u.camera.dir[2]});
-    const V right = normalize(cross(V{0.0f, 1.0f, 0.0f}, fwd));
-    const V up = cross(fwd, right);
-    for (int i = 0; i < 3; i++) c.pos[i] = u.camera.pos[i];
-    c.fwd[0] = fwd.x, c.fwd[1] = fwd.y, c.fwd[2] = fwd.z;
-    c.right[0] = right.x, c.right[1] = right.y, c.right[2] = right.z;
-    c.up[0] = up.x, c.up[1] = up.y, c.up[2] = up.z;
-    c.fov = u.camera.pane_width / (2.0f * u.camera.pane_distance * c.aspect);
-    c.wm1 = (float)(u.width - 1u);
-    c.hm1 = (float)(u.height - 1u);
+    const CamBasis b = host_cam_basis(u.camera, u.width, u.height);   // rb_host_cam.hpp: the steps themselves
+    c.aspect = b.aspect;
+    for (int i = 0; i < 3; i++) c.pos[i] = u.camera.pos[i], c.fwd[i] = b.fwd[i], c.right[i] = b.right[i], c.up[i] = b.up[i];
+    c.fov = b.fov;
+    c.wm1 = b.wm1;
+    c.hm1 = b.hm1;
     c.fast_wh = (RB_FAST_DIV && fast_den(c.wm1) && fast_den(c.hm1)) ? 1u : 0u;
     c.inv_wm1 = c.fast_wh ? 1.0f / c.wm1 : 0.0f;
     c.inv_hm1 = c.fast_wh ? 1.0f / c.hm1 : 0.0f;

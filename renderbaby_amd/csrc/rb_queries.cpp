@@ -1,8 +1,8 @@
 // rb_queries.cpp -- what an engine answers besides frames: closest-hit queries (rb_cast_rays / rb_render_hits / rb_pick), any-hit
 // occlusion, path-traced radiance along given rays, camera and hemisphere rays, lightmap texels and irradiance probes made on the
 // device, light points from a baked probe grid with or without the probes' depth moments, direct light by shadow rays to the
-// scene's emitters, and the denoiser over the first-hit buffers, with their device forms, their getters and their C entry points
-// (rb_abi.h; DESIGN.md sections 11-21).
+// scene's emitters, the denoiser over the first-hit buffers and the history it can be given across a camera move, with their
+// device forms, their getters and their C entry points (rb_abi.h; DESIGN.md sections 11-22).
 // Every sequence is here once: one prologue (query_prologue), one timed
 // launch (timed_launch), one runner per form -- run_pieces for the host forms, device_query_locked for the device forms --, over
 // them one runner for the families of "n items, `samples` each" in both forms (run_family: radiance, camera, hemisphere,
@@ -14,6 +14,7 @@
 #include <initializer_list>
 
 #include "rb_engine.hpp"
+#include "rb_host_cam.hpp"
 
 namespace {
 
@@ -952,7 +953,8 @@ int light_visible_device_locked(rb_engine* e, const rb_probe_grid& g, const rb_s
 
 // ---- the denoiser (rb_abi.h).  Like a query it is queued on the engine's stream behind whatever runs
 // there, reads the scene and the committed accumulation, and writes buffers of its own.
-rb::GuidePlanes guide_planes(rb_engine* e) { return rb::GuidePlanes{e->dn_nt.ptr, e->dn_pc.ptr, e->dn_al.ptr}; }
+rb::GuidePlanes guide_planes(rb_engine* e, int set) { return rb::GuidePlanes{e->dn_nt[set].ptr, e->dn_pc[set].ptr, e->dn_al[set].ptr}; }
+rb::GuidePlanes guide_planes(rb_engine* e) { return guide_planes(e, e->dn_set); }
 
 int denoise_ready(rb_engine* e) {
     if (rb::is_group(e)) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "the denoiser does not take a multi-device handle: a tap would cross a stripe boundary");
@@ -979,9 +981,10 @@ int ensure_guides(rb_engine* e) {
     rb::DevBuf<rb_surface> surf;
     HIP_TRY(e, hits.resize(n));
     HIP_TRY(e, surf.resize(n));
-    HIP_TRY(e, e->dn_nt.resize(n * 4));
-    HIP_TRY(e, e->dn_pc.resize(n * 4));
-    HIP_TRY(e, e->dn_al.resize(n * 4));
+    if (e->hist_valid && e->hist_set == e->dn_set) e->dn_set ^= 1;   // the history keeps the planes its frame was made with (section 22)
+    HIP_TRY(e, e->dn_nt[e->dn_set].resize(n * 4));
+    HIP_TRY(e, e->dn_pc[e->dn_set].resize(n * 4));
+    HIP_TRY(e, e->dn_al[e->dn_set].resize(n * 4));
     if (n) {
         HIP_TRY(e, hipEventRecord(e->ev_dn[0], e->stream));
         const uint32_t piece_rows = frame_piece_rows(w);   // as rb_render_hits
@@ -1012,10 +1015,79 @@ int denoise_params_check(const rb_engine* e, const rb_denoise_params* prm) {
     return RB_OK;
 }
 
-// device == true: the outputs are the caller's device buffers and nothing is waited for
-int denoise_locked(rb_engine* e, const rb_denoise_params* prm, uint8_t* rgba_out, float* linear_out, bool device) {
+int reproject_params_check(const rb_engine* e, const rb_reproject_params* prm) {
+    const char* why = nullptr;
+    if (!rb::reproject_params_valid(*prm, &why)) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "rb_reproject_params: %s", why);
+    return RB_OK;
+}
+
+// the view of a render camera (rb_abi.h): rb_host_cam.hpp's steps, then one operation per scalar
+rb_view view_of(const rb_camera& cam, uint32_t w, uint32_t h) {
+    const rb::CamBasis b = rb::host_cam_basis(cam, w, h);
+    rb_view v{};
+    for (int k = 0; k < 3; k++) v.pos[k] = cam.pos[k], v.right[k] = b.right[k], v.up[k] = b.up[k], v.fwd[k] = b.fwd[k];
+    v.cx = b.wm1 * 0.5f;
+    v.cy = b.hm1 * 0.5f;
+    const float fa = b.fov * b.aspect;
+    v.sx = v.cx / fa;
+    v.sy = v.cy / b.fov;
+    return v;
+}
+
+// Steps 2 to 4 of rb_denoise_history (section 22.2) on the engine's stream; the guides are current.  Afterwards e->hist_frame
+// holds F.
+int history_step(rb_engine* e, const rb_reproject_params& prm) {
+    const uint32_t w = e->sc.width, h = e->sc.height;
+    const size_t n = static_cast<size_t>(w) * h;
+    for (hipEvent_t& x : e->ev_rp)
+        if (!x) HIP_TRY(e, hipEventCreate(&x));
+    e->reproject_ms_pending = false;
+    e->last_reproject_ms = 0.0f;
+    HIP_TRY(e, e->hist_base.resize(n * 4));
+    // (an accepted update stands between H and an invalid base, and ensure_guides has built its guides into the other set)
+    const bool carry = !e->hist_base_valid && e->hist_valid && e->hist_w == w && e->hist_h == h && rb::view_finite(e->hist_view) &&
+                       e->hist_set != e->dn_set;
+    if (!e->hist_base_valid && !carry) {
+        e->hist_valid = false;
+        HIP_TRY(e, e->hist_frame.resize(n * 4));
+    }
+    HIP_TRY(e, hipEventRecord(e->ev_rp[0], e->stream));
+    if (!e->hist_base_valid) {
+        if (carry) {
+            rb::ReprojectArgs a{};
+            a.w = w;
+            a.h = h;
+            a.view = e->hist_view;
+            a.prev4 = e->hist_frame.ptr;
+            a.prev = guide_planes(e, e->hist_set);
+            a.cur = guide_planes(e);
+            a.out4 = e->hist_base.ptr;
+            const int st = rb::launch_reproject(prm, a, e->stream);
+            if (st) return rb::fail(e, RB_ERR_DEVICE, "reproject kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
+        } else {
+            HIP_TRY(e, hipMemsetAsync(e->hist_base.ptr, 0, n * 16, e->stream));   // every record NONE
+        }
+        e->hist_set = e->dn_set;   // the history's guides from here on: this update's planes, shared with the filter
+        e->hist_view = view_of(e->sc.uniforms.camera, w, h);
+        e->hist_w = w;
+        e->hist_h = h;
+        e->hist_base_valid = true;
+    }
+    const int st = rb::launch_history_merge(w, h, e->slot[e->cur].accum.ptr, e->hist_base.ptr, guide_planes(e), e->hist_frame.ptr, e->stream);
+    if (st) return rb::fail(e, RB_ERR_DEVICE, "history merge launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
+    HIP_TRY(e, hipEventRecord(e->ev_rp[1], e->stream));
+    e->hist_valid = true;
+    e->reproject_ms_pending = true;
+    return RB_OK;
+}
+
+// device == true: the outputs are the caller's device buffers and nothing is waited for.  rprm: rb_denoise_history -- the filter
+// runs on F of section 22 instead of the mean radiance
+int denoise_locked(rb_engine* e, const rb_denoise_params* prm, uint8_t* rgba_out, float* linear_out, bool device,
+                   const rb_reproject_params* rprm = nullptr) {
     int rc = denoise_ready(e);
     if (!rc) rc = denoise_params_check(e, prm);
+    if (!rc && rprm) rc = reproject_params_check(e, rprm);
     if (rc) return rc;
     if (!rgba_out && !linear_out) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "rgba_out and linear_out are both NULL");
     const size_t n = static_cast<size_t>(e->sc.width) * e->sc.height;
@@ -1037,6 +1109,16 @@ int denoise_locked(rb_engine* e, const rb_denoise_params* prm, uint8_t* rgba_out
     for (int k = 0; k < 2; ++k) {
         HIP_TRY(e, e->dn_r[k].resize(n * 4));
         a.r[k] = e->dn_r[k].ptr;
+    }
+    if (!device) {   // (reserved before the history moves: a failed reservation leaves H as it was)
+        if (rgba_out) HIP_TRY(e, e->dn_rgba.resize(n));
+        if (linear_out) HIP_TRY(e, e->dn_linear.resize(n * 4));
+    }
+    if (rprm) {
+        rc = history_step(e, *rprm);
+        if (rc) return rc;
+        a.accum = nullptr;
+        a.color4 = e->hist_frame.ptr;
     }
     if (device) {
         a.rgba_out = reinterpret_cast<uint32_t*>(rgba_out);
@@ -1080,6 +1162,59 @@ int denoise_guides_locked(rb_engine* e, rb_guide* guides_out) {
     rc = query_copy_out(e, guides_out, joined.ptr, n * sizeof(rb_guide), page_locked(guides_out));
     if (rc) return rc;
     HIP_TRY(e, hipStreamSynchronize(e->stream));   // `joined` is freed on return
+    return RB_OK;
+}
+
+// ---- temporal reprojection (rb_abi.h)
+// the refusals the forms of rb_reproject share; before a device is touched (e may be NULL: the engine-less form)
+int reproject_check(rb_engine* e, const char* who, const rb_reproject_params* prm, uint32_t w, uint32_t h, const rb_view* view, const void* prev4,
+                    const void* prev_guides, const void* cur_guides, const void* out4) {
+    if (!prm || !view || !prev4 || !prev_guides || !cur_guides || !out4)
+        return rb::fail(e, RB_ERR_NULL_ARGUMENT, "%s: params / prev_view / prev4 / prev_guides / cur_guides / out4 is NULL", who);
+    if (const int rc = reproject_params_check(e, prm)) return rc;
+    if (!rb::view_finite(*view)) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: a word of prev_view is not finite", who);
+    if (static_cast<uint64_t>(w) * h >= (1ull << 31)) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: a frame of %u x %u pixels is too large", who, w, h);
+    return RB_OK;
+}
+
+int reproject_device_locked(rb_engine* e, const rb_reproject_params& prm, uint32_t w, uint32_t h, const rb_view& view, const float* d_prev4,
+                            const rb_guide* d_prev_guides, const rb_guide* d_cur_guides, const float* d_cur4, float* d_out4) {
+    const size_t n = static_cast<size_t>(w) * h;
+    int rc = device_range(e, d_prev4, n * 16, 16, "d_prev4");
+    if (!rc) rc = device_range(e, d_prev_guides, n * sizeof(rb_guide), 16, "d_prev_guides");
+    if (!rc) rc = device_range(e, d_cur_guides, n * sizeof(rb_guide), 16, "d_cur_guides");
+    if (!rc && d_cur4) rc = device_range(e, d_cur4, n * 16, 16, "d_cur4");
+    if (!rc) rc = device_range(e, d_out4, n * 16, 16, "d_out4");
+    if (rc) return rc;
+    HIP_TRY(e, e->rp_planes.reserve(n * 24));   // the planes of the two guide arrays: scratch in stream order
+    float* const planes = e->rp_planes.ptr;
+    return device_stream_locked(e, [&](rb::LaunchInfo* li) {
+        li->kernel_name = "k_reproject";
+        rb::ReprojectArgs a{};
+        a.w = w;
+        a.h = h;
+        a.view = view;
+        a.prev4 = d_prev4;
+        a.prev = rb::GuidePlanes{planes, planes + n * 4, planes + n * 8};
+        a.cur = rb::GuidePlanes{planes + n * 12, planes + n * 16, planes + n * 20};
+        a.cur4 = d_cur4;
+        a.out4 = d_out4;
+        if (const int st = rb::launch_guide_split(d_prev_guides, n, a.prev, e->stream)) return st;
+        if (const int st = rb::launch_guide_split(d_cur_guides, n, a.cur, e->stream)) return st;
+        return rb::launch_reproject(prm, a, e->stream);
+    });
+}
+
+int history_read_locked(rb_engine* e, float* out4) {
+    int rc = denoise_ready(e);
+    if (rc) return rc;
+    if (!e->hist_valid || e->hist_w != e->sc.width || e->hist_h != e->sc.height)   // (a history of another size is none: out4 is the current frame's)
+        return rb::fail(e, RB_ERR_NOT_INITIALIZED, "rb_history_read: the engine has no history of this size (rb_denoise_history makes it)");
+    const size_t n = static_cast<size_t>(e->hist_w) * e->hist_h;
+    if (n == 0) return RB_OK;
+    rc = query_copy_out(e, out4, e->hist_frame.ptr, n * 16, page_locked(out4));
+    if (rc) return rc;
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
     return RB_OK;
 }
 
@@ -1951,6 +2086,105 @@ int rb_denoise_buffers(int32_t device, const rb_denoise_params* params, uint32_t
     if (out4) s.download(out4, d_linear.ptr, n * 16);
     if (rgba_out) s.download(rgba_out, d_rgba.ptr, n * 4);
     return s.finish("rb_denoise_buffers");
+}
+
+int rb_view_from_camera(const rb_camera* cam, uint32_t w, uint32_t h, rb_view* out) {
+    if (!cam || !out) return rb::fail(nullptr, RB_ERR_NULL_ARGUMENT, "rb_view_from_camera: cam / out is NULL");
+    *out = view_of(*cam, w, h);
+    return RB_OK;
+}
+
+int rb_reproject_default_params(rb_reproject_params* p) {
+    if (!p) return RB_ERR_NULL_ARGUMENT;
+    *p = rb_reproject_params{};
+    p->sigma_depth = 0.02f;    // the denoiser's plane distance and floor (section 13)
+    p->normal_min = 0.9f;      // from the literature, or the sweep of DESIGN.md section 22.5: section 22.7 says which
+    p->albedo_floor = 0.01f;
+    p->max_history = 32.0f;
+    return RB_OK;
+}
+
+int rb_reproject_buffers(int32_t device, const rb_reproject_params* params, uint32_t w, uint32_t h, const rb_view* prev_view,
+                         const float* prev4, const rb_guide* prev_guides, const rb_guide* cur_guides, const float* cur4, float* out4) {
+    if (const int rc = reproject_check(nullptr, "rb_reproject_buffers", params, w, h, prev_view, prev4, prev_guides, cur_guides, out4)) return rc;
+    const size_t n = static_cast<size_t>(w) * h;
+    if (n == 0) return RB_OK;
+    rb::DevBuf<float> d_prev4, d_cur4, d_out, d_pl[6];
+    rb::DevBuf<rb_guide> d_guides;   // staging of one guide array at a time
+    DeviceScope s(device);
+    s.alloc(d_prev4, n * 4);
+    if (cur4) s.alloc(d_cur4, n * 4);
+    s.alloc(d_out, n * 4);
+    for (rb::DevBuf<float>& b : d_pl) s.alloc(b, n * 4);
+    s.alloc(d_guides, n);
+    rb::ReprojectArgs a{};
+    a.w = w;
+    a.h = h;
+    a.view = *prev_view;
+    a.prev4 = d_prev4.ptr;
+    a.prev = rb::GuidePlanes{d_pl[0].ptr, d_pl[1].ptr, d_pl[2].ptr};
+    a.cur = rb::GuidePlanes{d_pl[3].ptr, d_pl[4].ptr, d_pl[5].ptr};
+    a.cur4 = cur4 ? d_cur4.ptr : nullptr;
+    a.out4 = d_out.ptr;
+    s.upload(d_prev4.ptr, prev4, n * 16);
+    if (cur4) s.upload(d_cur4.ptr, cur4, n * 16);
+    s.upload(d_guides.ptr, prev_guides, n * sizeof(rb_guide));
+    s.run([&] { return rb::launch_guide_split(d_guides.ptr, n, a.prev, s.stream); });
+    s.upload(d_guides.ptr, cur_guides, n * sizeof(rb_guide));   // (in stream order behind the split that read the staging)
+    s.run([&] { return rb::launch_guide_split(d_guides.ptr, n, a.cur, s.stream); });
+    s.run([&] { return rb::launch_reproject(*params, a, s.stream); });
+    s.download(out4, d_out.ptr, n * 16);
+    return s.finish("rb_reproject_buffers");
+}
+
+int rb_reproject_device(rb_engine* e, const rb_reproject_params* params, uint32_t w, uint32_t h, const rb_view* prev_view, const float* d_prev4,
+                        const rb_guide* d_prev_guides, const rb_guide* d_cur_guides, const float* d_cur4, float* d_out4) {
+    return engine_entry(
+        e, static_cast<size_t>(w) * h,
+        [&] { return reproject_check(e, "rb_reproject_device", params, w, h, prev_view, d_prev4, d_prev_guides, d_cur_guides, d_out4); },
+        [&](rb_engine* t) { return reproject_device_locked(t, *params, w, h, *prev_view, d_prev4, d_prev_guides, d_cur_guides, d_cur4, d_out4); });
+}
+
+int rb_denoise_history(rb_engine* e, const rb_reproject_params* rparams, const rb_denoise_params* dparams, uint8_t* rgba_out, float* linear_out) {
+    if (!e || !rparams || !dparams) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    return denoise_locked(e, dparams, rgba_out, linear_out, false, rparams);
+}
+
+int rb_denoise_history_device(rb_engine* e, const rb_reproject_params* rparams, const rb_denoise_params* dparams, uint8_t* d_rgba_out,
+                              float* d_linear_out) {
+    if (!e || !rparams || !dparams) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    return denoise_locked(e, dparams, d_rgba_out, d_linear_out, true, rparams);
+}
+
+int rb_history_read(rb_engine* e, float* out4) {
+    if (!e) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (!out4) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "out4 is NULL");
+    return history_read_locked(e, out4);
+}
+
+int rb_history_reset(rb_engine* e) {
+    if (!e) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (rb::is_group(e)) return RB_OK;   // a multi-device handle keeps no history
+    e->hist_valid = false;
+    e->hist_base_valid = false;
+    return RB_OK;
+}
+
+int rb_last_reproject_ms(rb_engine* e, float* ms) {
+    if (!e || !ms) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (e->reproject_ms_pending) {   // the history step is not waited for: its events are read here
+        rb::set_device(e);
+        HIP_TRY(e, hipEventSynchronize(e->ev_rp[1]));
+        HIP_TRY(e, hipEventElapsedTime(&e->last_reproject_ms, e->ev_rp[0], e->ev_rp[1]));
+        e->reproject_ms_pending = false;
+    }
+    *ms = e->last_reproject_ms;
+    return RB_OK;
 }
 
 const char* rb_last_query_kernel_name(const rb_engine* e) {

@@ -493,6 +493,7 @@ int update_fields(rb_engine* e, const rb_config* cfg) {
     e->spec_valid = false;
     e->color_budget = 0;
     e->dn_guides_valid = false;   // the denoiser's guides are this scene's and this camera's
+    e->hist_base_valid = false;   // ... and so is the base the history was carried into (section 22)
     e->emit_valid = false;        // ... and the emitter table this scene's
     for (uint32_t f = 0; f < rb::kFieldCount; ++f)
         if (const int rc = apply_field(e, static_cast<rb::Field>(f), plan, cfg)) return rc;
@@ -877,6 +878,8 @@ void rb_destroy(rb_engine* e) {
     for (hipEvent_t x : e->ev_q)
         if (x) (void)hipEventDestroy(x);
     for (hipEvent_t x : e->ev_dn)
+        if (x) (void)hipEventDestroy(x);
+    for (hipEvent_t x : e->ev_rp)
         if (x) (void)hipEventDestroy(x);
     for (hipEvent_t x : e->ev_lm)
         if (x) (void)hipEventDestroy(x);

@@ -833,6 +833,71 @@ class Engine:
         """(kernel ms of the most recent denoise, ms of the guide build it had to make -- 0 when it had the guides)"""
         return self._last_ms(self._lib.rb_last_denoise_ms, 2)
 
+    # ---- temporal reprojection (rb_abi.h; DESIGN.md section 22)
+    def reproject(self, prev4, prev_guides, view, cur_guides, cur4=None, params=None, out=None, size=None):
+        """rb_reproject_buffers on the engine's device / rb_reproject_device: REPROJECT of section 22.1, and with ``cur4`` MERGE on
+        top.  Host arrays: ``prev4`` / ``cur4`` (h, w, 4) float32 frame records, the guides abi.GUIDE[h, w] -> (h, w, 4) float32.
+        Torch tensors on the engine's device: (h * w, 4) float32 records and (h * w, 12) float32 guides, ``size`` = (w, h) -> an
+        (h * w, 4) tensor (``out`` if given); every tensor is used where it lies and nothing crosses to the host.  ``view``: the
+        previous camera's abi.VIEW (``view_from_camera``); ``params``: abi.REPROJECT_PARAMS, by default the library's."""
+        p = np.ascontiguousarray(reproject_defaults() if params is None else params, dtype=abi.REPROJECT_PARAMS).reshape(1)
+        v = np.ascontiguousarray(view, dtype=abi.VIEW).reshape(1)
+        f = Form(self.query_device, prev4, prev_guides, cur_guides, cur4, out)
+        if size is None:
+            if f.on_device or np.ndim(cur_guides) != 2:
+                raise ValueError("size: (w, h) is needed unless cur_guides is an abi.GUIDE[h, w] array")
+            size = np.shape(cur_guides)[::-1]
+        w, h = int(size[0]), int(size[1])
+        n = w * h
+        prev4, pp = f.input("prev4", _frame_records(prev4), abi.FRAME_RECORD, n)
+        pg, pgp = f.input("prev_guides", prev_guides, abi.GUIDE, n)
+        cg, cgp = f.input("cur_guides", cur_guides, abi.GUIDE, n)
+        cur4, cp = f.optional("cur4", None if cur4 is None else _frame_records(cur4), abi.FRAME_RECORD, n)
+        res, op = f.output("out", None if out is None else _frame_records(out), abi.FRAME_RECORD, n)
+        if n and f.on_device:
+            self._device_call(self._lib.rb_reproject_device, p.ctypes.data, w, h, v.ctypes.data, pp, pgp, cgp, cp, op)
+        elif n:
+            _check_global(self._lib.rb_reproject_buffers(self.query_device, p.ctypes.data, w, h, v.ctypes.data, pp, pgp, cgp, cp, op))
+        return res if f.on_device else res.view(np.float32).reshape(h, w, 4)
+
+    def denoise_history(self, rparams=None, dparams=None, linear=False, out=None):
+        """rb_denoise_history: ``denoise`` on the frame with its history -- the previous call's records carried across the
+        camera move of the last update (REPROJECT), the accumulation merged onto them (MERGE), the filter over the result.
+        ``rparams``: abi.REPROJECT_PARAMS (``temporal.params(...)``), ``dparams``: abi.DENOISE_PARAMS, by default the library's.
+        ``linear`` and ``out`` as ``denoise`` has them.  Call it once per displayed frame, after the frame's passes."""
+        rp = np.ascontiguousarray(reproject_defaults() if rparams is None else rparams, dtype=abi.REPROJECT_PARAMS).reshape(1)
+        dp = np.ascontiguousarray(denoise_defaults() if dparams is None else dparams, dtype=abi.DENOISE_PARAMS).reshape(1)
+        w, h = self.size()
+        if is_tensor(out):
+            import torch
+            dtype = torch.float32 if linear else torch.uint8
+            if out.device != torch_device(self.query_device) or out.dtype != dtype or not out.is_contiguous() \
+                    or tuple(out.shape) != (h, w, 4):
+                raise ValueError(f"out: a contiguous {dtype} tensor of shape ({h}, {w}, 4) on cuda:{self.query_device} is needed")
+            ptr = out.data_ptr() if out.numel() else None
+            self._device_call(self._lib.rb_denoise_history_device, rp.ctypes.data, dp.ctypes.data, *((None, ptr) if linear else (ptr, None)))
+            return out
+        res, _ = host_out("out", out, np.float32 if linear else np.uint8, (h, w, 4))
+        ptr = res.ctypes.data
+        self._check(self._lib.rb_denoise_history(self._h, rp.ctypes.data, dp.ctypes.data, *((None, ptr) if linear else (ptr, None))))
+        return res
+
+    def history(self):
+        """rb_history_read: the frame records of the most recent ``denoise_history`` -- (h, w, 4) float32, {mean r, g, b,
+        count} -- before the filter; RenderError (not initialised) without one."""
+        w, h = self.size()
+        out = np.empty((h, w, 4), dtype=np.float32)
+        self._check(self._lib.rb_history_read(self._h, out.ctypes.data))
+        return out
+
+    def history_reset(self):
+        """rb_history_reset: the next ``denoise_history`` starts without history"""
+        self._check(self._lib.rb_history_reset(self._h))
+
+    def last_reproject_ms(self):
+        """kernel ms of REPROJECT (0 when the base was there already) plus MERGE in the most recent denoise_history"""
+        return self._last_ms(self._lib.rb_last_reproject_ms)
+
     def fast_bvh_builder(self):
         """("host-sah" | "device-lbvh" | "", build milliseconds) of the tree RB_FLAG_FAST_BVH walks."""
         return self._builder(self._lib.rb_fast_bvh_builder)
@@ -1061,6 +1126,61 @@ def denoise_defaults():
     if rc != abi.RB_OK:
         raise RenderError(rc, "rb_denoise_default_params")
     return p[0]
+
+
+def view_from_camera(uniforms_or_camera, w=None, h=None):
+    """rb_view_from_camera: the abi.VIEW scalar of a render camera (abi.CAMERA with ``w`` and ``h``, or abi.UNIFORMS, which
+    brings its own size); host only.  ``temporal.view_from_camera`` is its numpy model."""
+    a = np.asarray(uniforms_or_camera)
+    if a.dtype == abi.UNIFORMS:
+        u = a.reshape(-1)[0]
+        a, w, h = u["camera"], (u["width"] if w is None else w), (u["height"] if h is None else h)
+    cam = np.ascontiguousarray(a, dtype=abi.CAMERA).reshape(1)
+    v = np.zeros(1, dtype=abi.VIEW)
+    _check_global(load().rb_view_from_camera(cam.ctypes.data, int(w), int(h), v.ctypes.data))
+    return v[0]
+
+
+def reproject_defaults():
+    """rb_reproject_default_params as an abi.REPROJECT_PARAMS scalar."""
+    p = np.zeros(1, dtype=abi.REPROJECT_PARAMS)
+    rc = load().rb_reproject_default_params(p.ctypes.data)
+    if rc != abi.RB_OK:
+        raise RenderError(rc, "rb_reproject_default_params")
+    return p[0]
+
+
+def _frame_records(x):
+    """(h, w, 4) or (n, 4) float32 frame records as abi.FRAME_RECORD[n]; a tensor as it stands"""
+    if is_tensor(x):
+        return x
+    a = np.asarray(x)
+    if a.dtype == abi.FRAME_RECORD:
+        return a
+    if a.ndim < 1 or a.shape[-1] != 4:
+        raise ValueError(f"frame records: (..., 4) float32 is needed, not {a.shape}")
+    if not (isinstance(x, np.ndarray) and a.dtype == np.float32 and a.flags.c_contiguous):
+        a = np.ascontiguousarray(a, dtype=np.float32)
+    return a.reshape(-1, 4).view(abi.FRAME_RECORD).reshape(-1)
+
+
+def reproject_buffers(prev4, prev_guides, view, cur_guides, cur4=None, params=None, device=-1):
+    """rb_reproject_buffers: REPROJECT of section 22.1 -- with ``cur4`` MERGE on top -- on its own: (h, w, 4) float32 frame
+    records and abi.GUIDE[h, w] in, (h, w, 4) float32 out; host arrays, the work on the GPU, no engine.
+    ``temporal.reproject`` and ``temporal.merge`` are its numpy model."""
+    cg = np.ascontiguousarray(cur_guides, dtype=abi.GUIDE)
+    pg = np.ascontiguousarray(prev_guides, dtype=abi.GUIDE)
+    if cg.ndim != 2 or pg.shape != cg.shape:
+        raise ValueError(f"previous guides {pg.shape} and current guides {cg.shape} differ")
+    h, w = cg.shape
+    f, call = _engineless(device)
+    p4, pp = f.input("prev4", _frame_records(prev4), abi.FRAME_RECORD, w * h)
+    c4, cp = f.optional("cur4", None if cur4 is None else _frame_records(cur4), abi.FRAME_RECORD, w * h)
+    p = np.ascontiguousarray(reproject_defaults() if params is None else params, dtype=abi.REPROJECT_PARAMS).reshape(1)
+    v = np.ascontiguousarray(view, dtype=abi.VIEW).reshape(1)
+    out = np.zeros((h, w, 4), dtype=np.float32)   # (a refused call writes nothing)
+    call("rb_reproject_buffers", p.ctypes.data, w, h, v.ctypes.data, pp or p4.ctypes.data, pg.ctypes.data, cg.ctypes.data, cp, out.ctypes.data)
+    return out
 
 
 def denoise_buffers(color, guides, params=None, device=-1):

@@ -1,0 +1,389 @@
+"""Temporal reprojection on the device (rb_reproject*, rb_denoise_history) against its numpy model
+(renderbaby_amd/temporal.py) and the hand-written expectations of tests/_reproject_cases.py.  Every comparison is exact, on
+uint32 views of the records, and leaves no pixel out."""
+import functools
+
+import numpy as np
+import pytest
+
+from renderbaby_amd import Change, Engine, RenderConfig, RenderError, abi, denoise, engine, scenes, temporal
+from tests import _reproject_cases as cases
+from tests._reproject_cases import bits
+from tests.conftest import has_gpu
+from tests.test_gpu_query import _copy
+
+pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not has_gpu(), reason="needs a GPU")]
+
+f32 = np.float32
+INVALID_OPTIONS, NULL_ARGUMENT, NOT_INITIALIZED = 18, 15, 17
+# (w, h): one pixel, one wave's row, one column, block and wave tails in both directions (a block is 64 x 4), several blocks
+SHAPES = [(1, 1), (64, 1), (1, 5), (67, 5), (130, 9), (64, 48)]
+REAL_SHAPES = [s for s in SHAPES if s[0] > 1 and s[1] > 1]   # a render camera needs two pixels each way (wm1, hm1 > 0)
+
+
+def same(got, want, what=""):
+    bad = np.argwhere((bits(got) != bits(want)).any(-1))
+    assert len(bad) == 0, (what, len(bad), bad[:4], [got[tuple(b)] for b in bad[:4]], [want[tuple(b)] for b in bad[:4]])
+
+
+# ---- 1. rb_reproject_buffers against the model
+def synthetic(w, h, seed, clean=False):
+    """a made-up pair of frames that takes every branch at any size: a plane seen under a view moved by a fraction of a pixel
+    plus jitter, three classes with class-0 islands, normals and plane distances on both sides of their thresholds, albedo on
+    both sides of the floor, records with non-finite words, zero and negative counts, points behind the view and off-screen.
+    ``clean``: the same plane moved by a quarter of a pixel and nothing that rejects a tap, so that the smallest frames blend too"""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    view = cases.flat_view(w, h)
+    yy, xx = np.mgrid[0:h, 0:w]
+    region = ((xx * 3) // max(w, 1) + (yy * 2) // max(h, 1)) % 3
+    classes = np.array([abi.HIT_GROUND, abi.HIT_TRIANGLE, abi.HIT_SPHERE], np.uint32)
+
+    def guides(shift_x, shift_y):
+        g = cases.flat_guides(view, w, h, shift_x=shift_x, shift_y=shift_y)
+        g["albedo"] = (rng.random((h, w, 3)) ** 3).astype(f32)
+        if clean:
+            return g
+        g["cls"] = classes[region]
+        g["cls"][rng.random((h, w)) < 0.08] = 0
+        n = np.array([0, 0, -1], f32) + rng.normal(0, 0.2, (h, w, 3)).astype(f32)
+        g["normal"] = (n / np.sqrt((n * n).sum(-1, keepdims=True), dtype=f32)).astype(f32)
+        g["pos"][..., 2] += rng.normal(0, 0.008, (h, w)).astype(f32)   # den = 0.02 t: on both sides of it
+        g["t"] = (f32(1) + rng.random((h, w)).astype(f32) * f32(0.2)).astype(f32)
+        return g
+    pg = guides(0.0, 0.0)
+    prev4 = np.concatenate([rng.gamma(0.5, 0.8, (h, w, 3)), rng.integers(1, 40, (h, w, 1))], -1).astype(f32)
+    cur4 = np.concatenate([rng.gamma(0.5, 0.8, (h, w, 3)), rng.integers(0, 5, (h, w, 1))], -1).astype(f32)
+    if clean:
+        return prev4, pg, view, guides(0.25, -0.25), cur4
+    cg = guides(0.37 + rng.normal(0, 0.8, (h, w)), -0.21 + rng.normal(0, 0.8, (h, w)))
+    k = max(1, h * w // 30)
+    for z in (-1.0, -2.5, np.nan, np.inf):   # z = 0, z < 0, non-finite
+        cg["pos"][rng.integers(0, h, k), rng.integers(0, w, k), 2] = z
+    cg["pos"][rng.integers(0, h, k), rng.integers(0, w, k), 0] = 1e30   # far off screen: X beyond any int
+    for a in (prev4, cur4):
+        a[rng.integers(0, h, k), rng.integers(0, w, k), rng.integers(0, 4, k)] = np.array([np.nan, np.inf, -np.inf, 0.0, -1.0], f32)[rng.integers(0, 5, k)]
+    return prev4, pg, view, cg, cur4
+
+
+@pytest.mark.parametrize("w,h", SHAPES)
+def test_buffers_equal_the_model_on_made_up_frames(w, h):
+    prev4, pg, view, cg, cur4 = synthetic(w, h, w * h, clean=True)
+    want = temporal.reproject(prev4, pg, view, cg)
+    assert (want[..., 3] > 0).all(), "every pixel of the clean frame has history"
+    same(engine.reproject_buffers(prev4, pg, view, cg, None, device=0), want, "REPROJECT, clean")
+    same(engine.reproject_buffers(prev4, pg, view, cg, cur4, device=0), temporal.merge(want, cg, cur4), "REPROJECT + MERGE, clean")
+    for seed in (1, 2):
+        prev4, pg, view, cg, cur4 = synthetic(w, h, 1000 * seed + w * h)
+        for p in (temporal.default_params(), temporal.params(normal_min=0.5, sigma_depth=0.005, albedo_floor=0.3, max_history=8.0)):
+            want = temporal.reproject(prev4, pg, view, cg, p)
+            same(engine.reproject_buffers(prev4, pg, view, cg, None, p, device=0), want, "REPROJECT")
+            same(engine.reproject_buffers(prev4, pg, view, cg, cur4, p, device=0), temporal.merge(want, cg, cur4), "REPROJECT + MERGE")
+    if w * h >= 64 * 48:   # the made-up frame does take the branches
+        took = want[..., 3] > 0
+        assert 0.2 < took.mean() < 0.95 and (want[..., 3] == 8.0).any() and (want[took][:, 3] < 8.0).any()
+
+
+@functools.lru_cache(maxsize=None)
+def real_pair(name, w, h):
+    """(prev4, prev guides, prev view, cur guides, cur4, model history) of a scene rendered at 4 spp under two cameras 2 degrees
+    apart; computed once and shared"""
+    make = {"feature": lambda: scenes.feature_scene(width=w, height=h, spp=4), "mesh578": lambda: scenes.mesh_scene(12, 12, w, h, 4, 4, seed=7)}[name]
+    s = make()
+    rc = RenderConfig.from_scene(s)
+    e = Engine.new(rc, device=0)
+    try:
+        e.render(rc)
+        g0, f0 = e.denoise_guides(), temporal.frame_records(e.read_accumulation())
+        v0 = engine.view_from_camera(s.uniforms)
+        moved = turned(s, 2.0)
+        e.update(RenderConfig(uniforms=Change.update(moved.uniforms)))
+        e.render_current()
+        g1, f1 = e.denoise_guides(), temporal.frame_records(e.read_accumulation())
+    finally:
+        e.close()
+    want = temporal.reproject(f0, g0, v0, g1)
+    for a in (g0, g1, f0, f1, want):
+        a.flags.writeable = False
+    return f0, g0, v0, g1, f1, want
+
+
+def turned(s, degrees):
+    """the scene with its camera turned about the y axis"""
+    t = _copy(s)
+    d = np.asarray(t.uniforms["camera"]["dir"][0], np.float64)
+    c, sn = np.cos(np.radians(degrees)), np.sin(np.radians(degrees))
+    t.uniforms["camera"]["dir"][0] = (c * d[0] + sn * d[2], d[1], -sn * d[0] + c * d[2])
+    return t
+
+
+@pytest.mark.parametrize("w,h", REAL_SHAPES)
+@pytest.mark.parametrize("name", ["feature", "mesh578"])
+@pytest.mark.parametrize("with_cur", [False, True], ids=["reproject", "merge"])
+def test_buffers_equal_the_model_on_rendered_frames(name, w, h, with_cur):
+    f0, g0, v0, g1, f1, want = real_pair(name, w, h)
+    # section 13's exception covers a NaN the model's own arithmetic generates: these inputs must produce none
+    assert np.isfinite(want).all() and np.isfinite(f0).all() and np.isfinite(f1).all()
+    merged = temporal.merge(want, g1, f1)
+    assert np.isfinite(merged).all()
+    if w * h >= 64 * 48:
+        assert (want[..., 3] > 0).mean() > 0.3, "two degrees apart most of the frame has history"
+        assert ((want[..., 3] == 0) & (g1["cls"] != 0)).any(), "... and some of it has none"
+    got = engine.reproject_buffers(f0, g0, v0, g1, f1 if with_cur else None, device=0)
+    same(got, merged if with_cur else want, name)
+
+
+EXACT = cases.exact_cases()
+
+
+@pytest.mark.parametrize("case", EXACT, ids=[c[0] for c in EXACT])
+def test_exact_cases_on_the_device(case):
+    _, prev, pg, view, cg, p, want = case
+    same(engine.reproject_buffers(prev, pg, view, cg, None, p, device=0), want)
+
+
+def test_rejections_and_merge_cases_on_the_device():
+    for name, prev, pg, view, cg, p, want in cases.rejection_cases():
+        got = engine.reproject_buffers(prev, pg, view, cg, None, p, device=0)
+        same(got, temporal.reproject(prev, pg, view, cg, p), name)
+        assert np.array_equal(bits(got[cases.PIXEL]), bits(want)), (name, got[cases.PIXEL], want)
+    # MERGE alone: a history that reprojects onto itself exactly (whole pixels, shift 0), then the cases' current records
+    hst, g, cur, want = (np.concatenate([a, np.zeros_like(a)[:, :6]], 1) for a in cases.merge_cases())   # 16 pixels: dyadic sx
+    n = hst.shape[1]
+    assert n == 16
+    view = cases.flat_view(n, 1)
+    fg = cases.flat_guides(view, n, 1)
+    fg["cls"] = np.where(g["cls"] == 0, abi.HIT_GROUND, g["cls"])
+    cg = fg.copy()
+    cg["cls"] = g["cls"]
+    prev = hst.copy()
+    prev[hst[..., 3] == 0] = (1, 1, 1, -1)   # "no history" as a record the reprojection rejects
+    p = temporal.params(max_history=64.0)
+    hist = temporal.reproject(prev, fg, view, cg, p)
+    live = (g["cls"] != 0) & (hst[..., 3] > 0)
+    assert np.array_equal(bits(hist[live]), bits(hst[live])) and not hist[~live].any()
+    same(engine.reproject_buffers(prev, fg, view, cg, cur, p, device=0), want, "MERGE")
+    same(temporal.merge(hist, cg, cur), want, "the model's MERGE")
+
+
+def test_buffers_refuse_bad_arguments():
+    prev4, pg, view, cg, cur4 = synthetic(8, 4, 5)
+    for kw in (dict(sigma_depth=0.0), dict(normal_min=2.0), dict(albedo_floor=-1.0), dict(max_history=0.0), dict(flags=4)):
+        with pytest.raises(RenderError) as ei:
+            engine.reproject_buffers(prev4, pg, view, cg, cur4, temporal.params(**kw), device=0)
+        assert ei.value.code == INVALID_OPTIONS, kw
+    bad = view.copy()
+    bad["sx"] = np.nan
+    with pytest.raises(RenderError) as ei:
+        engine.reproject_buffers(prev4, pg, bad, cg, cur4, device=0)
+    assert ei.value.code == INVALID_OPTIONS
+
+
+# ---- 2. rb_reproject_device on torch tensors
+def test_device_form_gives_the_same_bits_and_refuses_bad_ranges():
+    import torch
+    w, h = 67, 5
+    f0, g0, v0, g1, f1, want = real_pair("feature", w, h)
+    n = w * h
+    s = scenes.feature_scene(width=16, height=8, spp=1)
+    rc = RenderConfig.from_scene(s)
+    cold = Engine.new(rc, device=0)
+    e = Engine.new(rc, device=0)   # (the engine lends its device and stream: its own scene and size do not matter)
+    multi = Engine.new(rc, devices=[0, 0], gather_peer_copy=True)
+    try:
+        dev = lambda a, row: torch.from_numpy(np.ascontiguousarray(a).view(f32).reshape(-1, row).copy()).to("cuda:0")   # noqa: E731
+        d_f0, d_g0, d_g1, d_f1 = dev(f0, 4), dev(g0, 12), dev(g1, 12), dev(f1, 4)
+        p = np.ascontiguousarray(temporal.default_params()).reshape(1)
+        v = np.ascontiguousarray(v0).reshape(1)
+        out = torch.full((n, 4), 7.0, device="cuda:0")
+        args = (p.ctypes.data, w, h, v.ctypes.data, d_f0.data_ptr(), d_g0.data_ptr(), d_g1.data_ptr(), d_f1.data_ptr(), out.data_ptr())
+        assert cold._lib.rb_reproject_device(cold._h, *args) == NOT_INITIALIZED
+        e.update(rc)
+        multi.update(rc)
+        # through the binding: REPROJECT alone into a new tensor, REPROJECT + MERGE into `out`
+        got = e.reproject(d_f0, d_g0, v0, d_g1, size=(w, h))
+        assert isinstance(got, torch.Tensor) and tuple(got.shape) == (n, 4) and e.last_query_kernel_name() == "k_reproject"
+        same(got.cpu().numpy().reshape(h, w, 4), want, "device REPROJECT")
+        assert e.reproject(d_f0, d_g0, v0, d_g1, d_f1, out=out, size=(w, h)) is out
+        merged = temporal.merge(want, g1, f1)
+        same(out.cpu().numpy().reshape(h, w, 4), merged, "device MERGE")
+        assert e.last_query_ms() > 0
+        # host arrays through the same method go to the engine-less form on the engine's device
+        same(e.reproject(f0, g0, v0, g1, f1), merged, "host form")
+        # a multi-device handle answers on devices[0]
+        out.fill_(7.0)
+        assert multi._lib.rb_reproject_device(multi._h, *args) == 0 and multi._lib.rb_sync(multi._h) == 0
+        same(out.cpu().numpy().reshape(h, w, 4), merged, "multi-device handle")
+        # every range refusal leaves the output untouched
+        out.fill_(7.0)
+        lib, hd = e._lib, e._h
+        host = np.zeros((n, 12), f32)
+        for i, base in ((4, d_f0), (5, d_g0), (6, d_g1), (7, d_f1), (8, out)):
+            for bad in (host.ctypes.data, base.data_ptr() + 4):   # a host pointer, a misaligned one
+                a = list(args)
+                a[i] = bad
+                assert lib.rb_reproject_device(hd, *a) == INVALID_OPTIONS, (i, bad)
+        a = list(args)
+        a[1], a[2] = 1 << 13, 1 << 13   # allocations that end before 2^26 records
+        assert lib.rb_reproject_device(hd, *a) == INVALID_OPTIONS
+        for i in (0, 3, 4, 5, 6, 8):
+            a = list(args)
+            a[i] = None
+            assert lib.rb_reproject_device(hd, *a) == NULL_ARGUMENT, i
+        badp = np.ascontiguousarray(temporal.params(max_history=0.0)).reshape(1)
+        assert lib.rb_reproject_device(hd, badp.ctypes.data, *args[1:]) == INVALID_OPTIONS
+        assert lib.rb_sync(hd) == 0 and (out == 7.0).all().item()
+        with pytest.raises(ValueError):
+            e.reproject(d_f0, d_g0, v0, d_g1)   # tensors carry no frame size
+        with pytest.raises(ValueError):
+            e.reproject(d_f0, d_g0[:-1], v0, d_g1, size=(w, h))
+    finally:
+        for x in (cold, e, multi):
+            x.close()
+
+
+# ---- 3. the engine form
+def passes(e, first, n):
+    e.dispatch(first, n)
+    e.sync()
+
+
+def test_engine_form_follows_the_model_through_a_camera_move():
+    import torch
+    s = scenes.feature_scene(width=64, height=48, spp=4)
+    rc = RenderConfig.from_scene(s)
+    rp, dp = temporal.default_params(), denoise.default_params()
+    e = Engine.new(rc, device=0)
+    try:
+        e.render(rc)
+        with pytest.raises(RenderError) as ei:
+            e.history()
+        assert ei.value.code == NOT_INITIALIZED
+        # no history: rb_denoise's bits, and F is the mean radiance with acc.w
+        plain, plain_img = e.denoise(linear=True), e.denoise()
+        first = e.denoise_history(linear=True)
+        assert np.array_equal(bits(first), bits(plain)) and np.array_equal(e.denoise_history(), plain_img)
+        acc0, g0 = e.read_accumulation(), e.denoise_guides()
+        H0 = e.history()
+        same(H0, temporal.frame_records(acc0), "F without history")
+        assert (H0[..., 3] == 4).all()
+        v0 = engine.view_from_camera(s.uniforms)
+        # the camera moves; one pass; the call
+        moved = turned(s, 2.0)
+        e.update(RenderConfig(uniforms=Change.update(moved.uniforms)))
+        e.clear()
+        passes(e, 0, 1)
+        st = e.stats()
+        out1 = e.denoise_history(linear=True)
+        assert e.stats() == st, "rb_get_stats moved"
+        g1, acc1 = e.denoise_guides(), e.read_accumulation()
+        base = temporal.reproject(H0, g0, v0, g1, rp)
+        assert (base[..., 3] > 0).mean() > 0.3 and np.isfinite(base).all()
+        F1 = temporal.merge(base, g1, temporal.frame_records(acc1))
+        same(e.history(), F1, "F after the move")
+        assert (F1[..., 3] == 5).any() and (F1[..., 3] == 1).any()
+        same(out1, denoise.filter(F1, g1, dp), "the filtered frame")
+        assert e.last_reproject_ms() > 0
+        # the device-output form, and the RGBA8 frame: the same bits
+        d_lin = torch.empty((48, 64, 4), dtype=torch.float32, device="cuda:0")
+        d_img = torch.empty((48, 64, 4), dtype=torch.uint8, device="cuda:0")
+        assert e.denoise_history(linear=True, out=d_lin) is d_lin and e.denoise_history(out=d_img) is d_img
+        assert np.array_equal(bits(d_lin.cpu().numpy()), bits(out1))
+        assert np.array_equal(d_img.cpu().numpy(), denoise.filter(F1, g1, dp, rgba=True)[1]) and np.array_equal(e.denoise_history(), d_img.cpu().numpy())
+        same(e.history(), F1, "repeated calls do not count their own samples")
+        # one more pass under the same camera: the same base, the larger accumulation
+        passes(e, 1, 1)
+        out2 = e.denoise_history(linear=True)
+        acc2 = e.read_accumulation()
+        assert (acc2[..., 3] == 2).all()
+        F2 = temporal.merge(base, g1, temporal.frame_records(acc2))
+        same(e.history(), F2, "no double counting")
+        same(out2, denoise.filter(F2, g1, dp), "the filtered frame after the second pass")
+        assert F2[..., 3].max() == 6
+        # a query's side effects: none
+        before = e.stats()
+        e.denoise_history()
+        assert e.stats() == before and np.array_equal(bits(e.read_accumulation()), bits(acc2))
+        # a refused call leaves H as it was
+        for bad in (dict(rparams=temporal.params(normal_min=3.0)), dict(dparams=denoise.params(iterations=9)), dict(out=np.empty((2, 2, 4), np.uint8))):
+            with pytest.raises((RenderError, ValueError)):
+                e.denoise_history(**bad)
+        lib, hd = e._lib, e._h
+        rp1, dp1 = np.ascontiguousarray(rp).reshape(1), np.ascontiguousarray(dp).reshape(1)
+        host = np.empty((48, 64, 4), np.uint8)
+        assert lib.rb_denoise_history(hd, rp1.ctypes.data, dp1.ctypes.data, None, None) == NULL_ARGUMENT
+        assert lib.rb_denoise_history(hd, None, dp1.ctypes.data, host.ctypes.data, None) == NULL_ARGUMENT
+        assert lib.rb_denoise_history_device(hd, rp1.ctypes.data, dp1.ctypes.data, host.ctypes.data, None) == INVALID_OPTIONS
+        same(e.history(), F2, "H after refused calls")
+        # rb_history_reset: no history, rb_denoise's bits again
+        e.history_reset()
+        with pytest.raises(RenderError):
+            e.history()
+        assert np.array_equal(bits(e.denoise_history(linear=True)), bits(e.denoise(linear=True)))
+        same(e.history(), temporal.frame_records(acc2), "F after the reset")
+        # an update that changes the size: no history
+        small = turned(scenes.feature_scene(width=40, height=24, spp=1), 2.0)
+        e.update(RenderConfig(uniforms=Change.update(small.uniforms)))
+        with pytest.raises(RenderError):
+            e.history()
+        e.clear()
+        passes(e, 0, 1)
+        assert np.array_equal(bits(e.denoise_history(linear=True)), bits(e.denoise(linear=True)))
+        same(e.history(), temporal.frame_records(e.read_accumulation()), "F at the new size")
+    finally:
+        e.close()
+
+
+def test_a_call_between_iterator_frames_keeps_the_frames():
+    s = scenes.feature_scene(width=48, height=32, spp=4)
+    rc = RenderConfig.from_scene(s)
+
+    def frames(ask):
+        e = Engine.new(rc, device=0)
+        it = e.frame_iterator(rc)
+        out = []
+        while it.has_next():
+            out.append(it.next().pixels.copy())
+            if ask:
+                e.denoise_history(linear=True)
+                same(e.history(), temporal.frame_records(e.read_accumulation()), "F between frames")
+        st = e.stats()
+        e.close()
+        return out, st
+    plain, st0 = frames(False)
+    asked, st1 = frames(True)
+    assert len(plain) == len(asked) == 4
+    for a, b in zip(plain, asked):
+        assert np.array_equal(a, b)
+    for k in ("segments", "paths", "launches"):
+        assert st0[k] == st1[k], k
+
+
+def test_refusals_and_the_golden_frame():
+    s = scenes.feature_scene(width=32, height=24, spp=1)
+    rc = RenderConfig.from_scene(s)
+    sharded = Engine.new(rc, device=0, shard_rank=0, shard_count=2)
+    multi = Engine.new(rc, devices=[0, 0], gather_peer_copy=True)
+    cold = Engine.new(rc, device=0)
+    e = Engine.new(rc, device=0)
+    try:
+        sharded.render(rc)
+        multi.render(rc)
+        for x in (sharded, multi):
+            with pytest.raises(RenderError) as ei:
+                x.denoise_history()
+            assert ei.value.code == INVALID_OPTIONS
+        rp, dp = np.ascontiguousarray(temporal.default_params()).reshape(1), np.ascontiguousarray(denoise.default_params()).reshape(1)
+        buf = np.empty((24, 32, 4), np.uint8)
+        assert cold._lib.rb_denoise_history(cold._h, rp.ctypes.data, dp.ctypes.data, buf.ctypes.data, None) == NOT_INITIALIZED
+        frame = e.render(rc).pixels.copy()
+        e.denoise_history()
+        F = e.history()
+        for kw in (dict(sigma_depth=np.nan), dict(normal_min=-2.0), dict(albedo_floor=0.0), dict(max_history=0.5), dict(_reserved=(1, 0, 0))):
+            with pytest.raises(RenderError) as ei:
+                e.denoise_history(temporal.params(**kw))
+            assert ei.value.code == INVALID_OPTIONS, kw
+        same(e.history(), F, "H after refused calls")
+        assert np.array_equal(e.read_rgba(), frame) and np.array_equal(e.render_current().pixels, frame), "the golden frame"
+    finally:
+        for x in (sharded, multi, cold, e):
+            x.close()
