@@ -1,5 +1,6 @@
 // rb_engine.hpp -- the engine's state, shared by the runtime (rb_runtime.cpp), the acceleration structures it builds
-// (rb_accel.cpp) and the queries over them (rb_queries.cpp).  Host code only: not part of the ABI, and no .hip file includes it.
+// (rb_accel.cpp), the queries over them (rb_queries.cpp) and the frame's post-processing (rb_frame.cpp).  Host code only: not
+// part of the ABI, and no .hip file includes it.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -12,6 +13,7 @@
 #include "rb_color_plan.hpp"
 #include "rb_internal.hpp"
 #include "rb_rccl.hpp"
+#include "rb_stage_timer.hpp"
 #include "rb_update_plan.hpp"
 
 namespace rb {
@@ -195,22 +197,17 @@ struct rb_engine {
     rb::DevBuf<rb_surfel> lm_surfels;
     rb::DevBuf<rb_radiance> lm_sums;
     rb::DevBuf<float> lm_rgba[2];
-    hipEvent_t ev_lm[4] = {nullptr, nullptr, nullptr, nullptr};   // surfel stage begin / end, resolve begin / end
-    bool lm_timed[2] = {false, false};   // the most recent lightmap call recorded the pair (rb_last_lightmap_ms)
-    hipEvent_t ev_q[2] = {nullptr, nullptr};
-    std::vector<hipEvent_t> ev_cam;  // rb_trace_camera*, rb_*_hemisphere*: a pair around every piece's generator (rb_last_camera_rays_ms)
-    size_t cam_pieces = 0;           // pairs the most recent query recorded; 0 from every query's prologue on
-    std::vector<hipEvent_t> ev_sh;   // rb_bake_probes*: a pair around every piece's projection (rb_last_probe_project_ms)
-    size_t sh_pieces = 0;
-    std::vector<hipEvent_t> ev_depth;   // rb_bake_probe_depth*: a pair around every piece's projection (rb_last_probe_depth_project_ms)
-    size_t depth_pieces = 0;
+    // the stage times of the most recent query: reset by every query's prologue, the lightmap's two by
+    // a lightmap call alone
+    rb::StageTimer t_query;          // a query's kernels (rb_last_query_ms)
+    rb::StageTimer t_generator;      // a pair round every piece's generator (rb_last_camera_rays_ms)
+    rb::StageTimer t_sh, t_depth;    // ... round every piece's projection (rb_last_probe_project_ms, rb_last_probe_depth_project_ms)
+    rb::StageTimer t_lm_surfels, t_lm_resolve;   // the lightmap's first and last stage (rb_last_lightmap_ms)
     const char* last_query_kernel_name = "";
-    float last_query_ms = 0.0f;
-    bool query_ms_pending = false;   // the device forms return without waiting: rb_last_query_ms reads ev_q when asked
 
     // the denoiser (rb_denoise*): the guide planes of the scene and camera of the last accepted update (made
     // by the first denoise after it), the two colour buffers the iterations ping-pong between, staging for host outputs, and
-    // events of its own: like a query it moves neither the work counters nor the timing of a launch group
+    // timers of its own: like a query it moves neither the work counters nor the timing of a launch group
     // (two sets of planes: the history of section 22 keeps the set its frame was made with while the next update's guides are
     // built into the other one; dn_set is the current one)
     rb::DevBuf<float> dn_nt[2], dn_pc[2], dn_al[2];
@@ -218,9 +215,7 @@ struct rb_engine {
     bool dn_guides_valid = false;
     rb::DevBuf<float> dn_r[2], dn_linear;
     rb::DevBuf<uint32_t> dn_rgba;
-    hipEvent_t ev_dn[4] = {nullptr, nullptr, nullptr, nullptr};   // guide build begin / end, filter begin / end
-    float last_denoise_ms = 0.0f, last_guide_ms = 0.0f;
-    bool denoise_ms_pending = false;   // rb_denoise_device returns without waiting: rb_last_denoise_ms reads the events when asked
+    rb::StageTimer t_guides, t_filter;   // the guide build and the filter of the most recent denoise (rb_last_denoise_ms)
 
     // temporal reprojection (rb_denoise_history): the history H -- the frame records F of the most recent
     // call, the set of guide planes they belong to (hist_set), their view and size --, and the base B: H carried into the current
@@ -231,9 +226,7 @@ struct rb_engine {
     rb_view hist_view{};
     uint32_t hist_w = 0, hist_h = 0;
     bool hist_valid = false, hist_base_valid = false;
-    hipEvent_t ev_rp[2] = {nullptr, nullptr};   // REPROJECT (if made) and MERGE begin / end
-    float last_reproject_ms = 0.0f;
-    bool reproject_ms_pending = false;
+    rb::StageTimer t_history;   // REPROJECT (if made) and MERGE of the most recent rb_denoise_history (rb_last_reproject_ms)
 
     rb_stats stats{};
     float last_dispatch_ms = 0.0f;
@@ -279,7 +272,7 @@ inline bool is_group(const rb_engine* e) { return !e->parts.empty(); }
 inline void set_device(const rb_engine* e) { (void)hipSetDevice(e->device); }
 inline uint32_t kernel_of(const rb_options& opt) { return opt.kernel ? opt.kernel : RB_KERNEL_STREAM; }
 
-// ---- rb_runtime.cpp, for rb_queries.cpp (hidden: the library's dynamic symbols stay what they were)
+// ---- rb_runtime.cpp, for rb_queries.cpp and rb_frame.cpp (hidden: the library's dynamic symbols stay what they were)
 #define RB_HIDDEN __attribute__((visibility("hidden")))
 RB_HIDDEN int require_ready(rb_engine* e);      // the engine holds a scene that a launch may read, or the refusal
 RB_HIDDEN int ensure_prepared(rb_engine* e);    // the prepared triangles and the mesh walk's tree of the current scene

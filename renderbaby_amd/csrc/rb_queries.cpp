@@ -1,78 +1,49 @@
 // rb_queries.cpp -- what an engine answers besides frames: closest-hit queries (rb_cast_rays / rb_render_hits / rb_pick), any-hit
 // occlusion, path-traced radiance along given rays, camera and hemisphere rays, lightmap texels and irradiance probes made on the
 // device, light points from a baked probe grid with or without the probes' depth moments, direct light by shadow rays to the
-// scene's emitters, the denoiser over the first-hit buffers and the history it can be given across a camera move, with their
-// device forms, their getters and their C entry points (rb_abi.h; DESIGN.md sections 11-22).
+// scene's emitters, with their device forms, their getters and their C entry points (rb_abi.h; DESIGN.md sections 11-22; the
+// denoiser and the frame's history: rb_frame.cpp).
 // Every sequence is here once: one prologue (query_prologue), one timed
 // launch (timed_launch), one runner per form -- run_pieces for the host forms, device_query_locked for the device forms --, over
 // them one runner for the families of "n items, `samples` each" in both forms (run_family: radiance, camera, hemisphere,
 // probes), one shape for the engine entry points (engine_entry) and one scope for the engine-less forms (DeviceScope).  The
-// engine's state is rb_engine.hpp's; the launchers are rb_internal.hpp's.
+// engine's state is rb_engine.hpp's; the launchers are rb_internal.hpp's; what rb_frame.cpp needs too is rb_queries.hpp's.
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <initializer_list>
 
-#include "rb_engine.hpp"
-#include "rb_host_cam.hpp"
+#include "rb_queries.hpp"
 
 namespace {
 
-using rb::copy_error, rb::ensure_prepared, rb::make_params, rb::require_ready;
+using rb::copy_error, rb::device_range, rb::DeviceScope, rb::ensure_prepared, rb::frame_piece_rows, rb::page_locked, rb::query_copy_out,
+    rb::reproject_check, rb::require_ready, rb::scene_params, rb::stage_ms;
 
 // ------------------------------------------------------------------ closest-hit queries ----
 // (rb_abi.h)  A query reads the scene and writes its own scratch: it is queued on the engine's stream
 // behind whatever runs there -- a pass the iterator has started ahead included, which stays valid -- and uses events of its
 // own, so neither the work counters nor the timing of a launch group move.
-bool page_locked(const void* p) {
-    hipPointerAttribute_t attr{};
-    if (p && hipPointerGetAttributes(&attr, p) == hipSuccess && attr.type == hipMemoryTypeHost) return true;
-    (void)hipGetLastError();   // an unregistered pointer makes the query fail: that is the ordinary case
-    return false;
-}
 
-// device -> caller memory behind the stream's work: a DMA into page-locked memory, a blocking copy otherwise
-int query_copy_out(rb_engine* e, void* dst, const void* src, size_t bytes, bool pinned) {
-    if (pinned) {
-        HIP_TRY(e, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, e->stream));
-        return RB_OK;
-    }
-    HIP_TRY(e, hipStreamSynchronize(e->stream));
-    HIP_TRY(e, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
-    return RB_OK;
-}
-
-// the scene as a kernel of this module sees it, or the refusal of a traversal that its LDS stack column cannot hold
-int scene_params(rb_engine* e, rb::KParams* p) {
-    *p = make_params(e, 0, 0, e->cur, e->cur);
-    if (!e->stack_depth_covers) return rb::fail(e, RB_ERR_DEVICE, "internal: a traversal is deeper than its LDS stack column (%u entries)", p->stack_depth);
-    return RB_OK;
-}
-
-// what every query begins with; the kernel times of the query before -- rb_last_query_ms and the event pairs of its generator
-// and projection stages -- are gone from here on, however far this one gets.  p == nullptr: a query that reads no scene
+// what every query begins with; the kernel times of the query before -- rb_last_query_ms and those of its generator and
+// projection stages -- are gone from here on, however far this one gets.  p == nullptr: a query that reads no scene
 // (section 19) -- nothing is prepared for it.
 int query_prologue(rb_engine* e, rb::KParams* p) {
-    e->last_query_ms = 0.0f;
-    e->cam_pieces = e->sh_pieces = e->depth_pieces = 0;
+    for (rb::StageTimer* t : {&e->t_query, &e->t_generator, &e->t_sh, &e->t_depth}) t->reset();
     int rc = require_ready(e);
     if (!rc && p) rc = ensure_prepared(e);
     if (!rc && p) rc = scene_params(e, p);
-    if (rc) return rc;
-    for (hipEvent_t& x : e->ev_q)
-        if (!x) HIP_TRY(e, hipEventCreate(&x));
-    e->query_ms_pending = false;
-    return RB_OK;
+    return rc;
 }
 
-// what both runners time: `launch(li)` queues a query's kernels between its two events and returns a HIP status
+// what both runners time: `launch(li)` queues a query's kernels as one pair of e->t_query and returns a HIP status
 template <class Launch>
 int timed_launch(rb_engine* e, const char* kind, Launch&& launch) {
     rb::LaunchInfo li{};
-    HIP_TRY(e, hipEventRecord(e->ev_q[0], e->stream));
+    HIP_TRY(e, e->t_query.begin(e->stream));
     const int st = launch(&li);
     if (st) return rb::fail(e, RB_ERR_DEVICE, "%s kernel launch failed: %s", kind, hipGetErrorString(static_cast<hipError_t>(st)));
-    HIP_TRY(e, hipEventRecord(e->ev_q[1], e->stream));
+    HIP_TRY(e, e->t_query.end(e->stream));
     if (li.kernel_name) e->last_query_kernel_name = li.kernel_name;
     return RB_OK;
 }
@@ -101,8 +72,7 @@ int run_pieces(rb_engine* e, const char* kind, size_t piece, size_t n, std::init
         if (rc) return rc;
         HIP_TRY(e, hipStreamSynchronize(e->stream));   // the scratch is the next piece's
         float ms = 0.0f;
-        HIP_TRY(e, hipEventElapsedTime(&ms, e->ev_q[0], e->ev_q[1]));
-        e->last_query_ms += ms;
+        HIP_TRY(e, e->t_query.read(&ms));   // folded here: the next piece records the same pair again
     }
     return RB_OK;
 }
@@ -113,17 +83,14 @@ int device_query_locked(rb_engine* e, Launch&& launch) {
     rb::KParams p{};
     int rc = query_prologue(e, &p);
     if (!rc) rc = timed_launch(e, "query", [&](rb::LaunchInfo* li) { return launch(p, li); });
-    if (!rc) e->query_ms_pending = true;   // rb_last_query_ms reads the events when it is asked
-    return rc;
+    return rc;   // rb_last_query_ms reads the pair when it is asked
 }
 
 // ... of a query that reads no scene: the engine lends its device and its stream; `launch(li)` returns a HIP status
 template <class Launch>
 int device_stream_locked(rb_engine* e, Launch&& launch) {
-    int rc = query_prologue(e, nullptr);
-    if (!rc) rc = timed_launch(e, "query", launch);
-    if (!rc) e->query_ms_pending = true;
-    return rc;
+    const int rc = query_prologue(e, nullptr);
+    return rc ? rc : timed_launch(e, "query", launch);
 }
 
 int cast_rays_locked(rb_engine* e, const rb_ray* rays, size_t n, rb_hit* hits_out, rb_surface* surf_out) {
@@ -145,9 +112,6 @@ int cast_rays_locked(rb_engine* e, const rb_ray* rays, size_t n, rb_hit* hits_ou
                           return rb::launch_query(p, q, e->stream, li);
                       });
 }
-
-// rows of a frame of width w in one piece: whole 8-row tiles, about rb::kQueryPiece records, at least one band of tiles
-uint32_t frame_piece_rows(uint32_t w) { return w == 0 ? 8u : std::max<uint32_t>(8u, (rb::kQueryPiece / w) & ~7u); }
 
 // the pixel centres of rows [0, rows) x the whole width (global = image rows, else this shard's local rows), or of one pixel:
 // rows * w items, of which piece `done` begins at row done / w
@@ -192,25 +156,6 @@ int occluded_locked(rb_engine* e, const rb_ray* rays, const float* tmax, size_t 
                           a.mask = mask;
                           return rb::launch_occluded(p, a, e->stream, li);
                       });
-}
-
-// `bytes` of device memory of the engine's device at p, aligned to `align`?
-int device_range(rb_engine* e, const void* p, size_t bytes, size_t align, const char* what) {
-    hipPointerAttribute_t attr{};
-    const hipError_t st = hipPointerGetAttributes(&attr, p);
-    if (st != hipSuccess) (void)hipGetLastError();   // a pointer the runtime does not know: pageable host memory
-    if (st != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != e->device)
-        return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s is not device memory of device %d", what, e->device);
-    if (reinterpret_cast<uintptr_t>(p) % align != 0u) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s is not %zu-byte aligned", what, align);
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) {
-        (void)hipGetLastError();
-        return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: its allocation is unknown to the runtime", what);
-    }
-    const size_t off = static_cast<size_t>(static_cast<const char*>(p) - static_cast<const char*>(base));
-    if (off > size || bytes > size - off) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: its allocation ends before %zu bytes", what, bytes);
-    return RB_OK;
 }
 
 int occluded_device_locked(rb_engine* e, const rb_ray* d_rays, const float* d_tmax, size_t n, uint32_t mask, uint8_t* d_out) {
@@ -363,42 +308,6 @@ int trace_rays_locked(rb_engine* e, bool device, const rb_ray* rays, const uint3
 }
 
 // ---- camera rays made on the device (rb_abi.h)
-// `stage()` between the next event pair of `ev`, of which the call has recorded `pieces` so far: it queues a piece's stage and
-// returns a HIP status
-template <class Stage>
-int timed_pair(rb_engine* e, std::vector<hipEvent_t>& ev_all, size_t& pieces, Stage&& stage) {
-    while (ev_all.size() < 2 * (pieces + 1)) {
-        hipEvent_t x = nullptr;
-        if (const hipError_t st = hipEventCreate(&x)) return static_cast<int>(st);
-        ev_all.push_back(x);
-    }
-    hipEvent_t* const ev = &ev_all[2 * pieces];
-    if (const hipError_t st = hipEventRecord(ev[0], e->stream)) return static_cast<int>(st);
-    if (const int st = stage()) return st;
-    if (const hipError_t st = hipEventRecord(ev[1], e->stream)) return static_cast<int>(st);
-    pieces++;
-    return 0;
-}
-
-// a piece's generator between an event pair of its own (rb_last_camera_rays_ms): `gen()` queues it and returns a HIP status
-template <class Gen>
-int timed_generator(rb_engine* e, Gen&& gen) {
-    return timed_pair(e, e->ev_cam, e->cam_pieces, gen);
-}
-
-// the kernel ms between the `pieces` event pairs of `ev`; waits for the last of them
-int pairs_ms(rb_engine* e, const std::vector<hipEvent_t>& ev, size_t pieces, float* ms) {
-    *ms = 0.0f;
-    if (pieces == 0) return RB_OK;
-    HIP_TRY(e, hipEventSynchronize(ev[2 * pieces - 1]));
-    for (size_t i = 0; i < pieces; i++) {
-        float piece_ms = 0.0f;
-        HIP_TRY(e, hipEventElapsedTime(&piece_ms, ev[2 * i], ev[2 * i + 1]));
-        *ms += piece_ms;
-    }
-    return RB_OK;
-}
-
 // one piece, queued: the generator into the record scratch, the k_cam kernel of the scene's walk over it, the sum into `out`
 int camera_piece(rb_engine* e, const rb::KParams& p, const rb_camera_ex& cam, uint64_t first_pixel, size_t done, size_t m,
                  uint32_t first_sample, uint32_t samples, rb_radiance* out, rb::LaunchInfo* li) {
@@ -409,7 +318,7 @@ int camera_piece(rb_engine* e, const rb::KParams& p, const rb_camera_ex& cam, ui
     g.n = static_cast<uint32_t>(m);
     g.first_sample = first_sample;
     g.samples = samples;
-    if (const int st = timed_generator(e, [&] { return rb::launch_camera_rays(g, e->stream); })) return st;
+    if (const int st = e->t_generator.timed(e->stream, [&] { return rb::launch_camera_rays(g, e->stream); })) return st;
     return rb::launch_radiance(p, trace_args(e, e->q_rays.ptr, nullptr, out, done, m, first_sample, samples), e->stream, li, true);
 }
 
@@ -465,7 +374,7 @@ int hemi_piece(rb_engine* e, const rb::KParams& p, const HemiCall& c, const rb_s
         g.tmax = e->q_tmax.ptr;
         g.linear = 1u;
     }
-    if (const int st = timed_generator(e, [&] { return rb::launch_hemisphere_rays(g, e->stream); })) return st;
+    if (const int st = e->t_generator.timed(e->stream, [&] { return rb::launch_hemisphere_rays(g, e->stream); })) return st;
     if (!c.openness)
         return rb::launch_radiance(p, trace_args(e, e->q_rays.ptr, nullptr, static_cast<rb_radiance*>(out), done, m, c.first_sample, c.samples),
                                    e->stream, li, true);
@@ -543,15 +452,15 @@ int scene_emitters_locked(rb_engine* e, bool device, rb_emitter* out, size_t cap
     rb::KParams p{};
     if (const int rc = query_prologue(e, &p)) return rc;
     bool built = false;
-    HIP_TRY(e, hipEventRecord(e->ev_q[0], e->stream));
+    HIP_TRY(e, e->t_query.begin(e->stream));
     if (const int rc = ensure_emitters(e, p, &built)) return rc;
-    HIP_TRY(e, hipEventRecord(e->ev_q[1], e->stream));
+    HIP_TRY(e, e->t_query.end(e->stream));
+    if (!built) e->t_query.reset();   // the time is the build's: 0 when the table stood
     e->last_query_kernel_name = "k_emit_scatter";
     const size_t m = std::min<size_t>(e->emit_n, capacity);
     if (device) {
         if (m) HIP_TRY(e, hipMemcpyAsync(out, e->emit_table.ptr, m * sizeof(rb_emitter), hipMemcpyDeviceToDevice, e->stream));
         HIP_TRY(e, hipMemcpyAsync(d_count, e->emit_count.ptr, sizeof(uint32_t), hipMemcpyDeviceToDevice, e->stream));
-        e->query_ms_pending = built;
         return RB_OK;
     }
     if (m) {
@@ -559,7 +468,6 @@ int scene_emitters_locked(rb_engine* e, bool device, rb_emitter* out, size_t cap
     }
     *count = e->emit_n;
     HIP_TRY(e, hipStreamSynchronize(e->stream));
-    if (built) HIP_TRY(e, hipEventElapsedTime(&e->last_query_ms, e->ev_q[0], e->ev_q[1]));
     return RB_OK;
 }
 
@@ -613,7 +521,7 @@ int direct_piece(rb_engine* e, const rb::KParams& p, const DirectCall& c, const 
                  rb_radiance* out, rb::LaunchInfo* li) {
     rb::LightGenArgs g = light_gen_args(c, surfels, ids, e->q_rays.ptr, e->q_tmax.ptr, e->rad_colors.ptr, done, m);
     g.linear = direct_linear(m) ? 1u : 0u;
-    if (const int st = timed_generator(e, [&] { return rb::launch_light_rays(g, e->stream); })) return st;
+    if (const int st = e->t_generator.timed(e->stream, [&] { return rb::launch_light_rays(g, e->stream); })) return st;
     rb::OcclArgs a{};
     a.q.rays = e->q_rays.ptr;
     a.q.n = static_cast<uint32_t>(direct_items(m, c.samples));
@@ -685,10 +593,10 @@ int probe_scratch(rb_engine* e, size_t piece, uint32_t samples) {
 int probe_piece(rb_engine* e, const rb::KParams& p, const rb_probe* probes, const uint32_t* ids, size_t done, size_t m,
                 uint32_t first_sample, uint32_t samples, rb_sh9* out, rb::LaunchInfo* li) {
     const rb::ProbeGenArgs g = probe_gen_args(probes, ids, e->q_rays.ptr, done, m, first_sample, samples);
-    if (const int st = timed_generator(e, [&] { return rb::launch_probe_rays(g, e->stream); })) return st;
+    if (const int st = e->t_generator.timed(e->stream, [&] { return rb::launch_probe_rays(g, e->stream); })) return st;
     if (const int st = rb::launch_radiance(p, trace_args(e, e->q_rays.ptr, nullptr, e->rad_out.ptr, done, m, first_sample, samples), e->stream, li, true))
         return st;
-    return timed_pair(e, e->ev_sh, e->sh_pieces, [&] {
+    return e->t_sh.timed(e->stream, [&] {
         return rb::launch_sh_project(e->rad_colors.ptr, e->q_rays.ptr, static_cast<uint32_t>(m), samples, out, 0u, e->stream);
     });
 }
@@ -711,13 +619,13 @@ int depth_piece(rb_engine* e, const rb::KParams& p, const rb_probe* probes, cons
                 uint32_t samples, float max_distance, rb_probe_depth* out, rb::LaunchInfo* li) {
     rb::ProbeGenArgs g = probe_gen_args(probes, ids, e->q_rays.ptr, done, m, first_sample, samples);
     g.linear = 1u;
-    if (const int st = timed_generator(e, [&] { return rb::launch_probe_rays(g, e->stream); })) return st;
+    if (const int st = e->t_generator.timed(e->stream, [&] { return rb::launch_probe_rays(g, e->stream); })) return st;
     rb::QueryArgs q{};
     q.rays = e->q_rays.ptr;
     q.n = static_cast<uint32_t>(m * samples);
     q.hits = e->q_hits.ptr;
     if (const int st = rb::launch_query(p, q, e->stream, li)) return st;
-    return timed_pair(e, e->ev_depth, e->depth_pieces, [&] {
+    return e->t_depth.timed(e->stream, [&] {
         return rb::launch_depth_project(e->q_rays.ptr, e->q_hits.ptr, static_cast<uint32_t>(m), samples, max_distance, out, 0u, e->stream);
     });
 }
@@ -951,232 +859,7 @@ int light_visible_device_locked(rb_engine* e, const rb_probe_grid& g, const rb_s
     });
 }
 
-// ---- the denoiser (rb_abi.h).  Like a query it is queued on the engine's stream behind whatever runs
-// there, reads the scene and the committed accumulation, and writes buffers of its own.
-rb::GuidePlanes guide_planes(rb_engine* e, int set) { return rb::GuidePlanes{e->dn_nt[set].ptr, e->dn_pc[set].ptr, e->dn_al[set].ptr}; }
-rb::GuidePlanes guide_planes(rb_engine* e) { return guide_planes(e, e->dn_set); }
-
-int denoise_ready(rb_engine* e) {
-    if (rb::is_group(e)) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "the denoiser does not take a multi-device handle: a tap would cross a stripe boundary");
-    rb::set_device(e);
-    if (e->opt.shard_count > 1) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "the denoiser does not take a sharded engine: a tap would cross a stripe boundary");
-    const int rc = require_ready(e);
-    if (rc) return rc;
-    for (hipEvent_t& x : e->ev_dn)
-        if (!x) HIP_TRY(e, hipEventCreate(&x));
-    return RB_OK;
-}
-
-// the guide planes of the current scene: the pixel-centre rays through the query kernels straight into device memory, one pack
-int ensure_guides(rb_engine* e) {
-    e->last_guide_ms = 0.0f;
-    if (e->dn_guides_valid) return RB_OK;
-    rb::KParams p{};
-    int rc = ensure_prepared(e);
-    if (!rc) rc = scene_params(e, &p);
-    if (rc) return rc;
-    const uint32_t w = e->sc.width, h = e->sc.height;
-    const size_t n = static_cast<size_t>(w) * h;
-    rb::DevBuf<rb_hit> hits;       // the records live until the pack has read them
-    rb::DevBuf<rb_surface> surf;
-    HIP_TRY(e, hits.resize(n));
-    HIP_TRY(e, surf.resize(n));
-    if (e->hist_valid && e->hist_set == e->dn_set) e->dn_set ^= 1;   // the history keeps the planes its frame was made with (section 22)
-    HIP_TRY(e, e->dn_nt[e->dn_set].resize(n * 4));
-    HIP_TRY(e, e->dn_pc[e->dn_set].resize(n * 4));
-    HIP_TRY(e, e->dn_al[e->dn_set].resize(n * 4));
-    if (n) {
-        HIP_TRY(e, hipEventRecord(e->ev_dn[0], e->stream));
-        const uint32_t piece_rows = frame_piece_rows(w);   // as rb_render_hits
-        for (uint32_t r0 = 0; r0 < h; r0 += piece_rows) {
-            rb::QueryArgs q{};
-            q.win_y = r0;
-            q.win_w = w;
-            q.win_h = std::min(piece_rows, h - r0);
-            q.win_global = 1u;
-            q.hits = hits.ptr + static_cast<size_t>(r0) * w;
-            q.surf = surf.ptr + static_cast<size_t>(r0) * w;
-            const int st = rb::launch_query(p, q, e->stream, nullptr);
-            if (st) return rb::fail(e, RB_ERR_DEVICE, "query kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
-        }
-        const int st = rb::launch_guide_pack(p.u, hits.ptr, surf.ptr, w, h, guide_planes(e), e->stream);
-        if (st) return rb::fail(e, RB_ERR_DEVICE, "guide pack launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
-        HIP_TRY(e, hipEventRecord(e->ev_dn[1], e->stream));
-        HIP_TRY(e, hipStreamSynchronize(e->stream));
-        HIP_TRY(e, hipEventElapsedTime(&e->last_guide_ms, e->ev_dn[0], e->ev_dn[1]));
-    }
-    e->dn_guides_valid = true;
-    return RB_OK;
-}
-
-int denoise_params_check(const rb_engine* e, const rb_denoise_params* prm) {
-    const char* why = nullptr;
-    if (!rb::denoise_params_valid(*prm, &why)) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "rb_denoise_params: %s", why);
-    return RB_OK;
-}
-
-int reproject_params_check(const rb_engine* e, const rb_reproject_params* prm) {
-    const char* why = nullptr;
-    if (!rb::reproject_params_valid(*prm, &why)) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "rb_reproject_params: %s", why);
-    return RB_OK;
-}
-
-// the view of a render camera (rb_abi.h): rb_host_cam.hpp's steps, then one operation per scalar
-rb_view view_of(const rb_camera& cam, uint32_t w, uint32_t h) {
-    const rb::CamBasis b = rb::host_cam_basis(cam, w, h);
-    rb_view v{};
-    for (int k = 0; k < 3; k++) v.pos[k] = cam.pos[k], v.right[k] = b.right[k], v.up[k] = b.up[k], v.fwd[k] = b.fwd[k];
-    v.cx = b.wm1 * 0.5f;
-    v.cy = b.hm1 * 0.5f;
-    const float fa = b.fov * b.aspect;
-    v.sx = v.cx / fa;
-    v.sy = v.cy / b.fov;
-    return v;
-}
-
-// Steps 2 to 4 of rb_denoise_history (section 22.2) on the engine's stream; the guides are current.  Afterwards e->hist_frame
-// holds F.
-int history_step(rb_engine* e, const rb_reproject_params& prm) {
-    const uint32_t w = e->sc.width, h = e->sc.height;
-    const size_t n = static_cast<size_t>(w) * h;
-    for (hipEvent_t& x : e->ev_rp)
-        if (!x) HIP_TRY(e, hipEventCreate(&x));
-    e->reproject_ms_pending = false;
-    e->last_reproject_ms = 0.0f;
-    HIP_TRY(e, e->hist_base.resize(n * 4));
-    // (an accepted update stands between H and an invalid base, and ensure_guides has built its guides into the other set)
-    const bool carry = !e->hist_base_valid && e->hist_valid && e->hist_w == w && e->hist_h == h && rb::view_finite(e->hist_view) &&
-                       e->hist_set != e->dn_set;
-    if (!e->hist_base_valid && !carry) {
-        e->hist_valid = false;
-        HIP_TRY(e, e->hist_frame.resize(n * 4));
-    }
-    HIP_TRY(e, hipEventRecord(e->ev_rp[0], e->stream));
-    if (!e->hist_base_valid) {
-        if (carry) {
-            rb::ReprojectArgs a{};
-            a.w = w;
-            a.h = h;
-            a.view = e->hist_view;
-            a.prev4 = e->hist_frame.ptr;
-            a.prev = guide_planes(e, e->hist_set);
-            a.cur = guide_planes(e);
-            a.out4 = e->hist_base.ptr;
-            const int st = rb::launch_reproject(prm, a, e->stream);
-            if (st) return rb::fail(e, RB_ERR_DEVICE, "reproject kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
-        } else {
-            HIP_TRY(e, hipMemsetAsync(e->hist_base.ptr, 0, n * 16, e->stream));   // every record NONE
-        }
-        e->hist_set = e->dn_set;   // the history's guides from here on: this update's planes, shared with the filter
-        e->hist_view = view_of(e->sc.uniforms.camera, w, h);
-        e->hist_w = w;
-        e->hist_h = h;
-        e->hist_base_valid = true;
-    }
-    const int st = rb::launch_history_merge(w, h, e->slot[e->cur].accum.ptr, e->hist_base.ptr, guide_planes(e), e->hist_frame.ptr, e->stream);
-    if (st) return rb::fail(e, RB_ERR_DEVICE, "history merge launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
-    HIP_TRY(e, hipEventRecord(e->ev_rp[1], e->stream));
-    e->hist_valid = true;
-    e->reproject_ms_pending = true;
-    return RB_OK;
-}
-
-// device == true: the outputs are the caller's device buffers and nothing is waited for.  rprm: rb_denoise_history -- the filter
-// runs on F of section 22 instead of the mean radiance
-int denoise_locked(rb_engine* e, const rb_denoise_params* prm, uint8_t* rgba_out, float* linear_out, bool device,
-                   const rb_reproject_params* rprm = nullptr) {
-    int rc = denoise_ready(e);
-    if (!rc) rc = denoise_params_check(e, prm);
-    if (!rc && rprm) rc = reproject_params_check(e, rprm);
-    if (rc) return rc;
-    if (!rgba_out && !linear_out) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "rgba_out and linear_out are both NULL");
-    const size_t n = static_cast<size_t>(e->sc.width) * e->sc.height;
-    if (device) {
-        if (rgba_out) rc = device_range(e, rgba_out, n * 4, 4, "d_rgba_out");
-        if (!rc && linear_out) rc = device_range(e, linear_out, n * 16, 16, "d_linear_out");
-        if (rc) return rc;
-    }
-    rc = ensure_guides(e);
-    if (rc) return rc;
-    e->denoise_ms_pending = false;
-    e->last_denoise_ms = 0.0f;
-    if (n == 0) return RB_OK;
-    rb::DenoiseArgs a{};
-    a.w = e->sc.width;
-    a.h = e->sc.height;
-    a.accum = e->slot[e->cur].accum.ptr;
-    a.g = guide_planes(e);
-    for (int k = 0; k < 2; ++k) {
-        HIP_TRY(e, e->dn_r[k].resize(n * 4));
-        a.r[k] = e->dn_r[k].ptr;
-    }
-    if (!device) {   // (reserved before the history moves: a failed reservation leaves H as it was)
-        if (rgba_out) HIP_TRY(e, e->dn_rgba.resize(n));
-        if (linear_out) HIP_TRY(e, e->dn_linear.resize(n * 4));
-    }
-    if (rprm) {
-        rc = history_step(e, *rprm);
-        if (rc) return rc;
-        a.accum = nullptr;
-        a.color4 = e->hist_frame.ptr;
-    }
-    if (device) {
-        a.rgba_out = reinterpret_cast<uint32_t*>(rgba_out);
-        a.linear_out = linear_out;
-    } else {
-        if (rgba_out) {
-            HIP_TRY(e, e->dn_rgba.resize(n));
-            a.rgba_out = e->dn_rgba.ptr;
-        }
-        if (linear_out) {
-            HIP_TRY(e, e->dn_linear.resize(n * 4));
-            a.linear_out = e->dn_linear.ptr;
-        }
-    }
-    HIP_TRY(e, hipEventRecord(e->ev_dn[2], e->stream));
-    const int st = rb::launch_denoise(*prm, a, e->stream);
-    if (st) return rb::fail(e, RB_ERR_DEVICE, "denoise kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
-    HIP_TRY(e, hipEventRecord(e->ev_dn[3], e->stream));
-    if (device) {
-        e->denoise_ms_pending = true;
-        return RB_OK;
-    }
-    if (rgba_out) rc = query_copy_out(e, rgba_out, e->dn_rgba.ptr, n * 4, page_locked(rgba_out));
-    if (!rc && linear_out) rc = query_copy_out(e, linear_out, e->dn_linear.ptr, n * 16, page_locked(linear_out));
-    if (rc) return rc;
-    HIP_TRY(e, hipStreamSynchronize(e->stream));
-    HIP_TRY(e, hipEventElapsedTime(&e->last_denoise_ms, e->ev_dn[2], e->ev_dn[3]));
-    return RB_OK;
-}
-
-int denoise_guides_locked(rb_engine* e, rb_guide* guides_out) {
-    int rc = denoise_ready(e);
-    if (!rc) rc = ensure_guides(e);
-    if (rc) return rc;
-    const size_t n = static_cast<size_t>(e->sc.width) * e->sc.height;
-    if (n == 0) return RB_OK;
-    rb::DevBuf<rb_guide> joined;
-    HIP_TRY(e, joined.resize(n));
-    const int st = rb::launch_guide_join(guide_planes(e), n, joined.ptr, e->stream);
-    if (st) return rb::fail(e, RB_ERR_DEVICE, "guide join launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
-    rc = query_copy_out(e, guides_out, joined.ptr, n * sizeof(rb_guide), page_locked(guides_out));
-    if (rc) return rc;
-    HIP_TRY(e, hipStreamSynchronize(e->stream));   // `joined` is freed on return
-    return RB_OK;
-}
-
 // ---- temporal reprojection (rb_abi.h)
-// the refusals the forms of rb_reproject share; before a device is touched (e may be NULL: the engine-less form)
-int reproject_check(rb_engine* e, const char* who, const rb_reproject_params* prm, uint32_t w, uint32_t h, const rb_view* view, const void* prev4,
-                    const void* prev_guides, const void* cur_guides, const void* out4) {
-    if (!prm || !view || !prev4 || !prev_guides || !cur_guides || !out4)
-        return rb::fail(e, RB_ERR_NULL_ARGUMENT, "%s: params / prev_view / prev4 / prev_guides / cur_guides / out4 is NULL", who);
-    if (const int rc = reproject_params_check(e, prm)) return rc;
-    if (!rb::view_finite(*view)) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: a word of prev_view is not finite", who);
-    if (static_cast<uint64_t>(w) * h >= (1ull << 31)) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: a frame of %u x %u pixels is too large", who, w, h);
-    return RB_OK;
-}
-
 int reproject_device_locked(rb_engine* e, const rb_reproject_params& prm, uint32_t w, uint32_t h, const rb_view& view, const float* d_prev4,
                             const rb_guide* d_prev_guides, const rb_guide* d_cur_guides, const float* d_cur4, float* d_out4) {
     const size_t n = static_cast<size_t>(w) * h;
@@ -1205,24 +888,22 @@ int reproject_device_locked(rb_engine* e, const rb_reproject_params& prm, uint32
     });
 }
 
-int history_read_locked(rb_engine* e, float* out4) {
-    int rc = denoise_ready(e);
-    if (rc) return rc;
-    if (!e->hist_valid || e->hist_w != e->sc.width || e->hist_h != e->sc.height)   // (a history of another size is none: out4 is the current frame's)
-        return rb::fail(e, RB_ERR_NOT_INITIALIZED, "rb_history_read: the engine has no history of this size (rb_denoise_history makes it)");
-    const size_t n = static_cast<size_t>(e->hist_w) * e->hist_h;
-    if (n == 0) return RB_OK;
-    rc = query_copy_out(e, out4, e->hist_frame.ptr, n * 16, page_locked(out4));
-    if (rc) return rc;
-    HIP_TRY(e, hipStreamSynchronize(e->stream));
-    return RB_OK;
-}
+// the engine that answers a query (a multi-device handle: devices[0], which holds the whole scene) ...
+rb_engine* query_engine(rb_engine* e) { return rb::is_group(e) ? e->parts[0].get() : e; }
 
-// the engine that answers a query (a multi-device handle: devices[0], which holds the whole scene), made current
+// ... made current
 rb_engine* answering(rb_engine* e) {
-    rb_engine* const t = rb::is_group(e) ? e->parts[0].get() : e;
+    rb_engine* const t = query_engine(e);
     rb::set_device(t);
     return t;
+}
+
+// a getter of one of the query's stage times: the lock, the engine that answers, the read
+int query_stage_ms(rb_engine* e, rb::StageTimer rb_engine::*timer, float* ms) {
+    if (!e || !ms) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> lock(e->mu);
+    rb_engine* const t = query_engine(e);
+    return stage_ms(e, t, t->*timer, ms);
 }
 
 int answered(rb_engine* e, rb_engine* t, int rc) {
@@ -1348,23 +1029,18 @@ int lightmap_generate(const rb_lightmap_params& prm, const rb_gpu_triangle* d_tr
     return rb::lightmap_surfels(lightmap_args(prm, d_ptris, d_pshade, n_tris, d_uvs, n_uvs), d_surfels, d_owners, d_work, lightmap_piece_units(), stream);
 }
 
-int lightmap_events(rb_engine* e) {
-    for (hipEvent_t& x : e->ev_lm)
-        if (!x) HIP_TRY(e, hipEventCreate(&x));
-    e->lm_timed[0] = e->lm_timed[1] = false;
-    return RB_OK;
+// what a lightmap call begins with: the two stage times of the lightmap call before are gone (a query that is none leaves them)
+void lightmap_times_reset(rb_engine* e) {
+    e->t_lm_surfels.reset();
+    e->t_lm_resolve.reset();
 }
 
-// the surfel stage over the engine's scene between its own event pair, queued on the engine's stream
+// the surfel stage over the engine's scene as a pair of its own timer, queued on the engine's stream
 int lightmap_stage_surfels(rb_engine* e, const rb::KParams& p, const rb_lightmap_params& prm, rb_surfel* d_surfels, uint32_t* d_owners) {
-    const uint32_t n_tris = e->sc.n_tris;
-    if (const hipError_t st = hipEventRecord(e->ev_lm[0], e->stream)) return static_cast<int>(st);
-    const int st = lightmap_generate(prm, e->tris.ptr, n_tris, p.u.bvh_triangle_count, e->uvs.ptr, e->sc.n_uvs, e->lm_iota.ptr, e->lm_ptris.ptr,
-                                     e->lm_pshade.ptr, e->lm_work.ptr, d_surfels, d_owners, e->stream);
-    if (st) return st;
-    if (const hipError_t st1 = hipEventRecord(e->ev_lm[1], e->stream)) return static_cast<int>(st1);
-    e->lm_timed[0] = true;
-    return 0;
+    return e->t_lm_surfels.timed(e->stream, [&] {
+        return lightmap_generate(prm, e->tris.ptr, e->sc.n_tris, p.u.bvh_triangle_count, e->uvs.ptr, e->sc.n_uvs, e->lm_iota.ptr, e->lm_ptris.ptr,
+                                 e->lm_pshade.ptr, e->lm_work.ptr, d_surfels, d_owners, e->stream);
+    });
 }
 
 // the scratch of the surfel stage beside the caller's buffers
@@ -1382,8 +1058,8 @@ int lightmap_surfels_device_locked(rb_engine* e, const rb_lightmap_params& prm, 
     const size_t n = static_cast<size_t>(prm.width) * prm.height;
     int rc = device_range(e, d_surfels, n * sizeof(rb_surfel), 16, "d_surfels");
     if (!rc && d_owners) rc = device_range(e, d_owners, n * sizeof(uint32_t), 4, "d_owners");
-    if (!rc) rc = lightmap_events(e);
     if (rc) return rc;
+    lightmap_times_reset(e);
     return device_query_locked(e, [&](const rb::KParams& p, rb::LaunchInfo* li) {
         if (lightmap_scratch(e, n, d_owners == nullptr)) return static_cast<int>(hipErrorOutOfMemory);
         li->kernel_name = "k_lm_surfels";
@@ -1399,7 +1075,7 @@ int bake_lightmap_queue(rb_engine* e, const rb_lightmap_params& prm, uint32_t fi
     hp.offset = prm.offset;
     const HemiCall c{hp, first_sample, samples, false};
     const size_t piece = piece_items(RB_HEMI_PIECE_ITEMS, n, samples);
-    if (const int rc = lightmap_events(e)) return rc;
+    lightmap_times_reset(e);
     return device_query_locked(e, [&](const rb::KParams& p, rb::LaunchInfo* li) {
         hipError_t st = hipSuccess;
         if (lightmap_scratch(e, n, true) || hemi_scratch(e, c, piece)) return static_cast<int>(hipErrorOutOfMemory);
@@ -1414,11 +1090,9 @@ int bake_lightmap_queue(rb_engine* e, const rb_lightmap_params& prm, uint32_t fi
             }))
             return s;
         if (!d_rgba) return 0;
-        if (const hipError_t s = hipEventRecord(e->ev_lm[2], e->stream)) return static_cast<int>(s);
-        if (const int s = rb::launch_lightmap_resolve(sums, prm.width, prm.height, prm.dilate, d_rgba, e->lm_rgba[1].ptr, e->stream)) return s;
-        if (const hipError_t s = hipEventRecord(e->ev_lm[3], e->stream)) return static_cast<int>(s);
-        e->lm_timed[1] = true;
-        return 0;
+        return e->t_lm_resolve.timed(e->stream, [&] {
+            return rb::launch_lightmap_resolve(sums, prm.width, prm.height, prm.dilate, d_rgba, e->lm_rgba[1].ptr, e->stream);
+        });
     });
 }
 
@@ -1439,8 +1113,6 @@ int bake_lightmap_locked(rb_engine* e, const rb_lightmap_params& prm, uint32_t f
     if (!rc && sums_out) rc = query_copy_out(e, sums_out, e->lm_sums.ptr, n * sizeof(rb_radiance), page_locked(sums_out));
     if (rc) return rc;
     HIP_TRY(e, hipStreamSynchronize(e->stream));
-    HIP_TRY(e, hipEventElapsedTime(&e->last_query_ms, e->ev_q[0], e->ev_q[1]));
-    e->query_ms_pending = false;
     return RB_OK;
 }
 
@@ -1460,59 +1132,6 @@ int bake_lightmap_entry(rb_engine* e, const char* who, bool device, const rb_lig
                           : bake_lightmap_locked(t, *prm, first_sample, samples, rgba, sums);
         });
 }
-
-// The scope of an engine-less form: `device` made current (below 0: the current one stays) and a non-blocking stream of the
-// call's own, with one sticky HIP status: once it is bad every member does nothing, so a call is its steps in order and none
-// of them runs on a buffer that was not allocated.  It does not own the call's DevBufs: DECLARE IT AFTER THEM, so that on every
-// path -- finish(), or the destructor where a return comes earlier -- the stream is synchronised before any of them is freed.
-struct DeviceScope {
-    hipStream_t stream = nullptr;
-    hipError_t st = hipSuccess;
-    int32_t refused = -1;   // the device hipSetDevice did not take
-    explicit DeviceScope(int32_t device) {
-        if (device >= 0 && hipSetDevice(device) != hipSuccess) {
-            refused = device;
-            st = hipErrorInvalidDevice;
-        } else {
-            st = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
-        }
-    }
-    DeviceScope(const DeviceScope&) = delete;
-    DeviceScope& operator=(const DeviceScope&) = delete;
-    ~DeviceScope() { close(); }
-    bool ok() const { return st == hipSuccess; }
-    template <class T>
-    void alloc(rb::DevBuf<T>& buf, size_t count) {
-        if (ok()) st = buf.resize(count);
-    }
-    void upload(void* dst, const void* src, size_t bytes) {
-        if (ok() && bytes) st = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream);
-    }
-    void download(void* dst, const void* src, size_t bytes) {
-        if (ok() && bytes) st = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream);
-    }
-    // `launch()` queues kernels on `stream` and returns a HIP status.  A callable, not the status: the launch itself must not
-    // happen once a step before it has failed.
-    template <class Launch>
-    void run(Launch&& launch) {
-        if (ok()) st = static_cast<hipError_t>(launch());
-    }
-    void sync() {
-        if (ok()) st = hipStreamSynchronize(stream);
-    }
-    void close() {
-        if (!stream) return;
-        const hipError_t s = hipStreamSynchronize(stream);   // whatever st is: the call's buffers are freed after this
-        if (ok()) st = s;
-        (void)hipStreamDestroy(stream);
-        stream = nullptr;
-    }
-    int finish(const char* who) {
-        close();
-        if (refused >= 0) return rb::fail(nullptr, RB_ERR_DEVICE, "hipSetDevice(%d) failed", refused);
-        return ok() ? RB_OK : rb::fail(nullptr, RB_ERR_DEVICE, "%s failed: %s", who, hipGetErrorString(st));
-    }
-};
 
 }  // namespace
 
@@ -1997,144 +1616,10 @@ int rb_bake_lightmap_device(rb_engine* e, const rb_lightmap_params* params, uint
 int rb_last_lightmap_ms(rb_engine* e, float* surfels_ms, float* resolve_ms) {
     if (!e) return RB_ERR_NULL_ARGUMENT;
     std::lock_guard<std::mutex> lock(e->mu);
-    rb_engine* const t = rb::is_group(e) ? e->parts[0].get() : e;
-    float* const out[2] = {surfels_ms, resolve_ms};
-    for (int k = 0; k < 2; k++) {
-        if (!out[k]) continue;
-        *out[k] = 0.0f;
-        if (!t->lm_timed[k]) continue;
-        rb::set_device(t);
-        HIP_TRY(e, hipEventSynchronize(t->ev_lm[2 * k + 1]));
-        HIP_TRY(e, hipEventElapsedTime(out[k], t->ev_lm[2 * k], t->ev_lm[2 * k + 1]));
-    }
-    return RB_OK;
-}
-
-int rb_denoise_default_params(rb_denoise_params* p) {
-    if (!p) return RB_ERR_NULL_ARGUMENT;
-    *p = rb_denoise_params{};
-    p->iterations = 3;   // chosen on the quality test: DESIGN.md section 13.4
-    p->normal_power_log2 = 3;
-    p->sigma_depth = 0.02f;
-    p->sigma_color = 0.0f;   // the colour term is off: at a few samples per pixel it takes fireflies for edges
-    p->albedo_floor = 0.01f;
-    return RB_OK;
-}
-
-int rb_denoise(rb_engine* e, const rb_denoise_params* params, uint8_t* rgba_out, float* linear_out) {
-    if (!e || !params) return RB_ERR_NULL_ARGUMENT;
-    std::lock_guard<std::mutex> lock(e->mu);
-    return denoise_locked(e, params, rgba_out, linear_out, false);
-}
-
-int rb_denoise_device(rb_engine* e, const rb_denoise_params* params, uint8_t* d_rgba_out, float* d_linear_out) {
-    if (!e || !params) return RB_ERR_NULL_ARGUMENT;
-    std::lock_guard<std::mutex> lock(e->mu);
-    return denoise_locked(e, params, d_rgba_out, d_linear_out, true);
-}
-
-int rb_denoise_guides(rb_engine* e, rb_guide* guides_out) {
-    if (!e) return RB_ERR_NULL_ARGUMENT;
-    std::lock_guard<std::mutex> lock(e->mu);
-    if (!guides_out) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "guides_out is NULL");
-    return denoise_guides_locked(e, guides_out);
-}
-
-int rb_last_denoise_ms(rb_engine* e, float* ms, float* guide_build_ms) {
-    if (!e || !ms) return RB_ERR_NULL_ARGUMENT;
-    std::lock_guard<std::mutex> lock(e->mu);
-    if (e->denoise_ms_pending) {   // rb_denoise_device returned without waiting: its events are read here
-        rb::set_device(e);
-        HIP_TRY(e, hipEventSynchronize(e->ev_dn[3]));
-        HIP_TRY(e, hipEventElapsedTime(&e->last_denoise_ms, e->ev_dn[2], e->ev_dn[3]));
-        e->denoise_ms_pending = false;
-    }
-    *ms = e->last_denoise_ms;
-    if (guide_build_ms) *guide_build_ms = e->last_guide_ms;
-    return RB_OK;
-}
-
-int rb_denoise_buffers(int32_t device, const rb_denoise_params* params, uint32_t w, uint32_t h, const float* color4,
-                       const rb_guide* guides, float* out4, uint8_t* rgba_out) {
-    if (!params || !color4 || !guides) return rb::fail(nullptr, RB_ERR_NULL_ARGUMENT, "params / color4 / guides is NULL");
-    if (!out4 && !rgba_out) return rb::fail(nullptr, RB_ERR_NULL_ARGUMENT, "out4 and rgba_out are both NULL");
-    if (const int rc = denoise_params_check(nullptr, params)) return rc;
-    const size_t n = static_cast<size_t>(w) * h;
-    if (n >= (1ull << 31)) return rb::fail(nullptr, RB_ERR_INVALID_OPTIONS, "a frame of %u x %u pixels is too large", w, h);
-    if (n == 0) return RB_OK;
-    rb::DevBuf<float> d_color, d_nt, d_pc, d_al, d_r0, d_r1, d_linear;
-    rb::DevBuf<rb_guide> d_guides;
-    rb::DevBuf<uint32_t> d_rgba;
-    DeviceScope s(device);
-    for (rb::DevBuf<float>* b : {&d_color, &d_nt, &d_pc, &d_al, &d_r0, &d_r1}) s.alloc(*b, n * 4);
-    s.alloc(d_guides, n);
-    if (out4) s.alloc(d_linear, n * 4);
-    if (rgba_out) s.alloc(d_rgba, n);
-    s.upload(d_color.ptr, color4, n * 16);
-    s.upload(d_guides.ptr, guides, n * sizeof(rb_guide));
-    rb::DenoiseArgs a{};
-    a.w = w;
-    a.h = h;
-    a.color4 = d_color.ptr;
-    a.g = rb::GuidePlanes{d_nt.ptr, d_pc.ptr, d_al.ptr};
-    a.r[0] = d_r0.ptr;
-    a.r[1] = d_r1.ptr;
-    a.linear_out = d_linear.ptr;
-    a.rgba_out = d_rgba.ptr;
-    s.run([&] { return rb::launch_guide_split(d_guides.ptr, n, a.g, s.stream); });
-    s.run([&] { return rb::launch_denoise(*params, a, s.stream); });
-    if (out4) s.download(out4, d_linear.ptr, n * 16);
-    if (rgba_out) s.download(rgba_out, d_rgba.ptr, n * 4);
-    return s.finish("rb_denoise_buffers");
-}
-
-int rb_view_from_camera(const rb_camera* cam, uint32_t w, uint32_t h, rb_view* out) {
-    if (!cam || !out) return rb::fail(nullptr, RB_ERR_NULL_ARGUMENT, "rb_view_from_camera: cam / out is NULL");
-    *out = view_of(*cam, w, h);
-    return RB_OK;
-}
-
-int rb_reproject_default_params(rb_reproject_params* p) {
-    if (!p) return RB_ERR_NULL_ARGUMENT;
-    *p = rb_reproject_params{};
-    p->sigma_depth = 0.02f;    // the denoiser's plane distance and floor (section 13)
-    p->normal_min = 0.9f;      // from the literature, or the sweep of DESIGN.md section 22.5: section 22.7 says which
-    p->albedo_floor = 0.01f;
-    p->max_history = 32.0f;
-    return RB_OK;
-}
-
-int rb_reproject_buffers(int32_t device, const rb_reproject_params* params, uint32_t w, uint32_t h, const rb_view* prev_view,
-                         const float* prev4, const rb_guide* prev_guides, const rb_guide* cur_guides, const float* cur4, float* out4) {
-    if (const int rc = reproject_check(nullptr, "rb_reproject_buffers", params, w, h, prev_view, prev4, prev_guides, cur_guides, out4)) return rc;
-    const size_t n = static_cast<size_t>(w) * h;
-    if (n == 0) return RB_OK;
-    rb::DevBuf<float> d_prev4, d_cur4, d_out, d_pl[6];
-    rb::DevBuf<rb_guide> d_guides;   // staging of one guide array at a time
-    DeviceScope s(device);
-    s.alloc(d_prev4, n * 4);
-    if (cur4) s.alloc(d_cur4, n * 4);
-    s.alloc(d_out, n * 4);
-    for (rb::DevBuf<float>& b : d_pl) s.alloc(b, n * 4);
-    s.alloc(d_guides, n);
-    rb::ReprojectArgs a{};
-    a.w = w;
-    a.h = h;
-    a.view = *prev_view;
-    a.prev4 = d_prev4.ptr;
-    a.prev = rb::GuidePlanes{d_pl[0].ptr, d_pl[1].ptr, d_pl[2].ptr};
-    a.cur = rb::GuidePlanes{d_pl[3].ptr, d_pl[4].ptr, d_pl[5].ptr};
-    a.cur4 = cur4 ? d_cur4.ptr : nullptr;
-    a.out4 = d_out.ptr;
-    s.upload(d_prev4.ptr, prev4, n * 16);
-    if (cur4) s.upload(d_cur4.ptr, cur4, n * 16);
-    s.upload(d_guides.ptr, prev_guides, n * sizeof(rb_guide));
-    s.run([&] { return rb::launch_guide_split(d_guides.ptr, n, a.prev, s.stream); });
-    s.upload(d_guides.ptr, cur_guides, n * sizeof(rb_guide));   // (in stream order behind the split that read the staging)
-    s.run([&] { return rb::launch_guide_split(d_guides.ptr, n, a.cur, s.stream); });
-    s.run([&] { return rb::launch_reproject(*params, a, s.stream); });
-    s.download(out4, d_out.ptr, n * 16);
-    return s.finish("rb_reproject_buffers");
+    rb_engine* const t = query_engine(e);
+    if (surfels_ms)
+        if (const int rc = stage_ms(e, t, t->t_lm_surfels, surfels_ms)) return rc;
+    return resolve_ms ? stage_ms(e, t, t->t_lm_resolve, resolve_ms) : RB_OK;
 }
 
 int rb_reproject_device(rb_engine* e, const rb_reproject_params* params, uint32_t w, uint32_t h, const rb_view* prev_view, const float* d_prev4,
@@ -2145,95 +1630,14 @@ int rb_reproject_device(rb_engine* e, const rb_reproject_params* params, uint32_
         [&](rb_engine* t) { return reproject_device_locked(t, *params, w, h, *prev_view, d_prev4, d_prev_guides, d_cur_guides, d_cur4, d_out4); });
 }
 
-int rb_denoise_history(rb_engine* e, const rb_reproject_params* rparams, const rb_denoise_params* dparams, uint8_t* rgba_out, float* linear_out) {
-    if (!e || !rparams || !dparams) return RB_ERR_NULL_ARGUMENT;
-    std::lock_guard<std::mutex> lock(e->mu);
-    return denoise_locked(e, dparams, rgba_out, linear_out, false, rparams);
-}
-
-int rb_denoise_history_device(rb_engine* e, const rb_reproject_params* rparams, const rb_denoise_params* dparams, uint8_t* d_rgba_out,
-                              float* d_linear_out) {
-    if (!e || !rparams || !dparams) return RB_ERR_NULL_ARGUMENT;
-    std::lock_guard<std::mutex> lock(e->mu);
-    return denoise_locked(e, dparams, d_rgba_out, d_linear_out, true, rparams);
-}
-
-int rb_history_read(rb_engine* e, float* out4) {
-    if (!e) return RB_ERR_NULL_ARGUMENT;
-    std::lock_guard<std::mutex> lock(e->mu);
-    if (!out4) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "out4 is NULL");
-    return history_read_locked(e, out4);
-}
-
-int rb_history_reset(rb_engine* e) {
-    if (!e) return RB_ERR_NULL_ARGUMENT;
-    std::lock_guard<std::mutex> lock(e->mu);
-    if (rb::is_group(e)) return RB_OK;   // a multi-device handle keeps no history
-    e->hist_valid = false;
-    e->hist_base_valid = false;
-    return RB_OK;
-}
-
-int rb_last_reproject_ms(rb_engine* e, float* ms) {
-    if (!e || !ms) return RB_ERR_NULL_ARGUMENT;
-    std::lock_guard<std::mutex> lock(e->mu);
-    if (e->reproject_ms_pending) {   // the history step is not waited for: its events are read here
-        rb::set_device(e);
-        HIP_TRY(e, hipEventSynchronize(e->ev_rp[1]));
-        HIP_TRY(e, hipEventElapsedTime(&e->last_reproject_ms, e->ev_rp[0], e->ev_rp[1]));
-        e->reproject_ms_pending = false;
-    }
-    *ms = e->last_reproject_ms;
-    return RB_OK;
-}
-
 const char* rb_last_query_kernel_name(const rb_engine* e) {
     if (!e) return "";
     return rb::is_group(e) ? e->parts[0]->last_query_kernel_name : e->last_query_kernel_name;
 }
 
-int rb_last_query_ms(rb_engine* e, float* ms) {
-    if (!e || !ms) return RB_ERR_NULL_ARGUMENT;
-    std::lock_guard<std::mutex> lock(e->mu);
-    rb_engine* const t = rb::is_group(e) ? e->parts[0].get() : e;
-    if (t->query_ms_pending) {   // a device form returned without waiting: its events are read here
-        rb::set_device(t);
-        HIP_TRY(e, hipEventSynchronize(t->ev_q[1]));
-        HIP_TRY(e, hipEventElapsedTime(&t->last_query_ms, t->ev_q[0], t->ev_q[1]));
-        t->query_ms_pending = false;
-    }
-    *ms = t->last_query_ms;
-    return RB_OK;
-}
-
-int rb_last_camera_rays_ms(rb_engine* e, float* ms) {
-    if (!e || !ms) return RB_ERR_NULL_ARGUMENT;
-    std::lock_guard<std::mutex> lock(e->mu);
-    rb_engine* const t = rb::is_group(e) ? e->parts[0].get() : e;
-    *ms = 0.0f;
-    if (t->cam_pieces == 0) return RB_OK;
-    rb::set_device(t);
-    return answered(e, t, pairs_ms(t, t->ev_cam, t->cam_pieces, ms));
-}
-
-int rb_last_probe_project_ms(rb_engine* e, float* ms) {
-    if (!e || !ms) return RB_ERR_NULL_ARGUMENT;
-    std::lock_guard<std::mutex> lock(e->mu);
-    rb_engine* const t = rb::is_group(e) ? e->parts[0].get() : e;
-    *ms = 0.0f;
-    if (t->sh_pieces == 0) return RB_OK;
-    rb::set_device(t);
-    return answered(e, t, pairs_ms(t, t->ev_sh, t->sh_pieces, ms));
-}
-
-int rb_last_probe_depth_project_ms(rb_engine* e, float* ms) {
-    if (!e || !ms) return RB_ERR_NULL_ARGUMENT;
-    std::lock_guard<std::mutex> lock(e->mu);
-    rb_engine* const t = rb::is_group(e) ? e->parts[0].get() : e;
-    *ms = 0.0f;
-    if (t->depth_pieces == 0) return RB_OK;
-    rb::set_device(t);
-    return answered(e, t, pairs_ms(t, t->ev_depth, t->depth_pieces, ms));
-}
+int rb_last_query_ms(rb_engine* e, float* ms) { return query_stage_ms(e, &rb_engine::t_query, ms); }
+int rb_last_camera_rays_ms(rb_engine* e, float* ms) { return query_stage_ms(e, &rb_engine::t_generator, ms); }
+int rb_last_probe_project_ms(rb_engine* e, float* ms) { return query_stage_ms(e, &rb_engine::t_sh, ms); }
+int rb_last_probe_depth_project_ms(rb_engine* e, float* ms) { return query_stage_ms(e, &rb_engine::t_depth, ms); }
 
 }  // extern "C"

@@ -872,17 +872,9 @@ void rb_destroy(rb_engine* e) {
     for (rb::FrameSlot& s : e->slot)
         if (s.done) (void)hipEventDestroy(s.done);
     for (hipEvent_t x : e->ev_pool) (void)hipEventDestroy(x);
-    for (hipEvent_t x : e->ev_cam) (void)hipEventDestroy(x);
-    for (hipEvent_t x : e->ev_sh) (void)hipEventDestroy(x);
-    for (hipEvent_t x : e->ev_depth) (void)hipEventDestroy(x);
-    for (hipEvent_t x : e->ev_q)
-        if (x) (void)hipEventDestroy(x);
-    for (hipEvent_t x : e->ev_dn)
-        if (x) (void)hipEventDestroy(x);
-    for (hipEvent_t x : e->ev_rp)
-        if (x) (void)hipEventDestroy(x);
-    for (hipEvent_t x : e->ev_lm)
-        if (x) (void)hipEventDestroy(x);
+    for (rb::StageTimer* t : {&e->t_query, &e->t_generator, &e->t_sh, &e->t_depth, &e->t_lm_surfels, &e->t_lm_resolve, &e->t_guides,
+                              &e->t_filter, &e->t_history})
+        t->destroy();
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
 }
