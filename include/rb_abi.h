@@ -559,6 +559,9 @@ int rb_debug_rcp_det_exhaustive(uint32_t biased_exponent, uint32_t* out16);
  * in any bit (must be 0), out32[1] = index of one such triple, out32[2..17] = its o, d, v0, edge1, edge2, incoming hit.t,
  * out32[18..21] / out32[22..25] = the two results. */
 int rb_debug_triangle_trip(uint32_t n, uint32_t seed, uint32_t* out32);
+/* Test hook: the same sweep for the trip of the flat kernels (rb_debug_trace_form), which carries {t, slot} only: those two
+ * words against the compiler-laid form's, bit for bit.  out32 as above (the u, v words repeat the compiler-laid form's). */
+int rb_debug_triangle_trip_flat(uint32_t n, uint32_t seed, uint32_t* out32);
 /* Test hook: the root box of the single-node walk on `n` (at most 2^24) rays of six floats {origin, direction} and the box
  * box6 = {bmin, bmax}: out[i] bit 0 = the walk's slab test on its own reciprocals, bit 1 = the rule by which the single-node
  * trace kernels go past that test says the answer is known to be true (origin strictly inside a finite box, no NaN in the
@@ -588,6 +591,18 @@ int rb_debug_div_exhaustive(uint32_t b_begin, uint32_t b_count, uint32_t ea, uin
 /* Name of the render kernel the most recent rb_dispatch used ("k_trace", "k_trace_bvh",
  * "k_queue", "k_pixel"). */
 const char* rb_last_kernel_name(const rb_engine* e);
+/* Test hook: which instantiation of "k_trace" the most recent rb_dispatch of the stream kernel ran -- RB_TRACE_FORM_* bits;
+ * 0 for every other kernel.  A scene whose mesh and sphere materials all have texture_index < 0 (and, with the ground on, its
+ * lights too: an empty lights vector leaves one zero-filled light of index 0) runs the FLAT kernels, which carry no
+ * barycentrics through the triangle loop and have no texel lookup.  Same frames, bit for bit.  RB_TRACE_UV=1 in the environment
+ * when an engine is made keeps it on the kernels that carry u, v, whatever the scene (A/B measurements, tests). */
+enum {
+    RB_TRACE_FORM_FLAT = 1u,    /* k_trace_flat / k_trace_flat_direct */
+    RB_TRACE_FORM_BIG = 4u,     /* the 8-wave instantiation (large launches) */
+    RB_TRACE_FORM_STAGED = 8u,  /* a row's paths started in one pass (else every lane starts its own) */
+    RB_TRACE_FORM_MULTI = 16u   /* the per-segment ablation of a multi-node tree or a sphere tree */
+};
+uint32_t rb_debug_trace_form(const rb_engine* e);
 
 /* ---- Closest-hit queries (no reference counterpart).  A query answers, for one ray: what does
  * `closest_hit` hold at shader.wgsl:603, after the ground, BVH, sphere and point-light stages of one bounce-loop iteration?

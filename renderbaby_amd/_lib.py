@@ -68,6 +68,8 @@ SIGNATURES = {
     "rb_debug_rcp_det_exhaustive": (i32, [u32, vp]),
     "rb_debug_rnd_pm1_exhaustive": (i32, [vp]),
     "rb_debug_triangle_trip": (i32, [u32, u32, vp]),
+    "rb_debug_triangle_trip_flat": (i32, [u32, u32, vp]),
+    "rb_debug_trace_form": (u32, [vp]),
     "rb_debug_root_box": (i32, [vp, u32, vp, vp]),
     "rb_debug_normalize_sites": (i32, [vp, u32, u32, u32, u32, vp]),
     "rb_measure_salu_mix": (i32, [i32, u32, u32, P(C.c_double)]),

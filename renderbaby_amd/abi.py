@@ -143,6 +143,8 @@ RB_ERR_NO_MORE_FRAMES = 12
 RB_ERR_DEVICE = 16   # HIP runtime failure
 
 KERNEL_DEFAULT, KERNEL_PIXEL, KERNEL_QUEUE, KERNEL_STREAM = 0, 1, 2, 3
+# rb_debug_trace_form: which instantiation of "k_trace" ran
+TRACE_FORM_FLAT, TRACE_FORM_BIG, TRACE_FORM_STAGED, TRACE_FORM_MULTI = 1, 4, 8, 16
 FLAG_STATS = 1
 FLAG_NO_SPHERE_BVH = 2
 FLAG_FAST_BVH = 4

@@ -169,6 +169,8 @@ DEV float trip_unit(uint32_t& s) {   // [-1, 1)
     s = pcg(s);
     return (float)(int32_t)s * 0x1p-31f;
 }
+// FLAT (rb_debug_triangle_trip_flat): the flat kernels' trip, accept_trip<.., UV = false>, whose {t, slot} must be accept_slot<true>'s.
+template <bool FLAT>
 __global__ void __launch_bounds__(256) k_triangle_trip(uint32_t n_waves, uint32_t seed, uint32_t* mismatch) {
     const uint32_t wave = (blockIdx.x * 256u + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
     if (wave >= n_waves + kTripCases) return;
@@ -212,7 +214,12 @@ __global__ void __launch_bounds__(256) k_triangle_trip(uint32_t n_waves, uint32_
     if constexpr (RB_TRIP_BLOCK) asm("s_mov_b32 %0, 0x71800000" : "=s"(big));
     if (on) {
         accept_slot<true>(ra, rb_, rc, slot, o, d, want);
-        if constexpr (RB_TRIP_BLOCK) accept_trip<RB_TRIP_ASM - 1>(ra, rb_, rc, slot, o, d, big, got);
+        if constexpr (FLAT && RB_TRIP_BLOCK) {
+            TriHitT<false> flat;
+            flat.t = got.t, flat.slot = got.slot, flat.hit = false;
+            accept_trip<RB_TRIP_ASM - 1, false>(ra, rb_, rc, slot, o, d, big, flat);
+            got.t = flat.t, got.slot = flat.slot, got.u = want.u, got.v = want.v;   // no u, v to compare
+        } else if constexpr (RB_TRIP_BLOCK) accept_trip<RB_TRIP_ASM - 1>(ra, rb_, rc, slot, o, d, big, got);
         else accept_slot<true>(ra, rb_, rc, slot, o, d, got);
     }
     if (__float_as_uint(want.t) != __float_as_uint(got.t) || __float_as_uint(want.u) != __float_as_uint(got.u) ||
@@ -517,7 +524,18 @@ int rb_debug_triangle_trip(uint32_t n, uint32_t seed, uint32_t* out32) {
     if (n > (1u << 26)) return RB_ERR_INVALID_OPTIONS;
     return rb::round_trip(out32, 128, 128, [&](uint32_t* d) {
         const uint32_t n_waves = (n + 63u) / 64u, waves = n_waves + rb::kTripCases;
-        hipLaunchKernelGGL(rb::k_triangle_trip, dim3((waves + 3u) / 4u), dim3(256), 0, nullptr, n_waves, seed, d);
+        hipLaunchKernelGGL(rb::k_triangle_trip<false>, dim3((waves + 3u) / 4u), dim3(256), 0, nullptr, n_waves, seed, d);
+    });
+}
+
+// Test hook: the same sweep for the trip of k_trace_flat / k_trace_flat_direct, which carries {t, slot}: those two words against
+// accept_slot<true>'s.  out32 as above (the u, v words repeat accept_slot's).
+int rb_debug_triangle_trip_flat(uint32_t n, uint32_t seed, uint32_t* out32) {
+    if (!out32) return RB_ERR_NULL_ARGUMENT;
+    if (n > (1u << 26)) return RB_ERR_INVALID_OPTIONS;
+    return rb::round_trip(out32, 128, 128, [&](uint32_t* d) {
+        const uint32_t n_waves = (n + 63u) / 64u, waves = n_waves + rb::kTripCases;
+        hipLaunchKernelGGL(rb::k_triangle_trip<true>, dim3((waves + 3u) / 4u), dim3(256), 0, nullptr, n_waves, seed, d);
     });
 }
 

@@ -11,8 +11,12 @@ namespace {
 // -------------------------------------------------------------- textures --
 // shader.wgsl:153-191.  pow(c, 2.2) over the 256 possible channel values is a
 // host-computed table (same libm as the oracle), so textured hits stay bit-exact.
+// TEXEL = false (the flat kernels, k_trace_flat / k_trace_flat_direct; DESIGN.md section 4, "Scenes that carry no u, v"): the
+// launch has established that no material a segment can sample carries an index >= 0, so the texel way is not compiled and
+// the index is not looked at.
+template <bool TEXEL = true>
 DEV f3 sample_texture(const KParams& p, int32_t index, float uvx, float uvy) {
-    if (index < 0) {
+    if (!TEXEL || index < 0) {
         if (p.u.checkerboard_enabled > 0u) {
             int32_t u2 = f2i(floorf(uvx * 10.0f));
             int32_t v2 = f2i(floorf(uvy * 10.0f));
@@ -168,11 +172,20 @@ DEV void flush_tally(const Tally<STATS>& t, unsigned long long* counters) {
 }
 
 // -------------------------------------------------------- BVH traversal --
-struct TriHit {
+// UV = false: the winner without its barycentrics, for the flat kernels, whose scenes never read them (tri_uv is their only reader)
+template <bool UV>
+struct TriHitT {
     float t, u, v;
     uint32_t slot;  // position in bvh_indices (prepared-triangle index)
     bool hit;
 };
+template <>
+struct TriHitT<false> {
+    float t;
+    uint32_t slot;
+    bool hit;
+};
+using TriHit = TriHitT<true>;
 
 // shader.wgsl:282-392.  Same visit order (left pushed first, right popped first),
 // same strict `t > 0.001 && t < hit.t` acceptance, so the winner is the same
@@ -180,14 +193,17 @@ struct TriHit {
 // winner and is produced afterwards (tri_shade).  `stack` is this lane's column
 // of an LDS array [kStackDepth][blockDim]; the host has verified that the tree
 // fits (rb_bvh.cpp).
-DEV void test_slot(const v4f a, const v4f b, const v4f c, uint32_t slot, f3 o, f3 d, TriHit& h) {
+template <bool UV>   // (false: never run -- the flat kernels have no multi-node walk -- but intersect_bvh's text below them is compiled)
+DEV void test_slot(const v4f a, const v4f b, const v4f c, uint32_t slot, f3 o, f3 d, TriHitT<UV>& h) {
     float u, v;
     const float t = isect_triangle(o, d, mk(a.x, a.y, a.z), mk(b.x, b.y, b.z), mk(c.x, c.y, c.z), u, v);
     if (t > 0.001f && t < h.t) {
         h.hit = true;
         h.t = t;
-        h.u = u;
-        h.v = v;
+        if constexpr (UV) {
+            h.u = u;
+            h.v = v;
+        }
         h.slot = slot;
     }
 }
@@ -252,8 +268,9 @@ DEV void accept_slot(const v4f a, const v4f b, const v4f c, uint32_t slot, f3 o,
 // as it entered it, whichever lanes were on, none included (every instruction between is a vector one, which an empty mask
 // turns into nothing, or touches only the block's own scalar temporaries).
 // SKIP: 1 = one branch over the rest of the trip when no lane passes the u test, 2 = another one after the v test.  big: 2^100 (the caller holds it in a scalar register).
-template <int SKIP>
-DEV void accept_trip(const v4f a, const v4f b, const v4f c, uint32_t slot, f3 o, f3 d, float big, TriHit& hit) {
+// UV = false: the accepted hit moves slot and t only (TriHitT<false>); every other instruction is the same in both forms.
+template <int SKIP, bool UV = true>
+DEV void accept_trip(const v4f a, const v4f b, const v4f c, uint32_t slot, f3 o, f3 d, float big, TriHitT<UV>& hit) {
     float r8, r10, r11, r12, r13, r14, r15, r16, r17;
     uint64_t entry, keep, m, ds;
 #define RB_TRIP_HEAD                                                                                                     \
@@ -333,33 +350,57 @@ DEV void accept_trip(const v4f a, const v4f b, const v4f c, uint32_t slot, f3 o,
     "v_mul_f32_e32 %[r8], %[r12], %[r8]\n\t"                 /* t */                                                     \
     "v_cmpx_lt_f32_e32 vcc, %[tmin], %[r8]\n\t"              /* t > 0.001 */                                             \
     "v_cmpx_lt_f32_e32 vcc, %[r8], %[ht]\n\t"                /* t < hit.t */                                             \
-    "v_mov_b32_e32 %[hs], %[slot]\n\t"                                                                                   \
+    "v_mov_b32_e32 %[hs], %[slot]\n\t"
+#define RB_TRIP_MOVES_UV                                                                                                 \
     "v_mov_b32_e32 %[hv], %[r11]\n\t"                                                                                    \
     "v_mov_b32_e32 %[ht], %[r8]\n\t"                                                                                     \
     "v_mov_b32_e32 %[hu], %[r10]\n"
-#define RB_TRIP_OPERANDS                                                                                                 \
-    : [ht] "+v"(hit.t), [hu] "+v"(hit.u), [hv] "+v"(hit.v), [hs] "+v"(hit.slot), [r8] "=&v"(r8), [r10] "=&v"(r10),        \
+#define RB_TRIP_MOVES_T                                                                                                  \
+    "v_mov_b32_e32 %[ht], %[r8]\n"
+#define RB_TRIP_OUT_UV [ht] "+v"(hit.t), [hu] "+v"(hit.u), [hv] "+v"(hit.v), [hs] "+v"(hit.slot)
+#define RB_TRIP_OUT_T [ht] "+v"(hit.t), [hs] "+v"(hit.slot)
+#define RB_TRIP_TEMPS                                                                                                    \
+    [r8] "=&v"(r8), [r10] "=&v"(r10),                                                                                     \
       [r11] "=&v"(r11), [r12] "=&v"(r12), [r13] "=&v"(r13), [r14] "=&v"(r14), [r15] "=&v"(r15), [r16] "=&v"(r16),         \
-      [r17] "=&v"(r17), [entry] "=&s"(entry), [keep] "=&s"(keep), [m] "=&s"(m), [ds] "=&s"(ds)                            \
-    : [ax] "s"(a.x), [ay] "s"(a.y), [az] "s"(a.z), [bx] "s"(b.x), [by] "s"(b.y), [bz] "s"(b.z), [cx] "s"(c.x),            \
+      [r17] "=&v"(r17), [entry] "=&s"(entry), [keep] "=&s"(keep), [m] "=&s"(m), [ds] "=&s"(ds)
+#define RB_TRIP_IN                                                                                                       \
+    [ax] "s"(a.x), [ay] "s"(a.y), [az] "s"(a.z), [bx] "s"(b.x), [by] "s"(b.y), [bz] "s"(b.z), [cx] "s"(c.x),              \
       [cy] "s"(c.y), [cz] "s"(c.z), [slot] "s"(slot), [ox] "v"(o.x), [oy] "v"(o.y), [oz] "v"(o.z), [dx] "v"(d.x),         \
-      [dy] "v"(d.y), [dz] "v"(d.z), [eps] "s"(1e-6f), [big] "s"(big), [tmin] "s"(0.001f)                             \
-    : "vcc", "scc"   /* s_or_b64 and s_and_saveexec_b64 write scc */
+      [dy] "v"(d.y), [dz] "v"(d.z), [eps] "s"(1e-6f)
+#define RB_TRIP_CLOBBERS "vcc", "scc"   /* s_or_b64 and s_and_saveexec_b64 write scc */
+#define RB_TRIP_OPS_UV : RB_TRIP_OUT_UV, RB_TRIP_TEMPS : RB_TRIP_IN, [big] "s"(big), [tmin] "s"(0.001f) : RB_TRIP_CLOBBERS
+#define RB_TRIP_OPS_T : RB_TRIP_OUT_T, RB_TRIP_TEMPS : RB_TRIP_IN, [big] "s"(big), [tmin] "s"(0.001f) : RB_TRIP_CLOBBERS
 #define RB_TRIP_SKIP "s_cbranch_execz .Ltrip_end_%=\n\t"
-    if constexpr (SKIP == 2) {
-        asm volatile(RB_TRIP_HEAD RB_TRIP_SKIP RB_TRIP_TAIL RB_TRIP_SKIP RB_TRIP_LAST ".Ltrip_end_%=:\n\t"
-                     "s_mov_b64 exec, %[entry]" RB_TRIP_OPERANDS);
-    } else if constexpr (SKIP == 1) {
-        asm volatile(RB_TRIP_HEAD RB_TRIP_SKIP RB_TRIP_TAIL RB_TRIP_LAST ".Ltrip_end_%=:\n\t"
-                     "s_mov_b64 exec, %[entry]" RB_TRIP_OPERANDS);
-    } else {
-        asm volatile(RB_TRIP_HEAD RB_TRIP_TAIL RB_TRIP_LAST "\ts_mov_b64 exec, %[entry]" RB_TRIP_OPERANDS);
+    // one statement per form: the same blocks in the same order, with the moves' variant put in
+#define RB_TRIP_EMIT(MOVES, OPS)                                                                                         \
+    if constexpr (SKIP == 2) {                                                                                           \
+        asm volatile(RB_TRIP_HEAD RB_TRIP_SKIP RB_TRIP_TAIL RB_TRIP_SKIP RB_TRIP_LAST MOVES ".Ltrip_end_%=:\n\t"         \
+                     "s_mov_b64 exec, %[entry]" OPS);                                                                    \
+    } else if constexpr (SKIP == 1) {                                                                                    \
+        asm volatile(RB_TRIP_HEAD RB_TRIP_SKIP RB_TRIP_TAIL RB_TRIP_LAST MOVES ".Ltrip_end_%=:\n\t"                      \
+                     "s_mov_b64 exec, %[entry]" OPS);                                                                    \
+    } else {                                                                                                             \
+        asm volatile(RB_TRIP_HEAD RB_TRIP_TAIL RB_TRIP_LAST MOVES "\ts_mov_b64 exec, %[entry]" OPS);                     \
     }
+    if constexpr (UV) {
+        RB_TRIP_EMIT(RB_TRIP_MOVES_UV, RB_TRIP_OPS_UV)
+    } else {
+        RB_TRIP_EMIT(RB_TRIP_MOVES_T, RB_TRIP_OPS_T)
+    }
+#undef RB_TRIP_EMIT
 #undef RB_TRIP_SKIP
 #undef RB_TRIP_HEAD
+#undef RB_TRIP_MOVES_UV
+#undef RB_TRIP_MOVES_T
+#undef RB_TRIP_OUT_UV
+#undef RB_TRIP_OUT_T
+#undef RB_TRIP_TEMPS
+#undef RB_TRIP_IN
+#undef RB_TRIP_CLOBBERS
+#undef RB_TRIP_OPS_UV
+#undef RB_TRIP_OPS_T
 #undef RB_TRIP_TAIL
 #undef RB_TRIP_LAST
-#undef RB_TRIP_OPERANDS
 }
 
 // (One triangle per step.  r01-r02 tested two per step with packed f32 math: on gfx950 a packed f32 instruction issues at
@@ -705,13 +746,17 @@ DEV TriHit intersect_bvh_fast(const KParams& p, f3 o, f3 d, uint32_t* stack, uin
 // TRIP (with MULTI = false; k_trace and k_trace_direct only): the triangle loop in the form the RB_TRIP_* knobs above choose.
 // Every other caller of the single-node walk keeps the double-buffered loop and accept_slot as they were.
 // box (TRIP only): kBoxUnknown, or the staged answer of the root box's slab test for this lane's ray.
-template <bool STATS, bool MULTI = true, bool TRIP = false>
-DEV TriHit intersect_bvh(const KParams& p, f3 o, f3 d, uint32_t* stack, uint32_t stride, Tally<STATS>& tl, uint32_t box = kBoxUnknown) {
-    TriHit h;
+// UV (the flat kernels pass false; they need TRIP and the hand-laid trip): accept_trip's.
+template <bool STATS, bool MULTI = true, bool TRIP = false, bool UV = true>
+DEV TriHitT<UV> intersect_bvh(const KParams& p, f3 o, f3 d, uint32_t* stack, uint32_t stride, Tally<STATS>& tl, uint32_t box = kBoxUnknown) {
+    static_assert(UV || (TRIP && !MULTI && RB_TRIP_BLOCK && RB_TRIP_PLAIN != 0), "the flat forms exist for the hand-laid trip only");
+    TriHitT<UV> h;
     h.hit = false;
     h.t = 1e20f;
-    h.u = 0.0f;
-    h.v = 0.0f;
+    if constexpr (UV) {
+        h.u = 0.0f;
+        h.v = 0.0f;
+    }
     h.slot = 0u;
     const uint32_t node_count = p.u.bvh_node_count;
     if (node_count == 0u) return h;
@@ -756,7 +801,7 @@ DEV TriHit intersect_bvh(const KParams& p, f3 o, f3 d, uint32_t* stack, uint32_t
             auto test = [&](const v4f a, const v4f b, const v4f c, uint32_t slot) {
                 if constexpr (STATS) tl.tris++;
                 const float before = h.t;
-                if constexpr (trip && RB_TRIP_BLOCK) accept_trip<RB_TRIP_ASM - 1>(a, b, c, slot, o, d, big, h);
+                if constexpr (trip && RB_TRIP_BLOCK) accept_trip<RB_TRIP_ASM - 1, UV>(a, b, c, slot, o, d, big, h);
                 else accept_slot<!MULTI>(a, b, c, slot, o, d, h);
                 if constexpr (STATS) tl.mesh_hits += (h.t != before) ? 1u : 0u;
             };

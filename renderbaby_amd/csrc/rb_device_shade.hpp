@@ -195,8 +195,8 @@ struct SegState {
 };
 
 // Ground and the BVH winner, shader.wgsl:552-571
-template <bool STATS>
-DEV SegState segment_pre(const KParams& p, const Path& pt, const TriHit th, Tally<STATS>& tl) {
+template <bool STATS, bool UV = true>
+DEV SegState segment_pre(const KParams& p, const Path& pt, const TriHitT<UV> th, Tally<STATS>& tl) {
     const f3 o = pt.o, d = pt.d;
     tl.segments++;
 
@@ -338,8 +338,11 @@ DEV void segment_spheres(const KParams& p, f3 o, f3 d, float a, float& closest_t
 #endif
 // TRIM (the kernels of single-node trees that also pass TRIP: k_trace and k_trace_direct): the four
 // normalizes of an iteration are normalize_trim (rb_device_math.hpp), same values with fewer guards.
-template <bool STATS, bool PARK = true, bool JOINED = true, bool TRIM = false>
-DEV bool segment_post(const KParams& p, Path& pt, const TriHit th, const SegState st, float closest_t, uint32_t sphere_idx,
+// UV = false (the flat kernels; DESIGN.md section 4, "Scenes that carry no u, v"): the launch has established that use_tex never
+// holds together with tri_won_a and that no sampled material has a texture index >= 0, so tri_uv and the texel way of
+// sample_texture are not compiled.  The ground's uv and the checkerboard stay.
+template <bool STATS, bool PARK = true, bool JOINED = true, bool TRIM = false, bool UV = true>
+DEV bool segment_post(const KParams& p, Path& pt, const TriHitT<UV> th, const SegState st, float closest_t, uint32_t sphere_idx,
                       Tally<STATS>& tl) {
     const f3 o = pt.o, d = pt.d;
     const float a = dot(d, d);
@@ -468,8 +471,10 @@ DEV bool segment_post(const KParams& p, Path& pt, const TriHit th, const SegStat
         scattered = near_zero(sd) ? normal : (one_norm ? nin : normalize_for<TRIM>(sd));
         albedo = m.diffuse;
         if (use_tex) {
-            if (tri_won_a) tri_uv(p, th, uvx, uvy);
-            albedo = albedo * sample_texture(p, m.tex, uvx, uvy);
+            if constexpr (UV) {
+                if (tri_won_a) tri_uv(p, th, uvx, uvy);
+            }
+            albedo = albedo * sample_texture<UV>(p, m.tex, uvx, uvy);
         }
     }
     if (absorbed) return false;
@@ -602,24 +607,25 @@ DEV void segment_resolve(const KParams& p, f3 o, f3 d, const TriHit th, const Se
 }
 
 // One iteration of the bounce loop after the triangle traversal (`th`: its winner).
-template <bool STATS, bool SPHTREE = true, bool PARK = true, bool JOINED = true, bool LEAN = false, bool TRIM = false>
-DEV bool segment_finish(const KParams& p, Path& pt, const TriHit th, uint32_t* stack, uint32_t stride,
+template <bool STATS, bool SPHTREE = true, bool PARK = true, bool JOINED = true, bool LEAN = false, bool TRIM = false, bool UV = true>
+DEV bool segment_finish(const KParams& p, Path& pt, const TriHitT<UV> th, uint32_t* stack, uint32_t stride,
                         Tally<STATS>& tl) {
-    const SegState st = segment_pre<STATS>(fresh_params(p), pt, th, tl);
+    const SegState st = segment_pre<STATS, UV>(fresh_params(p), pt, th, tl);
     float closest_t = st.closest_t;
     uint32_t sphere_idx = 0xFFFFFFFFu;
     segment_spheres<STATS, SPHTREE, LEAN>(fresh_params(p), pt.o, pt.d, dot(pt.d, pt.d), closest_t, sphere_idx, stack, stride, tl);
-    return segment_post<STATS, PARK, JOINED, TRIM>(fresh_params(p), pt, th, st, closest_t, sphere_idx, tl);
+    return segment_post<STATS, PARK, JOINED, TRIM, UV>(fresh_params(p), pt, th, st, closest_t, sphere_idx, tl);
 }
 
 // One whole iteration of the bounce loop: traversal + everything else.  MULTI = false: trees of at most one node AND no
 // sphere tree (k_trace's default instantiations).
 // TRIP: intersect_bvh's (k_trace and k_trace_direct pass it for their single-node instantiations), and segment_post's TRIM.
 // box: intersect_bvh's (k_trace hands over the staged answer of a primary ray it has just taken).
-template <bool STATS, bool MULTI = true, bool JOINED = true, bool TRIP = false>
+// UV: intersect_bvh's and segment_post's (the flat kernels pass false).
+template <bool STATS, bool MULTI = true, bool JOINED = true, bool TRIP = false, bool UV = true>
 DEV bool segment(const KParams& p, Path& pt, uint32_t* stack, uint32_t stride, Tally<STATS>& tl, uint32_t box = kBoxUnknown) {
-    const TriHit th = intersect_bvh<STATS, MULTI, TRIP>(fresh_params(p), pt.o, pt.d, stack, stride, tl, box);
-    return segment_finish<STATS, MULTI, true, JOINED, !MULTI, TRIP && !MULTI>(p, pt, th, stack, stride, tl);
+    const TriHitT<UV> th = intersect_bvh<STATS, MULTI, TRIP, UV>(fresh_params(p), pt.o, pt.d, stack, stride, tl, box);
+    return segment_finish<STATS, MULTI, true, JOINED, !MULTI, TRIP && !MULTI, UV>(p, pt, th, stack, stride, tl);
 }
 
 // ----------------------------------------------------------------- camera --

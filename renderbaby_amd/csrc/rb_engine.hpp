@@ -123,6 +123,8 @@ struct rb_engine {
 
     rb::SceneFacts sc;               // what rb_update decides on (rb_update_plan.hpp): lengths, uniforms, frame size; changed by commit_* only
     bool scene_valid = false;        // the buffers hold a scene that passed plan_update (set by the last update)
+    bool trace_uv = false;           // RB_TRACE_UV=1 when the engine was made: KParams::no_uv stays 0 (the kernels with u, v)
+    uint32_t last_trace_form = 0;    // the last render launch's LaunchInfo::trace_form (rb_debug_trace_form)
     rb_progressive prh{};            // gpu_wrapper.rs:19-53
     bool iter_initialized = false;   // RaytracerFrameIterator::initialized (lib.rs:131)
     uint32_t iter_passes_per_frame = 1;  // rb_iter_set_passes_per_frame (1 = the reference's one frame per pass)

@@ -356,12 +356,16 @@ struct KParams {
     uint32_t* stack_overflow;      // fast walk: entries beyond kStackDepth, [entry][grid * block] (nullptr if never needed)
     Cam cam;                       // set by launch_render
     const float* sph_scan;         // float4 {centre, radius * radius} per sphere, caller's order: pass 1 of the lean sphere scan
+    // what the runtime has established of the scene for the plain walk (make_params; 0 = not known; no kernel reads it: plan_launch
+    // picks the kernel by it): no segment of this launch reads a triangle's u, v or a texel
+    uint32_t no_uv;
 };
 
 struct LaunchInfo {
     uint32_t grid, block;
     size_t lds_bytes;
     const char* kernel_name;
+    uint32_t trace_form;   // launch_render, the plain walk: RB_TRACE_FORM_* bits of the instantiation that ran (rb_abi.h); else 0
 };
 
 // The walk of a query over this scene with these flags -- rb_cast_rays' rule, which launch_query, launch_occluded and

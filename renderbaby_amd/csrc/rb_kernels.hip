@@ -466,7 +466,8 @@ struct ItemQueue {
 // forced batches), and MULTI, which keeps that form whatever the batch (its segment code leaves the start no registers
 // to win).  The choice is made at compile time so that no instantiation carries both start codes; the two forms are two
 // kernels, k_trace and k_trace_direct, around this one body.
-template <bool STATS, bool MULTI, bool STAGED, bool JOINED>
+// UV: segment's (k_trace_flat and k_trace_flat_direct pass false; DESIGN.md section 4, "Scenes that carry no u, v").
+template <bool STATS, bool MULTI, bool STAGED, bool JOINED, bool UV = true>
 DEV void trace_body(const KParams& p, v4f* s_ring) {
     extern __shared__ __attribute__((aligned(16))) uint32_t s_stack[];
     const uint32_t tid = threadIdx.x;
@@ -580,7 +581,7 @@ DEV void trace_body(const KParams& p, v4f* s_ring) {
         // (53 v_mov_b32 per iteration; profiles/r12_ktrace_moves_before.txt).
         if (__ballot(active) == 0ull && exhausted && loc_next == loc_end) break;
         if (active) {
-            const bool alive = segment<STATS, MULTI, JOINED, !MULTI>(p, pt, &s_stack[tid], kTraceBlock, tl, box);
+            const bool alive = segment<STATS, MULTI, JOINED, !MULTI, UV>(p, pt, &s_stack[tid], kTraceBlock, tl, box);
             if (!alive) {
                 cring.finish(colors, item, pt.color);
                 tl.paths++;
@@ -604,6 +605,23 @@ __global__ void __launch_bounds__(kTraceBlock, WAVES) k_trace_direct(const KPara
     // none, and the 6-wave one goes from 64 registers (8 waves resident) to 68 (7)
     trace_body<STATS, MULTI, false, STATS || MULTI>(p, s_ring);
 }
+// k_trace<false, false, WAVES> and k_trace_direct<false, false, WAVES> for the launches whose scene never reads a triangle's u, v
+// or a texel (KParams::no_uv; DESIGN.md section 4, "Scenes that carry no u, v"): the trip carries {t, slot}, segment_post has no
+// tri_uv and no texel way.
+// Kernels of their own, not instantiations of the two above: a scene with a texture keeps those, bit for bit.
+#define RB_TRACE_FLAT (RB_TRIP_BLOCK && RB_TRIP_PLAIN != 0)   // they are written around the hand-laid trip
+#if RB_TRACE_FLAT
+template <int WAVES>
+__global__ void __launch_bounds__(kTraceBlock, WAVES) k_trace_flat(const KParams p) {
+    __shared__ __attribute__((aligned(16))) v4f s_ring[(kTraceBlock / 64u) * kRingWaveStaged];
+    trace_body<false, false, true, true, false>(p, s_ring);
+}
+template <int WAVES>
+__global__ void __launch_bounds__(kTraceBlock, WAVES) k_trace_flat_direct(const KParams p) {
+    __shared__ __attribute__((aligned(16))) v4f s_ring[(kTraceBlock / 64u) * kRingRows * 64u];
+    trace_body<false, false, false, false, false>(p, s_ring);   // (the two scatter normalizes, as k_trace_direct keeps them)
+}
+#endif
 
 // k_trace for multi-node BVHs.  With 128-triangle leaves and no t-culling (the reference's
 // traversal, kept for exactness) a ray visits a handful of leaves, but the number varies a lot
@@ -1585,7 +1603,8 @@ Cam host_cam(const rb_uniforms& u) {
 // The trace kernel of a plan.  The stats build never takes the 8-wave k_trace: `big` is false for it (plan_launch), and no such
 // kernel is instantiated.
 using TraceKernel = void (*)(const KParams);
-constexpr LaunchConsts kLaunchConsts = {kTraceBlock, kRingRows, kTraceManyItems, kChunkWaveLds, kSphWaveLds, RB_SPH_WAVES, RB_CHUNK_WAVES, RB_XCD_BANDS != 0};
+constexpr LaunchConsts kLaunchConsts = {kTraceBlock, kRingRows, kTraceManyItems, kChunkWaveLds, kSphWaveLds, RB_SPH_WAVES, RB_CHUNK_WAVES, RB_XCD_BANDS != 0,
+                                        RB_TRACE_FLAT != 0};
 template <bool STATS>
 static TraceKernel trace_kernel(const LaunchPlan& pl) {
     switch (pl.variant) {
@@ -1597,6 +1616,14 @@ static TraceKernel trace_kernel(const LaunchPlan& pl) {
         case kTracePlain: break;
     }
     if (pl.plain == kPlainMulti) return k_trace<STATS, true>;
+#if RB_TRACE_FLAT
+    if constexpr (!STATS)
+        if (pl.flat) {
+            constexpr int W6 = RB_TRACE_WAVES, W8 = RB_TRACE_WAVES_BIG;
+            const bool staged = pl.plain == kPlainStaged;
+            return pl.big ? (staged ? k_trace_flat<W8> : k_trace_flat_direct<W8>) : (staged ? k_trace_flat<W6> : k_trace_flat_direct<W6>);
+        }
+#endif
     if constexpr (!STATS)
         if (pl.big) return pl.plain == kPlainStaged ? k_trace<false, false, RB_TRACE_WAVES_BIG> : k_trace_direct<false, false, RB_TRACE_WAVES_BIG>;
     return pl.plain == kPlainStaged ? k_trace<STATS, false> : k_trace_direct<STATS, false>;
@@ -1637,6 +1664,9 @@ int launch_render(const KParams& p_, uint32_t kernel, bool stats, void* stream_,
         const LaunchPlan pl = plan_launch(p, stats, device_cu_count_cached(), max_dynamic_lds(dev), kLaunchConsts);
         li = pl.li;
         if (li.grid == 0) return 0;
+        if (pl.variant == kTracePlain)
+            li.trace_form = (pl.flat ? RB_TRACE_FORM_FLAT : 0u) | (pl.big ? RB_TRACE_FORM_BIG : 0u) | (pl.plain == kPlainStaged ? RB_TRACE_FORM_STAGED : 0u) |
+                            (pl.plain == kPlainMulti ? RB_TRACE_FORM_MULTI : 0u);
         KParams q = p;
         q.queue_batch = pl.queue_batch, q.queue_groups = pl.queue_groups, q.queue_region = pl.queue_region;
         q.magic_S = pl.magic_S, q.magic_tiles_x = pl.magic_tiles_x;

@@ -17,6 +17,7 @@ struct LaunchConsts {
     uint32_t chunk_wave_lds, sph_wave_lds;   // kChunkWaveLds, kSphWaveLds
     uint32_t sph_waves, chunk_waves;     // RB_SPH_WAVES, RB_CHUNK_WAVES
     bool xcd_bands;                      // RB_XCD_BANDS
+    bool flat = false;                   // the build has the flat kernels (the hand-laid trip they are written around is on)
 };
 
 // the trace walks, in the order of their names; of the plain walk the instantiation too
@@ -28,6 +29,7 @@ struct LaunchPlan {
     LaunchInfo li{};               // block, grid (0: nothing to launch), LDS bytes, and the name rb_last_kernel_name reports
     PlainKind plain = kPlainDirect;
     bool big = false;              // the plain walk's 8-wave instantiation (never MULTI's, never a stats build's)
+    bool flat = false;             // the plain walk's kernels without u, v and the texel way (k_trace_flat, k_trace_flat_direct; never MULTI's, never a stats build's)
     bool sph_tree = false;         // the chunked walk's SPHTREE instantiation
     uint32_t queue_batch = 0, queue_groups = 1, queue_region = 0, magic_S = 0, magic_tiles_x = 0;   // KParams' fields of these names
     uint32_t queue_start[kQueueGroups] = {};   // the queue's initial value: [0] alone, or one band-local start per group
@@ -123,6 +125,8 @@ inline LaunchPlan plan_launch(const KParams& p, bool stats, uint32_t cus, size_t
         pl.plain = (p.u.bvh_node_count > 1u || p.sph_nodes != nullptr) ? kPlainMulti
                    : pl.queue_batch % (k.ring_rows * 64u) == 0u        ? kPlainStaged : kPlainDirect;
         pl.big = pl.plain != kPlainMulti && !stats && items >= k.many_items;
+        // what the runtime has established of the scene (KParams::no_uv) picks the flat kernels
+        pl.flat = k.flat && pl.plain != kPlainMulti && !stats && p.no_uv != 0u;
     }
     return pl;
 }

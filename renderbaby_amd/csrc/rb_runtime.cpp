@@ -239,6 +239,11 @@ rb::KParams rb::make_params(rb_engine* e, uint32_t first_pass, uint32_t n_passes
     p.queue_batch = e->opt._reserved[2] ? std::min<uint32_t>(((std::min<uint32_t>(e->opt._reserved[2], 4096u) + 63u) / 64u) * 64u, 4096u) : 0u;
     p.no_leaf_stepping = e->opt._reserved[3];
     p.lds_mode = e->opt._reserved[4];
+    // The flat kernels' precondition ("Scenes that carry no u, v").  The lights come into it with the ground:
+    // only a ground hit leaves use_texture set where no mesh or sphere material has a texture, and a light that wins after it is
+    // sampled with its own index.  Trees the plain non-MULTI walk never sees establish nothing.
+    const bool single = p.u.bvh_node_count <= 1u && p.sph_nodes == nullptr && !e->trace_uv;
+    p.no_uv = (single && e->sc.no_uv && (e->sc.untex_lights || p.u.ground_enabled == 0u)) ? 1u : 0u;
     return p;
 }
 
@@ -413,7 +418,7 @@ int queue_group(rb_engine* e, uint32_t first_pass, uint32_t n_passes, int src, i
         }
         if (ev[3]) HIP_TRY(e, hipEventRecord(ev[3], acc));
         if (overlap) HIP_TRY(e, hipEventRecord(e->ev_accumulated[part], acc));
-        if (li.kernel_name) e->last_kernel_name = li.kernel_name;
+        if (li.kernel_name) e->last_kernel_name = li.kernel_name, e->last_trace_form = li.trace_form;
         done += n;
         launches++;
     }
@@ -644,6 +649,8 @@ rb_engine* create_single(const rb_config* cfg, const rb_options& opt) {
     if (const char* rw = std::getenv("RB_REFERENCE_WALK"); rw && rw[0] == '1')
         e->opt.flags = (e->opt.flags & ~(rb::kOwnTreeFlags | RB_FLAG_DEVICE_LBVH | RB_FLAG_CHUNK_WALK | RB_FLAG_SKIP_NEAR_DEGENERATE)) |
                        RB_FLAG_REFERENCE_WALK;
+    // RB_TRACE_UV=1: this engine's plain walk keeps the kernels that carry u, v, whatever the scene (A/B runs, tests)
+    if (const char* uv = std::getenv("RB_TRACE_UV"); uv && uv[0] == '1') e->trace_uv = true;
     auto bail = [&](const char* what, hipError_t st) -> rb_engine* {
         rb::fail(nullptr, RB_ERR_DEVICE, "%s failed: %s", what, hipGetErrorString(st));
         rb_destroy(e);
@@ -1233,6 +1240,11 @@ const char* rb_version(void) { return "renderbaby-hip 0.3 (gfx950)"; }
 const char* rb_last_kernel_name(const rb_engine* e) {
     if (!e) return "";
     return rb::is_group(e) ? e->parts[0]->last_kernel_name : e->last_kernel_name;
+}
+
+uint32_t rb_debug_trace_form(const rb_engine* e) {
+    if (!e) return 0u;
+    return rb::is_group(e) ? e->parts[0]->last_trace_form : e->last_trace_form;
 }
 
 int rb_device_name(int device, char* buf, size_t buf_len) {

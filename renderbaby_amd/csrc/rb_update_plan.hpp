@@ -63,7 +63,22 @@ struct SceneFacts {
     bool own_tree = false;           // RB_FLAG_BUILD_TREE*: the tree follows the triangles field
     uint32_t shard_rank = 0, shard_count = 0, stripe_rows = 0;
     ShardLayout layout(uint32_t h) const { return shard_layout(h, shard_rank, shard_count, stripe_rows); }
+    // What the plain walk's flat kernels rest on ("Scenes that carry no u, v"): each is false until the
+    // field it reads has been taken, and recomputed (commit_trace_facts) whenever that field is taken or deleted.
+    bool untex_meshes = false, untex_spheres = false;   // every material of the field has texture_index < 0
+    bool untex_lights = false;       // the same of the lights, the zero-filled phantom of an empty vector (index 0) included
+    bool no_uv = false;              // untex_meshes && untex_spheres: no segment reads the winning triangle's u, v
 };
+
+// ---- the facts of the flat kernels, from a field's data as the caller hands it over
+// every material's texture index is negative.  An index >= n_tex counts as a texture: sample_texture answers it in its texel way.
+template <typename T>
+inline bool untextured(const T* v, size_t n) {
+    if (n > 0 && !v) return false;
+    for (size_t i = 0; i < n; ++i)
+        if (v[i].material.texture_index >= 0) return false;
+    return true;
+}
 
 // ---- the field table
 enum Field : uint32_t { kUniforms, kSpheres, kUvs, kMeshes, kLights, kNodes, kIndices, kTriangles, kTextures, kFieldCount };
@@ -291,6 +306,21 @@ inline int plan_update(const SceneFacts& sc, const rb_config* cfg, UpdatePlan& p
 // ---- the only places where facts change.  A field's facts change when its buffer has been written (the uniforms': when
 // the frame has its size), the own tree's when it has been built, the rest at the end of the update: an update that fails
 // half-way on the device leaves facts that describe the buffers as far as they got.
+
+// the flat kernels' facts of a field that is taken or deleted.  A deleted field has no element a launch reads: vacuously true.
+// (An empty lights vector leaves one zero-filled light, texture index 0, which the kernels scan like any other.)
+inline void commit_trace_facts(SceneFacts& sc, const UpdatePlan& pl, const rb_config* cfg, Field f) {
+    const bool take = pl.act[f] == Act::Take;
+    const rb_field& fd = field_of(cfg, f);
+    switch (f) {
+        case kMeshes: sc.untex_meshes = !take || untextured(static_cast<const rb_mesh*>(fd.ptr), fd.count); break;
+        case kSpheres: sc.untex_spheres = !take || untextured(static_cast<const rb_sphere*>(fd.ptr), fd.count); break;
+        case kLights: sc.untex_lights = !take || (fd.count > 0 && untextured(static_cast<const rb_point_light*>(fd.ptr), fd.count)); break;
+        default: return;
+    }
+    sc.no_uv = sc.untex_meshes && sc.untex_spheres;
+}
+
 inline void commit_field(SceneFacts& sc, const UpdatePlan& pl, const rb_config* cfg, Field f) {
     if (f == kUniforms) {
         if (pl.act[f] == Act::Take) {
@@ -303,6 +333,7 @@ inline void commit_field(SceneFacts& sc, const UpdatePlan& pl, const rb_config* 
     }
     if (pl.act[f] == Act::None) return;
     sc.*kFields[f].len = pl.len[f];
+    commit_trace_facts(sc, pl, cfg, f);
     if (f == kNodes) {
         const rb_bvh_node* src = static_cast<const rb_bvh_node*>(cfg->bvh_nodes.ptr);
         sc.host_nodes.assign(src, src + pl.len[f]);

@@ -444,6 +444,10 @@ class Engine:
     def last_kernel_name(self):
         return (self._lib.rb_last_kernel_name(self._h) or b"").decode()
 
+    def trace_form(self):
+        """abi.TRACE_FORM_* bits of the k_trace instantiation the last render ran (rb_debug_trace_form)"""
+        return int(self._lib.rb_debug_trace_form(self._h))
+
     # ---- the queries (rb_abi.h): every array argument goes through _marshal.Form, every call through _query
     _ray_records = staticmethod(ray_records)
 
