@@ -22,7 +22,8 @@ bvh_nodes or bvh_indices.  A refused config leaves the model's scene as it was.
 ``Model.scene`` is the merged scene, ``Model.kept`` the ``counts_kept`` mask ``_oracle.render`` takes.
 
 The second half carries the steps of the update-sequence tests: named functions ``(scene, rng) -> RenderConfig`` that send
-``uniforms`` as Update plus the fields their name says, everything else Keep; the fixed scripts; and ``random_script``.
+``uniforms`` as Update plus the fields their name says, everything else Keep; the fixed scripts; ``random_script``; and
+``caches_script``, one engine's life over what the frame does not show: the emitter table and the frame history.
 """
 import dataclasses
 import functools
@@ -652,6 +653,74 @@ _GEOMETRY = {False: ["triangles_shrink", "nodes_cyclic", "triangles_permute_mesh
                      "indices_reverse_leaves", "triangles_create_taken", "tree_create_taken", "uvs_new_values", "indices_reverse_leaves", "tree_swap"],
              True: ["triangles_shrink", "own_with_nodes", "own_triangles_100", "triangles_permute_meshes", "own_triangles_128", "triangles_bad_mesh",
                     "own_triangles_129", "uniforms_nodes_below", "own_triangles_delete", "own_triangles_578", "triangles_create_taken", "uvs_new_values"]}
+
+
+# ---- what only the engine's per-scene caches see: the emitter table and the frame history (section 22.2)
+def turned_about_y(direction, degrees):
+    """a camera direction turned about the y axis, in float64 (tests/test_gpu_reproject.py turns its cameras with it)"""
+    d = np.asarray(direction, np.float64)
+    c, sn = np.cos(np.radians(degrees)), np.sin(np.radians(degrees))
+    return (c * d[0] + sn * d[2], d[1], -sn * d[0] + c * d[2])
+
+
+def _quarter_indices(n):
+    """one index in each quarter of an array of n: behind a kept count of 0.3 to 0.6 n some of them stay and some go"""
+    return sorted({(2 * q + 1) * n // 8 for q in range(4)} & set(range(n)))
+
+
+def spheres_emissive(scene, rng):
+    """the same spheres, four of them emissive, one in each quarter of the array; radii and centres as they were"""
+    sp = scene.spheres.copy()
+    for k in _quarter_indices(len(sp)):
+        sp["material"]["emissive"][k] = f32(rng.uniform(5.0, 20.0)) * _colour(rng, 0.5, 1.0)
+    return _rc(scene, spheres=sp)
+
+
+def spheres_emissive_edge(scene, rng):
+    """section 21.1's "largest component > 0" at its edges, all finite: -1 2 0 qualifies, -1 0 -0 does not, 0 0 1e-30 does"""
+    sp = scene.spheres.copy()
+    for k, em in zip(_quarter_indices(len(sp)), ((-1.0, 2.0, 0.0), (-1.0, 0.0, -0.0), (0.0, 0.0, 1e-30))):
+        sp["material"]["emissive"][k] = em
+    return _rc(scene, spheres=sp)
+
+
+def lights_one_dark(scene, rng):
+    """the lights as they are, the first one that shines with its emission 0: it stays in the buffer and leaves the table"""
+    lt = scene.lights.copy() if len(scene.lights) else make_lights(2, rng)
+    lit = np.flatnonzero(lt["material"]["emissive"].max(1) > 0)
+    lt["material"]["emissive"][int(lit[0]) if len(lit) else 0] = 0
+    return _rc(scene, lights=lt)
+
+
+def uniforms_camera_small(scene, rng):
+    """the camera turned by 2 degrees: most of the frame keeps its history"""
+    u = _uniforms(scene)
+    u["camera"]["dir"][0] = turned_about_y(u["camera"]["dir"][0], 2.0)
+    return _rc(scene, uniforms=u)
+
+
+# (not in _COMMON or LEGAL: random_script draws from LEGAL, and the scripts that exist stay as they are)
+_CACHES_ONLY = [spheres_emissive, spheres_emissive_edge, lights_one_dark, uniforms_camera_small]
+STEPS.update({f.__name__: f for f in _CACHES_ONLY})
+
+# One engine's life over the emitter table and the frame history.  tests/test_update_model.py states what it must show.
+_CACHES = {False: "triangles_shrink", True: "own_triangles_129"}
+
+
+def caches_script(own_tree=False):
+    geometry = _CACHES[bool(own_tree)]
+    return ["spheres_emissive", "meshes_too_short",                 # a table change, then a refused step
+            "uniforms_spheres_below",                               # the kept count alone drops emissive spheres
+            "uniforms_counts_above",
+            "uniforms_camera_small", "uvs_odd",                     # a camera move, then a refused step
+            "uniforms_camera_small", "uniforms_camera_small",       # two in a row
+            geometry,                                               # geometry between two history calls
+            "lights_one_dark", "uniforms_triangles_below",          # the kept count alone drops the emissive triangles
+            "spheres_65", "spheres_emissive_edge", "spheres_moved",
+            "uniforms_resolution", "uniforms_camera_small", "uniforms_resolution",   # a size change with a live history, and back
+            "uniforms_color_hash", "lights_none", "uniforms_color_hash",             # the triangle part empties under the hash
+            "triangles_permute_meshes", "lights_more", "spheres_emissive", "create_spheres_shorter", "triangles_shrink",
+            "spheres_delete"]
 
 
 def fixed_script(own_tree=False):

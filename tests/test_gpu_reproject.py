@@ -9,6 +9,7 @@ import pytest
 from renderbaby_amd import Change, Engine, RenderConfig, RenderError, abi, denoise, engine, scenes, temporal
 from tests import _reproject_cases as cases
 from tests._reproject_cases import bits
+from tests._update_model import turned_about_y
 from tests.conftest import has_gpu
 from tests.test_gpu_query import _copy
 
@@ -110,9 +111,7 @@ def real_pair(name, w, h):
 def turned(s, degrees):
     """the scene with its camera turned about the y axis"""
     t = _copy(s)
-    d = np.asarray(t.uniforms["camera"]["dir"][0], np.float64)
-    c, sn = np.cos(np.radians(degrees)), np.sin(np.radians(degrees))
-    t.uniforms["camera"]["dir"][0] = (c * d[0] + sn * d[2], d[1], -sn * d[0] + c * d[2])
+    t.uniforms["camera"]["dir"][0] = turned_about_y(t.uniforms["camera"]["dir"][0], degrees)
     return t
 
 
@@ -314,6 +313,23 @@ def test_engine_form_follows_the_model_through_a_camera_move():
         assert lib.rb_denoise_history(hd, None, dp1.ctypes.data, host.ctypes.data, None) == NULL_ARGUMENT
         assert lib.rb_denoise_history_device(hd, rp1.ctypes.data, dp1.ctypes.data, host.ctypes.data, None) == INVALID_OPTIONS
         same(e.history(), F2, "H after refused calls")
+        # an update that changes the size while the history is live: there is none of the new size, on the way out and on the
+        # way back (the second time under the camera and the passes of acc2, which the lines below go on with)
+        for sized in (turned(scenes.feature_scene(width=40, height=24, spp=1), 2.0), moved):
+            assert e.history().shape != (sized.height, sized.width, 4), "a history of the other size is live"
+            e.update(RenderConfig(uniforms=Change.update(sized.uniforms)))
+            with pytest.raises(RenderError) as ei:
+                e.history()
+            assert ei.value.code == NOT_INITIALIZED
+            e.clear()
+            passes(e, 0, 1)
+            assert np.array_equal(bits(e.denoise_history(linear=True)), bits(e.denoise(linear=True)))
+            acc = e.read_accumulation()
+            assert acc.shape == (sized.height, sized.width, 4)
+            same(e.history(), temporal.frame_records(acc), "F after a size change with a live history")
+            assert (e.history()[..., 3] == 1).all()
+        passes(e, 1, 1)
+        assert np.array_equal(bits(e.read_accumulation()), bits(acc2))
         # rb_history_reset: no history, rb_denoise's bits again
         e.history_reset()
         with pytest.raises(RenderError):

@@ -4,6 +4,12 @@ and the builders' bookkeeping, and -- where no kept count cuts a buffer short --
 fresh engine that received the merged scene in one Create.  tests/test_update_model.py shows on the oracle alone that every
 accepted step of these scripts changes what is seen, so an engine that ignored an update cannot pass.
 
+What the frame does not show is held as well.  The emitter table equals direct.scene_emitters under
+the counts in force in every byte after every step, cut short or refused or not, and rb_direct_light on the scene's own
+surfels equals the fold of the model in every word; which of the two is the first use after the update alternates.
+test_caches_sequence adds the frame history (section 22.2): rb_denoise_history after every step against temporal.py and
+denoise.py, through small camera moves, refused updates, a size change and back, and geometry steps.
+
 A failure names (configuration, step index, step name) and what differed: the field the step sent and the structure that is
 derived from it (prepared triangles, is_metal / fuzz, sph_scan, a tree, tex_info, a count) is where to look in apply_field,
 update_fields, ensure_prepared and accel_params."""
@@ -13,10 +19,11 @@ import functools
 import numpy as np
 import pytest
 
-from renderbaby_amd import Engine, RenderConfig, RenderError, abi, bvh
+from renderbaby_amd import Engine, RenderConfig, RenderError, abi, aov, bvh, denoise, direct, engine, temporal
 from renderbaby_amd.engine import Change
 from tests import _oracle
 from tests import _update_model as M
+from tests.test_gpu_direct import model_sums
 from tests.test_gpu_query import pixel_centre_rays
 
 pytestmark = pytest.mark.gpu
@@ -39,22 +46,39 @@ CONFIGS = {
     "build_tree_host": (dict(build_tree="host"), False, True),
 }
 SCRIPTS = {"fixed": None, "random1": 1, "random2": 2, "random3": 3}
+CACHES_CONFIGS = ["default", "reference_walk", "fast_bvh", "sphere_tree_device", "kernel_queue", "build_tree_device", "build_tree_host"]
+N_SURFELS = 130   # two blocks of 64 surfels and a part
+SAMPLES, FIRST_SAMPLE = 4, 3
 
 
 def _u32(a):
     return np.ascontiguousarray(a).view(np.uint32)
 
 
+def _bytes(a):
+    return np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+
+
+def script_names(script, own_tree):
+    if script == "caches":
+        return M.caches_script(own_tree)
+    return M.fixed_script(own_tree) if script == "fixed" else M.random_script(SCRIPTS[script], 10, own_tree)
+
+
 # ------------------------------------------------------------------ the reference ---
 @functools.lru_cache(maxsize=None)
 def reference(script, large, own_tree):
     """The model over a script, once for every engine that runs it: the first scene, then per step
-    dict(name, rc, refused, scene, kept, acc, rgba, segments) -- the oracle's frame of the scene the model holds after the step."""
-    names = M.fixed_script(own_tree) if script == "fixed" else M.random_script(SCRIPTS[script], 10, own_tree)
+    dict(name, rc, refused, scene, kept, acc, rgba, segments, table) -- the oracle's frame of the scene the model holds after the
+    step, and the model's emitter table (direct.scene_emitters) under the counts in force."""
+    names = script_names(script, own_tree)
 
     def rendered(model, **more):
         acc, _, rgba, st = _oracle.render(model.scene, counts_kept=model.kept)
-        return dict(scene=model.scene, kept=model.kept, acc=_u32(acc), rgba=rgba, segments=st["segments"], **more)
+        n_spheres, _, n_triangles = M.effective_counts(model.scene, model.kept)
+        table = direct.scene_emitters(model.scene, triangle_count=n_triangles, spheres_count=n_spheres)
+        table.flags.writeable = False
+        return dict(scene=model.scene, kept=model.kept, acc=_u32(acc), rgba=rgba, segments=st["segments"], table=table, **more)
 
     first = M.Model(bvh.build_canonical if own_tree else None)
     rc0 = M.create_config(M.base_scene(large), with_tree=not own_tree)
@@ -120,8 +144,9 @@ def nothing_cut_short(want):
     return M.effective_counts(s, want["kept"]) == (len(s.spheres), len(s.bvh_nodes), len(s.bvh_triangles))
 
 
-def queries(eng, scene, render_first):
-    """{name: uint32 words} of the queries and bakes over the frame's pixel-centre rays"""
+def queries(eng, scene, render_first, surfels=None):
+    """{name: uint32 words} of the queries and bakes over the frame's pixel-centre rays; `surfels`: the (points, normals) direct
+    light is asked for at, by default this engine's own scene_surfels"""
     O, D = pixel_centre_rays(scene)
     O, D = O.reshape(-1, 3), D.reshape(-1, 3)
     out = {}
@@ -136,50 +161,173 @@ def queries(eng, scene, render_first):
     out["lightmap surfels"], out["lightmap owners"] = _u32(s), _u32(owners)
     if render_first:
         eng.render_current()
+    out["trace_form"] = np.array([eng.trace_form()], np.uint32)      # (a fresh engine derives its facts from one Create)
     out["denoise_guides"] = _u32(eng.denoise_guides())
+    out["scene_emitters"] = _bytes(eng.scene_emitters())
+    pts, nrm = scene_surfels(eng, scene) if surfels is None else surfels
+    if len(pts):
+        out["direct_light"] = _u32(eng.direct_light(pts, nrm, SAMPLES, first_sample=FIRST_SAMPLE))
     return out
 
 
-def check_against_fresh(eng, kw, own_tree, want, where, render_first=True):
-    """the long-lived engine's queries word for word against an engine that was just created on the merged scene"""
+def scene_surfels(eng, scene, m=N_SURFELS):
+    """tests/test_gpu_hemisphere.py's scene_surfels -- the first m hit points of the pixel-centre rays, their normals turned
+    towards the camera -- for a scene that may show fewer than m: then what there is"""
+    _, pts, nrm = aov.ambient_occlusion_surfels(scene.uniforms, eng.render_hits())
+    return np.ascontiguousarray(pts[:m]), np.ascontiguousarray(nrm[:m])
+
+
+def check_emitters(eng, want, where, sums_first, sums=True):
+    """The engine's emitter table against the model's in every byte, and the sums of rb_direct_light on the scene's own surfels
+    against direct.fold of the model's contributions under the engine's own any-hit bytes, in every word; `sums_first`: which of
+    the two is the first use of the table after the update; without `sums` the table alone.  Returns the surfels, or None."""
+    table = want["table"]
+
+    def check_table():
+        got = eng.scene_emitters()
+        assert got.shape == table.shape and np.array_equal(_bytes(got), _bytes(table)), \
+            (where, "emitter table differs from the model's", len(got), len(table), M.effective_counts(want["scene"], want["kept"]))
+
+    def check_sums():
+        pts, nrm = scene_surfels(eng, want["scene"])
+        if len(pts):
+            got = eng.direct_light(pts, nrm, SAMPLES, first_sample=FIRST_SAMPLE)
+            model = model_sums(eng, table, pts, nrm, SAMPLES, FIRST_SAMPLE, None, abi.MASK_ALL)[0]
+            bad = np.nonzero((_u32(got).reshape(-1, 4) != _u32(model).reshape(-1, 4)).any(1))[0]
+            assert len(bad) == 0, (where, "direct light differs from the fold of the model", len(bad), bad[:5], got[bad[:5]], model[bad[:5]])
+        return pts, nrm
+    if not sums:
+        check_table()
+        return None
+    if sums_first:
+        surfels = check_sums()
+        check_table()
+    else:
+        check_table()
+        surfels = check_sums()
+    return surfels
+
+
+class HistoryChain:
+    """rb_denoise_history across the steps of one engine's life against temporal.py and denoise.py, on
+    uint32 views with nothing left out.  `previous` is (F, guides, view) of the last accepted step, None before the first."""
+
+    def __init__(self, eng):
+        self.eng, self.previous = eng, None
+        self.rp, self.dp = temporal.default_params(), denoise.default_params()
+        self.shares, self.geometry = [], []     # (step, name, share of records that carry history), (step, name, carried, rejected)
+        self.size_changes = self.refusals = self.plain_first = 0
+
+    @staticmethod
+    def same(got, want, where, what):
+        bad = np.argwhere((_u32(got) != _u32(want)).any(-1))
+        assert got.shape == want.shape and len(bad) == 0, (where, what, len(bad), bad[:4], [got[tuple(b)] for b in bad[:4]], [want[tuple(b)] for b in bad[:4]])
+
+    def size_changed(self, where):
+        """an accepted update to another size stands between the history and the next call: there is none to read"""
+        with pytest.raises(RenderError):
+            self.eng.history()
+        assert self.previous is not None, (where, "the size changed without a live history")
+        self.size_changes += 1
+
+    def refused(self, where):
+        """a refused update changed nothing: the base stayed valid and the call gives the previous step's F again"""
+        self.eng.denoise_history(linear=True)
+        self.same(self.eng.history(), self.previous[0], where, "F after a refused update")
+        self.refusals += 1
+
+    def accepted(self, scene, where, name, plain_first=False):
+        eng = self.eng
+        if plain_first:
+            eng.denoise()                       # the guides are built, and the plane set flipped, by the other entry
+            self.plain_first += 1
+        out = eng.denoise_history(linear=True)
+        F, g, acc = eng.history(), eng.denoise_guides(), eng.read_accumulation()
+        view = engine.view_from_camera(scene.uniforms)
+        cur = temporal.frame_records(acc)
+        carried = self.previous is not None and self.previous[0].shape == F.shape
+        if carried:
+            Fp, gp, vp = self.previous
+            want = temporal.merge(temporal.reproject(Fp, gp, vp, g, self.rp), g, cur)
+        else:
+            want = cur
+        self.same(F, want, where, "F differs from the model's" + ("" if carried else " (no history of this size)"))
+        self.same(out, denoise.filter(F, g, self.dp), where, "the filtered frame")
+        self.same(eng.denoise_history(linear=True), out, where, "a second call's filtered frame")
+        self.same(eng.history(), F, where, "a second call in the same step moved F")
+        has = F[..., 3] > acc[..., 3]
+        if name == "uniforms_camera_small":
+            self.shares.append((where[1], name, float(has.mean())))
+        if name.startswith(("triangles_", "own_triangles_")):
+            self.geometry.append((where[1], name, int(has.sum()), int(((g["cls"] != 0) & ~has).sum())))
+        self.previous = (F, g, view)
+
+    def conditions(self, config):
+        """what keeps the chain from passing vacuously"""
+        print(config, "share of records with history after uniforms_camera_small:", self.shares, "geometry steps (carried, rejected):", self.geometry)
+        assert self.shares and all(share >= 0.3 for _, _, share in self.shares), (config, self.shares)
+        assert any(c > 0 and r > 0 for _, _, c, r in self.geometry), (config, self.geometry)
+        assert (self.size_changes, self.refusals, self.plain_first) == (2, 2, 1), (config, self.size_changes, self.refusals, self.plain_first)
+
+
+def check_against_fresh(eng, kw, own_tree, want, where, render_first=True, surfels=None):
+    """the long-lived engine's queries word for word against an engine that was just created on the merged scene; both are asked
+    for direct light at the same surfels, the long-lived engine's"""
     scene = want["scene"]
+    if surfels is None:
+        surfels = scene_surfels(eng, scene)
     rc = M.create_config(scene, with_tree=not own_tree)
     fresh = Engine.new(rc, device=0, **kw)
     try:
         fresh.update(rc)
-        b = queries(fresh, scene, True)
+        b = queries(fresh, scene, True, surfels)
     finally:
         fresh.close()
-    a = queries(eng, scene, render_first)
+    a = queries(eng, scene, render_first, surfels)
     for name in b:
         assert a[name].shape == b[name].shape and np.array_equal(a[name], b[name]), (where, name, "differs from a fresh engine's: the update left something stale")
 
 
-def run_sequence(config, script):
+def run_sequence(config, script, history=False, sums_every=1):
+    """`history`: rb_denoise_history is called after every step's frame and held to the model (HistoryChain); `sums_every`: the
+    direct-light sums are held to the model at every step, or at every second one (the table at every step either way)"""
     kw, large, own_tree = CONFIGS[config]
     steps = reference(script, large, own_tree)
     eng = Engine.new(steps[0]["rc"], device=0, stats=True, **kw)
     seen = {}
     try:
-        last = None
+        last = last_name = None
+        chain = HistoryChain(eng) if history else None
         for i, st in enumerate(steps):
             where = (config, i - 1, st["name"])
             if st["refused"] is not None:
                 with pytest.raises(RenderError):
                     eng.update(st["rc"])
                 assert st["acc"] is last["acc"] or np.array_equal(st["acc"], last["acc"])      # the model did not move either
+                assert np.array_equal(_bytes(st["table"]), _bytes(last["table"]))
             else:
                 eng.update(st["rc"])
+                if chain and last is not None and st["rgba"].shape != last["rgba"].shape:
+                    chain.size_changed(where)
             check_frame(eng, st, where)
+            if chain and st["refused"] is not None:
+                chain.refused(where)
+            elif chain:   # the second of two small camera moves in a row: rb_denoise builds the guides
+                chain.accepted(st["scene"], where, st["name"], plain_first=st["name"] == last_name == "uniforms_camera_small")
             got = check_bookkeeping(eng, kw, st, where)
+            # every step, cut short or not, refused or not; which call is the first use of the table alternates
+            surfels = check_emitters(eng, st, where, sums_first=(i // sums_every) % 2 == 0, sums=i % sums_every == 0)
             if st["refused"] is None:
                 if nothing_cut_short(st):
-                    check_against_fresh(eng, kw, own_tree, st, where)
+                    check_against_fresh(eng, kw, own_tree, st, where, surfels=surfels)
                 last = st
+            last_name = st["name"]
             s = st["scene"]
             seen.setdefault(got, set()).add((len(s.spheres), len(s.bvh_triangles)))
         if large:   # the device builders of the library's own tree were what ran where the config asked for them
             assert any(own.startswith("device-") for _, _, own, _ in seen), (config, seen)
+        if chain:
+            chain.conditions(config)
     finally:
         eng.close()
     return len(steps) - 1, seen
@@ -188,7 +336,15 @@ def run_sequence(config, script):
 @pytest.mark.parametrize("script", sorted(SCRIPTS))
 @pytest.mark.parametrize("config", sorted(CONFIGS))
 def test_update_sequence(config, script):
-    run_sequence(config, script)
+    run_sequence(config, script, sums_every=2)   # (the sums at every step cost some of these cases half again their time)
+
+
+@pytest.mark.parametrize("config", CACHES_CONFIGS)
+def test_caches_sequence(config):
+    """M.caches_script: the emitter table through emissive spheres, kept counts, dark lights and the colour hash, and the frame
+    history through small camera moves, refused updates, a size change and back, and a geometry step
+    (tests/test_update_model.py holds the script to what it must show)."""
+    run_sequence(config, "caches", history=True)
 
 
 # ------------------------------------------------- updates between iterator frames ---

@@ -1,27 +1,30 @@
 """tests/_update_model.py on the CPU: the model against a reading of gpu_wrapper.rs on hand-written sequences, and the
 condition that keeps tests/test_gpu_update_sequences.py honest -- every accepted step of every script it runs changes what
-the ORACLE sees, so that an engine which ignored the update could not pass.  No device."""
+the ORACLE sees, so that an engine which ignored the update could not pass.  For the caches script, whose subject the frame
+does not show, the conditions are on the model's emitter table (renderbaby_amd/direct.py) as well.  No device."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
-from renderbaby_amd import bvh, scenes
+from renderbaby_amd import abi, bvh, direct, scenes
 from renderbaby_amd.engine import Change, RenderConfig
 from tests import _oracle
 from tests import _update_model as M
 
 f32 = np.float32
-SCRIPTS = [("fixed", None), ("random", 1), ("random", 2), ("random", 3)]
+SCRIPTS = [("fixed", None), ("random", 1), ("random", 2), ("random", 3), ("caches", None)]
 VARIANTS = {"caller": dict(own_tree=False, large=False), "caller-large": dict(own_tree=False, large=True), "own": dict(own_tree=True, large=False)}
 
 
 def script_names(kind, seed, own_tree):
+    if kind == "caches":
+        return M.caches_script(own_tree)
     return M.fixed_script(own_tree) if kind == "fixed" else M.random_script(seed, 10, own_tree)
 
 
 def script_id(kind, seed):
-    return "fixed" if kind == "fixed" else f"random{seed}"
+    return kind if kind in ("fixed", "caches") else f"random{seed}"
 
 
 # ------------------------------------------------------- the model, rule by rule ---
@@ -219,7 +222,10 @@ def test_random_scripts_are_legal_and_reach_every_kind():
             drawn |= set(names)
         assert len(drawn) >= 15
     assert not set(M.LEGAL[True]) & {"tree_swap", "tree_create_taken", "indices_reverse_leaves", "nodes_cyclic", "nodes_leaf_past_indices"}
-    assert set(M.fixed_script(False)) | set(M.fixed_script(True)) == set(M.STEPS)   # the fixed script runs every step there is
+    caches_only = {f.__name__ for f in M._CACHES_ONLY}
+    assert set(M.fixed_script(False)) | set(M.fixed_script(True)) == set(M.STEPS) - caches_only   # the fixed script runs every step there is ...
+    assert caches_only <= set(M.caches_script(False)) and caches_only <= set(M.caches_script(True))   # ... but the caches script's own
+    assert not caches_only & (set(M.LEGAL[False]) | set(M.LEGAL[True]))
 
 
 def test_a_kept_count_above_the_buffer_is_the_buffers_length_for_the_oracle():
@@ -231,3 +237,110 @@ def test_a_kept_count_above_the_buffer_is_the_buffers_length_for_the_oracle():
     u["spheres_count"], u["bvh_node_count"], u["bvh_triangle_count"] = len(s.spheres) + 7, len(s.bvh_nodes) + 3, len(s.bvh_triangles) + 100
     assert m.apply(RenderConfig(uniforms=Change.update(u))) is None and m.kept == 7
     assert np.array_equal(_oracle.render(m.scene, counts_kept=7)[0].view(np.uint32), _oracle.render(s)[0].view(np.uint32))
+
+
+# ------------------------------------------- the caches script: what it must show ---
+def model_table(scene, kept, **counts):
+    """direct.scene_emitters of the model's scene under the counts in force (`counts` overrides one of them)"""
+    ns, _, nt = M.effective_counts(scene, kept)
+    kw = dict(triangle_count=nt, spheres_count=ns)
+    kw.update(counts)
+    return direct.scene_emitters(scene, **kw)
+
+
+def _prims(table, kind):
+    return set(int(p) for p in table["prim"][table["kind"] == kind])
+
+
+@pytest.mark.parametrize("own_tree", [False, True], ids=["caller", "own"])
+def test_caches_script_moves_the_emitter_table(own_tree):
+    """Conditions on tests/test_gpu_update_sequences.py::test_caches_sequence's input, from the model and direct.py alone: the
+    table takes every kind, changes often, changes under counts that are cut short, loses emitters to a kept count alone, loses
+    its triangles to the colour hash, and stands across every refused step."""
+    names = M.caches_script(own_tree)
+    first = M.Model(bvh.build_canonical if own_tree else None)
+    first.apply(M.create_config(M.base_scene(), with_tree=not own_tree))
+    prev, prev_scene = model_table(first.scene, first.kept), first.scene
+    all_kinds = changes = changes_cut_short = sphere_by_count = triangle_by_count = emptied_by_hash = refused = 0
+    for i, name, rc, why, model in M.run_script(names, "caches", own_tree=own_tree, tree_builder=bvh.build_canonical):
+        s, kept = model.scene, model.kept
+        now = model_table(s, kept)
+        if why is not None:
+            refused += 1
+            assert s is prev_scene and now.tobytes() == prev.tobytes(), (i, name)
+            continue
+        ns, _, nt = M.effective_counts(s, kept)
+        all_kinds += set(int(k) for k in now["kind"]) == {abi.HIT_TRIANGLE, abi.HIT_SPHERE, abi.HIT_LIGHT}
+        if now.tobytes() != prev.tobytes():
+            changes += 1
+            changes_cut_short += (ns, nt) != (len(s.spheres), len(s.bvh_triangles))
+        uniforms_only = all(getattr(rc, f).tag == abi.KEEP for f in M.FIELDS[1:])
+        lost_s = _prims(prev, abi.HIT_SPHERE) - _prims(now, abi.HIT_SPHERE)
+        lost_t = _prims(prev, abi.HIT_TRIANGLE) - _prims(now, abi.HIT_TRIANGLE)
+        # "alone": the step sent the uniforms only, and with the whole buffer counted the emitter would still be there
+        if uniforms_only and lost_s and lost_s <= _prims(model_table(s, kept, spheres_count=None), abi.HIT_SPHERE):
+            assert min(lost_s) >= ns
+            sphere_by_count += 1
+        if uniforms_only and lost_t and lost_t <= _prims(model_table(s, kept, triangle_count=None), abi.HIT_TRIANGLE):
+            assert min(lost_t) >= nt
+            triangle_by_count += 1
+        if uniforms_only and lost_t and not _prims(now, abi.HIT_TRIANGLE) and int(s.uniforms["color_hash_enabled"][0]) \
+                and int(prev_scene.uniforms["color_hash_enabled"][0]) == 0 and nt == len(s.bvh_triangles):
+            emptied_by_hash += 1
+        prev, prev_scene = now, s
+    got = dict(all_kinds=all_kinds, changes=changes, changes_cut_short=changes_cut_short, sphere_by_count=sphere_by_count,
+               triangle_by_count=triangle_by_count, emptied_by_hash=emptied_by_hash, refused=refused)
+    print(got)
+    assert all_kinds >= 1 and changes >= 12 and changes_cut_short >= 2, got
+    assert sphere_by_count >= 1 and triangle_by_count >= 1 and emptied_by_hash >= 1 and refused >= 2, got
+
+
+def test_caches_script_has_the_steps_in_the_places_the_history_chain_needs():
+    for own in (False, True):
+        names = M.caches_script(own)
+        assert 20 <= len(names) <= 28
+        assert {"spheres_emissive", "uniforms_spheres_below", "uniforms_counts_above", "spheres_65", "spheres_emissive_edge", "spheres_moved",
+                "create_spheres_shorter", "spheres_delete", "lights_one_dark", "lights_none", "lights_more", "uniforms_triangles_below",
+                "triangles_permute_meshes", "triangles_shrink"} <= set(names)
+        pairs = list(zip(names, names[1:]))
+        assert names.count("uniforms_color_hash") == 2
+        on, off = (i for i, n in enumerate(names) if n == "uniforms_color_hash")
+        assert off - on >= 2                                             # a step, and with it a table query, between on and off
+        assert any(b in M.REFUSED for a, b in pairs if a == "spheres_emissive")                       # refused after a table change
+        assert any(b in M.REFUSED for a, b in pairs if a == "uniforms_camera_small")                  # refused after a camera move
+        assert ("uniforms_camera_small", "uniforms_camera_small") in pairs
+        k = names.index("uniforms_resolution")
+        assert k > 0 and names[k + 1:k + 3] == ["uniforms_camera_small", "uniforms_resolution"]
+        assert any(n.startswith(("triangles_", "own_triangles_")) for n in names[1:-1])
+
+
+def test_the_scripts_that_existed_are_unchanged():
+    """the fixed and the random scripts, step for step, as they stood before the caches steps were added"""
+    materials = ["meshes_swap_metal", "meshes_shininess", "meshes_too_short", "meshes_texture_none", "meshes_texture_valid", "uvs_new_values",
+                 "uvs_odd", "meshes_texture_past_end", "meshes_swap_metal", "meshes_texture_valid", "textures_other", "textures_empty",
+                 "uvs_shorter", "textures_none", "textures_other", "lights_more", "lights_fewer", "lights_none", "create_ignored", "lights_more"]
+    spheres = ["spheres_64", "spheres_65", "uniforms_spheres_below", "spheres_64", "spheres_moved", "spheres_empty", "spheres_delete",
+               "spheres_70", "create_spheres_shorter", "uniforms_resolution", "uniforms_color_hash", "uniforms_camera", "uniforms_nodes_below",
+               "uniforms_triangles_below", "uniforms_all_below", "uniforms_counts_above", "uniforms_color_hash", "uniforms_resolution",
+               "spheres_40"]
+    assert M.fixed_script(False) == materials + spheres + [
+        "triangles_shrink", "nodes_cyclic", "triangles_permute_meshes", "triangles_bad_mesh", "tree_swap", "nodes_leaf_past_indices",
+        "indices_reverse_leaves", "triangles_create_taken", "tree_create_taken", "uvs_new_values", "indices_reverse_leaves", "tree_swap"]
+    assert M.fixed_script(True) == materials + spheres + [
+        "triangles_shrink", "own_with_nodes", "own_triangles_100", "triangles_permute_meshes", "own_triangles_128", "triangles_bad_mesh",
+        "own_triangles_129", "uniforms_nodes_below", "own_triangles_delete", "own_triangles_578", "triangles_create_taken", "uvs_new_values"]
+    assert M.random_script(1, 10, False) == ["spheres_empty", "spheres_delete", "uniforms_nodes_below", "indices_reverse_leaves", "meshes_shininess",
+                                             "meshes_too_short", "uniforms_counts_above", "indices_reverse_leaves", "lights_more",
+                                             "create_spheres_shorter"]
+    assert M.random_script(1, 10, True) == ["spheres_empty", "spheres_moved", "uniforms_triangles_below", "own_triangles_578", "meshes_shininess",
+                                            "create_ignored", "own_triangles_578", "lights_fewer", "own_triangles_100", "spheres_65"]
+    assert M.random_script(2, 10, False) == ["create_ignored", "textures_none", "lights_more", "spheres_64", "uniforms_counts_above", "spheres_70",
+                                             "lights_fewer", "triangles_bad_mesh", "uniforms_counts_above", "uniforms_spheres_below"]
+    assert M.random_script(2, 10, True) == ["create_spheres_shorter", "textures_none", "lights_more", "spheres_65", "create_ignored", "spheres_70",
+                                            "lights_none", "triangles_create_taken", "create_ignored", "uniforms_nodes_below"]
+    assert M.random_script(3, 10, False) == ["uniforms_counts_above", "meshes_texture_valid", "uvs_shorter", "textures_other", "uvs_shorter",
+                                             "uniforms_all_below", "create_spheres_shorter", "triangles_permute_meshes", "meshes_shininess",
+                                             "meshes_texture_valid"]
+    assert M.random_script(3, 10, True) == ["create_ignored", "meshes_texture_valid", "uvs_shorter", "textures_other", "uvs_shorter",
+                                            "uniforms_counts_above", "own_triangles_100", "triangles_bad_mesh", "meshes_shininess",
+                                            "meshes_texture_valid"]
