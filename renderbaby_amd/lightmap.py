@@ -1,6 +1,7 @@
 """The numpy model of the device's lightmap stages (csrc/rb_lightmap.hip): the same binary32 operations
 in the same order, so ``owners`` / ``surfels`` equal ``rb_lightmap_surfels`` and ``resolve`` equals ``rb_lightmap_resolve`` bit
-for bit.
+for bit.  (Where the arithmetic makes a NaN -- a surfel past the finite range, a quotient of the resolve -- its sign and payload are
+numpy's here and the device's there: section 17.1.)
 
 ``prepare``      what the engine's upload makes of a triangle: v0, e1, e2 and the normal the walks report
 ``texel_space``  the corners A, B, C of every triangle in texels, row 0 on top
@@ -23,8 +24,8 @@ def prepare(tris):
     """(v0, e1, e2, n), each (m, 3) float32: e1 = v1 - v0, e2 = v2 - v0, n = normalize(cross(e1, e2)) (k_prep_tris)"""
     t = np.asarray(tris, dtype=abi.GPU_TRIANGLE).reshape(-1)
     v0 = t["v0"].astype(f32)
-    e1, e2 = (t["v1"] - v0).astype(f32), (t["v2"] - v0).astype(f32)
     with np.errstate(all="ignore"):
+        e1, e2 = (t["v1"] - v0).astype(f32), (t["v2"] - v0).astype(f32)
         c = np.stack([((e1[:, 1] * e2[:, 2]).astype(f32) - (e1[:, 2] * e2[:, 1]).astype(f32)).astype(f32),
                       ((e1[:, 2] * e2[:, 0]).astype(f32) - (e1[:, 0] * e2[:, 2]).astype(f32)).astype(f32),
                       ((e1[:, 0] * e2[:, 1]).astype(f32) - (e1[:, 1] * e2[:, 0]).astype(f32)).astype(f32)], axis=1)
@@ -170,7 +171,8 @@ def resolve(sums, width, height, dilate=0):
         for dx, dy in NEIGHBOURS:
             q = pad[1 + dy:1 + dy + height, 1 + dx:1 + dx + width]
             live = q[..., 3] != 0
-            acc = np.where(live[..., None], (acc + q[..., :3]).astype(f32), acc)
+            with np.errstate(all="ignore"):
+                acc = np.where(live[..., None], (acc + q[..., :3]).astype(f32), acc)
             cnt += live
         fill = (prev[..., 3] == 0) & (cnt > 0)
         out = prev.copy()

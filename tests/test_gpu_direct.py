@@ -43,6 +43,21 @@ def lamps():
     return scenes.Scene(s.uniforms, sp, s.lights, s.meshes, s.bvh_nodes, s.bvh_indices, s.bvh_triangles, s.uvs, name="lamps")
 
 
+def long_table():
+    """20 003 candidates, five blocks of the table's 32-bit scan (4096 flags a block on gfx950: 256 threads of 16 items,
+    rocPRIM's default_scan_config_base): the 1 % of emissive spheres the scene draws for itself, emission set on the spheres 0, 1,
+    4095, 4096, 4097, 9999 and 19999 -- the ends of the list and either side of the first block edge --, and after the spheres
+    three lights of which the middle one is dark"""
+    s = scenes.spheres_scene(n=20000, width=24, height=16, spp=1, max_depth=4, extent=40.0)
+    sp = s.spheres.copy()
+    for k in (0, 1, 4095, 4096, 4097, 9999, 19999):
+        sp["material"]["emissive"][k] = (3.0 + k, 2.0, 1.0)
+    lights = np.zeros(3, dtype=abi.POINT_LIGHT)
+    lights["center"], lights["radius"] = [(-30.0, 40.0, 0.0), (0.0, 45.0, 5.0), (30.0, 40.0, -5.0)], (1.0, 2.0, 0.5)
+    lights["material"]["emissive"] = [(50.0, 40.0, 30.0), (0.0, 0.0, 0.0), (10.0, 20.0, 30.0)]
+    return scenes.Scene(s.uniforms, sp, lights, s.meshes, s.bvh_nodes, s.bvh_indices, s.bvh_triangles, s.uvs, name="long table")
+
+
 def mixed_surfels(e, scene):
     """130 hit points of the scene with model_surfels' special ones -- the invalid ones among them -- mixed in"""
     pts, nrm = scene_surfels(e, scene, M)
@@ -54,7 +69,7 @@ def mixed_surfels(e, scene):
 
 # ---- 1. the table
 TABLE_SCENES = {"feature": lambda: scenes.feature_scene(width=24, height=16), "feature, colour hash": lambda: scenes.feature_scene(width=24, height=16, color_hash=1),
-                "cornell": lambda: scenes.cornell(32, 32, 1, 4), "no emitter": scenes.sky_only, "mesh": _mesh, "lamps": lamps}
+                "cornell": lambda: scenes.cornell(32, 32, 1, 4), "no emitter": scenes.sky_only, "mesh": _mesh, "lamps": lamps, "long table": long_table}
 
 
 @pytest.mark.parametrize("name", list(TABLE_SCENES))
