@@ -13,7 +13,7 @@ NUMERICS := -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -fno-fast
 HIPFLAGS := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) $(NUMERICS) -fno-slp-vectorize -Wall -Wno-unused-function
 SRCS     := $(CSRC)/rb_kernels.hip $(CSRC)/rb_debug.hip $(CSRC)/rb_query.hip $(CSRC)/rb_denoise.hip $(CSRC)/rb_reproject.hip $(CSRC)/rb_radiance.hip $(CSRC)/rb_camera.hip $(CSRC)/rb_hemisphere.hip $(CSRC)/rb_probe.hip $(CSRC)/rb_probe_light.hip $(CSRC)/rb_probe_depth.hip $(CSRC)/rb_probe_visibility.hip $(CSRC)/rb_lightmap.hip $(CSRC)/rb_direct.hip $(CSRC)/rb_build.hip $(CSRC)/rb_runtime.cpp $(CSRC)/rb_queries.cpp $(CSRC)/rb_frame.cpp $(CSRC)/rb_accel.cpp $(CSRC)/rb_bvh.cpp $(CSRC)/rb_rccl.cpp
 HDRS     := $(CSRC)/rb_internal.hpp $(CSRC)/rb_device_common.hpp $(CSRC)/rb_device_math.hpp $(CSRC)/rb_device_sincos.hpp $(CSRC)/rb_device_sh.hpp $(CSRC)/rb_device_probe.hpp \
-            $(CSRC)/rb_device_intersect.hpp $(CSRC)/rb_device_shade.hpp $(CSRC)/rb_device_chunk.hpp $(CSRC)/rb_device_centre.hpp $(CSRC)/rb_host_cam.hpp $(CSRC)/rb_rccl.hpp $(CSRC)/rb_chunk_math.hpp $(CSRC)/rb_engine.hpp $(CSRC)/rb_stage_timer.hpp $(CSRC)/rb_queries.hpp $(CSRC)/rb_color_plan.hpp $(CSRC)/rb_launch_plan.hpp $(CSRC)/rb_update_plan.hpp include/rb_abi.h
+            $(CSRC)/rb_device_intersect.hpp $(CSRC)/rb_device_shade.hpp $(CSRC)/rb_device_chunk.hpp $(CSRC)/rb_device_centre.hpp $(CSRC)/rb_host_cam.hpp $(CSRC)/rb_rccl.hpp $(CSRC)/rb_chunk_math.hpp $(CSRC)/rb_engine.hpp $(CSRC)/rb_stage_timer.hpp $(CSRC)/rb_queries.hpp $(CSRC)/rb_color_plan.hpp $(CSRC)/rb_launch_plan.hpp $(CSRC)/rb_update_plan.hpp $(CSRC)/rb_tri_filter.hpp include/rb_abi.h
 OBJS     := $(patsubst $(CSRC)/%,build/obj/%.o,$(SRCS))
 
 all: $(OUT) oracle

@@ -562,6 +562,15 @@ int rb_debug_triangle_trip(uint32_t n, uint32_t seed, uint32_t* out32);
 /* Test hook: the same sweep for the trip of the flat kernels (rb_debug_trace_form), which carries {t, slot} only: those two
  * words against the compiler-laid form's, bit for bit.  out32 as above (the u, v words repeat the compiler-laid form's). */
 int rb_debug_triangle_trip_flat(uint32_t n, uint32_t seed, uint32_t* out32);
+/* Test hook: the same sweep for the trip of the triangle sift's second pass (RB_TRACE_FORM_SIFT), which takes the triangle's record
+ * per lane; uv = 0: the form that carries {t, slot}, else the one with u, v.  out32 as above. */
+int rb_debug_triangle_trip_vec(uint32_t n, uint32_t seed, uint32_t uv, uint32_t* out32);
+/* Test hook: the first pass of the triangle sift on `n` (at most 2^22) rays of six floats {origin, direction}, with the table of
+ * the engine's single node and the origin region of its current camera and spheres: out[4 i + b] = ray i's candidate bits of
+ * block b of 32 slots (bit k: slot first + 32 b + k; 0 for a block the list does not have), list2 = {first, end} of the node's list.  Conservative: every slot whose
+ * triangle the reference's test accepts for the ray has its bit set.  RB_ERR_INVALID_OPTIONS if this engine's scene does not
+ * sift (more than one node, a list beyond 128 slots, fewer than 4 live triangles, nothing to reject, RB_TRI_FILTER=0). */
+int rb_debug_tri_filter(rb_engine* e, const float* rays, uint32_t n, uint32_t* out, uint32_t* list2);
 /* Test hook: the root box of the single-node walk on `n` (at most 2^24) rays of six floats {origin, direction} and the box
  * box6 = {bmin, bmax}: out[i] bit 0 = the walk's slab test on its own reciprocals, bit 1 = the rule by which the single-node
  * trace kernels go past that test says the answer is known to be true (origin strictly inside a finite box, no NaN in the
@@ -598,6 +607,9 @@ const char* rb_last_kernel_name(const rb_engine* e);
  * when an engine is made keeps it on the kernels that carry u, v, whatever the scene (A/B measurements, tests). */
 enum {
     RB_TRACE_FORM_FLAT = 1u,    /* k_trace_flat / k_trace_flat_direct */
+    RB_TRACE_FORM_SIFT = 2u,    /* with FLAT and STAGED: k_trace_sift, the single node's triangle list sifted by a conservative box test
+                                 * per group of triangles, the exact test on each lane's own survivors (same frames, bit for bit;
+                                 * RB_TRI_FILTER=0 in the environment when an engine is made keeps it on k_trace_flat) */
     RB_TRACE_FORM_BIG = 4u,     /* the 8-wave instantiation (large launches) */
     RB_TRACE_FORM_STAGED = 8u,  /* a row's paths started in one pass (else every lane starts its own) */
     RB_TRACE_FORM_MULTI = 16u   /* the per-segment ablation of a multi-node tree or a sphere tree */

@@ -69,6 +69,8 @@ SIGNATURES = {
     "rb_debug_rnd_pm1_exhaustive": (i32, [vp]),
     "rb_debug_triangle_trip": (i32, [u32, u32, vp]),
     "rb_debug_triangle_trip_flat": (i32, [u32, u32, vp]),
+    "rb_debug_triangle_trip_vec": (i32, [u32, u32, u32, vp]),
+    "rb_debug_tri_filter": (i32, [vp, vp, u32, vp, vp]),
     "rb_debug_trace_form": (u32, [vp]),
     "rb_debug_root_box": (i32, [vp, u32, vp, vp]),
     "rb_debug_normalize_sites": (i32, [vp, u32, u32, u32, u32, vp]),

@@ -145,6 +145,7 @@ RB_ERR_DEVICE = 16   # HIP runtime failure
 KERNEL_DEFAULT, KERNEL_PIXEL, KERNEL_QUEUE, KERNEL_STREAM = 0, 1, 2, 3
 # rb_debug_trace_form: which instantiation of "k_trace" ran
 TRACE_FORM_FLAT, TRACE_FORM_BIG, TRACE_FORM_STAGED, TRACE_FORM_MULTI = 1, 4, 8, 16
+TRACE_FORM_SIFT = 2
 FLAG_STATS = 1
 FLAG_NO_SPHERE_BVH = 2
 FLAG_FAST_BVH = 4

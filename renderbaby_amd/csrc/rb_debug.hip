@@ -170,8 +170,10 @@ DEV float trip_unit(uint32_t& s) {   // [-1, 1)
     return (float)(int32_t)s * 0x1p-31f;
 }
 // FLAT (rb_debug_triangle_trip_flat): the flat kernels' trip, accept_trip<.., UV = false>, whose {t, slot} must be accept_slot<true>'s.
-template <bool FLAT>
-__global__ void __launch_bounds__(256) k_triangle_trip(uint32_t n_waves, uint32_t seed, uint32_t* mismatch) {
+// VREC (rb_debug_triangle_trip_vec): the trip of the sift's pass 2, which takes the record and the slot in vector registers -- the
+// same triples, handed over per lane.
+template <bool FLAT, bool VREC>
+DEV void trip_sweep(uint32_t n_waves, uint32_t seed, uint32_t* mismatch) {
     const uint32_t wave = (blockIdx.x * 256u + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
     if (wave >= n_waves + kTripCases) return;
     f3 o, d, v0, e1, e2;
@@ -200,6 +202,9 @@ __global__ void __launch_bounds__(256) k_triangle_trip(uint32_t n_waves, uint32_
     const v4f ra = {uni(v0.x), uni(v0.y), uni(v0.z), 0.0f}, rb_ = {uni(e1.x), uni(e1.y), uni(e1.z), 0.0f},
               rc = {uni(e2.x), uni(e2.y), uni(e2.z), 1.0f};
     const uint32_t slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)(wave + 1u));
+    v4f va = {v0.x, v0.y, v0.z, 0.0f}, vb = {e1.x, e1.y, e1.z, 0.0f}, vc = {e2.x, e2.y, e2.z, 1.0f};
+    uint32_t vslot = wave + 1u;
+    if constexpr (VREC) asm volatile("" : "+v"(va.x), "+v"(va.y), "+v"(va.z), "+v"(vb.x), "+v"(vb.y), "+v"(vb.z), "+v"(vc.x), "+v"(vc.y), "+v"(vc.z), "+v"(vslot));
     if (wave >= n_waves) {
         TriHit own;
         own.t = 1e20f, own.u = 0.0f, own.v = 0.0f, own.slot = 0u, own.hit = false;
@@ -217,9 +222,11 @@ __global__ void __launch_bounds__(256) k_triangle_trip(uint32_t n_waves, uint32_
         if constexpr (FLAT && RB_TRIP_BLOCK) {
             TriHitT<false> flat;
             flat.t = got.t, flat.slot = got.slot, flat.hit = false;
-            accept_trip<RB_TRIP_ASM - 1, false>(ra, rb_, rc, slot, o, d, big, flat);
+            if constexpr (VREC) accept_trip<RB_TRIP_ASM - 1, false, true>(va, vb, vc, vslot, o, d, big, flat);
+            else accept_trip<RB_TRIP_ASM - 1, false>(ra, rb_, rc, slot, o, d, big, flat);
             got.t = flat.t, got.slot = flat.slot, got.u = want.u, got.v = want.v;   // no u, v to compare
-        } else if constexpr (RB_TRIP_BLOCK) accept_trip<RB_TRIP_ASM - 1>(ra, rb_, rc, slot, o, d, big, got);
+        } else if constexpr (RB_TRIP_BLOCK && VREC) accept_trip<RB_TRIP_ASM - 1, true, true>(va, vb, vc, vslot, o, d, big, got);
+        else if constexpr (RB_TRIP_BLOCK) accept_trip<RB_TRIP_ASM - 1>(ra, rb_, rc, slot, o, d, big, got);
         else accept_slot<true>(ra, rb_, rc, slot, o, d, got);
     }
     if (__float_as_uint(want.t) != __float_as_uint(got.t) || __float_as_uint(want.u) != __float_as_uint(got.u) ||
@@ -234,6 +241,31 @@ __global__ void __launch_bounds__(256) k_triangle_trip(uint32_t n_waves, uint32_
             mismatch[25] = want.slot;
         }
     }
+}
+
+template <bool FLAT>
+__global__ void __launch_bounds__(256) k_triangle_trip(uint32_t n_waves, uint32_t seed, uint32_t* mismatch) {
+    trip_sweep<FLAT, false>(n_waves, seed, mismatch);
+}
+template <bool FLAT>
+__global__ void __launch_bounds__(256) k_triangle_trip_vec(uint32_t n_waves, uint32_t seed, uint32_t* mismatch) {
+    trip_sweep<FLAT, true>(n_waves, seed, mismatch);
+}
+
+// Pass 1 of the triangle sift on the caller's rays (rb_debug_tri_filter): sift_ray and sift_block as k_trace_sift runs them, over
+// the list [first, end) of the node and the table and region in p.  out[4 i + b] = ray i's candidate bits of block b.
+__global__ void __launch_bounds__(256) k_tri_filter(const KParams p, const float* rays, uint32_t n, uint32_t first, uint32_t end, uint32_t* out) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const f3 o = mk(rays[i * 6u], rays[i * 6u + 1u], rays[i * 6u + 2u]), d = mk(rays[i * 6u + 3u], rays[i * 6u + 4u], rays[i * 6u + 5u]);
+    const SiftRay r = sift_ray(p, o, d);
+    uint32_t ends = p.sift_block_ends, g0 = 0u, b = 0u;
+    for (uint32_t base = first; base < end && b < 4u; base += 32u, ends >>= 8, b++) {
+        const uint32_t g1 = ends & 0xFFu;
+        out[i * 4u + b] = sift_block(p, r, d, g0, g1, (end - base < 32u) ? end - base : 32u);
+        g0 = g1;
+    }
+    for (; b < 4u; b++) out[i * 4u + b] = 0u;   // blocks the list does not have
 }
 
 // What the scalar unit sustains next to the vector units (rb_measure_salu_mix, tools/salu_mix.py):
@@ -492,6 +524,16 @@ double measure_l1_gather(size_t table_bytes, uint32_t rounds) {
     return best;
 }
 }  // namespace
+
+// rb_debug_tri_filter's device half (rb_runtime.cpp has the engine): n rays of six floats each, four mask words per ray out
+int debug_tri_filter(const KParams& p, const float* rays, uint32_t n, uint32_t first, uint32_t end, uint32_t* out) {
+    const size_t out_bytes = (size_t)n * 16u, in_bytes = (size_t)n * 24u;   // one buffer: the result words, then the rays
+    return round_trip(out, out_bytes, out_bytes + in_bytes, [&](uint32_t* d) {
+        float* dr = reinterpret_cast<float*>(d + (size_t)n * 4u);
+        (void)hipMemcpy(dr, rays, in_bytes, hipMemcpyHostToDevice);
+        hipLaunchKernelGGL(k_tri_filter, dim3((n + 255u) / 256u), dim3(256), 0, nullptr, p, dr, n, first, end, d);
+    });
+}
 }  // namespace rb
 
 extern "C" {
@@ -536,6 +578,18 @@ int rb_debug_triangle_trip_flat(uint32_t n, uint32_t seed, uint32_t* out32) {
     return rb::round_trip(out32, 128, 128, [&](uint32_t* d) {
         const uint32_t n_waves = (n + 63u) / 64u, waves = n_waves + rb::kTripCases;
         hipLaunchKernelGGL(rb::k_triangle_trip<true>, dim3((waves + 3u) / 4u), dim3(256), 0, nullptr, n_waves, seed, d);
+    });
+}
+
+// Test hook: the same sweep for the trip of the sift's pass 2 (k_trace_sift), which takes the record in vector registers; `uv`
+// nonzero: the form that carries u, v.  out32 as above.
+int rb_debug_triangle_trip_vec(uint32_t n, uint32_t seed, uint32_t uv, uint32_t* out32) {
+    if (!out32) return RB_ERR_NULL_ARGUMENT;
+    if (n > (1u << 26)) return RB_ERR_INVALID_OPTIONS;
+    return rb::round_trip(out32, 128, 128, [&](uint32_t* d) {
+        const uint32_t n_waves = (n + 63u) / 64u, waves = n_waves + rb::kTripCases;
+        if (uv) hipLaunchKernelGGL(rb::k_triangle_trip_vec<false>, dim3((waves + 3u) / 4u), dim3(256), 0, nullptr, n_waves, seed, d);
+        else hipLaunchKernelGGL(rb::k_triangle_trip_vec<true>, dim3((waves + 3u) / 4u), dim3(256), 0, nullptr, n_waves, seed, d);
     });
 }
 

@@ -269,7 +269,9 @@ DEV void accept_slot(const v4f a, const v4f b, const v4f c, uint32_t slot, f3 o,
 // turns into nothing, or touches only the block's own scalar temporaries).
 // SKIP: 1 = one branch over the rest of the trip when no lane passes the u test, 2 = another one after the v test.  big: 2^100 (the caller holds it in a scalar register).
 // UV = false: the accepted hit moves slot and t only (TriHitT<false>); every other instruction is the same in both forms.
-template <int SKIP, bool UV = true>
+// VREC = true (pass 2 of the triangle sift, sift_triangles below): the record and the slot are per-lane values in vector registers.
+// The instruction text is the same, so t (and u, v) are the same bits for the same triangle and ray.
+template <int SKIP, bool UV = true, bool VREC = false>
 DEV void accept_trip(const v4f a, const v4f b, const v4f c, uint32_t slot, f3 o, f3 d, float big, TriHitT<UV>& hit) {
     float r8, r10, r11, r12, r13, r14, r15, r16, r17;
     uint64_t entry, keep, m, ds;
@@ -363,13 +365,13 @@ DEV void accept_trip(const v4f a, const v4f b, const v4f c, uint32_t slot, f3 o,
     [r8] "=&v"(r8), [r10] "=&v"(r10),                                                                                     \
       [r11] "=&v"(r11), [r12] "=&v"(r12), [r13] "=&v"(r13), [r14] "=&v"(r14), [r15] "=&v"(r15), [r16] "=&v"(r16),         \
       [r17] "=&v"(r17), [entry] "=&s"(entry), [keep] "=&s"(keep), [m] "=&s"(m), [ds] "=&s"(ds)
-#define RB_TRIP_IN                                                                                                       \
-    [ax] "s"(a.x), [ay] "s"(a.y), [az] "s"(a.z), [bx] "s"(b.x), [by] "s"(b.y), [bz] "s"(b.z), [cx] "s"(c.x),              \
-      [cy] "s"(c.y), [cz] "s"(c.z), [slot] "s"(slot), [ox] "v"(o.x), [oy] "v"(o.y), [oz] "v"(o.z), [dx] "v"(d.x),         \
+#define RB_TRIP_IN(K)                                                                                                    \
+    [ax] K(a.x), [ay] K(a.y), [az] K(a.z), [bx] K(b.x), [by] K(b.y), [bz] K(b.z), [cx] K(c.x),                            \
+      [cy] K(c.y), [cz] K(c.z), [slot] K(slot), [ox] "v"(o.x), [oy] "v"(o.y), [oz] "v"(o.z), [dx] "v"(d.x),               \
       [dy] "v"(d.y), [dz] "v"(d.z), [eps] "s"(1e-6f)
 #define RB_TRIP_CLOBBERS "vcc", "scc"   /* s_or_b64 and s_and_saveexec_b64 write scc */
-#define RB_TRIP_OPS_UV : RB_TRIP_OUT_UV, RB_TRIP_TEMPS : RB_TRIP_IN, [big] "s"(big), [tmin] "s"(0.001f) : RB_TRIP_CLOBBERS
-#define RB_TRIP_OPS_T : RB_TRIP_OUT_T, RB_TRIP_TEMPS : RB_TRIP_IN, [big] "s"(big), [tmin] "s"(0.001f) : RB_TRIP_CLOBBERS
+#define RB_TRIP_OPS_UV(K) : RB_TRIP_OUT_UV, RB_TRIP_TEMPS : RB_TRIP_IN(K), [big] "s"(big), [tmin] "s"(0.001f) : RB_TRIP_CLOBBERS
+#define RB_TRIP_OPS_T(K) : RB_TRIP_OUT_T, RB_TRIP_TEMPS : RB_TRIP_IN(K), [big] "s"(big), [tmin] "s"(0.001f) : RB_TRIP_CLOBBERS
 #define RB_TRIP_SKIP "s_cbranch_execz .Ltrip_end_%=\n\t"
     // one statement per form: the same blocks in the same order, with the moves' variant put in
 #define RB_TRIP_EMIT(MOVES, OPS)                                                                                         \
@@ -382,10 +384,14 @@ DEV void accept_trip(const v4f a, const v4f b, const v4f c, uint32_t slot, f3 o,
     } else {                                                                                                             \
         asm volatile(RB_TRIP_HEAD RB_TRIP_TAIL RB_TRIP_LAST MOVES "\ts_mov_b64 exec, %[entry]" OPS);                     \
     }
-    if constexpr (UV) {
-        RB_TRIP_EMIT(RB_TRIP_MOVES_UV, RB_TRIP_OPS_UV)
+    if constexpr (UV && VREC) {
+        RB_TRIP_EMIT(RB_TRIP_MOVES_UV, RB_TRIP_OPS_UV("v"))
+    } else if constexpr (UV) {
+        RB_TRIP_EMIT(RB_TRIP_MOVES_UV, RB_TRIP_OPS_UV("s"))
+    } else if constexpr (VREC) {
+        RB_TRIP_EMIT(RB_TRIP_MOVES_T, RB_TRIP_OPS_T("v"))
     } else {
-        RB_TRIP_EMIT(RB_TRIP_MOVES_T, RB_TRIP_OPS_T)
+        RB_TRIP_EMIT(RB_TRIP_MOVES_T, RB_TRIP_OPS_T("s"))
     }
 #undef RB_TRIP_EMIT
 #undef RB_TRIP_SKIP
@@ -731,6 +737,89 @@ struct FastWalk {
     }
 };
 
+// The triangle sift of a single-node tree (k_trace_sift; DESIGN.md section 4, "The triangle sift"): the list's triangles in the
+// two-pass form the sphere scan has (segment_spheres).  Pass 1, full width, wave-uniform records: one conservative box test per
+// GROUP of neighbouring triangles (rb_tri_filter.hpp) leaves a candidate bit per slot.  It is the conservative half of chunk_child
+// (rb_device_chunk.hpp) at a leaf: a hit the reference's f32 test ACCEPTS has its exact plane point within mm of the triangle's
+// box and its reported t within dt of that point's parameter (section 4.1, E1-E7), mm = Sp (KP f + KS), dt = Sp (KT f + KD), f the
+// bound of |e1| |e2| / |a^| for this ray's own |cos| (the group's cone), Sp >= |o - v0| + L / 2.  Sp is one constant per launch,
+// folded into p.sift_k*: it holds for every origin inside p.sift_lo..hi, which a lane checks once per segment; a lane outside
+// takes every slot.  Every compare is written so that a NaN means "candidate".  Pass 2, per lane, ascending slots: the lane's own
+// candidates through accept_trip with the record in vector registers -- same instructions, same bits; the strict t < hit.t in
+// ascending order keeps the reference's winner.
+constexpr float kSiftFMax = 1.5e5f;   // kChunkFMax (rb_kernels.hip checks)
+// what pass 1 holds of a ray for the whole list
+struct SiftRay {
+    f3 inv, oi;    // approximate reciprocals of d, and o * inv: their error and the slab values' rounding are inside sift_ks (sift_region)
+    bool inside;   // the origin is inside the region Sp was made for, and no reciprocal is beyond sift_rmax (or a NaN)
+};
+DEV SiftRay sift_ray(const KParams& p, f3 o, f3 d) {
+    SiftRay r;
+    r.inv = mk(__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y), __builtin_amdgcn_rcpf(d.z));
+    r.oi = mk(o.x * r.inv.x, o.y * r.inv.y, o.z * r.inv.z);
+    const f3 lo = ld3(p.sift_lo), hi = ld3(p.sift_hi);
+    r.inside = ((__builtin_amdgcn_fcmpf(o.x, lo.x, 2) & __builtin_amdgcn_fcmpf(o.x, hi.x, 4) & __builtin_amdgcn_fcmpf(o.y, lo.y, 2) &
+                 __builtin_amdgcn_fcmpf(o.y, hi.y, 4) & __builtin_amdgcn_fcmpf(o.z, lo.z, 2) & __builtin_amdgcn_fcmpf(o.z, hi.z, 4) &
+                 // the slab values are sums of separately rounded products, c r - o r -+ (h + mm) |r|: a reciprocal so large that one of
+                 // them overflows (a direction component that is a tiny normal float, or 0) would leave an infinity where the exact
+                 // value is finite.  Below sift_rmax none can (sift_region); a lane beyond it takes every slot.  5: ordered <=
+                 __builtin_amdgcn_fcmpf(fabsf(r.inv.x), p.sift_rmax, 5) & __builtin_amdgcn_fcmpf(fabsf(r.inv.y), p.sift_rmax, 5) &
+                 __builtin_amdgcn_fcmpf(fabsf(r.inv.z), p.sift_rmax, 5)) >>
+                __lane_id()) & 1ull;   // ordered compares: a NaN origin, a NaN or infinite reciprocal are outside
+    return r;
+}
+// Pass 1 over one block of the list: its n <= 32 slots are covered by groups [g0, g1) (wave-uniform); slot base + k ends at bit k.
+DEV uint32_t sift_block(const KParams& p, const SiftRay& r, f3 d, uint32_t g0, uint32_t g1, uint32_t n) {
+    const float kp = p.sift_kp, ks = p.sift_ks, kt = p.sift_kt, kd = p.sift_kd;
+    const cf4p groups = (cf4p)p.sift_groups;
+    const f3 inv = r.inv, oi = r.oi;
+    uint32_t cand = 0u;
+    for (uint32_t g = g1; g != g0; g--) {   // last group first
+        const cf4p rec = groups + (size_t)(g - 1u) * 4u;
+        const v4f r0 = rec[0], r1 = rec[1], r2 = rec[2];
+        const uint32_t count = __float_as_uint(rec[3].y);
+        const float y = __builtin_fmaf(d.z, r2.z, __builtin_fmaf(d.y, r2.y, d.x * r2.x));
+        const float lb = fabsf(y) - r2.w;
+        const float fl = r0.w * __builtin_amdgcn_rcpf(lb);
+        const float f = (lb > 1e-6f && fl < r1.w) ? fl : r1.w;   // NaN -> the cap
+        const float mm = __builtin_fmaf(kp, f, ks), thr = 0.001f - __builtin_fmaf(kt, f, kd);
+        const float tcx = __builtin_fmaf(r0.x, inv.x, -oi.x), tcy = __builtin_fmaf(r0.y, inv.y, -oi.y), tcz = __builtin_fmaf(r0.z, inv.z, -oi.z);
+        const float hx = r1.x + mm, hy = r1.y + mm, hz = r1.z + mm;
+        const float ix = fabsf(inv.x), iy = fabsf(inv.y), iz = fabsf(inv.z);
+        const float tn = fmaxf(fmaxf(__builtin_fmaf(-hx, ix, tcx), __builtin_fmaf(-hy, iy, tcy)), __builtin_fmaf(-hz, iz, tcz));
+        const float tf = fminf(fminf(__builtin_fmaf(hx, ix, tcx), __builtin_fmaf(hy, iy, tcy)), __builtin_fmaf(hz, iz, tcz));
+        // keep = (!(tf < tn) && !(tf < thr)) || !(f <= kSiftFMax), as lane masks joined by scalar instructions (11: unordered >=,
+        // 10: unordered >): written with bools the compiler branches round the second and third compare
+        const uint64_t keep = (__builtin_amdgcn_fcmpf(tf, tn, 11) & __builtin_amdgcn_fcmpf(tf, thr, 11)) | __builtin_amdgcn_fcmpf(f, kSiftFMax, 10);
+        uint32_t ones;
+        asm("v_cndmask_b32_e64 %0, 0, -1, %1" : "=v"(ones) : "s"(keep));
+        cand = __builtin_amdgcn_alignbit(cand, ones, 32u - count);   // `count` copies of the bit shifted in
+    }
+    if (!r.inside) cand = 0xFFFFFFFFu;
+    return cand & (0xFFFFFFFFu >> (32u - n));
+}
+template <bool UV>
+DEV void sift_triangles(const KParams& p, f3 o, f3 d, uint32_t first, uint32_t end, float big, TriHitT<UV>& h) {
+    const SiftRay r = sift_ray(p, o, d);
+    const cf4p ptris = (cf4p)p.ptris;
+    uint32_t ends = p.sift_block_ends, g0 = 0u;
+    for (uint32_t base = first; base < end; base += 32u, ends >>= 8) {
+        const uint32_t g1 = ends & 0xFFu;
+        uint32_t cand = sift_block(p, r, d, g0, g1, (end - base < 32u) ? end - base : 32u);
+        g0 = g1;
+        const cf4p block = ptris + (size_t)base * 4u;
+        while (cand != 0u) {
+            const uint32_t k = (uint32_t)__ffs((int)cand) - 1u;
+            cand &= cand - 1u;
+            const cf4p rec = block + __umul24(k, 4u);
+            v4f a = rec[0], b = rec[1], c = rec[2];
+            uint32_t live = __float_as_uint(c.w);
+            asm volatile("" : "+v"(a.x), "+v"(b.x), "+v"(live));   // all three parts asked for before `live` is looked at: one wait
+            if (live != 0u) accept_trip<RB_TRIP_ASM - 1, UV, true>(a, b, c, base + k, o, d, big, h);   // guard :336
+        }
+    }
+}
+
 template <bool STATS>
 DEV TriHit intersect_bvh_fast(const KParams& p, f3 o, f3 d, uint32_t* stack, uint32_t stride, Tally<STATS>& tl) {
     FastWalk<STATS> w;
@@ -747,9 +836,11 @@ DEV TriHit intersect_bvh_fast(const KParams& p, f3 o, f3 d, uint32_t* stack, uin
 // Every other caller of the single-node walk keeps the double-buffered loop and accept_slot as they were.
 // box (TRIP only): kBoxUnknown, or the staged answer of the root box's slab test for this lane's ray.
 // UV (the flat kernels pass false; they need TRIP and the hand-laid trip): accept_trip's.
-template <bool STATS, bool MULTI = true, bool TRIP = false, bool UV = true>
+// SIFT (k_trace_sift: TRIP, the hand-laid trip, no STATS): the list through sift_triangles.
+template <bool STATS, bool MULTI = true, bool TRIP = false, bool UV = true, bool SIFT = false>
 DEV TriHitT<UV> intersect_bvh(const KParams& p, f3 o, f3 d, uint32_t* stack, uint32_t stride, Tally<STATS>& tl, uint32_t box = kBoxUnknown) {
     static_assert(UV || (TRIP && !MULTI && RB_TRIP_BLOCK && RB_TRIP_PLAIN != 0), "the flat forms exist for the hand-laid trip only");
+    static_assert(!SIFT || (TRIP && !MULTI && !STATS && RB_TRIP_BLOCK), "the sift is written around the hand-laid trip; counting builds keep the plain loop");
     TriHitT<UV> h;
     h.hit = false;
     h.t = 1e20f;
@@ -805,7 +896,9 @@ DEV TriHitT<UV> intersect_bvh(const KParams& p, f3 o, f3 d, uint32_t* stack, uin
                 else accept_slot<!MULTI>(a, b, c, slot, o, d, h);
                 if constexpr (STATS) tl.mesh_hits += (h.t != before) ? 1u : 0u;
             };
-            if constexpr (trip && RB_TRIP_PLAIN != 0) {
+            if constexpr (SIFT) {
+                sift_triangles<UV>(p, o, d, first, end, big, h);
+            } else if constexpr (trip && RB_TRIP_PLAIN != 0) {
                 // The record is requested at the top of its own trip, into the registers the arithmetic reads, and waited for
                 // there: no second register set, no copies, no clamped address of a next record, and one compare at the bottom.
                 // (Eight waves per SIMD cover the scalar load: profiles/r25_c2_bench_ab.txt.)

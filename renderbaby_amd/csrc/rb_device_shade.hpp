@@ -622,9 +622,10 @@ DEV bool segment_finish(const KParams& p, Path& pt, const TriHitT<UV> th, uint32
 // TRIP: intersect_bvh's (k_trace and k_trace_direct pass it for their single-node instantiations), and segment_post's TRIM.
 // box: intersect_bvh's (k_trace hands over the staged answer of a primary ray it has just taken).
 // UV: intersect_bvh's and segment_post's (the flat kernels pass false).
-template <bool STATS, bool MULTI = true, bool JOINED = true, bool TRIP = false, bool UV = true>
+// SIFT: intersect_bvh's (the sift kernels pass true).
+template <bool STATS, bool MULTI = true, bool JOINED = true, bool TRIP = false, bool UV = true, bool SIFT = false>
 DEV bool segment(const KParams& p, Path& pt, uint32_t* stack, uint32_t stride, Tally<STATS>& tl, uint32_t box = kBoxUnknown) {
-    const TriHitT<UV> th = intersect_bvh<STATS, MULTI, TRIP, UV>(fresh_params(p), pt.o, pt.d, stack, stride, tl, box);
+    const TriHitT<UV> th = intersect_bvh<STATS, MULTI, TRIP, UV, SIFT>(fresh_params(p), pt.o, pt.d, stack, stride, tl, box);
     return segment_finish<STATS, MULTI, true, JOINED, !MULTI, TRIP && !MULTI, UV>(p, pt, th, stack, stride, tl);
 }
 

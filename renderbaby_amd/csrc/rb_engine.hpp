@@ -14,6 +14,7 @@
 #include "rb_internal.hpp"
 #include "rb_rccl.hpp"
 #include "rb_stage_timer.hpp"
+#include "rb_tri_filter.hpp"
 #include "rb_update_plan.hpp"
 
 namespace rb {
@@ -125,6 +126,13 @@ struct rb_engine {
     bool scene_valid = false;        // the buffers hold a scene that passed plan_update (set by the last update)
     bool trace_uv = false;           // RB_TRACE_UV=1 when the engine was made: KParams::no_uv stays 0 (the kernels with u, v)
     uint32_t last_trace_form = 0;    // the last render launch's LaunchInfo::trace_form (rb_debug_trace_form)
+    // The triangle sift of a single-node tree (rb_tri_filter.hpp; DESIGN.md section 4, "The triangle sift").  The table is remade
+    // with the prepared triangles (ensure_prepared), the region per launch (make_params): it follows the camera and the spheres.
+    bool tri_filter = true;          // RB_TRI_FILTER=0 when the engine was made: KParams::sift stays 0 (k_trace_flat as before)
+    rb::SiftTable sift_table;        // empty: no table (more than one node, a list beyond kSiftMaxSlots, nothing to reject)
+    rb::DevBuf<rb::SiftGroup> sift_groups;
+    float sph_box[6] = {0, 0, 0, 0, 0, 0};   // lo, hi of the uploaded spheres (all of them, whatever the patched count)
+    bool sph_box_any = false;
     rb_progressive prh{};            // gpu_wrapper.rs:19-53
     bool iter_initialized = false;   // RaytracerFrameIterator::initialized (lib.rs:131)
     uint32_t iter_passes_per_frame = 1;  // rb_iter_set_passes_per_frame (1 = the reference's one frame per pass)

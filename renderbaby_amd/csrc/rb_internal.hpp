@@ -359,6 +359,13 @@ struct KParams {
     // what the runtime has established of the scene for the plain walk (make_params; 0 = not known; no kernel reads it: plan_launch
     // picks the kernel by it): no segment of this launch reads a triangle's u, v or a texel
     uint32_t no_uv;
+    // the triangle sift of a single-node tree (rb_tri_filter.hpp; sift_triangles): 1 = the table below serves this launch's node
+    uint32_t sift;
+    const float* sift_groups;      // SiftGroup records, 64 B each, in slot order
+    uint32_t sift_block_ends;      // byte b: the groups of the list's blocks 0..b of 32 slots
+    float sift_lo[3], sift_hi[3];  // the origin region: a lane whose origin is outside takes every slot
+    float sift_kp, sift_ks, sift_kt, sift_kd;   // Sp_max times ChunkMargins' KP, KS (plus pass 1's own rounding), KT, KD
+    float sift_rmax;               // the largest |1 / d| component for which no product of pass 1's slab values can overflow
 };
 
 struct LaunchInfo {
@@ -612,6 +619,7 @@ int launch_chunk_gather(const PrepTri* ptris, const uint32_t* pos_slot, const ui
 int launch_deinterleave(const uint32_t* gathered, uint32_t* frame, uint32_t width, uint32_t height, uint32_t padded_rows,
                         uint32_t stripe_rows, uint32_t shard_count, void* stream);
 size_t max_dynamic_lds(int device);   // hipDeviceAttributeMaxSharedMemoryPerBlock
+int debug_tri_filter(const KParams& p, const float* rays, uint32_t n, uint32_t first, uint32_t end, uint32_t* out);   // rb_debug.hip: pass 1 of the sift, four mask words per ray; an RB_* status
 int debug_walk_profile(unsigned long long* out64, int reset);   // pass occupancy counters of a profiling build, tools/ablate/rb_profile.patch (-1 otherwise)
 int device_cu_count(int device);
 uint32_t device_cu_count_cached();   // of the current device; asked once per device

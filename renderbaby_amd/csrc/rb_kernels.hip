@@ -29,6 +29,7 @@ constexpr float kChunkKD = 16.0f * 5.9604645e-8f * 1.01f;   // along, the relati
 #define RB_CHUNK_MARGINS_DEFINED
 #include "rb_device_chunk.hpp"
 #include "rb_launch_plan.hpp"
+#include "rb_tri_filter.hpp"
 #include "rb_host_cam.hpp"
 
 #pragma clang fp contract(off)
@@ -467,7 +468,8 @@ struct ItemQueue {
 // to win).  The choice is made at compile time so that no instantiation carries both start codes; the two forms are two
 // kernels, k_trace and k_trace_direct, around this one body.
 // UV: segment's (k_trace_flat and k_trace_flat_direct pass false; DESIGN.md section 4, "Scenes that carry no u, v").
-template <bool STATS, bool MULTI, bool STAGED, bool JOINED, bool UV = true>
+// SIFT: segment's (k_trace_sift passes true; DESIGN.md section 4, "The triangle sift").
+template <bool STATS, bool MULTI, bool STAGED, bool JOINED, bool UV = true, bool SIFT = false>
 DEV void trace_body(const KParams& p, v4f* s_ring) {
     extern __shared__ __attribute__((aligned(16))) uint32_t s_stack[];
     const uint32_t tid = threadIdx.x;
@@ -581,7 +583,7 @@ DEV void trace_body(const KParams& p, v4f* s_ring) {
         // (53 v_mov_b32 per iteration; profiles/r12_ktrace_moves_before.txt).
         if (__ballot(active) == 0ull && exhausted && loc_next == loc_end) break;
         if (active) {
-            const bool alive = segment<STATS, MULTI, JOINED, !MULTI, UV>(p, pt, &s_stack[tid], kTraceBlock, tl, box);
+            const bool alive = segment<STATS, MULTI, JOINED, !MULTI, UV, SIFT>(p, pt, &s_stack[tid], kTraceBlock, tl, box);
             if (!alive) {
                 cring.finish(colors, item, pt.color);
                 tl.paths++;
@@ -621,6 +623,15 @@ __global__ void __launch_bounds__(kTraceBlock, WAVES) k_trace_flat_direct(const 
     __shared__ __attribute__((aligned(16))) v4f s_ring[(kTraceBlock / 64u) * kRingRows * 64u];
     trace_body<false, false, false, false, false>(p, s_ring);   // (the two scatter normalizes, as k_trace_direct keeps them)
 }
+// k_trace_flat with the triangle list sifted (sift_triangles; DESIGN.md section 4, "The triangle sift"): a kernel of its own, so
+// that k_trace_flat keeps its code.  plan_launch picks it by KParams::sift; RB_TRI_FILTER=0 keeps an engine on k_trace_flat.
+template <int WAVES>
+__global__ void __launch_bounds__(kTraceBlock, WAVES) k_trace_sift(const KParams p) {
+    __shared__ __attribute__((aligned(16))) v4f s_ring[(kTraceBlock / 64u) * kRingWaveStaged];
+    trace_body<false, false, true, true, false, true>(p, s_ring);
+}
+static_assert(kSiftFMax == kChunkFMax && kSiftKS == kChunkKS && kSiftKP == kChunkKP && kSiftKT == kChunkKT && kSiftKD == kChunkKD,
+              "the sift's margins are the chunked walk's");
 #endif
 
 // k_trace for multi-node BVHs.  With 128-triangle leaves and no t-culling (the reference's
@@ -1621,6 +1632,7 @@ static TraceKernel trace_kernel(const LaunchPlan& pl) {
         if (pl.flat) {
             constexpr int W6 = RB_TRACE_WAVES, W8 = RB_TRACE_WAVES_BIG;
             const bool staged = pl.plain == kPlainStaged;
+            if (pl.sift) return pl.big ? k_trace_sift<W8> : k_trace_sift<W6>;
             return pl.big ? (staged ? k_trace_flat<W8> : k_trace_flat_direct<W8>) : (staged ? k_trace_flat<W6> : k_trace_flat_direct<W6>);
         }
 #endif
@@ -1665,7 +1677,7 @@ int launch_render(const KParams& p_, uint32_t kernel, bool stats, void* stream_,
         li = pl.li;
         if (li.grid == 0) return 0;
         if (pl.variant == kTracePlain)
-            li.trace_form = (pl.flat ? RB_TRACE_FORM_FLAT : 0u) | (pl.big ? RB_TRACE_FORM_BIG : 0u) | (pl.plain == kPlainStaged ? RB_TRACE_FORM_STAGED : 0u) |
+            li.trace_form = (pl.sift ? RB_TRACE_FORM_SIFT : 0u) | (pl.flat ? RB_TRACE_FORM_FLAT : 0u) | (pl.big ? RB_TRACE_FORM_BIG : 0u) | (pl.plain == kPlainStaged ? RB_TRACE_FORM_STAGED : 0u) |
                             (pl.plain == kPlainMulti ? RB_TRACE_FORM_MULTI : 0u);
         KParams q = p;
         q.queue_batch = pl.queue_batch, q.queue_groups = pl.queue_groups, q.queue_region = pl.queue_region;

@@ -30,6 +30,7 @@ struct LaunchPlan {
     PlainKind plain = kPlainDirect;
     bool big = false;              // the plain walk's 8-wave instantiation (never MULTI's, never a stats build's)
     bool flat = false;             // the plain walk's kernels without u, v and the texel way (k_trace_flat, k_trace_flat_direct; never MULTI's, never a stats build's)
+    bool sift = false;             // the staged flat kernel with the triangle list sifted (k_trace_sift; only with flat and kPlainStaged)
     bool sph_tree = false;         // the chunked walk's SPHTREE instantiation
     uint32_t queue_batch = 0, queue_groups = 1, queue_region = 0, magic_S = 0, magic_tiles_x = 0;   // KParams' fields of these names
     uint32_t queue_start[kQueueGroups] = {};   // the queue's initial value: [0] alone, or one band-local start per group
@@ -127,6 +128,8 @@ inline LaunchPlan plan_launch(const KParams& p, bool stats, uint32_t cus, size_t
         pl.big = pl.plain != kPlainMulti && !stats && items >= k.many_items;
         // what the runtime has established of the scene (KParams::no_uv) picks the flat kernels
         pl.flat = k.flat && pl.plain != kPlainMulti && !stats && p.no_uv != 0u;
+        // ... and what it has established of the node's list (KParams::sift, rb_tri_filter.hpp) the sifted form of the staged one
+        pl.sift = pl.flat && pl.plain == kPlainStaged && p.sift != 0u && p.u.bvh_node_count == 1u;
     }
     return pl;
 }

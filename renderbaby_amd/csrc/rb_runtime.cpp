@@ -96,6 +96,46 @@ int prep_sphere_scan(rb_engine* e) {
     return RB_OK;
 }
 
+// The sift's group table of a single-node tree, from the node and the prepared triangles as the device holds them (the f32
+// edges the kernels use; at most kSiftMaxSlots records of 64 B come back).  Any other tree, or a list with nothing to reject,
+// leaves the table empty.
+int prep_tri_filter(rb_engine* e) {
+    e->sift_table = rb::SiftTable{};
+    if (!e->tri_filter || rb::kernel_of(e->opt) != RB_KERNEL_STREAM || rb::node_count(e->sc) != 1u || !e->nodes.ptr || !e->ptris.ptr) return RB_OK;
+    rb_bvh_node node{};
+    HIP_TRY(e, hipMemcpyAsync(&node, e->nodes.ptr, sizeof node, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    const uint32_t len = e->sc.n_indices, first = node.first_primitive, count = node.primitive_count;
+    const uint32_t end = (static_cast<uint64_t>(first) + count < len) ? first + count : len;   // guard :331, as intersect_bvh has it
+    if (first >= end || end - first > rb::kSiftMaxSlots) return RB_OK;
+    std::vector<rb::PrepTri> list(end);   // indexed by slot; only [first, end) is read
+    HIP_TRY(e, hipMemcpyAsync(list.data() + first, e->ptris.ptr + first, (end - first) * sizeof(rb::PrepTri), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    rb::SiftTable tb;
+    rb::build_sift_table(list.data(), first, end, tb);
+    if (!rb::sift_pays(tb)) return RB_OK;
+    HIP_TRY(e, e->sift_groups.resize(tb.groups.size()));
+    HIP_TRY(e, hipMemcpyAsync(e->sift_groups.ptr, tb.groups.data(), tb.groups.size() * sizeof(rb::SiftGroup), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));   // `tb.groups` is pageable host memory
+    e->sift_table = std::move(tb);
+    return RB_OK;
+}
+
+// the box of the spheres just uploaded (centre -+ |radius|, outward): part of the sift's origin region.  A spheres field is taken
+// whole (apply_field uploads `src, n` as the new array), so these are all the spheres the device holds.
+void keep_sphere_box(rb_engine* e, const rb_sphere* s, size_t n) {
+    e->sph_box_any = false;
+    for (size_t i = 0; s && i < n; ++i) {
+        const float r = std::fabs(s[i].radius) * 1.0001f;
+        for (int k = 0; k < 3; ++k) {
+            const float lo = s[i].center[k] - r, hi = s[i].center[k] + r;
+            e->sph_box[k] = e->sph_box_any ? std::min(e->sph_box[k], lo) : lo;
+            e->sph_box[3 + k] = e->sph_box_any ? std::max(e->sph_box[3 + k], hi) : hi;
+        }
+        e->sph_box_any = true;
+    }
+}
+
 int prep_materials(rb_engine* e, rb_material* first, size_t stride, size_t n) {
     if (!first || n == 0) return RB_OK;
     int rc = rb::launch_prep_materials(first, static_cast<uint32_t>(stride), static_cast<uint32_t>(n), e->stream);
@@ -150,6 +190,7 @@ int apply_field(rb_engine* e, rb::Field f, const rb::UpdatePlan& pl, const rb_co
         case kSpheres:
             rc = prep_materials(e, &e->spheres.ptr->material, sizeof(rb_sphere), n);
             if (!rc) rc = prep_sphere_scan(e);
+            keep_sphere_box(e, static_cast<const rb_sphere*>(src), n);
             if (!rc) rc = build_sphere_bvh(e, static_cast<const rb_sphere*>(src), n);
             break;
         case kMeshes: rc = prep_materials(e, &e->meshes.ptr->material, sizeof(rb_mesh), n); break;
@@ -189,7 +230,8 @@ int rb::ensure_prepared(rb_engine* e) {
     // ---- the mesh walk's tree (rb_accel.cpp): the chunked walk's if wanted, else the library's own if wanted
     e->chunk.rec = e->own.rec = {};
     rc = rb::build_chunk_tree(e, tri_count);
-    return (rc || e->chunk.rec.built()) ? rc : rb::build_own_tree(e, tri_count);
+    if (!rc && !e->chunk.rec.built()) rc = rb::build_own_tree(e, tri_count);
+    return rc ? rc : prep_tri_filter(e);
 }
 
 rb::KParams rb::make_params(rb_engine* e, uint32_t first_pass, uint32_t n_passes, int src, int dst) {
@@ -244,6 +286,24 @@ rb::KParams rb::make_params(rb_engine* e, uint32_t first_pass, uint32_t n_passes
     // sampled with its own index.  Trees the plain non-MULTI walk never sees establish nothing.
     const bool single = p.u.bvh_node_count <= 1u && p.sph_nodes == nullptr && !e->trace_uv;
     p.no_uv = (single && e->sc.no_uv && (e->sc.untex_lights || p.u.ground_enabled == 0u)) ? 1u : 0u;
+    // The sift ("The triangle sift"): the table of this node's list, and the region of this launch's origins --
+    // the table's triangles, the camera and the spheres.  Anything else a ray may start from is outside it and takes every slot.
+    if (single && p.u.bvh_node_count == 1u && !e->sift_table.groups.empty() && e->sift_groups.ptr) {
+        float extra[2][6];
+        uint32_t n_extra = 0;
+        for (int k = 0; k < 3; ++k) extra[0][k] = extra[0][3 + k] = p.u.camera.pos[k];
+        n_extra++;
+        if (e->sph_box_any && p.u.spheres_count > 0u) std::memcpy(extra[n_extra++], e->sph_box, sizeof e->sph_box);
+        const rb::SiftRegion r = rb::sift_region(e->sift_table, extra, n_extra);
+        if (r.on) {
+            p.sift = 1u;
+            p.sift_groups = reinterpret_cast<const float*>(e->sift_groups.ptr);
+            p.sift_block_ends = e->sift_table.block_ends;
+            for (int k = 0; k < 3; ++k) p.sift_lo[k] = r.lo[k], p.sift_hi[k] = r.hi[k];
+            p.sift_kp = r.kp, p.sift_ks = r.ks, p.sift_kt = r.kt, p.sift_kd = r.kd;
+            p.sift_rmax = r.rmax;
+        }
+    }
     return p;
 }
 
@@ -651,6 +711,8 @@ rb_engine* create_single(const rb_config* cfg, const rb_options& opt) {
                        RB_FLAG_REFERENCE_WALK;
     // RB_TRACE_UV=1: this engine's plain walk keeps the kernels that carry u, v, whatever the scene (A/B runs, tests)
     if (const char* uv = std::getenv("RB_TRACE_UV"); uv && uv[0] == '1') e->trace_uv = true;
+    // RB_TRI_FILTER=0: this engine's plain walk keeps the kernels whose triangle loop runs every trip (A/B runs, tests)
+    if (const char* tf = std::getenv("RB_TRI_FILTER"); tf && tf[0] == '0') e->tri_filter = false;
     auto bail = [&](const char* what, hipError_t st) -> rb_engine* {
         rb::fail(nullptr, RB_ERR_DEVICE, "%s failed: %s", what, hipGetErrorString(st));
         rb_destroy(e);
@@ -1261,6 +1323,21 @@ int rb_debug_walk_profile(uint64_t out64[64], int reset) {
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "counter width");
     if (hipDeviceSynchronize() != hipSuccess) return RB_ERR_DEVICE;
     return rb::debug_walk_profile(reinterpret_cast<unsigned long long*>(out64), reset) == 0 ? RB_OK : RB_ERR_DEVICE;
+}
+
+int rb_debug_tri_filter(rb_engine* e, const float* rays, uint32_t n, uint32_t* out, uint32_t* list2) {
+    if (!e || !rays || !out || !list2) return RB_ERR_NULL_ARGUMENT;
+    std::lock_guard<std::mutex> g(e->mu);
+    rb::set_device(e);
+    if (int rc = require_ready(e)) return rc;
+    if (int rc = ensure_prepared(e)) return rc;
+    const rb::KParams p = make_params(e, 0, 0, e->cur, e->cur);
+    if (p.sift == 0u) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "this engine's scene does not sift its triangle list");
+    if (n == 0u) return RB_OK;
+    if (n > (1u << 22)) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "at most 2^22 rays");
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    list2[0] = e->sift_table.first, list2[1] = e->sift_table.end;
+    return rb::debug_tri_filter(p, rays, n, list2[0], list2[1], out);
 }
 
 }  // extern "C"

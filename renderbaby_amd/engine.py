@@ -448,6 +448,14 @@ class Engine:
         """abi.TRACE_FORM_* bits of the k_trace instantiation the last render ran (rb_debug_trace_form)"""
         return int(self._lib.rb_debug_trace_form(self._h))
 
+    def tri_filter_masks(self, origins, directions):
+        """rb_debug_tri_filter: the sift's candidate bits of n rays -> (bool [slots of the node's list][n], first slot)"""
+        rays = np.ascontiguousarray(np.concatenate([np.asarray(origins, np.float32), np.asarray(directions, np.float32)], axis=1))
+        out, lst = np.zeros((len(rays), 4), np.uint32), np.zeros(2, np.uint32)
+        self._check(self._lib.rb_debug_tri_filter(self._h, rays.ctypes.data, len(rays), out.ctypes.data, lst.ctypes.data))
+        bits = (out[:, :, None] >> np.arange(32, dtype=np.uint32)) & 1
+        return bits.reshape(len(rays), 128)[:, :int(lst[1] - lst[0])].T.astype(bool), int(lst[0])
+
     # ---- the queries (rb_abi.h): every array argument goes through _marshal.Form, every call through _query
     _ray_records = staticmethod(ray_records)
 

@@ -24,6 +24,10 @@ drain, store and take; the texture lookup).  What an anchor cannot separate stay
 Executions are the phase rows of profiles/r15_ktrace_phases.txt where one exists ("measured"); everything else is marked
 "assumed" with its reason.
 
+k_trace_sift ("The triangle sift") has two loops where the others have the triangle loop: pass 1, a trip per
+group of triangles (C2: six quads), and pass 2, a trip per candidate of the wave's busiest lane (SIFT_TRIPS, counted by
+tools/tri_filter_stats.py on a sample of C2's rays).  The table has a row for each.
+
    python tools/ktrace_budget.py [build/rb_kernels.s] [kernel substring, default k_traceILb0ELb0ELi8] [measured VALU per segment, default 26.89]
 """
 import os
@@ -35,6 +39,8 @@ import isa_blocks  # noqa: E402
 TRIANGLES, SPHERES, LIGHTS = 12, 8, 1
 # profiles/r15_ktrace_phases.txt, "this tree": executions per segment x 64
 PASS2_TRIPS, LIGHT_PASS2_TRIPS, REJECTION_ROUNDS = 1.62, 0.0, 4.14
+# k_trace_sift: C2's groups, and pass 2's trips per iteration (profiles/r33_tri_filter_stats.txt, waves of mixed segments)
+SIFT_GROUPS, SIFT_TRIPS = 6, 3.88
 
 _ARITH = ("v_add_f32", "v_sub_f32", "v_subrev_f32", "v_mul_f32", "v_fma_f32", "v_fmac_f32", "v_mac_f32", "v_mad_f32", "v_min_f32", "v_max_f32",
           "v_med3_f32", "v_cvt_", "v_div_scale_f32", "v_div_fmas_f32", "v_div_fixup_f32", "v_ldexp_f32", "v_frexp_", "v_rndne_f32", "v_floor_f32",
@@ -75,11 +81,31 @@ def _ops(body):
     return [i.op for b in body for i in b.instrs]
 
 
+def sift_loops(blocks):
+    """k_trace_sift's two triangle loops as ((header, body) of pass 1, (header, body) of pass 2), or None for every other kernel.
+    Pass 1 is the one-block innermost loop that fetches a 64-byte group record with one scalar load and shifts the group's bits in
+    with v_alignbit_b32; pass 2 is the next innermost loop, the one that fetches its records per lane."""
+    loops = inner_loops(blocks)
+    for k, (h, body) in enumerate(loops[:-1]):
+        ops = _ops(body)
+        if len(body) == 1 and any(o.startswith("s_load_dwordx16") for o in ops) and any(o.startswith("v_alignbit_b32") for o in ops):
+            nh, nbody = loops[k + 1]
+            if any(o.startswith("global_load_dwordx4") for o in _ops(nbody)) and any(o.startswith("v_cmpx") for o in _ops(nbody)):
+                return (h, body), (nh, nbody)
+    return None
+
+
+def triangle_loops(blocks):
+    """the loops over the node's triangle list, in text order: the triangle loop, or the sift's two"""
+    sift = sift_loops(blocks)
+    return list(sift) if sift else [isa_blocks.triangle_loop(blocks)]
+
+
 def scan_loops(blocks):
     """k_trace's two-pass scans that follow the triangle loop, in text order: [(pass 1, pass 2) of the spheres, (pass 1,
     pass 2) of the point lights], each pass as (header, body).  Pass 1 is a one-block innermost loop that fetches its records
     with scalar loads and computes no reciprocal; pass 2 is the next innermost loop, the one with the square root."""
-    tri, _ = isa_blocks.triangle_loop(blocks)
+    tri = triangle_loops(blocks)[-1][0]
     loops = [l for l in inner_loops(blocks) if l[0].line > tri.line]
     out = []
     for k, (h, body) in enumerate(loops[:-1]):
@@ -104,13 +130,19 @@ def rejection_loop(blocks):
 
 def rows(blocks):
     """(name, trips per iteration, instructions of one trip, hash loop?, scalar instructions of one trip) for every loop of the table"""
-    tri_h, tri_body = isa_blocks.triangle_loop(blocks)
+    sift = sift_loops(blocks)
+    tri_h, tri_body = sift[1] if sift else isa_blocks.triangle_loop(blocks)
     fallback = [b for b in tri_body if any(i.op.startswith("v_div_scale") for i in b.instrs)]
     trip = [i for b in tri_body if b not in fallback for i in b.valu]
     scans = scan_loops(blocks)
     salu = lambda body: sum(b.counts()["salu"] for b in body)
-    out = [(f"triangle loop {tri_h.name}, a trip", TRIANGLES, trip, False, salu([b for b in tri_body if b not in fallback])),
-           (f"  its division fallback ({len(fallback)} blocks, branched over)", 0, [i for b in fallback for i in b.valu], False, salu(fallback))]
+    out = []
+    if sift:
+        (h1, b1) = sift[0]
+        out.append((f"sift pass 1 {h1.name}, a group", SIFT_GROUPS, [i for b in b1 for i in b.valu], False, salu(b1)))
+    out += [(f"{'sift pass 2' if sift else 'triangle loop'} {tri_h.name}, a trip", SIFT_TRIPS if sift else TRIANGLES, trip, False,
+             salu([b for b in tri_body if b not in fallback])),
+            (f"  its division fallback ({len(fallback)} blocks, branched over)", 0, [i for b in fallback for i in b.valu], False, salu(fallback))]
     names = ("sphere", "light")
     trips = ((SPHERES, PASS2_TRIPS), (LIGHTS, LIGHT_PASS2_TRIPS))
     for k, ((h1, b1), (h2, b2)) in enumerate(scans[:2]):
@@ -226,10 +258,12 @@ def once_groups(blocks):
     loop that no row of rows() counts, each block once; blocks outside the loop (set-up, the final drain) are not listed."""
     idx = {id(b): k for k, b in enumerate(blocks)}
     outer = next(b for b in blocks if b.depth == 1 and b.loop == b.name)
-    tri_h, tri_body = isa_blocks.triangle_loop(blocks)
+    tris = triangle_loops(blocks)
+    tri_h = tris[0][0]
     scans = scan_loops(blocks)
     rh, rbody = rejection_loop(blocks)
-    in_rows = {id(b) for body in [tri_body, rbody] + [l[1] for pair in scans[:2] for l in pair] for b in body}
+    in_rows = {id(b) for body in [l[1] for l in tris] + [rbody] + [l[1] for pair in scans[:2] for l in pair] for b in body}
+    tri_last = max(idx[id(b)] for l in tris for b in l[1])   # the sift: its block loop and pass 2's set-up lie between its two loops
     todo = [b for b in blocks if b.depth >= 1 and id(b) not in in_rows and (b.loop == outer.name or b.depth >= 2)]
     sites = normalize_sites(blocks)
     site_of = {}
@@ -322,6 +356,8 @@ def once_groups(blocks):
                 put("refill round 2, open_row's drain, ColorRing::take", b, 0.0, "assumed", "runs when a reservation ends inside a round: once in queue_batch items")
             else:
                 put("refill round 1, open_row's drain, ColorRing::take", b, 1.0, "assumed", "12.3 lanes end a path per iteration: some lane is idle")
+        elif len(tris) > 1 and t < k < tri_last:
+            put("sift: the list's block loop, pass 1's exit and pass 2's set-up", b, 1.0, "assumed", "one block of 32 slots")
         elif t < k < s1:
             put("segment_pre: ground, triangle winner", b, 1.01, "measured", "segment entry row")
         elif s1 <= k <= l2 + 8 and b.depth >= 2:
@@ -388,9 +424,8 @@ def main():
         tot = [a + b for a, b in zip(tot, per)]
         print(f"{name:58s} {trips:6.2f} {n:5d} {c['arith']:6d} {c['cmp']:5d} {c['book']:5d} {c['slow']:5d} {salu:5d} | {per[0]:8.1f} {per[1]:8.1f} {per[2]:8.1f} {per[3]:10.1f} {per[4]:8.1f}")
     print(f"{'the loops above':58s} {'':6s} {'':5s} {'':6s} {'':5s} {'':5s} {'':5s} {'':5s} | {tot[0]:8.1f} {tot[1]:8.1f} {tot[2]:8.1f} {tot[3]:10.1f} {tot[4]:8.1f}")
-    tri_h, tri_body = isa_blocks.triangle_loop(blocks)
     print("# bookkeeping and slow instructions of the intersection loops, by opcode (static, one trip):")
-    for name, _, instrs, hashes, _ in rows(blocks)[:4]:
+    for name, _, instrs, hashes, _ in rows(blocks)[:5 if sift_loops(blocks) else 4]:
         if name.lstrip().startswith("its division"):
             continue
         ops = {}

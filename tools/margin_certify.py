@@ -196,6 +196,56 @@ k_has_eff = k_has / (1 + 5 * u) / (1 + 2 * u)
 checks.append(("sphere: sqrt(E u) + the rest <= kSphK", k_need, k_has_eff))
 
 
+# =====================================================================================================================
+# The triangle sift of the single-node kernels (rb_device_intersect.hpp sift_block; rb_tri_filter.hpp; DESIGN.md section 4, "The
+# triangle sift").  It culls with the same two inequalities at a leaf; what differs from chunk_child is certified here.
+#   Sp.  One S per launch: S = 1.001 (diagonal of the region R + lhalf), R the padded box of the closed groups' triangles, the camera
+#        and the spheres, lhalf = half the largest sum of a closed group's extents.  A lane uses it only if o is strictly inside R
+#        (ordered compares).  v0 is in R, so |o - v0| <= diag R; an edge is no longer than the sum of its box's extents, so L / 2 <=
+#        lhalf; two vertices L apart are in R, so diag R >= L: S >= max(|o - v0| + L / 2, L) as the claim wants.
+#   slab.  Per axis, with r = the approximate reciprocal (v_rcp_f32: within 1 ulp, |r d - 1| <= e = 2 u), M = the largest coordinate
+#        magnitude in R:  oi^ = fl(o r),  tc^ = fma(c, r, -oi^),  mm^ = fma(S KP, f, ks'),  hm^ = fl(h + mm^),  t^ = fma(-+hm^, |r|, tc^).
+#        tc^ = (c - o) r + E,  |E| <= (u (1 + u) |o| + u |c - o|) |r|;  t^ d is the plane (c - o) -+ hm^ misplaced by at most
+#        (|c - o| + hm)(e + u + e u) + (1 + e)(u (1 + u) M + u S) + u (h + 2 mm),  |c - o| <= S, h <= S, mm <= S mS + 8 u M:
+#            <= u S sift_S + u M sift_M,   and ks' = S KS + 8 u (M + S)  (kSiftSlabUlps = 8).
+#        With that inside mm, every axis' computed [tn, tf] holds the exact interval of the box inflated by the across bound, so
+#        tn^ <= t* <= tf^: the compares lose nothing further.  (v_max3 / v_min3 drop a NaN axis: fewer constraints, never more.)
+#   overflow.  The slab analysis above is the standard model's, which holds while nothing overflows; the products c r, o r and
+#        hm |r| are rounded one by one, so one of them can be infinite where the exact slab value is small (a direction component
+#        that is a tiny normal float: |r| up to 2^126).  A lane uses its slab values only if every |r| <= rmax = fl_down(1e38 / reach),
+#        reach = 2 M + S + mm_max, mm_max = S KP 1.5e5 + ks' (f <= 1.5e5, or the lane is a candidate whatever they are); otherwise, and
+#        for a NaN, it takes every slot.  Then |c r|, |o r| <= M rmax, hm |r| <= (S + mm_max) rmax, and every sum of them, rounded, is at
+#        most reach rmax (1 + u)^2 <= 1e38 (1 + u)^2 < FLT_MAX: sift_overflow below.
+#   along.  Reject if tf^ < fl(0.001 - dt^), dt^ = fma(S KT, f, S KD).  An accepted hit has t^ > fl(0.001) as floats, so t^ - fl(0.001)
+#        is at least one ulp of 0.001f, 2^-33 = 1.95 u x 0.001, which covers the half ulp of the subtraction while |0.001 - dt| <=
+#        0.001; beyond that its rounding and the fma's are 2 u dt, taken from the constants: KT, KD times (1 - 4 u).  No slab term.
+#   cone.  lb = |y^| - s, y^ = fma(dz, nz, fma(dy, ny, dx nx)), n = fl(axis cos_a'), cos_a' = cos(alpha)(1 - 1e-6) - 1e-7, s = sin(alpha)
+#        (1 + 1e-5) + 2e-6.  |y^| <= |d| x cos_a' + (3 roundings + n's own) <= x cos(alpha) + sift_dot u, and every member's normal is
+#        within alpha of +-axis: |cos(d, n_k)| >= x cos(alpha) - sin(alpha) sqrt(1 - x^2) >= x cos(alpha) - sin(alpha) >= lb.
+#   f.   fl = fl(fk rcp(lb)) >= (stored bound) c0 1.00001 / lb needs (1 + 2e-6) >= (1 + e)(1 + u) / ... : sift_rcp below.
+e_rcp = 2 * u
+mS_sift = KP * 150000 + KS + 8 * u
+sift_S = (2 + mS_sift) * (e_rcp / u + 1 + e_rcp) + (1 + e_rcp) + (1 + 2 * mS_sift)
+sift_M = 8 * u * (e_rcp / u + 1 + e_rcp) + (1 + e_rcp) * (1 + u) + 2 * 8 * u
+SLAB_ULPS = 8                          # kSiftSlabUlps
+sift_dot = (gamma(3) / u + 1) * D_max + 4      # three roundings and n's own on |d||n| <= D_max; 4 u: |d| x cos_a' against x cos(alpha) is already below
+sift_rcp = (1 + e_rcp) * (1 + u) / (1 - e_rcp)
+FLT_MAX = (2 - Fr(1, 2 ** 23)) * Fr(2) ** 127
+sift_overflow = Fr(10) ** 38 * (1 + u) ** 2
+sift_checks = [
+    ("sift across, u part + its slab values (S term)", worst(c3, c4) + sift_S, KS / u + SLAB_ULPS),
+    ("sift across, its slab values (M term)", sift_M, Fr(SLAB_ULPS)),
+    ("sift along,  F part, |o - v0| term", c1t / D_min, KT / u * (1 - 4 * u)),
+    ("sift along,  F part, L term", c2t / D_min, KT / u / 2 * (1 - 4 * u)),
+    ("sift along,  u part", worst(c3t, c4t) / D_min, KD / u * (1 - 4 * u)),
+    ("sift along,  half an ulp of fl(0.001 - dt)", u * Fr(1, 1000), Fr(1, 2 ** 33)),
+    ("sift cone: the dot product's rounding in s", sift_dot * u, Fr(2, 10 ** 6)),
+    ("sift f: the reciprocal and the product in fk", sift_rcp, 1 + Fr(2, 10 ** 6)),
+    ("sift slab values: no product or sum overflows below rmax", sift_overflow / Fr(10) ** 38, FLT_MAX / Fr(10) ** 38),
+]
+checks += sift_checks
+
+
 def main():
     f = lambda x: f"{float(x):.4f}"
     print("u = 2^-24;  units below: u for the constants, 1 for ratios")
@@ -205,6 +255,7 @@ def main():
     print(f"  across:  dist(Q*, box) <= u F |d| ({f(c1)} s + {f(c2)} L) + u ({f(c3)} s + {f(c4)} L)     [DESIGN r03 by hand: 11.2 s + 4.6 L; 10 u L]")
     print(f"  along:   |d||t^ - t*|  <= u F |d| ({f(c1t)} s + {f(c2t)} L) + u ({f(c3t)} s + {f(c4t)} L)     [DESIGN r03 by hand: 10.2 s + 4.6 L; 4 u t^]")
     print(f"  kernel:  slab planes misplaced by <= {f(k_slab)} u S;  the along comparison loses <= {f(k_cmp)} u S")
+    print(f"  sift:    slab planes misplaced by <= {f(sift_S)} u S + {f(sift_M)} u M (ks carries {SLAB_ULPS} u (S + M) for them);  |y^| - x cos(alpha) <= {f(sift_dot)} u")
     print(f"  spheres: |disc^ - disc*| <= {f(E_sphere)} u a max(|o - c|, r)^2   (assumed < 26 by kSphK; sampled: 8.9)   sqrt(E u) = {float(sqrtEu):.4e}")
     ok = True
     print("\n  check                                              needs      has        used")
@@ -217,7 +268,7 @@ def main():
             fmt = (lambda x: f"{float(x):.4e}") if float(has) < 0.01 else f
             print(f"  {name:50s} {fmt(need):>8s}   {fmt(has):>8s}   {float(need / has):6.3f}   {'ok' if good else 'FAIL'}")
         ok &= good
-    print("\nPASS: every accepted hit lies inside what chunk_child keeps, for every ray and triangle that meet H1-H4;\n      every reported sphere hit inside what sphere_child keeps (normalised directions, no underflow)" if ok else "\nFAIL")
+    print("\nPASS: every accepted hit lies inside what chunk_child keeps, for every ray and triangle that meet H1-H4,\n      and inside what sift_block keeps for every origin inside its region;\n      every reported sphere hit inside what sphere_child keeps (normalised directions, no underflow)" if ok else "\nFAIL")
     return 0 if ok else 1
 
 

@@ -36,8 +36,8 @@ lines = {p: bench_line(f"{out}/{p}.log") for p in "abcd"}
 b = lines["a"]
 kernel = b["roofline"]["kernel"].replace("<false>", "")
 def is_dom(name):   # the un-instrumented instantiation of the dominant kernel: k_trace<false, ...>, k_trace_bvh<false, false, 256u>, ...
-    # (... or k_trace's kernel for scenes without u, v, k_trace_flat<8>, which the engine reports under the same name)
-    return name.startswith(kernel + "<false") or (kernel == "k_trace" and name.startswith("k_trace_flat<"))
+    # (... or k_trace's kernels for scenes without u, v, k_trace_flat<8> and k_trace_sift<8>, which the engine reports under the same name)
+    return name.startswith(kernel + "<false") or (kernel == "k_trace" and name.startswith(("k_trace_flat<", "k_trace_sift<")))
 steps_run = b["steps"] + b["warmup"]
 seg_run = b["config"]["segments_per_step"] * steps_run     # segments the dominant kernel traced in a PMC pass
 cnt = {}
