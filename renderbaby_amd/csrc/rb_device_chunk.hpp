@@ -1,6 +1,11 @@
-// rb_device_chunk.hpp -- the chunked walk's per-ray pieces: the child test with its culling margins and
-// the node step.  Shared by the render kernel (rb_kernels.hip, k_trace_chunk) and the query kernel (rb_query.hip, k_query_chunk),
-// which schedule them differently around the same pooled leaf phase.
+// rb_device_chunk.hpp -- the chunked walk, defined once for every kernel that runs it: the child test with
+// its culling margins and the node step, and around them the wave's phases -- the wave's corner of LDS (chunk_lds), a lane's walk
+// state (ChunkLane, chunk_set_aside), the root box (chunk_begin), the node phase (chunk_node_phase), the pooled leaf phase
+// (chunk_leaf_phase), the step after a round (chunk_leaf_retire) and the winner's record (chunk_winner).  k_rad_chunk /
+// k_cam_chunk (rb_radiance.hip), k_query_chunk and k_occl_chunk (rb_query.hip) run these phases and keep what differs between
+// them: where a lane's ray comes from, when the wave refills and finishes, and what a finished walk is worth.  k_trace_chunk
+// (rb_kernels.hip) uses chunk_node_step alone and keeps its own copy of the phases (DESIGN.md section 4.2 says why): a fix to the
+// phases here belongs there too.
 #pragma once
 #include "rb_device_shade.hpp"
 
@@ -135,6 +140,199 @@ DEV bool chunk_node_step(const KParams& p, uint32_t* stack, uint32_t stride, f3 
     sp--;
     cur = stack[sp * stride];
     return true;
+}
+
+// ---------------------------------------------------------------- the wave's phases around the node step ----
+// Two shapes of work alternate inside one wavefront: lane = RAY at the nodes, lane = TRIANGLE for the pooled chunks.
+
+// This wave's corner of LDS behind the block's traversal stacks (kChunkWaveLds bytes)
+struct ChunkLds {
+    lds_v4f* rayrec;   // [64][2]: {o, chunk put aside}, {d, chunk stood at}
+    lds_u64* best;     // [64]: (t bits) << 32 | rank
+    lds_u32* units;    // [128]: ray lane (| 64: its second chunk) of every pooled (ray, chunk) pair
+};
+DEV ChunkLds chunk_lds(uint32_t* s_stack, uint32_t stack_depth, uint32_t block, uint32_t tid) {
+    unsigned char* const wl = reinterpret_cast<unsigned char*>(s_stack + stack_depth * block) + (tid >> 6) * kChunkWaveLds;
+    return {(lds_v4f*)wl, (lds_u64*)(wl + 64u * 32u), (lds_u32*)(wl + 64u * 40u)};
+}
+
+// A lane's walk.  The phases act on the lanes whose state is kChunkWalk and set kChunkDone where a lane has nothing left; every
+// other value is the kernel's own (a lane without a ray, or one whose segment has yet to begin).  The phases take the lane by
+// value and return it, chunk_set_aside takes it by reference, and the state is a word, not a flag: each of these decides what
+// the compiler makes of the node loop (profiles/r34_chunk_walk_shared.txt has the forms that were tried and what each cost).
+constexpr uint32_t kChunkWalk = 2u, kChunkDone = 3u;
+struct ChunkLane {
+    uint32_t cur;             // the node or chunk the lane stands at (kChunkNone: nothing else left to walk)
+    uint32_t pend;            // the chunk this lane has put aside
+    int sp;                   // entries on its stack column
+    unsigned long long key;   // (t bits) << 32 | rank of the best hit so far; what its entry of `best` starts a round with
+    uint32_t state;           // kChunkWalk, kChunkDone or a value of the kernel's own
+};
+
+// A lane whose walk arrives at a chunk while it holds none aside keeps the chunk for the next leaf phase and goes on with the
+// subtree it had put aside, so it takes part in twice as many node passes between two waits (the best t it culls with is then
+// one chunk behind: never wrong, rarely wasteful -- few chunk visits hit)
+DEV void chunk_set_aside(ChunkLane& L, uint32_t* stack, uint32_t stride) {
+    if (L.state == kChunkWalk && L.cur != kChunkNone && (L.cur & kChunkLeaf) != 0u && L.pend == kChunkNone) {
+        L.pend = L.cur;
+        if (L.sp == 0) {
+            L.cur = kChunkNone;
+        } else {
+            L.sp--;
+            L.cur = stack[L.sp * stride];
+        }
+    }
+}
+
+// Start of a walk: the root's own box (shader.wgsl:283-315; inv = rcp_exact of d's components), then its two children.
+// The lane walks if its ray meets that box.
+template <bool STATS>
+DEV ChunkLane chunk_begin(const KParams& fp, f3 o, f3 inv, ChunkLane L, Tally<STATS>& tl) {
+    const cf4p rn = (cf4p)fp.nodes;
+    const v4f n0 = rn[0], n1 = rn[1];
+    if constexpr (STATS) tl.nodes++;
+    if (isect_aabb(o, inv, mk(n0.x, n0.y, n0.z), mk(n1.x, n1.y, n1.z))) {
+        L.cur = fp.chunk_root;
+        L.state = kChunkWalk;
+    } else {
+        L.state = kChunkDone;
+    }
+    return L;
+}
+
+// Tree: a few node steps while enough lanes are at a node.  `bound`: the t a child is culled against -- the t of the lane's key
+// in the closest-hit kernels, tmax in the any-hit one.
+template <bool STATS>
+DEV ChunkLane chunk_node_phase(const KParams& p, uint32_t* stack, uint32_t stride, f3 o, f3 d, f3 inv, float bound, ChunkLane L,
+                               Tally<STATS>& tl) {
+#pragma unroll 1
+    for (int it = 0; it < RB_CHUNK_NODE_STEPS; ++it) {
+        const bool at_node = L.state == kChunkWalk && L.cur != kChunkNone && (L.cur & kChunkLeaf) == 0u;
+        const uint32_t n = (uint32_t)__popcll(__ballot(at_node));
+        if (n == 0u || (it > 0 && n < (uint32_t)RB_CHUNK_NODE_LANES)) break;
+        if (at_node) {
+            if (!chunk_node_step<STATS>(p, stack, stride, o, d, inv, bound, L.cur, L.sp, tl)) {
+                if (L.pend != kChunkNone) L.cur = kChunkNone;   // nothing left to walk, one chunk still to be tested
+                else L.state = kChunkDone;
+            }
+            chunk_set_aside(L, stack, stride);
+        }
+    }
+    return L;
+}
+
+// One round of the leaf phase = 64 / kChunkTris pairs: this lane's pair, its ray record and its triangle's three pieces
+struct ChunkRound {
+    v4f r0, r1, a, b, c;
+    uint32_t rl;
+    bool valid;
+};
+DEV ChunkRound chunk_fetch(cf4p ca, cf4p cb, cf4p cc, const ChunkLds& w, uint32_t lane, uint32_t g0, uint32_t n_units) {
+    ChunkRound r;
+    const uint32_t g = g0 + lane / kChunkTris;
+    const bool ok = g < n_units;
+    const uint32_t e = w.units[ok ? g : 0u];   // (entry 0 exists: n_units != 0)
+    r.rl = e & 63u;
+    r.r0 = w.rayrec[r.rl * 2u];
+    r.r1 = w.rayrec[r.rl * 2u + 1u];
+    const uint32_t ref = __float_as_uint((e & 64u) ? r.r1.w : r.r0.w), first = ref & 0x03FFFFFFu, cnt = ((ref >> 26) & 31u) + 1u;
+    const uint32_t j = lane & (kChunkTris - 1u);
+    r.valid = ok && j < cnt;
+    const uint32_t pos = first + (j < cnt ? j : 0u);   // (position `first` exists: a chunk holds at least one triangle)
+    r.a = ca[pos];
+    r.b = cb[pos];
+    r.c = cc[pos];
+    return r;
+}
+
+// Leaves: pool the (ray, chunk) pairs of the lanes that hold a chunk, kChunkTris lanes per pair -- one triangle per lane, records
+// read as consecutive 16-byte pieces of three arrays, the ray fetched from LDS, the reference's intersect_triangle unchanged --
+// and a hit goes to its ray's entry of `best` with one LDS atomic min.  When the wave has run its rounds, a lane that took part
+// -- it waited at a chunk (lf) or held one aside -- calls after(lf): its entry of `best` is then the key after those rounds.
+// after(lf) does what the kernel makes of that key and must end in chunk_leaf_retire(L, lf, ...).  (Why a callable and not a
+// returned flag: profiles/r34_chunk_walk_shared.txt.)
+// AHEAD: the next round's ray records and triangle pieces are requested before this round's are tested (the render and radiance
+// kernels).  RANK: the key's low word is the triangle's rank in the reference's visit order, so that the minimum is the
+// reference's strict `t < closest` in visit order; without it the word stays zero (any hit: the bound is the ray lane's, which
+// compares after the round).
+template <bool AHEAD, bool RANK, bool STATS, class After>
+DEV void chunk_leaf_phase(const KParams& p, const ChunkLds& w, uint32_t lane, f3 o, f3 d, const ChunkLane L, Tally<STATS>& tl, After after) {
+    const bool lf = L.state == kChunkWalk && L.cur != kChunkNone && (L.cur & kChunkLeaf) != 0u;   // waits at a chunk
+    const bool lp = L.state == kChunkWalk && L.pend != kChunkNone;                                // holds one aside
+    const unsigned long long m = __ballot(lf), mp = __ballot(lp);
+    const uint32_t n_pend = (uint32_t)__popcll(mp), n_units = n_pend + (uint32_t)__popcll(m);
+    const uint32_t n_node = (uint32_t)__popcll(__ballot(L.state == kChunkWalk && L.cur != kChunkNone && !lf));
+    if (!(n_units != 0u && (n_units >= (uint32_t)RB_CHUNK_LEAF_LANES || n_node == 0u))) return;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    if (lp) w.units[(uint32_t)__popcll(mp & below)] = lane;
+    if (lf) w.units[n_pend + (uint32_t)__popcll(m & below)] = lane | 64u;
+    if (lf || lp) {
+        const v4f r0 = {o.x, o.y, o.z, __uint_as_float(L.pend)}, r1 = {d.x, d.y, d.z, __uint_as_float(L.cur)};
+        w.rayrec[lane * 2u] = r0;
+        w.rayrec[lane * 2u + 1u] = r1;
+        w.best[lane] = L.key;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    const cf4p ca = (cf4p)p.chunk_a, cb = (cf4p)p.chunk_b, cc = (cf4p)p.chunk_c;
+    constexpr uint32_t kPairsPerRound = 64u / kChunkTris;
+    ChunkRound nx;
+    if constexpr (AHEAD) nx = chunk_fetch(ca, cb, cc, w, lane, 0u, n_units);
+#pragma unroll 1
+    for (uint32_t g0 = 0; g0 < n_units; g0 += kPairsPerRound) {
+        ChunkRound r;
+        if constexpr (AHEAD) {
+            r = nx;
+            if (g0 + kPairsPerRound < n_units) nx = chunk_fetch(ca, cb, cc, w, lane, g0 + kPairsPerRound, n_units);
+        } else {
+            r = chunk_fetch(ca, cb, cc, w, lane, g0, n_units);
+        }
+        if constexpr (STATS) tl.tris += r.valid ? 1u : 0u;
+        float u, v;
+        const float t = isect_triangle(mk(r.r0.x, r.r0.y, r.r0.z), mk(r.r1.x, r.r1.y, r.r1.z), mk(r.a.x, r.a.y, r.a.z),
+                                       mk(r.b.x, r.b.y, r.b.z), mk(r.c.x, r.c.y, r.c.z), u, v);
+        if (r.valid && t > 0.001f) {
+            unsigned long long k = (unsigned long long)__float_as_uint(t) << 32;
+            if constexpr (RANK) k |= __float_as_uint(r.a.w);
+            __hip_atomic_fetch_min(&w.best[r.rl], k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+            if constexpr (STATS) tl.mesh_hits++;
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    if (lf || lp) after(lf);
+}
+
+// After a round, for a lane that took part (lf || lp): the chunk the lane stood at is done (lf), or there was nothing left to
+// walk -- pop, or the walk is complete.
+DEV ChunkLane chunk_leaf_retire(ChunkLane L, bool lf, uint32_t* stack, uint32_t stride) {
+    L.pend = kChunkNone;
+    if (L.state == kChunkWalk && (lf || L.cur == kChunkNone)) {
+        if (L.sp == 0) {
+            L.state = kChunkDone;
+        } else {
+            L.sp--;
+            L.cur = stack[L.sp * stride];
+        }
+    }
+    chunk_set_aside(L, stack, stride);
+    return L;
+}
+
+// A complete walk's hit: (t, u, v) of the winner again from its prepared record, the same operations on the same values
+DEV TriHit chunk_winner(const KParams& fp, f3 o, f3 d, unsigned long long key) {
+    TriHit th;
+    th.hit = key != kChunkNoHit;
+    th.t = 1e20f;
+    th.u = th.v = 0.0f;
+    th.slot = 0u;
+    if (th.hit) {
+        th.slot = cptr(fp.chunk_rank_slot)[(uint32_t)key];
+        const cf4p tp = (cf4p)fp.ptris + (size_t)th.slot * 4u;
+        const v4f a = tp[0], b = tp[1], c = tp[2];
+        th.t = isect_triangle(o, d, mk(a.x, a.y, a.z), mk(b.x, b.y, b.z), mk(c.x, c.y, c.z), th.u, th.v);
+    }
+    return th;
 }
 
 }  // namespace

@@ -816,8 +816,10 @@ __global__ void __launch_bounds__(BLOCK, RB_BVH_WAVES) k_trace_bvh(const KParams
 #ifndef RB_CHUNK_FINISH_LANES
 #define RB_CHUNK_FINISH_LANES 32 // shade once this many lanes have finished their walk (or nobody walks)
 #endif
-// (Twins of this body: k_query_chunk / k_occl_chunk, rb_query.hip, and k_rad_chunk, rb_radiance.hip, which starts its paths from a
-// ray buffer -- a fix to phases 2-5 here belongs there too; k_trace_bvh's walk likewise has k_rad_bvh.)
+// (Twin of this body: the walk's phases in rb_device_chunk.hpp, which k_rad_chunk / k_cam_chunk, k_query_chunk and k_occl_chunk run
+// -- a fix to phases 2-5 here belongs there too.  This kernel keeps its own copy: built from the shared phases it has the same
+// registers and instruction count and is 0.6 % slower on C3 and the lamp scene, outside the run-to-run margin
+// (profiles/r34_chunk_walk_ab.txt).  k_trace_bvh's walk likewise has k_rad_bvh.)
 // SPHTREE: the instantiation for scenes that also have a sphere tree (more than 64 spheres), whose per-lane walk runs inside
 // segment_finish; the other one leaves that walk out of its register allocation
 template <bool STATS, bool SPHTREE>

@@ -145,135 +145,31 @@ __global__ void __launch_bounds__(kQueryBlock) k_query(const KParams p, const Qu
     query_finish(p, q, ql, th, stack, kQueryBlock, wave, lane, stage);
 }
 
-// ---- the chunked walk: lane = ray at the nodes, lane = triangle for the pooled chunks (k_trace_chunk's phases 3 and 4
-// with nothing to refill: a lane leaves the loop's work when its walk is complete, the wave when all have).
+// ---- the chunked walk (rb_device_chunk.hpp) with nothing to refill: a lane leaves the loop's work when its walk is complete, the
+// wave when all have.
 __global__ void __launch_bounds__(kQueryBlock) k_query_chunk(const KParams p, const QueryArgs q) {
     extern __shared__ __attribute__((aligned(16))) uint32_t s_stack[];
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t wave = blockIdx.x * (kQueryBlock / 64u) + (tid >> 6);
     uint32_t* const stack = stack_column(s_stack, tid);
-    unsigned char* const wl = reinterpret_cast<unsigned char*>(s_stack + p.stack_depth * kQueryBlock) + (tid >> 6) * kChunkWaveLds;
-    lds_v4f* const rayrec = (lds_v4f*)wl;                    // [64][2]: {o, chunk put aside}, {d, chunk stood at}
-    lds_u64* const best = (lds_u64*)(wl + 64u * 32u);        // [64]: (t bits) << 32 | rank
-    lds_u32* const units = (lds_u32*)(wl + 64u * 40u);       // [128]: ray lane (| 64: its second chunk) of every pooled (ray, chunk) pair
+    const ChunkLds wl = chunk_lds(s_stack, p.stack_depth, kQueryBlock, tid);
     Tally<false> tl;
 
     const QueryLane ql = query_lane(fresh_params(p), q, wave, lane);
     const f3 o = ql.o, d = ql.d;
-    bool trav = false;
-    uint32_t cur = kChunkNone, pend = kChunkNone;
-    unsigned long long key = kChunkNoHit;
-    int sp = 0;
+    ChunkLane L = {kChunkNone, kChunkNone, 0, kChunkNoHit, kChunkDone};
     const f3 inv = mk(rcp_exact(d.x), rcp_exact(d.y), rcp_exact(d.z));
-    if (ql.valid) {   // the root's own box (shader.wgsl:283-315), then its two children
-        const KParams& fp = fresh_params(p);
-        const cf4p rn = (cf4p)fp.nodes;
-        const v4f n0 = rn[0], n1 = rn[1];
-        if (isect_aabb(o, inv, mk(n0.x, n0.y, n0.z), mk(n1.x, n1.y, n1.z))) {
-            cur = fp.chunk_root;
-            trav = true;
-        }
-    }
-    auto set_aside = [&]() {
-        if (trav && cur != kChunkNone && (cur & kChunkLeaf) != 0u && pend == kChunkNone) {
-            pend = cur;
-            if (sp == 0) {
-                cur = kChunkNone;
-            } else {
-                sp--;
-                cur = stack[sp * kQueryBlock];
-            }
-        }
-    };
-    set_aside();   // (a root that is one chunk)
+    if (ql.valid) L = chunk_begin<false>(fresh_params(p), o, inv, L, tl);
+    chunk_set_aside(L, stack, kQueryBlock);   // (a root that is one chunk)
 
-    while (__ballot(trav) != 0ull) {
-        // ---- tree: a few node steps while enough lanes are at a node
-#pragma unroll 1
-        for (int it = 0; it < RB_CHUNK_NODE_STEPS; ++it) {
-            const bool at_node = trav && cur != kChunkNone && (cur & kChunkLeaf) == 0u;
-            const uint32_t n = (uint32_t)__popcll(__ballot(at_node));
-            if (n == 0u || (it > 0 && n < (uint32_t)RB_CHUNK_NODE_LANES)) break;
-            if (at_node) {
-                if (!chunk_node_step<false>(p, stack, kQueryBlock, o, d, inv, __uint_as_float((uint32_t)(key >> 32)), cur, sp, tl)) {
-                    if (pend != kChunkNone) cur = kChunkNone;   // nothing left to walk, one chunk still to be tested
-                    else trav = false;
-                }
-                set_aside();
-            }
-        }
-        // ---- leaves: pool the (ray, chunk) pairs of the lanes that hold a chunk, kChunkTris lanes per pair
-        const bool lf = trav && cur != kChunkNone && (cur & kChunkLeaf) != 0u;   // waits at a chunk
-        const bool lp = trav && pend != kChunkNone;                              // holds one aside
-        const unsigned long long m = __ballot(lf), mp = __ballot(lp);
-        const uint32_t n_pend = (uint32_t)__popcll(mp), n_units = n_pend + (uint32_t)__popcll(m);
-        const uint32_t n_node = (uint32_t)__popcll(__ballot(trav && cur != kChunkNone && !lf));
-        if (n_units != 0u && (n_units >= (uint32_t)RB_CHUNK_LEAF_LANES || n_node == 0u)) {
-            const unsigned long long below = (1ull << lane) - 1ull;
-            if (lp) units[(uint32_t)__popcll(mp & below)] = lane;
-            if (lf) units[n_pend + (uint32_t)__popcll(m & below)] = lane | 64u;
-            if (lf || lp) {
-                const v4f r0 = {o.x, o.y, o.z, __uint_as_float(pend)}, r1 = {d.x, d.y, d.z, __uint_as_float(cur)};
-                rayrec[lane * 2u] = r0;
-                rayrec[lane * 2u + 1u] = r1;
-                best[lane] = key;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            const cf4p ca = (cf4p)p.chunk_a, cb = (cf4p)p.chunk_b, cc = (cf4p)p.chunk_c;
-            constexpr uint32_t kPairsPerRound = 64u / kChunkTris;
-#pragma unroll 1
-            for (uint32_t g0 = 0; g0 < n_units; g0 += kPairsPerRound) {
-                const uint32_t g = g0 + lane / kChunkTris;
-                const bool ok = g < n_units;
-                const uint32_t e = units[ok ? g : 0u];   // (entry 0 exists: n_units != 0)
-                const uint32_t rl = e & 63u;
-                const v4f r0 = rayrec[rl * 2u], r1 = rayrec[rl * 2u + 1u];
-                const uint32_t ref = __float_as_uint((e & 64u) ? r1.w : r0.w), first = ref & 0x03FFFFFFu, cnt = ((ref >> 26) & 31u) + 1u;
-                const uint32_t j = lane & (kChunkTris - 1u);
-                const bool valid = ok && j < cnt;
-                const uint32_t pos = first + (j < cnt ? j : 0u);   // (position `first` exists: a chunk holds at least one triangle)
-                const v4f ta = ca[pos], tb = cb[pos], tc = cc[pos];
-                float u, v;
-                const float t = isect_triangle(mk(r0.x, r0.y, r0.z), mk(r1.x, r1.y, r1.z), mk(ta.x, ta.y, ta.z), mk(tb.x, tb.y, tb.z),
-                                               mk(tc.x, tc.y, tc.z), u, v);
-                if (valid && t > 0.001f) {
-                    const unsigned long long k = ((unsigned long long)__float_as_uint(t) << 32) | __float_as_uint(ta.w);
-                    __hip_atomic_fetch_min(&best[rl], k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            if (lf || lp) {
-                key = best[lane];
-                pend = kChunkNone;
-                if (lf || cur == kChunkNone) {   // the chunk the lane stood at is done, or there was nothing left to walk
-                    if (sp == 0) {
-                        trav = false;
-                    } else {
-                        sp--;
-                        cur = stack[sp * kQueryBlock];
-                    }
-                }
-                set_aside();
-            }
-        }
+    while (__ballot(L.state == kChunkWalk) != 0ull) {
+        L = chunk_node_phase<false>(p, stack, kQueryBlock, o, d, inv, __uint_as_float((uint32_t)(L.key >> 32)), L, tl);
+        chunk_leaf_phase<false, true, false>(p, wl, lane, o, d, L, tl, [&L, &wl, lane, stack](bool lf) {
+            L.key = wl.best[lane];
+            L = chunk_leaf_retire(L, lf, stack, kQueryBlock);
+        });
     }
-
-    // ---- the winner's (t, u, v) again from its prepared record: the same operations on the same values
-    TriHit th;
-    th.hit = key != kChunkNoHit;
-    th.t = 1e20f;
-    th.u = th.v = 0.0f;
-    th.slot = 0u;
-    if (th.hit) {
-        const KParams& fp = fresh_params(p);
-        th.slot = cptr(fp.chunk_rank_slot)[(uint32_t)key];
-        const cf4p tp = (cf4p)fp.ptris + (size_t)th.slot * 4u;
-        const v4f a = tp[0], b = tp[1], c = tp[2];
-        th.t = isect_triangle(o, d, mk(a.x, a.y, a.z), mk(b.x, b.y, b.z), mk(c.x, c.y, c.z), th.u, th.v);
-    }
-    query_finish(p, q, ql, th, stack, kQueryBlock, wave, lane, (lds_v4f*)wl);
+    query_finish(p, q, ql, chunk_winner(fresh_params(p), o, d, L.key), stack, kQueryBlock, wave, lane, wl.rayrec);
 }
 
 // ================================================================= any-hit occlusion ====
@@ -458,19 +354,16 @@ __global__ void __launch_bounds__(kQueryBlock) k_occl(const KParams p, const Occ
     occl_store(a, ol, wave, lane, occluded);
 }
 
-// ---- the chunked walk: k_query_chunk's node and pooled leaf phases with the key starting at (bits(tmax) << 32), so that
-// chunk_node_step culls on tmax with the section 4.2 margin from the first step: that margin bounds the reference's reported t
-// of any accepted hit below a child, so no triangle with a reported t < tmax is culled.  The pooled lanes fold their t into
-// best[ray] as before; a ray whose best t has come below tmax after a round is answered and leaves the walk.
+// ---- the chunked walk with every lane's entry of `best` starting each round at (bits(tmax) << 32) and the nodes culled on tmax
+// with the section 4.2 margin from the first step: that margin bounds the reference's reported t of any accepted hit below a
+// child, so no triangle with a reported t < tmax is culled.  The pooled lanes fold their t into best[ray] as in k_query_chunk; a
+// ray whose best t has come below tmax after a round is answered and leaves the walk.
 __global__ void __launch_bounds__(kQueryBlock) k_occl_chunk(const KParams p, const OcclArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t s_stack[];
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t wave = blockIdx.x * (kQueryBlock / 64u) + (tid >> 6);
     uint32_t* const stack = stack_column(s_stack, tid);
-    unsigned char* const wl = reinterpret_cast<unsigned char*>(s_stack + p.stack_depth * kQueryBlock) + (tid >> 6) * kChunkWaveLds;
-    lds_v4f* const rayrec = (lds_v4f*)wl;                    // [64][2]: {o, chunk put aside}, {d, chunk stood at}
-    lds_u64* const best = (lds_u64*)(wl + 64u * 32u);        // [64]: (t bits) << 32 | rank
-    lds_u32* const units = (lds_u32*)(wl + 64u * 40u);       // [128]: ray lane (| 64: its second chunk) of every pooled (ray, chunk) pair
+    const ChunkLds wl = chunk_lds(s_stack, p.stack_depth, kQueryBlock, tid);
     Tally<false> tl;
 
     const OcclLane ol = occl_lane(fresh_params(p), a, wave, lane);
@@ -478,109 +371,22 @@ __global__ void __launch_bounds__(kQueryBlock) k_occl_chunk(const KParams p, con
     bool occluded = false;
     if (ol.walk) occluded = occl_early<true>(fresh_params(p), a.mask, o, d, ol.tmax, stack, kQueryBlock);
     const uint32_t tmax_bits = __float_as_uint(ol.tmax);     // (positive: bit patterns order like the values)
-    const unsigned long long key = (unsigned long long)tmax_bits << 32;
-    bool trav = false;
-    uint32_t cur = kChunkNone, pend = kChunkNone;
-    int sp = 0;
+    ChunkLane L = {kChunkNone, kChunkNone, 0, (unsigned long long)tmax_bits << 32, kChunkDone};
     const f3 inv = mk(rcp_exact(d.x), rcp_exact(d.y), rcp_exact(d.z));
-    if (ol.walk && !occluded && (a.mask & RB_MASK_TRIANGLES) != 0u) {   // the root's own box (shader.wgsl:283-315)
-        const KParams& fp = fresh_params(p);
-        const cf4p rn = (cf4p)fp.nodes;
-        const v4f n0 = rn[0], n1 = rn[1];
-        if (isect_aabb(o, inv, mk(n0.x, n0.y, n0.z), mk(n1.x, n1.y, n1.z))) {
-            cur = fp.chunk_root;
-            trav = true;
-        }
-    }
-    auto set_aside = [&]() {
-        if (trav && cur != kChunkNone && (cur & kChunkLeaf) != 0u && pend == kChunkNone) {
-            pend = cur;
-            if (sp == 0) {
-                cur = kChunkNone;
-            } else {
-                sp--;
-                cur = stack[sp * kQueryBlock];
-            }
-        }
-    };
-    set_aside();   // (a root that is one chunk)
+    if (ol.walk && !occluded && (a.mask & RB_MASK_TRIANGLES) != 0u) L = chunk_begin<false>(fresh_params(p), o, inv, L, tl);
+    chunk_set_aside(L, stack, kQueryBlock);   // (a root that is one chunk)
 
-    while (__ballot(trav) != 0ull) {
-        // ---- tree: a few node steps while enough lanes are at a node
-#pragma unroll 1
-        for (int it = 0; it < RB_CHUNK_NODE_STEPS; ++it) {
-            const bool at_node = trav && cur != kChunkNone && (cur & kChunkLeaf) == 0u;
-            const uint32_t n = (uint32_t)__popcll(__ballot(at_node));
-            if (n == 0u || (it > 0 && n < (uint32_t)RB_CHUNK_NODE_LANES)) break;
-            if (at_node) {
-                if (!chunk_node_step<false>(p, stack, kQueryBlock, o, d, inv, ol.tmax, cur, sp, tl)) {
-                    if (pend != kChunkNone) cur = kChunkNone;   // nothing left to walk, one chunk still to be tested
-                    else trav = false;
-                }
-                set_aside();
+    while (__ballot(L.state == kChunkWalk) != 0ull) {
+        L = chunk_node_phase<false>(p, stack, kQueryBlock, o, d, inv, ol.tmax, L, tl);
+        chunk_leaf_phase<false, false, false>(p, wl, lane, o, d, L, tl, [&L, &wl, &occluded, lane, stack, tmax_bits](bool lf) {
+            if ((uint32_t)(wl.best[lane] >> 32) < tmax_bits) {   // a reported t with 0.001 < t < tmax: answered
+                occluded = true;
+                L.state = kChunkDone;
+                L.cur = kChunkNone;
+                L.sp = 0;
             }
-        }
-        // ---- leaves: pool the (ray, chunk) pairs of the lanes that hold a chunk, kChunkTris lanes per pair
-        const bool lf = trav && cur != kChunkNone && (cur & kChunkLeaf) != 0u;   // waits at a chunk
-        const bool lp = trav && pend != kChunkNone;                              // holds one aside
-        const unsigned long long m = __ballot(lf), mp = __ballot(lp);
-        const uint32_t n_pend = (uint32_t)__popcll(mp), n_units = n_pend + (uint32_t)__popcll(m);
-        const uint32_t n_node = (uint32_t)__popcll(__ballot(trav && cur != kChunkNone && !lf));
-        if (n_units != 0u && (n_units >= (uint32_t)RB_CHUNK_LEAF_LANES || n_node == 0u)) {
-            const unsigned long long below = (1ull << lane) - 1ull;
-            if (lp) units[(uint32_t)__popcll(mp & below)] = lane;
-            if (lf) units[n_pend + (uint32_t)__popcll(m & below)] = lane | 64u;
-            if (lf || lp) {
-                const v4f r0 = {o.x, o.y, o.z, __uint_as_float(pend)}, r1 = {d.x, d.y, d.z, __uint_as_float(cur)};
-                rayrec[lane * 2u] = r0;
-                rayrec[lane * 2u + 1u] = r1;
-                best[lane] = key;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            const cf4p ca = (cf4p)p.chunk_a, cb = (cf4p)p.chunk_b, cc = (cf4p)p.chunk_c;
-            constexpr uint32_t kPairsPerRound = 64u / kChunkTris;
-#pragma unroll 1
-            for (uint32_t g0 = 0; g0 < n_units; g0 += kPairsPerRound) {
-                const uint32_t g = g0 + lane / kChunkTris;
-                const bool ok = g < n_units;
-                const uint32_t e = units[ok ? g : 0u];   // (entry 0 exists: n_units != 0)
-                const uint32_t rl = e & 63u;
-                const v4f r0 = rayrec[rl * 2u], r1 = rayrec[rl * 2u + 1u];
-                const uint32_t ref = __float_as_uint((e & 64u) ? r1.w : r0.w), first = ref & 0x03FFFFFFu, cnt = ((ref >> 26) & 31u) + 1u;
-                const uint32_t j = lane & (kChunkTris - 1u);
-                const bool valid = ok && j < cnt;
-                const uint32_t pos = first + (j < cnt ? j : 0u);   // (position `first` exists: a chunk holds at least one triangle)
-                const v4f ta = ca[pos], tb = cb[pos], tc = cc[pos];
-                float u, v;
-                const float t = isect_triangle(mk(r0.x, r0.y, r0.z), mk(r1.x, r1.y, r1.z), mk(ta.x, ta.y, ta.z), mk(tb.x, tb.y, tb.z),
-                                               mk(tc.x, tc.y, tc.z), u, v);
-                if (valid && t > 0.001f) {   // (the bound is the ray lane's: it compares after the round)
-                    const unsigned long long k = (unsigned long long)__float_as_uint(t) << 32;
-                    __hip_atomic_fetch_min(&best[rl], k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            if (lf || lp) {
-                if ((uint32_t)(best[lane] >> 32) < tmax_bits) {   // a reported t with 0.001 < t < tmax: answered
-                    occluded = true;
-                    trav = false;
-                    cur = kChunkNone;
-                    sp = 0;
-                }
-                pend = kChunkNone;
-                if (trav && (lf || cur == kChunkNone)) {   // the chunk the lane stood at is done, or there was nothing left to walk
-                    if (sp == 0) {
-                        trav = false;
-                    } else {
-                        sp--;
-                        cur = stack[sp * kQueryBlock];
-                    }
-                }
-                set_aside();
-            }
-        }
+            L = chunk_leaf_retire(L, lf, stack, kQueryBlock);
+        });
     }
     occl_store(a, ol, wave, lane, occluded);
 }

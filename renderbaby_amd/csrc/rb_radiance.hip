@@ -313,9 +313,8 @@ __global__ void __launch_bounds__(kRadBlock, RB_RAD_BVH_WAVES) k_rad_bvh(const K
 __global__ void __launch_bounds__(kRadBlock, RB_RAD_BVH_WAVES) k_cam_bvh(const KParams p, const RadArgs a) { rad_bvh_body<CamStart>(p, a); }
 
 // ======================================================== k_rad_chunk ====
-// k_trace_chunk's phases 2-5 (rb_kernels.hip): lane = ray down the two-box nodes (chunk_node_step),
-// lane = triangle for the pooled 16-triangle chunks with one LDS atomic min on (t, rank) per hit, segment_finish for the
-// lanes whose walk is complete.  SPHTREE: the instantiation for scenes that also have a sphere tree.
+// The chunked walk (rb_device_chunk.hpp) over the rays of a buffer, scheduled like k_trace_chunk.
+// SPHTREE: the instantiation for scenes that also have a sphere tree.
 template <bool SPHTREE, class Start>
 DEV void rad_chunk_body(const KParams& p, const RadArgs& a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t s_stack[];
@@ -323,177 +322,58 @@ DEV void rad_chunk_body(const KParams& p, const RadArgs& a) {
     const uint32_t lane = tid & 63u;
     uint32_t* const stack = stack_column(s_stack, tid);
     Tally<false> tl;
-    // this wave's corner of LDS behind the traversal stacks
-    unsigned char* const wl = reinterpret_cast<unsigned char*>(s_stack + p.stack_depth * kRadBlock) + (tid >> 6) * kChunkWaveLds;
-    lds_v4f* const rayrec = (lds_v4f*)wl;                    // [64][2]: {o, chunk put aside}, {d, chunk stood at}
-    lds_u64* const best = (lds_u64*)(wl + 64u * 32u);        // [64]: (t bits) << 32 | rank
-    lds_u32* const units = (lds_u32*)(wl + 64u * 40u);       // [128]: ray lane (| 64: its second chunk) of every pooled (ray, chunk) pair
+    const ChunkLds wl = chunk_lds(s_stack, p.stack_depth, kRadBlock, tid);
 
-    enum : uint32_t { IDLE = 0, BEGIN = 1, TRAV = 2, FINISH = 3 };
-    uint32_t state = IDLE;
-    uint32_t item = 0, cur = 0;
-    uint32_t pend = kChunkNone;   // the chunk this lane has put aside (cur == kChunkNone: nothing else left to walk)
+    enum : uint32_t { IDLE = 0, BEGIN = 1, TRAV = kChunkWalk, FINISH = kChunkDone };   // L.state: the kernel's own two and the walk's two
+    static_assert(IDLE != TRAV && IDLE != FINISH && BEGIN != TRAV && BEGIN != FINISH, "a lane that is idle or about to begin must not look like one that walks or is done");
+    uint32_t item = 0;
+    ChunkLane L = {0u, kChunkNone, 0, kChunkNoHit, IDLE};
     RadQueue iq(a, rad_total_items(a));
     Path pt;
     pt.depth = 0;
     f3 inv = mk(0, 0, 0);
-    unsigned long long key = kChunkNoHit;
-    int sp = 0;
-    auto set_aside = [&]() {
-        if (state == TRAV && cur != kChunkNone && (cur & kChunkLeaf) != 0u && pend == kChunkNone) {
-            pend = cur;
-            if (sp == 0) {
-                cur = kChunkNone;
-            } else {
-                sp--;
-                cur = stack[sp * kRadBlock];
-            }
-        }
-    };
 
     for (;;) {
         // ---- (1) hand items to idle lanes
-        iq.refill(a, lane, [&] { return state == IDLE; },
+        iq.refill(a, lane, [&] { return L.state == IDLE; },
                   [&](uint32_t it, uint32_t ray, uint32_t hs) {
                       item = it;
-                      if (Start::start(fresh_params(p), a, it, ray, hs, pt)) state = BEGIN;
+                      if (Start::start(fresh_params(p), a, it, ray, hs, pt)) L.state = BEGIN;
                   });
-        if (__ballot(state != IDLE) == 0ull) {
+        if (__ballot(L.state != IDLE) == 0ull) {
             if (iq.drained()) break;
             continue;
         }
 
-        // ---- (2) start of a segment: the root's own box (shader.wgsl:283-315), then its two children
-        if (state == BEGIN) {
-            const KParams& fp = fresh_params(p);
+        // ---- (2) start of a segment
+        if (L.state == BEGIN) {
             inv = mk(rcp_exact(pt.d.x), rcp_exact(pt.d.y), rcp_exact(pt.d.z));
-            key = kChunkNoHit;
-            sp = 0;
-            const cf4p rn = (cf4p)fp.nodes;
-            const v4f n0 = rn[0], n1 = rn[1];
-            if (isect_aabb(pt.o, inv, mk(n0.x, n0.y, n0.z), mk(n1.x, n1.y, n1.z))) {
-                cur = fp.chunk_root;
-                state = TRAV;
-            } else {
-                state = FINISH;
-            }
+            L.key = kChunkNoHit;
+            L.sp = 0;
+            L = chunk_begin<false>(fresh_params(p), pt.o, inv, L, tl);
         }
 
-        // ---- (3) tree: a few node steps while enough lanes are at a node
-#pragma unroll 1
-        for (int it = 0; it < RB_CHUNK_NODE_STEPS; ++it) {
-            const bool at_node = state == TRAV && cur != kChunkNone && (cur & kChunkLeaf) == 0u;
-            const uint32_t n = (uint32_t)__popcll(__ballot(at_node));
-            if (n == 0u || (it > 0 && n < (uint32_t)RB_CHUNK_NODE_LANES)) break;
-            if (at_node) {
-                if (!chunk_node_step<false>(p, stack, kRadBlock, pt.o, pt.d, inv, __uint_as_float((uint32_t)(key >> 32)), cur, sp, tl)) {
-                    if (pend != kChunkNone) cur = kChunkNone;   // nothing left to walk, one chunk still to be tested
-                    else state = FINISH;
-                }
-                set_aside();
-            }
-        }
-
-        // ---- (4) leaves: pool the (ray, chunk) pairs of the lanes that hold a chunk, kChunkTris lanes per pair
+        // ---- (3) tree, (4) leaves: the walk's phases
         {
-            const bool lf = state == TRAV && cur != kChunkNone && (cur & kChunkLeaf) != 0u;   // waits at a chunk
-            const bool lp = state == TRAV && pend != kChunkNone;                              // holds one aside
-            const unsigned long long m = __ballot(lf), mp = __ballot(lp);
-            const uint32_t n_pend = (uint32_t)__popcll(mp), n_units = n_pend + (uint32_t)__popcll(m);
-            const uint32_t n_node = (uint32_t)__popcll(__ballot(state == TRAV && cur != kChunkNone && !lf));
-            if (n_units != 0u && (n_units >= (uint32_t)RB_CHUNK_LEAF_LANES || n_node == 0u)) {
-                const unsigned long long below = (1ull << lane) - 1ull;
-                if (lp) units[(uint32_t)__popcll(mp & below)] = lane;
-                if (lf) units[n_pend + (uint32_t)__popcll(m & below)] = lane | 64u;
-                if (lf || lp) {
-                    const v4f r0 = {pt.o.x, pt.o.y, pt.o.z, __uint_as_float(pend)}, r1 = {pt.d.x, pt.d.y, pt.d.z, __uint_as_float(cur)};
-                    rayrec[lane * 2u] = r0;
-                    rayrec[lane * 2u + 1u] = r1;
-                    best[lane] = key;
-                }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                const cf4p ca = (cf4p)p.chunk_a, cb = (cf4p)p.chunk_b, cc = (cf4p)p.chunk_c;
-                // one round = four pairs; the next round's ray records and triangle pieces are requested before
-                // this round's are tested
-                constexpr uint32_t kPairsPerRound = 64u / kChunkTris;
-                struct Round {
-                    v4f r0, r1, a, b, c;
-                    uint32_t rl;
-                    bool valid;
-                };
-                auto fetch = [&](uint32_t g0) {
-                    Round r;
-                    const uint32_t g = g0 + lane / kChunkTris;
-                    const bool ok = g < n_units;
-                    const uint32_t e = units[ok ? g : 0u];   // (entry 0 exists: n_units != 0)
-                    r.rl = e & 63u;
-                    r.r0 = rayrec[r.rl * 2u];
-                    r.r1 = rayrec[r.rl * 2u + 1u];
-                    const uint32_t ref = __float_as_uint((e & 64u) ? r.r1.w : r.r0.w), first = ref & 0x03FFFFFFu, cnt = ((ref >> 26) & 31u) + 1u;
-                    const uint32_t j = lane & (kChunkTris - 1u);
-                    r.valid = ok && j < cnt;
-                    const uint32_t pos = first + (j < cnt ? j : 0u);   // (position `first` exists: a chunk holds at least one triangle)
-                    r.a = ca[pos];
-                    r.b = cb[pos];
-                    r.c = cc[pos];
-                    return r;
-                };
-                Round nx = fetch(0u);
-#pragma unroll 1
-                for (uint32_t g0 = 0; g0 < n_units; g0 += kPairsPerRound) {
-                    const Round r = nx;
-                    if (g0 + kPairsPerRound < n_units) nx = fetch(g0 + kPairsPerRound);
-                    float u, v;
-                    const float t = isect_triangle(mk(r.r0.x, r.r0.y, r.r0.z), mk(r.r1.x, r.r1.y, r.r1.z), mk(r.a.x, r.a.y, r.a.z),
-                                                   mk(r.b.x, r.b.y, r.b.z), mk(r.c.x, r.c.y, r.c.z), u, v);
-                    if (r.valid && t > 0.001f) {
-                        const unsigned long long k = ((unsigned long long)__float_as_uint(t) << 32) | __float_as_uint(r.a.w);
-                        __hip_atomic_fetch_min(&best[r.rl], k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                    }
-                }
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                if (lf || lp) {
-                    key = best[lane];
-                    pend = kChunkNone;
-                    if (lf || cur == kChunkNone) {   // the chunk the lane stood at is done, or there was nothing left to walk
-                        if (sp == 0) {
-                            state = FINISH;
-                        } else {
-                            sp--;
-                            cur = stack[sp * kRadBlock];
-                        }
-                    }
-                    set_aside();
-                }
-            }
+            L = chunk_node_phase<false>(p, stack, kRadBlock, pt.o, pt.d, inv, __uint_as_float((uint32_t)(L.key >> 32)), L, tl);
+            chunk_leaf_phase<true, true, false>(p, wl, lane, pt.o, pt.d, L, tl, [&](bool lf) {
+                L.key = wl.best[lane];
+                L = chunk_leaf_retire(L, lf, stack, kRadBlock);
+            });
         }
 
         // ---- (5) finished walks: the winner's record, the rest of the segment (shading), next ray
         {
-            const uint32_t n_fin = (uint32_t)__popcll(__ballot(state == FINISH));
-            const uint32_t n_trav = (uint32_t)__popcll(__ballot(state == TRAV));
-            if (n_fin != 0u && (n_fin >= (uint32_t)RB_RAD_FINISH_LANES || n_trav == 0u) && state == FINISH) {
-                TriHit th;
-                th.hit = key != kChunkNoHit;
-                th.t = 1e20f;
-                th.u = th.v = 0.0f;
-                th.slot = 0u;
-                if (th.hit) {
-                    // (t, u, v) of the winner again from its prepared record: the same operations on the same values
-                    const KParams& fp = fresh_params(p);
-                    th.slot = cptr(fp.chunk_rank_slot)[(uint32_t)key];
-                    const cf4p tp = (cf4p)fp.ptris + (size_t)th.slot * 4u;
-                    const v4f ta = tp[0], tb = tp[1], tc = tp[2];
-                    th.t = isect_triangle(pt.o, pt.d, mk(ta.x, ta.y, ta.z), mk(tb.x, tb.y, tb.z), mk(tc.x, tc.y, tc.z), th.u, th.v);
-                }
+            const uint32_t n_fin = (uint32_t)__popcll(__ballot(L.state == FINISH));
+            const uint32_t n_trav = (uint32_t)__popcll(__ballot(L.state == TRAV));
+            if (n_fin != 0u && (n_fin >= (uint32_t)RB_RAD_FINISH_LANES || n_trav == 0u) && L.state == FINISH) {
+                const TriHit th = chunk_winner(fresh_params(p), pt.o, pt.d, L.key);
                 const bool alive = segment_finish<false, SPHTREE>(p, pt, th, stack, kRadBlock, tl);
                 if (alive) {
-                    state = BEGIN;
+                    L.state = BEGIN;
                 } else {
                     rad_store(a, item, pt.color);
-                    state = IDLE;
+                    L.state = IDLE;
                 }
             }
         }

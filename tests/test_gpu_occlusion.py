@@ -204,6 +204,73 @@ def test_against_the_oracle_walk():
         e.close()
 
 
+# ---- 2b. the chunked walk's acceptance threshold, against the oracle's triangle test
+_NEAR = {}
+
+
+def _near_surface_rays():
+    """129 rays that start 0.0015 from a triangle of a 578-triangle mesh (15 caller nodes, some 40 chunks of 16) and point at
+    it: at its centroid, or at the middle of one of its edges, which it shares with a neighbour; every eighth points away.  Per
+    ray the oracle's own t (rbo_intersect_triangle) of every triangle the ray comes near; computed once."""
+    if _NEAR:
+        return _NEAR["s"], _NEAR["O"], _NEAR["D"], _NEAR["T"]
+    s = scenes.mesh_scene(12, 12, 40, 30, 1, 4, seed=3)
+    tr = s.bvh_triangles
+    v0, v1, v2 = (tr[k].astype(np.float64) for k in ("v0", "v1", "v2"))
+    nrm = np.cross(v1 - v0, v2 - v0)
+    area = np.linalg.norm(nrm, axis=1)
+    O, D = [], []
+    for j, k in enumerate(np.nonzero(area > 1e-4)[0]):
+        n_ = nrm[k] / area[k]
+        aim = (v0[k] + v1[k] + v2[k]) / 3.0 if j % 2 == 0 else (v1[k] + v2[k]) / 2.0
+        away = j % 8 == 7
+        o, d = (aim + 0.0015 * n_).astype(f32), (n_ if away else -n_).astype(f32)
+        # rays the device leaves as they are (it normalises), and whose oracle t of the aimed triangle is well inside (0.001, 0.002)
+        if not np.array_equal(_normalize(d).view(np.uint32), d.view(np.uint32)):
+            continue
+        t = _oracle.isect_triangle(o, d, tr[k]["v0"], tr[k]["v1"], tr[k]["v2"])[0]
+        if away or j % 2 == 1 or 0.0012 < t < 0.0018:
+            O.append(o)
+            D.append(d)
+        if len(O) == 129:
+            break
+    assert len(O) == 129
+    O, D = np.array(O, f32), np.array(D, f32)
+    # the oracle's t of every triangle whose plane the ray meets anywhere near the triangle (float64 prefilter, generous)
+    T = []
+    for o, d in zip(O.astype(np.float64), D.astype(np.float64)):
+        den = nrm @ d
+        with np.errstate(divide="ignore", invalid="ignore"):
+            tt = np.einsum("ij,ij->i", nrm, v0 - o) / den
+        p = o + tt[:, None] * d
+        r = np.maximum(np.linalg.norm(v1 - v0, axis=1), np.linalg.norm(v2 - v0, axis=1))
+        near = np.isfinite(tt) & (np.linalg.norm(p - v0, axis=1) <= 1.5 * r + 1e-3)
+        T.append(np.array([_oracle.isect_triangle(o.astype(f32), d.astype(f32), tr[k]["v0"], tr[k]["v1"], tr[k]["v2"])[0]
+                           for k in np.nonzero(near | (den == 0.0))[0]], f32))
+    _NEAR.update(s=s, O=O, D=D, T=T)
+    return s, O, D, T
+
+
+@pytest.mark.parametrize("n", [1, 63, 65, 129])
+def test_chunk_walk_accepts_hits_just_past_the_threshold(n):
+    """k_occl_chunk with waves that start with lanes that never walk (1, 63, 65 and 129 rays): a hit at t = 0.0015 is a hit (the
+    reference accepts t > 0.001), with tmax = 0.0019 so that nothing farther along the ray answers for it, and with no bound."""
+    s, O, D, T = _near_surface_rays()
+    O, D, T = O[:n], D[:n], T[:n]
+    e = _engine(s)
+    try:
+        for bound in (f32(0.0019), None):
+            tm = f32(1e20) if bound is None else bound
+            want = np.array([OCC if np.any((t > f32(0.001)) & (t < tm)) else VIS for t in T], np.uint8)
+            out = e.occluded(O, D, None if bound is None else np.full(n, bound, f32))
+            assert e.last_query_kernel_name() == "k_occl_chunk"
+            assert np.array_equal(out, want), (bound, np.nonzero(out != want)[0][:5])
+            if bound is not None and n >= 63:
+                assert (want == OCC).sum() * 3 >= n and (want == VIS).any()   # (the rays aimed at centroids hit by construction)
+    finally:
+        e.close()
+
+
 # ---- 3. masks
 def test_masks():
     s = scenes.feature_scene(width=48, height=32)
