@@ -302,6 +302,39 @@ class Engine final : public Renderer {
                              const rb_light_params& p, rb_radiance* d_out, uint32_t samples, uint32_t first_sample = 0) {
         check(h_->e, rb_direct_light_device(h_->e, d_emitters, n_emit, d_surfels, d_seeds, n, &p, first_sample, samples, d_out));
     }
+    // ---- ... with a weighted pick (extension; rb_abi.h): the scene's table of pick weights by power, and
+    // direct_light with the emitters picked by it -- or, for a table of the caller's, by `cdf` (one inclusive weight per emitter;
+    // empty: by the power of those emitters)
+    std::vector<uint32_t> scene_emitter_cdf() {
+        size_t count = 0;
+        check(h_->e, rb_scene_emitter_cdf(h_->e, nullptr, 0, &count));
+        std::vector<uint32_t> out(count);
+        check(h_->e, rb_scene_emitter_cdf(h_->e, out.data(), out.size(), &count));
+        return out;
+    }
+    std::vector<rb_radiance> direct_light_cdf(const std::vector<rb_surfel>& surfels, uint32_t samples, uint32_t first_sample = 0,
+                                              const uint32_t* seeds = nullptr, const rb_light_params& p = light_params(),
+                                              const std::vector<rb_emitter>& emitters = {}, const std::vector<uint32_t>& cdf = {}) {
+        if (!cdf.empty() && cdf.size() != emitters.size()) throw std::invalid_argument("direct_light_cdf: one cdf entry per emitter is needed");
+        std::vector<rb_radiance> out(surfels.size());
+        check(h_->e, rb_direct_light_cdf(h_->e, emitters.empty() ? nullptr : emitters.data(), cdf.empty() ? nullptr : cdf.data(), emitters.size(),
+                                         surfels.data(), seeds, surfels.size(), &p, first_sample, samples, out.data()));
+        return out;
+    }
+    // the table by power of a caller's emitters, no engine, made on `device` (-1: the current one)
+    static std::vector<uint32_t> emitter_cdf(const std::vector<rb_emitter>& emitters, int32_t device = -1) {
+        std::vector<uint32_t> out(emitters.size());
+        check(nullptr, rb_emitter_cdf(device, emitters.data(), emitters.size(), out.data()));
+        return out;
+    }
+    void scene_emitter_cdf_device(uint32_t* d_out, size_t capacity, uint32_t* d_count) {
+        check(h_->e, rb_scene_emitter_cdf_device(h_->e, d_out, capacity, d_count));
+    }
+    void direct_light_cdf_device(const rb_emitter* d_emitters, const uint32_t* d_cdf, size_t n_emit, const rb_surfel* d_surfels,
+                                 const uint32_t* d_seeds, size_t n, const rb_light_params& p, rb_radiance* d_out, uint32_t samples,
+                                 uint32_t first_sample = 0) {
+        check(h_->e, rb_direct_light_cdf_device(h_->e, d_emitters, d_cdf, n_emit, d_surfels, d_seeds, n, &p, first_sample, samples, d_out));
+    }
     // ---- lightmap texels made on the device (extension; rb_abi.h): the surfel of every texel of an atlas
     // over the scene's uvs, and the bake of the whole map in one call (rgba in sample_texture's layout, row 0 on top)
     static rb_lightmap_params lightmap_params(uint32_t width, uint32_t height, uint32_t mesh = RB_LIGHTMAP_ALL_MESHES, bool flip = false,

@@ -99,6 +99,12 @@ SIGNATURES = {
     "rb_light_rays": (i32, [i32, vp, sz, vp, vp, sz, vp, u32, u32, vp, vp, vp]),
     "rb_direct_light": (i32, [vp, vp, sz, vp, vp, sz, vp, u32, u32, vp]),
     "rb_direct_light_device": (i32, [vp, vp, sz, vp, vp, sz, vp, u32, u32, vp]),
+    "rb_emitter_cdf": (i32, [i32, vp, sz, vp]),
+    "rb_scene_emitter_cdf": (i32, [vp, vp, sz, P(sz)]),
+    "rb_scene_emitter_cdf_device": (i32, [vp, vp, sz, vp]),
+    "rb_light_rays_cdf": (i32, [i32, vp, vp, sz, vp, vp, sz, vp, u32, u32, vp, vp, vp]),
+    "rb_direct_light_cdf": (i32, [vp, vp, vp, sz, vp, vp, sz, vp, u32, u32, vp]),
+    "rb_direct_light_cdf_device": (i32, [vp, vp, vp, sz, vp, vp, sz, vp, u32, u32, vp]),
     "rb_lightmap_surfels": (i32, [i32, vp, sz, vp, sz, vp, vp, vp]),
     "rb_lightmap_surfels_device": (i32, [vp, vp, vp, vp]),
     "rb_lightmap_resolve": (i32, [i32, u32, u32, vp, u32, vp]),

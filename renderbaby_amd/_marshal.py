@@ -18,6 +18,8 @@ RECORDS = {rec: (np.dtype(elem), rec.itemsize // np.dtype(elem).itemsize) for re
 TABLES = {rec: (np.dtype(np.float32), rec.itemsize // 4) for rec in (abi.EMITTER, abi.GUIDE, abi.FRAME_RECORD)}
 # the ids of random streams: uint32 on the host; as a tensor int32 or uint32, only the bits count
 SEEDS = np.dtype(np.uint32)
+# the pick weights of direct_light, one inclusive entry per emitter: the same words under the same rule
+CDF = SEEDS
 
 
 def layout(dtype):

@@ -93,26 +93,29 @@ def _mean(rad):
 
 
 def direct_irradiance(engine, points, normals, samples, emitters=None, first_sample=0, seeds=None, offset=1e-3, shorten=1e-3,
-                      mask=abi.MASK_ALL):
+                      mask=abi.MASK_ALL, pick="uniform"):
     """What reaches each point directly from the lights, over pi, as float32 (m, 3): ``samples`` shadow rays per point towards
     points drawn on the scene's emitters (Engine.direct_light, rb_direct_light) -- the first bounce of
     ``irradiance_device`` with far less noise where the lights are small, and none of its further bounces or its sky.
     ``emitters``: an abi.EMITTER table of the caller's instead of the scene's.  numpy arrays -> float32 (m, 3); torch tensors on
-    the engine's device -> an (m, 3) tensor there.  A point without a valid sample is 0 0 0."""
+    the engine's device -> an (m, 3) tensor there.  A point without a valid sample is 0 0 0.  ``pick``: Engine.direct_light's --
+    "uniform", "power" (emitters picked in proportion to emission times area: the same mean with less noise where the lights
+    differ) or a caller's table of weights (section 23)."""
     return _mean(engine.direct_light(points, normals, samples, emitters=emitters, first_sample=first_sample, seeds=seeds, offset=offset,
-                                     shorten=shorten, mask=mask))
+                                     shorten=shorten, mask=mask, pick=pick))
 
 
 def lightmap_direct(engine, width, height, samples, emitters=None, first_sample=0, mesh=None, flip=False, offset=1e-3, shorten=1e-3,
-                    mask=abi.MASK_ALL, dilate=2):
+                    mask=abi.MASK_ALL, dilate=2, pick="uniform"):
     """``lightmap`` with direct light alone: the surfels of the engine's scene over its uvs (Engine.lightmap_surfels on the
     device), ``samples`` shadow rays per texel (Engine.direct_light on the device; the stream id is the texel index), the
     resolve of the sums (lightmap_resolve) -> float32 (height, width, 4) in ``lightmap``'s layout.  No surfel is ever on the
-    host; the sums cross once."""
+    host; the sums cross once.  ``pick``: Engine.direct_light's."""
     from . import engine as _engine
     surf, _ = engine.lightmap_surfels(width, height, mesh=mesh, flip=flip, out=(_engine.device_new(abi.SURFEL, int(width) * int(height),
                                                                                                      engine.query_device), None))
-    sums = engine.direct_light(surf, None, samples, emitters=emitters, first_sample=first_sample, offset=offset, shorten=shorten, mask=mask)
+    sums = engine.direct_light(surf, None, samples, emitters=emitters, first_sample=first_sample, offset=offset, shorten=shorten, mask=mask,
+                               pick=pick)
     return _engine.lightmap_resolve(_engine.download(sums, abi.RADIANCE), width, height, dilate=dilate, device=engine.query_device)
 
 

@@ -2,6 +2,9 @@
 // normative definition): the scene's emitter table by an order-preserving compaction -- flag, exclusive scan, scatter -- over the
 // raw scene arrays; the shadow ray of every (surfel, sample) item towards a point drawn on a uniformly picked emitter, with its
 // bound and its unoccluded contribution; and the ordered sum of a surfel's contributions under the any-hit bytes of those rays.
+// Beside the uniform pick, the pick by a table of integer weights (rb_emitter_cdf, rb_light_rays_cdf, rb_direct_light_cdf;
+// section 23): the table by power -- every record's power and their maximum, the quantised weights, an inclusive scan -- and the
+// same item with the emitter found in a table by a halving search.
 // The generator runs before the kernels that walk the records (k_occl*, rb_query.hip), as k_hemi_rays does (section 16).  Same
 // numerics contract as rb_kernels.hip: every step one binary32 operation in the order written, no FMA contraction, correctly
 // rounded / and sqrt, so that renderbaby_amd/direct.py equals this file bit for bit.
@@ -97,7 +100,14 @@ __global__ void __launch_bounds__(256) k_emit_scatter(const EmitArgs s, uint32_t
 // one whole 64-byte segment, so no fetched byte is wasted), and the triangle and sphere arms are a branch, not selects -- a
 // table of one kind, which is the common one (a mesh's emissive quads, or lamps only), then pays for one arm, and a mixed wave
 // pays for both either way (section 21.3; argued from the instruction counts, not measured against selects).
-__global__ void __launch_bounds__(256) k_light_rays(const LightGenArgs g) {
+// The item is defined once, light_item, for both picks (sections 21.1 and 23.1).  kCdf: the emitter comes from the inclusive
+// table cdf[N] of pick weights and the factor is float(Q) / float(q) where the uniform pick has float(N).  The table's total Q
+// = cdf[N - 1] is one address for the whole launch, so its test is wave-uniform; the search is up to 24 dependent 4-byte loads
+// per lane from a table that lives in L2, each lane at its own place (the draws are independent), and it reads inside the table
+// whatever the table holds: lo + len <= N and 1 <= half <= len - 1 throughout.  An item that the table leaves without a pick
+// (Q == 0, Q > 2^24, or q == 0 from a malformed table) is what an item of an empty table is: dark, with the direction 0 0 0.
+template <bool kCdf>
+DEV void light_item(const LightGenArgs g, const uint32_t* __restrict__ cdf) {
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
     const GenItem it = gen_item(t, g.samples, g.linear);
     const uint32_t sf = it.idx, smp = it.smp;
@@ -126,9 +136,36 @@ __global__ void __launch_bounds__(256) k_light_rays(const LightGenArgs g) {
     f3 d = mk(0, 0, 0);
     float tmax = 0.0f;
     v4f contrib = v4f{0.0f, 0.0f, 0.0f, valid ? 1.0f : 0.0f};
-    if (valid && N != 0u) {
-        const float fn = (float)N;   // N <= 2^24: exact
-        const uint32_t j = min((uint32_t)(u0 * fn), N - 1u);
+    uint32_t j = 0u;
+    float fn = 0.0f;       // the factor: float(N), or float(Q) / float(q)
+    bool picked = N != 0u;
+    if constexpr (kCdf) {
+        const uint32_t Q = N != 0u ? cdf[N - 1u] : 0u;
+        picked = Q != 0u && Q <= (1u << 24);
+        if (valid && picked) {
+            const float fq = (float)Q;   // Q <= 2^24: exact
+            const uint32_t tq = min((uint32_t)(u0 * fq), Q - 1u);
+            uint32_t lo = 0u, len = N;
+            while (len > 1u) {
+                const uint32_t half = len >> 1;
+                if (cdf[lo + half - 1u] <= tq) {
+                    lo += half;
+                    len -= half;
+                } else {
+                    len = half;
+                }
+            }
+            j = lo;
+            const uint32_t q = cdf[j] - (j != 0u ? cdf[j - 1u] : 0u);
+            picked = q != 0u;
+            fn = fq / (float)q;
+        }
+    }
+    if (valid && picked) {
+        if constexpr (!kCdf) {
+            fn = (float)N;   // N <= 2^24: exact
+            j = min((uint32_t)(u0 * fn), N - 1u);
+        }
         const v4f* const ep = reinterpret_cast<const v4f*>(g.emitters) + (size_t)j * 4u;
         const v4f e0 = ep[0], e1 = ep[1], e2 = ep[2], e3 = ep[3];
         const f3 a = mk(e0.x, e0.y, e0.z), b = mk(e1.x, e1.y, e1.z), c = mk(e2.x, e2.y, e2.z), em = mk(e3.x, e3.y, e3.z);
@@ -176,6 +213,52 @@ __global__ void __launch_bounds__(256) k_light_rays(const LightGenArgs g) {
     reinterpret_cast<v4f*>(g.contrib)[t] = contrib;
 }
 
+__global__ void __launch_bounds__(256) k_light_rays(const LightGenArgs g) { light_item<false>(g, nullptr); }
+__global__ void __launch_bounds__(256) k_light_rays_cdf(const LightGenArgs g, const uint32_t* __restrict__ cdf) { light_item<true>(g, cdf); }
+
+// ================================================= the table by power ====
+// p_j of section 23.1 for every record, and the largest of them folded into *pmax (zeroed before the launch): p >= 0, so the
+// floats order as their bit patterns do and the maximum is an integer one -- exact, whatever order the atomics arrive in.
+DEV float emit_power(const rb_emitter* __restrict__ em, uint32_t j) {
+    const v4f* const ep = reinterpret_cast<const v4f*>(em) + (size_t)j * 4u;
+    const v4f e0 = ep[0], e1 = ep[1], e2 = ep[2], e3 = ep[3];
+    const f3 a = mk(e0.x, e0.y, e0.z), b = mk(e1.x, e1.y, e1.z), c = mk(e2.x, e2.y, e2.z), em3 = mk(e3.x, e3.y, e3.z);
+    const uint32_t kind = __float_as_uint(e0.w);
+    const float area = e2.w;
+    const bool good = finite3(a) && finite3(b) && finite3(c) && finite3(em3) && finite1(area) && area > 0.0f &&
+                      (kind == (uint32_t)RB_HIT_TRIANGLE || kind == (uint32_t)RB_HIT_SPHERE || kind == (uint32_t)RB_HIT_LIGHT);
+    const float m = fmaxf(fmaxf(em3.x, em3.y), em3.z);
+    const float p = fminf(m * area, 3.4028235e38f);
+    return (good && m > 0.0f && p > 0.0f) ? p : 0.0f;
+}
+
+__global__ void __launch_bounds__(256) k_emit_power(const rb_emitter* __restrict__ em, uint32_t n, float* __restrict__ power,
+                                                    uint32_t* __restrict__ pmax) {
+    __shared__ uint32_t block_max;
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (threadIdx.x == 0u) block_max = 0u;
+    __syncthreads();
+    float p = 0.0f;
+    if (j < n) {
+        p = emit_power(em, j);
+        power[j] = p;
+    }
+    uint32_t bits = __float_as_uint(p);
+    for (int off = 32; off > 0; off >>= 1) bits = max(bits, (uint32_t)__shfl_xor((int)bits, off, 64));
+    if ((threadIdx.x & 63u) == 0u && bits != 0u) atomicMax(&block_max, bits);
+    __syncthreads();
+    if (threadIdx.x == 0u && block_max != 0u) atomicMax(pmax, block_max);
+}
+
+// q_j = p_j > 0 ? max(1, uint((p_j / pmax) * float(S))) : 0; pmax == 0: every p is 0
+__global__ void __launch_bounds__(256) k_emit_quant(const float* __restrict__ power, const uint32_t* __restrict__ pmax, uint32_t n,
+                                                    float scale, uint32_t* __restrict__ q) {
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= n) return;
+    const float p = power[j], top = __uint_as_float(*pmax);
+    q[j] = p > 0.0f ? max(1u, (uint32_t)((p / top) * scale)) : 0u;
+}
+
 // ======================================================= k_direct_fold ====
 // lane = surfel, a block of 64 surfels per wavefront as k_rad_sum has it: sample row s of the block is 64 contiguous result
 // bytes and 1 KiB of colours.  `linear`: the items lie surfel by surfel instead (a piece of fewer than 64 surfels, which would
@@ -211,7 +294,46 @@ hipError_t scan_bytes_for(uint32_t total, size_t* bytes) {
                                    rocprim::plus<uint32_t>(), static_cast<hipStream_t>(nullptr));
 }
 
+hipError_t cdf_scan_bytes_for(uint32_t n, size_t* bytes) {
+    *bytes = 0;
+    return rocprim::inclusive_scan(nullptr, *bytes, static_cast<uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr), n, rocprim::plus<uint32_t>(),
+                                   static_cast<hipStream_t>(nullptr));
+}
+
 }  // namespace
+
+// the powers and the quantised weights of n records, the word of the largest power and the scan's own scratch behind them;
+// 0: the scan could not be sized
+size_t emitter_cdf_work_bytes(uint32_t n) {
+    size_t scan = 0;
+    if (n == 0u) return 256u;
+    if (cdf_scan_bytes_for(n, &scan) != hipSuccess) return 0;
+    return 2u * align256(4u * (size_t)n) + 256u + align256(scan) + 256u;
+}
+
+// cdf[n] of em[n] by power (section 23.1), queued on `stream`: the powers and their maximum, the quantised weights, their
+// inclusive sums -- integers, so the scan's order does not show.  Nothing is waited for.
+int launch_emitter_cdf(const rb_emitter* em, uint32_t n, void* work, uint32_t* cdf, void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (n == 0u) return 0;
+    if (em == nullptr || work == nullptr || cdf == nullptr || n > RB_MAX_EMITTERS) return (int)hipErrorInvalidValue;
+    size_t scan = 0;
+    if (const hipError_t st = cdf_scan_bytes_for(n, &scan)) return (int)st;
+    char* const base = static_cast<char*>(work);
+    float* const power = reinterpret_cast<float*>(base);
+    uint32_t* const q = reinterpret_cast<uint32_t*>(base + align256(4u * (size_t)n));
+    uint32_t* const pmax = reinterpret_cast<uint32_t*>(base + 2u * align256(4u * (size_t)n));
+    void* const tmp = base + 2u * align256(4u * (size_t)n) + 256u;
+    uint32_t L = 0u;
+    while ((1u << L) < n) L++;
+    const float scale = (float)(1u << (24u - L));
+    if (const hipError_t st = hipMemsetAsync(pmax, 0, sizeof(uint32_t), stream)) return (int)st;
+    hipLaunchKernelGGL(k_emit_power, dim3((n + 255u) / 256u), dim3(256), 0, stream, em, n, power, pmax);
+    if (const hipError_t st = hipGetLastError()) return (int)st;
+    hipLaunchKernelGGL(k_emit_quant, dim3((n + 255u) / 256u), dim3(256), 0, stream, power, pmax, n, scale, q);
+    if (const hipError_t st = hipGetLastError()) return (int)st;
+    return (int)rocprim::inclusive_scan(tmp, scan, q, cdf, n, rocprim::plus<uint32_t>(), stream);
+}
 
 uint64_t emitter_candidates(const EmitArgs& s) { return (uint64_t)s.n_tris + s.n_spheres + s.n_lights; }
 
@@ -255,14 +377,19 @@ int launch_emitter_scatter(const EmitArgs& s, const void* work, rb_emitter* out,
 
 // One piece: every record, bound and colour of it, queued on `stream`; nothing is waited for.  Item order: g.n surfels rounded
 // up to whole blocks of 64, the padding written as invalid items; linear order: g.n surfels' g.n * samples items.
-int launch_light_rays(const LightGenArgs& g, void* stream_) {
+// `cdf`: nullptr for the uniform pick (k_light_rays), or g.n_emit inclusive pick weights in device memory (k_light_rays_cdf)
+int launch_light_rays(const LightGenArgs& g, void* stream_, const uint32_t* cdf) {
     if (g.n == 0u) return 0;
     if (g.surfels == nullptr || g.recs == nullptr || g.tmax == nullptr || g.contrib == nullptr || g.samples == 0u) return (int)hipErrorInvalidValue;
     if (g.emitters == nullptr && (g.n_emit != 0u)) return (int)hipErrorInvalidValue;
     if (g.n_emit > RB_MAX_EMITTERS) return (int)hipErrorInvalidValue;
     const uint64_t lanes = gen_lanes(g.n, g.samples, g.linear);
     if (lanes == 0u) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_light_rays, dim3((uint32_t)((lanes + 255u) / 256u)), dim3(256), 0, static_cast<hipStream_t>(stream_), g);
+    const dim3 grid((uint32_t)((lanes + 255u) / 256u));
+    if (cdf != nullptr && g.n_emit != 0u)
+        hipLaunchKernelGGL(k_light_rays_cdf, grid, dim3(256), 0, static_cast<hipStream_t>(stream_), g, cdf);
+    else
+        hipLaunchKernelGGL(k_light_rays, grid, dim3(256), 0, static_cast<hipStream_t>(stream_), g);
     return (int)hipGetLastError();
 }
 

@@ -198,6 +198,12 @@ struct rb_engine {
     rb::DevBuf<unsigned char> emit_work;
     uint32_t emit_n = 0;
     bool emit_valid = false;
+    // the weighted pick (rb_scene_emitter_cdf / rb_direct_light_cdf): the scene's table by power, made
+    // by the first call that needs it after the emitter table and kept as long; the table by power of a caller's emitters and
+    // a caller's own table as the host form stages it; the build's scratch
+    rb::DevBuf<uint32_t> emit_cdf, emit_cdf_given;
+    rb::DevBuf<unsigned char> emit_cdf_work;
+    bool emit_cdf_valid = false;
     // lightmap texels made on the device (rb_lightmap_surfels_device / rb_bake_lightmap*): the triangles
     // prepared in triangle order, the cover pass's scratch, and what a bake keeps between its stages
     rb::DevBuf<rb::PrepTri> lm_ptris;

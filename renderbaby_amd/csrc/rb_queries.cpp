@@ -1,7 +1,8 @@
 // rb_queries.cpp -- what an engine answers besides frames: closest-hit queries (rb_cast_rays / rb_render_hits / rb_pick), any-hit
 // occlusion, path-traced radiance along given rays, camera and hemisphere rays, lightmap texels and irradiance probes made on the
 // device, light points from a baked probe grid with or without the probes' depth moments, direct light by shadow rays to the
-// scene's emitters, with their device forms, their getters and their C entry points (rb_abi.h; DESIGN.md sections 11-22; the
+// scene's emitters picked uniformly or by a table of weights, with their device forms, their getters and their C entry points
+// (rb_abi.h; DESIGN.md sections 11-23; the
 // denoiser and the frame's history: rb_frame.cpp).
 // Every sequence is here once: one prologue (query_prologue), one timed
 // launch (timed_launch), one runner per form -- run_pieces for the host forms, device_query_locked for the device forms --, over
@@ -442,6 +443,59 @@ int ensure_emitters(rb_engine* e, const rb::KParams& p, bool* built) {
     return RB_OK;
 }
 
+// n inclusive pick weights by power of the n records at d_em into d_cdf, over the engine's scratch; queued, nothing waits
+int queue_emitter_cdf(rb_engine* e, const rb_emitter* d_em, uint32_t n, uint32_t* d_cdf) {
+    const size_t bytes = rb::emitter_cdf_work_bytes(n);
+    if (bytes == 0) return rb::fail(e, RB_ERR_DEVICE, "the pick table's scan could not be sized");
+    HIP_TRY(e, e->emit_cdf_work.reserve(bytes));
+    const int st = rb::launch_emitter_cdf(d_em, n, e->emit_cdf_work.ptr, d_cdf, e->stream);
+    if (st) return rb::fail(e, RB_ERR_DEVICE, "pick table launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
+    return RB_OK;
+}
+
+// The pick weights by power of the scene's emitter table, which stands (ensure_emitters): made if the last update left none,
+// kept as long as the table.  *built: this call made them.
+int ensure_emitter_cdf(rb_engine* e, bool* built) {
+    *built = false;
+    if (e->emit_cdf_valid) return RB_OK;
+    HIP_TRY(e, e->emit_cdf.reserve(std::max<size_t>(e->emit_n, 1)));
+    if (const int rc = queue_emitter_cdf(e, e->emit_table.ptr, e->emit_n, e->emit_cdf.ptr)) return rc;
+    e->emit_cdf_valid = true;
+    *built = true;
+    return RB_OK;
+}
+
+// rb_scene_emitter_cdf in both forms, as scene_emitters_locked: the emitter table first, outside the events; the build of the
+// weights, if there is one, between them; then the copies
+int scene_emitter_cdf_locked(rb_engine* e, bool device, uint32_t* out, size_t capacity, size_t* count, uint32_t* d_count) {
+    if (device) {
+        int rc = capacity ? device_range(e, out, capacity * sizeof(uint32_t), 4, "d_out") : RB_OK;
+        if (!rc) rc = device_range(e, d_count, sizeof(uint32_t), 4, "d_count");
+        if (rc) return rc;
+    }
+    rb::KParams p{};
+    if (const int rc = query_prologue(e, &p)) return rc;
+    bool built = false;
+    if (const int rc = ensure_emitters(e, p, &built)) return rc;
+    HIP_TRY(e, e->t_query.begin(e->stream));
+    if (const int rc = ensure_emitter_cdf(e, &built)) return rc;
+    HIP_TRY(e, e->t_query.end(e->stream));
+    if (!built) e->t_query.reset();   // the time is the build's: 0 when the weights stood
+    e->last_query_kernel_name = "k_emit_quant";
+    const size_t m = std::min<size_t>(e->emit_n, capacity);
+    if (device) {
+        if (m) HIP_TRY(e, hipMemcpyAsync(out, e->emit_cdf.ptr, m * sizeof(uint32_t), hipMemcpyDeviceToDevice, e->stream));
+        HIP_TRY(e, hipMemcpyAsync(d_count, e->emit_count.ptr, sizeof(uint32_t), hipMemcpyDeviceToDevice, e->stream));
+        return RB_OK;
+    }
+    if (m) {
+        if (const int rc = query_copy_out(e, out, e->emit_cdf.ptr, m * sizeof(uint32_t), page_locked(out))) return rc;
+    }
+    *count = e->emit_n;
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    return RB_OK;
+}
+
 // rb_scene_emitters in both forms: the build, if there is one, between the query's two events; then the copies
 int scene_emitters_locked(rb_engine* e, bool device, rb_emitter* out, size_t capacity, size_t* count, uint32_t* d_count) {
     if (device) {
@@ -477,6 +531,7 @@ struct DirectCall {
     uint32_t first_sample, samples;
     const rb_emitter* emitters;
     uint32_t n_emit;
+    const uint32_t* cdf = nullptr;   // the pick weights of rb_direct_light_cdf, n_emit of them; nullptr: the uniform pick
 };
 
 rb::LightGenArgs light_gen_args(const DirectCall& c, const rb_surfel* surfels, const uint32_t* ids, rb_ray* recs, float* tmax, float* contrib,
@@ -521,7 +576,7 @@ int direct_piece(rb_engine* e, const rb::KParams& p, const DirectCall& c, const 
                  rb_radiance* out, rb::LaunchInfo* li) {
     rb::LightGenArgs g = light_gen_args(c, surfels, ids, e->q_rays.ptr, e->q_tmax.ptr, e->rad_colors.ptr, done, m);
     g.linear = direct_linear(m) ? 1u : 0u;
-    if (const int st = e->t_generator.timed(e->stream, [&] { return rb::launch_light_rays(g, e->stream); })) return st;
+    if (const int st = e->t_generator.timed(e->stream, [&] { return rb::launch_light_rays(g, e->stream, c.cdf); })) return st;
     rb::OcclArgs a{};
     a.q.rays = e->q_rays.ptr;
     a.q.n = static_cast<uint32_t>(direct_items(m, c.samples));
@@ -532,14 +587,18 @@ int direct_piece(rb_engine* e, const rb::KParams& p, const DirectCall& c, const 
     return rb::launch_direct_fold(e->q_occl.ptr, e->rad_colors.ptr, static_cast<uint32_t>(m), c.samples, g.linear, out, e->stream);
 }
 
-int direct_light_locked(rb_engine* e, bool device, const rb_emitter* emitters, size_t n_emit, const rb_surfel* surfels, const uint32_t* seeds,
-                        size_t n, const rb_light_params& prm, uint32_t first_sample, uint32_t samples, rb_radiance* out) {
+// `weighted`: rb_direct_light_cdf -- the pick by `cdf`, the caller's n_emit weights, or (nullptr) by the table's power: the scene's
+// kept weights for the scene's table, and for a caller's table weights made for this call in the engine's scratch, queued
+int direct_light_locked(rb_engine* e, bool device, bool weighted, const rb_emitter* emitters, const uint32_t* cdf, size_t n_emit,
+                        const rb_surfel* surfels, const uint32_t* seeds, size_t n, const rb_light_params& prm, uint32_t first_sample,
+                        uint32_t samples, rb_radiance* out) {
     DirectCall c{prm, first_sample, samples, emitters, static_cast<uint32_t>(n_emit)};
     if (device) {   // every buffer of the caller's before anything is queued or the table is made: a refused call has done nothing
         int rc = device_range(e, surfels, n * sizeof(rb_surfel), 16, "d_surfels");
         if (!rc && seeds) rc = device_range(e, seeds, n * sizeof(uint32_t), 4, "d_seeds");
         if (!rc) rc = device_range(e, out, n * sizeof(rb_radiance), 16, "d_out");
         if (!rc && emitters && n_emit > 0) rc = device_range(e, emitters, n_emit * sizeof(rb_emitter), 16, "d_emitters");
+        if (!rc && emitters && cdf && n_emit > 0) rc = device_range(e, cdf, n_emit * sizeof(uint32_t), 4, "d_cdf");
         if (rc) return rc;
     }
     if (!emitters) {   // the scene's own table
@@ -548,13 +607,28 @@ int direct_light_locked(rb_engine* e, bool device, const rb_emitter* emitters, s
         int rc = query_prologue(e, &p);
         if (!rc) rc = ensure_emitters(e, p, &built);
         if (rc) return rc;
+        if (!rc && weighted) rc = ensure_emitter_cdf(e, &built);
+        if (rc) return rc;
         c.emitters = e->emit_table.ptr;
         c.n_emit = e->emit_n;
+        if (weighted) c.cdf = e->emit_cdf.ptr;
     } else if (!device) {   // a caller's table in host memory: staged once per call
         if (const int rc = require_ready(e)) return rc;
         HIP_TRY(e, e->emit_given.reserve(std::max<size_t>(n_emit, 1)));
         if (n_emit > 0) HIP_TRY(e, hipMemcpyAsync(e->emit_given.ptr, emitters, n_emit * sizeof(rb_emitter), hipMemcpyHostToDevice, e->stream));
         c.emitters = e->emit_given.ptr;
+    } else if (weighted) {
+        if (const int rc = require_ready(e)) return rc;
+    }
+    if (emitters && weighted && n_emit > 0) {   // a caller's table: its weights, or those its power gives, beside it
+        if (device && cdf) {
+            c.cdf = cdf;
+        } else {
+            HIP_TRY(e, e->emit_cdf_given.reserve(n_emit));
+            if (cdf) HIP_TRY(e, hipMemcpyAsync(e->emit_cdf_given.ptr, cdf, n_emit * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+            else if (const int rc = queue_emitter_cdf(e, c.emitters, c.n_emit, e->emit_cdf_given.ptr)) return rc;
+            c.cdf = e->emit_cdf_given.ptr;
+        }
     }
     return run_family(e, device, "direct light", RB_HEMI_PIECE_ITEMS, n, samples,
                       {FAMILY_ARRAY(surfels, e->hemi_surfels, 16, "d_surfels"), FAMILY_ARRAY(seeds, e->rad_seeds, 4, "d_seeds")},
@@ -751,6 +825,15 @@ int light_check(rb_engine* e, const char* who, const rb_light_params* prm, size_
     return RB_OK;
 }
 
+// a table of pick weights in host memory: inclusive sums, so non-decreasing, with a total of at most 2^24 (section 23.1)
+int cdf_check(rb_engine* e, const char* who, const uint32_t* cdf, size_t n_emit) {
+    if (n_emit > RB_MAX_EMITTERS) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s takes at most 2^24 emitters", who);
+    for (size_t j = 1; j < n_emit; j++)
+        if (cdf[j] < cdf[j - 1]) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: cdf[%zu] is below cdf[%zu]", who, j, j - 1);
+    if (n_emit > 0 && cdf[n_emit - 1] > RB_MAX_EMITTERS) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: the cdf's total is above 2^24", who);
+    return RB_OK;
+}
+
 // the refusals every probe entry point shares; before a device is touched (e may be NULL: rb_probe_rays)
 int probe_check(rb_engine* e, const char* who, size_t n, uint32_t first_sample, uint32_t samples) {
     if (const int rc = samples_check(e, who, "probe", first_sample, samples)) return rc;
@@ -940,16 +1023,23 @@ int hemisphere_entry(rb_engine* e, const char* who, bool openness, bool device, 
         [&](rb_engine* t) { return hemisphere_locked(t, device, HemiCall{*prm, first_sample, samples, openness}, surfels, seeds, n, out); });
 }
 
-// the two engine entry points of rb_direct_light; emitters == nullptr: the scene's own table, and n_emit is not looked at
-int direct_light_entry(rb_engine* e, const char* who, bool device, const rb_emitter* emitters, size_t n_emit, const rb_surfel* surfels,
-                       const uint32_t* seeds, size_t n, const rb_light_params* prm, uint32_t first_sample, uint32_t samples, rb_radiance* out) {
+// the four engine entry points of rb_direct_light; emitters == nullptr: the scene's own table, and n_emit is not looked at.
+// `weighted`: the _cdf forms, whose table of weights must come with a table of emitters; one in host memory is looked at here
+int direct_light_entry(rb_engine* e, const char* who, bool device, bool weighted, const rb_emitter* emitters, const uint32_t* cdf, size_t n_emit,
+                       const rb_surfel* surfels, const uint32_t* seeds, size_t n, const rb_light_params* prm, uint32_t first_sample,
+                       uint32_t samples, rb_radiance* out) {
     return engine_entry(
         e, n,
         [&] {
             if (n > 0 && (!surfels || !prm || !out)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "%s: surfels / params / out is NULL", who);
-            return prm ? light_check(e, who, prm, emitters ? n_emit : 0, n, first_sample, samples, true) : RB_OK;
+            if (prm)
+                if (const int rc = light_check(e, who, prm, emitters ? n_emit : 0, n, first_sample, samples, true)) return rc;
+            if (cdf && !emitters) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: a cdf without emitters (the scene's table has the scene's own)", who);
+            return (cdf && !device) ? cdf_check(e, who, cdf, n_emit) : RB_OK;
         },
-        [&](rb_engine* t) { return direct_light_locked(t, device, emitters, n_emit, surfels, seeds, n, *prm, first_sample, samples, out); });
+        [&](rb_engine* t) {
+            return direct_light_locked(t, device, weighted, emitters, cdf, n_emit, surfels, seeds, n, *prm, first_sample, samples, out);
+        });
 }
 
 // the two engine entry points of the probe family
@@ -1133,6 +1223,58 @@ int bake_lightmap_entry(rb_engine* e, const char* who, bool device, const rb_lig
         });
 }
 
+
+// rb_light_rays and rb_light_rays_cdf (`weighted`: the pick by `cdf`, or by the table's power where it is NULL)
+int light_rays_entry(const char* who, int32_t device, bool weighted, const rb_emitter* emitters, const uint32_t* cdf, size_t n_emit,
+                     const rb_surfel* surfels, const uint32_t* seeds, size_t n, const rb_light_params* params, uint32_t first_sample,
+                     uint32_t samples, rb_ray* rays_out, float* tmax_out, float* contrib_out) {
+    if ((n_emit > 0 && !emitters) || (n > 0 && (!surfels || !params || !rays_out || !tmax_out || !contrib_out)))
+        return rb::fail(nullptr, RB_ERR_NULL_ARGUMENT, "%s: emitters / surfels / params / rays_out / tmax_out / contrib_out is NULL", who);
+    if (params)
+        if (const int rc = light_check(nullptr, who, params, n_emit, n, first_sample, samples, false)) return rc;
+    if (cdf)
+        if (const int rc = cdf_check(nullptr, who, cdf, n_emit)) return rc;
+    if (n == 0) return RB_OK;
+    const size_t piece = std::min(n, std::max<size_t>((size_t(1) << 22) / samples, 1));   // whole surfels, about 2^22 items
+    rb::DevBuf<rb_emitter> d_emit;
+    rb::DevBuf<rb_surfel> d_surfels;
+    rb::DevBuf<uint32_t> d_ids;
+    rb::DevBuf<rb_ray> d_rays;
+    rb::DevBuf<float> d_tmax, d_contrib;
+    rb::DevBuf<uint32_t> d_cdf;
+    rb::DevBuf<unsigned char> d_work;
+    DeviceScope s(device);
+    s.alloc(d_emit, std::max<size_t>(n_emit, 1));
+    s.alloc(d_surfels, piece);
+    if (seeds) s.alloc(d_ids, piece);
+    s.alloc(d_rays, piece * samples);
+    s.alloc(d_tmax, piece * samples);
+    s.alloc(d_contrib, piece * samples * 4);
+    s.upload(d_emit.ptr, emitters, n_emit * sizeof(rb_emitter));   // once per call
+    if (weighted && n_emit > 0) {
+        s.alloc(d_cdf, n_emit);
+        if (cdf) {
+            s.upload(d_cdf.ptr, cdf, n_emit * sizeof(uint32_t));
+        } else {
+            s.alloc(d_work, std::max<size_t>(rb::emitter_cdf_work_bytes(static_cast<uint32_t>(n_emit)), 256));
+            s.run([&] { return rb::launch_emitter_cdf(d_emit.ptr, static_cast<uint32_t>(n_emit), d_work.ptr, d_cdf.ptr, s.stream); });
+        }
+    }
+    const DirectCall c{*params, first_sample, samples, d_emit.ptr, static_cast<uint32_t>(n_emit), d_cdf.ptr};
+    for (size_t done = 0; done < n && s.ok(); done += piece) {
+        const size_t m = std::min(piece, n - done), items = m * samples;
+        s.upload(d_surfels.ptr, surfels + done, m * sizeof(rb_surfel));
+        if (seeds) s.upload(d_ids.ptr, seeds + done, m * sizeof(uint32_t));
+        rb::LightGenArgs g = light_gen_args(c, d_surfels.ptr, seeds ? d_ids.ptr : nullptr, d_rays.ptr, d_tmax.ptr, d_contrib.ptr, done, m);
+        g.linear = 1u;
+        s.run([&] { return rb::launch_light_rays(g, s.stream, c.cdf); });
+        s.download(rays_out + done * samples, d_rays.ptr, items * sizeof(rb_ray));
+        s.download(tmax_out + done * samples, d_tmax.ptr, items * sizeof(float));
+        s.download(contrib_out + done * samples * 4, d_contrib.ptr, items * 4 * sizeof(float));
+        s.sync();   // the scratch is the next piece's
+    }
+    return s.finish(who);
+}
 }  // namespace
 
 extern "C" {
@@ -1327,51 +1469,79 @@ int rb_scene_emitters_device(rb_engine* e, rb_emitter* d_out, size_t capacity, u
         [&](rb_engine* t) { return scene_emitters_locked(t, true, d_out, capacity, nullptr, d_count); });
 }
 
+int rb_scene_emitter_cdf(rb_engine* e, uint32_t* out, size_t capacity, size_t* count) {
+    return engine_entry(
+        e,
+        [&]() -> int {
+            if (!count || (capacity > 0 && !out)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "rb_scene_emitter_cdf: count is NULL, or out with a capacity above 0");
+            return RB_OK;
+        },
+        [&](rb_engine* t) { return scene_emitter_cdf_locked(t, false, out, capacity, count, nullptr); });
+}
+
+int rb_scene_emitter_cdf_device(rb_engine* e, uint32_t* d_out, size_t capacity, uint32_t* d_count) {
+    return engine_entry(
+        e,
+        [&]() -> int {
+            if (!d_count || (capacity > 0 && !d_out))
+                return rb::fail(e, RB_ERR_NULL_ARGUMENT, "rb_scene_emitter_cdf_device: d_count is NULL, or d_out with a capacity above 0");
+            return RB_OK;
+        },
+        [&](rb_engine* t) { return scene_emitter_cdf_locked(t, true, d_out, capacity, nullptr, d_count); });
+}
+
+int rb_emitter_cdf(int32_t device, const rb_emitter* emitters, size_t n_emit, uint32_t* cdf_out) {
+    if (n_emit > 0 && (!emitters || !cdf_out)) return rb::fail(nullptr, RB_ERR_NULL_ARGUMENT, "rb_emitter_cdf: emitters / cdf_out is NULL");
+    if (n_emit > RB_MAX_EMITTERS) return rb::fail(nullptr, RB_ERR_INVALID_OPTIONS, "rb_emitter_cdf takes at most 2^24 emitters");
+    if (n_emit == 0) return RB_OK;
+    rb::DevBuf<rb_emitter> d_emit;
+    rb::DevBuf<uint32_t> d_cdf;
+    rb::DevBuf<unsigned char> d_work;
+    DeviceScope s(device);
+    s.alloc(d_emit, n_emit);
+    s.alloc(d_cdf, n_emit);
+    s.alloc(d_work, std::max<size_t>(rb::emitter_cdf_work_bytes(static_cast<uint32_t>(n_emit)), 256));
+    s.upload(d_emit.ptr, emitters, n_emit * sizeof(rb_emitter));
+    s.run([&] { return rb::launch_emitter_cdf(d_emit.ptr, static_cast<uint32_t>(n_emit), d_work.ptr, d_cdf.ptr, s.stream); });
+    s.download(cdf_out, d_cdf.ptr, n_emit * sizeof(uint32_t));
+    return s.finish("rb_emitter_cdf");
+}
+
+
 int rb_light_rays(int32_t device, const rb_emitter* emitters, size_t n_emit, const rb_surfel* surfels, const uint32_t* seeds, size_t n,
                   const rb_light_params* params, uint32_t first_sample, uint32_t samples, rb_ray* rays_out, float* tmax_out, float* contrib_out) {
-    if ((n_emit > 0 && !emitters) || (n > 0 && (!surfels || !params || !rays_out || !tmax_out || !contrib_out)))
-        return rb::fail(nullptr, RB_ERR_NULL_ARGUMENT, "rb_light_rays: emitters / surfels / params / rays_out / tmax_out / contrib_out is NULL");
-    if (params)
-        if (const int rc = light_check(nullptr, "rb_light_rays", params, n_emit, n, first_sample, samples, false)) return rc;
-    if (n == 0) return RB_OK;
-    const size_t piece = std::min(n, std::max<size_t>((size_t(1) << 22) / samples, 1));   // whole surfels, about 2^22 items
-    rb::DevBuf<rb_emitter> d_emit;
-    rb::DevBuf<rb_surfel> d_surfels;
-    rb::DevBuf<uint32_t> d_ids;
-    rb::DevBuf<rb_ray> d_rays;
-    rb::DevBuf<float> d_tmax, d_contrib;
-    DeviceScope s(device);
-    s.alloc(d_emit, std::max<size_t>(n_emit, 1));
-    s.alloc(d_surfels, piece);
-    if (seeds) s.alloc(d_ids, piece);
-    s.alloc(d_rays, piece * samples);
-    s.alloc(d_tmax, piece * samples);
-    s.alloc(d_contrib, piece * samples * 4);
-    s.upload(d_emit.ptr, emitters, n_emit * sizeof(rb_emitter));   // once per call
-    const DirectCall c{*params, first_sample, samples, d_emit.ptr, static_cast<uint32_t>(n_emit)};
-    for (size_t done = 0; done < n && s.ok(); done += piece) {
-        const size_t m = std::min(piece, n - done), items = m * samples;
-        s.upload(d_surfels.ptr, surfels + done, m * sizeof(rb_surfel));
-        if (seeds) s.upload(d_ids.ptr, seeds + done, m * sizeof(uint32_t));
-        rb::LightGenArgs g = light_gen_args(c, d_surfels.ptr, seeds ? d_ids.ptr : nullptr, d_rays.ptr, d_tmax.ptr, d_contrib.ptr, done, m);
-        g.linear = 1u;
-        s.run([&] { return rb::launch_light_rays(g, s.stream); });
-        s.download(rays_out + done * samples, d_rays.ptr, items * sizeof(rb_ray));
-        s.download(tmax_out + done * samples, d_tmax.ptr, items * sizeof(float));
-        s.download(contrib_out + done * samples * 4, d_contrib.ptr, items * 4 * sizeof(float));
-        s.sync();   // the scratch is the next piece's
-    }
-    return s.finish("rb_light_rays");
+    return light_rays_entry("rb_light_rays", device, false, emitters, nullptr, n_emit, surfels, seeds, n, params, first_sample, samples, rays_out,
+                            tmax_out, contrib_out);
+}
+
+int rb_light_rays_cdf(int32_t device, const rb_emitter* emitters, const uint32_t* cdf, size_t n_emit, const rb_surfel* surfels,
+                      const uint32_t* seeds, size_t n, const rb_light_params* params, uint32_t first_sample, uint32_t samples, rb_ray* rays_out,
+                      float* tmax_out, float* contrib_out) {
+    return light_rays_entry("rb_light_rays_cdf", device, true, emitters, cdf, n_emit, surfels, seeds, n, params, first_sample, samples, rays_out,
+                            tmax_out, contrib_out);
 }
 
 int rb_direct_light(rb_engine* e, const rb_emitter* emitters, size_t n_emit, const rb_surfel* surfels, const uint32_t* seeds, size_t n,
                     const rb_light_params* params, uint32_t first_sample, uint32_t samples, rb_radiance* out) {
-    return direct_light_entry(e, "rb_direct_light", false, emitters, n_emit, surfels, seeds, n, params, first_sample, samples, out);
+    return direct_light_entry(e, "rb_direct_light", false, false, emitters, nullptr, n_emit, surfels, seeds, n, params, first_sample, samples, out);
 }
 
 int rb_direct_light_device(rb_engine* e, const rb_emitter* d_emitters, size_t n_emit, const rb_surfel* d_surfels, const uint32_t* d_seeds,
                            size_t n, const rb_light_params* params, uint32_t first_sample, uint32_t samples, rb_radiance* d_out) {
-    return direct_light_entry(e, "rb_direct_light_device", true, d_emitters, n_emit, d_surfels, d_seeds, n, params, first_sample, samples, d_out);
+    return direct_light_entry(e, "rb_direct_light_device", true, false, d_emitters, nullptr, n_emit, d_surfels, d_seeds, n, params, first_sample,
+                              samples, d_out);
+}
+
+int rb_direct_light_cdf(rb_engine* e, const rb_emitter* emitters, const uint32_t* cdf, size_t n_emit, const rb_surfel* surfels,
+                        const uint32_t* seeds, size_t n, const rb_light_params* params, uint32_t first_sample, uint32_t samples, rb_radiance* out) {
+    return direct_light_entry(e, "rb_direct_light_cdf", false, true, emitters, cdf, n_emit, surfels, seeds, n, params, first_sample, samples, out);
+}
+
+int rb_direct_light_cdf_device(rb_engine* e, const rb_emitter* d_emitters, const uint32_t* d_cdf, size_t n_emit, const rb_surfel* d_surfels,
+                               const uint32_t* d_seeds, size_t n, const rb_light_params* params, uint32_t first_sample, uint32_t samples,
+                               rb_radiance* d_out) {
+    return direct_light_entry(e, "rb_direct_light_cdf_device", true, true, d_emitters, d_cdf, n_emit, d_surfels, d_seeds, n, params, first_sample,
+                              samples, d_out);
 }
 
 int rb_probe_rays(int32_t device, const rb_probe* probes, const uint32_t* seeds, size_t n, uint32_t first_sample, uint32_t samples,

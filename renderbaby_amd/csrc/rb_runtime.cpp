@@ -560,6 +560,7 @@ int update_fields(rb_engine* e, const rb_config* cfg) {
     e->dn_guides_valid = false;   // the denoiser's guides are this scene's and this camera's
     e->hist_base_valid = false;   // ... and so is the base the history was carried into (section 22)
     e->emit_valid = false;        // ... and the emitter table this scene's
+    e->emit_cdf_valid = false;    // ... with its pick weights by power (section 23)
     for (uint32_t f = 0; f < rb::kFieldCount; ++f)
         if (const int rc = apply_field(e, static_cast<rb::Field>(f), plan, cfg)) return rc;
     if (plan.own_tree != rb::OwnTree::Keep) {   // the tree follows the triangles field (RB_FLAG_BUILD_TREE)

@@ -7,8 +7,11 @@ of ``rb_direct_light`` bit for bit.
 ``qualifies``       which of such records are emitters
 ``draws``           what the generator draws for every (surfel, sample) item: three numbers, always
 ``pick``            the emitter an item's first draw picks
+``emitter_weights``, ``emitter_cdf``, ``pick_cdf``  the pick weighted by a table (section 23): the power of every record, the
+                    quantised inclusive table ``rb_emitter_cdf`` makes of them, and the record an item's first draw picks from a table
 ``barycentrics``, ``points``  the point an item's second and third draws make on its emitter, and the emitter's normal there
-``rays``          (origins, directions, bounds, contributions) of the items: what ``rb_light_rays`` returns
+``rays``          (origins, directions, bounds, contributions) of the items: what ``rb_light_rays`` returns -- with ``cdf``,
+                    what ``rb_light_rays_cdf`` returns
 ``fold``            abi.RADIANCE[m] from the contributions and the any-hit bytes of the items' shadow rays
 """
 import numpy as np
@@ -99,6 +102,83 @@ def pick(u0, n_emit):
     return np.minimum((np.asarray(u0, f32) * f32(n_emit)).astype(f32).astype(u32), u32(n_emit - 1)).astype(np.int64)
 
 
+MAX_WEIGHT = f32(3.4028235e38)
+MAX_CDF = 1 << 24
+
+
+def emitter_weights(em):
+    """p[n] float32, the pick weight of every record by its power (section 23.1): min(m area, 3.4028235e38) with m the largest
+    component of ``emissive`` when the record is good in section 21.1's sense, m > 0 and the product is > 0; else 0"""
+    e = np.asarray(em, dtype=abi.EMITTER).reshape(-1)
+    with np.errstate(all="ignore"):
+        good = (np.isfinite(e["a"]).all(1) & np.isfinite(e["b"]).all(1) & np.isfinite(e["c"]).all(1) & np.isfinite(e["emissive"]).all(1)
+                & np.isfinite(e["area"]) & (e["area"] > 0) & np.isin(e["kind"], KINDS))
+        m = np.where(good, e["emissive"].max(1), f32(0)).astype(f32)
+        p = np.minimum((m * e["area"]).astype(f32), MAX_WEIGHT).astype(f32)
+        return np.where(good & (m > 0) & (p > 0), p, f32(0)).astype(f32)
+
+
+def cdf_scale(n):
+    """S = 2^(24 - L), L the smallest integer with 2^L >= n"""
+    return 1 << (24 - max(int(n) - 1, 0).bit_length())
+
+
+def emitter_cdf(em):
+    """uint32[n], the quantised inclusive table by power (section 23.1): q_j = max(1, uint((p_j / pmax) float(S))) for p_j > 0,
+    else 0; cdf[j] = q_0 + ... + q_j.  What rb_emitter_cdf returns."""
+    p = emitter_weights(em)
+    if len(p) > abi.MAX_EMITTERS:
+        raise ValueError("at most 2^24 emitters are taken")
+    if len(p) == 0:
+        return np.zeros(0, u32)
+    pmax = p.max()
+    with np.errstate(all="ignore"):
+        r = ((p / pmax).astype(f32) * f32(cdf_scale(len(p)))).astype(f32)
+        q = np.where(p > 0, np.maximum(np.where(p > 0, r, f32(0)).astype(u32), u32(1)), u32(0)).astype(u32)
+    return np.cumsum(q, dtype=u64).astype(u32)
+
+
+def search_cdf(t, cdf):
+    """j of every t by the halving search of section 23.1, literally: lo = 0, len = N; while len > 1: half = len >> 1; if
+    cdf[lo + half - 1] <= t: lo += half, len -= half; else len = half.  The first j with cdf[j] > t in a non-decreasing table;
+    for any contents every index read is inside the table (checked here)."""
+    cdf = np.asarray(cdf, u32).reshape(-1)
+    t = np.asarray(t, u32).reshape(-1)
+    n = len(cdf)
+    lo = np.zeros(len(t), np.int64)
+    ln = np.full(len(t), n, np.int64)
+    while (ln > 1).any():
+        go = ln > 1
+        half = ln >> 1
+        idx = np.where(go, lo + half - 1, 0)
+        if not ((idx >= 0) & (idx < n)).all():
+            raise IndexError("the search left the table")
+        up = go & (cdf[idx] <= t)
+        lo = np.where(up, lo + half, lo)
+        ln = np.where(up, ln - half, np.where(go, half, ln))
+    return lo
+
+
+def pick_cdf(u0, cdf):
+    """(j, q, Q) of the items' first draws and an inclusive table of any contents (section 23.1): Q = cdf[N - 1];
+    t = min(uint(u0 float(Q)), Q - 1); j by the halving search, which reads inside the table whatever it holds;
+    q = cdf[j] - cdf[j - 1], wrapping.  Q == 0 or Q > 2^24: no pick is made and every q is 0 (a dark item)."""
+    cdf = np.asarray(cdf, u32).reshape(-1)
+    u0 = np.asarray(u0, f32).reshape(-1)
+    n = len(cdf)
+    if n == 0:
+        raise ValueError("an empty table picks nothing")
+    Q = int(cdf[n - 1])
+    j = np.zeros(len(u0), np.int64)
+    if Q == 0 or Q > MAX_CDF:
+        return j, np.zeros(len(u0), u32), Q
+    t = np.minimum((u0 * f32(Q)).astype(f32).astype(u32), u32(Q - 1))
+    j = search_cdf(t, cdf)
+    below = np.where(j > 0, cdf[np.maximum(j - 1, 0)], u32(0)).astype(u32)
+    q = (cdf[j].astype(u64) - below.astype(u64)).astype(u32)   # wrapping
+    return j, q, Q
+
+
 def barycentrics(u1, u2):
     """(bu, bv) of a triangle's point: su = sqrt(u1), bv = u2 su, bu = su - bv; the point is (a + bu b) + bv c"""
     u1, u2 = np.asarray(u1, f32), np.asarray(u2, f32)
@@ -126,11 +206,14 @@ def points(E, u1, u2):
     return np.where(tri, q_tri, q_sph).astype(f32), np.where(tri, ne_tri, ne_sph).astype(f32)
 
 
-def rays(emitters, surf, first_sample, samples, seeds=None, offset=1e-3, shorten=1e-3):
+def rays(emitters, surf, first_sample, samples, seeds=None, offset=1e-3, shorten=1e-3, cdf=None):
     """(origins (n, 3), directions (n, 3), bounds (n,), contributions (n, 4)) of the items (surfel, sample), surfel-major -- item
     i * samples + k is sample ``first_sample`` + k of ``surf[i]`` --: what rb_light_rays returns.  A lit item has a bound above
     0 and its unoccluded contribution; a dark one the bound 0 and +0 +0 +0; the fourth component is 1 for a valid item.  An
-    invalid item (an invalid surfel, section 16.1) has its surfel's position as given and direction 0 0 0."""
+    invalid item (an invalid surfel, section 16.1) has its surfel's position as given and direction 0 0 0.
+    ``cdf``: a uint32 table of pick weights, one inclusive entry per emitter (``emitter_cdf``, or any contents): what
+    rb_light_rays_cdf returns (section 23) -- the pick by ``pick_cdf``, the factor float(Q) / float(q) in place of float(N); an
+    item the table leaves without a pick is dark and has direction 0 0 0, as every item of an empty table."""
     em = np.asarray(emitters, dtype=abi.EMITTER).reshape(-1)
     n_emit = len(em)
     if n_emit > abi.MAX_EMITTERS:
@@ -157,8 +240,17 @@ def rays(emitters, surf, first_sample, samples, seeds=None, offset=1e-3, shorten
     if n_emit == 0 or n == 0:
         return org, d, tmax, contrib
     with np.errstate(all="ignore"):
-        fn = f32(n_emit)
-        E = em[pick(dr["u0"], n_emit)]
+        if cdf is None:
+            fn = f32(n_emit)
+            E = em[pick(dr["u0"], n_emit)]
+        else:
+            cdf = np.asarray(cdf, u32).reshape(-1)
+            if len(cdf) != n_emit:
+                raise ValueError("cdf: one entry per emitter is needed")
+            j, q, Q = pick_cdf(dr["u0"], cdf)
+            valid = valid & (q != 0)   # from here on: the items that have a pick
+            fn = (f32(Q) / q.astype(f32)).astype(f32)
+            E = em[j]
         area = E["area"]
         tri = E["kind"] == abi.HIT_TRIANGLE
         good = (np.isfinite(E["a"]).all(1) & np.isfinite(E["b"]).all(1) & np.isfinite(E["c"]).all(1) & np.isfinite(E["emissive"]).all(1)

@@ -21,7 +21,7 @@ import numpy as np
 from . import abi
 from ._lib import load
 from .bvh import own_tree_readback, sphere_tree_readback
-from ._marshal import (SEEDS, Form, device_new, device_tensor, download, grid_records, host_in, host_out, host_ptr, is_tensor, probe_records,
+from ._marshal import (CDF, SEEDS, Form, device_new, device_tensor, download, grid_records, host_in, host_out, host_ptr, is_tensor, probe_records,
                        ray_records, surfel_records, torch_device, upload)
 
 
@@ -617,6 +617,23 @@ class Engine:
         self._check(self._lib.rb_scene_emitters(self._h, host_ptr(table), len(table), C.byref(count)))
         return table
 
+    def scene_emitter_cdf(self, out=None):
+        """rb_scene_emitter_cdf: the pick weights by power of the scene's emitter table (``direct.emitter_cdf`` of
+        ``scene_emitters``), made on the device by the first call that needs them after an update ->
+        uint32[count].  ``out``: a (capacity,) int32 or uint32 tensor on the engine's device selects
+        rb_scene_emitter_cdf_device: (out, count) comes back, as ``scene_emitters`` has it."""
+        if out is not None:
+            dev = self.query_device
+            out, op = device_tensor("out", out, CDF, dev)
+            cnt = device_new(np.int32, 1, dev)
+            self._device_call(self._lib.rb_scene_emitter_cdf_device, op, len(out), cnt.data_ptr())
+            return out, int(cnt.cpu().numpy().view(np.uint32)[0])
+        count = C.c_size_t(0)
+        self._check(self._lib.rb_scene_emitter_cdf(self._h, None, 0, C.byref(count)))
+        table = np.zeros(count.value, dtype=CDF)
+        self._check(self._lib.rb_scene_emitter_cdf(self._h, host_ptr(table), len(table), C.byref(count)))
+        return table
+
     @staticmethod
     def _light_params(offset, shorten, mask=abi.MASK_ALL):
         prm = np.zeros(1, dtype=abi.LIGHT_PARAMS)
@@ -624,7 +641,7 @@ class Engine:
         return prm
 
     def direct_light(self, points, normals, samples, emitters=None, first_sample=0, seeds=None, offset=1e-3, shorten=1e-3,
-                     mask=abi.MASK_ALL, out=None):
+                     mask=abi.MASK_ALL, out=None, pick="uniform"):
         """rb_direct_light: what reaches (m, 3) surface points directly from the lights, by ``samples`` shadow rays per point,
         each aimed at a point drawn on a uniformly picked emitter and walked by rb_occluded among the stages of ``mask`` ->
         abi.RADIANCE[m] (``sum`` over the samples, ``weight``: the valid samples; sum / weight is the direct irradiance over
@@ -632,10 +649,23 @@ class Engine:
         (``scene_emitters``), or an abi.EMITTER table of the caller's -- one light, or one group of lights, gets a map of its
         own.  ``shorten``: the fraction of its length a shadow ray ends short of the sampled point.  Torch tensors on the
         engine's device for the points and normals, the table ((n, 16) float32) or ``out`` ((m, 4) float32) go to
-        rb_direct_light_device: nothing crosses to the host."""
+        rb_direct_light_device: nothing crosses to the host.
+        ``pick``: how a sample picks its emitter (DESIGN.md section 23) -- "uniform": rb_direct_light as it always was;
+        "power": rb_direct_light_cdf by the table's power, the scene's kept weights (``scene_emitter_cdf``) or those made for
+        the caller's table; or the caller's own inclusive weights beside the caller's ``emitters``, a uint32 array or an
+        int32 / uint32 tensor with one entry per emitter.  The estimate keeps its mean as long as every emitter that can
+        light a point keeps a weight above 0."""
         samples, first_sample = _sample_range(samples, first_sample)
         surf = surfel_records(points, normals)
-        f = Form(self.query_device, surf, seeds, emitters, out)
+        weights = None
+        if isinstance(pick, str):
+            if pick not in ("uniform", "power"):
+                raise ValueError('pick: "uniform", "power" or a table of weights')
+        elif emitters is None:
+            raise ValueError("pick: a table of weights goes with a table of emitters")
+        else:
+            weights = pick
+        f = Form(self.query_device, surf, seeds, emitters, out, weights)
         surf, fp = f.input("points / normals", surf, abi.SURFEL)
         n = len(surf)
         table, tp, n_emit = None, None, 0
@@ -650,7 +680,15 @@ class Engine:
         seeds, sp = f.optional("seeds", seeds, SEEDS, n)
         res, op = f.output("out", out, abi.RADIANCE, n)
         prm = self._light_params(offset, shorten, mask)
-        self._query(f, "rb_direct_light", tp, n_emit, fp, sp, n, prm.ctypes.data, first_sample, samples, op)
+        if isinstance(pick, str) and pick == "uniform":
+            self._query(f, "rb_direct_light", tp, n_emit, fp, sp, n, prm.ctypes.data, first_sample, samples, op)
+            return res
+        cp = None
+        if weights is not None:
+            if f.on_device and not is_tensor(weights):
+                weights = upload(host_in("pick", weights, CDF)[0].view(np.int32), np.dtype(np.int32), self.query_device)
+            weights, cp = f.input("pick", weights, CDF, n_emit)
+        self._query(f, "rb_direct_light_cdf", tp, cp, n_emit, fp, sp, n, prm.ctypes.data, first_sample, samples, op)
         return res
 
     # ---- lightmap texels made on the device (rb_abi.h)
@@ -1049,11 +1087,23 @@ def hemisphere_rays_device(points, normals, samples, first_sample=0, seeds=None,
     return rays, seeds_out
 
 
-def light_rays(emitters, points, normals, samples, first_sample=0, seeds=None, offset=1e-3, shorten=1e-3, device=-1):
+def emitter_cdf(emitters, device=-1):
+    """rb_emitter_cdf: the pick weights by power of an abi.EMITTER table, no engine -> uint32[n], inclusive (DESIGN.md section
+    23).  ``direct.emitter_cdf`` is its numpy model."""
+    f, call = _engineless(device)
+    table, tp = f.input("emitters", emitters, abi.EMITTER)
+    cdf = np.zeros(len(table), dtype=CDF)
+    call("rb_emitter_cdf", tp, len(table), host_ptr(cdf))
+    return cdf
+
+
+def light_rays(emitters, points, normals, samples, first_sample=0, seeds=None, offset=1e-3, shorten=1e-3, device=-1, cdf=None):
     """rb_light_rays: the generator of direct_light alone, no engine -- (abi.RAY[m * samples], float32 bounds[m * samples],
     float32 contributions (m * samples, 4)) of an abi.EMITTER table and (m, 3) points and normals, item i * samples + k: the
     shadow ray's origin and direction (0 0 0: an invalid item), the bound rb_occluded walks it to (0: a dark item) and the
-    unoccluded contribution with 1 for a valid item behind it.  ``direct.rays`` is its numpy model."""
+    unoccluded contribution with 1 for a valid item behind it.  ``direct.rays`` is its numpy model.  ``cdf``: None for the
+    uniform pick, or rb_light_rays_cdf's weighted one: "power", or uint32 inclusive weights, one per
+    emitter."""
     f, call = _engineless(device)
     table, tp = f.input("emitters", emitters, abi.EMITTER)
     surf, fp = f.input("points", surfel_records(np.asarray(points, np.float32), np.asarray(normals, np.float32)), abi.SURFEL)
@@ -1061,8 +1111,18 @@ def light_rays(emitters, points, normals, samples, first_sample=0, seeds=None, o
     tmax, contrib = np.zeros(len(rays), dtype=np.float32), np.zeros((len(rays), 4), dtype=np.float32)
     seeds, sp = f.optional("seeds", seeds, SEEDS, len(surf))
     prm = Engine._light_params(offset, shorten)
-    call("rb_light_rays", tp, len(table), fp, sp, len(surf), prm.ctypes.data, int(first_sample), int(samples), host_ptr(rays), host_ptr(tmax),
-         host_ptr(contrib))
+    if cdf is None:
+        call("rb_light_rays", tp, len(table), fp, sp, len(surf), prm.ctypes.data, int(first_sample), int(samples), host_ptr(rays),
+             host_ptr(tmax), host_ptr(contrib))
+        return rays, tmax, contrib
+    if isinstance(cdf, str):
+        if cdf != "power":
+            raise ValueError('cdf: None, "power" or a table of weights')
+        cp = None
+    else:
+        cdf, cp = f.input("cdf", cdf, CDF, len(table))
+    call("rb_light_rays_cdf", tp, cp, len(table), fp, sp, len(surf), prm.ctypes.data, int(first_sample), int(samples), host_ptr(rays),
+         host_ptr(tmax), host_ptr(contrib))
     return rays, tmax, contrib
 
 
