@@ -569,7 +569,8 @@ int rb_debug_triangle_trip_vec(uint32_t n, uint32_t seed, uint32_t uv, uint32_t*
  * the engine's single node and the origin region of its current camera and spheres: out[4 i + b] = ray i's candidate bits of
  * block b of 32 slots (bit k: slot first + 32 b + k; 0 for a block the list does not have), list2 = {first, end} of the node's list.  Conservative: every slot whose
  * triangle the reference's test accepts for the ray has its bit set.  RB_ERR_INVALID_OPTIONS if this engine's scene does not
- * sift (more than one node, a list beyond 128 slots, fewer than 4 live triangles, nothing to reject, RB_TRI_FILTER=0). */
+ * sift (more than one node, a list beyond 128 slots, fewer than 4 live triangles, nothing to reject, a scene that carries u, v --
+ * only the flat kernels sift --, RB_TRI_FILTER=0). */
 int rb_debug_tri_filter(rb_engine* e, const float* rays, uint32_t n, uint32_t* out, uint32_t* list2);
 /* Test hook: the root box of the single-node walk on `n` (at most 2^24) rays of six floats {origin, direction} and the box
  * box6 = {bmin, bmax}: out[i] bit 0 = the walk's slab test on its own reciprocals, bit 1 = the rule by which the single-node

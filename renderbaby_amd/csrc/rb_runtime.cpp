@@ -1333,7 +1333,8 @@ int rb_debug_tri_filter(rb_engine* e, const float* rays, uint32_t n, uint32_t* o
     if (int rc = require_ready(e)) return rc;
     if (int rc = ensure_prepared(e)) return rc;
     const rb::KParams p = make_params(e, 0, 0, e->cur, e->cur);
-    if (p.sift == 0u) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "this engine's scene does not sift its triangle list");
+    // (a table may stand while the scene carries u, v: only the flat kernels sift, plan_launch)
+    if (p.sift == 0u || p.no_uv == 0u) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "this engine's scene does not sift its triangle list");
     if (n == 0u) return RB_OK;
     if (n > (1u << 22)) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "at most 2^22 rays");
     HIP_TRY(e, hipStreamSynchronize(e->stream));

@@ -12,7 +12,10 @@ inside the root box.  The staged form is the one that sifts, so every launch res
 Beside the frames: the trip of pass 2, which takes the record in vector registers, against the compiler-laid triangle test on the
 triples of tests/test_gpu_triangle_trip.py, every word; and pass 1 on the device (rb_debug_tri_filter) against the float32 reference
 test -- no accepted slot may be missing from a ray's mask -- and against the numpy model, whose masks may differ in at most 1 % of
-the bits (the approximate reciprocal is not the model's), or the model is not the kernel."""
+the bits (the approximate reciprocal is not the model's), or the model is not the kernel.  That comparison runs on the Cornell
+table and on the named tables of tests/_tri_filter_cases.py (groups of 1 to 4, bent groups, open groups between closed ones, dead
+slots, a list from slot 7, 2 to 4 blocks, scenes far away, small and large), there under rays aimed at the triangles' edges and
+vertices on grazing rays; each of those scenes is also rendered three ways at 33 x 17."""
 import contextlib
 import dataclasses
 import os
@@ -28,7 +31,7 @@ pytestmark = pytest.mark.gpu
 
 FLAT, SIFT, STAGED = abi.TRACE_FORM_FLAT, abi.TRACE_FORM_SIFT, abi.TRACE_FORM_STAGED
 SIZES = [(64, 48), (33, 17)]
-SPP, DEPTH = 4, 8
+SPP, DEPTH = T.SPP, T.DEPTH
 
 
 def _u32(a):
@@ -78,40 +81,7 @@ def _three_ways(scene, sifts):
 
 
 # ----------------------------------------------------------------------------------- the scenes ---
-def _soup(n, w, h, seed=7, extra=()):
-    """n ordinary triangles (pairs of them quads, the rest singles) scattered in front of the camera in one node, two spheres
-    and a sky, so that paths bounce between triangles, spheres and nothing; `extra`: triangles appended as they are"""
-    rng = np.random.default_rng(seed + n)
-    tris = []
-    while len(tris) < n:
-        c = rng.uniform((-3, 0.5, -7), (3, 5.5, -2))
-        a, b = rng.normal(size=3), rng.normal(size=3)
-        a *= rng.uniform(0.4, 1.6) / np.linalg.norm(a)
-        b -= a * (a @ b) / (a @ a)
-        b *= rng.uniform(0.4, 1.6) / np.linalg.norm(b)
-        q = scenes._quad(tuple(c - a - b), tuple(c + a - b), tuple(c + a + b), tuple(c - a + b))
-        tris += q if n - len(tris) >= 2 and rng.uniform() < 0.7 else q[:1]
-    tris = tris[:n] + list(extra)
-    sp = np.zeros(2, dtype=abi.SPHERE)
-    sp[0]["center"], sp[0]["radius"] = (-1.2, 1.0, -3.0), 0.8
-    sp[0]["material"] = scenes.sphere_material("mirror", (0.9, 0.9, 0.9))
-    sp[1]["center"], sp[1]["radius"] = (1.4, 2.5, -4.0), 0.7
-    sp[1]["material"] = scenes.sphere_material("plastic", (0.3, 0.6, 0.9))
-    u = scenes.make_uniforms(w, h, SPP, DEPTH, cam_pos=(0, 3, 5), cam_dir=(0, 0, -1), ground_enabled=0, sky=(0.5, 0.7, 1.0))
-    half = len(tris) // 2
-    groups = [(scenes.material(**scenes.KHAKI), tris[:half]), (scenes.material(**scenes.GREEN), tris[half:])] if half else \
-        [(scenes.material(**scenes.KHAKI), tris)]
-    s = scenes._finish("soup", u, sp, np.zeros(0, dtype=abi.POINT_LIGHT), groups)
-    assert len(s.bvh_nodes) == 1 and int(s.bvh_nodes["primitive_count"][0]) == len(tris)
-    return s
-
-
-NAN = float("nan")
-ODD = [((0, 1, -4), (0, 1, -4), (0, 1, -4)),                     # a point
-       ((-1, 1, -4), (0, 1, -4), (1, 1, -4)),                    # a segment: N = 0
-       ((NAN, 1, -4), (1, 1, -4), (0, 2, -4)),                   # a NaN vertex
-       ((-1e30, -1e30, -9), (1e30, -1e30, -9), (0, 1e30, -9)),   # beyond the range the bounds are claimed for
-       ((0, 0, -5), (0, 0, -5), (1, 1, -5))]
+_soup, ODD = T._soup, T.ODD      # (tests/_tri_filter_cases.py: the CPU tests build their tables from the same scenes)
 
 
 @pytest.mark.parametrize("w,h", SIZES)
@@ -214,6 +184,47 @@ def test_device_masks_hold_every_accepted_hit_and_are_the_models():
             assert share <= 0.01, (what, share)
     finally:
         e.close()
+
+
+@pytest.mark.parametrize("name", T.tables())
+def test_device_masks_on_other_tables(name):
+    scene = T.table_scene(name)
+    (groups, reg, tri), (list_first, list_end) = T.table_of(name)
+    rng = np.random.default_rng([36, T.tables().index(name)])       # (tests/test_tri_filter_model.py holds the model on the same rays)
+    aimed = T.aimed_rays(tri, reg, rng)[:2]
+    families = [("aimed", aimed, False), ("inside the region", T.region_rays(reg, 20_000, rng), True),
+                ("from the triangles", T.surface_rays(tri, 20_000, rng), True),
+                # held to the model like the random families, for the same reason -- one rule, two reciprocals: on the bent table
+                # these rays are where the cone's s decides (tests/test_tri_filter_model.py shows how much of the mask hangs on it)
+                ("along the edges", T.edge_rays(tri, reg, 10_000, rng), True)]
+    rc = RenderConfig.from_scene(scene)
+    e = Engine.new(rc, queue_batch=256)
+    try:
+        e.render(rc)
+        assert e.trace_form() & SIFT, (name, e.trace_form())
+        for what, (o, d), like_the_model in families:
+            dev, first = e.tri_filter_masks(o, d)
+            assert first == list_first == int(scene.bvh_nodes["first_primitive"][0])
+            assert dev.shape == (list_end - list_first, len(o))
+            ot, dt = np.ascontiguousarray(o.T), np.ascontiguousarray(d.T)
+            acc, model = T._accepted(tri, ot, dt), T.M.candidate_mask(groups, reg, ot, dt)
+            assert not acc[~tri[3]].any()                            # a dead slot accepts nothing; its candidate bit is free: pass 2 skips it
+            assert not (acc & ~dev).any(), (name, what, "accepted hits missing from the device's mask", int((acc & ~dev).sum()))
+            share = float((dev != model)[tri[3]].mean())
+            print(f"{name}, {what}: {len(o)} rays, {int(acc.sum())} accepted, device candidates per ray {dev.sum(0).mean():.2f}, "
+                  f"device and model differ in {share:.5%} of the live slots' bits")
+            assert not dev.all(), (name, what, "pass 1 rejects nothing")
+            if like_the_model:
+                assert share <= 0.01, (name, what, share)
+    finally:
+        e.close()
+
+
+@pytest.mark.parametrize("name", [n for n in T.tables() if n not in ("soup33", "soup64", "soup128")])   # (those: test_single_nodes)
+def test_other_tables_three_ways(name):
+    scene = T.table_scene(name)
+    assert (scene.width, scene.height) == (33, 17)
+    _three_ways(scene, True)                           # (for `offset` and `mixed` the oracle is the judge of what the list is)
 
 
 def test_scenes_that_do_not_sift_say_so():

@@ -12,7 +12,11 @@ missing from a candidate mask.  Zero, not few.  CPU only.
    products of a slab value would overflow one by one, so such a lane must take every slot;
  * the Cornell box's table: rays from inside the box, from the camera and from under the light quad's 0.01 gap;
  * every ray family of tests/_edge_scenes.py against that scene's table, and tests/_root_box_cases.py's origins and directions
-   (+-0, subnormal, infinite and NaN components; faces, edges and corners of the box) against the Cornell table.
+   (+-0, subnormal, infinite and NaN components; faces, edges and corners of the box) against the Cornell table;
+ * the tables of tests/_tri_filter_cases.py's named scenes -- groups of 1 to 4, open groups between closed ones, dead slots, a
+   list that starts at slot 7, scenes far from the origin, 2^-10 and 2^10 as large -- under the rays aimed at their triangles' edges
+   and vertices on grazing rays, and two random families.  The conditions that keep the aimed family from being empty are checked
+   here, by the reference test alone.
 
 The constants pass 1 rests on are pinned as tests/test_margin_bound.py pins the chunked walk's."""
 import os
@@ -23,6 +27,7 @@ import pytest
 from renderbaby_amd import scenes
 from renderbaby_amd import tri_filter_model as M
 from tests import _edge_scenes, _root_box_cases
+from tests import _tri_filter_cases as T
 from tests._tri_filter_cases import MC, F32, ROOT, _tool, _prepared, _scene_table, _hold, _unit, tiny_component_rays
 
 
@@ -203,3 +208,61 @@ def test_edge_scene_families():
                 assert acc.any() and cand.all()
                 cand, acc = _hold(_scene_table(sub, o), np.asarray(o, F32), _unit(np.asarray(d, F32) + F32([1e-3, 2e-3, 0])), "aimed, tilted")
                 assert acc.any() and cand.sum(0).mean() < 0.25 * cand.shape[0], "the wall's quads are not sifted"
+
+
+# ------------------------------------------------------------------------- the named tables ---
+def test_every_group_size_occurs_and_every_table_sifts():
+    sizes, blocks = set(), {}
+    for name in T.tables():
+        (groups, reg, tri), (first, end) = T.table_of(name)
+        assert sum(c for _, c, _ in groups) == end - first == len(tri[0])
+        closed = [c for _, c, g in groups if g["closed"][0]]
+        assert int(tri[3].sum()) >= M.MIN_LIVE and closed and bool(reg["on"][0]), (name, "the model says this list does not sift")
+        sizes |= set(closed)
+        blocks[name] = (end - first + 31) // 32
+    assert sizes == {1, 2, 3, 4}, sizes
+    assert [blocks[n] for n in T.SOUPS] == [2, 2, 4, 4]
+    groups, _, tri = T.table_of("mixed")[0]
+    kinds = [bool(g["closed"][0]) for _, _, g in groups]
+    assert kinds[0] and kinds[-1] and not all(kinds[1:-1]) and int((~tri[3]).sum()) == 1, "open groups between closed ones, one dead slot"
+    (_, _, tri), (first, end) = T.table_of("offset")
+    assert (first, end) == (7, 47) and int((~tri[3]).sum()) == 3
+
+
+@pytest.mark.parametrize("name", T.tables())
+def test_named_tables(name):
+    tb, _ = T.table_of(name)
+    _, reg, tri = tb
+    rng = np.random.default_rng([36, T.tables().index(name)])
+    o, d, slot, outside = T.aimed_rays(tri, reg, rng)
+    assert len(o) <= T.MAX_AIMED and tri[3][slot].all()
+    lo, hi = reg["lo"][:, 0], reg["hi"][:, 0]
+    assert ((o > lo) & (o < hi)).all(), "an aimed origin outside the region"
+    accepts, refuses, outside_share = T.aimed_census(tri, o, d, slot, outside)
+    print(f"{name}: {len(o)} aimed rays; of the (ray, aimed slot) pairs the reference accepts {accepts:.1%}, refuses {refuses:.1%}; "
+          f"{outside_share:.2%} of the accepted have P outside the exact triangle")
+    assert accepts >= 0.10 and refuses >= 0.10 and outside_share >= 0.01, (name, accepts, refuses, outside_share)
+    cand, _ = _hold(tb, o, d, f"{name}, aimed")
+    assert not cand.all(), "pass 1 rejects nothing of the aimed rays"
+    cand, acc = _hold(tb, *T.region_rays(reg, 20_000, rng), f"{name}, inside the region")
+    assert acc.any() and cand.mean() < 0.5, "the box test no longer sifts this table"
+    _hold(tb, *T.surface_rays(tri, 20_000, rng), f"{name}, from the triangles")
+    _hold(tb, *T.edge_rays(tri, reg, 10_000, rng), f"{name}, along the edges")
+
+
+def test_rays_along_the_edges_of_bent_groups_see_the_sign_of_s():
+    # what tests/test_gpu_tri_filter.py's comparison of the device's masks with the model's rests on for `lb = |d . n| - s`: on
+    # the bent table a model with the sign turned gives other masks in a large share of the bits of this family (on planar
+    # groups, s = 2e-6, in a few of a million), so a kernel with that sign cannot stay within 1 % of the model there
+    import types
+    src = open(M.__file__).read()
+    assert src.count('lb = np.abs(y) - grp["s"]') == 1
+    turned = types.ModuleType("tri_filter_model_turned")
+    exec(compile(src.replace('lb = np.abs(y) - grp["s"]', 'lb = np.abs(y) + grp["s"]'), turned.__name__, "exec"), turned.__dict__)
+    (groups, reg, tri), _ = T.table_of("bent")
+    assert [c for _, c, _ in groups] == [2] * 6 and all(8e-4 < float(g["s"][0]) < 1e-3 for _, _, g in groups)
+    o, d = T.edge_rays(tri, reg, 10_000, np.random.default_rng(36))
+    ot, dt = np.ascontiguousarray(o.T), np.ascontiguousarray(d.T)
+    share = float((M.candidate_mask(groups, reg, ot, dt) != turned.candidate_mask(groups, reg, ot, dt)).mean())
+    print(f"bent, along the edges: {len(o)} rays, the sign of s turned changes {share:.1%} of the bits")
+    assert len(o) > 4000 and share > 0.10
