@@ -1,7 +1,7 @@
 """Camera rays made on the device next to the same rays given by the caller:
 
     python tools/camera_rate.py [--configs c2,c3,lamp,c4] [--runs 5] [--samples 16] [--width 1920 --height 1080]
-                                [--out profiles/r13_camera_rate.txt]
+                                [--child-timeout 300] [--out profiles/r13_camera_rate.txt]
 
 One process per configuration.  In it, at --width x --height, a thin-lens PERSPECTIVE camera where the scene's own camera
 stands, and two ways to the same paths:
@@ -20,20 +20,12 @@ from rb_last_camera_rays_ms; one warm-up pair, then `runs` alternating pairs, me
 the camera form's median is at most the ray form's median plus the larger of the two spreads plus the generator's median.  The
 exit status says whether it held for every configuration.
 """
-import argparse, os, statistics, subprocess, sys
+import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _rate import Report, alternating, child_argv, child_exit, child_header, med, med_text, run_children, scene_of
 
 HEADER = (f"{'scene':6} {'pixels':>9} {'spp':>4}  {'camera kernel':13} {'ms':>18}  {'generator ms':>18}  {'ray kernel':12} {'ms':>18}  {'rays* ms':>18}  "
           f"{'camera/rays':>11}  held")
-
-
-def scene_of(name):
-    from renderbaby_amd import refscenes, scenes
-    return {"c2": scenes.cornell_c2, "c3": scenes.mesh_c3, "c4": scenes.spheres_scene, "lamp": refscenes.ref_lamp}[name]()
-
-
-def med(xs):
-    return statistics.median(xs), max(xs) - min(xs)
 
 
 def one(name, width, height, samples, runs):
@@ -61,23 +53,20 @@ def one(name, width, height, samples, runs):
     reordered[:whole * samples] = records[:whole * samples].view(n // 64, 64, samples, 8).permute(0, 2, 1, 3).reshape(-1, 8)
     out_c = torch.empty((n, 4), dtype=torch.float32, device=dev)
     out_r = torch.empty((n * samples, 4), dtype=torch.float32, device=dev)
-    ms, names = {"camera": [], "gen": [], "rays": [], "rays*": []}, {}
-    for run in range(runs + 1):
-        for which in (("camera", "rays", "rays*") if run % 2 == 0 else ("rays*", "rays", "camera")):
-            if which == "camera":
-                e.trace_camera(cam, samples, out=out_c)
-            else:
-                e.trace_ray_records(records if which == "rays" else reordered, samples=1, out=out_r)
-            names[which] = e.last_query_kernel_name()
-            if run:
-                ms[which].append(e.last_query_ms())
-                if which == "camera":
-                    ms["gen"].append(e.last_camera_rays_ms())
-    (mc, sc), (mg, sg), (mr, sr), (mi, si) = med(ms["camera"]), med(ms["gen"]), med(ms["rays"]), med(ms["rays*"])
+
+    def measure(which):   # (kernel ms, the generator's share, the kernel's name)
+        if which == "camera":
+            e.trace_camera(cam, samples, out=out_c)
+        else:
+            e.trace_ray_records(records if which == "rays" else reordered, samples=1, out=out_r)
+        return e.last_query_ms(), e.last_camera_rays_ms(), e.last_query_kernel_name()
+    got = alternating(("camera", "rays", "rays*"), runs, measure)
+    (cam_ms, gen, cam_k), (ray_ms, _, ray_k), (item_ms, _, _) = (tuple(zip(*got[which])) for which in ("camera", "rays", "rays*"))
+    (mc, sc), mg, (mr, sr) = med(cam_ms), med(gen)[0], med(ray_ms)
     ok = mc <= mr + max(sc, sr) + mg
     e.close()
-    return (f"{name:6} {n:9d} {samples:4d}  {names['camera']:13} {mc:9.3f} ({sc:6.3f})  {mg:9.3f} ({sg:6.3f})  {names['rays']:12} {mr:9.3f} ({sr:6.3f})  {mi:9.3f} ({si:6.3f})  "
-            f"{mc / mr:11.3f}  {ok}"), ok
+    return (f"{name:6} {n:9d} {samples:4d}  {cam_k[-1]:13} {med_text(cam_ms)}  {med_text(gen)}  {ray_k[-1]:12} {med_text(ray_ms)}  "
+            f"{med_text(item_ms)}  {mc / mr:11.3f}  {ok}"), ok
 
 
 def main():
@@ -87,45 +76,27 @@ def main():
     ap.add_argument("--samples", type=int, default=16)
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--child-timeout", type=int, default=300, help="seconds one configuration's process may take")
     ap.add_argument("--out", default=None)
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--header", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
-    if a.child:   # one configuration in this process: its line, the verdict at its end
+    if a.child:   # one configuration in this process: its line, the verdict as the exit status
         if a.header:
-            from renderbaby_amd import engine
-            print(f"# {engine.device_name(0)}", flush=True)
-        print(one(a.child, a.width, a.height, a.samples, a.runs)[0], flush=True)
-        return 0
+            child_header()
+        line, ok = one(a.child, a.width, a.height, a.samples, a.runs)
+        print(line, flush=True)
+        child_exit(ok)
     from renderbaby_amd._lib import source_fingerprint   # (this process never opens the device: the children do)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    out_file = open(a.out, "w") if a.out else None
-
-    def say(s=""):
-        print(s, flush=True)
-        if out_file:   # line by line: a run that is cut short keeps what it measured
-            out_file.write(s + "\n")
-            out_file.flush()
-    say(f"# library sources {source_fingerprint()}; {a.runs} alternating runs after one warm-up pair; kernel ms as median (max - min)")
-    say("# camera = rb_trace_camera_device (generator + trace + sum, rb_last_query_ms; generator alone: rb_last_camera_rays_ms);")
-    say("# rays = rb_trace_rays_device, samples = 1, on the camera's n x spp records made by rb_camera_rays; one process per scene")
-    say("# rays* = the same records in the camera form's item order, [64 pixels][sample][64]: recorded, not judged")
-    say(HEADER)
-    held = True
-    for i, name in enumerate(a.configs.split(",")):
-        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", name, "--runs", str(a.runs), "--samples", str(a.samples),
-                            "--width", str(a.width), "--height", str(a.height)] + (["--header"] if i == 0 else []), stdout=subprocess.PIPE, text=True)
-        for line in p.stdout.splitlines():
-            say(line)
-        if p.returncode != 0:
-            say(f"{name:6} failed: exit status {p.returncode}")
-            held = False
-            break   # whatever ended that process may have left the device in a bad state: nothing more is started on it
-        held = held and p.stdout.rstrip().endswith("True")
-    say(f"# camera median <= ray median + max(spreads) + generator median for every scene: {held}")
-    if out_file:
-        out_file.close()
+    with Report(a.out) as r:
+        r.say(f"# library sources {source_fingerprint()}; {a.runs} alternating runs after one warm-up pair; kernel ms as median (max - min)")
+        r.say("# camera = rb_trace_camera_device (generator + trace + sum, rb_last_query_ms; generator alone: rb_last_camera_rays_ms);")
+        r.say("# rays = rb_trace_rays_device, samples = 1, on the camera's n x spp records made by rb_camera_rays; one process per scene")
+        r.say("# rays* = the same records in the camera form's item order, [64 pixels][sample][64]: recorded, not judged")
+        r.say(HEADER)
+        held, _ = run_children(r, lambda name, first: child_argv(__file__, name, a, ("runs", "samples", "width", "height"), first),
+                               a.configs.split(","), a.child_timeout)
+        r.say(f"# camera median <= ray median + max(spreads) + generator median for every scene: {held}")
     return 0 if held else 1
 
 

@@ -17,18 +17,7 @@ Then the quality figures of section 13: 256 x 256, depth 4, mean squared error o
 """
 import argparse, os, statistics, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
-
-def med(xs):
-    return statistics.median(xs), max(xs) - min(xs)
-
-
-def scene_of(name, w, h, spp):
-    from renderbaby_amd import scenes
-    s = scenes.cornell_c2() if name == "c2" else scenes.mesh_c3() if name == "c3" else None
-    if s is None:
-        raise SystemExit(f"unknown configuration {name}")
-    return s.with_params(width=w, height=h, spp=spp)
+from _rate import env, med, scene_of
 
 
 def tap_bytes(cls, iterations):
@@ -76,7 +65,7 @@ def main():
     for name in a.configs.split(","):
         for size in a.sizes.split(","):
             w, h = (int(x) for x in size.split("x"))
-            s = scene_of(name, w, h, a.spp)
+            s = scene_of(name).with_params(width=w, height=h, spp=a.spp)
             rc = RenderConfig.from_scene(s)
             e = Engine.new(rc, device=0)
             e.render(rc)
@@ -115,11 +104,10 @@ def main():
             p2, res = denoise.params(iterations=2), {"plain": [], "lds": []}
             for r in range(a.repeats + 1):
                 for v in ("plain", "lds"):
-                    os.environ["RB_DENOISE_VARIANT"] = v
-                    ms = run(p2)[0]
+                    with env("RB_DENOISE_VARIANT", v):
+                        ms = run(p2)[0]
                     if r:
                         res[v].append(ms)
-            os.environ.pop("RB_DENOISE_VARIANT", None)
             base = statistics.median(by_k[0])
             (pl, pls), (ld, lds) = med(res["plain"]), med(res["lds"])
             print(f"  steps 1 + 2 with prepare + finish: plain {pl:.3f} ({pls:.3f}) ms, LDS-staged {ld:.3f} ({lds:.3f}) ms; "

@@ -1,7 +1,8 @@
 """Direct light by shadow rays to the scene's emitters: what the stages cost, and how much noise the
 estimator removes.
 
-    python tools/direct_light_rate.py [--runs 5] [--samples 16] [--width 1920 --height 1080] [--out profiles/r26_direct_light_rate.txt]
+    python tools/direct_light_rate.py [--runs 5] [--samples 16] [--width 1920 --height 1080] [--child-timeout 300]
+                                      [--out profiles/r26_direct_light_rate.txt]
 
 Timings, kernel ms as median (max - min) of `runs` calls after a warm-up call:
 
@@ -19,17 +20,9 @@ height --, one surfel per sample so that the per-sample values come back; per po
 channels, and the ratio of the two variances: how many times fewer samples the direct estimator needs for the same noise.
 One process per scene.
 """
-import argparse, os, statistics, subprocess, sys
+import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
-
-def med(xs):
-    return f"{statistics.median(xs):9.3f} ({max(xs) - min(xs):6.3f})"
-
-
-def scene_of(name):
-    from renderbaby_amd import refscenes, scenes
-    return {"c2": scenes.cornell_c2, "c5": scenes.mesh_c5, "lamp": refscenes.ref_lamp, "cornell": scenes.cornell_c1}[name]()
+from _rate import Report, child_argv, child_exit, med_text, run_children, scene_of
 
 
 def engine_of(s):
@@ -56,7 +49,7 @@ def table(name, runs):
     e.close()
     kinds = {2: "triangles", 3: "spheres", 4: "lights"}
     what = ", ".join(f"{int((t['kind'] == k).sum())} {v}" for k, v in kinds.items())
-    return [f"table    {name:7} {len(s.bvh_triangles):8d} triangles {len(s.spheres):4d} spheres {len(s.lights):3d} lights -> {len(t):6d} emitters ({what})  {med(ms)} ms"]
+    return [f"table    {name:7} {len(s.bvh_triangles):8d} triangles {len(s.spheres):4d} spheres {len(s.lights):3d} lights -> {len(t):6d} emitters ({what})  {med_text(ms)} ms"]
 
 
 def stages(name, width, height, samples, runs):
@@ -95,9 +88,9 @@ def stages(name, width, height, samples, runs):
     fold = [a - g - w for a, g, w in zip(ms["all"], ms["gen"], ms["walk"])]
     lit = float((out[:, :3].sum(1) > 0).float().mean().item())
     e.close()
-    return [f"direct   {name:7} {n:8d} surfels x {samples:3d}, {len(tab)} emitters, {kernel}: all {med(ms['all'])} ms  generator {med(ms['gen'])}  "
-            f"walk alone {med(ms['walk'])}  fold (the rest) {med(fold)}; {100 * lit:.1f} % of the surfels lit",
-            f"openness {name:7} {n:8d} surfels x {samples:3d}, radius 1e20: all {med(ms['open'])} ms  generator {med(ms['open_gen'])}"]
+    return [f"direct   {name:7} {n:8d} surfels x {samples:3d}, {len(tab)} emitters, {kernel}: all {med_text(ms['all'])} ms  generator {med_text(ms['gen'])}  "
+            f"walk alone {med_text(ms['walk'])}  fold (the rest) {med_text(fold)}; {100 * lit:.1f} % of the surfels lit",
+            f"openness {name:7} {n:8d} surfels x {samples:3d}, radius 1e20: all {med_text(ms['open'])} ms  generator {med_text(ms['open_gen'])}"]
 
 
 def noise(name, points, samples):
@@ -132,6 +125,7 @@ def main():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--noise-points", type=int, default=64)
     ap.add_argument("--noise-samples", type=int, default=1024)
+    ap.add_argument("--child-timeout", type=int, default=300, help="seconds one child process may take")
     ap.add_argument("--out", default=None)
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
@@ -140,34 +134,16 @@ def main():
         lines = (table(name, a.runs) if kind == "table" else stages(name, a.width, a.height, a.samples, a.runs) if kind == "stages"
                  else noise(name, a.noise_points, a.noise_samples))
         print("\n".join(lines), flush=True)
-        return 0
+        child_exit()
     from renderbaby_amd._lib import source_fingerprint   # (this process never opens the device: the children do)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    out_file = open(a.out, "w") if a.out else None
-
-    def say(s=""):
-        print(s, flush=True)
-        if out_file:   # line by line: a run that is cut short keeps what it measured
-            out_file.write(s + "\n")
-            out_file.flush()
-    say(f"# library sources {source_fingerprint()}; kernel ms as median (max - min) of {a.runs} calls after a warm-up call; one process per line group")
-    say("# table: rb_scene_emitters after an rb_update (flag, scan, the wait for the total, scatter); direct: rb_direct_light_device, its generator's")
-    say("# share, rb_occluded_device alone on the same records and bounds, the fold as the rest; openness: rb_openness_hemisphere_device, the yardstick")
-    say("# noise: max_depth = 1, black sky, one surfel per sample; variance of the per-sample mean of the three channels, per floor point")
-    ok = True
-    for child in ("table:c5", "table:lamp", "stages:c2", "noise:cornell", "noise:lamp"):
-        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", child, "--runs", str(a.runs), "--samples", str(a.samples),
-                            "--width", str(a.width), "--height", str(a.height), "--noise-points", str(a.noise_points),
-                            "--noise-samples", str(a.noise_samples)], stdout=subprocess.PIPE, text=True)
-        for line in p.stdout.splitlines():
-            say(line)
-        if p.returncode != 0:
-            say(f"{child} failed: exit status {p.returncode}")
-            ok = False
-            break   # whatever ended that process may have left the device in a bad state: nothing more is started on it
-    if out_file:
-        out_file.close()
+    with Report(a.out) as r:
+        r.say(f"# library sources {source_fingerprint()}; kernel ms as median (max - min) of {a.runs} calls after a warm-up call; one process per line group")
+        r.say("# table: rb_scene_emitters after an rb_update (flag, scan, the wait for the total, scatter); direct: rb_direct_light_device, its generator's")
+        r.say("# share, rb_occluded_device alone on the same records and bounds, the fold as the rest; openness: rb_openness_hemisphere_device, the yardstick")
+        r.say("# noise: max_depth = 1, black sky, one surfel per sample; variance of the per-sample mean of the three channels, per floor point")
+        options = ("runs", "samples", "width", "height", "noise_points", "noise_samples")
+        ok, _ = run_children(r, lambda name, first: child_argv(__file__, name, a, options),
+                             ("table:c5", "table:lamp", "stages:c2", "noise:cornell", "noise:lamp"), a.child_timeout)
     return 0 if ok else 1
 
 

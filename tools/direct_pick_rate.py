@@ -1,7 +1,8 @@
 """Direct light with a weighted pick: what the pick by a table costs beside the uniform pick, what the
 table costs to make, and how much noise the pick by power removes.
 
-    python tools/direct_pick_rate.py [--runs 5] [--samples 16] [--width 1920 --height 1080] [--out profiles/r35_direct_pick_rate.txt]
+    python tools/direct_pick_rate.py [--runs 5] [--samples 16] [--width 1920 --height 1080] [--child-timeout 300]
+                                     [--out profiles/r35_direct_pick_rate.txt]
 
 Timings, kernel ms as median (max - min) of `runs` calls after a warm-up call, both picks in one process on the same surfels
 and samples -- the uniform pick, rb_direct_light_device as it always was, is the yardstick:
@@ -16,28 +17,24 @@ Noise, by direct_light_rate.py's method: one surfel per sample so that the per-s
 of the mean of the three channels under either pick, and the ratio uniform / power, on ground points of
 spheres_scene(n = 100 000) (993 emitters) and on 8 floor points of the feature scene (5 emitters).  One process per scene.
 """
-import argparse, os, statistics, subprocess, sys
+import argparse, os, statistics, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _rate import Report, child_argv, child_exit, med_text, run_children, scene_of
 
 
-def med(xs):
-    return f"{statistics.median(xs):9.3f} ({max(xs) - min(xs):6.3f})"
-
-
-def scene_of(name):
+def spheres(n, with_lights=False):
     import numpy as np
     from renderbaby_amd import abi, scenes
-    if name == "c2":
-        return scenes.cornell_c2()
-    if name == "feature":
-        return scenes.feature_scene()
-    s = scenes.spheres_scene(n=1_000_000 if name == "c4" else 100_000)
-    if name != "c4":
+    s = scenes.spheres_scene(n=n)
+    if not with_lights:
         return s
     lights = np.zeros(2, dtype=abi.POINT_LIGHT)   # the sphere arm twice over: the table then has two kinds
     lights["center"], lights["radius"] = [(-30.0, 40.0, 0.0), (30.0, 40.0, -5.0)], (1.0, 0.5)
     lights["material"]["emissive"] = [(50.0, 40.0, 30.0), (10.0, 20.0, 30.0)]
     return scenes.Scene(s.uniforms, s.spheres, lights, s.meshes, s.bvh_nodes, s.bvh_indices, s.bvh_triangles, s.uvs, name="c4 with lights")
+
+
+OWN = {"c4": lambda: spheres(1_000_000, with_lights=True), "c4like": lambda: spheres(100_000)}   # (not the table's c4)
 
 
 def engine_of(s):
@@ -59,7 +56,7 @@ def stages(name, width, height, samples, runs):
     import numpy as np
     import torch
     from renderbaby_amd import Change, RenderConfig, aov
-    s = scene_of(name).with_params(width=width, height=height, spp=1)
+    s = scene_of(name, OWN).with_params(width=width, height=height, spp=1)
     e, _ = engine_of(s)
     _, pts, nrm = aov.ambient_occlusion_surfels(s.uniforms, e.render_hits())
     if name == "c4":
@@ -90,16 +87,16 @@ def stages(name, width, height, samples, runs):
     e.close()
     share = lambda g, a: 100 * statistics.median(g) / statistics.median(a)
     return [f"direct   {name:7} {n:8d} surfels x {samples:3d}, {len(tab)} emitters ({what}), {kernel}:",
-            f"         uniform  all {med(ms['uni'])} ms  generator {med(ms['uni_gen'])}  ({share(ms['uni_gen'], ms['uni']):.1f} % of the call)",
-            f"         by power all {med(ms['pow'])} ms  generator {med(ms['pow_gen'])}  ({share(ms['pow_gen'], ms['pow']):.1f} % of the call); "
+            f"         uniform  all {med_text(ms['uni'])} ms  generator {med_text(ms['uni_gen'])}  ({share(ms['uni_gen'], ms['uni']):.1f} % of the call)",
+            f"         by power all {med_text(ms['pow'])} ms  generator {med_text(ms['pow_gen'])}  ({share(ms['pow_gen'], ms['pow']):.1f} % of the call); "
             f"generator x {statistics.median(ms['pow_gen']) / statistics.median(ms['uni_gen']):.2f}, call x {statistics.median(ms['pow']) / statistics.median(ms['uni']):.3f}",
-            f"table    {name:7} rb_scene_emitter_cdf of {len(cdf)} emitters, total {int(cdf[-1]) if len(cdf) else 0}: {med(ms['build'])} ms"]
+            f"table    {name:7} rb_scene_emitter_cdf of {len(cdf)} emitters, total {int(cdf[-1]) if len(cdf) else 0}: {med_text(ms['build'])} ms"]
 
 
 def noise(name, points, samples):
     import numpy as np
     from renderbaby_amd import aov, direct
-    s = scene_of(name)
+    s = scene_of(name, OWN)
     if name == "feature":
         pts = np.array([(x, -1.0, z) for x in (-1.5, 0.5) for z in (-3.0, -2.0, -1.0, 0.0)], np.float32)
         nrm = np.tile(np.float32([0, 1, 0]), (len(pts), 1))
@@ -131,6 +128,7 @@ def main():
     ap.add_argument("--samples", type=int, default=16)
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--child-timeout", type=int, default=300, help="seconds one child process may take")
     ap.add_argument("--out", default=None)
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
@@ -139,33 +137,15 @@ def main():
         lines = (stages(name, a.width, a.height, a.samples, a.runs) if kind == "stages"
                  else noise(name, 6, 65536) if name == "c4like" else noise(name, 8, 4096))
         print("\n".join(lines), flush=True)
-        return 0
+        child_exit()
     from renderbaby_amd._lib import source_fingerprint   # (this process never opens the device: the children do)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    out_file = open(a.out, "w") if a.out else None
-
-    def say(s=""):
-        print(s, flush=True)
-        if out_file:   # line by line: a run that is cut short keeps what it measured
-            out_file.write(s + "\n")
-            out_file.flush()
-    say(f"# library sources {source_fingerprint()}; kernel ms as median (max - min) of {a.runs} calls after a warm-up call; one process per line group")
-    say("# direct: rb_direct_light_device (uniform, the yardstick) and rb_direct_light_cdf_device with the scene's kept table (by power) on the same")
-    say("# surfels and samples, all three stages and the generator's share; table: rb_scene_emitter_cdf after an rb_update and rb_scene_emitters")
-    say("# noise: one surfel per sample; variance of the per-sample mean of the three channels under either pick, per point")
-    ok = True
-    for child in ("stages:c2", "stages:c4", "noise:c4like", "noise:feature"):
-        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", child, "--runs", str(a.runs), "--samples", str(a.samples),
-                            "--width", str(a.width), "--height", str(a.height)], stdout=subprocess.PIPE, text=True)
-        for line in p.stdout.splitlines():
-            say(line)
-        if p.returncode != 0:
-            say(f"{child} failed: exit status {p.returncode}")
-            ok = False
-            break   # whatever ended that process may have left the device in a bad state: nothing more is started on it
-    if out_file:
-        out_file.close()
+    with Report(a.out) as r:
+        r.say(f"# library sources {source_fingerprint()}; kernel ms as median (max - min) of {a.runs} calls after a warm-up call; one process per line group")
+        r.say("# direct: rb_direct_light_device (uniform, the yardstick) and rb_direct_light_cdf_device with the scene's kept table (by power) on the same")
+        r.say("# surfels and samples, all three stages and the generator's share; table: rb_scene_emitter_cdf after an rb_update and rb_scene_emitters")
+        r.say("# noise: one surfel per sample; variance of the per-sample mean of the three channels under either pick, per point")
+        ok, _ = run_children(r, lambda name, first: child_argv(__file__, name, a, ("runs", "samples", "width", "height")),
+                             ("stages:c2", "stages:c4", "noise:c4like", "noise:feature"), a.child_timeout)
     return 0 if ok else 1
 
 

@@ -2,7 +2,7 @@
 section 16.7):
 
     python tools/hemisphere_rate.py [--configs c2,c3,lamp,c4] [--runs 5] [--samples 16] [--surfels 1048576]
-                                    [--width 1920 --height 1080] [--out profiles/r16_hemisphere_rate.txt]
+                                    [--width 1920 --height 1080] [--child-timeout 300] [--out profiles/r16_hemisphere_rate.txt]
 
 One process per configuration.  In it the scene at --width x --height, `surfels` surfels spread evenly over the first hits of
 its pixel centres (Engine.render_hits; the normal turned towards the camera), and two ways to the same paths:
@@ -22,32 +22,21 @@ Then, in the same process, wall time end to end (a host clock around calls that 
 `wall_runs` calls after one warm-up call each, alternating): bake.irradiance against bake.irradiance_device on `wall_surfels`
 of those points, and aov.ambient_occlusion against aov.ambient_occlusion_device on the whole frame's first hits.
 """
-import argparse, os, statistics, subprocess, sys, time
+import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _rate import Report, alternating, child_argv, child_exit, child_header, med, med_text, run_children, scene_of
 
 HEADER = (f"{'scene':6} {'surfels':>9} {'spp':>4}  {'hemi kernel':13} {'ms':>18}  {'generator ms':>18}  {'ray kernel':12} {'ms':>18}  "
           f"{'hemi/rays':>9}  held")
 
 
-def scene_of(name):
-    from renderbaby_amd import refscenes, scenes
-    return {"c2": scenes.cornell_c2, "c3": scenes.mesh_c3, "c4": scenes.spheres_scene, "lamp": refscenes.ref_lamp}[name]()
-
-
-def med(xs):
-    return statistics.median(xs), max(xs) - min(xs)
-
-
 def wall(fns, runs):
     """seconds of each of `fns`, alternating, after one warm-up call each: [(median, spread), ...]"""
-    t = [[] for _ in fns]
-    for run in range(runs + 1):
-        for i, fn in (list(enumerate(fns)) if run % 2 == 0 else list(enumerate(fns))[::-1]):
-            t0 = time.perf_counter()
-            fn()
-            if run:
-                t[i].append(time.perf_counter() - t0)
-    return [med(x) for x in t]
+    def seconds(fn):
+        t0 = time.perf_counter()
+        fn()
+        return time.perf_counter() - t0
+    return [med(x) for x in alternating(fns, runs, seconds).values()]
 
 
 def one(name, width, height, samples, runs, n, wall_surfels, wall_runs):
@@ -56,7 +45,7 @@ def one(name, width, height, samples, runs, n, wall_surfels, wall_runs):
     import torch
     from renderbaby_amd import Engine, RenderConfig, aov, bake, engine
 
-    def progress(what):   # (stderr: the parent passes it through while it holds this process's lines back)
+    def progress(what):   # (stderr: the parent passes it through)
         print(f"[{name}] {what}", file=sys.stderr, flush=True)
     s = scene_of(name).with_params(width=width, height=height, spp=1)
     rc = RenderConfig.from_scene(s)
@@ -80,21 +69,18 @@ def one(name, width, height, samples, runs, n, wall_surfels, wall_runs):
     out_h = torch.empty((n, 4), dtype=torch.float32, device=dev)
     out_r = torch.empty((n * samples, 4), dtype=torch.float32, device=dev)
     progress("records made")
-    ms, names = {"hemi": [], "gen": [], "rays": []}, {}
-    for run in range(runs + 1):
-        for which in (("hemi", "rays") if run % 2 == 0 else ("rays", "hemi")):
-            if which == "hemi":
-                e.trace_hemisphere(tp, tn, samples, out=out_h)
-            else:
-                e.trace_ray_records(records, samples=1, out=out_r)
-            names[which] = e.last_query_kernel_name()
-            if run:
-                ms[which].append(e.last_query_ms())
-                if which == "hemi":
-                    ms["gen"].append(e.last_camera_rays_ms())
-    (mh, sh), (mg, sg), (mr, sr) = med(ms["hemi"]), med(ms["gen"]), med(ms["rays"])
+
+    def measure(which):   # (kernel ms, the generator's share, the kernel's name)
+        if which == "hemi":
+            e.trace_hemisphere(tp, tn, samples, out=out_h)
+        else:
+            e.trace_ray_records(records, samples=1, out=out_r)
+        return e.last_query_ms(), e.last_camera_rays_ms(), e.last_query_kernel_name()
+    got = alternating(("hemi", "rays"), runs, measure)
+    hemi, gen, rays = [v[0] for v in got["hemi"]], [v[1] for v in got["hemi"]], [v[0] for v in got["rays"]]
+    (mh, sh), mg, (mr, sr) = med(hemi), med(gen)[0], med(rays)
     ok = mh <= mr + max(sh, sr) + mg
-    lines = [f"{name:6} {n:9d} {samples:4d}  {names['hemi']:13} {mh:9.3f} ({sh:6.3f})  {mg:9.3f} ({sg:6.3f})  {names['rays']:12} {mr:9.3f} ({sr:6.3f})  "
+    lines = [f"{name:6} {n:9d} {samples:4d}  {got['hemi'][-1][2]:13} {med_text(hemi)}  {med_text(gen)}  {got['rays'][-1][2]:12} {med_text(rays)}  "
              f"{mh / mr:9.3f}  {ok}"]
     del records, out_r
     progress("kernels timed")
@@ -120,48 +106,27 @@ def main():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--wall-surfels", type=int, default=1 << 20)
     ap.add_argument("--wall-runs", type=int, default=3)
+    ap.add_argument("--child-timeout", type=int, default=300, help="seconds one configuration's process may take")
     ap.add_argument("--out", default=None)
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--header", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
-    if a.child:   # one configuration in this process: its lines, the verdict at the end of the first
+    if a.child:   # one configuration in this process: its lines, the verdict as the exit status
         if a.header:
-            from renderbaby_amd import engine
-            print(f"# {engine.device_name(0)}", flush=True)
+            child_header()
         lines, ok = one(a.child, a.width, a.height, a.samples, a.runs, a.surfels, min(a.wall_surfels, a.surfels), a.wall_runs)
         print("\n".join(lines), flush=True)
-        return 0
+        child_exit(ok)
     from renderbaby_amd._lib import source_fingerprint   # (this process never opens the device: the children do)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    out_file = open(a.out, "w") if a.out else None
-
-    def say(s=""):
-        print(s, flush=True)
-        if out_file:   # line by line: a run that is cut short keeps what it measured
-            out_file.write(s + "\n")
-            out_file.flush()
-    say(f"# library sources {source_fingerprint()}; {a.runs} alternating runs after one warm-up pair; kernel ms as median (max - min)")
-    say("# hemi = rb_trace_hemisphere_device (generator + trace + sum, rb_last_query_ms; generator alone: rb_last_camera_rays_ms);")
-    say("# rays = rb_trace_rays_device, samples = 1, on the surfels' n x spp records made by rb_hemisphere_rays; one process per scene")
-    say(f"# #wall lines: end-to-end seconds of the host path and of the device path, median (max - min) of {a.wall_runs} alternating calls after a warm-up call")
-    say(HEADER)
-    held = True
-    for i, name in enumerate(a.configs.split(",")):
-        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", name, "--runs", str(a.runs), "--samples", str(a.samples),
-                            "--surfels", str(a.surfels), "--width", str(a.width), "--height", str(a.height), "--wall-surfels", str(a.wall_surfels),
-                            "--wall-runs", str(a.wall_runs)] + (["--header"] if i == 0 else []), stdout=subprocess.PIPE, text=True)
-        for line in p.stdout.splitlines():
-            say(line)
-        if p.returncode != 0:
-            say(f"{name:6} failed: exit status {p.returncode}")
-            held = False
-            break   # whatever ended that process may have left the device in a bad state: nothing more is started on it
-        judged = [ln for ln in p.stdout.splitlines() if ln.startswith(name) and not ln.startswith("#")]
-        held = held and len(judged) == 1 and judged[0].rstrip().endswith("True")
-    say(f"# hemisphere median <= ray median + max(spreads) + generator median for every scene: {held}")
-    if out_file:
-        out_file.close()
+    with Report(a.out) as r:
+        r.say(f"# library sources {source_fingerprint()}; {a.runs} alternating runs after one warm-up pair; kernel ms as median (max - min)")
+        r.say("# hemi = rb_trace_hemisphere_device (generator + trace + sum, rb_last_query_ms; generator alone: rb_last_camera_rays_ms);")
+        r.say("# rays = rb_trace_rays_device, samples = 1, on the surfels' n x spp records made by rb_hemisphere_rays; one process per scene")
+        r.say(f"# #wall lines: end-to-end seconds of the host path and of the device path, median (max - min) of {a.wall_runs} alternating calls after a warm-up call")
+        r.say(HEADER)
+        options = ("runs", "samples", "surfels", "width", "height", "wall_surfels", "wall_runs")
+        held, _ = run_children(r, lambda name, first: child_argv(__file__, name, a, options, first), a.configs.split(","), a.child_timeout)
+        r.say(f"# hemisphere median <= ray median + max(spreads) + generator median for every scene: {held}")
     return 0 if held else 1
 
 

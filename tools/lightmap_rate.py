@@ -1,7 +1,7 @@
 """The lightmap bake next to the hemisphere form it is built on, and what the numpy model costs a caller:
 
     python tools/lightmap_rate.py [--configs lamp,cubes] [--atlases 1024,4096] [--runs 5] [--samples 16] [--tile 64]
-                                  [--model-atlas 1024] [--out profiles/r18_lightmap_rate.txt]
+                                  [--model-atlas 1024] [--child-timeout 300] [--out profiles/r18_lightmap_rate.txt]
 
 One process per scene.  `lamp`: the reference's lamp fixture with the uvs it carries (charts overlap: the owner rule decides).
 `cubes`: the cube example tiled --tile x --tile times, every cube's two textured faces in a cell of their own of the atlas
@@ -16,8 +16,9 @@ the larger of the two spreads plus the medians of surfels_ms and resolve_ms.  Th
 Reported beside, without a pass mark: the bytes the surfel stage writes per second (36 B per texel: surfel and owner), and the
 host seconds of the numpy model (lightmap.surfels) for the --model-atlas atlas: what a caller pays without the feature.
 """
-import argparse, os, statistics, subprocess, sys, time
+import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _rate import Report, alternating, child_argv, child_exit, child_header, med, med_text, run_children
 
 HEADER = (f"{'scene':6} {'tris':>7} {'atlas':>6} {'owned':>6} {'spp':>4}  {'bake ms':>18}  {'surfels ms':>16}  {'resolve ms':>16}  "
           f"{'hemisphere ms':>18}  {'bake/hemi':>9}  {'surfel TB/s':>11}  held")
@@ -46,10 +47,6 @@ def tiled_cubes(k):
     return scenes.Scene(u, s.spheres, s.lights, s.meshes, nodes, indices, tris, uvs.reshape(-1).copy(), s.textures, "cubes")
 
 
-def med(xs):
-    return statistics.median(xs), max(xs) - min(xs)
-
-
 def one(name, atlases, samples, runs, tile, model_atlas):
     import numpy as np
     import torch
@@ -73,25 +70,22 @@ def one(name, atlases, samples, runs, tile, model_atlas):
         pts, nrm = surf[:, 0:3].contiguous(), surf[:, 4:7].contiguous()
         out_b = torch.empty((n, 4), dtype=torch.float32, device=dev)
         out_h = torch.empty((n, 4), dtype=torch.float32, device=dev)
-        ms = {"bake": [], "surf": [], "res": [], "hemi": []}
-        for run in range(runs + 1):
-            for which in (("bake", "hemi") if run % 2 == 0 else ("hemi", "bake")):
-                if which == "bake":
-                    e.bake_lightmap(side, side, samples, dilate=2, out=out_b)
-                else:
-                    e.trace_hemisphere(pts, nrm, samples, out=out_h)
-                if run:
-                    ms[which].append(e.last_query_ms())
-                    if which == "bake":
-                        a, b = e.last_lightmap_ms()
-                        ms["surf"].append(a)
-                        ms["res"].append(b)
-        (mb, sb), (msf, ssf), (mrs, srs), (mh, sh) = med(ms["bake"]), med(ms["surf"]), med(ms["res"]), med(ms["hemi"])
+
+        def measure(which):   # (kernel ms, surfels ms, resolve ms)
+            if which == "bake":
+                e.bake_lightmap(side, side, samples, dilate=2, out=out_b)
+            else:
+                e.trace_hemisphere(pts, nrm, samples, out=out_h)
+            return (e.last_query_ms(),) + tuple(e.last_lightmap_ms())
+        got = alternating(("bake", "hemi"), runs, measure)
+        bake, surfels, resolve = ([v[i] for v in got["bake"]] for i in range(3))
+        hemi = [v[0] for v in got["hemi"]]
+        (mb, sb), (msf, ssf), (mrs, srs), (mh, sh) = med(bake), med(surfels), med(resolve), med(hemi)
         ok = mb <= mh + max(sb, sh) + msf + mrs
         held = held and ok
         rate = n * 36 / (msf * 1e-3) / 1e12
-        lines.append(f"{name:6} {len(s.bvh_triangles):7d} {side:6d} {100.0 * owned / n:5.1f}% {samples:4d}  {mb:9.3f} ({sb:6.3f})  {msf:7.3f} ({ssf:6.3f})  "
-                     f"{mrs:7.3f} ({srs:6.3f})  {mh:9.3f} ({sh:6.3f})  {mb / mh:9.3f}  {rate:11.3f}  {ok}")
+        lines.append(f"{name:6} {len(s.bvh_triangles):7d} {side:6d} {100.0 * owned / n:5.1f}% {samples:4d}  {med_text(bake)}  {msf:7.3f} ({ssf:6.3f})  "
+                     f"{mrs:7.3f} ({srs:6.3f})  {med_text(hemi)}  {mb / mh:9.3f}  {rate:11.3f}  {ok}")
         progress(f"atlas {side} timed")
         del surf, own, pts, nrm, out_b, out_h
     t0 = time.perf_counter()
@@ -109,47 +103,26 @@ def main():
     ap.add_argument("--samples", type=int, default=16)
     ap.add_argument("--tile", type=int, default=64)
     ap.add_argument("--model-atlas", type=int, default=1024)
+    ap.add_argument("--child-timeout", type=int, default=300, help="seconds one scene's process may take")
     ap.add_argument("--out", default=None)
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--header", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
-    atlases = [int(x) for x in a.atlases.split(",")]
     if a.child:   # one scene in this process: its lines, the verdict as the exit status
         if a.header:
-            from renderbaby_amd import engine
-            print(f"# {engine.device_name(0)}", flush=True)
-        lines, ok = one(a.child, atlases, a.samples, a.runs, a.tile, a.model_atlas)
+            child_header()
+        lines, ok = one(a.child, [int(x) for x in a.atlases.split(",")], a.samples, a.runs, a.tile, a.model_atlas)
         print("\n".join(lines), flush=True)
-        return 0 if ok else 3
+        child_exit(ok)
     from renderbaby_amd._lib import source_fingerprint   # (this process never opens the device: the children do)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    out_file = open(a.out, "w") if a.out else None
-
-    def say(s=""):
-        print(s, flush=True)
-        if out_file:   # line by line: a run that is cut short keeps what it measured
-            out_file.write(s + "\n")
-            out_file.flush()
-    say(f"# library sources {source_fingerprint()}; {a.runs} alternating runs after one warm-up pair; kernel ms as median (max - min)")
-    say("# bake = rb_bake_lightmap_device (surfels + trace + resolve with dilate 2, rb_last_query_ms; first and last stage: rb_last_lightmap_ms);")
-    say("# hemisphere = rb_trace_hemisphere_device on the surfels rb_lightmap_surfels_device made beforehand; one process per scene")
-    say(HEADER)
-    held = True
-    for i, name in enumerate(a.configs.split(",")):
-        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", name, "--atlases", a.atlases, "--runs", str(a.runs),
-                            "--samples", str(a.samples), "--tile", str(a.tile), "--model-atlas", str(a.model_atlas)]
-                           + (["--header"] if i == 0 else []), stdout=subprocess.PIPE, text=True)
-        for line in p.stdout.splitlines():
-            say(line)
-        if p.returncode not in (0, 3):
-            say(f"{name:6} failed: exit status {p.returncode}")
-            held = False
-            break   # whatever ended that process may have left the device in a bad state: nothing more is started on it
-        held = held and p.returncode == 0
-    say(f"# bake median <= hemisphere median + max(spreads) + surfels median + resolve median for every scene and atlas: {held}")
-    if out_file:
-        out_file.close()
+    with Report(a.out) as r:
+        r.say(f"# library sources {source_fingerprint()}; {a.runs} alternating runs after one warm-up pair; kernel ms as median (max - min)")
+        r.say("# bake = rb_bake_lightmap_device (surfels + trace + resolve with dilate 2, rb_last_query_ms; first and last stage: rb_last_lightmap_ms);")
+        r.say("# hemisphere = rb_trace_hemisphere_device on the surfels rb_lightmap_surfels_device made beforehand; one process per scene")
+        r.say(HEADER)
+        options = ("atlases", "runs", "samples", "tile", "model_atlas")
+        held, _ = run_children(r, lambda name, first: child_argv(__file__, name, a, options, first), a.configs.split(","), a.child_timeout)
+        r.say(f"# bake median <= hemisphere median + max(spreads) + surfels median + resolve median for every scene and atlas: {held}")
     return 0 if held else 1
 
 

@@ -11,17 +11,9 @@ not above the closest-hit median by more than the larger of the two spreads; the
 Then whole-call times, recorded and not judged: rb_occluded / rb_cast_rays from host memory, the device forms, and one
 ambient_occlusion at 1920 x 1080 x 16 on C3 end to end.
 """
-import argparse, os, statistics, sys, time
+import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
-
-def scene_of(name):
-    from renderbaby_amd import refscenes, scenes
-    return {"c3": scenes.mesh_c3, "c5": scenes.mesh_c5, "c4": scenes.spheres_scene, "lamp": refscenes.ref_lamp}[name]()
-
-
-def med(xs):
-    return statistics.median(xs), max(xs) - min(xs)
+from _rate import Report, alternating, med, med_text, scene_of
 
 
 def ao_rays_device(uniforms, dirs, hits, n_dirs, seed, max_hits):
@@ -63,15 +55,8 @@ def main():
     from renderbaby_amd import Engine, RenderConfig, abi, aov, engine
     from renderbaby_amd._lib import source_fingerprint
     held = True
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    out_file = open(a.out, "w") if a.out else None
-
-    def say(s=""):
-        print(s, flush=True)
-        if out_file:   # line by line: a run that is cut short keeps what it measured
-            out_file.write(s + "\n")
-            out_file.flush()
+    report = Report(a.out)
+    say = report.say
     say(f"# {engine.device_name(0)}; library sources {source_fingerprint()}; {a.runs} alternating runs after one warm-up pair; kernel ms as median (max - min)")
     say(f"# closest = rb_cast_rays_device, hits only; any = rb_occluded_device, tmax NULL, RB_MASK_ALL; same process, same buffers")
     say(f"{'scene':6} {'rays':10} {'n':>10} {'occluded':>9}  {'closest kernel':15} {'ms':>18}  {'any kernel':13} {'ms':>18}  {'any/closest':>11}  held")
@@ -92,22 +77,21 @@ def main():
             n = len(rays)
             hits = torch.empty((n, 12), dtype=torch.float32, device=dev)
             out = torch.empty(n, dtype=torch.uint8, device=dev)
-            ms = {"closest": [], "any": []}
-            names = {}
-            for run in range(a.runs + 1):
-                for which in (("closest", "any") if run % 2 == 0 else ("any", "closest")):
-                    if which == "closest":
-                        e.cast_ray_records(rays, hits_out=hits)
-                    else:
-                        e.occluded_records(rays, out=out)
-                    names[which] = e.last_query_kernel_name()
-                    if run:
-                        ms[which].append(e.last_query_ms())
+
+            def measure(which):   # (kernel ms, the kernel's name)
+                if which == "closest":
+                    e.cast_ray_records(rays, hits_out=hits)
+                else:
+                    e.occluded_records(rays, out=out)
+                return e.last_query_ms(), e.last_query_kernel_name()
+            got = alternating(("closest", "any"), a.runs, measure)
+            ms = {which: [v[0] for v in got[which]] for which in got}
+            names = {which: got[which][-1][1] for which in got}
             (mc, sc), (ma, sa) = med(ms["closest"]), med(ms["any"])
             ok = ma <= mc + max(sc, sa)
             held = held and ok
             occ = float((out == abi.OCCL_OCCLUDED).float().mean())
-            say(f"{name:6} {label:10} {n:10d} {occ:9.3f}  {names['closest']:15} {mc:9.3f} ({sc:6.3f})  {names['any']:13} {ma:9.3f} ({sa:6.3f})  {ma / mc:11.3f}  {ok}")
+            say(f"{name:6} {label:10} {n:10d} {occ:9.3f}  {names['closest']:15} {med_text(ms['closest'])}  {names['any']:13} {med_text(ms['any'])}  {ma / mc:11.3f}  {ok}")
             del hits, out
         # whole calls on the pixel rays: host memory in and out against the device forms
         host = pix.cpu().numpy().view(abi.RAY).reshape(-1)
@@ -133,8 +117,7 @@ def main():
         del pix, dirs, sets
         torch.cuda.empty_cache()
     say(f"# any-hit median <= closest-hit median + max(spreads) on every scene and ray set: {held}")
-    if out_file:
-        out_file.close()
+    report.close()
     return 0 if held else 1
 
 

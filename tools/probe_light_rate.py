@@ -17,16 +17,12 @@ One warm-up pair, then `runs` alternating pairs; kernel ms from rb_last_query_ms
 effective rate of the corner records read, 8 x 112 B per point, in GB/s (what the caches serve of it never reaches memory).
 Nothing is required of the numbers: the faster shape becomes kLightShapeDefault by hand.
 """
-import argparse, os, statistics, sys
+import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _rate import Report, alternating, env, med, med_text, scene_of
 
 HEADER = f"{'scene':6} {'grid':>6} {'points':10} {'shape':5} {'kernel':18} {'n':>8} {'ms':>18} {'points/s':>10} {'GB/s':>8}"
 SHAPES = ("pairs", "wide")
-
-
-def scene_of(name):
-    from renderbaby_amd import scenes
-    return {"c2": scenes.cornell_c2, "c3": scenes.mesh_c3, "feature": scenes.feature_scene}[name]()
 
 
 def one(name, width, height, grids, runs, say):
@@ -59,19 +55,15 @@ def one(name, width, height, grids, runs, say):
         co = torch.from_numpy(sums.view(np.float32).reshape(-1, 28)).to(dev)
         e.probe_coefficients(co, out=co)
         for order, t in orders.items():
-            ms = {sh: [] for sh in SHAPES}
-            kernel = {}
-            for run in range(runs + 1):
-                for sh in (SHAPES if run % 2 == 0 else SHAPES[::-1]):
-                    os.environ["RB_LIGHT_SHAPE"] = sh
+
+            def measure(sh):   # (kernel ms, the kernel's name)
+                with env("RB_LIGHT_SHAPE", sh):
                     e.light_points(grid, co, t, out=out)
-                    kernel[sh] = e.last_query_kernel_name()
-                    if run:
-                        ms[sh].append(e.last_query_ms())
-            for sh in SHAPES:
-                med, spread = statistics.median(ms[sh]), max(ms[sh]) - min(ms[sh])
-                say(f"{name:6} {g:4d}^3 {order:10} {sh:5} {kernel[sh]:18} {m:8d} {med:9.3f} ({spread:6.3f}) {m / med * 1e3:10.3e} {m * 8 * 112 / med / 1e6:8.1f}")
-    os.environ.pop("RB_LIGHT_SHAPE", None)
+                return e.last_query_ms(), e.last_query_kernel_name()
+            for sh, got in alternating(SHAPES, runs, measure).items():
+                ms = [v[0] for v in got]
+                v = med(ms)[0]
+                say(f"{name:6} {g:4d}^3 {order:10} {sh:5} {got[-1][1]:18} {m:8d} {med_text(ms)} {m / v * 1e3:10.3e} {m * 8 * 112 / v / 1e6:8.1f}")
     e.close()
 
 
@@ -86,15 +78,8 @@ def main():
     a = ap.parse_args()
     from renderbaby_amd import engine
     from renderbaby_amd._lib import source_fingerprint
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    out_file = open(a.out, "w") if a.out else None
-
-    def say(s=""):
-        print(s, flush=True)
-        if out_file:   # line by line: a run that is cut short keeps what it measured
-            out_file.write(s + "\n")
-            out_file.flush()
+    report = Report(a.out)
+    say = report.say
     say(f"# {engine.device_name(0)}")
     say(f"# library sources {source_fingerprint()}; {a.runs} alternating runs after one warm-up pair; kernel ms (rb_last_query_ms) as median (max - min)")
     say("# rb_light_points_device on the first hits of the frame's pixel centres (coherent) and on the same surfels shuffled; shape = RB_LIGHT_SHAPE;")
@@ -102,8 +87,7 @@ def main():
     say(HEADER)
     for name in a.configs.split(","):
         one(name, a.width, a.height, [int(g) for g in a.grids.split(",")], a.runs, say)
-    if out_file:
-        out_file.close()
+    report.close()
     return 0
 
 

@@ -22,22 +22,14 @@ One process.  Per scene:
 One warm-up pair, then `runs` alternating pairs; median (max - min).  Nothing is required of the numbers: the faster fold becomes
 kDepthShapeDefault by hand.
 """
-import argparse, os, statistics, sys
+import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _rate import Report, alternating, env, med, med_text, scene_of
 
 BAKE_HEADER = (f"{'scene':6} {'fold':8} {'probes':>7} {'spp':>5}  {'kernel':14} {'total ms':>18}  {'generator ms':>18}  {'query ms':>18}  "
                f"{'projection ms':>18}  {'items/s':>10} {'proj GB/s':>9}")
 BLEND_HEADER = f"{'scene':6} {'grid':>6} {'points':10} {'kernel':18} {'n':>8} {'ms':>18} {'points/s':>10} {'GB/s':>8}"
 FOLDS = ("lds", "readlane")
-
-
-def scene_of(name):
-    from renderbaby_amd import scenes
-    return {"c2": scenes.cornell_c2, "c3": scenes.mesh_c3, "feature": scenes.feature_scene}[name]()
-
-
-def med(xs):
-    return statistics.median(xs), max(xs) - min(xs)
 
 
 def one(name, a, say):
@@ -62,29 +54,24 @@ def one(name, a, say):
     pos = torch.from_numpy(np.ascontiguousarray((pts[pick] + np.float32(0.05) * nrm[pick]).astype(np.float32))).to(dev)
     maps = torch.empty((a.probes, 256), dtype=torch.float32, device=dev)
     reach = float(1.5 * np.linalg.norm((hi - lo) / 16.0))
-    t = {f: dict(total=[], gen=[], proj=[]) for f in FOLDS}
-    kernel, words = {}, {}
-    for run in range(a.runs + 1):
-        for f in (FOLDS if run % 2 == 0 else FOLDS[::-1]):
-            os.environ["RB_DEPTH_SHAPE"] = f
+    words = {}
+
+    def bake(f):   # (total, generator and projection ms, the kernel's name); the warm-up call's words are kept
+        with env("RB_DEPTH_SHAPE", f):
             e.bake_probe_depth(pos, a.samples, reach, out=maps)
-            kernel[f] = e.last_query_kernel_name()
-            if run == 0:
-                words[f] = maps.view(torch.int32).clone()
-            else:
-                t[f]["total"].append(e.last_query_ms())
-                t[f]["gen"].append(e.last_camera_rays_ms())
-                t[f]["proj"].append(e.last_probe_depth_project_ms())
-    os.environ.pop("RB_DEPTH_SHAPE", None)
+        if f not in words:
+            words[f] = maps.view(torch.int32).clone()
+        return e.last_query_ms(), e.last_camera_rays_ms(), e.last_probe_depth_project_ms(), e.last_query_kernel_name()
+    baked = alternating(FOLDS, a.runs, bake)
     if not torch.equal(words["lds"], words["readlane"]):
         raise SystemExit("the two folds disagree")
     say(BAKE_HEADER)
     items = a.probes * a.samples
-    for f in FOLDS:
-        tot, gen, proj = med(t[f]["total"]), med(t[f]["gen"]), med(t[f]["proj"])
-        query = med([x - y - z for x, y, z in zip(t[f]["total"], t[f]["gen"], t[f]["proj"])])
-        cells = "  ".join(f"{v:9.3f} ({sp:6.3f})" for v, sp in (tot, gen, query, proj))
-        say(f"{name:6} {f:8} {a.probes:7d} {a.samples:5d}  {kernel[f]:14} {cells}  {items / tot[0] * 1e3:10.3e} {items * 48 / proj[0] / 1e6:9.1f}")
+    for f, got in baked.items():
+        tot, gen, proj = ([v[i] for v in got] for i in range(3))
+        query = [x - y - z for x, y, z in zip(tot, gen, proj)]
+        cells = "  ".join(med_text(x) for x in (tot, gen, query, proj))
+        say(f"{name:6} {f:8} {a.probes:7d} {a.samples:5d}  {got[-1][3]:14} {cells}  {items / med(tot)[0] * 1e3:10.3e} {items * 48 / med(proj)[0] / 1e6:9.1f}")
 
     # ---- the blend
     surf = np.zeros(m, dtype=abi.SURFEL)
@@ -111,17 +98,13 @@ def one(name, a, say):
         calls = {"plain": (lambda pts_t: e.light_points(grid, co, pts_t, out=out), 8 * 112),
                  "visible": (lambda pts_t: e.light_points_visible(grid, co, mom, pts_t, normal_bias=0.01 * cell, out=out), 8 * 128)}
         for order, pts_t in orders.items():
-            ms = {k: [] for k in calls}
-            kname = {}
-            for run in range(a.runs + 1):
-                for k in (list(calls) if run % 2 == 0 else list(calls)[::-1]):
-                    calls[k][0](pts_t)
-                    kname[k] = e.last_query_kernel_name()
-                    if run:
-                        ms[k].append(e.last_query_ms())
-            for k in calls:
-                v, sp = med(ms[k])
-                say(f"{name:6} {g:4d}^3 {order:10} {kname[k]:18} {m:8d} {v:9.3f} ({sp:6.3f}) {m / v * 1e3:10.3e} {m * calls[k][1] / v / 1e6:8.1f}")
+            def blend(k):   # (kernel ms, the kernel's name)
+                calls[k][0](pts_t)
+                return e.last_query_ms(), e.last_query_kernel_name()
+            for k, got in alternating(calls, a.runs, blend).items():
+                ms = [x[0] for x in got]
+                v = med(ms)[0]
+                say(f"{name:6} {g:4d}^3 {order:10} {got[-1][1]:18} {m:8d} {med_text(ms)} {m / v * 1e3:10.3e} {m * calls[k][1] / v / 1e6:8.1f}")
         del mom, co
     e.close()
 
@@ -140,23 +123,15 @@ def main():
     a.grids = [int(g) for g in a.grids.split(",")]
     from renderbaby_amd import engine
     from renderbaby_amd._lib import source_fingerprint
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    out_file = open(a.out, "w") if a.out else None
-
-    def say(s=""):
-        print(s, flush=True)
-        if out_file:   # line by line: a run that is cut short keeps what it measured
-            out_file.write(s + "\n")
-            out_file.flush()
+    report = Report(a.out)
+    say = report.say
     say(f"# {engine.device_name(0)}")
     say(f"# library sources {source_fingerprint()}; {a.runs} alternating runs after one warm-up pair; kernel ms as median (max - min); one process")
     say("# bake: rb_bake_probe_depth_device, fold = RB_DEPTH_SHAPE; proj GB/s = the 48 B of record and hit quads read per item over the projection's time")
     say("# blend: rb_light_points_device against rb_light_points_visible_device on the same points; GB/s = 8 corners x (112 B, or 112 + 16 B) per point")
     for name in a.configs.split(","):
         one(name, a, say)
-    if out_file:
-        out_file.close()
+    report.close()
     return 0
 
 

@@ -13,23 +13,7 @@ page-locked, and rb_pick latency.
 import argparse, ctypes as C, json, os, statistics, subprocess, sys, time
 # (the yardstick child imports the package of the tree it was pointed at)
 sys.path.insert(0, os.environ.get("RB_QUERY_RATE_TREE") or os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
-
-def scene_of(name):
-    from renderbaby_amd import refscenes, scenes
-    if name == "c3":
-        return scenes.mesh_c3()
-    if name == "c5":
-        return scenes.mesh_c5()
-    if name == "c4":
-        return scenes.spheres_scene()
-    if name == "lamp":
-        return refscenes.ref_lamp()
-    raise SystemExit(f"unknown configuration {name}")
-
-
-def med(xs):
-    return statistics.median(xs), max(xs) - min(xs)
+from _rate import med, scene_of
 
 
 def yardstick(name, repeats):

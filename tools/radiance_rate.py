@@ -20,23 +20,14 @@ n x 32 B at the HBM rate a device copy of the ray buffer achieves in the same pr
 Whole-call times of the host form, and on c3 of bake.irradiance on 2^20 points x 16, are recorded beside these.
 The exit status says whether the requirement held on every judged scene.
 """
-import argparse, os, statistics, subprocess, sys, time
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import argparse, os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _rate import Report, alternating, child_exit, med, med_text, run_children, scene_of
 JUDGED = ("c3", "lamp", "c5", "c4")
 
 
-def scene_of(name):
-    from renderbaby_amd import refscenes, scenes
-    return {"c3": scenes.mesh_c3, "c5": scenes.mesh_c5, "c4": scenes.spheres_scene, "lamp": refscenes.ref_lamp, "c2": scenes.cornell_c2}[name]()
-
-
-def med(xs):
-    return statistics.median(xs), max(xs) - min(xs)
-
-
 def one(name, runs, samples, whole):
-    """the measurements of one scene, as lines on stdout; the last line says whether the requirement held"""
+    """the measurements of one scene, as lines on stdout; whether the requirement held, or the scene is not judged"""
     import numpy as np
     import torch
     from renderbaby_amd import Engine, RenderConfig, abi, aov, bake
@@ -51,18 +42,15 @@ def one(name, runs, samples, whole):
     rays[:, 0:3] = torch.tensor(s.uniforms["camera"]["pos"][0], dtype=torch.float32, device=dev)
     rays[:, 4:7] = torch.from_numpy(dirs).to(dev)
     out = torch.empty((n, 4), dtype=torch.float32, device=dev)
-    ms = {"render": [], "query": []}
-    for run in range(runs + 1):
-        for which in (("render", "query") if run % 2 == 0 else ("query", "render")):
-            if which == "render":
-                e.dispatch(0, samples)
-                e.sync()
-                t = e.last_dispatch_ms()
-            else:
-                e.trace_ray_records(rays, samples=samples, out=out)
-                t = e.last_query_ms()
-            if run:
-                ms[which].append(t)
+
+    def measure(which):
+        if which == "render":
+            e.dispatch(0, samples)
+            e.sync()
+            return e.last_dispatch_ms()
+        e.trace_ray_records(rays, samples=samples, out=out)
+        return e.last_query_ms()
+    ms = alternating(("render", "query"), runs, measure)
     # the HBM rate a copy of the ray buffer achieves (read + write), for the allowance
     copy = torch.empty_like(rays)
     best = None
@@ -79,8 +67,8 @@ def one(name, runs, samples, whole):
     ok = mq <= mr + max(sr, sq) + allowance
     judged = name in JUDGED
     lit = float((out[:, :3] != 0).any(1).float().mean())
-    print(f"{name:5} {s.width}x{s.height}x{samples} {n * samples:11d}  {e.last_kernel_name():14} {mr:9.3f} ({sr:6.3f})  {e.last_query_kernel_name():12} "
-          f"{mq:9.3f} ({sq:6.3f})  {mq / mr:6.3f}  {allowance:7.3f} ms at {rate / 1e12:.2f} TB/s  {'held' if ok else 'MISSED'}{'' if judged else ' (recorded, not judged)'}"
+    print(f"{name:5} {s.width}x{s.height}x{samples} {n * samples:11d}  {e.last_kernel_name():14} {med_text(ms['render'])}  {e.last_query_kernel_name():12} "
+          f"{med_text(ms['query'])}  {mq / mr:6.3f}  {allowance:7.3f} ms at {rate / 1e12:.2f} TB/s  {'held' if ok else 'MISSED'}{'' if judged else ' (recorded, not judged)'}"
           f"  lit {lit:.3f}", flush=True)
     if whole:
         host = rays.cpu().numpy().view(abi.RAY).reshape(-1)
@@ -102,7 +90,7 @@ def one(name, runs, samples, whole):
             print(f"#   c3 bake.irradiance, 2^20 points x 16 rays (rays built in numpy, host form): {(time.perf_counter() - t0) * 1e3:.0f} ms end to end, "
                   f"kernels {e.last_query_ms():.1f} ms, mean {float(irr.mean()):.4f}", flush=True)
     e.close()
-    print(f"RESULT {name} {int(ok or not judged)}", flush=True)
+    return ok or not judged
 
 
 def main():
@@ -112,54 +100,26 @@ def main():
     ap.add_argument("--samples", type=int, default=16)
     ap.add_argument("--out", default=None)
     ap.add_argument("--no-whole-calls", action="store_true")
-    ap.add_argument("--scene-timeout", type=int, default=300, help="seconds one scene's process may take")
+    ap.add_argument("--scene-timeout", "--child-timeout", type=int, default=300, help="seconds one scene's process may take")
     ap.add_argument("--one", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
-    if a.one:
-        one(a.one, a.runs, a.samples, not a.no_whole_calls)
-        return 0
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    out_file = open(a.out, "w") if a.out else None
+    if a.one:   # one scene in this process: its lines, the verdict as the exit status
+        child_exit(one(a.one, a.runs, a.samples, not a.no_whole_calls))
+    from renderbaby_amd._lib import source_fingerprint   # (this process never opens the device: the children do)
+    with Report(a.out) as r:
+        r.say(f"# library sources {source_fingerprint()}; one process per scene; {a.runs} alternating runs after one warm-up pair; kernel ms as median (max - min)")
+        r.say("# render = rb_dispatch(e, 0, samples), rb_last_dispatch_ms (all launches, k_accumulate included); query = rb_trace_rays_device on the")
+        r.say("# pixel-centre rays, rb_last_query_ms (all launches, k_rad_sum included).  The same number of paths through the same per-path code;")
+        r.say("# the paths differ (jitter and seeds), so the work is the same statistically.  Requirement on c3, lamp, c5, c4: query <= render +")
+        r.say("# max(spreads) + the time of reading n x 32 B of rays at the HBM rate of a device copy of the ray buffer (column `rays`).")
+        r.say(f"{'scene':5} {'frame':16} {'paths':>11}  {'render kernel':14} {'ms':>18}  {'query kernel':12} {'ms':>18}  {'q/r':>6}  rays")
 
-    def say(s=""):
-        print(s, flush=True)
-        if out_file:   # line by line: a run that is cut short keeps what it measured
-            out_file.write(s + "\n")
-            out_file.flush()
-    from renderbaby_amd._lib import source_fingerprint
-    say(f"# library sources {source_fingerprint()}; one process per scene; {a.runs} alternating runs after one warm-up pair; kernel ms as median (max - min)")
-    say("# render = rb_dispatch(e, 0, samples), rb_last_dispatch_ms (all launches, k_accumulate included); query = rb_trace_rays_device on the")
-    say("# pixel-centre rays, rb_last_query_ms (all launches, k_rad_sum included).  The same number of paths through the same per-path code;")
-    say("# the paths differ (jitter and seeds), so the work is the same statistically.  Requirement on c3, lamp, c5, c4: query <= render +")
-    say("# max(spreads) + the time of reading n x 32 B of rays at the HBM rate of a device copy of the ray buffer (column `rays`).")
-    say(f"{'scene':5} {'frame':16} {'paths':>11}  {'render kernel':14} {'ms':>18}  {'query kernel':12} {'ms':>18}  {'q/r':>6}  rays")
-    held = True
-    for name in a.configs.split(","):
-        cmd = [sys.executable, os.path.abspath(__file__), "--one", name, "--runs", str(a.runs), "--samples", str(a.samples)] + (["--no-whole-calls"] if a.no_whole_calls else [])
-        try:   # a time limit of its own per scene: building the scene, a dozen launches of a second at the most, the whole calls
-            p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=a.scene_timeout)
-        except subprocess.TimeoutExpired as ex:
-            for line in (ex.stdout or "").splitlines() if isinstance(ex.stdout, str) else []:
-                say(line)
-            say(f"# {name}: the measuring process did not end within {a.scene_timeout} s and was killed; nothing more is started")
-            held = False
-            break
-        ok = False
-        for line in p.stdout.splitlines():
-            if line.startswith("RESULT "):
-                ok = line.split()[2] == "1"
-            else:
-                say(line)
-        if p.returncode != 0:
-            say(f"# {name}: the measuring process ended with status {p.returncode}")
-            ok = False
-            held = False
-            break   # nothing more is started on the device after a failure
-        held = held and ok
-    say(f"# the requirement held on every judged scene: {held}")
-    if out_file:
-        out_file.close()
+        def argv_of(name, first):
+            return ([sys.executable, os.path.abspath(__file__), "--one", name, "--runs", str(a.runs), "--samples", str(a.samples)]
+                    + (["--no-whole-calls"] if a.no_whole_calls else []))
+        # a time limit of its own per scene: building the scene, a dozen launches of a second at the most, the whole calls
+        held, _ = run_children(r, argv_of, a.configs.split(","), a.scene_timeout, merge_stderr=True)
+        r.say(f"# the requirement held on every judged scene: {held}")
     return 0 if held else 1
 
 

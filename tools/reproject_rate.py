@@ -13,20 +13,9 @@ camera.  The camera turns in 16 steps of 0.5 degrees; per step one 1-spp pass an
 frame, rb_denoise, the history alone (rb_history_read) and history + filter -- with the colour term off and on -- and per step
 the share of filterable pixels that had no history.  ``--sweep``: the last step's history + filter over normal_min x max_history.
 """
-import argparse, os, statistics, sys
+import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
-
-def med(xs):
-    return statistics.median(xs), max(xs) - min(xs)
-
-
-def scene_of(name, w, h, spp):
-    from renderbaby_amd import scenes
-    s = scenes.cornell_c2() if name == "c2" else scenes.mesh_c3() if name == "c3" else None
-    if s is None:
-        raise SystemExit(f"unknown configuration {name}")
-    return s.with_params(width=w, height=h, spp=spp)
+from _rate import med, scene_of
 
 
 def turned(uniforms, degrees):
@@ -51,7 +40,7 @@ def speed(a):
     for name in a.configs.split(","):
         for size in a.sizes.split(","):
             w, h = (int(x) for x in size.split("x"))
-            s = scene_of(name, w, h, 1)
+            s = scene_of(name).with_params(width=w, height=h, spp=1)
             rc = RenderConfig.from_scene(s)
             e = Engine.new(rc, device=0)
             e.render(rc)
