@@ -335,6 +335,35 @@ class Engine final : public Renderer {
                                  uint32_t first_sample = 0) {
         check(h_->e, rb_direct_light_cdf_device(h_->e, d_emitters, d_cdf, n_emit, d_surfels, d_seeds, n, &p, first_sample, samples, d_out));
     }
+    // ---- ... with the emitters picked per grid cell (extension; rb_abi.h): one table of pick weights per
+    // cell of `grid` (its counts count cells), nx * ny * nz rows of one entry per emitter; `tables` empty: made for the call
+    static std::vector<uint32_t> emitter_grid_cdf(const std::vector<rb_emitter>& emitters, const rb_probe_grid& grid, int32_t device = -1) {
+        std::vector<uint32_t> out(emitters.size() * grid.counts[0] * grid.counts[1] * grid.counts[2]);
+        check(nullptr, rb_emitter_grid_cdf(device, emitters.data(), emitters.size(), &grid, out.data()));
+        return out;
+    }
+    // d_emitters == nullptr: the scene's table, n_emit its count (scene_emitters().size())
+    void emitter_grid_cdf_device(const rb_emitter* d_emitters, size_t n_emit, const rb_probe_grid& grid, uint32_t* d_tables_out) {
+        check(h_->e, rb_emitter_grid_cdf_device(h_->e, d_emitters, n_emit, &grid, d_tables_out));
+    }
+    // `emitters` empty: the scene's table, of `scene_count` records (scene_emitters().size())
+    std::vector<rb_radiance> direct_light_grid(const std::vector<rb_surfel>& surfels, const rb_probe_grid& grid, uint32_t samples,
+                                               size_t scene_count = 0, uint32_t first_sample = 0, const uint32_t* seeds = nullptr,
+                                               const rb_light_params& p = light_params(), const std::vector<rb_emitter>& emitters = {},
+                                               const std::vector<uint32_t>& tables = {}) {
+        const size_t n_emit = emitters.empty() ? scene_count : emitters.size();
+        if (!tables.empty() && tables.size() != n_emit * grid.counts[0] * grid.counts[1] * grid.counts[2])
+            throw std::invalid_argument("direct_light_grid: one entry per cell and emitter is needed");
+        std::vector<rb_radiance> out(surfels.size());
+        check(h_->e, rb_direct_light_grid(h_->e, emitters.empty() ? nullptr : emitters.data(), &grid, tables.empty() ? nullptr : tables.data(),
+                                          n_emit, surfels.data(), seeds, surfels.size(), &p, first_sample, samples, out.data()));
+        return out;
+    }
+    void direct_light_grid_device(const rb_emitter* d_emitters, const rb_probe_grid& grid, const uint32_t* d_tables, size_t n_emit,
+                                  const rb_surfel* d_surfels, const uint32_t* d_seeds, size_t n, const rb_light_params& p, rb_radiance* d_out,
+                                  uint32_t samples, uint32_t first_sample = 0) {
+        check(h_->e, rb_direct_light_grid_device(h_->e, d_emitters, &grid, d_tables, n_emit, d_surfels, d_seeds, n, &p, first_sample, samples, d_out));
+    }
     // ---- lightmap texels made on the device (extension; rb_abi.h): the surfel of every texel of an atlas
     // over the scene's uvs, and the bake of the whole map in one call (rgba in sample_texture's layout, row 0 on top)
     static rb_lightmap_params lightmap_params(uint32_t width, uint32_t height, uint32_t mesh = RB_LIGHTMAP_ALL_MESHES, bool flip = false,

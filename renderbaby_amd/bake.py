@@ -100,9 +100,29 @@ def direct_irradiance(engine, points, normals, samples, emitters=None, first_sam
     ``emitters``: an abi.EMITTER table of the caller's instead of the scene's.  numpy arrays -> float32 (m, 3); torch tensors on
     the engine's device -> an (m, 3) tensor there.  A point without a valid sample is 0 0 0.  ``pick``: Engine.direct_light's --
     "uniform", "power" (emitters picked in proportion to emission times area: the same mean with less noise where the lights
-    differ) or a caller's table of weights (section 23)."""
+    differ), a caller's table of weights (section 23), or ("grid", grid[, tables]): a table per cell of a grid, weighted by
+    power over squared distance to the cell (section 24; ``pick_grid`` makes such a grid)."""
     return _mean(engine.direct_light(points, normals, samples, emitters=emitters, first_sample=first_sample, seeds=seeds, offset=offset,
                                      shorten=shorten, mask=mask, pick=pick))
+
+
+def pick_grid(emitters, counts, points=None):
+    """The abi.PROBE_GRID of ``counts`` = (nx, ny, nz) cells over the bounding box of an abi.EMITTER table -- the spheres
+    ``direct.emitter_bounds`` puts about its records -- and, if given, (m, 3) ``points``: what ``pick=("grid", grid)`` and
+    Engine.emitter_grid take.  An axis along which the box is flat gets a cell of size 1."""
+    from . import direct, probes
+    ce, re = direct.emitter_bounds(emitters)
+    ok = np.isfinite(ce).all(1) & np.isfinite(re)
+    lo = [ce[ok] - re[ok, None]] + ([] if points is None else [np.asarray(points, np.float32).reshape(-1, 3)])
+    hi = [ce[ok] + re[ok, None]] + lo[1:]
+    lo, hi = np.concatenate(lo).astype(np.float64), np.concatenate(hi).astype(np.float64)
+    if not len(lo):
+        raise ValueError("pick_grid: neither emitters nor points to span a box")
+    lo, hi = lo.min(0), hi.max(0)
+    hi = np.where(hi > lo, hi, lo + 1.0)
+    g = probes.grid_params(lo, hi, counts)
+    g["origin"] = lo   # the counts count cells: the origin is the box's corner, not the first cell's centre
+    return g
 
 
 def lightmap_direct(engine, width, height, samples, emitters=None, first_sample=0, mesh=None, flip=False, offset=1e-3, shorten=1e-3,

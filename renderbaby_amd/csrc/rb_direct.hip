@@ -5,6 +5,8 @@
 // Beside the uniform pick, the pick by a table of integer weights (rb_emitter_cdf, rb_light_rays_cdf, rb_direct_light_cdf;
 // section 23): the table by power -- every record's power and their maximum, the quantised weights, an inclusive scan -- and the
 // same item with the emitter found in a table by a halving search.
+// And the pick per grid cell (rb_emitter_grid_cdf, rb_light_rays_grid, rb_direct_light_grid; section 24): one such table per
+// cell of a regular grid, weighted by power over squared distance to the cell, and the item searching the row of its surfel's cell.
 // The generator runs before the kernels that walk the records (k_occl*, rb_query.hip), as k_hemi_rays does (section 16).  Same
 // numerics contract as rb_kernels.hip: every step one binary32 operation in the order written, no FMA contraction, correctly
 // rounded / and sqrt, so that renderbaby_amd/direct.py equals this file bit for bit.
@@ -106,8 +108,23 @@ __global__ void __launch_bounds__(256) k_emit_scatter(const EmitArgs s, uint32_t
 // per lane from a table that lives in L2, each lane at its own place (the draws are independent), and it reads inside the table
 // whatever the table holds: lo + len <= N and 1 <= half <= len - 1 throughout.  An item that the table leaves without a pick
 // (Q == 0, Q > 2^24, or q == 0 from a malformed table) is what an item of an empty table is: dark, with the direction 0 0 0.
-template <bool kCdf>
-DEV void light_item(const LightGenArgs g, const uint32_t* __restrict__ cdf) {
+// kPick == PICK_GRID (section 24): `cdf` holds one such table per grid cell, row after row, and a valid item searches the row
+// of the cell its surfel's position falls into -- the nearest cell for a point outside the grid --, so Q is per lane.  In item
+// order the 64 lanes of a wave are 64 neighbouring surfels of one sample and mostly share a row.  row < rows for every float
+// the position holds, and the search stays inside its row as it stays inside the one table: every index read is in
+// [0, rows * N - 1] whatever the tables hold.  An invalid item reads row 0's total and nothing else.
+enum PickMode { PICK_UNIFORM, PICK_CDF, PICK_GRID };
+
+// the cell of section 24 along one axis: min((uint32_t)max(f, 0.0f), count - 1), the conversion truncating and saturating; f is
+// no NaN (a valid surfel's position and the grid's origin are finite, the step is finite and above 0)
+DEV uint32_t grid_axis(float pos, float origin, float step, uint32_t count) {
+    const float f = fmaxf((pos - origin) / step, 0.0f);
+    return f >= 4294967296.0f ? count - 1u : min((uint32_t)f, count - 1u);
+}
+
+template <PickMode kPick>
+DEV void light_item(const LightGenArgs g, const uint32_t* __restrict__ cdf, const rb_probe_grid* grid = nullptr) {
+    constexpr bool kCdf = kPick != PICK_UNIFORM;
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
     const GenItem it = gen_item(t, g.samples, g.linear);
     const uint32_t sf = it.idx, smp = it.smp;
@@ -139,6 +156,14 @@ DEV void light_item(const LightGenArgs g, const uint32_t* __restrict__ cdf) {
     uint32_t j = 0u;
     float fn = 0.0f;       // the factor: float(N), or float(Q) / float(q)
     bool picked = N != 0u;
+    if constexpr (kPick == PICK_GRID) {
+        if (valid) {
+            const uint32_t ix = grid_axis(pos.x, grid->origin[0], grid->step[0], grid->counts[0]);
+            const uint32_t iy = grid_axis(pos.y, grid->origin[1], grid->step[1], grid->counts[1]);
+            const uint32_t iz = grid_axis(pos.z, grid->origin[2], grid->step[2], grid->counts[2]);
+            cdf += (size_t)((iz * grid->counts[1] + iy) * grid->counts[0] + ix) * N;   // rows * N <= RB_MAX_GRID_ENTRIES
+        }
+    }
     if constexpr (kCdf) {
         const uint32_t Q = N != 0u ? cdf[N - 1u] : 0u;
         picked = Q != 0u && Q <= (1u << 24);
@@ -213,8 +238,11 @@ DEV void light_item(const LightGenArgs g, const uint32_t* __restrict__ cdf) {
     reinterpret_cast<v4f*>(g.contrib)[t] = contrib;
 }
 
-__global__ void __launch_bounds__(256) k_light_rays(const LightGenArgs g) { light_item<false>(g, nullptr); }
-__global__ void __launch_bounds__(256) k_light_rays_cdf(const LightGenArgs g, const uint32_t* __restrict__ cdf) { light_item<true>(g, cdf); }
+__global__ void __launch_bounds__(256) k_light_rays(const LightGenArgs g) { light_item<PICK_UNIFORM>(g, nullptr); }
+__global__ void __launch_bounds__(256) k_light_rays_cdf(const LightGenArgs g, const uint32_t* __restrict__ cdf) { light_item<PICK_CDF>(g, cdf); }
+__global__ void __launch_bounds__(256) k_light_rays_grid(const LightGenArgs g, const uint32_t* __restrict__ tables, const rb_probe_grid grid) {
+    light_item<PICK_GRID>(g, tables, &grid);
+}
 
 // ================================================= the table by power ====
 // p_j of section 23.1 for every record, and the largest of them folded into *pmax (zeroed before the launch): p >= 0, so the
@@ -257,6 +285,93 @@ __global__ void __launch_bounds__(256) k_emit_quant(const float* __restrict__ po
     if (j >= n) return;
     const float p = power[j], top = __uint_as_float(*pmax);
     q[j] = p > 0.0f ? max(1u, (uint32_t)((p / top) * scale)) : 0u;
+}
+
+// ================================================= the tables per cell ====
+// {ce, re} of section 24 for every record, beside k_emit_power's p: a sphere that holds the emitter.  A record that is not good
+// has p = 0 and its bound is never looked at.
+__global__ void __launch_bounds__(256) k_emit_bound(const rb_emitter* __restrict__ em, uint32_t n, v4f* __restrict__ bound) {
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= n) return;
+    const v4f* const ep = reinterpret_cast<const v4f*>(em) + (size_t)j * 4u;
+    const v4f e0 = ep[0], e1 = ep[1], e2 = ep[2];
+    const f3 a = mk(e0.x, e0.y, e0.z), b = mk(e1.x, e1.y, e1.z), c = mk(e2.x, e2.y, e2.z);
+    f3 ce = a;
+    float re = fabsf(b.x);
+    if (__float_as_uint(e0.w) == (uint32_t)RB_HIT_TRIANGLE) {
+        ce = a + 0.33333334f * (b + c);
+        const f3 v0 = a - ce, v1 = (a + b) - ce, v2 = (a + c) - ce;
+        const float l0 = (v0.x * v0.x + v0.y * v0.y) + v0.z * v0.z;
+        const float l1 = (v1.x * v1.x + v1.y * v1.y) + v1.z * v1.z;
+        const float l2 = (v2.x * v2.x + v2.y * v2.y) + v2.z * v2.z;
+        const float m01 = l0 > l1 ? l0 : l1;
+        re = sqrt_exact(m01 > l2 ? m01 : l2);
+    }
+    bound[j] = v4f{ce.x, ce.y, ce.z, re};
+}
+
+// w of section 24: the power over the squared distance from the cell's centre to the bound's centre, no nearer than the two
+// radii together.  max and min are `x > y ? x : y` and `x < y ? x : y`, so w is in [0, 3.4028235e38] -- never a NaN -- whatever
+// the bound holds, and the floats order as their bit patterns do.
+DEV float grid_weight(v4f bnd, float p, f3 cc, float hd) {
+    const f3 v = mk(bnd.x, bnd.y, bnd.z) - cc;
+    const float d2 = (v.x * v.x + v.y * v.y) + v.z * v.z;
+    const float r0 = bnd.w + hd;
+    const float fl = r0 * r0;
+    const float x = p / (d2 > fl ? d2 : fl);
+    const float w = x < 3.4028235e38f ? x : 3.4028235e38f;
+    return p > 0.0f ? w : 0.0f;
+}
+
+// One block per cell, row = blockIdx.x, and GRID_CHUNK entries of its row per step.  Sweep 1: the row's largest weight, folded
+// on the bit pattern over the wave and through one LDS word.  Sweep 2: w again from the record's 20 bytes (L2 holds them; a
+// rows * N float scratch would cost a global round trip more than it saves), q, and the inclusive sums chunk by chunk -- a wave
+// scan by lane shuffles, the four waves joined through LDS, the chunk's total carried into the next.  Integer sums: the row
+// does not depend on the scan's shape.  The row is the only global write, 4 B per lane, coalesced.
+constexpr uint32_t GRID_CHUNK = 256u;
+__global__ void __launch_bounds__(256) k_grid_rows(const v4f* __restrict__ bound, const float* __restrict__ power, uint32_t n,
+                                                   const rb_probe_grid grid, float scale, uint32_t* __restrict__ tables) {
+    __shared__ uint32_t row_max;
+    __shared__ uint32_t wave_sum[4];
+    const uint32_t row = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t nx = grid.counts[0], ny = grid.counts[1];
+    const uint32_t ix = row % nx, iy = (row / nx) % ny, iz = row / (nx * ny);
+    const f3 cc = mk(grid.origin[0] + ((float)ix + 0.5f) * grid.step[0], grid.origin[1] + ((float)iy + 0.5f) * grid.step[1],
+                     grid.origin[2] + ((float)iz + 0.5f) * grid.step[2]);
+    const float sx = grid.step[0], sy = grid.step[1], sz = grid.step[2];
+    const float hd = sqrt_exact(0.25f * ((sx * sx + sy * sy) + sz * sz));
+
+    if (tid == 0u) row_max = 0u;
+    __syncthreads();
+    uint32_t bits = 0u;
+    for (uint32_t j = tid; j < n; j += GRID_CHUNK) bits = max(bits, __float_as_uint(grid_weight(bound[j], power[j], cc, hd)));
+    for (int off = 32; off > 0; off >>= 1) bits = max(bits, (uint32_t)__shfl_xor((int)bits, off, 64));
+    if (lane == 0u && bits != 0u) atomicMax(&row_max, bits);
+    __syncthreads();
+    const float wmax = __uint_as_float(row_max);
+
+    uint32_t* const out = tables + (size_t)row * n;
+    uint32_t carry = 0u;
+    for (uint32_t base = 0u; base < n; base += GRID_CHUNK) {   // (n <= 2^24: base + tid does not wrap)
+        const uint32_t j = base + tid;
+        uint32_t q = 0u;
+        if (j < n) {
+            const float p = power[j];
+            if (p > 0.0f) q = wmax > 0.0f ? max(1u, (uint32_t)((grid_weight(bound[j], p, cc, hd) / wmax) * scale)) : 1u;
+        }
+        uint32_t sum = q;
+        for (uint32_t off = 1u; off < 64u; off <<= 1) {
+            const uint32_t up = (uint32_t)__shfl_up((int)sum, off, 64);
+            if (lane >= off) sum += up;
+        }
+        if (lane == 63u) wave_sum[wave] = sum;
+        __syncthreads();
+        const uint32_t s0 = wave_sum[0], s1 = wave_sum[1], s2 = wave_sum[2], s3 = wave_sum[3];
+        const uint32_t before = wave == 0u ? 0u : wave == 1u ? s0 : wave == 2u ? s0 + s1 : (s0 + s1) + s2;
+        if (j < n) out[j] = (carry + before) + sum;
+        carry += ((s0 + s1) + s2) + s3;
+        __syncthreads();   // wave_sum is the next chunk's
+    }
 }
 
 // ======================================================= k_direct_fold ====
@@ -335,6 +450,33 @@ int launch_emitter_cdf(const rb_emitter* em, uint32_t n, void* work, uint32_t* c
     return (int)rocprim::inclusive_scan(tmp, scan, q, cdf, n, rocprim::plus<uint32_t>(), stream);
 }
 
+// the powers, the word of their largest (k_emit_power's, not read here) and the bounds of n records
+size_t emitter_grid_work_bytes(uint32_t n) { return align256(4u * (size_t)n) + 256u + align256(16u * (size_t)n) + 256u; }
+
+// tables[rows * n] of em[n] over `grid` (section 24), queued on `stream`: the powers and the bounds, one lane per record, then
+// one block per cell.  Nothing is waited for.  The caller has checked the grid and rows * n <= RB_MAX_GRID_ENTRIES.
+int launch_emitter_grid(const rb_emitter* em, uint32_t n, const rb_probe_grid& grid, void* work, uint32_t* tables, void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (n == 0u) return 0;
+    const uint64_t rows = (uint64_t)grid.counts[0] * grid.counts[1] * grid.counts[2];
+    if (em == nullptr || work == nullptr || tables == nullptr || n > RB_MAX_EMITTERS || rows == 0u || rows * n > RB_MAX_GRID_ENTRIES)
+        return (int)hipErrorInvalidValue;
+    char* const base = static_cast<char*>(work);
+    float* const power = reinterpret_cast<float*>(base);
+    uint32_t* const pmax = reinterpret_cast<uint32_t*>(base + align256(4u * (size_t)n));
+    v4f* const bound = reinterpret_cast<v4f*>(base + align256(4u * (size_t)n) + 256u);
+    uint32_t L = 0u;
+    while ((1u << L) < n) L++;
+    const float scale = (float)(1u << (24u - L));
+    if (const hipError_t st = hipMemsetAsync(pmax, 0, sizeof(uint32_t), stream)) return (int)st;
+    hipLaunchKernelGGL(k_emit_power, dim3((n + 255u) / 256u), dim3(256), 0, stream, em, n, power, pmax);
+    if (const hipError_t st = hipGetLastError()) return (int)st;
+    hipLaunchKernelGGL(k_emit_bound, dim3((n + 255u) / 256u), dim3(256), 0, stream, em, n, bound);
+    if (const hipError_t st = hipGetLastError()) return (int)st;
+    hipLaunchKernelGGL(k_grid_rows, dim3((uint32_t)rows), dim3(256), 0, stream, bound, power, n, grid, scale, tables);
+    return (int)hipGetLastError();
+}
+
 uint64_t emitter_candidates(const EmitArgs& s) { return (uint64_t)s.n_tris + s.n_spheres + s.n_lights; }
 
 // flags and offsets of every candidate, the scan's own scratch behind them; 0: the scan could not be sized
@@ -377,8 +519,9 @@ int launch_emitter_scatter(const EmitArgs& s, const void* work, rb_emitter* out,
 
 // One piece: every record, bound and colour of it, queued on `stream`; nothing is waited for.  Item order: g.n surfels rounded
 // up to whole blocks of 64, the padding written as invalid items; linear order: g.n surfels' g.n * samples items.
-// `cdf`: nullptr for the uniform pick (k_light_rays), or g.n_emit inclusive pick weights in device memory (k_light_rays_cdf)
-int launch_light_rays(const LightGenArgs& g, void* stream_, const uint32_t* cdf) {
+// `cdf`: nullptr for the uniform pick (k_light_rays), or g.n_emit inclusive pick weights in device memory (k_light_rays_cdf);
+// with `cells`, one such table per cell of that grid (k_light_rays_grid)
+int launch_light_rays(const LightGenArgs& g, void* stream_, const uint32_t* cdf, const rb_probe_grid* cells) {
     if (g.n == 0u) return 0;
     if (g.surfels == nullptr || g.recs == nullptr || g.tmax == nullptr || g.contrib == nullptr || g.samples == 0u) return (int)hipErrorInvalidValue;
     if (g.emitters == nullptr && (g.n_emit != 0u)) return (int)hipErrorInvalidValue;
@@ -386,7 +529,9 @@ int launch_light_rays(const LightGenArgs& g, void* stream_, const uint32_t* cdf)
     const uint64_t lanes = gen_lanes(g.n, g.samples, g.linear);
     if (lanes == 0u) return (int)hipErrorInvalidValue;
     const dim3 grid((uint32_t)((lanes + 255u) / 256u));
-    if (cdf != nullptr && g.n_emit != 0u)
+    if (cdf != nullptr && cells != nullptr && g.n_emit != 0u)
+        hipLaunchKernelGGL(k_light_rays_grid, grid, dim3(256), 0, static_cast<hipStream_t>(stream_), g, cdf, *cells);
+    else if (cdf != nullptr && g.n_emit != 0u)
         hipLaunchKernelGGL(k_light_rays_cdf, grid, dim3(256), 0, static_cast<hipStream_t>(stream_), g, cdf);
     else
         hipLaunchKernelGGL(k_light_rays, grid, dim3(256), 0, static_cast<hipStream_t>(stream_), g);

@@ -204,6 +204,10 @@ struct rb_engine {
     rb::DevBuf<uint32_t> emit_cdf, emit_cdf_given;
     rb::DevBuf<unsigned char> emit_cdf_work;
     bool emit_cdf_valid = false;
+    // the pick per grid cell (rb_emitter_grid_cdf_device / rb_direct_light_grid): the tables of one call
+    // -- made for it, or a caller's as the host form stages them -- and the build's scratch.  The engine keeps no grid.
+    rb::DevBuf<uint32_t> emit_grid_tables;
+    rb::DevBuf<unsigned char> emit_grid_work;
     // lightmap texels made on the device (rb_lightmap_surfels_device / rb_bake_lightmap*): the triangles
     // prepared in triangle order, the cover pass's scratch, and what a bake keeps between its stages
     rb::DevBuf<rb::PrepTri> lm_ptris;

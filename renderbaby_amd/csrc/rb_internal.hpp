@@ -490,10 +490,14 @@ struct LightGenArgs {
     uint32_t linear;
 };
 // `cdf`: the pick weighted by g.n_emit inclusive uint32 weights in device memory (k_light_rays_cdf)
-int launch_light_rays(const LightGenArgs& g, void* stream, const uint32_t* cdf = nullptr);
+// ... with `grid`: one such table per cell of it, row after row (k_light_rays_grid)
+int launch_light_rays(const LightGenArgs& g, void* stream, const uint32_t* cdf = nullptr, const rb_probe_grid* grid = nullptr);
 // the table by power of em[n] into cdf[n] over `work` (emitter_cdf_work_bytes; 0: the scan could not be sized); queued, no wait
 size_t emitter_cdf_work_bytes(uint32_t n);
 int launch_emitter_cdf(const rb_emitter* em, uint32_t n, void* work, uint32_t* cdf, void* stream);
+// the tables per cell of em[n] over `grid` into tables[rows * n], over `work` (emitter_grid_work_bytes); queued, no wait
+size_t emitter_grid_work_bytes(uint32_t n);
+int launch_emitter_grid(const rb_emitter* em, uint32_t n, const rb_probe_grid& grid, void* work, uint32_t* tables, void* stream);
 int launch_direct_fold(const uint8_t* occl, const float* contrib, uint32_t n, uint32_t samples, uint32_t linear, rb_radiance* out, void* stream);
 // ---- rb_probe.hip: irradiance probes made on the device.  One launch of k_probe_rays writes the records
 // of one piece of whole probes, in k_cam_rays' format and k_hemi_rays' two orders; k_sh_project folds the colours launch_radiance

@@ -532,6 +532,7 @@ struct DirectCall {
     const rb_emitter* emitters;
     uint32_t n_emit;
     const uint32_t* cdf = nullptr;   // the pick weights of rb_direct_light_cdf, n_emit of them; nullptr: the uniform pick
+    const rb_probe_grid* grid = nullptr;   // rb_direct_light_grid: `cdf` holds one table of n_emit per cell of this grid (section 24)
 };
 
 rb::LightGenArgs light_gen_args(const DirectCall& c, const rb_surfel* surfels, const uint32_t* ids, rb_ray* recs, float* tmax, float* contrib,
@@ -576,7 +577,7 @@ int direct_piece(rb_engine* e, const rb::KParams& p, const DirectCall& c, const 
                  rb_radiance* out, rb::LaunchInfo* li) {
     rb::LightGenArgs g = light_gen_args(c, surfels, ids, e->q_rays.ptr, e->q_tmax.ptr, e->rad_colors.ptr, done, m);
     g.linear = direct_linear(m) ? 1u : 0u;
-    if (const int st = e->t_generator.timed(e->stream, [&] { return rb::launch_light_rays(g, e->stream, c.cdf); })) return st;
+    if (const int st = e->t_generator.timed(e->stream, [&] { return rb::launch_light_rays(g, e->stream, c.cdf, c.grid); })) return st;
     rb::OcclArgs a{};
     a.q.rays = e->q_rays.ptr;
     a.q.n = static_cast<uint32_t>(direct_items(m, c.samples));
@@ -628,6 +629,88 @@ int direct_light_locked(rb_engine* e, bool device, bool weighted, const rb_emitt
             if (cdf) HIP_TRY(e, hipMemcpyAsync(e->emit_cdf_given.ptr, cdf, n_emit * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
             else if (const int rc = queue_emitter_cdf(e, c.emitters, c.n_emit, e->emit_cdf_given.ptr)) return rc;
             c.cdf = e->emit_cdf_given.ptr;
+        }
+    }
+    return run_family(e, device, "direct light", RB_HEMI_PIECE_ITEMS, n, samples,
+                      {FAMILY_ARRAY(surfels, e->hemi_surfels, 16, "d_surfels"), FAMILY_ARRAY(seeds, e->rad_seeds, 4, "d_seeds")},
+                      FAMILY_ARRAY(out, e->rad_out, 16, "d_out"), [&](size_t piece) { return direct_scratch(e, piece, samples); },
+                      [&](const rb::KParams& p, const void* const* in, void* o, size_t done, size_t m, rb::LaunchInfo* li) {
+                          return direct_piece(e, p, c, static_cast<const rb_surfel*>(in[0]), static_cast<const uint32_t*>(in[1]), done, m,
+                                              static_cast<rb_radiance*>(o), li);
+                      });
+}
+
+// ---- direct light with the emitters picked per grid cell (rb_abi.h)
+size_t grid_cells(const rb_probe_grid& g) { return static_cast<size_t>(g.counts[0]) * g.counts[1] * g.counts[2]; }
+
+// the tables of the n records at d_em over `grid` into d_tables, over the engine's scratch; queued, nothing waits
+int queue_emitter_grid(rb_engine* e, const rb_emitter* d_em, uint32_t n, const rb_probe_grid& grid, uint32_t* d_tables) {
+    HIP_TRY(e, e->emit_grid_work.reserve(rb::emitter_grid_work_bytes(n)));
+    const int st = rb::launch_emitter_grid(d_em, n, grid, e->emit_grid_work.ptr, d_tables, e->stream);
+    if (st) return rb::fail(e, RB_ERR_DEVICE, "grid table launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
+    return RB_OK;
+}
+
+// the scene's table for a call that names its length: the table, made if need be, and n_emit held to its count
+int scene_emitters_counted(rb_engine* e, size_t n_emit) {
+    rb::KParams p{};
+    bool built = false;
+    int rc = query_prologue(e, &p);
+    if (!rc) rc = ensure_emitters(e, p, &built);
+    if (rc) return rc;
+    if (n_emit != e->emit_n) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "n_emit is %zu, the scene's table has %u emitters", n_emit, e->emit_n);
+    return RB_OK;
+}
+
+// rb_emitter_grid_cdf_device: the caller's buffers, the scene's table where it is asked for -- outside the events --, the build
+int emitter_grid_device_locked(rb_engine* e, const rb_emitter* d_emitters, size_t n_emit, const rb_probe_grid& grid, uint32_t* d_tables) {
+    int rc = n_emit > 0 ? device_range(e, d_tables, grid_cells(grid) * n_emit * sizeof(uint32_t), 4, "d_tables_out") : RB_OK;
+    if (!rc && d_emitters && n_emit > 0) rc = device_range(e, d_emitters, n_emit * sizeof(rb_emitter), 16, "d_emitters");
+    if (!rc) rc = d_emitters ? query_prologue(e, nullptr) : scene_emitters_counted(e, n_emit);
+    if (rc) return rc;
+    e->last_query_kernel_name = "k_grid_rows";
+    if (n_emit == 0) return RB_OK;
+    HIP_TRY(e, e->t_query.begin(e->stream));
+    if ((rc = queue_emitter_grid(e, d_emitters ? d_emitters : e->emit_table.ptr, static_cast<uint32_t>(n_emit), grid, d_tables))) return rc;
+    HIP_TRY(e, e->t_query.end(e->stream));
+    return RB_OK;
+}
+
+// rb_direct_light_grid in both forms: direct_light_locked with one table per cell, the caller's or made for this call; the
+// pieces share them
+int direct_light_grid_locked(rb_engine* e, bool device, const rb_emitter* emitters, const rb_probe_grid& grid, const uint32_t* tables,
+                             size_t n_emit, const rb_surfel* surfels, const uint32_t* seeds, size_t n, const rb_light_params& prm,
+                             uint32_t first_sample, uint32_t samples, rb_radiance* out) {
+    DirectCall c{prm, first_sample, samples, emitters, static_cast<uint32_t>(n_emit)};
+    c.grid = &grid;
+    const size_t entries = grid_cells(grid) * n_emit;
+    if (device) {   // every buffer of the caller's before anything is queued or a table is made: a refused call has done nothing
+        int rc = device_range(e, surfels, n * sizeof(rb_surfel), 16, "d_surfels");
+        if (!rc && seeds) rc = device_range(e, seeds, n * sizeof(uint32_t), 4, "d_seeds");
+        if (!rc) rc = device_range(e, out, n * sizeof(rb_radiance), 16, "d_out");
+        if (!rc && emitters && n_emit > 0) rc = device_range(e, emitters, n_emit * sizeof(rb_emitter), 16, "d_emitters");
+        if (!rc && tables && entries > 0) rc = device_range(e, tables, entries * sizeof(uint32_t), 4, "d_tables");
+        if (rc) return rc;
+    }
+    if (!emitters) {   // the scene's own table
+        if (const int rc = scene_emitters_counted(e, n_emit)) return rc;
+        c.emitters = e->emit_table.ptr;
+    } else {
+        if (const int rc = require_ready(e)) return rc;
+        if (!device) {   // a caller's table in host memory: staged once per call
+            HIP_TRY(e, e->emit_given.reserve(std::max<size_t>(n_emit, 1)));
+            if (n_emit > 0) HIP_TRY(e, hipMemcpyAsync(e->emit_given.ptr, emitters, n_emit * sizeof(rb_emitter), hipMemcpyHostToDevice, e->stream));
+            c.emitters = e->emit_given.ptr;
+        }
+    }
+    if (entries > 0) {
+        if (device && tables) {
+            c.cdf = tables;
+        } else {
+            HIP_TRY(e, e->emit_grid_tables.reserve(entries));
+            if (tables) HIP_TRY(e, hipMemcpyAsync(e->emit_grid_tables.ptr, tables, entries * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+            else if (const int rc = queue_emitter_grid(e, c.emitters, c.n_emit, grid, e->emit_grid_tables.ptr)) return rc;
+            c.cdf = e->emit_grid_tables.ptr;
         }
     }
     return run_family(e, device, "direct light", RB_HEMI_PIECE_ITEMS, n, samples,
@@ -867,6 +950,23 @@ int light_points_check(rb_engine* e, const char* who, const rb_probe_grid* g, co
     return RB_OK;
 }
 
+// the refusals the entry points of the pick per grid cell share (section 24), before a device is touched: a NULL grid,
+// rb_light_points' of the grid, the entry cap
+int emitter_grid_check(rb_engine* e, const char* who, const rb_probe_grid* g, size_t n_emit) {
+    if (const int rc = light_points_check(e, who, g, nullptr, nullptr, 0, nullptr)) return rc;
+    if (n_emit > RB_MAX_EMITTERS) return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s takes at most 2^24 emitters", who);
+    if (static_cast<uint64_t>(grid_cells(*g)) * std::max<size_t>(n_emit, 1) > RB_MAX_GRID_ENTRIES)
+        return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: the grid's tables take at most 2^26 entries (cells times emitters)", who);
+    return RB_OK;
+}
+
+// tables in host memory: every row a table in cdf_check's sense
+int grid_tables_check(rb_engine* e, const char* who, const rb_probe_grid& g, const uint32_t* tables, size_t n_emit) {
+    for (size_t r = 0, rows = grid_cells(g); r < rows && n_emit > 0; r++)
+        if (const int rc = cdf_check(e, who, tables + r * n_emit, n_emit)) return rc;
+    return RB_OK;
+}
+
 size_t grid_probes(const rb_probe_grid& g) { return static_cast<size_t>(g.counts[0]) * g.counts[1] * g.counts[2]; }
 
 // points per launch of the engine-less rb_light_points: RB_LIGHT_PIECE_POINTS in the environment (tests: a piece boundary at
@@ -1039,6 +1139,24 @@ int direct_light_entry(rb_engine* e, const char* who, bool device, bool weighted
         },
         [&](rb_engine* t) {
             return direct_light_locked(t, device, weighted, emitters, cdf, n_emit, surfels, seeds, n, *prm, first_sample, samples, out);
+        });
+}
+
+// the two engine entry points of rb_direct_light_grid; tables in host memory are looked at here
+int direct_light_grid_entry(rb_engine* e, const char* who, bool device, const rb_emitter* emitters, const rb_probe_grid* grid,
+                            const uint32_t* tables, size_t n_emit, const rb_surfel* surfels, const uint32_t* seeds, size_t n,
+                            const rb_light_params* prm, uint32_t first_sample, uint32_t samples, rb_radiance* out) {
+    return engine_entry(
+        e, n,
+        [&] {
+            if (n > 0 && (!surfels || !prm || !out)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "%s: surfels / params / out is NULL", who);
+            if (prm)
+                if (const int rc = light_check(e, who, prm, n_emit, n, first_sample, samples, true)) return rc;
+            if (const int rc = emitter_grid_check(e, who, grid, n_emit)) return rc;
+            return (tables && !device) ? grid_tables_check(e, who, *grid, tables, n_emit) : RB_OK;
+        },
+        [&](rb_engine* t) {
+            return direct_light_grid_locked(t, device, emitters, *grid, tables, n_emit, surfels, seeds, n, *prm, first_sample, samples, out);
         });
 }
 
@@ -1224,18 +1342,23 @@ int bake_lightmap_entry(rb_engine* e, const char* who, bool device, const rb_lig
 }
 
 
-// rb_light_rays and rb_light_rays_cdf (`weighted`: the pick by `cdf`, or by the table's power where it is NULL)
+// rb_light_rays, rb_light_rays_cdf (`weighted`: the pick by `cdf`, or by the table's power where it is NULL) and
+// rb_light_rays_grid (`gridded`: `cdf` holds one table per cell of `grid`, or NULL: made here)
 int light_rays_entry(const char* who, int32_t device, bool weighted, const rb_emitter* emitters, const uint32_t* cdf, size_t n_emit,
                      const rb_surfel* surfels, const uint32_t* seeds, size_t n, const rb_light_params* params, uint32_t first_sample,
-                     uint32_t samples, rb_ray* rays_out, float* tmax_out, float* contrib_out) {
+                     uint32_t samples, rb_ray* rays_out, float* tmax_out, float* contrib_out, bool gridded = false,
+                     const rb_probe_grid* grid = nullptr) {
     if ((n_emit > 0 && !emitters) || (n > 0 && (!surfels || !params || !rays_out || !tmax_out || !contrib_out)))
         return rb::fail(nullptr, RB_ERR_NULL_ARGUMENT, "%s: emitters / surfels / params / rays_out / tmax_out / contrib_out is NULL", who);
     if (params)
         if (const int rc = light_check(nullptr, who, params, n_emit, n, first_sample, samples, false)) return rc;
+    if (gridded)
+        if (const int rc = emitter_grid_check(nullptr, who, grid, n_emit)) return rc;
     if (cdf)
-        if (const int rc = cdf_check(nullptr, who, cdf, n_emit)) return rc;
+        if (const int rc = gridded ? grid_tables_check(nullptr, who, *grid, cdf, n_emit) : cdf_check(nullptr, who, cdf, n_emit)) return rc;
     if (n == 0) return RB_OK;
     const size_t piece = std::min(n, std::max<size_t>((size_t(1) << 22) / samples, 1));   // whole surfels, about 2^22 items
+    const size_t entries = (gridded ? grid_cells(*grid) : 1) * n_emit;
     rb::DevBuf<rb_emitter> d_emit;
     rb::DevBuf<rb_surfel> d_surfels;
     rb::DevBuf<uint32_t> d_ids;
@@ -1252,22 +1375,25 @@ int light_rays_entry(const char* who, int32_t device, bool weighted, const rb_em
     s.alloc(d_contrib, piece * samples * 4);
     s.upload(d_emit.ptr, emitters, n_emit * sizeof(rb_emitter));   // once per call
     if (weighted && n_emit > 0) {
-        s.alloc(d_cdf, n_emit);
+        s.alloc(d_cdf, entries);
         if (cdf) {
-            s.upload(d_cdf.ptr, cdf, n_emit * sizeof(uint32_t));
+            s.upload(d_cdf.ptr, cdf, entries * sizeof(uint32_t));
+        } else if (gridded) {
+            s.alloc(d_work, rb::emitter_grid_work_bytes(static_cast<uint32_t>(n_emit)));
+            s.run([&] { return rb::launch_emitter_grid(d_emit.ptr, static_cast<uint32_t>(n_emit), *grid, d_work.ptr, d_cdf.ptr, s.stream); });
         } else {
             s.alloc(d_work, std::max<size_t>(rb::emitter_cdf_work_bytes(static_cast<uint32_t>(n_emit)), 256));
             s.run([&] { return rb::launch_emitter_cdf(d_emit.ptr, static_cast<uint32_t>(n_emit), d_work.ptr, d_cdf.ptr, s.stream); });
         }
     }
-    const DirectCall c{*params, first_sample, samples, d_emit.ptr, static_cast<uint32_t>(n_emit), d_cdf.ptr};
+    const DirectCall c{*params, first_sample, samples, d_emit.ptr, static_cast<uint32_t>(n_emit), d_cdf.ptr, gridded ? grid : nullptr};
     for (size_t done = 0; done < n && s.ok(); done += piece) {
         const size_t m = std::min(piece, n - done), items = m * samples;
         s.upload(d_surfels.ptr, surfels + done, m * sizeof(rb_surfel));
         if (seeds) s.upload(d_ids.ptr, seeds + done, m * sizeof(uint32_t));
         rb::LightGenArgs g = light_gen_args(c, d_surfels.ptr, seeds ? d_ids.ptr : nullptr, d_rays.ptr, d_tmax.ptr, d_contrib.ptr, done, m);
         g.linear = 1u;
-        s.run([&] { return rb::launch_light_rays(g, s.stream, c.cdf); });
+        s.run([&] { return rb::launch_light_rays(g, s.stream, c.cdf, c.grid); });
         s.download(rays_out + done * samples, d_rays.ptr, items * sizeof(rb_ray));
         s.download(tmax_out + done * samples, d_tmax.ptr, items * sizeof(float));
         s.download(contrib_out + done * samples * 4, d_contrib.ptr, items * 4 * sizeof(float));
@@ -1542,6 +1668,56 @@ int rb_direct_light_cdf_device(rb_engine* e, const rb_emitter* d_emitters, const
                                rb_radiance* d_out) {
     return direct_light_entry(e, "rb_direct_light_cdf_device", true, true, d_emitters, d_cdf, n_emit, d_surfels, d_seeds, n, params, first_sample,
                               samples, d_out);
+}
+
+int rb_emitter_grid_cdf(int32_t device, const rb_emitter* emitters, size_t n_emit, const rb_probe_grid* grid, uint32_t* tables_out) {
+    if (!grid || (n_emit > 0 && (!emitters || !tables_out)))
+        return rb::fail(nullptr, RB_ERR_NULL_ARGUMENT, "rb_emitter_grid_cdf: grid / emitters / tables_out is NULL");
+    if (const int rc = emitter_grid_check(nullptr, "rb_emitter_grid_cdf", grid, n_emit)) return rc;
+    if (n_emit == 0) return RB_OK;
+    const size_t entries = grid_cells(*grid) * n_emit;
+    rb::DevBuf<rb_emitter> d_emit;
+    rb::DevBuf<uint32_t> d_tables;
+    rb::DevBuf<unsigned char> d_work;
+    DeviceScope s(device);
+    s.alloc(d_emit, n_emit);
+    s.alloc(d_tables, entries);
+    s.alloc(d_work, rb::emitter_grid_work_bytes(static_cast<uint32_t>(n_emit)));
+    s.upload(d_emit.ptr, emitters, n_emit * sizeof(rb_emitter));
+    s.run([&] { return rb::launch_emitter_grid(d_emit.ptr, static_cast<uint32_t>(n_emit), *grid, d_work.ptr, d_tables.ptr, s.stream); });
+    s.download(tables_out, d_tables.ptr, entries * sizeof(uint32_t));
+    return s.finish("rb_emitter_grid_cdf");
+}
+
+int rb_emitter_grid_cdf_device(rb_engine* e, const rb_emitter* d_emitters, size_t n_emit, const rb_probe_grid* grid, uint32_t* d_tables_out) {
+    return engine_entry(
+        e,
+        [&]() -> int {
+            if (!grid || (n_emit > 0 && !d_tables_out)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "rb_emitter_grid_cdf_device: grid / d_tables_out is NULL");
+            return emitter_grid_check(e, "rb_emitter_grid_cdf_device", grid, n_emit);
+        },
+        [&](rb_engine* t) { return emitter_grid_device_locked(t, d_emitters, n_emit, *grid, d_tables_out); });
+}
+
+int rb_light_rays_grid(int32_t device, const rb_emitter* emitters, const rb_probe_grid* grid, const uint32_t* tables, size_t n_emit,
+                       const rb_surfel* surfels, const uint32_t* seeds, size_t n, const rb_light_params* params, uint32_t first_sample,
+                       uint32_t samples, rb_ray* rays_out, float* tmax_out, float* contrib_out) {
+    return light_rays_entry("rb_light_rays_grid", device, true, emitters, tables, n_emit, surfels, seeds, n, params, first_sample, samples, rays_out,
+                            tmax_out, contrib_out, true, grid);
+}
+
+int rb_direct_light_grid(rb_engine* e, const rb_emitter* emitters, const rb_probe_grid* grid, const uint32_t* tables, size_t n_emit,
+                         const rb_surfel* surfels, const uint32_t* seeds, size_t n, const rb_light_params* params, uint32_t first_sample,
+                         uint32_t samples, rb_radiance* out) {
+    return direct_light_grid_entry(e, "rb_direct_light_grid", false, emitters, grid, tables, n_emit, surfels, seeds, n, params, first_sample, samples,
+                                   out);
+}
+
+int rb_direct_light_grid_device(rb_engine* e, const rb_emitter* d_emitters, const rb_probe_grid* grid, const uint32_t* d_tables, size_t n_emit,
+                                const rb_surfel* d_surfels, const uint32_t* d_seeds, size_t n, const rb_light_params* params,
+                                uint32_t first_sample, uint32_t samples, rb_radiance* d_out) {
+    return direct_light_grid_entry(e, "rb_direct_light_grid_device", true, d_emitters, grid, d_tables, n_emit, d_surfels, d_seeds, n, params,
+                                   first_sample, samples, d_out);
 }
 
 int rb_probe_rays(int32_t device, const rb_probe* probes, const uint32_t* seeds, size_t n, uint32_t first_sample, uint32_t samples,

@@ -9,9 +9,12 @@ of ``rb_direct_light`` bit for bit.
 ``pick``            the emitter an item's first draw picks
 ``emitter_weights``, ``emitter_cdf``, ``pick_cdf``  the pick weighted by a table (section 23): the power of every record, the
                     quantised inclusive table ``rb_emitter_cdf`` makes of them, and the record an item's first draw picks from a table
+``emitter_bounds``, ``grid_weights``, ``emitter_grid_cdf``, ``grid_cell``  the pick per grid cell (section 24): a sphere about
+                    every record, its weight in every cell, the tables ``rb_emitter_grid_cdf`` makes -- one row per cell --, and
+                    the row a surfel's position searches
 ``barycentrics``, ``points``  the point an item's second and third draws make on its emitter, and the emitter's normal there
 ``rays``          (origins, directions, bounds, contributions) of the items: what ``rb_light_rays`` returns -- with ``cdf``,
-                    what ``rb_light_rays_cdf`` returns
+                    what ``rb_light_rays_cdf`` returns; with ``grid``, what ``rb_light_rays_grid`` returns
 ``fold``            abi.RADIANCE[m] from the contributions and the any-hit bytes of the items' shadow rays
 """
 import numpy as np
@@ -179,6 +182,107 @@ def pick_cdf(u0, cdf):
     return j, q, Q
 
 
+def _gt(x, y):
+    """max(x, y) as section 24 has it: x > y ? x : y"""
+    return np.where(x > y, x, y).astype(f32)
+
+
+def _grid(grid):
+    """(origin (3,) float32, step (3,) float32, counts (3,) int64, rows) of an abi.PROBE_GRID whose counts count cells"""
+    g = np.asarray(grid, dtype=abi.PROBE_GRID).reshape(())
+    cnt = g["counts"].astype(np.int64)
+    return g["origin"].astype(f32), g["step"].astype(f32), cnt, int(cnt[0] * cnt[1] * cnt[2])
+
+
+def emitter_bounds(em):
+    """(ce (n, 3), re (n,)) float32, a sphere that holds every record (section 24).  A triangle: ce = a + ((b + c) 0.33333334),
+    re = sqrt of the largest of |a - ce|^2, |(a + b) - ce|^2, |(a + c) - ce|^2; any other kind: ce = a, re = |b.x|."""
+    e = np.asarray(em, dtype=abi.EMITTER).reshape(-1)
+    a, b, c = e["a"].astype(f32), e["b"].astype(f32), e["c"].astype(f32)
+    with np.errstate(all="ignore"):
+        ce = (a + ((b + c).astype(f32) * f32(0.33333334)).astype(f32)).astype(f32)
+        ls = []
+        for corner in (a, (a + b).astype(f32), (a + c).astype(f32)):
+            v = (corner - ce).astype(f32)
+            ls.append(_dot(v, v).astype(f32))
+        re = np.sqrt(_gt(_gt(ls[0], ls[1]), ls[2]), dtype=f32)
+    tri = e["kind"] == abi.HIT_TRIANGLE
+    return np.where(tri[:, None], ce, a).astype(f32), np.where(tri, re, np.abs(b[:, 0])).astype(f32)
+
+
+def grid_centres(grid):
+    """(rows, 3) float32: cc = origin + (float(i) + 0.5) step of every cell, row = (iz ny + iy) nx + ix"""
+    org, step, cnt, rows = _grid(grid)
+    r = np.arange(rows, dtype=np.int64)
+    idx = np.stack([r % cnt[0], (r // cnt[0]) % cnt[1], r // (cnt[0] * cnt[1])], axis=1)
+    with np.errstate(all="ignore"):
+        return (org[None, :] + ((idx.astype(f32) + f32(0.5)).astype(f32) * step[None, :]).astype(f32)).astype(f32)
+
+
+def grid_weights(em, grid):
+    """w (rows, n) float32 of section 24: p_j / max(d2, (re + hd)^2), at most 3.4028235e38, and 0 where p_j is 0; never a NaN"""
+    p = emitter_weights(em)
+    ce, re = emitter_bounds(em)
+    _, step, _, rows = _grid(grid)
+    cc = grid_centres(grid)
+    with np.errstate(all="ignore"):
+        hd = np.sqrt((f32(0.25) * (((step[0] * step[0]).astype(f32) + (step[1] * step[1]).astype(f32)).astype(f32)
+                                   + (step[2] * step[2]).astype(f32)).astype(f32)).astype(f32), dtype=f32)
+        v = (ce[None, :, :] - cc[:, None, :]).astype(f32)
+        d2 = _dot(v, v).astype(f32)
+        r0 = (re + hd).astype(f32)
+        fl = np.broadcast_to((r0 * r0).astype(f32)[None, :], d2.shape)
+        x = (p[None, :] / _gt(d2, fl)).astype(f32)
+        w = np.where(x < MAX_WEIGHT, x, MAX_WEIGHT).astype(f32)
+    return np.where(p[None, :] > 0, w, f32(0)).astype(f32).reshape(rows, len(p))
+
+
+def emitter_grid_cdf(em, grid):
+    """uint32[rows * n], the tables of section 24, row r at [r n, (r + 1) n): q = max(1, uint((w / wmax_r) float(S))) for
+    p_j > 0 -- 1 where the row's largest weight is 0 --, else 0, summed inclusively along the row.  What rb_emitter_grid_cdf
+    returns."""
+    p = emitter_weights(em)
+    n = len(p)
+    rows = _grid(grid)[3]
+    if n > abi.MAX_EMITTERS or rows * max(n, 1) > abi.MAX_GRID_ENTRIES:
+        raise ValueError("at most 2^24 emitters and 2^26 entries are taken")
+    if n == 0:
+        return np.zeros(0, u32)
+    w = grid_weights(em, grid)
+    wmax = w.max(axis=1)[:, None]
+    with np.errstate(all="ignore"):
+        r = ((w / wmax).astype(f32) * f32(cdf_scale(n))).astype(f32)
+        some = np.broadcast_to(wmax > 0, w.shape)
+        q = np.where(some, np.maximum(np.where(some, r, f32(0)).astype(u32), u32(1)), u32(1))
+        q = np.where(p[None, :] > 0, q, u32(0)).astype(u32)
+    return np.cumsum(q, axis=1, dtype=u64).astype(u32).reshape(-1)
+
+
+def grid_cell(pos, grid):
+    """row (m,) int64 of the cell each of (m, 3) finite positions searches (section 24): per axis f = (pos - origin) / step,
+    i = min(uint(max(f, 0)), count - 1), truncating and saturating; the nearest cell for a point outside the grid"""
+    org, step, cnt, _ = _grid(grid)
+    pos = np.asarray(pos, f32).reshape(-1, 3)
+    with np.errstate(all="ignore"):
+        f = ((pos - org[None, :]).astype(f32) / step[None, :]).astype(f32)
+        f = np.where(f > 0, f, f32(0)).astype(f32)
+        big = ~(f < f32(4294967296.0))
+        i = np.minimum(np.where(big, f32(0), f).astype(np.int64), (cnt - 1)[None, :])
+        i = np.where(big, (cnt - 1)[None, :], i)
+    return (i[:, 2] * cnt[1] + i[:, 1]) * cnt[0] + i[:, 0]
+
+
+def pick_grid(u0, rows, tables, n_emit):
+    """(j, q, Q) per item of ``pick_cdf`` in the row each item searches; an item whose row is < 0 makes no pick (q = 0)"""
+    tables = np.asarray(tables, u32).reshape(-1, n_emit)
+    u0 = np.asarray(u0, f32).reshape(-1)
+    j, q, Q = np.zeros(len(u0), np.int64), np.zeros(len(u0), u32), np.zeros(len(u0), np.int64)
+    for r in np.unique(rows[rows >= 0]):
+        sel = rows == r
+        j[sel], q[sel], Q[sel] = pick_cdf(u0[sel], tables[r])
+    return j, q, Q
+
+
 def barycentrics(u1, u2):
     """(bu, bv) of a triangle's point: su = sqrt(u1), bv = u2 su, bu = su - bv; the point is (a + bu b) + bv c"""
     u1, u2 = np.asarray(u1, f32), np.asarray(u2, f32)
@@ -206,14 +310,16 @@ def points(E, u1, u2):
     return np.where(tri, q_tri, q_sph).astype(f32), np.where(tri, ne_tri, ne_sph).astype(f32)
 
 
-def rays(emitters, surf, first_sample, samples, seeds=None, offset=1e-3, shorten=1e-3, cdf=None):
+def rays(emitters, surf, first_sample, samples, seeds=None, offset=1e-3, shorten=1e-3, cdf=None, grid=None, tables=None):
     """(origins (n, 3), directions (n, 3), bounds (n,), contributions (n, 4)) of the items (surfel, sample), surfel-major -- item
     i * samples + k is sample ``first_sample`` + k of ``surf[i]`` --: what rb_light_rays returns.  A lit item has a bound above
     0 and its unoccluded contribution; a dark one the bound 0 and +0 +0 +0; the fourth component is 1 for a valid item.  An
     invalid item (an invalid surfel, section 16.1) has its surfel's position as given and direction 0 0 0.
     ``cdf``: a uint32 table of pick weights, one inclusive entry per emitter (``emitter_cdf``, or any contents): what
     rb_light_rays_cdf returns (section 23) -- the pick by ``pick_cdf``, the factor float(Q) / float(q) in place of float(N); an
-    item the table leaves without a pick is dark and has direction 0 0 0, as every item of an empty table."""
+    item the table leaves without a pick is dark and has direction 0 0 0, as every item of an empty table.
+    ``grid``: an abi.PROBE_GRID of cells: what rb_light_rays_grid returns (section 24) -- the same with every item searching the
+    row of ``tables`` (uint32[rows * n_emit], any contents; None: ``emitter_grid_cdf``) that ``grid_cell`` gives its surfel."""
     em = np.asarray(emitters, dtype=abi.EMITTER).reshape(-1)
     n_emit = len(em)
     if n_emit > abi.MAX_EMITTERS:
@@ -240,7 +346,18 @@ def rays(emitters, surf, first_sample, samples, seeds=None, offset=1e-3, shorten
     if n_emit == 0 or n == 0:
         return org, d, tmax, contrib
     with np.errstate(all="ignore"):
-        if cdf is None:
+        if grid is not None:
+            if cdf is not None:
+                raise ValueError("cdf and grid: one pick at a time")
+            tables = emitter_grid_cdf(em, grid) if tables is None else np.asarray(tables, u32).reshape(-1)
+            if len(tables) != _grid(grid)[3] * n_emit:
+                raise ValueError("tables: one entry per cell and emitter is needed")
+            row = np.where(ok, grid_cell(np.where(ok[:, None], pos, f32(0)), grid), -1)[i]
+            j, q, Q = pick_grid(dr["u0"], row, tables, n_emit)
+            valid = valid & (q != 0)
+            fn = (Q.astype(f32) / q.astype(f32)).astype(f32)
+            E = em[j]
+        elif cdf is None:
             fn = f32(n_emit)
             E = em[pick(dr["u0"], n_emit)]
         else:

@@ -634,6 +634,26 @@ class Engine:
         self._check(self._lib.rb_scene_emitter_cdf(self._h, host_ptr(table), len(table), C.byref(count)))
         return table
 
+    def emitter_grid(self, grid, emitters=None, out=None):
+        """rb_emitter_grid_cdf_device: the pick tables per grid cell (``direct.emitter_grid_cdf`` is the
+        model) of an abi.PROBE_GRID whose counts count cells -- uint32[rows * n], row r at [r n, (r + 1) n).  ``emitters``: None
+        for the scene's own table, or an abi.EMITTER table of the caller's.  Host arrays in, a numpy array out; a tensor for
+        ``emitters`` or ``out`` (int32 / uint32, rows * n entries) keeps everything on the engine's device and the tensor comes
+        back: ``direct_light(pick=("grid", grid, tables))`` takes it as it is.  The engine keeps no grid."""
+        g, rows = grid_records(grid)
+        f = Form(self.query_device, emitters, out, staged=True)
+        tp, n_emit = None, len(self.scene_emitters())
+        if emitters is not None:
+            table, tp = f.input("emitters", emitters, abi.EMITTER)
+            n_emit = len(table)
+        if rows * max(n_emit, 1) > abi.MAX_GRID_ENTRIES:
+            raise ValueError("grid: at most 2^26 entries (cells times emitters) are taken")
+        if out is None:
+            out = device_new(np.int32, rows * n_emit, self.query_device)
+        res, op = f.output("out", out, CDF, rows * n_emit)
+        self._device_call(self._lib.rb_emitter_grid_cdf_device, tp, n_emit, g.ctypes.data, op)
+        return f.result(res, CDF)
+
     @staticmethod
     def _light_params(offset, shorten, mask=abi.MASK_ALL):
         prm = np.zeros(1, dtype=abi.LIGHT_PARAMS)
@@ -654,11 +674,18 @@ class Engine:
         "power": rb_direct_light_cdf by the table's power, the scene's kept weights (``scene_emitter_cdf``) or those made for
         the caller's table; or the caller's own inclusive weights beside the caller's ``emitters``, a uint32 array or an
         int32 / uint32 tensor with one entry per emitter.  The estimate keeps its mean as long as every emitter that can
-        light a point keeps a weight above 0."""
+        light a point keeps a weight above 0.
+        ("grid", grid) or ("grid", grid, tables): rb_direct_light_grid, the pick per grid cell -- ``grid``
+        an abi.PROBE_GRID whose counts count cells, ``tables`` what ``emitter_grid`` returns (None: made for this call)."""
         samples, first_sample = _sample_range(samples, first_sample)
         surf = surfel_records(points, normals)
-        weights = None
-        if isinstance(pick, str):
+        weights, cells = None, None
+        if isinstance(pick, tuple):
+            if len(pick) not in (2, 3) or pick[0] != "grid":
+                raise ValueError('pick: ("grid", grid) or ("grid", grid, tables)')
+            cells, rows = grid_records(pick[1])
+            weights = pick[2] if len(pick) == 3 else None
+        elif isinstance(pick, str):
             if pick not in ("uniform", "power"):
                 raise ValueError('pick: "uniform", "power" or a table of weights')
         elif emitters is None:
@@ -684,6 +711,15 @@ class Engine:
             self._query(f, "rb_direct_light", tp, n_emit, fp, sp, n, prm.ctypes.data, first_sample, samples, op)
             return res
         cp = None
+        if cells is not None:
+            if emitters is None:
+                n_emit = len(self.scene_emitters())
+            if weights is not None:
+                if f.on_device and not is_tensor(weights):
+                    weights = upload(host_in("pick", weights, CDF)[0].view(np.int32), np.dtype(np.int32), self.query_device)
+                weights, cp = f.input("pick", weights, CDF, rows * n_emit)
+            self._query(f, "rb_direct_light_grid", tp, cells.ctypes.data, cp, n_emit, fp, sp, n, prm.ctypes.data, first_sample, samples, op)
+            return res
         if weights is not None:
             if f.on_device and not is_tensor(weights):
                 weights = upload(host_in("pick", weights, CDF)[0].view(np.int32), np.dtype(np.int32), self.query_device)
@@ -1097,13 +1133,28 @@ def emitter_cdf(emitters, device=-1):
     return cdf
 
 
-def light_rays(emitters, points, normals, samples, first_sample=0, seeds=None, offset=1e-3, shorten=1e-3, device=-1, cdf=None):
+def emitter_grid_cdf(emitters, grid, device=-1):
+    """rb_emitter_grid_cdf: the pick tables per grid cell of an abi.EMITTER table and an abi.PROBE_GRID whose counts count cells, no
+    engine -> uint32[rows * n], row r at [r n, (r + 1) n).  ``direct.emitter_grid_cdf`` is its numpy model."""
+    f, call = _engineless(device)
+    table, tp = f.input("emitters", emitters, abi.EMITTER)
+    g, rows = grid_records(grid)
+    if rows * max(len(table), 1) > abi.MAX_GRID_ENTRIES:
+        raise ValueError("grid: at most 2^26 entries (cells times emitters) are taken")
+    tables = np.zeros(rows * len(table), dtype=CDF)
+    call("rb_emitter_grid_cdf", tp, len(table), g.ctypes.data, host_ptr(tables))
+    return tables
+
+
+def light_rays(emitters, points, normals, samples, first_sample=0, seeds=None, offset=1e-3, shorten=1e-3, device=-1, cdf=None, grid=None,
+               tables=None):
     """rb_light_rays: the generator of direct_light alone, no engine -- (abi.RAY[m * samples], float32 bounds[m * samples],
     float32 contributions (m * samples, 4)) of an abi.EMITTER table and (m, 3) points and normals, item i * samples + k: the
     shadow ray's origin and direction (0 0 0: an invalid item), the bound rb_occluded walks it to (0: a dark item) and the
     unoccluded contribution with 1 for a valid item behind it.  ``direct.rays`` is its numpy model.  ``cdf``: None for the
     uniform pick, or rb_light_rays_cdf's weighted one: "power", or uint32 inclusive weights, one per
-    emitter."""
+    emitter.  ``grid``: rb_light_rays_grid's pick per grid cell by ``tables`` (uint32[rows * n]; None: made
+    for this call)."""
     f, call = _engineless(device)
     table, tp = f.input("emitters", emitters, abi.EMITTER)
     surf, fp = f.input("points", surfel_records(np.asarray(points, np.float32), np.asarray(normals, np.float32)), abi.SURFEL)
@@ -1111,6 +1162,14 @@ def light_rays(emitters, points, normals, samples, first_sample=0, seeds=None, o
     tmax, contrib = np.zeros(len(rays), dtype=np.float32), np.zeros((len(rays), 4), dtype=np.float32)
     seeds, sp = f.optional("seeds", seeds, SEEDS, len(surf))
     prm = Engine._light_params(offset, shorten)
+    if grid is not None:
+        if cdf is not None:
+            raise ValueError("cdf and grid: one pick at a time")
+        g, rows = grid_records(grid)
+        tables, cp = f.optional("tables", tables, CDF, rows * len(table))
+        call("rb_light_rays_grid", tp, g.ctypes.data, cp, len(table), fp, sp, len(surf), prm.ctypes.data, int(first_sample), int(samples),
+             host_ptr(rays), host_ptr(tmax), host_ptr(contrib))
+        return rays, tmax, contrib
     if cdf is None:
         call("rb_light_rays", tp, len(table), fp, sp, len(surf), prm.ctypes.data, int(first_sample), int(samples), host_ptr(rays),
              host_ptr(tmax), host_ptr(contrib))
