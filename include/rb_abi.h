@@ -1275,6 +1275,50 @@ int rb_direct_light_grid_device(rb_engine* e, const rb_emitter* d_emitters, cons
                                 const rb_surfel* d_surfels, const uint32_t* d_seeds, size_t n, const rb_light_params* params,
                                 uint32_t first_sample, uint32_t samples, rb_radiance* d_out);
 
+/* ---- Per-cell tables that learn visibility from tallies (the normative definition;
+ * renderbaby_amd/direct.py: tally, grid_weights(tally=...), emitter_grid_cdf(tally=...), bit for bit).  Section 24's weight has no
+ * visibility term; every direct-light call pays for one -- the any-hit byte of every shadow ray -- and the fold forgets which
+ * emitter in which cell it belonged to.  Here the caller keeps that answer and the table build uses it.  Additive: nothing
+ * above changes.
+ *   TALLY   rb_grid_tally[rows N], record r N + j belongs to emitter j in cell r (GRID of section 24, the same cap).  uint32_t
+ *           sums that wrap; the caller owns the array, its lifetime and its zeroing.
+ *   COUNT   item (i, k) of a grid call has section 24's row r and pick j.  It is counted when the bound stored for it is > 0:
+ *           valid, picked and lit, a real shadow ray.  A counted item adds 1 to tried[r N + j], and 1 to seen[r N + j] if its
+ *           result byte is RB_OCCL_VISIBLE.  Invalid surfels, items without a pick, items facing away and padding count nothing.
+ *           Integer atomics: the sums are exact in any order.
+ *   WEIGHT  t = tried, s = min(seen, tried), prior a finite with 0 < a <= 16777216: f = ((float)s + a) / ((float)t + a);
+ *           w' = w * f with w of section 24; wmax_r, q_j and the row as section 24 with w' for w; the floor of 1 stays with
+ *           p_j > 0.  f is in [0, 1] and never a NaN -- above 0 for a >= 2^-117, below that it can underflow --, and an emitter
+ *           with power stays reachable by the floor, so the estimator keeps its mean for any tally.  An all-zero tally, and one
+ *           with seen >= tried everywhere, give rb_emitter_grid_cdf's rows bit for bit (f = 1).
+ * Tables are unbiased for any samples that did not go into their tally: train on one sample range, render another. */
+typedef struct rb_grid_tally {
+    uint32_t tried, seen;
+} rb_grid_tally;
+/* rb_direct_light_grid with one more argument, the tally (rows n_emit records), read and written: the count of every piece is
+ * queued behind its walk and its kernel time is added to the call's.  out may be NULL for a training-only call (no fold runs);
+ * with out given the sums are rb_direct_light_grid's bits.  The host form uploads the tally once, every piece adds to the one
+ * device copy, and the call downloads it at the end.  tally == NULL: RB_ERR_NULL_ARGUMENT.  Every other refusal is
+ * rb_direct_light_grid's, comes before a device is touched and leaves the tally unwritten.  Pieces, sharded engines,
+ * multi-device handles, the reported names and times as rb_direct_light_grid. */
+int rb_direct_light_grid_tally(rb_engine* e, const rb_emitter* emitters, const rb_probe_grid* grid, const uint32_t* tables, size_t n_emit,
+                               const rb_surfel* surfels, const uint32_t* seeds, size_t n, const rb_light_params* params,
+                               uint32_t first_sample, uint32_t samples, rb_radiance* out, rb_grid_tally* tally);
+/* The same on device memory of the engine's device: d_tally (4-byte aligned, rows n_emit records) is range-checked, the call
+ * queues and returns. */
+int rb_direct_light_grid_tally_device(rb_engine* e, const rb_emitter* d_emitters, const rb_probe_grid* grid, const uint32_t* d_tables,
+                                      size_t n_emit, const rb_surfel* d_surfels, const uint32_t* d_seeds, size_t n,
+                                      const rb_light_params* params, uint32_t first_sample, uint32_t samples, rb_radiance* d_out,
+                                      rb_grid_tally* d_tally);
+/* rb_emitter_grid_cdf with WEIGHT above: protocol and refusals are its own; a prior that is not finite, <= 0 or > 16777216 is
+ * RB_ERR_INVALID_OPTIONS, a NULL tally with n_emit > 0 RB_ERR_NULL_ARGUMENT. */
+int rb_emitter_grid_learned(int32_t device, const rb_emitter* emitters, size_t n_emit, const rb_probe_grid* grid, const rb_grid_tally* tally,
+                            float prior, uint32_t* tables_out);
+/* rb_emitter_grid_cdf_device with WEIGHT above; d_tally 4-byte aligned, range-checked.  The engine keeps nothing.
+ * rb_last_query_kernel_name reports "k_grid_rows_seen". */
+int rb_emitter_grid_learned_device(rb_engine* e, const rb_emitter* d_emitters, size_t n_emit, const rb_probe_grid* grid,
+                                   const rb_grid_tally* d_tally, float prior, uint32_t* d_tables_out);
+
 /* ---- Edge-avoiding denoiser over the first-hit buffers (no reference counterpart).  An a-trous wavelet
  * filter (Dammertz et al. 2010) on the albedo-demodulated mean radiance, guided by the first hit of every pixel-centre ray.
  * Section 13 is the normative definition: every step one IEEE binary32 operation in a fixed order, so that the device's result
@@ -1479,6 +1523,7 @@ static_assert(offsetof(rb_emitter, b) == 16, "b @16");
 static_assert(offsetof(rb_emitter, area) == 44, "area @44");
 static_assert(offsetof(rb_emitter, emissive) == 48, "emissive @48");
 static_assert(sizeof(rb_light_params) == 32, "rb_light_params is 32 B");
+static_assert(sizeof(rb_grid_tally) == 8, "rb_grid_tally is 8 B");
 static_assert(offsetof(rb_light_params, mask) == 8, "mask @8");
 static_assert(sizeof(rb_guide) == 48, "rb_guide is 48 B");
 static_assert(sizeof(rb_denoise_params) == 32, "rb_denoise_params is 32 B");
@@ -1525,6 +1570,7 @@ _Static_assert(sizeof(rb_probe_depth) == 1024, "rb_probe_depth is 1024 B");
 _Static_assert(sizeof(rb_light_visibility) == 16, "rb_light_visibility is 16 B");
 _Static_assert(sizeof(rb_emitter) == 64, "rb_emitter is 64 B");
 _Static_assert(sizeof(rb_light_params) == 32, "rb_light_params is 32 B");
+_Static_assert(sizeof(rb_grid_tally) == 8, "rb_grid_tally is 8 B");
 _Static_assert(sizeof(rb_guide) == 48, "rb_guide is 48 B");
 _Static_assert(sizeof(rb_denoise_params) == 32, "rb_denoise_params is 32 B");
 _Static_assert(sizeof(rb_view) == 64, "rb_view is 64 B");

@@ -364,6 +364,41 @@ class Engine final : public Renderer {
                                   uint32_t samples, uint32_t first_sample = 0) {
         check(h_->e, rb_direct_light_grid_device(h_->e, d_emitters, &grid, d_tables, n_emit, d_surfels, d_seeds, n, &p, first_sample, samples, d_out));
     }
+    // ---- ... and tables that learn visibility (extension; rb_abi.h): `tally` holds one record per cell and
+    // emitter, which the call adds its shadow rays to (the caller zeroes it and keeps it); `sums` false: a training-only call
+    std::vector<rb_radiance> direct_light_grid_tally(const std::vector<rb_surfel>& surfels, const rb_probe_grid& grid, uint32_t samples,
+                                                     std::vector<rb_grid_tally>& tally, size_t scene_count = 0, uint32_t first_sample = 0,
+                                                     const uint32_t* seeds = nullptr, const rb_light_params& p = light_params(),
+                                                     const std::vector<rb_emitter>& emitters = {}, const std::vector<uint32_t>& tables = {},
+                                                     bool sums = true) {
+        const size_t n_emit = emitters.empty() ? scene_count : emitters.size();
+        const size_t entries = n_emit * grid.counts[0] * grid.counts[1] * grid.counts[2];
+        if (tally.size() != entries || (!tables.empty() && tables.size() != entries))
+            throw std::invalid_argument("direct_light_grid_tally: one entry per cell and emitter is needed");
+        std::vector<rb_radiance> out(sums ? surfels.size() : 0);
+        rb_grid_tally none{};
+        check(h_->e, rb_direct_light_grid_tally(h_->e, emitters.empty() ? nullptr : emitters.data(), &grid, tables.empty() ? nullptr : tables.data(),
+                                                n_emit, surfels.data(), seeds, surfels.size(), &p, first_sample, samples,
+                                                sums ? out.data() : nullptr, tally.empty() ? &none : tally.data()));
+        return out;
+    }
+    void direct_light_grid_tally_device(const rb_emitter* d_emitters, const rb_probe_grid& grid, const uint32_t* d_tables, size_t n_emit,
+                                        const rb_surfel* d_surfels, const uint32_t* d_seeds, size_t n, const rb_light_params& p,
+                                        rb_radiance* d_out, rb_grid_tally* d_tally, uint32_t samples, uint32_t first_sample = 0) {
+        check(h_->e, rb_direct_light_grid_tally_device(h_->e, d_emitters, &grid, d_tables, n_emit, d_surfels, d_seeds, n, &p, first_sample,
+                                                       samples, d_out, d_tally));
+    }
+    static std::vector<uint32_t> emitter_grid_learned(const std::vector<rb_emitter>& emitters, const rb_probe_grid& grid,
+                                                      const std::vector<rb_grid_tally>& tally, float prior = 1.0f, int32_t device = -1) {
+        std::vector<uint32_t> out(emitters.size() * grid.counts[0] * grid.counts[1] * grid.counts[2]);
+        if (tally.size() != out.size()) throw std::invalid_argument("emitter_grid_learned: one record per cell and emitter is needed");
+        check(nullptr, rb_emitter_grid_learned(device, emitters.data(), emitters.size(), &grid, tally.data(), prior, out.data()));
+        return out;
+    }
+    void emitter_grid_learned_device(const rb_emitter* d_emitters, size_t n_emit, const rb_probe_grid& grid, const rb_grid_tally* d_tally,
+                                     float prior, uint32_t* d_tables_out) {
+        check(h_->e, rb_emitter_grid_learned_device(h_->e, d_emitters, n_emit, &grid, d_tally, prior, d_tables_out));
+    }
     // ---- lightmap texels made on the device (extension; rb_abi.h): the surfel of every texel of an atlas
     // over the scene's uvs, and the bake of the whole map in one call (rgba in sample_texture's layout, row 0 on top)
     static rb_lightmap_params lightmap_params(uint32_t width, uint32_t height, uint32_t mesh = RB_LIGHTMAP_ALL_MESHES, bool flip = false,

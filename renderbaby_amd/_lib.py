@@ -110,6 +110,10 @@ SIGNATURES = {
     "rb_light_rays_grid": (i32, [i32, vp, vp, vp, sz, vp, vp, sz, vp, u32, u32, vp, vp, vp]),
     "rb_direct_light_grid": (i32, [vp, vp, vp, vp, sz, vp, vp, sz, vp, u32, u32, vp]),
     "rb_direct_light_grid_device": (i32, [vp, vp, vp, vp, sz, vp, vp, sz, vp, u32, u32, vp]),
+    "rb_direct_light_grid_tally": (i32, [vp, vp, vp, vp, sz, vp, vp, sz, vp, u32, u32, vp, vp]),
+    "rb_direct_light_grid_tally_device": (i32, [vp, vp, vp, vp, sz, vp, vp, sz, vp, u32, u32, vp, vp]),
+    "rb_emitter_grid_learned": (i32, [i32, vp, sz, vp, vp, C.c_float, vp]),
+    "rb_emitter_grid_learned_device": (i32, [vp, vp, sz, vp, vp, C.c_float, vp]),
     "rb_lightmap_surfels": (i32, [i32, vp, sz, vp, sz, vp, vp, vp]),
     "rb_lightmap_surfels_device": (i32, [vp, vp, vp, vp]),
     "rb_lightmap_resolve": (i32, [i32, u32, u32, vp, u32, vp]),

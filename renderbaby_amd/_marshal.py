@@ -16,6 +16,8 @@ RECORDS = {rec: (np.dtype(elem), rec.itemsize // np.dtype(elem).itemsize) for re
 # ... and a table a call reads whole, beside its per-item arrays: the emitters of direct_light, (n, 16) float32
 # ... and the per-pixel planes of ``Engine.reproject``: guide records, (n, 12) float32, and frame records, (n, 4)
 TABLES = {rec: (np.dtype(np.float32), rec.itemsize // 4) for rec in (abi.EMITTER, abi.GUIDE, abi.FRAME_RECORD)}
+# ... and the tally a grid call of direct_light adds to, one record per (cell, emitter): (n, 2) int32, only the bits count
+TABLES[abi.GRID_TALLY] = (np.dtype(np.int32), 2)
 # the ids of random streams: uint32 on the host; as a tensor int32 or uint32, only the bits count
 SEEDS = np.dtype(np.uint32)
 # the pick weights of direct_light, one inclusive entry per emitter: the same words under the same rule

@@ -95,6 +95,9 @@ EMITTER = np.dtype([("a", f4, (3,)), ("kind", u4), ("b", f4, (3,)), ("prim", u4)
 LIGHT_PARAMS = np.dtype([("offset", f4), ("shorten", f4), ("mask", u4), ("flags", u4), ("_reserved", u4, (4,))])
 MAX_EMITTERS = 1 << 24
 MAX_GRID_ENTRIES = 1 << 26   # cells times emitters of the pick per grid cell
+# the tally of shadow rays tried and seen per (cell, emitter), record r * n + j, and the largest prior
+GRID_TALLY = np.dtype([("tried", u4), ("seen", u4)])
+MAX_PRIOR = 16777216.0
 # any-hit occlusion (rb_occluded): result bytes and stage masks
 OCCL_VISIBLE, OCCL_OCCLUDED, OCCL_INVALID = 0, 1, 255
 MASK_GROUND, MASK_TRIANGLES, MASK_SPHERES, MASK_LIGHTS, MASK_ALL = 1, 2, 4, 8, 15

@@ -101,7 +101,13 @@ def direct_irradiance(engine, points, normals, samples, emitters=None, first_sam
     the engine's device -> an (m, 3) tensor there.  A point without a valid sample is 0 0 0.  ``pick``: Engine.direct_light's --
     "uniform", "power" (emitters picked in proportion to emission times area: the same mean with less noise where the lights
     differ), a caller's table of weights (section 23), or ("grid", grid[, tables]): a table per cell of a grid, weighted by
-    power over squared distance to the cell (section 24; ``pick_grid`` makes such a grid)."""
+    power over squared distance to the cell (section 24; ``pick_grid`` makes such a grid); or ("learned", grid, rounds, samples):
+    such tables times the visibility ``learn_grid`` observes at these points first, over ``rounds`` x ``samples`` training
+    samples that lie behind the rendered range and are not rendered (section 25)."""
+    if isinstance(pick, tuple) and len(pick) > 0 and pick[0] == "learned":
+        from . import engine as _engine
+        pick = _learned(engine, pick, _engine.surfel_records(points, normals), samples, emitters=emitters, first_sample=first_sample,
+                        seeds=seeds, offset=offset, shorten=shorten, mask=mask)
     return _mean(engine.direct_light(points, normals, samples, emitters=emitters, first_sample=first_sample, seeds=seeds, offset=offset,
                                      shorten=shorten, mask=mask, pick=pick))
 
@@ -125,15 +131,63 @@ def pick_grid(emitters, counts, points=None):
     return g
 
 
+def learn_grid(engine, grid, surfels, rounds, samples, prior=1.0, emitters=None, first_sample=1 << 20, seeds=None, offset=1e-3,
+               shorten=1e-3, mask=abi.MASK_ALL):
+    """Pick tables per grid cell that have learned which emitters the surfels see: ``rounds`` training-only
+    calls of Engine.direct_light(tally=...) over ``surfels`` (abi.SURFEL records, or a tensor of them), ``samples`` samples each
+    -- round r draws samples ``first_sample`` + r ``samples`` ... --, round 0 on section 24's tables and every later round on
+    the tables of the round before, all adding to one running tally; after each round Engine.emitter_grid(tally=..., prior=...)
+    makes the next tables.  -> (tables, tally) as the engine's forms return them: numpy arrays for numpy surfels, tensors on
+    the engine's device for a tensor.  The tables are unbiased for any samples that did not go into their tally: render with
+    a sample range the training did not use.  ``rounds`` = 0: section 24's tables and an empty tally."""
+    from . import engine as _engine
+    rounds, samples, first_sample = int(rounds), int(samples), int(first_sample)
+    if rounds < 0 or samples < 1 or first_sample + rounds * samples > 2 ** 32:
+        raise ValueError("learn_grid: rounds >= 0, samples >= 1, and the training samples must end within 32 bits")
+    g, rows = _engine.grid_records(grid)
+    on_device = _engine.is_tensor(surfels)
+    n_emit = len(engine.scene_emitters()) if emitters is None else len(emitters)
+    if on_device:
+        import torch
+        tally = torch.zeros((rows * n_emit, 2), dtype=torch.int32, device=surfels.device)
+        given = emitters
+        if emitters is not None and not _engine.is_tensor(emitters):   # staged once for all rounds
+            given = _engine.upload(np.ascontiguousarray(emitters, dtype=abi.EMITTER), abi.EMITTER, engine.query_device)
+        tables = engine.emitter_grid(g, emitters=given, out=torch.zeros(rows * n_emit, dtype=torch.int32, device=surfels.device))
+    else:
+        tally = np.zeros(rows * n_emit, dtype=abi.GRID_TALLY)
+        given = emitters
+        tables = engine.emitter_grid(g, emitters=given)
+    for r in range(rounds):
+        engine.direct_light(surfels, None, samples, emitters=given, first_sample=first_sample + r * samples, seeds=seeds, offset=offset,
+                            shorten=shorten, mask=mask, out=False, pick=("grid", g, tables), tally=tally)
+        tables = engine.emitter_grid(g, emitters=given, tally=tally, prior=prior, out=tables if on_device else None)
+    return tables, tally
+
+
+def _learned(engine, pick, surf, samples, first_sample=0, **kw):
+    """``pick`` as Engine.direct_light takes it: ("learned", grid, rounds, samples[, prior]) becomes ("grid", grid, tables) with
+    tables trained on the sample range behind the rendered one"""
+    if not (isinstance(pick, tuple) and len(pick) > 0 and pick[0] == "learned"):
+        return pick
+    if len(pick) not in (4, 5):
+        raise ValueError('pick: ("learned", grid, rounds, samples) or ("learned", grid, rounds, samples, prior)')
+    tables, _ = learn_grid(engine, pick[1], surf, pick[2], pick[3], prior=pick[4] if len(pick) == 5 else 1.0,
+                           first_sample=int(first_sample) + int(samples), **kw)
+    return ("grid", pick[1], tables)
+
+
 def lightmap_direct(engine, width, height, samples, emitters=None, first_sample=0, mesh=None, flip=False, offset=1e-3, shorten=1e-3,
                     mask=abi.MASK_ALL, dilate=2, pick="uniform"):
     """``lightmap`` with direct light alone: the surfels of the engine's scene over its uvs (Engine.lightmap_surfels on the
     device), ``samples`` shadow rays per texel (Engine.direct_light on the device; the stream id is the texel index), the
     resolve of the sums (lightmap_resolve) -> float32 (height, width, 4) in ``lightmap``'s layout.  No surfel is ever on the
-    host; the sums cross once.  ``pick``: Engine.direct_light's."""
+    host; the sums cross once.  ``pick``: ``direct_irradiance``'s, ("learned", grid, rounds, samples) included: the training runs over
+    the same texels, on the device."""
     from . import engine as _engine
     surf, _ = engine.lightmap_surfels(width, height, mesh=mesh, flip=flip, out=(_engine.device_new(abi.SURFEL, int(width) * int(height),
                                                                                                      engine.query_device), None))
+    pick = _learned(engine, pick, surf, samples, emitters=emitters, first_sample=first_sample, offset=offset, shorten=shorten, mask=mask)
     sums = engine.direct_light(surf, None, samples, emitters=emitters, first_sample=first_sample, offset=offset, shorten=shorten, mask=mask,
                                pick=pick)
     return _engine.lightmap_resolve(_engine.download(sums, abi.RADIANCE), width, height, dilate=dilate, device=engine.query_device)

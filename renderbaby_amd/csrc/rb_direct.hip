@@ -7,10 +7,15 @@
 // same item with the emitter found in a table by a halving search.
 // And the pick per grid cell (rb_emitter_grid_cdf, rb_light_rays_grid, rb_direct_light_grid; section 24): one such table per
 // cell of a regular grid, weighted by power over squared distance to the cell, and the item searching the row of its surfel's cell.
+// And the tables that learn visibility (rb_direct_light_grid_tally, rb_emitter_grid_learned; section 25): a count per (cell,
+// emitter) of shadow rays tried and seen, kept by integer atomics behind the walk, and section 24's weight times the seen share.
 // The generator runs before the kernels that walk the records (k_occl*, rb_query.hip), as k_hemi_rays does (section 16).  Same
 // numerics contract as rb_kernels.hip: every step one binary32 operation in the order written, no FMA contraction, correctly
 // rounded / and sqrt, so that renderbaby_amd/direct.py equals this file bit for bit.
 #include <hip/hip_runtime.h>
+
+#include <cstdlib>
+#include <cstring>
 
 #include <rocprim/device/device_scan.hpp>
 
@@ -122,6 +127,44 @@ DEV uint32_t grid_axis(float pos, float origin, float step, uint32_t count) {
     return f >= 4294967296.0f ? count - 1u : min((uint32_t)f, count - 1u);
 }
 
+// The pick from a table (sections 23.1 and 24.1), once for the generator and for the count of section 25: the row a valid
+// item's position searches (PICK_GRID; `row` stays 0 otherwise), Q, the halving search, q and the factor float(Q) / float(q).
+// Returns whether the item has a pick; an invalid item reads the total of the table's first row and nothing else.
+template <PickMode kPick>
+DEV bool table_pick(const uint32_t* __restrict__ cdf, const rb_probe_grid* grid, uint32_t N, bool valid, f3 pos, float u0, uint32_t& row,
+                    uint32_t& j, float& fn) {
+    if constexpr (kPick == PICK_GRID) {
+        if (valid) {
+            const uint32_t ix = grid_axis(pos.x, grid->origin[0], grid->step[0], grid->counts[0]);
+            const uint32_t iy = grid_axis(pos.y, grid->origin[1], grid->step[1], grid->counts[1]);
+            const uint32_t iz = grid_axis(pos.z, grid->origin[2], grid->step[2], grid->counts[2]);
+            row = (iz * grid->counts[1] + iy) * grid->counts[0] + ix;
+            cdf += (size_t)row * N;   // rows * N <= RB_MAX_GRID_ENTRIES
+        }
+    }
+    const uint32_t Q = N != 0u ? cdf[N - 1u] : 0u;
+    bool picked = Q != 0u && Q <= (1u << 24);
+    if (valid && picked) {
+        const float fq = (float)Q;   // Q <= 2^24: exact
+        const uint32_t tq = min((uint32_t)(u0 * fq), Q - 1u);
+        uint32_t lo = 0u, len = N;
+        while (len > 1u) {
+            const uint32_t half = len >> 1;
+            if (cdf[lo + half - 1u] <= tq) {
+                lo += half;
+                len -= half;
+            } else {
+                len = half;
+            }
+        }
+        j = lo;
+        const uint32_t q = cdf[j] - (j != 0u ? cdf[j - 1u] : 0u);
+        picked = q != 0u;
+        fn = fq / (float)q;
+    }
+    return picked;
+}
+
 template <PickMode kPick>
 DEV void light_item(const LightGenArgs g, const uint32_t* __restrict__ cdf, const rb_probe_grid* grid = nullptr) {
     constexpr bool kCdf = kPick != PICK_UNIFORM;
@@ -156,35 +199,9 @@ DEV void light_item(const LightGenArgs g, const uint32_t* __restrict__ cdf, cons
     uint32_t j = 0u;
     float fn = 0.0f;       // the factor: float(N), or float(Q) / float(q)
     bool picked = N != 0u;
-    if constexpr (kPick == PICK_GRID) {
-        if (valid) {
-            const uint32_t ix = grid_axis(pos.x, grid->origin[0], grid->step[0], grid->counts[0]);
-            const uint32_t iy = grid_axis(pos.y, grid->origin[1], grid->step[1], grid->counts[1]);
-            const uint32_t iz = grid_axis(pos.z, grid->origin[2], grid->step[2], grid->counts[2]);
-            cdf += (size_t)((iz * grid->counts[1] + iy) * grid->counts[0] + ix) * N;   // rows * N <= RB_MAX_GRID_ENTRIES
-        }
-    }
     if constexpr (kCdf) {
-        const uint32_t Q = N != 0u ? cdf[N - 1u] : 0u;
-        picked = Q != 0u && Q <= (1u << 24);
-        if (valid && picked) {
-            const float fq = (float)Q;   // Q <= 2^24: exact
-            const uint32_t tq = min((uint32_t)(u0 * fq), Q - 1u);
-            uint32_t lo = 0u, len = N;
-            while (len > 1u) {
-                const uint32_t half = len >> 1;
-                if (cdf[lo + half - 1u] <= tq) {
-                    lo += half;
-                    len -= half;
-                } else {
-                    len = half;
-                }
-            }
-            j = lo;
-            const uint32_t q = cdf[j] - (j != 0u ? cdf[j - 1u] : 0u);
-            picked = q != 0u;
-            fn = fq / (float)q;
-        }
+        uint32_t row = 0u;
+        picked = table_pick<kPick>(cdf, grid, N, valid, pos, u0, row, j, fn);
     }
     if (valid && picked) {
         if constexpr (!kCdf) {
@@ -328,9 +345,18 @@ DEV float grid_weight(v4f bnd, float p, f3 cc, float hd) {
 // rows * N float scratch would cost a global round trip more than it saves), q, and the inclusive sums chunk by chunk -- a wave
 // scan by lane shuffles, the four waves joined through LDS, the chunk's total carried into the next.  Integer sums: the row
 // does not depend on the scan's shape.  The row is the only global write, 4 B per lane, coalesced.
+// kSeen (section 25): w' = w f in both sweeps, f from the 8-byte record of (row, j) in the caller's tally and the prior.
 constexpr uint32_t GRID_CHUNK = 256u;
-__global__ void __launch_bounds__(256) k_grid_rows(const v4f* __restrict__ bound, const float* __restrict__ power, uint32_t n,
-                                                   const rb_probe_grid grid, float scale, uint32_t* __restrict__ tables) {
+
+// f of section 25: ((float)s + a) / ((float)t + a) with s = min(seen, tried); in [0, 1], never a NaN, for 0 < a <= 2^24
+DEV float seen_share(const uint32_t* __restrict__ rec, float prior) {   // two 4-byte loads: the tally is 4-byte aligned
+    const uint32_t t = rec[0], s = min(rec[1], t);
+    return ((float)s + prior) / ((float)t + prior);
+}
+
+template <bool kSeen>
+DEV void grid_rows(const v4f* __restrict__ bound, const float* __restrict__ power, uint32_t n, const rb_probe_grid& grid, float scale,
+                   uint32_t* __restrict__ tables, const uint32_t* __restrict__ tally, float prior) {
     __shared__ uint32_t row_max;
     __shared__ uint32_t wave_sum[4];
     const uint32_t row = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
@@ -344,7 +370,12 @@ __global__ void __launch_bounds__(256) k_grid_rows(const v4f* __restrict__ bound
     if (tid == 0u) row_max = 0u;
     __syncthreads();
     uint32_t bits = 0u;
-    for (uint32_t j = tid; j < n; j += GRID_CHUNK) bits = max(bits, __float_as_uint(grid_weight(bound[j], power[j], cc, hd)));
+    if constexpr (kSeen) tally += (size_t)row * n * 2u;   // rows * n <= RB_MAX_GRID_ENTRIES records
+    for (uint32_t j = tid; j < n; j += GRID_CHUNK) {
+        float w = grid_weight(bound[j], power[j], cc, hd);
+        if constexpr (kSeen) w = w * seen_share(tally + (size_t)j * 2u, prior);
+        bits = max(bits, __float_as_uint(w));
+    }
     for (int off = 32; off > 0; off >>= 1) bits = max(bits, (uint32_t)__shfl_xor((int)bits, off, 64));
     if (lane == 0u && bits != 0u) atomicMax(&row_max, bits);
     __syncthreads();
@@ -357,7 +388,11 @@ __global__ void __launch_bounds__(256) k_grid_rows(const v4f* __restrict__ bound
         uint32_t q = 0u;
         if (j < n) {
             const float p = power[j];
-            if (p > 0.0f) q = wmax > 0.0f ? max(1u, (uint32_t)((grid_weight(bound[j], p, cc, hd) / wmax) * scale)) : 1u;
+            if (p > 0.0f) {
+                float w = grid_weight(bound[j], p, cc, hd);
+                if constexpr (kSeen) w = w * seen_share(tally + (size_t)j * 2u, prior);
+                q = wmax > 0.0f ? max(1u, (uint32_t)((w / wmax) * scale)) : 1u;
+            }
         }
         uint32_t sum = q;
         for (uint32_t off = 1u; off < 64u; off <<= 1) {
@@ -372,6 +407,89 @@ __global__ void __launch_bounds__(256) k_grid_rows(const v4f* __restrict__ bound
         carry += ((s0 + s1) + s2) + s3;
         __syncthreads();   // wave_sum is the next chunk's
     }
+}
+
+__global__ void __launch_bounds__(256) k_grid_rows(const v4f* __restrict__ bound, const float* __restrict__ power, uint32_t n,
+                                                   const rb_probe_grid grid, float scale, uint32_t* __restrict__ tables) {
+    grid_rows<false>(bound, power, n, grid, scale, tables, nullptr, 0.0f);
+}
+__global__ void __launch_bounds__(256) k_grid_rows_seen(const v4f* __restrict__ bound, const float* __restrict__ power, uint32_t n,
+                                                        const rb_probe_grid grid, float scale, uint32_t* __restrict__ tables,
+                                                        const uint32_t* __restrict__ tally, float prior) {
+    grid_rows<true>(bound, power, n, grid, scale, tables, tally, prior);
+}
+
+// ========================================================= k_grid_tally ====
+// The count of section 25, behind the walk: lane = surfel and the items of a surfel at k_direct_fold's places, in both orders.
+// An item whose stored bound is > 0 was valid, picked and lit -- a real shadow ray --, and only such an item is looked at: its
+// pick is made again from the surfel's position (the row, once per lane), the item's first draw and the row's search, which is
+// the generator's own function on the same tables, so (row, j) is the record the ray was aimed at and row * N + j < rows * N
+// whatever the tables hold.  Integer atomics in global memory whose old value nobody reads: the sums are exact in any order.
+// The lanes of a wave are 64 neighbouring surfels of one sample and mostly share a row; how many share a record depends on the
+// table (all 64 with one emitter), and atomics on one address are served one after another (section 25.5: 0.6 G adds/s on two
+// emitters).  kCombine, the form that is launched: per sample the wave groups its counted lanes by record -- the first
+// counted lane's record is broadcast, a ballot finds the lanes that share it, that lane adds the two popcounts, the group
+// leaves the mask -- so a record gets one add per wave and sample, and the loop runs once per distinct record, 64 times at the
+// most.  Every lane of a wave stays in the sample loop (its trip count is the launch's) so that the ballots see whole waves;
+// a lane behind the last surfel counts nothing.  The plain form, one add per item, is kept for the measurement
+// (RB_GRID_TALLY=plain); both give the same sums.
+template <bool kCombine>
+DEV void grid_tally(const LightGenArgs& g, const uint32_t* __restrict__ tables, const rb_probe_grid& grid, const uint8_t* __restrict__ occl,
+                    uint32_t* __restrict__ tally) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u;
+    const bool live = i < g.n;
+    const uint32_t S = g.samples, N = g.n_emit;
+    const size_t row0 = g.linear != 0u ? (size_t)i * S : ((size_t)(i >> 6) * S) * 64u + (i & 63u);
+    const size_t step = g.linear != 0u ? 1u : 64u;
+    f3 pos = mk(0, 0, 0);
+    uint32_t sid = 0u;
+    if (live) {
+        const v4f s0 = reinterpret_cast<const v4f*>(g.surfels)[(size_t)i * 2u];
+        pos = mk(s0.x, s0.y, s0.z);
+        sid = g.ids != nullptr ? g.ids[i] : g.id_base + i;
+    }
+    for (uint32_t s = 0; s < S; s++) {
+        bool counted = false, visible = false;
+        uint32_t key = 0u;   // row * N + j < 2^26
+        if (live) {
+            const size_t t = row0 + (size_t)s * step;
+            if (g.tmax[t] > 0.0f) {
+                uint32_t seed = pcg(sid + pcg(g.first_sample + s));
+                const float u0 = rnd(seed);
+                uint32_t row = 0u, j = 0u;
+                float fn = 0.0f;
+                counted = table_pick<PICK_GRID>(tables, &grid, N, true, pos, u0, row, j, fn);   // (false: tables changed under the call)
+                key = row * N + j;
+                visible = occl[t] == (uint8_t)RB_OCCL_VISIBLE;
+            }
+        }
+        if constexpr (kCombine) {
+            unsigned long long todo = __ballot(counted);
+            while (todo != 0ull) {   // wave-uniform: every lane holds the same mask
+                const int leader = __ffsll(todo) - 1;
+                const uint32_t k = (uint32_t)__shfl((int)key, leader, 64);
+                const bool mine = counted && key == k;
+                const unsigned long long same = __ballot(mine), seen = __ballot(mine && visible);
+                if (lane == (uint32_t)leader) {
+                    atomicAdd(tally + (size_t)k * 2u, (uint32_t)__popcll(same));
+                    if (seen != 0ull) atomicAdd(tally + (size_t)k * 2u + 1u, (uint32_t)__popcll(seen));
+                }
+                todo &= ~same;   // the leader is in `same`: the loop ends
+            }
+        } else if (counted) {
+            atomicAdd(tally + (size_t)key * 2u, 1u);
+            if (visible) atomicAdd(tally + (size_t)key * 2u + 1u, 1u);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) k_grid_tally(const LightGenArgs g, const uint32_t* __restrict__ tables, const rb_probe_grid grid,
+                                                    const uint8_t* __restrict__ occl, uint32_t* __restrict__ tally) {
+    grid_tally<true>(g, tables, grid, occl, tally);
+}
+__global__ void __launch_bounds__(256) k_grid_tally_plain(const LightGenArgs g, const uint32_t* __restrict__ tables, const rb_probe_grid grid,
+                                                          const uint8_t* __restrict__ occl, uint32_t* __restrict__ tally) {
+    grid_tally<false>(g, tables, grid, occl, tally);
 }
 
 // ======================================================= k_direct_fold ====
@@ -455,7 +573,9 @@ size_t emitter_grid_work_bytes(uint32_t n) { return align256(4u * (size_t)n) + 2
 
 // tables[rows * n] of em[n] over `grid` (section 24), queued on `stream`: the powers and the bounds, one lane per record, then
 // one block per cell.  Nothing is waited for.  The caller has checked the grid and rows * n <= RB_MAX_GRID_ENTRIES.
-int launch_emitter_grid(const rb_emitter* em, uint32_t n, const rb_probe_grid& grid, void* work, uint32_t* tables, void* stream_) {
+// `tally`: rows * n records in device memory and a prior the caller has checked -- the learned weight of section 25 (k_grid_rows_seen)
+int launch_emitter_grid(const rb_emitter* em, uint32_t n, const rb_probe_grid& grid, void* work, uint32_t* tables, void* stream_,
+                        const rb_grid_tally* tally, float prior) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (n == 0u) return 0;
     const uint64_t rows = (uint64_t)grid.counts[0] * grid.counts[1] * grid.counts[2];
@@ -473,7 +593,11 @@ int launch_emitter_grid(const rb_emitter* em, uint32_t n, const rb_probe_grid& g
     if (const hipError_t st = hipGetLastError()) return (int)st;
     hipLaunchKernelGGL(k_emit_bound, dim3((n + 255u) / 256u), dim3(256), 0, stream, em, n, bound);
     if (const hipError_t st = hipGetLastError()) return (int)st;
-    hipLaunchKernelGGL(k_grid_rows, dim3((uint32_t)rows), dim3(256), 0, stream, bound, power, n, grid, scale, tables);
+    if (tally != nullptr)
+        hipLaunchKernelGGL(k_grid_rows_seen, dim3((uint32_t)rows), dim3(256), 0, stream, bound, power, n, grid, scale, tables,
+                           reinterpret_cast<const uint32_t*>(tally), prior);
+    else
+        hipLaunchKernelGGL(k_grid_rows, dim3((uint32_t)rows), dim3(256), 0, stream, bound, power, n, grid, scale, tables);
     return (int)hipGetLastError();
 }
 
@@ -535,6 +659,26 @@ int launch_light_rays(const LightGenArgs& g, void* stream_, const uint32_t* cdf,
         hipLaunchKernelGGL(k_light_rays_cdf, grid, dim3(256), 0, static_cast<hipStream_t>(stream_), g, cdf);
     else
         hipLaunchKernelGGL(k_light_rays, grid, dim3(256), 0, static_cast<hipStream_t>(stream_), g);
+    return (int)hipGetLastError();
+}
+
+// The count of one piece behind its walk (section 25): g as the piece's generator had it, `tables` and `cells` its tables and
+// grid, `occl` the walk's bytes beside g.tmax; adds into tally[rows * g.n_emit].  Queued, nothing is waited for.
+int launch_grid_tally(const LightGenArgs& g, const uint32_t* tables, const rb_probe_grid& cells, const uint8_t* occl, rb_grid_tally* tally,
+                      void* stream_) {
+    if (g.n == 0u || g.n_emit == 0u) return 0;
+    if (g.surfels == nullptr || g.tmax == nullptr || tables == nullptr || occl == nullptr || tally == nullptr || g.samples == 0u)
+        return (int)hipErrorInvalidValue;
+    const uint64_t rows = (uint64_t)cells.counts[0] * cells.counts[1] * cells.counts[2];
+    if (g.n_emit > RB_MAX_EMITTERS || rows == 0u || rows * g.n_emit > RB_MAX_GRID_ENTRIES) return (int)hipErrorInvalidValue;
+    if (gen_lanes(g.n, g.samples, g.linear) == 0u) return (int)hipErrorInvalidValue;
+    const char* const form = std::getenv("RB_GRID_TALLY");   // "plain": one add per item, for the measurement of section 25.5
+    if (form != nullptr && std::strcmp(form, "plain") == 0)
+        hipLaunchKernelGGL(k_grid_tally_plain, dim3((g.n + 255u) / 256u), dim3(256), 0, static_cast<hipStream_t>(stream_), g, tables, cells, occl,
+                           reinterpret_cast<uint32_t*>(tally));
+    else
+        hipLaunchKernelGGL(k_grid_tally, dim3((g.n + 255u) / 256u), dim3(256), 0, static_cast<hipStream_t>(stream_), g, tables, cells, occl,
+                           reinterpret_cast<uint32_t*>(tally));
     return (int)hipGetLastError();
 }
 

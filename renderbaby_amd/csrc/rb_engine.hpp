@@ -208,6 +208,8 @@ struct rb_engine {
     // -- made for it, or a caller's as the host form stages them -- and the build's scratch.  The engine keeps no grid.
     rb::DevBuf<uint32_t> emit_grid_tables;
     rb::DevBuf<unsigned char> emit_grid_work;
+    // the host form's tally of rb_direct_light_grid_tally between its upload and its download (section 25); the engine keeps none
+    rb::DevBuf<rb_grid_tally> emit_grid_tally;
     // lightmap texels made on the device (rb_lightmap_surfels_device / rb_bake_lightmap*): the triangles
     // prepared in triangle order, the cover pass's scratch, and what a bake keeps between its stages
     rb::DevBuf<rb::PrepTri> lm_ptris;

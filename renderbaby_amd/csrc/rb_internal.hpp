@@ -497,7 +497,12 @@ size_t emitter_cdf_work_bytes(uint32_t n);
 int launch_emitter_cdf(const rb_emitter* em, uint32_t n, void* work, uint32_t* cdf, void* stream);
 // the tables per cell of em[n] over `grid` into tables[rows * n], over `work` (emitter_grid_work_bytes); queued, no wait
 size_t emitter_grid_work_bytes(uint32_t n);
-int launch_emitter_grid(const rb_emitter* em, uint32_t n, const rb_probe_grid& grid, void* work, uint32_t* tables, void* stream);
+// ... with `tally` (rows * n records, device memory) and `prior`: the learned weight (k_grid_rows_seen)
+int launch_emitter_grid(const rb_emitter* em, uint32_t n, const rb_probe_grid& grid, void* work, uint32_t* tables, void* stream,
+                        const rb_grid_tally* tally = nullptr, float prior = 0.0f);
+// the count of one piece of a grid call behind its walk, added into tally[rows * g.n_emit] (k_grid_tally)
+int launch_grid_tally(const LightGenArgs& g, const uint32_t* tables, const rb_probe_grid& cells, const uint8_t* occl, rb_grid_tally* tally,
+                      void* stream);
 int launch_direct_fold(const uint8_t* occl, const float* contrib, uint32_t n, uint32_t samples, uint32_t linear, rb_radiance* out, void* stream);
 // ---- rb_probe.hip: irradiance probes made on the device.  One launch of k_probe_rays writes the records
 // of one piece of whole probes, in k_cam_rays' format and k_hemi_rays' two orders; k_sh_project folds the colours launch_radiance

@@ -253,7 +253,8 @@ FamilyArray family_array(const void* caller, rb::DevBuf<T>& stage, const char* s
 // The runner of the families of "n > 0 items, `samples` samples each": pieces of whole blocks of 64 items and at most `limit`
 // (item, sample) pairs.  `ins`: up to two input arrays, `out`: the result array.  `scratch(piece)` reserves what a piece needs
 // beside them and returns an rb code; `piece_fn(p, in, out, done, m, li)` queues items [done, done + m) of the call, whose
-// arrays begin at in[0], in[1] (nullptr: left out) and out in device memory, and returns a HIP status.
+// arrays begin at in[0], in[1] (nullptr: left out) and out (nullptr: the caller left the result out) in device memory, and
+// returns a HIP status.
 // Device form: the caller's buffers are checked, then every piece is queued on them between the query's two events (the pieces
 // share the scratch in stream order); nothing is waited for.  Host form: run_pieces over the staging buffers.
 template <class Scratch, class Piece>
@@ -265,12 +266,13 @@ int run_family(rb_engine* e, bool device, const char* kind, size_t limit, size_t
         for (const FamilyArray& a : ins)
             if (a.caller)
                 if (const int rc = device_range(e, a.caller, n * a.stride, a.align, a.name)) return rc;
-        if (const int rc = device_range(e, out.caller, n * out.stride, out.align, out.name)) return rc;
+        if (out.caller)   // (left out: a family that allows it has said so before it came here)
+            if (const int rc = device_range(e, out.caller, n * out.stride, out.align, out.name)) return rc;
         return device_query_locked(e, [&](const rb::KParams& p, rb::LaunchInfo* li) {
             if (scratch(piece)) return static_cast<int>(hipErrorOutOfMemory);
             return for_pieces(n, piece, [&](size_t done, size_t m) {
                 for (int k = 0; k < 2; k++) in[k] = ins[k].caller ? static_cast<const char*>(ins[k].caller) + done * ins[k].stride : nullptr;
-                return piece_fn(p, in, static_cast<char*>(const_cast<void*>(out.caller)) + done * out.stride, done, m, li);
+                return piece_fn(p, in, out.caller ? static_cast<char*>(const_cast<void*>(out.caller)) + done * out.stride : nullptr, done, m, li);
             });
         });
     }
@@ -291,7 +293,7 @@ int run_family(rb_engine* e, bool device, const char* kind, size_t limit, size_t
         staged[k] = PieceIn{ins[k].caller, ptr, ins[k].stride};
         in[k] = ptr;
     }
-    if ((rc = reserve(out, &d_out)) != RB_OK) return rc;
+    if (out.caller && (rc = reserve(out, &d_out)) != RB_OK) return rc;
     return run_pieces(e, kind, piece, n, {staged[0], staged[1]}, {{const_cast<void*>(out.caller), d_out, out.stride}},
                       [&](size_t done, size_t m, rb::LaunchInfo* li) { return piece_fn(p, in, d_out, done, m, li); });
 }
@@ -533,6 +535,7 @@ struct DirectCall {
     uint32_t n_emit;
     const uint32_t* cdf = nullptr;   // the pick weights of rb_direct_light_cdf, n_emit of them; nullptr: the uniform pick
     const rb_probe_grid* grid = nullptr;   // rb_direct_light_grid: `cdf` holds one table of n_emit per cell of this grid (section 24)
+    rb_grid_tally* tally = nullptr;        // rb_direct_light_grid_tally: rows * n_emit records in device memory, added to (section 25)
 };
 
 rb::LightGenArgs light_gen_args(const DirectCall& c, const rb_surfel* surfels, const uint32_t* ids, rb_ray* recs, float* tmax, float* contrib,
@@ -572,7 +575,8 @@ int direct_scratch(rb_engine* e, size_t piece, uint32_t samples) {
 
 // one piece, queued: surfels [done, done + m) of the call, at `surfels` / `ids` in device memory, into out[m], as hemi_piece's
 // openness branch has it but in item order (direct_linear: linear order): the generator, the k_occl kernel of the scene's walk
-// over every record of the piece's blocks, the fold
+// over every record of the piece's blocks, the count of a tallied call (section 25), the fold (out == nullptr: a training-only
+// call, none)
 int direct_piece(rb_engine* e, const rb::KParams& p, const DirectCall& c, const rb_surfel* surfels, const uint32_t* ids, size_t done, size_t m,
                  rb_radiance* out, rb::LaunchInfo* li) {
     rb::LightGenArgs g = light_gen_args(c, surfels, ids, e->q_rays.ptr, e->q_tmax.ptr, e->rad_colors.ptr, done, m);
@@ -585,6 +589,9 @@ int direct_piece(rb_engine* e, const rb::KParams& p, const DirectCall& c, const 
     a.out = e->q_occl.ptr;
     a.mask = c.prm.mask;
     if (const int st = rb::launch_occluded(p, a, e->stream, li)) return st;
+    if (c.tally && c.cdf && c.grid)
+        if (const int st = rb::launch_grid_tally(g, c.cdf, *c.grid, e->q_occl.ptr, c.tally, e->stream)) return st;
+    if (!out) return 0;
     return rb::launch_direct_fold(e->q_occl.ptr, e->rad_colors.ptr, static_cast<uint32_t>(m), c.samples, g.linear, out, e->stream);
 }
 
@@ -644,9 +651,11 @@ int direct_light_locked(rb_engine* e, bool device, bool weighted, const rb_emitt
 size_t grid_cells(const rb_probe_grid& g) { return static_cast<size_t>(g.counts[0]) * g.counts[1] * g.counts[2]; }
 
 // the tables of the n records at d_em over `grid` into d_tables, over the engine's scratch; queued, nothing waits
-int queue_emitter_grid(rb_engine* e, const rb_emitter* d_em, uint32_t n, const rb_probe_grid& grid, uint32_t* d_tables) {
+// (d_tally: the learned weight of section 25 with `prior`)
+int queue_emitter_grid(rb_engine* e, const rb_emitter* d_em, uint32_t n, const rb_probe_grid& grid, uint32_t* d_tables,
+                       const rb_grid_tally* d_tally = nullptr, float prior = 0.0f) {
     HIP_TRY(e, e->emit_grid_work.reserve(rb::emitter_grid_work_bytes(n)));
-    const int st = rb::launch_emitter_grid(d_em, n, grid, e->emit_grid_work.ptr, d_tables, e->stream);
+    const int st = rb::launch_emitter_grid(d_em, n, grid, e->emit_grid_work.ptr, d_tables, e->stream, d_tally, prior);
     if (st) return rb::fail(e, RB_ERR_DEVICE, "grid table launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
     return RB_OK;
 }
@@ -662,34 +671,41 @@ int scene_emitters_counted(rb_engine* e, size_t n_emit) {
     return RB_OK;
 }
 
-// rb_emitter_grid_cdf_device: the caller's buffers, the scene's table where it is asked for -- outside the events --, the build
-int emitter_grid_device_locked(rb_engine* e, const rb_emitter* d_emitters, size_t n_emit, const rb_probe_grid& grid, uint32_t* d_tables) {
+// rb_emitter_grid_cdf_device: the caller's buffers, the scene's table where it is asked for -- outside the events --, the build;
+// `learned`: rb_emitter_grid_learned_device, with the caller's tally and prior
+int emitter_grid_device_locked(rb_engine* e, const rb_emitter* d_emitters, size_t n_emit, const rb_probe_grid& grid, uint32_t* d_tables,
+                               bool learned = false, const rb_grid_tally* d_tally = nullptr, float prior = 0.0f) {
     int rc = n_emit > 0 ? device_range(e, d_tables, grid_cells(grid) * n_emit * sizeof(uint32_t), 4, "d_tables_out") : RB_OK;
+    if (!rc && learned && n_emit > 0) rc = device_range(e, d_tally, grid_cells(grid) * n_emit * sizeof(rb_grid_tally), 4, "d_tally");
     if (!rc && d_emitters && n_emit > 0) rc = device_range(e, d_emitters, n_emit * sizeof(rb_emitter), 16, "d_emitters");
     if (!rc) rc = d_emitters ? query_prologue(e, nullptr) : scene_emitters_counted(e, n_emit);
     if (rc) return rc;
-    e->last_query_kernel_name = "k_grid_rows";
+    e->last_query_kernel_name = learned ? "k_grid_rows_seen" : "k_grid_rows";
     if (n_emit == 0) return RB_OK;
     HIP_TRY(e, e->t_query.begin(e->stream));
-    if ((rc = queue_emitter_grid(e, d_emitters ? d_emitters : e->emit_table.ptr, static_cast<uint32_t>(n_emit), grid, d_tables))) return rc;
+    if ((rc = queue_emitter_grid(e, d_emitters ? d_emitters : e->emit_table.ptr, static_cast<uint32_t>(n_emit), grid, d_tables,
+                                 learned ? d_tally : nullptr, prior)))
+        return rc;
     HIP_TRY(e, e->t_query.end(e->stream));
     return RB_OK;
 }
 
 // rb_direct_light_grid in both forms: direct_light_locked with one table per cell, the caller's or made for this call; the
-// pieces share them
+// pieces share them.  `tally`: rb_direct_light_grid_tally -- the caller's records, in device memory as they are, from host memory
+// uploaded once, added to by every piece and downloaded at the end; `out` may then be nullptr
 int direct_light_grid_locked(rb_engine* e, bool device, const rb_emitter* emitters, const rb_probe_grid& grid, const uint32_t* tables,
                              size_t n_emit, const rb_surfel* surfels, const uint32_t* seeds, size_t n, const rb_light_params& prm,
-                             uint32_t first_sample, uint32_t samples, rb_radiance* out) {
+                             uint32_t first_sample, uint32_t samples, rb_radiance* out, rb_grid_tally* tally = nullptr) {
     DirectCall c{prm, first_sample, samples, emitters, static_cast<uint32_t>(n_emit)};
     c.grid = &grid;
     const size_t entries = grid_cells(grid) * n_emit;
     if (device) {   // every buffer of the caller's before anything is queued or a table is made: a refused call has done nothing
         int rc = device_range(e, surfels, n * sizeof(rb_surfel), 16, "d_surfels");
         if (!rc && seeds) rc = device_range(e, seeds, n * sizeof(uint32_t), 4, "d_seeds");
-        if (!rc) rc = device_range(e, out, n * sizeof(rb_radiance), 16, "d_out");
+        if (!rc && (out || !tally)) rc = device_range(e, out, n * sizeof(rb_radiance), 16, "d_out");
         if (!rc && emitters && n_emit > 0) rc = device_range(e, emitters, n_emit * sizeof(rb_emitter), 16, "d_emitters");
         if (!rc && tables && entries > 0) rc = device_range(e, tables, entries * sizeof(uint32_t), 4, "d_tables");
+        if (!rc && tally && entries > 0) rc = device_range(e, tally, entries * sizeof(rb_grid_tally), 4, "d_tally");
         if (rc) return rc;
     }
     if (!emitters) {   // the scene's own table
@@ -713,13 +729,24 @@ int direct_light_grid_locked(rb_engine* e, bool device, const rb_emitter* emitte
             c.cdf = e->emit_grid_tables.ptr;
         }
     }
-    return run_family(e, device, "direct light", RB_HEMI_PIECE_ITEMS, n, samples,
-                      {FAMILY_ARRAY(surfels, e->hemi_surfels, 16, "d_surfels"), FAMILY_ARRAY(seeds, e->rad_seeds, 4, "d_seeds")},
-                      FAMILY_ARRAY(out, e->rad_out, 16, "d_out"), [&](size_t piece) { return direct_scratch(e, piece, samples); },
-                      [&](const rb::KParams& p, const void* const* in, void* o, size_t done, size_t m, rb::LaunchInfo* li) {
-                          return direct_piece(e, p, c, static_cast<const rb_surfel*>(in[0]), static_cast<const uint32_t*>(in[1]), done, m,
-                                              static_cast<rb_radiance*>(o), li);
-                      });
+    const bool staged_tally = tally && !device && entries > 0;
+    if (tally && entries > 0) c.tally = tally;
+    if (staged_tally) {
+        HIP_TRY(e, e->emit_grid_tally.reserve(entries));
+        HIP_TRY(e, hipMemcpyAsync(e->emit_grid_tally.ptr, tally, entries * sizeof(rb_grid_tally), hipMemcpyHostToDevice, e->stream));
+        c.tally = e->emit_grid_tally.ptr;
+    }
+    const int rc = run_family(e, device, "direct light", RB_HEMI_PIECE_ITEMS, n, samples,
+                              {FAMILY_ARRAY(surfels, e->hemi_surfels, 16, "d_surfels"), FAMILY_ARRAY(seeds, e->rad_seeds, 4, "d_seeds")},
+                              FAMILY_ARRAY(out, e->rad_out, 16, "d_out"), [&](size_t piece) { return direct_scratch(e, piece, samples); },
+                              [&](const rb::KParams& p, const void* const* in, void* o, size_t done, size_t m, rb::LaunchInfo* li) {
+                                  return direct_piece(e, p, c, static_cast<const rb_surfel*>(in[0]), static_cast<const uint32_t*>(in[1]), done,
+                                                      m, static_cast<rb_radiance*>(o), li);
+                              });
+    if (rc || !staged_tally) return rc;
+    if (const int st = query_copy_out(e, tally, e->emit_grid_tally.ptr, entries * sizeof(rb_grid_tally), page_locked(tally))) return st;
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    return RB_OK;
 }
 
 // ---- irradiance probes made on the device (rb_abi.h)
@@ -960,6 +987,13 @@ int emitter_grid_check(rb_engine* e, const char* who, const rb_probe_grid* g, si
     return RB_OK;
 }
 
+// the prior of section 25: finite, 0 < a <= 2^24
+int prior_check(rb_engine* e, const char* who, float prior) {
+    if (!(std::isfinite(prior) && prior > 0.0f && prior <= 16777216.0f))
+        return rb::fail(e, RB_ERR_INVALID_OPTIONS, "%s: the prior must be finite, above 0 and at most 16777216", who);
+    return RB_OK;
+}
+
 // tables in host memory: every row a table in cdf_check's sense
 int grid_tables_check(rb_engine* e, const char* who, const rb_probe_grid& g, const uint32_t* tables, size_t n_emit) {
     for (size_t r = 0, rows = grid_cells(g); r < rows && n_emit > 0; r++)
@@ -1142,21 +1176,26 @@ int direct_light_entry(rb_engine* e, const char* who, bool device, bool weighted
         });
 }
 
-// the two engine entry points of rb_direct_light_grid; tables in host memory are looked at here
+// the two engine entry points of rb_direct_light_grid; tables in host memory are looked at here.  `tallied`: those of
+// rb_direct_light_grid_tally, which need a tally and may leave out `out`
 int direct_light_grid_entry(rb_engine* e, const char* who, bool device, const rb_emitter* emitters, const rb_probe_grid* grid,
                             const uint32_t* tables, size_t n_emit, const rb_surfel* surfels, const uint32_t* seeds, size_t n,
-                            const rb_light_params* prm, uint32_t first_sample, uint32_t samples, rb_radiance* out) {
+                            const rb_light_params* prm, uint32_t first_sample, uint32_t samples, rb_radiance* out, bool tallied = false,
+                            rb_grid_tally* tally = nullptr) {
     return engine_entry(
         e, n,
         [&] {
-            if (n > 0 && (!surfels || !prm || !out)) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "%s: surfels / params / out is NULL", who);
+            if (tallied && !tally) return rb::fail(e, RB_ERR_NULL_ARGUMENT, "%s: tally is NULL", who);
+            if (n > 0 && (!surfels || !prm || (!out && !tallied)))
+                return rb::fail(e, RB_ERR_NULL_ARGUMENT, "%s: surfels / params / out is NULL", who);
             if (prm)
                 if (const int rc = light_check(e, who, prm, n_emit, n, first_sample, samples, true)) return rc;
             if (const int rc = emitter_grid_check(e, who, grid, n_emit)) return rc;
             return (tables && !device) ? grid_tables_check(e, who, *grid, tables, n_emit) : RB_OK;
         },
         [&](rb_engine* t) {
-            return direct_light_grid_locked(t, device, emitters, *grid, tables, n_emit, surfels, seeds, n, *prm, first_sample, samples, out);
+            return direct_light_grid_locked(t, device, emitters, *grid, tables, n_emit, surfels, seeds, n, *prm, first_sample, samples, out,
+                                            tally);
         });
 }
 
@@ -1401,6 +1440,35 @@ int light_rays_entry(const char* who, int32_t device, bool weighted, const rb_em
     }
     return s.finish(who);
 }
+// rb_emitter_grid_cdf, and (`learned`) rb_emitter_grid_learned with the caller's tally and prior
+int emitter_grid_host(const char* who, int32_t device, const rb_emitter* emitters, size_t n_emit, const rb_probe_grid* grid, bool learned,
+                      const rb_grid_tally* tally, float prior, uint32_t* tables_out) {
+    if (!grid || (n_emit > 0 && (!emitters || !tables_out || (learned && !tally))))
+        return rb::fail(nullptr, RB_ERR_NULL_ARGUMENT, "%s: grid / emitters / tally / tables_out is NULL", who);
+    if (const int rc = emitter_grid_check(nullptr, who, grid, n_emit)) return rc;
+    if (learned)
+        if (const int rc = prior_check(nullptr, who, prior)) return rc;
+    if (n_emit == 0) return RB_OK;
+    const size_t entries = grid_cells(*grid) * n_emit;
+    rb::DevBuf<rb_emitter> d_emit;
+    rb::DevBuf<uint32_t> d_tables;
+    rb::DevBuf<rb_grid_tally> d_tally;
+    rb::DevBuf<unsigned char> d_work;
+    DeviceScope s(device);
+    s.alloc(d_emit, n_emit);
+    s.alloc(d_tables, entries);
+    if (learned) s.alloc(d_tally, entries);
+    s.alloc(d_work, rb::emitter_grid_work_bytes(static_cast<uint32_t>(n_emit)));
+    s.upload(d_emit.ptr, emitters, n_emit * sizeof(rb_emitter));
+    if (learned) s.upload(d_tally.ptr, tally, entries * sizeof(rb_grid_tally));
+    s.run([&] {
+        return rb::launch_emitter_grid(d_emit.ptr, static_cast<uint32_t>(n_emit), *grid, d_work.ptr, d_tables.ptr, s.stream,
+                                       learned ? d_tally.ptr : nullptr, prior);
+    });
+    s.download(tables_out, d_tables.ptr, entries * sizeof(uint32_t));
+    return s.finish(who);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1671,22 +1739,25 @@ int rb_direct_light_cdf_device(rb_engine* e, const rb_emitter* d_emitters, const
 }
 
 int rb_emitter_grid_cdf(int32_t device, const rb_emitter* emitters, size_t n_emit, const rb_probe_grid* grid, uint32_t* tables_out) {
-    if (!grid || (n_emit > 0 && (!emitters || !tables_out)))
-        return rb::fail(nullptr, RB_ERR_NULL_ARGUMENT, "rb_emitter_grid_cdf: grid / emitters / tables_out is NULL");
-    if (const int rc = emitter_grid_check(nullptr, "rb_emitter_grid_cdf", grid, n_emit)) return rc;
-    if (n_emit == 0) return RB_OK;
-    const size_t entries = grid_cells(*grid) * n_emit;
-    rb::DevBuf<rb_emitter> d_emit;
-    rb::DevBuf<uint32_t> d_tables;
-    rb::DevBuf<unsigned char> d_work;
-    DeviceScope s(device);
-    s.alloc(d_emit, n_emit);
-    s.alloc(d_tables, entries);
-    s.alloc(d_work, rb::emitter_grid_work_bytes(static_cast<uint32_t>(n_emit)));
-    s.upload(d_emit.ptr, emitters, n_emit * sizeof(rb_emitter));
-    s.run([&] { return rb::launch_emitter_grid(d_emit.ptr, static_cast<uint32_t>(n_emit), *grid, d_work.ptr, d_tables.ptr, s.stream); });
-    s.download(tables_out, d_tables.ptr, entries * sizeof(uint32_t));
-    return s.finish("rb_emitter_grid_cdf");
+    return emitter_grid_host("rb_emitter_grid_cdf", device, emitters, n_emit, grid, false, nullptr, 0.0f, tables_out);
+}
+
+int rb_emitter_grid_learned(int32_t device, const rb_emitter* emitters, size_t n_emit, const rb_probe_grid* grid, const rb_grid_tally* tally,
+                            float prior, uint32_t* tables_out) {
+    return emitter_grid_host("rb_emitter_grid_learned", device, emitters, n_emit, grid, true, tally, prior, tables_out);
+}
+
+int rb_emitter_grid_learned_device(rb_engine* e, const rb_emitter* d_emitters, size_t n_emit, const rb_probe_grid* grid,
+                                   const rb_grid_tally* d_tally, float prior, uint32_t* d_tables_out) {
+    return engine_entry(
+        e,
+        [&]() -> int {
+            if (!grid || (n_emit > 0 && (!d_tables_out || !d_tally)))
+                return rb::fail(e, RB_ERR_NULL_ARGUMENT, "rb_emitter_grid_learned_device: grid / d_tally / d_tables_out is NULL");
+            if (const int rc = emitter_grid_check(e, "rb_emitter_grid_learned_device", grid, n_emit)) return rc;
+            return prior_check(e, "rb_emitter_grid_learned_device", prior);
+        },
+        [&](rb_engine* t) { return emitter_grid_device_locked(t, d_emitters, n_emit, *grid, d_tables_out, true, d_tally, prior); });
 }
 
 int rb_emitter_grid_cdf_device(rb_engine* e, const rb_emitter* d_emitters, size_t n_emit, const rb_probe_grid* grid, uint32_t* d_tables_out) {
@@ -1718,6 +1789,21 @@ int rb_direct_light_grid_device(rb_engine* e, const rb_emitter* d_emitters, cons
                                 uint32_t first_sample, uint32_t samples, rb_radiance* d_out) {
     return direct_light_grid_entry(e, "rb_direct_light_grid_device", true, d_emitters, grid, d_tables, n_emit, d_surfels, d_seeds, n, params,
                                    first_sample, samples, d_out);
+}
+
+int rb_direct_light_grid_tally(rb_engine* e, const rb_emitter* emitters, const rb_probe_grid* grid, const uint32_t* tables, size_t n_emit,
+                               const rb_surfel* surfels, const uint32_t* seeds, size_t n, const rb_light_params* params,
+                               uint32_t first_sample, uint32_t samples, rb_radiance* out, rb_grid_tally* tally) {
+    return direct_light_grid_entry(e, "rb_direct_light_grid_tally", false, emitters, grid, tables, n_emit, surfels, seeds, n, params,
+                                   first_sample, samples, out, true, tally);
+}
+
+int rb_direct_light_grid_tally_device(rb_engine* e, const rb_emitter* d_emitters, const rb_probe_grid* grid, const uint32_t* d_tables,
+                                      size_t n_emit, const rb_surfel* d_surfels, const uint32_t* d_seeds, size_t n,
+                                      const rb_light_params* params, uint32_t first_sample, uint32_t samples, rb_radiance* d_out,
+                                      rb_grid_tally* d_tally) {
+    return direct_light_grid_entry(e, "rb_direct_light_grid_tally_device", true, d_emitters, grid, d_tables, n_emit, d_surfels, d_seeds, n,
+                                   params, first_sample, samples, d_out, true, d_tally);
 }
 
 int rb_probe_rays(int32_t device, const rb_probe* probes, const uint32_t* seeds, size_t n, uint32_t first_sample, uint32_t samples,

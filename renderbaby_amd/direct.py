@@ -12,6 +12,9 @@ of ``rb_direct_light`` bit for bit.
 ``emitter_bounds``, ``grid_weights``, ``emitter_grid_cdf``, ``grid_cell``  the pick per grid cell (section 24): a sphere about
                     every record, its weight in every cell, the tables ``rb_emitter_grid_cdf`` makes -- one row per cell --, and
                     the row a surfel's position searches
+``count``, ``tally``, ``seen_share``  the tables that learn visibility (section 25): the count of shadow rays tried and seen per
+                    (cell, emitter) given the result bytes, and the factor a tally puts on a weight; ``grid_weights`` and
+                    ``emitter_grid_cdf`` take a tally and a prior
 ``barycentrics``, ``points``  the point an item's second and third draws make on its emitter, and the emitter's normal there
 ``rays``          (origins, directions, bounds, contributions) of the items: what ``rb_light_rays`` returns -- with ``cdf``,
                     what ``rb_light_rays_cdf`` returns; with ``grid``, what ``rb_light_rays_grid`` returns
@@ -219,8 +222,26 @@ def grid_centres(grid):
         return (org[None, :] + ((idx.astype(f32) + f32(0.5)).astype(f32) * step[None, :]).astype(f32)).astype(f32)
 
 
-def grid_weights(em, grid):
-    """w (rows, n) float32 of section 24: p_j / max(d2, (re + hd)^2), at most 3.4028235e38, and 0 where p_j is 0; never a NaN"""
+def _prior(prior):
+    a = f32(prior)
+    if not (np.isfinite(a) and 0 < a <= f32(abi.MAX_PRIOR)):
+        raise ValueError("prior: finite, above 0 and at most 16777216")
+    return a
+
+
+def seen_share(tally, prior):
+    """f float32 of every abi.GRID_TALLY record (section 25): t = tried, s = min(seen, tried), f = (float(s) + a) / (float(t) + a);
+    in [0, 1] and never a NaN for a finite prior a with 0 < a <= 16777216"""
+    t = np.asarray(tally, dtype=abi.GRID_TALLY)
+    a = _prior(prior)
+    s = np.minimum(t["seen"], t["tried"])
+    with np.errstate(all="ignore"):
+        return ((s.astype(f32) + a).astype(f32) / (t["tried"].astype(f32) + a).astype(f32)).astype(f32)
+
+
+def grid_weights(em, grid, tally=None, prior=None):
+    """w (rows, n) float32 of section 24: p_j / max(d2, (re + hd)^2), at most 3.4028235e38, and 0 where p_j is 0; never a NaN.
+    ``tally`` (abi.GRID_TALLY[rows * n]) and ``prior``: w' = w f of section 25, f by ``seen_share``; None: section 24 untouched"""
     p = emitter_weights(em)
     ce, re = emitter_bounds(em)
     _, step, _, rows = _grid(grid)
@@ -234,13 +255,20 @@ def grid_weights(em, grid):
         fl = np.broadcast_to((r0 * r0).astype(f32)[None, :], d2.shape)
         x = (p[None, :] / _gt(d2, fl)).astype(f32)
         w = np.where(x < MAX_WEIGHT, x, MAX_WEIGHT).astype(f32)
-    return np.where(p[None, :] > 0, w, f32(0)).astype(f32).reshape(rows, len(p))
+    w = np.where(p[None, :] > 0, w, f32(0)).astype(f32).reshape(rows, len(p))
+    if tally is None:
+        return w
+    t = np.asarray(tally, dtype=abi.GRID_TALLY).reshape(-1)
+    if len(t) != rows * len(p):
+        raise ValueError("tally: one record per cell and emitter is needed")
+    with np.errstate(all="ignore"):
+        return (w * seen_share(t, prior).reshape(rows, len(p))).astype(f32)
 
 
-def emitter_grid_cdf(em, grid):
+def emitter_grid_cdf(em, grid, tally=None, prior=1.0):
     """uint32[rows * n], the tables of section 24, row r at [r n, (r + 1) n): q = max(1, uint((w / wmax_r) float(S))) for
     p_j > 0 -- 1 where the row's largest weight is 0 --, else 0, summed inclusively along the row.  What rb_emitter_grid_cdf
-    returns."""
+    returns.  ``tally``: the learned tables of section 25 -- the same with w' = w f, what rb_emitter_grid_learned returns."""
     p = emitter_weights(em)
     n = len(p)
     rows = _grid(grid)[3]
@@ -248,7 +276,7 @@ def emitter_grid_cdf(em, grid):
         raise ValueError("at most 2^24 emitters and 2^26 entries are taken")
     if n == 0:
         return np.zeros(0, u32)
-    w = grid_weights(em, grid)
+    w = grid_weights(em, grid) if tally is None else grid_weights(em, grid, tally, prior)
     wmax = w.max(axis=1)[:, None]
     with np.errstate(all="ignore"):
         r = ((w / wmax).astype(f32) * f32(cdf_scale(n))).astype(f32)
@@ -281,6 +309,46 @@ def pick_grid(u0, rows, tables, n_emit):
         sel = rows == r
         j[sel], q[sel], Q[sel] = pick_cdf(u0[sel], tables[r])
     return j, q, Q
+
+
+def count(entries, index, bound, occl, into=None):
+    """abi.GRID_TALLY[entries], the count of section 25 over items whose record is ``index`` (row n + j), whose stored bound is
+    ``bound`` and whose result byte is ``occl``: an item with bound > 0 adds 1 to ``tried`` of its record, and 1 to ``seen`` if
+    its byte is abi.OCCL_VISIBLE; any other item counts nothing.  uint32 sums that wrap, on top of ``into`` (not changed)."""
+    out = np.zeros(entries, dtype=abi.GRID_TALLY) if into is None else np.array(into, dtype=abi.GRID_TALLY).reshape(-1)
+    if len(out) != entries:
+        raise ValueError("into: one record per cell and emitter is needed")
+    index = np.asarray(index, np.int64).reshape(-1)
+    counted = np.asarray(bound, f32).reshape(-1) > 0
+    vis = np.asarray(occl, np.uint8).reshape(-1) == abi.OCCL_VISIBLE
+    if not (len(index) == len(counted) == len(vis)):
+        raise ValueError("index, bound, occl: one entry per item is needed")
+    if entries == 0:
+        return out
+    tried = np.bincount(index[counted], minlength=entries).astype(u64)
+    seen = np.bincount(index[counted & vis], minlength=entries).astype(u64)
+    out["tried"] = ((out["tried"].astype(u64) + tried) & u64(0xFFFFFFFF)).astype(u32)
+    out["seen"] = ((out["seen"].astype(u64) + seen) & u64(0xFFFFFFFF)).astype(u32)
+    return out
+
+
+def tally(emitters, surf, first_sample, samples, grid, occl, tables=None, seeds=None, offset=1e-3, shorten=1e-3, into=None):
+    """abi.GRID_TALLY[rows * n] after a call of rb_direct_light_grid_tally whose shadow rays -- ``rays(grid=grid, tables=tables)``,
+    surfel-major -- got the bytes ``occl`` from rb_occluded, on top of ``into`` (None: zeros): every item's row and pick as the
+    generator has them, counted by ``count``"""
+    em = np.asarray(emitters, dtype=abi.EMITTER).reshape(-1)
+    surf = np.asarray(surf, dtype=abi.SURFEL).reshape(-1)
+    n_emit, rows = len(em), _grid(grid)[3]
+    if n_emit == 0 or len(surf) == 0:
+        return count(rows * n_emit, np.zeros(0, np.int64), np.zeros(0, f32), np.zeros(0, np.uint8), into)
+    tables = emitter_grid_cdf(em, grid) if tables is None else np.asarray(tables, u32).reshape(-1)
+    bound = rays(em, surf, first_sample, samples, seeds, offset, shorten, grid=grid, tables=tables)[2]
+    dr = draws(len(surf), first_sample, samples, seeds)
+    pos = surf["pos"].astype(f32)
+    fin = np.isfinite(pos).all(1)
+    row = grid_cell(np.where(fin[:, None], pos, f32(0)), grid)[dr["surfel"]]
+    j = pick_grid(dr["u0"], np.where(bound > 0, row, -1), tables, n_emit)[0]
+    return count(rows * n_emit, row * n_emit + j, bound, occl, into)
 
 
 def barycentrics(u1, u2):

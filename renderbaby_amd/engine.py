@@ -634,14 +634,30 @@ class Engine:
         self._check(self._lib.rb_scene_emitter_cdf(self._h, host_ptr(table), len(table), C.byref(count)))
         return table
 
-    def emitter_grid(self, grid, emitters=None, out=None):
+    def _tally_in(self, f, tally, entries):
+        """(what the call takes, pointer, the caller's numpy array to copy back into or None) of a tally argument: abi.GRID_TALLY
+        records in host memory, or an (entries, 2) int32 tensor on the engine's device; a numpy array beside tensors is staged"""
+        if is_tensor(tally) or not f.on_device:
+            if not is_tensor(tally) and not (isinstance(tally, np.ndarray) and tally.dtype == abi.GRID_TALLY and tally.flags.c_contiguous
+                                             and tally.flags.writeable):
+                raise ValueError("tally: a writable contiguous abi.GRID_TALLY array (it is added to in place) or a tensor is needed")
+            t, p = f.input("tally", tally, abi.GRID_TALLY, entries)
+            return t, p, None
+        back = tally if isinstance(tally, np.ndarray) and tally.dtype == abi.GRID_TALLY else None
+        t, p = f.input("tally", upload(host_in("tally", tally, abi.GRID_TALLY, entries)[0], abi.GRID_TALLY, self.query_device),
+                       abi.GRID_TALLY, entries)
+        return t, p, back
+
+    def emitter_grid(self, grid, emitters=None, tally=None, prior=1.0, out=None):
         """rb_emitter_grid_cdf_device: the pick tables per grid cell (``direct.emitter_grid_cdf`` is the
         model) of an abi.PROBE_GRID whose counts count cells -- uint32[rows * n], row r at [r n, (r + 1) n).  ``emitters``: None
         for the scene's own table, or an abi.EMITTER table of the caller's.  Host arrays in, a numpy array out; a tensor for
         ``emitters`` or ``out`` (int32 / uint32, rows * n entries) keeps everything on the engine's device and the tensor comes
-        back: ``direct_light(pick=("grid", grid, tables))`` takes it as it is.  The engine keeps no grid."""
+        back: ``direct_light(pick=("grid", grid, tables))`` takes it as it is.  The engine keeps no grid.
+        ``tally``: rb_emitter_grid_learned_device, the tables that learn visibility -- the abi.GRID_TALLY
+        records ``direct_light(tally=...)`` keeps (an array, or an (rows * n, 2) int32 tensor) and a ``prior`` in (0, 16777216]."""
         g, rows = grid_records(grid)
-        f = Form(self.query_device, emitters, out, staged=True)
+        f = Form(self.query_device, emitters, out, tally, staged=True)
         tp, n_emit = None, len(self.scene_emitters())
         if emitters is not None:
             table, tp = f.input("emitters", emitters, abi.EMITTER)
@@ -651,6 +667,10 @@ class Engine:
         if out is None:
             out = device_new(np.int32, rows * n_emit, self.query_device)
         res, op = f.output("out", out, CDF, rows * n_emit)
+        if tally is not None:
+            kept, kp = f.input("tally", tally, abi.GRID_TALLY, rows * n_emit)
+            self._device_call(self._lib.rb_emitter_grid_learned_device, tp, n_emit, g.ctypes.data, kp, float(prior), op)
+            return f.result(res, CDF)
         self._device_call(self._lib.rb_emitter_grid_cdf_device, tp, n_emit, g.ctypes.data, op)
         return f.result(res, CDF)
 
@@ -661,7 +681,7 @@ class Engine:
         return prm
 
     def direct_light(self, points, normals, samples, emitters=None, first_sample=0, seeds=None, offset=1e-3, shorten=1e-3,
-                     mask=abi.MASK_ALL, out=None, pick="uniform"):
+                     mask=abi.MASK_ALL, out=None, pick="uniform", tally=None):
         """rb_direct_light: what reaches (m, 3) surface points directly from the lights, by ``samples`` shadow rays per point,
         each aimed at a point drawn on a uniformly picked emitter and walked by rb_occluded among the stages of ``mask`` ->
         abi.RADIANCE[m] (``sum`` over the samples, ``weight``: the valid samples; sum / weight is the direct irradiance over
@@ -676,7 +696,11 @@ class Engine:
         int32 / uint32 tensor with one entry per emitter.  The estimate keeps its mean as long as every emitter that can
         light a point keeps a weight above 0.
         ("grid", grid) or ("grid", grid, tables): rb_direct_light_grid, the pick per grid cell -- ``grid``
-        an abi.PROBE_GRID whose counts count cells, ``tables`` what ``emitter_grid`` returns (None: made for this call)."""
+        an abi.PROBE_GRID whose counts count cells, ``tables`` what ``emitter_grid`` returns (None: made for this call).
+        ``tally`` (with a grid pick): rb_direct_light_grid_tally -- abi.GRID_TALLY[rows * n_emit], or an
+        (rows * n_emit, 2) int32 tensor, to which the call adds the shadow rays it tried and saw per (cell, emitter);
+        ``emitter_grid(tally=...)`` makes tables of it.  The caller zeroes and keeps it.  ``out=False`` with a tally: a
+        training-only call, no sums are made and None comes back."""
         samples, first_sample = _sample_range(samples, first_sample)
         surf = surfel_records(points, normals)
         weights, cells = None, None
@@ -692,7 +716,14 @@ class Engine:
             raise ValueError("pick: a table of weights goes with a table of emitters")
         else:
             weights = pick
-        f = Form(self.query_device, surf, seeds, emitters, out, weights)
+        if tally is not None and cells is None:
+            raise ValueError('tally: it goes with pick=("grid", grid[, tables])')
+        train_only = out is False
+        if train_only and tally is None:
+            raise ValueError("out=False: a call without sums needs a tally")
+        if train_only:
+            out = None
+        f = Form(self.query_device, surf, seeds, emitters, out, weights, tally)
         surf, fp = f.input("points / normals", surf, abi.SURFEL)
         n = len(surf)
         table, tp, n_emit = None, None, 0
@@ -705,7 +736,7 @@ class Engine:
                 table, tp = f.input("emitters", device_new(abi.EMITTER, 1, self.query_device) if f.on_device else np.zeros(1, dtype=abi.EMITTER),
                                     abi.EMITTER)
         seeds, sp = f.optional("seeds", seeds, SEEDS, n)
-        res, op = f.output("out", out, abi.RADIANCE, n)
+        res, op = (None, None) if train_only else f.output("out", out, abi.RADIANCE, n)
         prm = self._light_params(offset, shorten, mask)
         if isinstance(pick, str) and pick == "uniform":
             self._query(f, "rb_direct_light", tp, n_emit, fp, sp, n, prm.ctypes.data, first_sample, samples, op)
@@ -718,6 +749,16 @@ class Engine:
                 if f.on_device and not is_tensor(weights):
                     weights = upload(host_in("pick", weights, CDF)[0].view(np.int32), np.dtype(np.int32), self.query_device)
                 weights, cp = f.input("pick", weights, CDF, rows * n_emit)
+            if tally is not None:
+                kept, kp, back = self._tally_in(f, tally, rows * n_emit)
+                if kp is None:   # no record to add to (no emitter, or an empty array): one that is never touched stands in
+                    kept = device_new(abi.GRID_TALLY, 1, self.query_device) if f.on_device else np.zeros(1, dtype=abi.GRID_TALLY)
+                    kp = kept.data_ptr() if f.on_device else kept.ctypes.data
+                self._query(f, "rb_direct_light_grid_tally", tp, cells.ctypes.data, cp, n_emit, fp, sp, n, prm.ctypes.data, first_sample,
+                            samples, op, kp)
+                if back is not None and back.size:
+                    back[...] = download(kept, abi.GRID_TALLY).reshape(back.shape)
+                return res
             self._query(f, "rb_direct_light_grid", tp, cells.ctypes.data, cp, n_emit, fp, sp, n, prm.ctypes.data, first_sample, samples, op)
             return res
         if weights is not None:
@@ -1143,6 +1184,20 @@ def emitter_grid_cdf(emitters, grid, device=-1):
         raise ValueError("grid: at most 2^26 entries (cells times emitters) are taken")
     tables = np.zeros(rows * len(table), dtype=CDF)
     call("rb_emitter_grid_cdf", tp, len(table), g.ctypes.data, host_ptr(tables))
+    return tables
+
+
+def emitter_grid_learned(emitters, grid, tally, prior=1.0, device=-1):
+    """rb_emitter_grid_learned: ``emitter_grid_cdf`` with the weight times the seen share of an abi.GRID_TALLY[rows * n] and a
+    ``prior`` in (0, 16777216].  ``direct.emitter_grid_cdf(tally=...)`` is its numpy model."""
+    f, call = _engineless(device)
+    table, tp = f.input("emitters", emitters, abi.EMITTER)
+    g, rows = grid_records(grid)
+    if rows * max(len(table), 1) > abi.MAX_GRID_ENTRIES:
+        raise ValueError("grid: at most 2^26 entries (cells times emitters) are taken")
+    kept, kp = f.input("tally", tally, abi.GRID_TALLY, rows * len(table))
+    tables = np.zeros(rows * len(table), dtype=CDF)
+    call("rb_emitter_grid_learned", tp, len(table), g.ctypes.data, kp, float(prior), host_ptr(tables))
     return tables
 
 

@@ -6,7 +6,8 @@
                                  [--denoise [--denoise-iterations N]]
                                  [--camera equirect|ortho|thin-lens [--ortho-width W] [--aperture A --focus-distance F] [--jitter]]
                                  [--probe x,y,z [--probe-normal x,y,z]] [--device-rays]
-                                 [--lightmap W H [--lightmap-mesh i] [--lightmap-flip] [--direct [--pick power | --pick grid NX NY NZ]]]
+                                 [--lightmap W H [--lightmap-mesh i] [--lightmap-flip] [--direct [--pick power | --pick grid NX NY NZ |
+                                                                                          --pick learned NX NY NZ [--learn ROUNDS SAMPLES]]]]
                                  [--probe-grid NX NY NZ] [--lit-by-probes NX NY NZ [--probe-visibility]]
 
 scene file -> scene_io.load_scene (the importer's and the Scene->RenderConfig adapter's rules) ->
@@ -29,7 +30,9 @@ of the same texels (aov.ambient_occlusion_map) as out.lightmap.ao.png, and with 
 spp shadow rays per texel to points on the scene's emitters (bake.lightmap_direct -> Engine.direct_light)
 -- as out.lightmap.direct.png; --pick power picks each ray's emitter in proportion to its emission times its area (section 23);
 --pick grid NX NY NZ picks it from a table per cell of a grid over the bounding box of the emitters and the mesh, weighted by
-power over squared distance to the cell (bake.pick_grid -> Engine.direct_light(pick=("grid", grid)); section 24).
+power over squared distance to the cell (bake.pick_grid -> Engine.direct_light(pick=("grid", grid)); section 24);
+--pick learned NX NY NZ trains such tables first on which emitters the texels of each cell see -- --learn ROUNDS SAMPLES training
+samples per texel, default 2 16, which lie behind the rendered ones and are not rendered (bake.learn_grid; section 25).
 --probe-grid NX NY NZ bakes a grid of irradiance probes
 over the bounding box of the scene's triangles and spheres (probes.grid -> bake.probes: Engine.bake_probes, spp uniform-sphere
 rays per probe, traced and projected onto SH9 on the device) and writes out.probes.npz with `positions`
@@ -68,15 +71,19 @@ ap.add_argument("--lightmap-mesh", type=int, default=None, help="--lightmap for 
 ap.add_argument("--lightmap-flip", action="store_true", help="--lightmap with the triangles' normals negated")
 ap.add_argument("--direct", action="store_true", help="with --lightmap: also the map of the direct light alone, by shadow rays to the scene's emitters, as out.lightmap.direct.png")
 ap.add_argument("--pick", nargs="+", default=["uniform"], metavar="HOW",
-                help="--direct: how a shadow ray picks its emitter: uniform, power (DESIGN.md section 23) or grid NX NY NZ (section 24)")
+                help="--direct: how a shadow ray picks its emitter: uniform, power (DESIGN.md section 23), grid NX NY NZ (section 24) or learned NX NY NZ (section 25)")
+ap.add_argument("--learn", type=int, nargs=2, metavar=("ROUNDS", "SAMPLES"), default=[2, 16],
+                help="--pick learned: training rounds and samples per texel and round (DESIGN.md section 25)")
 ap.add_argument("--probe-grid", type=int, nargs=3, metavar=("NX", "NY", "NZ"), default=None,
                 help="also bake a grid of irradiance probes over the scene's bounding box, as out.probes.npz")
 ap.add_argument("--lit-by-probes", type=int, nargs=3, metavar=("NX", "NY", "NZ"), default=None,
                 help="also light the first hits from a grid of probes baked over the scene's bounding box, as out.probe_lit.png")
 ap.add_argument("--probe-visibility", action="store_true", help="--lit-by-probes with the probes' depth maps and the leak-free blend (DESIGN.md section 20)")
 a = ap.parse_args()
-if a.pick not in (["uniform"], ["power"]) and not (len(a.pick) == 4 and a.pick[0] == "grid" and all(c.isdigit() and int(c) > 0 for c in a.pick[1:])):
-    ap.error("--pick: uniform, power or grid NX NY NZ")
+if a.pick not in (["uniform"], ["power"]) and not (len(a.pick) == 4 and a.pick[0] in ("grid", "learned") and all(c.isdigit() and int(c) > 0 for c in a.pick[1:])):
+    ap.error("--pick: uniform, power, grid NX NY NZ or learned NX NY NZ")
+if a.learn[0] < 0 or a.learn[1] < 1:
+    ap.error("--learn: ROUNDS >= 0 and SAMPLES >= 1")
 aovs = [n for n in a.aov.split(",") if n]
 for n in aovs:
     if n not in aov.NAMES + ("ao",):
@@ -164,11 +171,12 @@ if a.lightmap:
           f"with {eng.last_query_kernel_name()} in {eng.last_query_ms():.3f} ms (surfels {surfels_ms:.3f}, resolve {resolve_ms:.3f}) -> {base}.lightmap{ext}")
     if a.direct:
         pick = a.pick[0]
-        if pick == "grid":
+        if pick in ("grid", "learned"):
             tri = s.bvh_triangles
-            pick = ("grid", bake.pick_grid(eng.scene_emitters(), [int(c) for c in a.pick[1:]],
-                                           points=np.concatenate([tri[k].reshape(-1, 3) for k in ("v0", "v1", "v2")])))
-        picked = " ".join(a.pick)
+            cells = bake.pick_grid(eng.scene_emitters(), [int(c) for c in a.pick[1:]],
+                                   points=np.concatenate([tri[k].reshape(-1, 3) for k in ("v0", "v1", "v2")]))
+            pick = ("grid", cells) if pick == "grid" else ("learned", cells, a.learn[0], a.learn[1])
+        picked = " ".join(a.pick) + (f" after {a.learn[0]} rounds of {a.learn[1]} training samples" if a.pick[0] == "learned" else "")
         direct_map = bake.lightmap_direct(eng, w, h, spp, mesh=a.lightmap_mesh, flip=a.lightmap_flip, pick=pick)
         scene_io.export_png(f"{base}.lightmap.direct{ext}", Frame(w, h, bake.lightmap_texture(direct_map).view(np.uint8)))
         print(f"direct-light map of {len(eng.scene_emitters())} emitters, {spp} shadow rays per texel picked by {picked}, with {eng.last_query_kernel_name()} "
